@@ -12,10 +12,20 @@ full.  The 512 games of a GPU run as four lanes of 128 (separate streams: the tr
 trunks of the others on the same CUs; rlzero_amd.selfplay.plan_lanes); a simulation step of a lane is two launches, trunk -> tree
 step -- the reference's selection rule never reads a prior, so the policy GEMM and the priors of a search's expansions are written
 in one batch per move, inside the timed region.  Games are independent: N GPUs play N x 512 games with no collective in the
-timed region (weak scaling); rank 0 prints ONE JSON line.  `value` is the MEDIAN of --regions (5) timed regions of K steps
-each, every region bracketed by barrier + synchronize.
+timed region (weak scaling); rank 0 prints ONE JSON line.  `value` is the MEDIAN of --regions timed regions of K steps
+each, every region bracketed by barrier + synchronize; `ms_per_step` is that region's milliseconds per step.
 
-On the line (what each number means and how it is priced: DESIGN.md section 5):
+A plain run does only what the headline needs: set up, W + 3 warm-up moves, ONE timed region of K steps (unless --regions says
+otherwise), --dump-outputs DIR if asked, the line.  --full adds everything below (and five regions by default):
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+--dump-outputs DIR writes what the timed path computed in its last step, rank 0's games, one row per game by game id: game_id.npy,
+ply.npy, move.npy (float64 [games]) and pi.npy (float64 [games, actions]: the pi of the move); --game muzero: every environment's
+last obs, action, reward, policy and root_value.  Beyond 64 MB a fixed, seeded sample of the rows (sample.npy).  The warm-up has a
+fixed length and every seed is fixed, so the same arguments give the same arrays.
+
+On the --full line (what each number means and how it is priced: DESIGN.md section 5):
   roofline       the dominant kernel (the network trunk on one lane's leaves): algorithmic flops per launch / launch
                  duration, against the peak of the pipe it runs on
   roofline_tree  the tree step against the HBM roofline (algorithmic bytes of SURVEY.md 8d)
@@ -203,6 +213,72 @@ def time_resident_launches(sp, torch, n_moves=4):
     return {'search_ms': both - bases, 'bases_ms': bases, 'launches': len(pairs), 'stats': stats}
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES_MAX = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """``arrays``: name -> array with one row per game (environment), written as out_dir/<name>.npy in float64; beyond DUMP_BYTES_MAX
+    in all, a fixed, seeded sample of the rows (the same in every run, their indices in sample.npy)."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = 8 * sum(int(np.prod(v.shape[1:])) for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if n * row_bytes > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.RandomState(0).choice(n, DUMP_BYTES_MAX // (row_bytes + 8), replace=False))
+        arrays = dict({k: v[rows] for k, v in arrays.items()}, sample=rows)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(v, dtype=np.float64))
+
+
+def dump_selfplay_outputs(out_dir, sp, device_moves, last_step):
+    """What the last timed step gave a caller of the self-play path, one row per game that made a move in it, by game id: the game's
+    ply, the pi of the move (the reference's expression on the root visits) and the move drawn.  (Slots take their games in an order
+    of the device's choosing: by game id, two runs compare row for row.)"""
+    import numpy as np
+    rows = []   # (game id, ply, move, pi)
+    if device_moves:
+        from rlzero_amd._hip import PLAY_RECORD_WORDS, PLAY_RUNNING
+        from rlzero_amd.selfplay import batch_pi_and_moves, move_uniform
+        for lane in sp.lanes:   # the log row of the lane's last move: one record per slot, read by the host already
+            eng = lane.eng
+            rec = lane.host_np[(eng.play_steps - 1) % eng.play_log.shape[0]]
+            rec = rec[(rec[:, 4] & PLAY_RUNNING) != 0]
+            gids = rec[:, 0].astype(np.uint32).astype(np.int64) | (rec[:, 1].astype(np.int64) << 32)
+            plies, visits = rec[:, 2].astype(np.int64), rec[:, PLAY_RECORD_WORDS:]
+            legal = visits >= 0
+            pis, moves = batch_pi_and_moves(np.where(legal, visits, 0), legal, sp.temperature, move_uniform(sp.seed, gids, plies))
+            rows.extend(zip(gids, plies, moves, pis))
+    else:
+        before = last_step.get('slot_game', sp.slot_game)
+        ended = {t.game_id: t for t in last_step.get('done', [])}
+        for s, gid in enumerate(before):
+            if gid in ended:   # the game ended with this step: its last move is in its trajectory
+                t = ended[gid]
+                rows.append((gid, len(t.moves) - 1, t.moves[-1], t.pis[-1]))
+            elif gid >= 0 and sp.slot_game[s] == gid and sp.slot_moves[s]:
+                rows.append((gid, len(sp.slot_moves[s]) - 1, sp.slot_moves[s][-1], sp.slot_pis[s][-1]))
+    rows.sort(key=lambda r: int(r[0]))
+    write_outputs(out_dir, {'game_id': [r[0] for r in rows], 'ply': [r[1] for r in rows], 'move': [r[2] for r in rows],
+                            'pi': np.array([r[3] for r in rows]).reshape(len(rows), sp.eng.n_actions)})
+
+
+def dump_muzero_outputs(out_dir, sp):
+    """MuZero: every environment's last move -- observation, action, reward, the policy of the root visits, root value."""
+    D, A = sp.net.obs_dim, sp.n_actions
+    if sp.fused_moves:
+        ring, _ = sp.device_history()
+        row = ring[:, (sp._t - 1) % ring.shape[1]]
+        vis = row[:, D + 2:D + 2 + A]
+        fields = {'obs': row[:, :D], 'action': row[:, D], 'reward': row[:, D + 1], 'policy': vis / vis.sum(axis=1, keepdims=True),
+                  'root_value': row[:, D + 2 + A]}
+    else:
+        h = (sp._t - 1) % sp.HIST
+        fields = {'obs': sp._h_obs[h], 'action': sp._h_act[h], 'reward': sp._h_rew[h], 'policy': sp._h_pol[h], 'root_value': sp._h_val[h]}
+    write_outputs(out_dir, fields)
+
+
 # --------------------------------------------------------------------------- CPU baseline
 def cpu_worker(seconds, game, board, n_playout):
     """One process of the CPU baseline: the oracle plays self-play moves of the same configuration in reference
@@ -345,7 +421,7 @@ def child_line(flags, timeout=900):
 def run_fill_config(args):
     """The same engine with 1536 games in flight (the layout plan_lanes picks: with the receptive-field trunk ONE resident lane whose
     launch runs in three rounds of two games per CU; before, two lanes of 768), as a child process -> the fields of its line worth keeping."""
-    rec = child_line(['--games', FILL_GAMES_PER_GPU, '--steps', args.steps, '--warmup', max(args.warmup, 3),
+    rec = child_line(['--full', '--games', FILL_GAMES_PER_GPU, '--steps', args.steps, '--warmup', max(args.warmup, 3),
                       '--regions', 1, '--net-algo', args.net_algo, '--graph', args.graph, '--noise', args.noise, '--deferred', args.deferred,
                       '--no-cpu-baseline', '--no-games-leg', '--no-fill', '--no-configs', '--timeline', 0], 600)
     if rec is None:
@@ -385,7 +461,7 @@ def run_timeline_leg(args):
 def run_config_legs(args):
     out = {}
     for key, flags, cpu_s in CONFIG_LEGS:
-        rec = child_line(flags + ['--cpu-seconds', max(1.0, cpu_s * args.cpu_seconds / 60.0), '--regions', 1, '--no-games-leg',
+        rec = child_line(flags + ['--full', '--cpu-seconds', max(1.0, cpu_s * args.cpu_seconds / 60.0), '--regions', 1, '--no-games-leg',
                                   '--no-fill', '--no-configs', '--timeline', 0] + (['--no-cpu-baseline'] if args.no_cpu_baseline else []), 600)
         if rec is None:
             out[key] = {'error': 'the child process printed no line'}
@@ -579,9 +655,10 @@ def run_muzero(args, rank, world, device, dist, red_device, use_dist=False, cpu_
     gc.collect()
     gc.freeze()
     sims0 = sp.sims_done
-    sp.sim_events = []  # HIP events around every 8th simulation step (one hipGraph replay) of the timed region
-    if sp.fused:
-        sp.search_events = []  # ... or around every fused search launch (all simulations of a move)
+    if args.full:   # (the roofline's samples)
+        sp.sim_events = []  # HIP events around every 8th simulation step (one hipGraph replay) of the timed region
+        if sp.fused:
+            sp.search_events = []  # ... or around every fused search launch (all simulations of a move)
     t0 = time.perf_counter()
     # (fused moves: launches of sp.moves_per_launch moves, records read two launches behind.  The episodes stay alive until the clock
     # has stopped: dropping them -- 10 MB of records per launch, 1.3 GB over 2048 moves -- inside the region cost 57 ms of munmap)
@@ -602,6 +679,8 @@ def run_muzero(args, rank, world, device, dist, red_device, use_dist=False, cpu_
         total = float(c.item())
     sp.tree.check()
     del episodes
+    if rank == 0 and args.dump_outputs:
+        dump_muzero_outputs(args.dump_outputs, sp)
     if rank == 0:
         roofline = None
         events = sp.search_events if sp.fused else sp.sim_events
@@ -684,7 +763,14 @@ def main():
                          'game length)')
     ap.add_argument('--no-fill', '--no-literal-config', dest='no_fill', action='store_true',
                     help='skip the extra N=1 measurement with %d games in flight (child process)' % FILL_GAMES_PER_GPU)
-    ap.add_argument('--regions', type=int, default=5, help='timed regions of K steps each; value = their median')
+    ap.add_argument('--regions', type=int, default=None, help='timed regions of K steps each; value = their median (default: 1, '
+                                                                 'with --full 5)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: CPU baseline, the %d-games fill, the other configurations, the '
+                         'launch trace, kernel timing samples and rooflines, the self-play games/s leg, N > 1: the trajectory '
+                         'gather; five timed regions by default' % FILL_GAMES_PER_GPU)
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write what their last step computed as DIR/<name>.npy (float64; module docstring)')
     ap.add_argument('--score-mode', default='uct_ref', choices=['uct_ref', 'puct'],
                     help="uct_ref: the reference's selection rule (node.py:32-42, 75-88; bit-exact); puct: the opt-in AlphaZero "
                          "rule Q + c P sqrt(N_parent) / (N + 1) (every level scans all children; parity by the oracle's restatement)")
@@ -729,6 +815,11 @@ def main():
                     help='independent batches of games on separate HIP streams (the tree / FC kernels of one lane run beside the '
                          'network trunks of the others); 0 = what rlzero_amd.selfplay.plan_lanes picks for the batch (512 games: 4)')
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
+    if not args.full:   # a plain run: the headline figure alone (module docstring)
+        args.no_cpu_baseline = args.no_fill = args.no_configs = args.no_games_leg = True
+        args.timeline = args.eager_every = 0
     if args.cpu_worker is not None:
         cpu_worker(args.cpu_worker, args.game, args.board, args.playouts)
         return
@@ -897,7 +988,10 @@ def main():
         next_id[0] += world * n
         return ids
 
+    last_step = {}   # the games the latest step finished (and, see timed_step, the slots' games before it)
+
     def account(done):
+        last_step['done'] = done
         finished[0] += len(done)
         first_gen_plies.extend(len(t.moves) for t in done if t.game_id < world * G)
         if (use_dist or args.dump_trajectories) and len(gather_sample) < GATHER_SAMPLE_GAMES:
@@ -928,12 +1022,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # un-timed warm-up: the W moves asked for, and at least ~0.3 s of GPU work in all (the GPU has idled through the CPU
-    # baseline and the child legs: its clocks ramp within the first moves)
-    t_ramp, n_ramp = time.perf_counter(), 0
-    while n_ramp < args.warmup or (time.perf_counter() - t_ramp < 0.3 and n_ramp < args.warmup + 3):
+    # un-timed warm-up: the W moves asked for and three more (the GPU has idled through the set-up -- and with --full the CPU
+    # baseline and the child legs --: its clocks ramp within the first moves).  A fixed count, not a time: the same arguments
+    # reach the same games, so --dump-outputs can be compared run against run
+    n_ramp = args.warmup + 3
+    for _ in range(n_ramp):
         one_step()
-        n_ramp += 1
+
+    def timed_step():
+        if args.dump_outputs and not device_moves:   # (host-driven moves: the slots' games before the step, for dump_selfplay_outputs)
+            last_step['slot_game'] = sp.slot_game.copy()
+        one_step()
     # (the interpreter's housekeeping out of the regions, as in run_muzero: a generation-2 pass over torch's object graph stalls the
     # host for tens of milliseconds)
     import gc
@@ -942,17 +1041,19 @@ def main():
         gc.freeze()
     # --regions timed regions of K steps each, every one bracketed by barrier + synchronize; the MEDIAN region is reported
     regions = []
-    power = PowerSampler()
+    power = PowerSampler() if args.full else None
     for _ in range(max(1, args.regions)):
         fence()   # (device-driven moves: also reads the rows of the moves before the region -- counted before it, not in it)
         sims0, fin0 = sp.sims_done, finished[0]
-        power.start()
+        if power:
+            power.start()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            one_step()
+            timed_step()
         fence()
         dt = time.perf_counter() - t0
-        power.stop()
+        if power:
+            power.stop()
         if use_dist:
             # every rank's own (seconds, simulations, games finished) of the region, on every rank: the line reports MAX time /
             # SUM work (the contract) AND each rank's own rate, so a throttling or straggling GPU shows
@@ -965,9 +1066,11 @@ def main():
         else:
             regions.append((dt, float(sp.sims_done - sims0), float(finished[0] - fin0), [float(sp.sims_done - sims0) / dt]))
     elapsed, total_sims, total_finished, per_rank_rates = sorted(regions, key=lambda r: r[1] / r[0])[len(regions) // 2]
+    if rank == 0 and args.dump_outputs:   # (before anything below plays on)
+        dump_selfplay_outputs(args.dump_outputs, sp, device_moves, last_step)
     # the resident search's kernel by itself: lone launches between HIP events on its own stream, behind the timed regions
     resident_timing = None
-    if rank == 0 and resident_route and device_moves and len(sp.lanes) == 1:
+    if args.full and rank == 0 and resident_route and device_moves and len(sp.lanes) == 1:
         sims_keep, fin_keep = sp.sims_done, finished[0]
         try:
             resident_timing = time_resident_launches(sp, torch)
@@ -994,7 +1097,7 @@ def main():
         sp.eager_every = 0
         sims_sampled = sp.sims_done - sims_keep
         sp.sims_done, finished[0] = sims_keep, fin_keep
-    elif args.graph <= 0:
+    elif args.full and args.graph <= 0:
         sims_sampled = 0
         for ev in evaluators:
             if isinstance(ev, TimedEvaluator):
@@ -1009,7 +1112,7 @@ def main():
     reuse_dropped_timed = int(sum(st.reuse_dropped for st in all_stats))   # kept subtrees over the carry limit (0 = the reference's unbounded update_with_move)
     # the dominant kernel by itself (no other lane on the GPU): its duration on the CUs it is given
     exclusive_ms = None
-    if isinstance(evaluator, TimedEvaluator) and getattr(evaluator.inner, 'hip', None) is not None and rank == 0:
+    if args.full and isinstance(evaluator, TimedEvaluator) and getattr(evaluator.inner, 'hip', None) is not None and rank == 0:
         lane0 = sp.lanes[0]
         torch.cuda.synchronize()
         with torch.cuda.stream(lane0.stream):

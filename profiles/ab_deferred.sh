@@ -1,5 +1,5 @@
 # same box, alternating: the deferred-priors route against the three-launch step (512 games, four lanes; then 2 / 3 lanes, fill, C-legs)
-F="--no-configs --no-cpu-baseline --no-fill --no-games-leg --steps 10 --warmup 3"
+F="--full --no-configs --no-cpu-baseline --no-fill --no-games-leg --steps 10 --warmup 3"
 show() { python -c "
 import json,sys
 d=json.loads(open('gpurun_out/$1.json').read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # M sims/s, ms per move, us per trunk launch; default workload and 512 games
 set -e
 mkdir -p gpurun_out
-F="--no-cpu-baseline --no-literal-config --no-configs --no-games-leg --steps 8 --warmup 3 ${EXTRA}"
+F="--full --no-cpu-baseline --no-literal-config --no-configs --no-games-leg --steps 8 --warmup 3 ${EXTRA}"
 for rep in 1 2; do
 for lib in ref new; do
   for games in ${GAMES:-512 1536}; do

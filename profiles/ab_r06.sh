@@ -1,7 +1,7 @@
 #!/bin/bash
 # A / B of library variants on ONE box, alternating: bash profiles/ab_r06.sh <variant.so> [<variant.so> ...]   (the first entry "base" = the in-tree library)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 3 --timeline 0 --steps 8 --warmup 3"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 3 --timeline 0 --steps 8 --warmup 3"
 for rep in 1 2; do
   for lib in base "$@"; do
     if [ "$lib" = base ]; then unset RZ_HIP_LIBRARY; else export RZ_HIP_LIBRARY="$ROOT/$lib"; fi

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=/tmp/rz_r06i
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0 --graph 0 --steps 1 --warmup 1"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0 --graph 0 --steps 1 --warmup 1"
 echo "# 512 games x 800 simulations per launch of k_delta_res (409 600 simulations; 2048 waves): per launch"
 for c in SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_MFMA SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY; do
     rocprofv3 --pmc $c --output-format csv -d "$OUT/$c" -o p -- $B > /dev/null 2> "$OUT/$c.err"

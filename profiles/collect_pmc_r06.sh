@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=/tmp/rz_r06p
 rm -rf "$OUT"; mkdir -p "$OUT" "$ROOT/gpurun_out/r06"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0"
 pmc() {
     tag=$1; shift
     for c in FETCH_SIZE WRITE_SIZE; do

@@ -8,10 +8,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r02
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-literal-config --no-configs"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-literal-config --no-configs"
 
 # 1. the default line exactly as the driver runs it (CPU baseline, literal configs[3] share, C1 / C2 / C3 / C5 legs)
-python3 "$ROOT/bench.py" > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 "$ROOT/bench.py" --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "default line done"
 
 # 2. per-kernel times: the default command under rocprofv3 (hipGraph replays) and eager runs (true durations)

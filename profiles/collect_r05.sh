@@ -9,11 +9,11 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=/tmp/rz_r05
 rm -rf "$OUT"; mkdir -p "$OUT" "$ROOT/gpurun_out/r05"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0"
 
 # 1. the default line exactly as the driver runs it
 if [ "${1:-}" != quick ]; then
-python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "default line done"
 fi
 

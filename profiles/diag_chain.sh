@@ -1,5 +1,5 @@
 set -e
-F="--no-configs --no-cpu-baseline --no-fill --no-games-leg --steps 10 --warmup 3"
+F="--full --no-configs --no-cpu-baseline --no-fill --no-games-leg --steps 10 --warmup 3"
 python bench.py $F > gpurun_out/d_base.json 2>/dev/null
 RZ_DIAG_SKIP_FC=1 python bench.py $F > gpurun_out/d_skipfc.json 2>/dev/null
 python bench.py $F --noise 0 > gpurun_out/d_nonoise.json 2>/dev/null

@@ -2,7 +2,7 @@
 # The deferred policy GEMM (k_heads_split over the store) after pairing its workgroups per XCD: duration and HBM reads per launch
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=/tmp/rz_gemm; rm -rf $OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0 --graph 0"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --timeline 0 --graph 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $B --steps 2 > /dev/null 2>&1
 python3 - <<PY
 import csv, glob

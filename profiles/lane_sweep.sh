@@ -1,7 +1,7 @@
 #!/bin/bash
 # Lanes of games x hardware queues x batch size on one MI355X (what profiles/r03/lane_sweeps.txt holds and selfplay.plan_lanes is
 # built on).  Run from the repository root:   bash profiles/lane_sweep.sh > gpurun_out/lane_sweeps.txt
-F="--no-cpu-baseline --no-fill --no-configs --no-games-leg --steps 6 --warmup 3 --regions 1"
+F="--full --no-cpu-baseline --no-fill --no-configs --no-games-leg --steps 6 --warmup 3 --regions 1"
 run() {  # queues, bench flags
     q=$1; shift
     GPU_MAX_HW_QUEUES=$q python bench.py $F "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('queues $q $*:', round(d['value']/1e6, 3), d['ms_per_step'], (d.get('roofline') or {}).get('avg_launch_ms'))"

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=/tmp/rz_r03_mfma
 rm -rf "$OUT"; mkdir -p "$OUT" "$ROOT/gpurun_out/r03"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --steps 1 --warmup 0 --playouts 40 --graph 0 --lanes 1 --games 768"
+ARGS="--full --no-cpu-baseline --no-games-leg --no-fill --no-configs --regions 1 --steps 1 --warmup 0 --playouts 40 --graph 0 --lanes 1 --games 768"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
     --output-format csv -d "$OUT/pmc_mfma" -o p -- python3 "$ROOT/bench.py" $ARGS > /dev/null 2> "$OUT/pmc_mfma.err"
 rocprofv3 --kernel-trace --output-format csv -d "$OUT/pmc_mfma_trace" -o t -- python3 "$ROOT/bench.py" $ARGS > /dev/null 2>> "$OUT/pmc_mfma.err"

@@ -14,8 +14,14 @@ if REPO not in sys.path:
 GOLDEN = os.path.join(HERE, 'golden')
 
 # rlzero_amd claims 8 hardware queues on import (four lanes of games: rlzero_amd/__init__.py); the collection hook below asks
-# torch for the GPU -- which starts the runtime -- before any test imports the package, so the variable is set here
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
+# torch for the GPU -- which starts the runtime -- before any test imports the package, so the variable is set here.  The suite
+# tests that layout: a smaller value from the environment (a host may set HIP's default of 4 for every process) is raised to 8
+try:
+    _queues = int(os.environ.get('GPU_MAX_HW_QUEUES', '0'))
+except ValueError:
+    _queues = 0
+if _queues < 8:
+    os.environ['GPU_MAX_HW_QUEUES'] = '8'
 
 
 def pytest_configure(config):

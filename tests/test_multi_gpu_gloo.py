@@ -163,7 +163,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         env.pop(k, None)
     dump2, dump1 = str(tmp_path / 'two.json'), str(tmp_path / 'one.json')
     common = ['--steps', '2', '--warmup', '1', '--board', '9', '--playouts', '40', '--no-cpu-baseline',
-              '--no-literal-config', '--no-configs']
+              '--no-literal-config', '--no-configs', '--full']   # (--full: the games leg and the trajectory gather)
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--games', '32', '--dump-trajectories',
            dump2] + common
     out = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -216,7 +216,7 @@ def test_bench_collectives_on_rccl_with_one_rank():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2',
            '--warmup', '1', '--board', '9', '--playouts', '40', '--games', '32', '--no-cpu-baseline',
-           '--no-literal-config', '--no-configs']
+           '--no-literal-config', '--no-configs', '--full']
     out = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     rec = json.loads([ln for ln in out.stdout.decode().splitlines() if ln.startswith('{')][-1])
@@ -521,7 +521,7 @@ def test_bench_four_ranks_on_one_gpu():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '4', '--games', '64', '--steps', '2', '--warmup', '1', '--board', '9',
-           '--playouts', '40', '--regions', '1', '--no-cpu-baseline', '--no-literal-config', '--no-configs']
+           '--playouts', '40', '--regions', '1', '--no-cpu-baseline', '--no-literal-config', '--no-configs', '--full']
     out = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     rec = json.loads([ln for ln in out.stdout.decode().splitlines() if ln.startswith('{')][-1])
