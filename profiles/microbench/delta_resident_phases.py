@@ -13,7 +13,7 @@ import numpy as np, torch
 from rlzero_amd.engine import HipNetEvaluator, MCTSEngine
 from rlzero_amd.games.gomoku.policy_value_net import PolicyValueNet
 lib = H.load()
-NAMES = [(0, 'leaf + changed cells'), (1, 'distances, ballots'), (2, 'bar'), (3, 'maps, base records'), (4, 'bar'), (5, 'conv1'), (6, 'bar'), (7, 'conv2'),
+NAMES = [(0, 'leaf + changed cells'), (1, 'distances, requests, ranks'), (3, 'maps, base records'), (4, 'bar'), (5, 'conv1'), (6, 'bar'), (7, 'conv2'),
          (9, 'bar + conv3 + heads'), (10, 'bar'), (11, 'features'), (12, 'bar'), (16, 'value layer'), (17, 'expand + backup'), (18, 'selection')]
 sizes = [int(a) for a in sys.argv[1:]] or [1, 256, 512]
 for games in sizes:

@@ -25,6 +25,9 @@
 // base that is not a subset of the leaf) is evaluated by the same code WITHOUT a base, in four passes over the board's quadrants
 // (each pass: conv3 on <= 8 x 8 cells, conv2 on the 9 x 9 and conv1 on the 10 x 10 around them) -- no second kernel, no host decision.
 // mode 1 builds the bases that way and writes the cache.
+// (the prologue of a pass has ONE barrier: every wave ballots the membership of all four 64-cell blocks, so ranks and totals are in
+// its registers, and a thread requests the base records it holds as soon as it knows it holds them -- one fetch, stored in the same
+// phase; profiles/r07/ab_prologue.txt)
 // (issue priorities of the resident search's phases, s_setprio: its serial tree phase -- one wave, ~20 k cycles a simulation -- ahead of
 // the OTHER game's trunk waves on the same SIMDs: +2.5 % on the whole line, profiles/r06/ab_prio.txt; PRO: the trunk's prologue likewise)
 #ifndef RZ_DELTA_TREE_PRIO
@@ -52,8 +55,8 @@ constexpr int kShareFloats = kT3 * 4 * 96;      // the waves' shares of the head
 constexpr int kHeadW = 128 * 6 * 4 + 128 * 4 + 32;   // the 1 x 1 head convolutions' weights [128][6], conv3's biases [128], the head biases [6 + 2], staged once
 // (the planes: the hi pieces only -- the lo pieces of 0 / 1 planes are zero and conv1 skips their products)
 constexpr int kOffC1 = sp::kInPieceBytes, kOffC2 = kOffC1 + kC1Slots * P1, kOffZero = kOffC2 + kC2Slots * P2, kOffHead = kOffZero + P2,
-              kOffMap1 = kOffHead + kHeadW, kOffMap2 = kOffMap1 + kGrid * 4, kOffList = kOffMap2 + kGrid * 4, kOffCnt = kOffList + 3 * 128 * 2,
-              kLdsBytes = kOffCnt + 5 * 4 * 4;
+              kOffMap1 = kOffHead + kHeadW, kOffMap2 = kOffMap1 + kGrid * 4, kOffList = kOffMap2 + kGrid * 4,
+              kLdsBytes = kOffList + 3 * 128 * 2;
 static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's records (dead behind conv2)");
 static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + 512) <= 160 * 1024, "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
@@ -340,13 +343,37 @@ __device__ __forceinline__ void init_maps(char *lds, int tid) {
     if (tid < 3 * 128 / 2) reinterpret_cast<uint32_t *>(lds + kOffList)[tid] = 19u | (19u << 16);
 }
 
+// Chebyshev distance of cell (cy, cx) to the changed cells (pass -1) / to quadrant `pass` of the board
+__device__ __forceinline__ int cell_dist(int cy, int cx, int pass, const int (&dys)[kMaxD], const int (&dxs)[kMaxD], int BH, int BW) {
+    int dist = 1000;
+    if (pass < 0) {
+#pragma unroll
+        for (int i = 0; i < kMaxD; ++i) {
+            const int ady = cy > dys[i] ? cy - dys[i] : dys[i] - cy, adx = cx > dxs[i] ? cx - dxs[i] : dxs[i] - cx;
+            const int d = ady > adx ? ady : adx;
+            dist = d < dist ? d : dist;
+        }
+    } else {
+        const int y0 = 8 * (pass >> 1), x0 = 8 * (pass & 1);
+        const int y1 = (y0 + 8 < BH ? y0 + 8 : BH) - 1, x1 = (x0 + 8 < BW ? x0 + 8 : BW) - 1;   // (inclusive)
+        const int ddy = cy < y0 ? y0 - cy : (cy > y1 ? cy - y1 : 0), ddx = cx < x0 ? x0 - cx : (cx > x1 ? cx - x1 : 0);
+        dist = ddy > ddx ? ddy : ddx;
+    }
+    return dist;
+}
+
+// 16 bytes of a base's records (offset >= kBaseBytes: zeros, no memory access -- the buffer's range check)
+constexpr int kOutside = 1 << 30;
+__device__ __forceinline__ f32x4 load_rec(__amdgpu_buffer_rsrc_t rsrc, int off) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+}
+
 // The passes of one leaf: -1 = against the base (use_delta), 0 .. 3 = the board's quadrants without one.  -> tiles computed: conv3 | conv2 << 16.
 __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &da, char *lds, int tid0, int wave, const Leaf &leaf, const Layers &ly,
                                             f32x4 headv, bool &use_delta, Prof &prof) {
     char *in0 = lds, *c1 = lds + kOffC1, *c2 = lds + kOffC2, *zrec = lds + kOffZero, *headw = lds + kOffHead;
     uint32_t *map1 = reinterpret_cast<uint32_t *>(lds + kOffMap1), *map2 = reinterpret_cast<uint32_t *>(lds + kOffMap2);
     uint16_t *list1 = reinterpret_cast<uint16_t *>(lds + kOffList), *list2 = list1 + 128, *list3 = list2 + 128;
-    int *cnt = reinterpret_cast<int *>(lds + kOffCnt);   // [5 sets][4 waves]
     float *shares = reinterpret_cast<float *>(c1);
     const int mode = da.mode, BH = nd.BH, BW = nd.BW, S = nd.S;
     const float k1 = ly.k1, k2 = ly.k2, k3 = ly.k3, act1 = ly.act1, act2 = ly.act2, act3 = ly.act3;
@@ -373,28 +400,32 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         const int mypos = is_cell ? (cy + 1) * kRowW + cx + 1 : 0;
         if (RZ_DELTA_PRO_PRIO) __builtin_amdgcn_s_setprio(RZ_DELTA_PRO_PRIO);
         // ---- the distance of this thread's cell to the changed cells (delta) / to the pass's quadrant
-        int dist = 1000;
-        if (pass < 0) {
-#pragma unroll
-            for (int i = 0; i < kMaxD; ++i) {
-                const int ady = cy > dys[i] ? cy - dys[i] : dys[i] - cy, adx = cx > dxs[i] ? cx - dxs[i] : dxs[i] - cx;
-                const int d = ady > adx ? ady : adx;
-                dist = d < dist ? d : dist;
-            }
-        } else {
-            const int y0 = 8 * (pass >> 1), x0 = 8 * (pass & 1);
-            const int y1 = (y0 + 8 < BH ? y0 + 8 : BH) - 1, x1 = (x0 + 8 < BW ? x0 + 8 : BW) - 1;   // (inclusive)
-            const int ddy = cy < y0 ? y0 - cy : (cy > y1 ? cy - y1 : 0), ddx = cx < x0 ? x0 - cx : (cx > x1 ? cx - x1 : 0);
-            dist = ddy > ddx ? ddy : ddx;
-        }
+        const int dist = cell_dist(cy, cx, pass, dys, dxs, BH, BW);
         // sets: 0 = conv1 computes, 1 = conv2 computes, 2 = conv3 computes, 3 = conv1 records held, 4 = conv2 records held
-        const int th0 = pass < 0 ? 1 : 2, th1 = pass < 0 ? 2 : 1, th2 = pass < 0 ? 3 : 0, th3 = pass < 0 ? 3 : 2, th4 = pass < 0 ? 4 : 1;
-        const bool f[5] = {is_cell && dist <= th0, is_cell && dist <= th1, is_cell && dist <= th2, is_cell && dist <= th3, is_cell && dist <= th4};
-        // the records conv2 / conv3 read but this leaf does not recompute come from the base: requested now, stored behind the barrier
-        // (their places are ranks over the whole workgroup)
+        const int th[5] = {pass < 0 ? 1 : 2, pass < 0 ? 2 : 1, pass < 0 ? 3 : 0, pass < 0 ? 3 : 2, pass < 0 ? 4 : 1};
+        bool f[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) f[k] = is_cell && dist <= th[k];
+        // the records conv2 / conv3 read but this leaf does not recompute come from the base: requested NOW, straight into the
+        // registers they are stored from (no barrier lies between).  Every load is issued by every thread --
+        // a load under a branch makes hipcc wait for every outstanding load first --; a thread that holds no such record reads
+        // past the end of a buffer resource instead, which returns zeros without touching memory.
         const bool g1 = pass < 0 && f[3] && !f[0], g2 = pass < 0 && f[4] && !f[1];
-        // (their lines are TOUCHED now -- one dword of each 128-byte line, so that the copies behind the barrier find them in L2; the
-        // copies themselves as registers across the barrier cost 60-110 spilled registers, however the loads were placed)
+        const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, kBaseBytes, 0x00020000);
+        f32x4 r1[8], r2[16];
+        {
+            const int o1 = g1 ? tid * 128 : kOutside, o2 = g2 ? (int)kBaseC2 + tid * 256 : kOutside;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) r1[i] = load_rec(b_rsrc, o1 + 16 * i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) r2[i] = load_rec(b_rsrc, o2 + 16 * i);
+        }
+        float bv[6];   // ... and, behind them (the copies' waits do not include these), the features of a cell outside conv3's window
+        {
+            const int ov = pass < 0 && is_cell && !f[2] ? (int)kBaseV + tid * 4 : kOutside;
+#pragma unroll
+            for (int o = 0; o < 6; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
+        }
         // (conv1's weights and the biases: requested per pass, so that nothing of them is live across conv3)
         sp::f16x8 a1[3][2];
         f32x4 bias1[4];
@@ -407,43 +438,38 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
             for (int gg = 0; gg < 4; ++gg) bias1[gg] = *reinterpret_cast<const f32x4 *>(nd.b1 + 8 * gg + 4 * (lane >> 5));
         }
         f32x4 bias2 = *reinterpret_cast<const f32x4 *>(nd.b2 + 16 * wave + 4 * g);
-        // (unconditional loads -- every thread's number is a valid index of the base's arrays: a load under a branch makes hipcc wait
-        // for every outstanding load first)
-        const float touch = *reinterpret_cast<const float *>(base + (size_t)tid * 128) + *reinterpret_cast<const float *>(base + kBaseC2 + (size_t)tid * 256) +
-                            *reinterpret_cast<const float *>(base + kBaseC2 + (size_t)tid * 256 + 128);
-        float bv[6];   // ... and the features of a cell outside conv3's window
+        // ranks and totals without a barrier: every wave evaluates the membership of all four 64-cell blocks (its own block's ballots
+        // give the ranks inside the wave, the blocks before it the offsets); the same values in every wave, so the budget test is uniform
+        int rank[5], tot[5];
+        {
+            int before[5] = {0, 0, 0, 0, 0}, all[5] = {0, 0, 0, 0, 0};
+            unsigned long long own[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-        for (int o = 0; o < 6; ++o) bv[o] = reinterpret_cast<const float *>(base + kBaseV)[o * kCells + tid];
-        int rank[5];
+            for (int b = 0; b < 4; ++b) {
+                const int cell = 64 * b + lane, by = (cell * da.bw_rcp) >> 16, bx = cell - by * BW;
+                const int d = cell_dist(by, bx, pass, dys, dxs, BH, BW);
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const unsigned long long b = __ballot(f[k]);
-            rank[k] = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-            if (lane == 0) cnt[k * 4 + wave] = __popcll(b);
+                for (int k = 0; k < 5; ++k) {
+                    const unsigned long long m = __ballot(cell < S && d <= th[k]);
+                    const int c = __popcll(m);
+                    all[k] += c;
+                    before[k] += b < wave ? c : 0;
+                    own[k] = b == wave ? m : own[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                rank[k] = before[k] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(own[k] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)own[k], 0u));
+                tot[k] = all[k];
+            }
+        }
+        NET_TICK(1);   // distances, requests, ranks
+        if (pass < 0 && (tot[0] > 32 * kT1 || tot[1] > 16 * kT2 || tot[2] > 16 * kT3 || tot[3] > kC1Slots || tot[4] > kC2Slots)) {
+            use_delta = false;   // (uniform) the windows exceed the budget: the four passes without a base (nothing is written yet)
+            continue;
         }
         // (maps and lists: every map entry is the zero record and every list entry a valid position when a pass begins -- set once per
         // launch, init_maps; a pass puts back what it changed, and a lane past a list's count may read any position: its column is dropped)
-        NET_TICK(1);   // distances, requests, ballots, map / list defaults
-        __syncthreads();
-        NET_TICK(2);
-        int tot[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            int before = 0, all = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int c = cnt[k * 4 + w];
-                before += w < wave ? c : 0;
-                all += c;
-            }
-            rank[k] += before;
-            tot[k] = all;
-        }
-        if (pass < 0 && (tot[0] > 32 * kT1 || tot[1] > 16 * kT2 || tot[2] > 16 * kT3 || tot[3] > kC1Slots || tot[4] > kC2Slots)) {
-            use_delta = false;   // (uniform) the windows exceed the budget: the four passes without a base
-            __syncthreads();     // (cnt is rewritten)
-            continue;
-        }
         uint32_t rec1 = 0, rec2 = 0;
         if (f[3]) {
             rec1 = lds_addr(c1 + rank[3] * P1);
@@ -458,20 +484,11 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         if (f[2]) list3[rank[2]] = (uint16_t)mypos;
         if (pass <= 0 && is_cell) *reinterpret_cast<f16x4 *>(in0 + ((cy + 1) * sp::kInCols + (cx + 1)) * 8) = cell_planes;
         if (pass <= 0 && store_head && tid < 226) reinterpret_cast<f32x4 *>(headw)[tid] = headv;
-        asm volatile("" ::"v"(touch));
         if (g1) {
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(base + (size_t)tid * 128);
-            f32x4 r1[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r1[i] = src[i];
 #pragma unroll
             for (int i = 0; i < 8; ++i) *(lds_v4)(uintptr_t)(rec1 + 16 * i) = r1[i];
         }
         if (g2) {
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(base + kBaseC2 + (size_t)tid * 256);
-            f32x4 r2[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) r2[i] = src[i];
 #pragma unroll
             for (int i = 0; i < 16; ++i) *(lds_v4)(uintptr_t)(rec2 + 16 * i) = r2[i];
         }
@@ -484,7 +501,7 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
 #pragma unroll
                 for (int p = 0; p < 2; ++p) a2[tap][0][p] = sp::load_w(w_rsrc, lane * 16, (tap * 2 + p) * 1024);
         }
-        NET_TICK(3);   // ranks, maps, lists, planes, the base's records
+        NET_TICK(3);   // maps, lists, planes, the base's records (their arrival)
         __syncthreads();
         NET_TICK(4);
 
@@ -767,6 +784,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     }
     if (mode == 0 && is_active == 0) return;   // (uniform; before any barrier; behind the stores above so that the flag's load is
                                                // one of the batch, not a round trip of its own at the top)
+    __syncthreads();   // the zeroed halo and the default maps before the first pass writes its cells into them
     NET_TICK(0);   // requests, scalars, header, planes, zeroing
     const int n_tiles = delta_passes(nd, da, lds, tid0, wave, leaf, ly, headv, use_delta, prof);
     const int n_conv3_tiles = n_tiles & 0xffff;
