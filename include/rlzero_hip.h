@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 26
+#define RZ_ABI_VERSION 27
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -310,6 +310,11 @@ int rz_root_visits(rz_engine *e, int32_t *d_visits, void *stream);
 int rz_root_wsum(rz_engine *e, double *d_w, void *stream);
 int rz_root_priors(rz_engine *e, float *d_p, void *stream);
 int rz_root_stats(rz_engine *e, int32_t *d_n, double *d_w, void *stream);
+/* The values resignation looks at, one wave per game: d_out [n_games][2] fp64 = {v_root, q_best}, v_root = -W(root) / N(root) (the
+ * root holds values as seen by the player who moved into it: the value for the player to move), q_best = max W(c) / N(c) over
+ * the root's children with N > 0.  NaN where N(root) == 0 / no child is visited.  Separately rounded IEEE divisions: the bits
+ * numpy gives for the same W and N. */
+int rz_root_values(rz_engine *e, double *d_out, void *stream);
 
 /* Tree reuse: AlphaZeroMCTS.update_with_move (alphazero_mcts.py:96-103).  d_moves[g] >= 0:
  * the subtree of that root child becomes the tree (statistics kept); -1: fresh tree
@@ -342,8 +347,18 @@ int rz_step_games(rz_engine *e, const int32_t *d_moves, int32_t *d_winner, uint8
  * The log: int32 [ring_steps][n_games][RZ_PLAY_RECORD_WORDS + A]; the record of move step s (counted per engine from
  * rz_play_attach) and slot g is row s % ring_steps.  Words: [0..1] game id (int64), [2] ply before the move, [3] the move (action)
  * or -1, [4] RZ_PLAY_* flags | (winner + 1) << 16, [5] N(root), [6] float bits of the draw's distance to the nearer interval edge
- * (relative), [7] reserved; then per action the visit count of the root child, -1 for an illegal action.  The host must read a
- * row before ring_steps more moves overwrite it.
+ * (relative), [7] the resignation statistic (below; 0 while resignation is off); then per action the visit count of the root
+ * child, -1 for an illegal action.  The host must read a row before ring_steps more moves overwrite it.
+ *
+ * Resignation (AlphaGo Zero's rule; an opt-in extension -- the reference plays every game to its end -- off after every
+ * rz_play_attach).  rz_play_set_resign(threshold, disabled_frac) turns it on: for every RUNNING slot that has just searched,
+ * k_play_draw forms v_root = -W(root) / N(root) and q_best = max W(c) / N(c) over the root's children with N > 0 (the values of
+ * rz_root_values) and logs s = max(v_root, q_best) (NaN when either is) as float bits in word [7].  A game whose uniform
+ * u(seed, game id) -- splitmix64 keyed with a salt of its own (rlzero_amd/selfplay.py: resign_uniform, the same bits) -- is below
+ * disabled_frac is a calibration game: it never resigns, its records carry RZ_PLAY_NO_RESIGN, and RZ_PLAY_WOULD_RESIGN where the
+ * rule would have fired.  In every other game the mover resigns when v_root < threshold and q_best < threshold (NaN never
+ * fires): no draw, move -1, flags RUNNING | SEARCHED | ENDED | RESIGNED, winner 1 - ply % 2 (player 0 moves first), and
+ * rz_play_apply ends the game as it ends a finished one (fresh tree, slot idle, refill) without a game step.
  *
  * Slots refill themselves: a slot whose game has ended (or that is idle) takes the next entry of a queue of game ids shared by
  * the engines (lanes) of a GPU -- d_queue_ids int64 [..], d_queue_ctl int32 [2] = {head, entries valid}; the device advances
@@ -355,7 +370,10 @@ enum {
     RZ_PLAY_STALLED = 2,   /* no move drawn (u too close to an interval edge): waiting for rz_play_resolve */
     RZ_PLAY_RESOLVED = 4,  /* the move came from rz_play_resolve */
     RZ_PLAY_ENDED = 8,     /* the game ended with this move; winner + 1 in bits 16.. (0: tie) */
-    RZ_PLAY_SEARCHED = 16  /* the slot took part in the search before this move step (n_playout simulations) */
+    RZ_PLAY_SEARCHED = 16, /* the slot took part in the search before this move step (n_playout simulations) */
+    RZ_PLAY_RESIGNED = 32, /* the mover resigned (move -1, with RZ_PLAY_ENDED and the winner) */
+    RZ_PLAY_NO_RESIGN = 64,     /* a calibration game: resignation disabled (every searched record of it while the rule is on) */
+    RZ_PLAY_WOULD_RESIGN = 128  /* a calibration game's record where the rule would have fired */
 };
 typedef struct rz_play_config {
     uint64_t seed;         /* move uniforms keyed (seed, game id, ply), Dirichlet streams keyed (seed, game id) */
@@ -379,6 +397,11 @@ int rz_play_draw(rz_engine *e, void *stream);
  * games and the refill of idle slots (rz_play_apply without a draw before it only refills: how a run starts).  A
  * rz_deferred_flush between the two calls leaves the restart of the pending-priors counters to this launch. */
 int rz_play_apply(rz_engine *e, void *stream);
+/* The resignation rule (above), enqueued on `stream` as a write into a small device buffer that k_play_draw reads -- not a kernel
+ * argument: a captured move graph takes a new threshold without a new capture.  threshold NaN: off again (word [7] 0, no resign
+ * flags).  disabled_frac in [0, 1].  Valid after rz_play_attach; a graph captured before the FIRST call since rz_play_attach keeps
+ * the resignation-free draw (capture again). */
+int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, void *stream);
 /* The host's decision for a stalled slot (one tiny launch); taken by the next rz_play_draw. */
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream);
 /* Drop every game: all slots idle with fresh trees (a run that stops early). */

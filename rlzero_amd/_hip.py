@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -81,6 +81,7 @@ class RzPlayConfig(Structure):
 
 PLAY_RECORD_WORDS = 8
 PLAY_RUNNING, PLAY_STALLED, PLAY_RESOLVED, PLAY_ENDED, PLAY_SEARCHED = 1, 2, 4, 8, 16
+PLAY_RESIGNED, PLAY_NO_RESIGN, PLAY_WOULD_RESIGN = 32, 64, 128   # resignation (rz_play_set_resign, ABI 27)
 
 
 class HipError(RuntimeError):
@@ -128,11 +129,13 @@ _SIGNATURES = {
     'rz_root_wsum': (c_int, [P, P, P]),
     'rz_root_priors': (c_int, [P, P, P]),
     'rz_root_stats': (c_int, [P, P, P, P]),
+    'rz_root_values': (c_int, [P, P, P]),
     'rz_advance_roots': (c_int, [P, P, P]),
     'rz_step_games': (c_int, [P, P, P, P, P]),
     'rz_play_attach': (c_int, [P, POINTER(RzPlayConfig)]),
     'rz_play_draw': (c_int, [P, P]),
     'rz_play_apply': (c_int, [P, P]),
+    'rz_play_set_resign': (c_int, [P, c_double, c_double, P]),
     'rz_play_resolve': (c_int, [P, c_int32, c_int32, P]),
     'rz_play_stop': (c_int, [P, P]),
     'rz_play_state': (c_int, [P, P, P, P, POINTER(c_int64)]),

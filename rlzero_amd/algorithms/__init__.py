@@ -8,6 +8,8 @@ name BASELINE.json uses, with the lock-step counterpart of ``policy_evaluate``'s
 (``rlzero_amd.evaluate``).
 """
 from ..evaluate import BatchedEvaluation, DuelResult
-from ..selfplay import (BatchedSelfPlay, Trajectory, broadcast_weights, gather_trajectories, shard_game_ids)
+from ..selfplay import (BatchedSelfPlay, Trajectory, broadcast_weights, calibrate_resign_threshold, gather_trajectories,
+                        shard_game_ids)
 
-__all__ = ['BatchedSelfPlay', 'BatchedEvaluation', 'DuelResult', 'Trajectory', 'gather_trajectories', 'shard_game_ids', 'broadcast_weights']
+__all__ = ['BatchedSelfPlay', 'BatchedEvaluation', 'DuelResult', 'Trajectory', 'gather_trajectories', 'shard_game_ids', 'broadcast_weights',
+           'calibrate_resign_threshold']

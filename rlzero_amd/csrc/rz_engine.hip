@@ -857,6 +857,26 @@ __global__ void k_root_stats(Dev E, int32_t *n, double *w) {
     w[g] = rec_w(R[1]);
 }
 
+// {v_root, q_best} per game (rz_root_values): -W / N of the root, max W / N over the root's children with N > 0; NaN where undefined
+__global__ __launch_bounds__(kWave) void k_root_values(Dev E, double *out) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int4 *R = arena_records(E, g, E.cur_arena[g]);
+    const int4 lo = R[0];
+    const int fc = lo.y;
+    const int nv = rec_k(lo) > 0 ? lo.z : 0;
+    double qb = -INFINITY;
+    for (int r = lane; r < nv; r += kWave) {   // (visited child records: fc .. fc + nv, in rank order; the maximum needs no order)
+        const int n = R[2 * (fc + r)].x;
+        if (n > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)n);
+    }
+    for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
+    if (lane == 0) {
+        out[2 * (long long)g] = lo.x > 0 ? -(rec_w(R[1]) / (double)lo.x) : NAN;
+        out[2 * (long long)g + 1] = qb > -INFINITY ? qb : NAN;
+    }
+}
+
 // ------------------------------------------------------------------ tree reuse
 __device__ __forceinline__ void fresh_root(const Dev &E, int g, int arena, int lane) {
     if (lane == 0) {
@@ -1112,14 +1132,23 @@ struct Play {
     int ring, words;
     uint64_t seed;
     double inv_t, margin;
+    double *resign;            // [2] {threshold, disabled_frac} (rz_play_set_resign; NaN threshold: off)
+    int resign_on;             // rz_play_set_resign called since rz_play_attach: k_play_draw reads `resign` (else never)
 };
 enum { kPlayIdle = 0, kPlayRunning = 1, kPlayStalled = 2 };
+constexpr int kStepResign = -3;   // Play::stepm of a slot whose mover resigned: k_play_apply ends the game without a step
 
 // rlzero_amd/selfplay.py: move_uniform(seed, game id, ply) -- 53 high bits of a splitmix64 chain: the same bits
 __device__ __forceinline__ double play_uniform(uint64_t seed, uint64_t game, uint64_t ply) {
     uint64_t x = mix64(seed);
     x = mix64(x ^ game);
     x = mix64(x ^ ply);
+    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// rlzero_amd/selfplay.py: resign_uniform(seed, game id) -- a game has resignation disabled (calibration) when it is below disabled_frac
+__device__ __forceinline__ double resign_uniform(uint64_t seed, uint64_t game) {
+    const uint64_t x = mix64(mix64(seed ^ 0x72657369676E0000ull) ^ game);
     return (double)(x >> 11) * (1.0 / 9007199254740992.0);
 }
 
@@ -1158,6 +1187,10 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     bool legal[kWords];
     double x[kWords];
     double mx = -INFINITY;
+    // resignation (rz_play_set_resign): read only once it has been configured -- the rule-free path has no extra memory traffic
+    const double thr = Y.resign_on ? Y.resign[0] : NAN;
+    const bool rs = !isnan(thr) && state == kPlayRunning;
+    double qb = -INFINITY;   // max W / N over the visited children (rz_root_values)
 #pragma unroll
     for (int j = 0; j < kWords; ++j) {
         const int r = lane_action_rank(E, occ, L, j, lane, before);
@@ -1167,6 +1200,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         if (a < E.A) rec[RZ_PLAY_RECORD_WORDS + a] = legal[j] ? cnt[j] : -1;
         x[j] = legal[j] ? Y.inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
         mx = fmax(mx, x[j]);
+        if (rs && cnt[j] > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)cnt[j]);
     }
     const int64_t gid = Y.game_id[g];
     const int ply = Y.ply[g];
@@ -1204,8 +1238,30 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
 #pragma unroll
     for (int j = 0; j < kWords; ++j) sh_e[64 * j + lane] = legal[j] ? exp(x[j] - mx) : 0.0;   // :12
+    int extra = 0;   // RZ_PLAY_NO_RESIGN / RZ_PLAY_WOULD_RESIGN of a calibration game
+    if (rs) {
+        for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
+        if (lane == 0) {
+            const double n_root = (double)lo.x;
+            const double v_root = lo.x > 0 ? -(rec_w(R[1]) / n_root) : NAN;
+            const double q_best = qb > -INFINITY ? qb : NAN;
+            const double s = (isnan(v_root) || isnan(q_best)) ? NAN : fmax(v_root, q_best);
+            rec[7] = __float_as_int((float)s);
+            const bool fire = v_root < thr && q_best < thr;
+            if (resign_uniform(Y.seed, (uint64_t)gid) < Y.resign[1]) {
+                extra = RZ_PLAY_NO_RESIGN | (fire ? RZ_PLAY_WOULD_RESIGN : 0);
+            } else if (fire) {   // the mover resigns: no draw; k_play_apply ends the game
+                rec[3] = -1;
+                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_ENDED | RZ_PLAY_RESIGNED | ((1 - ply % 2) + 1) << 16;
+                rec[6] = 0;
+                Y.keep[g] = -2;
+                Y.stepm[g] = kStepResign;
+                extra = -1;
+            }
+        }
+    }
     __syncthreads();
-    if (lane == 0) {
+    if (lane == 0 && extra >= 0) {
         // cumsum in action order (numpy's cumsum is sequential too), then the first interval whose upper edge exceeds u x total
         double total = 0.0;
         for (int a = 0; a < E.A; ++a) total += sh_e[a];
@@ -1229,13 +1285,13 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         rec[6] = __float_as_int((float)rel);
         if (ok) {
             rec[3] = chosen;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED;
+            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | extra;
             Y.ply[g] = ply + 1;
             Y.keep[g] = chosen;
             Y.stepm[g] = chosen;
         } else {
             rec[3] = -1;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_STALLED;
+            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_STALLED | extra;
             Y.state[g] = kPlayStalled;
             E.active[g] = 0;   // the coming searches skip the slot until the host has decided
             Y.keep[g] = -2;
@@ -1266,9 +1322,9 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     if (mv >= 0) step_body(E, g, lane, mv, who, over);   // (idle and stalled slots make no move)
     if (lane != 0) return;
     if (drawn && E.pend != nullptr) E.pend[g] = 0;
-    if (state == kPlayRunning && mv >= 0 && over) {
+    if (state == kPlayRunning && ((mv >= 0 && over) || mv == kStepResign)) {
         int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
-        rec[4] |= RZ_PLAY_ENDED | ((who + 1) << 16);
+        if (mv >= 0) rec[4] |= RZ_PLAY_ENDED | ((who + 1) << 16);   // (a resignation's record is complete: k_play_draw)
         state = kPlayIdle;
         Y.state[g] = state;
         Y.game_id[g] = -1;
@@ -1303,6 +1359,12 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
 }
 
 __global__ void k_play_resolve(Play Y, int slot, int move) { Y.mailbox[slot] = move; }
+__global__ void k_play_set_resign(double *resign, double threshold, double disabled_frac) {
+    if (threadIdx.x == 0) {
+        resign[0] = threshold;
+        resign[1] = disabled_frac;
+    }
+}
 __global__ void k_play_no_draw(Play Y) { Y.step_ab[1] = Y.step_ab[0]; }   // rz_play_apply without a draw: the step k_play_apply reads
 
 __global__ void k_play_stop(Dev E, Play Y) {
@@ -1959,6 +2021,13 @@ int rz_root_stats(rz_engine *e, int32_t *d_n, double *d_w, void *stream) {
     return launched("k_root_stats");
 }
 
+int rz_root_values(rz_engine *e, double *d_out, void *stream) {
+    RZ_ENTER(e);
+    RZ_NEED(d_out);
+    k_root_values<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_out);
+    return launched("k_root_values");
+}
+
 int rz_advance_roots(rz_engine *e, const int32_t *d_moves, void *stream) {
     RZ_ENTER(e);
     RZ_NEED(d_moves);
@@ -1994,6 +2063,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
         if (Y.keep == nullptr && (rc = dev_alloc(e, &Y.keep, G)) != RZ_OK) return rc;
         if (Y.stepm == nullptr && (rc = dev_alloc(e, &Y.stepm, G)) != RZ_OK) return rc;
         if (Y.step_ab == nullptr && (rc = dev_alloc(e, &Y.step_ab, 2)) != RZ_OK) return rc;
+        if (Y.resign == nullptr && (rc = dev_alloc(e, &Y.resign, 2)) != RZ_OK) return rc;
         if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
     }
     Y.queue_ids = cfg->d_queue_ids;
@@ -2018,6 +2088,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.seed = cfg->seed;
     Y.inv_t = 1.0 / cfg->temperature;
     Y.margin = cfg->stall_margin > 0.0 ? cfg->stall_margin : 1e-10 * (Y.inv_t > 1.0 ? Y.inv_t : 1.0);
+    Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
     RZ_HIP(hipMemset(Y.step_ab, 0, 8));
     RZ_HIP(hipMemset(Y.ply, 0, (size_t)G * 4));
     RZ_HIP(hipMemset(Y.top_hwm, 0, (size_t)G * 4));
@@ -2046,6 +2117,15 @@ int rz_play_apply(rz_engine *e, void *stream) {
     e->play_drawn = false;
     e->play_steps += 1;
     return launched("k_play_apply");
+}
+
+int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, void *stream) {
+    RZ_ENTER(e);
+    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    if (!(disabled_frac >= 0.0 && disabled_frac <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_resign: disabled_frac %g not in [0, 1]", disabled_frac);
+    k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
+    e->play.resign_on = 1;
+    return launched("k_play_set_resign");
 }
 
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream) {

@@ -1061,6 +1061,14 @@ class MCTSEngine(object):
               'rz_root_stats')
         return self.root_n.cpu().numpy(), self.root_w.cpu().numpy()
 
+    def root_values(self):
+        """-> float64 [G, 2]: {v_root, q_best} per game (rz_root_values) -- -W / N of the root (the value for the player to move) and
+        max W / N over the root's children with N > 0; NaN where undefined.  What resignation compares with its threshold."""
+        if getattr(self, '_root_values', None) is None:
+            self._root_values = self.torch.empty((self.n_games, 2), dtype=self.torch.float64, device=self.device)
+        check(self.lib.rz_root_values(self.handle, _ptr(self._root_values), self.stream()), 'rz_root_values')
+        return self._root_values.cpu().numpy()
+
     def advance(self, moves):
         """update_with_move for every game: move >= 0 keep that subtree, -1 reset, -2 skip."""
         self.flush_deferred()   # (the kept subtree's prior blocks are copied: they must be written)
@@ -1139,6 +1147,7 @@ class MCTSEngine(object):
             self.play_log = t.zeros(shape, dtype=t.int32, device=self.device)
             attach()
         self.play_steps = 0
+        self.play_resign_on = False   # (rz_play_attach turns resignation off)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log
@@ -1210,6 +1219,14 @@ class MCTSEngine(object):
         check(self.lib.rz_play_apply(self.handle, self.stream()), 'rz_play_apply')
         self.roots_epoch += 1
         self.play_steps += 1
+
+    def play_set_resign(self, threshold, disabled_frac):
+        """The resignation rule of the move step on the device (rz_play_set_resign), enqueued on the current stream: the mover resigns
+        when v_root and q_best are both below ``threshold`` (NaN: off), except in the calibration games (resign_uniform below
+        ``disabled_frac``).  After play_attach; a whole-move graph captured before the first call since play_attach keeps the
+        resignation-free draw (``play_resign_on`` tells: capture again)."""
+        check(self.lib.rz_play_set_resign(self.handle, float(threshold), float(disabled_frac), self.stream()), 'rz_play_set_resign')
+        self.play_resign_on = True
 
     def play_resolve(self, slot, move):
         check(self.lib.rz_play_resolve(self.handle, int(slot), int(move), self.stream()), 'rz_play_resolve')

@@ -41,6 +41,38 @@ def move_uniform(seed, game_id, ply):
     return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
+_RESIGN_SALT = np.uint64(0x72657369676E0000)   # ("resign": keeps the calibration draw apart from the move and noise streams)
+
+
+def resign_uniform(seed, game_id):
+    """Uniform in [0,1) for (seed, game): a game whose value is below ``disabled_frac`` is a calibration game (resignation disabled;
+    the device's resign_uniform, the same bits)."""
+    with np.errstate(over='ignore'):
+        x = _splitmix64(_splitmix64(np.uint64(seed) ^ _RESIGN_SALT) ^ np.asarray(game_id, dtype=np.uint64))
+    return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def fp_margin(resign_stats, winner):
+    """The lowest resignation statistic a non-loser saw on their own plies (player 0 moves the even plies; on a tie both players
+    count): a calibration game would have been resigned by a player who did not lose at every threshold above it.  NaN statistics
+    never fire; NaN when there is no finite one."""
+    st = np.asarray(resign_stats, dtype=np.float32)
+    own = st if winner < 0 else st[int(winner)::2]
+    own = own[~np.isnan(own)]
+    return np.float32(own.min()) if own.size else np.float32(np.nan)
+
+
+def calibrate_resign_threshold(trajectories, target=0.05):
+    """AlphaGo Zero's calibration: the largest threshold ``t`` such that at most ``target`` of the calibration games (``no_resign``)
+    have ``fp_margin < t`` -- i.e. would have been resigned by a player who did not lose.  -inf without calibration games."""
+    margins = np.array([t.fp_margin for t in trajectories if getattr(t, 'no_resign', False)], dtype=np.float64)
+    if margins.size == 0:
+        return float('-inf')
+    margins = np.sort(np.where(np.isnan(margins), np.inf, margins))   # (a game whose statistic was never finite never fires)
+    k = int(np.floor(float(target) * margins.size + 1e-9))   # false positives allowed
+    return float(margins[k]) if k < margins.size else float('inf')
+
+
 def visits_to_pi(counts, temperature):
     """alphazero_mcts.py:10-14,91-92 on the visit counts of the legal moves."""
     x = 1.0 / temperature * np.log(np.asarray(counts) + 1e-10)
@@ -93,7 +125,15 @@ def shard_game_ids(n_games_total, rank, world_size):
 class Trajectory(object):
     """One finished game: what start_self_play returns, in compact form."""
 
-    def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku'):
+    def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku', resigned=False, no_resign=False,
+                 resign_stats=None, fp_margin=np.nan):
+        """Resignation (BatchedSelfPlay.set_resign): ``resigned`` -- the game ended with the loser's resignation; ``moves`` / ``pis``
+        are the plies actually played (the resigning search's pi is not recorded).  ``no_resign``: a calibration game (played
+        out).  ``resign_stats``: float32 max(v_root, q_best) of every search of the game -- one more than the moves of a resigned
+        game --, None with resignation off.  ``fp_margin``: a calibration game's selfplay.fp_margin, else NaN."""
+        self.resigned, self.no_resign = bool(resigned), bool(no_resign)
+        self.resign_stats = None if resign_stats is None else np.asarray(resign_stats, dtype=np.float32)
+        self.fp_margin = np.float32(fp_margin)
         self.game_id = int(game_id)
         self.game = game
         self.board_size, self.n_in_row = board_size, int(n_in_row)
@@ -114,7 +154,8 @@ class Trajectory(object):
         return env
 
     def z(self):
-        """+1 for the plies of the winner, -1 for the loser's, 0 on a tie (game.py:121-126)."""
+        """+1 for the plies of the winner, -1 for the loser's, 0 on a tie (game.py:121-126); a resigned game's winner is the
+        player who did not resign."""
         movers = np.arange(len(self.moves)) % 2  # player 0 moves first
         if self.winner == -1:
             return np.zeros(len(self.moves))
@@ -374,14 +415,58 @@ class BatchedSelfPlay(object):
         self.cell_taken = np.zeros((G, self.eng.n_cells), dtype=bool)  # host mirror of the root boards
         self.slot_moves = [[] for _ in range(G)]
         self.slot_pis = [[] for _ in range(G)]
+        self.slot_stats = [[] for _ in range(G)]   # resignation statistic of every search of the slot's game (set_resign)
         self.sims_done = 0
         self.moves_done = 0
+        self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
+        self.resign_would = 0   # plies of calibration games where the rule fired (RZ_PLAY_WOULD_RESIGN on the device)
+
+    @property
+    def resign_on(self):
+        return not np.isnan(self.resign_threshold)
+
+    def set_resign(self, threshold, disabled_frac=0.1):
+        """AlphaGo Zero's resignation for every lane (an opt-in extension: the reference plays every game to its end): the player to
+        move resigns when both v_root and q_best of its search (MCTSEngine.root_values) are below ``threshold``, except in the
+        calibration games -- resign_uniform(seed, game id) < ``disabled_frac`` -- which are played out and measure the false
+        positives (Trajectory.fp_margin, calibrate_resign_threshold).  ``threshold`` None / NaN: off.  Before or after
+        device_attach, between runs; the first rule on an attached object whose whole-move graphs were captured without one
+        attaches again (same settings) so that they are captured with it -- a later threshold reaches the graphs as it is."""
+        threshold = float('nan') if threshold is None else float(threshold)
+        disabled_frac = float(disabled_frac)
+        if not 0.0 <= disabled_frac <= 1.0:
+            raise ValueError('disabled_frac %r not in [0, 1]' % disabled_frac)
+        self.resign_threshold, self.resign_disabled_frac = threshold, disabled_frac
+        if not getattr(self, '_dev_on', False):
+            return
+        if not np.isnan(threshold) and any(lane.move_graph is not None and not lane.eng.play_resign_on for lane in self.lanes):
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the rule before the capture)
+            return
+        self._apply_resign()
+
+    def _apply_resign(self):
+        for lane in self.lanes:
+            if self.resign_on or lane.eng.play_resign_on:
+                with self._on(lane):
+                    lane.eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
+
+    def _calibration(self, game_ids):
+        """-> bool per game: resignation disabled (a calibration game) under the current rule."""
+        return resign_uniform(self.seed, game_ids) < self.resign_disabled_frac
+
+    def _resign_record(self, stats, winner, no_resign, resigned):
+        """Trajectory keywords of a finished game under the rule (none without it)."""
+        if not self.resign_on:
+            return {}
+        stats = np.asarray(stats, dtype=np.float32)
+        return dict(resigned=resigned, no_resign=no_resign, resign_stats=stats,
+                    fp_margin=fp_margin(stats, winner) if no_resign else np.nan)
 
     @classmethod
     def for_network(cls, net_module, board, n_in_row, n_games, n_playout, c_puct=5.0, device='cuda:0',
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
-                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, **engine_kw):
+                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -397,7 +482,8 @@ class BatchedSelfPlay(object):
         before the hipGraphs are captured (rlzero_amd.trace attaches its buffer there).  ``net_algo``: HipNet.set_algo for every lane's
         evaluator -- None keeps the default ('split_f16', the f32-accurate trunk); 'split_f16_fp8' is the OPT-IN arithmetic narrower than
         the reference's f32 (boards of 11 .. 16 rows and columns).  ``delta_trunk``: False = the full-board trunk on every leaf (the
-        checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU)."""
+        checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU).
+        ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -473,6 +559,8 @@ class BatchedSelfPlay(object):
                  eager_every=eager_every)
         sp.trunk_workgroups = int(wgs)
         sp.lanes_measured = measured   # {lanes: simulations / s} when the layout was chosen by measurement, else None
+        if resign is not None:
+            sp.set_resign(*(resign if isinstance(resign, (tuple, list)) else (resign, )))
         if before_warm is not None:
             before_warm(sp)
         sp.warm_graphs()
@@ -510,6 +598,7 @@ class BatchedSelfPlay(object):
             self.cell_taken[s] = False
             self.slot_moves[s] = []
             self.slot_pis[s] = []
+            self.slot_stats[s] = []
         # a game's Dirichlet noise (read by the PUCT rule only), like its move draws, is keyed by (seed, game id): the trajectory
         # does not depend on the slot, lane or GPU the game is played on
         with np.errstate(over='ignore'):
@@ -605,6 +694,20 @@ class BatchedSelfPlay(object):
                 lane.evaluator.hip.check_flags()
         self.sims_done += eng.n_playout * len(running)
         moves = np.full(eng.n_games, -2, dtype=np.int32)
+        resigned = running[:0]
+        if self.resign_on and len(running):
+            # the rule of k_play_draw on the same fp64 values: the mover resigns when v_root and q_best are both below the threshold
+            with self._on(lane):
+                vals = lane.eng.root_values()[running - lo]
+            stat = np.maximum(vals[:, 0], vals[:, 1]).astype(np.float32)   # (NaN when either is)
+            fire = (vals[:, 0] < self.resign_threshold) & (vals[:, 1] < self.resign_threshold)
+            calib = self._calibration(self.slot_game[running])
+            self.resign_would += int((fire & calib).sum())
+            for i, s_ in enumerate(running):
+                self.slot_stats[s_].append(stat[i])
+            resigned = running[fire & ~calib]
+            moves[resigned - lo] = -1    # (no move; the tree is dropped, like reset_player at the end of a game)
+            running = running[~(fire & ~calib)]
         if len(running):
             us = move_uniform(self.seed, self.slot_game[running], self.slot_ply[running])
             taken = self.cell_taken[running]
@@ -626,10 +729,13 @@ class BatchedSelfPlay(object):
             winner, ended = lane.eng.advance_and_step(moves, step_moves)  # tree reuse before the boards change
         self.moves_done += len(running)
         done = []
-        for s in running:
-            if ended[s - lo]:
+        for s in sorted(list(running) + list(resigned)):
+            quit_ = s in resigned
+            if quit_ or ended[s - lo]:
+                win = 1 - len(self.slot_moves[s]) % 2 if quit_ else int(winner[s - lo])   # (player 0 moves the even plies)
+                extra = self._resign_record(self.slot_stats[s], win, bool(self._calibration(self.slot_game[s])), quit_)
                 done.append(Trajectory(self.slot_game[s], eng.board_size, eng.n_in_row,
-                                       self.slot_moves[s], self.slot_pis[s], winner[s - lo], game=eng.game))
+                                       self.slot_moves[s], self.slot_pis[s], win, game=eng.game, **extra))
                 self.slot_game[s] = -1
         return done
 
@@ -785,6 +891,8 @@ class BatchedSelfPlay(object):
             with self._on(lane):
                 lane.eng.play_attach(self.seed, self.temperature, self._queue_ids, self._queue_ctl, ring_steps=ring_steps,
                                      stall_margin=stall_margin)
+                if self.resign_on:   # (before the capture: the graph's draw then reads the rule's buffer -- set_resign)
+                    lane.eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
@@ -797,6 +905,7 @@ class BatchedSelfPlay(object):
         max_plies = self.eng.n_cells
         self._pi_buf = np.empty((self.n_slots, max_plies, self.eng.n_actions), dtype=np.float64)   # (pages are touched as games grow)
         self._mv_buf = np.zeros((self.n_slots, max_plies), dtype=np.int32)
+        self._st_buf = np.zeros((self.n_slots, max_plies), dtype=np.float32)   # resignation statistic per searched ply (word 7)
         self._stalls = {}               # slot -> (game id, ply, pi, move): decided here, waiting for the device to take it
         self.stalls_resolved = 0
         self.slot_game[:] = -1
@@ -873,7 +982,8 @@ class BatchedSelfPlay(object):
         return done
 
     def _harvest(self, lane, keep):
-        from ._hip import PLAY_ENDED, PLAY_RECORD_WORDS, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED, PLAY_STALLED, HipError
+        from ._hip import (PLAY_ENDED, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED,
+                           PLAY_STALLED, PLAY_WOULD_RESIGN, HipError)
         rows = []
         while lane.inflight and (len(lane.inflight) > keep or lane.inflight[0][1].query()):
             batch, ev = lane.inflight.pop(0)
@@ -897,12 +1007,30 @@ class BatchedSelfPlay(object):
         legal = visits >= 0
         # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
         pis, chosen = batch_pi_and_moves(np.where(legal, visits, 0), legal, self.temperature, move_uniform(self.seed, gids, plies))
-        not_plain = (flags & (PLAY_STALLED | PLAY_RESOLVED)) != 0
+        not_plain = (flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED)) != 0
         wrong = ~not_plain & (chosen != moves)
         if wrong.any():
             bad = np.nonzero(wrong)[0][0]
             raise HipError('the move drawn on the device (%d) is not numpy\'s (%d): game %d, ply %d' % (moves[bad], chosen[bad], gids[bad], plies[bad]))
-        self.sims_done += eng.n_playout * int(((flags & PLAY_SEARCHED) != 0).sum())
+        searched = (flags & PLAY_SEARCHED) != 0
+        self.sims_done += eng.n_playout * int(searched.sum())
+        stats = np.ascontiguousarray(rec[:, 7]).view(np.float32)
+        if self.resign_on:
+            # the device's decision against its logged statistic s (float32 of the fp64 s it compared): resigned / would resign
+            # => s <= threshold, played on => s >= threshold or NaN; the calibration flag against this side's draw
+            t32 = np.float32(self.resign_threshold)
+            calib = self._calibration(gids)
+            fired = (flags & (PLAY_RESIGNED | PLAY_WOULD_RESIGN)) != 0
+            with np.errstate(invalid='ignore'):
+                bad = searched & (((flags & PLAY_NO_RESIGN) != 0) != calib)
+                bad |= searched & fired & ~(stats <= t32)
+                bad |= searched & ~fired & (stats < t32)
+                bad |= ((flags & PLAY_RESIGNED) != 0) & calib
+            if bad.any():
+                i = np.nonzero(bad)[0][0]
+                raise HipError('the device\'s resignation flags 0x%x of game %d ply %d disagree with s = %r, threshold %r, calibration %s' % (
+                    flags[i], gids[i], plies[i], float(stats[i]), self.resign_threshold, bool(calib[i])))
+            self.resign_would += int(((flags & PLAY_WOULD_RESIGN) != 0).sum())
         special = not_plain | ((flags & PLAY_ENDED) != 0) | (plies == 0)
         done = []
         first = np.searchsorted(row_i, np.arange(len(rows) + 1))   # records of row r: first[r] .. first[r + 1]
@@ -919,10 +1047,13 @@ class BatchedSelfPlay(object):
                         slots[i], gids[i], plies[i], self.slot_game[slots[i]], self.slot_ply[slots[i]]))
                 self._pi_buf[s, plies[easy]] = pis[easy]
                 self._mv_buf[s, plies[easy]] = moves[easy]
+                self._st_buf[s, plies[easy]] = stats[easy]
                 self.slot_ply[s] += 1
                 self.moves_done += int(easy.size)
             for i in np.nonzero(special[a:b])[0] + a:
                 s, f, gid, ply = int(slots[i]), int(flags[i]), int(gids[i]), int(plies[i])
+                if f & PLAY_SEARCHED:   # (a stall's searched record comes before the resolved one of its ply)
+                    self._st_buf[s, ply] = stats[i]
                 if f & PLAY_STALLED:
                     known = self._stalls.get(s)
                     if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
@@ -942,6 +1073,13 @@ class BatchedSelfPlay(object):
                     self._started += 1
                 if self.slot_game[s] != gid or self.slot_ply[s] != ply:
                     raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (s, gid, ply, self.slot_game[s], self.slot_ply[s]))
+                if f & PLAY_RESIGNED:   # the game ends without a move: the plies before it
+                    winner = ((int(rec[i, 4]) >> 16) & 3) - 1
+                    extra = self._resign_record(self._st_buf[s, :ply + 1].copy(), winner, False, True)
+                    done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :ply].tolist(), self._pi_buf[s, :ply].copy(),
+                                           winner, game=eng.game, **extra))
+                    self.slot_game[s] = -1
+                    continue
                 self._pi_buf[s, ply] = pi
                 self._mv_buf[s, ply] = mv
                 self.slot_ply[s] += 1
@@ -949,7 +1087,9 @@ class BatchedSelfPlay(object):
                 if f & PLAY_ENDED:
                     winner = ((int(rec[i, 4]) >> 16) & 3) - 1
                     n = ply + 1
-                    done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :n].tolist(), self._pi_buf[s, :n].copy(), winner, game=eng.game))
+                    extra = self._resign_record(self._st_buf[s, :n].copy(), winner, bool(self._calibration(gid)), False)
+                    done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :n].tolist(), self._pi_buf[s, :n].copy(), winner,
+                                           game=eng.game, **extra))
                     self.slot_game[s] = -1
         return done
 
@@ -999,9 +1139,24 @@ class BatchedSelfPlay(object):
 
 
 # ------------------------------------------------------------------------- multi-GPU gather
+def _resign_word(t):
+    """Header word 3: bit 32 resigned, bit 33 calibration game, low 32 bits the float bits of a calibration game's fp_margin; 0 for
+    every game played without resignation (the format of a run without it is unchanged)."""
+    no_resign = bool(getattr(t, 'no_resign', False))
+    low = int(np.float32(t.fp_margin).view(np.uint32)) if no_resign else 0
+    return (int(bool(getattr(t, 'resigned', False))) << 32) | (int(no_resign) << 33) | low
+
+
+def _resign_fields(word):
+    word = int(word)
+    no_resign = bool((word >> 33) & 1)
+    margin = np.uint32(word & 0xFFFFFFFF).view(np.float32) if no_resign else np.float32(np.nan)
+    return dict(resigned=bool((word >> 32) & 1), no_resign=no_resign, fp_margin=margin)
+
+
 def pack_trajectories(trajs, n_cells):
-    """-> (header int64 [n,4] = game id, plies, winner, 0 ; moves int64 [P] ; pis float64 [P,S])."""
-    header = np.array([[t.game_id, len(t.moves), t.winner, 0] for t in trajs], dtype=np.int64).reshape(-1, 4)
+    """-> (header int64 [n,4] = game id, plies, winner, resignation word (_resign_word) ; moves int64 [P] ; pis float64 [P,S])."""
+    header = np.array([[t.game_id, len(t.moves), t.winner, _resign_word(t)] for t in trajs], dtype=np.int64).reshape(-1, 4)
     moves = np.array([m for t in trajs for m in t.moves], dtype=np.int64)
     pis = np.concatenate([t.pis for t in trajs], axis=0) if trajs else np.zeros((0, n_cells))
     return header, moves, pis.reshape(-1, n_cells)
@@ -1009,10 +1164,10 @@ def pack_trajectories(trajs, n_cells):
 
 def unpack_trajectories(header, moves, pis, board_size, n_in_row, game='gomoku'):
     out, at = [], 0
-    for gid, plies, winner, _ in header:
+    for gid, plies, winner, word in header:
         plies = int(plies)
         out.append(Trajectory(gid, board_size, n_in_row, moves[at:at + plies], pis[at:at + plies], winner,
-                              game=game))
+                              game=game, **_resign_fields(word)))
         at += plies
     return out
 
@@ -1041,7 +1196,7 @@ def payload_of(trajs, n_cells, pi_dtype):
     at = 0
     for i, t in enumerate(trajs):
         k = len(t.moves)
-        header[i] = (t.game_id, k, t.winner, 0)
+        header[i] = (t.game_id, k, t.winner, _resign_word(t))
         moves[at:at + k] = t.moves
         if k:
             pis[at:at + k] = t.pis   # (numpy converts while it copies)

@@ -147,17 +147,28 @@ class ReplayBuffer(Sequence):
 class TrainPipeline:
 
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
-                 selfplay_games_in_flight=0, buffer_size=None, seed=None):
+                 selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
+                 resign_fp_target=0.05):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
         256-game round (~200 k augmented samples) would keep its last 1000 samples and drop > 99 % of what the GPU
         produced.  Pass 1000 to get the reference's number in either mode.  ``seed``: of the batched mode's move draws
         (uniforms keyed (seed, game id, ply)); None = drawn on rank 0.  Under a launcher (RANK / WORLD_SIZE set, or an
-        initialised process group) the pipeline is one of the ranks: see the module docstring."""
+        initialised process group) the pipeline is one of the ranks: see the module docstring.
+        ``resign``: self-play resignation (BatchedSelfPlay.set_resign; batched mode only, an opt-in extension): 'off', a threshold,
+        or 'auto' -- the first round all calibration games with threshold -inf (statistics only), then after every round rank 0
+        sets the threshold from the calibration games of the last rounds (selfplay.calibrate_resign_threshold, at most
+        ``resign_fp_target`` false positives) and hands it to every rank.  ``resign_disabled_frac``: the calibration games."""
+        if resign != 'off' and selfplay_games_in_flight <= 0:
+            raise ValueError('resignation is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.rank, self.world = self._init_ranks()
         if self.world > 1 and selfplay_games_in_flight <= 0:
             raise ValueError('several ranks share a collection round: selfplay_games_in_flight must be > 0 (games per GPU)')
+        self.resign_mode = resign if resign in ('off', 'auto') else float(resign)
+        self.resign_disabled_frac, self.resign_fp_target = float(resign_disabled_frac), float(resign_fp_target)
+        self.resign_threshold = None if resign == 'off' else float('-inf') if resign == 'auto' else float(resign)
+        self._resign_history = []   # calibration games of the last rounds (rank 0, 'auto')
         # board and game
         self.board_size = board_size
         self.n_in_row = n_in_row
@@ -276,6 +287,10 @@ class TrainPipeline:
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
                 device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed)
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
+        if self.resign_mode != 'off':
+            # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
+            first = self.resign_mode == 'auto' and not self._resign_history and self.resign_threshold == float('-inf')
+            self._batched.set_resign(self.resign_threshold, 1.0 if first else self.resign_disabled_frac)
         # the move step on the device (rz_play_*: the host reads the games from a log behind the GPU); RZ_TRAIN_HOST_MOVES=1: the
         # host-driven loop -- the same trajectories either way (tests/test_device_moves.py)
         if os.environ.get('RZ_TRAIN_HOST_MOVES') == '1':
@@ -326,6 +341,7 @@ class TrainPipeline:
         if self.world > 1:
             local = self._play_games([g for g in ids if g % self.world == self.rank])
             merged = gather_trajectories(local, self.board_size, self.n_in_row, dst=0, pi_dtype=np.float32)
+            self._resign_round(merged)
             return [t.as_reference_tuple() for t in merged] if merged is not None else []
         # one rank: every finished game becomes start_self_play's tuple (planes from its move list) WHILE the others are played --
         # behind an idle GPU that was a tenth of a round; the round's order stays the game ids'
@@ -338,8 +354,35 @@ class TrainPipeline:
                 consume(ready.pop(cursor[0]))
                 cursor[0] += 1
         local = self._play_games(list(ids), on_finished=take)
+        self._resign_round(local)
         rest = [t for t in sorted(local, key=lambda t: t.game_id) if t.game_id >= cursor[0] or consume is None]
         return [ready[t.game_id] if t.game_id in ready else t.as_reference_tuple() for t in rest]
+
+    RESIGN_ROUNDS = 4   # 'auto': rounds of calibration games the threshold is set from
+
+    def _resign_round(self, trajs):
+        """After a collection round (``trajs``: every rank's games on rank 0, None elsewhere): rank 0 prints the round's
+        resignations, the calibration games' false-positive rate at the threshold played and -- 'auto' -- sets the next threshold,
+        which every rank takes."""
+        if self.resign_mode == 'off':
+            return
+        from rlzero.algorithms import calibrate_resign_threshold
+        if trajs is not None:
+            calib = [t for t in trajs if t.no_resign]
+            played = self.resign_threshold
+            fp = np.mean([t.fp_margin < played for t in calib]) if calib else float('nan')
+            if self.resign_mode == 'auto':
+                self._resign_history = (self._resign_history + [calib])[-self.RESIGN_ROUNDS:]
+                self.resign_threshold = calibrate_resign_threshold([t for r in self._resign_history for t in r], self.resign_fp_target)
+            print('resign: {} of {} games resigned, calibration false positives {:.3f} of {} at threshold {:.4f}; next threshold {:.4f}'.format(
+                sum(t.resigned for t in trajs), len(trajs), fp, len(calib), played, self.resign_threshold), flush=True)
+        if self.world > 1 and self.resign_mode == 'auto':   # rank 0's threshold on every rank
+            import torch.distributed as dist
+            on_gpu = dist.get_backend() == 'nccl'
+            t = torch.tensor([self.resign_threshold], dtype=torch.float64, device=self.device if on_gpu else 'cpu')
+            dist.broadcast(t, src=0)
+            self.resign_threshold = float(t.item())
+            self._resign_history = self._resign_history or [[]]   # (past the first round on every rank)
 
     def collect_selfplay_data(self, n_games=1):
         """collect self-play data for training."""
@@ -484,7 +527,18 @@ def main():
     ap.add_argument('--check-freq', type=int, default=50)
     ap.add_argument('--games-in-flight', type=int, default=0, help='per GPU; 0 = the reference flow, one game at a time')
     ap.add_argument('--seed', type=int, default=None)
+    ap.add_argument('--resign-threshold', default='off',
+                    help="self-play resignation (batched mode only): off, auto (calibrated every round) or a value threshold")
+    ap.add_argument('--resign-disabled-frac', type=float, default=0.1, help='games played out to measure false positives')
+    ap.add_argument('--resign-fp-target', type=float, default=0.05, help="'auto': false-positive rate the threshold allows")
     args = ap.parse_args()
+    if args.resign_threshold != 'off' and args.games_in_flight <= 0:
+        ap.error('--resign-threshold needs --games-in-flight > 0 (batched self-play)')
+    if args.resign_threshold not in ('off', 'auto'):
+        try:
+            float(args.resign_threshold)
+        except ValueError:
+            ap.error('--resign-threshold: off, auto or a number, not %r' % args.resign_threshold)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.seed is not None:   # a reproducible run: initial weights, random.sample of the replay buffer, numpy draws
@@ -492,7 +546,9 @@ def main():
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
     pipe = TrainPipeline(board_size=args.board, n_in_row=args.n_in_row, n_playout=args.playouts, game_batch_num=args.batches,
-                         check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed)
+                         check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed,
+                         resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
+                         resign_fp_target=args.resign_fp_target)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
