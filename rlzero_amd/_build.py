@@ -20,7 +20,7 @@ REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, 'librlzero_hip.so')
 OBJ_DIR = os.path.join(PKG, 'csrc', '_obj')
 SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip')]
-HEADERS = [os.path.join(REPO, "include", "rlzero_hip.h"), os.path.join(PKG, "csrc", "rz_trace.h"), os.path.join(PKG, "csrc", "rz_tree.h"), os.path.join(PKG, "csrc", "rz_delta.h")]
+HEADERS = [os.path.join(REPO, "include", "rlzero_hip.h"), os.path.join(PKG, "csrc", "rz_trace.h"), os.path.join(PKG, "csrc", "rz_tree.h"), os.path.join(PKG, "csrc", "rz_delta.h"), os.path.join(PKG, "csrc", "rz_window.h")]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fno-fast-math', '-fno-slp-vectorize', '-std=c++17',
          '-fPIC', '-Wall', '-Wno-unused-function']
 MARKER = b'RZ_SOURCE_HASH='

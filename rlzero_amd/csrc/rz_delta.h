@@ -27,7 +27,8 @@
 // mode 1 builds the bases that way and writes the cache.
 // (the prologue of a pass has ONE barrier: every wave ballots the membership of all four 64-cell blocks, so ranks and totals are in
 // its registers, and a thread requests the base records it holds as soon as it knows it holds them -- one fetch, stored in the same
-// phase; profiles/r07/ab_prologue.txt)
+// phase; profiles/r07/ab_prologue.txt; k_delta_res: pass -1's sets come from the selecting wave instead, leaf_windows --
+// profiles/r08/ab_windows.txt)
 // (issue priorities of the resident search's phases, s_setprio: its serial tree phase -- one wave, ~20 k cycles a simulation -- ahead of
 // the OTHER game's trunk waves on the same SIMDs: +2.5 % on the whole line, profiles/r06/ab_prio.txt; PRO: the trunk's prologue likewise)
 #ifndef RZ_DELTA_TREE_PRIO
@@ -58,7 +59,11 @@ constexpr int kOffC1 = sp::kInPieceBytes, kOffC2 = kOffC1 + kC1Slots * P1, kOffZ
               kOffMap1 = kOffHead + kHeadW, kOffMap2 = kOffMap1 + kGrid * 4, kOffList = kOffMap2 + kGrid * 4,
               kLdsBytes = kOffList + 3 * 128 * 2;
 static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's records (dead behind conv2)");
-static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + 512) <= 160 * 1024, "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf)");
+// the resident search's hand-over from the selection to the next leaf's prologue (leaf_windows): the four window sets of pass -1
+// (radius 1 .. 4) as 4 x 4 words, their words' popcounts, the verdict (use_delta | parity << 1 | nD << 8)
+constexpr int kWinSets = rzw::kRadii * rzw::kWords, kWinLds = kWinSets * 8 + kWinSets * 4 + 16;
+static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + kWinLds + 512) <= 160 * 1024,
+              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
 
 // The base cache: per game a header (the stones the two bases were computed from) and per (game, parity) the records.
@@ -80,6 +85,7 @@ struct DeltaArgs {
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
+    const uint64_t *win;     // k_delta_res: the window table of the net's board (rz_window.h; NULL elsewhere)
 };
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -323,6 +329,7 @@ struct Leaf {
     _Float16 *dst16;          // the policy pieces' place in the store (NULL: none)
     float *vdst;              // the value head's input row (global memory, or LDS in the resident search)
     float *dst32;             // f32 features (tests; NULL otherwise)
+    const uint64_t *sets;     // delta_passes<true>: pass -1's window sets, handed over in LDS (leaf_windows)
     bool deferred, store_head;
 };
 struct Layers {
@@ -368,7 +375,13 @@ __device__ __forceinline__ f32x4 load_rec(__amdgpu_buffer_rsrc_t rsrc, int off) 
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
 }
 
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+    return ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 // The passes of one leaf: -1 = against the base (use_delta), 0 .. 3 = the board's quadrants without one.  -> tiles computed: conv3 | conv2 << 16.
+// SETS (k_delta_res): pass -1 takes its cell sets, ranks and totals from leaf.sets (leaf_windows) instead of the distances and ballots.
+template <bool SETS>
 __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &da, char *lds, int tid0, int wave, const Leaf &leaf, const Layers &ly,
                                             f32x4 headv, bool &use_delta, Prof &prof) {
     char *in0 = lds, *c1 = lds + kOffC1, *c2 = lds + kOffC2, *zrec = lds + kOffZero, *headw = lds + kOffHead;
@@ -399,13 +412,23 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         const bool is_cell = tid < S;
         const int mypos = is_cell ? (cy + 1) * kRowW + cx + 1 : 0;
         if (RZ_DELTA_PRO_PRIO) __builtin_amdgcn_s_setprio(RZ_DELTA_PRO_PRIO);
-        // ---- the distance of this thread's cell to the changed cells (delta) / to the pass's quadrant
-        const int dist = cell_dist(cy, cx, pass, dys, dxs, BH, BW);
         // sets: 0 = conv1 computes, 1 = conv2 computes, 2 = conv3 computes, 3 = conv1 records held, 4 = conv2 records held
         const int th[5] = {pass < 0 ? 1 : 2, pass < 0 ? 2 : 1, pass < 0 ? 3 : 0, pass < 0 ? 3 : 2, pass < 0 ? 4 : 1};
         bool f[5];
+        uint64_t own[5];   // (SETS, pass -1: set k = the window of radius th[k] handed over by the selection; the wave's word of it)
+        const bool handed = SETS && pass < 0;   // (uniform)
+        if (handed) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) f[k] = is_cell && dist <= th[k];
+            for (int k = 0; k < 5; ++k) {
+                own[k] = uni64(leaf.sets[4 * (th[k] - 1) + wave]);
+                f[k] = (own[k] >> lane) & 1ull;   // (cells past the board: no bit)
+            }
+        } else {
+            // ---- the distance of this thread's cell to the changed cells (delta) / to the pass's quadrant
+            const int dist = cell_dist(cy, cx, pass, dys, dxs, BH, BW);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) f[k] = is_cell && dist <= th[k];
+        }
         // the records conv2 / conv3 read but this leaf does not recompute come from the base: requested NOW, straight into the
         // registers they are stored from (no barrier lies between).  Every load is issued by every thread --
         // a load under a branch makes hipcc wait for every outstanding load first --; a thread that holds no such record reads
@@ -440,8 +463,23 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         f32x4 bias2 = *reinterpret_cast<const f32x4 *>(nd.b2 + 16 * wave + 4 * g);
         // ranks and totals without a barrier: every wave evaluates the membership of all four 64-cell blocks (its own block's ballots
         // give the ranks inside the wave, the blocks before it the offsets); the same values in every wave, so the budget test is uniform
+        // (SETS, pass -1: the handed-over words' popcounts give the same)
         int rank[5], tot[5];
-        {
+        if (handed) {
+            const int *cnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                int before = 0, all = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int c = __builtin_amdgcn_readfirstlane(cnt[4 * (th[k] - 1) + w]);
+                    all += c;
+                    before += w < wave ? c : 0;
+                }
+                rank[k] = before + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(own[k] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)own[k], 0u));
+                tot[k] = all;
+            }
+        } else {
             int before[5] = {0, 0, 0, 0, 0}, all[5] = {0, 0, 0, 0, 0};
             unsigned long long own[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
 #pragma unroll
@@ -772,6 +810,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (mode != 1 && !deferred && feat16 != nullptr)   // rz_net_delta_trunk_engine: the FC GEMM's own tiles (policy and value K-steps), as trunk_rows_body writes them
         leaf.dst16 = feat16 + ((size_t)(board >> 5) * (nd.groups_act + nd.groups_val) * 1024 + (board & 31) * 16);
     leaf.dst32 = (mode != 1 && da.feat32 != nullptr) ? da.feat32 + (size_t)board * 6 * S : nullptr;
+    leaf.sets = nullptr;
     leaf.deferred = deferred;
     leaf.store_head = true;
 
@@ -786,7 +825,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
                                                // one of the batch, not a round trip of its own at the top)
     __syncthreads();   // the zeroed halo and the default maps before the first pass writes its cells into them
     NET_TICK(0);   // requests, scalars, header, planes, zeroing
-    const int n_tiles = delta_passes(nd, da, lds, tid0, wave, leaf, ly, headv, use_delta, prof);
+    const int n_tiles = delta_passes<false>(nd, da, lds, tid0, wave, leaf, ly, headv, use_delta, prof);
     const int n_conv3_tiles = n_tiles & 0xffff;
 
     if (mode == 1 && par_b == 0 && tid0 == 0) {   // the header of this game's bases (the launch behind this one reads it)
@@ -812,6 +851,52 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (TRACE && tid0 == 0) rz_trace_write(later.trace, RZ_TRACE_TRUNK, deferred ? slot_ : 0, board, trace_t0);
 }
 
+// The hand-over of k_delta_res: wave 0, behind a selection (the leaf in LDS: select_body's lds_leaf), sets the next leaf against the root
+// -- changed_cells' verdict -- and, for pass -1, the cells within Chebyshev distance 1 .. 4 of its changed cells: per radius the union
+// of the window table's rows of the (at most kMaxD) changed cells.  Lane 16 i + 4 (r - 1) + w reads word w of the radius-r row of
+// changed cell i, two lane swaps OR the four cells' rows.  -> ws: [kWinSets] words, [kWinSets] their popcounts, the verdict.
+__device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
+                                             int lane, uint64_t *ws) {
+    uint64_t ls[8];
+    int nst = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        ls[q] = uni64(leaf_lds[q]);
+        nst += __popcll(ls[q]);
+    }
+    const int tm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(leaf_lds + 2 * RZ_BOARD_WORDS)[0]);
+    const int lc = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(leaf_lds + 2 * RZ_BOARD_WORDS)[1]);
+    int dys[kMaxD], dxs[kMaxD], parity = 0, nD = 0;
+    const bool use_delta = changed_cells(ls, rs, nst, tm, lc, nst > 0, base_ok, h_tm, da.bw_rcp, BW, dys, dxs, parity, nD);
+    const int i = lane >> 4;
+    int dy = dys[0], dx = dxs[0];
+#pragma unroll
+    for (int j = 1; j < kMaxD; ++j) {
+        dy = i == j ? dys[j] : dy;
+        dx = i == j ? dxs[j] : dx;
+    }
+    const bool any = dy >= 0;   // (no such cell: -100)
+    const uint64_t row = da.win[(any ? dy * BW + dx : 0) * kWinSets + (lane & (kWinSets - 1))];
+    unsigned lo = any ? (unsigned)row : 0u, hi = any ? (unsigned)(row >> 32) : 0u;
+    {   // (a swap leaves the lane's own value and its partner's: the OR does not care which is which)
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        lo = a[0] | a[1];
+        hi = b[0] | b[1];
+    }
+    {
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        lo = a[0] | a[1];
+        hi = b[0] | b[1];
+    }
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    int *cnt = reinterpret_cast<int *>(ws + kWinSets);
+    if (lane < kWinSets) {
+        ws[lane] = v;
+        cnt[lane] = __popcll(v);
+    }
+    if (lane == 0) cnt[kWinSets] = (use_delta ? 1 : 0) | (parity << 1) | (nD << 8);
+}
+
 // RESIDENT SEARCH with receptive-field evaluation (rz_net_search_resident on boards of 11 .. 16 rows and columns once the base cache
 // exists): k_trunk_rows_res's loop -- leaf -> trunk -> value head -> expand / backup -> next selection, n_sims times in ONE launch, one
 // workgroup per game, the leaf handed over through LDS, the tree code the engine's own (rz_tree.h) -- with the delta passes as the
@@ -825,6 +910,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ float res_vrow[kResVrow];
     __shared__ float res_part[rzt::kDefWaves][rzt::kWave];
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
+    __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     const int game = blockIdx.x;
     if (game >= res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier)
     const unsigned long long clk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
@@ -874,17 +960,22 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         reinterpret_cast<int *>(res_leaf + 2 * RZ_BOARD_WORDS)[1] = res.E.leaf_last[game];
     }
     __syncthreads();
-    if (res.select_first != 0) {   // AlphaZeroMCTS._playout's select loop for the first simulation of the search (rz_select_step's work)
-        if (wave == 0) rzt::select_body<false>(res.E, nullptr, game, tid0 & 63, 0, res_leaf);
-        __syncthreads();
+    if (wave == 0) {
+        // AlphaZeroMCTS._playout's select loop for the first simulation of the search (rz_select_step's work), or its leaf from
+        // rz_select_step; either way the hand-over of the first leaf's windows
+        if (res.select_first != 0) rzt::select_body<false>(res.E, nullptr, game, tid0 & 63, 0, res_leaf);
+        __builtin_amdgcn_wave_barrier();
+        leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, tid0 & 63, res_win);
     }
+    __syncthreads();
     int tiles_total = 0, tiles2_total = 0, deltas = 0, cells_total = 0;
     for (int sim = 0; sim < res.n_sims; ++sim) {
         // (the thread's number is opaque per simulation: hipcc otherwise hoists the tree code's lane-dependent addresses out of this
         // loop and spills them)
         int tid_s = tid0;
         asm volatile("" : "+v"(tid_s));
-        // ---- the leaf, from LDS (select_body's lds_leaf): wave-uniform values
+        // ---- the leaf, from LDS (select_body's lds_leaf): wave-uniform values; the verdict and the window sets of pass -1 from the
+        // selection's hand-over (leaf_windows)
         uint64_t ls[8];
         int nst = 0;
 #pragma unroll
@@ -896,9 +987,13 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         const int tm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_leaf + 2 * RZ_BOARD_WORDS)[0]);
         const int lc = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_leaf + 2 * RZ_BOARD_WORDS)[1]);
         const bool has_last = nst > 0;
+        const int verdict = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_win + kWinSets)[kWinSets]);
+        bool use_delta = (verdict & 1) != 0;
+        const int parity = (verdict >> 1) & 1, nD = verdict >> 8;
         Leaf leaf;
-        int parity = 0, nD = 0;
-        bool use_delta = changed_cells(ls, rs, nst, tm, lc, has_last, base_ok, h_tm, da.bw_rcp, BW, leaf.dys, leaf.dxs, parity, nD);
+        leaf.sets = res_win;
+#pragma unroll
+        for (int i = 0; i < kMaxD; ++i) leaf.dys[i] = leaf.dxs[i] = -100;   // (pass -1 reads the sets; the passes without a base, no cells)
         leaf.base = da.recs + ((size_t)game * 2 + parity) * kBaseBytes;
         leaf.cell_planes = planes_of(ls, tid_s, tm, has_last, lc, nst);
         // the game's slot advances by one per simulation (expand_backup_body<DEF>); the value inputs stay in LDS
@@ -908,7 +1003,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         leaf.deferred = true;
         leaf.store_head = sim == 0;
         NET_TICK(0);
-        const int n_tiles = delta_passes(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
+        const int n_tiles = delta_passes<true>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
         tiles_total += n_tiles & 0xffff;
         tiles2_total += n_tiles >> 16;
         deltas += use_delta ? 1 : 0;
@@ -926,7 +1021,11 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         __syncthreads();        // the tree's updates before the selection's loads
         NET_TICK(17);
         const bool more = sim + 1 < res.n_sims;
-        if (wave == 0 && more) rzt::select_body<false>(res.E, nullptr, game, lane, 0, res_leaf);
+        if (wave == 0 && more) {
+            rzt::select_body<false>(res.E, nullptr, game, lane, 0, res_leaf);
+            __builtin_amdgcn_wave_barrier();
+            leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, lane, res_win);
+        }
         if (RZ_DELTA_TREE_PRIO) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         NET_TICK(18);

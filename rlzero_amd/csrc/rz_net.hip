@@ -39,6 +39,7 @@
 #include "rlzero_hip.h"
 #include "rz_trace.h"
 #include "rz_tree.h"
+#include "rz_window.h"
 
 void rz_set_error(const char *msg);  // rz_engine.hip
 
@@ -2657,6 +2658,7 @@ struct rz_net {
     char *d_base_recs = nullptr;
     unsigned *d_delta_stats = nullptr;
     uint8_t *d_base_ones = nullptr;   // [base_games] of 1: the `active` flags of a caller that has none
+    uint64_t *d_win = nullptr;        // the window table of the net's board (rz_window.h; the board is fixed per net): k_delta_res
     int base_games = 0;
     bool delta_resident = true;       // rz_net_delta_resident: rz_net_search_resident runs k_delta_res where the cache allows
 };
@@ -3012,6 +3014,7 @@ int rz_net_destroy(rz_net *net) {
     if (net->d_base_recs) (void)hipFree(net->d_base_recs);
     if (net->d_delta_stats) (void)hipFree(net->d_delta_stats);
     if (net->d_base_ones) (void)hipFree(net->d_base_ones);
+    if (net->d_win) (void)hipFree(net->d_win);
     delete net;
     return RZ_OK;
 }
@@ -3475,7 +3478,7 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         if (select_first) {   // a search begins: the bases of its roots (a continued search finds them, or takes the route without)
             if ((rc = rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream)) != RZ_OK) return rc;
         }
-        dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, net->d_delta_stats, 0, (65536 + net->dev.BW - 1) / net->dev.BW};
+        dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, net->d_delta_stats, 0, (65536 + net->dev.BW - 1) / net->dev.BW, net->d_win};
         dl::k_delta_res<<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (k_delta_res) failed");
         return RZ_OK;
@@ -3520,6 +3523,13 @@ int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
     if (n_games < 1) return net_fail(RZ_ERR_ARG, "rz_net_delta_reserve: n_games must be positive");
     if (n_games <= net->base_games) return RZ_OK;
     (void)hipDeviceSynchronize();
+    if (!net->d_win) {   // the window table of the net's board (k_delta_res's leaf_windows)
+        std::vector<uint64_t> win(rzw::kEntries);
+        rzw::window_table(win.data(), net->dev.BH, net->dev.BW);
+        if (hipMalloc((void **)&net->d_win, win.size() * sizeof(uint64_t)) != hipSuccess) return net_fail(RZ_ERR_OOM, "hipMalloc failed (window table)");
+        if (hipMemcpy(net->d_win, win.data(), win.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+            return net_fail(RZ_ERR_HIP, "hipMemcpy failed (window table)");
+    }
     if (net->d_base_hdr) (void)hipFree(net->d_base_hdr);
     if (net->d_base_recs) (void)hipFree(net->d_base_recs);
     if (net->d_base_ones) (void)hipFree(net->d_base_ones);

@@ -1,0 +1,254 @@
+"""The window sets of a receptive-field leaf (rz_window.h, rz_delta.h: leaf_windows / delta_passes<true>).
+
+k_delta_res takes the five cell sets of a leaf's pass against the base -- the cells within Chebyshev distance 1, 2, 3, 3, 4 of its
+changed cells -- as unions of the window table's rows, handed over by the selection, instead of every wave's distances and ballots.
+The table must be exactly what cell_dist gives (CPU), and the resident search must select, evaluate and count exactly what the
+two-launch step (k_trunk_delta, which keeps the distances and ballots) does on the same leaves (GPU): the same trees bit for bit
+(priors and values come out of the features) and the same delta counters."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RADII, WORDS = 4, 4
+DRIVER = r'''
+#include <cstdio>
+#include <vector>
+#include "rz_window.h"
+int main() {
+    std::vector<uint64_t> t(rzw::kEntries);
+    for (int rows = 11; rows <= 16; ++rows)
+        for (int cols = 11; cols <= 16; ++cols) {
+            rzw::window_table(t.data(), rows, cols);
+            fwrite(t.data(), sizeof(uint64_t), t.size(), stdout);
+        }
+    return 0;
+}
+'''
+
+
+def _cell_dist(rows, cols, changed):
+    """cell_dist of rz_delta.h, pass -1: per cell of the board, min over the changed cells (y, x) of max(|dy|, |dx|)."""
+    y, x = np.divmod(np.arange(rows * cols), cols)
+    dist = np.full(rows * cols, 1000)
+    for cy, cx in changed:
+        dist = np.minimum(dist, np.maximum(np.abs(y - cy), np.abs(x - cx)))
+    return dist
+
+
+def _words(members):
+    """bool [cells <= 256] -> the 256-bit mask as four uint64 words."""
+    bits = np.zeros(256, dtype=np.uint64)
+    bits[:len(members)] = members.astype(np.uint64)
+    return [int((bits[64 * w:64 * w + 64] << np.arange(64, dtype=np.uint64)).sum(dtype=np.uint64)) for w in range(WORDS)]
+
+
+@pytest.fixture(scope='module')
+def tables():
+    cxx = next((c for c in ('c++', 'g++', 'clang++') if shutil.which(c)), None)
+    assert cxx is not None, 'a host C++ compiler builds the table driver'
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, 'win.cpp'), os.path.join(tmp, 'win')
+        with open(src, 'w') as f:
+            f.write(DRIVER)
+        subprocess.run([cxx, '-std=c++17', '-O1', '-I', os.path.join(REPO, 'rlzero_amd', 'csrc'), src, '-o', exe], check=True)
+        raw = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout
+    t = np.frombuffer(raw, dtype=np.uint64).reshape(6, 6, 256, RADII, WORDS)
+    return {(11 + i, 11 + j): t[i, j] for i in range(6) for j in range(6)}
+
+
+@pytest.mark.parametrize('rows', range(11, 17))
+def test_window_table_is_cell_dist(tables, rows):
+    """Every cell, radius 1 .. 4 and board of 11 .. 16 rows and columns: the row of the table is the set of on-board cells within
+    that Chebyshev distance; cells past the board have empty rows."""
+    for cols in range(11, 17):
+        t = tables[(rows, cols)]
+        S = rows * cols
+        for c in range(S):
+            dist = _cell_dist(rows, cols, [divmod(c, cols)])
+            for r in range(1, RADII + 1):
+                assert [int(v) for v in t[c, r - 1]] == _words(dist <= r), (rows, cols, c, r)
+        assert not t[S:].any()
+
+
+def test_window_unions_are_cell_dist(tables):
+    """Up to kMaxD = 4 changed cells (corners, edges, the middle, repeated cells): the OR of their rows is cell_dist's set for every
+    threshold of pass -1 (1, 2, 3, 4)."""
+    rs = np.random.RandomState(1)
+    for (rows, cols), t in tables.items():
+        S = rows * cols
+        special = [0, cols - 1, S - cols, S - 1, cols // 2, (rows // 2) * cols, S // 2]
+        for trial in range(40):
+            n = 1 + trial % 4
+            cells = [int(c) for c in (rs.choice(special, n) if trial % 3 == 0 else rs.randint(0, S, n))]
+            dist = _cell_dist(rows, cols, [divmod(c, cols) for c in cells])
+            for r in range(1, RADII + 1):
+                got = [0] * WORDS
+                for c in cells:
+                    got = [g | int(v) for g, v in zip(got, t[c, r - 1])]
+                assert got == _words(dist <= r), (rows, cols, cells, r)
+
+
+# ---- the resident search (k_delta_res) against the two-launch step (k_trunk_delta) on the same leaves
+
+STATS = ('delta', 'no_base', 'cells', 'tiles3', 'tiles2')
+
+
+def _net(B, seed):
+    import torch
+    from rlzero_amd.games.gomoku.policy_value_net import PolicyValueNet
+    torch.manual_seed(seed)
+    return PolicyValueNet(B)
+
+
+def _edge_roots(B, count, seed):
+    """Roots whose last move lies on a corner or an edge (and one empty board): the depth-0 leaf of a search is the root, its one
+    changed cell that last move; the depth-1 leaves add a stone on every free cell, corners and edges included."""
+    from oracle.gomoku_ref import RefGomoku
+    rs = np.random.RandomState(seed)
+    S = B * B
+    lasts = [0, B - 1, S - B, S - 1, B // 2, (B // 2) * B, (B // 2) * B + B - 1, S - 1 - B // 2]
+    envs = [RefGomoku(B, 5)]
+    while len(envs) < count:
+        last = lasts[len(envs) % len(lasts)]
+        others = [int(c) for c in rs.permutation(S) if c != last][:2 * rs.randint(0, 8)]
+        e = RefGomoku.from_moves(B, 5, others + [last])
+        if not e.game_end_winner()[0]:
+            envs.append(e)
+    return envs
+
+
+def _late_roots(B, count, seed, empty_cells=None, n_empty=5):
+    """Nearly full boards without a line (cell (y, x) black when (x + 2 y) mod 4 < 2, balanced by leaving a few more cells empty):
+    `empty_cells` (or `n_empty` random cells) left free.  The trees go deep: with the free cells far apart, leaves of three or four
+    changed cells exceed the windows' budget; with few of them, leaves of more than kMaxD changed cells are reached.  Both take the
+    passes without a base."""
+    from oracle.gomoku_ref import RefGomoku
+    rs = np.random.RandomState(seed)
+    S = B * B
+    envs = []
+    for i in range(count):
+        empty = set(empty_cells) if empty_cells is not None else set(rs.choice(S, n_empty, replace=False).tolist())
+        black = [c for c in range(S) if c not in empty and (c % B + 2 * (c // B)) % 4 < 2]
+        white = [c for c in range(S) if c not in empty and (c % B + 2 * (c // B)) % 4 >= 2]
+        while not 0 <= len(black) - len(white) <= 1:
+            big = black if len(black) > len(white) else white
+            big.pop(rs.randint(len(big)))
+        rs.shuffle(black)
+        rs.shuffle(white)
+        moves = [m for pair in zip(black, white) for m in pair] + black[len(white):]
+        e = RefGomoku.from_moves(B, 5, moves)
+        if not e.game_end_winner()[0]:
+            envs.append(e)
+    return envs
+
+
+def _search(net, envs, chunks, resident, select_first_0=False):
+    """Searches from `envs`, `chunks` simulations at a time -> (root visits, whole trees, delta counters).  select_first_0: every
+    chunk after the first is continued as rz_select_step + the resident launch with select_first = 0 (its first leaf from the
+    engine's leaf arrays)."""
+    from rlzero_amd.engine import HipNetEvaluator, MCTSEngine, check, int_to_bits
+    B = envs[0].board_size
+    sims = sum(chunks)
+    evaluator = HipNetEvaluator(net, B, 'cuda:0', max_boards=len(envs))
+    evaluator.resident_search = resident
+    evaluator.delta_trunk = True
+    eng = MCTSEngine(B, 5, n_games=len(envs), n_playout=sims, device='cuda:0', add_noise=True, noise_seed=3)
+    assert evaluator.resident_ok(eng) == resident and evaluator.deferred_ok(eng) and evaluator.delta_ok(eng)
+    stones = np.array([[int_to_bits(e.bitboards()[0]), int_to_bits(e.bitboards()[1])] for e in envs], dtype=np.uint64)
+    eng.set_roots(stones, [e.current_player() for e in envs], [e.last_move for e in envs], reset_trees=True)
+    eng.set_noise_keys()
+    evaluator.hip.delta_stats(reset=True)
+    for i, n in enumerate(chunks):
+        if select_first_0 and i > 0:
+            m = eng._deferred_begin(evaluator, n)
+            assert m == n
+            check(eng.lib.rz_select_step(eng.handle, None, eng.stream()), 'rz_select_step')
+            evaluator.search_resident(eng, n, False)
+            eng._def_pending += n
+            eng._def_stream = eng.torch.cuda.current_stream(eng.device)
+            eng.flush_deferred()
+        else:
+            eng.simulate(evaluator, n, use_graph=False)
+    st = evaluator.hip.delta_stats()
+    visits = eng.root_visits().copy()
+    trees = [eng.tree_dump(g) for g in range(len(envs))]
+    eng.check()
+    eng.close()
+    evaluator.hip.close()
+    return visits, trees, {k: st[k] for k in STATS}
+
+
+def _same(net, envs, chunks, select_first_0=False):
+    v_res, t_res, s_res = _search(net, envs, chunks, True, select_first_0)
+    v_two, t_two, s_two = _search(net, envs, chunks, False)
+    assert s_res['delta'] + s_res['no_base'] == len(envs) * sum(chunks), s_res
+    assert s_res == s_two
+    assert np.array_equal(v_res, v_two)
+    assert t_res == t_two
+    return s_res
+
+
+def _over_budget_leaf(trees, B, kmax=4):
+    """A visited leaf of at most kMaxD changed cells whose windows exceed rz_delta.h's budget (conv1 128, conv2 / conv3 128 cells
+    computed, 128 / 164 records held)."""
+    for tree in trees:
+        for path in tree:
+            if not 1 <= len(path) <= kmax:
+                continue
+            dist = _cell_dist(B, B, [divmod(int(c), B) for c in path])
+            tot = [(dist <= th).sum() for th in (1, 2, 3, 3, 4)]
+            if tot[0] > 128 or tot[1] > 128 or tot[2] > 128 or tot[3] > 128 or tot[4] > 164:
+                return True
+    return False
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('B', [11, 15, 16])
+def test_edges_corners_and_depth_zero_leaves(B):
+    """Corner / edge / central last moves and an empty board, one search per board size (16 x 16: the board fills all four 64-cell
+    blocks): counters and trees equal the two-launch step's."""
+    envs = _edge_roots(B, 24, seed=B)
+    s = _same(_net(B, 30 + B), envs, [48])
+    assert s['delta'] > 0 and s['tiles3'] > 0, s
+
+
+@pytest.mark.gpu
+def test_over_budget_leaves_take_the_route_without_a_base():
+    """16 x 16, six free cells far apart: leaves of three or four changed cells whose windows exceed the budget take the passes
+    without a base, the rest the pass against it."""
+    B = 16
+    net = _net(B, 41)
+    envs = _late_roots(B, 12, seed=3, empty_cells=[3 * B + 3, 3 * B + 12, 12 * B + 3, 12 * B + 12, 8 * B + 3, 8 * B + 12])
+    s = _same(net, envs, [96])
+    assert s['no_base'] > 0 and s['delta'] > 0, s
+    _, trees, _ = _search(net, envs, [96], True)
+    assert _over_budget_leaf(trees, B)
+
+
+@pytest.mark.gpu
+def test_leaves_beyond_kmaxd_changed_cells():
+    """11 x 11 (no window set can exceed the budget there), five free cells: leaves deeper than kMaxD = 4 changed cells take the
+    passes without a base."""
+    B = 11
+    net = _net(B, 42)
+    envs = _late_roots(B, 8, seed=4, n_empty=5)
+    s = _same(net, envs, [200])
+    assert s['no_base'] > 0 and s['delta'] > 0, s
+    _, trees, _ = _search(net, envs, [200], True)
+    assert any(len(p) > 4 for t in trees for p in t)
+    assert not _over_budget_leaf(trees, B)
+
+
+@pytest.mark.gpu
+def test_select_first_zero():
+    """A search continued with select_first = 0 (the first leaf of the launch from rz_select_step through the engine's leaf arrays,
+    its windows built before the loop) equals the two-launch step run in the same chunks."""
+    B = 15
+    envs = _edge_roots(B, 16, seed=7) + _late_roots(B, 4, seed=8, n_empty=8)
+    s = _same(_net(B, 50), envs, [24, 16, 8], select_first_0=True)
+    assert s['delta'] > 0, s
