@@ -518,7 +518,8 @@ int rz_net_set_heads_algo(rz_net *net, int32_t heads_algo);
 int rz_net_create(int32_t height, int32_t width, int32_t n_actions, int32_t device, rz_net **out);
 int rz_net_destroy(rz_net *net);
 /* Uploads (and re-packs) the 16 tensors of PolicyValueNet.state_dict().  Later calls reuse the device
- * buffers of the first one, so launches captured in a hipGraph stay valid across weight updates. */
+ * buffers of the first one, so launches captured in a hipGraph stay valid across weight updates.  Every
+ * receptive-field base (rz_net_delta_bases) is invalidated: it was computed with the previous weights. */
 int rz_net_load(rz_net *net, const float *const *h_params, int32_t n_params);
 int rz_net_reserve(rz_net *net, int32_t max_boards);
 int rz_net_trunk(rz_net *net, const float *d_obs, int32_t n_boards, float *d_feat, void *stream);
@@ -549,7 +550,9 @@ int rz_net_trace_attach(rz_net *net, void *d_trace);   /* see rz_trace_attach */
  * arithmetic cell by cell, and takes every other cell from the base: THE SAME BITS as rz_net_trunk_leaves_deferred (the store slot
  * d_slot_of_board[b], the value rows of *out).  The cache validates itself: a leaf whose stones do not contain the cached root's, or
  * with more than four changed cells, or a game without bases, is evaluated by the same kernel without a base (four passes over
- * the board's quadrants) -- correct whatever the caller did, only slower; rebuild the bases whenever the roots move.
+ * the board's quadrants) -- correct whatever the caller did, only slower; rebuild the bases whenever the roots move.  The bases
+ * belong to the weights they were built with: rz_net_load invalidates every one of them, so after an upload a leaf takes the
+ * route without a base until rz_net_delta_bases runs again -- correct, only slower; rebuild them after every rz_net_load too.
  * Boards of 11 .. 16 rows and columns, RZ_NET_SPLIT_F16.  d_active (may be NULL): games whose flag is 0 are skipped.  d_feat32 (may be
  * NULL): also the features as f32 [n][6][S] (tests); d_slot_of_board may then be NULL (nothing goes to the store; out may be NULL).
  * without_base != 0: every leaf takes the four-pass route (a checker). */

@@ -3152,6 +3152,10 @@ int rz_net_load(rz_net *net, const float *const *h_params, int32_t n_params) {
             for (int k = 0; k < 2 * S; ++k) t[((size_t)(k / 4) * 64 + j) * 4 + k % 4] = h_params[12][(size_t)j * 2 * S + k];
         if (rc == RZ_OK) rc = net_upload(net, t, &net->d_w1t);
     }
+    // the receptive-field bases hold activations of the weights they were built with: none survives an upload (a leaf of a game
+    // without a valid base takes the route without one until rz_net_delta_bases runs again)
+    if (rc == RZ_OK && net->base_games > 0 && hipMemset(net->d_base_hdr, 0, (size_t)net->base_games * sizeof(dl::BaseHdr)) != hipSuccess)
+        rc = net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->loaded = rc == RZ_OK;
     return rc;
 }
@@ -3623,6 +3627,7 @@ int rz_net_delta_bases_engine(rz_net *net, rz_engine *engine, void *stream) {
     rzt::Dev dev;
     int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
     if (rc != RZ_OK) return rc;
+    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (dev.BH != net->dev.BH || dev.BW != net->dev.BW) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
     return rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream);
 }
@@ -3631,6 +3636,7 @@ int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *
     rzt::Dev dev;
     int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
     if (rc != RZ_OK) return rc;
+    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
     if (dev.K != 1 || dev.pend_cap <= 0 || dev.pend == nullptr)
         return net_fail(RZ_ERR_ARG, "rz_net_delta_step is the deferred-priors route: one simulation in flight, rz_deferred_reserve first");
@@ -3657,7 +3663,8 @@ int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream) {
     net->dev.feat_ld = 16 * (net->dev.groups_act + net->dev.groups_val);
     net->dev.feat_val_off = 16 * net->dev.groups_act;
     const DeferredOut later{nullptr, 0, nullptr, 0, nullptr, 0};
-    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, dev.active, nullptr, net->d_delta_stats, 0, (65536 + net->dev.BW - 1) / net->dev.BW};
+    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, dev.active ? dev.active : net->d_base_ones, nullptr, net->d_delta_stats, 0,
+                     (65536 + net->dev.BW - 1) / net->dev.BW};
     dl::k_trunk_delta<false><<<dim3((unsigned)dev.n_games), dim3(256), 0, (hipStream_t)stream>>>(
         net->dev, LeafBits{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last}, net->d_feat16, dev.n_games, later, da);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta failed");

@@ -94,6 +94,25 @@ PARAM_ORDER = ('conv1.weight', 'conv1.bias', 'conv2.weight', 'conv2.bias', 'conv
                'val_fc2.weight', 'val_fc2.bias')
 
 
+def param_shapes(rows, cols, n_actions):
+    """The shape of every tensor of PolicyValueNet(rows, cols, n_actions).state_dict(), in PARAM_ORDER."""
+    S = rows * cols
+    return ((32, 4, 3, 3), (32, ), (64, 32, 3, 3), (64, ), (128, 64, 3, 3), (128, ), (4, 128, 1, 1), (4, ),
+            (n_actions, 4 * S), (n_actions, ), (2, 128, 1, 1), (2, ), (64, 2 * S), (64, ), (1, 64), (1, ))
+
+
+def check_state_dict(state_dict, rows, cols, n_actions):
+    """Raise ValueError unless ``state_dict`` holds every tensor of PolicyValueNet(rows, cols, n_actions) with its shape: rz_net_load
+    reads the host arrays at the sizes of the net's own board."""
+    for name, want in zip(PARAM_ORDER, param_shapes(rows, cols, n_actions)):
+        if name not in state_dict:
+            raise ValueError('the state dict has no %r (a PolicyValueNet state dict holds %s)' % (name, ', '.join(PARAM_ORDER)))
+        got = tuple(int(v) for v in state_dict[name].shape)
+        if got != want:
+            raise ValueError('%r has shape %s, the net of a %d x %d board with %d actions needs %s'
+                             % (name, got, rows, cols, n_actions, want))
+
+
 
 def compact_grid_board(rows, cols):
     """The boards k_trunk_split has a compact LDS grid for (rz_net.hip: launch_trunk / rz_net_search_resident): N-tiles of
@@ -128,6 +147,7 @@ class HipNet(object):
         self.handle = handle
         self.max_boards = 0
         self._want = int(max_boards)
+        self.generation = 0   # weight uploads so far (load_state_dict): per-weights caches of a caller key on it
 
     def set_algo(self, algo):
         """conv2 / conv3 algorithm: 'split_f16' (default: direct convolution on the f16 matrix pipe, every f32
@@ -299,7 +319,9 @@ class HipNet(object):
 
     def load_state_dict(self, state_dict):
         """Upload (and re-pack into MFMA fragment order) the 16 tensors of a
-        PolicyValueNet.state_dict(); call again after every optimiser step."""
+        PolicyValueNet.state_dict(); call again after every optimiser step.  The receptive-field bases of the old weights are
+        dropped (rz_net_load): rebuild them (prepare_search does when ``generation`` moves)."""
+        check_state_dict(state_dict, self.rows, self.cols, self.n_actions)
         arrays = []
         for name in PARAM_ORDER:
             t = state_dict[name]
@@ -308,9 +330,15 @@ class HipNet(object):
             arrays.append(a)
         ptrs = (ctypes.c_void_p * 16)(*[a.ctypes.data for a in arrays])
         check(self.lib.rz_net_load(self.handle, ptrs, 16), 'rz_net_load')
+        self.generation += 1
         self.reserve(max(self._want, self.max_boards))
         self._split_ok = self.range_info()['split_ok']
         return self
+
+    def route_state(self):
+        """What the weights decide of an evaluator's route (split_ok: rz_net_load's activation bounds): a change moves the launches
+        a hipGraph captured to another route."""
+        return self.reads_positions(), self.supports_deferred(), self.supports_delta(), self.supports_resident()
 
     def reserve(self, max_boards):
         check(self.lib.rz_net_reserve(self.handle, int(max_boards)), 'rz_net_reserve')
@@ -407,7 +435,7 @@ class HipNetEvaluator(object):
         Cheap when nothing moved.  A missed call costs time only: a leaf whose base is stale takes the kernel's route without one."""
         if not self.delta_ok(eng) or eng.sims_in_flight != 1 or eng._capturing or not (self.deferred_ok(eng) or self.delta_three_launch_ok(eng)):
             return
-        key = (id(eng), eng.roots_epoch, id(eng.handle))
+        key = (id(eng), eng.roots_epoch, id(eng.handle), self.hip.generation)   # (bases of other roots or of other weights: rebuilt)
         if getattr(self, '_delta_key', None) == key:
             return
         if getattr(self.hip, '_delta_games', 0) < eng.n_games:
@@ -504,7 +532,12 @@ class HipNetEvaluator(object):
                 self.hip.torch.cuda.synchronize(self.hip.device)
                 eng.flush_deferred()
                 self.hip.torch.cuda.synchronize(self.hip.device)
+        before = self.hip.route_state() if hasattr(self.hip, '_split_ok') else None
         self.hip.load_state_dict(self.module.state_dict())
+        if before is not None and self.hip.route_state() != before:
+            # the weights moved the route (finite activation bounds or not): graphs captured on the old one must not be replayed
+            for eng in list(getattr(self, '_capturing_engines', ())):
+                eng._drop_graphs('the new weights changed the evaluation route')
         self._seen = self._fingerprint()
         self._seen_content = self._fingerprint(content=True)[1]
 
@@ -1029,7 +1062,20 @@ class MCTSEngine(object):
         finally:
             self._capturing = False
         self._graphs[key] = (graph, evaluator)
+        self._note_capture(evaluator)
         return graph
+
+    def _note_capture(self, evaluator):
+        """The evaluator (or the one it wraps) knows this engine holds graphs of it: a refresh that changes its route drops them."""
+        import weakref
+        inner = getattr(evaluator, 'inner', evaluator)
+        refs = getattr(inner, '_capturing_engines', None)
+        if refs is None:
+            try:
+                refs = inner._capturing_engines = weakref.WeakSet()
+            except AttributeError:   # (an evaluator without instance attributes has no route to change)
+                return
+        refs.add(self)
 
     # ------------------------------------------------------------------ read-out
     def root_visits(self):
@@ -1198,6 +1244,7 @@ class MCTSEngine(object):
             self._capturing = False
         self._move_graph_ev = evaluator
         self._move_graph = graph
+        self._note_capture(evaluator)
         return graph
 
     def play_move_replay(self, graph):

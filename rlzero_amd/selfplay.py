@@ -568,7 +568,9 @@ class BatchedSelfPlay(object):
 
     def warm_graphs(self):
         """Capture the simulation-chunk hipGraph of every lane (before any game is started: the capture
-        runs the chunk once).  Weight updates keep the graphs valid: rz_net_load reuses its device buffers."""
+        runs the chunk once).  Weight updates keep the graphs valid: rz_net_load reuses its device buffers.  Weights that change
+        the evaluation route (HipNetEvaluator.refresh: no finite activation bound, or finite again) drop them, and the lane's next
+        replay raises HipError instead of running the old route: call warm_graphs (or device_attach) again before the next run."""
         if not self.use_graph:
             return
         per = self.eng.graph_chunk(self.sims_per_graph)
@@ -579,7 +581,8 @@ class BatchedSelfPlay(object):
         self.torch.cuda.synchronize()
 
     def refresh_weights(self):
-        """Re-upload the network weights of every lane if the torch module changed (after a learner step)."""
+        """Re-upload the network weights of every lane if the torch module changed (after a learner step).  Captured graphs stay
+        valid unless the new weights change the evaluation route (see warm_graphs): they are then dropped, not captured again."""
         for lane in self.lanes:
             refresh = getattr(lane.evaluator, 'refresh_if_changed', None)
             if refresh is not None:

@@ -6,6 +6,8 @@ selection rule never reads (node.py:32-42,75-88) -- are written in one batch bef
 Pinned here: (1) the priors are, bit for bit, those of the route that writes them inside every tree step, the values agree with
 it to f32 rounding and with the reference's CPU outputs to 1e-4; (2) the trees are EXACTLY the oracle's when it is fed the values
 this route produces; (3) when the flushes happen -- store size, hipGraphs, tree reuse -- changes no bit."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -220,11 +222,35 @@ def test_an_evaluator_of_another_route_takes_over_cleanly():
     evaluator.refresh_if_changed()
     assert eng._def_pending == 0
     eng.sim_chunk(evaluator, 3)
+    # ... and the steps after the refresh are those of a fresh evaluator on the new weights, bit for bit (nothing the old weights
+    # derived -- the store, the roots' bases -- is used), and not those of the old weights
+    assert eng._def_pending == 3
+    got = _tree_bits(eng)   # (reading the trees writes the pending priors)
+
+    def twin(last):
+        other = MCTSEngine(B, n, n_games=4, n_playout=40, device='cuda:0')
+        old = HipNetEvaluator(_net(B, seed=3).to('cuda:0'), B, 'cuda:0', max_boards=4)
+        other.reset_games()
+        for ev_, k in ((old, 10), (SyntheticEvaluator('vlin'), 5), (old, 10)):
+            other.sim_chunk(ev_, k)
+        last = old if last is None else HipNetEvaluator(last, B, 'cuda:0', max_boards=4)
+        other.sim_chunk(last, 3)
+        out = _tree_bits(other)
+        other.close()
+        return out
+    assert got == twin(copy.deepcopy(net)) and got != twin(None)
+    eng.sim_chunk(evaluator, 1)   # (pending again: resetting the roots must write it)
+    assert eng._def_pending == 1
     eng.reset_games()
     assert eng._def_pending == 0
     eng.check()
     eng.close()
     evaluator.hip.close()
+
+
+def _tree_bits(eng):
+    """The root visits and root values as bytes, then every game's whole tree (_whole_tree)."""
+    return [eng.root_visits().tobytes(), eng.root_values().tobytes()] + [_whole_tree(eng, g) for g in range(eng.n_games)]
 
 
 def test_resident_search_is_the_two_launch_step_in_one_launch():

@@ -354,3 +354,24 @@ def test_fp8_model_rounds_to_the_ocp_grids():
     ah, al = m.split(a)
     wh, wl = m.split(w)
     assert float(((ah * wh + ah * wl + al * wh) - a.double() * w.double()).abs().max()) < 2.0 ** -21 * 16
+
+
+@pytest.mark.parametrize('shape', [(6, 6, 36), (15, 15, 225), (12, 16, 192), (6, 7, 7)])
+def test_state_dict_shapes_are_checked_before_an_upload(shape):
+    """HipNet.load_state_dict refuses, before rz_net_load reads the host arrays at its own board's sizes, a state dict of another
+    board or one missing a tensor; param_shapes is what PolicyValueNet itself holds."""
+    from rlzero_amd.engine import PARAM_ORDER, check_state_dict, param_shapes
+    from rlzero_amd.games.gomoku.policy_value_net import PolicyValueNet
+    rows, cols, acts = shape
+    sd = PolicyValueNet(rows, cols, acts).state_dict()
+    assert [tuple(sd[k].shape) for k in PARAM_ORDER] == list(param_shapes(rows, cols, acts))
+    check_state_dict(sd, rows, cols, acts)
+    check_state_dict({k: v.numpy() for k, v in sd.items()}, rows, cols, acts)   # (numpy arrays too)
+    with pytest.raises(ValueError, match='act_fc1.weight'):
+        check_state_dict(PolicyValueNet(9).state_dict(), rows, cols, acts)
+    with pytest.raises(ValueError, match='act_fc1.weight'):
+        check_state_dict(sd, rows, cols, acts + 1)
+    short = dict(sd)
+    del short['conv2.bias']
+    with pytest.raises(ValueError, match='conv2.bias'):
+        check_state_dict(short, rows, cols, acts)
