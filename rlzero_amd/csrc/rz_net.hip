@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -2942,6 +2943,39 @@ static void launch_search_rows(dim3 grid, hipStream_t stream, const NetDev &nd, 
     else k_trunk_rows_res<NT><<<grid, dim3(256), 0, stream>>>(nd, leaves, store, n_games, flags, later, res);
 }
 
+// f(std::integral_constant<int, rows>): the row-tile kernels are instantiated per board height (rows_kernel_covers)
+template <typename F>
+static void with_board_rows(int rows, F &&f) {
+    switch (rows) {
+        case 11: f(std::integral_constant<int, 11>{}); break;
+        case 12: f(std::integral_constant<int, 12>{}); break;
+        case 13: f(std::integral_constant<int, 13>{}); break;
+        case 14: f(std::integral_constant<int, 14>{}); break;
+        case 15: f(std::integral_constant<int, 15>{}); break;
+        default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
+// How k_trunk_split covers a board (trunk_class()).  ``ms``: waves that share an N-tile's output channels -- 4: one tile; 2: two tiles x two
+// channel halves; 3: 9x9, three tiles + the fourth wave on a quarter of conv3's channels; 1: four tiles, one per wave; 0: two tiles per wave.
+// ``compact``: at most two tiles that fit the 9 x 15 LDS grid (67-69 KB: two workgroups per CU), unless RZ_NET_COMPACT=0.
+struct TrunkClass { int ms; bool compact; };
+
+// THE launch of k_trunk_split: every instantiation is named here and nowhere else (RES: the resident search's, which has none for ms = 0).
+// ``compact``: the caller's decision, from TrunkClass::compact and its own run-time conditions.
+template <bool RES>
+static void launch_trunk_split(int ms, bool compact, dim3 grid, hipStream_t st, const NetDev &nd, const float *obs, LeafBits leaves, float *f32,
+                               _Float16 *f16, int n_boards, unsigned *flags, float *raw, float *hid, const DeferredOut &later, const ResArgs<RES> &res) {
+    const dim3 wg(256);
+    if (compact && ms == 4) k_trunk_split<1, 4, RES, 9, 15><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if (compact) k_trunk_split<1, 2, RES, 9, 15><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if (ms == 4) k_trunk_split<1, 4, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if (ms == 2) k_trunk_split<1, 2, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if (ms == 3) k_trunk_split<1, 3, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if (RES || ms == 1) k_trunk_split<1, 1, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
+    else if constexpr (!RES) k_trunk_split<2, 1, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, nullptr, nullptr, later, res);
+}
+
 extern "C" {
 
 int rz_net_create(int32_t height, int32_t width, int32_t n_actions, int32_t device, rz_net **out) {
@@ -3211,6 +3245,23 @@ int rz_net_reserve(rz_net *net, int32_t max_boards) {
 // 16 MFMA columns empty)
 static bool rows_kernel_covers(int bh, int bw) { return bh >= 11 && bh <= 16 && bw >= 11 && bw <= 16; }
 
+// The route -- which kernels evaluate a leaf -- as the library decides it for the net it holds: rows_kernel_covers() and the four functions
+// below.  rlzero_amd/route.py decides the same for the Python callers BEFORE they call: that module is the one other place that must agree
+// with these, and the RZ_ERR_ARG returns of the entry points are the backstop where the two disagree.
+static bool split_trunk_ok(const rz_net *net) {   // the split-f16 trunks (both kernels), finite activation bounds: positions, deferred priors
+    return (net->algo == RZ_NET_SPLIT_F16 || net->algo == RZ_NET_SPLIT_F16_TILES) && net->split_ok;
+}
+static bool delta_covers(const rz_net *net) {   // k_trunk_rows' boards, its arithmetic, positions: the receptive-field trunk
+    return split_trunk_ok(net) && net->algo == RZ_NET_SPLIT_F16 && !net->fp8_cross && rows_kernel_covers(net->dev.BH, net->dev.BW);
+}
+static bool compact_grid_covers(const rz_net *net, int tiles) {   // (route.py: compact_grid_board) at most 7 columns, tile rows + halo within 15
+    return net->compact_grid && tiles <= 2 && net->dev.BW <= 7 && tiles * net->dev.tile_rows + 2 <= 15;
+}
+static TrunkClass trunk_class(const rz_net *net) {
+    const int tiles = (net->dev.BH + net->dev.tile_rows - 1) / net->dev.tile_rows;
+    return TrunkClass{tiles <= 1 ? 4 : tiles <= 2 ? 2 : (tiles == 3 && net->dev.tile_rows == 3) ? 3 : tiles <= 4 ? 1 : 0, compact_grid_covers(net, tiles)};
+}
+
 static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t n_boards, void *stream,
                          LeafBits leaves = LeafBits{nullptr, nullptr, nullptr}, DeferredOut later = DeferredOut{nullptr, 0, nullptr, 0, nullptr}) {
     const dim3 grid((unsigned)n_boards);
@@ -3220,7 +3271,7 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
     // caller's buffer or when the f32 GEMM is forced
     // a net whose weights give no finite activation bound (rz_net_load) never runs on the f16 pipe
     const bool split_algo = net->algo == RZ_NET_SPLIT_F16 || net->algo == RZ_NET_SPLIT_F16_TILES;
-    const int algo = (split_algo && !net->split_ok) ? RZ_NET_DIRECT : (split_algo ? RZ_NET_SPLIT_F16 : net->algo);
+    const int algo = split_trunk_ok(net) ? RZ_NET_SPLIT_F16 : split_algo ? RZ_NET_DIRECT : net->algo;
     const bool split = algo == RZ_NET_SPLIT_F16;
     const bool want_f32 = !split || !internal || net->heads_algo == RZ_NET_HEADS_F32;
     if (internal) {
@@ -3240,7 +3291,7 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
         _Float16 *f16 = later.slot_of ? net->d_store16 : internal ? net->d_feat16 : nullptr;
         float *f32 = later.slot_of ? nullptr : want_f32 ? d_feat : nullptr;
         if (later.slot_of) net->feat16_valid = net->feat32_valid = false;   // (nothing for rz_net_heads_gemm)
-        const int tiles = (net->dev.BH + net->dev.tile_rows - 1) / net->dev.tile_rows;
+        const TrunkClass tc = trunk_class(net);
         const bool bits = leaves.stones != nullptr;
         // Small batches of small boards (every board has a workgroup of its own, nothing of another lane to overlap with): the
         // trunk's workgroups run the FC layers on their boards themselves -- no FC launch, no kernel boundary (same bits).
@@ -3248,7 +3299,7 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
         // boards): AUTO takes this route while the weights are at most 40 KB (6 x 6: 39 KB, TicTacToe one game +6 %, 16 games +3 %;
         // Connect4: 26 KB); at 9 x 9 (146 KB) the
         // launch it saves is cheaper than the stream it costs (64 games -5 %, profiles/r03/in_trunk_fc.txt)
-        const bool fc_here = !later.slot_of && internal && tiles <= 4 && net->dev.BH <= 10 && !rows_kernel_covers(net->dev.BH, net->dev.BW) &&
+        const bool fc_here = !later.slot_of && internal && tc.ms != 0 && net->dev.BH <= 10 && !rows_kernel_covers(net->dev.BH, net->dev.BW) &&
                              (net->heads_algo == RZ_NET_HEADS_IN_TRUNK ||
                               (net->heads_algo == RZ_NET_HEADS_AUTO && net->max_wgs == 0 && n_boards <= wg_cap &&
                                ((size_t)net->dev.A * 4 * net->dev.S + (size_t)64 * 2 * net->dev.S) * 4 <= 40 * 1024));
@@ -3256,31 +3307,17 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
         net->raw_from_trunk = fc_here;
         if (fc_here) net->feat16_valid = false;   // (the pieces stayed in LDS)
         if (net->algo == RZ_NET_SPLIT_F16 && rows_kernel_covers(net->dev.BH, net->dev.BW)) {   // wide boards: one N-tile per row
-            const hipStream_t st = (hipStream_t)stream;
             const bool fp8 = net->fp8_cross;   // (float planes in this mode were refused by the callers)
-            switch (net->dev.BH) {
-                case 11: launch_trunk_rows<11>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-                case 12: launch_trunk_rows<12>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-                case 13: launch_trunk_rows<13>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-                case 14: launch_trunk_rows<14>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-                case 15: launch_trunk_rows<15>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-                default: launch_trunk_rows<16>(bits, pgrid, st, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8); break;
-            }
-        } else if (tiles <= 2 && !fc_here && net->compact_grid && (2 * n_boards > wg_cap || net->compact_always) && net->dev.BW <= 7 && tiles * net->dev.tile_rows + 2 <= 15) {
-            // small boards, more boards than CUs: the compact LDS grid (9 x 15 positions, 67 KB): two workgroups per CU
+            with_board_rows(net->dev.BH, [&](auto nt) {
+                launch_trunk_rows<decltype(nt)::value>(bits, pgrid, (hipStream_t)stream, net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, later, fp8);
+            });
+        } else {
+            // small boards, more boards than half the CUs: the compact LDS grid, two workgroups per CU
+            const bool compact = tc.compact && !fc_here && (2 * n_boards > wg_cap || net->compact_always);
             const dim3 cgrid((unsigned)(n_boards < 2 * wg_cap ? n_boards : 2 * wg_cap));
-            if (tiles <= 1) k_trunk_split<1, 4, false, 9, 15><<<cgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, nullptr, nullptr, later);
-            else k_trunk_split<1, 2, false, 9, 15><<<cgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, nullptr, nullptr, later);
-        } else if (tiles <= 1)        // one tile: the four waves share the output channels
-            k_trunk_split<1, 4><<<pgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, raw, hid, later);
-        else if (tiles <= 2)   // two tiles x two channel halves
-            k_trunk_split<1, 2><<<pgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, raw, hid, later);
-        else if (tiles == 3 && net->dev.tile_rows == 3)   // 9x9: three tiles + the fourth wave on a quarter of conv3's channels
-            k_trunk_split<1, 3><<<pgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, raw, hid, later);
-        else if (tiles <= 4)   // four tiles cover the board: one per wave
-            k_trunk_split<1><<<pgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, raw, hid, later);
-        else
-            k_trunk_split<2><<<pgrid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, d_obs, leaves, f32, f16, n_boards, net->d_flags, nullptr, nullptr, later);
+            launch_trunk_split<false>(tc.ms, compact, compact ? cgrid : pgrid, (hipStream_t)stream, net->dev, d_obs, leaves, f32, f16, n_boards,
+                                      net->d_flags, raw, hid, later, ResArgs<false>{});
+        }
     }
     else
         k_trunk<<<grid, dim3(kTrunkThreads), 0, (hipStream_t)stream>>>(net->dev, d_obs, d_feat, n_boards);
@@ -3359,15 +3396,11 @@ int rz_net_trunk_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
     if (n_boards == 0) return RZ_OK;
     if (!d_stones || !d_to_move || !d_last_cell) return net_fail(RZ_ERR_ARG, "NULL device pointer");
     if (n_boards > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
-    if ((net->algo != RZ_NET_SPLIT_F16 && net->algo != RZ_NET_SPLIT_F16_TILES) || !net->split_ok)
+    if (!split_trunk_ok(net))
         return net_fail(RZ_ERR_ARG, "rz_net_trunk_leaves needs the RZ_NET_SPLIT_F16 trunk (the others read float planes: rz_net_trunk)");
     launch_trunk(net, nullptr, net->d_feat, n_boards, stream, LeafBits{d_stones, d_to_move, d_last_cell});
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_split failed");
     return RZ_OK;
-}
-
-static bool deferred_trunk_covers(const rz_net *net) {   // the split-f16 trunks (both kernels), fed positions
-    return (net->algo == RZ_NET_SPLIT_F16 || net->algo == RZ_NET_SPLIT_F16_TILES) && net->split_ok;
 }
 
 int rz_net_deferred_reserve(rz_net *net, int32_t max_boards, int32_t slots) {
@@ -3409,7 +3442,7 @@ int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const in
     int rc = net_ready(net, n_boards);
     if (rc != RZ_OK) return rc;
     if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
-    if (!deferred_trunk_covers(net))
+    if (!split_trunk_ok(net))
         return net_fail(RZ_ERR_ARG, "the deferred-priors route needs the RZ_NET_SPLIT_F16 trunk (a net with finite activation bounds)");
     if (n_boards > net->store_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
     if (n_boards > 0) {
@@ -3443,8 +3476,8 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         return net_fail(RZ_ERR_ARG, "rz_net_search_resident: more simulations than the store has slots", detail);
     }
     const bool rows = net->algo == RZ_NET_SPLIT_F16 && rows_kernel_covers(net->dev.BH, net->dev.BW);
-    const int tiles = (net->dev.BH + net->dev.tile_rows - 1) / net->dev.tile_rows;
-    if (!deferred_trunk_covers(net) || (!rows && (tiles > 4 || net->dev.BH > 10 || net->dev.BW > 10)))
+    const TrunkClass tc = trunk_class(net);
+    if (!split_trunk_ok(net) || (!rows && (tc.ms == 0 || net->dev.BH > 10 || net->dev.BW > 10)))
         return net_fail(RZ_ERR_ARG, "the resident search needs the RZ_NET_SPLIT_F16 trunk on a board of 11 .. 16 rows and columns (the row-tile "
                                     "kernel) or of up to 10 x 10 (k_trunk_split with one N-tile per wave)");
     if (dev.K != 1 || dev.score_mode != RZ_SCORE_UCT_REF || dev.pend_cap <= 0)
@@ -3452,12 +3485,13 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || dev.A != net->dev.A) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
     // receptive-field evaluation (rz_net_delta_reserve for this many games, the default trunk on a board of 11 .. 16 rows and columns):
     // k_delta_res, TWO workgroups per CU; rz_net_delta_resident(net, 0) keeps k_trunk_rows_res
-    const bool delta_res = net->delta_resident && rows && !net->fp8_cross && net->split_ok && net->base_games >= dev.n_games;
+    const bool delta_res = net->delta_resident && delta_covers(net) && net->base_games >= dev.n_games;
     // k_trunk_rows_res holds a CU (151 KB of LDS) for a whole search: at most one game per CU.  k_delta_res holds half a CU and its
     // workgroups depend on nothing outside their game: a batch beyond two per CU runs in ROUNDS, the dispatcher handing a CU's free half
     // to the next game of the grid as a search ends (1024 / 1536 games: two / three rounds of 512, the chip full throughout)
-    // (small boards on the compact LDS grid, launch_trunk's condition: 69 KB, two workgroups per CU -- the same freedom)
-    const bool compact_res = !rows && tiles <= 2 && net->compact_grid && net->dev.BW <= 7 && tiles * net->dev.tile_rows + 2 <= 15;
+    // (small boards on the compact LDS grid: 69 KB, two workgroups per CU -- the same freedom; and for fewer games too: the smaller grid
+    // is 1-2 % ahead even with ONE game on the chip, TicTacToe 93.3 -> 94.6 k)
+    const bool compact_res = !rows && tc.compact;
     if (dev.n_games > net->store_boards || (!delta_res && !compact_res && dev.n_games > net->n_cus))
         return net_fail(RZ_ERR_ARG, "the resident search runs one workgroup per game, at most one per CU (any number with rz_net_delta_reserve, or on a board of "
                                     "the compact grid) and rz_net_deferred_reserve()d");
@@ -3487,36 +3521,15 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (k_delta_res) failed");
         return RZ_OK;
     }
-    if (!rows) {   // (the launches of launch_trunk for these boards, RES instantiations)
-        _Float16 *store = net->d_store16;
-        const int ng = dev.n_games;
-        if (compact_res) {   // two games per CU -- and for fewer games too: the smaller grid is 1-2 % ahead even with ONE game on the chip (TicTacToe 93.3 -> 94.6 k)
-            if (tiles <= 1) k_trunk_split<1, 4, true, 9, 15><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-            else k_trunk_split<1, 2, true, 9, 15><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-            if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (compact grid) failed");
-            return RZ_OK;
-        }
-        if (tiles <= 1) k_trunk_split<1, 4, true><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-        else if (tiles <= 2) k_trunk_split<1, 2, true><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-        else if (tiles == 3 && net->dev.tile_rows == 3) k_trunk_split<1, 3, true><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-        else k_trunk_split<1, 1, true><<<grid, dim3(256), 0, st>>>(net->dev, nullptr, leaves, nullptr, store, ng, net->d_flags, nullptr, nullptr, later, res);
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search failed");
-        return RZ_OK;
-    }
-    switch (net->dev.BH) {
-        case 11: launch_search_rows<11>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-        case 12: launch_search_rows<12>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-        case 13: launch_search_rows<13>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-        case 14: launch_search_rows<14>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-        case 15: launch_search_rows<15>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-        default: launch_search_rows<16>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross); break;
-    }
+    if (rows)
+        with_board_rows(net->dev.BH, [&](auto nt) {
+            launch_search_rows<decltype(nt)::value>(grid, st, net->dev, leaves, net->d_store16, dev.n_games, net->d_flags, later, res, net->fp8_cross);
+        });
+    else   // (the launches of launch_trunk for these boards, RES instantiations)
+        launch_trunk_split<true>(tc.ms, compact_res, grid, st, net->dev, nullptr, leaves, nullptr, net->d_store16, dev.n_games, net->d_flags,
+                                 nullptr, nullptr, later, res);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search failed");
     return RZ_OK;
-}
-
-static bool delta_covers(const rz_net *net) {   // k_trunk_rows' boards, its arithmetic, positions
-    return net->algo == RZ_NET_SPLIT_F16 && !net->fp8_cross && net->split_ok && rows_kernel_covers(net->dev.BH, net->dev.BW);
 }
 
 int rz_net_delta_reserve(rz_net *net, int32_t n_games) {

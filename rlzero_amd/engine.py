@@ -12,12 +12,15 @@ One simulation step of all games = what the reference does once per game in
     rz_expand_backup    expand / terminal value + update_recursive
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
 
 from . import _hip
+from . import route as _route
 from ._hip import HipError, check
+from .route import compact_grid_board   # noqa: F401  (the board rules live in route.py; importable from here as before)
 
 WORDS = _hip.BOARD_WORDS
 
@@ -113,22 +116,14 @@ def check_state_dict(state_dict, rows, cols, n_actions):
                              % (name, got, rows, cols, n_actions, want))
 
 
-
-def compact_grid_board(rows, cols):
-    """The boards k_trunk_split has a compact LDS grid for (rz_net.hip: launch_trunk / rz_net_search_resident): N-tiles of
-    min(32 // cols, 16) rows, at most two of them, at most 7 columns, tile rows + the halo inside 15 grid rows."""
-    if os.environ.get('RZ_NET_COMPACT', '1') == '0' or cols > 7 or cols < 1:
-        return False
-    tile_rows = min(32 // cols, 16)
-    tiles = (rows + tile_rows - 1) // tile_rows
-    return tiles <= 2 and tiles * tile_rows + 2 <= 15
-
-
 class HipNet(object):
     """The hand-written fused fp32-MFMA forward (csrc/rz_net.hip) of a PolicyValueNet."""
 
     def __init__(self, board_size, device='cuda:0', max_boards=512):
         import torch
+        self.handle = None
+        # what the route depends on (route(): set_algo / set_heads_algo / load_state_dict move them) and what was reserved so far
+        self.algo, self.heads_algo, self._split_ok, self._store, self._delta_games = 'split_f16', 'auto', True, (0, 0), 0
         self.lib = _hip.load()
         self.torch = torch
         dev = torch.device(device)
@@ -141,6 +136,7 @@ class HipNet(object):
             self.rows = self.cols = int(board_size)
             self.n_actions = self.rows * self.cols
         self.board_size, self.n_cells = board_size, self.rows * self.cols
+        self.n_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         handle = ctypes.c_void_p()
         check(self.lib.rz_net_create(self.rows, self.cols, self.n_actions, self.device.index,
                                      ctypes.byref(handle)), 'rz_net_create')
@@ -162,10 +158,13 @@ class HipNet(object):
         self.algo = algo
         return self
 
+    def route(self, **how):
+        """route.decide() for this net: ``how`` holds the evaluator's and the engine's side (default: whatever serves the net best)."""
+        return _route.decide(self.rows, self.cols, self.algo, self._split_ok, self.heads_algo, **how)
+
     def reads_positions(self):
-        """True when the trunk can be fed the engine's leaf bitboards (rz_net_trunk_leaves): the 'split_f16' trunk of a
-        net with finite activation bounds.  The tree kernels then write no observation planes at all."""
-        return getattr(self, 'algo', 'split_f16') in ('split_f16', 'split_f16_tiles', 'split_f16_fp8') and getattr(self, '_split_ok', True)
+        """True when the trunk can be fed the engine's leaf bitboards (rz_net_trunk_leaves): the tree kernels then write no planes."""
+        return not self.route(environ={}).needs_planes
 
     def trunk_leaves(self, eng):
         """The trunk on the engine's current leaves, read as bitboards (no float planes), into the internal buffer."""
@@ -177,9 +176,8 @@ class HipNet(object):
 
     # -- deferred priors (include/rlzero_hip.h: rz_value_head) -------------------------------------------------
     def supports_deferred(self):
-        """True when this net's trunk can leave the policy features in a store and hand the tree step the value head's inputs
-        (rz_net_trunk_leaves_deferred): the 'split_f16' trunks, every board size."""
-        return getattr(self, 'algo', 'split_f16') in ('split_f16', 'split_f16_tiles', 'split_f16_fp8') and getattr(self, '_split_ok', True)
+        """True when this net's trunk can leave the policy features in a store (rz_net_trunk_leaves_deferred): every board size."""
+        return self.route(environ={}).deferred
 
     def deferred_bytes_per_slot(self, n_boards):
         """Device bytes one store slot (one simulation step of ``n_boards`` leaves) takes: f16 feature pieces + logits."""
@@ -191,7 +189,7 @@ class HipNet(object):
     def deferred_reserve(self, n_boards, slots):
         """-> True when the store was (re)allocated (rz_net_deferred_reserve grows it when either number exceeds what it holds): device
         addresses captured in hipGraphs before that are stale."""
-        have = getattr(self, '_store', (0, 0))
+        have = self._store
         check(self.lib.rz_net_deferred_reserve(self.handle, int(n_boards), int(slots)), 'rz_net_deferred_reserve')
         moved = int(n_boards) > have[0] or int(slots) > have[1]
         if moved:
@@ -210,12 +208,11 @@ class HipNet(object):
     # -- receptive-field leaf evaluation (include/rlzero_hip.h: rz_net_delta_*) ------------------------------------
     def supports_delta(self):
         """True when leaves can be evaluated against cached bases of the root (boards of 11 .. 16 rows and columns, 'split_f16')."""
-        return (getattr(self, 'algo', 'split_f16') == 'split_f16' and getattr(self, '_split_ok', True)
-                and 11 <= self.rows <= 16 and 11 <= self.cols <= 16)
+        return self.route(environ={}).delta
 
     def delta_reserve(self, n_games):
         check(self.lib.rz_net_delta_reserve(self.handle, int(n_games)), 'rz_net_delta_reserve')
-        self._delta_games = max(getattr(self, '_delta_games', 0), int(n_games))
+        self._delta_games = max(self._delta_games, int(n_games))
 
     def delta_invalidate(self):
         check(self.lib.rz_net_delta_invalidate(self.handle, self._stream()), 'rz_net_delta_invalidate')
@@ -255,16 +252,13 @@ class HipNet(object):
                 'resident_sclk_ghz': ghz}
 
     def compact_resident(self):
-        """Boards whose resident search runs on the COMPACT LDS grid (k_trunk_split<.., RES, 9, 15>: 69 KB, TWO games per CU and any
-        number of games per launch): rz_net_search_resident's rule -- at most two N-tiles, at most 7 columns, tile rows + halo within 15
-        (3x3 .. 7x7, Connect4's 6x7); RZ_NET_COMPACT=0 switches the grid off."""
-        return compact_grid_board(self.rows, self.cols) and self.supports_resident()
+        """True when the resident search runs on the COMPACT LDS grid (k_trunk_split<.., RES, 9, 15>: 69 KB, TWO games per CU and any
+        number of games per launch): 3x3 .. 7x7, Connect4's 6x7 (route.compact_grid_board); RZ_NET_COMPACT=0 switches the grid off."""
+        return self.route().compact_resident
 
     def supports_resident(self):
         """True when whole searches can run as ONE launch, one workgroup per game (rz_net_search_resident)."""
-        if getattr(self, 'algo', 'split_f16') not in ('split_f16', 'split_f16_fp8') or not getattr(self, '_split_ok', True):
-            return False
-        return (11 <= self.rows <= 16 and 11 <= self.cols <= 16) or (self.rows <= 10 and self.cols <= 10)
+        return self.route(environ={}).resident
 
     def search_resident(self, eng, n_sims, select_first=False):
         """``n_sims`` simulations of every active game of ``eng`` in one launch; the first leaves come from rz_select_step before
@@ -338,7 +332,8 @@ class HipNet(object):
     def route_state(self):
         """What the weights decide of an evaluator's route (split_ok: rz_net_load's activation bounds): a change moves the launches
         a hipGraph captured to another route."""
-        return self.reads_positions(), self.supports_deferred(), self.supports_delta(), self.supports_resident()
+        r = self.route(environ={})
+        return not r.needs_planes, r.deferred, r.delta, r.resident
 
     def reserve(self, max_boards):
         check(self.lib.rz_net_reserve(self.handle, int(max_boards)), 'rz_net_reserve')
@@ -389,7 +384,7 @@ class HipNet(object):
         return feat
 
     def close(self):
-        if getattr(self, 'handle', None):
+        if self.handle:
             self.lib.rz_net_destroy(self.handle)
             self.handle = None
 
@@ -407,102 +402,107 @@ class HipNetEvaluator(object):
     trunk reads the leaf POSITIONS (the engine's bitboards) and ``needs_obs`` is False: no observation planes are
     written or read; the f32 trunks and the un-fused ``__call__`` route take the float planes."""
     fused_heads = True
-    # Deferred priors (RZ_SCORE_UCT_REF, one simulation in flight, boards of 11 .. 16 rows): a simulation step is trunk ->
-    # tree step; the policy half of the evaluation and the priors of the expanded nodes are written in one batch before
-    # anything reads them (MCTSEngine.flush_deferred).  False: the three-launch route (trunk -> FC GEMM -> tree step).
+    # The three switches of the route (plain attributes: callers assign them; WHERE each route exists is route.decide()'s to say).
+    # Deferred priors: a simulation step is trunk -> tree step; the policy half of the evaluation and the priors of the expanded nodes
+    # are written in one batch before anything reads them (MCTSEngine.flush_deferred).  False: trunk -> FC GEMM -> tree step.
     deferred_priors = True
+    # Receptive-field leaf evaluation (csrc/rz_delta.h): the trunk recomputes only the windows around the stones a leaf adds to its
+    # search's root, on top of activations of the root cached once per move ("bases") -- the same bits as the full kernel.
+    # RZ_NET_DELTA=0 (or delta_trunk = False): the full kernel on every leaf.
+    delta_trunk = True
+    # The resident search: for a batch of at most one game per CU the simulations of a search run as ONE launch, one workgroup per
+    # game (trunk -> value head -> expand / backup -> selection, no kernel boundary; the deferred route's trees, values and priors).
+    # With the receptive-field trunk (k_delta_res) or the compact-grid kernel a CU holds TWO games and a launch takes any number of
+    # them: beyond two per CU it runs in rounds; plan_lanes says when that pays.  RZ_NET_DELTA_RESIDENT=0: never k_delta_res.
+    resident_search = True
 
+    def route(self, eng):
+        """How ``eng``'s leaves are evaluated with this evaluator -> route.Route (route.decide: the one place that knows the rule)."""
+        hip = self.hip   # (positional: this runs once or twice per search, next to a dozen host calls of a third of a millisecond's move)
+        return _route.decide(hip.rows, hip.cols, hip.algo, hip._split_ok, hip.heads_algo, self.use_positions, self.deferred_priors, self.delta_trunk,
+                             self.resident_search, eng.score_mode, eng.sims_in_flight, eng.n_games, hip.n_cus, eng.rows == hip.rows and eng.cols == hip.cols)
+
+    # -- views of the route (route.Route says what each means) ---------------------------------------------------------------------
     @property
     def needs_obs(self):
-        return not (self.use_positions and self.hip.reads_positions())
+        return self.hip.route(use_positions=self.use_positions).needs_planes
 
     def deferred_ok(self, eng):
         """Whether ``eng``'s simulation steps take the deferred-priors route with this evaluator."""
-        return (self.deferred_priors and self.use_positions and eng.score_mode == _hip.SCORE_UCT_REF and eng.sims_in_flight == 1
-                and self.hip.supports_deferred())
-
-    # Receptive-field leaf evaluation (csrc/rz_delta.h): on boards of 11 .. 16 rows and columns the deferred route's trunk recomputes only
-    # the windows around the stones a leaf adds to its search's root, on top of activations of the root cached once per move
-    # ("bases") -- the same bits as the full kernel.  RZ_NET_DELTA=0 (or delta_trunk = False): the full kernel on every leaf.
-    delta_trunk = True
+        return self.route(eng).deferred
 
     def delta_ok(self, eng):
-        return (self.delta_trunk and os.environ.get('RZ_NET_DELTA', '1') != '0' and self.hip.supports_delta()
-                and eng.rows == self.hip.rows and eng.cols == self.hip.cols)
+        return self.route(eng).delta
 
-    def prepare_search(self, eng):
-        """Before the steps of a search of ``eng``: the bases of its CURRENT roots (the engine counts what moves them: roots_epoch).
-        Cheap when nothing moved.  A missed call costs time only: a leaf whose base is stale takes the kernel's route without one."""
-        if not self.delta_ok(eng) or eng.sims_in_flight != 1 or eng._capturing or not (self.deferred_ok(eng) or self.delta_three_launch_ok(eng)):
-            return
-        key = (id(eng), eng.roots_epoch, id(eng.handle), self.hip.generation)   # (bases of other roots or of other weights: rebuilt)
-        if getattr(self, '_delta_key', None) == key:
-            return
-        if getattr(self.hip, '_delta_games', 0) < eng.n_games:
+    def resident_delta_ok(self, eng):
+        return self.route(eng).resident_delta
+
+    def resident_ok(self, eng):
+        return self.route(eng).resident
+
+    def resident_per_cu(self, eng):
+        return self.route(eng).resident_per_cu
+
+    def delta_three_launch_ok(self, eng):
+        return self.route(eng).delta_three_launch
+
+    def reserve_bases(self, eng):
+        """Room in the receptive-field base cache for every game of ``eng``.  Growing it moves the cache: the device is synchronised
+        first and the engine's graphs, which hold the old addresses, are dropped."""
+        if self.hip._delta_games < eng.n_games:
             self.hip.torch.cuda.synchronize(self.hip.device)
             self.hip.delta_reserve(eng.n_games)
             eng._drop_graphs('rz_net_delta_reserve moved the base cache')
+
+    def prepare_search(self, eng, r=None):
+        """Before the steps of a search of ``eng``: the bases of its CURRENT roots (the engine counts what moves them: roots_epoch).
+        Cheap when nothing moved.  A missed call costs time only: a leaf whose base is stale takes the kernel's route without one."""
+        r = self.route(eng) if r is None else r
+        if not r.delta or eng.sims_in_flight != 1 or eng._capturing or not (r.deferred or r.delta_three_launch):
+            return
+        key = (id(eng), eng.roots_epoch, id(eng.handle), self.hip.generation)   # (bases of other roots or of other weights: rebuilt)
+        if self._delta_key == key:
+            return
+        self.reserve_bases(eng)
         self.hip.delta_bases_engine(eng)
         self._delta_key = key
 
     def deferred_trunk(self, eng):
-        if self.delta_ok(eng):
-            self.prepare_search(eng)   # (nothing while a graph is captured: the eager warm-up steps before a capture reserve the cache)
-            if getattr(self.hip, '_delta_games', 0) >= eng.n_games:
+        r = self.route(eng)
+        if r.delta:
+            self.prepare_search(eng, r)   # (nothing while a graph is captured: the eager warm-up steps before a capture reserve the cache)
+            if self.hip._delta_games >= eng.n_games:
                 return self.hip.delta_step(eng)
         return self.hip.trunk_leaves_deferred(eng)
 
-    # The resident search: for a batch of at most one game per CU the simulations of a search run as ONE launch, one workgroup per
-    # game (trunk -> value head -> expand / backup -> selection, no kernel boundary; the deferred route's trees, values and priors).
-    resident_search = True
-
-    def resident_delta_ok(self, eng):
-        """The resident search with the receptive-field trunk (k_delta_res): TWO games per CU.  RZ_NET_DELTA_RESIDENT=0: never."""
-        return self.delta_ok(eng) and os.environ.get('RZ_NET_DELTA_RESIDENT', '1') != '0'
-
-    def resident_ok(self, eng):
-        n_cus = self.hip.torch.cuda.get_device_properties(self.hip.device).multi_processor_count
-        # (k_delta_res takes any number of games: beyond two per CU the launch runs in rounds; plan_lanes says when that pays)
-        return (self.resident_search and self.deferred_ok(eng) and self.hip.supports_resident()
-                and (self.resident_per_cu(eng) >= 2 or eng.n_games <= n_cus))
-
-    def resident_per_cu(self, eng):
-        """Resident workgroups a CU holds: two of k_delta_res (boards of 11 .. 16 rows and columns) and of the compact-grid kernel (boards
-        of up to 7 columns), one otherwise.  With two, a launch takes ANY number of games: beyond 2 x CUs it runs in rounds."""
-        return 2 if (self.resident_delta_ok(eng) or (self.hip.compact_resident() and eng.rows == self.hip.rows and eng.cols == self.hip.cols)) else 1
-
     def search_resident(self, eng, n_sims, select_first=False):
-        want = self.resident_delta_ok(eng)
-        if getattr(self, '_delta_res_set', None) != want:
+        want = self.route(eng).resident_delta
+        if self._delta_res_set != want:
             check(self.hip.lib.rz_net_delta_resident(self.hip.handle, 1 if want else 0), 'rz_net_delta_resident')
             self._delta_res_set = want
-        if want and getattr(self.hip, '_delta_games', 0) < eng.n_games and not eng._capturing:
-            self.hip.torch.cuda.synchronize(self.hip.device)
-            self.hip.delta_reserve(eng.n_games)   # (the library then runs k_delta_res and builds the roots' bases itself)
-            eng._drop_graphs('rz_net_delta_reserve moved the base cache')
+        if want and not eng._capturing:
+            self.reserve_bases(eng)   # (the library then runs k_delta_res and builds the roots' bases itself)
         self.hip.search_resident(eng, n_sims, select_first)
 
-    def delta_three_launch_ok(self, eng):
-        """The three-launch step (trunk -> FC GEMM -> tree step: the PUCT rule, or deferred_priors = False) with the receptive-field
-        trunk: positions, one simulation in flight per tree, the f16 FC GEMM."""
-        return (self.delta_ok(eng) and not self.needs_obs and eng.sims_in_flight == 1 and not self.deferred_ok(eng)
-                and getattr(self.hip, 'heads_algo', 'auto') != 'f32')
-
     def raw_heads(self, eng):
-        if not self.needs_obs:
-            if self.delta_three_launch_ok(eng):
-                self.prepare_search(eng)   # (nothing while a graph is captured: the eager steps before a capture reserve the cache)
-                if getattr(self.hip, '_delta_games', 0) >= eng.n_games:
-                    self.hip.delta_trunk_engine(eng)
-                    return self.hip.heads_gemm(eng.n_leaves)
-            self.hip.trunk_leaves(eng)
-        else:
+        """The three-launch step (trunk -> FC GEMM -> tree step: the PUCT rule, or deferred_priors = False); on positions, one
+        simulation in flight per tree and the f16 FC GEMM the trunk is the receptive-field one."""
+        r = self.route(eng)
+        if r.needs_planes:
             self.hip.trunk_internal(eng.obs)
+            return self.hip.heads_gemm(eng.n_leaves)
+        if r.delta_three_launch:
+            self.prepare_search(eng, r)   # (nothing while a graph is captured: the eager steps before a capture reserve the cache)
+            if self.hip._delta_games >= eng.n_games:
+                self.hip.delta_trunk_engine(eng)
+                return self.hip.heads_gemm(eng.n_leaves)
+        self.hip.trunk_leaves(eng)
         return self.hip.heads_gemm(eng.n_leaves)
 
     def __init__(self, net_module, board_size, device='cuda:0', max_boards=512, use_positions=True):
         self.module = net_module
         self.use_positions = bool(use_positions)
+        self._delta_key = self._delta_res_set = None   # the roots / weights the bases were built for; what rz_net_delta_resident was told
         self.hip = HipNet(board_size, device, max_boards)
         self.refresh()
 
@@ -532,7 +532,7 @@ class HipNetEvaluator(object):
                 self.hip.torch.cuda.synchronize(self.hip.device)
                 eng.flush_deferred()
                 self.hip.torch.cuda.synchronize(self.hip.device)
-        before = self.hip.route_state() if hasattr(self.hip, '_split_ok') else None
+        before = self.hip.route_state() if self.hip.generation else None   # (nothing to compare with before the first upload)
         self.hip.load_state_dict(self.module.state_dict())
         if before is not None and self.hip.route_state() != before:
             # the weights moved the route (finite activation bounds or not): graphs captured on the old one must not be replayed
@@ -804,13 +804,28 @@ class MCTSEngine(object):
         return self.obs
 
     # ------------------------------------------------------------------ the hot loop
+    def _ask(self, evaluator):
+        """-> (route.Route of this engine's searches with ``evaluator``, its owner or None, what to call before a search).  The ONLY place
+        that duck-types an evaluator: ours (HipNetEvaluator), or a wrapper that holds one as ``.inner`` (bench.py's), owns a route();
+        anything else -- synthetic, rollout, host, torch-module evaluators, a test's stub -- answers for itself where it defines
+        ``needs_obs`` / ``deferred_ok`` / ``resident_ok`` / ``resident_per_cu`` / ``prepare_search`` and takes the plain route where not."""
+        owner = getattr(evaluator, 'inner', evaluator)
+        if hasattr(owner, 'route'):
+            r = owner.route(self)
+            return r, owner, functools.partial(owner.prepare_search, self, r)
+        ask = lambda name, default: getattr(evaluator, name, lambda eng: default)(self)   # noqa: E731
+        r = _route.Route(needs_planes=bool(getattr(evaluator, 'needs_obs', True)), deferred=bool(ask('deferred_ok', False)), delta=False,
+                         delta_three_launch=False, resident=bool(ask('resident_ok', False)), resident_delta=False, compact_resident=False,
+                         resident_per_cu=ask('resident_per_cu', 1))
+        return r, None, functools.partial(ask, 'prepare_search', None)
+
     def sim_step(self, evaluator):
         """One simulation for every active game (enqueued, not synchronised)."""
-        ok = getattr(evaluator, 'deferred_ok', None)
-        if self.sims_in_flight > 1 or (ok is not None and ok(self)):
-            return self.sim_chunk(evaluator, 1)   # (the deferred route's store bookkeeping lives there)
+        r = self._ask(evaluator)[0]
+        if self.sims_in_flight > 1 or r.deferred:
+            return self.sim_chunk(evaluator, 1, r)   # (the deferred route's store bookkeeping lives there)
         self.flush_deferred()
-        obs = _ptr(self.obs) if getattr(evaluator, 'needs_obs', True) else None
+        obs = _ptr(self.obs) if r.needs_planes else None
         check(self.lib.rz_select_step(self.handle, obs, self.stream()), 'rz_select_step')
         logp, value = evaluator(self)
         if getattr(evaluator, 'returns_probs', False):
@@ -826,16 +841,16 @@ class MCTSEngine(object):
     def _in_flight(self, k_backup, k_select):
         check(self.lib.rz_set_in_flight(self.handle, int(k_backup), int(k_select)), 'rz_set_in_flight')
 
-    def sim_chunk(self, evaluator, n):
+    def sim_chunk(self, evaluator, n, r=None):
         """``n`` simulations of every active game: select, (evaluate, expand+backup+select) x
         (n-1), evaluate, expand+backup -- consecutive simulations share one tree launch.
-        With ``sims_in_flight`` = K > 1: ceil(n / K) steps of K simulations each (the last one with the remainder)."""
+        With ``sims_in_flight`` = K > 1: ceil(n / K) steps of K simulations each (the last one with the remainder).
+        ``r``: the route, when the caller has asked for it already."""
         if n <= 0:
             return
         K = self.sims_in_flight
-        ok = getattr(evaluator, 'deferred_ok', None)
-        deferred = ok is not None and ok(self)
-        if not deferred:
+        r = self._ask(evaluator)[0] if r is None else r
+        if not r.deferred:
             self.flush_deferred()   # (an evaluator of another route takes over: its expansions write their priors at once)
         if isinstance(evaluator, HostEvaluator):
             if K > 1:
@@ -850,9 +865,9 @@ class MCTSEngine(object):
         begin = getattr(evaluator, 'begin_chunk', None)  # optional evaluator hook (bench.py's timing wrapper)
         if begin is not None:
             begin()
-        if deferred:
-            return self._sim_chunk_deferred(evaluator, n)
-        obs = _ptr(self.obs) if getattr(evaluator, 'needs_obs', True) else None
+        if r.deferred:
+            return self._sim_chunk_deferred(evaluator, n, r.resident)
+        obs = _ptr(self.obs) if r.needs_planes else None
         steps = -(-n // K)
         counts = [min(K, n - i * K) for i in range(steps)] + [0]  # slots in flight in step i
         if K > 1:
@@ -940,28 +955,22 @@ class MCTSEngine(object):
             self._move_graph = None   # (warm_move_graph's whole-move graph bakes the same addresses in)
             self._graphs_dropped = why
 
-    def _sim_chunk_deferred(self, evaluator, n):
+    def _sim_chunk_deferred(self, evaluator, n, resident):
         """sim_chunk on the deferred-priors route: per step the trunk (policy features into the step's store slot, value inputs
-        on) and ONE tree launch (value head, backup, next selection)."""
+        on) and ONE tree launch (value head, backup, next selection) -- or, ``resident``, one launch for all of them."""
         lib, h = self.lib, self.handle
-        res_ok = getattr(evaluator, 'resident_ok', None)
-        resident = res_ok is not None and res_ok(self)
         while n > 0:
             m = self._deferred_begin(evaluator, n)
             if resident:   # the m simulations in ONE launch, one workgroup per game, the first selection included
                 evaluator.search_resident(self, m, True)
-                if not self._capturing:
-                    self._def_pending += m
-                    self._def_stream = self.torch.cuda.current_stream(self.device)
-                n -= m
-                continue
-            check(lib.rz_select_step(h, None, self.stream()), 'rz_select_step')
-            for i in range(m):
-                head = evaluator.deferred_trunk(self)
-                if i + 1 < m:
-                    check(lib.rz_tree_step_deferred(h, ctypes.byref(head), self.stream()), 'rz_tree_step_deferred')
-                else:
-                    check(lib.rz_expand_backup_deferred(h, ctypes.byref(head), self.stream()), 'rz_expand_backup_deferred')
+            else:
+                check(lib.rz_select_step(h, None, self.stream()), 'rz_select_step')
+                for i in range(m):
+                    head = evaluator.deferred_trunk(self)
+                    if i + 1 < m:
+                        check(lib.rz_tree_step_deferred(h, ctypes.byref(head), self.stream()), 'rz_tree_step_deferred')
+                    else:
+                        check(lib.rz_expand_backup_deferred(h, ctypes.byref(head), self.stream()), 'rz_expand_backup_deferred')
             if not self._capturing:
                 self._def_pending += m
                 self._def_stream = self.torch.cuda.current_stream(self.device)
@@ -1006,16 +1015,11 @@ class MCTSEngine(object):
         use_graph: replay a hipGraph holding ``sims_per_graph`` simulations (captured by
         ``warm_graph``) instead of launching kernel by kernel; device-side evaluators only."""
         n = self.n_playout if n_sims is None else int(n_sims)
-        prep = getattr(evaluator, 'prepare_search', None) or getattr(getattr(evaluator, 'inner', None), 'prepare_search', None)
-        if prep is not None:
-            prep(self)   # (per-root work of the evaluator: a graph replay calls nothing of it)
-        res_ok = getattr(evaluator, 'resident_ok', None)
-        if not use_graph or isinstance(evaluator, HostEvaluator) or (res_ok is not None and res_ok(self)):
-            self.sim_chunk(evaluator, n)   # (the resident search is two launches for the whole search: nothing to capture)
-            return
+        r, _, prepare = self._ask(evaluator)
+        prepare()   # (per-root work of the evaluator: a graph replay calls nothing of it)
         per = self._whole_steps(sims_per_graph)
-        if per > n:
-            self.sim_chunk(evaluator, n)
+        if not use_graph or isinstance(evaluator, HostEvaluator) or r.resident or per > n:
+            self.sim_chunk(evaluator, n, r)   # (the resident search is two launches for the whole search: nothing to capture)
             return
         key = (id(evaluator), per)
         if key not in self._graphs:
@@ -1023,16 +1027,14 @@ class MCTSEngine(object):
             raise HipError('call warm_graph(evaluator, %d) before simulate(use_graph=True)%s' % (per, ' (the graphs were dropped: %s)' % why if why else ''))
         graph = self._graphs[key][0]
         full, rest = divmod(n, per)
-        ok = getattr(evaluator, 'deferred_ok', None)
-        deferred = ok is not None and ok(self)
         for _ in range(full):
-            if deferred:   # the replay writes `per` more slots of the store
+            if r.deferred:   # the replay writes `per` more slots of the store
                 if self._deferred_begin(evaluator, per) < per:
                     raise HipError('the deferred-priors store (%d slots) is smaller than a graph of %d steps' % (self._def_slots, per))
                 self._def_pending += per
                 self._def_stream = self.torch.cuda.current_stream(self.device)
             graph.replay()
-        self.sim_chunk(evaluator, rest)
+        self.sim_chunk(evaluator, rest, r)
 
     def warm_graph(self, evaluator, per):
         """Capture ``per`` simulations into a hipGraph (torch.cuda.CUDAGraph around our launches
@@ -1043,8 +1045,8 @@ class MCTSEngine(object):
         key = (id(evaluator), per)
         if key in self._graphs:
             return self._graphs[key][0]
-        res_ok = getattr(evaluator, 'resident_ok', None)
-        if res_ok is not None and res_ok(self):
+        r, owner, _ = self._ask(evaluator)
+        if r.resident:
             return None   # (the resident search is one launch per search: simulate() replays no graph for it)
         cur = t.cuda.current_stream(self.device)
         side = t.cuda.Stream(device=self.device)
@@ -1062,13 +1064,12 @@ class MCTSEngine(object):
         finally:
             self._capturing = False
         self._graphs[key] = (graph, evaluator)
-        self._note_capture(evaluator)
+        self._note_capture(owner or evaluator)
         return graph
 
-    def _note_capture(self, evaluator):
-        """The evaluator (or the one it wraps) knows this engine holds graphs of it: a refresh that changes its route drops them."""
+    def _note_capture(self, inner):
+        """The evaluator (the one a wrapper holds) knows this engine holds graphs of it: a refresh that changes its route drops them."""
         import weakref
-        inner = getattr(evaluator, 'inner', evaluator)
         refs = getattr(inner, '_capturing_engines', None)
         if refs is None:
             try:
@@ -1217,17 +1218,15 @@ class MCTSEngine(object):
         refill of slots -- replayed once per move (play_move_replay), the log row taken from the device's own step counter.  None
         when the route or the store (fewer than n_playout slots) does not allow it."""
         t = self.torch
-        res_ok = getattr(evaluator, 'resident_ok', None)
-        if res_ok is None or not res_ok(self) or getattr(self, 'play_log', None) is None:
+        r, owner, _ = self._ask(evaluator)
+        if not r.resident or getattr(self, 'play_log', None) is None:
             return None
         n = self.n_playout
         self.flush_deferred()
         if self._deferred_begin(evaluator, n) < n or self._def_slots < n:   # (reserves the store; a search must fit between two flushes)
             return None
-        inner = getattr(evaluator, 'inner', evaluator)
-        if getattr(inner, 'resident_delta_ok', None) is not None and inner.resident_delta_ok(self) and getattr(inner.hip, '_delta_games', 0) < self.n_games:
-            t.cuda.synchronize(self.device)
-            inner.hip.delta_reserve(self.n_games)   # (before the capture: the base cache of the receptive-field trunk)
+        if r.resident_delta:
+            owner.reserve_bases(self)   # (before the capture: the base cache of the receptive-field trunk; chunk graphs of the old one go)
         hip, lib, h = evaluator.hip, self.lib, self.handle
         t.cuda.synchronize(self.device)
         graph = t.cuda.CUDAGraph()
@@ -1244,7 +1243,7 @@ class MCTSEngine(object):
             self._capturing = False
         self._move_graph_ev = evaluator
         self._move_graph = graph
-        self._note_capture(evaluator)
+        self._note_capture(owner or evaluator)
         return graph
 
     def play_move_replay(self, graph):

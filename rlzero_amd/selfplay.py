@@ -19,7 +19,9 @@ rank 0 (RCCL when the process group backend is nccl, gloo in the CPU tests).
 """
 import numpy as np
 
+from . import route as _route
 from ._hip import HipError
+from .route import fc_in_trunk_pays   # noqa: F401  (a board rule: route.py; importable from here as before)
 
 _MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -346,13 +348,16 @@ def choose_lanes_by_measurement(key, table_pick, hw_queues, n_games, build, time
     return cache[key]
 
 
-def fc_in_trunk_pays(rows, cols, n_actions):
-    """True when the trunk's workgroups should run the first FC layers on their own boards (HipNet.set_heads_algo('in_trunk'))
-    instead of a GEMM launch of its own: boards of up to 10 rows whose FC weights (hi + lo f16) are at most 40 KB -- every workgroup
-    streams them for its one board (6x6: 39 KB, TicTacToe +6 %; Connect4: 26 KB, 512 games on two lanes +3 %; 9x9: 146 KB, -5 to
-    -11 %: profiles/r03/in_trunk_fc.txt)."""
-    cells = rows * cols
-    return rows <= 10 and (n_actions * 4 * cells + 64 * 2 * cells) * 4 <= 40 * 1024
+def plan_route(rows, cols, game, net_algo, score_mode, in_flight, deferred_priors=None, delta_trunk=None, resident_search=None,
+               n_games=0, n_cus=0):
+    """What plan_lanes() is told of the route (its ``deferred`` / ``cells`` / ``in_flight`` / ``resident_per_cu``) for the evaluators
+    for_network() will build from these arguments: route.decide() on numbers alone -- no net, no engine, no GPU."""
+    r = _route.decide(rows, cols, net_algo or 'split_f16', deferred_priors=deferred_priors is not False, delta_trunk=delta_trunk is not False,
+                      resident_search=resident_search is not False, score_mode=score_mode, in_flight=in_flight, n_games=n_games, n_cus=n_cus)
+    algo_of_small_boards = (net_algo or 'split_f16') in _route.EVERY_BOARD_SPLIT_TRUNKS
+    return dict(deferred=r.deferred and game == 'gomoku' and _route.rows_kernel_board(rows, cols),   # (the table's deferred rows: 15x15 Gomoku and its kin)
+                cells=rows * cols if ((r.deferred and algo_of_small_boards) or in_flight > 1) else None, in_flight=in_flight,
+                resident_per_cu=r.resident_per_cu if r.resident else 1)
 
 
 class _Lane(object):
@@ -390,17 +395,14 @@ class BatchedSelfPlay(object):
             offset += eng.n_games
         n_cus = torch.cuda.get_device_properties(engines[0].device).multi_processor_count
 
-        def per_cu(ev, eng):   # resident workgroups a CU holds: two of the receptive-field kernel (k_delta_res) and of the compact grid's
-            inner = getattr(ev, 'inner', ev)
-            fn = getattr(inner, 'resident_per_cu', None)
-            return fn(eng) if fn is not None else 1
-        if len(engines) > 1 and sum(e.n_games for e in engines) > n_cus * min(per_cu(ev, e) for ev, e in zip(evaluators, engines)):
+        # (resident workgroups a CU holds: two of the receptive-field kernel (k_delta_res) and of the compact grid's)
+        asked = [eng._ask(ev) for eng, ev in zip(engines, evaluators)]
+        if len(engines) > 1 and sum(e.n_games for e in engines) > n_cus * min(r.resident_per_cu for r, _, _ in asked):
             # lanes that share CUs: the resident search (a workgroup keeps its CU for a whole search) is for games that have a CU
             # each -- these lanes run the two-launch step, whose trunk workgroups make way for the other lanes every step
-            for ev in evaluators:
-                inner = getattr(ev, 'inner', ev)   # (bench.py wraps its evaluators)
-                if hasattr(inner, 'resident_search'):
-                    inner.resident_search = False
+            for _, owner, _ in asked:
+                if owner is not None:
+                    owner.resident_search = False
         self.eng = engines[0]  # geometry (board size, n_playout) is common to all lanes
         self.evaluator = evaluators[0]
         self.n_slots = offset
@@ -491,20 +493,10 @@ class BatchedSelfPlay(object):
         K = max(1, int(sims_in_flight))
         shape0 = net_shape if net_shape is not None else board
         rows0, cols0 = (shape0[0], shape0[1]) if isinstance(shape0, (tuple, list)) else (shape0, shape0)
-        deferred = (deferred_priors is not False and K == 1 and engine_kw.get('score_mode', 'uct_ref') in ('uct_ref', 0)
-                    and game == 'gomoku' and 11 <= rows0 <= 16 and 11 <= cols0 <= 16
-                    and net_algo in (None, 'split_f16', 'split_f16_tiles', 'split_f16_fp8'))
-        small_trunk = (K == 1 and deferred_priors is not False and engine_kw.get('score_mode', 'uct_ref') in ('uct_ref', 0)
-                       and net_algo in (None, 'split_f16', 'split_f16_tiles'))   # (the two-launch step on a small board)
-        import os
-        delta_res = (deferred and resident_search is not False and delta_trunk is not False and net_algo in (None, 'split_f16')
-                     and os.environ.get('RZ_NET_DELTA', '1') != '0' and os.environ.get('RZ_NET_DELTA_RESIDENT', '1') != '0')
-        from .engine import compact_grid_board
-        compact_res = (small_trunk and not deferred and resident_search is not False and net_algo in (None, 'split_f16')
-                       and max(rows0, cols0) <= 10 and compact_grid_board(rows0, cols0))
-        auto_lanes, auto_wgs, heads_algo = plan_lanes(n_games * K, n_cus, deferred=deferred,
-                                                      cells=rows0 * cols0 if (small_trunk or K > 1) else None, in_flight=K,
-                                                      resident_per_cu=2 if (delta_res or compact_res) else 1)
+        planned = plan_route(rows0, cols0, game, net_algo, engine_kw.get('score_mode', 'uct_ref'), K, deferred_priors=deferred_priors,
+                             delta_trunk=delta_trunk, resident_search=resident_search, n_games=n_games, n_cus=n_cus)
+        deferred = planned['deferred']
+        auto_lanes, auto_wgs, heads_algo = plan_lanes(n_games * K, n_cus, **planned)
         measured = None
         if lanes == 'table':
             lanes = None
@@ -529,10 +521,8 @@ class BatchedSelfPlay(object):
             wgs, heads_algo = (0, 'parts') if lanes > 1 else (0, 'auto')
         if trunk_workgroups is not None:
             wgs = trunk_workgroups
-        shape = net_shape if net_shape is not None else board
-        rows, cols = (shape[0], shape[1]) if isinstance(shape, (tuple, list)) else (shape, shape)
-        acts = shape[2] if isinstance(shape, (tuple, list)) and len(shape) > 2 else rows * cols
-        if heads_algo == 'parts' and int(wgs) == 0 and fc_in_trunk_pays(rows, cols, acts):
+        acts = shape0[2] if isinstance(shape0, (tuple, list)) and len(shape0) > 2 else rows0 * cols0
+        if heads_algo == 'parts' and int(wgs) == 0 and fc_in_trunk_pays(rows0, cols0, acts):
             heads_algo = 'in_trunk'   # small FC layers: no GEMM launch at all (each lane's chain loses a kernel and a boundary)
         lanes = max(1, min(int(lanes), n_games))
         per_lane = [n_games // lanes + (1 if i < n_games % lanes else 0) for i in range(lanes)]
@@ -541,8 +531,7 @@ class BatchedSelfPlay(object):
             engines.append(MCTSEngine(board, n_in_row, n_games=g_lane, n_playout=n_playout, c_puct=c_puct,
                                       device=str(device), game=game, add_noise=add_noise, sims_in_flight=K,
                                       noise_seed=(int(seed) * 7919 + len(engines)) & 0x7fffffff, **engine_kw))
-            ev = HipNetEvaluator(net_module, net_shape if net_shape is not None else board, str(device),
-                                 max_boards=g_lane * K)
+            ev = HipNetEvaluator(net_module, shape0, str(device), max_boards=g_lane * K)
             if net_algo is not None:
                 ev.hip.set_algo(net_algo)
             ev.hip.set_max_workgroups(max(0, int(wgs)))
@@ -633,7 +622,7 @@ class BatchedSelfPlay(object):
                 lane.primed = False
             return
         n = self.eng.n_playout
-        if all(getattr(lane.evaluator, 'resident_ok', None) is not None and lane.evaluator.resident_ok(lane.eng) for lane in self.lanes):
+        if all(lane.eng._ask(lane.evaluator)[0].resident for lane in self.lanes):
             for lane in self.lanes:   # one launch per lane for the whole search: nothing to interleave, no graph
                 self._simulate_lane(lane)
             return
@@ -666,9 +655,9 @@ class BatchedSelfPlay(object):
         """Enqueue the n_playout simulations of ONE lane on its stream (graph replays + the eager remainder)."""
         n = self.eng.n_playout
         with self._on(lane):
-            res_ok = getattr(lane.evaluator, 'resident_ok', None)
-            if res_ok is not None and res_ok(lane.eng):   # one launch for the whole search: no graph, no chunks
-                lane.eng.sim_chunk(lane.evaluator, n)
+            r = lane.eng._ask(lane.evaluator)[0]
+            if r.resident:   # one launch for the whole search: no graph, no chunks
+                lane.eng.sim_chunk(lane.evaluator, n, r)
                 return
             if self.use_graph:
                 per = self.eng.graph_chunk(self.sims_per_graph)
