@@ -578,7 +578,7 @@ int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *
  * (policy_value_net.py:34-46 on gomoku_env.py:95-114's planes). */
 int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream);
 /* counters since the last reset (synchronises): {leaves evaluated against a base, leaves without one, conv3 tiles of 16 cells, changed
- * cells, conv2 tiles of 16 cells, 0, and -- of workgroup 0 of the LAST resident launch -- its shader-clock cycles >> 8 and its ticks
+ * cells, conv2 tiles of 16 cells, root scans of the resident search answered from the pre-scan, and -- of workgroup 0 of the LAST resident launch -- its shader-clock cycles >> 8 and its ticks
  * of the constant 100 MHz clock: the clock the search ran at = 256 [6] / (10 ns [7])} */
 int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
 /* RESIDENT SEARCH -- n_sims consecutive simulations of every active game of `engine` (AlphaZeroMCTS.simulate's loop,

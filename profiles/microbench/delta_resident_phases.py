@@ -14,7 +14,11 @@ from rlzero_amd.engine import HipNetEvaluator, MCTSEngine
 from rlzero_amd.games.gomoku.policy_value_net import PolicyValueNet
 lib = H.load()
 NAMES = [(0, 'leaf + changed cells'), (1, 'distances, requests, ranks'), (3, 'maps, base records'), (4, 'bar'), (5, 'conv1'), (6, 'bar'), (7, 'conv2'),
-         (9, 'bar + conv3 + heads'), (10, 'bar'), (11, 'features'), (12, 'bar'), (16, 'value layer'), (17, 'expand + backup'), (18, 'selection')]
+         (9, 'bar + conv3 + heads'), (10, 'bar'), (11, 'features'), (12, 'bar'), (16, 'value layer'), (17, 'expand + backup'),
+         # the selection's own rows (-DRZ_SEL_TICKS=<mask>, rz_delta.h: a tick that is off leaves its cycles to the next one taken; 18 = the rest,
+         # without any of them the whole selection) and wave 1's pre-scan with the barrier wait behind it
+         (2, 'sel: root record'), (8, 'sel: root scan / answer'), (13, 'sel: level-0 cell'), (14, 'sel: deeper levels'), (15, 'sel: terminal test + leaf stores'),
+         (18, 'selection (rest: hand-over)'), (19, 'wave 1: pre-scan'), (20, 'wave 1: wait behind it')]
 sizes = [int(a) for a in sys.argv[1:]] or [1, 256, 512]
 for games in sizes:
     torch.manual_seed(0)
@@ -43,5 +47,5 @@ for games in sizes:
     print('%d games, %d simulations: %.2f us per simulation of a game (events, bases included), %d cycles (%.2f GHz); %.2f conv3 / %.2f conv2 tiles, %.2f changed cells per leaf, %d leaves without a base' % (
         games, sims, us, total, total / us / 1e3, st['tiles3'] / max(1, st['delta'] + st['no_base']), st['tiles2'] / max(1, st['delta'] + st['no_base']),
         st['cells'] / max(1, st['delta'] + st['no_base']), st['no_base']))
-    print('   ' + '  '.join('%s=%d' % (nm, out[k] / sims) for k, nm in NAMES), flush=True)
+    print('   ' + '  '.join('%s=%d' % (nm, out[k] / sims) for k, nm in NAMES) + '  prescans=%d' % st['prescans'], flush=True)
     eng.close(); ev.hip.close()

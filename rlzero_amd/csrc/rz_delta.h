@@ -37,6 +37,11 @@
 #ifndef RZ_DELTA_PRO_PRIO
 #define RZ_DELTA_PRO_PRIO 0
 #endif
+// (k_delta_res: wave 1 scores the root's siblings for the next selection while wave 0 backs the simulation up -- rzt::root_prescan;
+// 0: the selection scans the root itself, as before -- profiles/r09/ab_prescan.txt)
+#ifndef RZ_DELTA_PRESCAN
+#define RZ_DELTA_PRESCAN 1
+#endif
 
 namespace dl {
 
@@ -62,8 +67,8 @@ static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's 
 // the resident search's hand-over from the selection to the next leaf's prologue (leaf_windows): the four window sets of pass -1
 // (radius 1 .. 4) as 4 x 4 words, their words' popcounts, the verdict (use_delta | parity << 1 | nD << 8)
 constexpr int kWinSets = rzw::kRadii * rzw::kWords, kWinLds = kWinSets * 8 + kWinSets * 4 + 16;
-static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + kWinLds + 512) <= 160 * 1024,
-              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets)");
+static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + kWinLds + (int)sizeof(rzt::RootPre) + 512) <= 160 * 1024,
+              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
 
 // The base cache: per game a header (the stones the two bases were computed from) and per (game, parity) the records.
@@ -80,8 +85,9 @@ struct DeltaArgs {
                              // head features [6][kCells] f32 (behind their ReLU)
     const uint8_t *active;   // mode 0: games whose flag is 0 are skipped (NULL: none is)
     float *feat32;           // the features as f32 [board][6 S] (tests; NULL otherwise)
-    unsigned *stats;         // [8] counters (NULL: none): delta leaves, leaves without a base, conv3 tiles, changed cells, conv2 tiles, -, and of
-                             // workgroup 0 of the LAST resident launch: shader-clock cycles >> 8, ticks of the constant 100 MHz clock
+    unsigned *stats;         // [8] counters (NULL: none): delta leaves, leaves without a base, conv3 tiles, changed cells, conv2 tiles, root scans
+                             // answered from the pre-scan (k_delta_res), and of workgroup 0 of the LAST resident launch: shader-clock
+                             // cycles >> 8, ticks of the constant 100 MHz clock
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
@@ -855,6 +861,27 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
 // -- changed_cells' verdict -- and, for pass -1, the cells within Chebyshev distance 1 .. 4 of its changed cells: per radius the union
 // of the window table's rows of the (at most kMaxD) changed cells.  Lane 16 i + 4 (r - 1) + w reads word w of the radius-r row of
 // changed cell i, two lane swaps OR the four cells' rows.  -> ws: [kWinSets] words, [kWinSets] their popcounts, the verdict.
+// (the lane's word of its changed cell's rows, zero without one -> the sets, the popcounts, the verdict)
+__device__ __forceinline__ void windows_store(uint64_t row, bool use_delta, int parity, int nD, int lane, uint64_t *ws) {
+    unsigned lo = (unsigned)row, hi = (unsigned)(row >> 32);
+    {   // (a swap leaves the lane's own value and its partner's: the OR does not care which is which)
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        lo = a[0] | a[1];
+        hi = b[0] | b[1];
+    }
+    {
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        lo = a[0] | a[1];
+        hi = b[0] | b[1];
+    }
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    int *cnt = reinterpret_cast<int *>(ws + kWinSets);
+    if (lane < kWinSets) {
+        ws[lane] = v;
+        cnt[lane] = __popcll(v);
+    }
+    if (lane == 0) cnt[kWinSets] = (use_delta ? 1 : 0) | (parity << 1) | (nD << 8);
+}
 __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
                                              int lane, uint64_t *ws) {
     uint64_t ls[8];
@@ -877,24 +904,61 @@ __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uin
     }
     const bool any = dy >= 0;   // (no such cell: -100)
     const uint64_t row = da.win[(any ? dy * BW + dx : 0) * kWinSets + (lane & (kWinSets - 1))];
-    unsigned lo = any ? (unsigned)row : 0u, hi = any ? (unsigned)(row >> 32) : 0u;
-    {   // (a swap leaves the lane's own value and its partner's: the OR does not care which is which)
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        lo = a[0] | a[1];
-        hi = b[0] | b[1];
+    windows_store(any ? row : 0ull, use_delta, parity, nD, lane, ws);
+}
+
+// select_body's hook in k_delta_res: the root pre-scan's hand-over (rz_tree.h: RootPre) and, in the profile build, the selection's
+// own phases (RZ_SEL_TICKS: bit i = tick i is taken -- a tick costs ~400 cycles itself, so the rows come from builds with different
+// placements; a tick that is off leaves its cycles to the next one)
+#if defined(RZ_NET_PROFILE) && !defined(RZ_SEL_TICKS)
+#define RZ_SEL_TICKS 0
+#endif
+struct ResHook {
+    static constexpr bool kOn = true;
+    rzt::RootPre *pre;
+    // the leaf's changed cells against the root as the selection walks: the path's cells (depth >= 1), the root's last move (depth 0).
+    // Lane 16 i + 4 (r - 1) + w asks for word w of the radius-r row of changed cell i the moment that cell is chosen -- leaf_windows'
+    // lane layout --, so the rows arrive under the rest of the level, the terminal test and the leaf's stores.  (every level issues its
+    // load: past kMaxD cells no lane keeps it, and a load under a branch would wait for the loads before it)
+    const uint64_t *win;
+    int depth;
+    bool any0;
+    uint64_t row;
+    __device__ __forceinline__ void root_cell(int last, int stones, int lane) {
+        any0 = stones > 0 && last >= 0 && last < kCells;
+        row = win[(any0 ? last : 0) * kWinSets + (lane & (kWinSets - 1))];
     }
-    {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        lo = a[0] | a[1];
-        hi = b[0] | b[1];
+    __device__ __forceinline__ void cell(int level, int c, int lane) {
+        const uint64_t v = win[c * kWinSets + (lane & (kWinSets - 1))];
+        row = (lane >> 4) == level ? v : row;
     }
-    const uint64_t v = ((uint64_t)hi << 32) | lo;
-    int *cnt = reinterpret_cast<int *>(ws + kWinSets);
-    if (lane < kWinSets) {
-        ws[lane] = v;
-        cnt[lane] = __popcll(v);
+#ifdef RZ_NET_PROFILE
+    Prof *prof;
+    __device__ __forceinline__ void tick(int i, int arrived) {   // -> net_prof[2, 8, 13, 14, 15]
+        if ((RZ_SEL_TICKS >> i) & 1) {
+            asm volatile("" ::"v"(arrived));
+            const int slot = i == 0 ? 2 : i == 1 ? 8 : 12 + i;
+            __builtin_amdgcn_sched_barrier(0);
+            const long long now = __builtin_readcyclecounter();
+            prof->acc[slot] += now - prof->t;
+            prof->t = now;
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
-    if (lane == 0) cnt[kWinSets] = (use_delta ? 1 : 0) | (parity << 1) | (nD << 8);
+#else
+    __device__ __forceinline__ void tick(int, int) {}
+#endif
+};
+
+// The same hand-over behind a selection made HERE: the rows were requested during the descent (ResHook), and the verdict is
+// changed_cells' without the leaf: against a base that is the root (base_ok) the changed cells are the path's cells -- the last move is
+// one of them -- or, at depth 0, the root's last move (none on an empty board); parity = depth & 1; more than kMaxD cells or no base:
+// no delta.
+__device__ __forceinline__ void path_windows(const ResHook &hook, bool base_ok, int lane, uint64_t *ws) {
+    const int depth = hook.depth;
+    const bool mine = depth == 0 ? (lane < 16 && hook.any0) : (lane >> 4) < depth;
+    const int nD = depth == 0 ? (hook.any0 ? 1 : 0) : depth;
+    windows_store(mine ? hook.row : 0ull, base_ok && nD <= kMaxD, depth & 1, nD, lane, ws);
 }
 
 // RESIDENT SEARCH with receptive-field evaluation (rz_net_search_resident on boards of 11 .. 16 rows and columns once the base cache
@@ -911,6 +975,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ float res_part[rzt::kDefWaves][rzt::kWave];
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
+    __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
     const int game = blockIdx.x;
     if (game >= res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier)
     const unsigned long long clk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
@@ -953,6 +1018,17 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         init_maps(lds, tid0);
         for (int i = tid0; i < kResVrow; i += 256) res_vrow[i] = 0.0f;
     }
+    if (tid0 == 0) res_pre.scan = res_pre.valid = res_pre.answered = 0;   // (no stash yet: a select_first == 0 launch's first selection was not made here)
+    ResHook hook;
+    hook.pre = &res_pre;
+    hook.win = da.win;
+    hook.depth = 0;
+    hook.any0 = false;
+    hook.row = 0ull;
+#ifdef RZ_NET_PROFILE
+    hook.prof = &prof;
+    long long pre_cycles = 0, pre_wait = 0;   // wave 1: the pre-scan, the barrier behind it (= its slack under expand + backup)
+#endif
     if (res.select_first == 0 && tid0 == 0) {   // the first leaf was selected by rz_select_step: from the engine's leaf arrays
 #pragma unroll
         for (int q = 0; q < 8; ++q) res_leaf[q] = res.E.leaf_stones[(size_t)game * 8 + q];
@@ -963,9 +1039,13 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     if (wave == 0) {
         // AlphaZeroMCTS._playout's select loop for the first simulation of the search (rz_select_step's work), or its leaf from
         // rz_select_step; either way the hand-over of the first leaf's windows
-        if (res.select_first != 0) rzt::select_body<false>(res.E, nullptr, game, tid0 & 63, 0, res_leaf);
-        __builtin_amdgcn_wave_barrier();
-        leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, tid0 & 63, res_win);
+        const int lane0 = tid0 & 63;
+        if (res.select_first != 0) {
+            rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane0, 0, res_leaf, &hook);
+            path_windows(hook, base_ok, lane0, res_win);
+        } else {
+            leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, lane0, res_win);
+        }
     }
     __syncthreads();
     int tiles_total = 0, tiles2_total = 0, deltas = 0, cells_total = 0;
@@ -1016,15 +1096,38 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         if (res.vh.groups == 128) rzt::value_quarter_lds<16>(res.vh, res_vrow, lane, wave, res_part);
         else rzt::value_quarter_lds<8>(res.vh, res_vrow, lane, wave, res_part);
         NET_TICK(16);
-        if (wave == 0) rzt::expand_backup_body<float, false, false, false, true>(res.E, nullptr, nullptr, game, lane, rz_raw_heads(), 0, res.vh, res_part);
-        else __syncthreads();   // (the barrier inside the body, where the quarters meet)
-        __syncthreads();        // the tree's updates before the selection's loads
-        NET_TICK(17);
         const bool more = sim + 1 < res.n_sims;
+        if (wave == 0) {
+            rzt::expand_backup_body<float, false, false, false, true>(res.E, nullptr, nullptr, game, lane, rz_raw_heads(), 0, res.vh, res_part);
+        } else {
+            __syncthreads();   // (the barrier inside the body, where the quarters meet)
+            // wave 1, idle until the next barrier: the root's siblings for the next selection (it reads the tree, it writes LDS)
+            if (RZ_DELTA_PRESCAN && wave == 1 && more) {
+#ifdef RZ_NET_PROFILE
+                const long long t0 = __builtin_readcyclecounter();
+#endif
+                rzt::root_prescan<rzt::kWords>(res.E, game, lane, &res_pre);
+#ifdef RZ_NET_PROFILE
+                __builtin_amdgcn_s_waitcnt(0);
+                const long long t1 = __builtin_readcyclecounter();
+                pre_cycles += t1 - t0;
+                pre_wait -= t1;
+#endif
+            }
+        }
+        __syncthreads();        // the tree's updates before the selection's loads; the pre-scan's answer
+#ifdef RZ_NET_PROFILE
+        if (RZ_DELTA_PRESCAN && wave == 1 && more) pre_wait += __builtin_readcyclecounter();
+#endif
+        NET_TICK(17);
         if (wave == 0 && more) {
-            rzt::select_body<false>(res.E, nullptr, game, lane, 0, res_leaf);
-            __builtin_amdgcn_wave_barrier();
-            leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, lane, res_win);
+            hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
+            // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
+            // and kept -- spilled -- across the trunk)
+            int lane_t = lane;
+            asm volatile("" : "+v"(lane_t));
+            rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, 0, res_leaf, &hook);
+            path_windows(hook, base_ok, lane_t, res_win);
         }
         if (RZ_DELTA_TREE_PRIO) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
@@ -1036,6 +1139,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         atomicAdd(da.stats + 2, (unsigned)tiles_total);
         atomicAdd(da.stats + 3, (unsigned)cells_total);
         atomicAdd(da.stats + 4, (unsigned)tiles2_total);
+        atomicAdd(da.stats + 5, (unsigned)res_pre.answered);
         if (game == 0) {   // the clock this search ran at: cycles / (ticks x 10 ns)
             da.stats[6] = (unsigned)((__builtin_readcyclecounter() - clk0) >> 8);
             da.stats[7] = (unsigned)(__builtin_amdgcn_s_memrealtime() - rt0);
@@ -1043,9 +1147,14 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     }
 #ifdef RZ_NET_PROFILE
     if (blockIdx.x == 0 && tid0 == 0) {
-        for (int i = 0; i < 24; ++i) net_prof[i] = prof_acc[i];
+        for (int i = 0; i < 24; ++i)
+            if (i != 19 && i != 20) net_prof[i] = prof_acc[i];
         net_prof[23] = __builtin_readcyclecounter() - prof_k0;
         net_prof[22] = tiles_total;
+    }
+    if (blockIdx.x == 0 && tid0 == 64) {   // wave 1's first lane: the pre-scan and the wait behind it
+        net_prof[19] = pre_cycles;
+        net_prof[20] = pre_wait;
     }
 #endif
 }

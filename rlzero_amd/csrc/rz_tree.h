@@ -490,9 +490,26 @@ __device__ __forceinline__ int wave_first_max(double best, int besti, bool wide 
 // Score every child of a fully visited (or dense) node, lane r0 = lane + 64 j takes child r0, and
 // return the first maximum; the winner's record is broadcast so the descent needs no reload.
 // (W: a board of W words has at most 64 W children per node -- W of the four child slots of a lane exist)
-template <bool PUCT, int W = kWords>
+// PRE (root_prescan below: an idle wave scores the root's children while the selecting wave backs the simulation up): child `skip`
+// is left out, the wave's best score comes back in *best_out (-inf without a candidate), and the record loads carry sc1 -- 16-byte
+// buffer loads that bypass the CU's L1.  The backup stores to records of the same 128-byte lines at that moment (child `skip` shares
+// a line with three siblings); a plain load that misses L1 before such a store and fills it afterwards would leave the old copy of
+// child `skip` in L1, where the selecting wave's later PLAIN load of that record would find it.  Every other load of the scan is plain.
+template <bool SC1>
+__device__ __forceinline__ int4 load_half(const int4 *R, int idx) {
+    if constexpr (SC1) {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4 *>(R), 0, 0x7fffffff, 0x00020000);
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, idx * 16, 0, 16);   // (aux 16 = sc1)
+        return make_int4((int)v[0], (int)v[1], (int)v[2], (int)v[3]);
+    } else {
+        return R[idx];
+    }
+}
+template <bool PUCT, int W = kWords, bool PRE = false>
 __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const float *P, const int4 &lo,
-                                             const int4 &hi, double parent_term, int lane, int4 &clo, int4 &chi) {
+                                             const int4 &hi, double parent_term, int lane, int4 &clo, int4 &chi,
+                                             int skip = -1, double *best_out = nullptr) {
+    static_assert(!(PRE && PUCT), "the pre-scan is the reference rule's");
     const int k = rec_k(lo), fc = lo.y, pb = hi.z;
     // the lane's (up to) four children r0 = lane + 64 j: all loads first, then the scores; the lane keeps the RECORD
     // of its best child in registers (no array survives the loop: an array of records selected by a run-time index
@@ -500,19 +517,21 @@ __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const 
     int4 l0 = make_int4(0, -1, 0, 0), l1 = l0, l2 = l0, l3 = l0;
     int4 h0 = make_int4(0, 0, -1, 0), h1 = h0, h2 = h0, h3 = h0;
     float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-    if (lane < k) { l0 = R[2 * (fc + lane)]; h0 = R[2 * (fc + lane) + 1]; if (PUCT) p0 = P[pb + lane]; }
+    if (lane < k) { l0 = load_half<PRE>(R, 2 * (fc + lane)); h0 = load_half<PRE>(R, 2 * (fc + lane) + 1); if (PUCT) p0 = P[pb + lane]; }
     if constexpr (W >= 2) {
-        if (lane + 64 < k) { l1 = R[2 * (fc + lane + 64)]; h1 = R[2 * (fc + lane + 64) + 1]; if (PUCT) p1 = P[pb + lane + 64]; }
+        if (lane + 64 < k) { l1 = load_half<PRE>(R, 2 * (fc + lane + 64)); h1 = load_half<PRE>(R, 2 * (fc + lane + 64) + 1); if (PUCT) p1 = P[pb + lane + 64]; }
     }
     if constexpr (W > 2) {
-        if (lane + 128 < k) { l2 = R[2 * (fc + lane + 128)]; h2 = R[2 * (fc + lane + 128) + 1]; if (PUCT) p2 = P[pb + lane + 128]; }
-        if (lane + 192 < k) { l3 = R[2 * (fc + lane + 192)]; h3 = R[2 * (fc + lane + 192) + 1]; if (PUCT) p3 = P[pb + lane + 192]; }
+        if (lane + 128 < k) { l2 = load_half<PRE>(R, 2 * (fc + lane + 128)); h2 = load_half<PRE>(R, 2 * (fc + lane + 128) + 1); if (PUCT) p2 = P[pb + lane + 128]; }
+        if (lane + 192 < k) { l3 = load_half<PRE>(R, 2 * (fc + lane + 192)); h3 = load_half<PRE>(R, 2 * (fc + lane + 192) + 1); if (PUCT) p3 = P[pb + lane + 192]; }
     }
     double best = -INFINITY;
     int besti = 0x7fffffff;
     int4 blo = l0, bhi = h0;
     auto consider = [&](const int4 &cl, const int4 &ch, float prior, int r0) {
-        if (r0 < k) {
+        bool in = r0 < k;
+        if constexpr (PRE) in = in && r0 != skip;
+        if (in) {
             const double sc = PUCT ? puct(rec_w(ch), cl.x, prior, parent_term, E.c_puct)
                                    : uct_ref(rec_w(ch), cl.x, parent_term, E.c_puct);
             if (sc > best) {
@@ -531,13 +550,66 @@ __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const 
     }
     // (TicTacToe, Connect4, the end of a 6 x 6 game: at most 16 children, two stages of the arg-max less; a scalar branch)
     const int r = __builtin_amdgcn_readfirstlane(wave_first_max<W>(best, besti, W > 2 || __builtin_amdgcn_readfirstlane(k) > 16));
+    if constexpr (PRE) *best_out = -INFINITY;
     if (r >= k) return r;
     const int l = r & 63;
+    if constexpr (PRE) {
+        const long long b = __double_as_longlong(best);
+        *best_out = __hiloint2double(__builtin_amdgcn_readlane((int)(b >> 32), l), __builtin_amdgcn_readlane((int)b, l));
+    }
     clo = make_int4(__builtin_amdgcn_readlane(blo.x, l), __builtin_amdgcn_readlane(blo.y, l),
                     __builtin_amdgcn_readlane(blo.z, l), __builtin_amdgcn_readlane(blo.w, l));
     chi = make_int4(__builtin_amdgcn_readlane(bhi.x, l), __builtin_amdgcn_readlane(bhi.y, l),
                     __builtin_amdgcn_readlane(bhi.z, l), __builtin_amdgcn_readlane(bhi.w, l));
     return r;
+}
+
+// ---- the root's siblings scored ahead of the selection (k_delta_res, rz_delta.h).  A backup changes only the records on its own
+// path: while the selecting wave backs simulation s up, every child of the root except the one it descended into (`r`) already has
+// the record the NEXT selection will score, and that selection's parent term is known too: logtab[N + 1].  select_body<.., Hook>
+// leaves a STASH in LDS at level 0 (what it holds anyway), an idle wave of the same workgroup runs root_prescan between two barriers
+// that are there already -- it reads global memory and writes LDS, nothing else -- and the next select_body, when the root record it
+// loads is the stash's with N + 1, scores child r alone and takes it against the helper's winner.  Any mismatch (no stash, another
+// record, helper not run) is answered by the unchanged scan: a forgotten case costs time, never a different tree.
+struct RootPre {
+    // the stash (select_body): the root record's first half as the selection left it (N, first child, visited children, k | capacity),
+    // the child it descended into, "the next selection scans the root" (reference rule, every child visited), the game's arena
+    int4 lo;
+    int r, scan, arena;
+    int answered;   // root scans answered so far in this launch (kept here: a register across the trunk is a spill)
+    // the helper's answer (root_prescan): the first maximum over the children other than r (besti 0x7fffffff: none), that child's
+    // record, the parent term the scores were made with; valid: made from THIS stash
+    int4 clo, chi;
+    double best, term;
+    int besti, valid, pad1[2];
+};
+struct NoHook { static constexpr bool kOn = false; };   // select_body's default: no stash, no answer, the code it always had
+
+template <int W = kWords>
+__device__ __forceinline__ void root_prescan(const Dev &E, int g, int lane, RootPre *pre) {
+    const int4 lo = make_int4(__builtin_amdgcn_readfirstlane(pre->lo.x), __builtin_amdgcn_readfirstlane(pre->lo.y),
+                              __builtin_amdgcn_readfirstlane(pre->lo.z), __builtin_amdgcn_readfirstlane(pre->lo.w));
+    const int r = __builtin_amdgcn_readfirstlane(pre->r), scan = __builtin_amdgcn_readfirstlane(pre->scan);
+    const int arena = __builtin_amdgcn_readfirstlane(pre->arena);
+    const int n1 = lo.x + 1, k = rec_k(lo);
+    // (the parent term must exist; the records' byte offsets must fit a buffer resource -- a load past it returns zeros, never faults)
+    const bool ok = scan != 0 && n1 >= 1 && n1 < E.logtab_n && lo.y >= 0 && ((long long)lo.y + k) * 32 < 0x7fffffffll;
+    if (ok) {
+        const int4 *R = arena_records(E, g, arena);
+        const double term = E.logtab[n1];
+        int4 clo = make_int4(0, -1, 0, 0), chi = make_int4(0, 0, -1, 0);
+        double best;
+        const int4 nohi = make_int4(0, 0, -1, 0);   // (the root's second half: the reference rule reads none of it)
+        const int bi = scan_children<false, W, true>(E, R, nullptr, lo, nohi, term, lane, clo, chi, r, &best);
+        if (lane == 0) {
+            pre->clo = clo;
+            pre->chi = chi;
+            pre->best = best;
+            pre->term = term;
+            pre->besti = bi;
+        }
+    }
+    if (lane == 0) pre->valid = ok ? 1 : 0;
 }
 
 // VL = false: the reference's search, ONE simulation in flight per tree (bit-exact).  VL = true (opt-in, E.K > 1,
@@ -550,8 +622,14 @@ __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const 
 // `lds_leaf` (the resident search kernels, rz_net.hip): the leaf position also goes to LDS -- uint64 [8] stones, then side to move
 // and last cell as two int32 -- where the trunk of the SAME workgroup reads it behind a barrier (a scalar load of the leaf arrays
 // could hit the scalar cache's copy of the previous simulation's leaf).
-template <bool VL, int W = kWords>
-__device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr) {
+// `hook` (Hook::kOn; k_delta_res): hook->pre is the root pre-scan's hand-over (RootPre above; its `answered` counts the root scans it
+// answered); hook->root_cell(last, stones, lane) and hook->cell(level, cell, lane) report the root's last move and each level's cell the moment
+// it is chosen, hook->depth the leaf's depth (the caller requests what it needs per cell during the descent instead of behind it);
+// hook->tick(i, v) is a phase tick of the profile build behind the arrival of v.  NoHook: none of it.
+template <bool VL, int W = kWords, class Hook = NoHook>
+__device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr,
+                                            Hook *hook = nullptr) {
+    static_assert(!(Hook::kOn && VL), "the root pre-scan is the sequential search's");
     const int gk = VL ? g * E.K + j : g;
     // every load that does not depend on another one is issued before `active` is tested: a kernel of dependent
     // round trips (an inactive game's slots exist, reading them is harmless)
@@ -567,6 +645,15 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
     window = E.line_tab[lane];
     uint64_t window_hi = 0;
     if constexpr (W == 2) window_hi = E.line_tab[kWave + lane];
+    // the helper's answer and the stash it was made from (LDS: asked for with the first loads); the stash this selection leaves
+    RootPre was = {};
+    bool pre_ok = false;
+    int4 st_lo = make_int4(0, -1, 0, 0);
+    int st_r = 0, st_scan = 0;
+    if constexpr (Hook::kOn) {
+        was = *hook->pre;
+        pre_ok = __builtin_amdgcn_readfirstlane(was.scan != 0 && was.valid != 0 ? 1 : 0) != 0;
+    }
     if (!act) return;
     int4 *R = arena_records(E, g, arena);
     const float *P = arena_priors(E, g, arena);
@@ -579,6 +666,16 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
     if (lane == 0) path[0] = 0;
 
     int4 lo = R[0], hi = R[1];  // the record of `node`: loaded for the root, broadcast by the scans below
+    // (Hook: the record of the child the last selection descended into, asked for together with the root's -- its slot is known from
+    // the stash; without an answer, any record: the root's)
+    int4 plo = lo, phi = hi;
+    if constexpr (Hook::kOn) {
+        const int s = pre_ok ? was.lo.y + was.r : 0;
+        plo = R[2 * s];
+        phi = R[2 * s + 1];
+        hook->root_cell(last, nst, lane);
+        hook->tick(0, lo.x);
+    }
     for (int it = 0; it <= S; ++it) {
         const int k = rec_k(lo);
         if (k == 0) break;  // leaf: never expanded, or a terminal position
@@ -628,6 +725,9 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
             }
             r = nv;
             fresh = 1;
+            if constexpr (Hook::kOn) {
+                if (it == 0) st_lo = make_int4(lo.x, fc, nv + 1, pack_kc(k, cap));   // (the record written below)
+            }
             if (lane == 0) {
                 R[2 * node] = make_int4(lo.x + (VL ? 1 : 0), fc, nv + 1, pack_kc(k, cap));
                 if (VL) {
@@ -642,7 +742,34 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
                 flag(E, g, RZ_FLAG_LOGTAB, lane);
                 break;
             }
-            r = scan_children<false, W>(E, R, P, lo, hi, E.logtab[pn], lane, clo, chi);
+            bool answered = false;
+            int r_pre = 0;
+            if constexpr (Hook::kOn) {
+                // the root as the stash foretold it (one more visit, nothing else moved): child r's fresh score against the helper's
+                // first maximum over the others -- larger score wins, equal scores go to the lower index, a score that is not above
+                // -inf is no candidate: wave_first_max over all k
+                if (it == 0 && pre_ok && lo.x == was.lo.x + 1 && lo.y == was.lo.y && lo.z == was.lo.z && lo.w == was.lo.w) {
+                    const double sr = uct_ref(rec_w(phi), plo.x, was.term, E.c_puct);
+                    const bool cand = sr > -INFINITY, none = was.besti == 0x7fffffff;
+                    const bool mine = cand && (none || sr > was.best || (sr == was.best && was.r < was.besti));
+                    const bool take = __builtin_amdgcn_readfirstlane(mine ? 1 : 0) != 0;
+                    r_pre = __builtin_amdgcn_readfirstlane(take ? was.r : was.besti);
+                    const int4 wlo = take ? plo : was.clo, whi = take ? phi : was.chi;
+                    clo = make_int4(__builtin_amdgcn_readfirstlane(wlo.x), __builtin_amdgcn_readfirstlane(wlo.y),
+                                    __builtin_amdgcn_readfirstlane(wlo.z), __builtin_amdgcn_readfirstlane(wlo.w));
+                    chi = make_int4(__builtin_amdgcn_readfirstlane(whi.x), __builtin_amdgcn_readfirstlane(whi.y),
+                                    __builtin_amdgcn_readfirstlane(whi.z), __builtin_amdgcn_readfirstlane(whi.w));
+                    if (lane == 0) hook->pre->answered += 1;
+                    answered = true;
+                }
+            }
+            r = answered ? r_pre : scan_children<false, W>(E, R, P, lo, hi, E.logtab[pn], lane, clo, chi);
+            if constexpr (Hook::kOn) {
+                if (it == 0) st_lo = lo;
+            }
+        }
+        if constexpr (Hook::kOn) {
+            if (it == 0) hook->tick(1, r);
         }
         if (r >= k) {
             flag(E, g, RZ_FLAG_INTERNAL, lane);
@@ -661,6 +788,14 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
             flag(E, g, RZ_FLAG_INTERNAL, lane);
             break;
         }
+        if constexpr (Hook::kOn) {
+            hook->cell(depth, cell, lane);
+            if (it == 0) {   // the stash: the root is scanned next time when every child has been visited (reference rule)
+                st_r = r;
+                st_scan = !use_puct && st_lo.z == k ? 1 : 0;
+                hook->tick(2, cell);
+            }
+        }
         if (to_move == 0) set_bit<W>(st[0], cell); else set_bit<W>(st[1], cell);
         last = cell;
         to_move ^= 1;
@@ -671,6 +806,17 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         if (fresh) break;  // a first-visit child has no statistics and no children yet
         lo = clo;
         hi = chi;
+    }
+    if constexpr (Hook::kOn) {
+        hook->tick(3, node);
+        hook->depth = depth;
+        if (lane == 0) {
+            RootPre *pre = hook->pre;
+            pre->lo = st_lo;
+            pre->r = st_r;
+            pre->scan = st_scan;
+            pre->arena = arena;
+        }
     }
     if (lane == 0 && top != top0) E.top[g] = top;
     if (VL && fresh == 0 && lane == 0) {  // the path ends in an existing leaf (unexpanded or terminal): virtual loss on it
@@ -715,6 +861,7 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
             reinterpret_cast<int *>(lds_leaf + 2 * kWords)[1] = last;
         }
     }
+    if constexpr (Hook::kOn) hook->tick(4, term);
     if (obs != nullptr)
         write_obs(obs + (long long)gk * 4 * S, to_move == 0 ? st[0] : st[1],
                   to_move == 0 ? st[1] : st[0], last, nst, S, lane);

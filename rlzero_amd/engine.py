@@ -244,12 +244,13 @@ class HipNet(object):
 
     def delta_stats(self, reset=False):
         """{'delta': leaves evaluated against a base, 'no_base': leaves that took the four passes, 'tiles3' / 'tiles2': conv3 / conv2 tiles of
-        16 cells, 'cells': changed cells, 'resident_sclk_ghz': the shader clock the last resident search ran at}"""
+        16 cells, 'cells': changed cells, 'prescans': root scans of the resident search that an idle wave had made ahead of the selection
+        (k_delta_res), 'resident_sclk_ghz': the shader clock the last resident search ran at}"""
         out = (ctypes.c_uint32 * 8)()
         check(self.lib.rz_net_delta_stats(self.handle, out, 1 if reset else 0), 'rz_net_delta_stats')
         ghz = (256.0 * out[6]) / (10.0 * out[7]) if out[7] else None   # (cycles per nanosecond of the last resident launch's workgroup 0)
         return {'delta': int(out[0]), 'no_base': int(out[1]), 'tiles3': int(out[2]), 'cells': int(out[3]), 'tiles2': int(out[4]),
-                'resident_sclk_ghz': ghz}
+                'prescans': int(out[5]), 'resident_sclk_ghz': ghz}
 
     def compact_resident(self):
         """True when the resident search runs on the COMPACT LDS grid (k_trunk_split<.., RES, 9, 15>: 69 KB, TWO games per CU and any
