@@ -73,9 +73,11 @@ enum {
     RZ_FLAG_ILLEGAL_MOVE = 4,
     RZ_FLAG_LOGTAB = 8,
     RZ_FLAG_INTERNAL = 16,
-    RZ_FLAG_REUSE_DROPPED = 32 /* NOT an error: rz_advance_roots found the kept subtree larger than pool_factor * n_playout
-                                  expanded nodes and restarted that game's search from a fresh root (the reference's tree
-                                  is unbounded, alphazero_mcts.py:96-103); counted in rz_stats.reuse_dropped */
+    RZ_FLAG_REUSE_DROPPED = 32 /* NOT an error: rz_advance_roots found the kept subtree larger than the carry limit (see
+                                  rz_config.pool_factor: more than int(pool_factor * n_playout) + 7 expanded nodes for a
+                                  pool_factor * n_playout without a fraction, or too many prior floats / record slots) and
+                                  restarted that game's search from a fresh root (the reference's tree is unbounded,
+                                  alphazero_mcts.py:96-103); counted in rz_stats.reuse_dropped, part of rz_stats.error_flags */
 };
 
 typedef struct rz_engine rz_engine;
@@ -95,8 +97,20 @@ typedef struct rz_config {
                             distribution as numpy's, not its global stream.  RZ_SCORE_UCT_REF never reads
                             the prior, so the noise cannot change its search. */
     double c_puct;       /* AlphaZeroPlayer(c_puct=) */
-    double pool_factor;  /* arena slots per game = pool_factor*n_playout*B*B + B*B + 2;
-                            0 -> 2.0 */
+    double pool_factor;  /* sizes a game's two arenas (0 -> 2.0), A = actions of a position:
+                              qcap = int((pool_factor + 1) * n_playout) + 8    expanded nodes (= prior blocks),
+                              prior floats = qcap * A,
+                              record slots = qcap * A + 2 (RZ_SCORE_PUCT: a record per child) or
+                                             qcap * 16 + 2 * A + 64 (RZ_SCORE_UCT_REF: records of visited children only, in
+                                             blocks of 4, 8, ... doubling up to the node's children).
+                            An expansion that does not fit is refused and flagged (RZ_FLAG_BLOCKS_FULL: nodes or prior
+                            floats, RZ_FLAG_ARENA_FULL: record slots), never written.  rz_advance_roots carries a kept
+                            subtree only when it leaves room for the n_playout expansions of the coming search -- summed
+                            over its expanded nodes (k children, a child block of c records each):
+                              sum k <= prior floats - (n_playout + 1) * A,
+                              1 + sum c <= record slots - (n_playout + 1) * 8 - 2 * A,
+                              nodes <= qcap - n_playout - 1;
+                            else the subtree is dropped (RZ_FLAG_REUSE_DROPPED). */
     int32_t device;      /* HIP device ordinal */
     int32_t noise_seed;  /* seed of the Dirichlet stream */
     int32_t board_height; /* RZ_GAME_CONNECT4 only (0 -> 6) */

@@ -496,6 +496,7 @@ __global__ void k_tree_step_ml(Dev E, const float *logp, const float *value, Raw
         __syncthreads();
         // phase B: the owner's wave walks the slots of ITS node in slot order (slots at different nodes do not see each
         // other within a level: the groups run side by side; at the root all slots are one group)
+        int cap0 = -1;   // the capacity of the node's child block before this pass grew it (phase C needs it when the arena is full)
         if (w < ks && SL[w].active && SL[w].owner == w)
         for (int j = w; j < ks; ++j) {
             if (!SL[j].active || SL[j].owner != w) continue;
@@ -516,8 +517,12 @@ __global__ void k_tree_step_ml(Dev E, const float *logp, const float *value, Raw
             if (!puct_mode && nv < k) {
                 if (nv == cap) {  // the child vector grows: its new block is allocated in phase C (in owner order, whatever the
                                   // groups' timing) and written from the staged copy
+                    if (cap0 < 0) cap0 = cap;
                     cap = cap == 0 ? (k < kFirstCap ? k : kFirstCap) : (2 * cap < k ? 2 * cap : k);
-                    if (lane == 0) SL[o].moved = 1;
+                    if (lane == 0) {
+                        SL[o].moved = 1;
+                        SL[o].pad1 = cap0;
+                    }
                 }
                 r = nv;
                 fresh = true;
@@ -613,7 +618,22 @@ __global__ void k_tree_step_ml(Dev E, const float *logp, const float *value, Raw
             const int4 xlo = SL[o].xlo;
             const int need = rec_cap(xlo);
             if ((long long)top + need > E.cap) {
+                // no room for the grown block: the node keeps its old one (full: cap0 visited children, the staged records of the
+                // slots that chose a child inside it are written one by one below), and the slots that chose a child past it end
+                // at the node itself with fresh = 2, as select_body does -- nothing is written at an offset the old block does not
+                // own (with no block yet its first-child offset is -1)
                 flag(E, g, RZ_FLAG_ARENA_FULL, lane);
+                const int cap0 = SL[o].pad1;
+                if (lane == 0) {
+                    for (int j = o; j < ks; ++j)
+                        if (SL[j].owner == o && SL[j].rank >= cap0) {
+                            SL[j].rank = -1;
+                            SL[j].fresh = 2;
+                            SL[j].depth -= 1;
+                        }
+                    SL[o].xlo = make_int4(xlo.x, xlo.y, cap0, pack_kc(rec_k(xlo), cap0));
+                    SL[o].moved = 0;
+                }
                 continue;
             }
             if (lane == 0) SL[o].xlo = make_int4(xlo.x, top, xlo.z, xlo.w);
@@ -979,12 +999,13 @@ __device__ __forceinline__ void advance_body(const Dev &E, int g, int lane, int 
         __syncthreads();  // records and queue entries written by other lanes are read next iteration
     }
     if (full) {
-        // The reference's tree is unbounded; here the kept subtree is limited to pool_factor * n_playout expanded
-        // nodes.  A larger one is DROPPED (the search restarts from a fresh root, like update_with_move(-1)):
+        // The reference's tree is unbounded; here the kept subtree is limited to qcap - n_playout - 1 expanded nodes
+        // (and the prior floats / record slots tested above).  A larger one is DROPPED (the search restarts from a fresh root, like update_with_move(-1)):
         // a deviation from the reference that is counted (rz_stats.reuse_dropped) and flagged per game with the
         // non-fatal RZ_FLAG_REUSE_DROPPED, never silent and never fatal for the rest of the batch.
         if (lane == 0) {
             atomicOr(&E.err[g], RZ_FLAG_REUSE_DROPPED);
+            atomicOr(E.err_any, RZ_FLAG_REUSE_DROPPED);   // (rz_stats.error_flags is the OR over the games: this bit too)
             atomicAdd(E.reuse_drops, 1);
         }
         fresh_root(E, g, dst_arena, lane);

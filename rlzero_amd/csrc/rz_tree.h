@@ -819,7 +819,9 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         }
     }
     if (lane == 0 && top != top0) E.top[g] = top;
-    if (VL && fresh == 0 && lane == 0) {  // the path ends in an existing leaf (unexpanded or terminal): virtual loss on it
+    // the path ends in an existing leaf (unexpanded or terminal), or in the node a full arena stopped it at (fresh == 2: the backup
+    // trades a virtual loss for the value there as well): virtual loss on it
+    if (VL && fresh != 1 && lane == 0) {
         *rec_n(R, node) = lo.x + 1;
         *rec_wsum(R, node) = rec_w(hi) - 1.0;
     }

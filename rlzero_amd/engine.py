@@ -704,9 +704,10 @@ class MCTSEngine(object):
 
     def check(self):
         """Raise if any game overflowed its arena / received an illegal move.  Returns the statistics;
-        ``reuse_dropped`` counts kept subtrees that exceeded the carry limit (pool_factor * n_playout expanded
-        nodes) and were replaced by a fresh root -- a counted deviation from the reference's unbounded tree, not
-        an error."""
+        ``reuse_dropped`` counts kept subtrees that exceeded the carry limit (more than qcap - n_playout - 1 expanded
+        nodes, qcap = int((pool_factor + 1) * n_playout) + 8, or the like for prior floats and record slots:
+        rz_config.pool_factor in include/rlzero_hip.h) and were replaced by a fresh root -- a counted deviation from
+        the reference's unbounded tree, not an error."""
         st = self.stats()
         if st.error_flags & ~_hip.FLAG_REUSE_DROPPED:
             names = [n for bit, n in _hip.FLAG_NAMES.items() if st.error_flags & bit]
