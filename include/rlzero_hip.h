@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 27
+#define RZ_ABI_VERSION 28
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -307,6 +307,19 @@ int rz_trace_attach(rz_engine *e, void *d_trace);   /* the evaluator's half: rz_
  * SAME build that run tree code outside the engine's own launches -- rz_net_search_resident.  out_bytes must be that build's
  * sizeof(Dev); valid until rz_destroy / the next rz_deferred_reserve. */
 int rz_device_view(rz_engine *e, void *out, int64_t out_bytes);
+/* Per-game simulation counts of rz_net_search_resident (ABI 28): d_counts int32 [n_games], every count >= 1 (the caller's to
+ * check) -- game g runs min(d_counts[g], n_sims) simulations of a launch, whose n_sims stays the maximum the store slots are
+ * reserved for; the trees, priors and values of a game are those of a uniform search with its count.  d_order (or NULL: identity)
+ * int32 [n_games], a permutation: workgroup b of k_delta_res searches game d_order[b] (longest first keeps a full search out of
+ * the last round of a grid beyond two games per CU; the other resident kernels keep the identity).  Both arrays are copied on
+ * `stream`.  d_counts NULL clears them.  They come before rz_play_set_cap's budgets while set.  RZ_ERR_ARG on an engine without the
+ * resident search's route (RZ_SCORE_PUCT, sims_in_flight > 1), and from the step-by-step tree calls while counts are set. */
+int rz_set_playouts(rz_engine *e, const int32_t *d_counts, const int32_t *d_order, void *stream);
+/* What the resident search reads: the counts and the order in force (rz_set_playouts', else rz_play_set_cap's, else NULL / NULL) */
+int rz_playouts_view(rz_engine *e, const int32_t **d_counts, const int32_t **d_order);
+/* Host copies of both for inspection (synchronous): *h_source = 0 none in force, 1 rz_set_playouts', 2 rz_play_set_cap's, | 4 when an
+ * order is in force (h_order is written then, h_counts whenever *h_source != 0; either may be NULL) */
+int rz_playouts_read(rz_engine *e, int32_t *h_counts, int32_t *h_order, int32_t *h_source);
 /* int32 [n_games]: the store slot the NEXT leaf of each game goes to (= steps since the last flush); the trunk reads it */
 int rz_deferred_slots(rz_engine *e, const int32_t **d_slot_of_game);
 /* rz_expand_backup / rz_tree_step of this route (pair with rz_select_step(e, NULL, ..) + rz_net_trunk_leaves_deferred) */
@@ -374,6 +387,15 @@ int rz_step_games(rz_engine *e, const int32_t *d_moves, int32_t *d_winner, uint8
  * fires): no draw, move -1, flags RUNNING | SEARCHED | ENDED | RESIGNED, winner 1 - ply % 2 (player 0 moves first), and
  * rz_play_apply ends the game as it ends a finished one (fresh tree, slot idle, refill) without a game step.
  *
+ * Playout cap randomization (KataGo, Wu 2019, section 3.1; an opt-in extension, off after every rz_play_attach; ABI 28).
+ * rz_play_set_cap(n_fast, p_full) turns it on: the search before ply `ply` of game `gid` has the full budget n_playout when
+ * cap_uniform(seed, gid, ply) < p_full -- a splitmix64 chain with a salt of its own (rlzero_amd/selfplay.py: cap_uniform, the same
+ * bits) -- and n_fast simulations otherwise.  k_play_apply writes the budget of every slot that is running after the step (a
+ * refilled slot at ply 0 included) into a device array that the resident search reads (min(budget, n_sims) simulations for the
+ * game), a one-workgroup kernel behind it orders the slots -- full budget, fast, inactive; stable -- for k_delta_res's workgroups,
+ * and k_play_draw sets RZ_PLAY_FULL on the searched records of full searches.  Only those are policy training samples; every
+ * game still gives a value target.  Dirichlet noise and temperature are the same on both kinds of move.
+ *
  * Slots refill themselves: a slot whose game has ended (or that is idle) takes the next entry of a queue of game ids shared by
  * the engines (lanes) of a GPU -- d_queue_ids int64 [..], d_queue_ctl int32 [2] = {head, entries valid}; the device advances
  * head atomically, the host may append ids and then raise the count -- and starts that game: empty board, player 0 to move, a
@@ -387,7 +409,8 @@ enum {
     RZ_PLAY_SEARCHED = 16, /* the slot took part in the search before this move step (n_playout simulations) */
     RZ_PLAY_RESIGNED = 32, /* the mover resigned (move -1, with RZ_PLAY_ENDED and the winner) */
     RZ_PLAY_NO_RESIGN = 64,     /* a calibration game: resignation disabled (every searched record of it while the rule is on) */
-    RZ_PLAY_WOULD_RESIGN = 128  /* a calibration game's record where the rule would have fired */
+    RZ_PLAY_WOULD_RESIGN = 128, /* a calibration game's record where the rule would have fired */
+    RZ_PLAY_FULL = 256     /* playout cap (rz_play_set_cap): a searched record whose search had the full budget; never set without a cap */
 };
 typedef struct rz_play_config {
     uint64_t seed;         /* move uniforms keyed (seed, game id, ply), Dirichlet streams keyed (seed, game id) */
@@ -416,6 +439,16 @@ int rz_play_apply(rz_engine *e, void *stream);
  * flags).  disabled_frac in [0, 1].  Valid after rz_play_attach; a graph captured before the FIRST call since rz_play_attach keeps
  * the resignation-free draw (capture again). */
 int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, void *stream);
+/* The playout cap (above), enqueued on `stream` as writes into small device arrays -- the rule and the budgets of the searches that
+ * are coming under it: a captured move graph takes new values without a new capture.  n_fast in 1 .. n_playout, p_full in (0, 1];
+ * p_full NaN: off again (every search n_playout simulations, no RZ_PLAY_FULL).  Valid after rz_play_attach on an engine of the
+ * resident search's route (RZ_SCORE_UCT_REF, sims_in_flight == 1; RZ_ERR_ARG otherwise); a graph captured before the FIRST call
+ * since rz_play_attach has no cap (capture again).  While a cap is set the step-by-step tree calls (rz_tree_step*,
+ * rz_expand_backup*) return RZ_ERR_ARG: only rz_net_search_resident knows per-game budgets. */
+int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream);
+/* Whether the cap's searches take their workgroups in the partition's order (default) or in slot order (0: no order kernel in the
+ * move step; a measurement's switch).  A host-side setting read when launches are enqueued: set it before a move graph is captured. */
+int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
 /* The host's decision for a stalled slot (one tiny launch); taken by the next rz_play_draw. */
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream);
 /* Drop every game: all slots idle with fresh trees (a run that stops early). */

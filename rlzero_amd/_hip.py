@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -82,6 +82,7 @@ class RzPlayConfig(Structure):
 PLAY_RECORD_WORDS = 8
 PLAY_RUNNING, PLAY_STALLED, PLAY_RESOLVED, PLAY_ENDED, PLAY_SEARCHED = 1, 2, 4, 8, 16
 PLAY_RESIGNED, PLAY_NO_RESIGN, PLAY_WOULD_RESIGN = 32, 64, 128   # resignation (rz_play_set_resign, ABI 27)
+PLAY_FULL = 256   # playout cap (rz_play_set_cap, ABI 28): the record's search had the full budget
 
 
 class HipError(RuntimeError):
@@ -136,6 +137,11 @@ _SIGNATURES = {
     'rz_play_draw': (c_int, [P, P]),
     'rz_play_apply': (c_int, [P, P]),
     'rz_play_set_resign': (c_int, [P, c_double, c_double, P]),
+    'rz_play_set_cap': (c_int, [P, c_int32, c_double, P]),
+    'rz_set_playouts': (c_int, [P, P, P, P]),
+    'rz_playouts_view': (c_int, [P, POINTER(c_void_p), POINTER(c_void_p)]),
+    'rz_play_set_cap_order': (c_int, [P, c_int32]),
+    'rz_playouts_read': (c_int, [P, P, P, POINTER(c_int32)]),
     'rz_play_resolve': (c_int, [P, c_int32, c_int32, P]),
     'rz_play_stop': (c_int, [P, P]),
     'rz_play_state': (c_int, [P, P, P, P, POINTER(c_int64)]),

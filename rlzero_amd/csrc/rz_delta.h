@@ -976,8 +976,10 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
-    const int game = blockIdx.x;
-    if (game >= res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier)
+    // (rz_set_playouts' order: the games with the most simulations in the first round of a grid of more than two games per CU)
+    const int game = res.order != nullptr ? res.order[blockIdx.x] : (int)blockIdx.x;
+    if ((unsigned)game >= (unsigned)res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier; an order's entry out of range: no game)
+    const int n_sims = res_sims(res, game);   // the GAME's simulations (uniform: a scalar register)
     const unsigned long long clk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
     const int tid0 = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     const int BW = nd.BW;
@@ -1049,7 +1051,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     }
     __syncthreads();
     int tiles_total = 0, tiles2_total = 0, deltas = 0, cells_total = 0;
-    for (int sim = 0; sim < res.n_sims; ++sim) {
+    for (int sim = 0; sim < n_sims; ++sim) {
         // (the thread's number is opaque per simulation: hipcc otherwise hoists the tree code's lane-dependent addresses out of this
         // loop and spills them)
         int tid_s = tid0;
@@ -1096,7 +1098,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         if (res.vh.groups == 128) rzt::value_quarter_lds<16>(res.vh, res_vrow, lane, wave, res_part);
         else rzt::value_quarter_lds<8>(res.vh, res_vrow, lane, wave, res_part);
         NET_TICK(16);
-        const bool more = sim + 1 < res.n_sims;
+        const bool more = sim + 1 < n_sims;
         if (wave == 0) {
             rzt::expand_backup_body<float, false, false, false, true>(res.E, nullptr, nullptr, game, lane, rz_raw_heads(), 0, res.vh, res_part);
         } else {
@@ -1135,7 +1137,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     }
     if (da.stats != nullptr && tid0 == 0) {
         atomicAdd(da.stats + 0, (unsigned)deltas);
-        atomicAdd(da.stats + 1, (unsigned)(res.n_sims - deltas));
+        atomicAdd(da.stats + 1, (unsigned)(n_sims - deltas));
         atomicAdd(da.stats + 2, (unsigned)tiles_total);
         atomicAdd(da.stats + 3, (unsigned)cells_total);
         atomicAdd(da.stats + 4, (unsigned)tiles2_total);

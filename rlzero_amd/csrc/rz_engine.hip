@@ -1155,6 +1155,13 @@ struct Play {
     double inv_t, margin;
     double *resign;            // [2] {threshold, disabled_frac} (rz_play_set_resign; NaN threshold: off)
     int resign_on;             // rz_play_set_resign called since rz_play_attach: k_play_draw reads `resign` (else never)
+    // playout cap randomization (rz_play_set_cap): a search has n_full simulations when cap_uniform(seed, game id, ply) < p_full,
+    // else n_fast
+    double *cap;               // [2] {n_fast, p_full} (NaN p_full: off -- every search has n_full)
+    int32_t *sims_of;          // [G] simulations of the slot's COMING search (k_play_apply, k_play_cap); read by the resident search
+    int32_t *order;            // [G] k_play_order's: the slots with a full search, those with a fast one, the inactive ones
+    int n_full;                // the engine's n_playout
+    int cap_on;                // rz_play_set_cap called since rz_play_attach: the kernels read `cap` (else never)
 };
 enum { kPlayIdle = 0, kPlayRunning = 1, kPlayStalled = 2 };
 constexpr int kStepResign = -3;   // Play::stepm of a slot whose mover resigned: k_play_apply ends the game without a step
@@ -1171,6 +1178,20 @@ __device__ __forceinline__ double play_uniform(uint64_t seed, uint64_t game, uin
 __device__ __forceinline__ double resign_uniform(uint64_t seed, uint64_t game) {
     const uint64_t x = mix64(mix64(seed ^ 0x72657369676E0000ull) ^ game);
     return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// rlzero_amd/selfplay.py: cap_uniform(seed, game id, ply) -- the search before ply `ply` of a game has the full budget when it is
+// below p_full (a chain of its own: apart from the move, noise and calibration streams)
+__device__ __forceinline__ double cap_uniform(uint64_t seed, uint64_t game, uint64_t ply) {
+    const uint64_t x = mix64(mix64(mix64(seed ^ 0x706C61796F757400ull) ^ game) ^ ply);
+    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+}
+__device__ __forceinline__ bool cap_full(const Play &Y, int64_t gid, int ply) {
+    const double p = Y.cap[1];
+    return !isnan(p) && cap_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply) < p;
+}
+__device__ __forceinline__ void cap_write(const Play &Y, int g, int64_t gid, int ply) {
+    Y.sims_of[g] = (isnan(Y.cap[1]) || cap_full(Y, gid, ply)) ? Y.n_full : (int)Y.cap[0];
 }
 
 // One wave per slot: the root's visit counts into the log, then the draw of alphazero_mcts.py:88-92,147-148 in fp64 -- taken only
@@ -1260,6 +1281,8 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
 #pragma unroll
     for (int j = 0; j < kWords; ++j) sh_e[64 * j + lane] = legal[j] ? exp(x[j] - mx) : 0.0;   // :12
     int extra = 0;   // RZ_PLAY_NO_RESIGN / RZ_PLAY_WOULD_RESIGN of a calibration game
+    // (rz_play_set_cap: the budget of the search behind this record -- what k_play_apply / k_play_cap wrote into sims_of for it)
+    const int full = (Y.cap_on && lane == 0 && cap_full(Y, gid, ply)) ? RZ_PLAY_FULL : 0;
     if (rs) {
         for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
         if (lane == 0) {
@@ -1273,7 +1296,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
                 extra = RZ_PLAY_NO_RESIGN | (fire ? RZ_PLAY_WOULD_RESIGN : 0);
             } else if (fire) {   // the mover resigns: no draw; k_play_apply ends the game
                 rec[3] = -1;
-                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_ENDED | RZ_PLAY_RESIGNED | ((1 - ply % 2) + 1) << 16;
+                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_ENDED | RZ_PLAY_RESIGNED | full | ((1 - ply % 2) + 1) << 16;
                 rec[6] = 0;
                 Y.keep[g] = -2;
                 Y.stepm[g] = kStepResign;
@@ -1306,13 +1329,13 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         rec[6] = __float_as_int((float)rel);
         if (ok) {
             rec[3] = chosen;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | extra;
+            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | extra | full;
             Y.ply[g] = ply + 1;
             Y.keep[g] = chosen;
             Y.stepm[g] = chosen;
         } else {
             rec[3] = -1;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_STALLED | extra;
+            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_STALLED | extra | full;
             Y.state[g] = kPlayStalled;
             E.active[g] = 0;   // the coming searches skip the slot until the host has decided
             Y.keep[g] = -2;
@@ -1354,7 +1377,11 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     }
     Y.stepm[g] = -1;
     Y.keep[g] = -2;
-    if (state != kPlayIdle) return;
+    if (state != kPlayIdle) {
+        // the budget of the slot's coming search (a stalled slot is not searched; k_play_draw has counted the ply already)
+        if (Y.cap_on && state == kPlayRunning) cap_write(Y, g, Y.game_id[g], Y.ply[g]);
+        return;
+    }
     int head = Y.queue_ctl[0];
     int64_t gid = -1;
     while (head < Y.queue_ctl[1]) {
@@ -1377,6 +1404,68 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     E.noise_key[g] = mix64(mix64(Y.seed ^ 0x6E6F697365000000ull) ^ (uint64_t)gid);   // rlzero_amd/selfplay.py: _start
     E.noise_ctr[g] = 0;
     E.active[g] = 1;
+    if (Y.cap_on) cap_write(Y, g, gid, 0);
+}
+
+// rz_play_set_cap: the rule into its device array, then the budgets of the searches that are coming under it
+__global__ void k_play_cap(Dev E, Play Y, double n_fast, double p_full) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.n_games) return;
+    const int64_t gid = Y.game_id[g];
+    const int ply = Y.ply[g];
+    const bool full = isnan(p_full) || gid < 0 || cap_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply) < p_full;
+    Y.sims_of[g] = full ? Y.n_full : (int)n_fast;
+    if (g == 0) {
+        Y.cap[0] = n_fast;
+        Y.cap[1] = p_full;
+    }
+}
+
+// The order of k_delta_res's workgroups under per-game budgets: a STABLE partition of the slots -- full budget (>= n_full), fewer
+// simulations, inactive -- so that no full search starts in the last round of a grid of more than two games per CU.  ONE workgroup,
+// any number of games in chunks of 256: ballot + mbcnt prefix per wave, the waves' totals through LDS.
+__global__ __launch_bounds__(256) void k_play_order(const uint8_t *__restrict__ active, const int32_t *__restrict__ sims_of, int n_full,
+                                                    int n_games, int32_t *__restrict__ order) {
+    __shared__ int cnt[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int run[3] = {0, 0, 0};   // the next free place of each class (uniform)
+    // pass 1: the classes' totals -> where each begins
+    int t0 = 0, t1 = 0;
+    for (int c0 = 0; c0 < n_games; c0 += 256) {
+        const int g = c0 + tid;
+        const bool act = g < n_games && active[g] != 0;
+        const bool full = act && sims_of[g] >= n_full;
+        t0 += __popcll(__ballot(full));
+        t1 += __popcll(__ballot(act && !full));
+    }
+    if (lane == 0) cnt[wave][0] = t0, cnt[wave][1] = t1;
+    __syncthreads();
+    for (int w = 0; w < 4; ++w) run[1] += cnt[w][0], run[2] += cnt[w][0] + cnt[w][1];
+    __syncthreads();
+    // pass 2: every slot to its place
+    for (int c0 = 0; c0 < n_games; c0 += 256) {
+        const int g = c0 + tid;
+        const bool act = g < n_games && active[g] != 0;
+        const int cls = g >= n_games ? -1 : !act ? 2 : sims_of[g] >= n_full ? 0 : 1;
+        int before = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned long long m = __ballot(cls == c);
+            const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+            if (cls == c) before = pre;
+            if (lane == 0) cnt[wave][c] = __popcll(m);
+        }
+        __syncthreads();
+        if (cls >= 0) {
+            int at = run[cls] + before;
+            for (int w = 0; w < wave; ++w) at += cnt[w][cls];
+            order[at] = g;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            for (int w = 0; w < 4; ++w) run[c] += cnt[w][c];
+        __syncthreads();
+    }
 }
 
 __global__ void k_play_resolve(Play Y, int slot, int move) { Y.mailbox[slot] = move; }
@@ -1437,6 +1526,10 @@ struct rz_engine {
     Play play = {};      // rz_play_attach
     bool play_on = false, play_drawn = false;
     long long play_steps = 0;   // move steps enqueued (rz_play_apply calls) since rz_play_attach
+    // rz_set_playouts: the host's per-game simulation counts (and workgroup order) of the resident search, copies of the caller's
+    int32_t *pl_counts = nullptr, *pl_order = nullptr;
+    bool pl_on = false, pl_ordered = false;
+    bool cap_ordered = true;   // rz_play_set_cap_order: k_play_order runs and the resident search follows it
 };
 
 namespace {
@@ -1730,6 +1823,14 @@ int rz_log_table_size(rz_engine *e, int64_t *count) {
         if ((p) == nullptr) return fail(RZ_ERR_ARG, "%s is NULL", #p);   \
     } while (0)
 
+// per-game simulation counts exist in the resident search only (rz_net_search_resident): the step-by-step routes refuse them
+#define RZ_NO_PLAYOUTS(e)                                                                                                             \
+    do {                                                                                                                              \
+        if ((e)->pl_on || ((e)->play_on && (e)->play.cap_on))                                                                         \
+            return fail(RZ_ERR_ARG, "%s: per-game simulation counts (rz_set_playouts, rz_play_set_cap) are served by the resident "  \
+                                    "search only (rz_net_search_resident); clear them for this route", __func__);                    \
+    } while (0)
+
 static inline dim3 per_game(const rz_engine *e) { return dim3((unsigned)e->cfg.n_games); }
 static inline dim3 per_leaf(const rz_engine *e) { return dim3((unsigned)(e->cfg.n_games * e->dev.K)); }
 static inline dim3 flat_grid(const rz_engine *e) { return dim3((unsigned)((e->cfg.n_games + 255) / 256)); }
@@ -1835,6 +1936,7 @@ int rz_eval_rollout(rz_engine *e, uint64_t seed, uint32_t sim_index, int32_t n_l
 
 int rz_expand_backup(rz_engine *e, const float *d_logp, const float *d_value, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
     if (e->dev.K > 1) {
         if (e->ml) k_tree_step_ml<false><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, d_logp, d_value, RawHeads(), nullptr, e->kb, 0);
@@ -1847,6 +1949,7 @@ int rz_expand_backup(rz_engine *e, const float *d_logp, const float *d_value, vo
 
 int rz_expand_backup_f64(rz_engine *e, const float *d_logp, const double *d_value, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
     if (e->dev.K > 1) return fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
     k_expand_backup<double><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value);
@@ -1855,6 +1958,7 @@ int rz_expand_backup_f64(rz_engine *e, const float *d_logp, const double *d_valu
 
 int rz_expand_backup_probs(rz_engine *e, const float *d_probs, const double *d_value, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
     if (e->dev.K > 1) return fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
     k_expand_backup<double, true><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_probs, d_value);
@@ -1863,6 +1967,7 @@ int rz_expand_backup_probs(rz_engine *e, const float *d_probs, const double *d_v
 
 int rz_tree_step(rz_engine *e, const float *d_logp, const float *d_value, float *d_obs, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
     e->n_select += 1;
     if (e->dev.K > 1) {
@@ -1885,6 +1990,7 @@ static int raw_heads_ok(rz_engine *e, const rz_raw_heads *h) {
 
 int rz_expand_backup_raw(rz_engine *e, const rz_raw_heads *heads, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     int rc = raw_heads_ok(e, heads);
     if (rc != RZ_OK) return rc;
     const RawHeads rh = *heads;
@@ -1956,6 +2062,7 @@ int rz_expand_backup_deferred(rz_engine *e, const rz_value_head *head, void *str
     int rc = check_engine(e);
     if (rc != RZ_OK) return rc;
     if ((rc = deferred_ok(e, head)) != RZ_OK) return rc;
+    RZ_NO_PLAYOUTS(e);
     const dim3 block(kWave * kDefWaves);
     switch (head->groups) {   // = 4 waves x 2 halves x PER
         case 16: k_expand_backup_def<2><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head); break;
@@ -1970,6 +2077,7 @@ int rz_tree_step_deferred(rz_engine *e, const rz_value_head *head, void *stream)
     int rc = check_engine(e);
     if (rc != RZ_OK) return rc;
     if ((rc = deferred_ok(e, head)) != RZ_OK) return rc;
+    RZ_NO_PLAYOUTS(e);
     e->n_select += 1;
     const dim3 block(kWave * kDefWaves);
     if (e->dev.trace && head->groups == 128) {   // (the traced instantiation exists for the 15 x 15 board's head: rz_trace_attach)
@@ -2001,6 +2109,7 @@ int rz_deferred_flush(rz_engine *e, const rz_deferred_logits *logits, int32_t n_
 
 int rz_tree_step_raw(rz_engine *e, const rz_raw_heads *heads, float *d_obs, void *stream) {
     RZ_ENTER(e);
+    RZ_NO_PLAYOUTS(e);
     int rc = raw_heads_ok(e, heads);
     if (rc != RZ_OK) return rc;
     e->n_select += 1;
@@ -2085,6 +2194,9 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
         if (Y.stepm == nullptr && (rc = dev_alloc(e, &Y.stepm, G)) != RZ_OK) return rc;
         if (Y.step_ab == nullptr && (rc = dev_alloc(e, &Y.step_ab, 2)) != RZ_OK) return rc;
         if (Y.resign == nullptr && (rc = dev_alloc(e, &Y.resign, 2)) != RZ_OK) return rc;
+        if (Y.cap == nullptr && (rc = dev_alloc(e, &Y.cap, 2)) != RZ_OK) return rc;
+        if (Y.sims_of == nullptr && (rc = dev_alloc(e, &Y.sims_of, G)) != RZ_OK) return rc;
+        if (Y.order == nullptr && (rc = dev_alloc(e, &Y.order, G)) != RZ_OK) return rc;
         if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
     }
     Y.queue_ids = cfg->d_queue_ids;
@@ -2110,6 +2222,8 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.inv_t = 1.0 / cfg->temperature;
     Y.margin = cfg->stall_margin > 0.0 ? cfg->stall_margin : 1e-10 * (Y.inv_t > 1.0 ? Y.inv_t : 1.0);
     Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
+    Y.cap_on = 0;      // (and so is the playout cap: rz_play_set_cap)
+    Y.n_full = e->cfg.n_playout;
     RZ_HIP(hipMemset(Y.step_ab, 0, 8));
     RZ_HIP(hipMemset(Y.ply, 0, (size_t)G * 4));
     RZ_HIP(hipMemset(Y.top_hwm, 0, (size_t)G * 4));
@@ -2135,6 +2249,8 @@ int rz_play_apply(rz_engine *e, void *stream) {
     const Play &Y = e->play;
     if (!e->play_drawn) k_play_no_draw<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(Y);   // (the step counter k_play_draw would have handed on)
     k_play_apply<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, Y, e->play_drawn ? 1 : 0);
+    // (rz_play_set_cap: the workgroup order of the coming search, from the budgets k_play_apply has just written)
+    if (Y.cap_on && e->cap_ordered) k_play_order<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(e->dev.active, Y.sims_of, Y.n_full, e->cfg.n_games, Y.order);
     e->play_drawn = false;
     e->play_steps += 1;
     return launched("k_play_apply");
@@ -2147,6 +2263,82 @@ int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, voi
     k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
     e->play.resign_on = 1;
     return launched("k_play_set_resign");
+}
+
+static int playouts_route_ok(rz_engine *e, const char *what) {
+    if (e->dev.K != 1 || e->dev.score_mode != RZ_SCORE_UCT_REF)
+        return fail(RZ_ERR_ARG, "%s: per-game simulation counts need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)", what);
+    return RZ_OK;
+}
+
+int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream) {
+    RZ_ENTER(e);
+    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    int rc = playouts_route_ok(e, "rz_play_set_cap");
+    if (rc != RZ_OK) return rc;
+    if (!std::isnan(p_full)) {
+        if (!(p_full > 0.0 && p_full <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_cap: p_full %g not in (0, 1]", p_full);
+        if (n_fast < 1 || n_fast > e->cfg.n_playout) return fail(RZ_ERR_ARG, "rz_play_set_cap: n_fast %d not in 1 .. n_playout = %d", n_fast, e->cfg.n_playout);
+    }
+    const Play &Y = e->play;
+    k_play_cap<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, Y, (double)n_fast, p_full);
+    k_play_order<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(e->dev.active, Y.sims_of, Y.n_full, e->cfg.n_games, Y.order);
+    e->play.cap_on = 1;
+    return launched("k_play_cap");
+}
+
+int rz_play_set_cap_order(rz_engine *e, int32_t longest_first) {
+    if (e == nullptr) return fail(RZ_ERR_ARG, "engine handle is NULL");
+    e->cap_ordered = longest_first != 0;
+    return RZ_OK;
+}
+
+int rz_set_playouts(rz_engine *e, const int32_t *d_counts, const int32_t *d_order, void *stream) {
+    RZ_ENTER(e);
+    if (d_counts == nullptr) {
+        if (d_order != nullptr) return fail(RZ_ERR_ARG, "rz_set_playouts: an order without counts");
+        e->pl_on = e->pl_ordered = false;
+        return RZ_OK;
+    }
+    int rc = playouts_route_ok(e, "rz_set_playouts");
+    if (rc != RZ_OK) return rc;
+    const long long G = e->cfg.n_games;
+    if (e->pl_counts == nullptr && (rc = dev_alloc(e, &e->pl_counts, G)) != RZ_OK) return rc;
+    if (e->pl_order == nullptr && (rc = dev_alloc(e, &e->pl_order, G)) != RZ_OK) return rc;
+    RZ_HIP(hipMemcpyAsync(e->pl_counts, d_counts, (size_t)G * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
+    if (d_order != nullptr) RZ_HIP(hipMemcpyAsync(e->pl_order, d_order, (size_t)G * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
+    e->pl_on = true;
+    e->pl_ordered = d_order != nullptr;
+    return RZ_OK;
+}
+
+int rz_playouts_view(rz_engine *e, const int32_t **d_counts, const int32_t **d_order) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if (!d_counts || !d_order) return fail(RZ_ERR_ARG, "NULL output pointer");
+    *d_counts = *d_order = nullptr;
+    if (e->pl_on) {   // the host's counts come before the device's rule
+        *d_counts = e->pl_counts;
+        *d_order = e->pl_ordered ? e->pl_order : nullptr;
+    } else if (e->play_on && e->play.cap_on) {
+        *d_counts = e->play.sims_of;
+        *d_order = e->cap_ordered ? e->play.order : nullptr;
+    }
+    return RZ_OK;
+}
+
+int rz_playouts_read(rz_engine *e, int32_t *h_counts, int32_t *h_order, int32_t *h_source) {
+    RZ_ENTER(e);
+    RZ_NEED(h_source);
+    const int32_t *dc = nullptr, *dor = nullptr;
+    int rc = rz_playouts_view(e, &dc, &dor);
+    if (rc != RZ_OK) return rc;
+    RZ_HIP(hipDeviceSynchronize());
+    const size_t G = (size_t)e->cfg.n_games;
+    if (dc != nullptr && h_counts != nullptr) RZ_HIP(hipMemcpy(h_counts, dc, G * 4, hipMemcpyDeviceToHost));
+    if (dor != nullptr && h_order != nullptr) RZ_HIP(hipMemcpy(h_order, dor, G * 4, hipMemcpyDeviceToHost));
+    *h_source = dc == nullptr ? 0 : (e->pl_on ? 1 : 2) | (dor != nullptr ? 4 : 0);
+    return RZ_OK;
 }
 
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream) {

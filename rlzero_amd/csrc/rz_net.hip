@@ -900,9 +900,19 @@ template <> struct ResArgs<true> {
     rz_value_head vh;    // valfeat unused: the inputs stay in LDS
     int n_sims;          // simulations of this launch: n_sims x (trunk, expand / backup), a selection between two of them
     int select_first;    // != 0: the launch begins with the selection of the first leaf itself (no rz_select_step before it)
+    // rz_set_playouts (NULL: every game runs n_sims): game g runs min(sims_of[g], n_sims) simulations -- n_sims stays the launch's
+    // maximum, the store slots pend[g] .. pend[g] + n_sims - 1 stay reserved for it; `order` (k_delta_res only, NULL: identity):
+    // workgroup b searches game order[b]
+    const int32_t *sims_of;
+    const int32_t *order;
 };
-__device__ __forceinline__ int res_sims(const ResArgs<false> &) { return 0; }
-__device__ __forceinline__ int res_sims(const ResArgs<true> &r) { return r.n_sims; }
+// the simulations of `game`'s workgroup: one load from a uniform address, once per workgroup
+__device__ __forceinline__ int res_sims(const ResArgs<false> &, int) { return 0; }
+__device__ __forceinline__ int res_sims(const ResArgs<true> &r, int game) {
+    if (r.sims_of == nullptr) return r.n_sims;
+    const int n = __builtin_amdgcn_readfirstlane(r.sims_of[game]);
+    return n < r.n_sims ? n : r.n_sims;
+}
 
 // Deferred priors (rz_value_head, include/rlzero_hip.h): where a board's features go when no FC GEMM follows the trunk -- the policy
 // pieces into slot slot_of[board] of a store of `slot_halfs` f16 values per slot (tiles of groups_act K-steps), the value head's
@@ -948,9 +958,11 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
     __shared__ float res_part[RES ? rzt::kDefWaves : 1][RES ? rzt::kWave : 1];
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[RES ? 2 * RZ_BOARD_WORDS + 1 : 1];
     int res_slot0 = 0;
+    int res_n = 0;   // (RES: the simulations of this workgroup's game)
     if constexpr (RES) {
         if ((int)blockIdx.x >= n_boards || res.E.active[blockIdx.x] == 0) return;   // (uniform: before any barrier)
         res_slot0 = res.E.pend[blockIdx.x];
+        res_n = res_sims(res, blockIdx.x);
         res_vrow[threadIdx.x] = 0.0f;
     }
     constexpr int POS = RW * RH, IC = RW + 2;   // positions of the halo grid; columns of the observation planes' grid
@@ -1131,7 +1143,7 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
     NET_TICK(15);
     prof_acc[9] = prof_t - prof_k0;   // the prologue
 #endif
-    for (int board = blockIdx.x, sim = 0; RES ? sim < res_sims(res) : board < n_boards; RES ? (void)++sim : (void)(board += gridDim.x)) {
+    for (int board = blockIdx.x, sim = 0; RES ? sim < res_n : board < n_boards; RES ? (void)++sim : (void)(board += gridDim.x)) {
     int tid = tid0;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1530,7 +1542,7 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
         else __syncthreads();   // (the barrier inside the body, where the quarters meet)
         __syncthreads();        // the tree's updates before the selection's loads
         NET_TICK(17);
-        const bool more = sim + 1 < res_sims(res);
+        const bool more = sim + 1 < res_n;
         if (wave == 0 && more) rzt::select_body<false, kResWords>(res.E, nullptr, game, lane, 0, res_leaf);
         if (RW != kRowW && RZ_SPLIT_TREE_PRIO) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
@@ -1731,9 +1743,11 @@ __device__ __forceinline__ void trunk_rows_body(const NetDev &nd, const float *_
     __shared__ float res_part[RES ? rzt::kDefWaves : 1][RES ? rzt::kWave : 1];
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[RES ? 2 * RZ_BOARD_WORDS + 1 : 1];
     int res_slot0 = 0;
+    int res_n = 0;   // (RES: the simulations of this workgroup's game)
     if constexpr (RES) {
         if ((int)blockIdx.x >= n_boards || res.E.active[blockIdx.x] == 0) return;   // (uniform: before any barrier)
         res_slot0 = res.E.pend[blockIdx.x];
+        res_n = res_sims(res, blockIdx.x);
         for (int i = threadIdx.x; i < 512; i += 256) res_vrow[i] = 0.0f;
     }
 #ifdef RZ_NET_PROFILE
@@ -1910,7 +1924,7 @@ __device__ __forceinline__ void trunk_rows_body(const NetDev &nd, const float *_
     prof_acc[9] = prof_t - prof_k0;   // the prologue
 #endif
     // (RES: the "boards" of this workgroup are the leaves of its game's simulations, one after the other)
-    for (int board = blockIdx.x, sim = 0; RES ? sim < res_sims(res) : board < n_boards; RES ? (void)++sim : (void)(board += gridDim.x)) {
+    for (int board = blockIdx.x, sim = 0; RES ? sim < res_n : board < n_boards; RES ? (void)++sim : (void)(board += gridDim.x)) {
     int tid = tid0;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2114,7 +2128,7 @@ __device__ __forceinline__ void trunk_rows_body(const NetDev &nd, const float *_
         else __syncthreads();   // (the barrier inside the body, where the quarters meet)
         __syncthreads();        // the tree's updates before the selection's loads
         NET_TICK(17);
-        const bool more = sim + 1 < res_sims(res);
+        const bool more = sim + 1 < res_n;
         if (wave == 0 && more) rzt::select_body<false>(res.E, nullptr, game, lane, 0, res_leaf);
         __syncthreads();
         NET_TICK(18);
@@ -3507,6 +3521,11 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     res.vh.groups = net->vf_groups;
     res.n_sims = n_sims;
     res.select_first = select_first ? 1 : 0;
+    // rz_set_playouts: a game with fewer simulations leaves the slots pend[g] + sims_of[g] .. of the feature store as they were
+    // (zeros, or finite features of an earlier search).  They are NOT skipped: rz_net_deferred_gemm runs over them -- rows do not mix,
+    // the GEMM raises no range flag (only the trunk's stores do) -- and what it computes there is IGNORED: k_deferred_priors reads the
+    // slots below pend[g] only, and pend[g] counts the leaves the game stored.
+    if ((rc = rz_playouts_view(engine, &res.sims_of, &res.order)) != RZ_OK) return rc;
     const DeferredOut later{dev.pend, (long long)net->store_tiles * net->dev.groups_act * 1024, nullptr, 0, nullptr, net->store_slots};
     const LeafBits leaves{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last};
     const dim3 grid((unsigned)dev.n_games);

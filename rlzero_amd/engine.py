@@ -680,6 +680,7 @@ class MCTSEngine(object):
         # cap of an evaluator's store + logits (a flush every slots steps when n_playout needs more): a whole 800-simulation search of
         # 4096 games is 15 GB of 288 -- below the cap the search is one launch and the move one hipGraph (19 MB per slot at 4096 games)
         self.deferred_max_bytes = 32 << 30
+        self._playouts = None   # set_playouts: (counts, order) device tensors of the per-game simulation counts in force
 
     # ------------------------------------------------------------------ plumbing
     def stream(self):
@@ -852,6 +853,9 @@ class MCTSEngine(object):
             return
         K = self.sims_in_flight
         r = self._ask(evaluator)[0] if r is None else r
+        if not r.resident and (self._playouts is not None or getattr(self, 'play_cap_on', False)):
+            raise ValueError('per-game simulation counts (set_playouts, play_set_cap) need the resident search: this evaluator\'s '
+                             'route for this engine has none')
         if not r.deferred:
             self.flush_deferred()   # (an evaluator of another route takes over: its expansions write their priors at once)
         if isinstance(evaluator, HostEvaluator):
@@ -963,6 +967,8 @@ class MCTSEngine(object):
         lib, h = self.lib, self.handle
         while n > 0:
             m = self._deferred_begin(evaluator, n)
+            if m < n and (self._playouts is not None or getattr(self, 'play_cap_on', False)):
+                raise ValueError('per-game simulation counts need the whole search in one launch: %d simulations, %d store slots' % (n, m))
             if resident:   # the m simulations in ONE launch, one workgroup per game, the first selection included
                 evaluator.search_resident(self, m, True)
             else:
@@ -1037,6 +1043,48 @@ class MCTSEngine(object):
                 self._def_stream = self.torch.cuda.current_stream(self.device)
             graph.replay()
         self.sim_chunk(evaluator, rest, r)
+
+    def set_playouts(self, counts, longest_first=True, order=None):
+        """Per-game simulation counts of the resident search (rz_set_playouts): game g of the coming ``simulate`` / ``sim_chunk``
+        calls runs min(counts[g], n_sims) simulations and ends with the tree, priors and values of a uniform search of that many.
+        ``counts``: n_games integers >= 1, or None: every game n_sims again.  ``longest_first``: the workgroups of the
+        receptive-field kernel (k_delta_res) take the games in descending order of their counts (stable), so that no long search
+        starts in the last round of a launch of more than two games per CU; ``order``: an explicit permutation instead.  The order
+        changes no result.  Routes without a resident search refuse: ValueError here for what the engine knows (PUCT,
+        sims_in_flight > 1), ValueError from the search for an evaluator without one."""
+        t = self.torch
+        if counts is None:
+            check(self.lib.rz_set_playouts(self.handle, None, None, self.stream()), 'rz_set_playouts')
+            self._playouts = None
+            return
+        if self.sims_in_flight != 1 or self.score_mode != _hip.SCORE_UCT_REF:
+            raise ValueError('per-game simulation counts need the resident search (score_mode uct_ref, sims_in_flight 1)')
+        c = np.asarray(counts)
+        if c.shape != (self.n_games, ) or not np.issubdtype(c.dtype, np.integer) or (c < 1).any() or (c > 0x7FFFFFFF).any():
+            raise ValueError('counts: %d integers >= 1, one per game' % self.n_games)
+        c = c.astype(np.int32)
+        if order is not None:
+            o = np.asarray(order, dtype=np.int64)
+            if o.shape != c.shape or (np.sort(o) != np.arange(self.n_games)).any():
+                raise ValueError('order: a permutation of the %d games' % self.n_games)
+        else:
+            o = np.argsort(-c.astype(np.int64), kind='stable') if longest_first else None
+        dc = t.from_numpy(c).to(self.device)
+        do = None if o is None else t.from_numpy(o.astype(np.int32)).to(self.device)
+        check(self.lib.rz_set_playouts(self.handle, _ptr(dc), None if do is None else _ptr(do), self.stream()), 'rz_set_playouts')
+        self._playouts = (dc, do)
+
+    def playouts(self):
+        """-> (counts int32 [G] or None, order int32 [G] or None, 'host' / 'device' / None): the per-game simulation counts and the
+        workgroup order the next resident search reads -- set_playouts' (host), else play_set_cap's (device); synchronises."""
+        counts, order = np.zeros(self.n_games, np.int32), np.zeros(self.n_games, np.int32)
+        source = ctypes.c_int32(0)
+        check(self.lib.rz_playouts_read(self.handle, ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(order.ctypes.data),
+                                        ctypes.byref(source)), 'rz_playouts_read')
+        src = source.value
+        if src == 0:
+            return None, None, None
+        return counts, (order if src & 4 else None), 'host' if src & 3 == 1 else 'device'
 
     def warm_graph(self, evaluator, per):
         """Capture ``per`` simulations into a hipGraph (torch.cuda.CUDAGraph around our launches
@@ -1197,6 +1245,7 @@ class MCTSEngine(object):
             attach()
         self.play_steps = 0
         self.play_resign_on = False   # (rz_play_attach turns resignation off)
+        self.play_cap_on = False      # (and the playout cap)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log
@@ -1224,6 +1273,8 @@ class MCTSEngine(object):
         if not r.resident or getattr(self, 'play_log', None) is None:
             return None
         n = self.n_playout
+        if self._playouts is not None:
+            raise HipError('warm_move_graph: clear set_playouts first (the graph would hold the host\'s counts, not play_set_cap\'s)')
         self.flush_deferred()
         if self._deferred_begin(evaluator, n) < n or self._def_slots < n:   # (reserves the store; a search must fit between two flushes)
             return None
@@ -1275,6 +1326,25 @@ class MCTSEngine(object):
         resignation-free draw (``play_resign_on`` tells: capture again)."""
         check(self.lib.rz_play_set_resign(self.handle, float(threshold), float(disabled_frac), self.stream()), 'rz_play_set_resign')
         self.play_resign_on = True
+
+    def play_set_cap(self, n_fast, p_full):
+        """Playout cap randomization of the move step on the device (rz_play_set_cap), enqueued on the current stream: the search
+        before ply ``ply`` of game ``gid`` has n_playout simulations when selfplay.cap_uniform(seed, gid, ply) < ``p_full``, else
+        ``n_fast``; records of full searches carry PLAY_FULL.  ``p_full`` NaN: off.  After play_attach; a whole-move graph captured
+        before the first call since play_attach has no cap (``play_cap_on`` tells: capture again) -- later values reach it as they
+        are.  ValueError where the engine has no resident search (PUCT, sims_in_flight > 1)."""
+        p_full = float(p_full)
+        if self.sims_in_flight != 1 or self.score_mode != _hip.SCORE_UCT_REF:
+            raise ValueError('the playout cap needs the resident search (score_mode uct_ref, sims_in_flight 1)')
+        if not np.isnan(p_full) and not (0.0 < p_full <= 1.0 and 1 <= int(n_fast) <= self.n_playout):
+            raise ValueError('playout cap: n_fast %r in 1 .. n_playout = %d, p_full %r in (0, 1]' % (n_fast, self.n_playout, p_full))
+        check(self.lib.rz_play_set_cap(self.handle, int(n_fast), p_full, self.stream()), 'rz_play_set_cap')
+        self.play_cap_on = True
+
+    def play_set_cap_order(self, longest_first):
+        """Whether play_set_cap's searches follow the device's longest-first partition (default) or the slot order; before the move
+        graph is captured."""
+        check(self.lib.rz_play_set_cap_order(self.handle, 1 if longest_first else 0), 'rz_play_set_cap_order')
 
     def play_resolve(self, slot, move):
         check(self.lib.rz_play_resolve(self.handle, int(slot), int(move), self.stream()), 'rz_play_resolve')

@@ -54,6 +54,19 @@ def resign_uniform(seed, game_id):
     return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
+_CAP_SALT = np.uint64(0x706C61796F757400)   # ("playout": the budget draw's own stream)
+
+
+def cap_uniform(seed, game_id, ply):
+    """Uniform in [0,1) for (seed, game, ply) of playout cap randomization: the search before ply ``ply`` of the game has the full
+    budget when it is below ``p_full`` (the device's cap_uniform, the same bits)."""
+    with np.errstate(over='ignore'):
+        x = _splitmix64(np.uint64(seed) ^ _CAP_SALT)
+        x = _splitmix64(x ^ np.asarray(game_id, dtype=np.uint64))
+        x = _splitmix64(x ^ np.asarray(ply, dtype=np.uint64))
+    return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
 def fp_margin(resign_stats, winner):
     """The lowest resignation statistic a non-loser saw on their own plies (player 0 moves the even plies; on a tie both players
     count): a calibration game would have been resigned by a player who did not lose at every threshold above it.  NaN statistics
@@ -128,11 +141,14 @@ class Trajectory(object):
     """One finished game: what start_self_play returns, in compact form."""
 
     def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku', resigned=False, no_resign=False,
-                 resign_stats=None, fp_margin=np.nan):
+                 resign_stats=None, fp_margin=np.nan, full=None):
         """Resignation (BatchedSelfPlay.set_resign): ``resigned`` -- the game ended with the loser's resignation; ``moves`` / ``pis``
         are the plies actually played (the resigning search's pi is not recorded).  ``no_resign``: a calibration game (played
         out).  ``resign_stats``: float32 max(v_root, q_best) of every search of the game -- one more than the moves of a resigned
-        game --, None with resignation off.  ``fp_margin``: a calibration game's selfplay.fp_margin, else NaN."""
+        game --, None with resignation off.  ``fp_margin``: a calibration game's selfplay.fp_margin, else NaN.
+        Playout cap (BatchedSelfPlay.set_playout_cap): ``full`` -- a bool per search of the game, True where it had the full budget
+        (one entry more than the moves of a resigned game, like ``resign_stats``); None with the cap off."""
+        self.full = None if full is None else np.asarray(full, dtype=bool).reshape(-1)
         self.resigned, self.no_resign = bool(resigned), bool(no_resign)
         self.resign_stats = None if resign_stats is None else np.asarray(resign_stats, dtype=np.float32)
         self.fp_margin = np.float32(fp_margin)
@@ -194,6 +210,14 @@ class Trajectory(object):
     def as_reference_tuple(self):
         """(winner, [(state, mcts_prob, z), ...]) -- start_self_play's return value."""
         return self.winner, list(zip(self.states(), list(self.pis), self.z()))
+
+    def training_samples(self):
+        """[(state, mcts_prob, z), ...] of the plies a learner takes its policy target from: under a playout cap the plies whose
+        search had the full budget (``full``), each with its own state and z; every ply without a cap."""
+        samples = list(zip(self.states(), list(self.pis), self.z()))
+        if self.full is None:
+            return samples
+        return [sm for sm, f in zip(samples, self.full[:len(self.moves)]) if f]
 
 
 
@@ -422,6 +446,49 @@ class BatchedSelfPlay(object):
         self.moves_done = 0
         self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
         self.resign_would = 0   # plies of calibration games where the rule fired (RZ_PLAY_WOULD_RESIGN on the device)
+        self.playout_cap = None   # set_playout_cap: (n_fast, p_full)
+        self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
+        self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
+        self.full_plies = 0   # searches with the full budget so far (with the cap off: every search)
+
+    def set_playout_cap(self, n_fast, p_full=None):
+        """Playout cap randomization (KataGo, Wu 2019, section 3.1; an opt-in extension) for every lane and BOTH loops (run,
+        run_device): the search before ply ``ply`` of game ``gid`` has n_playout simulations when cap_uniform(seed, gid, ply) <
+        ``p_full`` and ``n_fast`` otherwise, so a game depends on (seed, game id, cap) only.  Trajectory.full tells which plies had
+        the full budget; Trajectory.training_samples() keeps those.  ``n_fast`` None: off.  Between runs; like set_resign, the first
+        cap on an attached object whose whole-move graphs were captured without one attaches again, later values reach the graphs
+        as they are.  Dirichlet noise and temperature are untouched: KataGo also drops the noise on fast moves, which is
+        deliberately out of scope here.  ValueError for values out of range and for lanes without a resident search (two-launch
+        lanes, PUCT, sims_in_flight > 1, host evaluators)."""
+        if n_fast is None:
+            self.playout_cap = None
+            for lane in self.lanes:
+                with self._on(lane):
+                    lane.eng.set_playouts(None)
+        else:
+            n_fast, p_full = int(n_fast), float(p_full if p_full is not None else 'nan')
+            if not 1 <= n_fast <= self.eng.n_playout:
+                raise ValueError('n_fast %d not in 1 .. n_playout = %d' % (n_fast, self.eng.n_playout))
+            if not 0.0 < p_full <= 1.0:
+                raise ValueError('p_full %r not in (0, 1]' % p_full)
+            for lane in self.lanes:
+                if not lane.eng._ask(lane.evaluator)[0].resident:
+                    raise ValueError('the playout cap needs the resident search on every lane (this route has none: two-launch lanes, '
+                                     'PUCT, sims_in_flight > 1 and host evaluators search every game alike)')
+            self.playout_cap = (n_fast, p_full)
+        if not getattr(self, '_dev_on', False):
+            return
+        if self.playout_cap is not None and any(lane.move_graph is not None and not lane.eng.play_cap_on for lane in self.lanes):
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the cap before the capture)
+            return
+        for lane in self.lanes:
+            if self.playout_cap is not None or lane.eng.play_cap_on:
+                with self._on(lane):
+                    lane.eng.play_set_cap(*(self.playout_cap or (1, float('nan'))))
+
+    def _full(self, game_ids, plies):
+        """-> bool per (game, ply): the search has the full budget under the current cap."""
+        return cap_uniform(self.seed, game_ids, plies) < self.playout_cap[1]
 
     @property
     def resign_on(self):
@@ -468,7 +535,7 @@ class BatchedSelfPlay(object):
     def for_network(cls, net_module, board, n_in_row, n_games, n_playout, c_puct=5.0, device='cuda:0',
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
-                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, **engine_kw):
+                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None, **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -485,7 +552,8 @@ class BatchedSelfPlay(object):
         evaluator -- None keeps the default ('split_f16', the f32-accurate trunk); 'split_f16_fp8' is the OPT-IN arithmetic narrower than
         the reference's f32 (boards of 11 .. 16 rows and columns).  ``delta_trunk``: False = the full-board trunk on every leaf (the
         checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU).
-        ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign."""
+        ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign.  ``playout_cap``: None (off) or (n_fast, p_full):
+        set_playout_cap."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -550,6 +618,8 @@ class BatchedSelfPlay(object):
         sp.lanes_measured = measured   # {lanes: simulations / s} when the layout was chosen by measurement, else None
         if resign is not None:
             sp.set_resign(*(resign if isinstance(resign, (tuple, list)) else (resign, )))
+        if playout_cap is not None:
+            sp.set_playout_cap(*playout_cap)
         if before_warm is not None:
             before_warm(sp)
         sp.warm_graphs()
@@ -591,6 +661,7 @@ class BatchedSelfPlay(object):
             self.slot_moves[s] = []
             self.slot_pis[s] = []
             self.slot_stats[s] = []
+            self.slot_full[s] = []
         # a game's Dirichlet noise (read by the PUCT rule only), like its move draws, is keyed by (seed, game id): the trajectory
         # does not depend on the slot, lane or GPU the game is played on
         with np.errstate(over='ignore'):
@@ -651,11 +722,16 @@ class BatchedSelfPlay(object):
                     with self._on(lane):
                         lane.eng.sim_chunk(lane.evaluator, min(chunk, n - c0))
 
-    def _simulate_lane(self, lane):
-        """Enqueue the n_playout simulations of ONE lane on its stream (graph replays + the eager remainder)."""
+    def _simulate_lane(self, lane, host_counts=True):
+        """Enqueue the n_playout simulations of ONE lane on its stream (graph replays + the eager remainder).  ``host_counts``: under
+        a playout cap the budgets come from here (the host-driven loop); False: from the device's move step."""
         n = self.eng.n_playout
         with self._on(lane):
             r = lane.eng._ask(lane.evaluator)[0]
+            if host_counts and self.playout_cap is not None:
+                gids, plies = self.slot_game[lane.slots], self.slot_ply[lane.slots]
+                full = self._full(np.maximum(gids, 0), plies) | (gids < 0)   # (an idle slot is not searched)
+                lane.eng.set_playouts(np.where(full, n, self.playout_cap[0]).astype(np.int32), longest_first=self.cap_longest_first)
             if r.resident:   # one launch for the whole search: no graph, no chunks
                 lane.eng.sim_chunk(lane.evaluator, n, r)
                 return
@@ -684,7 +760,15 @@ class BatchedSelfPlay(object):
             # and the query waits for the device)
             if hasattr(getattr(lane.evaluator, 'hip', None), 'check_flags') and getattr(lane.evaluator, 'needs_obs', True):
                 lane.evaluator.hip.check_flags()
-        self.sims_done += eng.n_playout * len(running)
+        if self.playout_cap is not None and len(running):
+            full = self._full(self.slot_game[running], self.slot_ply[running])
+            for i, s_ in enumerate(running):
+                self.slot_full[s_].append(bool(full[i]))
+            self.sims_done += int(np.where(full, eng.n_playout, self.playout_cap[0]).sum())
+            self.full_plies += int(full.sum())
+        else:
+            self.sims_done += eng.n_playout * len(running)
+            self.full_plies += len(running)
         moves = np.full(eng.n_games, -2, dtype=np.int32)
         resigned = running[:0]
         if self.resign_on and len(running):
@@ -726,6 +810,8 @@ class BatchedSelfPlay(object):
             if quit_ or ended[s - lo]:
                 win = 1 - len(self.slot_moves[s]) % 2 if quit_ else int(winner[s - lo])   # (player 0 moves the even plies)
                 extra = self._resign_record(self.slot_stats[s], win, bool(self._calibration(self.slot_game[s])), quit_)
+                if self.playout_cap is not None:
+                    extra['full'] = self.slot_full[s]
                 done.append(Trajectory(self.slot_game[s], eng.board_size, eng.n_in_row,
                                        self.slot_moves[s], self.slot_pis[s], win, game=eng.game, **extra))
                 self.slot_game[s] = -1
@@ -885,6 +971,10 @@ class BatchedSelfPlay(object):
                                      stall_margin=stall_margin)
                 if self.resign_on:   # (before the capture: the graph's draw then reads the rule's buffer -- set_resign)
                     lane.eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
+                lane.eng.set_playouts(None)   # (the device's budgets, not a host-driven run's last counts)
+                lane.eng.play_set_cap_order(self.cap_longest_first)
+                if self.playout_cap is not None:   # (likewise: the graph's search then reads the budgets -- set_playout_cap)
+                    lane.eng.play_set_cap(*self.playout_cap)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
@@ -898,6 +988,7 @@ class BatchedSelfPlay(object):
         self._pi_buf = np.empty((self.n_slots, max_plies, self.eng.n_actions), dtype=np.float64)   # (pages are touched as games grow)
         self._mv_buf = np.zeros((self.n_slots, max_plies), dtype=np.int32)
         self._st_buf = np.zeros((self.n_slots, max_plies), dtype=np.float32)   # resignation statistic per searched ply (word 7)
+        self._fl_buf = np.zeros((self.n_slots, max_plies), dtype=bool)         # full budget per searched ply (PLAY_FULL)
         self._stalls = {}               # slot -> (game id, ply, pi, move): decided here, waiting for the device to take it
         self.stalls_resolved = 0
         self.slot_game[:] = -1
@@ -954,7 +1045,7 @@ class BatchedSelfPlay(object):
                 with self._on(lane):
                     lane.uncopied.append(lane.eng.play_move_replay(lane.move_graph))
             else:
-                self._simulate_lane(lane)
+                self._simulate_lane(lane, host_counts=False)
                 with self._on(lane):
                     lane.uncopied.append(lane.eng.play_move())
             if len(lane.uncopied) >= self._copy_every:
@@ -974,7 +1065,7 @@ class BatchedSelfPlay(object):
         return done
 
     def _harvest(self, lane, keep):
-        from ._hip import (PLAY_ENDED, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED,
+        from ._hip import (PLAY_ENDED, PLAY_FULL, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED,
                            PLAY_STALLED, PLAY_WOULD_RESIGN, HipError)
         rows = []
         while lane.inflight and (len(lane.inflight) > keep or lane.inflight[0][1].query()):
@@ -1005,7 +1096,19 @@ class BatchedSelfPlay(object):
             bad = np.nonzero(wrong)[0][0]
             raise HipError('the move drawn on the device (%d) is not numpy\'s (%d): game %d, ply %d' % (moves[bad], chosen[bad], gids[bad], plies[bad]))
         searched = (flags & PLAY_SEARCHED) != 0
-        self.sims_done += eng.n_playout * int(searched.sum())
+        fulls = (flags & PLAY_FULL) != 0
+        if self.playout_cap is not None:
+            # the device's budget flag against this side's draw on the same key
+            bad = searched & (fulls != self._full(gids, plies))
+            if bad.any():
+                i = np.nonzero(bad)[0][0]
+                raise HipError('the device\'s budget flag 0x%x of game %d ply %d disagrees with cap_uniform = %r, p_full %r' % (
+                    flags[i], gids[i], plies[i], float(cap_uniform(self.seed, gids[i], plies[i])), self.playout_cap[1]))
+            self.sims_done += int(np.where(fulls, eng.n_playout, self.playout_cap[0])[searched].sum())
+            self.full_plies += int((fulls & searched).sum())
+        else:
+            self.sims_done += eng.n_playout * int(searched.sum())
+            self.full_plies += int(searched.sum())
         stats = np.ascontiguousarray(rec[:, 7]).view(np.float32)
         if self.resign_on:
             # the device's decision against its logged statistic s (float32 of the fp64 s it compared): resigned / would resign
@@ -1040,12 +1143,14 @@ class BatchedSelfPlay(object):
                 self._pi_buf[s, plies[easy]] = pis[easy]
                 self._mv_buf[s, plies[easy]] = moves[easy]
                 self._st_buf[s, plies[easy]] = stats[easy]
+                self._fl_buf[s, plies[easy]] = fulls[easy]
                 self.slot_ply[s] += 1
                 self.moves_done += int(easy.size)
             for i in np.nonzero(special[a:b])[0] + a:
                 s, f, gid, ply = int(slots[i]), int(flags[i]), int(gids[i]), int(plies[i])
                 if f & PLAY_SEARCHED:   # (a stall's searched record comes before the resolved one of its ply)
                     self._st_buf[s, ply] = stats[i]
+                    self._fl_buf[s, ply] = fulls[i]
                 if f & PLAY_STALLED:
                     known = self._stalls.get(s)
                     if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
@@ -1068,6 +1173,8 @@ class BatchedSelfPlay(object):
                 if f & PLAY_RESIGNED:   # the game ends without a move: the plies before it
                     winner = ((int(rec[i, 4]) >> 16) & 3) - 1
                     extra = self._resign_record(self._st_buf[s, :ply + 1].copy(), winner, False, True)
+                    if self.playout_cap is not None:
+                        extra['full'] = self._fl_buf[s, :ply + 1].copy()
                     done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :ply].tolist(), self._pi_buf[s, :ply].copy(),
                                            winner, game=eng.game, **extra))
                     self.slot_game[s] = -1
@@ -1080,6 +1187,8 @@ class BatchedSelfPlay(object):
                     winner = ((int(rec[i, 4]) >> 16) & 3) - 1
                     n = ply + 1
                     extra = self._resign_record(self._st_buf[s, :n].copy(), winner, bool(self._calibration(gid)), False)
+                    if self.playout_cap is not None:
+                        extra['full'] = self._fl_buf[s, :n].copy()
                     done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :n].tolist(), self._pi_buf[s, :n].copy(), winner,
                                            game=eng.game, **extra))
                     self.slot_game[s] = -1
@@ -1108,6 +1217,9 @@ class BatchedSelfPlay(object):
             self.device_attach(queue_capacity=len(game_ids), **self._attach_kw)   # (a longer queue: attach again, same settings)
         else:
             self.device_stop()
+        for lane in self.lanes:   # (a host-driven run's last counts: the device's budgets rule here)
+            with self._on(lane):
+                lane.eng.set_playouts(None)
         self.device_queue(game_ids)
         out, n_moves = [], 0
         while len(out) < len(game_ids):
@@ -1136,7 +1248,25 @@ def _resign_word(t):
     every game played without resignation (the format of a run without it is unchanged)."""
     no_resign = bool(getattr(t, 'no_resign', False))
     low = int(np.float32(t.fp_margin).view(np.uint32)) if no_resign else 0
-    return (int(bool(getattr(t, 'resigned', False))) << 32) | (int(no_resign) << 33) | low
+    word = (int(bool(getattr(t, 'resigned', False))) << 32) | (int(no_resign) << 33) | low
+    full = getattr(t, 'full', None)
+    if full is not None:
+        # the playout cap: bit 34 the game was played under one (its plies' budget flags travel as bit 32 of the move words: _move_words),
+        # bit 35 the flag of a resigned game's last search, which has no move
+        word |= 1 << 34
+        if len(full) > len(t.moves) and full[len(t.moves)]:
+            word |= 1 << 35
+    return word
+
+
+def _move_words(t):
+    """A game's moves as int64 words; under a playout cap bit 32 of a word says that the ply's search had the full budget (without
+    one the words are the moves: the format of a run without a cap is unchanged)."""
+    moves = np.asarray(t.moves, dtype=np.int64).reshape(-1)
+    full = getattr(t, 'full', None)
+    if full is None:
+        return moves
+    return moves | (np.asarray(full[:len(moves)], dtype=np.int64) << 32)
 
 
 def _resign_fields(word):
@@ -1146,10 +1276,21 @@ def _resign_fields(word):
     return dict(resigned=bool((word >> 32) & 1), no_resign=no_resign, fp_margin=margin)
 
 
+def _full_field(word, move_words):
+    """-> (moves, Trajectory.full or None) from the header word and the move words of one game (_resign_word, _move_words)."""
+    word, move_words = int(word), np.asarray(move_words, dtype=np.int64)
+    if not (word >> 34) & 1:
+        return move_words, None
+    full = ((move_words >> 32) & 1).astype(bool)
+    if (word >> 32) & 1:   # (a resigned game: the flag of the search that resigned)
+        full = np.append(full, bool((word >> 35) & 1))
+    return move_words & 0xFFFFFFFF, full
+
+
 def pack_trajectories(trajs, n_cells):
     """-> (header int64 [n,4] = game id, plies, winner, resignation word (_resign_word) ; moves int64 [P] ; pis float64 [P,S])."""
     header = np.array([[t.game_id, len(t.moves), t.winner, _resign_word(t)] for t in trajs], dtype=np.int64).reshape(-1, 4)
-    moves = np.array([m for t in trajs for m in t.moves], dtype=np.int64)
+    moves = np.concatenate([_move_words(t) for t in trajs]) if trajs else np.zeros(0, dtype=np.int64)
     pis = np.concatenate([t.pis for t in trajs], axis=0) if trajs else np.zeros((0, n_cells))
     return header, moves, pis.reshape(-1, n_cells)
 
@@ -1158,8 +1299,9 @@ def unpack_trajectories(header, moves, pis, board_size, n_in_row, game='gomoku')
     out, at = [], 0
     for gid, plies, winner, word in header:
         plies = int(plies)
-        out.append(Trajectory(gid, board_size, n_in_row, moves[at:at + plies], pis[at:at + plies], winner,
-                              game=game, **_resign_fields(word)))
+        mv, full = _full_field(word, moves[at:at + plies])
+        out.append(Trajectory(gid, board_size, n_in_row, mv, pis[at:at + plies], winner,
+                              game=game, full=full, **_resign_fields(word)))
         at += plies
     return out
 
@@ -1189,7 +1331,7 @@ def payload_of(trajs, n_cells, pi_dtype):
     for i, t in enumerate(trajs):
         k = len(t.moves)
         header[i] = (t.game_id, k, t.winner, _resign_word(t))
-        moves[at:at + k] = t.moves
+        moves[at:at + k] = _move_words(t)
         if k:
             pis[at:at + k] = t.pis   # (numpy converts while it copies)
         at += k

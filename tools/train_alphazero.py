@@ -148,7 +148,7 @@ class TrainPipeline:
 
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
-                 resign_fp_target=0.05):
+                 resign_fp_target=0.05, playout_cap=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -159,7 +159,12 @@ class TrainPipeline:
         ``resign``: self-play resignation (BatchedSelfPlay.set_resign; batched mode only, an opt-in extension): 'off', a threshold,
         or 'auto' -- the first round all calibration games with threshold -inf (statistics only), then after every round rank 0
         sets the threshold from the calibration games of the last rounds (selfplay.calibrate_resign_threshold, at most
-        ``resign_fp_target`` false positives) and hands it to every rank.  ``resign_disabled_frac``: the calibration games."""
+        ``resign_fp_target`` false positives) and hands it to every rank.  ``resign_disabled_frac``: the calibration games.
+        ``playout_cap``: None or (n_fast, p_full) -- playout cap randomization (BatchedSelfPlay.set_playout_cap; batched mode only, an
+        opt-in extension): the replay buffer takes the plies searched with the full budget (Trajectory.training_samples)."""
+        if playout_cap is not None and selfplay_games_in_flight <= 0:
+            raise ValueError('the playout cap is a batched self-play option: selfplay_games_in_flight must be > 0')
+        self.playout_cap = None if playout_cap is None else (int(playout_cap[0]), float(playout_cap[1]))
         if resign != 'off' and selfplay_games_in_flight <= 0:
             raise ValueError('resignation is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.rank, self.world = self._init_ranks()
@@ -285,7 +290,7 @@ class TrainPipeline:
             self._batched = BatchedSelfPlay.for_network(
                 self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
-                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed)
+                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap)
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
         if self.resign_mode != 'off':
             # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
@@ -330,6 +335,19 @@ class TrainPipeline:
         with open(os.path.join(os.environ['RZ_TRAIN_TRACE'], 'rank%d.jsonl' % self.rank), 'a') as f:
             f.write(json.dumps(rec) + '\n')
 
+    def _tuple(self, t):
+        """start_self_play's tuple of a trajectory; under a playout cap with the full-budget plies only."""
+        return t.as_reference_tuple() if self.playout_cap is None else (t.winner, t.training_samples())
+
+    def _cap_round(self, trajs):
+        """After a collection round under a playout cap (``trajs``: None off rank 0): the share of plies searched with the full budget."""
+        if self.playout_cap is None or trajs is None:
+            return
+        plies = sum(len(t.moves) for t in trajs)
+        full = sum(int(t.full[:len(t.moves)].sum()) for t in trajs)
+        print('playout cap: {} of {} plies searched with the full budget ({:.3f}); n_fast {}, p_full {}'.format(
+            full, plies, full / max(plies, 1), *self.playout_cap), flush=True)
+
     def _collect_batched(self, n_games, consume=None):
         """One collection round: ``n_games`` games in all, game g played by rank g mod world (selfplay.shard_game_ids),
         one gather to rank 0 (pi as float32: what the learner consumes).  -> start_self_play's tuples on rank 0, in game
@@ -342,21 +360,23 @@ class TrainPipeline:
             local = self._play_games([g for g in ids if g % self.world == self.rank])
             merged = gather_trajectories(local, self.board_size, self.n_in_row, dst=0, pi_dtype=np.float32)
             self._resign_round(merged)
-            return [t.as_reference_tuple() for t in merged] if merged is not None else []
+            self._cap_round(merged)
+            return [self._tuple(t) for t in merged] if merged is not None else []
         # one rank: every finished game becomes start_self_play's tuple (planes from its move list) WHILE the others are played --
         # behind an idle GPU that was a tenth of a round; the round's order stays the game ids'
         ready, cursor = {}, [ids.start]
 
         def take(trajs):
             for t in trajs:
-                ready[t.game_id] = t.as_reference_tuple()
+                ready[t.game_id] = self._tuple(t)
             while consume is not None and cursor[0] in ready:   # (the replay buffer's order is the reference's: game by game)
                 consume(ready.pop(cursor[0]))
                 cursor[0] += 1
         local = self._play_games(list(ids), on_finished=take)
         self._resign_round(local)
+        self._cap_round(local)
         rest = [t for t in sorted(local, key=lambda t: t.game_id) if t.game_id >= cursor[0] or consume is None]
-        return [ready[t.game_id] if t.game_id in ready else t.as_reference_tuple() for t in rest]
+        return [ready[t.game_id] if t.game_id in ready else self._tuple(t) for t in rest]
 
     RESIGN_ROUNDS = 4   # 'auto': rounds of calibration games the threshold is set from
 
@@ -516,7 +536,20 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def playout_cap_arg(text):
+    """--playout-cap N_FAST:P_FULL -> (n_fast, p_full)."""
+    import argparse
+    try:
+        n_fast, p_full = text.split(':')
+        n_fast, p_full = int(n_fast), float(p_full)
+    except ValueError:
+        raise argparse.ArgumentTypeError('N_FAST:P_FULL, e.g. 100:0.25, not %r' % text)
+    if n_fast < 1 or not 0.0 < p_full <= 1.0:
+        raise argparse.ArgumentTypeError('N_FAST >= 1 and P_FULL in (0, 1], not %r' % text)
+    return n_fast, p_full
+
+
+def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku on MI355X (no arguments: the reference script\'s run)')
     ap.add_argument('--gpus', type=int, default=1, help='processes (one per GPU); > 1 without a launcher starts them itself')
@@ -531,7 +564,14 @@ def main():
                     help="self-play resignation (batched mode only): off, auto (calibrated every round) or a value threshold")
     ap.add_argument('--resign-disabled-frac', type=float, default=0.1, help='games played out to measure false positives')
     ap.add_argument('--resign-fp-target', type=float, default=0.05, help="'auto': false-positive rate the threshold allows")
-    args = ap.parse_args()
+    ap.add_argument('--playout-cap', type=playout_cap_arg, default=None, metavar='N_FAST:P_FULL',
+                    help='playout cap randomization (batched mode only): a search has --playouts simulations with probability P_FULL, '
+                         'else N_FAST; only the full ones become policy samples')
+    args = ap.parse_args(argv)
+    if args.playout_cap is not None and args.games_in_flight <= 0:
+        ap.error('--playout-cap needs --games-in-flight > 0 (batched self-play)')
+    if args.playout_cap is not None and args.playout_cap[0] > args.playouts:
+        ap.error('--playout-cap: N_FAST %d exceeds --playouts %d' % (args.playout_cap[0], args.playouts))
     if args.resign_threshold != 'off' and args.games_in_flight <= 0:
         ap.error('--resign-threshold needs --games-in-flight > 0 (batched self-play)')
     if args.resign_threshold not in ('off', 'auto'):
@@ -539,6 +579,11 @@ def main():
             float(args.resign_threshold)
         except ValueError:
             ap.error('--resign-threshold: off, auto or a number, not %r' % args.resign_threshold)
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.seed is not None:   # a reproducible run: initial weights, random.sample of the replay buffer, numpy draws
@@ -548,7 +593,7 @@ def main():
     pipe = TrainPipeline(board_size=args.board, n_in_row=args.n_in_row, n_playout=args.playouts, game_batch_num=args.batches,
                          check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed,
                          resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
-                         resign_fp_target=args.resign_fp_target)
+                         resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
