@@ -9,6 +9,8 @@
   ``rlzero/games/gomoku/alphazero_agent.py:31-46`` on torch CPU tensors.
 * ``numpy_weights``: deterministic weights from ``numpy.random.RandomState`` (MT19937 is
   stable across numpy versions) so net fixtures need not store parameters.
+* ``sharp_weights``: the same with every ``.weight`` tensor times a gain, so that values spread over (-1, 1) and the
+  policy is peaked: a fixture on them notices an error of the value path that ``numpy_weights``' near-constant values hide.
 """
 import numpy as np
 
@@ -73,6 +75,15 @@ def numpy_weights(board_size, seed):
     return out
 
 
+def sharp_weights(board_size, seed, gain):
+    """``numpy_weights(board_size, seed)`` with every ``.weight`` tensor multiplied by ``gain`` (in fp32), biases unchanged."""
+    out = numpy_weights(board_size, seed)
+    for name in out:
+        if name.endswith('.weight'):
+            out[name] = (out[name] * np.float32(gain)).astype(np.float32)
+    return out
+
+
 def net_forward(weights, obs, dtype=None):
     """policy_value_net.py:34-52 on torch CPU.  ``weights``: {name: array/tensor};
     ``obs``: [b,4,B,B].  Returns (log_probs [b,S], value [b,1]) as torch tensors."""
@@ -98,9 +109,10 @@ class NetEvaluator(object):
     """alphazero_agent.py:31-46: batch-1 forward, p = exp(log_softmax)[legal] (not
     renormalised), v = python float of the fp32 value."""
 
-    def __init__(self, weights, board_size):
+    def __init__(self, weights, board_size, dtype=None):
         self.weights = weights
         self.board_size = board_size
+        self.dtype = dtype   # (None: torch.float32, the reference's; torch.float64 for a rounding-free run of the same net)
         self.n_calls = 0
 
     def __call__(self, env):
@@ -109,7 +121,7 @@ class NetEvaluator(object):
         rows, cols = self.board_size if isinstance(self.board_size, (tuple, list)) else (self.board_size, self.board_size)
         obs = env.current_state().reshape(-1, 4, rows, cols)
         with torch.no_grad():
-            logp, v = net_forward(self.weights, np.ascontiguousarray(obs))
+            logp, v = net_forward(self.weights, np.ascontiguousarray(obs), self.dtype)
         probs = np.exp(logp.numpy().flatten())
         self.n_calls += 1
         return list(zip(legal, probs[legal])), v.item()

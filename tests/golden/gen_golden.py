@@ -21,10 +21,18 @@ not travel to the GPU box, so its outputs are committed here as data:
                    9x9 / 200: per ply the root's visit counts, the move, the uniform, and the SMALLEST GAP between the two best
                    finite UCT scores any selection of that search met (node.py:41-42, 75-88: a device whose leaf values differ
                    from torch's by 1e-7 may legitimately take the other child only where that gap is tiny)
+  g9_sharpnet_B*.npz, g9_sharpsearch_B*.json.gz, g9_sharpgames.json.gz
+                   boards of 11, 15 and 16 rows on sharp_weights (values spread over (-1, 1), peaked policies): the reference's net on
+                   24 positions per board; searches of the reference's AlphaZeroMCTS with its own evaluator (per simulation the leaf's
+                   path and value, the root record, the tree dump); self-play games in g8's format.  Stored with them: e_value / e_logp
+                   = max |torch f32 - torch f64| over every recorded position and leaf, and which cases / plies the oracle rebuilds
+                   identically under values moved by +-4 e_value and under fp64 values ("robust": see gen_g9)
   g6_rollout.json.gz pure-MCTS opponent (RolloutMCTS / RolloutPlayer) with np.random.rand drawn from a
                    recorded private stream: root statistics, chosen moves, a full duel
 
-Usage:  python tests/golden/gen_golden.py        (rewrites the files next to it)
+Usage:  python tests/golden/gen_golden.py        (rewrites the files next to it; g8 and g9 only when named)
+        python tests/golden/gen_golden.py g8     (that fixture alone)
+        python tests/golden/gen_golden.py g9
 
 Only reference *outputs* are stored; no reference source text is copied.
 """
@@ -57,7 +65,7 @@ from rlzero.games.gomoku.alphazero_agent import AlphaZeroAgent  # noqa: E402
 from rlzero.mcts.alphazero_mcts import AlphaZeroMCTS, AlphaZeroPlayer  # noqa: E402
 from rlzero.mcts.rollout_mcts import RolloutMCTS, RolloutPlayer  # noqa: E402
 
-from oracle.evaluators import numpy_weights, v0, vlin  # noqa: E402  (pure functions)
+from oracle.evaluators import numpy_weights, sharp_weights, v0, vlin  # noqa: E402  (pure functions)
 
 EVALS = {'v0': v0, 'vlin': vlin}
 
@@ -429,6 +437,288 @@ def gen_g8():
     return {'games': games}
 
 
+# ---------------------------------------------------------------------------- G9
+G9_NETS = {11: (952, 2.5), 15: (908, 2.5), 16: (908, 2.6)}   # board -> (seed, gain) of sharp_weights: chosen on the CPU (see tests/test_sharp_fixture.py for the conditions)
+G9_SIMS = {11: 150, 15: 400, 16: 300}
+G9_MARGIN = 4            # E = G9_MARGIN * e_value: the amplitude the robust cases withstand and the device tests allow
+G9_SEEDS = (1, 2, 3, 4)  # of the perturbations' signs
+
+
+def sharp_agent(B):
+    seed, gain = G9_NETS[B]
+    agent = AlphaZeroAgent(B)
+    w = sharp_weights(B, seed, gain)
+    agent.policy_value_net.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
+    return agent, w
+
+
+def random_root(B, rs, n_stones, edge=None):
+    """A non-terminal position of ``n_stones`` random stones; ``edge`` 0..3: the last one on the top / bottom / left / right edge."""
+    while True:
+        cells = [int(c) for c in rs.permutation(B * B)[:n_stones]]
+        if edge is not None and n_stones:
+            k = int(rs.randint(1, B - 1))
+            last = (k, (B - 1) * B + k, k * B, k * B + B - 1)[edge]
+            cells = [c for c in cells if c != last][:n_stones - 1] + [last]
+        env = new_env(B, 5)
+        for m in cells:
+            env.step(m)
+            if env.game_end_winner()[0]:
+                break
+        if not env.game_end_winner()[0] and len(env.states) == n_stones:
+            return cells
+
+
+def late_root(B, rs, lo, hi):
+    """A nearly full board without a line, lo .. hi cells empty: cell (y, x) black when (x + 2 y) mod 4 < 2 (runs of two along rows
+    and diagonals); stones of the colour in excess are taken off again, so the first draw may leave more than ``hi`` cells empty."""
+    for n_empty in range(hi, 0, -1):
+        empty = set(rs.choice(B * B, n_empty, replace=False).tolist())
+        black = [c for c in range(B * B) if c not in empty and (c % B + 2 * (c // B)) % 4 < 2]
+        white = [c for c in range(B * B) if c not in empty and (c % B + 2 * (c // B)) % 4 >= 2]
+        while not 0 <= len(black) - len(white) <= 1:
+            big = black if len(black) > len(white) else white
+            big.pop(rs.randint(len(big)))
+        if lo <= B * B - len(black) - len(white) <= hi:
+            break
+    else:
+        raise RuntimeError('no late root')
+    rs.shuffle(black)
+    rs.shuffle(white)
+    moves = [int(m) for pair in zip(black, white) for m in pair] + [int(m) for m in black[len(white):]]
+    env = new_env(B, 5, moves)
+    assert not env.game_end_winner()[0]
+    return moves
+
+
+def near_win_root(B):
+    """The side to move holds an open four in the middle row; the other side's stones lie apart on the top row."""
+    r = B // 2
+    return [m for pair in zip([r * B + 3 + j for j in range(4)], [0, 2, 4, 6]) for m in pair]
+
+
+def sign_of(order, cells, seed):
+    """+1 / -1 from a hash of the position (who holds which cell) and a seed."""
+    key = repr((sorted((int(m), int(cells[m])) for m in order), int(seed))).encode()
+    return 1.0 if hashlib.sha1(key).digest()[0] & 1 else -1.0
+
+
+def perturbed(base, amplitude, seed):
+    def fn(env):
+        priors, v = base(env)
+        return priors, v + sign_of(env.order, env.cells, seed) * amplitude
+    return fn
+
+
+def g9_variants(w, B, amplitude):
+    """The five evaluators a robust case must give the reference's tree with: the oracle's torch net moved by +-amplitude (4 sign seeds), fp64."""
+    from oracle.evaluators import NetEvaluator
+    return [perturbed(NetEvaluator(w, B), amplitude, s_) for s_ in G9_SEEDS] + [NetEvaluator(w, B, torch.float64)]
+
+
+def g9_search_case(B, name, pre, sims):
+    agent, w = sharp_agent(B)
+    env = new_env(B, 5, pre)
+    mcts = AlphaZeroMCTS(agent.policy_value_fn, n_playout=sims, c_puct=5)
+    log, obs = [], []
+    real_pvf = mcts.policy_value_fn
+
+    def spy(e):
+        probs, v = real_pvf(e)
+        log.append([[int(m) for m in e.states.keys()][len(pre):], hexf(np.float32(v)), bool(e.game_end_winner()[0])])
+        assert float(np.float32(v)) == v
+        obs.append(e.current_state().astype(np.uint8))
+        return probs, v
+
+    mcts.policy_value_fn = spy
+    with torch.no_grad():
+        acts, probs = mcts.simulate(env, temperature=1.0)
+    rec = {'B': B, 'n': 5, 'name': name, 'pre': [int(m) for m in pre], 'n_playout': sims, 'c_puct': 5, 'T': 1.0,
+           'leaves': [[p, v] for p, v, _ in log], 'terminal': [i for i, (_, _, t) in enumerate(log) if t]}
+    rec.update(root_record(mcts, acts, probs))
+    rec['tree'] = ref_tree_dump(mcts._root)
+    return rec, np.array(obs)
+
+
+def g9_game(B, sims, seed, max_plies):
+    """realnet_game on sharp_weights, stopped after ``max_plies`` plies (None: the whole game)."""
+    agent, w = sharp_agent(B)
+    inj = InjectedChoice(seed)
+    np.random.choice = inj
+    per_ply = []
+
+    class Stop(Exception):
+        pass
+
+    try:
+        env = GomokuEnv(board_size=B, n_in_row=5)
+        player = AlphaZeroPlayer(agent.policy_value_fn, n_playout=sims, c_puct=5, is_selfplay=True)
+        real_sim = player.mcts.simulate
+
+        def spy(game_env, temperature=1e-3):
+            if max_plies is not None and len(per_ply) == max_plies:
+                raise Stop()
+            with torch.no_grad():
+                acts, probs = real_sim(game_env, temperature)
+            root = player.mcts._root
+            per_ply.append({'acts': [int(a) for a in acts], 'N': [int(root._children[a].explore_count) for a in acts],
+                            'root_N': int(root.explore_count)})
+            return acts, probs
+
+        player.mcts.simulate = spy
+        winner = None
+        try:
+            winner, _ = GameControl(env).start_self_play(player, temperature=1.0)
+        except Stop:
+            pass
+    finally:
+        np.random.choice = inj.real
+    moves = [int(m) for m in env.states.keys()][:len(per_ply)]
+    for rec, u, mv in zip(per_ply, inj.used, moves):
+        rec['u'] = hexf(u)
+        rec['move'] = mv
+    return {'B': B, 'n': 5, 'n_playout': sims, 'c_puct': 5, 'T': 1.0, 'seed': seed, 'winner': None if winner is None else int(winner),
+            'moves': moves, 'plies': per_ply}
+
+
+def g9_case_robust(rec, w, amplitude):
+    from oracle.gomoku_ref import RefGomoku
+    from oracle.mcts_ref import RefSearch, tree_dump
+    want = {tuple(p): n for p, n, _ in rec['tree']}
+    for fn in g9_variants(w, rec['B'], amplitude):
+        s_ = RefSearch(fn, rec['n_playout'], rec['c_puct'])
+        with torch.no_grad():
+            s_.simulate(RefGomoku.from_moves(rec['B'], 5, rec['pre']), 1.0)
+        if {p: n for p, (n, _) in tree_dump(s_.root).items()} != want:
+            return False
+    return True
+
+
+def g9_game_robust_plies(game, w, amplitude):
+    from oracle.gomoku_ref import RefGomoku
+    from oracle.mcts_ref import RefPlayer, inverse_cdf_choice
+    shortest = len(game['plies'])
+    for fn in g9_variants(w, game['B'], amplitude):
+        env = RefGomoku(game['B'], 5)
+        env.reset()
+        player = RefPlayer(fn, n_playout=game['n_playout'], c_puct=5, is_selfplay=True,
+                           choice=inverse_cdf_choice(float.fromhex(p['u']) for p in game['plies']))
+        k = 0
+        for ply in game['plies'][:shortest]:
+            with torch.no_grad():
+                acts, probs = player.mcts.simulate(env, 1.0)
+            if list(acts) != ply['acts'] or [kid.n for kid in player.mcts.root.kids] != ply['N']:
+                break
+            move = player.choice(acts, probs)
+            if int(move) != ply['move']:
+                break
+            player.mcts.update_with_move(move)
+            env.step(move)
+            k += 1
+        shortest = min(shortest, k)
+    return shortest
+
+
+def g9_positions(B, rs):
+    """24 legal positions as move lists: empty, one corner stone, last move on each edge, 16 mid-game, two with at most 12 empty cells."""
+    S = B * B
+    out = [[], [S - 1]]
+    out += [random_root(B, rs, int(rs.randint(8, S // 2)), edge) for edge in range(4)]
+    out += [random_root(B, rs, int(rs.randint(2, 2 * S // 3))) for _ in range(16)]
+    out += [late_root(B, rs, 9, 12), late_root(B, rs, 4, 8)]
+    return out
+
+
+def g9_errors(agent, w, obs):
+    """max |torch f32 - torch f64| of the value and of the log-probabilities over ``obs`` (the reference's module in f32, one position
+    per call as its evaluator runs it; the restatement in f64), and the f64 values / spreads of the log-probabilities."""
+    from oracle.evaluators import net_forward
+    ev_, el_, values, spread = 0.0, 0.0, [], []
+    with torch.no_grad():
+        for i in range(0, len(obs), 256):
+            x = obs[i:i + 256].astype(np.float32)
+            both = [agent.policy_value_net(torch.from_numpy(x[j:j + 1])) for j in range(len(x))]
+            lp32, v32 = torch.cat([b[0] for b in both]), torch.cat([b[1] for b in both])
+            lp64, v64 = net_forward(w, x, torch.float64)
+            ev_ = max(ev_, float((v32.double() - v64).abs().max()))
+            el_ = max(el_, float((lp32.double() - lp64).abs().max()))
+            values += v64.flatten().tolist()
+            spread += (lp64.max(dim=1).values - lp64.min(dim=1).values).tolist()
+    return ev_, el_, values, spread
+
+
+def gen_g9():
+    np.random.seed(9)   # (the reference's Dirichlet noise draws from the global stream: it never reaches the selection)
+    report = []
+    games_out = {'games': []}
+    game_spec = {11: [(150, 9111, None), (150, 9112, None)], 15: [(300, 9151, 12), (300, 9152, 12)], 16: []}
+    for B in (11, 15, 16):
+        rs = np.random.RandomState(9000 + B)
+        agent, w = sharp_agent(B)
+        seed, gain = G9_NETS[B]
+        # --- positions
+        positions = g9_positions(B, rs)
+        obs, logp, value = [], [], []
+        for moves in positions:
+            env = new_env(B, 5, moves)
+            assert not env.game_end_winner()[0]
+            o = np.ascontiguousarray(env.current_state().reshape(-1, 4, B, B))
+            with torch.no_grad():
+                lp, v = agent.policy_value_net(torch.from_numpy(o).float())
+            obs.append(o[0].astype(np.uint8))
+            logp.append(lp.numpy()[0])
+            value.append(v.numpy().reshape(-1)[0])
+        # --- searches
+        specs = [('empty', []), ('edge', random_root(B, rs, 30, edge=B % 4)), ('near_win', near_win_root(B))]
+        if B != 11:
+            specs.append(('late', late_root(B, rs, 10, 14)))
+        specs += [('mid%d' % k, random_root(B, rs, int(rs.randint(10, 60)))) for k in range(2)]
+        cases, leaf_obs = [], [np.array(obs)]
+        for name, pre in specs:
+            rec, o = g9_search_case(B, name, pre, G9_SIMS[B])
+            cases.append(rec)
+            leaf_obs.append(o)
+        all_obs = np.concatenate(leaf_obs)
+        e_value, e_logp, values, spread = g9_errors(agent, w, all_obs)
+        amplitude = G9_MARGIN * e_value
+        for rec in cases:
+            rec['robust'] = g9_case_robust(rec, w, amplitude)
+            rec['max_depth'] = max(len(p) for p, _ in rec['leaves'])
+        values = np.array(values)
+        stats = {'value_std': float(values.std()), 'saturated_share': float((np.abs(values) > 0.99).mean()),
+                 'logp_spread': float(np.mean(spread)), 'n_positions': int(len(values))}
+        head = {'B': B, 'seed': seed, 'gain': gain, 'e_value': hexf(e_value), 'e_logp': hexf(e_logp), 'margin': G9_MARGIN,
+                'perturbation_seeds': list(G9_SEEDS), 'stats': stats}
+        for part in range(0, len(cases), 3):   # (three cases a file: every committed fixture stays below 30 KB)
+            write_json('g9_sharpsearch_B%d_%d.json' % (B, part // 3), dict(head, cases=cases[part:part + 3]))
+        bits = np.packbits(np.array(obs).reshape(len(obs), 4, B * B), axis=2)
+        mv = -np.ones((len(positions), B * B), dtype=np.int16)
+        for i, m in enumerate(positions):
+            mv[i, :len(m)] = m
+        name = 'g9_sharpnet_B%d.npz' % B
+        np.savez_compressed(os.path.join(HERE, name), B=np.array(B), seed=np.array(seed), gain=np.array(gain), plane_bits=bits, moves=mv,
+                            log_probs=np.array(logp, dtype=np.float32), value=np.array(value, dtype=np.float32),
+                            e_value=np.array(e_value), e_logp=np.array(e_logp))
+        print('%-18s %8.1f KB' % (name, os.path.getsize(os.path.join(HERE, name)) / 1024.0))
+        for sims, gseed, max_plies in game_spec[B]:
+            rejected = []   # (seeds whose game a rounding decides before ply 8: the next candidate is taken, at most 20)
+            for cand in range(gseed, gseed + 200, 10):
+                game = g9_game(B, sims, cand, max_plies)
+                game['robust_plies'] = g9_game_robust_plies(game, w, amplitude)
+                if game['robust_plies'] >= 8:
+                    break
+                rejected.append([cand, game['robust_plies']])
+            else:
+                raise RuntimeError('no game with 8 robust plies among 20 candidates')
+            game.update(weights_seed=seed, gain=gain, e_value=hexf(e_value), rejected_seeds=rejected)
+            games_out['games'].append(game)
+        report.append((B, e_value, e_logp, stats, [(c['name'], c['robust'], c['max_depth']) for c in cases],
+                       [(len(g['plies']), g['robust_plies']) for g in games_out['games'] if g['B'] == B]))
+    write_json('g9_sharpgames.json', games_out)
+    for row in report:
+        print(row)
+
+
 # ---------------------------------------------------------------------------- net
 def load_numpy_weights(agent, B, seed):
     w = numpy_weights(B, seed)
@@ -616,6 +906,9 @@ def write_json(name, obj):
 def main():
     if sys.argv[1:] == ['g8']:   # (this fixture alone: the others do not depend on it)
         write_json('g8_realnet.json', gen_g8())
+        return
+    if sys.argv[1:] == ['g9']:   # (likewise: it writes its own files)
+        gen_g9()
         return
     np.random.seed(0)
     write_json('g1_rules.json', gen_g1())

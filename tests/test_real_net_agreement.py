@@ -1,7 +1,9 @@
 """The device's search with ITS OWN network values against the reference's own run with torch-CPU values (tests/golden/g8_realnet.json.gz:
 whole self-play games at 6x6 / 400 and 9x9 / 200 playouts): every difference must sit behind a selection whose two best UCT scores
 (node.py:41-42, 75-88) the reference itself recorded as a near-tie -- otherwise it is a bug, not rounding.  The figures themselves
-(plies identical, first difference per game) are profiles/r06/real_net_agreement.txt, written by profiles/real_net_agreement.py."""
+(plies identical, first difference per game) are profiles/r06/real_net_agreement.txt, written by profiles/real_net_agreement.py.
+Its weights (numpy_weights) keep the values constant to about 1e-4, so these games pin the TREE, not the net: searches whose values
+steer them, on boards of 11 .. 16 rows and against the reference's own runs, are tests/test_sharp_net_rows.py."""
 import os
 import sys
 
