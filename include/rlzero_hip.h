@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 28
+#define RZ_ABI_VERSION 29
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -329,6 +329,27 @@ int rz_tree_step_deferred(rz_engine *e, const rz_value_head *head, void *stream)
  * with its Dirichlet noise: the operations of rz_expand_backup_raw -- and empties the slots.  Must run before
  * rz_advance_roots / rz_set_roots / the prior read-outs; without pending slots a no-op. */
 int rz_deferred_flush(rz_engine *e, const rz_deferred_logits *logits, int32_t n_slots, void *stream);
+/* The kept flush (ABI 29), for the move step on the device: between rz_play_draw and rz_play_apply the move is known, and the only
+ * priors of the search that anything can read afterwards are those of the blocks that survive update_with_move -- the kept child's
+ * subtree and the root's own block.  Priors exist for every block a caller can reach; blocks of subtrees a move discards are never
+ * written.  rz_deferred_keep lists the pending records that are needed -- leaf board == root board; or the mover's stone on the
+ * cell of the move (every leaf below the kept child, and harmlessly a transposition); or every record with a block where no move
+ * was drawn (a stall, a resignation) -- as rows[i] = slot * n_games + game, game-major, slots ascending, *count of them (device
+ * memory: the launches that follow read it there).  rz_net_deferred_gemm_rows forms the logits of listed row i in row i of its
+ * output; rz_deferred_flush_kept writes those records' priors, the operations of rz_deferred_flush on the same numbers.  RZ_ERR_ARG
+ * outside a drawn move.  Every other reader of priors (read-outs, rz_advance_roots, rz_set_roots) needs rz_deferred_flush. */
+typedef struct rz_kept_rows {
+    const int32_t *rows;  /* device, [capacity] */
+    const int32_t *count; /* device, [1] */
+    int64_t capacity;     /* slots reserved * n_games */
+    int32_t n_games;
+    int32_t reserved;
+} rz_kept_rows;
+int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream);
+int rz_deferred_flush_kept(rz_engine *e, const rz_deferred_logits *logits, void *stream);
+/* h_out2 = {records listed, records with a block (what rz_deferred_flush would have written)} over the rz_deferred_keep calls since
+ * the last reset; synchronises */
+int rz_deferred_keep_stats(rz_engine *e, uint64_t *h_out2, int32_t reset);
 
 /* Root statistics after the simulations (AlphaZeroMCTS.simulate, alphazero_mcts.py:88-90):
  * visit count / W of the root child of every action, 0 for illegal or unvisited actions;
@@ -586,6 +607,10 @@ int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const in
                                  int32_t n_boards, const int32_t *d_slot_of_board, rz_value_head *out, void *stream);
 /* act_fc1 (policy_value_net.py:43) over the stored leaves of slots [0, n_slots) as ONE GEMM (k_heads_split's arithmetic) */
 int rz_net_deferred_gemm(rz_net *net, int32_t n_boards, int32_t n_slots, rz_deferred_logits *out, void *stream);
+/* The same GEMM over the listed rows of the store only (rz_deferred_keep): the A fragments are gathered row by row, the K quarters,
+ * the MFMA order, the sum of the quarters and the epilogue are rz_net_deferred_gemm's -- the same bits -- and the logits of listed row
+ * i are row i of `out` (rows_per_slot = 0: not slot-indexed).  A fixed grid strides over the device's count. */
+int rz_net_deferred_gemm_rows(rz_net *net, const rz_kept_rows *kept, rz_deferred_logits *out, void *stream);
 int rz_net_trace_attach(rz_net *net, void *d_trace);   /* see rz_trace_attach */
 /* RECEPTIVE-FIELD ("delta") LEAF EVALUATION -- PolicyValueNet.forward (policy_value_net.py:34-52) on the leaves of a search WITHOUT
  * recomputing what the root already determines.  The reference's search is near breadth-first (alphazero_mcts.py:42-71 under

@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -73,6 +73,11 @@ class RzDeferredLogits(Structure):
     _fields_ = [('raw', c_void_p), ('ld', c_int32), ('rows_per_slot', c_int32)]
 
 
+class RzKeptRows(Structure):
+    """rz_kept_rows: the pending records a drawn move needs (rz_deferred_keep), device pointers."""
+    _fields_ = [('rows', c_void_p), ('count', c_void_p), ('capacity', c_int64), ('n_games', c_int32), ('reserved', c_int32)]
+
+
 class RzPlayConfig(Structure):
     """rz_play_config: the move step on the device (uniform / noise seed, temperature, the shared queue of game ids, the log)."""
     _fields_ = [('seed', c_uint64), ('temperature', c_double), ('stall_margin', c_double), ('d_queue_ids', c_void_p),
@@ -126,6 +131,9 @@ _SIGNATURES = {
     'rz_expand_backup_deferred': (c_int, [P, POINTER(RzValueHead), P]),
     'rz_tree_step_deferred': (c_int, [P, POINTER(RzValueHead), P]),
     'rz_deferred_flush': (c_int, [P, POINTER(RzDeferredLogits), c_int32, P]),
+    'rz_deferred_keep': (c_int, [P, POINTER(RzKeptRows), P]),
+    'rz_deferred_flush_kept': (c_int, [P, POINTER(RzDeferredLogits), P]),
+    'rz_deferred_keep_stats': (c_int, [P, POINTER(c_uint64), c_int32]),
     'rz_root_visits': (c_int, [P, P, P]),
     'rz_root_wsum': (c_int, [P, P, P]),
     'rz_root_priors': (c_int, [P, P, P]),
@@ -165,6 +173,7 @@ _SIGNATURES = {
     'rz_net_deferred_reserve': (c_int, [P, c_int32, c_int32]),
     'rz_net_trunk_leaves_deferred': (c_int, [P, P, P, P, c_int32, P, POINTER(RzValueHead), P]),
     'rz_net_deferred_gemm': (c_int, [P, c_int32, c_int32, POINTER(RzDeferredLogits), P]),
+    'rz_net_deferred_gemm_rows': (c_int, [P, POINTER(RzKeptRows), POINTER(RzDeferredLogits), P]),
     'rz_net_search_resident': (c_int, [P, P, c_int32, c_int32, P]),
     'rz_net_delta_reserve': (c_int, [P, c_int32]),
     'rz_net_delta_invalidate': (c_int, [P, P]),

@@ -123,16 +123,13 @@ __global__ __launch_bounds__(kWave * kDefWaves) void k_tree_step_def(Dev E, Valu
 // The flush: the priors of the node expanded in step `slot` of game g -- exp(log_softmax) of the leaf's logits over its legal
 // moves, mixed with the Dirichlet noise of counter pend_ctr: expand_backup_body<RAW>'s operations on the same numbers (the
 // logits are final: k_heads_split's epilogue), into the block that step reserved.  grid = (games, slots).
-__global__ __launch_bounds__(kWave) void k_deferred_priors(Dev E, const float *__restrict__ raw, int ld, long long rows_per_slot) {
-    const int g = blockIdx.x, slot = blockIdx.y, lane = threadIdx.x;
-    if (slot >= E.pend[g]) return;
-    const long long rec = (long long)slot * E.n_games + g;
+// record `rec` = slot * n_games + g, its logits at `r`: the body of both grids below
+__device__ __forceinline__ void deferred_priors_body(const Dev &E, int g, long long rec, const float *__restrict__ r, int lane) {
     const int pb = E.pend_pb[rec];
     if (pb < 0) return;
     const int ctr = E.pend_ctr[rec];
     uint64_t st[2][kWords];
     load_board(E.pend_stones, (int)rec, st);
-    const float *r = raw + ((size_t)slot * rows_per_slot + g) * ld;
     float x[kWords];
     float mx = -INFINITY;
 #pragma unroll
@@ -177,6 +174,114 @@ __global__ __launch_bounds__(kWave) void k_deferred_priors(Dev E, const float *_
         float prior = expf(x[j] - lse);
         if (E.add_noise) prior = 0.75f * prior + 0.25f * (noise[j] / noise_sum);
         P[pb + rk] = prior;
+    }
+}
+
+__global__ __launch_bounds__(kWave) void k_deferred_priors(Dev E, const float *__restrict__ raw, int ld, long long rows_per_slot) {
+    const int g = blockIdx.x, slot = blockIdx.y, lane = threadIdx.x;
+    if (slot >= E.pend[g]) return;
+    deferred_priors_body(E, g, (long long)slot * E.n_games + g, raw + ((size_t)slot * rows_per_slot + g) * ld, lane);
+}
+
+// ------------------------------------------------------------------ the kept flush (between k_play_draw and k_play_apply)
+// The move is known (Play::keep), and a prior block matters only if it survives update_with_move: advance_body copies the blocks
+// of the kept child's subtree and reads one float of the root's own block.  The priors of every other expansion of the search lie
+// in the arena the move abandons: they are never formed.  A record is NEEDED when
+//   * its leaf board is the root board (the root's own block, expanded in this search: the chosen child's prior is read from it), or
+//   * the leaf board has the mover's stone on the cell the move occupies: every leaf below the kept child has, and so has a leaf
+//     that reaches the same stones in another order -- a row too many, never one too few --, or
+//   * no move was drawn (keep == -2: a stalled slot keeps its whole tree and its counter restarts in k_play_apply; a resignation),
+//     or the move is not legal (advance_body flags it).
+// k_keep_mark: one workgroup per game, a wave per 64 slots: the needed records as bit masks, their number and the number of
+// records with a block (what the full flush writes).
+struct Keep {
+    unsigned long long *mask;   // [G][words]: bit s % 64 of word s / 64 = record (s, g) is needed
+    int32_t *cnt, *pcnt;        // [G] needed records / records with a block
+    int32_t *rows;              // [slots * G] the needed records, game-major, slots ascending
+    int32_t *count;             // [1] their number
+    unsigned long long *stats;  // [2] needed / with a block, summed since the last reset (rz_deferred_keep_stats)
+    int words;
+};
+
+__global__ __launch_bounds__(256) void k_keep_mark(Dev E, const int32_t *__restrict__ keep_of, Keep Kp) {
+    __shared__ int sh[4][2];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = E.pend[g] < E.pend_cap ? E.pend[g] : E.pend_cap;
+    const int keep = keep_of[g];
+    uint64_t root[2][kWords], occ[kWords];
+    load_board(E.root_stones, g, root);
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) occ[j] = root[0][j] | root[1][j];
+    const Legal L = legal_of(E, occ, lane);
+    int rank = 0, cell = 0;
+    const bool all = keep < 0 || !locate_action(E, occ, L, keep, rank, cell);
+    const bool second = E.root_to_move[g] != 0;   // the mover's colour
+    int kept = 0, with_block = 0;
+    for (int s0 = 64 * wave; s0 < n; s0 += 256) {
+        const int s = s0 + lane;
+        const long long rec = (long long)s * E.n_games + g;
+        const bool has = s < n && E.pend_pb[rec] >= 0;
+        bool need = has && all;
+        if (has && !all) {
+            uint64_t st[2][kWords];
+            load_board(E.pend_stones, (int)rec, st);
+            bool same = true;
+            uint64_t mine[kWords];
+#pragma unroll
+            for (int j = 0; j < kWords; ++j) {
+                same = same && st[0][j] == root[0][j] && st[1][j] == root[1][j];
+                mine[j] = second ? st[1][j] : st[0][j];
+            }
+            need = same || test_bit(mine, cell);
+        }
+        const unsigned long long m = __ballot(need);
+        if (lane == 0) Kp.mask[(long long)g * Kp.words + (s0 >> 6)] = m;
+        kept += __popcll(m);
+        with_block += __popcll(__ballot(has));
+    }
+    if (lane == 0) sh[wave][0] = kept, sh[wave][1] = with_block;
+    __syncthreads();
+    if (tid == 0) {
+        Kp.cnt[g] = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
+        Kp.pcnt[g] = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
+    }
+}
+
+// k_keep_rows: one wave per game: where the game's rows begin (the prefix of cnt over the games before it), then its needed
+// records in slot order (ballot masks of k_keep_mark + mbcnt: k_play_order's compaction).  The last game's wave leaves the total.
+__global__ __launch_bounds__(kWave) void k_keep_rows(Dev E, Keep Kp) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const bool last = g == E.n_games - 1;
+    int base = 0, pending = 0;
+    for (int h = lane; h < g; h += kWave) base += Kp.cnt[h];
+    if (last)
+        for (int h = lane; h < E.n_games; h += kWave) pending += Kp.pcnt[h];
+    for (int off = 32; off >= 1; off >>= 1) {
+        base += __shfl_xor(base, off);
+        pending += __shfl_xor(pending, off);
+    }
+    const int n = E.pend[g] < E.pend_cap ? E.pend[g] : E.pend_cap;
+    int at = base;
+    for (int s0 = 0; s0 < n; s0 += kWave) {
+        const unsigned long long m = Kp.mask[(long long)g * Kp.words + (s0 >> 6)];
+        const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+        if ((m >> lane) & 1ull) Kp.rows[at + pre] = (s0 + lane) * E.n_games + g;
+        at += __popcll(m);
+    }
+    if (last && lane == 0) {
+        Kp.count[0] = at;
+        Kp.stats[0] += (unsigned long long)at;
+        Kp.stats[1] += (unsigned long long)pending;
+    }
+}
+
+// k_deferred_priors over the listed records: a fixed grid of waves (the count is the device's), logits of row i in row i
+__global__ __launch_bounds__(kWave) void k_deferred_priors_rows(Dev E, const float *__restrict__ raw, int ld, const int32_t *__restrict__ rows,
+                                                                const int32_t *__restrict__ count) {
+    const int lane = threadIdx.x, n = count[0];
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int rec = rows[i];
+        deferred_priors_body(E, rec % E.n_games, rec, raw + (size_t)i * ld, lane);
     }
 }
 
@@ -1530,6 +1635,7 @@ struct rz_engine {
     int32_t *pl_counts = nullptr, *pl_order = nullptr;
     bool pl_on = false, pl_ordered = false;
     bool cap_ordered = true;   // rz_play_set_cap_order: k_play_order runs and the resident search follows it
+    Keep keep = {};            // the kept flush (rz_deferred_keep): sized by rz_deferred_reserve
 };
 
 namespace {
@@ -2030,6 +2136,17 @@ int rz_deferred_reserve(rz_engine *e, int32_t slots) {
         if ((rc = dev_alloc(e, &e->dev.pend, G)) != RZ_OK) return rc;
     }
     RZ_HIP(hipMemset(e->dev.pend, 0, (size_t)G * sizeof(int32_t)));
+    // the kept flush: a mask bit and a place in the row list per record, two counts per game
+    Keep &kp = e->keep;
+    kp.words = (slots + 63) / 64;
+    if ((rc = dev_alloc(e, &kp.mask, (long long)kp.words * G)) != RZ_OK) return rc;
+    if ((rc = dev_alloc(e, &kp.rows, (long long)slots * G)) != RZ_OK) return rc;
+    if (kp.cnt == nullptr) {
+        if ((rc = dev_alloc(e, &kp.cnt, G)) != RZ_OK || (rc = dev_alloc(e, &kp.pcnt, G)) != RZ_OK) return rc;
+        if ((rc = dev_alloc(e, &kp.count, 1)) != RZ_OK || (rc = dev_alloc(e, &kp.stats, 2)) != RZ_OK) return rc;
+        RZ_HIP(hipMemset(kp.stats, 0, 2 * sizeof(unsigned long long)));
+    }
+    RZ_HIP(hipMemset(kp.count, 0, sizeof(int32_t)));
     e->dev.pend_cap = slots;
     return RZ_OK;
 }
@@ -2105,6 +2222,50 @@ int rz_deferred_flush(rz_engine *e, const rz_deferred_logits *logits, int32_t n_
     // (between rz_play_draw and rz_play_apply the counters restart in k_play_apply: one launch less in the chain of a move)
     if (!(e->play_on && e->play_drawn)) k_deferred_reset<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev);
     return launched("k_deferred_priors");
+}
+
+static int keep_ok(rz_engine *e) {
+    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    if (!(e->play_on && e->play_drawn)) return fail(RZ_ERR_ARG, "the kept flush runs between rz_play_draw and rz_play_apply (the move decides what is kept)");
+    return RZ_OK;
+}
+
+int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if (!out) return fail(RZ_ERR_ARG, "NULL output pointer");
+    if ((rc = keep_ok(e)) != RZ_OK) return rc;
+    k_keep_mark<<<per_game(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play.keep, e->keep);
+    k_keep_rows<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->keep);
+    out->rows = e->keep.rows;
+    out->count = e->keep.count;
+    out->capacity = (int64_t)e->dev.pend_cap * e->cfg.n_games;
+    out->n_games = e->cfg.n_games;
+    out->reserved = 0;
+    return launched("k_keep_rows");
+}
+
+int rz_deferred_flush_kept(rz_engine *e, const rz_deferred_logits *logits, void *stream) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if ((rc = keep_ok(e)) != RZ_OK) return rc;
+    if (!logits || !logits->raw) return fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
+    if (logits->ld < e->dev.A) return fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
+    // (eight waves per CU of a large chip; the counters restart in k_play_apply)
+    k_deferred_priors_rows<<<dim3(2048), dim3(kWave), 0, as_stream(stream)>>>(e->dev, logits->raw, logits->ld, e->keep.rows, e->keep.count);
+    return launched("k_deferred_priors_rows");
+}
+
+int rz_deferred_keep_stats(rz_engine *e, uint64_t *h_out2, int32_t reset) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if (!h_out2) return fail(RZ_ERR_ARG, "NULL output pointer");
+    h_out2[0] = h_out2[1] = 0;
+    if (!e->keep.stats) return RZ_OK;
+    RZ_HIP(hipDeviceSynchronize());
+    RZ_HIP(hipMemcpy(h_out2, e->keep.stats, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reset) RZ_HIP(hipMemset(e->keep.stats, 0, 2 * sizeof(uint64_t)));
+    return RZ_OK;
 }
 
 int rz_tree_step_raw(rz_engine *e, const rz_raw_heads *heads, float *d_obs, void *stream) {

@@ -2397,17 +2397,22 @@ struct FsFrags {
 // is unconditional -- a load under a branch makes hipcc wait for ALL outstanding loads (vmcnt(0)) before each use,
 // which serialises the ring: a step past the end of the wave's K range re-reads the last feature step against the
 // all-zero weight fragment `zero` (pack_split_fc appends one), and so does an N-tile past the last output tile.
-template <int TM, int TN>
+// ROWS (k_heads_rows): the lane's board of A-tile m is a row of its own somewhere in the store -- far[m] points at that board's
+// fragment of K-step 0 (its tile, its place lane_a in the fragment); the step is added as for a whole tile.
+template <int TM, int TN, bool ROWS = false>
 __device__ __forceinline__ void fs_load(FsFrags<TM, TN> &f, const f32x4 *__restrict__ fa, const f32x4 *const (&fb)[TN],
-                                        const f32x4 *__restrict__ zero, int steps_a, int a_step0, int step, int k1, int lane) {
+                                        const f32x4 *__restrict__ zero, int steps_a, int a_step0, int step, int k1, int lane,
+                                        const f32x4 *const *far = nullptr) {
     const bool live = step < k1;
     const int sa = a_step0 + (live ? step : k1 - 1);
     const int lane_a = ((lane & 31) << 1) | (lane >> 5);  // features: [board % 32][k / 8 % 2] x 8 f16 (k_trunk_split)
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
-            f.a[m][p] = __builtin_bit_cast(sp::f16x8, fa[(((size_t)m * steps_a + sa) * 2 + p) * 64 + lane_a]);
+        for (int p = 0; p < 2; ++p) {
+            if constexpr (ROWS) f.a[m][p] = __builtin_bit_cast(sp::f16x8, far[m][((size_t)sa * 2 + p) * 64]);
+            else f.a[m][p] = __builtin_bit_cast(sp::f16x8, fa[(((size_t)m * steps_a + sa) * 2 + p) * 64 + lane_a]);
+        }
 #pragma unroll
     for (int n = 0; n < TN; ++n) {
         // (a tile that does not exist has fb[n] == zero: every step of it reads the one zero fragment)
@@ -2419,13 +2424,14 @@ __device__ __forceinline__ void fs_load(FsFrags<TM, TN> &f, const f32x4 *__restr
 
 // acc[m][n] += sum over K-steps [k0, k1) of A-tile m (features) x B-tile n (weights, fb[n] -> its step 0, or the zero
 // fragment for a tile that does not exist)
-template <int TM, int TN, int DEPTH>
+template <int TM, int TN, int DEPTH, bool ROWS = false>
 __device__ __forceinline__ void fs_gemm(sp::f32x16 (&acc)[TM][TN], const f32x4 *__restrict__ fa, const f32x4 *const (&fb)[TN],
-                                        const f32x4 *__restrict__ zero, int steps_a, int a_step0, int k0, int k1, int lane) {
+                                        const f32x4 *__restrict__ zero, int steps_a, int a_step0, int k0, int k1, int lane,
+                                        const f32x4 *const *far = nullptr) {
     if (k0 >= k1) return;
     FsFrags<TM, TN> ring[DEPTH];
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d) fs_load<TM, TN>(ring[d], fa, fb, zero, steps_a, a_step0, k0 + d, k1, lane);
+    for (int d = 0; d < DEPTH; ++d) fs_load<TM, TN, ROWS>(ring[d], fa, fb, zero, steps_a, a_step0, k0 + d, k1, lane, far);
     __builtin_amdgcn_sched_barrier(0);
     for (int k = k0; k < k1; k += DEPTH) {
 #pragma unroll
@@ -2438,7 +2444,7 @@ __device__ __forceinline__ void fs_gemm(sp::f32x16 (&acc)[TM][TN], const f32x4 *
                     for (int n = 0; n < TN; ++n)
                         acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring[d].a[m][combo == 2], ring[d].b[n][combo == 1],
                                                                           acc[m][n], 0, 0, 0);
-            fs_load<TM, TN>(ring[d], fa, fb, zero, steps_a, a_step0, k + d + DEPTH, k1, lane);
+            fs_load<TM, TN, ROWS>(ring[d], fa, fb, zero, steps_a, a_step0, k + d + DEPTH, k1, lane, far);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -2543,6 +2549,82 @@ __global__ __launch_bounds__(256) void k_heads_split(NetDev nd, const f32x4 *__r
 #pragma unroll
             for (int r = 0; r < 16; ++r) dst[(8 * (r >> 2) + (r & 3)) * 64] = fmaxf(fmaf(v[r], scale, bias), 0.0f);
         }
+    }
+}
+
+// k_heads_rows: k_heads_split<TM, TN, DEPTH, false, PAIRED>'s policy GEMM over a LIST of rows of the deferred store (the kept flush:
+// rz_deferred_keep) -- rows[i] = slot * n_games + game is board game % 32 of store tile slot * store_tiles + game / 32, and lane l of
+// A-tile m of row block b gathers row rows[32 * (TM * b + m) + (l & 31)]: a per-lane base under fs_load's index.  The K quarters per
+// wave, the MFMA order, the LDS sum in wave order and fmaf(sum, scale, bias) are k_heads_split's and MFMA rows do not mix: the logits
+// of a row are the bits of the GEMM over the whole store.  Output row i = listed row i.  The count is the device's (the launch sits
+// in a captured move), so the grid is FIXED: its workgroups stride over the row blocks below the count -- the two output groups of a
+// block 8 apart, one XCD (PAIRED) -- and meet at a barrier before `part` is written again.  Every load is unconditional (fs_load): a
+// row past the count reads the first listed row again, and what it computes lands in rows nobody reads (the logits buffer has rows
+// for whole blocks: the list's capacity is a multiple of 32 * TM).
+template <int TM, int TN, int DEPTH>
+__global__ __launch_bounds__(256) void k_heads_rows(NetDev nd, const f32x4 *__restrict__ store16, float *__restrict__ raw,
+                                                    const int32_t *__restrict__ rows, const int32_t *__restrict__ count, int n_games,
+                                                    int store_tiles) {
+    __shared__ sp::f32x16 part[4][TM * TN][64];  // [K quarter][tile][lane]
+    const int n_act_tiles = nd.Npad / 32, n_groups = (n_act_tiles + TN - 1) / TN;
+    int block0 = blockIdx.x, group = 0, stride = gridDim.x;
+    if (n_groups == 2) {   // (the host's grid is a multiple of 16)
+        group = (block0 >> 3) & 1;
+        block0 = ((block0 >> 4) << 3) | (block0 & 7);
+        stride >>= 1;
+    }
+    const int n = count[0];
+    const int n_blocks = (n + 32 * TM - 1) / (32 * TM);
+    __builtin_amdgcn_s_setprio(3);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int K = nd.groups_act, k0 = wave * K / 4, k1 = (wave + 1) * K / 4;
+    const f32x4 *zero = nd.fs_act + (size_t)n_act_tiles * K * 128;  // one all-zero K-step behind the weights
+    const int col = lane & 31, h = lane >> 5;
+    const f32x4 *fb[TN];
+#pragma unroll
+    for (int t = 0; t < TN; ++t) fb[t] = TN * group + t < n_act_tiles ? nd.fs_act + (size_t)(TN * group + t) * K * 128 : zero;
+    const float scale = nd.s_inv[3];
+    for (int blk = block0; blk < n_blocks; blk += stride) {   // (uniform: every wave of the workgroup meets the barriers)
+        const f32x4 *far[TM];
+#pragma unroll
+        for (int m = 0; m < TM; ++m) {
+            const int i = 32 * (TM * blk + m) + col;
+            const int rec = rows[i < n ? i : 0];
+            const int slot = rec / n_games, g = rec - slot * n_games;
+            far[m] = store16 + (size_t)(slot * store_tiles + (g >> 5)) * K * 128 + (((g & 31) << 1) | h);
+        }
+        sp::f32x16 acc[TM][TN];
+#pragma unroll
+        for (int m = 0; m < TM; ++m)
+#pragma unroll
+            for (int t = 0; t < TN; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
+        fs_gemm<TM, TN, DEPTH, true>(acc, nullptr, fb, zero, K, 0, k0, k1, lane, far);
+#pragma unroll
+        for (int m = 0; m < TM; ++m)
+#pragma unroll
+            for (int t = 0; t < TN; ++t) part[wave][m * TN + t][lane] = acc[m][t];
+        __syncthreads();
+        // wave w finishes tiles w, w + 4, ...: D column = output (lane & 31), rows = boards 8g + 4h + j
+#pragma unroll
+        for (int t = wave; t < TM * TN; t += 4) {
+            const int m = t / TN, nt = t % TN;
+            if (TN * group + nt >= n_act_tiles) continue;
+            sp::f32x16 v = part[0][t][lane];
+#pragma unroll
+            for (int q = 1; q < 4; ++q) {
+                const sp::f32x16 pq = part[q][t][lane];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) v[r] += pq[r];
+            }
+            const int c = 32 * (TN * group + nt) + col;
+            const float bias = nd.fc_act_b[c];
+            float *dst = raw + (size_t)(32 * (TM * blk + m) + 4 * h) * nd.Npad + c;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dst[(size_t)(8 * (r >> 2) + (r & 3)) * nd.Npad] = fmaf(v[r], scale, bias);
+        }
+        __syncthreads();   // `part` is written again in the next round
     }
 }
 
@@ -3741,6 +3823,29 @@ int rz_net_deferred_gemm(rz_net *net, int32_t n_boards, int32_t n_slots, rz_defe
     out->raw = net->d_store_raw;
     out->ld = net->dev.Npad;
     out->rows_per_slot = net->store_tiles * 32;
+    return RZ_OK;
+}
+
+int rz_net_deferred_gemm_rows(rz_net *net, const rz_kept_rows *kept, rz_deferred_logits *out, void *stream) {
+    if (!kept || !out) return net_fail(RZ_ERR_ARG, "NULL argument");
+    int rc = net_ready(net, kept->n_games);
+    if (rc != RZ_OK) return rc;
+    if (!kept->rows || !kept->count) return net_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
+    // a listed row addresses slot rows[i] / n_games < capacity / n_games of the store, and logits row i < capacity exists
+    if (kept->n_games < 1 || kept->n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)net->store_slots * kept->n_games)
+        return net_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
+    NetDev nd = net->dev;
+    nd.groups_val = 0;   // a tile of the store holds the policy K-steps only
+    const int n_act_tiles = nd.Npad / 32, n_groups = (n_act_tiles + 3) / 4;
+    if (n_groups > 2) return net_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
+    // one workgroup per CU (`part` is 128 KB of its LDS), whole groups of 16 (k_heads_rows: the output groups of a block 8 apart)
+    const dim3 grid((unsigned)(((net->n_cus > 16 ? net->n_cus : 16) + 15) / 16 * 16));
+    k_heads_rows<2, 4, 3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(nd, reinterpret_cast<const f32x4 *>(net->d_store16), net->d_store_raw,
+                                                                     kept->rows, kept->count, kept->n_games, net->store_tiles);
+    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_rows failed");
+    out->raw = net->d_store_raw;
+    out->ld = net->dev.Npad;
+    out->rows_per_slot = 0;
     return RZ_OK;
 }
 

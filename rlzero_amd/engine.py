@@ -273,6 +273,12 @@ class HipNet(object):
               'rz_net_deferred_gemm')
         return out
 
+    def deferred_gemm_rows(self, kept):
+        """act_fc1 over the listed rows of the store (RzKeptRows of the engine's rz_deferred_keep) -> RzDeferredLogits, row i = listed row i."""
+        out = _hip.RzDeferredLogits()
+        check(self.lib.rz_net_deferred_gemm_rows(self.handle, ctypes.byref(kept), ctypes.byref(out), self._stream()), 'rz_net_deferred_gemm_rows')
+        return out
+
     def range_info(self):
         """What rz_net_load derived from the weights for the split-f16 trunk: bounds on the activations of conv1 /
         conv2 / the head features for observation planes in [0, 1], the power-of-two scales their f16 pieces are
@@ -681,6 +687,9 @@ class MCTSEngine(object):
         # 4096 games is 15 GB of 288 -- below the cap the search is one launch and the move one hipGraph (19 MB per slot at 4096 games)
         self.deferred_max_bytes = 32 << 30
         self._playouts = None   # set_playouts: (counts, order) device tensors of the per-game simulation counts in force
+        # the flush of a move on the device writes only the priors the move keeps (RZ_FLUSH_KEPT=0: all of them, as every other flush
+        # does); read when the flush is enqueued -- a captured move keeps the setting it was captured under
+        self.flush_kept = os.environ.get('RZ_FLUSH_KEPT', '1') != '0'
 
     # ------------------------------------------------------------------ plumbing
     def stream(self):
@@ -984,9 +993,10 @@ class MCTSEngine(object):
                 self._def_stream = self.torch.cuda.current_stream(self.device)
             n -= m
 
-    def flush_deferred(self):
+    def flush_deferred(self, move=False):
         """Write the priors of every expansion since the last flush (one GEMM over the stored leaves + one kernel).  Called by
-        whatever reads priors or moves trees (advance, set_roots, root_priors, arena) and when the store is full."""
+        whatever reads priors or moves trees (advance, set_roots, root_priors, arena) and when the store is full.  ``move``: the
+        caller stands between rz_play_draw and rz_play_apply -- the flush may leave out what the move discards (flush_kept)."""
         if self._def_pending <= 0 or self._def_ev is None:
             return
         # the pending steps were enqueued on _def_stream; a caller on another stream (a direct engine user, a read-out from the
@@ -994,11 +1004,34 @@ class MCTSEngine(object):
         cur, then = self.torch.cuda.current_stream(self.device), getattr(self, '_def_stream', None)
         if then is not None and then != cur:
             cur.wait_stream(then)
-        logits = self._def_ev.hip.deferred_gemm(self.n_leaves, self._def_pending)
-        check(self.lib.rz_deferred_flush(self.handle, ctypes.byref(logits), self._def_pending, self.stream()), 'rz_deferred_flush')
+        if move:
+            self._enqueue_move_flush(self._def_ev.hip, self._def_pending)
+        else:
+            logits = self._def_ev.hip.deferred_gemm(self.n_leaves, self._def_pending)
+            check(self.lib.rz_deferred_flush(self.handle, ctypes.byref(logits), self._def_pending, self.stream()), 'rz_deferred_flush')
         if then is not None and then != cur:
             then.wait_stream(cur)
         self._def_pending = 0
+
+    def _enqueue_move_flush(self, hip, n_slots):
+        """The flush of a move's search, between rz_play_draw and rz_play_apply, on the current stream: the priors of the records the
+        drawn move keeps (``flush_kept``: the kept child's subtree and the root's own block -- blocks of subtrees the move discards
+        are never written), or of all ``n_slots`` x n_games of them."""
+        lib, h, st = self.lib, self.handle, self.stream()
+        if self.flush_kept:
+            kept = _hip.RzKeptRows()
+            check(lib.rz_deferred_keep(h, ctypes.byref(kept), st), 'rz_deferred_keep')
+            logits = hip.deferred_gemm_rows(kept)
+            check(lib.rz_deferred_flush_kept(h, ctypes.byref(logits), st), 'rz_deferred_flush_kept')
+        else:
+            logits = hip.deferred_gemm(self.n_leaves, n_slots)
+            check(lib.rz_deferred_flush(h, ctypes.byref(logits), n_slots, st), 'rz_deferred_flush')
+
+    def flush_kept_stats(self, reset=False):
+        """-> (records the kept flushes wrote, records the full flush would have written) since the last reset; synchronises."""
+        out = (ctypes.c_uint64 * 2)()
+        check(self.lib.rz_deferred_keep_stats(self.handle, out, 1 if reset else 0), 'rz_deferred_keep_stats')
+        return int(out[0]), int(out[1])
 
     def _whole_steps(self, n_sims):
         """``n_sims`` rounded down to whole steps of K simulations (at least one step)."""
@@ -1256,7 +1289,7 @@ class MCTSEngine(object):
         before the kept subtree is copied), tree reuse + game step + the end / refill of slots (rz_play_apply).  -> the log row."""
         st = self.stream()
         check(self.lib.rz_play_draw(self.handle, st), 'rz_play_draw')
-        self.flush_deferred()
+        self.flush_deferred(move=True)
         check(self.lib.rz_play_apply(self.handle, st), 'rz_play_apply')
         self.roots_epoch += 1
         row = self.play_steps % self.play_log.shape[0]
@@ -1289,8 +1322,7 @@ class MCTSEngine(object):
                 st = self.stream()
                 evaluator.search_resident(self, n, True)
                 check(lib.rz_play_draw(h, st), 'rz_play_draw')
-                logits = hip.deferred_gemm(self.n_leaves, n)
-                check(lib.rz_deferred_flush(h, ctypes.byref(logits), n, st), 'rz_deferred_flush')
+                self._enqueue_move_flush(hip, n)
                 check(lib.rz_play_apply(h, st), 'rz_play_apply')
         finally:
             self._capturing = False
