@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 29
+#define RZ_ABI_VERSION 30
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -420,7 +420,21 @@ int rz_step_games(rz_engine *e, const int32_t *d_moves, int32_t *d_winner, uint8
  * Slots refill themselves: a slot whose game has ended (or that is idle) takes the next entry of a queue of game ids shared by
  * the engines (lanes) of a GPU -- d_queue_ids int64 [..], d_queue_ctl int32 [2] = {head, entries valid}; the device advances
  * head atomically, the host may append ids and then raise the count -- and starts that game: empty board, player 0 to move, a
- * fresh tree, its Dirichlet stream keyed (seed, game id) exactly as rlzero_amd.selfplay keys it. */
+ * fresh tree, its Dirichlet stream keyed (seed, game id) exactly as rlzero_amd.selfplay keys it.
+ *
+ * Network-vs-network matches (an opt-in mode, off after every rz_play_attach; ABI 30): GameControl.start_play (game.py:61-94) with
+ * two AlphaZeroPlayer(is_selfplay=False) (alphazero_mcts.py:136-165), each with a network of its own.  rz_play_set_match hands
+ * over a table of openings -- legal, non-terminal positions -- and changes three things in the move step, none in a search kernel:
+ *   * games 2k and 2k + 1 are a PAIR: a refilled slot starts from opening (game id >> 1) % n_openings (stones, side to move, last
+ *     move; fresh tree; ply 0, counted from the opening), and network A is player 0 of the even game, player 1 of the odd one;
+ *   * the draw's uniform is that of (seed, game id >> 1, 2 * ply + 1): the second of get_action's two draws (:157), shared by the
+ *     two games of a pair -- a network against itself plays every pair as the same game twice;
+ *   * every move is searched from a fresh root (reset_player, :158): k_play_apply drops the tree where it keeps the drawn child's
+ *     subtree in self-play, after a resolved stall too.
+ * rz_play_side(side) sets the engine's active flags to the running games whose mover is network `side`.  One move of a match, all
+ * on one stream: rz_play_side(0), the resident search with A's evaluator, rz_play_side(1), the resident search with B's,
+ * rz_play_draw, the flush of the pending priors, rz_play_apply.  Stalled and idle slots are searched by neither.  The log is the
+ * one above; who won and by how much is the host's to say (rlzero_amd/match.py). */
 #define RZ_PLAY_RECORD_WORDS 8
 enum {
     RZ_PLAY_RUNNING = 1,   /* the slot holds a game: the visit counts are valid */
@@ -470,6 +484,20 @@ int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream);
 /* Whether the cap's searches take their workgroups in the partition's order (default) or in slot order (0: no order kernel in the
  * move step; a measurement's switch).  A host-side setting read when launches are enqueued: set it before a move graph is captured. */
 int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
+/* Match mode (above).  The table -- d_open_stones uint64 [n_openings][2][RZ_BOARD_WORDS], d_open_to_move / d_open_last int32
+ * [n_openings], device memory -- is copied on `stream` into the engine's own; launches enqueued after the call read it.
+ * n_openings == 0 (pointers ignored): off again.  Valid after rz_play_attach, before the games are queued, on an engine without
+ * Dirichlet noise on the resident search's route (RZ_SCORE_UCT_REF, sims_in_flight == 1), with neither resignation nor a playout
+ * cap set since rz_play_attach: RZ_ERR_ARG otherwise -- and rz_play_set_resign / rz_play_set_cap return RZ_ERR_ARG while it is on.
+ * Like theirs, the flag is a kernel argument: with it off the move step reads and writes nothing more than before. */
+int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t *d_open_to_move, const int32_t *d_open_last, int32_t n_openings,
+                      void *stream);
+/* The active flags of the coming search: slot g is searched iff it is running and its mover is network `side` (0 = A, 1 = B; A
+ * moves iff (side to move == 0) == (game id even)).  One launch, a thread per slot.  RZ_ERR_ARG while match mode is off. */
+int rz_play_side(rz_engine *e, int32_t side, void *stream);
+/* A host copy of the active flags uint8 [n_games] for inspection (synchronous): what rz_set_active, the move step and rz_play_side
+ * have left for the next search. */
+int rz_active_read(rz_engine *e, uint8_t *h_active);
 /* The host's decision for a stalled slot (one tiny launch); taken by the next rz_play_draw. */
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream);
 /* Drop every game: all slots idle with fresh trees (a run that stops early). */

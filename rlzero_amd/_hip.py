@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -150,6 +150,9 @@ _SIGNATURES = {
     'rz_playouts_view': (c_int, [P, POINTER(c_void_p), POINTER(c_void_p)]),
     'rz_play_set_cap_order': (c_int, [P, c_int32]),
     'rz_playouts_read': (c_int, [P, P, P, POINTER(c_int32)]),
+    'rz_play_set_match': (c_int, [P, P, P, P, c_int32, P]),
+    'rz_play_side': (c_int, [P, c_int32, P]),
+    'rz_active_read': (c_int, [P, P]),
     'rz_play_resolve': (c_int, [P, c_int32, c_int32, P]),
     'rz_play_stop': (c_int, [P, P]),
     'rz_play_state': (c_int, [P, P, P, P, POINTER(c_int64)]),

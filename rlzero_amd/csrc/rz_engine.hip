@@ -40,6 +40,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1267,6 +1268,12 @@ struct Play {
     int32_t *order;            // [G] k_play_order's: the slots with a full search, those with a fast one, the inactive ones
     int n_full;                // the engine's n_playout
     int cap_on;                // rz_play_set_cap called since rz_play_attach: the kernels read `cap` (else never)
+    // network-vs-network matches (rz_play_set_match): games 2k and 2k + 1 start from opening k % n_open, share their draw uniforms and
+    // are searched from a fresh root by the network whose turn it is (k_play_side); the engine's own copies of the caller's table
+    const uint64_t *open_stones;   // [n_open][2][kWords]
+    const int32_t *open_to_move, *open_last;   // [n_open]
+    int n_open;
+    int match_on;              // rz_play_set_match in force: the kernels read the table and the pair's uniform (else never)
 };
 enum { kPlayIdle = 0, kPlayRunning = 1, kPlayStalled = 2 };
 constexpr int kStepResign = -3;   // Play::stepm of a slot whose mover resigned: k_play_apply ends the game without a step
@@ -1301,6 +1308,8 @@ __device__ __forceinline__ void cap_write(const Play &Y, int g, int64_t gid, int
 
 // One wave per slot: the root's visit counts into the log, then the draw of alphazero_mcts.py:88-92,147-148 in fp64 -- taken only
 // when the uniform lies farther than `margin` from both edges of its interval (the host's numpy evaluation is the arbiter).
+// In a match (rz_play_set_match) the uniform is the pair's -- (seed, game id >> 1, 2 ply + 1) -- and the move keeps no subtree:
+// keep = -1, so k_play_apply starts the next search of the game from a fresh root; stepm stays the move.
 __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     __shared__ double sh_e[kWave * kWords];
     const int g = blockIdx.x;
@@ -1369,7 +1378,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
                 Y.state[g] = kPlayRunning;
                 Y.ply[g] = ply + 1;
                 E.active[g] = 1;
-                Y.keep[g] = mv;
+                Y.keep[g] = Y.match_on ? -1 : mv;   // (a match searches every move from a fresh root: reset_player, :158)
                 Y.stepm[g] = mv;
             } else {
                 rec[3] = -1;
@@ -1414,7 +1423,9 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         // cumsum in action order (numpy's cumsum is sequential too), then the first interval whose upper edge exceeds u x total
         double total = 0.0;
         for (int a = 0; a < E.A; ++a) total += sh_e[a];
-        const double u = play_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply);
+        // (a match: the uniform of the PAIR and of the second of get_action's two draws, alphazero_mcts.py:157)
+        const double u = Y.match_on ? play_uniform(Y.seed, (uint64_t)gid >> 1, 2ull * (uint64_t)ply + 1ull)
+                                    : play_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply);
         const double target = u * total;
         double c = 0.0, below = 0.0;
         int chosen = -1;
@@ -1436,7 +1447,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
             rec[3] = chosen;
             rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | extra | full;
             Y.ply[g] = ply + 1;
-            Y.keep[g] = chosen;
+            Y.keep[g] = Y.match_on ? -1 : chosen;
             Y.stepm[g] = chosen;
         } else {
             rec[3] = -1;
@@ -1452,7 +1463,8 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
 // The rest of a move in ONE launch, one wave per slot: update_with_move with the move just drawn (advance_body: before the board
 // changes), env.step + game_end_winner (step_body), then the end of a finished game (reset_player, game.py:128) and the refill of an
 // idle slot from the queue of game ids (GomokuEnv.reset, gomoku_env.py:33-47: empty board, player 0; a fresh tree; the game's
-// noise key).  drawn == 0 (no k_play_draw before it): only the refill.  The pending-priors counter of the game restarts here
+// noise key; in a match -- rz_play_set_match -- the opening of the game's pair instead of the empty board).  drawn == 0 (no
+// k_play_draw before it): only the refill.  The pending-priors counter of the game restarts here
 // (the flush of the move's search ran just before: rz_deferred_flush leaves its own reset launch out between draw and apply).
 __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) {
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -1502,9 +1514,16 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     Y.ply[g] = 0;
     Y.state[g] = kPlayRunning;
     Y.mailbox[g] = -1;
-    for (int j = 0; j < 2 * kWords; ++j) E.root_stones[(long long)g * 2 * kWords + j] = 0ull;
-    E.root_to_move[g] = 0;
-    E.root_last[g] = -1;
+    if (Y.match_on) {   // the pair's opening; plies count from it
+        const long long o = (long long)((gid >> 1) % Y.n_open);
+        for (int j = 0; j < 2 * kWords; ++j) E.root_stones[(long long)g * 2 * kWords + j] = Y.open_stones[o * 2 * kWords + j] & E.valid[j % kWords];
+        E.root_to_move[g] = Y.open_to_move[o] & 1;
+        E.root_last[g] = Y.open_last[o];
+    } else {
+        for (int j = 0; j < 2 * kWords; ++j) E.root_stones[(long long)g * 2 * kWords + j] = 0ull;
+        E.root_to_move[g] = 0;
+        E.root_last[g] = -1;
+    }
     fresh_root(E, g, E.cur_arena[g], 0);
     E.noise_key[g] = mix64(mix64(Y.seed ^ 0x6E6F697365000000ull) ^ (uint64_t)gid);   // rlzero_amd/selfplay.py: _start
     E.noise_ctr[g] = 0;
@@ -1573,6 +1592,15 @@ __global__ __launch_bounds__(256) void k_play_order(const uint8_t *__restrict__ 
     }
 }
 
+// rz_play_side: the slots the coming search takes -- the running games whose mover is network `side` (0 = A: player 0 of the even
+// game of a pair, player 1 of the odd one).  side < 0: every running game (what k_play_apply leaves; match mode turned off).
+__global__ void k_play_side(Dev E, Play Y, int side) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.n_games) return;
+    const bool a_moves = (E.root_to_move[g] == 0) == ((Y.game_id[g] & 1) == 0);
+    E.active[g] = (Y.state[g] == kPlayRunning && (side < 0 || side == (a_moves ? 0 : 1))) ? 1 : 0;
+}
+
 __global__ void k_play_resolve(Play Y, int slot, int move) { Y.mailbox[slot] = move; }
 __global__ void k_play_set_resign(double *resign, double threshold, double disabled_frac) {
     if (threadIdx.x == 0) {
@@ -1636,6 +1664,7 @@ struct rz_engine {
     bool pl_on = false, pl_ordered = false;
     bool cap_ordered = true;   // rz_play_set_cap_order: k_play_order runs and the resident search follows it
     Keep keep = {};            // the kept flush (rz_deferred_keep): sized by rz_deferred_reserve
+    int open_cap = 0;          // rz_play_set_match: openings the engine's copy of the table has room for
 };
 
 namespace {
@@ -2384,6 +2413,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.margin = cfg->stall_margin > 0.0 ? cfg->stall_margin : 1e-10 * (Y.inv_t > 1.0 ? Y.inv_t : 1.0);
     Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
     Y.cap_on = 0;      // (and so is the playout cap: rz_play_set_cap)
+    Y.match_on = 0;    // (and match mode: rz_play_set_match)
     Y.n_full = e->cfg.n_playout;
     RZ_HIP(hipMemset(Y.step_ab, 0, 8));
     RZ_HIP(hipMemset(Y.ply, 0, (size_t)G * 4));
@@ -2421,6 +2451,7 @@ int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, voi
     RZ_ENTER(e);
     if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
     if (!(disabled_frac >= 0.0 && disabled_frac <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_resign: disabled_frac %g not in [0, 1]", disabled_frac);
+    if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_resign: a match is on (rz_play_set_match): its games are played to the end");
     k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
     e->play.resign_on = 1;
     return launched("k_play_set_resign");
@@ -2437,6 +2468,7 @@ int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream) {
     if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
     int rc = playouts_route_ok(e, "rz_play_set_cap");
     if (rc != RZ_OK) return rc;
+    if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_cap: a match is on (rz_play_set_match): every search of it has n_playout simulations");
     if (!std::isnan(p_full)) {
         if (!(p_full > 0.0 && p_full <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_cap: p_full %g not in (0, 1]", p_full);
         if (n_fast < 1 || n_fast > e->cfg.n_playout) return fail(RZ_ERR_ARG, "rz_play_set_cap: n_fast %d not in 1 .. n_playout = %d", n_fast, e->cfg.n_playout);
@@ -2499,6 +2531,65 @@ int rz_playouts_read(rz_engine *e, int32_t *h_counts, int32_t *h_order, int32_t 
     if (dc != nullptr && h_counts != nullptr) RZ_HIP(hipMemcpy(h_counts, dc, G * 4, hipMemcpyDeviceToHost));
     if (dor != nullptr && h_order != nullptr) RZ_HIP(hipMemcpy(h_order, dor, G * 4, hipMemcpyDeviceToHost));
     *h_source = dc == nullptr ? 0 : (e->pl_on ? 1 : 2) | (dor != nullptr ? 4 : 0);
+    return RZ_OK;
+}
+
+int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t *d_open_to_move, const int32_t *d_open_last, int32_t n_openings,
+                      void *stream) {
+    RZ_ENTER(e);
+    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    Play &Y = e->play;
+    if (n_openings == 0) {   // off again: the slots' flags as k_play_apply leaves them
+        if (Y.match_on) k_play_side<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, Y, -1);
+        Y.match_on = 0;
+        return launched("k_play_side");
+    }
+    if (n_openings < 0 || !d_open_stones || !d_open_to_move || !d_open_last) return fail(RZ_ERR_ARG, "rz_play_set_match: a table of n_openings >= 1 positions is needed");
+    if (e->cfg.add_noise) return fail(RZ_ERR_ARG, "rz_play_set_match: a match is played without Dirichlet noise (add_noise = 0)");
+    if (e->dev.K != 1 || e->dev.score_mode != RZ_SCORE_UCT_REF)
+        return fail(RZ_ERR_ARG, "rz_play_set_match: matches need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)");
+    if (Y.resign_on || Y.cap_on) return fail(RZ_ERR_ARG, "rz_play_set_match: resignation or a playout cap is set (attach again: a match has neither)");
+    if (n_openings > e->open_cap) {   // (hipFree waits for the device: no launch still reads the old table)
+        const void *old[3] = {Y.open_stones, Y.open_to_move, Y.open_last};
+        for (const void *p : old) {
+            if (p == nullptr) continue;
+            e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), const_cast<void *>(p)), e->allocs.end());
+            RZ_HIP(hipFree(const_cast<void *>(p)));
+        }
+        Y.open_stones = nullptr, Y.open_to_move = Y.open_last = nullptr;
+        e->open_cap = 0;
+        uint64_t *st = nullptr;
+        int32_t *tm = nullptr, *la = nullptr;
+        int rc = RZ_OK;
+        if ((rc = dev_alloc(e, &st, (long long)n_openings * 2 * kWords)) != RZ_OK) return rc;
+        Y.open_stones = st;
+        if ((rc = dev_alloc(e, &tm, n_openings)) != RZ_OK) return rc;
+        Y.open_to_move = tm;
+        if ((rc = dev_alloc(e, &la, n_openings)) != RZ_OK) return rc;
+        Y.open_last = la;
+        e->open_cap = n_openings;
+    }
+    RZ_HIP(hipMemcpyAsync(const_cast<uint64_t *>(Y.open_stones), d_open_stones, (size_t)n_openings * 2 * kWords * 8, hipMemcpyDeviceToDevice, as_stream(stream)));
+    RZ_HIP(hipMemcpyAsync(const_cast<int32_t *>(Y.open_to_move), d_open_to_move, (size_t)n_openings * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
+    RZ_HIP(hipMemcpyAsync(const_cast<int32_t *>(Y.open_last), d_open_last, (size_t)n_openings * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
+    Y.n_open = n_openings;
+    Y.match_on = 1;
+    return RZ_OK;
+}
+
+int rz_play_side(rz_engine *e, int32_t side, void *stream) {
+    RZ_ENTER(e);
+    if (!e->play_on || !e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_side: call rz_play_set_match first");
+    if (side != 0 && side != 1) return fail(RZ_ERR_ARG, "rz_play_side: side %d is neither 0 (network A) nor 1 (network B)", side);
+    k_play_side<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play, side);
+    return launched("k_play_side");
+}
+
+int rz_active_read(rz_engine *e, uint8_t *h_active) {
+    RZ_ENTER(e);
+    RZ_NEED(h_active);
+    RZ_HIP(hipDeviceSynchronize());
+    RZ_HIP(hipMemcpy(h_active, e->dev.active, (size_t)e->cfg.n_games, hipMemcpyDeviceToHost));
     return RZ_OK;
 }
 

@@ -1279,6 +1279,7 @@ class MCTSEngine(object):
         self.play_steps = 0
         self.play_resign_on = False   # (rz_play_attach turns resignation off)
         self.play_cap_on = False      # (and the playout cap)
+        self.play_match_on = False    # (and match mode)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log
@@ -1305,6 +1306,8 @@ class MCTSEngine(object):
         r, owner, _ = self._ask(evaluator)
         if not r.resident or getattr(self, 'play_log', None) is None:
             return None
+        if getattr(self, 'play_match_on', False):
+            raise HipError('warm_move_graph: a match (play_set_match) searches with two evaluators per move; its moves are enqueued eagerly')
         n = self.n_playout
         if self._playouts is not None:
             raise HipError('warm_move_graph: clear set_playouts first (the graph would hold the host\'s counts, not play_set_cap\'s)')
@@ -1377,6 +1380,41 @@ class MCTSEngine(object):
         """Whether play_set_cap's searches follow the device's longest-first partition (default) or the slot order; before the move
         graph is captured."""
         check(self.lib.rz_play_set_cap_order(self.handle, 1 if longest_first else 0), 'rz_play_set_cap_order')
+
+    def play_set_match(self, openings):
+        """Match mode of the move step on the device (rz_play_set_match), enqueued on the current stream: ``openings`` = (stones
+        uint64 [n, 2, WORDS], to_move [n], last_move [n]) -- n >= 1 legal, non-terminal positions (match.opening_arrays) -- or None:
+        off again.  While it is on, games 2k and 2k + 1 start from opening k % n, share their draw uniforms (seed, k, 2 ply + 1),
+        every move is searched from a fresh root and ``play_side`` says which network's games the coming search takes.  After
+        play_attach and before the games are queued.  HipError (the library's argument error) on an engine with Dirichlet noise,
+        the PUCT rule or sims_in_flight > 1, or with resignation or a playout cap set since play_attach; play_set_resign and
+        play_set_cap are refused the same way while a match is on."""
+        t = self.torch
+        if openings is None:
+            check(self.lib.rz_play_set_match(self.handle, None, None, None, 0, self.stream()), 'rz_play_set_match')
+            self.play_match_on, self._play_openings = False, None
+            return
+        stones, to_move, last = openings
+        stones = np.ascontiguousarray(stones, dtype=np.uint64)
+        n = stones.shape[0]
+        if n < 1 or stones.shape != (n, 2, WORDS):
+            raise ValueError('openings: stones uint64 [n >= 1, 2, %d]' % WORDS)
+        dev = [t.from_numpy(stones.view(np.int64)).to(self.device)] + \
+              [t.from_numpy(np.ascontiguousarray(x, dtype=np.int32).reshape(n)).to(self.device) for x in (to_move, last)]
+        check(self.lib.rz_play_set_match(self.handle, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), n, self.stream()), 'rz_play_set_match')
+        self._play_openings = dev   # (alive until the engine's copy, enqueued on the stream, has been made)
+        self.play_match_on = True
+
+    def play_side(self, side):
+        """The active flags of the coming search of a match (rz_play_side): the running games whose mover is network ``side``
+        (0 = A: player 0 of even game ids, player 1 of odd ones; 1 = B).  One launch on the current stream."""
+        check(self.lib.rz_play_side(self.handle, int(side), self.stream()), 'rz_play_side')
+
+    def active_flags(self):
+        """-> uint8 [G]: the engine's active flags as the next search would read them (rz_active_read); synchronises."""
+        out = np.zeros(self.n_games, np.uint8)
+        check(self.lib.rz_active_read(self.handle, ctypes.c_void_p(out.ctypes.data)), 'rz_active_read')
+        return out
 
     def play_resolve(self, slot, move):
         check(self.lib.rz_play_resolve(self.handle, int(slot), int(move), self.stream()), 'rz_play_resolve')

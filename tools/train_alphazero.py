@@ -9,7 +9,9 @@ Two ways to collect self-play data:
     through ``GameControl.start_self_play`` and ``AlphaZeroPlayer`` (search on the GPU);
   * ``selfplay_games_in_flight  > 0``: that many games in lock-step per collection round and GPU
     (``rlzero_amd.selfplay.BatchedSelfPlay``), the mode the hardware is built for; ``policy_evaluate``'s games then
-    run in lock-step as well (``rlzero_amd.evaluate.BatchedEvaluation``).
+    run in lock-step as well (``rlzero_amd.evaluate.BatchedEvaluation``), and ``--gate-against CKPT`` adds, at every
+    ``check_freq``, the score of a match from paired openings against that checkpoint (``rlzero_amd.match``: reported next to
+    the pure-MCTS win ratio, nothing is decided on it).
 
 Several GPUs (``python tools/train_alphazero.py --gpus N ...`` starts one process per GPU itself, or run it under
 ``torch.distributed.run``): the games of a collection round are dealt to the ranks by id (game g -> rank g mod N, no
@@ -148,7 +150,7 @@ class TrainPipeline:
 
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
-                 resign_fp_target=0.05, playout_cap=None):
+                 resign_fp_target=0.05, playout_cap=None, gate_against=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -161,7 +163,13 @@ class TrainPipeline:
         sets the threshold from the calibration games of the last rounds (selfplay.calibrate_resign_threshold, at most
         ``resign_fp_target`` false positives) and hands it to every rank.  ``resign_disabled_frac``: the calibration games.
         ``playout_cap``: None or (n_fast, p_full) -- playout cap randomization (BatchedSelfPlay.set_playout_cap; batched mode only, an
-        opt-in extension): the replay buffer takes the plies searched with the full budget (Trajectory.training_samples)."""
+        opt-in extension): the replay buffer takes the plies searched with the full budget (Trajectory.training_samples).
+        ``gate_against``: None or a checkpoint (batched mode only): at every ``check_freq`` the current network plays a match from
+        paired openings against it (rlzero_amd.match) and the score is printed next to the pure-MCTS win ratio; nothing is decided
+        on it."""
+        if gate_against is not None and selfplay_games_in_flight <= 0:
+            raise ValueError('the gate match is a batched-mode option: selfplay_games_in_flight must be > 0')
+        self.gate_against, self._gate, self._gate_rounds = gate_against, None, 0
         if playout_cap is not None and selfplay_games_in_flight <= 0:
             raise ValueError('the playout cap is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.playout_cap = None if playout_cap is None else (int(playout_cap[0]), float(playout_cap[1]))
@@ -490,6 +498,24 @@ class TrainPipeline:
                                                                   win_cnt[2], win_cnt[-1]))
         return win_ratio
 
+    def gate_match(self, n_pairs=8, n_openings=4, opening_plies=2):
+        """The current network (A) against the ``gate_against`` checkpoint (B): ``n_pairs`` pairs from ``n_openings`` fresh openings
+        -> the score (rlzero_amd.match.score).  Monitoring only."""
+        from rlzero_amd.match import BatchedMatch, load_checkpoint, paired_openings, score
+        if self._gate is None:
+            opponent = load_checkpoint(self.gate_against, self.board_size, str(self.device))
+            self._gate = BatchedMatch.for_networks(self.alphazero_agent.policy_value_net, opponent, self.board_size, self.n_in_row,
+                                                   n_games=2 * n_pairs, n_playout=self.n_playout, c_puct=self.c_puct,
+                                                   device=str(self.device), seed=self.selfplay_seed)
+        self._gate.refresh_weights()
+        self._gate.seed = (self.selfplay_seed + 0x9E37 * self._gate_rounds) & 0x7fffffff   # fresh openings and draws every time
+        self._gate_rounds += 1
+        openings = paired_openings(self.board_size, self.n_in_row, n_openings, opening_plies, self._gate.seed)
+        s = score(self._gate.run(n_pairs, openings))
+        print('gate against {}: score: {:.3f}, win: {}, lose: {}, tie: {}, elo: {:+.0f}'.format(
+            self.gate_against, s['a_score'], s['a_wins'], s['b_wins'], s['ties'], s['elo_diff']))
+        return s
+
     def _sync_weights(self):
         """After rank 0's policy_update: its parameters on every rank (one broadcast; nothing to do in one process)."""
         if self.world > 1:
@@ -510,6 +536,8 @@ class TrainPipeline:
                 if lead and (i + 1) % self.check_freq == 0:
                     print('current self-play batch: {}'.format(i + 1))
                     win_ratio = self.policy_evaluate()
+                    if self.gate_against is not None:
+                        self.gate_match()
                     self.alphazero_agent.save_model('./current_policy.model')
                     if win_ratio > self.best_win_ratio:
                         print('New best policy!!!!!!!!')
@@ -567,7 +595,12 @@ def parse_args(argv=None):
     ap.add_argument('--playout-cap', type=playout_cap_arg, default=None, metavar='N_FAST:P_FULL',
                     help='playout cap randomization (batched mode only): a search has --playouts simulations with probability P_FULL, '
                          'else N_FAST; only the full ones become policy samples')
+    ap.add_argument('--gate-against', default=None, metavar='CKPT',
+                    help='batched mode only: at every --check-freq also report the match score of the current network against this '
+                         'checkpoint (paired openings; nothing is decided on it)')
     args = ap.parse_args(argv)
+    if args.gate_against is not None and args.games_in_flight <= 0:
+        ap.error('--gate-against needs --games-in-flight > 0 (batched mode)')
     if args.playout_cap is not None and args.games_in_flight <= 0:
         ap.error('--playout-cap needs --games-in-flight > 0 (batched self-play)')
     if args.playout_cap is not None and args.playout_cap[0] > args.playouts:
@@ -593,7 +626,7 @@ def main():
     pipe = TrainPipeline(board_size=args.board, n_in_row=args.n_in_row, n_playout=args.playouts, game_batch_num=args.batches,
                          check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed,
                          resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
-                         resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap)
+                         resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
