@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 30
+#define RZ_ABI_VERSION 31
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -799,6 +799,55 @@ int rz_mz_root_children(rz_muzero *e, int32_t what, void *d_out, void *stream);
 int rz_mz_root_stats(rz_muzero *e, int32_t *d_n, double *d_value_sum, double *d_vmin, double *d_vmax, void *stream);
 int rz_mz_geometry(rz_muzero *e, int32_t *slots_per_game, int64_t *device_bytes);
 int rz_mz_error_flags(rz_muzero *e, int32_t *flags);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Device replay buffer (ABI 31; rz_replay.hip; an opt-in extension -- the reference's learner keeps its samples in a host
+ * deque, tools/train_alphazero.py:32,59-79,88-90).  Gomoku, square boards of 3 .. 16 rows, A = B * B actions.
+ *
+ * The store is a ring of `capacity` self-contained POSITIONS (eviction is per position, nothing refers to a game):
+ *   stones  uint64 [capacity][2][RZ_BOARD_WORDS]   [0] = the stones of the player to move, [1] = the opponent's (bit a = cell a)
+ *   meta    int32  [capacity]                      bits 0..8 last move + 1 (0: none), bit 9 ply parity, bits 10..11 z + 1
+ *   pi      float32[capacity][A]
+ * The write cursor and the count are HOST state of the handle (rz_replay_state) and travel to the kernels as arguments.
+ * Position j counts from the OLDEST one held; an ENTRY is e = 8 * j + k, k = the symmetry in get_equi_data's order
+ * (train_alphazero.py:59-79) -- entry for entry what deque(maxlen = 8 * capacity).extend(get_equi_data(play_data)) holds.
+ * Every call below takes a stream and is ordered on it; calls of one handle come from one host thread.
+ *
+ * rz_replay_set_tables: h_src_state / h_src_pi int16 [8][A] -- for output cell o of symmetry k the SOURCE cell of the planes
+ *   and of pi.  Two different permutations (the reference rotates the planes by +k * 90 degrees and pi through a flipud /
+ *   rot90 / flipud sandwich): the host obtains both by pushing arange(A) through the reference's numpy expressions
+ *   (rlzero_amd/replay.py: symmetry_tables).  Entries outside 0 .. A-1 are refused.  Required before gather / sample.
+ * rz_replay_add: n_games finished games in ONE launch (k_replay_add: a workgroup per game, a thread per ply).  h_offsets int32
+ *   [n_games + 1] into h_moves int32 / h_keep uint8 (a game's plies; a game longer than A plies is refused), h_winner int32
+ *   (0, 1, -1 = tie), h_pi float32 [kept plies of all games, in order][A].  Thread p forms the position before move p from the
+ *   moves q < p (a stone of ply q is the mover's when q and p have the same parity) and z (+1 on the winner's plies, -1 on the
+ *   loser's, 0 on a tie: game.py:121-126); the kept plies are compacted in ply order and written, with their pi rows, to
+ *   consecutive ring slots modulo capacity; plies without a keep flag still place their stones.  Of more kept plies than the
+ *   capacity only the last `capacity` are written.  One staging copy (pinned host memory of the handle) precedes the launch.
+ * rz_replay_gather: n entries in ONE launch (k_replay_gather: a workgroup per entry, a thread per output cell) into
+ *   d_states float32 [n][4][B][B] (own stones, the opponent's, the last move's one-hot, ones iff the ply is even:
+ *   gomoku_env.py:95-114), d_pis float32 [n][A], d_zs float32 [n].  The indices are int64, from the host (h_indices: checked
+ *   here, RZ_ERR_ARG for one outside 0 .. 8 * count - 1) or from the device (d_indices: checked by the kernel -- such an entry
+ *   is not written and bit 1 of the flags of rz_replay_poll_errors is set); exactly one of the two is not NULL.
+ * rz_replay_sample: the same kernel body with the indices drawn on the device (k_replay_sample): entry i of update `step` is
+ *   mulhi64(x, 8 * count) of the splitmix64 chain x = sm(sm(sm(seed ^ "replay\0\0") ^ step) ^ i) -- WITH replacement, where
+ *   random.sample draws without; integer only, every entry's probability within 2^-64 of 1 / (8 * count).
+ *   rlzero_amd/replay.py: replay_index gives the same bits.  RZ_ERR_ARG on an empty buffer.
+ * rz_replay_read: a SYNCHRONOUS copy of n raw records from position `first` (oldest = 0) to host arrays (any may be NULL).
+ * rz_replay_poll_errors: the device's flag word (waits for `stream`), cleared by the call. */
+typedef struct rz_replay rz_replay;
+int rz_replay_create(int32_t board_size, int64_t capacity, int32_t device, rz_replay **out);
+int rz_replay_destroy(rz_replay *r);
+int rz_replay_set_tables(rz_replay *r, const int16_t *h_src_state, const int16_t *h_src_pi, void *stream);
+int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity);
+int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
+                  const int32_t *h_winner, const float *h_pi, void *stream);
+int rz_replay_gather(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, int64_t n, float *d_states, float *d_pis,
+                     float *d_zs, void *stream);
+int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_states, float *d_pis, float *d_zs,
+                     void *stream);
+int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream);
+int rz_replay_poll_errors(rz_replay *r, int32_t *flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, 'librlzero_hip.so')
 OBJ_DIR = os.path.join(PKG, 'csrc', '_obj')
-SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip')]
+SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip', 'rz_replay.hip')]
 HEADERS = [os.path.join(REPO, "include", "rlzero_hip.h"), os.path.join(PKG, "csrc", "rz_trace.h"), os.path.join(PKG, "csrc", "rz_tree.h"), os.path.join(PKG, "csrc", "rz_delta.h"), os.path.join(PKG, "csrc", "rz_window.h")]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fno-fast-math', '-fno-slp-vectorize', '-std=c++17',
          '-fPIC', '-Wall', '-Wno-unused-function']
@@ -36,7 +36,7 @@ def _digest(paths, extra=''):
 
 
 def source_hash():
-    """Hash of everything the library is built from: the three sources, the headers, the flags."""
+    """Hash of everything the library is built from: the four sources, the headers, the flags."""
     return _digest(SOURCES + HEADERS, ' '.join(FLAGS))
 
 

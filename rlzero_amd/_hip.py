@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -88,6 +88,7 @@ PLAY_RECORD_WORDS = 8
 PLAY_RUNNING, PLAY_STALLED, PLAY_RESOLVED, PLAY_ENDED, PLAY_SEARCHED = 1, 2, 4, 8, 16
 PLAY_RESIGNED, PLAY_NO_RESIGN, PLAY_WOULD_RESIGN = 32, 64, 128   # resignation (rz_play_set_resign, ABI 27)
 PLAY_FULL = 256   # playout cap (rz_play_set_cap, ABI 28): the record's search had the full budget
+REPLAY_BAD_INDEX = 1   # rz_replay_poll_errors (ABI 31): an entry index from the device was out of range
 
 
 class HipError(RuntimeError):
@@ -206,6 +207,15 @@ _SIGNATURES = {
     'rz_mz_root_stats': (c_int, [P, P, P, P, P, P]),
     'rz_mz_geometry': (c_int, [P, POINTER(c_int32), POINTER(c_int64)]),
     'rz_mz_error_flags': (c_int, [P, POINTER(c_int32)]),
+    'rz_replay_create': (c_int, [c_int32, c_int64, c_int32, POINTER(c_void_p)]),
+    'rz_replay_destroy': (c_int, [P]),
+    'rz_replay_set_tables': (c_int, [P, P, P, P]),
+    'rz_replay_state': (c_int, [P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    'rz_replay_add': (c_int, [P, c_int32, P, P, P, P, P, P]),
+    'rz_replay_gather': (c_int, [P, P, P, c_int64, P, P, P, P]),
+    'rz_replay_sample': (c_int, [P, c_uint64, c_uint64, c_int64, P, P, P, P]),
+    'rz_replay_read': (c_int, [P, c_int64, c_int64, P, P, P, P]),
+    'rz_replay_poll_errors': (c_int, [P, POINTER(c_int32), P]),
 }
 
 _lib = None

@@ -1,0 +1,446 @@
+// rz_replay.hip -- the device replay buffer (include/rlzero_hip.h: rz_replay_*, ABI 31).
+//
+// The learner's samples live in device memory as a ring of self-contained positions (two bitboards, one meta word, a pi row) and
+// a mini-batch is ONE launch: k_replay_gather / k_replay_sample write the observation planes, the symmetry-transformed pi and z
+// of every entry straight into the learner's tensors.  The eight symmetries are two tables of source cells the host obtained
+// from the reference's own numpy expressions (tools/train_alphazero.py:59-79) -- the planes and pi are permuted DIFFERENTLY there,
+// and nothing here re-derives either permutation.  k_replay_add forms the positions of finished games from their move lists.
+//
+// Bounds: every slot is reduced modulo the capacity, every table entry is checked at upload (< A), an entry index from the device
+// is checked by the kernel before anything is read, moves are checked on the host (< A) and index registers, not memory.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "rlzero_hip.h"
+
+void rz_set_error(const char *msg);  // rz_engine.hip
+
+namespace {
+
+constexpr int kMaxCells = RZ_MAX_BOARD_SIZE * RZ_MAX_BOARD_SIZE;   // 256: plies of a game = threads of k_replay_add
+constexpr int kRecWords = 2 * RZ_BOARD_WORDS;                      // uint64 words of a position's stones
+constexpr unsigned long long kReplaySalt = 0x7265706C61790000ull;  // "replay": the sampler's own stream
+constexpr int kMetaParityBit = 9, kMetaZShift = 10;
+constexpr int kFlagBadIndex = 1;
+
+struct ReplayDev {
+    unsigned long long *stones;   // [capacity][2][RZ_BOARD_WORDS]
+    int32_t *meta;                // [capacity]
+    float *pi;                    // [capacity][A]
+    const int16_t *src_state;     // [8][A]
+    const int16_t *src_pi;        // [8][A]
+    int32_t *err;
+    long long capacity;
+    int A;
+};
+
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    unsigned long long z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// entry i of update `step`: the high half of x * n_entries (integer only; a value's probability is floor or ceil of 2^64 / n over
+// 2^64, i.e. within 2^-64 of 1 / n)
+__device__ __forceinline__ long long replay_index(unsigned long long seed, unsigned long long step, unsigned long long i,
+                                                  unsigned long long n_entries) {
+    unsigned long long x = splitmix64(seed ^ kReplaySalt);
+    x = splitmix64(x ^ step);
+    x = splitmix64(x ^ i);
+    return (long long)__umul64hi(x, n_entries);
+}
+
+// One workgroup per game, thread p = ply p (blockDim.x == 256 >= plies).  `base[g]`: kept plies of the games before g; a kept ply of
+// global rank t goes to slot (cursor + t) % capacity unless t < skip (more kept plies than slots: only the last `capacity` are
+// written, so no two threads of the launch share a slot).
+__global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int32_t *__restrict__ offsets, const int32_t *__restrict__ base,
+                                                           const int32_t *__restrict__ winner, const int32_t *__restrict__ moves,
+                                                           const uint8_t *__restrict__ keep, const float *__restrict__ pi_rows,
+                                                           long long cursor, long long skip) {
+    __shared__ int32_t s_moves[kMaxCells];
+    __shared__ int32_t s_slot[kMaxCells];
+    __shared__ int32_t s_row[kMaxCells];
+    __shared__ int32_t s_kept[kMaxCells / 64];
+    const int g = blockIdx.x, p = threadIdx.x, lane = p & 63, wave = p >> 6;
+    const int off = offsets[g];
+    const int P = min(offsets[g + 1] - off, kMaxCells);
+    const bool in = p < P;
+    s_moves[p] = in ? (moves[off + p] & (kMaxCells - 1)) : 0;
+    const bool kept = in && keep[off + p] != 0;
+    const unsigned long long ballot = __ballot(kept);
+    if (lane == 0) s_kept[wave] = __popcll(ballot);
+    __syncthreads();
+    int rank = __popcll(ballot & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) rank += s_kept[w];
+    const long long t = (long long)base[g] + rank;
+    int slot = -1;
+    if (kept && t >= skip) {
+        slot = (int)((cursor + t) % R.capacity);
+        unsigned long long own[RZ_BOARD_WORDS] = {0, 0, 0, 0}, opp[RZ_BOARD_WORDS] = {0, 0, 0, 0};
+        for (int q = 0; q < p; ++q) {
+            const int m = s_moves[q];
+            const unsigned long long bit = 1ull << (m & 63);
+            const bool mine = ((q ^ p) & 1) == 0;   // ply q was the mover's when q and p have the same parity
+#pragma unroll
+            for (int w = 0; w < RZ_BOARD_WORDS; ++w) {
+                own[w] |= (mine && (m >> 6) == w) ? bit : 0ull;
+                opp[w] |= (!mine && (m >> 6) == w) ? bit : 0ull;
+            }
+        }
+        unsigned long long *rec = R.stones + (long long)slot * kRecWords;
+#pragma unroll
+        for (int w = 0; w < RZ_BOARD_WORDS; ++w) {
+            rec[w] = own[w];
+            rec[RZ_BOARD_WORDS + w] = opp[w];
+        }
+        const int win = winner[g];
+        const int z = win < 0 ? 0 : ((p & 1) == win ? 1 : -1);
+        const int last = p > 0 ? s_moves[p - 1] + 1 : 0;
+        R.meta[slot] = last | ((p & 1) << kMetaParityBit) | ((z + 1) << kMetaZShift);
+    }
+    s_slot[p] = slot;
+    s_row[p] = (int32_t)t;
+    __syncthreads();
+    // the pi rows: a wave per kept ply, coalesced
+    for (int q = wave; q < P; q += kMaxCells / 64) {
+        const int sl = s_slot[q];
+        if (sl < 0) continue;
+        const float *src = pi_rows + (long long)s_row[q] * R.A;
+        float *dst = R.pi + (long long)sl * R.A;
+        for (int o = lane; o < R.A; o += 64) dst[o] = src[o];
+    }
+}
+
+// entry e -> output row i: a thread per output cell (blockDim.x >= A)
+__device__ __forceinline__ void replay_emit(const ReplayDev &R, long long e, long long oldest, long long i, float *__restrict__ states,
+                                            float *__restrict__ pis, float *__restrict__ zs) {
+    const int o = threadIdx.x, A = R.A, k = (int)(e & 7);
+    const long long slot = (oldest + (e >> 3)) % R.capacity;
+    const unsigned long long *rec = R.stones + slot * kRecWords;   // (uniform across the workgroup)
+    const unsigned long long a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], b0 = rec[4], b1 = rec[5], b2 = rec[6], b3 = rec[7];
+    const int meta = R.meta[slot];
+    if (o == 0) zs[i] = (float)(((meta >> kMetaZShift) & 3) - 1);
+    if (o >= A) return;
+    const int s = R.src_state[k * A + o];
+    const int w = s >> 6;
+    const unsigned long long own = w == 0 ? a0 : w == 1 ? a1 : w == 2 ? a2 : a3;
+    const unsigned long long opp = w == 0 ? b0 : w == 1 ? b1 : w == 2 ? b2 : b3;
+    float *out = states + i * 4 * A;
+    out[o] = (float)((own >> (s & 63)) & 1ull);
+    out[A + o] = (float)((opp >> (s & 63)) & 1ull);
+    out[2 * A + o] = (s + 1 == (meta & 511)) ? 1.0f : 0.0f;
+    out[3 * A + o] = ((meta >> kMetaParityBit) & 1) ? 0.0f : 1.0f;
+    pis[i * A + o] = R.pi[slot * A + R.src_pi[k * A + o]];
+}
+
+__global__ __launch_bounds__(kMaxCells) void k_replay_gather(ReplayDev R, const long long *__restrict__ indices, long long oldest,
+                                                              long long n_entries, float *__restrict__ states, float *__restrict__ pis,
+                                                              float *__restrict__ zs) {
+    const long long i = blockIdx.x;
+    const long long e = indices[i];
+    if (e < 0 || e >= n_entries) {   // an index from the device: nothing is read or written for it
+        if (threadIdx.x == 0) atomicOr(R.err, kFlagBadIndex);
+        return;
+    }
+    replay_emit(R, e, oldest, i, states, pis, zs);
+}
+
+__global__ __launch_bounds__(kMaxCells) void k_replay_sample(ReplayDev R, unsigned long long seed, unsigned long long step, long long oldest,
+                                                              long long n_entries, float *__restrict__ states, float *__restrict__ pis,
+                                                              float *__restrict__ zs) {
+    const long long i = blockIdx.x;
+    replay_emit(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
+}
+
+int rp_fail(int code, const char *msg) {
+    rz_set_error(msg);
+    return code;
+}
+
+}  // namespace
+
+struct rz_replay {
+    ReplayDev dev = {};
+    int board = 0, device = 0;
+    long long cursor = 0, count = 0;   // next slot written; positions held
+    int16_t *d_tables = nullptr;
+    bool tables = false;
+    // one staging pair (pinned host + device), reused: the host half after `copied`, the device half after `consumed`
+    void *h_stage = nullptr, *d_stage = nullptr;
+    size_t stage_bytes = 0;
+    hipEvent_t copied = nullptr, consumed = nullptr;
+    bool in_flight = false;
+};
+
+namespace {
+
+int rp_ready(rz_replay *r) {
+    if (r == nullptr) return rp_fail(RZ_ERR_ARG, "replay handle is NULL");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipGetDevice failed");
+    if (cur != r->device && hipSetDevice(r->device) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    return RZ_OK;
+}
+
+// the staging pair with room for `bytes`, its host half free to be written; `stream` waits for the device half's last reader
+int rp_stage(rz_replay *r, size_t bytes, hipStream_t stream) {
+    if (r->in_flight && hipEventSynchronize(r->copied) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventSynchronize failed (replay staging)");
+    if (bytes > r->stage_bytes) {
+        if (r->in_flight && hipEventSynchronize(r->consumed) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventSynchronize failed (replay staging)");
+        r->in_flight = false;
+        if (r->h_stage) (void)hipHostFree(r->h_stage);
+        if (r->d_stage) (void)hipFree(r->d_stage);
+        r->h_stage = r->d_stage = nullptr;
+        r->stage_bytes = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc(&r->h_stage, want, hipHostMallocDefault) != hipSuccess) return rp_fail(RZ_ERR_OOM, "hipHostMalloc failed (replay staging)");
+        if (hipMalloc(&r->d_stage, want) != hipSuccess) return rp_fail(RZ_ERR_OOM, "hipMalloc failed (replay staging)");
+        r->stage_bytes = want;
+    }
+    if (r->in_flight && hipStreamWaitEvent(stream, r->consumed, 0) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipStreamWaitEvent failed (replay staging)");
+    return RZ_OK;
+}
+
+int rp_upload(rz_replay *r, size_t bytes, hipStream_t stream) {
+    if (hipMemcpyAsync(r->d_stage, r->h_stage, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "staging copy failed (replay)");
+    if (hipEventRecord(r->copied, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventRecord failed (replay)");
+    return RZ_OK;
+}
+
+int rp_launched(rz_replay *r, hipStream_t stream, const char *what) {
+    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, what);
+    if (hipEventRecord(r->consumed, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventRecord failed (replay)");
+    r->in_flight = true;
+    return RZ_OK;
+}
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int rp_outputs(rz_replay *r, int64_t n, const float *d_states, const float *d_pis, const float *d_zs) {
+    if (!r->tables) return rp_fail(RZ_ERR_ARG, "rz_replay_set_tables has not been called");
+    if (n < 0 || n > 0x7fffffffLL) return rp_fail(RZ_ERR_ARG, "n out of range");
+    if (n > 0 && (d_states == nullptr || d_pis == nullptr || d_zs == nullptr)) return rp_fail(RZ_ERR_ARG, "NULL output buffer");
+    return RZ_OK;
+}
+
+inline unsigned rp_block(const rz_replay *r) { return (unsigned)((r->dev.A + 63) / 64 * 64); }
+inline long long rp_oldest(const rz_replay *r) { return ((r->cursor - r->count) % r->dev.capacity + r->dev.capacity) % r->dev.capacity; }
+
+}  // namespace
+
+extern "C" {
+
+int rz_replay_create(int32_t board_size, int64_t capacity, int32_t device, rz_replay **out) {
+    if (out == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (board_size < 3 || board_size > RZ_MAX_BOARD_SIZE) return rp_fail(RZ_ERR_ARG, "board_size outside 3 .. 16");
+    if (capacity < 1 || capacity > (1LL << 24)) return rp_fail(RZ_ERR_ARG, "capacity outside 1 .. 2^24 positions");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rp_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    rz_replay *r = new (std::nothrow) rz_replay();
+    if (!r) return rp_fail(RZ_ERR_OOM, "host allocation failed");
+    r->board = board_size;
+    r->device = device;
+    ReplayDev &D = r->dev;
+    D.A = board_size * board_size;
+    D.capacity = capacity;
+    const size_t cap = (size_t)capacity, A = (size_t)D.A;
+    bool ok = hipMalloc((void **)&D.stones, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
+              hipMalloc((void **)&D.meta, cap * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&D.pi, cap * A * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&r->d_tables, 2 * 8 * A * sizeof(int16_t)) == hipSuccess && hipMalloc((void **)&D.err, sizeof(int32_t)) == hipSuccess;
+    if (!ok) {
+        rz_replay_destroy(r);
+        return rp_fail(RZ_ERR_OOM, "hipMalloc failed (replay store)");
+    }
+    D.src_state = r->d_tables;
+    D.src_pi = r->d_tables + 8 * A;
+    ok = hipMemset(D.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(D.stones, 0, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
+         hipMemset(D.meta, 0, cap * sizeof(int32_t)) == hipSuccess && hipMemset(D.pi, 0, cap * A * sizeof(float)) == hipSuccess &&
+         hipEventCreateWithFlags(&r->copied, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&r->consumed, hipEventDisableTiming) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        rz_replay_destroy(r);
+        return rp_fail(RZ_ERR_HIP, "initialisation of the replay store failed");
+    }
+    *out = r;
+    return RZ_OK;
+}
+
+int rz_replay_destroy(rz_replay *r) {
+    if (r == nullptr) return RZ_OK;
+    (void)hipSetDevice(r->device);
+    (void)hipDeviceSynchronize();
+    if (r->copied) (void)hipEventDestroy(r->copied);
+    if (r->consumed) (void)hipEventDestroy(r->consumed);
+    if (r->h_stage) (void)hipHostFree(r->h_stage);
+    void *dev[] = {r->d_stage, r->dev.stones, r->dev.meta, r->dev.pi, r->d_tables, r->dev.err};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    delete r;
+    return RZ_OK;
+}
+
+int rz_replay_set_tables(rz_replay *r, const int16_t *h_src_state, const int16_t *h_src_pi, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (h_src_state == nullptr || h_src_pi == nullptr) return rp_fail(RZ_ERR_ARG, "NULL table");
+    const int A = r->dev.A;
+    for (int i = 0; i < 8 * A; ++i)
+        if (h_src_state[i] < 0 || h_src_state[i] >= A || h_src_pi[i] < 0 || h_src_pi[i] >= A) return rp_fail(RZ_ERR_ARG, "table entry outside 0 .. A-1");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t half = (size_t)8 * A * sizeof(int16_t);
+    rc = rp_stage(r, 2 * half, s);
+    if (rc != RZ_OK) return rc;
+    memcpy(r->h_stage, h_src_state, half);
+    memcpy((char *)r->h_stage + half, h_src_pi, half);
+    rc = rp_upload(r, 2 * half, s);
+    if (rc != RZ_OK) return rc;
+    if (hipMemcpyAsync(r->d_tables, r->d_stage, 2 * half, hipMemcpyDeviceToDevice, s) != hipSuccess) return rp_fail(RZ_ERR_HIP, "table copy failed (replay)");
+    rc = rp_launched(r, s, "table copy failed (replay)");
+    if (rc != RZ_OK) return rc;
+    r->tables = true;
+    return RZ_OK;
+}
+
+int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity) {
+    if (r == nullptr) return rp_fail(RZ_ERR_ARG, "replay handle is NULL");
+    if (count) *count = r->count;
+    if (cursor) *cursor = r->cursor;
+    if (capacity) *capacity = r->dev.capacity;
+    return RZ_OK;
+}
+
+int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
+                  const int32_t *h_winner, const float *h_pi, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (n_games < 0) return rp_fail(RZ_ERR_ARG, "n_games < 0");
+    if (n_games == 0) return RZ_OK;
+    if (h_offsets == nullptr || h_winner == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    const int A = r->dev.A;
+    if (h_offsets[0] != 0) return rp_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
+    std::vector<int32_t> base((size_t)n_games);
+    long long kept = 0;
+    for (int g = 0; g < n_games; ++g) {
+        const long long P = (long long)h_offsets[g + 1] - h_offsets[g];
+        if (P < 0) return rp_fail(RZ_ERR_ARG, "h_offsets must not decrease");
+        if (P > A) return rp_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
+        if (h_winner[g] < -1 || h_winner[g] > 1) return rp_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
+        if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rp_fail(RZ_ERR_ARG, "NULL argument");
+        base[(size_t)g] = (int32_t)kept;
+        for (int p = h_offsets[g]; p < h_offsets[g + 1]; ++p) {
+            if (h_moves[p] < 0 || h_moves[p] >= A) return rp_fail(RZ_ERR_ARG, "a move is outside the board");
+            kept += h_keep[p] != 0;
+        }
+    }
+    const long long total = h_offsets[n_games];
+    if (kept == 0) return RZ_OK;
+    if (h_pi == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    // staging: offsets | base | winner | moves | keep | pi rows
+    const size_t o_off = 0, o_base = o_off + align16(((size_t)n_games + 1) * 4), o_win = o_base + align16((size_t)n_games * 4),
+                 o_moves = o_win + align16((size_t)n_games * 4), o_keep = o_moves + align16((size_t)total * 4),
+                 o_pi = o_keep + align16((size_t)total), bytes = o_pi + (size_t)kept * A * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    rc = rp_stage(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    char *h = (char *)r->h_stage, *d = (char *)r->d_stage;
+    memcpy(h + o_off, h_offsets, ((size_t)n_games + 1) * 4);
+    memcpy(h + o_base, base.data(), (size_t)n_games * 4);
+    memcpy(h + o_win, h_winner, (size_t)n_games * 4);
+    memcpy(h + o_moves, h_moves, (size_t)total * 4);
+    memcpy(h + o_keep, h_keep, (size_t)total);
+    memcpy(h + o_pi, h_pi, (size_t)kept * A * sizeof(float));
+    rc = rp_upload(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    const long long cap = r->dev.capacity, skip = kept > cap ? kept - cap : 0;
+    hipLaunchKernelGGL(k_replay_add, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
+                       (const int32_t *)(d + o_win), (const int32_t *)(d + o_moves), (const uint8_t *)(d + o_keep), (const float *)(d + o_pi),
+                       r->cursor, skip);
+    rc = rp_launched(r, s, "k_replay_add launch failed");
+    if (rc != RZ_OK) return rc;
+    r->cursor = (r->cursor + kept) % cap;
+    r->count = r->count + kept > cap ? cap : r->count + kept;
+    return RZ_OK;
+}
+
+int rz_replay_gather(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, int64_t n, float *d_states, float *d_pis,
+                     float *d_zs, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    rc = rp_outputs(r, n, d_states, d_pis, d_zs);
+    if (rc != RZ_OK) return rc;
+    if ((h_indices == nullptr) == (d_indices == nullptr)) return rp_fail(RZ_ERR_ARG, "exactly one of h_indices / d_indices");
+    if (n == 0) return RZ_OK;
+    const long long n_entries = 8 * r->count;
+    if (n_entries == 0) return rp_fail(RZ_ERR_ARG, "the replay buffer is empty");
+    hipStream_t s = (hipStream_t)stream;
+    const long long *idx = (const long long *)d_indices;
+    if (h_indices != nullptr) {
+        for (int64_t i = 0; i < n; ++i)
+            if (h_indices[i] < 0 || h_indices[i] >= n_entries) return rp_fail(RZ_ERR_ARG, "entry index outside 0 .. 8 * count - 1");
+        rc = rp_stage(r, (size_t)n * 8, s);
+        if (rc != RZ_OK) return rc;
+        memcpy(r->h_stage, h_indices, (size_t)n * 8);
+        rc = rp_upload(r, (size_t)n * 8, s);
+        if (rc != RZ_OK) return rc;
+        idx = (const long long *)r->d_stage;
+    }
+    hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
+    if (h_indices != nullptr) return rp_launched(r, s, "k_replay_gather launch failed");
+    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, "k_replay_gather launch failed");
+    return RZ_OK;
+}
+
+int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_states, float *d_pis, float *d_zs, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    rc = rp_outputs(r, n, d_states, d_pis, d_zs);
+    if (rc != RZ_OK) return rc;
+    const long long n_entries = 8 * r->count;
+    if (n_entries == 0) return rp_fail(RZ_ERR_ARG, "the replay buffer is empty");
+    if (n == 0) return RZ_OK;
+    hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
+                       (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
+    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, "k_replay_sample launch failed");
+    return RZ_OK;
+}
+
+int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (first < 0 || n < 0 || first + n > r->count) return rp_fail(RZ_ERR_ARG, "positions outside 0 .. count - 1");
+    hipStream_t s = (hipStream_t)stream;
+    const long long cap = r->dev.capacity, start = (rp_oldest(r) + first) % cap;
+    const long long n1 = n < cap - start ? n : cap - start;   // up to the ring's end, then from its start
+    const size_t A = (size_t)r->dev.A;
+    bool ok = true;
+    for (int part = 0; part < 2; ++part) {
+        const long long from = part == 0 ? start : 0, cnt = part == 0 ? n1 : n - n1, at = part == 0 ? 0 : n1;
+        if (cnt <= 0) continue;
+        if (h_stones) ok = ok && hipMemcpyAsync(h_stones + at * kRecWords, r->dev.stones + from * kRecWords, (size_t)cnt * kRecWords * 8, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_meta) ok = ok && hipMemcpyAsync(h_meta + at, r->dev.meta + from, (size_t)cnt * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_pi) ok = ok && hipMemcpyAsync(h_pi + at * A, r->dev.pi + from * A, (size_t)cnt * A * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rp_fail(RZ_ERR_HIP, "read-back failed (replay)");
+    return RZ_OK;
+}
+
+int rz_replay_poll_errors(rz_replay *r, int32_t *flags, void *stream) {
+    int rc = rp_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (flags == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(flags, r->dev.err, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemsetAsync(r->dev.err, 0, sizeof(int32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return rp_fail(RZ_ERR_HIP, "reading the replay flags failed");
+    return RZ_OK;
+}
+
+}  // extern "C"

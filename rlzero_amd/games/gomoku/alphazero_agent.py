@@ -28,6 +28,8 @@ class AlphaZeroAgent(object):
                                     weight_decay=weight_decay)
 
     def _tensor(self, batch):
+        if isinstance(batch, torch.Tensor):   # (already a tensor -- a batch gathered on the device: no numpy detour)
+            return batch.to(self.device, torch.float32)
         return torch.as_tensor(np.array(batch), dtype=torch.float32).to(self.device)
 
     def policy_value_fn(self, game_env):

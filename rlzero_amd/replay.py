@@ -1,0 +1,250 @@
+"""The learner's replay buffer in device memory (rz_replay_*, csrc/rz_replay.hip; an opt-in extension).
+
+The reference keeps its augmented samples in a host ``deque`` and forms a mini-batch with ``random.sample`` + ``np.array`` + a
+host-to-device copy (tools/train_alphazero.py:32,59-79,88-96).  ``DeviceReplay`` holds the POSITIONS of finished games -- two
+bitboards, one meta word and a pi row each -- in a ring on the GPU, filled from the games' move lists (``add``), and one kernel
+launch writes a mini-batch straight into torch tensors: the four observation planes, the symmetry-transformed pi and z
+(``gather`` for given entry indices, ``sample`` for indices drawn on the device).
+
+The contract: ``DeviceReplay(B, C)`` after any sequence of ``add`` calls holds exactly the entries of the trainer's host
+``ReplayBuffer(8 * C, B)`` after ``extend_samples(t.training_samples())`` for the same games -- entry 8 j + k is symmetry k (in
+``get_equi_data``'s order) of the j-th oldest position held, and ``gather([i])`` equals the float32 casts of the host entry ``i``
+bit for bit.
+
+The eight symmetries are TABLES, not arithmetic: ``symmetry_tables`` pushes ``arange(A)`` through the reference's own numpy
+expressions and the kernels look the source cell of every output cell up.  There are two tables because the reference permutes
+the planes and pi differently (the planes are rotated by +k quarter turns, pi goes through a flipud / rot90 / flipud sandwich:
+SURVEY.md D-9): for an odd number of quarter turns the planes turn one way and pi the other.
+
+``sample`` draws WITH replacement -- entry i of update ``step`` is ``replay_index(seed, step, i, len(buffer))``, a counter-based
+uniform -- where the reference's ``random.sample`` draws without: a documented deviation; ``gather`` takes whatever indices the
+caller drew.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _hip
+from ._hip import HipError
+from .selfplay import _splitmix64
+
+_MASK = (1 << 64) - 1
+_REPLAY_SALT = np.uint64(0x7265706C61790000)   # ("replay": the sampler's own stream, apart from the move / noise / cap draws)
+META_PARITY_BIT, META_Z_SHIFT = 9, 10          # the meta word: bits 0..8 last move + 1 (0: none), bit 9 ply parity, bits 10..11 z + 1
+
+
+def symmetry_tables(board_size):
+    """-> (src_state, src_pi), int16 [8][A]: for output cell ``o`` of symmetry ``k`` the source cell of the planes and of pi, i.e.
+    ``entry_state[c].flat == state[c].flat[src_state[k]]`` and ``entry_pi == pi[src_pi[k]]``.  Obtained by pushing the cell numbers
+    through the numpy expressions the trainer's ReplayBuffer forms an entry with (get_equi_data's, train_alphazero.py:59-79)."""
+    size = int(board_size)
+    cells = np.arange(size * size, dtype=np.int16)
+    states, grids = cells.reshape(1, 1, size, size), cells.reshape(1, size, size)
+    src_state, src_pi = [], []
+    for k in range(8):
+        quarter_turns, mirrored = k // 2 + 1, k % 2 == 1
+        turned = np.rot90(states, quarter_turns, axes=(2, 3))
+        pi_turned = np.rot90(grids[:, ::-1, :], quarter_turns, axes=(1, 2))
+        if mirrored:
+            src_state.append(np.ascontiguousarray(turned[:, :, :, ::-1]).reshape(-1))
+            src_pi.append(np.ascontiguousarray(pi_turned[:, :, ::-1][:, ::-1, :]).reshape(-1))
+        else:
+            src_state.append(np.ascontiguousarray(turned).reshape(-1))
+            src_pi.append(np.ascontiguousarray(pi_turned[:, ::-1, :]).reshape(-1))
+    return np.stack(src_state).astype(np.int16), np.stack(src_pi).astype(np.int16)
+
+
+def replay_indices(seed, step, n, n_entries):
+    """Entries 0 .. n-1 of update ``step``: int64 [n] in [0, n_entries) -- the device's draw (k_replay_sample), the same bits.
+    The high half of x * n_entries for the 64-bit x of a splitmix64 chain over (seed, step, i): integer only, every entry's
+    probability is floor or ceil of 2^64 / n_entries over 2^64, i.e. within 2^-64 of uniform."""
+    n_entries = int(n_entries)
+    if not 0 < n_entries < (1 << 31):
+        raise ValueError('n_entries %d not in 1 .. 2^31 - 1' % n_entries)
+    with np.errstate(over='ignore'):
+        x = _splitmix64(np.uint64(int(seed) & _MASK) ^ _REPLAY_SALT)
+        x = _splitmix64(x ^ np.uint64(int(step) & _MASK))
+        x = _splitmix64(x ^ np.arange(int(n), dtype=np.uint64))
+    # mulhi64(x, n_entries) in 64-bit pieces: n_entries < 2^31, so neither product overflows
+    m, lo32 = np.uint64(n_entries), np.uint64(0xFFFFFFFF)
+    hi = (x >> np.uint64(32)) * m + (((x & lo32) * m) >> np.uint64(32))
+    return (hi >> np.uint64(32)).astype(np.int64)
+
+
+def replay_index(seed, step, i, n_entries):
+    """Entry ``i`` of update ``step`` (replay_indices, one value, in Python integers)."""
+    def sm(x):
+        x = (x + 0x9E3779B97F4A7C15) & _MASK
+        z = x
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
+        return z ^ (z >> 31)
+    n_entries = int(n_entries)
+    if n_entries <= 0:
+        raise ValueError('n_entries %d must be positive' % n_entries)
+    x = sm((int(seed) & _MASK) ^ int(_REPLAY_SALT))
+    x = sm(x ^ (int(step) & _MASK))
+    x = sm(x ^ (int(i) & _MASK))
+    return (x * n_entries) >> 64
+
+
+def pack_positions(trajectories, board_size):
+    """The raw records ``DeviceReplay.add`` stores for these games, formed on the host: (stones uint64 [N][2][4], meta int32 [N],
+    pi float32 [N][A]) of the kept plies in order -- what ``DeviceReplay.read`` returns for them."""
+    A = int(board_size) ** 2
+    stones, meta, pis = [], [], []
+    for t in trajectories:
+        P = len(t.moves)
+        keep = np.ones(P, dtype=bool) if t.full is None else t.full[:P]
+        z = t.z()
+        for p in range(P):
+            if not keep[p]:
+                continue
+            rec = [[0] * _hip.BOARD_WORDS, [0] * _hip.BOARD_WORDS]
+            for q in range(p):
+                m = t.moves[q]
+                rec[(q ^ p) & 1][m >> 6] |= 1 << (m & 63)
+            stones.append(rec)
+            meta.append((t.moves[p - 1] + 1 if p else 0) | ((p & 1) << META_PARITY_BIT) | ((int(z[p]) + 1) << META_Z_SHIFT))
+            pis.append(np.asarray(t.pis[p], dtype=np.float32))
+    return (np.array(stones, dtype=np.uint64).reshape(-1, 2, _hip.BOARD_WORDS), np.array(meta, dtype=np.int32),
+            np.array(pis, dtype=np.float32).reshape(-1, A))
+
+
+def _ptr(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+class DeviceReplay(object):
+    """A ring of ``capacity_positions`` positions of Gomoku games on ``device``; ``len()`` is 8 x the positions held (entries, like
+    the host buffer).  No CPU fallback: HipError without a GPU."""
+
+    def __init__(self, board_size, capacity_positions, device='cuda:0', seed=0):
+        import torch
+        self.torch = torch
+        self.lib = _hip.load()
+        dev = torch.device(device)
+        if dev.type != 'cuda' or not torch.cuda.is_available():
+            raise HipError('the device replay buffer needs an MI355X (device=%r, cuda available=%s); there is no CPU fallback'
+                           % (device, torch.cuda.is_available()))
+        self.device = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+        self.board_size, self.capacity = int(board_size), int(capacity_positions)
+        self.n_actions = self.board_size ** 2
+        self.seed = int(seed)
+        self.step = 0   # the next update ``sample`` draws without a ``step``
+        handle = ctypes.c_void_p()
+        _hip.check(self.lib.rz_replay_create(self.board_size, self.capacity, self.device.index, ctypes.byref(handle)), 'rz_replay_create')
+        self.handle = handle
+        self.src_state, self.src_pi = symmetry_tables(self.board_size)
+        _hip.check(self.lib.rz_replay_set_tables(self.handle, _ptr(self.src_state), _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables')
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _state(self):
+        count, cursor, cap = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(self.lib.rz_replay_state(self.handle, ctypes.byref(count), ctypes.byref(cursor), ctypes.byref(cap)), 'rz_replay_state')
+        return count.value, cursor.value, cap.value
+
+    @property
+    def positions(self):
+        return self._state()[0]
+
+    def __len__(self):
+        return 8 * self._state()[0]
+
+    def add(self, trajectories):
+        """The positions of finished games (selfplay.Trajectory; ``pis`` float64 or float32), in order: every ply, or under a
+        playout cap the plies searched with the full budget (``full``, as ``training_samples()`` keeps them -- the other plies
+        still place their stones).  One staging copy and one launch for all of them.  -> positions added."""
+        trajectories = list(trajectories)
+        A = self.n_actions
+        offsets, moves, keeps, winners, rows = [0], [], [], [], []
+        for t in trajectories:
+            if getattr(t, 'game', 'gomoku') != 'gomoku':
+                raise ValueError('the device replay buffer holds Gomoku positions, not %r' % (t.game, ))
+            if t.board_size != self.board_size:
+                raise ValueError('a game of board size %r in a buffer of %d' % (t.board_size, self.board_size))
+            P = len(t.moves)
+            keep = np.ones(P, dtype=np.uint8) if t.full is None else np.asarray(t.full[:P], dtype=np.uint8)
+            if len(keep) != P:
+                raise ValueError('game %d: %d budget flags for %d plies' % (t.game_id, len(keep), P))
+            if P:
+                pis = np.asarray(t.pis)
+                if pis.shape != (P, A):
+                    raise ValueError('game %d: pi of shape %r, not %r' % (t.game_id, pis.shape, (P, A)))
+                rows.append(pis[keep != 0].astype(np.float32, copy=False))
+            offsets.append(offsets[-1] + P)
+            moves.extend(t.moves)
+            keeps.append(keep)
+            winners.append(t.winner)
+        if not trajectories:
+            return 0
+        h_off = np.asarray(offsets, dtype=np.int32)
+        h_moves = np.asarray(moves, dtype=np.int32)
+        h_keep = np.ascontiguousarray(np.concatenate(keeps)) if keeps else np.zeros(0, dtype=np.uint8)
+        h_win = np.asarray(winners, dtype=np.int32)
+        h_pi = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, A), dtype=np.float32)
+        _hip.check(self.lib.rz_replay_add(self.handle, len(trajectories), _ptr(h_off), _ptr(h_moves), _ptr(h_keep), _ptr(h_win), _ptr(h_pi),
+                                          self._stream()), 'rz_replay_add')
+        return int(h_keep.sum())
+
+    def _outputs(self, n):
+        t, B = self.torch, self.board_size
+        return (t.empty((n, 4, B, B), dtype=t.float32, device=self.device), t.empty((n, self.n_actions), dtype=t.float32, device=self.device),
+                t.empty((n, ), dtype=t.float32, device=self.device))
+
+    def gather(self, indices):
+        """Entries ``indices`` (a Python sequence, a numpy array or a device int64 tensor) -> (states float32 [n, 4, B, B], pis
+        float32 [n, A], zs float32 [n]) on the device, one launch.  An index outside 0 .. len - 1 raises (host indices before the
+        launch; device indices after it, from the kernel's flag -- that entry's rows are not written)."""
+        t = self.torch
+        if isinstance(indices, t.Tensor):
+            if indices.device != self.device or indices.dtype != t.int64:
+                raise ValueError('device indices: an int64 tensor on %s' % (self.device, ))
+            idx = indices.contiguous().view(-1)
+            states, pis, zs = self._outputs(idx.numel())
+            st = self._stream()
+            _hip.check(self.lib.rz_replay_gather(self.handle, None, idx.data_ptr(), idx.numel(), states.data_ptr(), pis.data_ptr(),
+                                                 zs.data_ptr(), st), 'rz_replay_gather')
+            flags = ctypes.c_int32()
+            _hip.check(self.lib.rz_replay_poll_errors(self.handle, ctypes.byref(flags), st), 'rz_replay_poll_errors')
+            if flags.value & _hip.REPLAY_BAD_INDEX:
+                raise HipError('rz_replay_gather: an entry index from the device is outside 0 .. %d' % (len(self) - 1))
+            return states, pis, zs
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        states, pis, zs = self._outputs(len(idx))
+        _hip.check(self.lib.rz_replay_gather(self.handle, _ptr(idx), None, len(idx), states.data_ptr(), pis.data_ptr(), zs.data_ptr(),
+                                             self._stream()), 'rz_replay_gather')
+        return states, pis, zs
+
+    def sample(self, n, step=None):
+        """``n`` entries drawn on the device, with replacement: entry i is ``replay_index(seed, step, i, len(self))``.  ``step``:
+        the update's number; None = an internal counter, advanced by the call."""
+        if step is None:
+            step, self.step = self.step, self.step + 1
+        states, pis, zs = self._outputs(int(n))
+        _hip.check(self.lib.rz_replay_sample(self.handle, self.seed & _MASK, int(step) & _MASK, int(n), states.data_ptr(), pis.data_ptr(),
+                                             zs.data_ptr(), self._stream()), 'rz_replay_sample')
+        return states, pis, zs
+
+    def read(self, first=0, n=None):
+        """The raw records of positions ``first`` .. ``first + n - 1`` (oldest = 0), a synchronous copy: (stones uint64 [n][2][4] --
+        [0] the mover's, [1] the opponent's --, meta int32 [n], pi float32 [n][A])."""
+        n = self.positions - first if n is None else int(n)
+        stones = np.zeros((n, 2, _hip.BOARD_WORDS), dtype=np.uint64)
+        meta = np.zeros(n, dtype=np.int32)
+        pi = np.zeros((n, self.n_actions), dtype=np.float32)
+        _hip.check(self.lib.rz_replay_read(self.handle, int(first), n, _ptr(stones), _ptr(meta), _ptr(pi), self._stream()), 'rz_replay_read')
+        return stones, meta, pi
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.rz_replay_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass

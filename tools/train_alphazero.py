@@ -150,7 +150,8 @@ class TrainPipeline:
 
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
-                 resign_fp_target=0.05, playout_cap=None, gate_against=None):
+                 resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
+                 device_replay=False):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -166,7 +167,17 @@ class TrainPipeline:
         opt-in extension): the replay buffer takes the plies searched with the full budget (Trajectory.training_samples).
         ``gate_against``: None or a checkpoint (batched mode only): at every ``check_freq`` the current network plays a match from
         paired openings against it (rlzero_amd.match) and the score is printed next to the pure-MCTS win ratio; nothing is decided
-        on it."""
+        on it.
+        ``batch_size`` / ``updates_per_round``: entries per mini-batch and ``policy_update`` calls per collection round (the
+        reference's 32 and 1, train_alphazero.py:33,130-131), for either buffer.  ``device_replay`` (batched mode on a GPU only, an
+        opt-in extension): rank 0's ``data_buffer`` is a ``rlzero_amd.replay.DeviceReplay`` -- the finished games go to device
+        memory from their move lists, a mini-batch is one launch (``sample``: drawn on the device WITH replacement, keyed (seed,
+        update)), and the KL / explained variances of ``policy_update`` are computed on the device."""
+        if device_replay and selfplay_games_in_flight <= 0:
+            raise ValueError('the device replay buffer is a batched-mode option: selfplay_games_in_flight must be > 0')
+        if int(batch_size) < 1 or int(updates_per_round) < 1:
+            raise ValueError('batch_size and updates_per_round must be >= 1')
+        self.device_replay, self.updates_per_round, self._updates = bool(device_replay), int(updates_per_round), 0
         if gate_against is not None and selfplay_games_in_flight <= 0:
             raise ValueError('the gate match is a batched-mode option: selfplay_games_in_flight must be > 0')
         self.gate_against, self._gate, self._gate_rounds = gate_against, None, 0
@@ -197,7 +208,7 @@ class TrainPipeline:
             buffer_size = 1000 if selfplay_games_in_flight <= 0 else \
                 max(1000, selfplay_games_in_flight * self.world * board_size * board_size * 8)
         self.buffer_size = int(buffer_size)
-        self.batch_size = 32
+        self.batch_size = int(batch_size)
         # (the reference's deque of augmented samples, the symmetries formed on access: ReplayBuffer)
         self.data_buffer = ReplayBuffer(self.buffer_size, self.board_size)
         self.play_batch_size = 1
@@ -207,6 +218,12 @@ class TrainPipeline:
         self.game_batch_num = game_batch_num
         self.best_win_ratio = 0.0
         self.device = self._pick_device()
+        if self.device_replay:
+            if self.device.type != 'cuda':
+                raise ValueError('the device replay buffer needs a GPU (this process runs on %s)' % (self.device, ))
+            if self.rank == 0:   # (rank 0 holds the buffer, as with the host one; sized like the batched mode's default: one round)
+                from rlzero_amd.replay import DeviceReplay
+                self.data_buffer = DeviceReplay(self.board_size, max(1, self.buffer_size // 8), device=str(self.device))
         self.pure_mcts_playout_num = 100
         self.selfplay_games_in_flight = selfplay_games_in_flight
         self.alphazero_agent = AlphaZeroAgent(self.board_size, device=self.device)
@@ -217,6 +234,8 @@ class TrainPipeline:
         self._next_game_id = 0
         self._trace_rounds = 0
         self.selfplay_seed = self._agree_on(random.getrandbits(31) if seed is None else int(seed))
+        if self.device_replay and self.rank == 0:
+            self.data_buffer.seed = self.selfplay_seed   # (the sampler's stream: keyed (seed, update, entry))
         if self.world > 1:   # every rank starts from rank 0's weights
             from rlzero.algorithms import broadcast_weights
             broadcast_weights(self.alphazero_agent.policy_value_net, src=0)
@@ -344,7 +363,10 @@ class TrainPipeline:
             f.write(json.dumps(rec) + '\n')
 
     def _tuple(self, t):
-        """start_self_play's tuple of a trajectory; under a playout cap with the full-budget plies only."""
+        """start_self_play's tuple of a trajectory; under a playout cap with the full-budget plies only.  With the device replay
+        buffer the trajectory itself: its positions are formed on the device from the move list (DeviceReplay.add)."""
+        if self.device_replay:
+            return t
         return t.as_reference_tuple() if self.playout_cap is None else (t.winner, t.training_samples())
 
     def _cap_round(self, trajs):
@@ -414,7 +436,14 @@ class TrainPipeline:
 
     def collect_selfplay_data(self, n_games=1):
         """collect self-play data for training."""
+        pending = []   # (device replay: the round's games, one DeviceReplay.add for all of them)
+
         def consume(game):
+            if self.device_replay:
+                plies = len(game.moves)
+                self.episode_len = plies if game.full is None else int(game.full[:plies].sum())
+                pending.append(game)
+                return
             winner, play_data = game
             play_data = list(play_data)
             self.episode_len = len(play_data)
@@ -429,10 +458,48 @@ class TrainPipeline:
                      for _ in range(n_games)]
         for game in games:
             consume(game)
+        if pending:
+            self.data_buffer.add(pending)
 
     # ------------------------------------------------------------------ learning
+    def _policy_update_device(self):
+        """policy_update with the device replay buffer: the mini-batch is one launch into device tensors (drawn on the device, keyed
+        (seed, update counter)), the KL and the explained variances stay on the device -- one .item() per value the host decides on
+        or prints (the KL of every epoch: the early stop)."""
+        state_batch, mcts_probs_batch, winner_batch = self.data_buffer.sample(self.batch_size, step=self._updates)
+        self._updates += 1
+        net = self.alphazero_agent.policy_value_net
+
+        def policy_value(states):   # (AlphaZeroAgent.policy_value without the host copy)
+            log_probs, value = net(states)
+            return torch.exp(log_probs.detach()), value.detach()
+        old_probs, old_v = policy_value(state_batch)
+        for _ in range(self.epochs):
+            loss, entropy = self.alphazero_agent.learn(state_batch, mcts_probs_batch, winner_batch)
+            new_probs, new_v = policy_value(state_batch)
+            kl = torch.mean(torch.sum(old_probs * (torch.log(old_probs + 1e-10) - torch.log(new_probs + 1e-10)), dim=1)).item()
+            if kl > self.kl_targ * 4:  # early stopping if D_KL diverges badly
+                break
+        if kl > self.kl_targ * 2 and self.lr_multiplier > 0.1:
+            self.lr_multiplier /= 1.5
+        elif kl < self.kl_targ / 2 and self.lr_multiplier < 10:
+            self.lr_multiplier *= 1.5
+        var_z = torch.var(winner_batch, unbiased=False)
+        explained_var_old = (1 - torch.var(winner_batch - old_v.flatten(), unbiased=False) / var_z).item()
+        explained_var_new = (1 - torch.var(winner_batch - new_v.flatten(), unbiased=False) / var_z).item()
+        print(('kl:{:.5f},'
+               'lr_multiplier:{:.3f},'
+               'loss:{},'
+               'entropy:{},'
+               'explained_var_old:{:.3f},'
+               'explained_var_new:{:.3f}').format(kl, self.lr_multiplier, loss, entropy, explained_var_old,
+                                                  explained_var_new))
+        return loss, entropy
+
     def policy_update(self):
         """update the policy-value net."""
+        if self.device_replay:
+            return self._policy_update_device()
         mini_batch = random.sample(self.data_buffer, self.batch_size)
         state_batch, mcts_probs_batch, winner_batch = (list(col) for col in zip(*mini_batch))
         old_probs, old_v = self.alphazero_agent.policy_value(state_batch)
@@ -531,7 +598,8 @@ class TrainPipeline:
                 if lead:
                     print('batch i:{}, episode_len:{}'.format(i + 1, self.episode_len))
                     if len(self.data_buffer) > self.batch_size:
-                        loss, entropy = self.policy_update()
+                        for _ in range(self.updates_per_round):
+                            loss, entropy = self.policy_update()
                 self._sync_weights()
                 if lead and (i + 1) % self.check_freq == 0:
                     print('current self-play batch: {}'.format(i + 1))
@@ -598,7 +666,18 @@ def parse_args(argv=None):
     ap.add_argument('--gate-against', default=None, metavar='CKPT',
                     help='batched mode only: at every --check-freq also report the match score of the current network against this '
                          'checkpoint (paired openings; nothing is decided on it)')
+    ap.add_argument('--batch-size', type=int, default=32, help='entries of a mini-batch')
+    ap.add_argument('--updates-per-round', type=int, default=1, help='policy updates after every collection round')
+    ap.add_argument('--device-replay', action='store_true',
+                    help='batched mode on a GPU only: the replay buffer lives in device memory and a mini-batch is one kernel launch '
+                         '(drawn on the device, with replacement)')
     args = ap.parse_args(argv)
+    if args.batch_size < 1 or args.updates_per_round < 1:
+        ap.error('--batch-size and --updates-per-round must be >= 1')
+    if args.device_replay and args.games_in_flight <= 0:
+        ap.error('--device-replay needs --games-in-flight > 0 (batched mode)')
+    if args.device_replay and not torch.cuda.is_available():
+        ap.error('--device-replay needs a GPU')
     if args.gate_against is not None and args.games_in_flight <= 0:
         ap.error('--gate-against needs --games-in-flight > 0 (batched mode)')
     if args.playout_cap is not None and args.games_in_flight <= 0:
@@ -626,7 +705,8 @@ def main():
     pipe = TrainPipeline(board_size=args.board, n_in_row=args.n_in_row, n_playout=args.playouts, game_batch_num=args.batches,
                          check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed,
                          resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
-                         resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against)
+                         resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against,
+                         batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
