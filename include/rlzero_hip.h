@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 31
+#define RZ_ABI_VERSION 32
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -347,6 +347,13 @@ typedef struct rz_kept_rows {
 } rz_kept_rows;
 int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream);
 int rz_deferred_flush_kept(rz_engine *e, const rz_deferred_logits *logits, void *stream);
+/* Policy on demand (ABI 32; rz_net_search_resident_values): the pending records carry no policy features, so EVERY flush goes by rows --
+ * rows (rz_deferred_keep, or rz_deferred_keep_all: every record with a block of every game, inside a drawn move or outside one; it
+ * leaves rz_deferred_keep_stats alone) -> rz_net_policy_rows -> rz_net_deferred_gemm_rows -> rz_deferred_flush_kept, or outside a drawn
+ * move rz_deferred_flush_rows: the same priors over the listed rows, and the slots emptied as rz_deferred_flush empties them.  A pending
+ * record also holds its leaf's side to move and last move (one word; every deferred route writes it). */
+int rz_deferred_keep_all(rz_engine *e, rz_kept_rows *out, void *stream);
+int rz_deferred_flush_rows(rz_engine *e, const rz_deferred_logits *logits, void *stream);
 /* h_out2 = {records listed, records with a block (what rz_deferred_flush would have written)} over the rz_deferred_keep calls since
  * the last reset; synchronises */
 int rz_deferred_keep_stats(rz_engine *e, uint64_t *h_out2, int32_t reset);
@@ -697,6 +704,17 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
  * flush) is not written anywhere and its game is flagged RZ_FLAG_INTERNAL by the tree code -- never an out-of-bounds write.
  * The same holds for rz_net_trunk_leaves_deferred (slot d_slot_of_board[b]). */
 int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream);
+/* POLICY ON DEMAND (ABI 32).  Under RZ_SCORE_UCT_REF a search never reads a prior, and a move keeps well under 1 % of a search's
+ * expansions: rz_net_search_resident_values is rz_net_search_resident whose leaves are evaluated for the two value planes only --
+ * k_delta_res without the policy head sums, their shares and their stores; nothing is written to the feature store.  Trees, values
+ * and records are rz_net_search_resident's, bit for bit.  It exists where k_delta_res runs (rz_net_delta_reserve for the engine's
+ * games, rz_net_delta_resident on, a board of 11 .. 16 rows and columns): RZ_ERR_ARG elsewhere, never another kernel.  The records of
+ * such a search must be flushed by rows: rz_net_policy_rows evaluates the listed records' leaves once more (the leaf from the record,
+ * against the game's bases where they are still the leaf's; otherwise without a base) and writes their four policy planes to the
+ * record's own place in the store -- the bits rz_net_search_resident writes there -- for rz_net_deferred_gemm_rows behind it.  Records
+ * of the two kinds of search must not share a flush: flush between them. */
+int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream);
+int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream);
 int rz_net_heads(rz_net *net, int32_t n_boards, float *d_logp, float *d_value, void *stream);
 /* only the FC GEMM of the heads on the internal features; returns the device pointers that
  * rz_tree_step_raw / rz_expand_backup_raw consume (valid until the next rz_net_reserve / load) */

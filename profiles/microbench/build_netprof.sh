@@ -6,9 +6,9 @@ set -e
 cd "$(dirname "$0")/../.."
 F="--offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -std=c++17 -fPIC -Wno-unused-function -Iinclude"
 H=$(python -c "import rlzero_amd._build as b; print(b.source_hash())")
-mkdir -p /tmp/netprof
-for f in rz_engine rz_net rz_muzero; do
-  hipcc $F -DRZ_NET_PROFILE $NETPROF_EXTRA -DRZ_SOURCE_HASH="\"$H\"" -c rlzero_amd/csrc/$f.hip -o /tmp/netprof/$f.o &
+O=$(mktemp -d)
+for f in rz_engine rz_net rz_muzero rz_replay; do
+  hipcc $F -DRZ_NET_PROFILE $NETPROF_EXTRA -DRZ_SOURCE_HASH="\"$H\"" -c rlzero_amd/csrc/$f.hip -o $O/$f.o &
 done
 wait
-hipcc --offload-arch=gfx950 -shared -fPIC /tmp/netprof/*.o -o profiles/microbench/librlzero_netprof.so
+hipcc --offload-arch=gfx950 -shared -fPIC $O/*.o -o profiles/microbench/librlzero_netprof.so

@@ -1,7 +1,10 @@
 """Cycles per phase of ONE simulation of the resident search with the receptive-field trunk (k_delta_res; wave 0 of the workgroup of
 game 0), from a library built with -DRZ_NET_PROFILE (profiles/microbench/build_netprof.sh):
 
-    python profiles/microbench/delta_resident_phases.py [games ...]     (default: 1, 256, 512 games; a whole 800-simulation search each)
+    python profiles/microbench/delta_resident_phases.py [--values] [games ...]     (default: 1, 256, 512 games; a whole 800-simulation search each)
+
+--values: the search of policy on demand (k_delta_res<false>: no policy features; the engine here has no move step, so the decision
+is forced).
 """
 import ctypes, os, sys
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '.'))
@@ -19,7 +22,11 @@ NAMES = [(0, 'leaf + changed cells'), (1, 'distances, requests, ranks'), (3, 'ma
          # without any of them the whole selection) and wave 1's pre-scan with the barrier wait behind it
          (2, 'sel: root record'), (8, 'sel: root scan / answer'), (13, 'sel: level-0 cell'), (14, 'sel: deeper levels'), (15, 'sel: terminal test + leaf stores'),
          (18, 'selection (rest: hand-over)'), (19, 'wave 1: pre-scan'), (20, 'wave 1: wait behind it')]
-sizes = [int(a) for a in sys.argv[1:]] or [1, 256, 512]
+VALUES = '--values' in sys.argv[1:]
+if VALUES:
+    import rlzero_amd.route as _R
+    _R.policy_on_demand = lambda *a, **k: True
+sizes = [int(a) for a in sys.argv[1:] if a != '--values'] or [1, 256, 512]
 for games in sizes:
     torch.manual_seed(0)
     net = PolicyValueNet(15).to('cuda:0')
@@ -39,6 +46,7 @@ for games in sizes:
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev.hip.delta_stats(reset=True)
     a.record(); eng.sim_chunk(ev, sims); b.record(); torch.cuda.synchronize()
+    assert (eng.search_launches[True] > 0) == VALUES and (eng.search_launches[False] > 0) != VALUES
     st = ev.hip.delta_stats()
     out = (ctypes.c_longlong * 24)()
     assert lib.rz_net_debug_profile(out) == 0

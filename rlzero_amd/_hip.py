@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -134,6 +134,8 @@ _SIGNATURES = {
     'rz_deferred_flush': (c_int, [P, POINTER(RzDeferredLogits), c_int32, P]),
     'rz_deferred_keep': (c_int, [P, POINTER(RzKeptRows), P]),
     'rz_deferred_flush_kept': (c_int, [P, POINTER(RzDeferredLogits), P]),
+    'rz_deferred_keep_all': (c_int, [P, POINTER(RzKeptRows), P]),
+    'rz_deferred_flush_rows': (c_int, [P, POINTER(RzDeferredLogits), P]),
     'rz_deferred_keep_stats': (c_int, [P, POINTER(c_uint64), c_int32]),
     'rz_root_visits': (c_int, [P, P, P]),
     'rz_root_wsum': (c_int, [P, P, P]),
@@ -178,6 +180,8 @@ _SIGNATURES = {
     'rz_net_trunk_leaves_deferred': (c_int, [P, P, P, P, c_int32, P, POINTER(RzValueHead), P]),
     'rz_net_deferred_gemm': (c_int, [P, c_int32, c_int32, POINTER(RzDeferredLogits), P]),
     'rz_net_deferred_gemm_rows': (c_int, [P, POINTER(RzKeptRows), POINTER(RzDeferredLogits), P]),
+    'rz_net_search_resident_values': (c_int, [P, P, c_int32, c_int32, P]),
+    'rz_net_policy_rows': (c_int, [P, P, POINTER(RzKeptRows), P]),
     'rz_net_search_resident': (c_int, [P, P, c_int32, c_int32, P]),
     'rz_net_delta_reserve': (c_int, [P, c_int32]),
     'rz_net_delta_invalidate': (c_int, [P, P]),

@@ -238,18 +238,19 @@ __device__ __forceinline__ void conv3_g(lds_u32 map, const uint16_t *list3, cons
 
 // the lane's head values [tile][output] of T tiles (T = 4: 24 values, T = 8: 48) -> those of the T / 4 tiles its lane group is left with,
 // summed over the four lane groups in f4::reduce_scatter_96's order: (group 0 + group 1) + (group 2 + group 3).  Group g keeps tiles
-// (T / 2) (g & 1) + (T / 4) (g >> 1) + ...
-template <int T>
-__device__ __forceinline__ void reduce_scatter(const float (&vals)[6 * T], float (&out)[6 * T / 4]) {
-    float r1[3 * T];
+// (T / 2) (g & 1) + (T / 4) (g >> 1) + ...  O = outputs per tile (6: all; 4 / 2: the policy / the value planes alone, each value through the same swaps
+// and sums)
+template <int T, int O = 6>
+__device__ __forceinline__ void reduce_scatter(const float (&vals)[O * T], float (&out)[O * T / 4]) {
+    float r1[O * T / 2];
 #pragma unroll
-    for (int i = 0; i < 3 * T; ++i) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(vals[i]), __float_as_uint(vals[3 * T + i]), false, false);
+    for (int i = 0; i < O * T / 2; ++i) {
+        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(vals[i]), __float_as_uint(vals[O * T / 2 + i]), false, false);
         r1[i] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     }
 #pragma unroll
-    for (int i = 0; i < 3 * T / 2; ++i) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r1[i]), __float_as_uint(r1[3 * T / 2 + i]), false, false);
+    for (int i = 0; i < O * T / 4; ++i) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r1[i]), __float_as_uint(r1[O * T / 4 + i]), false, false);
         out[i] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     }
 }
@@ -280,13 +281,15 @@ __device__ __forceinline__ void conv2_tiles(lds_u32 map1, lds_u32 map2, const ui
 }
 
 // conv3 of NT <= 6 tiles + the two 1 x 1 head convolutions -> the wave's shares of the six head sums of these tiles (shares: the first
-// tile's).  headw (LDS): [128][6] weights, [128] biases.
-template <int NT>
+// tile's).  headw (LDS): [128][6] weights, [128] biases.  Outputs OLO .. OHI - 1 alone (even bounds: 0 .. 3 the policy planes, 4 / 5 the
+// value planes): the others' products, swaps and shares do not exist, the ones kept go through the operations they go through among all six.
+template <int NT, int OLO = 0, int OHI = 6>
 __device__ __forceinline__ void conv3_tiles(lds_u32 map2, const uint16_t *list3, const void *wts, int lane, int wave, bool sync,
                                             const char *headw, float k3, float *shares) {
-    constexpr int T = NT <= 4 ? 4 : 8;
+    constexpr int T = NT <= 4 ? 4 : 8, O = OHI - OLO;
+    static_assert(OLO % 2 == 0 && OHI % 2 == 0 && 0 <= OLO && OLO < OHI && OHI <= 6, "pairs of outputs");
     const int n = lane & 15, g = lane >> 4;
-    float vals[6 * T];
+    float vals[O * T];
     {
         f32x4 acc[2][NT];
         conv3_g<NT>(map2, list3, wts, lane, sync, acc);
@@ -309,22 +312,22 @@ __device__ __forceinline__ void conv3_tiles(lds_u32 map2, const uint16_t *list3,
                     for (int j = 0; j < 4; ++j) {
                         const float hv = fmaxf(fmaf(acc[m][t < NT ? t : 0][j], k3, b3r[m][j]), 0.0f);
 #pragma unroll
-                        for (int o2 = 0; o2 < 3; ++o2) {
+                        for (int o2 = OLO / 2; o2 < OHI / 2; ++o2) {
                             const int e = 6 * j + 2 * o2;
                             v2[o2] = __builtin_elementwise_fma(f32x2{hwr[m][e >> 2][e & 3], hwr[m][e >> 2][(e & 3) + 1]}, f32x2{hv, hv}, v2[o2]);
                         }
                     }
             }
 #pragma unroll
-            for (int o = 0; o < 6; ++o) vals[t * 6 + o] = v2[o >> 1][o & 1];
+            for (int o = OLO; o < OHI; ++o) vals[t * O + o - OLO] = v2[o >> 1][o & 1];
         }
     }
-    float mine[6 * T / 4];
-    reduce_scatter<T>(vals, mine);
+    float mine[O * T / 4];
+    reduce_scatter<T, O>(vals, mine);
     const int t0 = (T / 2) * (g & 1) + (T / 4) * (g >> 1);
 #pragma unroll
-    for (int i = 0; i < 6 * T / 4; ++i)
-        if (t0 + i / 6 < NT) shares[((t0 + i / 6) * 4 + wave) * 96 + (i % 6) * 16 + n] = mine[i];
+    for (int i = 0; i < O * T / 4; ++i)
+        if (t0 + i / O < NT) shares[((t0 + i / O) * 4 + wave) * 96 + (OLO + i % O) * 16 + n] = mine[i];
 }
 
 // ---- what the pass loop of a leaf needs (one struct so that the two kernels below share the loop)
@@ -387,7 +390,9 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 
 // The passes of one leaf: -1 = against the base (use_delta), 0 .. 3 = the board's quadrants without one.  -> tiles computed: conv3 | conv2 << 16.
 // SETS (k_delta_res): pass -1 takes its cell sets, ranks and totals from leaf.sets (leaf_windows) instead of the distances and ballots.
-template <bool SETS>
+// OLO, OHI: the head planes this leaf is evaluated for (conv3_tiles; the base's values of the others are not requested either) -- all six,
+// the value planes alone (the search of policy on demand: 4, 6) or the policy planes alone (its flush, k_trunk_policy_rows: 0, 4).
+template <bool SETS, int OLO = 0, int OHI = 6>
 __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &da, char *lds, int tid0, int wave, const Leaf &leaf, const Layers &ly,
                                             f32x4 headv, bool &use_delta, Prof &prof) {
     char *in0 = lds, *c1 = lds + kOffC1, *c2 = lds + kOffC2, *zrec = lds + kOffZero, *headw = lds + kOffHead;
@@ -453,7 +458,7 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         {
             const int ov = pass < 0 && is_cell && !f[2] ? (int)kBaseV + tid * 4 : kOutside;
 #pragma unroll
-            for (int o = 0; o < 6; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
+            for (int o = OLO; o < OHI; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
         }
         // (conv1's weights and the biases: requested per pass, so that nothing of them is live across conv3)
         sp::f16x8 a1[3][2];
@@ -622,15 +627,15 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
             const int first = nt3 <= 6 ? nt3 : 4;
             switch (first) {
                 case 0: __syncthreads(); break;   // (the barrier behind conv2, which the other cases meet inside conv3_g)
-                case 1: conv3_tiles<1>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
-                case 2: conv3_tiles<2>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
-                case 3: conv3_tiles<3>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
-                case 4: conv3_tiles<4>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
-                case 5: conv3_tiles<5>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
-                default: conv3_tiles<6>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                case 1: conv3_tiles<1, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                case 2: conv3_tiles<2, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                case 3: conv3_tiles<3, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                case 4: conv3_tiles<4, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                case 5: conv3_tiles<5, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
+                default: conv3_tiles<6, OLO, OHI>(m2, list3, t3p, lane, wave, true, headw, k3, shares); break;
             }
-            if (nt3 == 7) conv3_tiles<3>(m2, list3 + 64, t3p, lane, wave, false, headw, k3, shares + 4 * 4 * 96);
-            else if (nt3 >= 8) conv3_tiles<4>(m2, list3 + 64, t3p, lane, wave, false, headw, k3, shares + 4 * 4 * 96);
+            if (nt3 == 7) conv3_tiles<3, OLO, OHI>(m2, list3 + 64, t3p, lane, wave, false, headw, k3, shares + 4 * 4 * 96);
+            else if (nt3 >= 8) conv3_tiles<4, OLO, OHI>(m2, list3 + 64, t3p, lane, wave, false, headw, k3, shares + 4 * 4 * 96);
         }
         NET_TICK(9);   // the barrier behind conv2, conv3 + heads
         __syncthreads();
@@ -646,7 +651,7 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
             const float *share = shares + (rank[2] >> 4) * 4 * 96 + (rank[2] & 15);
             float *basev = mode == 1 ? reinterpret_cast<float *>(const_cast<char *>(base) + kBaseV) : nullptr;
 #pragma unroll
-            for (int o = 0; o < 6; ++o) {
+            for (int o = OLO; o < OHI; ++o) {
                 float v;
                 if (f[2]) {
                     float s = share[o * 16];
@@ -968,7 +973,11 @@ __device__ __forceinline__ void path_windows(const ResHook &hook, bool base_ok, 
 // under the other game's matrix work, and a batch of 2 x CUs games (the 512 per GPU of BASELINE.json configs[3]) is ONE launch per
 // search on one stream: no lanes, no hardware-queue layout, no kernel boundary inside a search.  The bases of the roots are built
 // by the launch before this one (rz_net_search_resident); the header is compared with the root once per search.
+// POL = false (policy on demand, rz_net_search_resident_values): a simulation needs the two value planes only, and under the reference's
+// selection rule nothing a search reads depends on a prior -- the four policy planes of a leaf are neither computed nor stored here;
+// k_trunk_policy_rows forms them at the flush, for the records the flush lists.
 constexpr int kResVrow = 512;
+template <bool POL>
 __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__restrict__ store16, DeferredOut later, DeltaArgs da, ResArgs<true> res) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     __shared__ float res_vrow[kResVrow];
@@ -1079,13 +1088,13 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         leaf.base = da.recs + ((size_t)game * 2 + parity) * kBaseBytes;
         leaf.cell_planes = planes_of(ls, tid_s, tm, has_last, lc, nst);
         // the game's slot advances by one per simulation (expand_backup_body<DEF>); the value inputs stay in LDS
-        leaf.dst16 = slot0 + sim < later.n_slots ? store16 + (size_t)(slot0 + sim) * later.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16 : nullptr;
+        leaf.dst16 = POL && slot0 + sim < later.n_slots ? store16 + (size_t)(slot0 + sim) * later.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16 : nullptr;
         leaf.vdst = res_vrow;
         leaf.dst32 = nullptr;
         leaf.deferred = true;
         leaf.store_head = sim == 0;
         NET_TICK(0);
-        const int n_tiles = delta_passes<true>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
+        const int n_tiles = delta_passes<true, POL ? 0 : 4, 6>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
         tiles_total += n_tiles & 0xffff;
         tiles2_total += n_tiles >> 16;
         deltas += use_delta ? 1 : 0;
@@ -1159,6 +1168,89 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         net_prof[20] = pre_wait;
     }
 #endif
+}
+
+// POLICY ON DEMAND, the flush's side: the four policy planes of the LISTED records of a search made by k_delta_res<false>, written to the
+// record's own place in the feature store (slot rows[i] / n_games, the game's tile and column: where k_delta_res<true> writes them
+// during the search), so that k_heads_rows and k_deferred_priors_rows run behind it unchanged.  A record holds the leaf (stones, side to
+// move, last move: rzt::pend_lw); the leaf is evaluated as k_trunk_delta evaluates one -- changed_cells against the header of the game's
+// bases, delta_passes<false> -- for outputs 0 .. 3: the same code on the same leaf against the same base, hence the same bits.  A stale
+// or missing base, or more than kMaxD changed cells: the four passes without a base.  Fixed grid (two workgroups per CU), the count is
+// the device's.  It counts nothing in da.stats: those are the leaves of searches.
+struct PolicyRows {
+    const int32_t *rows, *count;   // the records (slot * n_games + game), their number
+    const uint64_t *stones;        // [record][2][RZ_BOARD_WORDS]
+    const int32_t *lw;             // [record] rzt::pend_lw_pack(side to move, last move)
+    int n_games, n_slots;
+    long long slot_halfs;          // halves per slot of the store
+};
+__global__ __launch_bounds__(256, 2) void k_trunk_policy_rows(NetDev nd, _Float16 *__restrict__ store16, DeltaArgs da, PolicyRows pr) {
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
+    const int tid0 = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const int BW = nd.BW;
+    Prof prof;
+#ifdef RZ_NET_PROFILE
+    for (int i = 0; i < 24; ++i) prof.acc[i] = 0;
+    prof.t = __builtin_readcyclecounter();
+#endif
+    Layers ly;
+    ly.t2p = reinterpret_cast<const char *>(nd.t2) + (size_t)wave * rt::Geo<32>::steps * 2 * 1024;
+    ly.t3p = reinterpret_cast<const char *>(nd.t3) + (size_t)(2 * wave) * rt::Geo<64>::steps * 2 * 1024;
+    f32x4 headv = tid0 < 192 ? reinterpret_cast<const f32x4 *>(nd.whp)[tid0] : reinterpret_cast<const f32x4 *>(nd.b3)[(tid0 - 192) & 31];
+    {
+        const float *bh = nd.bh + (tid0 == 225 ? 4 : 0);
+        const f32x4 hbv = {bh[0], bh[1], tid0 == 225 ? 0.0f : bh[2], tid0 == 225 ? 0.0f : bh[3]};
+        headv = (tid0 == 224 || tid0 == 225) ? hbv : headv;
+    }
+    ly.k1 = nd.s_inv[2], ly.k2 = nd.s_inv[0], ly.k3 = nd.s_inv[1];
+    ly.act1 = nd.s_inv[5], ly.act2 = nd.s_inv[6], ly.act3 = nd.s_inv[7];
+    const int n_rows = pr.count[0];
+    {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        f32x4 *z = reinterpret_cast<f32x4 *>(lds);
+        for (int i = tid0; i < sp::kInPieceBytes / 16; i += 256) z[i] = zero;
+        if (tid0 < P2 / 16) reinterpret_cast<f32x4 *>(lds + kOffZero)[tid0] = zero;
+        init_maps(lds, tid0);
+    }
+    __syncthreads();
+    bool first = true;
+    for (int i = blockIdx.x; i < n_rows; i += gridDim.x) {
+        // (the thread's number is opaque per row, as per pass and per simulation: hipcc otherwise hoists the lane-dependent addresses)
+        int tid_r = tid0;
+        asm volatile("" : "+v"(tid_r));
+        // ---- the record (wave-uniform), the header of its game's bases: one block of unconditional requests
+        const int rec = pr.rows[i];
+        const int game = rec % pr.n_games, slot = rec / pr.n_games;
+        const uint64_t *sb = pr.stones + (size_t)rec * 8;
+        const BaseHdr *hd = da.hdr + game;
+        uint64_t ls[8], rs[8];
+        int nst = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            ls[q] = sb[q];
+            rs[q] = hd->stones[q];
+            nst += __popcll(ls[q]);
+        }
+        const int lw = pr.lw[rec];
+        const int h_tm = hd->to_move, h_valid = hd->valid;
+        const int tm = rzt::pend_lw_to_move(lw), lc = rzt::pend_lw_last(lw);
+        const bool has_last = nst > 0;
+        if ((unsigned)slot >= (unsigned)pr.n_slots) continue;   // (uniform; a record beyond the store has no features: never listed)
+        Leaf leaf;
+        int parity = 0, nD = 0;
+        bool use_delta = changed_cells(ls, rs, nst, tm, lc, has_last, h_valid != 0, h_tm, da.bw_rcp, BW, leaf.dys, leaf.dxs, parity, nD);
+        leaf.base = da.recs + ((size_t)game * 2 + parity) * kBaseBytes;
+        leaf.cell_planes = planes_of(ls, tid_r, tm, has_last, lc, nst);
+        leaf.dst16 = store16 + (size_t)slot * pr.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16;
+        leaf.vdst = nullptr;
+        leaf.dst32 = nullptr;
+        leaf.sets = nullptr;
+        leaf.deferred = false;
+        leaf.store_head = first;
+        first = false;
+        (void)delta_passes<false, 0, 4>(nd, da, lds, tid_r, wave, leaf, ly, headv, use_delta, prof);
+        __syncthreads();   // the next row rewrites planes, maps, lists and records
+    }
 }
 
 }  // namespace dl

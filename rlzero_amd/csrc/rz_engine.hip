@@ -204,11 +204,12 @@ struct Keep {
     int words;
 };
 
+// (keep_of == NULL: every record with a block of every game -- the full flush of policy on demand, rz_deferred_keep_all)
 __global__ __launch_bounds__(256) void k_keep_mark(Dev E, const int32_t *__restrict__ keep_of, Keep Kp) {
     __shared__ int sh[4][2];
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = E.pend[g] < E.pend_cap ? E.pend[g] : E.pend_cap;
-    const int keep = keep_of[g];
+    const int keep = keep_of != nullptr ? keep_of[g] : -2;
     uint64_t root[2][kWords], occ[kWords];
     load_board(E.root_stones, g, root);
 #pragma unroll
@@ -271,8 +272,10 @@ __global__ __launch_bounds__(kWave) void k_keep_rows(Dev E, Keep Kp) {
     }
     if (last && lane == 0) {
         Kp.count[0] = at;
-        Kp.stats[0] += (unsigned long long)at;
-        Kp.stats[1] += (unsigned long long)pending;
+        if (Kp.stats != nullptr) {   // (NULL: a full flush by rows -- the counters are the kept flushes')
+            Kp.stats[0] += (unsigned long long)at;
+            Kp.stats[1] += (unsigned long long)pending;
+        }
     }
 }
 
@@ -2160,6 +2163,7 @@ int rz_deferred_reserve(rz_engine *e, int32_t slots) {
     // (the records of a smaller reservation stay allocated until rz_destroy: reservations grow once or twice in a process)
     if ((rc = dev_alloc(e, &e->dev.pend_pb, (long long)slots * G)) != RZ_OK) return rc;
     if ((rc = dev_alloc(e, &e->dev.pend_ctr, (long long)slots * G)) != RZ_OK) return rc;
+    if ((rc = dev_alloc(e, &e->dev.pend_lw, (long long)slots * G)) != RZ_OK) return rc;
     if ((rc = dev_alloc(e, &e->dev.pend_stones, (long long)slots * G * 2 * kWords)) != RZ_OK) return rc;
     if (e->dev.pend == nullptr) {
         if ((rc = dev_alloc(e, &e->dev.pend, G)) != RZ_OK) return rc;
@@ -2272,6 +2276,35 @@ int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream) {
     out->n_games = e->cfg.n_games;
     out->reserved = 0;
     return launched("k_keep_rows");
+}
+
+int rz_deferred_keep_all(rz_engine *e, rz_kept_rows *out, void *stream) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if (!out) return fail(RZ_ERR_ARG, "NULL output pointer");
+    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    Keep all = e->keep;
+    all.stats = nullptr;
+    k_keep_mark<<<per_game(e), dim3(256), 0, as_stream(stream)>>>(e->dev, nullptr, all);
+    k_keep_rows<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, all);
+    out->rows = e->keep.rows;
+    out->count = e->keep.count;
+    out->capacity = (int64_t)e->dev.pend_cap * e->cfg.n_games;
+    out->n_games = e->cfg.n_games;
+    out->reserved = 0;
+    return launched("k_keep_rows");
+}
+
+int rz_deferred_flush_rows(rz_engine *e, const rz_deferred_logits *logits, void *stream) {
+    int rc = check_engine(e);
+    if (rc != RZ_OK) return rc;
+    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    if (!logits || !logits->raw) return fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
+    if (logits->ld < e->dev.A) return fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
+    k_deferred_priors_rows<<<dim3(2048), dim3(kWave), 0, as_stream(stream)>>>(e->dev, logits->raw, logits->ld, e->keep.rows, e->keep.count);
+    // (between rz_play_draw and rz_play_apply the counters restart in k_play_apply, as in rz_deferred_flush)
+    if (!(e->play_on && e->play_drawn)) k_deferred_reset<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev);
+    return launched("k_deferred_priors_rows");
 }
 
 int rz_deferred_flush_kept(rz_engine *e, const rz_deferred_logits *logits, void *stream) {

@@ -3558,7 +3558,8 @@ int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const in
     return RZ_OK;
 }
 
-int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
+// policy == false: rz_net_search_resident_values (policy on demand: k_delta_res<false> or a refusal)
+static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream, bool policy) {
     rzt::Dev dev;
     int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
     if (rc != RZ_OK) return rc;
@@ -3613,12 +3614,16 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     const dim3 grid((unsigned)dev.n_games);
     const hipStream_t st = (hipStream_t)stream;
     net->feat16_valid = net->feat32_valid = false;
+    if (!policy && !delta_res)
+        return net_fail(RZ_ERR_ARG, "rz_net_search_resident_values: the search without policy features is k_delta_res's (the default trunk on a board of "
+                                    "11 .. 16 rows and columns, rz_net_delta_reserve for the engine's games, rz_net_delta_resident on)");
     if (delta_res) {
         if (select_first) {   // a search begins: the bases of its roots (a continued search finds them, or takes the route without)
             if ((rc = rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream)) != RZ_OK) return rc;
         }
         dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, net->d_delta_stats, 0, (65536 + net->dev.BW - 1) / net->dev.BW, net->d_win};
-        dl::k_delta_res<<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
+        if (policy) dl::k_delta_res<true><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
+        else dl::k_delta_res<false><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (k_delta_res) failed");
         return RZ_OK;
     }
@@ -3630,6 +3635,38 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         launch_trunk_split<true>(tc.ms, compact_res, grid, st, net->dev, nullptr, leaves, nullptr, net->d_store16, dev.n_games, net->d_flags,
                                  nullptr, nullptr, later, res);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search failed");
+    return RZ_OK;
+}
+
+int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
+    return search_resident(net, engine, n_sims, select_first, stream, true);
+}
+
+int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
+    return search_resident(net, engine, n_sims, select_first, stream, false);
+}
+
+int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream) {
+    if (!kept) return net_fail(RZ_ERR_ARG, "NULL argument");
+    rzt::Dev dev;
+    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    if (rc != RZ_OK) return rc;
+    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
+    if (!kept->rows || !kept->count) return net_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
+    if (!delta_covers(net) || net->base_games < dev.n_games || !split_trunk_ok(net))
+        return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the receptive-field trunk (the default trunk on a board of 11 .. 16 rows and columns) and "
+                                    "rz_net_delta_reserve for the engine's games");
+    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || dev.A != net->dev.A) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if (dev.pend_cap <= 0 || dev.pend_stones == nullptr || dev.pend_lw == nullptr) return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: rz_deferred_reserve first");
+    // a listed row addresses slot rows[i] / n_games of the store (the kernel skips a slot beyond it) and the game's tile
+    if (kept->n_games != dev.n_games || dev.n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)dev.pend_cap * dev.n_games)
+        return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the rows are not this engine's, or more boards than rz_net_deferred_reserve()d");
+    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, nullptr, 0, (65536 + net->dev.BW - 1) / net->dev.BW, nullptr};
+    const dl::PolicyRows pr{kept->rows, kept->count, dev.pend_stones, dev.pend_lw, dev.n_games, net->store_slots,
+                            (long long)net->store_tiles * net->dev.groups_act * 1024};
+    const dim3 grid((unsigned)(2 * (net->n_cus > 0 ? net->n_cus : 1)));   // fixed: two workgroups per CU, striding over the device's count
+    dl::k_trunk_policy_rows<<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, net->d_store16, da, pr);
+    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_policy_rows failed");
     return RZ_OK;
 }
 

@@ -48,6 +48,8 @@ struct Dev {
     int pend_cap;
     int32_t *pend, *pend_pb, *pend_ctr;
     uint64_t *pend_stones;
+    int32_t *pend_lw;   // ... and its side to move and last move (pend_lw_pack): from three stones below the root on the stones do not tell the
+                        // last move, and a flush that evaluates the leaf again (policy on demand, rz_net_policy_rows) needs its planes
     unsigned long long *trace;   // rz_trace.h (NULL: none)
     uint64_t valid[kWords];
     // x / BW and x / n_row for x < 4096 as (x * rcp) >> 16 (rcp = ceil(65536 / d): exact while x * (rcp * d - 65536) < 65536): the
@@ -61,6 +63,11 @@ struct Dev {
     const uint64_t *line_tab;
     int line_masks;   // four-word boards: != 0 when the first n - 1 cells of every window fit the 64 bits of its mask (else cell by cell)
 };
+
+// a pending record's word: the leaf's last move + 1 (0: none) in the low half, its side to move above
+__host__ __device__ __forceinline__ int pend_lw_pack(int to_move, int last) { return ((last + 1) & 0xffff) | (to_move << 16); }
+__host__ __device__ __forceinline__ int pend_lw_to_move(int lw) { return (lw >> 16) & 1; }
+__host__ __device__ __forceinline__ int pend_lw_last(int lw) { return (lw & 0xffff) - 1; }
 
 // the packed node record
 constexpr int kFirstCap = 4;  // child records reserved at a node's first visited child
@@ -907,6 +914,7 @@ __device__ __forceinline__ void expand_backup_body(const Dev &E, const float *lo
     const int nblk = E.nblk[g];
     const int top_now = E.top[g];
     const int noise_ctr = E.noise_ctr[g];
+    const int leaf_tm = DEF ? E.leaf_to_move[gk] : 0, leaf_lc = DEF ? E.leaf_last[gk] : 0;   // (the pending record's word)
     const int32_t *path = E.path + (long long)gk * E.path_stride;
     const int path_lane = path[lane < E.path_stride ? lane : 0];  // the node of path level `lane` (if that level exists)
     uint64_t st[2][kWords];
@@ -1017,6 +1025,7 @@ __device__ __forceinline__ void expand_backup_body(const Dev &E, const float *lo
                 if (lane == 0) {
                     E.pend_pb[rec] = ptop;
                     E.pend_ctr[rec] = noise_ctr;
+                    E.pend_lw[rec] = pend_lw_pack(leaf_tm, leaf_lc);
                     if (E.add_noise) E.noise_ctr[g] = noise_ctr + 1;
                 }
                 store_board<W>(E.pend_stones, (int)rec, st, lane);

@@ -264,6 +264,12 @@ class HipNet(object):
     def search_resident(self, eng, n_sims, select_first=False):
         """``n_sims`` simulations of every active game of ``eng`` in one launch; the first leaves come from rz_select_step before
         the call, or (``select_first``) from the launch itself."""
+        # policy on demand: MCTSEngine._search_mode decides it for the launch that follows it, and that launch alone (a caller that drives
+        # the library itself gets the search that writes the store); the library refuses what it cannot do
+        if eng.__dict__.pop('_search_values', False):
+            check(self.lib.rz_net_search_resident_values(self.handle, eng.handle, int(n_sims), 1 if select_first else 0, self._stream()),
+                  'rz_net_search_resident_values')
+            return
         check(self.lib.rz_net_search_resident(self.handle, eng.handle, int(n_sims), 1 if select_first else 0, self._stream()), 'rz_net_search_resident')
 
     def deferred_gemm(self, n_boards, n_slots):
@@ -272,6 +278,10 @@ class HipNet(object):
         check(self.lib.rz_net_deferred_gemm(self.handle, int(n_boards), int(n_slots), ctypes.byref(out), self._stream()),
               'rz_net_deferred_gemm')
         return out
+
+    def policy_rows(self, eng, kept):
+        """Policy on demand: the policy planes of the listed records of ``eng`` into their places in the store (rz_net_policy_rows)."""
+        check(self.lib.rz_net_policy_rows(self.handle, eng.handle, ctypes.byref(kept), self._stream()), 'rz_net_policy_rows')
 
     def deferred_gemm_rows(self, kept):
         """act_fc1 over the listed rows of the store (RzKeptRows of the engine's rz_deferred_keep) -> RzDeferredLogits, row i = listed row i."""
@@ -683,6 +693,7 @@ class MCTSEngine(object):
                                # per-root work (HipNetEvaluator's receptive-field bases) compare it with the epoch they computed for
         # deferred priors: the evaluator whose store holds this engine's pending leaves, steps since the last flush, capacity
         self._def_ev, self._def_pending, self._def_slots, self._def_slot_ptr, self._capturing = None, 0, 0, None, False
+        self._def_values = False   # the pending records are policy on demand's (no policy features in the store: _search_mode)
         # cap of an evaluator's store + logits (a flush every slots steps when n_playout needs more): a whole 800-simulation search of
         # 4096 games is 15 GB of 288 -- below the cap the search is one launch and the move one hipGraph (19 MB per slot at 4096 games)
         self.deferred_max_bytes = 32 << 30
@@ -690,6 +701,10 @@ class MCTSEngine(object):
         # the flush of a move on the device writes only the priors the move keeps (RZ_FLUSH_KEPT=0: all of them, as every other flush
         # does); read when the flush is enqueued -- a captured move keeps the setting it was captured under
         self.flush_kept = os.environ.get('RZ_FLUSH_KEPT', '1') != '0'
+        # ... and where they do, a resident search leaves the policy half of its leaves to that flush (route.policy_on_demand;
+        # RZ_POLICY_ON_DEMAND=0: every search writes the feature store)
+        self.policy_on_demand = os.environ.get('RZ_POLICY_ON_DEMAND', '1') != '0'
+        self.search_launches = {True: 0, False: 0}   # resident search launches enqueued or captured: without / with policy features
 
     # ------------------------------------------------------------------ plumbing
     def stream(self):
@@ -936,7 +951,7 @@ class MCTSEngine(object):
         if self._def_ev is not evaluator:
             self.flush_deferred()
             hip = evaluator.hip
-            per_slot = hip.deferred_bytes_per_slot(self.n_leaves) + 80 * self.n_games
+            per_slot = hip.deferred_bytes_per_slot(self.n_leaves) + 84 * self.n_games
             slots = int(max(16, min(max(self.n_playout, 16), self.deferred_max_bytes // per_slot)))
             if self._capturing:
                 raise HipError('the deferred-priors store must be reserved before a hipGraph capture (warm_graph does that)')
@@ -979,8 +994,10 @@ class MCTSEngine(object):
             if m < n and (self._playouts is not None or getattr(self, 'play_cap_on', False)):
                 raise ValueError('per-game simulation counts need the whole search in one launch: %d simulations, %d store slots' % (n, m))
             if resident:   # the m simulations in ONE launch, one workgroup per game, the first selection included
+                self._search_mode(evaluator)
                 evaluator.search_resident(self, m, True)
             else:
+                self._search_mode(None)
                 check(lib.rz_select_step(h, None, self.stream()), 'rz_select_step')
                 for i in range(m):
                     head = evaluator.deferred_trunk(self)
@@ -992,6 +1009,26 @@ class MCTSEngine(object):
                 self._def_pending += m
                 self._def_stream = self.torch.cuda.current_stream(self.device)
             n -= m
+
+    def _search_mode(self, evaluator):
+        """The ONE place that decides how the next search launch treats the policy half of its leaves (route.policy_on_demand) -> True:
+        without policy features.  ``evaluator`` None: a search by steps, which always writes the store.  Records of a search made in
+        one mode must not meet the flush of the other: what is pending in the other mode is flushed first."""
+        values = False
+        if evaluator is not None:
+            values = _route.policy_on_demand(self._ask(evaluator)[0], move_step=bool(getattr(self, '_play_on', False)),
+                                             flush_kept=bool(self.flush_kept), match=bool(getattr(self, 'play_match_on', False)),
+                                             allowed=bool(self.policy_on_demand))
+        if self._def_pending > 0 and values != self._def_values:
+            if self._capturing:
+                raise HipError('records of the other search mode are pending: flush before the capture')
+            self.flush_deferred()
+        if evaluator is not None:
+            self._search_values = values   # (what HipNet.search_resident launches next)
+            self.search_launches[values] += 1
+        if not self._capturing:
+            self._def_values = values      # (what the pending records are)
+        return values
 
     def flush_deferred(self, move=False):
         """Write the priors of every expansion since the last flush (one GEMM over the stored leaves + one kernel).  Called by
@@ -1005,7 +1042,9 @@ class MCTSEngine(object):
         if then is not None and then != cur:
             cur.wait_stream(then)
         if move:
-            self._enqueue_move_flush(self._def_ev.hip, self._def_pending)
+            self._enqueue_move_flush(self._def_ev.hip, self._def_pending, self._def_values)
+        elif self._def_values:   # policy on demand: every record with a block, by rows (correct and slow: _search_mode's conditions)
+            self._enqueue_rows_flush(self._def_ev.hip, 'all')
         else:
             logits = self._def_ev.hip.deferred_gemm(self.n_leaves, self._def_pending)
             check(self.lib.rz_deferred_flush(self.handle, ctypes.byref(logits), self._def_pending, self.stream()), 'rz_deferred_flush')
@@ -1013,12 +1052,31 @@ class MCTSEngine(object):
             then.wait_stream(cur)
         self._def_pending = 0
 
-    def _enqueue_move_flush(self, hip, n_slots):
+    def _enqueue_rows_flush(self, hip, what):
+        """A flush of records of policy on demand: rows -> their policy planes (the trunk again, on the listed leaves) -> GEMM -> priors.
+        ``what``: 'kept' (a drawn move's), 'all_move' (every record with a block, inside a drawn move), 'all' (outside one: the slots
+        are emptied as rz_deferred_flush empties them)."""
+        lib, h, st = self.lib, self.handle, self.stream()
+        kept = _hip.RzKeptRows()
+        if what == 'kept':
+            check(lib.rz_deferred_keep(h, ctypes.byref(kept), st), 'rz_deferred_keep')
+        else:
+            check(lib.rz_deferred_keep_all(h, ctypes.byref(kept), st), 'rz_deferred_keep_all')
+        hip.policy_rows(self, kept)
+        logits = hip.deferred_gemm_rows(kept)
+        if what == 'all':
+            check(lib.rz_deferred_flush_rows(h, ctypes.byref(logits), st), 'rz_deferred_flush_rows')
+        else:
+            check(lib.rz_deferred_flush_kept(h, ctypes.byref(logits), st), 'rz_deferred_flush_kept')
+
+    def _enqueue_move_flush(self, hip, n_slots, values=False):
         """The flush of a move's search, between rz_play_draw and rz_play_apply, on the current stream: the priors of the records the
         drawn move keeps (``flush_kept``: the kept child's subtree and the root's own block -- blocks of subtrees the move discards
-        are never written), or of all ``n_slots`` x n_games of them."""
+        are never written), or of all ``n_slots`` x n_games of them.  ``values``: the records are policy on demand's."""
         lib, h, st = self.lib, self.handle, self.stream()
-        if self.flush_kept:
+        if values:   # (records without policy features: by rows, whatever flush_kept says by now)
+            self._enqueue_rows_flush(hip, 'kept' if self.flush_kept else 'all_move')
+        elif self.flush_kept:
             kept = _hip.RzKeptRows()
             check(lib.rz_deferred_keep(h, ctypes.byref(kept), st), 'rz_deferred_keep')
             logits = hip.deferred_gemm_rows(kept)
@@ -1323,9 +1381,10 @@ class MCTSEngine(object):
         try:
             with t.cuda.graph(graph):
                 st = self.stream()
+                values = self._search_mode(evaluator)   # (nothing is pending: flushed above)
                 evaluator.search_resident(self, n, True)
                 check(lib.rz_play_draw(h, st), 'rz_play_draw')
-                self._enqueue_move_flush(hip, n)
+                self._enqueue_move_flush(hip, n, values)
                 check(lib.rz_play_apply(h, st), 'rz_play_apply')
         finally:
             self._capturing = False

@@ -50,6 +50,27 @@ def fc_in_trunk_pays(rows, cols, n_actions):
     return rows <= 10 and (n_actions * 4 * cells + 64 * 2 * cells) * 4 <= 40 * 1024
 
 
+def policy_on_demand(route, move_step=False, flush_kept=True, match=False, allowed=True):
+    """Whether the NEXT resident search of an engine runs without policy features (rz_net_search_resident_values: the value planes per
+    leaf, the policy planes formed at the flush for the records it lists -- rz_net_policy_rows).  It pays where flushes are kept flushes:
+    ``route`` (a Route) runs k_delta_res, the engine has the device move step attached (``move_step``), its moves flush what they keep
+    (``flush_kept``), it plays no match (``match``: two evaluators a move, every change a full flush), and the engine's switch
+    (``allowed``: MCTSEngine.policy_on_demand, from RZ_POLICY_ON_DEMAND, '0' = off) allows it.  Everything else keeps writing the store.
+    The library refuses the call where k_delta_res does not run (RZ_ERR_ARG), whatever this says."""
+    return bool(route.resident and route.resident_delta and move_step and flush_kept and not match and allowed)
+
+
+def pend_lw_pack(to_move, last):
+    """The word a pending record carries beside its stones (rz_tree.h: pend_lw_pack): the leaf's last move + 1 (0: none) in the low half,
+    its side to move above."""
+    return ((int(last) + 1) & 0xffff) | (int(to_move) << 16)
+
+
+def pend_lw_unpack(word):
+    """-> (side to move, last move or -1)."""
+    return (int(word) >> 16) & 1, (int(word) & 0xffff) - 1
+
+
 Route = namedtuple('Route', 'needs_planes deferred delta delta_three_launch resident resident_delta compact_resident resident_per_cu')
 Route.__doc__ = """How the leaves of a search are evaluated:
 needs_planes        the trunk reads float observation planes (otherwise the engine's leaf bitboards: no plane is written)
