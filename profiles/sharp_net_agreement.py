@@ -4,7 +4,7 @@ tests/golden/g9_* (tests/golden/gen_golden.py g9; loaders: tests/sharp_fixture.p
 reference's net outputs on 24 positions per board, searches of the reference's AlphaZeroMCTS with its own torch-CPU evaluator (every
 simulation's leaf and value, the tree) and self-play games, with the tolerances E = 4 x max |torch f32 - torch f64| measured there.
 The functions below run the same work on the GPU and return the largest difference each route shows; tests/test_sharp_net_rows.py
-asserts them against E, and the report lists them:
+and tests/test_policy_on_demand_sharp.py assert them against E, and the report lists them:
 
     python profiles/sharp_net_agreement.py > profiles/sharp_net/agreement.txt      (on an MI355X)
 """
@@ -148,10 +148,16 @@ def leaf_errors(B):
 
 
 # ---------------------------------------------------------------------------------------------------------------- d. the searches
-def search_on_device(B, cases, resident):
+def search_on_device(B, cases, resident, on_demand=None, copies=1):
     """All ``cases`` of a board as the games of one engine, searched by the device with its own values ->
-    (trees [{path: (N, W)}], root visit vectors, delta counters, the route)."""
+    (trees [{path: (N, W)}], root visit vectors, delta counters, the route).  ``on_demand`` True / False: the engine has the device
+    move step attached and its switch set so (search_attached: one sim_chunk without / with policy features in the store), with
+    ``copies`` of every case (case k in slots k, k + n, ..: trees and visit vectors of every slot)."""
     from oracle.gomoku_ref import RefGomoku
+    if on_demand is not None:
+        assert resident, 'policy on demand is the resident search\'s'
+        r = search_attached(B, cases, on_demand, copies)
+        return r['trees'], r['visits'], r['stats'], r['route']
     from rlzero_amd.engine import HipNetEvaluator, MCTSEngine, int_to_bits
     sims = cases[0]['n_playout']
     envs = [RefGomoku.from_moves(B, c['n'], c['pre']) for c in cases]
@@ -183,6 +189,131 @@ def tree_difference(tree, rec):
         elif want[path][0] > 0:
             worst = max(worst, abs(tree[path][1] - want[path][1]) / want[path][0])
     return bad, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------- f. policy on demand
+COPIES = 7   # of every case in one engine: game indices beyond 32, the second 32-board tile of the feature store
+
+
+def expanded_leaves(rec):
+    """The paths of a case's non-terminal leaves: the nodes its search expands, each once."""
+    terminal = set(rec['terminal'])
+    return [tuple(p) for i, (p, _) in enumerate(rec['leaves']) if i not in terminal]
+
+
+def leaf_planes(B, rec, paths):
+    """float32 [n, 4, B, B]: the observation planes of ``rec``'s root with each of ``paths`` played on it."""
+    from oracle.gomoku_ref import RefGomoku
+    root = RefGomoku.from_moves(B, rec['n'], rec['pre'])
+    out = np.empty((len(paths), 4, B, B), dtype=np.float32)
+    for i, path in enumerate(paths):
+        env = root.clone()
+        for m in path:
+            env.step(m)
+        out[i] = env.current_state()
+    return out
+
+
+def logp64_rows(B, rec, paths):
+    """oracle.evaluators.net_forward in float64 on the CPU, one batch -> log-probabilities float64 [n, S]."""
+    import torch
+    from oracle.evaluators import net_forward
+    with torch.no_grad():
+        return net_forward(sf.weights(B), leaf_planes(B, rec, paths), torch.float64)[0].numpy()
+
+
+_logp64 = {}
+
+
+def logp64_of(B, rec):
+    """{path: float64 log-probabilities [S]} of every node the case's search expands; computed once per case and left unchanged."""
+    key = (B, rec['name'])
+    if key not in _logp64:
+        paths = expanded_leaves(rec)
+        rows = logp64_rows(B, rec, paths)
+        rows.setflags(write=False)
+        _logp64[key] = dict(zip(paths, rows))
+    return _logp64[key]
+
+
+def expanded_blocks(eng, slot):
+    """{path: (legal cells ascending, the node's prior block PRI[PB : PB + K] float32)} over the expanded nodes reachable from the
+    root of ``slot`` (reads the arena: whatever is pending is flushed)."""
+    from rlzero_amd.engine import bits_to_int
+    a = eng.arena(slot)
+    stones, _, _ = eng.get_roots()
+    out, stack = {}, [((), 0, bits_to_int(stones[slot, 0]) | bits_to_int(stones[slot, 1]))]
+    while stack:
+        path, s, occ = stack.pop()
+        k, pb = int(a['K'][s]), int(a['PB'][s])
+        if k == 0:
+            continue
+        assert 0 <= pb and pb + k <= len(a['PRI']), (slot, path, k, pb)
+        legal = eng.legal_actions(occ)
+        out[path] = (legal, a['PRI'][pb:pb + k].copy())
+        assert int(a['NV'][s]) <= len(legal), (slot, path, int(a['NV'][s]), len(legal))
+        for r in range(int(a['NV'][s])):
+            stack.append((path + (legal[r], ), int(a['FC'][s]) + r, occ | (1 << legal[r])))
+    return out
+
+
+def block_errors(blocks, ref, prefix=()):
+    """-> (max |log(float64(prior)) - ref[prefix + path][cell]| over every block of ``blocks`` and legal cell -- inf for a prior that
+    is zero, negative or not a number --, blocks whose K is not the number of legal moves)."""
+    worst, wrong_k = 0.0, 0
+    for path, (legal, pri) in blocks.items():
+        if len(pri) != len(legal):
+            wrong_k += 1
+            continue
+        with np.errstate(divide='ignore', invalid='ignore'):
+            err = np.abs(np.log(pri.astype(np.float64)) - ref[tuple(prefix) + path][legal])
+        worst = max(worst, float(np.max(np.where(np.isfinite(err), err, np.inf))))
+    return worst, wrong_k
+
+
+def attached_twin(B, cases, on_demand, copies=1, graph=False):
+    """tests/move_step_twin.py's Twin (evaluator + engine on the device move step, slots refilled) on the board's sharp weights:
+    case k at the root of slots k, k + n, ..; no noise, the cases' c_puct and simulation count."""
+    from oracle.gomoku_ref import RefGomoku
+    from move_step_twin import Twin
+    sims, c_puct = cases[0]['n_playout'], cases[0]['c_puct']
+    assert all((c['n_playout'], c['c_puct'], c['n']) == (sims, c_puct, 5) for c in cases)
+    envs = [RefGomoku.from_moves(B, c['n'], c['pre']) for c in cases] * copies
+    twin = Twin(on_demand, module_of(B), len(envs), sims, roots=envs, board=B, add_noise=False, c_puct=c_puct, graph=graph)
+    assert twin.ev.hip.range_info()['split_ok']
+    return twin
+
+
+def search_attached(B, cases, on_demand, copies=1):
+    """One sim_chunk of the cases' simulations on attached_twin, then everything a comparison reads, on the host -> {'route',
+    'launches' (search_launches), 'stats' (delta counters), 'visits', 'trees' and 'reachable' (move_step_twin.reachable) per slot,
+    'blocks' (expanded_blocks) of the first copy of every case, 'root_priors'}.  The first read-out flushes: on demand every record by
+    rows (k_trunk_policy_rows -> k_heads_rows -> k_deferred_priors_rows), else the store's GEMM and k_deferred_priors."""
+    from move_step_twin import reachable
+    twin = attached_twin(B, cases, on_demand, copies)
+    eng, hip, G = twin.eng, twin.ev.hip, len(cases) * copies
+    hip.delta_stats(reset=True)
+    twin.search()
+    out = {'route': twin.route, 'launches': twin.modes(), 'stats': hip.delta_stats()}
+    out['visits'] = eng.root_visits().copy()
+    out['trees'] = [eng.tree_dump(g) for g in range(G)]
+    out['reachable'] = [reachable(eng, g) for g in range(G)]
+    out['blocks'] = [expanded_blocks(eng, g) for g in range(len(cases))]
+    out['root_priors'] = eng.root_priors().copy()
+    twin.close()   # (engine.check(), HipNet.check_flags(), and: every search of the twin ran in its own mode)
+    return out
+
+
+def prior_errors(B, on_demand, searched=None):
+    """The priors a full flush writes against the float64 net -> [(case, max |log(float64(prior)) - logp64| over the legal cells of
+    every expanded node, expanded nodes, blocks of a wrong K)]; ``searched``: a search_attached result of the board's robust cases."""
+    cases = [c for c in sf.search(B)['cases'] if c['robust']]
+    r = search_attached(B, cases, on_demand, COPIES) if searched is None else searched
+    out = []
+    for rec, blocks in zip(cases, r['blocks']):
+        worst, wrong_k = block_errors(blocks, logp64_of(B, rec))
+        out.append((rec['name'], worst, len(blocks), wrong_k))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- e. the games
@@ -272,6 +403,15 @@ def report(out=sys.stdout):
                 bad, worst = tree_difference(tree, rec)
                 out.write('  search %-9s %s: %d of %d nodes with another N, max |W - W_ref| / N %.3g\n'
                           % (rec['name'], 'resident' if resident else 'two-launch', bad, len(rec['tree']), worst))
+        for on_demand in (True, False):   # the device move step attached, 7 copies of every case: policy on demand / the store written
+            mode = 'on demand' if on_demand else 'store'
+            trees, _, _, _ = search_on_device(B, robust, True, on_demand, COPIES)
+            w_err = [tree_difference(tree, robust[g % len(robust)]) for g, tree in enumerate(trees)]
+            out.write('  attached, %-9s: %d slots, %d nodes with another N, max |W - W_ref| / N %.3g (E = %.3g)\n'
+                      % (mode, len(w_err), sum(b for b, _ in w_err), max(x for _, x in w_err), E))
+            for name, worst, nodes, wrong_k in prior_errors(B, on_demand):
+                out.write('  priors %-9s %-9s: %d expanded nodes, %d with a wrong K, max |log prior - log_probs (f64)| %.3g (E_lp + 2^-22 = %.3g)\n'
+                          % (name, mode, nodes, wrong_k, worst, E_lp + 2.0 ** -22))
         out.flush()
     for g in sf.games():
         agree, stats = play_on_device(g, g['robust_plies'])

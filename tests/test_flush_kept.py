@@ -10,7 +10,8 @@ from oracle.connect4_ref import RefConnect4
 from oracle.gomoku_ref import RefGomoku
 from oracle.mcts_ref import RefSearch
 
-SEED = 13
+from move_step_twin import SEED, reachable as _reachable
+
 WORDS = 4   # 64-bit words of a colour's bitboard (RZ_BOARD_WORDS)
 
 
@@ -152,26 +153,6 @@ class _Twin(object):
         assert st.reuse_dropped == 0
         self.eng.close()
         self.ev.hip.close()
-
-
-def _reachable(eng, g):
-    """Every field of every node reachable from the root of game g, in breadth-first order, with the priors of every expanded one;
-    what lies above the arena tops, and child records beyond the visited ones, is old data."""
-    a = eng.arena(g)
-    out, slots, at = [('root_prior', np.float32(a['root_prior']).tobytes())], [0], 0
-    while at < len(slots):
-        s = slots[at]
-        at += 1
-        fc, nv, k, pb = int(a['FC'][s]), int(a['NV'][s]), int(a['K'][s]), int(a['PB'][s])
-        assert s < a['top']
-        pri = b''
-        if k > 0:
-            assert pb >= 0 and pb + k <= len(a['PRI'])
-            pri = a['PRI'][pb:pb + k].tobytes()
-            if nv > 0:
-                slots.extend(range(fc, fc + nv))
-        out.append((s, int(a['N'][s]), float(a['W'][s]).hex(), fc, nv, k, pb, pri))
-    return out
 
 
 def _same_trees(a, b, n_games, what):

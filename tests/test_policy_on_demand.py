@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import test_flush_kept as tfk
+from move_step_twin import Twin as _Twin
 from oracle.gomoku_ref import RefGomoku
 from oracle.mcts_ref import RefSearch
 
@@ -110,71 +111,6 @@ def test_deep_position_has_kept_leaves_three_below_the_root():
 
 
 # ----------------------------------------------------------------------------------------------- GPU: twins
-class _Twin(object):
-    """An engine with its evaluator on the device move step; ``on_demand`` False: the switch off, every search writes the store."""
-
-    def __init__(self, on_demand, net, G, n_playout, graph=False, stall_margin=0.0, cap=None, queue_games=None, roots=None):
-        import torch
-        from rlzero_amd.engine import HipNetEvaluator, MCTSEngine
-        self.ev = HipNetEvaluator(net, B, 'cuda:0', max_boards=G)
-        self.eng = MCTSEngine(B, N_ROW, n_games=G, n_playout=n_playout, device='cuda:0', add_noise=True, noise_seed=3)
-        assert self.eng.flush_kept
-        self.eng.policy_on_demand = on_demand
-        self.on_demand = on_demand
-        n_q = G if queue_games is None else queue_games
-        self.queue = torch.arange(n_q, dtype=torch.int64, device='cuda:0')
-        self.ctl = torch.tensor([0, n_q], dtype=torch.int32, device='cuda:0')
-        self.eng.play_attach(SEED, 1.0, self.queue, self.ctl, ring_steps=16, stall_margin=stall_margin)
-        self.eng.play_refill()
-        if cap is not None:
-            self.eng.play_set_cap(*cap)
-        if roots is not None:
-            from rlzero_amd.engine import int_to_bits
-            stones = np.array([[int_to_bits(e.bitboards()[0]), int_to_bits(e.bitboards()[1])] for e in roots], dtype=np.uint64)
-            self.eng.set_roots(stones, [e.current_player() for e in roots], [e.last_move for e in roots], reset_trees=True)
-        self.route = self.eng._ask(self.ev)[0]
-        assert self.route.resident and self.route.resident_delta
-        self.graph = None
-        if graph:
-            self.warm()
-
-    def warm(self):
-        self.graph = self.eng.warm_move_graph(self.ev)
-        assert self.graph is not None
-
-    def search(self, n=None):
-        self.eng.sim_chunk(self.ev, self.eng.n_playout if n is None else n, self.route)
-
-    def move(self, search=True):
-        import torch
-        if self.graph is not None:
-            row = self.eng.play_move_replay(self.graph)
-        else:
-            if search:
-                self.search()
-            row = self.eng.play_move()
-        torch.cuda.synchronize()
-        rows = self.eng.play_log[row].cpu().numpy().copy()
-        running = (rows[:, 4] & 1) != 0   # (an idle slot's row holds nothing to read; which slot stays idle is the refill's race)
-        gid = (rows[:, 0].astype(np.int64) & 0xFFFFFFFF) | (rows[:, 1].astype(np.int64) << 32)
-        slots = np.nonzero(running)[0]
-        self.slot_of = slots[np.argsort(gid[slots], kind='stable')]
-        assert len(set(gid[slots].tolist())) == len(slots)
-        return rows[self.slot_of]
-
-    def modes(self):
-        return dict(self.eng.search_launches)
-
-    def close(self):
-        st = self.eng.check()
-        self.ev.hip.check_flags()
-        assert st.reuse_dropped == 0
-        # every resident search of this twin ran in its own mode
-        assert self.eng.search_launches[not self.on_demand] == 0 and self.eng.search_launches[self.on_demand] > 0, self.eng.search_launches
-        self.eng.close()
-        self.ev.hip.close()
-
-
 def _net():
     return tfk._net('gomoku', B)[0]
 
