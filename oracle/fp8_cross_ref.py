@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE (never imported by the product): a float64 model of the opt-in RZ_NET_SPLIT_F16_FP8 trunk arithmetic
-(rlzero_amd/csrc/rz_net.hip: rt::slot_r F8, pack_rows_f8) -- not of the reference, which has no such mode.  parity: this mode is
+(rlzero_amd/csrc/rz_net.hip: rt::slot_r F8; the weights: rlzero_amd/csrc/rz_pack.h, pack_rows_f8) -- not of the reference, which has no such mode.  parity: this mode is
 OUTSIDE the reference's f32 arithmetic by design; the model says what the device should compute, the tests say how far that is
 from PolicyValueNet.forward (rlzero/games/gomoku/policy_value_net.py:34-52) in float64.
 
@@ -49,7 +49,7 @@ def conv_split3(a, w, b, pad):
 
 
 def weight_scale(w):
-    """pack_split: the power of two that brings the largest |w| into [2^13, 2^14)."""
+    """rzp::weight_scale (rz_pack.h): the power of two that brings the largest |w| into [2^13, 2^14)."""
     wmax = float(w.abs().max())
     return 2.0 ** (14 - np.frexp(wmax)[1]) if wmax > 0 and np.isfinite(wmax) else 1.0
 

@@ -9,6 +9,7 @@ The library carries the hash of what it was built from (sources, headers, flags)
 binary is rebuilt wherever it came from, and ``_hip.load()`` refuses a library whose hash differs from the sources beside it.
 Every source is compiled to an object of its own (in parallel; an object is reused while its own hash holds), then linked.
 """
+import glob
 import hashlib
 import os
 import re
@@ -20,7 +21,7 @@ REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, 'librlzero_hip.so')
 OBJ_DIR = os.path.join(PKG, 'csrc', '_obj')
 SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip', 'rz_replay.hip')]
-HEADERS = [os.path.join(REPO, "include", "rlzero_hip.h"), os.path.join(PKG, "csrc", "rz_trace.h"), os.path.join(PKG, "csrc", "rz_tree.h"), os.path.join(PKG, "csrc", "rz_delta.h"), os.path.join(PKG, "csrc", "rz_window.h")]
+HEADERS = [os.path.join(REPO, 'include', 'rlzero_hip.h')] + sorted(glob.glob(os.path.join(PKG, 'csrc', '*.h')))  # every header beside the sources
 FLAGS = ['--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fno-fast-math', '-fno-slp-vectorize', '-std=c++17',
          '-fPIC', '-Wall', '-Wno-unused-function']
 MARKER = b'RZ_SOURCE_HASH='

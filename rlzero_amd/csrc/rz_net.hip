@@ -26,6 +26,11 @@
 //                                 feature pieces k_trunk_split writes in MFMA fragment order (default behind it)
 //   k_heads_gemm, k_heads_finish  the same layers on the f32-input MFMA (32 x 32 output blocks); log_softmax and tanh
 // Every kernel and its design notes are described where it is defined.
+//
+// Host side (from `struct rz_net` on): the C ABI's entry points.  What rz_net_load computes before it uploads -- the fragment layouts
+// the kernels above read, the weight and activation scales, the e4m3 bytes -- is rz_pack.h (no HIP, tested on the CPU:
+// tests/test_net_pack.py); the records handed to the kernels (value head, store, delta arguments) are each built by one helper
+// beside net_ready, and every device buffer is a DevBuf the net owns.
 
 #include <hip/hip_runtime.h>
 
@@ -38,6 +43,7 @@
 #include <vector>
 
 #include "rlzero_hip.h"
+#include "rz_pack.h"
 #include "rz_trace.h"
 #include "rz_tree.h"
 #include "rz_window.h"
@@ -704,8 +710,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(3))) f16x8 *lds_frag;
 
-constexpr float kObsScale = 16.0f;  // observation planes (0 / 1) are stored times 16
-constexpr float kMaxActScale = 16.0f, kF16Room = 60000.0f;  // activation scales: powers of two <= 16 that keep bound * scale < 60000
+using rzp::kObsScale;   // (rz_pack.h: the host scales the weights by what the kernels scale the planes and activations by)
 constexpr int kGridPos = 18 * 18;
 // POS: positions of the halo grid (18 x 18 in general; the compact layout of small boards: see k_trunk_split's RW / RH)
 template <int CIN, int POS = kGridPos> struct Geo {
@@ -2712,6 +2717,20 @@ __global__ __launch_bounds__(64) void k_heads_finish(NetDev nd, const float *__r
 
 }  // namespace
 
+// A device allocation its holder owns: move-only, freed with the holder.  Reads as the pointer it holds.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr, bytes = 0; }
+    bool alloc(size_t n) { release(); return hipMalloc((void **)&p, n) == hipSuccess ? (bytes = n, true) : (p = nullptr, false); }
+    bool fill(int byte) { return hipMemset(p, byte, bytes) == hipSuccess; }
+};
+
 struct rz_net {
     int board_size = 0, device = 0;
     bool loaded = false;
@@ -2728,34 +2747,33 @@ struct rz_net {
     bool compact_grid = true;
     bool compact_always = false;
     NetDev dev;
-    std::vector<void *> allocs;
-    std::vector<size_t> alloc_bytes;
+    std::vector<DevBuf<char>> allocs;   // the parameter buffers, in rz_net_load's order
     size_t upload_cursor = 0;
-    float *d_feat = nullptr, *d_raw = nullptr, *d_hid = nullptr;
-    _Float16 *d_feat16 = nullptr;  // the features as hi + lo f16 pieces in fragment order (k_trunk_split -> k_heads_split)
+    DevBuf<float> d_feat, d_raw, d_hid;
+    DevBuf<_Float16> d_feat16;     // the features as hi + lo f16 pieces in fragment order (k_trunk_split -> k_heads_split)
     bool feat16_valid = false;     // the last trunk launch into the internal buffer wrote d_feat16
     bool feat32_valid = false;     // ... wrote d_feat (the split-f16 trunk skips it when the GEMM reads the f16 pieces)
     int heads_algo = RZ_NET_HEADS_AUTO;
     int raw_parts = 1;           // what the last launch_heads_gemm left in d_raw / d_hid: 1 = final, 4 = K-quarter sums
     bool raw_from_trunk = false; // the last trunk launch ran the FC layers itself (k_trunk_split, FC_HERE): d_raw / d_hid are final
     size_t raw_part_floats = 0, hid_part_floats = 0;  // stride between the parts
-    unsigned *d_flags = nullptr;
+    DevBuf<unsigned> d_flags;
     long long feat_boards = 0;
     size_t feat_floats = 0;
     // deferred priors (rz_net_deferred_reserve): the policy-feature store, the logits of a flush, the value head's inputs
-    _Float16 *d_store16 = nullptr;
-    float *d_store_raw = nullptr, *d_valfeat = nullptr;
-    const float *d_w1t = nullptr;        // val_fc1.weight as [groups][64][4] (rz_value_head)
+    DevBuf<_Float16> d_store16;
+    DevBuf<float> d_store_raw, d_valfeat;
+    const float *d_w1t = nullptr;        // val_fc1.weight as [groups][64][4] (rz_value_head; one of `allocs`)
     int vf_groups = 0;                    // K / 4 of the value head's first layer, padded to a multiple of 4
     int store_slots = 0, store_tiles = 0; // slots x 32-board tiles per slot
     unsigned long long *d_trace = nullptr; // rz_net_trace_attach
     long long store_boards = 0;
     // receptive-field leaf evaluation (rz_delta.h; rz_net_delta_*): the base cache of `base_games` games
-    dl::BaseHdr *d_base_hdr = nullptr;
-    char *d_base_recs = nullptr;
-    unsigned *d_delta_stats = nullptr;
-    uint8_t *d_base_ones = nullptr;   // [base_games] of 1: the `active` flags of a caller that has none
-    uint64_t *d_win = nullptr;        // the window table of the net's board (rz_window.h; the board is fixed per net): k_delta_res
+    DevBuf<dl::BaseHdr> d_base_hdr;
+    DevBuf<char> d_base_recs;
+    DevBuf<unsigned> d_delta_stats;
+    DevBuf<uint8_t> d_base_ones;      // [base_games] of 1: the `active` flags of a caller that has none
+    DevBuf<uint64_t> d_win;           // the window table of the net's board (rz_window.h; the board is fixed per net): k_delta_res
     int base_games = 0;
     bool delta_resident = true;       // rz_net_delta_resident: rz_net_search_resident runs k_delta_res where the cache allows
 };
@@ -2772,251 +2790,90 @@ int net_fail(int code, const char *msg, const char *detail = "") {
 // Parameter buffers are allocated by the first rz_net_load and REUSED by later ones (same shapes, same
 // order), so device pointers captured in hipGraphs stay valid across weight updates.
 template <typename T>
-int net_upload(rz_net *net, const std::vector<T> &host, const T **out) {
-    void *p = nullptr;
-    const size_t bytes = host.size() * sizeof(T);
+int net_upload(rz_net *net, const float *host, size_t count, const T **out) {
+    const size_t bytes = count * sizeof(float);
     if (net->upload_cursor < net->allocs.size()) {
-        if (net->alloc_bytes[net->upload_cursor] != bytes) return net_fail(RZ_ERR_ARG, "parameter size changed between loads");
-        p = net->allocs[net->upload_cursor];
+        if (net->allocs[net->upload_cursor].bytes != bytes) return net_fail(RZ_ERR_ARG, "parameter size changed between loads");
     } else {
-        if (hipMalloc(&p, bytes) != hipSuccess) return net_fail(RZ_ERR_OOM, "hipMalloc failed (net)");
-        net->allocs.push_back(p);
-        net->alloc_bytes.push_back(bytes);
+        DevBuf<char> fresh;
+        if (!fresh.alloc(bytes)) return net_fail(RZ_ERR_OOM, "hipMalloc failed (net)");
+        net->allocs.push_back(std::move(fresh));
     }
+    void *p = net->allocs[net->upload_cursor].p;
     net->upload_cursor += 1;
-    if (hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemcpy failed (net)");
+    if (hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipMemcpy failed (net)");
     *out = (const T *)p;
     return RZ_OK;
 }
 
-// weight [cout][cin][3][3] -> [tile][cin_step][3][lane][4]: lane = kq*16 + m holds
-// W[16*tile + m][4*step + kq][tap = 4*tg + e] (taps 9..11 are zero padding)
-std::vector<f32x4> pack_conv(const float *w, int cout, int cin) {
-    const int tiles = cout / 16, steps = cin / 4;
-    std::vector<f32x4> out((size_t)tiles * steps * 3 * 64);
-    for (int t = 0; t < tiles; ++t)
-        for (int s = 0; s < steps; ++s)
-            for (int tg = 0; tg < 3; ++tg)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int m = lane & 15, kq = lane >> 4;
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    for (int e = 0; e < 4; ++e) {
-                        const int tap = 4 * tg + e;
-                        if (tap < 9) v[e] = w[((size_t)(16 * t + m) * cin + (4 * s + kq)) * 9 + tap];
-                    }
-                    out[(((size_t)t * steps + s) * 3 + tg) * 64 + lane] = v;
-                }
-    return out;
+int net_ready(rz_net *net, int32_t n) {
+    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net->loaded) return net_fail(RZ_ERR_ARG, "rz_net_load has not been called");
+    if (n < 0) return net_fail(RZ_ERR_ARG, "negative batch");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipGetDevice failed");
+    if (cur != net->device && hipSetDevice(net->device) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    return RZ_OK;
 }
 
-// U = G g G^T for F(4x4,3x3) (G: 6x3), packed [tile][pass][cin_step][3][64 lanes] x 4: lane = kq*16 + m
-// holds components k = 4*j + e (j = 0..2) of pass p for U[16*tile + m][4*step + kq], component k =
-// (transform row i' = rows[p][k / 6], column j' = k % 6).  fp64, rounded once.
-std::vector<f32x4> pack_wino_f4(const float *w, int cout, int cin) {
-    static const double G[6][3] = {{1.0 / 4, 0, 0},          {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
-    static const int rows[3][2] = {{1, 2}, {3, 4}, {0, 5}};
-    const int tiles = cout / 16, steps = cin / 4;
-    std::vector<f32x4> out((size_t)tiles * 3 * steps * 3 * 64);
-    for (int t = 0; t < tiles; ++t)
-        for (int s = 0; s < steps; ++s)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int m = lane & 15, kq = lane >> 4;
-                const float *g = w + ((size_t)(16 * t + m) * cin + (4 * s + kq)) * 9;
-                double tmp[6][3], U[6][6];
-                for (int i = 0; i < 6; ++i)
-                    for (int c = 0; c < 3; ++c)
-                        tmp[i][c] = G[i][0] * g[0 * 3 + c] + G[i][1] * g[1 * 3 + c] + G[i][2] * g[2 * 3 + c];
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) U[i][j] = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                for (int p = 0; p < 3; ++p)
-                    for (int j = 0; j < 3; ++j) {
-                        f32x4 v;
-                        for (int e = 0; e < 4; ++e) {
-                            const int k = 4 * j + e;
-                            v[e] = (float)U[rows[p][k / 6]][k % 6];
-                        }
-                        out[((((size_t)t * 3 + p) * steps + s) * 3 + j) * 64 + lane] = v;
-                    }
-            }
-    return out;
+// ---- the records the entry points hand to the kernels and to the engine, each built in one place
+
+// the engine's device view, and the net ready for a batch of its games
+int engine_view(rz_net *net, rz_engine *engine, rzt::Dev *dev) {
+    int rc = rz_device_view(engine, dev, (int64_t)sizeof(*dev));
+    if (rc != RZ_OK) return rc;
+    return net_ready(net, dev->n_games);
 }
 
-// Split f16 weights (k_trunk_split): w * scale = hi + lo with scale = the power of two that brings the
-// largest |w| of the layer into [2^13, 2^14).  Packed [tile of 32 cout][step = tap * chunks + chunk][piece][lane]
-// x 8 f16: lane = h*32 + r holds W[32*tile + r][16*chunk + 8*h + j][tap], j = 0..7 (the A fragment of
-// v_mfma_f32_32x32x16_f16).
-std::vector<f32x4> pack_split(const float *w, int cout, int cin, float *scale_out) {
-    float wmax = 0.0f;
-    for (size_t i = 0; i < (size_t)cout * cin * 9; ++i) wmax = std::fmax(wmax, std::fabs(w[i]));
-    int e = 0;
-    if (wmax > 0.0f && std::isfinite(wmax)) {
-        (void)std::frexp(wmax, &e);  // wmax = f * 2^e, f in [0.5, 1)
-        e = 14 - e;                  // wmax * 2^e in [2^13, 2^14)
-    }
-    const float scale = std::ldexp(1.0f, e);
-    *scale_out = scale;
-    const int tiles = cout / 32, chunks = cin / 16, steps = 9 * chunks;
-    std::vector<f32x4> out((size_t)tiles * steps * 2 * 64);
-    _Float16 *o = reinterpret_cast<_Float16 *>(out.data());
-    for (int t = 0; t < tiles; ++t)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int c = 0; c < chunks; ++c)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int r = lane & 31, h = lane >> 5, s = tap * chunks + c;
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = w[((size_t)(32 * t + r) * cin + (16 * c + 8 * h + j)) * 9 + tap] * scale;
-                        const _Float16 hi = (_Float16)v;
-                        const _Float16 lo = (_Float16)(v - (float)hi);
-                        o[((((size_t)t * steps + s) * 2 + 0) * 64 + lane) * 8 + j] = hi;
-                        o[((((size_t)t * steps + s) * 2 + 1) * 64 + lane) * 8 + j] = lo;
-                    }
-                }
-    return out;
+int same_board(const rz_net *net, const rzt::Dev &dev, bool actions_too) {
+    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || (actions_too && dev.A != net->dev.A))
+        return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    return RZ_OK;
 }
 
-// The same weights for k_trunk_rows (scale as pack_split: the two kernels share the rescaling factors).  Packed
-// [tile of 16 cout][step = tap * chunks + chunk of 32 cin][piece][lane] x 8 f16: lane = g*16 + r holds
-// W[16*tile + r][32*chunk + 8*g + j][tap], j = 0..7 (the A fragment of v_mfma_f32_16x16x32_f16).
-std::vector<f32x4> pack_rows(const float *w, int cout, int cin, float scale) {
-    const int tiles = cout / 16, chunks = cin / 32, steps = 9 * chunks;
-    std::vector<f32x4> out((size_t)tiles * steps * 2 * 64);
-    _Float16 *o = reinterpret_cast<_Float16 *>(out.data());
-    for (int t = 0; t < tiles; ++t)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int c = 0; c < chunks; ++c)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int r = lane & 15, g = lane >> 4, s = tap * chunks + c;
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = w[((size_t)(16 * t + r) * cin + (32 * c + 8 * g + j)) * 9 + tap] * scale;
-                        const _Float16 hi = (_Float16)v;
-                        o[((((size_t)t * steps + s) * 2 + 0) * 64 + lane) * 8 + j] = hi;
-                        o[((((size_t)t * steps + s) * 2 + 1) * 64 + lane) * 8 + j] = (_Float16)(v - (float)hi);
-                    }
-                }
-    return out;
+// what the tree step of the deferred route needs of the value head (rows: the inputs in d_valfeat; the resident search keeps them in LDS)
+rz_value_head value_head_of(const rz_net *net, bool rows = true) {
+    return rz_value_head{rows ? net->d_valfeat.p : nullptr, net->d_w1t, net->dev.fc_val1_b, net->dev.fc_val2_w, net->dev.fc_val2_b,
+                         net->vf_groups * 4, net->vf_groups};
 }
 
-// OCP e4m3fn (1.4.3, bias 7, no infinities, largest finite 448) of x, round to nearest even, saturating
-unsigned char to_e4m3(float x) {
-    const unsigned char sign = std::signbit(x) ? 0x80 : 0;
-    double a = std::fabs((double)x);
-    if (!(a == a)) return 0x7f;
-    if (a >= 448.0) return sign | 0x7e;
-    if (a < std::ldexp(1.0, -10)) return sign;   // below half the smallest subnormal (2^-9): zero
-    int e = 0;
-    (void)std::frexp(a, &e);   // a = f 2^e, f in [0.5, 1)
-    int ex = e - 1;            // a = 1.m x 2^ex
-    if (ex < -6) ex = -6;      // subnormals share the exponent of the smallest normal
-    const double step = std::ldexp(1.0, ex - 3);
-    double qv = std::nearbyint(a / step);   // (the default rounding mode: to nearest even)
-    int m = (int)qv;   // 0 .. 16 in units of step
-    if (ex == -6 && m < 8) return sign | (unsigned char)m;   // subnormal
-    if (m == 16) { m = 8; ++ex; }
-    if (ex > 8 || (ex == 8 && m - 8 > 6)) return sign | 0x7e;
-    return sign | (unsigned char)(((ex + 7) << 3) | (m - 8));
+// f16 values per slot of the policy-feature store: store_tiles tiles of groups_act K-steps of 32 boards x 16 x (hi | lo)
+long long store_stride(const rz_net *net) { return (long long)net->store_tiles * net->dev.groups_act * 1024; }
+
+// the features of a launch go to the store's slot slot_of[board] (value_rows: and the value head's inputs to d_valfeat, the schedule
+// trace attached) / to where the ordinary route puts them
+DeferredOut store_out(const rz_net *net, const int32_t *slot_of, bool value_rows) {
+    return DeferredOut{slot_of, store_stride(net), value_rows ? net->d_valfeat.p : nullptr, value_rows ? net->vf_groups * 4 : 0,
+                       value_rows ? net->d_trace : nullptr, net->store_slots};
+}
+DeferredOut no_store() { return DeferredOut{nullptr, 0, nullptr, 0, nullptr, 0}; }
+
+// active == NULL: every game is; count: the delta counters
+dl::DeltaArgs delta_args(const rz_net *net, const uint8_t *active, float *feat32, bool count, int mode, const uint64_t *win = nullptr) {
+    return dl::DeltaArgs{net->d_base_hdr, net->d_base_recs, active ? active : net->d_base_ones.p, feat32, count ? net->d_delta_stats.p : nullptr,
+                         mode, (65536 + net->dev.BW - 1) / net->dev.BW, win};
 }
 
-// conv3 for the FP8 cross terms of k_trunk_rows (rt::slot_r, F8).  v = w * scale as in pack_rows (|v| < 2^14), hi = f16(v),
-// lo = f16(v - hi).  Packed [tile of 16 cout][tap][part][half][lane] x 16 bytes with lane = g*16 + r:
-//   part 0, half c: the hi f16 pieces of W[16 tile + r][32 c + 8 g + j][tap], j = 0..7 (pack_rows' hi fragment of chunk c);
-//   part 1: the lane's 32 bytes of the K = 128 block of the scaled MFMA, input channels 16 g + j, j = 0..15:
-//           half 0 = e4m3(lo * 2^5) (meets the activations' e5m2 value), half 1 = e4m3(hi * 2^-6) (meets e5m2((value - hi) 2^11));
-//           with the block's scale 2^-5 both products come out in the units of hi x hi.  |lo| <= 4 and |hi| <= 2^14: 128 and 256 of 448.
-std::vector<f32x4> pack_rows_f8(const float *w, int cout, int cin, float scale) {
-    const int tiles = cout / 16;
-    std::vector<f32x4> out((size_t)tiles * 9 * 2 * 2 * 64);
-    unsigned char *o = reinterpret_cast<unsigned char *>(out.data());
-    for (int t = 0; t < tiles; ++t)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = lane & 15, g = lane >> 4;
-                auto piece = [&](int ci, _Float16 *hi, _Float16 *lo) {
-                    const float v = w[((size_t)(16 * t + r) * cin + ci) * 9 + tap] * scale;
-                    *hi = (_Float16)v;
-                    *lo = (_Float16)(v - (float)*hi);
-                };
-                const size_t base = ((size_t)t * 9 + tap) * 4 * 1024 + (size_t)lane * 16;
-                for (int c = 0; c < 2; ++c)
-                    for (int j = 0; j < 8; ++j) {
-                        _Float16 hi, lo;
-                        piece(32 * c + 8 * g + j, &hi, &lo);
-                        memcpy(o + base + c * 1024 + j * 2, &hi, 2);
-                    }
-                for (int j = 0; j < 16; ++j) {
-                    _Float16 hi, lo;
-                    piece(16 * g + j, &hi, &lo);
-                    o[base + 2048 + j] = to_e4m3((float)lo * 32.0f);
-                    o[base + 3072 + j] = to_e4m3((float)hi * (1.0f / 64.0f));
-                }
-            }
-    return out;
+// the NetDev of a GEMM over the store's tiles, which hold the policy K-steps only; n_groups: groups of 128 policy outputs
+int policy_store_dev(const rz_net *net, NetDev *nd, int *n_groups) {
+    *nd = net->dev;
+    nd->groups_val = 0;
+    *n_groups = (nd->Npad / 32 + 3) / 4;
+    if (*n_groups > 2) return net_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
+    return RZ_OK;
 }
 
-// conv1 (32 x 4 x 3 x 3) for k_trunk_split: K-step = kernel row ky, k = 4 * kx + plane for kx = 0..3 (kx = 3: zero
-// padding); lane = h*32 + r holds k = 8*h .. 8*h + 7 of output channel r.  [ky][hi | lo][lane] x 8 f16.
-std::vector<f32x4> pack_split1(const float *w, float *scale_out) {
-    float wmax = 0.0f;
-    for (int i = 0; i < 32 * 4 * 9; ++i) wmax = std::fmax(wmax, std::fabs(w[i]));
-    int e = 0;
-    if (wmax > 0.0f && std::isfinite(wmax)) {
-        (void)std::frexp(wmax, &e);
-        e = 14 - e;
-    }
-    const float scale = std::ldexp(1.0f, e);
-    *scale_out = scale;
-    std::vector<f32x4> out((size_t)3 * 2 * 64);
-    _Float16 *o = reinterpret_cast<_Float16 *>(out.data());
-    for (int ky = 0; ky < 3; ++ky)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int r = lane & 31, h = lane >> 5;
-            for (int j = 0; j < 8; ++j) {
-                const int kx = 2 * h + (j >> 2), c = j & 3;
-                const float v = kx < 3 ? w[((r * 4 + c) * 3 + ky) * 3 + kx] * scale : 0.0f;
-                const _Float16 hi = (_Float16)v;
-                o[(((size_t)ky * 2 + 0) * 64 + lane) * 8 + j] = hi;
-                o[(((size_t)ky * 2 + 1) * 64 + lane) * 8 + j] = (_Float16)(v - (float)hi);
-            }
-        }
-    return out;
-}
-
-// FC weights for k_heads_split: w [n_out][k_in] row-major * scale = hi + lo (scale as in pack_split), packed
-// [32-output tile][K-step][hi | lo][lane] x 8 f16: lane = h*32 + c holds W[32*tile + c][16*step + 8*h + j], the B
-// fragment of v_mfma_f32_32x32x16_f16; zero beyond n_out / k_in.
-std::vector<f32x4> pack_split_fc(const float *w, int n_out, int k_in, int tiles, int steps, float *scale_out) {
-    float wmax = 0.0f;
-    for (size_t i = 0; i < (size_t)n_out * k_in; ++i) wmax = std::fmax(wmax, std::fabs(w[i]));
-    int e = 0;
-    if (wmax > 0.0f && std::isfinite(wmax)) {
-        (void)std::frexp(wmax, &e);
-        e = 14 - e;
-    }
-    const float scale = std::ldexp(1.0f, e);
-    *scale_out = scale;
-    std::vector<f32x4> out(((size_t)tiles * steps + 1) * 2 * 64, f32x4{0.f, 0.f, 0.f, 0.f});  // + one all-zero K-step
-    _Float16 *o = reinterpret_cast<_Float16 *>(out.data());
-    for (int t = 0; t < tiles; ++t)
-        for (int st = 0; st < steps; ++st)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int c = lane & 31, h = lane >> 5, row = 32 * t + c;
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * st + 8 * h + j;
-                    const float v = (row < n_out && k < k_in) ? w[(size_t)row * k_in + k] * scale : 0.0f;
-                    const _Float16 hi = (_Float16)v;
-                    o[((((size_t)t * steps + st) * 2 + 0) * 64 + lane) * 8 + j] = hi;
-                    o[((((size_t)t * steps + st) * 2 + 1) * 64 + lane) * 8 + j] = (_Float16)(v - (float)hi);
-                }
-            }
-    return out;
+// the internal feature buffer uses the padded layout of the FC GEMM (NetDev::feat_ld)
+void use_internal_feat_layout(rz_net *net) {
+    net->dev.feat_ld = 16 * (net->dev.groups_act + net->dev.groups_val);
+    net->dev.feat_val_off = 16 * net->dev.groups_act;
 }
 
 }  // namespace
 
 template <int NT>
 static void launch_trunk_rows(bool bits, dim3 grid, hipStream_t stream, const NetDev &nd, const float *d_obs, LeafBits leaves, float *f32,
-                              _Float16 *f16, int n_boards, unsigned *flags, DeferredOut later = DeferredOut{nullptr, 0, nullptr, 0, nullptr},
+                              _Float16 *f16, int n_boards, unsigned *flags, DeferredOut later = no_store(),
                               bool fp8 = false) {
     if (fp8 && bits) {   // (the schedule trace reads the default arithmetic's kernel)
         k_trunk_rows<NT, true, false, true><<<grid, dim3(256), 0, stream>>>(nd, d_obs, leaves, f32, f16, n_boards, flags, later);
@@ -3097,8 +2954,7 @@ int rz_net_create(int32_t height, int32_t width, int32_t n_actions, int32_t devi
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             net->n_cus = prop.multiProcessorCount;
     }
-    if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&net->d_flags, sizeof(unsigned)) != hipSuccess ||
-        hipMemset(net->d_flags, 0, sizeof(unsigned)) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || !net->d_flags.alloc(sizeof(unsigned)) || !net->d_flags.fill(0)) {
         delete net;
         return net_fail(RZ_ERR_OOM, "hipMalloc failed (net flags)");
     }
@@ -3131,20 +2987,6 @@ int rz_net_destroy(rz_net *net) {
     if (!net) return RZ_OK;
     (void)hipSetDevice(net->device);
     (void)hipDeviceSynchronize();
-    for (void *p : net->allocs) (void)hipFree(p);
-    if (net->d_feat) (void)hipFree(net->d_feat);
-    if (net->d_feat16) (void)hipFree(net->d_feat16);
-    if (net->d_raw) (void)hipFree(net->d_raw);
-    if (net->d_hid) (void)hipFree(net->d_hid);
-    if (net->d_flags) (void)hipFree(net->d_flags);
-    if (net->d_store16) (void)hipFree(net->d_store16);
-    if (net->d_store_raw) (void)hipFree(net->d_store_raw);
-    if (net->d_valfeat) (void)hipFree(net->d_valfeat);
-    if (net->d_base_hdr) (void)hipFree(net->d_base_hdr);
-    if (net->d_base_recs) (void)hipFree(net->d_base_recs);
-    if (net->d_delta_stats) (void)hipFree(net->d_delta_stats);
-    if (net->d_base_ones) (void)hipFree(net->d_base_ones);
-    if (net->d_win) (void)hipFree(net->d_win);
     delete net;
     return RZ_OK;
 }
@@ -3171,133 +3013,50 @@ int rz_net_load(rz_net *net, const float *const *h_params, int32_t n_params) {
     net->upload_cursor = 0;
     const int S = net->dev.S;
     NetDev &D = net->dev;
+    // the arithmetic is rz_pack.h's; here: the uploads, in an order that must not change (net_upload reuses the buffers of
+    // the first load by position)
+    const rzp::Prepared P = rzp::prepare(h_params, rzp::Shape{S, D.A, D.Npad, D.groups_act, D.groups_val});
+    net->split_ok = P.split_ok;
+    net->vf_groups = P.vf_groups;
+    memcpy(net->range_info, P.range_info, sizeof(net->range_info));
     int rc = RZ_OK;
-    auto up_vec4 = [&](const std::vector<f32x4> &v, const f32x4 **dst) { if (rc == RZ_OK) rc = net_upload(net, v, dst); };
-    auto up_f = [&](const float *src, size_t count, const float **dst) {
-        if (rc == RZ_OK) rc = net_upload(net, std::vector<float>(src, src + count), dst);
-    };
+    auto up = [&](const std::vector<float> &v, auto **dst) { if (rc == RZ_OK) rc = net_upload(net, v.data(), v.size(), dst); };
+    auto up_f = [&](const float *src, size_t count, const float **dst) { if (rc == RZ_OK) rc = net_upload(net, src, count, dst); };
     // order of PolicyValueNet.state_dict(): conv1.w,b conv2.w,b conv3.w,b act_conv1.w,b
     // act_fc1.w,b val_conv1.w,b val_fc1.w,b val_fc2.w,b
-    up_vec4(pack_conv(h_params[0], 32, 4), &D.w1);
+    up(P.w1, &D.w1);
     up_f(h_params[1], 32, &D.b1);
-    up_vec4(pack_conv(h_params[2], 64, 32), &D.w2);
+    up(P.w2, &D.w2);
     up_f(h_params[3], 64, &D.b2);
-    up_vec4(pack_conv(h_params[4], 128, 64), &D.w3);
-    up_vec4(pack_wino_f4(h_params[2], 64, 32), &D.u2f);
-    up_vec4(pack_wino_f4(h_params[4], 128, 64), &D.u3f);
-    {
-        float sw2 = 1.0f, sw3 = 1.0f;
-        up_vec4(pack_split(h_params[2], 64, 32, &sw2), &D.s2);
-        up_vec4(pack_split(h_params[4], 128, 64, &sw3), &D.s3);
-        up_vec4(pack_rows(h_params[2], 64, 32, sw2), &D.t2);
-        up_vec4(pack_rows(h_params[4], 128, 64, sw3), &D.t3);
-        up_vec4(pack_rows_f8(h_params[4], 128, 64, sw3), &D.t3f);
-        float sw1 = 1.0f;
-        up_vec4(pack_split1(h_params[0], &sw1), &D.s1);
-        float sfa = 1.0f, sfv = 1.0f;
-        up_vec4(pack_split_fc(h_params[8], D.A, 4 * S, D.Npad / 32, D.groups_act, &sfa), &D.fs_act);
-        up_vec4(pack_split_fc(h_params[12], 64, 2 * S, 2, D.groups_val, &sfv), &D.fs_val);
-        // Activation bounds for observation planes in [0, 1] (the MCTS leaves: 0 / 1): a ReLU output is at most its
-        // bias plus the positive weights times the bounds of their inputs.  Each layer's f16 pieces are stored times
-        // the largest power of two <= 16 that keeps bound * scale below 60000, so NO activation of such an input can
-        // leave the f16 range (the pieces of a value of size z carry an absolute error of max(2^-22 z, 2^-25): a
-        // bound 1000x above the real activations still leaves the error below f32 rounding).  Without finite
-        // bounds (inf / nan weights) the net runs on the exact-f32 direct trunk instead.
-        double b1v[32], b2v[64], b3v[128], bfv[6];
-        auto layer_bound = [](const float *w, const float *bias, int cout, int cin, int taps, const double *in, double *out) {
-            double top = 0.0;
-            for (int c = 0; c < cout; ++c) {
-                double acc = bias[c] > 0.0f ? (double)bias[c] : 0.0;
-                for (int i = 0; i < cin; ++i)
-                    for (int t = 0; t < taps; ++t) {
-                        const double wv = w[((size_t)c * cin + i) * taps + t];
-                        if (wv > 0.0) acc += wv * (in ? in[i] : 1.0);
-                        else if (!(wv <= 0.0)) acc = INFINITY;  // nan
-                    }
-                out[c] = acc;
-                top = std::fmax(top, acc);
-                if (!(acc >= 0.0)) top = INFINITY;
-            }
-            return top;
-        };
-        const double t1 = layer_bound(h_params[0], h_params[1], 32, 4, 9, nullptr, b1v);
-        const double t2 = layer_bound(h_params[2], h_params[3], 64, 32, 9, b1v, b2v);
-        (void)layer_bound(h_params[4], h_params[5], 128, 64, 9, b2v, b3v);
-        double tf = layer_bound(h_params[6], h_params[7], 4, 128, 1, b3v, bfv);
-        tf = std::fmax(tf, layer_bound(h_params[10], h_params[11], 2, 128, 1, b3v, bfv + 4));
-        auto act_scale = [](double bound) {
-            if (!(bound * sp::kMaxActScale >= sp::kF16Room)) return sp::kMaxActScale;  // also bound == 0
-            int e = 0;
-            (void)std::frexp(sp::kF16Room / bound, &e);   // kF16Room / bound = f * 2^e, f in [0.5, 1)
-            return std::ldexp(1.0f, e - 1);                // the largest power of two <= kF16Room / bound
-        };
-        net->split_ok = std::isfinite(t1) && std::isfinite(t2) && std::isfinite(tf) && t1 < 1e30 && t2 < 1e30 && tf < 1e30;
-        const float a1 = net->split_ok ? act_scale(t1) : sp::kMaxActScale, a2 = net->split_ok ? act_scale(t2) : sp::kMaxActScale,
-                    a3 = net->split_ok ? act_scale(tf) : sp::kMaxActScale;
-        const float info[8] = {(float)t1, (float)t2, (float)tf, a1, a2, a3, net->split_ok ? 1.0f : 0.0f, 0.0f};
-        memcpy(net->range_info, info, sizeof(info));
-        up_f(std::vector<float>{a2 / (a1 * sw2), 1.0f / (a2 * sw3), a1 / (sp::kObsScale * sw1),
-                                1.0f / (a3 * sfa), 1.0f / (a3 * sfv), a1, a2, a3}.data(), 8, &D.s_inv);
-    }
+    up(P.w3, &D.w3);
+    up(P.u2f, &D.u2f);
+    up(P.u3f, &D.u3f);
+    up(P.s2, &D.s2);
+    up(P.s3, &D.s3);
+    up(P.t2, &D.t2);
+    up(P.t3, &D.t3);
+    up(P.t3f, &D.t3f);
+    up(P.s1, &D.s1);
+    up(P.fs_act, &D.fs_act);
+    up(P.fs_val, &D.fs_val);
+    up(P.s_inv, &D.s_inv);
     up_f(h_params[5], 128, &D.b3);
-    {
-        std::vector<float> wh(6 * 128), bh(6);
-        memcpy(wh.data(), h_params[6], 4 * 128 * sizeof(float));
-        memcpy(wh.data() + 4 * 128, h_params[10], 2 * 128 * sizeof(float));
-        memcpy(bh.data(), h_params[7], 4 * sizeof(float));
-        memcpy(bh.data() + 4, h_params[11], 2 * sizeof(float));
-        if (rc == RZ_OK) rc = net_upload(net, wh, &D.wh);
-        std::vector<float> whp(128 * 6);
-        for (int c = 0; c < 128; ++c)
-            for (int o = 0; o < 6; ++o) whp[c * 6 + o] = wh[o * 128 + c];
-        if (rc == RZ_OK) rc = net_upload(net, whp, &D.whp);
-        if (rc == RZ_OK) rc = net_upload(net, bh, &D.bh);
-    }
-    {
-        const size_t ld = (size_t)16 * D.groups_act;
-        std::vector<float> t((size_t)D.Npad * ld, 0.0f), bias((size_t)D.Npad, 0.0f);
-        for (int j = 0; j < D.A; ++j) {
-            bias[j] = h_params[9][j];
-            memcpy(&t[(size_t)j * ld], h_params[8] + (size_t)j * 4 * S, (size_t)4 * S * sizeof(float));
-        }
-        if (rc == RZ_OK) rc = net_upload(net, t, &D.fc_act_w);
-        if (rc == RZ_OK) rc = net_upload(net, bias, &D.fc_act_b);
-    }
-    {
-        const size_t ld = (size_t)16 * D.groups_val;
-        std::vector<float> t((size_t)64 * ld, 0.0f);
-        for (int j = 0; j < 64; ++j)
-            memcpy(&t[(size_t)j * ld], h_params[12] + (size_t)j * 2 * S, (size_t)2 * S * sizeof(float));
-        if (rc == RZ_OK) rc = net_upload(net, t, &D.fc_val1_w);
-        up_f(h_params[13], 64, &D.fc_val1_b);
-    }
+    up(P.wh, &D.wh);
+    up(P.whp, &D.whp);
+    up(P.bh, &D.bh);
+    up(P.fc_act_w, &D.fc_act_w);
+    up(P.fc_act_b, &D.fc_act_b);
+    up(P.fc_val1_w, &D.fc_val1_w);
+    up_f(h_params[13], 64, &D.fc_val1_b);
     up_f(h_params[14], 64, &D.fc_val2_w);
     up_f(h_params[15], 1, &D.fc_val2_b);
-    {   // the value head's first layer for the tree step of the deferred route: [group of 4 inputs][hidden unit][4]
-        // four waves x two halves x PER groups of 4 inputs, PER = 2, 4, 8 or 16 (k_tree_step_def): 64 .. 512 inputs
-        const int need = (2 * S + 3) / 4;
-        net->vf_groups = need <= 16 ? 16 : need <= 32 ? 32 : need <= 64 ? 64 : 128;
-        std::vector<float> t((size_t)net->vf_groups * 64 * 4, 0.0f);
-        for (int j = 0; j < 64; ++j)
-            for (int k = 0; k < 2 * S; ++k) t[((size_t)(k / 4) * 64 + j) * 4 + k % 4] = h_params[12][(size_t)j * 2 * S + k];
-        if (rc == RZ_OK) rc = net_upload(net, t, &net->d_w1t);
-    }
+    up(P.w1t, &net->d_w1t);
     // the receptive-field bases hold activations of the weights they were built with: none survives an upload (a leaf of a game
     // without a valid base takes the route without one until rz_net_delta_bases runs again)
-    if (rc == RZ_OK && net->base_games > 0 && hipMemset(net->d_base_hdr, 0, (size_t)net->base_games * sizeof(dl::BaseHdr)) != hipSuccess)
+    if (rc == RZ_OK && net->base_games > 0 && !net->d_base_hdr.fill(0))
         rc = net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->loaded = rc == RZ_OK;
     return rc;
-}
-
-static int net_ready(rz_net *net, int32_t n) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
-    if (!net->loaded) return net_fail(RZ_ERR_ARG, "rz_net_load has not been called");
-    if (n < 0) return net_fail(RZ_ERR_ARG, "negative batch");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipGetDevice failed");
-    if (cur != net->device && hipSetDevice(net->device) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    return RZ_OK;
 }
 
 int rz_net_reserve(rz_net *net, int32_t max_boards) {
@@ -3305,30 +3064,25 @@ int rz_net_reserve(rz_net *net, int32_t max_boards) {
     if (rc != RZ_OK) return rc;
     if (max_boards <= net->feat_boards) return RZ_OK;
     (void)hipDeviceSynchronize();
-    if (net->d_feat) (void)hipFree(net->d_feat);
-    if (net->d_feat16) (void)hipFree(net->d_feat16);
-    if (net->d_raw) (void)hipFree(net->d_raw);
-    if (net->d_hid) (void)hipFree(net->d_hid);
-    net->d_feat = net->d_raw = net->d_hid = nullptr;
-    net->d_feat16 = nullptr;
+    net->d_feat.release();
+    net->d_feat16.release();
+    net->d_raw.release();
+    net->d_hid.release();
     net->feat16_valid = net->feat32_valid = false;
     net->feat_boards = 0;
     // internal features: [boards padded to 32][16 * (groups_act + groups_val)], zero filled once
     const size_t pad_boards = ((size_t)max_boards + 31) / 32 * 32;
     net->feat_floats = pad_boards * 16 * (size_t)(net->dev.groups_act + net->dev.groups_val);
-    if (hipMalloc((void **)&net->d_feat, net->feat_floats * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&net->d_raw, 4 * (((size_t)max_boards + 63) / 64 * 64) * net->dev.Npad * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&net->d_hid, 4 * (((size_t)max_boards + 63) / 64 * 64) * 64 * sizeof(float)) != hipSuccess)
+    if (!net->d_feat.alloc(net->feat_floats * sizeof(float)) ||
+        !net->d_raw.alloc(4 * (((size_t)max_boards + 63) / 64 * 64) * net->dev.Npad * sizeof(float)) ||
+        !net->d_hid.alloc(4 * (((size_t)max_boards + 63) / 64 * 64) * 64 * sizeof(float)))
         return net_fail(RZ_ERR_OOM, "hipMalloc failed (feature buffers)");
     // padded boards and the K tail must read as finite values (they meet zero weights)
-    if (hipMemset(net->d_feat, 0, net->feat_floats * sizeof(float)) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemset failed (feature buffer)");
+    if (!net->d_feat.fill(0)) return net_fail(RZ_ERR_HIP, "hipMemset failed (feature buffer)");
     {   // f16 pieces: [boards padded to 64][K-steps][hi | lo][16 x f16]; the K tail and padded boards stay zero
         const size_t bytes = (((size_t)max_boards + 63) / 64 * 64) * (size_t)(net->dev.groups_act + net->dev.groups_val) * 64;
-        if (hipMalloc((void **)&net->d_feat16, bytes) != hipSuccess)
-            return net_fail(RZ_ERR_OOM, "hipMalloc failed (f16 feature buffer)");
-        if (hipMemset(net->d_feat16, 0, bytes) != hipSuccess)
-            return net_fail(RZ_ERR_HIP, "hipMemset failed (f16 feature buffer)");
+        if (!net->d_feat16.alloc(bytes)) return net_fail(RZ_ERR_OOM, "hipMalloc failed (f16 feature buffer)");
+        if (!net->d_feat16.fill(0)) return net_fail(RZ_ERR_HIP, "hipMemset failed (f16 feature buffer)");
     }
     net->raw_part_floats = (((size_t)max_boards + 63) / 64 * 64) * net->dev.Npad;  // room for four K-quarter parts
     net->hid_part_floats = (((size_t)max_boards + 63) / 64 * 64) * 64;
@@ -3359,7 +3113,7 @@ static TrunkClass trunk_class(const rz_net *net) {
 }
 
 static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t n_boards, void *stream,
-                         LeafBits leaves = LeafBits{nullptr, nullptr, nullptr}, DeferredOut later = DeferredOut{nullptr, 0, nullptr, 0, nullptr}) {
+                         LeafBits leaves = LeafBits{nullptr, nullptr, nullptr}, DeferredOut later = no_store()) {
     const dim3 grid((unsigned)n_boards);
     // the internal buffer uses the padded layout of the FC GEMM, a caller's buffer the natural one
     const bool internal = d_feat == net->d_feat;
@@ -3374,8 +3128,8 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
         net->feat16_valid = split;
         net->feat32_valid = want_f32;
     }
-    net->dev.feat_ld = internal ? 16 * (net->dev.groups_act + net->dev.groups_val) : 6 * net->dev.S;
-    net->dev.feat_val_off = internal ? 16 * net->dev.groups_act : 4 * net->dev.S;
+    if (internal) use_internal_feat_layout(net);
+    else net->dev.feat_ld = 6 * net->dev.S, net->dev.feat_val_off = 4 * net->dev.S;
     // Winograd kernels are persistent: one workgroup per CU (LDS bound) loops over its boards
     const int wg_cap = net->max_wgs > 0 ? net->max_wgs : net->n_cus;
     const dim3 pgrid((unsigned)(n_boards < wg_cap ? n_boards : wg_cap));
@@ -3421,8 +3175,7 @@ static void launch_trunk(rz_net *net, const float *d_obs, float *d_feat, int32_t
 
 // The FC GEMM of the heads on the internal features -> net->d_raw (policy logits) / net->d_hid (value hidden layer).
 static void launch_heads_gemm(rz_net *net, const float *d_feat, int32_t n_boards, void *stream) {
-    net->dev.feat_ld = 16 * (net->dev.groups_act + net->dev.groups_val);
-    net->dev.feat_val_off = 16 * net->dev.groups_act;
+    use_internal_feat_layout(net);
     if (net->raw_from_trunk && d_feat == net->d_feat) {   // the trunk's workgroups ran these layers on their boards
         net->raw_parts = 1;
         return;
@@ -3437,7 +3190,7 @@ static void launch_heads_gemm(rz_net *net, const float *d_feat, int32_t n_boards
     if (d_feat != net->d_feat || !net->feat16_valid) algo = RZ_NET_HEADS_F32;
     else if (algo == RZ_NET_HEADS_F32 && !net->feat32_valid)  // F32 chosen after a trunk that wrote only the f16 pieces
         algo = net->max_wgs > 0 ? RZ_NET_HEADS_SPLIT_64 : RZ_NET_HEADS_SPLIT_32;
-    const f32x4 *f16 = reinterpret_cast<const f32x4 *>(net->d_feat16);
+    const f32x4 *f16 = reinterpret_cast<const f32x4 *>(net->d_feat16.p);
     const int n_act_tiles = net->dev.Npad / 32;
     net->raw_parts = 1;
     if (algo == RZ_NET_HEADS_SPLIT_PARTS) {
@@ -3509,23 +3262,20 @@ int rz_net_deferred_reserve(rz_net *net, int32_t max_boards, int32_t slots) {
     if (max_boards < net->store_boards) max_boards = net->store_boards;
     if (slots < net->store_slots) slots = net->store_slots;
     (void)hipDeviceSynchronize();
-    if (net->d_store16) (void)hipFree(net->d_store16);
-    if (net->d_store_raw) (void)hipFree(net->d_store_raw);
-    if (net->d_valfeat) (void)hipFree(net->d_valfeat);
-    net->d_store16 = nullptr;
-    net->d_store_raw = net->d_valfeat = nullptr;
+    net->d_store16.release();
+    net->d_store_raw.release();
+    net->d_valfeat.release();
     net->store_boards = 0;
     net->store_slots = 0;
     const int tiles = ((max_boards + 63) / 64) * 2;   // whole 64-board blocks: the GEMM's workgroups take two tiles
     const size_t store_bytes = (size_t)slots * tiles * net->dev.groups_act * 2048;
     const size_t raw_bytes = (size_t)slots * tiles * 32 * net->dev.Npad * sizeof(float);
     const size_t val_bytes = (size_t)tiles * 32 * net->vf_groups * 4 * sizeof(float);
-    if (hipMalloc((void **)&net->d_store16, store_bytes) != hipSuccess || hipMalloc((void **)&net->d_store_raw, raw_bytes) != hipSuccess ||
-        hipMalloc((void **)&net->d_valfeat, val_bytes) != hipSuccess)
+    if (!net->d_store16.alloc(store_bytes) || !net->d_store_raw.alloc(raw_bytes) || !net->d_valfeat.alloc(val_bytes))
         return net_fail(RZ_ERR_OOM, "hipMalloc failed (deferred-priors store)");
     // the K tail of a tile's last K-step, the rows of boards that do not exist and the padding of the value rows are never
     // written: they must read as finite values (they meet zero weights, or rows nobody reads)
-    if (hipMemset(net->d_store16, 0, store_bytes) != hipSuccess || hipMemset(net->d_valfeat, 0, val_bytes) != hipSuccess)
+    if (!net->d_store16.fill(0) || !net->d_valfeat.fill(0))
         return net_fail(RZ_ERR_HIP, "hipMemset failed (deferred-priors store)");
     net->store_tiles = tiles;
     net->store_slots = slots;
@@ -3543,27 +3293,18 @@ int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const in
     if (n_boards > net->store_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
     if (n_boards > 0) {
         if (!d_stones || !d_to_move || !d_last_cell || !d_slot_of_board) return net_fail(RZ_ERR_ARG, "NULL device pointer");
-        const DeferredOut later{d_slot_of_board, (long long)net->store_tiles * net->dev.groups_act * 1024, net->d_valfeat, net->vf_groups * 4, net->d_trace, net->store_slots};
-        launch_trunk(net, nullptr, net->d_feat, n_boards, stream, LeafBits{d_stones, d_to_move, d_last_cell}, later);
+        launch_trunk(net, nullptr, net->d_feat, n_boards, stream, LeafBits{d_stones, d_to_move, d_last_cell}, store_out(net, d_slot_of_board, true));
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the split-f16 trunk failed");
     }
-    memset(out, 0, sizeof(*out));
-    out->valfeat = net->d_valfeat;
-    out->w1t = net->d_w1t;
-    out->b1 = net->dev.fc_val1_b;
-    out->w2 = net->dev.fc_val2_w;
-    out->b2 = net->dev.fc_val2_b;
-    out->ld = net->vf_groups * 4;
-    out->groups = net->vf_groups;
+    *out = value_head_of(net);
     return RZ_OK;
 }
 
 // policy == false: rz_net_search_resident_values (policy on demand: k_delta_res<false> or a refusal)
 static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream, bool policy) {
     rzt::Dev dev;
-    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    int rc = engine_view(net, engine, &dev);
     if (rc != RZ_OK) return rc;
-    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (n_sims < 1) return net_fail(RZ_ERR_ARG, "rz_net_search_resident: n_sims must be positive");
     // a game's leaves go to store slots pend[g] .. pend[g] + n_sims - 1: more simulations than either side has slots can never fit
     // (and a leaf whose slot lies beyond the store is not written: the tree code flags its game RZ_FLAG_INTERNAL)
@@ -3579,7 +3320,7 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
                                     "kernel) or of up to 10 x 10 (k_trunk_split with one N-tile per wave)");
     if (dev.K != 1 || dev.score_mode != RZ_SCORE_UCT_REF || dev.pend_cap <= 0)
         return net_fail(RZ_ERR_ARG, "the resident search is the deferred-priors route: RZ_SCORE_UCT_REF, one simulation in flight, rz_deferred_reserve first");
-    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || dev.A != net->dev.A) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if ((rc = same_board(net, dev, true)) != RZ_OK) return rc;
     // receptive-field evaluation (rz_net_delta_reserve for this many games, the default trunk on a board of 11 .. 16 rows and columns):
     // k_delta_res, TWO workgroups per CU; rz_net_delta_resident(net, 0) keeps k_trunk_rows_res
     const bool delta_res = net->delta_resident && delta_covers(net) && net->base_games >= dev.n_games;
@@ -3595,13 +3336,7 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     if (rows ? (net->vf_groups != 64 && net->vf_groups != 128) : net->vf_groups > 64) return net_fail(RZ_ERR_INTERNAL, "value head groups");
     ResArgs<true> res;
     res.E = dev;
-    memset(&res.vh, 0, sizeof(res.vh));
-    res.vh.w1t = net->d_w1t;
-    res.vh.b1 = net->dev.fc_val1_b;
-    res.vh.w2 = net->dev.fc_val2_w;
-    res.vh.b2 = net->dev.fc_val2_b;
-    res.vh.ld = net->vf_groups * 4;
-    res.vh.groups = net->vf_groups;
+    res.vh = value_head_of(net, false);
     res.n_sims = n_sims;
     res.select_first = select_first ? 1 : 0;
     // rz_set_playouts: a game with fewer simulations leaves the slots pend[g] + sims_of[g] .. of the feature store as they were
@@ -3609,7 +3344,7 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     // the GEMM raises no range flag (only the trunk's stores do) -- and what it computes there is IGNORED: k_deferred_priors reads the
     // slots below pend[g] only, and pend[g] counts the leaves the game stored.
     if ((rc = rz_playouts_view(engine, &res.sims_of, &res.order)) != RZ_OK) return rc;
-    const DeferredOut later{dev.pend, (long long)net->store_tiles * net->dev.groups_act * 1024, nullptr, 0, nullptr, net->store_slots};
+    const DeferredOut later = store_out(net, dev.pend, false);
     const LeafBits leaves{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last};
     const dim3 grid((unsigned)dev.n_games);
     const hipStream_t st = (hipStream_t)stream;
@@ -3621,7 +3356,7 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         if (select_first) {   // a search begins: the bases of its roots (a continued search finds them, or takes the route without)
             if ((rc = rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream)) != RZ_OK) return rc;
         }
-        dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, net->d_delta_stats, 0, (65536 + net->dev.BW - 1) / net->dev.BW, net->d_win};
+        const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, true, 0, net->d_win);
         if (policy) dl::k_delta_res<true><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
         else dl::k_delta_res<false><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (k_delta_res) failed");
@@ -3649,21 +3384,19 @@ int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims
 int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream) {
     if (!kept) return net_fail(RZ_ERR_ARG, "NULL argument");
     rzt::Dev dev;
-    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    int rc = engine_view(net, engine, &dev);
     if (rc != RZ_OK) return rc;
-    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (!kept->rows || !kept->count) return net_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
     if (!delta_covers(net) || net->base_games < dev.n_games || !split_trunk_ok(net))
         return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the receptive-field trunk (the default trunk on a board of 11 .. 16 rows and columns) and "
                                     "rz_net_delta_reserve for the engine's games");
-    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || dev.A != net->dev.A) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if ((rc = same_board(net, dev, true)) != RZ_OK) return rc;
     if (dev.pend_cap <= 0 || dev.pend_stones == nullptr || dev.pend_lw == nullptr) return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: rz_deferred_reserve first");
     // a listed row addresses slot rows[i] / n_games of the store (the kernel skips a slot beyond it) and the game's tile
     if (kept->n_games != dev.n_games || dev.n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)dev.pend_cap * dev.n_games)
         return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the rows are not this engine's, or more boards than rz_net_deferred_reserve()d");
-    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, nullptr, 0, (65536 + net->dev.BW - 1) / net->dev.BW, nullptr};
-    const dl::PolicyRows pr{kept->rows, kept->count, dev.pend_stones, dev.pend_lw, dev.n_games, net->store_slots,
-                            (long long)net->store_tiles * net->dev.groups_act * 1024};
+    const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, false, 0);
+    const dl::PolicyRows pr{kept->rows, kept->count, dev.pend_stones, dev.pend_lw, dev.n_games, net->store_slots, store_stride(net)};
     const dim3 grid((unsigned)(2 * (net->n_cus > 0 ? net->n_cus : 1)));   // fixed: two workgroups per CU, striding over the device's count
     dl::k_trunk_policy_rows<<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, net->d_store16, da, pr);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_policy_rows failed");
@@ -3681,26 +3414,22 @@ int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
     if (!net->d_win) {   // the window table of the net's board (k_delta_res's leaf_windows)
         std::vector<uint64_t> win(rzw::kEntries);
         rzw::window_table(win.data(), net->dev.BH, net->dev.BW);
-        if (hipMalloc((void **)&net->d_win, win.size() * sizeof(uint64_t)) != hipSuccess) return net_fail(RZ_ERR_OOM, "hipMalloc failed (window table)");
+        if (!net->d_win.alloc(win.size() * sizeof(uint64_t))) return net_fail(RZ_ERR_OOM, "hipMalloc failed (window table)");
         if (hipMemcpy(net->d_win, win.data(), win.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
             return net_fail(RZ_ERR_HIP, "hipMemcpy failed (window table)");
     }
-    if (net->d_base_hdr) (void)hipFree(net->d_base_hdr);
-    if (net->d_base_recs) (void)hipFree(net->d_base_recs);
-    if (net->d_base_ones) (void)hipFree(net->d_base_ones);
-    net->d_base_ones = nullptr;
-    net->d_base_hdr = nullptr;
-    net->d_base_recs = nullptr;
+    net->d_base_hdr.release();
+    net->d_base_recs.release();
+    net->d_base_ones.release();
     net->base_games = 0;
     const size_t hdr_bytes = (size_t)n_games * sizeof(dl::BaseHdr), rec_bytes = (size_t)n_games * 2 * dl::kBaseBytes;
-    if (hipMalloc((void **)&net->d_base_hdr, hdr_bytes) != hipSuccess || hipMalloc((void **)&net->d_base_recs, rec_bytes) != hipSuccess ||
-        hipMalloc((void **)&net->d_base_ones, (size_t)n_games) != hipSuccess)
+    if (!net->d_base_hdr.alloc(hdr_bytes) || !net->d_base_recs.alloc(rec_bytes) || !net->d_base_ones.alloc((size_t)n_games))
         return net_fail(RZ_ERR_OOM, "hipMalloc failed (base cache)");
-    if (hipMemset(net->d_base_ones, 1, (size_t)n_games) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
-    if (!net->d_delta_stats && hipMalloc((void **)&net->d_delta_stats, 8 * sizeof(unsigned)) != hipSuccess)
+    if (!net->d_base_ones.fill(1)) return net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
+    if (!net->d_delta_stats && !net->d_delta_stats.alloc(8 * sizeof(unsigned)))
         return net_fail(RZ_ERR_OOM, "hipMalloc failed (delta counters)");
     // valid = 0: a leaf of a game without bases takes the four passes without a base
-    if (hipMemset(net->d_base_hdr, 0, hdr_bytes) != hipSuccess || hipMemset(net->d_delta_stats, 0, 8 * sizeof(unsigned)) != hipSuccess)
+    if (!net->d_base_hdr.fill(0) || !net->d_delta_stats.fill(0))
         return net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->base_games = n_games;
     return RZ_OK;
@@ -3727,10 +3456,9 @@ int rz_net_delta_bases(rz_net *net, const uint64_t *d_root_stones, const int32_t
     if (!delta_covers(net)) return net_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
     if (n_games > net->base_games) return net_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
     if (!d_root_stones || !d_root_to_move) return net_fail(RZ_ERR_ARG, "NULL device pointer");
-    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, net->d_base_ones, nullptr, nullptr, 1, (65536 + net->dev.BW - 1) / net->dev.BW};
-    const DeferredOut none{nullptr, 0, nullptr, 0, nullptr, 0};
+    const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, false, 1);
     dl::k_trunk_delta<false><<<dim3((unsigned)(2 * n_games)), dim3(256), 0, (hipStream_t)stream>>>(
-        net->dev, LeafBits{d_root_stones, d_root_to_move, nullptr}, nullptr, 2 * n_games, none, da);
+        net->dev, LeafBits{d_root_stones, d_root_to_move, nullptr}, nullptr, 2 * n_games, no_store(), da);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta (bases) failed");
     return RZ_OK;
 }
@@ -3747,9 +3475,8 @@ int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
     if (n_boards > 0) {
         if (!d_stones || !d_to_move || !d_last_cell) return net_fail(RZ_ERR_ARG, "NULL device pointer");
         if (!d_slot_of_board && !d_feat32) return net_fail(RZ_ERR_ARG, "rz_net_delta_leaves: neither a store slot nor an f32 buffer to write to");
-        const DeferredOut later{d_slot_of_board, (long long)net->store_tiles * net->dev.groups_act * 1024, net->d_valfeat, net->vf_groups * 4,
-                                net->d_trace, net->store_slots};
-        dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, d_active ? d_active : net->d_base_ones, d_feat32, net->d_delta_stats, without_base ? 2 : 0, (65536 + net->dev.BW - 1) / net->dev.BW};
+        const DeferredOut later = store_out(net, d_slot_of_board, true);
+        const dl::DeltaArgs da = delta_args(net, d_active, d_feat32, true, without_base ? 2 : 0);
         const dim3 grid((unsigned)n_boards);
         _Float16 *store = d_slot_of_board ? net->d_store16 : nullptr;
         if (d_slot_of_board) net->feat16_valid = net->feat32_valid = false;
@@ -3759,16 +3486,7 @@ int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
             dl::k_trunk_delta<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, LeafBits{d_stones, d_to_move, d_last_cell}, store, n_boards, later, da);
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta failed");
     }
-    if (out) {
-        memset(out, 0, sizeof(*out));
-        out->valfeat = net->d_valfeat;
-        out->w1t = net->d_w1t;
-        out->b1 = net->dev.fc_val1_b;
-        out->w2 = net->dev.fc_val2_w;
-        out->b2 = net->dev.fc_val2_b;
-        out->ld = net->vf_groups * 4;
-        out->groups = net->vf_groups;
-    }
+    if (out) *out = value_head_of(net);
     return RZ_OK;
 }
 
@@ -3776,22 +3494,20 @@ int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
 // slot pend[g], games whose active flag is 0 skipped)
 int rz_net_delta_bases_engine(rz_net *net, rz_engine *engine, void *stream) {
     rzt::Dev dev;
-    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    int rc = engine_view(net, engine, &dev);
     if (rc != RZ_OK) return rc;
-    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
-    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
     return rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream);
 }
 
 int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *stream) {
     rzt::Dev dev;
-    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    int rc = engine_view(net, engine, &dev);
     if (rc != RZ_OK) return rc;
-    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
     if (dev.K != 1 || dev.pend_cap <= 0 || dev.pend == nullptr)
         return net_fail(RZ_ERR_ARG, "rz_net_delta_step is the deferred-priors route: one simulation in flight, rz_deferred_reserve first");
-    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
     return rz_net_delta_leaves(net, dev.leaf_stones, dev.leaf_to_move, dev.leaf_last, dev.n_games, dev.pend, dev.active, nullptr, 0, out, stream);
 }
 
@@ -3799,25 +3515,21 @@ int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *
 // (policy and value K-steps of the FC GEMM: rz_net_heads_gemm next) -- the three-launch step (PUCT) on boards of 11 .. 16 rows.
 int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream) {
     rzt::Dev dev;
-    int rc = rz_device_view(engine, &dev, (int64_t)sizeof(dev));
+    int rc = engine_view(net, engine, &dev);
     if (rc != RZ_OK) return rc;
-    if ((rc = net_ready(net, dev.n_games)) != RZ_OK) return rc;
     if (!delta_covers(net)) return net_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
     if (dev.K != 1) return net_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine: one simulation in flight per tree (a base per game)");
-    if (dev.BH != net->dev.BH || dev.BW != net->dev.BW) return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
     if (dev.n_games > net->base_games) return net_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
     if (dev.n_games > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
     if (net->heads_algo == RZ_NET_HEADS_F32) return net_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine writes the f16 tiles only (RZ_NET_HEADS_F32 reads f32 features: rz_net_trunk_leaves)");
     net->feat16_valid = true;
     net->feat32_valid = false;
     net->raw_from_trunk = false;
-    net->dev.feat_ld = 16 * (net->dev.groups_act + net->dev.groups_val);
-    net->dev.feat_val_off = 16 * net->dev.groups_act;
-    const DeferredOut later{nullptr, 0, nullptr, 0, nullptr, 0};
-    dl::DeltaArgs da{net->d_base_hdr, net->d_base_recs, dev.active ? dev.active : net->d_base_ones, nullptr, net->d_delta_stats, 0,
-                     (65536 + net->dev.BW - 1) / net->dev.BW};
+    use_internal_feat_layout(net);
+    const dl::DeltaArgs da = delta_args(net, dev.active, nullptr, true, 0);
     dl::k_trunk_delta<false><<<dim3((unsigned)dev.n_games), dim3(256), 0, (hipStream_t)stream>>>(
-        net->dev, LeafBits{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last}, net->d_feat16, dev.n_games, later, da);
+        net->dev, LeafBits{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last}, net->d_feat16, dev.n_games, no_store(), da);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta failed");
     return RZ_OK;
 }
@@ -3847,14 +3559,13 @@ int rz_net_deferred_gemm(rz_net *net, int32_t n_boards, int32_t n_slots, rz_defe
     if (n_slots > 0 && n_boards > 0) {
         // the store is a list of n_slots * store_tiles tiles of groups_act K-steps each: k_heads_split's policy groups over all of
         // them (64 boards x 128 outputs per workgroup, the K quarters over its four waves: the bits of every other shape)
-        NetDev nd = net->dev;
-        nd.groups_val = 0;   // a tile of the store holds the policy K-steps only
-        const int n_act_tiles = nd.Npad / 32, n_groups = (n_act_tiles + 3) / 4;
-        if (n_groups > 2) return net_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
+        NetDev nd;
+        int n_groups = 0;
+        if ((rc = policy_store_dev(net, &nd, &n_groups)) != RZ_OK) return rc;
         const size_t pairs = (size_t)n_slots * net->store_tiles / 2;   // workgroups per output group: two board tiles each
         const dim3 grid((unsigned)(n_groups == 2 ? 2 * ((pairs + 7) / 8 * 8) : pairs));
         k_heads_split<2, 4, 3, false, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(
-            nd, reinterpret_cast<const f32x4 *>(net->d_store16), net->d_store_raw, nullptr, n_slots * net->store_tiles * 32);
+            nd, reinterpret_cast<const f32x4 *>(net->d_store16.p), net->d_store_raw, nullptr, n_slots * net->store_tiles * 32);
         if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_split failed");
     }
     out->raw = net->d_store_raw;
@@ -3871,13 +3582,12 @@ int rz_net_deferred_gemm_rows(rz_net *net, const rz_kept_rows *kept, rz_deferred
     // a listed row addresses slot rows[i] / n_games < capacity / n_games of the store, and logits row i < capacity exists
     if (kept->n_games < 1 || kept->n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)net->store_slots * kept->n_games)
         return net_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
-    NetDev nd = net->dev;
-    nd.groups_val = 0;   // a tile of the store holds the policy K-steps only
-    const int n_act_tiles = nd.Npad / 32, n_groups = (n_act_tiles + 3) / 4;
-    if (n_groups > 2) return net_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
+    NetDev nd;
+    int n_groups = 0;
+    if ((rc = policy_store_dev(net, &nd, &n_groups)) != RZ_OK) return rc;
     // one workgroup per CU (`part` is 128 KB of its LDS), whole groups of 16 (k_heads_rows: the output groups of a block 8 apart)
     const dim3 grid((unsigned)(((net->n_cus > 16 ? net->n_cus : 16) + 15) / 16 * 16));
-    k_heads_rows<2, 4, 3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(nd, reinterpret_cast<const f32x4 *>(net->d_store16), net->d_store_raw,
+    k_heads_rows<2, 4, 3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(nd, reinterpret_cast<const f32x4 *>(net->d_store16.p), net->d_store_raw,
                                                                      kept->rows, kept->count, kept->n_games, net->store_tiles);
     if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_rows failed");
     out->raw = net->d_store_raw;
