@@ -339,6 +339,7 @@ struct Leaf {
     float *vdst;              // the value head's input row (global memory, or LDS in the resident search)
     float *dst32;             // f32 features (tests; NULL otherwise)
     const uint64_t *sets;     // delta_passes<true>: pass -1's window sets, handed over in LDS (leaf_windows)
+    uint16_t *gtab;           // delta_passes<true>: THIS wave's table of the base records it copies (rz_gather.h: rzg::kTabEntries entries of LDS)
     bool deferred, store_head;
 };
 struct Layers {
@@ -388,6 +389,14 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
     return ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
+// set bits of a word (the same in every lane) below this lane's bit: rzg::below(word, lane)
+__device__ __forceinline__ int lane_below(uint64_t word) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(word >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)word, 0u));
+}
+static_assert(rzg::kC1Max == kC1Slots && rzg::kC2Max == kC2Slots && rzg::kC1Bytes * kCells == (int)kBaseC2 && rzg::kOutside == kOutside,
+              "rz_gather.h's records are the base's and the budget is this file's");
+static_assert(rzg::kC1Bytes <= P1 && rzg::kC2Bytes <= P2, "a record fits its LDS slot");
+
 // The passes of one leaf: -1 = against the base (use_delta), 0 .. 3 = the board's quadrants without one.  -> tiles computed: conv3 | conv2 << 16.
 // SETS (k_delta_res): pass -1 takes its cell sets, ranks and totals from leaf.sets (leaf_windows) instead of the distances and ballots.
 // OLO, OHI: the head planes this leaf is evaluated for (conv3_tiles; the base's values of the others are not requested either) -- all six,
@@ -428,55 +437,14 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         bool f[5];
         uint64_t own[5];   // (SETS, pass -1: set k = the window of radius th[k] handed over by the selection; the wave's word of it)
         const bool handed = SETS && pass < 0;   // (uniform)
+        int rank[5], tot[5];
         if (handed) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
                 own[k] = uni64(leaf.sets[4 * (th[k] - 1) + wave]);
                 f[k] = (own[k] >> lane) & 1ull;   // (cells past the board: no bit)
             }
-        } else {
-            // ---- the distance of this thread's cell to the changed cells (delta) / to the pass's quadrant
-            const int dist = cell_dist(cy, cx, pass, dys, dxs, BH, BW);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) f[k] = is_cell && dist <= th[k];
-        }
-        // the records conv2 / conv3 read but this leaf does not recompute come from the base: requested NOW, straight into the
-        // registers they are stored from (no barrier lies between, DESIGN.md section 3).  Every load is issued by every thread --
-        // a load under a branch makes hipcc wait for every outstanding load first --; a thread that holds no such record reads
-        // past the end of a buffer resource instead, which returns zeros without touching memory.
-        const bool g1 = pass < 0 && f[3] && !f[0], g2 = pass < 0 && f[4] && !f[1];
-        const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, kBaseBytes, 0x00020000);
-        f32x4 r1[8], r2[16];
-        {
-            const int o1 = g1 ? tid * 128 : kOutside, o2 = g2 ? (int)kBaseC2 + tid * 256 : kOutside;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r1[i] = load_rec(b_rsrc, o1 + 16 * i);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) r2[i] = load_rec(b_rsrc, o2 + 16 * i);
-        }
-        float bv[6];   // ... and, behind them (the copies' waits do not include these), the features of a cell outside conv3's window
-        {
-            const int ov = pass < 0 && is_cell && !f[2] ? (int)kBaseV + tid * 4 : kOutside;
-#pragma unroll
-            for (int o = OLO; o < OHI; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
-        }
-        // (conv1's weights and the biases: requested per pass, so that nothing of them is live across conv3)
-        sp::f16x8 a1[3][2];
-        f32x4 bias1[4];
-        if (32 * wave < 32 * kT1) {
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int p_ = 0; p_ < 2; ++p_) a1[ky][p_] = __builtin_bit_cast(sp::f16x8, nd.s1[(ky * 2 + p_) * 64 + lane]);
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) bias1[gg] = *reinterpret_cast<const f32x4 *>(nd.b1 + 8 * gg + 4 * (lane >> 5));
-        }
-        f32x4 bias2 = *reinterpret_cast<const f32x4 *>(nd.b2 + 16 * wave + 4 * g);
-        // ranks and totals without a barrier: every wave evaluates the membership of all four 64-cell blocks (its own block's ballots
-        // give the ranks inside the wave, the blocks before it the offsets); the same values in every wave, so the budget test is uniform
-        // (SETS, pass -1: the handed-over words' popcounts give the same)
-        int rank[5], tot[5];
-        if (handed) {
+            // ranks and totals: the handed-over words' popcounts (before the requests: conv1's weights depend on its total)
             const int *cnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
@@ -491,6 +459,104 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
                 tot[k] = all;
             }
         } else {
+            // ---- the distance of this thread's cell to the changed cells (delta) / to the pass's quadrant
+            const int dist = cell_dist(cy, cx, pass, dys, dxs, BH, BW);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) f[k] = is_cell && dist <= th[k];
+        }
+        // the records conv2 / conv3 read but this leaf does not recompute come from the base: requested NOW, straight into the
+        // registers they are stored from (no barrier lies between, DESIGN.md section 3).  Every load is issued by every thread --
+        // a load under a branch makes hipcc wait for every outstanding load first --; a thread that holds no such record reads
+        // past the end of a buffer resource instead, which returns zeros without touching memory.
+        // SETS, pass -1: the same bytes record by record (rz_gather.h) -- the lanes of a wave-instruction read whole records, 8 (conv1) or
+        // 16 (conv2) lanes each, so a 128-byte line is touched once, and 4 + 11 requests a wave replace the 8 + 16.  Which record a lane
+        // group copies comes from the wave's own table: lane L writes the entries of its held cells L, 64 + L, 128 + L, 192 + L that
+        // fall to this wave, the wave reads the entries of its rounds back (its LDS operations complete in order: no barrier).
+        const bool g1 = pass < 0 && f[3] && !f[0], g2 = pass < 0 && f[4] && !f[1];
+        const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, kBaseBytes, 0x00020000);
+        f32x4 r1[8], r2[16];
+        f32x4 q1[rzg::kC1Rounds], q2[rzg::kC2Rounds];
+        uint32_t d1[rzg::kC1Rounds], d2[rzg::kC2Rounds];   // where a round's 16 bytes go (no record: the zeros it was answered, to the zero record)
+        if constexpr (SETS) {
+            // (no branch around requests or stores: the passes without a base -- handed false -- go through the same instructions
+            // with no record anywhere, as they went through the cell-by-cell requests)
+            uint16_t *tab = leaf.gtab;
+            // (all sixteen words first, in one batch of LDS reads; they stay in vector registers -- the same value in every lane --:
+            // nothing here needs them in scalar ones)
+            uint64_t ws[rzw::kRadii][rzg::kWords];
+#pragma unroll
+            for (int r = 0; r < rzw::kRadii; ++r)
+#pragma unroll
+                for (int w = 0; w < rzg::kWords; ++w) ws[r][w] = leaf.sets[4 * r + w];
+            int n1 = 0, s1 = 0, n2 = 0, s2 = 0;   // held records / slots in the words before this one (the same in every lane)
+#pragma unroll
+            for (int w = 0; w < rzg::kWords; ++w) {
+                const uint64_t h1 = rzg::held(ws[2][w], ws[0][w]), h2 = rzg::held(ws[3][w], ws[1][w]);
+                const int cell = 64 * w + lane;
+                const int p1 = rzg::c1_place(n1 + lane_below(h1), wave), p2 = rzg::c2_place(n2 + lane_below(h2), wave);
+                const uint16_t e1 = rzg::entry(cell, s1 + lane_below(ws[2][w])), e2 = rzg::entry(cell, s2 + lane_below(ws[3][w]));
+                if (handed && ((h1 >> lane) & 1ull) && p1 >= 0) tab[p1] = e1;
+                if (handed && ((h2 >> lane) & 1ull) && p2 >= 0) tab[p2] = e2;
+                n1 += rzg::popcount(h1), s1 += rzg::popcount(ws[2][w]);
+                n2 += rzg::popcount(h2), s2 += rzg::popcount(ws[3][w]);
+            }
+            const uint32_t c1a = lds_addr(c1), c2a = lds_addr(c2);
+#pragma unroll
+            for (int i = 0; i < rzg::kC1Rounds; ++i) {
+                const int j = rzg::c1_record(i, wave, lane), chunk = rzg::c1_chunk(lane);
+                const uint16_t e = tab[rzg::c1_index(j)];
+                const bool has = handed && rzg::c1_has(j, n1);
+                d1[i] = has ? c1a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P1) : zaddr + 16u * (uint32_t)chunk;
+                q1[i] = load_rec(b_rsrc, rzg::c1_src(has, rzg::entry_cell(e), chunk));
+            }
+#pragma unroll
+            for (int i = 0; i < rzg::kC2Rounds; ++i) {
+                const int j = rzg::c2_record(i, wave, lane), chunk = rzg::c2_chunk(lane);
+                const uint16_t e = tab[rzg::c2_index(j)];
+                const bool has = handed && rzg::c2_has(j, n2);
+                d2[i] = has ? c2a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P2) : zaddr + 16u * (uint32_t)chunk;
+                q2[i] = load_rec(b_rsrc, rzg::c2_src(has, rzg::entry_cell(e), chunk, (int)kBaseC2));
+            }
+        } else {
+            const int o1 = g1 ? tid * 128 : kOutside, o2 = g2 ? (int)kBaseC2 + tid * 256 : kOutside;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) r1[i] = load_rec(b_rsrc, o1 + 16 * i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) r2[i] = load_rec(b_rsrc, o2 + 16 * i);
+        }
+        float bv[6];   // ... and, behind them (the copies' waits do not include these), the features of a cell outside conv3's window
+        {
+            const int ov = pass < 0 && is_cell && !f[2] ? (int)kBaseV + tid * 4 : kOutside;
+#pragma unroll
+            for (int o = OLO; o < OHI; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
+        }
+        // (conv1's weights and the biases: requested per pass, so that nothing of them is live across conv3)
+        // (SETS, pass -1: a wave without a conv1 tile -- the total is handed over -- requests them past the end of their buffers)
+        sp::f16x8 a1[3][2];
+        f32x4 bias1[4];
+        if constexpr (SETS) {
+            const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4 *>(nd.s1), 0, 6 * 64 * 16, 0x00020000);
+            const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(nd.b1), 0, 32 * 4, 0x00020000);
+            const bool runs = !handed || 32 * wave < tot[0];   // (uniform)
+            const int so = runs ? lane * 16 : kOutside, bo = runs ? 16 * (lane >> 5) : kOutside;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int p_ = 0; p_ < 2; ++p_) a1[ky][p_] = sp::load_w(s_rsrc, so, (ky * 2 + p_) * 1024);
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) bias1[gg] = load_rec(o_rsrc, bo + 32 * gg);
+        } else if (32 * wave < 32 * kT1) {
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int p_ = 0; p_ < 2; ++p_) a1[ky][p_] = __builtin_bit_cast(sp::f16x8, nd.s1[(ky * 2 + p_) * 64 + lane]);
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) bias1[gg] = *reinterpret_cast<const f32x4 *>(nd.b1 + 8 * gg + 4 * (lane >> 5));
+        }
+        f32x4 bias2 = *reinterpret_cast<const f32x4 *>(nd.b2 + 16 * wave + 4 * g);
+        // ranks and totals without a barrier: every wave evaluates the membership of all four 64-cell blocks (its own block's ballots
+        // give the ranks inside the wave, the blocks before it the offsets); the same values in every wave, so the budget test is uniform
+        if (!handed) {
             int before[5] = {0, 0, 0, 0, 0}, all[5] = {0, 0, 0, 0, 0};
             unsigned long long own[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
 #pragma unroll
@@ -533,13 +599,20 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         if (f[2]) list3[rank[2]] = (uint16_t)mypos;
         if (pass <= 0 && is_cell) *reinterpret_cast<f16x4 *>(in0 + ((cy + 1) * sp::kInCols + (cx + 1)) * 8) = cell_planes;
         if (pass <= 0 && store_head && tid < 226) reinterpret_cast<f32x4 *>(headw)[tid] = headv;
-        if (g1) {
+        if constexpr (SETS) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) *(lds_v4)(uintptr_t)(rec1 + 16 * i) = r1[i];
-        }
-        if (g2) {
+            for (int i = 0; i < rzg::kC1Rounds; ++i) *(lds_v4)(uintptr_t)d1[i] = q1[i];
 #pragma unroll
-            for (int i = 0; i < 16; ++i) *(lds_v4)(uintptr_t)(rec2 + 16 * i) = r2[i];
+            for (int i = 0; i < rzg::kC2Rounds; ++i) *(lds_v4)(uintptr_t)d2[i] = q2[i];
+        } else {
+            if (g1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) *(lds_v4)(uintptr_t)(rec1 + 16 * i) = r1[i];
+            }
+            if (g2) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) *(lds_v4)(uintptr_t)(rec2 + 16 * i) = r2[i];
+            }
         }
         __builtin_amdgcn_sched_barrier(0);   // (the requests below stay behind the stores of the base's records: their 96 registers are free again)
         f16x8 a2[9][1][2];   // conv2's weight fragments: requested here, conv1 -- one wave's work -- covers their latency
@@ -821,7 +894,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (mode != 1 && !deferred && feat16 != nullptr)   // rz_net_delta_trunk_engine: the FC GEMM's own tiles (policy and value K-steps), as trunk_rows_body writes them
         leaf.dst16 = feat16 + ((size_t)(board >> 5) * (nd.groups_act + nd.groups_val) * 1024 + (board & 31) * 16);
     leaf.dst32 = (mode != 1 && da.feat32 != nullptr) ? da.feat32 + (size_t)board * 6 * S : nullptr;
-    leaf.sets = nullptr;
+    leaf.sets = nullptr, leaf.gtab = nullptr;
     leaf.deferred = deferred;
     leaf.store_head = true;
 
@@ -982,6 +1055,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     __shared__ float res_vrow[kResVrow];
     __shared__ float res_part[rzt::kDefWaves][rzt::kWave];
+    static_assert(rzg::kTabEntries * 2 <= rzt::kWave * 4, "a wave's gather table lies in its row of the K-quarter sums");
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
@@ -1083,6 +1157,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         const int parity = (verdict >> 1) & 1, nD = verdict >> 8;
         Leaf leaf;
         leaf.sets = res_win;
+        leaf.gtab = reinterpret_cast<uint16_t *>(res_part[wave]);   // (the K-quarter sums: dead from the selection to the value layer)
 #pragma unroll
         for (int i = 0; i < kMaxD; ++i) leaf.dys[i] = leaf.dxs[i] = -100;   // (pass -1 reads the sets; the passes without a base, no cells)
         leaf.base = da.recs + ((size_t)game * 2 + parity) * kBaseBytes;
@@ -1244,7 +1319,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_policy_rows(NetDev nd, _Float1
         leaf.dst16 = store16 + (size_t)slot * pr.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16;
         leaf.vdst = nullptr;
         leaf.dst32 = nullptr;
-        leaf.sets = nullptr;
+        leaf.sets = nullptr, leaf.gtab = nullptr;
         leaf.deferred = false;
         leaf.store_head = first;
         first = false;

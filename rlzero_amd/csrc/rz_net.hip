@@ -46,6 +46,7 @@
 #include "rz_pack.h"
 #include "rz_trace.h"
 #include "rz_tree.h"
+#include "rz_gather.h"
 #include "rz_window.h"
 
 void rz_set_error(const char *msg);  // rz_engine.hip
