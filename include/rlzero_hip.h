@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 32
+#define RZ_ABI_VERSION 33
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -424,6 +424,15 @@ int rz_step_games(rz_engine *e, const int32_t *d_moves, int32_t *d_winner, uint8
  * and k_play_draw sets RZ_PLAY_FULL on the searched records of full searches.  Only those are policy training samples; every
  * game still gives a value target.  Dirichlet noise and temperature are the same on both kinds of move.
  *
+ * Per-ply temperature (AlphaGo Zero / AlphaZero: T = 1 for the first 30 plies, then T -> 0; KataGo: T decaying with a half-life of
+ * about the board size; an opt-in extension, off after every rz_play_attach; ABI 33).  rz_play_set_temperatures hands over a host
+ * table: T before ply p, the last entry for every later ply.  The library forms 1 / T on the host -- the IEEE division of
+ * rz_play_attach's 1 / temperature, and Python's --, pads the table to the board's cell count and writes it in stream order into a
+ * device array of its own, which k_play_draw indexes with the slot's ply (word [2] of the record: T follows from it, no record
+ * word or flag changes).  The stall margin follows the ply: the configured stall_margin if positive, else 1e-10 * max(1, 1 / T)
+ * with the ply's T.  A stalled slot keeps its ply, so the resolved move belongs to the same T.  The host forms pi and verifies
+ * every move with the same table.  Noise and the search are untouched; a match keeps the temperature of rz_play_attach.
+ *
  * Slots refill themselves: a slot whose game has ended (or that is idle) takes the next entry of a queue of game ids shared by
  * the engines (lanes) of a GPU -- d_queue_ids int64 [..], d_queue_ctl int32 [2] = {head, entries valid}; the device advances
  * head atomically, the host may append ids and then raise the count -- and starts that game: empty board, player 0 to move, a
@@ -488,6 +497,14 @@ int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, voi
  * since rz_play_attach has no cap (capture again).  While a cap is set the step-by-step tree calls (rz_tree_step*,
  * rz_expand_backup*) return RZ_ERR_ARG: only rz_net_search_resident knows per-game budgets. */
 int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream);
+/* The temperature schedule (above): h_temps double [n] in HOST memory, T before ply p; plies >= n use h_temps[n - 1].  The table
+ * travels as kernel arguments of small launches on `stream` that write the engine's device array -- not a kernel argument of the
+ * draw: a captured move graph takes a new table without a new capture.  n == 0 (h_temps ignored): off again, every ply at
+ * rz_play_attach's temperature, the same bits as before.  RZ_ERR_ARG for an entry that is not finite and positive, for n above the
+ * board's cell count (rows x cols -- a game has no more plies; Connect4 too, whatever its action count) and while a match is on.
+ * Valid after rz_play_attach; a graph captured before the FIRST call since rz_play_attach keeps the constant temperature (capture
+ * again). */
+int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, void *stream);
 /* Whether the cap's searches take their workgroups in the partition's order (default) or in slot order (0: no order kernel in the
  * move step; a measurement's switch).  A host-side setting read when launches are enqueued: set it before a move graph is captured. */
 int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
@@ -495,7 +512,8 @@ int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
  * [n_openings], device memory -- is copied on `stream` into the engine's own; launches enqueued after the call read it.
  * n_openings == 0 (pointers ignored): off again.  Valid after rz_play_attach, before the games are queued, on an engine without
  * Dirichlet noise on the resident search's route (RZ_SCORE_UCT_REF, sims_in_flight == 1), with neither resignation nor a playout
- * cap set since rz_play_attach: RZ_ERR_ARG otherwise -- and rz_play_set_resign / rz_play_set_cap return RZ_ERR_ARG while it is on.
+ * cap nor a temperature schedule set since rz_play_attach: RZ_ERR_ARG otherwise -- and rz_play_set_resign / rz_play_set_cap /
+ * rz_play_set_temperatures return RZ_ERR_ARG while it is on.
  * Like theirs, the flag is a kernel argument: with it off the move step reads and writes nothing more than before. */
 int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t *d_open_to_move, const int32_t *d_open_last, int32_t n_openings,
                       void *stream);

@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -149,6 +149,7 @@ _SIGNATURES = {
     'rz_play_apply': (c_int, [P, P]),
     'rz_play_set_resign': (c_int, [P, c_double, c_double, P]),
     'rz_play_set_cap': (c_int, [P, c_int32, c_double, P]),
+    'rz_play_set_temperatures': (c_int, [P, P, c_int32, P]),
     'rz_set_playouts': (c_int, [P, P, P, P]),
     'rz_playouts_view': (c_int, [P, POINTER(c_void_p), POINTER(c_void_p)]),
     'rz_play_set_cap_order': (c_int, [P, c_int32]),

@@ -1259,11 +1259,15 @@ struct Play {
     const int64_t *queue_ids;
     int32_t *queue_ctl;        // [0] head, [1] entries valid
     int32_t *log;
+    // per-ply temperature (rz_play_set_temperatures): 1 / T before ply p, padded with its last entry to the board's cell count S,
+    // then the stall margin of each ply: the configured one if positive, else 1e-10 * max(1 / T, 1) -- rz_play_attach's rule at the ply's T
+    const double *inv_t_of;    // [2][S]
     int ring, words;
     uint64_t seed;
     double inv_t, margin;
     double *resign;            // [2] {threshold, disabled_frac} (rz_play_set_resign; NaN threshold: off)
     int resign_on;             // rz_play_set_resign called since rz_play_attach: k_play_draw reads `resign` (else never)
+    int temp_on;               // rz_play_set_temperatures called since rz_play_attach: k_play_draw reads `inv_t_of` (else never)
     // playout cap randomization (rz_play_set_cap): a search has n_full simulations when cap_uniform(seed, game id, ply) < p_full,
     // else n_fast
     double *cap;               // [2] {n_fast, p_full} (NaN p_full: off -- every search has n_full)
@@ -1346,6 +1350,12 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     bool legal[kWords];
     double x[kWords];
     double mx = -INFINITY;
+    // the ply's temperature (rz_play_set_temperatures): the table is read only once it has been set; a stalled slot keeps its ply, so
+    // its move is judged at the same T
+    const int ply = Y.ply[g];
+    const int tp = ply < 0 ? 0 : (ply < E.S ? ply : E.S - 1);   // (ply < S always holds)
+    const double inv_t = Y.temp_on ? Y.inv_t_of[tp] : Y.inv_t;
+    const double margin = Y.temp_on ? Y.inv_t_of[E.S + tp] : Y.margin;
     // resignation (rz_play_set_resign): read only once it has been configured -- the rule-free path has no extra memory traffic
     const double thr = Y.resign_on ? Y.resign[0] : NAN;
     const bool rs = !isnan(thr) && state == kPlayRunning;
@@ -1357,12 +1367,11 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         legal[j] = a < E.A && r >= 0;
         cnt[j] = (legal[j] && r < nv) ? R[2 * (fc + r)].x : 0;
         if (a < E.A) rec[RZ_PLAY_RECORD_WORDS + a] = legal[j] ? cnt[j] : -1;
-        x[j] = legal[j] ? Y.inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
+        x[j] = legal[j] ? inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
         mx = fmax(mx, x[j]);
         if (rs && cnt[j] > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)cnt[j]);
     }
     const int64_t gid = Y.game_id[g];
-    const int ply = Y.ply[g];
     if (lane == 0) {
         rec[0] = (int32_t)(uint32_t)(uint64_t)gid;
         rec[1] = (int32_t)((uint64_t)gid >> 32);
@@ -1444,7 +1453,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         }
         double rel = 0.0;
         if (chosen >= 0) rel = fmin(target - below, c - target) / total;
-        const bool ok = chosen >= 0 && total > 0.0 && rel > Y.margin;
+        const bool ok = chosen >= 0 && total > 0.0 && rel > margin;
         rec[6] = __float_as_int((float)rel);
         if (ok) {
             rec[3] = chosen;
@@ -1546,6 +1555,17 @@ __global__ void k_play_cap(Dev E, Play Y, double n_fast, double p_full) {
         Y.cap[0] = n_fast;
         Y.cap[1] = p_full;
     }
+}
+
+// rz_play_set_temperatures: up to kTempChunk entries of the engine's table (1 / T per ply, then the margins), handed over by value -- a
+// write in stream order, so a move graph captured earlier reads the new table from its next replay on
+constexpr int kTempChunk = 64;
+struct TempChunk {
+    double v[kTempChunk];
+};
+__global__ __launch_bounds__(kTempChunk) void k_play_set_temps(double *inv_t_of, TempChunk c, int base, int count) {
+    const int i = threadIdx.x;
+    if (i < kTempChunk && base + i < count) inv_t_of[base + i] = c.v[i];
 }
 
 // The order of k_delta_res's workgroups under per-game budgets: a STABLE partition of the slots -- full budget (>= n_full), fewer
@@ -1668,6 +1688,7 @@ struct rz_engine {
     bool cap_ordered = true;   // rz_play_set_cap_order: k_play_order runs and the resident search follows it
     Keep keep = {};            // the kept flush (rz_deferred_keep): sized by rz_deferred_reserve
     int open_cap = 0;          // rz_play_set_match: openings the engine's copy of the table has room for
+    double play_margin_cfg = 0.0;   // rz_play_config::stall_margin as given (rz_play_set_temperatures: 0 -> the margin follows the ply's T)
 };
 
 namespace {
@@ -2420,6 +2441,11 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
         if (Y.cap == nullptr && (rc = dev_alloc(e, &Y.cap, 2)) != RZ_OK) return rc;
         if (Y.sims_of == nullptr && (rc = dev_alloc(e, &Y.sims_of, G)) != RZ_OK) return rc;
         if (Y.order == nullptr && (rc = dev_alloc(e, &Y.order, G)) != RZ_OK) return rc;
+        if (Y.inv_t_of == nullptr) {
+            double *tab = nullptr;
+            if ((rc = dev_alloc(e, &tab, 2 * e->dev.S)) != RZ_OK) return rc;
+            Y.inv_t_of = tab;
+        }
         if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
     }
     Y.queue_ids = cfg->d_queue_ids;
@@ -2447,6 +2473,8 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
     Y.cap_on = 0;      // (and so is the playout cap: rz_play_set_cap)
     Y.match_on = 0;    // (and match mode: rz_play_set_match)
+    e->play_margin_cfg = cfg->stall_margin;
+    Y.temp_on = 0;     // (and the temperature schedule: rz_play_set_temperatures)
     Y.n_full = e->cfg.n_playout;
     RZ_HIP(hipMemset(Y.step_ab, 0, 8));
     RZ_HIP(hipMemset(Y.ply, 0, (size_t)G * 4));
@@ -2488,6 +2516,32 @@ int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, voi
     k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
     e->play.resign_on = 1;
     return launched("k_play_set_resign");
+}
+
+int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, void *stream) {
+    RZ_ENTER(e);
+    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    Play &Y = e->play;
+    const int S = e->dev.S;
+    if (n < 0 || n > S) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: %d entries for a board of %d cells (a game has no more plies)", n, S);
+    if (n > 0 && h_temps == nullptr) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: NULL table");
+    if (Y.match_on) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: a match is on (rz_play_set_match): its moves keep the temperature of rz_play_attach");
+    for (int p = 0; p < n; ++p)
+        if (!(std::isfinite(h_temps[p]) && h_temps[p] > 0.0))
+            return fail(RZ_ERR_ARG, "rz_play_set_temperatures: entry %d (%g) is not a finite positive temperature", p, h_temps[p]);
+    // 1 / T on the host (the division of rz_play_attach), padded with the last entry; n == 0: the temperature of rz_play_attach.
+    // Behind it each ply's stall margin by rz_play_attach's rule.
+    for (int base = 0; base < 2 * S; base += kTempChunk) {
+        TempChunk c;
+        for (int i = 0; i < kTempChunk; ++i) {
+            const int p = (base + i) % S;
+            const double inv_t = n == 0 ? Y.inv_t : 1.0 / h_temps[p < n ? p : n - 1];
+            c.v[i] = base + i < S ? inv_t : (e->play_margin_cfg > 0.0 ? e->play_margin_cfg : 1e-10 * (inv_t > 1.0 ? inv_t : 1.0));
+        }
+        k_play_set_temps<<<dim3(1), dim3(kTempChunk), 0, as_stream(stream)>>>(const_cast<double *>(Y.inv_t_of), c, base, 2 * S);
+    }
+    Y.temp_on = 1;
+    return launched("k_play_set_temps");
 }
 
 static int playouts_route_ok(rz_engine *e, const char *what) {
@@ -2582,6 +2636,7 @@ int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t
     if (e->dev.K != 1 || e->dev.score_mode != RZ_SCORE_UCT_REF)
         return fail(RZ_ERR_ARG, "rz_play_set_match: matches need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)");
     if (Y.resign_on || Y.cap_on) return fail(RZ_ERR_ARG, "rz_play_set_match: resignation or a playout cap is set (attach again: a match has neither)");
+    if (Y.temp_on) return fail(RZ_ERR_ARG, "rz_play_set_match: a temperature schedule is set (attach again: a match keeps the temperature of rz_play_attach)");
     if (n_openings > e->open_cap) {   // (hipFree waits for the device: no launch still reads the old table)
         const void *old[3] = {Y.open_stones, Y.open_to_move, Y.open_last};
         for (const void *p : old) {

@@ -1338,6 +1338,7 @@ class MCTSEngine(object):
         self.play_resign_on = False   # (rz_play_attach turns resignation off)
         self.play_cap_on = False      # (and the playout cap)
         self.play_match_on = False    # (and match mode)
+        self.play_temp_on = False     # (and the temperature schedule)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log
@@ -1435,6 +1436,18 @@ class MCTSEngine(object):
         check(self.lib.rz_play_set_cap(self.handle, int(n_fast), p_full, self.stream()), 'rz_play_set_cap')
         self.play_cap_on = True
 
+    def play_set_temperatures(self, temps):
+        """The per-ply temperatures of the move step on the device (rz_play_set_temperatures), enqueued on the current stream:
+        ``temps[p]`` is T before ply p, the last entry holds for every later ply; None (or an empty table): off again, every ply at
+        play_attach's temperature.  After play_attach; a whole-move graph captured before the first call since play_attach keeps the
+        constant temperature (``play_temp_on`` tells: capture again) -- later tables reach it as they are.  HipError (the library's
+        argument error) for an entry that is not finite and positive, for more entries than the board has cells, and while a match
+        is on."""
+        tab = np.zeros(0) if temps is None else np.ascontiguousarray(temps, dtype=np.float64).reshape(-1)
+        check(self.lib.rz_play_set_temperatures(self.handle, ctypes.c_void_p(tab.ctypes.data) if tab.size else None, int(tab.size),
+                                                self.stream()), 'rz_play_set_temperatures')
+        self.play_temp_on = True
+
     def play_set_cap_order(self, longest_first):
         """Whether play_set_cap's searches follow the device's longest-first partition (default) or the slot order; before the move
         graph is captured."""
@@ -1446,8 +1459,8 @@ class MCTSEngine(object):
         off again.  While it is on, games 2k and 2k + 1 start from opening k % n, share their draw uniforms (seed, k, 2 ply + 1),
         every move is searched from a fresh root and ``play_side`` says which network's games the coming search takes.  After
         play_attach and before the games are queued.  HipError (the library's argument error) on an engine with Dirichlet noise,
-        the PUCT rule or sims_in_flight > 1, or with resignation or a playout cap set since play_attach; play_set_resign and
-        play_set_cap are refused the same way while a match is on."""
+        the PUCT rule or sims_in_flight > 1, or with resignation, a playout cap or a temperature schedule set since play_attach;
+        play_set_resign, play_set_cap and play_set_temperatures are refused the same way while a match is on."""
         t = self.torch
         if openings is None:
             check(self.lib.rz_play_set_match(self.handle, None, None, None, 0, self.stream()), 'rz_play_set_match')

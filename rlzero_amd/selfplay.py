@@ -96,6 +96,34 @@ def visits_to_pi(counts, temperature):
     return probs
 
 
+def step_schedule(t_early, n_plies, t_late):
+    """AlphaGo Zero's / AlphaZero's temperature schedule as a table for set_temperature_schedule: ``n_plies`` entries of ``t_early``
+    (T before plies 0 .. n_plies - 1), then ``t_late`` -- the last entry holds for every later ply.  float64 [n_plies + 1]."""
+    n_plies = int(n_plies)
+    if n_plies < 0:
+        raise ValueError('n_plies %d is negative' % n_plies)
+    return np.array([float(t_early)] * n_plies + [float(t_late)], dtype=np.float64)
+
+
+def decay_schedule(t_start, t_end, halflife, n):
+    """KataGo's kind of schedule: T before ply p is t_end + (t_start - t_end) * 0.5 ** (p / halflife) for p < ``n``; the last entry
+    holds for every later ply.  float64 [n]."""
+    ply = np.arange(int(n), dtype=np.float64)
+    return float(t_end) + (float(t_start) - float(t_end)) * 0.5 ** (ply / float(halflife))
+
+
+def _check_temperatures(temps, n_cells):
+    """-> the table as float64 [n]; ValueError for what rz_play_set_temperatures refuses."""
+    tab = np.array(temps, dtype=np.float64).reshape(-1)
+    if tab.size < 1:
+        raise ValueError('an empty temperature schedule (None turns it off)')
+    if not (np.isfinite(tab) & (tab > 0.0)).all():
+        raise ValueError('temperature schedule: every entry must be finite and positive')
+    if tab.size > n_cells:
+        raise ValueError('temperature schedule: %d entries for a board of %d cells (a game has no more plies)' % (tab.size, n_cells))
+    return tab
+
+
 def draw_move(acts, probs, u):
     """numpy's legacy choice(acts, p=probs) for the uniform ``u``."""
     cdf = np.cumsum(probs)
@@ -105,7 +133,8 @@ def draw_move(acts, probs, u):
 
 def batch_pi_and_moves(visits, legal, temperature, uniforms):
     """visits_to_pi + draw_move for many games at once: visits int [R, A], legal bool [R, A], uniforms [R]
-    -> (pi float64 [R, A] with zeros at illegal actions, chosen action int [R]).
+    -> (pi float64 [R, A] with zeros at illegal actions, chosen action int [R]).  ``temperature``: one T, or one per row [R] -- a
+    row is then bit for bit the scalar call at its T (1 / T and the product with the logarithms are elementwise).
 
     Bit-identical to the per-game expressions above (which are the reference's, alphazero_mcts.py:10-14,
     91-92,148): log / exp / divide are elementwise; the maximum is exact; the normalising sum is taken over
@@ -115,7 +144,10 @@ def batch_pi_and_moves(visits, legal, temperature, uniforms):
     visits = np.asarray(visits)
     legal = np.asarray(legal, dtype=bool)
     R, A = visits.shape
-    x = 1.0 / temperature * np.log(visits + 1e-10)
+    if np.ndim(temperature) == 0:
+        x = 1.0 / temperature * np.log(visits + 1e-10)
+    else:
+        x = (1.0 / np.asarray(temperature, dtype=np.float64).reshape(R))[:, None] * np.log(visits + 1e-10)
     mx = np.where(legal, x, -np.inf).max(axis=1)
     e = np.exp(np.where(legal, x - mx[:, None], -np.inf))  # exp(-inf) = 0 at illegal actions
     k = legal.sum(axis=1)
@@ -450,6 +482,8 @@ class BatchedSelfPlay(object):
         self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
         self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
         self.full_plies = 0   # searches with the full budget so far (with the cap off: every search)
+        self.temperature_schedule = None   # set_temperature_schedule: T before ply p, float64 [n <= cells]
+        self.pi_temperature = None         # set_temperature_schedule: the T of the stored pis (None: the ply's)
 
     def set_playout_cap(self, n_fast, p_full=None):
         """Playout cap randomization (KataGo, Wu 2019, section 3.1; an opt-in extension) for every lane and BOTH loops (run,
@@ -485,6 +519,51 @@ class BatchedSelfPlay(object):
             if self.playout_cap is not None or lane.eng.play_cap_on:
                 with self._on(lane):
                     lane.eng.play_set_cap(*(self.playout_cap or (1, float('nan'))))
+
+    def set_temperature_schedule(self, temps, pi_temperature=None):
+        """A per-ply move temperature (an opt-in extension: the reference's self-play has one T) for every lane and BOTH loops (run,
+        run_device): ``temps[p]`` is T before ply p and the last entry holds for every later ply -- step_schedule (AlphaGo Zero /
+        AlphaZero: T = 1 for the opening, then T -> 0) and decay_schedule (KataGo's half-life) build such tables.  None: off, every ply
+        at ``temperature`` again.  A game still depends on (seed, game id, settings) only: T follows from the ply.  Between runs,
+        before or after device_attach; like set_resign, the first schedule on an attached object whose whole-move graphs were
+        captured without one attaches again, later tables reach the graphs as they are.  Dirichlet noise is untouched, and
+        KataGo's "no temperature on fast moves" of a playout cap is deliberately out of scope.
+        ``pi_temperature``: None keeps the reference's rule -- the stored pi is the move distribution at the ply's T
+        (alphazero_mcts.py:88-92), one-hot where the schedule has cooled; a float forms Trajectory.pis with visits_to_pi at that T
+        instead, the moves still drawn at the ply's T (host side only, the same in both loops).
+        ValueError for entries that are not finite and positive, for more entries than the board has cells, and for a lane whose
+        engine is in match mode (a match keeps its own T)."""
+        if pi_temperature is not None:
+            pi_temperature = float(pi_temperature)
+            if not (np.isfinite(pi_temperature) and pi_temperature > 0.0):
+                raise ValueError('pi_temperature %r is not finite and positive' % pi_temperature)
+        tab = None if temps is None else _check_temperatures(temps, self.eng.n_cells)
+        if tab is not None and any(getattr(lane.eng, 'play_match_on', False) for lane in self.lanes):
+            raise ValueError('a lane\'s engine is in match mode (play_set_match): a match keeps its own temperature')
+        self.temperature_schedule, self.pi_temperature = tab, pi_temperature
+        if not getattr(self, '_dev_on', False):
+            return
+        if tab is not None and any(lane.move_graph is not None and not lane.eng.play_temp_on for lane in self.lanes):
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the table before the capture)
+            return
+        for lane in self.lanes:
+            if tab is not None or lane.eng.play_temp_on:
+                with self._on(lane):
+                    lane.eng.play_set_temperatures(tab)
+
+    def _temps(self, plies):
+        """-> T per row: the schedule's entry of the row's ply (the last one beyond it), or the one temperature."""
+        tab = self.temperature_schedule
+        if tab is None:
+            return self.temperature
+        return tab[np.minimum(np.asarray(plies, dtype=np.int64), tab.size - 1)]
+
+    def _pis_moves(self, visits, legal, plies, uniforms):
+        """batch_pi_and_moves at the rows' temperatures; the stored pi at pi_temperature where one is set."""
+        pis, chosen = batch_pi_and_moves(visits, legal, self._temps(plies), uniforms)
+        if self.pi_temperature is not None:
+            pis = batch_pi_and_moves(visits, legal, self.pi_temperature, uniforms)[0]
+        return pis, chosen
 
     def _full(self, game_ids, plies):
         """-> bool per (game, ply): the search has the full budget under the current cap."""
@@ -535,7 +614,8 @@ class BatchedSelfPlay(object):
     def for_network(cls, net_module, board, n_in_row, n_games, n_playout, c_puct=5.0, device='cuda:0',
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
-                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None, **engine_kw):
+                    deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None,
+                    temperature_schedule=None, pi_temperature=None, **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -553,7 +633,8 @@ class BatchedSelfPlay(object):
         the reference's f32 (boards of 11 .. 16 rows and columns).  ``delta_trunk``: False = the full-board trunk on every leaf (the
         checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU).
         ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign.  ``playout_cap``: None (off) or (n_fast, p_full):
-        set_playout_cap."""
+        set_playout_cap.  ``temperature_schedule``: None (off) or a table of per-ply temperatures, with ``pi_temperature``:
+        set_temperature_schedule."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -620,6 +701,8 @@ class BatchedSelfPlay(object):
             sp.set_resign(*(resign if isinstance(resign, (tuple, list)) else (resign, )))
         if playout_cap is not None:
             sp.set_playout_cap(*playout_cap)
+        if temperature_schedule is not None or pi_temperature is not None:
+            sp.set_temperature_schedule(temperature_schedule, pi_temperature=pi_temperature)
         if before_warm is not None:
             before_warm(sp)
         sp.warm_graphs()
@@ -792,7 +875,7 @@ class BatchedSelfPlay(object):
                 heights = taken.reshape(len(running), eng.rows, eng.cols).sum(axis=1)
             else:
                 legal = ~taken
-            pis, chosen = batch_pi_and_moves(visits[running - lo], legal, self.temperature, us)
+            pis, chosen = self._pis_moves(visits[running - lo], legal, self.slot_ply[running], us)
             cells = heights[np.arange(len(running)), chosen] * eng.cols + chosen if eng.game == 'connect4' else chosen
             moves[running - lo] = chosen
             self.cell_taken[running, cells] = True
@@ -975,6 +1058,8 @@ class BatchedSelfPlay(object):
                 lane.eng.play_set_cap_order(self.cap_longest_first)
                 if self.playout_cap is not None:   # (likewise: the graph's search then reads the budgets -- set_playout_cap)
                     lane.eng.play_set_cap(*self.playout_cap)
+                if self.temperature_schedule is not None:   # (likewise: the graph's draw then reads the table -- set_temperature_schedule)
+                    lane.eng.play_set_temperatures(self.temperature_schedule)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
@@ -1089,7 +1174,7 @@ class BatchedSelfPlay(object):
         visits = rec[:, W0:]
         legal = visits >= 0
         # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
-        pis, chosen = batch_pi_and_moves(np.where(legal, visits, 0), legal, self.temperature, move_uniform(self.seed, gids, plies))
+        pis, chosen = self._pis_moves(np.where(legal, visits, 0), legal, plies, move_uniform(self.seed, gids, plies))
         not_plain = (flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED)) != 0
         wrong = ~not_plain & (chosen != moves)
         if wrong.any():

@@ -151,7 +151,7 @@ class TrainPipeline:
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
-                 device_replay=False):
+                 device_replay=False, temperature_schedule=None, pi_temperature=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -172,7 +172,14 @@ class TrainPipeline:
         reference's 32 and 1, train_alphazero.py:33,130-131), for either buffer.  ``device_replay`` (batched mode on a GPU only, an
         opt-in extension): rank 0's ``data_buffer`` is a ``rlzero_amd.replay.DeviceReplay`` -- the finished games go to device
         memory from their move lists, a mini-batch is one launch (``sample``: drawn on the device WITH replacement, keyed (seed,
-        update)), and the KL / explained variances of ``policy_update`` are computed on the device."""
+        update)), and the KL / explained variances of ``policy_update`` are computed on the device.
+        ``temperature_schedule``: None or what --temperature-schedule parses to, ('step', t_early, n_plies, t_late) or ('decay',
+        t_start, t_end, halflife) -- a per-ply move temperature (BatchedSelfPlay.set_temperature_schedule; batched mode only, an
+        opt-in extension); ``pi_temperature``: None (the stored pi at the ply's T, the reference's rule) or the T of the stored pi."""
+        if (temperature_schedule is not None or pi_temperature is not None) and selfplay_games_in_flight <= 0:
+            raise ValueError('the temperature schedule is a batched self-play option: selfplay_games_in_flight must be > 0')
+        self.temperature_schedule = None if temperature_schedule is None else temperature_table(temperature_schedule, board_size * board_size)
+        self.pi_temperature = None if pi_temperature is None else float(pi_temperature)
         if device_replay and selfplay_games_in_flight <= 0:
             raise ValueError('the device replay buffer is a batched-mode option: selfplay_games_in_flight must be > 0')
         if int(batch_size) < 1 or int(updates_per_round) < 1:
@@ -317,7 +324,8 @@ class TrainPipeline:
             self._batched = BatchedSelfPlay.for_network(
                 self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
-                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap)
+                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
+                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature)
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
         if self.resign_mode != 'off':
             # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
@@ -645,6 +653,49 @@ def playout_cap_arg(text):
     return n_fast, p_full
 
 
+def temperature_schedule_arg(text):
+    """--temperature-schedule step:T_EARLY:N:T_LATE | decay:T_START:T_END:HALFLIFE -> ('step', t_early, n, t_late) or ('decay', t_start,
+    t_end, halflife)."""
+    import argparse
+    form = 'step:T_EARLY:N:T_LATE or decay:T_START:T_END:HALFLIFE'
+    parts = text.split(':')
+    try:
+        if parts[0] == 'step' and len(parts) == 4:
+            spec = ('step', float(parts[1]), int(parts[2]), float(parts[3]))
+            ok = spec[2] >= 0 and all(np.isfinite(t) and t > 0.0 for t in (spec[1], spec[3]))
+        elif parts[0] == 'decay' and len(parts) == 4:
+            spec = ('decay', float(parts[1]), float(parts[2]), float(parts[3]))
+            ok = all(np.isfinite(t) for t in spec[1:]) and spec[1] > 0.0 and spec[2] >= 0.0 and spec[3] > 0.0
+        else:
+            raise ValueError(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('%s, e.g. step:1.0:30:0.001, not %r' % (form, text))
+    if not ok:
+        raise argparse.ArgumentTypeError('%s with finite positive temperatures and half-life (T_END may be 0), N >= 0, not %r' % (form, text))
+    return spec
+
+
+def temperature_table(spec, n_cells):
+    """The table of a parsed --temperature-schedule for a board of ``n_cells`` cells (a game has no more plies)."""
+    from rlzero_amd.selfplay import decay_schedule, step_schedule
+    if spec[0] == 'step':
+        if spec[2] + 1 > n_cells:
+            raise ValueError('temperature schedule: N = %d early plies, the board has %d cells' % (spec[2], n_cells))
+        return step_schedule(spec[1], spec[2], spec[3])
+    return decay_schedule(spec[1], spec[2], spec[3], n_cells)
+
+
+def positive_float_arg(text):
+    import argparse
+    try:
+        value = float(text)
+    except ValueError:
+        value = float('nan')
+    if not (np.isfinite(value) and value > 0.0):
+        raise argparse.ArgumentTypeError('a finite positive number, not %r' % text)
+    return value
+
+
 def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku on MI355X (no arguments: the reference script\'s run)')
@@ -663,6 +714,11 @@ def parse_args(argv=None):
     ap.add_argument('--playout-cap', type=playout_cap_arg, default=None, metavar='N_FAST:P_FULL',
                     help='playout cap randomization (batched mode only): a search has --playouts simulations with probability P_FULL, '
                          'else N_FAST; only the full ones become policy samples')
+    ap.add_argument('--temperature-schedule', type=temperature_schedule_arg, default=None, metavar='step:T_EARLY:N:T_LATE | decay:T_START:T_END:HALFLIFE',
+                    help='batched mode only: the move temperature by ply -- T_EARLY for the first N plies, then T_LATE; or T_END + '
+                         '(T_START - T_END) * 0.5 ** (ply / HALFLIFE).  Default: one temperature, the reference\'s run')
+    ap.add_argument('--pi-temperature', type=positive_float_arg, default=None, metavar='T',
+                    help='batched mode only: the stored policy targets at this temperature (default: at the temperature of the move)')
     ap.add_argument('--gate-against', default=None, metavar='CKPT',
                     help='batched mode only: at every --check-freq also report the match score of the current network against this '
                          'checkpoint (paired openings; nothing is decided on it)')
@@ -684,6 +740,12 @@ def parse_args(argv=None):
         ap.error('--playout-cap needs --games-in-flight > 0 (batched self-play)')
     if args.playout_cap is not None and args.playout_cap[0] > args.playouts:
         ap.error('--playout-cap: N_FAST %d exceeds --playouts %d' % (args.playout_cap[0], args.playouts))
+    if args.temperature_schedule is not None and args.games_in_flight <= 0:
+        ap.error('--temperature-schedule needs --games-in-flight > 0 (batched self-play)')
+    if args.pi_temperature is not None and args.games_in_flight <= 0:
+        ap.error('--pi-temperature needs --games-in-flight > 0 (batched self-play)')
+    if args.temperature_schedule is not None and args.temperature_schedule[0] == 'step' and args.temperature_schedule[2] + 1 > args.board * args.board:
+        ap.error('--temperature-schedule: N = %d early plies, the board has %d cells' % (args.temperature_schedule[2], args.board * args.board))
     if args.resign_threshold != 'off' and args.games_in_flight <= 0:
         ap.error('--resign-threshold needs --games-in-flight > 0 (batched self-play)')
     if args.resign_threshold not in ('off', 'auto'):
@@ -706,7 +768,8 @@ def main():
                          check_freq=args.check_freq, selfplay_games_in_flight=args.games_in_flight, seed=args.seed,
                          resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
                          resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against,
-                         batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay)
+                         batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay,
+                         temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
