@@ -27,6 +27,7 @@ import math
 
 import numpy as np
 
+from . import playlog
 from ._hip import HipError
 from .selfplay import batch_pi_and_moves, move_uniform
 
@@ -187,12 +188,47 @@ def score(results):
 
 
 # ------------------------------------------------------------------------- the match
-class BatchedMatch(object):
+class MatchReader(object):
+    """What turns the log of a match's move step into MatchResults: seed and temperature, the counters and the book of the slots
+    (playlog.SlotBook).  numpy only -- BatchedMatch adds the engine; a test builds one alone.  ``resolve(slot, move)`` hands a stalled
+    slot's move back to the device."""
+
+    def __init__(self, n_slots, n_actions, max_plies, n_playout, resolve, seed=0, temperature=1e-3):
+        self.seed, self.temperature, self.n_playout = int(seed), float(temperature), n_playout
+        self._book_args = (n_slots, max_plies, resolve, dict(visits=(np.int32, (n_actions, ), 'move'),
+                                                             root_n=(np.int32, (), 'move')))
+        self.start_reading(())
+
+    stalls_resolved, moves_done, _started = playlog.counter('stalls_resolved'), playlog.counter('moves_done'), playlog.counter('started')
+
+    def start_reading(self, openings):
+        """A new match from ``openings`` (move lists): every slot idle, every counter zero."""
+        self.openings = [list(o) for o in openings]
+        self.book = playlog.SlotBook(*self._book_args)
+        self.sims_done, self._last_running = 0, -1
+
+    def read_rows(self, rows):
+        """Log rows int32 [R, G, words], oldest first -> (the games that ended in them, the RUNNING records of the last row)."""
+        slots, d, last_running = playlog.running(rows)
+        if slots.size == 0:
+            return [], last_running
+        # the reference's expression on the logged counts, the draw with the pair's uniform (numpy's inverse-CDF rule): the arbiter
+        _, chosen = batch_pi_and_moves(d.counts, d.legal, self.temperature, match_uniform(self.seed, d.game, d.ply))
+        playlog.check_moves(d, chosen)
+        self.sims_done += self.n_playout * playlog.check_match_roots(d, self.n_playout)
+        done = []
+        for f in self.book.feed(slots, d, chosen, dict(visits=d.visits, root_n=d.root_n)):
+            k = int(opening_of(f.game, len(self.openings)))
+            done.append(MatchResult(f.game, k, self.openings[k], f.moves, f.winner, f.columns['visits'], f.columns['root_n']))
+        return done, last_running
+
+
+class BatchedMatch(MatchReader):
     """A match between ``evaluator_a`` and ``evaluator_b`` in the slots of ONE engine (one lane); see the module docstring."""
 
     def __init__(self, engine, evaluator_a, evaluator_b, seed=0, temperature=1e-3, stall_margin=0.0, ring_steps=64, depth=2):
         self.eng, self.evaluators = engine, (evaluator_a, evaluator_b)
-        self.seed, self.temperature = int(seed), float(temperature)
+        MatchReader.__init__(self, engine.n_games, engine.n_actions, engine.n_cells, engine.n_playout, self._resolve, seed, temperature)
         self.stall_margin, self.ring_steps, self.depth = float(stall_margin), max(int(ring_steps), int(depth) + 3), int(depth)
         if engine.game != 'gomoku':
             raise ValueError('matches are played on Gomoku boards')
@@ -203,7 +239,6 @@ class BatchedMatch(object):
         # one lane: the stream current at construction, as a one-lane BatchedSelfPlay does (no stream of its own: a process's lanes
         # elsewhere keep the hardware queues they would have had)
         self.stream = self.torch.cuda.current_stream(engine.device)
-        self.stalls_resolved = self.moves_done = self.sims_done = 0
 
     @classmethod
     def for_networks(cls, net_a, net_b, board, n_in_row, n_games, n_playout, c_puct=5.0, device='cuda:0', seed=0, temperature=1e-3,
@@ -242,7 +277,7 @@ class BatchedMatch(object):
     def begin(self, n_pairs, openings):
         """Attach the move step, turn match mode on and queue the games of pairs 0 .. n_pairs - 1: the slots take the first of them."""
         t, eng = self.torch, self.eng
-        self.openings = [list(o) for o in openings]
+        self.start_reading(openings)
         arrays = opening_arrays(self.openings, eng.board_size, eng.n_in_row)
         ids = np.arange(2 * int(n_pairs), dtype=np.int64)
         with t.cuda.stream(self.stream):
@@ -256,12 +291,7 @@ class BatchedMatch(object):
         if not eng.play_log_on_host:
             raise HipError('a match reads its log in place: the engine\'s log ring must be host memory the device can address')
         self._log_np = self.log.numpy()
-        G = eng.n_games
-        self._slot_game, self._slot_ply = np.full(G, -1, np.int64), np.zeros(G, np.int64)
-        self._moves, self._visits, self._root_n = [[] for _ in range(G)], [[] for _ in range(G)], [[] for _ in range(G)]
-        self._stalls, self._inflight, self._last_running = {}, [], -1
-        self._started, self._n_games = 0, int(ids.size)
-        self.stalls_resolved = self.moves_done = self.sims_done = 0
+        self._inflight, self._n_games = [], int(ids.size)
 
     def step(self):
         """Enqueue one move and process the log rows that have arrived (all but the ``depth`` newest) -> the games found finished."""
@@ -281,64 +311,12 @@ class BatchedMatch(object):
 
     def read_row(self, row):
         """Process log row ``row`` (its move has finished on the device) -> the games that ended in it."""
-        from ._hip import PLAY_ENDED as ENDED, PLAY_RECORD_WORDS as W0, PLAY_RESOLVED as RESOLVED, PLAY_RUNNING as RUNNING, \
-            PLAY_SEARCHED as SEARCHED, PLAY_STALLED as STALLED
-        eng = self.eng
-        rec = self._log_np[row].copy()   # (the pinned row may be overwritten from now on)
-        flags = rec[:, 4] & 0xFFFF
-        slots = np.nonzero(flags & RUNNING)[0]
-        self._last_running = int(slots.size)
-        if slots.size == 0:
-            return []
-        rec, flags = rec[slots], flags[slots]
-        gids = rec[:, 0].astype(np.uint32).astype(np.int64) | (rec[:, 1].astype(np.int64) << 32)
-        plies, moves, visits = rec[:, 2].astype(np.int64), rec[:, 3], rec[:, W0:]
-        legal = visits >= 0
-        # the reference's expression on the logged counts, the draw with the pair's uniform (numpy's inverse-CDF rule): the arbiter
-        _, chosen = batch_pi_and_moves(np.where(legal, visits, 0), legal, self.temperature, match_uniform(self.seed, gids, plies))
-        searched = (flags & SEARCHED) != 0
-        plain = (flags & (STALLED | RESOLVED)) == 0
-        if (plain & (chosen != moves)).any():
-            i = int(np.nonzero(plain & (chosen != moves))[0][0])
-            raise HipError('the move drawn on the device (%d) is not numpy\'s (%d): game %d, ply %d' % (moves[i], chosen[i], gids[i], plies[i]))
-        if (searched & (rec[:, 5] != eng.n_playout)).any():   # (a fresh root and ONE search of n_playout simulations per move)
-            i = int(np.nonzero(searched & (rec[:, 5] != eng.n_playout))[0][0])
-            raise HipError('game %d ply %d was drawn from a root of %d visits, not n_playout = %d' % (gids[i], plies[i], rec[i, 5], eng.n_playout))
-        self.sims_done += eng.n_playout * int(searched.sum())
-        done = []
-        for i, s in enumerate(slots.tolist()):
-            f, gid, ply = int(flags[i]), int(gids[i]), int(plies[i])
-            if f & STALLED:
-                known = self._stalls.get(s)
-                if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
-                    self._stalls[s] = (gid, ply, int(chosen[i]), visits[i].copy())
-                    with self.torch.cuda.stream(self.stream):
-                        eng.play_resolve(s, int(chosen[i]))
-                continue
-            mv, vis = int(moves[i]), visits[i]
-            if f & RESOLVED:
-                known = self._stalls.pop(s, None)
-                if known is None or known[:2] != (gid, ply) or known[2] != mv:
-                    raise HipError('slot %d: the device resolved game %d ply %d with move %d, the host had decided %r' % (s, gid, ply, mv, known and known[:3]))
-                vis = known[3]
-                self.stalls_resolved += 1
-            if ply == 0:   # the slot has started this game
-                self._slot_game[s], self._slot_ply[s] = gid, 0
-                self._moves[s], self._visits[s], self._root_n[s] = [], [], []
-                self._started += 1
-            if self._slot_game[s] != gid or self._slot_ply[s] != ply:
-                raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (s, gid, ply, self._slot_game[s], self._slot_ply[s]))
-            self._moves[s].append(mv)
-            self._visits[s].append(vis.copy())
-            self._root_n[s].append(int(rec[i, 5]))
-            self._slot_ply[s] += 1
-            self.moves_done += 1
-            if f & ENDED:
-                k = int(opening_of(gid, len(self.openings)))
-                done.append(MatchResult(gid, k, self.openings[k], self._moves[s], ((int(rec[i, 4]) >> 16) & 3) - 1, self._visits[s],
-                                        self._root_n[s]))
-                self._slot_game[s] = -1
+        done, self._last_running = self.read_rows(self._log_np[[row]])   # (a copy: the pinned row may be overwritten from now on)
         return done
+
+    def _resolve(self, slot, move):
+        with self.torch.cuda.stream(self.stream):
+            self.eng.play_resolve(slot, move)
 
     def run(self, n_pairs, openings):
         """Play pairs 0 .. n_pairs - 1 (game ids 0 .. 2 n_pairs - 1) from ``openings`` (move lists: paired_openings) to the end

@@ -1,0 +1,181 @@
+"""The host's reader of the device move step's log (include/rlzero_hip.h, "The log: ..."): the one decoder of its records, and the
+book both consumers -- self-play (selfplay.SelfPlayReader) and matches (match.MatchReader) -- keep of what each slot is playing.
+numpy only: no torch, no engine; the owner hands in the rows, the arbiter's moves and a ``resolve`` callable."""
+import collections
+
+import numpy as np
+
+from ._hip import (PLAY_ENDED, PLAY_FULL, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED,
+                   PLAY_STALLED, PLAY_WOULD_RESIGN, HipError)
+
+Records = collections.namedtuple('Records', 'game ply move flags winner root_n edge stat visits legal counts')
+Finished = collections.namedtuple('Finished', 'slot game moves searched winner resigned columns')
+
+
+def decode(rec):
+    """Records int32 [..., PLAY_RECORD_WORDS + A] -> their fields as arrays [...]: game id (int64), ply before the move, the move or
+    -1, the PLAY_* flags, the winner (-1: none / a tie), N(root), the draw's distance to the nearer interval edge and the resignation
+    statistic (float32), and per action [..., A] the visit counts as logged (-1: illegal), ``legal``, and ``counts`` with 0 there."""
+    rec = np.asarray(rec)
+    visits = rec[..., PLAY_RECORD_WORDS:]
+    legal = visits >= 0
+    return Records(game=rec[..., 0].astype(np.uint32).astype(np.int64) | (rec[..., 1].astype(np.int64) << 32), ply=rec[..., 2].astype(np.int64),
+                   move=rec[..., 3], flags=rec[..., 4] & 0xFFFF, winner=((rec[..., 4] >> 16) & 3) - 1, root_n=rec[..., 5],
+                   edge=np.ascontiguousarray(rec[..., 6]).view(np.float32), stat=np.ascontiguousarray(rec[..., 7]).view(np.float32),
+                   visits=visits, legal=legal, counts=np.where(legal, visits, 0))
+
+
+def running(rows):
+    """Log rows int32 [R, G, words] -> (slot of every RUNNING record, row-major: a slot's records in move order; those records
+    decoded; the number of them in the last row)."""
+    on = (rows[..., 4] & PLAY_RUNNING) != 0
+    row_i, g_i = np.nonzero(on)
+    return g_i, decode(rows[row_i, g_i]), int(on[-1].sum())
+
+
+def check_moves(d, chosen):
+    """Every move the device drew is the arbiter's (a stalled, resolved or resigning record holds no draw)."""
+    wrong = ((d.flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED)) == 0) & (chosen != d.move)
+    if wrong.any():
+        i = np.nonzero(wrong)[0][0]
+        raise HipError('the move drawn on the device (%d) is not numpy\'s (%d): game %d, ply %d' % (d.move[i], chosen[i], d.game[i], d.ply[i]))
+
+
+def check_budgets(d, n_playout, cap=None, cap_u=None):
+    """-> (simulations, searches with the full budget) of the searched records.  Under a playout cap ``cap`` = (n_fast, p_full) the
+    device's budget flag is held against this side's draw on the same key, ``cap_u`` (selfplay.cap_uniform of the records)."""
+    searched = (d.flags & PLAY_SEARCHED) != 0
+    if cap is None:
+        return n_playout * int(searched.sum()), int(searched.sum())
+    fulls = (d.flags & PLAY_FULL) != 0
+    bad = searched & (fulls != (cap_u < cap[1]))
+    if bad.any():
+        i = np.nonzero(bad)[0][0]
+        raise HipError('the device\'s budget flag 0x%x of game %d ply %d disagrees with cap_uniform = %r, p_full %r' % (
+            d.flags[i], d.game[i], d.ply[i], float(cap_u[i]), cap[1]))
+    return int(np.where(fulls, n_playout, cap[0])[searched].sum()), int((fulls & searched).sum())
+
+
+def check_resignation(d, threshold, calib):
+    """The device's decision against its logged statistic s (float32 of the fp64 s it compared): resigned / would resign =>
+    s <= threshold, played on => s >= threshold or NaN; the calibration flag against this side's draw ``calib`` (bool per record).
+    -> the records of calibration games where the rule fired."""
+    t32, flags = np.float32(threshold), d.flags
+    searched = (flags & PLAY_SEARCHED) != 0
+    fired = (flags & (PLAY_RESIGNED | PLAY_WOULD_RESIGN)) != 0
+    with np.errstate(invalid='ignore'):
+        bad = searched & (((flags & PLAY_NO_RESIGN) != 0) != calib)
+        bad |= searched & fired & ~(d.stat <= t32)
+        bad |= searched & ~fired & (d.stat < t32)
+        bad |= ((flags & PLAY_RESIGNED) != 0) & calib
+    if bad.any():
+        i = np.nonzero(bad)[0][0]
+        raise HipError('the device\'s resignation flags 0x%x of game %d ply %d disagree with s = %r, threshold %r, calibration %s' % (
+            flags[i], d.game[i], d.ply[i], float(d.stat[i]), threshold, bool(calib[i])))
+    return int(((flags & PLAY_WOULD_RESIGN) != 0).sum())
+
+
+def check_match_roots(d, n_playout):
+    """A match draws every move from a fresh root and ONE search of n_playout simulations -> the searched records."""
+    bad = ((d.flags & PLAY_SEARCHED) != 0) & (d.root_n != n_playout)
+    if bad.any():
+        i = np.nonzero(bad)[0][0]
+        raise HipError('game %d ply %d was drawn from a root of %d visits, not n_playout = %d' % (d.game[i], d.ply[i], d.root_n[i], n_playout))
+    return int(((d.flags & PLAY_SEARCHED) != 0).sum())
+
+
+def counter(name):
+    """A counter of an owner's ``book`` as an attribute of the owner."""
+    return property(lambda self: getattr(self.book, name), lambda self, value: setattr(self.book, name, value))
+
+
+class SlotBook(object):
+    """Which game and ply every slot is at, what its plies logged, and the stalls the host has decided.
+
+    ``columns``: {name: (dtype, shape of one entry, 'move' | 'search')} -- what to keep per ply beside the move: a 'move' column of every
+    move played, a 'search' column of every SEARCHED record (the stalled one and the resigning one included: a resigned game has ``ply``
+    moves and ``ply + 1`` searches).  ``resolve(slot, move)`` hands a stalled slot's move back to the device."""
+
+    def __init__(self, n_slots, max_plies, resolve, columns):
+        self.resolve = resolve
+        self.slot_game = np.full(n_slots, -1, dtype=np.int64)
+        self.slot_ply = np.zeros(n_slots, dtype=np.int64)
+        self.move_cols = [name for name, (_, _, per) in columns.items() if per == 'move']
+        self.search_cols = [name for name, (_, _, per) in columns.items() if per == 'search']
+        self.moves = np.zeros((n_slots, max_plies), dtype=np.int32)
+        self.buf = dict((name, np.zeros((n_slots, max_plies) + tuple(shape), dtype=dtype))   # (pages are touched as games grow)
+                        for name, (dtype, shape, _) in columns.items())
+        self.stalls = {}    # slot -> (game id, ply, move, the 'move' columns of its record): decided here, waiting for the device to take it
+        self.started = self.stalls_resolved = self.moves_done = 0
+
+    def clear(self):
+        """Every slot idle, no stall waiting."""
+        self.slot_game[:] = -1
+        self.stalls = {}
+
+    def _expect(self, slot, game, ply):
+        if self.slot_game[slot] != game or self.slot_ply[slot] != ply:
+            raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (
+                slot, game, ply, self.slot_game[slot], self.slot_ply[slot]))
+
+    def _close(self, slot, game, plies, searched, winner, resigned):
+        self.slot_game[slot] = -1
+        cols = dict((name, self.buf[name][slot, :plies].copy()) for name in self.move_cols)
+        cols.update((name, self.buf[name][slot, :searched].copy()) for name in self.search_cols)
+        return Finished(slot, game, self.moves[slot, :plies].copy(), searched, winner, resigned, cols)
+
+    def feed(self, slots, d, chosen, values):
+        """The RUNNING records of one or more log rows, row-major (a new row begins where the slot number does not rise): ``slots``
+        their global slot numbers, ``d`` their fields (decode), ``chosen`` the arbiter's move and ``values`` {column: array} per
+        record -> [Finished] of the games that ended in them, each column copied up to its own length."""
+        flags, gids, plies = d.flags, d.game, d.ply
+        special = ((flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED | PLAY_ENDED)) != 0) | (plies == 0)
+        done = []
+        first = [0] + (np.nonzero(slots[1:] <= slots[:-1])[0] + 1).tolist() + [len(slots)]
+        for a, b in zip(first[:-1], first[1:]):
+            easy = np.nonzero(~special[a:b])[0] + a
+            if easy.size:   # moves in the middle of a game: the whole row at once
+                s, p = slots[easy], plies[easy]
+                bad = (self.slot_game[s] != gids[easy]) | (self.slot_ply[s] != p)
+                if bad.any():
+                    i = easy[np.nonzero(bad)[0][0]]
+                    self._expect(slots[i], gids[i], plies[i])
+                self.moves[s, p] = d.move[easy]
+                for name, buf in self.buf.items():
+                    buf[s, p] = values[name][easy]
+                self.slot_ply[s] += 1
+                self.moves_done += int(easy.size)
+            for i in np.nonzero(special[a:b])[0] + a:
+                s, f, gid, ply, mv = int(slots[i]), int(flags[i]), int(gids[i]), int(plies[i]), int(d.move[i])
+                if f & PLAY_SEARCHED:   # (a stall's searched record comes before the resolved one of its ply)
+                    for name in self.search_cols:
+                        self.buf[name][s, ply] = values[name][i]
+                if f & PLAY_STALLED:
+                    known = self.stalls.get(s)
+                    if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
+                        self.stalls[s] = (gid, ply, int(chosen[i]), dict((name, np.array(values[name][i])) for name in self.move_cols))
+                        self.resolve(s, int(chosen[i]))
+                    continue
+                played = None
+                if f & PLAY_RESOLVED:   # the move decided here: what its ply logged is in the stalled record
+                    known = self.stalls.pop(s, None)
+                    if known is None or known[:3] != (gid, ply, mv):
+                        raise HipError('slot %d: the device resolved game %d ply %d with move %d, the host had decided %r' % (
+                            s, gid, ply, mv, known and known[:3]))
+                    played = known[3]
+                    self.stalls_resolved += 1
+                if ply == 0:   # the slot has started this game
+                    self.slot_game[s], self.slot_ply[s] = gid, 0
+                    self.started += 1
+                self._expect(s, gid, ply)
+                if f & PLAY_RESIGNED:   # the game ends without a move: the plies before it
+                    done.append(self._close(s, gid, ply, ply + 1, int(d.winner[i]), True))
+                    continue
+                self.moves[s, ply] = mv
+                for name in self.move_cols:
+                    self.buf[name][s, ply] = values[name][i] if played is None else played[name]
+                self.slot_ply[s] += 1
+                self.moves_done += 1
+                if f & PLAY_ENDED:
+                    done.append(self._close(s, gid, ply + 1, ply + 1, int(d.winner[i]), False))
+        return done

@@ -19,8 +19,10 @@ rank 0 (RCCL when the process group backend is nccl, gloo in the CPU tests).
 """
 import numpy as np
 
+from . import playlog
 from . import route as _route
-from ._hip import HipError
+from ._hip import PLAY_FULL, HipError
+from .playlog import SlotBook
 from .route import fc_in_trunk_pays   # noqa: F401  (a board rule: route.py; importable from here as before)
 
 _MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -416,15 +418,102 @@ def plan_route(rows, cols, game, net_algo, score_mode, in_flight, deferred_prior
                 resident_per_cu=r.resident_per_cu if r.resident else 1)
 
 
+class SelfPlayReader(object):
+    """What turns the device move step's log into Trajectories (include/rlzero_hip.h: rz_play_*): the settings a game depends on, the
+    counters, and the book of the slots (playlog.SlotBook).  numpy only -- BatchedSelfPlay adds the engines; a test builds one alone.
+    ``resolve(slot, move)`` hands a stalled slot's move back to the device."""
+
+    def __init__(self, n_slots, n_actions, max_plies, n_playout, geometry, resolve, temperature=1.0, seed=0):
+        self.n_slots, self.n_playout, self.geometry = n_slots, n_playout, geometry   # geometry: (board_size, n_in_row, game)
+        self.temperature = float(temperature)
+        self.seed = int(seed)
+        self.book = SlotBook(n_slots, max_plies, resolve, dict(
+            pi=(np.float64, (n_actions, ), 'move'),
+            stat=(np.float32, (), 'search'),    # resignation statistic of every search (set_resign)
+            full=(bool, (), 'search')))         # full budget of every search (set_playout_cap)
+        self.slot_game, self.slot_ply = self.book.slot_game, self.book.slot_ply
+        self.sims_done = 0
+        self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
+        self.resign_would = 0   # plies of calibration games where the rule fired (RZ_PLAY_WOULD_RESIGN on the device)
+        self.playout_cap = None   # set_playout_cap: (n_fast, p_full)
+        self.full_plies = 0   # searches with the full budget so far (with the cap off: every search)
+        self.temperature_schedule = None   # set_temperature_schedule: T before ply p, float64 [n <= cells]
+        self.pi_temperature = None         # set_temperature_schedule: the T of the stored pis (None: the ply's)
+
+    moves_done, stalls_resolved, _started = playlog.counter('moves_done'), playlog.counter('stalls_resolved'), playlog.counter('started')
+
+    def _temps(self, plies):
+        """-> T per row: the schedule's entry of the row's ply (the last one beyond it), or the one temperature."""
+        tab = self.temperature_schedule
+        if tab is None:
+            return self.temperature
+        return tab[np.minimum(np.asarray(plies, dtype=np.int64), tab.size - 1)]
+
+    def _pis_moves(self, visits, legal, plies, uniforms):
+        """batch_pi_and_moves at the rows' temperatures; the stored pi at pi_temperature where one is set."""
+        pis, chosen = batch_pi_and_moves(visits, legal, self._temps(plies), uniforms)
+        if self.pi_temperature is not None:
+            pis = batch_pi_and_moves(visits, legal, self.pi_temperature, uniforms)[0]
+        return pis, chosen
+
+    def _full(self, game_ids, plies):
+        """-> bool per (game, ply): the search has the full budget under the current cap."""
+        return cap_uniform(self.seed, game_ids, plies) < self.playout_cap[1]
+
+    @property
+    def resign_on(self):
+        return not np.isnan(self.resign_threshold)
+
+    def _calibration(self, game_ids):
+        """-> bool per game: resignation disabled (a calibration game) under the current rule."""
+        return resign_uniform(self.seed, game_ids) < self.resign_disabled_frac
+
+    def _resign_record(self, stats, winner, no_resign, resigned):
+        """Trajectory keywords of a finished game under the rule (none without it)."""
+        if not self.resign_on:
+            return {}
+        stats = np.asarray(stats, dtype=np.float32)
+        return dict(resigned=resigned, no_resign=no_resign, resign_stats=stats,
+                    fp_margin=fp_margin(stats, winner) if no_resign else np.nan)
+
+    def read_rows(self, rows, lo=0):
+        """Log rows int32 [R, G, words] of the slots ``lo`` .. ``lo + G - 1``, oldest first -> (the trajectories of the games that
+        ended in them, the RUNNING records of the last row).  pi is formed here, from the logged visit counts with the reference's
+        expression, and every move and flag of the device is verified against this side's draw on the same key."""
+        g_i, d, last_running = playlog.running(rows)
+        if g_i.size == 0:
+            return [], last_running
+        # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
+        pis, chosen = self._pis_moves(d.counts, d.legal, d.ply, move_uniform(self.seed, d.game, d.ply))
+        playlog.check_moves(d, chosen)
+        cap = self.playout_cap
+        sims, full = playlog.check_budgets(d, self.n_playout, cap, None if cap is None else cap_uniform(self.seed, d.game, d.ply))
+        self.sims_done += sims
+        self.full_plies += full
+        if self.resign_on:
+            self.resign_would += playlog.check_resignation(d, self.resign_threshold, self._calibration(d.game))
+        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=(d.flags & PLAY_FULL) != 0))
+        done = []
+        for f in finished:
+            extra = self._resign_record(f.columns['stat'], f.winner, not f.resigned and bool(self._calibration(f.game)), f.resigned)
+            if cap is not None:
+                extra['full'] = f.columns['full']
+            done.append(Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
+                                   game=self.geometry[2], **extra))
+        return done, last_running
+
+
 class _Lane(object):
     """One engine + its evaluator + the HIP stream its kernels are enqueued on."""
 
     def __init__(self, engine, evaluator, stream, offset):
         self.eng, self.evaluator, self.stream, self.offset = engine, evaluator, stream, offset
         self.slots = slice(offset, offset + engine.n_games)
+        self.primed = False       # play_move_pipelined: the coming move's simulations are in flight
+        self.move_graph = None    # device_attach: the whole-move hipGraph of a resident lane
 
 
-class BatchedSelfPlay(object):
+class BatchedSelfPlay(SelfPlayReader):
     """Plays games on one GPU; slots are refilled as games end.
 
     ``engine`` / ``evaluator`` may be lists of equal length: each (engine, evaluator) pair is a
@@ -433,6 +522,9 @@ class BatchedSelfPlay(object):
     kernels of the other lane run beside it (they use no LDS), so the halves ping-pong and the
     tree work is hidden under the dense contraction.  Results do not depend on the lane split:
     games are independent and their uniforms are keyed by game id."""
+
+    _dev_on = False      # device_attach: the move step is on the device
+    _chunks_done = -1    # graph chunks of the host loop so far (eager_every)
 
     def __init__(self, engine, evaluator, temperature=1.0, seed=0, use_graph=False, sims_per_graph=8,
                  eager_every=0):
@@ -461,29 +553,18 @@ class BatchedSelfPlay(object):
                     owner.resident_search = False
         self.eng = engines[0]  # geometry (board size, n_playout) is common to all lanes
         self.evaluator = evaluators[0]
-        self.n_slots = offset
-        self.temperature = float(temperature)
-        self.seed = int(seed)
+        SelfPlayReader.__init__(self, offset, self.eng.n_actions, self.eng.n_cells, self.eng.n_playout,
+                                (self.eng.board_size, self.eng.n_in_row, self.eng.game), self._resolve, temperature=temperature, seed=seed)
         self.use_graph = use_graph
         self.sims_per_graph = sims_per_graph
         self.eager_every = int(eager_every)  # with graphs: every k-th chunk runs eagerly (timing samples)
         G = self.n_slots
-        self.slot_game = np.full(G, -1, dtype=np.int64)
-        self.slot_ply = np.zeros(G, dtype=np.int64)
         self.cell_taken = np.zeros((G, self.eng.n_cells), dtype=bool)  # host mirror of the root boards
         self.slot_moves = [[] for _ in range(G)]
         self.slot_pis = [[] for _ in range(G)]
         self.slot_stats = [[] for _ in range(G)]   # resignation statistic of every search of the slot's game (set_resign)
-        self.sims_done = 0
-        self.moves_done = 0
-        self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
-        self.resign_would = 0   # plies of calibration games where the rule fired (RZ_PLAY_WOULD_RESIGN on the device)
-        self.playout_cap = None   # set_playout_cap: (n_fast, p_full)
         self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
         self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
-        self.full_plies = 0   # searches with the full budget so far (with the cap off: every search)
-        self.temperature_schedule = None   # set_temperature_schedule: T before ply p, float64 [n <= cells]
-        self.pi_temperature = None         # set_temperature_schedule: the T of the stored pis (None: the ply's)
 
     def set_playout_cap(self, n_fast, p_full=None):
         """Playout cap randomization (KataGo, Wu 2019, section 3.1; an opt-in extension) for every lane and BOTH loops (run,
@@ -510,15 +591,7 @@ class BatchedSelfPlay(object):
                     raise ValueError('the playout cap needs the resident search on every lane (this route has none: two-launch lanes, '
                                      'PUCT, sims_in_flight > 1 and host evaluators search every game alike)')
             self.playout_cap = (n_fast, p_full)
-        if not getattr(self, '_dev_on', False):
-            return
-        if self.playout_cap is not None and any(lane.move_graph is not None and not lane.eng.play_cap_on for lane in self.lanes):
-            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the cap before the capture)
-            return
-        for lane in self.lanes:
-            if self.playout_cap is not None or lane.eng.play_cap_on:
-                with self._on(lane):
-                    lane.eng.play_set_cap(*(self.playout_cap or (1, float('nan'))))
+        self._apply_option(self._cap_option())
 
     def set_temperature_schedule(self, temps, pi_temperature=None):
         """A per-ply move temperature (an opt-in extension: the reference's self-play has one T) for every lane and BOTH loops (run,
@@ -541,37 +614,7 @@ class BatchedSelfPlay(object):
         if tab is not None and any(getattr(lane.eng, 'play_match_on', False) for lane in self.lanes):
             raise ValueError('a lane\'s engine is in match mode (play_set_match): a match keeps its own temperature')
         self.temperature_schedule, self.pi_temperature = tab, pi_temperature
-        if not getattr(self, '_dev_on', False):
-            return
-        if tab is not None and any(lane.move_graph is not None and not lane.eng.play_temp_on for lane in self.lanes):
-            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the table before the capture)
-            return
-        for lane in self.lanes:
-            if tab is not None or lane.eng.play_temp_on:
-                with self._on(lane):
-                    lane.eng.play_set_temperatures(tab)
-
-    def _temps(self, plies):
-        """-> T per row: the schedule's entry of the row's ply (the last one beyond it), or the one temperature."""
-        tab = self.temperature_schedule
-        if tab is None:
-            return self.temperature
-        return tab[np.minimum(np.asarray(plies, dtype=np.int64), tab.size - 1)]
-
-    def _pis_moves(self, visits, legal, plies, uniforms):
-        """batch_pi_and_moves at the rows' temperatures; the stored pi at pi_temperature where one is set."""
-        pis, chosen = batch_pi_and_moves(visits, legal, self._temps(plies), uniforms)
-        if self.pi_temperature is not None:
-            pis = batch_pi_and_moves(visits, legal, self.pi_temperature, uniforms)[0]
-        return pis, chosen
-
-    def _full(self, game_ids, plies):
-        """-> bool per (game, ply): the search has the full budget under the current cap."""
-        return cap_uniform(self.seed, game_ids, plies) < self.playout_cap[1]
-
-    @property
-    def resign_on(self):
-        return not np.isnan(self.resign_threshold)
+        self._apply_option(self._temperature_option())
 
     def set_resign(self, threshold, disabled_frac=0.1):
         """AlphaGo Zero's resignation for every lane (an opt-in extension: the reference plays every game to its end): the player to
@@ -585,30 +628,36 @@ class BatchedSelfPlay(object):
         if not 0.0 <= disabled_frac <= 1.0:
             raise ValueError('disabled_frac %r not in [0, 1]' % disabled_frac)
         self.resign_threshold, self.resign_disabled_frac = threshold, disabled_frac
-        if not getattr(self, '_dev_on', False):
+        self._apply_option(self._resign_option())
+
+    # An option of the device move step: (on here, the engine's attribute that says it is on there, how to hand it to an engine)
+    def _resign_option(self):
+        return self.resign_on, 'play_resign_on', lambda eng: eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
+
+    def _cap_option(self):
+        return self.playout_cap is not None, 'play_cap_on', lambda eng: eng.play_set_cap(*(self.playout_cap or (1, float('nan'))))
+
+    def _temperature_option(self):
+        return self.temperature_schedule is not None, 'play_temp_on', lambda eng: eng.play_set_temperatures(self.temperature_schedule)
+
+    def _apply_option(self, option, attaching=None):
+        """Hand an option to the lanes' engines after its setter, or (``attaching``: a lane, inside device_attach's stream context)
+        before that lane's whole-move graph is captured, so that the graph reads the option's buffer.  After a setter: nothing while
+        the move step is not attached; an option turned on over a graph captured without it attaches again with the same settings;
+        otherwise the lanes where it is on, or being turned on, take the new value as they are."""
+        on, flag, apply = option
+        if attaching is not None:
+            if on:
+                apply(attaching.eng)
+        elif not self._dev_on:
             return
-        if not np.isnan(threshold) and any(lane.move_graph is not None and not lane.eng.play_resign_on for lane in self.lanes):
-            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)   # (applies the rule before the capture)
-            return
-        self._apply_resign()
-
-    def _apply_resign(self):
-        for lane in self.lanes:
-            if self.resign_on or lane.eng.play_resign_on:
-                with self._on(lane):
-                    lane.eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
-
-    def _calibration(self, game_ids):
-        """-> bool per game: resignation disabled (a calibration game) under the current rule."""
-        return resign_uniform(self.seed, game_ids) < self.resign_disabled_frac
-
-    def _resign_record(self, stats, winner, no_resign, resigned):
-        """Trajectory keywords of a finished game under the rule (none without it)."""
-        if not self.resign_on:
-            return {}
-        stats = np.asarray(stats, dtype=np.float32)
-        return dict(resigned=resigned, no_resign=no_resign, resign_stats=stats,
-                    fp_margin=fp_margin(stats, winner) if no_resign else np.nan)
+        elif on and any(lane.move_graph is not None and not getattr(lane.eng, flag) for lane in self.lanes):
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)
+        else:
+            for lane in self.lanes:
+                if on or getattr(lane.eng, flag):
+                    with self._on(lane):
+                        apply(lane.eng)
 
     @classmethod
     def for_network(cls, net_module, board, n_in_row, n_games, n_playout, c_puct=5.0, device='cuda:0',
@@ -751,7 +800,7 @@ class BatchedSelfPlay(object):
             keys = _splitmix64(_splitmix64(np.uint64(self.seed) ^ np.uint64(0x6E6F697365000000)) ^ self.slot_game.astype(np.uint64))
         for lane in self.lanes:
             if mask[lane.slots].any():
-                if getattr(lane, 'primed', False):
+                if lane.primed:
                     # a pipelined run that stopped early (max_moves) left the next move's simulations enqueued: they end
                     # on the old roots, and the trees reset here must not be taken for searched ones
                     lane.stream.synchronize()
@@ -767,11 +816,11 @@ class BatchedSelfPlay(object):
                 lane.eng.set_active(active[lane.slots])
 
     def _simulate(self):
-        if any(getattr(lane, 'primed', False) for lane in self.lanes):
+        if any(lane.primed for lane in self.lanes):
             # a lane primed by play_move_pipelined has the coming move's simulations in flight already: searching it again
             # would double its visits -- the lanes are taken one by one, the primed ones as they are
             for lane in self.lanes:
-                if not getattr(lane, 'primed', False):
+                if not lane.primed:
                     self._simulate_lane(lane)
                 lane.primed = False
             return
@@ -785,7 +834,7 @@ class BatchedSelfPlay(object):
             full, n = divmod(n, per)
             for _ in range(full):
                 # timing samples: every k-th chunk of the run (counted across moves) is launched eagerly
-                c = self._chunks_done = getattr(self, '_chunks_done', -1) + 1
+                c = self._chunks_done = self._chunks_done + 1
                 eager = self.eager_every > 0 and c % self.eager_every == 0
                 for lane in self.lanes:
                     with self._on(lane):
@@ -822,7 +871,7 @@ class BatchedSelfPlay(object):
                 per = self.eng.graph_chunk(self.sims_per_graph)
                 full, n = divmod(n, per)
                 for _ in range(full):
-                    c = self._chunks_done = getattr(self, '_chunks_done', -1) + 1
+                    c = self._chunks_done = self._chunks_done + 1
                     if self.eager_every > 0 and c % self.eager_every == 0:
                         lane.eng.sim_chunk(lane.evaluator, per)
                     else:
@@ -917,12 +966,12 @@ class BatchedSelfPlay(object):
         the simulations of the coming move are already in flight.  Results are those of play_move(): games are
         independent and their uniforms are keyed by (game, ply)."""
         for lane in self.lanes:
-            if not getattr(lane, 'primed', False) and (self.slot_game[lane.slots] >= 0).any():
+            if not lane.primed and (self.slot_game[lane.slots] >= 0).any():
                 self._simulate_lane(lane)
                 lane.primed = True
         done_all = []
         for lane in self.lanes:
-            if not getattr(lane, 'primed', False):
+            if not lane.primed:
                 continue
             done = self._finish_lane(lane)
             lane.primed = False
@@ -956,11 +1005,11 @@ class BatchedSelfPlay(object):
         leaves their NEXT search finished on the device as well): the slots become idle, their trees are reset, no lane stays
         primed.  run() starts with this: games of an earlier run are neither played on nor searched a second time on top of a
         finished search."""
-        if not (self.slot_game >= 0).any() and not any(getattr(lane, 'primed', False) for lane in self.lanes):
+        if not (self.slot_game >= 0).any() and not any(lane.primed for lane in self.lanes):
             return
         self.slot_game[:] = -1
         for lane in self.lanes:
-            if getattr(lane, 'primed', False):
+            if lane.primed:
                 lane.stream.synchronize()
                 lane.primed = False
             self._retire_lane(lane)
@@ -1036,7 +1085,7 @@ class BatchedSelfPlay(object):
         t = self.torch
         from ._hip import PLAY_RECORD_WORDS
         dev = self.eng.device
-        if getattr(self, '_dev_on', False):
+        if self._dev_on:
             self.device_stop()
         self._attach_kw = dict(ring_steps=ring_steps, depth=depth, copy_every=copy_every, stall_margin=stall_margin, move_graphs=move_graphs)
         t.cuda.synchronize(dev)
@@ -1052,14 +1101,11 @@ class BatchedSelfPlay(object):
             with self._on(lane):
                 lane.eng.play_attach(self.seed, self.temperature, self._queue_ids, self._queue_ctl, ring_steps=ring_steps,
                                      stall_margin=stall_margin)
-                if self.resign_on:   # (before the capture: the graph's draw then reads the rule's buffer -- set_resign)
-                    lane.eng.play_set_resign(self.resign_threshold, self.resign_disabled_frac)
+                self._apply_option(self._resign_option(), attaching=lane)
                 lane.eng.set_playouts(None)   # (the device's budgets, not a host-driven run's last counts)
                 lane.eng.play_set_cap_order(self.cap_longest_first)
-                if self.playout_cap is not None:   # (likewise: the graph's search then reads the budgets -- set_playout_cap)
-                    lane.eng.play_set_cap(*self.playout_cap)
-                if self.temperature_schedule is not None:   # (likewise: the graph's draw then reads the table -- set_temperature_schedule)
-                    lane.eng.play_set_temperatures(self.temperature_schedule)
+                self._apply_option(self._cap_option(), attaching=lane)
+                self._apply_option(self._temperature_option(), attaching=lane)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
@@ -1069,14 +1115,8 @@ class BatchedSelfPlay(object):
             lane.inflight = []          # [(rows, event)] read-backs enqueued, oldest first
             lane.last_running = -1      # RUNNING records in the last row read (-1: none read yet)
             lane.primed = False
-        max_plies = self.eng.n_cells
-        self._pi_buf = np.empty((self.n_slots, max_plies, self.eng.n_actions), dtype=np.float64)   # (pages are touched as games grow)
-        self._mv_buf = np.zeros((self.n_slots, max_plies), dtype=np.int32)
-        self._st_buf = np.zeros((self.n_slots, max_plies), dtype=np.float32)   # resignation statistic per searched ply (word 7)
-        self._fl_buf = np.zeros((self.n_slots, max_plies), dtype=bool)         # full budget per searched ply (PLAY_FULL)
-        self._stalls = {}               # slot -> (game id, ply, pi, move): decided here, waiting for the device to take it
+        self.book.clear()
         self.stalls_resolved = 0
-        self.slot_game[:] = -1
         self._dev_on = True
         t.cuda.synchronize(dev)
 
@@ -1150,8 +1190,7 @@ class BatchedSelfPlay(object):
         return done
 
     def _harvest(self, lane, keep):
-        from ._hip import (PLAY_ENDED, PLAY_FULL, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED,
-                           PLAY_STALLED, PLAY_WOULD_RESIGN, HipError)
+        """The lane's log rows whose read-back has passed (all but the ``keep`` newest, and those only if ready) -> the finished games."""
         rows = []
         while lane.inflight and (len(lane.inflight) > keep or lane.inflight[0][1].query()):
             batch, ev = lane.inflight.pop(0)
@@ -1159,125 +1198,14 @@ class BatchedSelfPlay(object):
             rows.extend(batch)
         if not rows:
             return []
-        eng, lo, W0 = lane.eng, lane.slots.start, PLAY_RECORD_WORDS
-        G = eng.n_games
-        rec = lane.host_np[rows]                                # [rows, G, words] (a copy: the pinned rows may be overwritten from now on)
-        flags = rec[:, :, 4] & 0xFFFF
-        lane.last_running = int(((flags[-1] & PLAY_RUNNING) != 0).sum())
-        row_i, g_i = np.nonzero(flags & PLAY_RUNNING)           # (row-major: a slot's records in move order)
-        if row_i.size == 0:
-            return []
-        rec, flags = rec[row_i, g_i], flags[row_i, g_i]
-        slots = lo + g_i
-        gids = rec[:, 0].astype(np.uint32).astype(np.int64) | (rec[:, 1].astype(np.int64) << 32)
-        plies, moves = rec[:, 2].astype(np.int64), rec[:, 3]
-        visits = rec[:, W0:]
-        legal = visits >= 0
-        # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
-        pis, chosen = self._pis_moves(np.where(legal, visits, 0), legal, plies, move_uniform(self.seed, gids, plies))
-        not_plain = (flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED)) != 0
-        wrong = ~not_plain & (chosen != moves)
-        if wrong.any():
-            bad = np.nonzero(wrong)[0][0]
-            raise HipError('the move drawn on the device (%d) is not numpy\'s (%d): game %d, ply %d' % (moves[bad], chosen[bad], gids[bad], plies[bad]))
-        searched = (flags & PLAY_SEARCHED) != 0
-        fulls = (flags & PLAY_FULL) != 0
-        if self.playout_cap is not None:
-            # the device's budget flag against this side's draw on the same key
-            bad = searched & (fulls != self._full(gids, plies))
-            if bad.any():
-                i = np.nonzero(bad)[0][0]
-                raise HipError('the device\'s budget flag 0x%x of game %d ply %d disagrees with cap_uniform = %r, p_full %r' % (
-                    flags[i], gids[i], plies[i], float(cap_uniform(self.seed, gids[i], plies[i])), self.playout_cap[1]))
-            self.sims_done += int(np.where(fulls, eng.n_playout, self.playout_cap[0])[searched].sum())
-            self.full_plies += int((fulls & searched).sum())
-        else:
-            self.sims_done += eng.n_playout * int(searched.sum())
-            self.full_plies += int(searched.sum())
-        stats = np.ascontiguousarray(rec[:, 7]).view(np.float32)
-        if self.resign_on:
-            # the device's decision against its logged statistic s (float32 of the fp64 s it compared): resigned / would resign
-            # => s <= threshold, played on => s >= threshold or NaN; the calibration flag against this side's draw
-            t32 = np.float32(self.resign_threshold)
-            calib = self._calibration(gids)
-            fired = (flags & (PLAY_RESIGNED | PLAY_WOULD_RESIGN)) != 0
-            with np.errstate(invalid='ignore'):
-                bad = searched & (((flags & PLAY_NO_RESIGN) != 0) != calib)
-                bad |= searched & fired & ~(stats <= t32)
-                bad |= searched & ~fired & (stats < t32)
-                bad |= ((flags & PLAY_RESIGNED) != 0) & calib
-            if bad.any():
-                i = np.nonzero(bad)[0][0]
-                raise HipError('the device\'s resignation flags 0x%x of game %d ply %d disagree with s = %r, threshold %r, calibration %s' % (
-                    flags[i], gids[i], plies[i], float(stats[i]), self.resign_threshold, bool(calib[i])))
-            self.resign_would += int(((flags & PLAY_WOULD_RESIGN) != 0).sum())
-        special = not_plain | ((flags & PLAY_ENDED) != 0) | (plies == 0)
-        done = []
-        first = np.searchsorted(row_i, np.arange(len(rows) + 1))   # records of row r: first[r] .. first[r + 1]
-        for r in range(len(rows)):
-            a, b = int(first[r]), int(first[r + 1])
-            if a == b:
-                continue
-            easy = np.nonzero(~special[a:b])[0] + a
-            if easy.size:   # a move in the middle of a game: the whole row at once
-                s = slots[easy]
-                if (self.slot_game[s] != gids[easy]).any() or (self.slot_ply[s] != plies[easy]).any():
-                    i = easy[np.nonzero((self.slot_game[s] != gids[easy]) | (self.slot_ply[s] != plies[easy]))[0][0]]
-                    raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (
-                        slots[i], gids[i], plies[i], self.slot_game[slots[i]], self.slot_ply[slots[i]]))
-                self._pi_buf[s, plies[easy]] = pis[easy]
-                self._mv_buf[s, plies[easy]] = moves[easy]
-                self._st_buf[s, plies[easy]] = stats[easy]
-                self._fl_buf[s, plies[easy]] = fulls[easy]
-                self.slot_ply[s] += 1
-                self.moves_done += int(easy.size)
-            for i in np.nonzero(special[a:b])[0] + a:
-                s, f, gid, ply = int(slots[i]), int(flags[i]), int(gids[i]), int(plies[i])
-                if f & PLAY_SEARCHED:   # (a stall's searched record comes before the resolved one of its ply)
-                    self._st_buf[s, ply] = stats[i]
-                    self._fl_buf[s, ply] = fulls[i]
-                if f & PLAY_STALLED:
-                    known = self._stalls.get(s)
-                    if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
-                        self._stalls[s] = (gid, ply, pis[i], int(chosen[i]))
-                        with self._on(lane):
-                            eng.play_resolve(s - lo, int(chosen[i]))
-                    continue
-                pi, mv = pis[i], int(moves[i])
-                if f & PLAY_RESOLVED:
-                    known = self._stalls.pop(s, None)
-                    if known is None or known[:2] != (gid, ply) or known[3] != mv:
-                        raise HipError('slot %d: the device resolved game %d ply %d with move %d, the host had decided %r' % (s, gid, ply, mv, known))
-                    pi = known[2]
-                    self.stalls_resolved += 1
-                if ply == 0:   # the slot has started this game
-                    self.slot_game[s], self.slot_ply[s] = gid, 0
-                    self._started += 1
-                if self.slot_game[s] != gid or self.slot_ply[s] != ply:
-                    raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (s, gid, ply, self.slot_game[s], self.slot_ply[s]))
-                if f & PLAY_RESIGNED:   # the game ends without a move: the plies before it
-                    winner = ((int(rec[i, 4]) >> 16) & 3) - 1
-                    extra = self._resign_record(self._st_buf[s, :ply + 1].copy(), winner, False, True)
-                    if self.playout_cap is not None:
-                        extra['full'] = self._fl_buf[s, :ply + 1].copy()
-                    done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :ply].tolist(), self._pi_buf[s, :ply].copy(),
-                                           winner, game=eng.game, **extra))
-                    self.slot_game[s] = -1
-                    continue
-                self._pi_buf[s, ply] = pi
-                self._mv_buf[s, ply] = mv
-                self.slot_ply[s] += 1
-                self.moves_done += 1
-                if f & PLAY_ENDED:
-                    winner = ((int(rec[i, 4]) >> 16) & 3) - 1
-                    n = ply + 1
-                    extra = self._resign_record(self._st_buf[s, :n].copy(), winner, bool(self._calibration(gid)), False)
-                    if self.playout_cap is not None:
-                        extra['full'] = self._fl_buf[s, :n].copy()
-                    done.append(Trajectory(gid, eng.board_size, eng.n_in_row, self._mv_buf[s, :n].tolist(), self._pi_buf[s, :n].copy(), winner,
-                                           game=eng.game, **extra))
-                    self.slot_game[s] = -1
+        # (host_np[rows] is a copy: the pinned rows may be overwritten from now on)
+        done, lane.last_running = self.read_rows(lane.host_np[rows], lane.slots.start)
         return done
+
+    def _resolve(self, slot, move):
+        lane = next(lane for lane in self.lanes if lane.slots.start <= slot < lane.slots.stop)
+        with self._on(lane):
+            lane.eng.play_resolve(slot - lane.slots.start, move)
 
     def device_stop(self):
         """Drop every game and every row in flight: all slots idle (a run that stops early)."""
@@ -1287,8 +1215,7 @@ class BatchedSelfPlay(object):
                 lane.eng.play_stop()
             lane.stream.synchronize()
             lane.inflight, lane.uncopied, lane.last_running, lane.primed = [], [], 0, False
-        self.slot_game[:] = -1
-        self._stalls = {}
+        self.book.clear()
         self._queue_len = self._started = 0
 
     def run_device(self, game_ids, max_moves=None, on_finished=None):
@@ -1296,7 +1223,7 @@ class BatchedSelfPlay(object):
         games found finished after every enqueued move, while the GPU searches on (a consumer's per-game work -- the trainer's
         observation planes and replay-buffer entries -- then costs the round nothing)."""
         game_ids = list(game_ids)
-        if not getattr(self, '_dev_on', False):
+        if not self._dev_on:
             self.device_attach(queue_capacity=max(len(game_ids), 1))
         elif len(game_ids) > self._queue_ids.numel():
             self.device_attach(queue_capacity=len(game_ids), **self._attach_kw)   # (a longer queue: attach again, same settings)

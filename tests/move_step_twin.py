@@ -56,12 +56,12 @@ class Twin(object):
                 self.search()
             row = self.eng.play_move()
         torch.cuda.synchronize()
+        from rlzero_amd import playlog
         rows = self.eng.play_log[row].cpu().numpy().copy()
-        running = (rows[:, 4] & 1) != 0   # (an idle slot's row holds nothing to read; which slot stays idle is the refill's race)
-        gid = (rows[:, 0].astype(np.int64) & 0xFFFFFFFF) | (rows[:, 1].astype(np.int64) << 32)
-        slots = np.nonzero(running)[0]
-        self.slot_of = slots[np.argsort(gid[slots], kind='stable')]
-        assert len(set(gid[slots].tolist())) == len(slots)
+        # (an idle slot's row holds nothing to read; which slot stays idle is the refill's race)
+        slots, d, _ = playlog.running(rows[None])
+        self.slot_of = slots[np.argsort(d.game, kind='stable')]
+        assert len(set(d.game.tolist())) == len(slots)
         return rows[self.slot_of]
 
     def modes(self):

@@ -223,6 +223,8 @@ def _sp(board, n_games, n_playout, **extra):
 
 def _spy(sp):
     """Records of the device loop as _harvest consumes them -> {(game id, ply): (flags, N(root))} of the searched ones."""
+    from rlzero_amd import playlog
+    from rlzero_amd._hip import PLAY_SEARCHED
     seen, inner = {}, sp._harvest
 
     def harvest(lane, keep):
@@ -232,10 +234,9 @@ def _spy(sp):
         for r in before:
             if r in left:
                 continue
-            for rec in lane.host_np[r]:
-                if rec[4] & 1 and rec[4] & 16:   # RUNNING, SEARCHED
-                    gid = (int(rec[0]) & 0xFFFFFFFF) | (int(rec[1]) << 32)
-                    seen[(gid, int(rec[2]))] = (int(rec[4]) & 0xFFFF, int(rec[5]))
+            d = playlog.running(lane.host_np[r][None])[1]
+            for i in np.nonzero(d.flags & PLAY_SEARCHED)[0]:
+                seen[(int(d.game[i]), int(d.ply[i]))] = (int(d.flags[i]), int(d.root_n[i]))
         return out
     sp._harvest = harvest
     return seen

@@ -85,36 +85,31 @@ def test_games_against_the_oracle():
 
 def _check_rows(rows, temps, stats):
     """Every non-stalled searched record: the device's move is numpy's on the logged visits at the T of the record's ply."""
-    from rlzero_amd._hip import PLAY_RECORD_WORDS, PLAY_SEARCHED, PLAY_STALLED
+    from rlzero_amd import playlog
+    from rlzero_amd._hip import PLAY_SEARCHED, PLAY_STALLED
     from rlzero_amd.selfplay import batch_pi_and_moves, move_uniform
     from move_step_twin import SEED as TWIN_SEED
-    flags = rows[:, 4] & 0xFFFF
-    rows = rows[((flags & PLAY_SEARCHED) != 0) & ((flags & PLAY_STALLED) == 0)]
-    if not len(rows):
+    flags = playlog.decode(rows).flags
+    d = playlog.decode(rows[((flags & PLAY_SEARCHED) != 0) & ((flags & PLAY_STALLED) == 0)])
+    if not len(d.ply):
         return
-    gids = (rows[:, 0].astype(np.int64) & 0xFFFFFFFF) | (rows[:, 1].astype(np.int64) << 32)
-    plies = rows[:, 2].astype(np.int64)
-    visits = rows[:, PLAY_RECORD_WORDS:]
-    legal = visits >= 0
-    us = move_uniform(TWIN_SEED, gids, plies)
-    T = temps[np.minimum(plies, len(temps) - 1)]
-    want = batch_pi_and_moves(np.where(legal, visits, 0), legal, T, us)[1]
-    assert want.tolist() == rows[:, 3].tolist(), (plies.tolist(), T.tolist())
-    stats['checked'] += len(rows)
+    us = move_uniform(TWIN_SEED, d.game, d.ply)
+    T = temps[np.minimum(d.ply, len(temps) - 1)]
+    want = batch_pi_and_moves(d.counts, d.legal, T, us)[1]
+    assert want.tolist() == d.move.tolist(), (d.ply.tolist(), T.tolist())
+    stats['checked'] += len(d.ply)
     # (what the draw would have been at the attach's T = 1.0: told apart from the table's at least once, below)
-    stats['not_constant'] += int((batch_pi_and_moves(np.where(legal, visits, 0), legal, 1.0, us)[1] != rows[:, 3]).sum())
+    stats['not_constant'] += int((batch_pi_and_moves(d.counts, d.legal, 1.0, us)[1] != d.move).sum())
 
 
 def _moves_under(rows, temps):
     """How many of the rows' moves numpy draws on the logged visits under ANOTHER table."""
+    from rlzero_amd import playlog
     from rlzero_amd.selfplay import batch_pi_and_moves, move_uniform
     from move_step_twin import SEED as TWIN_SEED
-    gids = (rows[:, 0].astype(np.int64) & 0xFFFFFFFF) | (rows[:, 1].astype(np.int64) << 32)
-    plies = rows[:, 2].astype(np.int64)
-    visits = rows[:, 8:]
-    legal = visits >= 0
-    T = temps[np.minimum(plies, len(temps) - 1)]
-    return int((batch_pi_and_moves(np.where(legal, visits, 0), legal, T, move_uniform(TWIN_SEED, gids, plies))[1] == rows[:, 3]).sum())
+    d = playlog.decode(rows)
+    T = temps[np.minimum(d.ply, len(temps) - 1)]
+    return int((batch_pi_and_moves(d.counts, d.legal, T, move_uniform(TWIN_SEED, d.game, d.ply))[1] == d.move).sum())
 
 
 def test_table_updates_reach_a_captured_move_graph():
