@@ -1251,7 +1251,7 @@ __global__ void k_uct_scores(const double *w, const int32_t *n, const int32_t *n
 // ------------------------------------------------------------------ the move step on the device (include/rlzero_hip.h: rz_play_*)
 struct Play {
     int64_t *game_id;          // [G] -1: idle
-    int32_t *ply, *state;      // state: 0 idle, 1 running, 2 stalled
+    int32_t *ply, *state;      // state: ry::kIdle, kRunning, kStalled
     int32_t *mailbox;          // [G] the host's move for a stalled slot, -1: none
     int32_t *keep, *stepm;     // [G] the moves of this step (update_with_move / env.step), written by k_play_draw
     int32_t *top_hwm;          // [G] the fullest a game's arena has been at the end of a search (read before update_with_move compacts it)
@@ -1260,7 +1260,7 @@ struct Play {
     int32_t *queue_ctl;        // [0] head, [1] entries valid
     int32_t *log;
     // per-ply temperature (rz_play_set_temperatures): 1 / T before ply p, padded with its last entry to the board's cell count S,
-    // then the stall margin of each ply: the configured one if positive, else 1e-10 * max(1 / T, 1) -- rz_play_attach's rule at the ply's T
+    // then the stall margin of each ply (rz_play.h: temp_entry)
     const double *inv_t_of;    // [2][S]
     int ring, words;
     uint64_t seed;
@@ -1282,41 +1282,19 @@ struct Play {
     int n_open;
     int match_on;              // rz_play_set_match in force: the kernels read the table and the pair's uniform (else never)
 };
-enum { kPlayIdle = 0, kPlayRunning = 1, kPlayStalled = 2 };
-constexpr int kStepResign = -3;   // Play::stepm of a slot whose mover resigned: k_play_apply ends the game without a step
+namespace ry = rzplay;   // rz_play.h: the move step's rules, the record and a slot's decision (tested on the CPU)
 
-// rlzero_amd/selfplay.py: move_uniform(seed, game id, ply) -- 53 high bits of a splitmix64 chain: the same bits
-__device__ __forceinline__ double play_uniform(uint64_t seed, uint64_t game, uint64_t ply) {
-    uint64_t x = mix64(seed);
-    x = mix64(x ^ game);
-    x = mix64(x ^ ply);
-    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// rlzero_amd/selfplay.py: resign_uniform(seed, game id) -- a game has resignation disabled (calibration) when it is below disabled_frac
-__device__ __forceinline__ double resign_uniform(uint64_t seed, uint64_t game) {
-    const uint64_t x = mix64(mix64(seed ^ 0x72657369676E0000ull) ^ game);
-    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// rlzero_amd/selfplay.py: cap_uniform(seed, game id, ply) -- the search before ply `ply` of a game has the full budget when it is
-// below p_full (a chain of its own: apart from the move, noise and calibration streams)
-__device__ __forceinline__ double cap_uniform(uint64_t seed, uint64_t game, uint64_t ply) {
-    const uint64_t x = mix64(mix64(mix64(seed ^ 0x706C61796F757400ull) ^ game) ^ ply);
-    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
-__device__ __forceinline__ bool cap_full(const Play &Y, int64_t gid, int ply) {
-    const double p = Y.cap[1];
-    return !isnan(p) && cap_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply) < p;
-}
+// the budget of the slot's coming search (rz_play_set_cap), read by the resident search
 __device__ __forceinline__ void cap_write(const Play &Y, int g, int64_t gid, int ply) {
-    Y.sims_of[g] = (isnan(Y.cap[1]) || cap_full(Y, gid, ply)) ? Y.n_full : (int)Y.cap[0];
+    Y.sims_of[g] = ry::budget(Y.n_full, (int)Y.cap[0], Y.cap[1], Y.seed, (uint64_t)gid, (uint64_t)ply);
 }
 
 // One wave per slot: the root's visit counts into the log, then the draw of alphazero_mcts.py:88-92,147-148 in fp64 -- taken only
 // when the uniform lies farther than `margin` from both edges of its interval (the host's numpy evaluation is the arbiter).
 // In a match (rz_play_set_match) the uniform is the pair's -- (seed, game id >> 1, 2 ply + 1) -- and the move keeps no subtree:
 // keep = -1, so k_play_apply starts the next search of the game from a fresh root; stepm stays the move.
+// The kernel gathers the counts and computes log, the wave maximum and exp; the draw, the resignation rule and what the step
+// changes are rz_play.h's (ry::draw, ry::resign_rule, ry::decide), and lane 0 writes all of it at the end.
 __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     __shared__ double sh_e[kWave * kWords];
     const int g = blockIdx.x;
@@ -1324,152 +1302,86 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     const int step = Y.step_ab[0];
     if (g == 0 && lane == 0) Y.step_ab[1] = step;
     int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
-    const int state = Y.state[g];
-    if (state == kPlayIdle) {
-        if (lane == 0) {
-            rec[4] = 0;
-            Y.keep[g] = -2;
-            Y.stepm[g] = -1;
-        }
-        return;
-    }
-    // the root's children by action (k_root_children)
-    const int arena = E.cur_arena[g];
-    const int4 *R = arena_records(E, g, arena);
-    uint64_t st[2][kWords], occ[kWords];
-    load_board(E.root_stones, g, st);
+    ry::SlotIn in = {};
+    in.state = Y.state[g];
+    if (in.state != ry::kIdle) {
+        // the root's children by action (k_root_children)
+        const int arena = E.cur_arena[g];
+        const int4 *R = arena_records(E, g, arena);
+        uint64_t st[2][kWords], occ[kWords];
+        load_board(E.root_stones, g, st);
 #pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    const int4 lo = R[0];
-    const bool expanded = rec_k(lo) > 0;
-    const int fc = lo.y;
-    const int nv = expanded ? lo.z : 0;
-    int before = 0;
-    int cnt[kWords];
-    bool legal[kWords];
-    double x[kWords];
-    double mx = -INFINITY;
-    // the ply's temperature (rz_play_set_temperatures): the table is read only once it has been set; a stalled slot keeps its ply, so
-    // its move is judged at the same T
-    const int ply = Y.ply[g];
-    const int tp = ply < 0 ? 0 : (ply < E.S ? ply : E.S - 1);   // (ply < S always holds)
-    const double inv_t = Y.temp_on ? Y.inv_t_of[tp] : Y.inv_t;
-    const double margin = Y.temp_on ? Y.inv_t_of[E.S + tp] : Y.margin;
-    // resignation (rz_play_set_resign): read only once it has been configured -- the rule-free path has no extra memory traffic
-    const double thr = Y.resign_on ? Y.resign[0] : NAN;
-    const bool rs = !isnan(thr) && state == kPlayRunning;
-    double qb = -INFINITY;   // max W / N over the visited children (rz_root_values)
+        for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
+        const Legal L = legal_of(E, occ, lane);
+        const int4 lo = R[0];
+        const bool expanded = rec_k(lo) > 0;
+        const int fc = lo.y;
+        const int nv = expanded ? lo.z : 0;
+        int before = 0;
+        int cnt[kWords];
+        bool legal[kWords];
+        double x[kWords];
+        double mx = -INFINITY;
+        // the ply's temperature (rz_play_set_temperatures): the table is read only once it has been set; a stalled slot keeps its ply,
+        // so its move is judged at the same T
+        const int ply = Y.ply[g];
+        const int tp = ply < 0 ? 0 : (ply < E.S ? ply : E.S - 1);   // (ply < S always holds)
+        const double inv_t = Y.temp_on ? Y.inv_t_of[tp] : Y.inv_t;
+        const double margin = Y.temp_on ? Y.inv_t_of[E.S + tp] : Y.margin;
+        // resignation (rz_play_set_resign): read only once it has been configured -- the rule-free path has no extra memory traffic
+        const double thr = Y.resign_on ? Y.resign[0] : NAN;
+        const bool rs = !isnan(thr) && in.state == ry::kRunning;
+        double qb = -INFINITY;   // max W / N over the visited children (rz_root_values)
 #pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int r = lane_action_rank(E, occ, L, j, lane, before);
-        const int a = 64 * j + lane;
-        legal[j] = a < E.A && r >= 0;
-        cnt[j] = (legal[j] && r < nv) ? R[2 * (fc + r)].x : 0;
-        if (a < E.A) rec[RZ_PLAY_RECORD_WORDS + a] = legal[j] ? cnt[j] : -1;
-        x[j] = legal[j] ? inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
-        mx = fmax(mx, x[j]);
-        if (rs && cnt[j] > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)cnt[j]);
-    }
-    const int64_t gid = Y.game_id[g];
-    if (lane == 0) {
-        rec[0] = (int32_t)(uint32_t)(uint64_t)gid;
-        rec[1] = (int32_t)((uint64_t)gid >> 32);
-        rec[2] = ply;
-        rec[5] = lo.x;
-        rec[7] = 0;
-    }
-    if (state == kPlayStalled) {
-        const int mv = Y.mailbox[g];
-        if (lane == 0) {
-            if (mv >= 0) {   // the host has decided (rz_play_resolve)
-                rec[3] = mv;
-                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_RESOLVED;
-                rec[6] = 0;
-                Y.mailbox[g] = -1;
-                Y.state[g] = kPlayRunning;
-                Y.ply[g] = ply + 1;
-                E.active[g] = 1;
-                Y.keep[g] = Y.match_on ? -1 : mv;   // (a match searches every move from a fresh root: reset_player, :158)
-                Y.stepm[g] = mv;
-            } else {
-                rec[3] = -1;
-                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_STALLED;
-                rec[6] = 0;
-                Y.keep[g] = -2;
-                Y.stepm[g] = -1;
-            }
+        for (int j = 0; j < kWords; ++j) {
+            const int r = lane_action_rank(E, occ, L, j, lane, before);
+            const int a = 64 * j + lane;
+            legal[j] = a < E.A && r >= 0;
+            cnt[j] = (legal[j] && r < nv) ? R[2 * (fc + r)].x : 0;
+            if (a < E.A) rec[RZ_PLAY_RECORD_WORDS + a] = legal[j] ? cnt[j] : -1;
+            x[j] = legal[j] ? inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
+            mx = fmax(mx, x[j]);
+            if (rs && cnt[j] > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)cnt[j]);
         }
-        return;
-    }
-    // wave maximum of x (doubles: two 32-bit halves through the shuffle)
-    for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) sh_e[64 * j + lane] = legal[j] ? exp(x[j] - mx) : 0.0;   // :12
-    int extra = 0;   // RZ_PLAY_NO_RESIGN / RZ_PLAY_WOULD_RESIGN of a calibration game
-    // (rz_play_set_cap: the budget of the search behind this record -- what k_play_apply / k_play_cap wrote into sims_of for it)
-    const int full = (Y.cap_on && lane == 0 && cap_full(Y, gid, ply)) ? RZ_PLAY_FULL : 0;
-    if (rs) {
-        for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
-        if (lane == 0) {
-            const double n_root = (double)lo.x;
-            const double v_root = lo.x > 0 ? -(rec_w(R[1]) / n_root) : NAN;
-            const double q_best = qb > -INFINITY ? qb : NAN;
-            const double s = (isnan(v_root) || isnan(q_best)) ? NAN : fmax(v_root, q_best);
-            rec[7] = __float_as_int((float)s);
-            const bool fire = v_root < thr && q_best < thr;
-            if (resign_uniform(Y.seed, (uint64_t)gid) < Y.resign[1]) {
-                extra = RZ_PLAY_NO_RESIGN | (fire ? RZ_PLAY_WOULD_RESIGN : 0);
-            } else if (fire) {   // the mover resigns: no draw; k_play_apply ends the game
-                rec[3] = -1;
-                rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_ENDED | RZ_PLAY_RESIGNED | full | ((1 - ply % 2) + 1) << 16;
-                rec[6] = 0;
-                Y.keep[g] = -2;
-                Y.stepm[g] = kStepResign;
-                extra = -1;
-            }
-        }
-    }
-    __syncthreads();
-    if (lane == 0 && extra >= 0) {
-        // cumsum in action order (numpy's cumsum is sequential too), then the first interval whose upper edge exceeds u x total
-        double total = 0.0;
-        for (int a = 0; a < E.A; ++a) total += sh_e[a];
-        // (a match: the uniform of the PAIR and of the second of get_action's two draws, alphazero_mcts.py:157)
-        const double u = Y.match_on ? play_uniform(Y.seed, (uint64_t)gid >> 1, 2ull * (uint64_t)ply + 1ull)
-                                    : play_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply);
-        const double target = u * total;
-        double c = 0.0, below = 0.0;
-        int chosen = -1;
-        for (int a = 0; a < E.A; ++a) {
-            const double e = sh_e[a];
-            if (e > 0.0 && c + e > target) {
-                chosen = a;
-                below = c;
-                c += e;
-                break;
-            }
-            c += e;
-        }
-        double rel = 0.0;
-        if (chosen >= 0) rel = fmin(target - below, c - target) / total;
-        const bool ok = chosen >= 0 && total > 0.0 && rel > margin;
-        rec[6] = __float_as_int((float)rel);
-        if (ok) {
-            rec[3] = chosen;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | extra | full;
-            Y.ply[g] = ply + 1;
-            Y.keep[g] = Y.match_on ? -1 : chosen;
-            Y.stepm[g] = chosen;
+        const uint64_t gid = (uint64_t)Y.game_id[g];
+        in.game = (int64_t)gid;
+        in.ply = ply;
+        in.root_n = lo.x;
+        in.match = Y.match_on != 0;
+        if (in.state == ry::kStalled) {
+            in.mail = Y.mailbox[g];
         } else {
-            rec[3] = -1;
-            rec[4] = RZ_PLAY_RUNNING | RZ_PLAY_SEARCHED | RZ_PLAY_STALLED | extra | full;
-            Y.state[g] = kPlayStalled;
-            E.active[g] = 0;   // the coming searches skip the slot until the host has decided
-            Y.keep[g] = -2;
-            Y.stepm[g] = -1;
+            // wave maximum of x (doubles: two 32-bit halves through the shuffle)
+            for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+#pragma unroll
+            for (int j = 0; j < kWords; ++j) sh_e[64 * j + lane] = legal[j] ? exp(x[j] - mx) : 0.0;   // :12
+            if (rs)
+                for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
+            __syncthreads();
+            if (lane == 0) {
+                // (rz_play_set_cap: the budget of the search behind this record -- what k_play_apply / k_play_cap wrote into sims_of)
+                in.full = Y.cap_on ? ry::full_flag(Y.cap[1], Y.seed, gid, (uint64_t)ply) : 0;
+                in.resign_on = rs;
+                if (rs) {
+                    in.resign = ry::resign_rule(lo.x, rec_w(R[1]), qb, thr);
+                    in.calibration = ry::resign_uniform(Y.seed, gid) < Y.resign[1];
+                }
+                if (ry::needs_draw(in)) {
+                    const double u = in.match ? ry::match_uniform(Y.seed, gid, (uint64_t)ply) : ry::move_uniform(Y.seed, gid, (uint64_t)ply);
+                    in.draw = ry::draw(sh_e, E.A, u, margin);
+                }
+            }
         }
     }
+    if (lane != 0) return;
+    const ry::SlotOut o = ry::decide(in);
+    ry::write_record(rec, in, o);
+    Y.keep[g] = o.keep;
+    Y.stepm[g] = o.stepm;
+    if (o.clear_mail) Y.mailbox[g] = -1;
+    if (o.state != in.state) Y.state[g] = o.state;
+    if (o.ply != in.ply) Y.ply[g] = o.ply;
+    if (o.active >= 0) E.active[g] = (uint8_t)o.active;
 }
 
 // The rest of a move in ONE launch, one wave per slot: update_with_move with the move just drawn (advance_body: before the board
@@ -1495,10 +1407,10 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     if (mv >= 0) step_body(E, g, lane, mv, who, over);   // (idle and stalled slots make no move)
     if (lane != 0) return;
     if (drawn && E.pend != nullptr) E.pend[g] = 0;
-    if (state == kPlayRunning && ((mv >= 0 && over) || mv == kStepResign)) {
+    if (state == ry::kRunning && ((mv >= 0 && over) || mv == ry::kStepResign)) {
         int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
-        if (mv >= 0) rec[4] |= RZ_PLAY_ENDED | ((who + 1) << 16);   // (a resignation's record is complete: k_play_draw)
-        state = kPlayIdle;
+        if (mv >= 0) rec[ry::kRecFlags] |= ry::ended_flags(who);   // (a resignation's record is complete: k_play_draw)
+        state = ry::kIdle;
         Y.state[g] = state;
         Y.game_id[g] = -1;
         E.active[g] = 0;
@@ -1506,9 +1418,9 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     }
     Y.stepm[g] = -1;
     Y.keep[g] = -2;
-    if (state != kPlayIdle) {
+    if (state != ry::kIdle) {
         // the budget of the slot's coming search (a stalled slot is not searched; k_play_draw has counted the ply already)
-        if (Y.cap_on && state == kPlayRunning) cap_write(Y, g, Y.game_id[g], Y.ply[g]);
+        if (Y.cap_on && state == ry::kRunning) cap_write(Y, g, Y.game_id[g], Y.ply[g]);
         return;
     }
     int head = Y.queue_ctl[0];
@@ -1524,7 +1436,7 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     if (gid < 0) return;
     Y.game_id[g] = gid;
     Y.ply[g] = 0;
-    Y.state[g] = kPlayRunning;
+    Y.state[g] = ry::kRunning;
     Y.mailbox[g] = -1;
     if (Y.match_on) {   // the pair's opening; plies count from it
         const long long o = (long long)((gid >> 1) % Y.n_open);
@@ -1537,7 +1449,7 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
         E.root_last[g] = -1;
     }
     fresh_root(E, g, E.cur_arena[g], 0);
-    E.noise_key[g] = mix64(mix64(Y.seed ^ 0x6E6F697365000000ull) ^ (uint64_t)gid);   // rlzero_amd/selfplay.py: _start
+    E.noise_key[g] = ry::noise_key(Y.seed, (uint64_t)gid);
     E.noise_ctr[g] = 0;
     E.active[g] = 1;
     if (Y.cap_on) cap_write(Y, g, gid, 0);
@@ -1549,8 +1461,7 @@ __global__ void k_play_cap(Dev E, Play Y, double n_fast, double p_full) {
     if (g >= E.n_games) return;
     const int64_t gid = Y.game_id[g];
     const int ply = Y.ply[g];
-    const bool full = isnan(p_full) || gid < 0 || cap_uniform(Y.seed, (uint64_t)gid, (uint64_t)ply) < p_full;
-    Y.sims_of[g] = full ? Y.n_full : (int)n_fast;
+    Y.sims_of[g] = gid < 0 ? Y.n_full : ry::budget(Y.n_full, (int)n_fast, p_full, Y.seed, (uint64_t)gid, (uint64_t)ply);   // (an idle slot: no draw)
     if (g == 0) {
         Y.cap[0] = n_fast;
         Y.cap[1] = p_full;
@@ -1621,7 +1532,7 @@ __global__ void k_play_side(Dev E, Play Y, int side) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.n_games) return;
     const bool a_moves = (E.root_to_move[g] == 0) == ((Y.game_id[g] & 1) == 0);
-    E.active[g] = (Y.state[g] == kPlayRunning && (side < 0 || side == (a_moves ? 0 : 1))) ? 1 : 0;
+    E.active[g] = (Y.state[g] == ry::kRunning && (side < 0 || side == (a_moves ? 0 : 1))) ? 1 : 0;
 }
 
 __global__ void k_play_resolve(Play Y, int slot, int move) { Y.mailbox[slot] = move; }
@@ -1636,7 +1547,7 @@ __global__ void k_play_no_draw(Play Y) { Y.step_ab[1] = Y.step_ab[0]; }   // rz_
 __global__ void k_play_stop(Dev E, Play Y) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.n_games) return;
-    Y.state[g] = kPlayIdle;
+    Y.state[g] = ry::kIdle;
     Y.game_id[g] = -1;
     Y.mailbox[g] = -1;
     Y.keep[g] = -2;
@@ -1680,6 +1591,7 @@ struct rz_engine {
     double *d_logtab = nullptr;
     uint64_t *d_line_tab = nullptr;   // Dev::line_tab
     Play play = {};      // rz_play_attach
+    bool play_seen = false;   // rz_play_attach has been called: `play` holds the arrays it got (all of them once play_on)
     bool play_on = false, play_drawn = false;
     long long play_steps = 0;   // move steps enqueued (rz_play_apply calls) since rz_play_attach
     // rz_set_playouts: the host's per-game simulation counts (and workgroup order) of the resident search, copies of the caller's
@@ -1976,6 +1888,12 @@ int rz_log_table_size(rz_engine *e, int64_t *count) {
     do {                                 \
         int rc__ = check_engine(e);      \
         if (rc__ != RZ_OK) return rc__;  \
+    } while (0)
+// an entry point of the move step: a valid engine that rz_play_attach has been called on
+#define RZ_ENTER_PLAY(e)                                                                  \
+    do {                                                                                  \
+        RZ_ENTER(e);                                                                      \
+        if (!(e)->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");          \
     } while (0)
 #define RZ_NEED(p)                                                       \
     do {                                                                 \
@@ -2428,26 +2346,28 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     RZ_HIP(hipDeviceSynchronize());
     Play &Y = e->play;
     const long long G = e->cfg.n_games;
-    if (Y.top_hwm == nullptr) {   // (keyed on the array allocated LAST; an earlier attach that ran out of memory is retried array by array)
+    if (!e->play_seen) {   // the first rz_play_attach of this engine: no array yet
         memset(&Y, 0, sizeof(Y));
-        if (Y.game_id == nullptr && (rc = dev_alloc(e, &Y.game_id, G)) != RZ_OK) return rc;
-        if (Y.ply == nullptr && (rc = dev_alloc(e, &Y.ply, G)) != RZ_OK) return rc;
-        if (Y.state == nullptr && (rc = dev_alloc(e, &Y.state, G)) != RZ_OK) return rc;
-        if (Y.mailbox == nullptr && (rc = dev_alloc(e, &Y.mailbox, G)) != RZ_OK) return rc;
-        if (Y.keep == nullptr && (rc = dev_alloc(e, &Y.keep, G)) != RZ_OK) return rc;
-        if (Y.stepm == nullptr && (rc = dev_alloc(e, &Y.stepm, G)) != RZ_OK) return rc;
-        if (Y.step_ab == nullptr && (rc = dev_alloc(e, &Y.step_ab, 2)) != RZ_OK) return rc;
-        if (Y.resign == nullptr && (rc = dev_alloc(e, &Y.resign, 2)) != RZ_OK) return rc;
-        if (Y.cap == nullptr && (rc = dev_alloc(e, &Y.cap, 2)) != RZ_OK) return rc;
-        if (Y.sims_of == nullptr && (rc = dev_alloc(e, &Y.sims_of, G)) != RZ_OK) return rc;
-        if (Y.order == nullptr && (rc = dev_alloc(e, &Y.order, G)) != RZ_OK) return rc;
-        if (Y.inv_t_of == nullptr) {
-            double *tab = nullptr;
-            if ((rc = dev_alloc(e, &tab, 2 * e->dev.S)) != RZ_OK) return rc;
-            Y.inv_t_of = tab;
-        }
-        if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
+        e->play_seen = true;
     }
+    // Every array once per engine: an attach that ran out of memory is retried array by array -- what an earlier call got stays.
+    if (Y.game_id == nullptr && (rc = dev_alloc(e, &Y.game_id, G)) != RZ_OK) return rc;
+    if (Y.ply == nullptr && (rc = dev_alloc(e, &Y.ply, G)) != RZ_OK) return rc;
+    if (Y.state == nullptr && (rc = dev_alloc(e, &Y.state, G)) != RZ_OK) return rc;
+    if (Y.mailbox == nullptr && (rc = dev_alloc(e, &Y.mailbox, G)) != RZ_OK) return rc;
+    if (Y.keep == nullptr && (rc = dev_alloc(e, &Y.keep, G)) != RZ_OK) return rc;
+    if (Y.stepm == nullptr && (rc = dev_alloc(e, &Y.stepm, G)) != RZ_OK) return rc;
+    if (Y.step_ab == nullptr && (rc = dev_alloc(e, &Y.step_ab, 2)) != RZ_OK) return rc;
+    if (Y.resign == nullptr && (rc = dev_alloc(e, &Y.resign, 2)) != RZ_OK) return rc;
+    if (Y.cap == nullptr && (rc = dev_alloc(e, &Y.cap, 2)) != RZ_OK) return rc;
+    if (Y.sims_of == nullptr && (rc = dev_alloc(e, &Y.sims_of, G)) != RZ_OK) return rc;
+    if (Y.order == nullptr && (rc = dev_alloc(e, &Y.order, G)) != RZ_OK) return rc;
+    if (Y.inv_t_of == nullptr) {
+        double *tab = nullptr;
+        if ((rc = dev_alloc(e, &tab, 2 * e->dev.S)) != RZ_OK) return rc;
+        Y.inv_t_of = tab;
+    }
+    if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
     Y.queue_ids = cfg->d_queue_ids;
     Y.queue_ctl = cfg->d_queue_ctl;
     Y.log = cfg->d_log;
@@ -2469,7 +2389,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.words = RZ_PLAY_RECORD_WORDS + e->dev.A;
     Y.seed = cfg->seed;
     Y.inv_t = 1.0 / cfg->temperature;
-    Y.margin = cfg->stall_margin > 0.0 ? cfg->stall_margin : 1e-10 * (Y.inv_t > 1.0 ? Y.inv_t : 1.0);
+    Y.margin = ry::stall_margin(cfg->stall_margin, Y.inv_t);
     Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
     Y.cap_on = 0;      // (and so is the playout cap: rz_play_set_cap)
     Y.match_on = 0;    // (and match mode: rz_play_set_match)
@@ -2488,16 +2408,14 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
 }
 
 int rz_play_draw(rz_engine *e, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     k_play_draw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play);
     e->play_drawn = true;
     return launched("k_play_draw");
 }
 
 int rz_play_apply(rz_engine *e, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     const Play &Y = e->play;
     if (!e->play_drawn) k_play_no_draw<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(Y);   // (the step counter k_play_draw would have handed on)
     k_play_apply<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, Y, e->play_drawn ? 1 : 0);
@@ -2509,8 +2427,7 @@ int rz_play_apply(rz_engine *e, void *stream) {
 }
 
 int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     if (!(disabled_frac >= 0.0 && disabled_frac <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_resign: disabled_frac %g not in [0, 1]", disabled_frac);
     if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_resign: a match is on (rz_play_set_match): its games are played to the end");
     k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
@@ -2519,8 +2436,7 @@ int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, voi
 }
 
 int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     Play &Y = e->play;
     const int S = e->dev.S;
     if (n < 0 || n > S) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: %d entries for a board of %d cells (a game has no more plies)", n, S);
@@ -2530,14 +2446,10 @@ int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, voi
         if (!(std::isfinite(h_temps[p]) && h_temps[p] > 0.0))
             return fail(RZ_ERR_ARG, "rz_play_set_temperatures: entry %d (%g) is not a finite positive temperature", p, h_temps[p]);
     // 1 / T on the host (the division of rz_play_attach), padded with the last entry; n == 0: the temperature of rz_play_attach.
-    // Behind it each ply's stall margin by rz_play_attach's rule.
+    // Behind it each ply's stall margin by rz_play_attach's rule (rz_play.h: temp_entry).
     for (int base = 0; base < 2 * S; base += kTempChunk) {
-        TempChunk c;
-        for (int i = 0; i < kTempChunk; ++i) {
-            const int p = (base + i) % S;
-            const double inv_t = n == 0 ? Y.inv_t : 1.0 / h_temps[p < n ? p : n - 1];
-            c.v[i] = base + i < S ? inv_t : (e->play_margin_cfg > 0.0 ? e->play_margin_cfg : 1e-10 * (inv_t > 1.0 ? inv_t : 1.0));
-        }
+        TempChunk c = {};
+        for (int i = 0; i < kTempChunk && base + i < 2 * S; ++i) c.v[i] = ry::temp_entry(base + i, S, h_temps, n, Y.inv_t, e->play_margin_cfg);
         k_play_set_temps<<<dim3(1), dim3(kTempChunk), 0, as_stream(stream)>>>(const_cast<double *>(Y.inv_t_of), c, base, 2 * S);
     }
     Y.temp_on = 1;
@@ -2551,8 +2463,7 @@ static int playouts_route_ok(rz_engine *e, const char *what) {
 }
 
 int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     int rc = playouts_route_ok(e, "rz_play_set_cap");
     if (rc != RZ_OK) return rc;
     if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_cap: a match is on (rz_play_set_match): every search of it has n_playout simulations");
@@ -2623,8 +2534,7 @@ int rz_playouts_read(rz_engine *e, int32_t *h_counts, int32_t *h_order, int32_t 
 
 int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t *d_open_to_move, const int32_t *d_open_last, int32_t n_openings,
                       void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     Play &Y = e->play;
     if (n_openings == 0) {   // off again: the slots' flags as k_play_apply leaves them
         if (Y.match_on) k_play_side<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, Y, -1);
@@ -2682,23 +2592,20 @@ int rz_active_read(rz_engine *e, uint8_t *h_active) {
 }
 
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     if (slot < 0 || slot >= e->cfg.n_games || move < 0 || move >= e->dev.A) return fail(RZ_ERR_ARG, "rz_play_resolve: slot %d / move %d out of range", slot, move);
     k_play_resolve<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play, slot, move);
     return launched("k_play_resolve");
 }
 
 int rz_play_stop(rz_engine *e, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     k_play_stop<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play);
     return launched("k_play_stop");
 }
 
 int rz_play_state(rz_engine *e, int64_t *h_game_id, int32_t *h_ply, int32_t *h_state, int64_t *h_steps) {
-    RZ_ENTER(e);
-    if (!e->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");
+    RZ_ENTER_PLAY(e);
     RZ_HIP(hipDeviceSynchronize());
     const size_t G = (size_t)e->cfg.n_games;
     if (h_game_id) RZ_HIP(hipMemcpy(h_game_id, e->play.game_id, G * 8, hipMemcpyDeviceToHost));

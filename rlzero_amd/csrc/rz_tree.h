@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "rlzero_hip.h"
+#include "rz_play.h"
 #include "rz_trace.h"
 
 #pragma clang fp contract(off)
@@ -357,13 +358,7 @@ __device__ __forceinline__ double puct(double w, int n, float prior, double sqrt
     return q + cu;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using rzplay::mix64;   // (rz_play.h: one definition for host and device)
 
 // 32-bit integer hash (two multiplies, three xor-shifts): the uniforms of the noise come from a counter hashed with it
 __device__ __forceinline__ uint32_t hash32(uint32_t x) {
