@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE (never imported by the product): a float64 model of the opt-in RZ_NET_SPLIT_F16_FP8 trunk arithmetic
-(rlzero_amd/csrc/rz_net.hip: rt::slot_r F8; the weights: rlzero_amd/csrc/rz_pack.h, pack_rows_f8) -- not of the reference, which has no such mode.  parity: this mode is
+(rlzero_amd/csrc/rz_net_rows.h: rt::slot_r F8; the weights: rlzero_amd/csrc/rz_pack.h, pack_rows_f8) -- not of the reference, which has no such mode.  parity: this mode is
 OUTSIDE the reference's f32 arithmetic by design; the model says what the device should compute, the tests say how far that is
 from PolicyValueNet.forward (rlzero/games/gomoku/policy_value_net.py:34-52) in float64.
 

@@ -1,5 +1,5 @@
-// rz_delta.h -- receptive-field ("delta") leaf evaluation for boards of 11 .. 16 rows and columns; included by rz_net.hip inside its
-// anonymous namespace, behind namespace rt (it is the arithmetic of k_trunk_rows, cell by cell).
+// rz_delta.h -- receptive-field ("delta") leaf evaluation for boards of 11 .. 16 rows and columns, on the records and the arithmetic of
+// k_trunk_rows (rz_net_rows.h, namespace rt), cell by cell; rz_net.hip includes it with the other kernel families' headers.
 //
 // Why.  The reference's search (alphazero_mcts.py:42-71 under node.py:32-42's UCT rule) is near breadth-first: at 15 x 15 / 800
 // simulations a leaf is the root position plus ONE or TWO stones (mean depth 1.74).  PolicyValueNet.forward
@@ -29,6 +29,22 @@
 // its registers, and a thread requests the base records it holds as soon as it knows it holds them -- one fetch, stored in the same
 // phase; profiles/r07/ab_prologue.txt; k_delta_res: pass -1's sets come from the selecting wave instead, leaf_windows --
 // profiles/r08/ab_windows.txt)
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "rlzero_hip.h"
+#include "rz_gather.h"
+#include "rz_net_dev.h"
+#include "rz_net_rows.h"
+#include "rz_net_split.h"
+#include "rz_trace.h"
+#include "rz_tree.h"
+#include "rz_window.h"
+
 // (issue priorities of the resident search's phases, s_setprio: its serial tree phase -- one wave, ~20 k cycles a simulation -- ahead of
 // the OTHER game's trunk waves on the same SIMDs: +2.5 % on the whole line, profiles/r06/ab_prio.txt; PRO: the trunk's prologue likewise)
 #ifndef RZ_DELTA_TREE_PRIO
@@ -42,6 +58,8 @@
 #ifndef RZ_DELTA_PRESCAN
 #define RZ_DELTA_PRESCAN 1
 #endif
+
+namespace {
 
 namespace dl {
 
@@ -1329,3 +1347,5 @@ __global__ __launch_bounds__(256, 2) void k_trunk_policy_rows(NetDev nd, _Float1
 }
 
 }  // namespace dl
+
+}  // namespace
