@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 33
+#define RZ_ABI_VERSION 34
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -788,7 +788,7 @@ int rz_mz_expand_backup(rz_muzero *e, const float *d_reward, const float *d_prob
  * ([out][in]): dyn1.weight [64][64 + A], dyn1.bias, dyn2.weight, dyn2.bias, rew1.weight, rew1.bias, rew2.weight [1][64],
  * rew2.bias, pre1.weight, pre1.bias, pol.weight [A][64], pol.bias, val.weight [1][64], val.bias; call again after every
  * optimiser step.  rz_mz_search: d_hidden float32 [n_games][slots_per_game][64] with slot 0 = the root's state from the
- * initial inference (rz_mz_init_roots first); runs n_sims simulations of every game.  The six trace arrays (all or none):
+ * initial inference (rz_mz_init_roots first); runs n_sims simulations of every game and leaves every node's state at its slot.  The six trace arrays (all or none):
  * per simulation and game what the kernel selected and what its network returned, [n_sims][n_games] (probs:
  * x n_actions) -- the parity tests feed them to the CPython restatement of the pseudocode. */
 int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden);
@@ -796,10 +796,13 @@ int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace
                  int32_t *d_trace_leaf, float *d_trace_reward, float *d_trace_probs, float *d_trace_value, void *stream);
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
- * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac), n_sims simulations, the action
+ * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
+ * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action
  * drawn from visits ^ (1 / temperature) (arg-max at temperature <= 0), one record and the environment step with
  * auto-reset.  rz_mz_load_representation: HOST pointers to rep1.weight [64][obs_dim], rep1.bias, rep2.weight [64][64],
  * rep2.bias (torch layout), beside rz_mz_load_model.
+ * Whole moves run the four 64 x 64 layers on the f16 matrix pipe and keep d_hidden in their own format: a slot's 256 bytes
+ * are 64 f16 "hi" values followed by 64 f16 "lo" values, the state of unit k being (hi[k] + lo[k]) / 16.
  * The environments: d_state float64 [n_games][4] (x, x_dot, theta, theta_dot), d_steps / d_episode int64 [n_games], updated
  * in place (initial states of an episode: the counter-based stream of rlzero_amd/muzero/cartpole.py keyed (env_seed,
  * environment, episode)).  Random draws come from a counter-based stream keyed (noise_seed, environment, episode, step).
@@ -835,6 +838,27 @@ int rz_mz_root_children(rz_muzero *e, int32_t what, void *d_out, void *stream);
 int rz_mz_root_stats(rz_muzero *e, int32_t *d_n, double *d_value_sum, double *d_vmin, double *d_vmax, void *stream);
 int rz_mz_geometry(rz_muzero *e, int32_t *slots_per_game, int64_t *device_bytes);
 int rz_mz_error_flags(rz_muzero *e, int32_t *flags);
+/* A read-only view of the trees (ABI 34; tests and debugging: both calls launch no kernel).
+ * rz_mz_tree_nodes synchronises the device and copies every game's node records, h_nodes rz_mz_node [n_games][slots_per_game],
+ * and tops, h_top int32 [n_games] (slots handed out so far; records at or past a game's top are stale), to the HOST.  Every
+ * route leaves its complete trees there when a launch ends -- rz_mz_play_cartpole the trees of the launch's LAST move -- so
+ * what a search did can be read back without a trace: slots are handed out in expansion order (the expanded non-root slots
+ * sorted by first_child are the simulations in order), the children of slot s sit at first_child[s] + a, their priors are the
+ * network's probabilities, reward is stored in the node, and a leaf's value follows from the backup identity
+ * value_sum[s] = v[s] + sum over children (N_c * reward_c + discount * value_sum_c) (no v term for the root).
+ * rz_mz_search_plan: what a launch of the fused search (whole_moves 0: rz_mz_search) or of whole moves (whole_moves 1:
+ * rz_mz_play_cartpole) would be for the current shape (rz_mz_set_search_shape), from the function the launch itself uses: games
+ * per workgroup, whether the trees live in LDS (1) or stay in HBM (0), dynamic LDS bytes.  Any output pointer may be NULL. */
+typedef struct rz_mz_node {
+    int32_t n;           /* visit count */
+    int32_t first_child; /* slot of the first child, -1 = not expanded */
+    double value_sum;
+    double prior;
+    float reward;
+    int32_t pad;
+} rz_mz_node;
+int rz_mz_tree_nodes(rz_muzero *e, void *h_nodes, int32_t *h_top);
+int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Device replay buffer (ABI 31; rz_replay.hip; an opt-in extension -- the reference's learner keeps its samples in a host

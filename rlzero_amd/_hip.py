@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -212,6 +212,8 @@ _SIGNATURES = {
     'rz_mz_root_stats': (c_int, [P, P, P, P, P, P]),
     'rz_mz_geometry': (c_int, [P, POINTER(c_int32), POINTER(c_int64)]),
     'rz_mz_error_flags': (c_int, [P, POINTER(c_int32)]),
+    'rz_mz_tree_nodes': (c_int, [P, P, P]),
+    'rz_mz_search_plan': (c_int, [P, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     'rz_replay_create': (c_int, [c_int32, c_int64, c_int32, POINTER(c_void_p)]),
     'rz_replay_destroy': (c_int, [P]),
     'rz_replay_set_tables': (c_int, [P, P, P, P]),

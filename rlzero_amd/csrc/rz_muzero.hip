@@ -1026,11 +1026,16 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                     const unsigned long long key = mz_splitmix64(mz_splitmix64(mz_splitmix64(P.noise_seed ^ gs) ^
                                                                                 (unsigned long long)__double_as_longlong(env_g[5])) ^
                                                                  (unsigned long long)__double_as_longlong(env_g[4]));
-                    float gam[MAXA], gsum = 0.0f;
+                    // Both distributions are normalised in fp64 here, once per move: the float32 softmax and a float32 sum of the
+                    // gamma draws each add up to 1 only within a float32 ulp (6e-8), and the pseudocode's root priors are a
+                    // distribution (they sum to 1 within 1e-12: tests/test_muzero_moves_tree.py)
+                    float gam[MAXA];
+                    double gsum = 0.0, psum = 0.0;
 #pragma unroll
                     for (int a = 0; a < MAXA; ++a) {
                         gam[a] = a < A ? mz_gamma(P.alpha, (uint32_t)(key >> 32) + 0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key) : 0.0f;
-                        gsum += gam[a];
+                        gsum += (double)gam[a];
+                        psum += (double)probs[a];   // (0 past the last action: finish_prediction)
                     }
                     if (TREE_LDS) {
                         hot[0] = MzHot{0, 1, 0.0, 0.0, 0.0};
@@ -1041,11 +1046,11 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
 #pragma unroll
                     for (int a = 0; a < MAXA; ++a) {
                         if (a < A) {
-                            double pr = (double)probs[a];
+                            double pr = (double)probs[a] / psum;
                             if (P.noise_frac > 0.0) {
                                 double nf = P.noise_frac;
                                 asm volatile("" : "+v"(nf));   // (1 - nf formed here, not carried through the launch)
-                                pr = pr * (1.0 - nf) + ((double)gam[a] / (double)gsum) * nf;
+                                pr = pr * (1.0 - nf) + ((double)gam[a] / gsum) * nf;
                             }
                             if (TREE_LDS) {
                                 hot[1 + a] = MzHot{0, -1, 0.0, pr, 0.0};
@@ -1670,14 +1675,31 @@ int rz_mz_load_representation(rz_muzero *e, const float *const *h_params, int32_
     return RZ_OK;
 }
 
-static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, void *stream) {
+// What a launch of k_mz_search looks like for the engine's current shape: mz_launch_search launches exactly this, and
+// rz_mz_search_plan reports it (the tests prove through it which instantiation they ran).  `whole_moves`: the MOVES
+// instantiations (rz_mz_play_cartpole); they share the LDS layout of the move-by-move search, so the plan is the same today.
+struct MzPlan {
+    int gpw;        // games per workgroup
+    bool tree_lds;  // trees in LDS (k_mz_search<true, ...>) or in HBM (<false, ...>)
+    int lds;        // dynamic LDS bytes of the launch
+};
+static MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves) {
+    (void)whole_moves;
+    MzPlan p;
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
     // other, so the 16 columns of a tile are filled first (profiles/r02/muzero_search_shape.txt)
-    const int gpw = e->games_per_wg > 0 ? e->games_per_wg : kMzMaxGpw;
+    p.gpw = e->games_per_wg > 0 ? e->games_per_wg : kMzMaxGpw;
     // the trees go to LDS when two workgroups still fit on a CU
     const MzDev &D = e->dev;
-    const bool tree_lds = mz_search_lds_bytes(gpw, D.cap, D.path_stride, D.n_sims, true) <= 80 * 1024;
-    const int lds = mz_search_lds_bytes(gpw, D.cap, D.path_stride, D.n_sims, tree_lds);
+    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true) <= 80 * 1024;
+    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds);
+    return p;
+}
+
+static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, void *stream) {
+    const MzPlan plan = mz_search_plan(e, play != nullptr);
+    const int gpw = plan.gpw, lds = plan.lds;
+    const bool tree_lds = plan.tree_lds;
     if (lds > 160 * 1024) return mz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
     const dim3 grid((unsigned)((e->cfg.n_games + gpw - 1) / gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
@@ -1767,6 +1789,28 @@ int rz_mz_debug_profile(long long *h_out16) {
     return hipDeviceSynchronize() == hipSuccess && hipMemcpyFromSymbol(h_out16, HIP_SYMBOL(mz_prof), 16 * sizeof(long long)) == hipSuccess ? RZ_OK : RZ_ERR_HIP;
 }
 #endif
+
+int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
+    if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    const MzPlan plan = mz_search_plan(e, whole_moves != 0);
+    if (games_per_workgroup) *games_per_workgroup = plan.gpw;
+    if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
+    if (lds_bytes) *lds_bytes = plan.lds;
+    return RZ_OK;
+}
+
+int rz_mz_tree_nodes(rz_muzero *e, void *h_nodes, int32_t *h_top) {
+    int rc = mz_ready(e);
+    if (rc != RZ_OK) return rc;
+    if (h_nodes == nullptr || h_top == nullptr) return mz_fail(RZ_ERR_ARG, "h_nodes / h_top is NULL");
+    static_assert(sizeof(MzNode) == sizeof(rz_mz_node), "rz_mz_node is the device's node record");
+    const size_t G = (size_t)e->cfg.n_games;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(h_nodes, e->dev.nodes, G * (size_t)e->dev.cap * sizeof(MzNode), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(h_top, e->dev.top, G * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return mz_fail(RZ_ERR_HIP, "hipMemcpy(tree nodes) failed");
+    return RZ_OK;
+}
 
 int rz_mz_geometry(rz_muzero *e, int32_t *slots_per_game, int64_t *device_bytes) {
     if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");

@@ -434,6 +434,18 @@ class MuZeroSelfPlay(object):
         self._fused_state()
         return self._ring.cpu().numpy(), self._ep_start_dev.cpu().numpy()
 
+    def hidden_states(self):
+        """The hidden state of every tree node after the last search, float64 numpy [n_envs, slots, 64] (tests, debugging).
+        The move-by-move routes keep float32 states: returned as they are.  Whole moves keep a slot's 256 bytes as 64 f16
+        "hi" values followed by 64 f16 "lo" values (the operand pieces of the f16 matrix pipe, scaled by 16): decoded here,
+        state = (hi + lo) / 16."""
+        self.torch.cuda.synchronize(self.device)
+        raw = self.hidden.cpu().numpy()
+        if not self.fused_moves:
+            return raw.astype(np.float64)
+        pieces = np.ascontiguousarray(raw).view(np.float16).reshape(raw.shape[0], raw.shape[1], 2, raw.shape[2]).astype(np.float64)
+        return (pieces[:, :, 0] + pieces[:, :, 1]) / 16.0
+
     def _launch_moves(self, n_moves, buf):
         """Enqueue ``n_moves`` moves of every environment (one launch) and the copy of what ended during them."""
         t = self.torch

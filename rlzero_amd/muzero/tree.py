@@ -157,6 +157,31 @@ class MuZeroTree(object):
                                         _ptr(self.vmax), self.stream()), 'rz_mz_root_stats')
         return self.root_n, self.root_sum, self.vmin, self.vmax
 
+    # rz_mz_node (include/rlzero_hip.h): the 32-byte record of a tree node as the device keeps it
+    NODE_DTYPE = np.dtype([('N', '<i4'), ('first_child', '<i4'), ('value_sum', '<f8'), ('prior', '<f8'), ('reward', '<f4'),
+                           ('pad', '<i4')])
+
+    def nodes(self):
+        """-> (nodes, top): every game's node records, a numpy structured array [n_games, slots_per_game] (fields N,
+        first_child, value_sum, prior, reward), and the slots handed out so far, int32 [n_games] (records at or past a game's
+        top are stale).  Synchronises; launches nothing (tests, debugging).  After ``play_cartpole`` the trees are those of the
+        launch's last move."""
+        assert self.NODE_DTYPE.itemsize == 32
+        nodes = np.zeros((self.n_games, self.slots_per_game), dtype=self.NODE_DTYPE)
+        top = np.zeros(self.n_games, dtype=np.int32)
+        check(self.lib.rz_mz_tree_nodes(self.handle, ctypes.c_void_p(nodes.ctypes.data), ctypes.c_void_p(top.ctypes.data)),
+              'rz_mz_tree_nodes')
+        return nodes, top
+
+    def search_plan(self, whole_moves):
+        """What a launch of ``search_fused`` (``whole_moves`` false) or ``play_cartpole`` (true) would be for the current shape
+        (``set_search_shape``), from the host function the launch itself uses -> dict games_per_workgroup, tree_in_lds (bool),
+        lds_bytes."""
+        gpw, in_lds, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        check(self.lib.rz_mz_search_plan(self.handle, 1 if whole_moves else 0, ctypes.byref(gpw), ctypes.byref(in_lds),
+                                         ctypes.byref(lds)), 'rz_mz_search_plan')
+        return {'games_per_workgroup': gpw.value, 'tree_in_lds': bool(in_lds.value), 'lds_bytes': lds.value}
+
     def check(self):
         flags = ctypes.c_int32(0)
         check(self.lib.rz_mz_error_flags(self.handle, ctypes.byref(flags)), 'rz_mz_error_flags')
