@@ -799,7 +799,10 @@ int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup);
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action
  * drawn from visits ^ (1 / temperature) (arg-max at temperature <= 0), one record and the environment step with
- * auto-reset.  rz_mz_load_representation: HOST pointers to rep1.weight [64][obs_dim], rep1.bias, rep2.weight [64][64],
+ * auto-reset.  dirichlet_alpha >= 0.1, else RZ_ERR_ARG: a draw is a float32 Gamma(alpha) floored at 1e-30, and
+ * P(Gamma(alpha, 1) < 1e-30) = 1e-30^alpha / Gamma(alpha + 1) is 3.5e-8 at the default 0.25 and 1.05e-3 at 0.1 but 3.2e-2 at
+ * 0.05 and 0.128 at 0.03 -- when BOTH actions' draws are floored the noise is uniform where a Dirichlet draw is almost one-hot
+ * (at 0.1: about one move in 10^6; at 0.03: one in 60).  rz_mz_load_representation: HOST pointers to rep1.weight [64][obs_dim], rep1.bias, rep2.weight [64][64],
  * rep2.bias (torch layout), beside rz_mz_load_model.
  * Whole moves run the four 64 x 64 layers on the f16 matrix pipe and keep d_hidden in their own format: a slot's 256 bytes
  * are 64 f16 "hi" values followed by 64 f16 "lo" values, the state of unit k being (hi[k] + lo[k]) / 16.

@@ -1743,6 +1743,10 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
     if (play->ring_steps < 500 + n_moves || play->arena_rows < 1 || play->max_entries < (int64_t)e->cfg.n_games * n_moves || play->first_step < 0)
         return mz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (500 steps) + the launch, max_entries one entry per environment and move");
     if (!(play->dirichlet_alpha > 0.0) || play->noise_frac < 0.0 || play->noise_frac > 1.0) return mz_fail(RZ_ERR_ARG, "dirichlet_alpha must be > 0, noise_frac in [0, 1]");
+    // mz_gamma floors a draw at 1e-30: P(Gamma(alpha, 1) < 1e-30) is 1.05e-3 at alpha 0.1 and 0.128 at 0.03, and a move whose draws are
+    // ALL floored gets uniform noise where Dirichlet(alpha) is almost one-hot (tests/test_noise_streams_host.py states the figures)
+    if (play->dirichlet_alpha < 0.1)
+        return mz_fail(RZ_ERR_ARG, "dirichlet_alpha must be >= 0.1: below it the root noise's float32 draws reach their 1e-30 floor too often");
     MzPlay p = {};
     p.n_moves = n_moves;
     p.row = 4 + 4 + e->cfg.n_actions;

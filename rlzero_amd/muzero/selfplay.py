@@ -158,6 +158,14 @@ class ReplayBuffer(object):
 
 
 class MuZeroSelfPlay(object):
+    """Self-play of a batch of environments with one MuZero search per environment and move (the three routes of the module text).
+
+    Whole moves (``fused_moves``) need ``root_dirichlet_alpha >= 0.1`` and raise ``HipError`` otherwise, before any launch, as
+    ``rz_mz_play_cartpole`` does: the kernel's root noise is a float32 Gamma(alpha) draw per action floored at 1e-30, and
+    P(Gamma(alpha, 1) < 1e-30) = 1e-30 ^ alpha / Gamma(alpha + 1) grows from 3.5e-8 at the default 0.25 over 1.05e-3 at 0.1 to 0.128
+    at 0.03.  A move whose two draws are both floored gets uniform noise where Dirichlet(alpha) is almost one-hot: about one move
+    in 10^6 at 0.1, one in 60 at 0.03.  The move-by-move routes draw their noise in float64 and take any alpha > 0."""
+    MIN_FUSED_ALPHA = 0.1
 
     def __init__(self, net, env, n_sims=50, discount=0.997, temperature=1.0, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, seed=0, pb_c_base=19652.0, pb_c_init=1.25, use_graph=True, fused=None,
@@ -211,6 +219,11 @@ class MuZeroSelfPlay(object):
         self.fused_moves = can_fuse_moves if fused_moves is None else bool(fused_moves)
         if self.fused_moves and not can_fuse_moves:
             raise ValueError('fused_moves needs the fused search and a CartPoleBatch environment')
+        if self.fused_moves and not self.alpha >= self.MIN_FUSED_ALPHA:
+            from .._hip import HipError
+            self.tree.close()
+            raise HipError('dirichlet_alpha must be >= 0.1: below it the root noise\'s float32 draws reach their 1e-30 floor too often '
+                           '(root_dirichlet_alpha = %r; the move-by-move routes, fused_moves=False, take any alpha > 0)' % self.alpha)
         self.moves_per_launch = max(1, int(moves_per_launch))
         self._arena_rows = arena_rows
         self.noise_seed = int(seed)

@@ -647,3 +647,30 @@ def test_whole_moves_refuse_weights_without_finite_bounds():
     with pytest.raises(HipError, match='non-finite weights'):
         sp.collect(2)
     sp.close()
+
+
+@pytest.mark.gpu
+def test_whole_moves_refuse_a_dirichlet_alpha_below_a_tenth():
+    """The whole-move kernel floors a float32 Gamma(alpha) draw at 1e-30, and below alpha = 0.1 both actions' draws reach the floor too
+    often (tests/test_noise_streams_host.py: once in 10^6 moves at 0.1, once in 60 at 0.03): rz_mz_play_cartpole answers RZ_ERR_ARG and
+    MuZeroSelfPlay raises the same error before any launch.  0.1 itself plays, and the move-by-move search, whose noise is drawn in
+    float64 on the host side, takes a smaller alpha."""
+    import torch
+    from rlzero_amd._hip import HipError
+    from rlzero_amd.muzero import CartPoleBatch, MuZeroNet, MuZeroSelfPlay
+    torch.manual_seed(0)
+    net = MuZeroNet().to('cuda:0').eval()
+    with pytest.raises(HipError, match='dirichlet_alpha must be >= 0.1'):
+        MuZeroSelfPlay(net, CartPoleBatch(32, 'cuda:0', seed=0), n_sims=4, seed=0, root_dirichlet_alpha=0.05, fused_moves=True)
+    sp = MuZeroSelfPlay(net, CartPoleBatch(32, 'cuda:0', seed=0), n_sims=4, seed=0, root_dirichlet_alpha=0.1, fused_moves=True)
+    sp.alpha = 0.0999   # past the class's own check: the library's
+    with pytest.raises(HipError, match='dirichlet_alpha must be >= 0.1'):
+        sp.collect(1)
+    assert sp._t == 0
+    sp.alpha = 0.1
+    sp.collect(1)
+    assert sp._t == 1
+    sp.close()
+    sp = MuZeroSelfPlay(net, CartPoleBatch(32, 'cuda:0', seed=0), n_sims=4, seed=0, root_dirichlet_alpha=0.05, fused_moves=False)
+    sp.collect(1)
+    sp.close()
