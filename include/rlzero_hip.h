@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 34
+#define RZ_ABI_VERSION 35
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -911,6 +911,69 @@ int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, floa
                      void *stream);
 int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream);
 int rz_replay_poll_errors(rz_replay *r, int32_t *flags, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * MuZero device replay (ABI 35; rz_mz_replay.hip, rz_mz_target.h; an opt-in extension beside the host ReplayBuffer of
+ * rlzero_amd/muzero/selfplay.py).  Limits: obs_dim D <= 16, n_actions A <= 8, unroll_steps K 1 .. 16, td_steps 1 .. 64,
+ * max_episode_steps T <= 65536, capacity E <= 2^22 episodes and E * T <= 2^30 steps: RZ_ERR_ARG otherwise, before any launch.
+ *
+ * The store is fixed stride -- episode slot e holds up to T steps -- and structure of arrays:
+ *   obs        float32 [E][T][D]        action  int32   [E][T]        reward  float64 [E][T]
+ *   root_value float64 [E][T]           policy  float32 [E][T][A]     length  int32   [E]
+ * The slots form a ring over EPISODES; the write cursor, the count and a copy of the lengths are HOST state of the handle
+ * (rz_mz_replay_state; h_lengths int32 [count], oldest first, may be NULL) and travel to the kernels as arguments.  Episode j
+ * counts from the OLDEST one held: after any sequence of add / ingest calls the store holds what the host
+ * ReplayBuffer(capacity = E) holds after `add` of the same episodes in the same order (empty episodes skipped, the oldest
+ * dropped when full).  Every call below takes a stream and is ordered on it; calls of one handle come from one host thread.
+ *
+ * rz_mz_replay_create: h_disc float64 [td_steps + 1] = discount ** i as the HOST evaluates it (the very expression of
+ *   ReplayBuffer._value_target): no pow runs on the device.
+ * rz_mz_replay_add: n_episodes episodes in ONE launch (k_mzr_add: a workgroup per episode, a wave per step row, lanes across
+ *   the row).  h_rows float64 [sum of h_lengths][D + 4 + A], the episodes one behind the other, every row a packed record of
+ *   rz_mz_play_cartpole: obs (D) | action | reward | visit counts (A) | root value | done.  The policy stored is
+ *   (float)(visits / sum(visits)) with the division in fp64 (EpisodeSeq.fields_of_packed's expression); an episode whose
+ *   h_flags entry (may be NULL = 0) has bit 0 set carries the float32 POLICY in those columns, which is only cast.  obs is cast to
+ *   float32.  An episode longer than T, an action outside 0 .. A-1: RZ_ERR_ARG, nothing is stored.  One staging copy precedes
+ *   the launch.
+ * rz_mz_replay_ingest: the same kernel body (k_mzr_ingest) reading the rows from DEVICE memory -- d_arena float64
+ *   [arena_rows][row_doubles], the arena of a launch of rz_mz_play_cartpole on the same stream -- by the entries (h_lengths[i],
+ *   h_first_rows[i]); only the entry table is staged.  row_doubles must be D + 4 + A and every run of rows must lie inside
+ *   0 .. arena_rows - 1 (RZ_ERR_ARG; the kernel checks again and sets RZ_MZ_REPLAY_BAD_ROWS instead of reading outside).
+ * rz_mz_replay_gather: n entries in ONE launch (k_mzr_gather: a thread per entry and unroll step) into d_obs float32 [n][D],
+ *   d_actions int64 [n][K], d_tv / d_tr / d_mask float32 [n][K + 1], d_tp float32 [n][K + 1][A] -- ReplayBuffer.sample's six
+ *   arrays for those draws, bit for bit.  The draws are int64 [n][K + 2]: episode, position, the K filler actions (used for
+ *   actions[., k] when step position + k lies past the end), from the host (h_draws: checked here, RZ_ERR_ARG) or from the device
+ *   (d_draws: checked by the kernel -- such an entry is not written and RZ_MZ_REPLAY_BAD_INDEX is set); exactly one is not NULL.
+ *   Row k at step i = position + k: inside the episode (i < length) the value target is
+ *   (float)((i + td < length ? root_value[i + td] * disc[td] : 0.0) + reward[i] * disc[0] + reward[i + 1] * disc[1] + ...) over
+ *   the steps below min(i + td, length), summed in ascending order in fp64 (the build's -ffp-contract=off keeps multiply and
+ *   add apart), the policy row is the stored one and the mask 1; outside: 0, the uniform policy (float)(1.0 / A), 0.  For k > 0
+ *   the action and reward are those of step i - 1 while i - 1 < length, else the filler and 0.
+ * rz_mz_replay_sample: the same rows with the draws made on the device (k_mzr_sample): counter c = i * (K + 2) + j of update
+ *   `step` gives mulhi64(x, m) of the splitmix64 chain x = sm(sm(sm(seed ^ "mzreplay") ^ step) ^ c) -- j = 0 the episode, m =
+ *   count; j = 1 the position, m = that episode's length (the host buffer's distribution); j = 2 + k the filler of actions[., k],
+ *   m = A.  rlzero_amd/muzero/replay.py: mz_replay_draws gives the same bits.  RZ_ERR_ARG on an empty buffer.
+ * rz_mz_replay_read: a SYNCHRONOUS copy of episodes first .. first + n - 1 (oldest = 0) to host arrays of the store's stride
+ *   ([n][T][..], h_length [n]; any may be NULL).
+ * rz_mz_replay_poll_errors: the device's flag word (waits for `stream`), cleared by the call. */
+#define RZ_MZ_REPLAY_BAD_INDEX 1 /* a draw from the device was out of range */
+#define RZ_MZ_REPLAY_BAD_ROWS 2  /* an entry's rows lay outside its block */
+typedef struct rz_mz_replay rz_mz_replay;
+int rz_mz_replay_create(int32_t obs_dim, int32_t n_actions, int64_t capacity_episodes, int32_t max_episode_steps, int32_t unroll_steps,
+                        int32_t td_steps, const double *h_disc, int32_t device, rz_mz_replay **out);
+int rz_mz_replay_destroy(rz_mz_replay *r);
+int rz_mz_replay_state(rz_mz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity, int32_t *h_lengths);
+int rz_mz_replay_add(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int32_t *h_flags, const double *h_rows,
+                     void *stream);
+int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int64_t *h_first_rows, const double *d_arena,
+                        int64_t arena_rows, int32_t row_doubles, void *stream);
+int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, int64_t n, float *d_obs, int64_t *d_actions,
+                        float *d_tv, float *d_tr, float *d_tp, float *d_mask, void *stream);
+int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv,
+                        float *d_tr, float *d_tp, float *d_mask, void *stream);
+int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
+                      float *h_policy, int32_t *h_length, void *stream);
+int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -89,6 +89,7 @@ PLAY_RUNNING, PLAY_STALLED, PLAY_RESOLVED, PLAY_ENDED, PLAY_SEARCHED = 1, 2, 4, 
 PLAY_RESIGNED, PLAY_NO_RESIGN, PLAY_WOULD_RESIGN = 32, 64, 128   # resignation (rz_play_set_resign, ABI 27)
 PLAY_FULL = 256   # playout cap (rz_play_set_cap, ABI 28): the record's search had the full budget
 REPLAY_BAD_INDEX = 1   # rz_replay_poll_errors (ABI 31): an entry index from the device was out of range
+MZ_REPLAY_BAD_INDEX, MZ_REPLAY_BAD_ROWS = 1, 2   # rz_mz_replay_poll_errors (ABI 35): a draw from the device / an entry's rows out of range
 
 
 class HipError(RuntimeError):
@@ -223,6 +224,15 @@ _SIGNATURES = {
     'rz_replay_sample': (c_int, [P, c_uint64, c_uint64, c_int64, P, P, P, P]),
     'rz_replay_read': (c_int, [P, c_int64, c_int64, P, P, P, P]),
     'rz_replay_poll_errors': (c_int, [P, POINTER(c_int32), P]),
+    'rz_mz_replay_create': (c_int, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, P, c_int32, POINTER(c_void_p)]),
+    'rz_mz_replay_destroy': (c_int, [P]),
+    'rz_mz_replay_state': (c_int, [P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), P]),
+    'rz_mz_replay_add': (c_int, [P, c_int32, P, P, P, P]),
+    'rz_mz_replay_ingest': (c_int, [P, c_int32, P, P, P, c_int64, c_int32, P]),
+    'rz_mz_replay_gather': (c_int, [P, P, P, c_int64, P, P, P, P, P, P, P]),
+    'rz_mz_replay_sample': (c_int, [P, c_uint64, c_uint64, c_int64, P, P, P, P, P, P, P]),
+    'rz_mz_replay_read': (c_int, [P, c_int64, c_int64, P, P, P, P, P, P, P]),
+    'rz_mz_replay_poll_errors': (c_int, [P, POINTER(c_int32), P]),
 }
 
 _lib = None

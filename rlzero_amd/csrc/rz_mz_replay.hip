@@ -1,0 +1,503 @@
+// rz_mz_replay.hip -- the MuZero learner's replay buffer in device memory (include/rlzero_hip.h: rz_mz_replay_*, ABI 35).
+//
+// Finished episodes live on the GPU in fixed-stride slots -- slot e holds up to T steps, structure of arrays -- in a ring over
+// EPISODES, and a mini-batch of unrolled targets is ONE launch: k_mzr_gather / k_mzr_sample write the observation, the K actions
+// and the K + 1 value / reward / policy targets and masks of every entry straight into the learner's tensors, bit for bit what
+// rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample forms on the host (the rules and the arithmetic: rz_mz_target.h).  Episodes
+// arrive as packed float64 records, the format of rz_mz_play_cartpole: from a staged host block (k_mzr_add) or straight from a
+// launch's device arena (k_mzr_ingest: only a small entry table travels).
+//
+// Bounds: every slot is reduced modulo the capacity, every length is clamped to 0 .. T where it is read, every step index is compared
+// with that length before a read, rows of a block are checked against its row count (on the host and again in the kernel), and an
+// index from the device is checked by the kernel before anything is read -- such an entry is not written and a flag is set.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "rlzero_hip.h"
+#include "rz_mz_target.h"
+
+void rz_set_error(const char *msg);  // rz_engine.hip
+
+namespace {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kFlagBadIndex = RZ_MZ_REPLAY_BAD_INDEX, kFlagBadRows = RZ_MZ_REPLAY_BAD_ROWS;
+constexpr int kEntryWords = 4;   // an entry of the table of k_mzr_add / k_mzr_ingest: length, first row, slot, flags (bit 0: final policy)
+
+struct MzrDev {
+    float *obs;           // [E][T][D]
+    int32_t *action;      // [E][T]
+    double *reward;       // [E][T]
+    double *root_value;   // [E][T]
+    float *policy;        // [E][T][A]
+    int32_t *length;      // [E]
+    const double *disc;   // [td + 1]: discount ** i, formed on the host
+    int32_t *err;
+    int E, T, D, A, K, td;
+};
+
+struct MzrOut {
+    float *obs;           // [n][D]
+    long long *actions;   // [n][K]
+    float *tv, *tr;       // [n][K + 1]
+    float *tp;            // [n][K + 1][A]
+    float *mask;          // [n][K + 1]
+};
+
+__device__ __forceinline__ int mzr_slot(const MzrDev &R, long long s) { return (int)(((s % R.E) + R.E) % R.E); }
+__device__ __forceinline__ int mzr_length(const MzrDev &R, int slot) { return min(max(R.length[slot], 0), R.T); }
+
+// Entry e of the table: its rows of `rows` [n_rows][D + 4 + A] into its slot.  A workgroup per entry, a wave per step row with the
+// lanes across the row (D + 4 + A <= 28 doubles: one coalesced read), each lane casting and storing its own column.
+__device__ __forceinline__ void mzr_store(const MzrDev &R, const int32_t *__restrict__ table, const double *__restrict__ rows, long long n_rows) {
+    const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int len = min(max(table[kEntryWords * e], 0), R.T);
+    const long long first = table[kEntryWords * e + 1];
+    const int slot = mzr_slot(R, table[kEntryWords * e + 2]);
+    const bool final_policy = (table[kEntryWords * e + 3] & 1) != 0;
+    if (first < 0 || first + len > n_rows) {   // (checked on the host too: nothing outside the block is read)
+        if (threadIdx.x == 0) atomicOr(R.err, kFlagBadRows);
+        return;
+    }
+    const int D = R.D, A = R.A, W = D + 4 + A;
+    for (int t = wave; t < len; t += kWaves) {
+        const double *row = rows + (first + t) * W;
+        const long long at = (long long)slot * R.T + t;
+        if (lane < D) {
+            R.obs[at * D + lane] = (float)row[lane];
+        } else if (lane == D) {
+            R.action[at] = (int32_t)row[lane];
+        } else if (lane == D + 1) {
+            R.reward[at] = row[lane];
+        } else if (lane < D + 2 + A) {
+            R.policy[at * A + (lane - D - 2)] = rzmzt::policy_of_row(row, D, A, lane - D - 2, final_policy);
+        } else if (lane == D + 2 + A) {
+            R.root_value[at] = row[lane];
+        }
+    }
+    if (threadIdx.x == 0) R.length[slot] = len;
+}
+
+__global__ __launch_bounds__(kThreads) void k_mzr_add(MzrDev R, const int32_t *__restrict__ table, const double *__restrict__ rows, long long n_rows) {
+    mzr_store(R, table, rows, n_rows);
+}
+
+// the same body, the rows read from the arena of a launch of rz_mz_play_cartpole (device memory: the records never leave the GPU)
+__global__ __launch_bounds__(kThreads) void k_mzr_ingest(MzrDev R, const int32_t *__restrict__ table, const double *__restrict__ arena,
+                                                          long long arena_rows) {
+    mzr_store(R, table, arena, arena_rows);
+}
+
+// row k of output entry b from position `pos` of the episode in `slot` (length `len`, 0 <= pos < len)
+__device__ __forceinline__ void mzr_emit(const MzrDev &R, const MzrOut &O, long long b, int k, int slot, int len, int pos, long long filler) {
+    const long long base = (long long)slot * R.T;
+    const int K = R.K, A = R.A, D = R.D;
+    const rzmzt::Row r = rzmzt::unroll_row(R.reward + base, R.root_value + base, R.action + base, len, pos, k, R.td, R.disc, filler);
+    const long long o = b * (K + 1) + k;
+    O.tv[o] = r.value;
+    O.tr[o] = r.reward;
+    O.mask[o] = r.mask;
+    const float uniform = rzmzt::uniform_policy(A);
+    for (int a = 0; a < A; ++a) O.tp[o * A + a] = r.policy_step >= 0 ? R.policy[(base + r.policy_step) * A + a] : uniform;
+    if (k > 0) {
+        O.actions[b * K + (k - 1)] = r.action;
+    } else {
+        for (int d = 0; d < D; ++d) O.obs[b * D + d] = R.obs[(base + pos) * D + d];
+    }
+}
+
+// A thread per (entry, unroll step).  draws int64 [n][K + 2]: episode (0 = the oldest held), position, the K filler actions.
+__global__ __launch_bounds__(kThreads) void k_mzr_gather(MzrDev R, MzrOut O, const long long *__restrict__ draws, long long oldest, long long count,
+                                                          long long n) {
+    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const int K = R.K;
+    const long long b = tid / (K + 1);
+    const int k = (int)(tid % (K + 1));
+    if (b >= n) return;
+    const long long *dr = draws + b * (K + 2);
+    const long long ep = dr[0], pos = dr[1];
+    bool bad = ep < 0 || ep >= count;
+    int slot = 0, len = 0;
+    if (!bad) {
+        slot = mzr_slot(R, oldest + ep);
+        len = mzr_length(R, slot);
+        bad = pos < 0 || pos >= len;
+    }
+    for (int j = 0; j < K; ++j) bad = bad || dr[2 + j] < 0 || dr[2 + j] >= R.A;   // every thread of the entry comes to the same verdict
+    if (bad) {   // an index from the device: nothing of this entry is read or written
+        if (k == 0) atomicOr(R.err, kFlagBadIndex);
+        return;
+    }
+    mzr_emit(R, O, b, k, slot, len, (int)pos, k > 0 ? dr[2 + k - 1] : 0);
+}
+
+// The same rows with the draws made here: counter c = b (K + 2) + j of update `step` (rz_mz_target.h: draw) -- j = 0 the episode,
+// uniform over the episodes held; j = 1 the position, uniform over that episode's length; j = 2 + k the filler action of step k.
+__global__ __launch_bounds__(kThreads) void k_mzr_sample(MzrDev R, MzrOut O, unsigned long long seed, unsigned long long step, long long oldest,
+                                                          long long count, long long n) {
+    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const int K = R.K;
+    const long long b = tid / (K + 1);
+    const int k = (int)(tid % (K + 1));
+    if (b >= n) return;
+    const long long ep = rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 0), (uint64_t)count);
+    const int slot = mzr_slot(R, oldest + ep);
+    const int len = mzr_length(R, slot);
+    if (len == 0) {   // (an episode held is never empty)
+        if (k == 0) atomicOr(R.err, kFlagBadIndex);
+        return;
+    }
+    const int pos = (int)rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 1), (uint64_t)len);
+    const long long filler = k > 0 ? rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 2 + k - 1), (uint64_t)R.A) : 0;
+    mzr_emit(R, O, b, k, slot, len, pos, filler);
+}
+
+int mr_fail(int code, const char *msg) {
+    rz_set_error(msg);
+    return code;
+}
+
+}  // namespace
+
+struct rz_mz_replay {
+    MzrDev dev = {};
+    int device = 0;
+    long long cursor = 0, count = 0;   // next slot written; episodes held
+    std::vector<int32_t> lengths;      // [E] by slot: the host's copy of dev.length
+    double *d_disc = nullptr;
+    // one staging pair (pinned host + device), reused: the host half after `copied`, the device half after `consumed`
+    void *h_stage = nullptr, *d_stage = nullptr;
+    size_t stage_bytes = 0;
+    hipEvent_t copied = nullptr, consumed = nullptr;
+    bool in_flight = false;
+};
+
+namespace {
+
+int mr_ready(rz_mz_replay *r) {
+    if (r == nullptr) return mr_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipGetDevice failed");
+    if (cur != r->device && hipSetDevice(r->device) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    return RZ_OK;
+}
+
+// the staging pair with room for `bytes`, its host half free to be written; `stream` waits for the device half's last reader
+int mr_stage(rz_mz_replay *r, size_t bytes, hipStream_t stream) {
+    if (r->in_flight && hipEventSynchronize(r->copied) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventSynchronize failed (MuZero replay staging)");
+    if (bytes > r->stage_bytes) {
+        if (r->in_flight && hipEventSynchronize(r->consumed) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventSynchronize failed (MuZero replay staging)");
+        r->in_flight = false;
+        if (r->h_stage) (void)hipHostFree(r->h_stage);
+        if (r->d_stage) (void)hipFree(r->d_stage);
+        r->h_stage = r->d_stage = nullptr;
+        r->stage_bytes = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc(&r->h_stage, want, hipHostMallocDefault) != hipSuccess) return mr_fail(RZ_ERR_OOM, "hipHostMalloc failed (MuZero replay staging)");
+        if (hipMalloc(&r->d_stage, want) != hipSuccess) return mr_fail(RZ_ERR_OOM, "hipMalloc failed (MuZero replay staging)");
+        r->stage_bytes = want;
+    }
+    if (r->in_flight && hipStreamWaitEvent(stream, r->consumed, 0) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipStreamWaitEvent failed (MuZero replay staging)");
+    return RZ_OK;
+}
+
+int mr_upload(rz_mz_replay *r, size_t bytes, hipStream_t stream) {
+    if (hipMemcpyAsync(r->d_stage, r->h_stage, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "staging copy failed (MuZero replay)");
+    if (hipEventRecord(r->copied, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventRecord failed (MuZero replay)");
+    return RZ_OK;
+}
+
+int mr_launched(rz_mz_replay *r, hipStream_t stream, const char *what) {
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, what);
+    if (hipEventRecord(r->consumed, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventRecord failed (MuZero replay)");
+    r->in_flight = true;
+    return RZ_OK;
+}
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+inline long long mr_oldest(const rz_mz_replay *r) { return ((r->cursor - r->count) % r->dev.E + r->dev.E) % r->dev.E; }
+
+// The entry table of `n` episodes (empty ones skipped; of more than the capacity only the last E get a slot) in `table`; -> the
+// number of entries, or a negative code.  first_rows NULL: the episodes lie one behind the other.  Every run of rows is checked
+// against n_rows here.
+int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t *h_flags, const int64_t *h_first_rows, int64_t n_rows,
+             std::vector<int32_t> &table, long long *held) {
+    const long long E = r->dev.E;
+    long long kept = 0, next = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (h_lengths[i] < 0) return mr_fail(RZ_ERR_ARG, "an episode of negative length");
+        if (h_lengths[i] > r->dev.T) return mr_fail(RZ_ERR_ARG, "an episode is longer than max_episode_steps");
+        const long long first = h_first_rows ? h_first_rows[i] : next;
+        if (h_lengths[i] > 0 && (first < 0 || first > 0x7fffffffLL || first + h_lengths[i] > n_rows))
+            return mr_fail(RZ_ERR_ARG, "an episode's rows lie outside the block");
+        next = first + h_lengths[i];
+        kept += h_lengths[i] > 0;
+    }
+    const long long skip = kept > E ? kept - E : 0;
+    table.clear();
+    long long t = 0;
+    next = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const long long first = h_first_rows ? h_first_rows[i] : next;
+        next = first + h_lengths[i];
+        if (h_lengths[i] == 0) continue;
+        if (t >= skip) {
+            const int32_t entry[kEntryWords] = {h_lengths[i], (int32_t)first, (int32_t)((r->cursor + t) % E), h_flags ? h_flags[i] : 0};
+            table.insert(table.end(), entry, entry + kEntryWords);
+        }
+        ++t;
+    }
+    *held = kept;
+    return (int)(table.size() / kEntryWords);
+}
+
+void mr_commit(rz_mz_replay *r, const std::vector<int32_t> &table, long long kept) {
+    const long long E = r->dev.E;
+    for (size_t e = 0; e < table.size() / kEntryWords; ++e) r->lengths[(size_t)table[kEntryWords * e + 2]] = table[kEntryWords * e];
+    r->cursor = (r->cursor + kept) % E;
+    r->count = r->count + kept > E ? E : r->count + kept;
+}
+
+int mr_outputs(rz_mz_replay *r, int64_t n, const MzrOut &O) {
+    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (n > 0 && (O.obs == nullptr || O.actions == nullptr || O.tv == nullptr || O.tr == nullptr || O.tp == nullptr || O.mask == nullptr))
+        return mr_fail(RZ_ERR_ARG, "NULL output buffer");
+    return RZ_OK;
+}
+
+inline unsigned mr_blocks(const rz_mz_replay *r, int64_t n) { return (unsigned)((n * (r->dev.K + 1) + kThreads - 1) / kThreads); }
+
+}  // namespace
+
+extern "C" {
+
+int rz_mz_replay_create(int32_t obs_dim, int32_t n_actions, int64_t capacity_episodes, int32_t max_episode_steps, int32_t unroll_steps,
+                        int32_t td_steps, const double *h_disc, int32_t device, rz_mz_replay **out) {
+    if (out == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (obs_dim < 1 || obs_dim > RZ_MZR_MAX_OBS) return mr_fail(RZ_ERR_ARG, "obs_dim outside 1 .. 16");
+    if (n_actions < 1 || n_actions > RZ_MZR_MAX_ACTIONS) return mr_fail(RZ_ERR_ARG, "n_actions outside 1 .. 8");
+    if (unroll_steps < 1 || unroll_steps > RZ_MZR_MAX_UNROLL) return mr_fail(RZ_ERR_ARG, "unroll_steps outside 1 .. 16");
+    if (td_steps < 1 || td_steps > RZ_MZR_MAX_TD) return mr_fail(RZ_ERR_ARG, "td_steps outside 1 .. 64");
+    if (max_episode_steps < 1 || max_episode_steps > 65536) return mr_fail(RZ_ERR_ARG, "max_episode_steps outside 1 .. 65536");
+    if (capacity_episodes < 1 || capacity_episodes > (1LL << 22) || capacity_episodes * max_episode_steps > (1LL << 30))
+        return mr_fail(RZ_ERR_ARG, "capacity_episodes outside 1 .. 2^22, or more than 2^30 steps in all");
+    if (h_disc == nullptr) return mr_fail(RZ_ERR_ARG, "NULL discount table");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return mr_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    rz_mz_replay *r = new (std::nothrow) rz_mz_replay();
+    if (!r) return mr_fail(RZ_ERR_OOM, "host allocation failed");
+    r->device = device;
+    MzrDev &R = r->dev;
+    R.E = (int)capacity_episodes, R.T = max_episode_steps, R.D = obs_dim, R.A = n_actions, R.K = unroll_steps, R.td = td_steps;
+    r->lengths.assign((size_t)R.E, 0);
+    const size_t steps = (size_t)R.E * R.T, n_disc = (size_t)td_steps + 1;
+    bool ok = hipMalloc((void **)&R.obs, steps * R.D * sizeof(float)) == hipSuccess && hipMalloc((void **)&R.action, steps * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc((void **)&R.reward, steps * sizeof(double)) == hipSuccess && hipMalloc((void **)&R.root_value, steps * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&R.policy, steps * R.A * sizeof(float)) == hipSuccess && hipMalloc((void **)&R.length, (size_t)R.E * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc((void **)&r->d_disc, n_disc * sizeof(double)) == hipSuccess && hipMalloc((void **)&R.err, sizeof(int32_t)) == hipSuccess;
+    if (!ok) {
+        rz_mz_replay_destroy(r);
+        return mr_fail(RZ_ERR_OOM, "hipMalloc failed (MuZero replay store)");
+    }
+    R.disc = r->d_disc;
+    ok = hipMemset(R.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(R.obs, 0, steps * R.D * sizeof(float)) == hipSuccess &&
+         hipMemset(R.action, 0, steps * sizeof(int32_t)) == hipSuccess && hipMemset(R.reward, 0, steps * sizeof(double)) == hipSuccess &&
+         hipMemset(R.root_value, 0, steps * sizeof(double)) == hipSuccess && hipMemset(R.policy, 0, steps * R.A * sizeof(float)) == hipSuccess &&
+         hipMemset(R.length, 0, (size_t)R.E * sizeof(int32_t)) == hipSuccess &&
+         hipMemcpy(r->d_disc, h_disc, n_disc * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipEventCreateWithFlags(&r->copied, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&r->consumed, hipEventDisableTiming) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        rz_mz_replay_destroy(r);
+        return mr_fail(RZ_ERR_HIP, "initialisation of the MuZero replay store failed");
+    }
+    *out = r;
+    return RZ_OK;
+}
+
+int rz_mz_replay_destroy(rz_mz_replay *r) {
+    if (r == nullptr) return RZ_OK;
+    (void)hipSetDevice(r->device);
+    (void)hipDeviceSynchronize();
+    if (r->copied) (void)hipEventDestroy(r->copied);
+    if (r->consumed) (void)hipEventDestroy(r->consumed);
+    if (r->h_stage) (void)hipHostFree(r->h_stage);
+    void *dev[] = {r->d_stage, r->dev.obs, r->dev.action, r->dev.reward, r->dev.root_value, r->dev.policy, r->dev.length, r->d_disc, r->dev.err};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    delete r;
+    return RZ_OK;
+}
+
+int rz_mz_replay_state(rz_mz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity, int32_t *h_lengths) {
+    if (r == nullptr) return mr_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
+    if (count) *count = r->count;
+    if (cursor) *cursor = r->cursor;
+    if (capacity) *capacity = r->dev.E;
+    if (h_lengths) {
+        const long long oldest = mr_oldest(r);
+        for (long long j = 0; j < r->count; ++j) h_lengths[j] = r->lengths[(size_t)((oldest + j) % r->dev.E)];
+    }
+    return RZ_OK;
+}
+
+int rz_mz_replay_add(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int32_t *h_flags, const double *h_rows, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (n_episodes < 0) return mr_fail(RZ_ERR_ARG, "n_episodes < 0");
+    if (n_episodes == 0) return RZ_OK;
+    if (h_lengths == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    long long total = 0;
+    for (int32_t i = 0; i < n_episodes; ++i) total += h_lengths[i] > 0 ? h_lengths[i] : 0;
+    if (total > 0x7fffffffLL) return mr_fail(RZ_ERR_ARG, "more than 2^31 - 1 rows in one call");
+    std::vector<int32_t> table;
+    long long kept = 0;
+    const int n = mr_table(r, n_episodes, h_lengths, h_flags, nullptr, total, table, &kept);
+    if (n < 0) return n;
+    if (kept == 0) return RZ_OK;
+    if (h_rows == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    const int W = r->dev.D + 4 + r->dev.A;
+    for (long long row = 0; row < total; ++row) {
+        const double a = h_rows[row * W + r->dev.D];
+        if (!(a >= 0.0 && a < (double)r->dev.A && a == (double)(int)a)) return mr_fail(RZ_ERR_ARG, "an action is outside 0 .. A-1");
+    }
+    // staging: entry table | rows
+    const size_t o_rows = align16(table.size() * sizeof(int32_t)), bytes = o_rows + (size_t)total * W * sizeof(double);
+    hipStream_t s = (hipStream_t)stream;
+    rc = mr_stage(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    char *h = (char *)r->h_stage, *d = (char *)r->d_stage;
+    memcpy(h, table.data(), table.size() * sizeof(int32_t));
+    memcpy(h + o_rows, h_rows, (size_t)total * W * sizeof(double));
+    rc = mr_upload(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    hipLaunchKernelGGL(k_mzr_add, dim3((unsigned)n), dim3(kThreads), 0, s, r->dev, (const int32_t *)d, (const double *)(d + o_rows), total);
+    rc = mr_launched(r, s, "k_mzr_add launch failed");
+    if (rc != RZ_OK) return rc;
+    mr_commit(r, table, kept);
+    return RZ_OK;
+}
+
+int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int64_t *h_first_rows, const double *d_arena,
+                        int64_t arena_rows, int32_t row_doubles, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (n_episodes < 0) return mr_fail(RZ_ERR_ARG, "n_episodes < 0");
+    if (n_episodes == 0) return RZ_OK;
+    if (h_lengths == nullptr || h_first_rows == nullptr || d_arena == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (row_doubles != r->dev.D + 4 + r->dev.A) return mr_fail(RZ_ERR_ARG, "the arena's rows are not obs_dim + 4 + n_actions doubles");
+    if (arena_rows < 0 || arena_rows > 0x7fffffffLL) return mr_fail(RZ_ERR_ARG, "arena_rows outside 0 .. 2^31 - 1");
+    std::vector<int32_t> table;
+    long long kept = 0;
+    const int n = mr_table(r, n_episodes, h_lengths, nullptr, h_first_rows, arena_rows, table, &kept);
+    if (n < 0) return n;
+    if (kept == 0) return RZ_OK;
+    const size_t bytes = table.size() * sizeof(int32_t);
+    hipStream_t s = (hipStream_t)stream;
+    rc = mr_stage(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    memcpy(r->h_stage, table.data(), bytes);
+    rc = mr_upload(r, bytes, s);
+    if (rc != RZ_OK) return rc;
+    hipLaunchKernelGGL(k_mzr_ingest, dim3((unsigned)n), dim3(kThreads), 0, s, r->dev, (const int32_t *)r->d_stage, d_arena, (long long)arena_rows);
+    rc = mr_launched(r, s, "k_mzr_ingest launch failed");
+    if (rc != RZ_OK) return rc;
+    mr_commit(r, table, kept);
+    return RZ_OK;
+}
+
+int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv,
+                        float *d_tr, float *d_tp, float *d_mask, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
+    rc = mr_outputs(r, n, O);
+    if (rc != RZ_OK) return rc;
+    if ((h_draws == nullptr) == (d_draws == nullptr)) return mr_fail(RZ_ERR_ARG, "exactly one of h_draws / d_draws");
+    if (n == 0) return RZ_OK;
+    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    hipStream_t s = (hipStream_t)stream;
+    const long long oldest = mr_oldest(r);
+    const long long *draws = (const long long *)d_draws;
+    const int K = r->dev.K;
+    if (h_draws != nullptr) {
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t *dr = h_draws + i * (K + 2);
+            if (dr[0] < 0 || dr[0] >= r->count) return mr_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return mr_fail(RZ_ERR_ARG, "a position is outside its episode");
+            for (int j = 0; j < K; ++j)
+                if (dr[2 + j] < 0 || dr[2 + j] >= r->dev.A) return mr_fail(RZ_ERR_ARG, "a filler action is outside 0 .. A-1");
+        }
+        const size_t bytes = (size_t)n * (K + 2) * sizeof(int64_t);
+        rc = mr_stage(r, bytes, s);
+        if (rc != RZ_OK) return rc;
+        memcpy(r->h_stage, h_draws, bytes);
+        rc = mr_upload(r, bytes, s);
+        if (rc != RZ_OK) return rc;
+        draws = (const long long *)r->d_stage;
+    }
+    hipLaunchKernelGGL(k_mzr_gather, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
+    if (h_draws != nullptr) return mr_launched(r, s, "k_mzr_gather launch failed");
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_gather launch failed");
+    return RZ_OK;
+}
+
+int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv, float *d_tr,
+                        float *d_tp, float *d_mask, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
+    rc = mr_outputs(r, n, O);
+    if (rc != RZ_OK) return rc;
+    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (n == 0) return RZ_OK;
+    hipLaunchKernelGGL(k_mzr_sample, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
+                       (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_sample launch failed");
+    return RZ_OK;
+}
+
+int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
+                      float *h_policy, int32_t *h_length, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (first < 0 || n < 0 || first + n > r->count) return mr_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    hipStream_t s = (hipStream_t)stream;
+    const MzrDev &R = r->dev;
+    const long long E = R.E, start = (mr_oldest(r) + first) % E;
+    const long long n1 = n < E - start ? n : E - start;   // up to the ring's end, then from its start
+    const size_t T = (size_t)R.T, D = (size_t)R.D, A = (size_t)R.A;
+    bool ok = true;
+    for (int part = 0; part < 2; ++part) {
+        const long long from = part == 0 ? start : 0, cnt = part == 0 ? n1 : n - n1, at = part == 0 ? 0 : n1;
+        if (cnt <= 0) continue;
+        const size_t c = (size_t)cnt;
+        if (h_obs) ok = ok && hipMemcpyAsync(h_obs + at * T * D, R.obs + from * T * D, c * T * D * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_action) ok = ok && hipMemcpyAsync(h_action + at * T, R.action + from * T, c * T * sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_reward) ok = ok && hipMemcpyAsync(h_reward + at * T, R.reward + from * T, c * T * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_root_value) ok = ok && hipMemcpyAsync(h_root_value + at * T, R.root_value + from * T, c * T * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_policy) ok = ok && hipMemcpyAsync(h_policy + at * T * A, R.policy + from * T * A, c * T * A * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (h_length) ok = ok && hipMemcpyAsync(h_length + at, R.length + from, c * sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return mr_fail(RZ_ERR_HIP, "read-back failed (MuZero replay)");
+    return RZ_OK;
+}
+
+int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (flags == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(flags, r->dev.err, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemsetAsync(r->dev.err, 0, sizeof(int32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return mr_fail(RZ_ERR_HIP, "reading the MuZero replay flags failed");
+    return RZ_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,102 @@
+// rz_mz_target.h -- the MuZero learner's unrolled targets (rz_mz_replay.hip: k_mzr_gather, k_mzr_sample; include/rlzero_hip.h:
+// rz_mz_replay_*): everything about them that is neither a kernel launch nor a memory access.  Plain C++, no HIP include, so that
+// the CPU can test it against rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample (tests/test_mz_replay_host.py); the kernels call
+// these functions.  The arithmetic is fp64 multiply and add in the order of ReplayBuffer._value_target, the discounts come from a
+// table the host filled with `discount ** i` (no pow here), and the value is cast to float32 once: with -ffp-contract=off the
+// host's bits.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define RZT_FN __host__ __device__ __forceinline__
+#else
+#define RZT_FN inline
+#endif
+
+#define RZ_MZR_MAX_OBS 16      /* D: floats of an observation */
+#define RZ_MZR_MAX_ACTIONS 8   /* A */
+#define RZ_MZR_MAX_UNROLL 16   /* K */
+#define RZ_MZR_MAX_TD 64       /* td_steps */
+
+namespace rzmzt {
+
+// ---- the draws of k_mzr_sample (rlzero_amd/muzero/replay.py: mz_replay_draws, the same bits)
+RZT_FN uint64_t mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+RZT_FN uint64_t mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+constexpr uint64_t kSampleSalt = 0x6D7A7265706C6179ull;   // "mzreplay": the sampler's own stream, apart from rz_replay's
+
+// counter c of entry i of update `step`: c = i * (K + 2) + j -- j = 0 the episode, j = 1 the position, j = 2 + k the filler action
+// of unroll step k
+RZT_FN uint64_t draw_counter(uint64_t i, int K, int j) { return i * (uint64_t)(K + 2) + (uint64_t)j; }
+// the high half of x * n for the 64-bit x of the chain over (seed, step, c): in 0 .. n - 1, within 2^-64 of uniform
+RZT_FN int64_t draw(uint64_t seed, uint64_t step, uint64_t c, uint64_t n) {
+    uint64_t x = mix64(seed ^ kSampleSalt);
+    x = mix64(x ^ step);
+    x = mix64(x ^ c);
+    return (int64_t)mulhi64(x, n);
+}
+
+// ---- ReplayBuffer._value_target(ep, t): the n-step return from step t, bootstrapped from the root value td steps on if the
+// episode still runs there.  disc[i] = discount ** i, i = 0 .. td.
+RZT_FN double value_target(const double *reward, const double *root_value, int len, int t, int td, const double *disc) {
+    const int boot = t + td;
+    double value = boot < len ? root_value[boot] * disc[td] : 0.0;
+    const int end = boot < len ? boot : len;
+    for (int i = 0; t + i < end; ++i) value += reward[t + i] * disc[i];
+    return value;
+}
+
+// ---- row k of an entry at position `pos` of an episode of `len` steps (the inside / outside rules of ReplayBuffer.sample)
+struct Row {
+    float value;        // tv[b, k]
+    float reward;       // tr[b, k]
+    float mask;         // mask[b, k]
+    int policy_step;    // tp[b, k] = policy[policy_step], or the uniform policy when -1
+    int64_t action;     // actions[b, k - 1] (k > 0)
+};
+// `filler`: the action drawn for actions[b, k - 1] when step pos + k - 1 lies past the end
+RZT_FN Row unroll_row(const double *reward, const double *root_value, const int32_t *action, int len, int pos, int k, int td,
+                      const double *disc, int64_t filler) {
+    Row r;
+    const int i = pos + k;
+    const bool in = i < len;
+    r.value = in ? (float)value_target(reward, root_value, len, i, td, disc) : 0.0f;
+    r.mask = in ? 1.0f : 0.0f;
+    r.policy_step = in ? i : -1;
+    r.reward = 0.0f;
+    r.action = 0;
+    if (k > 0) {   // the action taken at step i - 1 and its reward: still real at i == len
+        const bool prev = i - 1 < len;
+        r.action = prev ? (int64_t)action[i - 1] : filler;
+        r.reward = prev ? (float)reward[i - 1] : 0.0f;
+    }
+    return r;
+}
+// np.full(.., 1.0 / n_actions, dtype=float32)
+RZT_FN float uniform_policy(int A) { return (float)(1.0 / (double)A); }
+
+// ---- a stored step from a packed record: float64 [obs (D) | action | reward | visits (A) | root value | done].  The policy is
+// EpisodeSeq.fields_of_packed's visits / sum(visits) in fp64 (visit counts are integers: the sum is exact in any order), cast
+// to float32; `final_policy`: the columns already hold the float32 policy (an Episode of the move-by-move routes), only cast.
+RZT_FN float policy_of_row(const double *row, int D, int A, int a, bool final_policy) {
+    const double *vis = row + D + 2;
+    if (final_policy) return (float)vis[a];
+    double sum = 0.0;
+    for (int b = 0; b < A; ++b) sum += vis[b];
+    return (float)(vis[a] / sum);
+}
+
+}  // namespace rzmzt

@@ -6,7 +6,8 @@ the small MLPs of the learned model and the learner on PyTorch-ROCm."""
 from .agent import MuZeroAgent
 from .cartpole import CartPoleBatch
 from .network import MuZeroNet
+from .replay import MuZeroDeviceReplay, mz_replay_draws
 from .selfplay import MuZeroSelfPlay, ReplayBuffer
 from .tree import MuZeroTree
 
-__all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree']
+__all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree', 'MuZeroDeviceReplay', 'mz_replay_draws']

@@ -21,8 +21,9 @@ class MuZeroAgent(object):
         self.optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=weight_decay)
 
     def learn(self, batch):
-        """batch = ReplayBuffer.sample(...) -> (loss, value loss, reward loss, policy loss) floats."""
-        obs, actions, tv, tr, tp, mask = (torch.from_numpy(a).to(self.device) for a in batch)
+        """batch = ReplayBuffer.sample(...) (numpy arrays) or MuZeroDeviceReplay.sample(...) (device tensors, taken as they are)
+        -> (loss, value loss, reward loss, policy loss) floats."""
+        obs, actions, tv, tr, tp, mask = ((a if isinstance(a, torch.Tensor) else torch.from_numpy(a)).to(self.device) for a in batch)
         K = actions.shape[1]
         net = self.net
         net.train()

@@ -340,10 +340,11 @@ class MuZeroSelfPlay(object):
         return t.multinomial(w / w.sum(dim=1, keepdim=True), 1, generator=self.gen).squeeze(1)
 
     # ------------------------------------------------------------------ game loop
-    def play_move(self):
-        """One move of every environment; returns the episodes that ended with it."""
+    def play_move(self, replay=None):
+        """One move of every environment; returns the episodes that ended with it.  ``replay`` (a MuZeroDeviceReplay): they are
+        handed to it as well (``collect``)."""
         if self.fused_moves:
-            finished = self._collect_fused(1)
+            finished = self._collect_fused(1, replay)
             self.obs = self.env.observe()
             return finished
         t = self.torch
@@ -356,6 +357,8 @@ class MuZeroSelfPlay(object):
                         visits.to(t.float64), root_value.to(t.float64)[:, None],
                         (terminated | truncated).to(t.float64)[:, None]), dim=1).cpu().numpy()
         finished = self._ingest(packed)
+        if replay is not None:
+            replay.add(finished)
         self.obs = nxt_obs
         return finished
 
@@ -486,9 +489,12 @@ class MuZeroSelfPlay(object):
         self.sims_done += self.n_sims * self.n_envs * n_moves
         self.moves_done += self.n_envs * n_moves
 
-    def _episodes_of_launch(self, buf):
-        """The finished episodes of a launch from its arena (host copy), ordered by (last move, environment)."""
-        _, (counters, entries, arena), event = buf
+    def _episodes_of_launch(self, buf, replay=None):
+        """The finished episodes of a launch from its arena (host copy), ordered by (last move, environment).  ``replay``: the
+        episodes also go to that device buffer, in the same order -- the ones in the arena from the launch's DEVICE arena (the
+        ingest is enqueued on the launch stream here, before this set of buffers is launched into again: stream order protects the
+        arena), the ones that missed it from the block the slow path fetches."""
+        (_, _, arena_dev), (counters, entries, arena), event = buf
         event.synchronize()
         D, A = self.net.obs_dim, self.n_actions
         n_rows, n_entries, missed = (int(v) for v in counters.numpy()[:3])
@@ -503,6 +509,8 @@ class MuZeroSelfPlay(object):
             used = min(n_rows, arena.shape[0])
             # (a copy: the pinned buffer is the next-but-one launch's; the episodes' fields are formed when they are asked for)
             finished._add_packed(arena.numpy()[:used].copy(), D, A, ent[fits, 2], ent[fits, 3])
+            if replay is not None:
+                replay.ingest(arena_dev, ent[fits, 2], ent[fits, 3])
         if missed:  # the arena was too small for these: their records are still in the ring
             t = self.torch
             env, end, length = (ent[~fits, c] for c in (0, 1, 2))
@@ -511,9 +519,11 @@ class MuZeroSelfPlay(object):
             step_idx = (np.repeat(end - length, length) + within) % self._ring.shape[1]
             block = self._ring[t.from_numpy(env_idx).to(self.device), t.from_numpy(step_idx).to(self.device)].cpu().numpy()
             finished._add_packed(block, D, A, length)
+            if replay is not None:
+                replay.add_packed(block, length)
         return finished
 
-    def _collect_fused(self, n_moves):
+    def _collect_fused(self, n_moves, replay=None):
         """``n_moves`` moves in launches of ``moves_per_launch``; what ended during a launch is read while the next one
         runs (the environments, their histories and the random streams live on the device: a launch needs nothing from
         the host, and the host reads finished episodes, not moves)."""
@@ -531,17 +541,19 @@ class MuZeroSelfPlay(object):
                 pending.append(bufs[which])
                 left -= k
                 which = (which + 1) % len(bufs)
-            finished.extend(self._episodes_of_launch(pending.pop(0)))
+            finished.extend(self._episodes_of_launch(pending.pop(0), replay))
         return finished
 
-    def collect(self, n_moves):
-        """``n_moves`` moves of every environment -> the finished episodes (an EpisodeSeq: len / iteration / indexing)."""
+    def collect(self, n_moves, replay=None):
+        """``n_moves`` moves of every environment -> the finished episodes (an EpisodeSeq: len / iteration / indexing).
+        ``replay`` (a MuZeroDeviceReplay): the finished episodes are also stored there, in the order of the returned sequence --
+        whole moves hand them over on the device (``_episodes_of_launch``), the move-by-move routes through ``replay.add``."""
         if self.fused_moves:
-            out = self._collect_fused(n_moves)
+            out = self._collect_fused(n_moves, replay)
             self.obs = self.env.observe()
         else:
             out = EpisodeSeq()
             for _ in range(n_moves):
-                out.extend(self.play_move())
+                out.extend(self.play_move(replay))
         self.tree.check()
         return out
