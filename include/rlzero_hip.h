@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 35
+#define RZ_ABI_VERSION 36
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -974,6 +974,35 @@ int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n
 int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
                       float *h_policy, int32_t *h_length, void *stream);
 int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * MuZero Reanalyse (ABI 36; rz_mz_replay.hip: k_mzr_positions, k_mzr_update; rz_mz_target.h; rlzero_amd/muzero/reanalyse.py):
+ * the two device ends of searching stored steps again with the current network.  Between them the caller runs a search from
+ * the observations handed out (rz_mz_init_roots + rz_mz_search or the step loop) and reads its roots (rz_mz_root_children,
+ * rz_mz_root_stats).  No function or kernel above changes.
+ *
+ * rz_mz_replay_positions: n entries in ONE launch (k_mzr_positions: a thread per entry and observation element).  Entry i is
+ *   resolved to a physical (slot, position), written to d_where int32 [n][2], and its stored observation goes to d_obs float32
+ *   [n][D].  The entries come from h_draws int64 [n][2] (episode, 0 = the oldest held; position: checked here, RZ_ERR_ARG, and
+ *   staged), from d_draws (device memory: checked by the kernel), or, both NULL, from the device's own draws of refresh `step`:
+ *   counter c = 2 i + j gives mulhi64(x, m) of x = sm(sm(sm(seed ^ "mzreanal") ^ step) ^ c) -- j = 0 the episode, m = count;
+ *   j = 1 the position, m = that episode's length (rlzero_amd/muzero/reanalyse.py: mz_reanalyse_draws gives the same bits; the
+ *   salt keeps a refresh and a mini-batch of one update number apart).  seed and step are ignored when draws are given.  A device
+ *   draw out of range: where = (-1, -1), the observation row zeroed, RZ_MZ_REPLAY_BAD_INDEX set, nothing read for it.
+ *   *ticket receives the number of episodes EVER stored in this handle (host state, advanced by add / ingest), also for n = 0.
+ * rz_mz_replay_update: ONE launch (k_mzr_update: a thread per entry and action, plus one per entry for the value).  For every
+ *   entry whose where is valid -- 0 <= slot < E, 0 <= position < T and below the slot's length, checked in the kernel -- it writes
+ *   policy[slot][position][a] = (float)((double)visits[a] / (double)sum(visits)) from d_visits int32 [n][A] (a sum of 0: the
+ *   uniform policy (float)(1.0 / A)) and root_value[slot][position] = d_root_sum[i] / (double)max(d_root_n[i], 1) (d_root_n int32
+ *   [n], d_root_sum float64 [n]: rz_mz_root_stats' N and value sum).  Nothing else is written; an entry with another where -- the
+ *   (-1, -1) of a refused or a padding row -- writes nothing.  `ticket` must be what rz_mz_replay_positions returned and still be
+ *   the handle's counter: an add or ingest in between may have given a slot to another episode, and the result of a search must
+ *   never land there -- RZ_ERR_ARG, no launch.  Two entries that name the same step BOTH write it: the search is deterministic,
+ *   so they carry the same bits and the order of the two writes does not matter. */
+int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, uint64_t seed, uint64_t step, int64_t n,
+                           int32_t *d_where, float *d_obs, int64_t *ticket, void *stream);
+int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, const int32_t *d_root_n,
+                        const double *d_root_sum, int64_t ticket, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,12 @@
-// rz_mz_replay.hip -- the MuZero learner's replay buffer in device memory (include/rlzero_hip.h: rz_mz_replay_*, ABI 35).
+// rz_mz_replay.hip -- the MuZero learner's replay buffer in device memory (include/rlzero_hip.h: rz_mz_replay_*, ABI 35; Reanalyse: ABI 36).
 //
 // Finished episodes live on the GPU in fixed-stride slots -- slot e holds up to T steps, structure of arrays -- in a ring over
 // EPISODES, and a mini-batch of unrolled targets is ONE launch: k_mzr_gather / k_mzr_sample write the observation, the K actions
 // and the K + 1 value / reward / policy targets and masks of every entry straight into the learner's tensors, bit for bit what
 // rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample forms on the host (the rules and the arithmetic: rz_mz_target.h).  Episodes
 // arrive as packed float64 records, the format of rz_mz_play_cartpole: from a staged host block (k_mzr_add) or straight from a
-// launch's device arena (k_mzr_ingest: only a small entry table travels).
+// launch's device arena (k_mzr_ingest: only a small entry table travels).  Reanalyse (k_mzr_positions, k_mzr_update) hands stored
+// observations out to a fresh search and takes its visit counts and root value back into the steps they came from.
 //
 // Bounds: every slot is reduced modulo the capacity, every length is clamped to 0 .. T where it is read, every step index is compared
 // with that length before a read, rows of a block are checked against its row count (on the host and again in the kernel), and an
@@ -156,6 +157,66 @@ __global__ __launch_bounds__(kThreads) void k_mzr_sample(MzrDev R, MzrOut O, uns
     mzr_emit(R, O, b, k, slot, len, pos, filler);
 }
 
+// Reanalyse, the way out: entry i resolved to a physical (slot, position) in `where` int32 [n][2] and its stored observation in
+// obs float32 [n][D].  A thread per (entry, observation element).  draws int64 [n][2] (episode, 0 = the oldest held; position), or
+// NULL: the draws of refresh `step` made here (rz_mz_target.h: reanalyse_draw).  An entry out of range: where = (-1, -1), a zeroed
+// row, the flag, and nothing of the store is read for it.
+__global__ __launch_bounds__(kThreads) void k_mzr_positions(MzrDev R, const long long *__restrict__ draws, unsigned long long seed,
+                                                             unsigned long long step, long long oldest, long long count, long long n,
+                                                             int32_t *__restrict__ where, float *__restrict__ obs) {
+    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const int D = R.D;
+    const long long i = tid / D;
+    const int d = (int)(tid % D);
+    if (i >= n) return;
+    long long ep, pos = -1;
+    if (draws != nullptr) {
+        ep = draws[2 * i], pos = draws[2 * i + 1];
+    } else {
+        ep = rzmzt::reanalyse_draw(seed, step, (uint64_t)i, 0, (uint64_t)count);
+    }
+    bool bad = ep < 0 || ep >= count;
+    int slot = 0;
+    if (!bad) {
+        slot = mzr_slot(R, oldest + ep);
+        const int len = mzr_length(R, slot);
+        if (draws == nullptr && len > 0) pos = rzmzt::reanalyse_draw(seed, step, (uint64_t)i, 1, (uint64_t)len);
+        bad = pos < 0 || pos >= len;   // (len == 0 with draws made here: an episode held is never empty)
+    }
+    if (bad) {
+        if (d == 0) {
+            atomicOr(R.err, kFlagBadIndex);
+            where[2 * i] = -1, where[2 * i + 1] = -1;
+        }
+        obs[i * D + d] = 0.0f;
+        return;
+    }
+    if (d == 0) where[2 * i] = slot, where[2 * i + 1] = (int32_t)pos;
+    obs[i * D + d] = R.obs[((long long)slot * R.T + pos) * D + d];
+}
+
+// Reanalyse, the way back: the policy and the root value of step where[i] from the visit counts and the root's (N, value sum) of a
+// fresh search (rz_mz_target.h: policy_of_visits, root_value_of).  A thread per (entry, action) plus one for the value; nothing
+// else of the step is written.  `where` is checked again here -- slot against E, position against T and the slot's length -- and
+// an entry that fails (the (-1, -1) of a refused or padded row among them) writes nothing.
+__global__ __launch_bounds__(kThreads) void k_mzr_update(MzrDev R, const int32_t *__restrict__ where, long long n, const int32_t *__restrict__ visits,
+                                                          const int32_t *__restrict__ root_n, const double *__restrict__ root_sum) {
+    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const int A = R.A;
+    const long long i = tid / (A + 1);
+    const int a = (int)(tid % (A + 1));
+    if (i >= n) return;
+    const int slot = where[2 * i], pos = where[2 * i + 1];
+    if (slot < 0 || slot >= R.E || pos < 0 || pos >= R.T) return;
+    if (pos >= mzr_length(R, slot)) return;
+    const long long at = (long long)slot * R.T + pos;
+    if (a < A) {
+        R.policy[at * A + a] = rzmzt::policy_of_visits(visits + i * A, A, a);
+    } else {
+        R.root_value[at] = rzmzt::root_value_of(root_n[i], root_sum[i]);
+    }
+}
+
 int mr_fail(int code, const char *msg) {
     rz_set_error(msg);
     return code;
@@ -167,6 +228,7 @@ struct rz_mz_replay {
     MzrDev dev = {};
     int device = 0;
     long long cursor = 0, count = 0;   // next slot written; episodes held
+    long long stored = 0;              // episodes ever stored: the ticket of rz_mz_replay_positions / rz_mz_replay_update
     std::vector<int32_t> lengths;      // [E] by slot: the host's copy of dev.length
     double *d_disc = nullptr;
     // one staging pair (pinned host + device), reused: the host half after `copied`, the device half after `consumed`
@@ -260,6 +322,7 @@ void mr_commit(rz_mz_replay *r, const std::vector<int32_t> &table, long long kep
     for (size_t e = 0; e < table.size() / kEntryWords; ++e) r->lengths[(size_t)table[kEntryWords * e + 2]] = table[kEntryWords * e];
     r->cursor = (r->cursor + kept) % E;
     r->count = r->count + kept > E ? E : r->count + kept;
+    r->stored += kept;
 }
 
 int mr_outputs(rz_mz_replay *r, int64_t n, const MzrOut &O) {
@@ -460,6 +523,58 @@ int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n
     hipLaunchKernelGGL(k_mzr_sample, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
                        (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
     if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_sample launch failed");
+    return RZ_OK;
+}
+
+int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, uint64_t seed, uint64_t step, int64_t n,
+                            int32_t *d_where, float *d_obs, int64_t *ticket, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (ticket == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_draws != nullptr && d_draws != nullptr) return mr_fail(RZ_ERR_ARG, "at most one of h_draws / d_draws");
+    *ticket = r->stored;
+    if (n == 0) return RZ_OK;
+    if (d_where == nullptr || d_obs == nullptr) return mr_fail(RZ_ERR_ARG, "NULL output buffer");
+    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    hipStream_t s = (hipStream_t)stream;
+    const long long oldest = mr_oldest(r);
+    const long long *draws = (const long long *)d_draws;
+    if (h_draws != nullptr) {
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t *dr = h_draws + 2 * i;
+            if (dr[0] < 0 || dr[0] >= r->count) return mr_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return mr_fail(RZ_ERR_ARG, "a position is outside its episode");
+        }
+        const size_t bytes = (size_t)n * 2 * sizeof(int64_t);
+        rc = mr_stage(r, bytes, s);
+        if (rc != RZ_OK) return rc;
+        memcpy(r->h_stage, h_draws, bytes);
+        rc = mr_upload(r, bytes, s);
+        if (rc != RZ_OK) return rc;
+        draws = (const long long *)r->d_stage;
+    }
+    const unsigned blocks = (unsigned)((n * r->dev.D + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_mzr_positions, dim3(blocks), dim3(kThreads), 0, s, r->dev, draws, (unsigned long long)seed, (unsigned long long)step, oldest,
+                       r->count, (long long)n, d_where, d_obs);
+    if (h_draws != nullptr) return mr_launched(r, s, "k_mzr_positions launch failed");
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_positions launch failed");
+    return RZ_OK;
+}
+
+int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, const int32_t *d_root_n,
+                        const double *d_root_sum, int64_t ticket, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    // an add or ingest since rz_mz_replay_positions may have given a slot to another episode: the search's result has no home
+    if (ticket != r->stored) return mr_fail(RZ_ERR_ARG, "stale ticket: episodes were stored since rz_mz_replay_positions");
+    if (n == 0) return RZ_OK;
+    if (d_where == nullptr || d_visits == nullptr || d_root_n == nullptr || d_root_sum == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    const unsigned blocks = (unsigned)((n * (r->dev.A + 1) + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_mzr_update, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, r->dev, d_where, (long long)n, d_visits, d_root_n,
+                       d_root_sum);
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_update launch failed");
     return RZ_OK;
 }
 

@@ -3,7 +3,8 @@
 // the CPU can test it against rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample (tests/test_mz_replay_host.py); the kernels call
 // these functions.  The arithmetic is fp64 multiply and add in the order of ReplayBuffer._value_target, the discounts come from a
 // table the host filled with `discount ** i` (no pow here), and the value is cast to float32 once: with -ffp-contract=off the
-// host's bits.
+// host's bits.  Reanalyse's arithmetic and draws (k_mzr_positions, k_mzr_update) are at the end, tested the same way
+// (tests/test_mz_reanalyse_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -97,6 +98,30 @@ RZT_FN float policy_of_row(const double *row, int D, int A, int a, bool final_po
     double sum = 0.0;
     for (int b = 0; b < A; ++b) sum += vis[b];
     return (float)(vis[a] / sum);
+}
+
+// ---- Reanalyse (k_mzr_positions, k_mzr_update; rlzero_amd/muzero/reanalyse.py): a stored step searched again, its policy and
+// root value replaced.
+// The policy of fresh visit counts: fields_of_packed's expression on integers (their sum is exact); a root that was never
+// visited gets the uniform policy.
+RZT_FN float policy_of_visits(const int32_t *visits, int A, int a) {
+    int64_t sum = 0;
+    for (int b = 0; b < A; ++b) sum += visits[b];
+    if (sum == 0) return uniform_policy(A);
+    return (float)((double)visits[a] / (double)sum);
+}
+// MuZeroSelfPlay.search's vsum / n.clamp_min(1)
+RZT_FN double root_value_of(int32_t n, double value_sum) { return value_sum / (double)(n > 1 ? n : 1); }
+
+constexpr uint64_t kReanalyseSalt = 0x6D7A7265616E616Cull;   // "mzreanal": a refresh and a mini-batch of one update number share no draw
+
+// counter c = 2 i + j of refresh `step` -- j = 0 the episode (n = episodes held), j = 1 the position (n = its length); the chain
+// of `draw` under the salt above (rlzero_amd/muzero/reanalyse.py: mz_reanalyse_draws, the same bits)
+RZT_FN int64_t reanalyse_draw(uint64_t seed, uint64_t step, uint64_t i, int j, uint64_t n) {
+    uint64_t x = mix64(seed ^ kReanalyseSalt);
+    x = mix64(x ^ step);
+    x = mix64(x ^ (2 * i + (uint64_t)j));
+    return (int64_t)mulhi64(x, n);
 }
 
 }  // namespace rzmzt

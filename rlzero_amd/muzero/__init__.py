@@ -6,8 +6,10 @@ the small MLPs of the learned model and the learner on PyTorch-ROCm."""
 from .agent import MuZeroAgent
 from .cartpole import CartPoleBatch
 from .network import MuZeroNet
+from .reanalyse import MuZeroReanalyser, mz_reanalyse_draws
 from .replay import MuZeroDeviceReplay, mz_replay_draws
 from .selfplay import MuZeroSelfPlay, ReplayBuffer
 from .tree import MuZeroTree
 
-__all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree', 'MuZeroDeviceReplay', 'mz_replay_draws']
+__all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree', 'MuZeroDeviceReplay', 'mz_replay_draws',
+           'MuZeroReanalyser', 'mz_reanalyse_draws']

@@ -269,6 +269,63 @@ class MuZeroDeviceReplay(object):
                    'rz_mz_replay_sample')
         return out
 
+    # ------------------------------------------------------------------ Reanalyse: stored steps out, fresh targets back
+    def positions(self, ep_idx=None, pos=None, n=None, seed=None, step=0):
+        """Entries resolved to physical steps and their stored observations, one launch (k_mzr_positions) -> (where int32 [n, 2]
+        = (slot, position), obs float32 [n, D], ticket).  The entries: ``ep_idx`` / ``pos`` [n] (episode 0 = the oldest held) as
+        numpy arrays / sequences (checked before the launch) or int64 device tensors (checked by the kernel: such an entry gets
+        where = (-1, -1), a zeroed observation and the BAD_INDEX flag of ``poll_errors``), or, both None, the device's own ``n``
+        draws of refresh ``step`` (reanalyse.py: mz_reanalyse_draws).  ``ticket`` counts the episodes ever stored here: ``update``
+        takes it back and refuses if an ``add`` / ``ingest`` came in between."""
+        t = self.torch
+        h_draws = d_draws = keep = None
+        if ep_idx is None:
+            if pos is not None or n is None:
+                raise ValueError('positions: draws (ep_idx and pos) or a number of entries to draw on the device')
+            n = int(n)
+        elif isinstance(ep_idx, t.Tensor) and isinstance(pos, t.Tensor):
+            for x in (ep_idx, pos):
+                if x.device != self.device or x.dtype != t.int64:
+                    raise ValueError('device draws: int64 tensors on %s' % (self.device, ))
+            n = ep_idx.numel()
+            if pos.numel() != n:
+                raise ValueError('%d episodes and %d positions' % (n, pos.numel()))
+            keep = t.stack((ep_idx.reshape(n), pos.reshape(n)), dim=1).contiguous()
+            d_draws = keep.data_ptr()
+        else:
+            ep_idx = np.asarray(ep_idx, dtype=np.int64).reshape(-1)
+            n = len(ep_idx)
+            keep = np.ascontiguousarray(np.stack((ep_idx, np.asarray(pos, dtype=np.int64).reshape(n)), axis=1))
+            h_draws = _ptr(keep)
+        where = t.empty((n, 2), dtype=t.int32, device=self.device)
+        obs = t.empty((n, self.obs_dim), dtype=t.float32, device=self.device)
+        ticket = ctypes.c_int64(-1)
+        _hip.check(self.lib.rz_mz_replay_positions(self.handle, h_draws, d_draws, (self.seed if seed is None else int(seed)) & _MASK,
+                                                   int(step) & _MASK, n, where.data_ptr(), obs.data_ptr(), ctypes.byref(ticket), self._stream()),
+                   'rz_mz_replay_positions')
+        return where, obs, ticket.value
+
+    def update(self, where, visits, root_n, root_sum, ticket):
+        """The policy and the root value of every step named by a valid row of ``where`` (int32 [n, 2], of ``positions``) from a
+        fresh search's ``visits`` int32 [n, A], ``root_n`` int32 [n] and ``root_sum`` float64 [n], one launch (k_mzr_update):
+        policy = float32(visits / sum(visits)), root value = root_sum / max(root_n, 1); nothing else is written, a row of
+        (-1, -1) writes nothing.  HipError, and no launch, if episodes were stored since ``ticket`` was given out."""
+        t = self.torch
+        n = int(where.shape[0]) if where.dim() == 2 else -1
+        for x, dtype, shape in ((where, t.int32, (n, 2)), (visits, t.int32, (n, self.n_actions)), (root_n, t.int32, (n, )),
+                                (root_sum, t.float64, (n, ))):
+            if not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError('update: contiguous tensors on %s -- where int32 [n, 2], visits int32 [n, %d], root_n int32 [n], '
+                                 'root_sum float64 [n]' % (self.device, self.n_actions))
+        _hip.check(self.lib.rz_mz_replay_update(self.handle, where.data_ptr(), n, visits.data_ptr(), root_n.data_ptr(), root_sum.data_ptr(),
+                                                int(ticket), self._stream()), 'rz_mz_replay_update')
+
+    def poll_errors(self):
+        """The device's flag word (_hip.MZ_REPLAY_BAD_INDEX / MZ_REPLAY_BAD_ROWS), cleared by the call; waits for the stream."""
+        flags = ctypes.c_int32()
+        _hip.check(self.lib.rz_mz_replay_poll_errors(self.handle, ctypes.byref(flags), self._stream()), 'rz_mz_replay_poll_errors')
+        return flags.value
+
     def read(self):
         """The episodes held, oldest first, as the host buffer keeps them: a list of ``Episode`` (obs float32 [n, D], actions
         int64 [n], rewards float64 [n], policies float32 [n, A], root_values float64 [n]).  A synchronous copy (tests, debugging)."""

@@ -7,6 +7,7 @@ its ``tools/train_alphazero.py`` (a pipeline class with ``collect_selfplay_data`
 
     python tools/train_muzero.py --envs 256 --iterations 60
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay   # episodes and mini-batches stay on the GPU
+    python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --reanalyse all   # and their targets stay fresh
 """
 import argparse
 import os
@@ -18,14 +19,33 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+NEEDS_DEVICE_REPLAY = '--reanalyse needs --device-replay: the steps are searched again and refreshed where they are stored, on the GPU'
+
+
+def reanalyse_arg(text):
+    """--reanalyse N|all -> 0 (off), a number of positions per iteration, or 'all'."""
+    if text == 'all':
+        return text
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError('a number of positions >= 0, or all')
+    return n
+
 
 class MuZeroPipeline(object):
 
     def __init__(self, n_envs=256, n_sims=50, unroll_steps=5, td_steps=10, discount=0.997, batch_size=256,
-                 moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False):
+                 moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
+                 reanalyse_batch=2048):
         """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
-        mini-batch is one launch there; otherwise the host ReplayBuffer, as before."""
-        from rlzero_amd.muzero import CartPoleBatch, MuZeroAgent, MuZeroDeviceReplay, MuZeroSelfPlay, ReplayBuffer
+        mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
+        ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
+        (or, 'all', every step held), are searched again with the current network and their policy and root value refreshed
+        (MuZeroReanalyser: a second, small search object; the self-play object and its counters are not touched).  0: off."""
+        self.reanalyse = reanalyse if reanalyse == 'all' else int(reanalyse or 0)
+        if self.reanalyse and not device_replay:
+            raise ValueError(NEEDS_DEVICE_REPLAY)
+        from rlzero_amd.muzero import CartPoleBatch, MuZeroAgent, MuZeroDeviceReplay, MuZeroReanalyser, MuZeroSelfPlay, ReplayBuffer
         self.agent = MuZeroAgent(device=device)
         self.env = CartPoleBatch(n_envs, device, seed=seed)
         self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed)
@@ -35,6 +55,9 @@ class MuZeroPipeline(object):
                                              unroll_steps=unroll_steps, td_steps=td_steps, discount=discount, device=device, seed=seed)
         else:
             self.buffer = ReplayBuffer(unroll_steps=unroll_steps, td_steps=td_steps, discount=discount, seed=seed)
+        self.reanalyser = None
+        if self.reanalyse:
+            self.reanalyser = MuZeroReanalyser(self.agent.net, self.buffer, n_sims=n_sims, batch=reanalyse_batch, discount=discount, seed=seed)
         self.batch_size = batch_size
         self.moves_per_iteration = moves_per_iteration
         self.updates_per_iteration = updates_per_iteration
@@ -53,6 +76,12 @@ class MuZeroPipeline(object):
             self.episode_len = float(np.mean([len(ep) for ep in episodes]))
         return len(episodes)
 
+    def reanalyse_targets(self):
+        """-> the number of stored steps refreshed (0 when off)."""
+        if self.reanalyser is None:
+            return 0
+        return self.reanalyser.reanalyse_all() if self.reanalyse == 'all' else self.reanalyser.reanalyse_sample(self.reanalyse)
+
     def policy_update(self):
         out = (0.0, 0.0, 0.0, 0.0)
         for _ in range(self.updates_per_iteration):
@@ -67,9 +96,11 @@ class MuZeroPipeline(object):
             n = self.collect_selfplay_data()
             if len(self.buffer) < 8:
                 continue
+            refreshed = self.reanalyse_targets()
             loss, lv, lr_, lp = self.policy_update()
             print('batch i:{}, episodes:{}, episode_len:{:.1f}, loss:{:.4f}, value:{:.4f}, reward:{:.4f}, '
-                  'policy:{:.4f}'.format(i + 1, n, self.episode_len, loss, lv, lr_, lp), flush=True)
+                  'policy:{:.4f}'.format(i + 1, n, self.episode_len, loss, lv, lr_, lp)
+                  + (', reanalysed:{}'.format(refreshed) if self.reanalyser is not None else ''), flush=True)
         return self.episode_len
 
 
@@ -83,9 +114,14 @@ if __name__ == '__main__':
     ap.add_argument('--device-replay', action='store_true', help='keep the replay buffer and the target formation on the GPU')
     ap.add_argument('--batch-size', type=int, default=256)
     ap.add_argument('--updates-per-iteration', type=int, default=40)
+    ap.add_argument('--reanalyse', type=reanalyse_arg, default=0, metavar='N|all',
+                    help='per iteration, search N stored steps (or all of them) again with the current network and refresh their targets '
+                         '(needs --device-replay; 0 = off)')
     args = ap.parse_args()
+    if args.reanalyse and not args.device_replay:
+        ap.error(NEEDS_DEVICE_REPLAY)
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
-                          updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay)
+                          updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse)
     pipe.run(args.iterations)
     if args.save:
         pipe.agent.save_model(args.save)
