@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 F="--offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -std=c++17 -fPIC -Wno-unused-function -Iinclude"
 H=$(python -c "import rlzero_amd._build as b; print(b.source_hash())")
 O=$(mktemp -d)
-for f in rz_engine rz_net rz_muzero rz_replay; do
+for f in rz_engine rz_net rz_muzero rz_replay rz_mz_replay; do
   hipcc $F -DRZ_NET_PROFILE $NETPROF_EXTRA -DRZ_SOURCE_HASH="\"$H\"" -c rlzero_amd/csrc/$f.hip -o $O/$f.o &
 done
 wait

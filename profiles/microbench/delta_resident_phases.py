@@ -16,12 +16,16 @@ import numpy as np, torch
 from rlzero_amd.engine import HipNetEvaluator, MCTSEngine
 from rlzero_amd.games.gomoku.policy_value_net import PolicyValueNet
 lib = H.load()
-NAMES = [(0, 'leaf + changed cells'), (1, 'distances, requests, ranks'), (3, 'maps, base records'), (4, 'bar'), (5, 'conv1'), (6, 'bar'), (7, 'conv2'),
+# (since the early release -- ResHook::leaf -- wave 0's rows from the release to conv2 are: 'sel: tail behind the release' + 'verdict' +
+# 'requests, ranks' + 'maps; wave 0: planes, conv1' = its arrival at the barrier before conv2, 'bar' behind them its wait there; rows 5 and 6
+# are those of the passes without a base; 'selection (up to the release)' ends at the release barrier; the last row is wave 1's)
+NAMES = [(0, 'verdict'), (1, 'requests, ranks'), (3, 'maps; wave 0: planes, conv1'), (4, 'bar'), (5, 'conv1'), (6, 'bar'), (7, 'conv2'),
          (9, 'bar + conv3 + heads'), (10, 'bar'), (11, 'features'), (12, 'bar'), (16, 'value layer'), (17, 'expand + backup'),
          # the selection's own rows (-DRZ_SEL_TICKS=<mask>, rz_delta.h: a tick that is off leaves its cycles to the next one taken; 18 = the rest,
          # without any of them the whole selection) and wave 1's pre-scan with the barrier wait behind it
-         (2, 'sel: root record'), (8, 'sel: root scan / answer'), (13, 'sel: level-0 cell'), (14, 'sel: deeper levels'), (15, 'sel: terminal test + leaf stores'),
-         (18, 'selection (rest: hand-over)'), (19, 'wave 1: pre-scan'), (20, 'wave 1: wait behind it')]
+         (2, 'sel: root record'), (8, 'sel: root scan / answer'), (13, 'sel: level-0 cell'), (14, 'sel: deeper levels'), (15, 'sel: tail behind the release'),
+         (18, 'selection (up to the release)'), (19, 'wave 1: pre-scan'), (20, 'wave 1: wait behind it'),
+         (21, 'wave 1: release -> its arrival at the barrier before conv2')]
 VALUES = '--values' in sys.argv[1:]
 if VALUES:
     import rlzero_amd.route as _R

@@ -350,14 +350,15 @@ __device__ __forceinline__ void conv3_tiles(lds_u32 map2, const uint16_t *list3,
 
 // ---- what the pass loop of a leaf needs (one struct so that the two kernels below share the loop)
 struct Leaf {
-    f16x4 cell_planes;        // the four planes of this thread's cell
+    f16x4 cell_planes;        // the four planes of this thread's cell (delta_passes<true>: not read, the planes are formed from leaf_lds)
+    const uint64_t *leaf_lds; // delta_passes<true>: the leaf in LDS (select_body's lds_leaf layout: stones [8], side to move, last cell)
     const char *base;         // the base of the leaf's parity (mode 1: the base being built)
     int dys[kMaxD], dxs[kMaxD];   // the changed cells (-100: none)
     _Float16 *dst16;          // the policy pieces' place in the store (NULL: none)
     float *vdst;              // the value head's input row (global memory, or LDS in the resident search)
     float *dst32;             // f32 features (tests; NULL otherwise)
     const uint64_t *sets;     // delta_passes<true>: pass -1's window sets, handed over in LDS (leaf_windows)
-    uint16_t *gtab;           // delta_passes<true>: THIS wave's table of the base records it copies (rz_gather.h: rzg::kTabEntries entries of LDS)
+    uint16_t *gtab;           // delta_passes<true>: THIS wave's table of the base records it copies (rz_gather.h: rzg::Split<3>::kTabEntries entries of LDS)
     bool deferred, store_head;
 };
 struct Layers {
@@ -415,6 +416,58 @@ static_assert(rzg::kC1Max == kC1Slots && rzg::kC2Max == kC2Slots && rzg::kC1Byte
               "rz_gather.h's records are the base's and the budget is this file's");
 static_assert(rzg::kC1Bytes <= P1 && rzg::kC2Bytes <= P2, "a record fits its LDS slot");
 
+__device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int tm_eff, bool has_last, int lc, int par_count);
+
+// the leaf the selection left in LDS (wave-uniform values)
+__device__ __forceinline__ void leaf_from_lds(const uint64_t *leaf_lds, uint64_t (&ls)[8], int &tm, int &lc, int &nst) {
+    nst = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        ls[q] = uni64(leaf_lds[q]);
+        nst += __popcll(ls[q]);
+    }
+    tm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(leaf_lds + 2 * RZ_BOARD_WORDS)[0]);
+    lc = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(leaf_lds + 2 * RZ_BOARD_WORDS)[1]);
+}
+
+// conv1 (4 -> 32) of tile `tile` of list1 (32 cells) by one wave: trunk_rows_body's conv1 with the lane's cell taken from the list
+__device__ __forceinline__ void conv1_tile(int tile, int total, int lane, const char *in0, const uint16_t *list1, const uint32_t *map1,
+                                           const sp::f16x8 (&a1)[3][2], const f32x4 (&bias1)[4], float k1, float act1) {
+    const int n32 = lane & 31, h = lane >> 5, idx = 32 * tile + n32;
+    const int pos = list1[idx];
+    const int py = (pos * 3641) >> 16, px = pos - py * kRowW;   // halo row / column (board row py - 1, column px - 1)
+    typedef const __attribute__((address_space(3))) f16x4 *lds_half;
+    const lds_half q = (lds_half)(in0 + ((py - 1) * sp::kInCols + (px - 1) + 2 * h) * 8);
+    sp::f16x8 b1[3];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int o = ky * sp::kInCols;
+        const f16x4 lo4 = q[o], hi4 = q[o + 1];
+        b1[ky] = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+    sp::f32x16 acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc1[r] = 0.0f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int combo = 0; combo < 3; combo += 2)   // (the lo pieces of 0 / 1 planes are zero: no hi x lo product)
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[ky][combo == 2], b1[ky], acc1, 0, 0, 0);
+    if (idx < total) {
+        const uint32_t rec = map1[pos] + (uint32_t)(4 * h * 2);
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+            float z[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = fmaxf(fmaf(acc1[4 * gg + j], k1, bias1[gg][j] * act1), 0.0f);
+            f16x4 hi, lo;
+            sp::split4(z, hi, lo);
+            *(lds_h4)(uintptr_t)(rec + 8 * gg * 2) = hi;
+            *(lds_h4)(uintptr_t)(rec + 8 * gg * 2 + 64) = lo;
+        }
+    }
+}
+
 // The passes of one leaf: -1 = against the base (use_delta), 0 .. 3 = the board's quadrants without one.  -> tiles computed: conv3 | conv2 << 16.
 // SETS (k_delta_res): pass -1 takes its cell sets, ranks and totals from leaf.sets (leaf_windows) instead of the distances and ballots.
 // OLO, OHI: the head planes this leaf is evaluated for (conv3_tiles; the base's values of the others are not requested either) -- all six,
@@ -430,7 +483,6 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
     const float k1 = ly.k1, k2 = ly.k2, k3 = ly.k3, act1 = ly.act1, act2 = ly.act2, act3 = ly.act3;
     const char *t2p = ly.t2p, *t3p = ly.t3p;
     const char *base = leaf.base;
-    const f16x4 cell_planes = leaf.cell_planes;
     const int (&dys)[kMaxD] = leaf.dys, (&dxs)[kMaxD] = leaf.dxs;
     _Float16 *dst16 = leaf.dst16;
     float *vdst = leaf.vdst, *dst32 = leaf.dst32;
@@ -486,56 +538,18 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         // registers they are stored from (no barrier lies between).  Every load is issued by every thread --
         // a load under a branch makes hipcc wait for every outstanding load first --; a thread that holds no such record reads
         // past the end of a buffer resource instead, which returns zeros without touching memory.
-        // SETS, pass -1: the same bytes record by record (rz_gather.h) -- the lanes of a wave-instruction read whole records, 8 (conv1) or
-        // 16 (conv2) lanes each, so a 128-byte line is touched once, and 4 + 11 requests a wave replace the 8 + 16.  Which record a lane
-        // group copies comes from the wave's own table: lane L writes the entries of its held cells L, 64 + L, 128 + L, 192 + L that
-        // fall to this wave, the wave reads the entries of its rounds back (its LDS operations complete in order: no barrier).
+        // SETS (k_delta_res): the same bytes record by record (rz_gather.h) -- the lanes of a wave-instruction read whole records, 8
+        // (conv1) or 16 (conv2) lanes each, so a 128-byte line is touched once.  The gather is the work of waves 1 .. 3 (the three-wave
+        // split, gathering wave gw = wave - 1: 6 + 14 requests a wave); wave 0 -- behind the selection's tail when the others are here,
+        // and conv1 of pass -1 is its work -- has no table and no gather in that pass.  Table, requests and stores stand in ONE uniform
+        // region further down, behind the maps and lists: with the requests up here and the stores down there, a branch around each
+        // spilled the requests' registers (profiles/TRIED.md, round 13); inside the region nothing is under a branch of its own.
         const bool g1 = pass < 0 && f[3] && !f[0], g2 = pass < 0 && f[4] && !f[1];
         const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, kBaseBytes, 0x00020000);
         f32x4 r1[8], r2[16];
-        f32x4 q1[rzg::kC1Rounds], q2[rzg::kC2Rounds];
-        uint32_t d1[rzg::kC1Rounds], d2[rzg::kC2Rounds];   // where a round's 16 bytes go (no record: the zeros it was answered, to the zero record)
-        if constexpr (SETS) {
-            // (no branch around requests or stores: the passes without a base -- handed false -- go through the same instructions
-            // with no record anywhere, as they went through the cell-by-cell requests)
-            uint16_t *tab = leaf.gtab;
-            // (all sixteen words first, in one batch of LDS reads; they stay in vector registers -- the same value in every lane --:
-            // nothing here needs them in scalar ones)
-            uint64_t ws[rzw::kRadii][rzg::kWords];
-#pragma unroll
-            for (int r = 0; r < rzw::kRadii; ++r)
-#pragma unroll
-                for (int w = 0; w < rzg::kWords; ++w) ws[r][w] = leaf.sets[4 * r + w];
-            int n1 = 0, s1 = 0, n2 = 0, s2 = 0;   // held records / slots in the words before this one (the same in every lane)
-#pragma unroll
-            for (int w = 0; w < rzg::kWords; ++w) {
-                const uint64_t h1 = rzg::held(ws[2][w], ws[0][w]), h2 = rzg::held(ws[3][w], ws[1][w]);
-                const int cell = 64 * w + lane;
-                const int p1 = rzg::c1_place(n1 + lane_below(h1), wave), p2 = rzg::c2_place(n2 + lane_below(h2), wave);
-                const uint16_t e1 = rzg::entry(cell, s1 + lane_below(ws[2][w])), e2 = rzg::entry(cell, s2 + lane_below(ws[3][w]));
-                if (handed && ((h1 >> lane) & 1ull) && p1 >= 0) tab[p1] = e1;
-                if (handed && ((h2 >> lane) & 1ull) && p2 >= 0) tab[p2] = e2;
-                n1 += rzg::popcount(h1), s1 += rzg::popcount(ws[2][w]);
-                n2 += rzg::popcount(h2), s2 += rzg::popcount(ws[3][w]);
-            }
-            const uint32_t c1a = lds_addr(c1), c2a = lds_addr(c2);
-#pragma unroll
-            for (int i = 0; i < rzg::kC1Rounds; ++i) {
-                const int j = rzg::c1_record(i, wave, lane), chunk = rzg::c1_chunk(lane);
-                const uint16_t e = tab[rzg::c1_index(j)];
-                const bool has = handed && rzg::c1_has(j, n1);
-                d1[i] = has ? c1a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P1) : zaddr + 16u * (uint32_t)chunk;
-                q1[i] = load_rec(b_rsrc, rzg::c1_src(has, rzg::entry_cell(e), chunk));
-            }
-#pragma unroll
-            for (int i = 0; i < rzg::kC2Rounds; ++i) {
-                const int j = rzg::c2_record(i, wave, lane), chunk = rzg::c2_chunk(lane);
-                const uint16_t e = tab[rzg::c2_index(j)];
-                const bool has = handed && rzg::c2_has(j, n2);
-                d2[i] = has ? c2a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P2) : zaddr + 16u * (uint32_t)chunk;
-                q2[i] = load_rec(b_rsrc, rzg::c2_src(has, rzg::entry_cell(e), chunk, (int)kBaseC2));
-            }
-        } else {
+        typedef rzg::Split<SETS ? 3 : 4> GS;
+        constexpr int NW = SETS ? 3 : 4;
+        if constexpr (!SETS) {
             const int o1 = g1 ? tid * 128 : kOutside, o2 = g2 ? (int)kBaseC2 + tid * 256 : kOutside;
 #pragma unroll
             for (int i = 0; i < 8; ++i) r1[i] = load_rec(b_rsrc, o1 + 16 * i);
@@ -549,13 +563,13 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
             for (int o = OLO; o < OHI; ++o) bv[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ov + o * kCells * 4, 0, 0));
         }
         // (conv1's weights and the biases: requested per pass, so that nothing of them is live across conv3)
-        // (SETS, pass -1: a wave without a conv1 tile -- the total is handed over -- requests them past the end of their buffers)
+        // (SETS, pass -1: conv1 is wave 0's, every tile of it; the other waves request them past the end of their buffers)
         sp::f16x8 a1[3][2];
         f32x4 bias1[4];
         if constexpr (SETS) {
             const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4 *>(nd.s1), 0, 6 * 64 * 16, 0x00020000);
             const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(nd.b1), 0, 32 * 4, 0x00020000);
-            const bool runs = !handed || 32 * wave < tot[0];   // (uniform)
+            const bool runs = !handed || wave == 0;   // (uniform)
             const int so = runs ? lane * 16 : kOutside, bo = runs ? 16 * (lane >> 5) : kOutside;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky)
@@ -615,13 +629,85 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
         if (f[0]) list1[rank[0]] = (uint16_t)mypos;
         if (f[1]) list2[rank[1]] = (uint16_t)mypos;
         if (f[2]) list3[rank[2]] = (uint16_t)mypos;
-        if (pass <= 0 && is_cell) *reinterpret_cast<f16x4 *>(in0 + ((cy + 1) * sp::kInCols + (cx + 1)) * 8) = cell_planes;
+        if constexpr (SETS) {
+            // (k_delta_res: the leaf is in LDS, and nobody has read it yet; pass -1: wave 0 writes the planes of every cell, below)
+            if (!handed && pass <= 0) {
+                uint64_t ls[8];
+                int tm, lc, nst;
+                leaf_from_lds(leaf.leaf_lds, ls, tm, lc, nst);
+                const f16x4 planes = planes_of(ls, tid, tm, nst > 0, lc, nst);
+                if (is_cell) *reinterpret_cast<f16x4 *>(in0 + ((cy + 1) * sp::kInCols + (cx + 1)) * 8) = planes;
+            }
+        } else {
+            if (pass <= 0 && is_cell) *reinterpret_cast<f16x4 *>(in0 + ((cy + 1) * sp::kInCols + (cx + 1)) * 8) = leaf.cell_planes;
+        }
         if (pass <= 0 && store_head && tid < 226) reinterpret_cast<f32x4 *>(headw)[tid] = headv;
         if constexpr (SETS) {
+          // ---- the gather (see above): which record a lane group copies comes from the wave's own table -- lane L writes the entries
+          // of its held cells L, 64 + L, 128 + L, 192 + L that fall to this wave, the wave reads the entries of its rounds back (its
+          // LDS operations complete in order: no barrier) --, then all requests, then all stores: no other work stands
+          // between a request and its store any more, these waves wait the latency out (profiles/r13/delta_resident_phases.txt).
+          if (!(handed && wave == 0)) {   // (uniform; wave 0 of the handed pass: no table, no gather)
+            // (no branch around single requests or stores: the passes without a base -- handed false -- go through the same
+            // instructions with no record anywhere, as they went through the cell-by-cell requests)
+            f32x4 q1[GS::kC1Rounds], q2[GS::kC2Rounds];
+            uint32_t d1[GS::kC1Rounds], d2[GS::kC2Rounds];   // where a round's 16 bytes go (no record: the zeros it was answered, to the zero record)
+            uint16_t *tab = leaf.gtab;
+            const int gw = wave - 1, gwi = gw < 0 ? 0 : gw;   // (wave 0: no place is its own, and the entries it reads back are nobody's)
+            const bool gathers = handed && gw >= 0;           // (uniform)
+            // held records / slots in the words before word w, and in all: the popcounts the hand-over stored behind the sets, scalar
+            // (W1 <= W3 and W2 <= W4, so a held set's count is a difference)
+            const int *wcnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
+            int pn1[rzg::kWords + 1], ps1[rzg::kWords + 1], pn2[rzg::kWords + 1], ps2[rzg::kWords + 1];
+            pn1[0] = ps1[0] = pn2[0] = ps2[0] = 0;
 #pragma unroll
-            for (int i = 0; i < rzg::kC1Rounds; ++i) *(lds_v4)(uintptr_t)d1[i] = q1[i];
+            for (int w = 0; w < rzg::kWords; ++w) {
+                const int k0 = __builtin_amdgcn_readfirstlane(wcnt[4 * 0 + w]), k1_ = __builtin_amdgcn_readfirstlane(wcnt[4 * 1 + w]);
+                const int k2_ = __builtin_amdgcn_readfirstlane(wcnt[4 * 2 + w]), k3_ = __builtin_amdgcn_readfirstlane(wcnt[4 * 3 + w]);
+                pn1[w + 1] = pn1[w] + k2_ - k0, ps1[w + 1] = ps1[w] + k2_;
+                pn2[w + 1] = pn2[w] + k3_ - k1_, ps2[w + 1] = ps2[w] + k3_;
+            }
+            const int n1 = pn1[rzg::kWords], n2 = pn2[rzg::kWords];
+            if (gathers) {
+                // (all sixteen words first, in one batch of LDS reads; they stay in vector registers -- the same value in every lane --:
+                // nothing here needs them in scalar ones)
+                uint64_t ws[rzw::kRadii][rzg::kWords];
 #pragma unroll
-            for (int i = 0; i < rzg::kC2Rounds; ++i) *(lds_v4)(uintptr_t)d2[i] = q2[i];
+                for (int r = 0; r < rzw::kRadii; ++r)
+#pragma unroll
+                    for (int w = 0; w < rzg::kWords; ++w) ws[r][w] = leaf.sets[4 * r + w];
+#pragma unroll
+                for (int w = 0; w < rzg::kWords; ++w) {
+                    const uint64_t h1 = rzg::held(ws[2][w], ws[0][w]), h2 = rzg::held(ws[3][w], ws[1][w]);
+                    const int cell = 64 * w + lane;
+                    const int p1 = rzg::c1_place<NW>(pn1[w] + lane_below(h1), gw), p2 = rzg::c2_place<NW>(pn2[w] + lane_below(h2), gw);
+                    const uint16_t e1 = rzg::entry(cell, ps1[w] + lane_below(ws[2][w])), e2 = rzg::entry(cell, ps2[w] + lane_below(ws[3][w]));
+                    if (((h1 >> lane) & 1ull) && p1 >= 0) tab[p1] = e1;
+                    if (((h2 >> lane) & 1ull) && p2 >= 0) tab[p2] = e2;
+                }
+            }
+            const uint32_t c1a = lds_addr(c1), c2a = lds_addr(c2);
+#pragma unroll
+            for (int i = 0; i < GS::kC1Rounds; ++i) {
+                const int j = rzg::c1_record<NW>(i, gwi, lane), chunk = rzg::c1_chunk(lane);
+                const uint16_t e = tab[rzg::c1_index<NW>(j)];
+                const bool has = gathers && rzg::c1_has(j, n1);
+                d1[i] = has ? c1a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P1) : zaddr + 16u * (uint32_t)chunk;
+                q1[i] = load_rec(b_rsrc, rzg::c1_src(has, rzg::entry_cell(e), chunk));
+            }
+#pragma unroll
+            for (int i = 0; i < GS::kC2Rounds; ++i) {
+                const int j = rzg::c2_record<NW>(i, gwi, lane), chunk = rzg::c2_chunk(lane);
+                const uint16_t e = tab[rzg::c2_index<NW>(j)];
+                const bool has = gathers && rzg::c2_has(j, n2);
+                d2[i] = has ? c2a + (uint32_t)rzg::dst(rzg::entry_slot(e), chunk, P2) : zaddr + 16u * (uint32_t)chunk;
+                q2[i] = load_rec(b_rsrc, rzg::c2_src(has, rzg::entry_cell(e), chunk, (int)kBaseC2));
+            }
+#pragma unroll
+            for (int i = 0; i < GS::kC1Rounds; ++i) *(lds_v4)(uintptr_t)d1[i] = q1[i];
+#pragma unroll
+            for (int i = 0; i < GS::kC2Rounds; ++i) *(lds_v4)(uintptr_t)d2[i] = q2[i];
+          }
         } else {
             if (g1) {
 #pragma unroll
@@ -641,49 +727,47 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
 #pragma unroll
                 for (int p = 0; p < 2; ++p) a2[tap][0][p] = sp::load_w(w_rsrc, lane * 16, (tap * 2 + p) * 1024);
         }
-        NET_TICK(3);   // maps, lists, planes, the base's records (their arrival)
-        __syncthreads();
-        NET_TICK(4);
-
-        // ---- conv1 (4 -> 32): tile w of 32 cells by wave w (trunk_rows_body's conv1 with the lane's cell taken from the list)
-        if (32 * wave < tot[0]) {
-            const int n32 = lane & 31, h = lane >> 5, idx = 32 * wave + n32;
-            const int pos = list1[idx];
-            const int py = (pos * 3641) >> 16, px = pos - py * kRowW;   // halo row / column (board row py - 1, column px - 1)
-            typedef const __attribute__((address_space(3))) f16x4 *lds_half;
-            const lds_half q = (lds_half)(in0 + ((py - 1) * sp::kInCols + (px - 1) + 2 * h) * 8);
-            sp::f16x8 b1[3];
+        if (handed) {
+            // ---- pass -1 of the resident search: conv1 reads the planes alone, so it does not wait for the gather -- wave 0, which comes
+            // here last (the selection's tail), does ALL of it in front of the pass's one barrier before conv2: the planes of every cell
+            // (lane L: cells L, 64 + L, 128 + L, 192 + L), the list and map entries of W1's cells in every word (the owners write the
+            // same values; this wave's LDS operations complete in order, so it reads its own back), then every tile of conv1.
+            if (wave == 0) {
+                uint64_t ls[8];
+                int tm, lc, nst;
+                leaf_from_lds(leaf.leaf_lds, ls, tm, lc, nst);
+                const int *cnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
+                int b0 = 0, b3 = 0;   // W1's / W3's cells in the words before this one
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int o = ky * sp::kInCols;
-                const f16x4 lo4 = q[o], hi4 = q[o + 1];
-                b1[ky] = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
-            sp::f32x16 acc1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[r] = 0.0f;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int combo = 0; combo < 3; combo += 2)   // (the lo pieces of 0 / 1 planes are zero: no hi x lo product)
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[ky][combo == 2], b1[ky], acc1, 0, 0, 0);
-            if (idx < tot[0]) {
-                const uint32_t rec = map1[pos] + (uint32_t)(4 * h * 2);
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    float z[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) z[j] = fmaxf(fmaf(acc1[4 * gg + j], k1, bias1[gg][j] * act1), 0.0f);
-                    f16x4 hi, lo;
-                    sp::split4(z, hi, lo);
-                    *(lds_h4)(uintptr_t)(rec + 8 * gg * 2) = hi;
-                    *(lds_h4)(uintptr_t)(rec + 8 * gg * 2 + 64) = lo;
+                for (int w = 0; w < 4; ++w) {
+                    const int cell = 64 * w + lane, y = (cell * da.bw_rcp) >> 16, x = cell - y * BW;
+                    const f16x4 planes = planes_of(ls, cell, tm, nst > 0, lc, nst);
+                    if (cell < S) *reinterpret_cast<f16x4 *>(in0 + ((y + 1) * sp::kInCols + (x + 1)) * 8) = planes;
+                    const uint64_t w1 = uni64(leaf.sets[4 * 0 + w]), w3 = uni64(leaf.sets[4 * 2 + w]);
+                    const int pos = (y + 1) * kRowW + x + 1;
+                    if ((w1 >> lane) & 1ull) {
+                        list1[b0 + lane_below(w1)] = (uint16_t)pos;
+                        map1[pos] = lds_addr(c1 + (b3 + lane_below(w3)) * P1);
+                    }
+                    b0 += __builtin_amdgcn_readfirstlane(cnt[4 * 0 + w]);
+                    b3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]);
                 }
+#pragma unroll 1
+                for (int tile = 0; 32 * tile < tot[0]; ++tile) conv1_tile(tile, tot[0], lane, in0, list1, map1, a1, bias1, k1, act1);
             }
+            NET_TICK(3);   // maps, lists, the base's records (their arrival); wave 0: the planes, conv1
+            __syncthreads();
+            NET_TICK(4);
+        } else {
+            NET_TICK(3);   // maps, lists, planes, the base's records (their arrival)
+            __syncthreads();
+            NET_TICK(4);
+            // ---- conv1 (4 -> 32): tile w of 32 cells by wave w
+            if (32 * wave < tot[0]) conv1_tile(wave, tot[0], lane, in0, list1, map1, a1, bias1, k1, act1);
+            NET_TICK(5);   // conv1
+            __syncthreads();
+            NET_TICK(6);
         }
-        NET_TICK(5);   // conv1
-        __syncthreads();
-        NET_TICK(6);
         if (mode == 1 && f[0]) {   // the base keeps conv1's records
             f32x4 *dstp = reinterpret_cast<f32x4 *>(const_cast<char *>(base) + (size_t)tid * 128);
 #pragma unroll
@@ -912,7 +996,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (mode != 1 && !deferred && feat16 != nullptr)   // rz_net_delta_trunk_engine: the FC GEMM's own tiles (policy and value K-steps), as trunk_rows_body writes them
         leaf.dst16 = feat16 + ((size_t)(board >> 5) * (nd.groups_act + nd.groups_val) * 1024 + (board & 31) * 16);
     leaf.dst32 = (mode != 1 && da.feat32 != nullptr) ? da.feat32 + (size_t)board * 6 * S : nullptr;
-    leaf.sets = nullptr, leaf.gtab = nullptr;
+    leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr;
     leaf.deferred = deferred;
     leaf.store_head = true;
 
@@ -1028,6 +1112,37 @@ struct ResHook {
         const uint64_t v = win[c * kWinSets + (lane & (kWinSets - 1))];
         row = (lane >> 4) == level ? v : row;
     }
+    // Behind the descent (select_body calls it once, whichever way the descent ended): the leaf to LDS, the hand-over of its windows --
+    // the rows were requested during the descent, and the verdict is changed_cells' without the leaf: against a base that is the root
+    // (base_ok) the changed cells are the path's cells -- the last move is one of them -- or, at depth 0, the root's last move (none on an
+    // empty board); parity = depth & 1; more than kMaxD cells or no base: no delta -- and, inside the simulation loop (release), the
+    // barrier waves 1 - 3 wait at: they start the next leaf's prologue while this wave finishes the selection (the stash, the terminal
+    // test, the leaf's stores to global memory: nothing of it is read before expand_backup_body, one trunk later, by this wave).
+    // (release: only for a game whose `active` flag the kernel has tested -- select_body returns in front of this call for an inactive
+    // game, and the other waves would wait at the barrier for ever; k_delta_res returns on such a game before its first barrier)
+    uint64_t *leaf_lds, *ws;
+    bool base_ok, release;
+    __device__ __forceinline__ void leaf(const uint64_t (&st)[2][rzt::kWords], int to_move, int last, int d, int lane) {
+        depth = d;
+        rzt::store_board<rzt::kWords>(leaf_lds, 0, st, lane);
+        if (lane == 0) {
+            reinterpret_cast<int *>(leaf_lds + 2 * rzt::kWords)[0] = to_move;
+            reinterpret_cast<int *>(leaf_lds + 2 * rzt::kWords)[1] = last;
+        }
+        const bool mine = d == 0 ? (lane < 16 && any0) : (lane >> 4) < d;
+        const int nD = d == 0 ? (any0 ? 1 : 0) : d;
+        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws);
+        if (release) __syncthreads();
+#ifdef RZ_NET_PROFILE
+        {   // -> net_prof[18]: the selection up to the release
+            __builtin_amdgcn_sched_barrier(0);
+            const long long now = __builtin_readcyclecounter();
+            prof->acc[18] += now - prof->t;
+            prof->t = now;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
+    }
 #ifdef RZ_NET_PROFILE
     Prof *prof;
     __device__ __forceinline__ void tick(int i, int arrived) {   // -> net_prof[2, 8, 13, 14, 15]
@@ -1046,17 +1161,6 @@ struct ResHook {
 #endif
 };
 
-// The same hand-over behind a selection made HERE: the rows were requested during the descent (ResHook), and the verdict is
-// changed_cells' without the leaf: against a base that is the root (base_ok) the changed cells are the path's cells -- the last move is
-// one of them -- or, at depth 0, the root's last move (none on an empty board); parity = depth & 1; more than kMaxD cells or no base:
-// no delta.
-__device__ __forceinline__ void path_windows(const ResHook &hook, bool base_ok, int lane, uint64_t *ws) {
-    const int depth = hook.depth;
-    const bool mine = depth == 0 ? (lane < 16 && hook.any0) : (lane >> 4) < depth;
-    const int nD = depth == 0 ? (hook.any0 ? 1 : 0) : depth;
-    windows_store(mine ? hook.row : 0ull, base_ok && nD <= kMaxD, depth & 1, nD, lane, ws);
-}
-
 // RESIDENT SEARCH with receptive-field evaluation (rz_net_search_resident on boards of 11 .. 16 rows and columns once the base cache
 // exists): k_trunk_rows_res's loop -- leaf -> trunk -> value head -> expand / backup -> next selection, n_sims times in ONE launch, one
 // workgroup per game, the leaf handed over through LDS, the tree code the engine's own (rz_tree.h) -- with the delta passes as the
@@ -1073,7 +1177,8 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     __shared__ float res_vrow[kResVrow];
     __shared__ float res_part[rzt::kDefWaves][rzt::kWave];
-    static_assert(rzg::kTabEntries * 2 <= rzt::kWave * 4, "a wave's gather table lies in its row of the K-quarter sums");
+    static_assert(rzg::Split<3>::kTabEntries == 14 * 4 + 6 * 8 && rzg::Split<3>::kTabEntries <= 128 && rzg::Split<3>::kTabEntries * 2 <= rzt::kWave * 4,
+                  "a gathering wave's table (104 entries) lies in its 128-entry row of the K-quarter sums");
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
@@ -1128,6 +1233,10 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     hook.depth = 0;
     hook.any0 = false;
     hook.row = 0ull;
+    hook.leaf_lds = res_leaf;
+    hook.ws = res_win;
+    hook.base_ok = base_ok;
+    hook.release = false;   // (the first selection: every wave meets the barrier behind it)
 #ifdef RZ_NET_PROFILE
     hook.prof = &prof;
     long long pre_cycles = 0, pre_wait = 0;   // wave 1: the pre-scan, the barrier behind it (= its slack under expand + backup)
@@ -1144,8 +1253,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         // rz_select_step; either way the hand-over of the first leaf's windows
         const int lane0 = tid0 & 63;
         if (res.select_first != 0) {
-            rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane0, 0, res_leaf, &hook);
-            path_windows(hook, base_ok, lane0, res_win);
+            rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane0, 0, res_leaf, &hook);   // (the hand-over: hook.leaf)
         } else {
             leaf_windows(res_leaf, rs, base_ok, h_tm, da, BW, lane0, res_win);
         }
@@ -1157,19 +1265,10 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         // loop and spills them)
         int tid_s = tid0;
         asm volatile("" : "+v"(tid_s));
-        // ---- the leaf, from LDS (select_body's lds_leaf): wave-uniform values; the verdict and the window sets of pass -1 from the
-        // selection's hand-over (leaf_windows)
-        uint64_t ls[8];
-        int nst = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint64_t v = res_leaf[q];
-            ls[q] = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-            nst += __popcll(ls[q]);
-        }
-        const int tm = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_leaf + 2 * RZ_BOARD_WORDS)[0]);
-        const int lc = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_leaf + 2 * RZ_BOARD_WORDS)[1]);
-        const bool has_last = nst > 0;
+        // ---- the verdict and the window sets of pass -1 from the selection's hand-over (ResHook::leaf, leaf_windows).  The leaf itself
+        // (LDS: res_leaf) is read where its planes are formed: by wave 0 in pass -1, by every thread in the passes without a base.
+        // Waves 1 .. 3 are here as soon as the leaf's cell is chosen -- wave 0 follows behind the selection's tail and meets them at the
+        // barrier before conv2.
         const int verdict = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_win + kWinSets)[kWinSets]);
         bool use_delta = (verdict & 1) != 0;
         const int parity = (verdict >> 1) & 1, nD = verdict >> 8;
@@ -1179,7 +1278,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
 #pragma unroll
         for (int i = 0; i < kMaxD; ++i) leaf.dys[i] = leaf.dxs[i] = -100;   // (pass -1 reads the sets; the passes without a base, no cells)
         leaf.base = da.recs + ((size_t)game * 2 + parity) * kBaseBytes;
-        leaf.cell_planes = planes_of(ls, tid_s, tm, has_last, lc, nst);
+        leaf.leaf_lds = res_leaf;
         // the game's slot advances by one per simulation (expand_backup_body<DEF>); the value inputs stay in LDS
         leaf.dst16 = POL && slot0 + sim < later.n_slots ? store16 + (size_t)(slot0 + sim) * later.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16 : nullptr;
         leaf.vdst = res_vrow;
@@ -1224,18 +1323,27 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         if (RZ_DELTA_PRESCAN && wave == 1 && more) pre_wait += __builtin_readcyclecounter();
 #endif
         NET_TICK(17);
-        if (wave == 0 && more) {
-            hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
-            // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
-            // and kept -- spilled -- across the trunk)
-            int lane_t = lane;
-            asm volatile("" : "+v"(lane_t));
-            rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, 0, res_leaf, &hook);
-            path_windows(hook, base_ok, lane_t, res_win);
+        // The next selection.  Its hook meets the RELEASE barrier the moment the leaf's cell is chosen, the leaf and its window sets in LDS
+        // (ResHook::leaf); waves 1 .. 3 wait for nothing else and go on to the next leaf's prologue, wave 0 finishes the selection
+        // beside them.  (res_leaf / res_win: written before the release, rewritten by the next selection, at least three barriers on;
+        // res_pre: the tail's stash is read by wave 1 behind the barrier inside expand_backup_body; the gather tables: rows 1 .. 3 of
+        // res_part, which the tail does not touch.)  The last simulation: no selection, no barrier, for anyone.
+        if (more) {
+            if (wave == 0) {
+                hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
+                hook.release = true;
+                // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
+                // and kept -- spilled -- across the trunk)
+                int lane_t = lane;
+                asm volatile("" : "+v"(lane_t));
+                rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, 0, res_leaf, &hook);
+                NET_TICK(15);   // wave 0: the selection's tail, behind the release
+            } else {
+                __syncthreads();   // the release
+                NET_TICK(18);
+            }
         }
         if (RZ_DELTA_TREE_PRIO) __builtin_amdgcn_s_setprio(0);
-        __syncthreads();
-        NET_TICK(18);
     }
     if (da.stats != nullptr && tid0 == 0) {
         atomicAdd(da.stats + 0, (unsigned)deltas);
@@ -1252,13 +1360,14 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
 #ifdef RZ_NET_PROFILE
     if (blockIdx.x == 0 && tid0 == 0) {
         for (int i = 0; i < 24; ++i)
-            if (i != 19 && i != 20) net_prof[i] = prof_acc[i];
+            if (i != 19 && i != 20 && i != 21) net_prof[i] = prof_acc[i];
         net_prof[23] = __builtin_readcyclecounter() - prof_k0;
         net_prof[22] = tiles_total;
     }
     if (blockIdx.x == 0 && tid0 == 64) {   // wave 1's first lane: the pre-scan and the wait behind it
         net_prof[19] = pre_cycles;
         net_prof[20] = pre_wait;
+        net_prof[21] = prof_acc[0] + prof_acc[1] + prof_acc[3];   // ... from the release to the barrier before conv2 (its arrival there)
     }
 #endif
 }
@@ -1337,7 +1446,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_policy_rows(NetDev nd, _Float1
         leaf.dst16 = store16 + (size_t)slot * pr.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16;
         leaf.vdst = nullptr;
         leaf.dst32 = nullptr;
-        leaf.sets = nullptr, leaf.gtab = nullptr;
+        leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr;
         leaf.deferred = false;
         leaf.store_head = first;
         first = false;

@@ -16,6 +16,9 @@
 // 192 + L; for each one that is held it knows j (the bits below it in H, plus the words before) and the slot (the same from W), and if
 // the record falls to its wave it writes the 16-bit entry cell | slot << 8 at the record's place in the wave's table.  The wave then
 // reads the entries of its rounds back (one wave's LDS operations complete in order).  76 entries a wave: 11 x 4 conv2, 4 x 8 conv1.
+//
+// Three waves (Split<3>, the functions' <3> forms; k_delta_res' handed pass): the same split over gathering waves 0 .. 2 -- a round is
+// 12 conv2 / 24 conv1 records, 14 / 6 rounds cover the budget, a wave's table has 14 x 4 + 6 x 8 = 104 entries.
 #pragma once
 #include <stdint.h>
 
@@ -32,11 +35,23 @@ constexpr int kC1Max = 128, kC2Max = 164;          // records of conv1's / conv2
 constexpr int kC1Bytes = 128, kC2Bytes = 256;      // a record in the base
 constexpr int kC1Lanes = kC1Bytes / 16, kC2Lanes = kC2Bytes / 16;              // lanes that move one record
 constexpr int kC1PerWave = 64 / kC1Lanes, kC2PerWave = 64 / kC2Lanes;          // records of one wave-instruction: 8 / 4
-constexpr int kC1PerRound = 4 * kC1PerWave, kC2PerRound = 4 * kC2PerWave;      // ... of a round of the four waves: 32 / 16
-constexpr int kC1Rounds = (kC1Max + kC1PerRound - 1) / kC1PerRound;            // 4
-constexpr int kC2Rounds = (kC2Max + kC2PerRound - 1) / kC2PerRound;            // 11
-constexpr int kTabC2 = 0, kTabC1 = kC2Rounds * kC2PerWave;                     // a wave's table: its conv2 entries, then its conv1 entries
-constexpr int kTabEntries = kTabC1 + kC1Rounds * kC1PerWave;                   // 76 (152 bytes)
+// the split over NW gathering waves (NW = 4: every wave of the workgroup, the names without a parameter below; NW = 3: waves 1 .. 3 of
+// the resident search's handed pass, numbered 0 .. 2 here, while wave 0 finishes the selection and runs conv1)
+template <int NW>
+struct Split {
+    static constexpr int kC1PerRound = NW * kC1PerWave, kC2PerRound = NW * kC2PerWave;          // records of a round of the NW waves
+    static constexpr int kC1Rounds = (kC1Max + kC1PerRound - 1) / kC1PerRound;                  // 4 waves: 4, 3 waves: 6
+    static constexpr int kC2Rounds = (kC2Max + kC2PerRound - 1) / kC2PerRound;                  // 4 waves: 11, 3 waves: 14
+    static constexpr int kTabC2 = 0, kTabC1 = kC2Rounds * kC2PerWave;                           // a wave's table: its conv2 entries, then its conv1 entries
+    static constexpr int kTabEntries = kTabC1 + kC1Rounds * kC1PerWave;                         // 4 waves: 76, 3 waves: 104
+};
+constexpr int kC1PerRound = Split<4>::kC1PerRound, kC2PerRound = Split<4>::kC2PerRound;      // ... of a round of the four waves: 32 / 16
+constexpr int kC1Rounds = Split<4>::kC1Rounds;                                  // 4
+constexpr int kC2Rounds = Split<4>::kC2Rounds;                                  // 11
+constexpr int kTabC2 = Split<4>::kTabC2, kTabC1 = Split<4>::kTabC1;            // a wave's table: its conv2 entries, then its conv1 entries
+constexpr int kTabEntries = Split<4>::kTabEntries;                              // 76 (152 bytes)
+static_assert(kC1Rounds == 4 && kC2Rounds == 11 && kTabEntries == 76, "the four-wave split");
+static_assert(Split<3>::kC1Rounds == 6 && Split<3>::kC2Rounds == 14 && Split<3>::kTabEntries == 104, "the three-wave split: 164 / 12 and 128 / 24 rounds");
 constexpr int kOutside = 1 << 30;                  // an offset past every buffer's end
 
 RZG_FN int popcount(uint64_t w) { return __builtin_popcountll(w); }
@@ -68,26 +83,26 @@ RZG_FN int cell_of(const uint64_t (&m)[kWords], int j) {
 }
 
 // ---- (round, wave, lane) -> (record, chunk)
-RZG_FN int c2_record(int round, int wave, int lane) { return kC2PerRound * round + kC2PerWave * wave + (int)((unsigned)lane / kC2Lanes); }
+template <int NW = 4> RZG_FN int c2_record(int round, int wave, int lane) { return Split<NW>::kC2PerRound * round + kC2PerWave * wave + (int)((unsigned)lane / kC2Lanes); }
 RZG_FN int c2_chunk(int lane) { return (int)((unsigned)lane % kC2Lanes); }
-RZG_FN int c1_record(int round, int wave, int lane) { return kC1PerRound * round + kC1PerWave * wave + (int)((unsigned)lane / kC1Lanes); }
+template <int NW = 4> RZG_FN int c1_record(int round, int wave, int lane) { return Split<NW>::kC1PerRound * round + kC1PerWave * wave + (int)((unsigned)lane / kC1Lanes); }
 RZG_FN int c1_chunk(int lane) { return (int)((unsigned)lane % kC1Lanes); }
 // rounds that hold a record, of a set of n
-RZG_FN int c2_rounds(int n) { return (n + kC2PerRound - 1) / kC2PerRound; }
-RZG_FN int c1_rounds(int n) { return (n + kC1PerRound - 1) / kC1PerRound; }
+template <int NW = 4> RZG_FN int c2_rounds(int n) { return (n + Split<NW>::kC2PerRound - 1) / Split<NW>::kC2PerRound; }
+template <int NW = 4> RZG_FN int c1_rounds(int n) { return (n + Split<NW>::kC1PerRound - 1) / Split<NW>::kC1PerRound; }
 
 // ---- the waves' tables: the wave a record falls to, its place there (c?_index(c?_record(i, wave, lane)) = first + per-wave i + lane group)
-RZG_FN int c2_wave(int j) { return (int)(((unsigned)j / kC2PerWave) % 4u); }
-RZG_FN int c2_index(int j) { return kTabC2 + (int)(((unsigned)j / kC2PerRound) * kC2PerWave + (unsigned)j % kC2PerWave); }
-RZG_FN int c1_wave(int j) { return (int)(((unsigned)j / kC1PerWave) % 4u); }
-RZG_FN int c1_index(int j) { return kTabC1 + (int)(((unsigned)j / kC1PerRound) * kC1PerWave + (unsigned)j % kC1PerWave); }
+template <int NW = 4> RZG_FN int c2_wave(int j) { return (int)(((unsigned)j / kC2PerWave) % (unsigned)NW); }
+template <int NW = 4> RZG_FN int c2_index(int j) { return Split<NW>::kTabC2 + (int)(((unsigned)j / Split<NW>::kC2PerRound) * kC2PerWave + (unsigned)j % kC2PerWave); }
+template <int NW = 4> RZG_FN int c1_wave(int j) { return (int)(((unsigned)j / kC1PerWave) % (unsigned)NW); }
+template <int NW = 4> RZG_FN int c1_index(int j) { return Split<NW>::kTabC1 + (int)(((unsigned)j / Split<NW>::kC1PerRound) * kC1PerWave + (unsigned)j % kC1PerWave); }
 RZG_FN uint16_t entry(int cell, int slot) { return (uint16_t)(cell | slot << 8); }
 RZG_FN int entry_cell(uint16_t e) { return e & 255; }
 RZG_FN int entry_slot(uint16_t e) { return e >> 8; }
 // the table place the owner of a held cell writes (-1: none -- the record falls to another wave or lies past the budget, whose
 // leaves take the passes without a base).  j: the cell's record number.
-RZG_FN int c2_place(int j, int wave) { return j < kC2Max && c2_wave(j) == wave ? c2_index(j) : -1; }
-RZG_FN int c1_place(int j, int wave) { return j < kC1Max && c1_wave(j) == wave ? c1_index(j) : -1; }
+template <int NW = 4> RZG_FN int c2_place(int j, int wave) { return j < kC2Max && c2_wave<NW>(j) == wave ? c2_index<NW>(j) : -1; }
+template <int NW = 4> RZG_FN int c1_place(int j, int wave) { return j < kC1Max && c1_wave<NW>(j) == wave ? c1_index<NW>(j) : -1; }
 
 // ---- the 16 bytes a lane moves: from this offset of the base (conv1 records at 0, conv2 records at `base_c2`) ...
 RZG_FN int c2_src(bool has, int cell, int chunk, int base_c2) { return has ? base_c2 + cell * kC2Bytes + 16 * chunk : kOutside; }

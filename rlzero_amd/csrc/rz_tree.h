@@ -626,7 +626,13 @@ __device__ __forceinline__ void root_prescan(const Dev &E, int g, int lane, Root
 // could hit the scalar cache's copy of the previous simulation's leaf).
 // `hook` (Hook::kOn; k_delta_res): hook->pre is the root pre-scan's hand-over (RootPre above; its `answered` counts the root scans it
 // answered); hook->root_cell(last, stones, lane) and hook->cell(level, cell, lane) report the root's last move and each level's cell the moment
-// it is chosen, hook->depth the leaf's depth (the caller requests what it needs per cell during the descent instead of behind it);
+// it is chosen (the caller requests what it needs per cell during the descent instead of behind it); hook->leaf(stones, side to move,
+// last cell, depth, lane) is called once directly behind the descent, whichever way it ended -- before the stash, the terminal test and
+// the leaf's stores to global memory: the hook puts the leaf into LDS itself (`lds_leaf` is not written a second time) and may meet a
+// barrier there that releases the workgroup's other waves, so everything below it runs beside them.  PRECONDITION of a hook that
+// meets a barrier: the caller has tested E.active[g] itself and calls select_body only for an active game (k_delta_res returns on an
+// inactive one before its first barrier) -- the early return on `!act` below lies in front of the hook, and nothing inside a launch
+// clears the flag (flag() sets error bits only);
 // hook->tick(i, v) is a phase tick of the profile build behind the arrival of v.  NoHook: none of it.
 template <bool VL, int W = kWords, class Hook = NoHook>
 __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr,
@@ -809,9 +815,11 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         lo = clo;
         hi = chi;
     }
+    // (every exit of the DESCENT comes through here once: the hook may meet a barrier.  The return on `!act` above does not: a
+    // caller whose hook meets one selects for active games only, see the hook's contract)
+    if constexpr (Hook::kOn) hook->leaf(st, to_move, last, depth, lane);
     if constexpr (Hook::kOn) {
         hook->tick(3, node);
-        hook->depth = depth;
         if (lane == 0) {
             RootPre *pre = hook->pre;
             pre->lo = st_lo;
@@ -858,7 +866,7 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         E.leaf_last[gk] = last;
     }
     store_board<W>(E.leaf_stones, gk, st, lane);
-    if (lds_leaf != nullptr) {
+    if (!Hook::kOn && lds_leaf != nullptr) {   // (Hook: the leaf went to LDS behind the descent, hook->leaf)
         store_board<W>(lds_leaf, 0, st, lane);
         if (lane == 0) {
             reinterpret_cast<int *>(lds_leaf + 2 * kWords)[0] = to_move;
