@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 36
+#define RZ_ABI_VERSION 37
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -1003,6 +1003,40 @@ int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_
                            int32_t *d_where, float *d_obs, int64_t *ticket, void *stream);
 int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, const int32_t *d_root_n,
                         const double *d_root_sum, int64_t ticket, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * MuZero prioritized replay (ABI 37; rz_mz_replay.hip: k_mzr_prio, k_mzr_scan, k_mzr_draw_prio; rz_mz_target.h;
+ * rlzero_amd/muzero/replay.py): arXiv:1911.08265v2 appendix G with alpha = 1.  Stored step t is drawn with probability
+ * w_t / total, where w_t = priority_weight(|root_value[t] - value_target(t)|) is a FIXED-POINT integer: p * 2^16 truncated, at
+ * least 1, 2^32 from p = 2^16 on, 1 for a NaN.  Integer sums are exact in any order, so the prefix sums a parallel scan forms
+ * on the device are the bits of a host loop (replay.py: mz_priority_weights, mz_prioritized_draws).  Opt-in: until
+ * rz_mz_replay_enable_priorities nothing of this is allocated or launched, and no function or kernel above changes.
+ *
+ * rz_mz_replay_enable_priorities: allocates cum uint64 [E][T] (the inclusive prefix of w inside each slot), mass uint64 [E],
+ *   ecum uint64 [E] (the inclusive prefix of the masses over the episodes held, oldest first), the total and a dirty mark per
+ *   slot, and marks every episode held.  RZ_ERR_ARG if E * T > 2^30 (the total stays below 2^62).  From then on add / ingest
+ *   mark the slots they wrote and update marks the slots of its valid `where` rows (a changed root value moves the priority of
+ *   its step and of the step td_steps before it, both in that slot), each with one small launch behind their own; the handle
+ *   notes on the host that the prefixes are stale.  A second call does nothing.
+ * rz_mz_replay_refresh_priorities: two launches on `stream`, no host synchronisation -- k_mzr_prio (a workgroup per episode
+ *   held; a clean slot returns at once, a marked one gets its weights, its prefix by a wave scan with a carry over the waves
+ *   and over chunks of 256 steps, its mass, and its mark cleared) and k_mzr_scan (one workgroup: ecum and the total).
+ * rz_mz_replay_read_priorities: SYNCHRONOUS (tests, debugging): refreshes, then h_w int64 [n][T] receives the weights of episodes
+ *   first .. first + n - 1 (oldest = 0) as differences of cum, 0 past an episode's end; *h_total (may be NULL) the total.
+ * rz_mz_replay_draw_prioritized: refreshes on `stream` if anything was written since the last refresh, then ONE launch
+ *   (k_mzr_draw_prio, a thread per entry).  Entry i takes ONE target g in 0 .. total - 1 -- d_targets[i] (int64 [n], device
+ *   memory) or, d_targets NULL, mulhi64(x, total) of x = sm(sm(sm(seed ^ "mzpriori") ^ step) ^ c), c = i * (K + 2) -- and
+ *   resolves it by two searches: j = the first episode with ecum[j] > g, then the first position of it with
+ *   cum[position] > g - ecum[j - 1].  d_draws int64 [n][K + 2] receives (j, position, K filler actions: counters c + 2 + k,
+ *   uniform over A; c + 1 is unused) in the layout rz_mz_replay_gather takes as d_draws, d_prob float64 [n] the step's
+ *   probability (double)w / (double)total.  A target outside 0 .. total - 1 sets RZ_MZ_REPLAY_BAD_INDEX; that entry's row is
+ *   all -1, which rz_mz_replay_gather refuses too, and its probability 0.  RZ_ERR_ARG on an empty buffer or while priorities
+ *   are off. */
+int rz_mz_replay_enable_priorities(rz_mz_replay *r, void *stream);
+int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream);
+int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int64_t *h_w, int64_t *h_total, void *stream);
+int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, const int64_t *d_targets, int64_t *d_draws,
+                                  double *d_prob, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// rz_mz_replay.hip -- the MuZero learner's replay buffer in device memory (include/rlzero_hip.h: rz_mz_replay_*, ABI 35; Reanalyse: ABI 36).
+// rz_mz_replay.hip -- the MuZero learner's replay buffer in device memory (include/rlzero_hip.h: rz_mz_replay_*, ABI 35; Reanalyse: ABI 36; prioritized
+// replay: ABI 37).
 //
 // Finished episodes live on the GPU in fixed-stride slots -- slot e holds up to T steps, structure of arrays -- in a ring over
 // EPISODES, and a mini-batch of unrolled targets is ONE launch: k_mzr_gather / k_mzr_sample write the observation, the K actions
@@ -6,7 +7,9 @@
 // rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample forms on the host (the rules and the arithmetic: rz_mz_target.h).  Episodes
 // arrive as packed float64 records, the format of rz_mz_play_cartpole: from a staged host block (k_mzr_add) or straight from a
 // launch's device arena (k_mzr_ingest: only a small entry table travels).  Reanalyse (k_mzr_positions, k_mzr_update) hands stored
-// observations out to a fresh search and takes its visit counts and root value back into the steps they came from.
+// observations out to a fresh search and takes its visit counts and root value back into the steps they came from.  Prioritized
+// replay (k_mzr_prio, k_mzr_scan, k_mzr_draw_prio; opt-in) keeps an integer priority per stored step and its prefix sums on the
+// device and draws steps in proportion to them.
 //
 // Bounds: every slot is reduced modulo the capacity, every length is clamped to 0 .. T where it is read, every step index is compared
 // with that length before a read, rows of a block are checked against its row count (on the host and again in the kernel), and an
@@ -217,6 +220,155 @@ __global__ __launch_bounds__(kThreads) void k_mzr_update(MzrDev R, const int32_t
     }
 }
 
+// ---- Prioritized replay (ABI 37; the arithmetic and the draws: rz_mz_target.h).  Step t of a held episode weighs
+// w = priority_weight(|root value - n-step return|), an integer; cum[slot][t] is the inclusive prefix of w inside the episode,
+// mass[slot] its last entry, ecum[j] the inclusive prefix of the masses over the episodes held, oldest first, and *total the sum
+// of everything.  Integer sums: the scans below give the bits of a loop in any order.  dirty[slot] != 0: the slot was written
+// (k_mzr_add / k_mzr_ingest / k_mzr_update) since its prefix was formed.
+constexpr int kScanThreads = 1024, kScanWaves = kScanThreads / 64;
+
+struct MzrPrio {
+    uint64_t *cum;     // [E][T]
+    uint64_t *mass;    // [E] by slot
+    uint64_t *ecum;    // [E] by age: 0 = the oldest held
+    uint64_t *total;   // [1]
+    int32_t *dirty;    // [E] by slot
+};
+
+// the inclusive scan of v over the 64 lanes of a wave
+__device__ __forceinline__ uint64_t mzr_wave_scan(uint64_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t below = (uint64_t)__shfl_up((unsigned long long)v, (unsigned)d, 64);
+        if (lane >= d) v += below;
+    }
+    return v;
+}
+
+// the slots first .. first + n - 1 (modulo E) were written
+__global__ __launch_bounds__(kThreads) void k_mzr_mark(MzrPrio P, int E, long long first, long long n) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n || i >= E) return;
+    P.dirty[(int)((first + i) % E)] = 1;
+}
+
+// the slots k_mzr_update wrote to: its own checks of `where`, entry by entry, and nothing but the mark of slot where[i].slot
+__global__ __launch_bounds__(kThreads) void k_mzr_mark_where(MzrDev R, MzrPrio P, const int32_t *__restrict__ where, long long n) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int slot = where[2 * i], pos = where[2 * i + 1];
+    if (slot < 0 || slot >= R.E || pos < 0 || pos >= R.T) return;
+    if (pos >= mzr_length(R, slot)) return;
+    P.dirty[slot] = 1;
+}
+
+// A workgroup per held episode; one whose slot is clean returns at once.  Chunks of kThreads steps: each thread forms its step's
+// weight, a wave scan, the waves' sums through LDS, and the chunk's sum carried into the next chunk (any T).
+__global__ __launch_bounds__(kThreads) void k_mzr_prio(MzrDev R, MzrPrio P, long long oldest, long long count) {
+    __shared__ uint64_t wave_sum[kWaves];
+    if ((long long)blockIdx.x >= count) return;
+    const int slot = mzr_slot(R, oldest + blockIdx.x);
+    const int mark = P.dirty[slot];
+    __syncthreads();   // (every thread has read the mark before thread 0 clears it)
+    if (mark == 0) return;
+    const int len = mzr_length(R, slot), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long base = (long long)slot * R.T;
+    uint64_t carry = 0;
+    for (int first = 0; first < len; first += kThreads) {
+        const int t = first + (int)threadIdx.x;
+        const uint64_t w = t < len ? rzmzt::priority_weight(rzmzt::priority_of(R.reward + base, R.root_value + base, len, t, R.td, R.disc)) : 0;
+        uint64_t s = mzr_wave_scan(w, lane);
+        if (lane == 63) wave_sum[wave] = s;
+        __syncthreads();
+        uint64_t chunk = 0;
+#pragma unroll
+        for (int v = 0; v < kWaves; ++v) {
+            if (v < wave) s += wave_sum[v];
+            chunk += wave_sum[v];
+        }
+        if (t < len) P.cum[base + t] = carry + s;
+        carry += chunk;
+        __syncthreads();   // (wave_sum is read before the next chunk writes it)
+    }
+    if (threadIdx.x == 0) {
+        P.mass[slot] = carry;
+        P.dirty[slot] = 0;
+    }
+}
+
+// ONE workgroup: thread i sums the masses of the episodes i * per .. (i + 1) * per - 1 (by age), a scan of the partial sums over
+// the workgroup, and the run walked again to write its prefixes.
+__global__ __launch_bounds__(kScanThreads) void k_mzr_scan(MzrPrio P, int E, long long oldest, long long count) {
+    __shared__ uint64_t wave_sum[kScanWaves];
+    if (count > E) count = E;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long per = (count + kScanThreads - 1) / kScanThreads;
+    const long long from = min((long long)threadIdx.x * per, count), to = min(from + per, count);
+    uint64_t run = 0;
+    for (long long j = from; j < to; ++j) run += P.mass[(int)((oldest + j) % E)];
+    uint64_t s = mzr_wave_scan(run, lane);
+    if (lane == 63) wave_sum[wave] = s;
+    __syncthreads();
+    uint64_t all = 0;
+#pragma unroll
+    for (int v = 0; v < kScanWaves; ++v) {
+        if (v < wave) s += wave_sum[v];
+        all += wave_sum[v];
+    }
+    uint64_t at = s - run;   // the sum of everything before this thread's run
+    for (long long j = from; j < to; ++j) {
+        at += P.mass[(int)((oldest + j) % E)];
+        P.ecum[j] = at;
+    }
+    if (threadIdx.x == 0) *P.total = all;
+}
+
+// A thread per entry: ONE target g in 0 .. total - 1 -- from the entry's stream or from `targets` -- resolved by two searches,
+// the episode in ecum, the position in the episode's cum; the draw row (episode by age, position, K fillers) in the layout of
+// k_mzr_gather and the step's probability w / total.  A target out of range (or a table that does not hold it): the flag, a row
+// of -1 that k_mzr_gather refuses as well, and probability 0.
+__global__ __launch_bounds__(kThreads) void k_mzr_draw_prio(MzrDev R, MzrPrio P, unsigned long long seed, unsigned long long step,
+                                                             const long long *__restrict__ targets, long long oldest, long long count, long long n,
+                                                             long long *__restrict__ draws, double *__restrict__ prob) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int K = R.K;
+    long long *dr = draws + i * (K + 2);
+    const uint64_t total = *P.total;
+    if (count > R.E) count = R.E;
+    bool bad = total == 0 || count <= 0;
+    uint64_t g = 0;
+    if (targets != nullptr) {
+        bad = bad || targets[i] < 0 || (uint64_t)targets[i] >= total;
+        g = (uint64_t)targets[i];
+    } else if (!bad) {
+        g = rzmzt::prio_target(seed, step, (uint64_t)i, K, total);
+    }
+    long long ep = 0, pos = 0;
+    uint64_t w = 0;
+    if (!bad) {
+        ep = rzmzt::upper_bound_u64(P.ecum, count, g);
+        bad = ep >= count;
+    }
+    if (!bad) {
+        const int slot = mzr_slot(R, oldest + ep);
+        const int len = mzr_length(R, slot);
+        const uint64_t *cum = P.cum + (long long)slot * R.T;
+        pos = rzmzt::upper_bound_u64(cum, len, g - (ep > 0 ? P.ecum[ep - 1] : 0));
+        bad = pos >= len;
+        if (!bad) w = cum[pos] - (pos > 0 ? cum[pos - 1] : 0);
+    }
+    if (bad) {
+        atomicOr(R.err, kFlagBadIndex);
+        for (int j = 0; j < K + 2; ++j) dr[j] = -1;
+        prob[i] = 0.0;
+        return;
+    }
+    dr[0] = ep, dr[1] = pos;
+    for (int k = 0; k < K; ++k) dr[2 + k] = rzmzt::prio_filler(seed, step, (uint64_t)i, K, k, (uint64_t)R.A);
+    prob[i] = (double)w / (double)total;
+}
+
 int mr_fail(int code, const char *msg) {
     rz_set_error(msg);
     return code;
@@ -236,6 +388,10 @@ struct rz_mz_replay {
     size_t stage_bytes = 0;
     hipEvent_t copied = nullptr, consumed = nullptr;
     bool in_flight = false;
+    // prioritized replay (rz_mz_replay_enable_priorities): nothing of it exists until it is enabled
+    MzrPrio prio = {};
+    bool prio_on = false;
+    bool prio_stale = false;   // a slot was written since the prefixes were formed: the next prioritized draw refreshes first
 };
 
 namespace {
@@ -334,6 +490,33 @@ int mr_outputs(rz_mz_replay *r, int64_t n, const MzrOut &O) {
 
 inline unsigned mr_blocks(const rz_mz_replay *r, int64_t n) { return (unsigned)((n * (r->dev.K + 1) + kThreads - 1) / kThreads); }
 
+// priorities on: the slots `first` .. + n - 1 (modulo E) were written by a kernel launched on `s` before this call
+int mr_mark(rz_mz_replay *r, long long first, long long n, hipStream_t s) {
+    if (!r->prio_on || n <= 0) return RZ_OK;
+    if (n > r->dev.E) n = r->dev.E;
+    hipLaunchKernelGGL(k_mzr_mark, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r->prio, r->dev.E, first, n);
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_mark launch failed");
+    r->prio_stale = true;
+    return RZ_OK;
+}
+// the slots of an entry table: contiguous modulo E from its first entry's
+int mr_mark_table(rz_mz_replay *r, const std::vector<int32_t> &table, hipStream_t s) {
+    if (!r->prio_on || table.empty()) return RZ_OK;
+    return mr_mark(r, table[2], (long long)(table.size() / kEntryWords), s);
+}
+
+// the prefixes of every slot written since they were last formed, then the prefix over the episodes: two launches on `s`
+int mr_refresh(rz_mz_replay *r, hipStream_t s) {
+    if (r->count > 0) {
+        const long long oldest = mr_oldest(r);
+        hipLaunchKernelGGL(k_mzr_prio, dim3((unsigned)r->count), dim3(kThreads), 0, s, r->dev, r->prio, oldest, r->count);
+        hipLaunchKernelGGL(k_mzr_scan, dim3(1), dim3(kScanThreads), 0, s, r->prio, r->dev.E, oldest, r->count);
+        if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_prio / k_mzr_scan launch failed");
+    }
+    r->prio_stale = false;
+    return RZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,7 +574,8 @@ int rz_mz_replay_destroy(rz_mz_replay *r) {
     if (r->copied) (void)hipEventDestroy(r->copied);
     if (r->consumed) (void)hipEventDestroy(r->consumed);
     if (r->h_stage) (void)hipHostFree(r->h_stage);
-    void *dev[] = {r->d_stage, r->dev.obs, r->dev.action, r->dev.reward, r->dev.root_value, r->dev.policy, r->dev.length, r->d_disc, r->dev.err};
+    void *dev[] = {r->d_stage, r->dev.obs, r->dev.action, r->dev.reward, r->dev.root_value, r->dev.policy, r->dev.length, r->d_disc, r->dev.err,
+                   r->prio.cum, r->prio.mass, r->prio.ecum, r->prio.total, r->prio.dirty};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     delete r;
@@ -444,7 +628,7 @@ int rz_mz_replay_add(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengt
     rc = mr_launched(r, s, "k_mzr_add launch failed");
     if (rc != RZ_OK) return rc;
     mr_commit(r, table, kept);
-    return RZ_OK;
+    return mr_mark_table(r, table, s);
 }
 
 int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int64_t *h_first_rows, const double *d_arena,
@@ -472,7 +656,7 @@ int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_le
     rc = mr_launched(r, s, "k_mzr_ingest launch failed");
     if (rc != RZ_OK) return rc;
     mr_commit(r, table, kept);
-    return RZ_OK;
+    return mr_mark_table(r, table, s);
 }
 
 int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv,
@@ -575,6 +759,12 @@ int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, cons
     hipLaunchKernelGGL(k_mzr_update, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, r->dev, d_where, (long long)n, d_visits, d_root_n,
                        d_root_sum);
     if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_update launch failed");
+    if (r->prio_on) {   // a changed root value moves the priority of its step and of the step td before it: both in this slot
+        hipLaunchKernelGGL(k_mzr_mark_where, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, r->prio,
+                           d_where, (long long)n);
+        if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_mark_where launch failed");
+        r->prio_stale = true;
+    }
     return RZ_OK;
 }
 
@@ -612,6 +802,91 @@ int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream) {
     if (hipMemcpyAsync(flags, r->dev.err, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemsetAsync(r->dev.err, 0, sizeof(int32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return mr_fail(RZ_ERR_HIP, "reading the MuZero replay flags failed");
+    return RZ_OK;
+}
+
+int rz_mz_replay_enable_priorities(rz_mz_replay *r, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (r->prio_on) return RZ_OK;
+    const MzrDev &R = r->dev;
+    if ((long long)R.E * R.T > (1LL << 30)) return mr_fail(RZ_ERR_ARG, "priorities need at most 2^30 steps in all (the total stays below 2^62)");
+    MzrPrio P = {};
+    const size_t E = (size_t)R.E;
+    const bool ok = hipMalloc((void **)&P.cum, E * R.T * sizeof(uint64_t)) == hipSuccess && hipMalloc((void **)&P.mass, E * sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc((void **)&P.ecum, E * sizeof(uint64_t)) == hipSuccess && hipMalloc((void **)&P.total, sizeof(uint64_t)) == hipSuccess &&
+                    hipMalloc((void **)&P.dirty, E * sizeof(int32_t)) == hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ok || hipMemsetAsync(P.cum, 0, E * R.T * sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(P.mass, 0, E * sizeof(uint64_t), s) != hipSuccess ||
+        hipMemsetAsync(P.ecum, 0, E * sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(P.total, 0, sizeof(uint64_t), s) != hipSuccess ||
+        hipMemsetAsync(P.dirty, 0, E * sizeof(int32_t), s) != hipSuccess) {
+        void *dev[] = {P.cum, P.mass, P.ecum, P.total, P.dirty};
+        for (void *p : dev)
+            if (p) (void)hipFree(p);
+        return mr_fail(ok ? RZ_ERR_HIP : RZ_ERR_OOM, "allocating the priority tables failed (MuZero replay)");
+    }
+    r->prio = P;
+    r->prio_on = true;
+    r->prio_stale = true;
+    return mr_mark(r, mr_oldest(r), r->count, s);   // every episode held
+}
+
+int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    return mr_refresh(r, (hipStream_t)stream);
+}
+
+int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int64_t *h_w, int64_t *h_total, void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    if (first < 0 || n < 0 || first + n > r->count) return mr_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    if (n > 0 && h_w == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    rc = mr_refresh(r, s);
+    if (rc != RZ_OK) return rc;
+    const MzrDev &R = r->dev;
+    const long long E = R.E, start = (mr_oldest(r) + first) % E;
+    const long long n1 = n < E - start ? n : E - start;   // up to the ring's end, then from its start
+    const size_t T = (size_t)R.T;
+    std::vector<uint64_t> cum((size_t)n * T);
+    uint64_t total = 0;
+    bool ok = true;
+    for (int part = 0; part < 2; ++part) {
+        const long long from = part == 0 ? start : 0, cnt = part == 0 ? n1 : n - n1, at = part == 0 ? 0 : n1;
+        if (cnt <= 0) continue;
+        ok = ok && hipMemcpyAsync(cum.data() + at * T, r->prio.cum + from * T, (size_t)cnt * T * sizeof(uint64_t), hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(&total, r->prio.total, sizeof(uint64_t), hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return mr_fail(RZ_ERR_HIP, "read-back failed (MuZero replay priorities)");
+    for (int64_t j = 0; j < n; ++j) {
+        const int len = r->lengths[(size_t)((start + j) % E)];
+        for (int t = 0; t < R.T; ++t)
+            h_w[(size_t)j * T + t] = t < len ? (int64_t)(cum[(size_t)j * T + t] - (t > 0 ? cum[(size_t)j * T + t - 1] : 0)) : 0;
+    }
+    if (h_total) *h_total = (int64_t)total;
+    return RZ_OK;
+}
+
+int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, const int64_t *d_targets, int64_t *d_draws, double *d_prob,
+                                  void *stream) {
+    int rc = mr_ready(r);
+    if (rc != RZ_OK) return rc;
+    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (n == 0) return RZ_OK;
+    if (d_draws == nullptr || d_prob == nullptr) return mr_fail(RZ_ERR_ARG, "NULL output buffer");
+    hipStream_t s = (hipStream_t)stream;
+    if (r->prio_stale) {
+        rc = mr_refresh(r, s);
+        if (rc != RZ_OK) return rc;
+    }
+    hipLaunchKernelGGL(k_mzr_draw_prio, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r->dev, r->prio, (unsigned long long)seed,
+                       (unsigned long long)step, (const long long *)d_targets, mr_oldest(r), r->count, (long long)n, (long long *)d_draws, d_prob);
+    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_draw_prio launch failed");
     return RZ_OK;
 }
 

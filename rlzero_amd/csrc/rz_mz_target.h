@@ -3,8 +3,9 @@
 // the CPU can test it against rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample (tests/test_mz_replay_host.py); the kernels call
 // these functions.  The arithmetic is fp64 multiply and add in the order of ReplayBuffer._value_target, the discounts come from a
 // table the host filled with `discount ** i` (no pow here), and the value is cast to float32 once: with -ffp-contract=off the
-// host's bits.  Reanalyse's arithmetic and draws (k_mzr_positions, k_mzr_update) are at the end, tested the same way
-// (tests/test_mz_reanalyse_host.py).
+// host's bits.  Reanalyse's arithmetic and draws (k_mzr_positions, k_mzr_update) follow, tested the same way
+// (tests/test_mz_reanalyse_host.py), and at the end the integer priorities, the draws and the search of prioritized replay
+// (k_mzr_prio, k_mzr_draw_prio; tests/test_mz_prioritized_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -122,6 +123,47 @@ RZT_FN int64_t reanalyse_draw(uint64_t seed, uint64_t step, uint64_t i, int j, u
     x = mix64(x ^ step);
     x = mix64(x ^ (2 * i + (uint64_t)j));
     return (int64_t)mulhi64(x, n);
+}
+
+// ---- Prioritized replay (k_mzr_prio, k_mzr_scan, k_mzr_draw_prio; rlzero_amd/muzero/replay.py: mz_priority_weights,
+// mz_prioritized_draws): arXiv:1911.08265v2 appendix G with alpha = 1 -- step t is drawn with probability p_t / sum p, where
+// p_t = |root value - n-step return| of the SAME stored step.  The priorities are FIXED-POINT integers (16 fraction bits), so that
+// sums are exact in any order and a parallel scan gives the bits of a Python loop.
+RZT_FN double priority_of(const double *reward, const double *root_value, int len, int t, int td, const double *disc) {
+    return __builtin_fabs(root_value[t] - value_target(reward, root_value, len, t, td, disc));
+}
+// p * 2^16 truncated (the product by a power of two is exact), at least 1 -- every stored step stays drawable -- and 2^32 from
+// p = 2^16 on, which bounds the total of 2^30 steps below 2^62; a NaN gives 1.
+RZT_FN uint64_t priority_weight(double p) {
+    if (!(p > 0.0)) return 1;   // zero, a NaN (and anything negative: fabs gives none)
+    if (p >= 65536.0) return 1ull << 32;
+    const uint64_t w = (uint64_t)(p * 65536.0);
+    return w > 1 ? w : 1;
+}
+
+constexpr uint64_t kPrioSalt = 0x6D7A7072696F7269ull;   // "mzpriori": the prioritized sampler's own stream
+
+// Entry i of update `step`, over the counters of `draw_counter`: j = 0 ONE uniform over 0 .. total - 1 that decides episode and
+// position together, j = 1 unused, j = 2 + k the filler action of unroll step k (uniform over A, as in `draw`).
+RZT_FN uint64_t prio_chain(uint64_t seed, uint64_t step, uint64_t c) {
+    uint64_t x = mix64(seed ^ kPrioSalt);
+    x = mix64(x ^ step);
+    return mix64(x ^ c);
+}
+RZT_FN uint64_t prio_target(uint64_t seed, uint64_t step, uint64_t i, int K, uint64_t total) {
+    return mulhi64(prio_chain(seed, step, draw_counter(i, K, 0)), total);
+}
+RZT_FN int64_t prio_filler(uint64_t seed, uint64_t step, uint64_t i, int K, int k, uint64_t A) {
+    return (int64_t)mulhi64(prio_chain(seed, step, draw_counter(i, K, 2 + k)), A);
+}
+// the first index of cum[0 .. n - 1] (non-decreasing) with cum[idx] > g; n if there is none
+RZT_FN int64_t upper_bound_u64(const uint64_t *cum, int64_t n, uint64_t g) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (cum[mid] > g) hi = mid; else lo = mid + 1;
+    }
+    return lo;
 }
 
 }  // namespace rzmzt

@@ -7,9 +7,9 @@ from .agent import MuZeroAgent
 from .cartpole import CartPoleBatch
 from .network import MuZeroNet
 from .reanalyse import MuZeroReanalyser, mz_reanalyse_draws
-from .replay import MuZeroDeviceReplay, mz_replay_draws
+from .replay import MuZeroDeviceReplay, mz_prioritized_draws, mz_priority_weights, mz_replay_draws
 from .selfplay import MuZeroSelfPlay, ReplayBuffer
 from .tree import MuZeroTree
 
 __all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree', 'MuZeroDeviceReplay', 'mz_replay_draws',
-           'MuZeroReanalyser', 'mz_reanalyse_draws']
+           'MuZeroReanalyser', 'mz_reanalyse_draws', 'mz_priority_weights', 'mz_prioritized_draws']

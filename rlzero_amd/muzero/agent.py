@@ -20,9 +20,11 @@ class MuZeroAgent(object):
         self.net = MuZeroNet(obs_dim, n_actions, hidden).to(self.device)
         self.optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=weight_decay)
 
-    def learn(self, batch):
+    def learn(self, batch, weights=None):
         """batch = ReplayBuffer.sample(...) (numpy arrays) or MuZeroDeviceReplay.sample(...) (device tensors, taken as they are)
-        -> (loss, value loss, reward loss, policy loss) floats."""
+        -> (loss, value loss, reward loss, policy loss) floats.  ``weights`` [b] (MuZeroDeviceReplay.sample_prioritized): the
+        importance weights of prioritized replay, a factor on every entry's loss before the mean (appendix G); the three
+        component losses returned stay unweighted."""
         obs, actions, tv, tr, tp, mask = ((a if isinstance(a, torch.Tensor) else torch.from_numpy(a)).to(self.device) for a in batch)
         K = actions.shape[1]
         net = self.net
@@ -38,7 +40,11 @@ class MuZeroAgent(object):
             lr_ = lr_ + scale_gradient(F.mse_loss(reward, tr[:, k], reduction='none'), g)
             lp = lp + scale_gradient(-(tp[:, k] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, k], g)
             state = scale_gradient(state, 0.5)
-        loss = (0.25 * lv + lr_ + lp).mean()
+        if weights is None:
+            loss = (0.25 * lv + lr_ + lp).mean()
+        else:
+            weights = (weights if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)).to(self.device, torch.float32)
+            loss = ((0.25 * lv + lr_ + lp) * weights).mean()
         self.optimizer.zero_grad()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), 5.0)

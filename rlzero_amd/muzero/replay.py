@@ -17,7 +17,15 @@ and adds in fp64 in the host's order and casts to float32 once (csrc/rz_mz_targe
 ``sample`` draws episode, position and filler actions from a counter-based stream (``mz_replay_draws``: the same bits on the
 host) -- the episode uniform over the episodes held, the position uniform over its length, the host buffer's distribution, but
 not the host buffer's ``RandomState`` sequence.
+
+Prioritized replay (``prioritized=True`` or ``enable_priorities()``; arXiv:1911.08265v2 appendix G with alpha = 1) draws a step
+with probability w / sum(w), w the fixed-point integer of |root value - n-step return| of that step
+(``mz_priority_weights``).  The weights and their prefix sums live on the device beside the store, so a Reanalyse that
+rewrites root values moves the priorities with no read-back; ``sample_prioritized`` returns the mini-batch and the
+importance weights (1 / (N P)) ** beta.  Integer sums are exact in any order: ``mz_prioritized_draws`` restates the device's
+draws bit for bit.
 """
+import bisect
 import ctypes
 
 import numpy as np
@@ -27,6 +35,7 @@ from .._hip import HipError
 
 _MASK = (1 << 64) - 1
 _SAMPLE_SALT = 0x6D7A7265706C6179   # "mzreplay" (csrc/rz_mz_target.h: kSampleSalt)
+_PRIO_SALT = 0x6D7A7072696F7269     # "mzpriori" (csrc/rz_mz_target.h: kPrioSalt)
 MAX_OBS, MAX_ACTIONS, MAX_UNROLL, MAX_TD = 16, 8, 16, 64
 FINAL_POLICY = 1                    # rz_mz_replay_add's flag: the visit columns of the episode's rows hold the float32 policy
 
@@ -64,6 +73,76 @@ def mz_replay_draws(seed, step, n, lengths, K, A):
     return ep, pos, filler
 
 
+def mz_priority_weights(rewards, root_values, td_steps, disc):
+    """The integer priorities of one episode's steps (k_mzr_prio, csrc/rz_mz_target.h: priority_of, priority_weight), int64
+    [len]: p = |root_values[t] - z_t| with z_t the n-step return as ``ReplayBuffer._value_target`` evaluates it, then
+    w = max(1, int(p * 65536)) below p = 65536, 2 ** 32 from there on, 1 for a NaN.  ``disc``: the discount, or the table
+    ``[discount ** i for i in range(td_steps + 1)]``."""
+    rewards, root_values = np.asarray(rewards, dtype=np.float64), np.asarray(root_values, dtype=np.float64)
+    td = int(td_steps)
+    if np.ndim(disc) == 0:
+        disc = [float(disc) ** i for i in range(td + 1)]
+    disc = np.asarray(disc, dtype=np.float64)
+    n = len(rewards)
+    out = np.zeros(n, dtype=np.int64)
+    for t in range(n):
+        boot = t + td
+        value = root_values[boot] * disc[td] if boot < n else 0.0
+        for i, r in enumerate(rewards[t:boot]):
+            value += r * disc[i]
+        p = abs(float(root_values[t]) - float(value))
+        if not p > 0.0:        # zero or a NaN
+            out[t] = 1
+        elif p >= 65536.0:
+            out[t] = 1 << 32
+        else:
+            out[t] = max(1, int(p * 65536.0))
+    return out
+
+
+def mz_prioritized_draws(seed, step, n, weights_per_episode, K, A, targets=None):
+    """The draws of ``prioritized_draws(n, step)`` over episodes with these integer step weights (oldest first), in Python
+    integers -- the device's bits (k_mzr_draw_prio): entry i takes ONE target g = (x * total) >> 64 for the 64-bit x of the
+    splitmix64 chain over (seed ^ "mzpriori", step, c = i (K + 2)), or ``targets[i]``; the episode is the first whose
+    inclusive prefix of episode masses exceeds g, the position the first whose inclusive prefix inside the episode exceeds
+    what is left of g; counter c + 1 is unused and c + 2 + k gives the filler of actions[i, k], uniform over A.
+    -> (ep int64 [n], pos int64 [n], filler int64 [n, K], prob float64 [n] = w / total, one division)."""
+    weights = [[int(w) for w in ws] for ws in weights_per_episode]
+    if not weights or min(len(ws) for ws in weights) <= 0:
+        raise ValueError('draws need at least one episode, none of them empty')
+    K, A = int(K), int(A)
+    cums, ecum, total = [], [], 0
+    for ws in weights:   # the device's tables: the inclusive prefix inside every episode, and over the episodes' masses
+        acc, cum = 0, []
+        for w in ws:
+            acc += w
+            cum.append(acc)
+        total += acc
+        cums.append(cum)
+        ecum.append(total)
+    base = _sm(_sm((int(seed) & _MASK) ^ _PRIO_SALT) ^ (int(step) & _MASK))
+
+    def chain(c):
+        return _sm(base ^ (c & _MASK))
+    n = int(n) if targets is None else len(targets)
+    ep = np.zeros(n, dtype=np.int64)
+    pos = np.zeros(n, dtype=np.int64)
+    filler = np.zeros((n, K), dtype=np.int64)
+    prob = np.zeros(n, dtype=np.float64)
+    for i in range(n):
+        c = i * (K + 2)
+        g = (chain(c) * total) >> 64 if targets is None else int(targets[i])
+        if not 0 <= g < total:
+            raise ValueError('target %d outside 0 .. %d' % (g, total - 1))
+        j = bisect.bisect_right(ecum, g)   # the first episode with ecum[j] > g (upper_bound_u64)
+        t = bisect.bisect_right(cums[j], g - (ecum[j - 1] if j else 0))
+        ep[i], pos[i] = j, t
+        prob[i] = float(weights[j][t]) / float(total)
+        for k in range(K):
+            filler[i, k] = (chain(c + 2 + k) * A) >> 64
+    return ep, pos, filler, prob
+
+
 def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
@@ -73,7 +152,7 @@ class MuZeroDeviceReplay(object):
     episodes held, like the host buffer.  No CPU fallback: HipError without a GPU."""
 
     def __init__(self, obs_dim, n_actions, capacity_episodes, max_episode_steps, unroll_steps=5, td_steps=10, discount=0.997,
-                 device='cuda:0', seed=0):
+                 device='cuda:0', seed=0, prioritized=False):
         import torch
         self.torch = torch
         self.lib = _hip.load()
@@ -94,6 +173,9 @@ class MuZeroDeviceReplay(object):
         _hip.check(self.lib.rz_mz_replay_create(self.obs_dim, self.n_actions, self.capacity, self.max_episode_steps, self.K, self.td_steps,
                                                 _ptr(self.disc), self.device.index, ctypes.byref(handle)), 'rz_mz_replay_create')
         self.handle = handle
+        self.prioritized = False
+        if prioritized:
+            self.enable_priorities()
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -268,6 +350,82 @@ class MuZeroDeviceReplay(object):
         _hip.check(self.lib.rz_mz_replay_sample(self.handle, self.seed & _MASK, int(step) & _MASK, int(n), *self._out_ptrs(out), self._stream()),
                    'rz_mz_replay_sample')
         return out
+
+    # ------------------------------------------------------------------ prioritized replay
+    def enable_priorities(self):
+        """Turns prioritized replay on: the per-step integer priorities, their prefix sums and the dirty marks are allocated on
+        the device and every episode held is marked; from here on ``add`` / ``ingest`` / ``update`` mark what they write and the
+        next prioritized draw refreshes the marked episodes on its own stream.  ``sample`` is not changed."""
+        if not self.prioritized:
+            _hip.check(self.lib.rz_mz_replay_enable_priorities(self.handle, self._stream()), 'rz_mz_replay_enable_priorities')
+            self.prioritized = True
+
+    def _need_priorities(self, what):
+        if not self.prioritized:
+            raise HipError('%s: priorities are off (MuZeroDeviceReplay(prioritized=True) or enable_priorities())' % what)
+
+    def refresh_priorities(self):
+        """The priorities of every episode written since the last refresh and the prefix over the episodes, two launches on the
+        current stream (a prioritized draw does this by itself when anything was written)."""
+        self._need_priorities('refresh_priorities')
+        _hip.check(self.lib.rz_mz_replay_refresh_priorities(self.handle, self._stream()), 'rz_mz_replay_refresh_priorities')
+
+    def priorities(self):
+        """The integer priority of every step held: a list of int64 arrays, oldest episode first (``mz_priority_weights`` of
+        each episode, bit for bit).  A synchronous copy (tests, debugging)."""
+        self._need_priorities('priorities')
+        n, T = len(self), self.max_episode_steps
+        w = np.zeros((max(n, 1), T), dtype=np.int64)
+        total = ctypes.c_int64()
+        if n:
+            _hip.check(self.lib.rz_mz_replay_read_priorities(self.handle, 0, n, _ptr(w), ctypes.byref(total), self._stream()),
+                       'rz_mz_replay_read_priorities')
+        out = [w[j, :int(m)].copy() for j, m in enumerate(self.lengths())]
+        if sum(int(x.sum()) for x in out) != total.value:
+            raise HipError('rz_mz_replay_read_priorities: the weights sum to %d, the device total is %d'
+                           % (sum(int(x.sum()) for x in out), total.value))
+        return out
+
+    def _draw_prioritized(self, n, step, targets):
+        t = self.torch
+        self._need_priorities('prioritized draws')
+        d_targets = None
+        if targets is not None:
+            if not isinstance(targets, t.Tensor):
+                targets = t.from_numpy(np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)).to(self.device)
+            if targets.device != self.device or targets.dtype != t.int64:
+                raise ValueError('targets: int64 on %s' % (self.device, ))
+            targets = targets.reshape(-1).contiguous()
+            n, d_targets = targets.numel(), targets.data_ptr()
+        n = int(n)
+        if step is None:
+            step, self.step = self.step, self.step + 1
+        draws = t.empty((n, self.K + 2), dtype=t.int64, device=self.device)
+        prob = t.empty((n, ), dtype=t.float64, device=self.device)
+        _hip.check(self.lib.rz_mz_replay_draw_prioritized(self.handle, self.seed & _MASK, int(step) & _MASK, n, d_targets, draws.data_ptr(),
+                                                          prob.data_ptr(), self._stream()), 'rz_mz_replay_draw_prioritized')
+        return draws, prob
+
+    def prioritized_draws(self, n, step=None, targets=None):
+        """``n`` steps drawn on the device in proportion to their priorities (``mz_prioritized_draws``: the same bits) ->
+        device tensors (ep_idx int64 [n], pos int64 [n], filler int64 [n, K], prob float64 [n]).  ``targets`` (int64 [n], numpy
+        or device): the entries' targets in 0 .. total - 1 instead of the stream's, e.g. stratified ones; one outside that
+        range raises (and its row is all -1).  ``step`` None: ``sample``'s counter, advanced by the call.  Waits for the
+        stream to read the flag word; ``sample_prioritized`` does not."""
+        draws, prob = self._draw_prioritized(n, step, targets)
+        if targets is not None and self.poll_errors() & _hip.MZ_REPLAY_BAD_INDEX:
+            raise HipError('rz_mz_replay_draw_prioritized: a target is outside 0 .. total - 1')
+        return draws[:, 0], draws[:, 1], draws[:, 2:], prob
+
+    def sample_prioritized(self, n, step=None, beta=1.0):
+        """A mini-batch drawn by priority -> (the six tensors of ``gather`` for the device's draws, weights float32 [n]): the
+        draw launch, then the gather launch on the draws where they lie -- no flag is polled, the library made the draws --
+        and weights = (n_steps * prob) ** -beta, the importance weights of the paper (n_steps: the steps held)."""
+        draws, prob = self._draw_prioritized(n, step, None)
+        out = self._outputs(int(n))
+        _hip.check(self.lib.rz_mz_replay_gather(self.handle, None, draws.data_ptr(), int(n), *self._out_ptrs(out), self._stream()), 'rz_mz_replay_gather')
+        n_steps = int(self.lengths().astype(np.int64).sum())
+        return out, ((n_steps * prob) ** (-float(beta))).float()
 
     # ------------------------------------------------------------------ Reanalyse: stored steps out, fresh targets back
     def positions(self, ep_idx=None, pos=None, n=None, seed=None, step=0):

@@ -8,6 +8,7 @@ its ``tools/train_alphazero.py`` (a pipeline class with ``collect_selfplay_data`
     python tools/train_muzero.py --envs 256 --iterations 60
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay   # episodes and mini-batches stay on the GPU
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --reanalyse all   # and their targets stay fresh
+    python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --prioritized-replay   # steps drawn by |value - return|
 """
 import argparse
 import os
@@ -20,6 +21,8 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 NEEDS_DEVICE_REPLAY = '--reanalyse needs --device-replay: the steps are searched again and refreshed where they are stored, on the GPU'
+PRIORITIES_NEED_DEVICE_REPLAY = ('--prioritized-replay needs --device-replay: the priorities are kept beside the stored steps, '
+                                 'on the GPU')
 
 
 def reanalyse_arg(text):
@@ -36,12 +39,18 @@ class MuZeroPipeline(object):
 
     def __init__(self, n_envs=256, n_sims=50, unroll_steps=5, td_steps=10, discount=0.997, batch_size=256,
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
-                 reanalyse_batch=2048):
+                 reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0):
         """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
         (or, 'all', every step held), are searched again with the current network and their policy and root value refreshed
-        (MuZeroReanalyser: a second, small search object; the self-play object and its counters are not touched).  0: off."""
+        (MuZeroReanalyser: a second, small search object; the self-play object and its counters are not touched).  0: off.
+        ``prioritized_replay`` (needs ``device_replay``): mini-batches are drawn in proportion to |search value - n-step return|
+        of the stored steps (MuZeroDeviceReplay.sample_prioritized) and the loss of an entry is scaled by its importance weight
+        (1 / (N P)) ** ``priority_beta``; a Reanalyse moves the priorities with the root values it rewrites."""
+        self.prioritized_replay, self.priority_beta = bool(prioritized_replay), float(priority_beta)
+        if self.prioritized_replay and not device_replay:
+            raise ValueError(PRIORITIES_NEED_DEVICE_REPLAY)
         self.reanalyse = reanalyse if reanalyse == 'all' else int(reanalyse or 0)
         if self.reanalyse and not device_replay:
             raise ValueError(NEEDS_DEVICE_REPLAY)
@@ -52,7 +61,8 @@ class MuZeroPipeline(object):
         self.device_replay = bool(device_replay)
         if self.device_replay:
             self.buffer = MuZeroDeviceReplay(self.agent.net.obs_dim, self.env.n_actions, 2000, int(self.env.max_episode_steps),
-                                             unroll_steps=unroll_steps, td_steps=td_steps, discount=discount, device=device, seed=seed)
+                                             unroll_steps=unroll_steps, td_steps=td_steps, discount=discount, device=device, seed=seed,
+                                             prioritized=self.prioritized_replay)
         else:
             self.buffer = ReplayBuffer(unroll_steps=unroll_steps, td_steps=td_steps, discount=discount, seed=seed)
         self.reanalyser = None
@@ -85,7 +95,10 @@ class MuZeroPipeline(object):
     def policy_update(self):
         out = (0.0, 0.0, 0.0, 0.0)
         for _ in range(self.updates_per_iteration):
-            if self.device_replay:
+            if self.prioritized_replay:
+                batch, weights = self.buffer.sample_prioritized(self.batch_size, beta=self.priority_beta)
+                out = self.agent.learn(batch, weights=weights)
+            elif self.device_replay:
                 out = self.agent.learn(self.buffer.sample(self.batch_size))
             else:
                 out = self.agent.learn(self.buffer.sample(self.batch_size, self.env.n_actions))
@@ -117,11 +130,18 @@ if __name__ == '__main__':
     ap.add_argument('--reanalyse', type=reanalyse_arg, default=0, metavar='N|all',
                     help='per iteration, search N stored steps (or all of them) again with the current network and refresh their targets '
                          '(needs --device-replay; 0 = off)')
+    ap.add_argument('--prioritized-replay', action='store_true',
+                    help='draw mini-batches in proportion to |search value - n-step return| of the stored steps and scale the loss by the '
+                         'importance weights (needs --device-replay)')
+    ap.add_argument('--priority-beta', type=float, default=1.0, metavar='B', help='exponent of the importance weights (1 / (N P)) ** B')
     args = ap.parse_args()
     if args.reanalyse and not args.device_replay:
         ap.error(NEEDS_DEVICE_REPLAY)
+    if args.prioritized_replay and not args.device_replay:
+        ap.error(PRIORITIES_NEED_DEVICE_REPLAY)
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
-                          updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse)
+                          updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
+                          prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta)
     pipe.run(args.iterations)
     if args.save:
         pipe.agent.save_model(args.save)
