@@ -42,13 +42,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "rlzero_hip.h"
+#include "rz_host.h"
 #include "rz_trace.h"
 
 #pragma clang fp contract(off)
@@ -1556,34 +1556,17 @@ __global__ void k_play_stop(Dev E, Play Y) {
     fresh_root(E, g, E.cur_arena[g], 0);
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define RZ_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t err__ = (call);                                                           \
-        if (err__ != hipSuccess)                                                             \
-            return fail(err__ == hipErrorOutOfMemory ? RZ_ERR_OOM : RZ_ERR_HIP, "%s failed: %s", \
-                        #call, hipGetErrorString(err__));                                    \
-    } while (0)
+thread_local char g_err[kRzErrBytes] = "";
 
 }  // namespace
 
-// shared with rz_net.hip: set the thread-local message returned by rz_last_error()
+// rz_host.h (rz_fail): set the thread-local message returned by rz_last_error()
 void rz_set_error(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg ? msg : ""); }
 
 struct rz_engine {
     rz_config cfg;
     Dev dev;
-    std::vector<void *> allocs;
-    long long bytes = 0;
+    DevPool pool;   // every device array of the engine (rz_stats::device_bytes: its count)
     long long n_select = 0;
     int kb = 1, ks = 1;  // rz_set_in_flight: slots the next launches back up / select (sims_in_flight > 1 only)
     bool ml = false;     // sims_in_flight > 1: the level-synchronous kernel (default) instead of the sequential restatement
@@ -1605,33 +1588,23 @@ struct rz_engine {
 
 namespace {
 
-template <typename T>
-int dev_alloc(rz_engine *e, T **out, long long count) {
-    void *p = nullptr;
-    const size_t bytes = (size_t)count * sizeof(T);
-    hipError_t err = hipMalloc(&p, bytes ? bytes : 8);
-    if (err != hipSuccess)
-        return fail(RZ_ERR_OOM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(err));
-    e->allocs.push_back(p);
-    e->bytes += (long long)bytes;
-    *out = (T *)p;
-    return RZ_OK;
-}
-
-int check_engine(rz_engine *e) {
-    if (e == nullptr) return fail(RZ_ERR_ARG, "engine handle is NULL");
-    int cur = -1;
-    RZ_HIP(hipGetDevice(&cur));
-    if (cur != e->cfg.device) RZ_HIP(hipSetDevice(e->cfg.device));
-    return RZ_OK;
+int eng_ready(rz_engine *e) {
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "engine handle is NULL");
+    return rz_on_device(e->cfg.device);
 }
 
 inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
+inline dim3 per_game(const rz_engine *e) { return dim3((unsigned)e->cfg.n_games); }
+inline dim3 per_leaf(const rz_engine *e) { return dim3((unsigned)(e->cfg.n_games * e->dev.K)); }
+inline dim3 flat_grid(const rz_engine *e) { return dim3((unsigned)((e->cfg.n_games + 255) / 256)); }
 
-int launched(const char *what) {
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(RZ_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(err));
-    return RZ_OK;
+// sims_in_flight > 1: every step-by-step route is one launch of the in-flight tree step -- the level-synchronous kernel, or its sequential
+// restatement (rz_config::in_flight_impl); kb / ks: the slots it backs up / selects, 0 for a route that does only the other half
+template <bool RAW>
+int launch_in_flight(rz_engine *e, const float *logp, const float *value, const RawHeads &rh, float *obs, int kb, int ks, void *stream) {
+    if (e->ml) k_tree_step_ml<RAW><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, logp, value, rh, obs, kb, ks);
+    else k_tree_step_vl<RAW><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, logp, value, rh, obs, kb, ks);
+    return rz_launched("k_tree_step_vl");
 }
 
 }  // namespace
@@ -1650,14 +1623,14 @@ const char *rz_source_hash(void) {
 const char *rz_last_error(void) { return g_err; }
 
 int rz_create(const rz_config *cfg, rz_engine **out) {
-    if (cfg == nullptr || out == nullptr) return fail(RZ_ERR_ARG, "cfg/out is NULL");
+    if (cfg == nullptr || out == nullptr) return rz_fail(RZ_ERR_ARG, "cfg/out is NULL");
     *out = nullptr;
     if (cfg->abi_version != RZ_ABI_VERSION)
-        return fail(RZ_ERR_ARG, "abi_version %d != library %d", cfg->abi_version, RZ_ABI_VERSION);
+        return rz_fail(RZ_ERR_ARG, "abi_version %d != library %d", cfg->abi_version, RZ_ABI_VERSION);
     int BH, BW, A, n_row = cfg->n_in_row;
     if (cfg->game_kind == RZ_GAME_GOMOKU) {
         if (cfg->board_size < 1 || cfg->board_size > RZ_MAX_BOARD_SIZE)
-            return fail(RZ_ERR_ARG, "board_size %d not in 1..%d", cfg->board_size, RZ_MAX_BOARD_SIZE);
+            return rz_fail(RZ_ERR_ARG, "board_size %d not in 1..%d", cfg->board_size, RZ_MAX_BOARD_SIZE);
         BH = BW = cfg->board_size;
         A = BH * BW;
     } else if (cfg->game_kind == RZ_GAME_CONNECT4) {
@@ -1665,28 +1638,28 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
         BW = cfg->board_width > 0 ? cfg->board_width : 7;
         if (n_row == 0) n_row = 4;
         if (BH > RZ_MAX_BOARD_SIZE || BW > RZ_MAX_BOARD_SIZE)
-            return fail(RZ_ERR_ARG, "board %dx%d exceeds %d", BH, BW, RZ_MAX_BOARD_SIZE);
+            return rz_fail(RZ_ERR_ARG, "board %dx%d exceeds %d", BH, BW, RZ_MAX_BOARD_SIZE);
         A = BW;
     } else {
-        return fail(RZ_ERR_ARG, "unknown game_kind %d", cfg->game_kind);
+        return rz_fail(RZ_ERR_ARG, "unknown game_kind %d", cfg->game_kind);
     }
-    if (n_row < 1 || (n_row > BH && n_row > BW)) return fail(RZ_ERR_ARG, "n_in_row %d does not fit the board", n_row);
-    if (cfg->n_games < 1) return fail(RZ_ERR_ARG, "n_games must be >= 1");
-    if (cfg->n_playout < 1) return fail(RZ_ERR_ARG, "n_playout must be >= 1");
+    if (n_row < 1 || (n_row > BH && n_row > BW)) return rz_fail(RZ_ERR_ARG, "n_in_row %d does not fit the board", n_row);
+    if (cfg->n_games < 1) return rz_fail(RZ_ERR_ARG, "n_games must be >= 1");
+    if (cfg->n_playout < 1) return rz_fail(RZ_ERR_ARG, "n_playout must be >= 1");
     if (cfg->score_mode != RZ_SCORE_UCT_REF && cfg->score_mode != RZ_SCORE_PUCT)
-        return fail(RZ_ERR_ARG, "unknown score_mode %d", cfg->score_mode);
-    if (!(cfg->c_puct >= 0.0)) return fail(RZ_ERR_ARG, "c_puct must be >= 0");
+        return rz_fail(RZ_ERR_ARG, "unknown score_mode %d", cfg->score_mode);
+    if (!(cfg->c_puct >= 0.0)) return rz_fail(RZ_ERR_ARG, "c_puct must be >= 0");
     if (cfg->sims_in_flight < 0 || cfg->sims_in_flight > RZ_MAX_IN_FLIGHT)
-        return fail(RZ_ERR_ARG, "sims_in_flight %d not in 0..%d", cfg->sims_in_flight, RZ_MAX_IN_FLIGHT);
-    if (cfg->in_flight_impl != 0 && cfg->in_flight_impl != 1) return fail(RZ_ERR_ARG, "unknown in_flight_impl %d", cfg->in_flight_impl);
+        return rz_fail(RZ_ERR_ARG, "sims_in_flight %d not in 0..%d", cfg->sims_in_flight, RZ_MAX_IN_FLIGHT);
+    if (cfg->in_flight_impl != 0 && cfg->in_flight_impl != 1) return rz_fail(RZ_ERR_ARG, "unknown in_flight_impl %d", cfg->in_flight_impl);
     int n_dev = 0;
     RZ_HIP(hipGetDeviceCount(&n_dev));
     if (cfg->device < 0 || cfg->device >= n_dev)
-        return fail(RZ_ERR_ARG, "device %d not in 0..%d", cfg->device, n_dev - 1);
+        return rz_fail(RZ_ERR_ARG, "device %d not in 0..%d", cfg->device, n_dev - 1);
     RZ_HIP(hipSetDevice(cfg->device));
 
     rz_engine *e = new (std::nothrow) rz_engine();
-    if (e == nullptr) return fail(RZ_ERR_OOM, "host allocation failed");
+    if (e == nullptr) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     e->cfg = *cfg;
     Dev &D = e->dev;
     memset(&D, 0, sizeof(D));
@@ -1711,7 +1684,7 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
         if (e->ml_lds > 160 * 1024) {
             const int need = e->ml_lds;
             delete e;
-            return fail(RZ_ERR_ARG, "sims_in_flight %d x %d actions needs %d bytes of LDS (> 160 KB)", cfg->sims_in_flight, A, need);
+            return rz_fail(RZ_ERR_ARG, "sims_in_flight %d x %d actions needs %d bytes of LDS (> 160 KB)", cfg->sims_in_flight, A, need);
         }
         // the attribute belongs to the kernel, not to this engine: set to the hardware's 160 KB once and for all, so that a
         // later engine with a smaller K x A cannot lower it under an earlier, larger one
@@ -1720,7 +1693,7 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
         hipError_t a2 = hipFuncSetAttribute((const void *)k_tree_step_ml<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
         if (a1 != hipSuccess || a2 != hipSuccess) {
             delete e;
-            return fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS %d bytes) failed", most);
+            return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS %d bytes) failed", most);
         }
     }
     D.score_mode = cfg->score_mode;
@@ -1746,11 +1719,11 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
     if (D.cap >= (1ll << 30) || D.pcap >= (1ll << 31))
     {
         delete e;
-        return fail(RZ_ERR_ARG, "n_playout %d is too large for 32-bit slot indices", cfg->n_playout);
+        return rz_fail(RZ_ERR_ARG, "n_playout %d is too large for 32-bit slot indices", cfg->n_playout);
     }
     int rc = RZ_OK;
 #define RZ_ALLOC(field, count)                               \
-    if (rc == RZ_OK) rc = dev_alloc(e, &D.field, (count))
+    if (rc == RZ_OK) rc = e->pool.alloc(&D.field, (count))
     RZ_ALLOC(R, slots * 2);
     RZ_ALLOC(P, G * 2 * D.pcap);
     RZ_ALLOC(cur_arena, G);
@@ -1776,8 +1749,8 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
     RZ_ALLOC(reuse_drops, 1);
     RZ_ALLOC(noise_ctr, G);
     RZ_ALLOC(noise_key, G);
-    if (rc == RZ_OK) rc = dev_alloc(e, &e->d_logtab, D.logtab_n);
-    if (rc == RZ_OK) rc = dev_alloc(e, &e->d_line_tab, 2 * kWave);
+    if (rc == RZ_OK) rc = e->pool.alloc(&e->d_logtab, D.logtab_n);
+    if (rc == RZ_OK) rc = e->pool.alloc(&e->d_line_tab, 2 * kWave);
 #undef RZ_ALLOC
     if (rc != RZ_OK) {
         rz_destroy(e);
@@ -1799,7 +1772,7 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
     if (herr == hipSuccess) herr = hipMemset(D.active, 1, G);
     if (herr != hipSuccess) {
         rz_destroy(e);
-        return fail(RZ_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(herr));
+        return rz_fail(RZ_ERR_HIP, "hipMemset failed: %s", hipGetErrorString(herr));
     }
     {
         std::vector<double> tab((size_t)D.logtab_n);
@@ -1808,7 +1781,7 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
         herr = hipMemcpy(e->d_logtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
         if (herr != hipSuccess) {
             rz_destroy(e);
-            return fail(RZ_ERR_HIP, "hipMemcpy(log table) failed: %s", hipGetErrorString(herr));
+            return rz_fail(RZ_ERR_HIP, "hipMemcpy(log table) failed: %s", hipGetErrorString(herr));
         }
     }
     {   // Dev::line_tab: the window of lane l -- bits j * stride of its n cells (boards of up to 128 cells: a low word [l] and a high word
@@ -1828,23 +1801,23 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
         herr = hipMemcpy(e->d_line_tab, tab, sizeof(tab), hipMemcpyHostToDevice);
         if (herr != hipSuccess) {
             rz_destroy(e);
-            return fail(RZ_ERR_HIP, "hipMemcpy(line table) failed: %s", hipGetErrorString(herr));
+            return rz_fail(RZ_ERR_HIP, "hipMemcpy(line table) failed: %s", hipGetErrorString(herr));
         }
     }
     {   // fresh trees
         std::vector<int32_t> mv((size_t)G, -1);
-        int32_t *d_mv = nullptr;
-        herr = hipMalloc((void **)&d_mv, G * 4);
+        DevBuf<int32_t> d_mv;
+        herr = d_mv.alloc(G * 4) ? hipSuccess : hipErrorOutOfMemory;
         if (herr == hipSuccess) herr = hipMemcpy(d_mv, mv.data(), G * 4, hipMemcpyHostToDevice);
         if (herr == hipSuccess) {
             k_advance<<<dim3((unsigned)G), dim3(kWave), 0, 0>>>(D, d_mv);
             k_set_noise_keys<<<dim3((unsigned)((G + 255) / 256)), dim3(256), 0, 0>>>(D, nullptr, nullptr);   // the default keys
             herr = hipDeviceSynchronize();
         }
-        if (d_mv) (void)hipFree(d_mv);
+        d_mv.release();
         if (herr != hipSuccess) {
             rz_destroy(e);
-            return fail(RZ_ERR_HIP, "tree initialisation failed: %s", hipGetErrorString(herr));
+            return rz_fail(RZ_ERR_HIP, "tree initialisation failed: %s", hipGetErrorString(herr));
         }
     }
     *out = e;
@@ -1855,13 +1828,12 @@ int rz_destroy(rz_engine *e) {
     if (e == nullptr) return RZ_OK;
     (void)hipSetDevice(e->cfg.device);
     (void)hipDeviceSynchronize();
-    for (void *p : e->allocs) (void)hipFree(p);
-    delete e;
+    delete e;   // (the pool frees)
     return RZ_OK;
 }
 
 int rz_geometry(rz_engine *e, int32_t *height, int32_t *width, int32_t *n_actions) {
-    if (e == nullptr) return fail(RZ_ERR_ARG, "engine handle is NULL");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "engine handle is NULL");
     if (height) *height = e->dev.BH;
     if (width) *width = e->dev.BW;
     if (n_actions) *n_actions = e->dev.A;
@@ -1869,9 +1841,8 @@ int rz_geometry(rz_engine *e, int32_t *height, int32_t *width, int32_t *n_action
 }
 
 int rz_upload_log_table(rz_engine *e, const double *h_table, int64_t count) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (h_table == nullptr || count < 2) return fail(RZ_ERR_ARG, "table is NULL or too short");
+    RZ_ENTER(eng_ready, e);
+    if (h_table == nullptr || count < 2) return rz_fail(RZ_ERR_ARG, "table is NULL or too short");
     if (count > e->dev.logtab_n) count = e->dev.logtab_n;
     RZ_HIP(hipDeviceSynchronize());
     RZ_HIP(hipMemcpy(e->d_logtab, h_table, (size_t)count * sizeof(double), hipMemcpyHostToDevice));
@@ -1879,91 +1850,73 @@ int rz_upload_log_table(rz_engine *e, const double *h_table, int64_t count) {
 }
 
 int rz_log_table_size(rz_engine *e, int64_t *count) {
-    if (e == nullptr || count == nullptr) return fail(RZ_ERR_ARG, "NULL argument");
+    if (e == nullptr || count == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *count = e->dev.logtab_n;
     return RZ_OK;
 }
 
-#define RZ_ENTER(e)                      \
-    do {                                 \
-        int rc__ = check_engine(e);      \
-        if (rc__ != RZ_OK) return rc__;  \
-    } while (0)
 // an entry point of the move step: a valid engine that rz_play_attach has been called on
 #define RZ_ENTER_PLAY(e)                                                                  \
     do {                                                                                  \
-        RZ_ENTER(e);                                                                      \
-        if (!(e)->play_on) return fail(RZ_ERR_ARG, "call rz_play_attach first");          \
+        RZ_ENTER(eng_ready, e);                                                           \
+        if (!(e)->play_on) return rz_fail(RZ_ERR_ARG, "call rz_play_attach first");       \
     } while (0)
-#define RZ_NEED(p)                                                       \
-    do {                                                                 \
-        if ((p) == nullptr) return fail(RZ_ERR_ARG, "%s is NULL", #p);   \
-    } while (0)
-
 // per-game simulation counts exist in the resident search only (rz_net_search_resident): the step-by-step routes refuse them
 #define RZ_NO_PLAYOUTS(e)                                                                                                             \
     do {                                                                                                                              \
         if ((e)->pl_on || ((e)->play_on && (e)->play.cap_on))                                                                         \
-            return fail(RZ_ERR_ARG, "%s: per-game simulation counts (rz_set_playouts, rz_play_set_cap) are served by the resident "  \
-                                    "search only (rz_net_search_resident); clear them for this route", __func__);                    \
+            return rz_fail(RZ_ERR_ARG, "%s: per-game simulation counts (rz_set_playouts, rz_play_set_cap) are served by the "          \
+                                       "resident search only (rz_net_search_resident); clear them for this route", __func__);        \
     } while (0)
-
-static inline dim3 per_game(const rz_engine *e) { return dim3((unsigned)e->cfg.n_games); }
-static inline dim3 per_leaf(const rz_engine *e) { return dim3((unsigned)(e->cfg.n_games * e->dev.K)); }
-static inline dim3 flat_grid(const rz_engine *e) { return dim3((unsigned)((e->cfg.n_games + 255) / 256)); }
 
 int rz_set_roots(rz_engine *e, const uint64_t *d_stones, const int32_t *d_to_move,
                  const int32_t *d_last_move, const uint8_t *d_mask, int reset_trees, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_stones); RZ_NEED(d_to_move); RZ_NEED(d_last_move);
     k_set_roots<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_stones, d_to_move,
                                                                    d_last_move, d_mask, reset_trees);
-    return launched("k_set_roots");
+    return rz_launched("k_set_roots");
 }
 
 int rz_get_roots(rz_engine *e, uint64_t *d_stones, int32_t *d_to_move, int32_t *d_last_move,
                  void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_stones); RZ_NEED(d_to_move); RZ_NEED(d_last_move);
     k_get_roots<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_stones, d_to_move, d_last_move);
-    return launched("k_get_roots");
+    return rz_launched("k_get_roots");
 }
 
 int rz_set_active(rz_engine *e, const uint8_t *d_active, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     k_set_active<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_active);
-    return launched("k_set_active");
+    return rz_launched("k_set_active");
 }
 
 int rz_set_noise_keys(rz_engine *e, const uint64_t *d_keys, const uint8_t *d_mask, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     k_set_noise_keys<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_keys, d_mask);
-    return launched("k_set_noise_keys");
+    return rz_launched("k_set_noise_keys");
 }
 
 int rz_set_in_flight(rz_engine *e, int32_t k_backup, int32_t k_select) {
-    if (e == nullptr) return fail(RZ_ERR_ARG, "engine handle is NULL");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "engine handle is NULL");
     if (k_backup < 0 || k_backup > e->dev.K || k_select < 0 || k_select > e->dev.K)
-        return fail(RZ_ERR_ARG, "in-flight counts (%d, %d) not in 0..%d", k_backup, k_select, e->dev.K);
+        return rz_fail(RZ_ERR_ARG, "in-flight counts (%d, %d) not in 0..%d", k_backup, k_select, e->dev.K);
     e->kb = k_backup;
     e->ks = k_select;
     return RZ_OK;
 }
 
 int rz_select_step(rz_engine *e, float *d_obs, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     e->n_select += 1;
-    if (e->dev.K > 1) {
-        if (e->ml) k_tree_step_ml<false><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, nullptr, nullptr, RawHeads(), d_obs, 0, e->ks);
-        else k_tree_step_vl<false><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, nullptr, nullptr, RawHeads(), d_obs, 0, e->ks);
-        return launched("k_tree_step_vl");
-    }
+    if (e->dev.K > 1) return launch_in_flight<false>(e, nullptr, nullptr, RawHeads(), d_obs, 0, e->ks, stream);
     k_select<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_obs);
-    return launched("k_select");
+    return rz_launched("k_select");
 }
 
 int rz_leaf_buffers(rz_engine *e, const uint64_t **d_stones, const int32_t **d_to_move, const int32_t **d_last_cell) {
-    if (e == nullptr || !d_stones || !d_to_move || !d_last_cell) return fail(RZ_ERR_ARG, "NULL argument");
+    if (e == nullptr || !d_stones || !d_to_move || !d_last_cell) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *d_stones = e->dev.leaf_stones;
     *d_to_move = e->dev.leaf_to_move;
     *d_last_cell = e->dev.leaf_last;
@@ -1971,151 +1924,139 @@ int rz_leaf_buffers(rz_engine *e, const uint64_t **d_stones, const int32_t **d_t
 }
 
 int rz_encode_leaf_obs(rz_engine *e, float *d_obs, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_obs);
     k_encode<<<per_leaf(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, 0, d_obs);
-    return launched("k_encode");
+    return rz_launched("k_encode");
 }
 
 int rz_encode_root_obs(rz_engine *e, float *d_obs, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_obs);
     k_encode<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, 1, d_obs);
-    return launched("k_encode");
+    return rz_launched("k_encode");
 }
 
 int rz_get_leaves(rz_engine *e, uint64_t *d_stones, int32_t *d_to_move, int32_t *d_last_move,
                   int32_t *d_terminal, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_stones); RZ_NEED(d_to_move); RZ_NEED(d_last_move); RZ_NEED(d_terminal);
-    if (e->dev.K > 1) return fail(RZ_ERR_ARG, "rz_get_leaves serves host evaluators: not available with sims_in_flight > 1");
+    if (e->dev.K > 1) return rz_fail(RZ_ERR_ARG, "rz_get_leaves serves host evaluators: not available with sims_in_flight > 1");
     k_get_leaves<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_stones, d_to_move,
                                                                     d_last_move, d_terminal);
-    return launched("k_get_leaves");
+    return rz_launched("k_get_leaves");
 }
 
 int rz_eval_synthetic(rz_engine *e, int kind, float *d_logp, float *d_value, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_value);
-    if (kind != RZ_EVAL_V0 && kind != RZ_EVAL_VLIN) return fail(RZ_ERR_ARG, "unknown evaluator %d", kind);
+    if (kind != RZ_EVAL_V0 && kind != RZ_EVAL_VLIN) return rz_fail(RZ_ERR_ARG, "unknown evaluator %d", kind);
     k_eval_synth<<<per_leaf(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, kind, d_logp, d_value);
-    return launched("k_eval_synth");
+    return rz_launched("k_eval_synth");
 }
 
 int rz_eval_rollout(rz_engine *e, uint64_t seed, uint32_t sim_index, int32_t n_limit, float *d_value,
                     void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_value);
-    if (n_limit < 0) return fail(RZ_ERR_ARG, "n_limit must be >= 0");
+    if (n_limit < 0) return rz_fail(RZ_ERR_ARG, "n_limit must be >= 0");
     k_eval_rollout<<<per_leaf(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, seed, sim_index, n_limit, d_value);
-    return launched("k_eval_rollout");
+    return rz_launched("k_eval_rollout");
 }
 
 int rz_expand_backup(rz_engine *e, const float *d_logp, const float *d_value, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
-    if (e->dev.K > 1) {
-        if (e->ml) k_tree_step_ml<false><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, d_logp, d_value, RawHeads(), nullptr, e->kb, 0);
-        else k_tree_step_vl<false><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value, RawHeads(), nullptr, e->kb, 0);
-        return launched("k_tree_step_vl");
-    }
+    if (e->dev.K > 1) return launch_in_flight<false>(e, d_logp, d_value, RawHeads(), nullptr, e->kb, 0, stream);
     k_expand_backup<float><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value);
-    return launched("k_expand_backup");
+    return rz_launched("k_expand_backup");
 }
 
 int rz_expand_backup_f64(rz_engine *e, const float *d_logp, const double *d_value, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
-    if (e->dev.K > 1) return fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
+    if (e->dev.K > 1) return rz_fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
     k_expand_backup<double><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value);
-    return launched("k_expand_backup");
+    return rz_launched("k_expand_backup");
 }
 
 int rz_expand_backup_probs(rz_engine *e, const float *d_probs, const double *d_value, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
-    if (e->dev.K > 1) return fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
+    if (e->dev.K > 1) return rz_fail(RZ_ERR_ARG, "host evaluators are not available with sims_in_flight > 1");
     k_expand_backup<double, true><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_probs, d_value);
-    return launched("k_expand_backup");
+    return rz_launched("k_expand_backup");
 }
 
 int rz_tree_step(rz_engine *e, const float *d_logp, const float *d_value, float *d_obs, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
     RZ_NEED(d_value);
     e->n_select += 1;
-    if (e->dev.K > 1) {
-        if (e->ml) k_tree_step_ml<false><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, d_logp, d_value, RawHeads(), d_obs, e->kb, e->ks);
-        else k_tree_step_vl<false><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value, RawHeads(), d_obs, e->kb, e->ks);
-        return launched("k_tree_step_vl");
-    }
+    if (e->dev.K > 1) return launch_in_flight<false>(e, d_logp, d_value, RawHeads(), d_obs, e->kb, e->ks, stream);
     k_tree_step<float><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_logp, d_value, d_obs);
-    return launched("k_tree_step");
+    return rz_launched("k_tree_step");
 }
 
 static int raw_heads_ok(rz_engine *e, const rz_raw_heads *h) {
-    if (!h || !h->raw || !h->hid || !h->w2 || !h->b2) return fail(RZ_ERR_ARG, "NULL device pointer");
-    if (h->ld < e->dev.A) return fail(RZ_ERR_ARG, "ld %d < n_actions %d", h->ld, e->dev.A);
-    if (h->n_parts != 1 && h->n_parts != 4) return fail(RZ_ERR_ARG, "n_parts %d is neither 1 nor 4", h->n_parts);
+    if (!h || !h->raw || !h->hid || !h->w2 || !h->b2) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (h->ld < e->dev.A) return rz_fail(RZ_ERR_ARG, "ld %d < n_actions %d", h->ld, e->dev.A);
+    if (h->n_parts != 1 && h->n_parts != 4) return rz_fail(RZ_ERR_ARG, "n_parts %d is neither 1 nor 4", h->n_parts);
     if (h->n_parts == 4 && (!h->act_scale || !h->act_bias || !h->val_scale || !h->val_bias))
-        return fail(RZ_ERR_ARG, "partial sums need their scales and biases");
+        return rz_fail(RZ_ERR_ARG, "partial sums need their scales and biases");
     return RZ_OK;
 }
 
 int rz_expand_backup_raw(rz_engine *e, const rz_raw_heads *heads, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
-    int rc = raw_heads_ok(e, heads);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(raw_heads_ok(e, heads));
     const RawHeads rh = *heads;
-    if (e->dev.K > 1) {
-        if (e->ml) k_tree_step_ml<true><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, nullptr, nullptr, rh, nullptr, e->kb, 0);
-        else k_tree_step_vl<true><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, nullptr, nullptr, rh, nullptr, e->kb, 0);
-        return launched("k_tree_step_vl");
-    }
+    if (e->dev.K > 1) return launch_in_flight<true>(e, nullptr, nullptr, rh, nullptr, e->kb, 0, stream);
     k_expand_backup_raw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, rh);
-    return launched("k_expand_backup_raw");
+    return rz_launched("k_expand_backup_raw");
 }
 
 static int deferred_ok(rz_engine *e, const rz_value_head *h) {
-    if (h == nullptr || !h->valfeat || !h->w1t || !h->b1 || !h->w2 || !h->b2) return fail(RZ_ERR_ARG, "rz_value_head: NULL pointer");
+    if (h == nullptr || !h->valfeat || !h->w1t || !h->b1 || !h->w2 || !h->b2) return rz_fail(RZ_ERR_ARG, "rz_value_head: NULL pointer");
     if ((h->groups != 16 && h->groups != 32 && h->groups != 64 && h->groups != 128) || h->ld != 4 * h->groups)
-        return fail(RZ_ERR_ARG, "rz_value_head: groups = %d must be 16, 32, 64 or 128 and ld = 4 * groups", h->groups);
+        return rz_fail(RZ_ERR_ARG, "rz_value_head: groups = %d must be 16, 32, 64 or 128 and ld = 4 * groups", h->groups);
     if (2 * e->dev.S > 4 * h->groups)   // (the kernels also size their bitboard arithmetic by it: words_of_per)
-        return fail(RZ_ERR_ARG, "rz_value_head: %d groups of 4 inputs do not hold the 2 x %d inputs of this board", h->groups, e->dev.S);
-    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+        return rz_fail(RZ_ERR_ARG, "rz_value_head: %d groups of 4 inputs do not hold the 2 x %d inputs of this board", h->groups, e->dev.S);
+    if (e->dev.pend_cap <= 0) return rz_fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
     return RZ_OK;
 }
 
 int rz_deferred_reserve(rz_engine *e, int32_t slots) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (slots < 1) return fail(RZ_ERR_ARG, "rz_deferred_reserve: slots must be positive");
+    RZ_ENTER(eng_ready, e);
+    if (slots < 1) return rz_fail(RZ_ERR_ARG, "rz_deferred_reserve: slots must be positive");
     if (e->cfg.score_mode != RZ_SCORE_UCT_REF || e->dev.K != 1)
-        return fail(RZ_ERR_ARG, "deferred priors need RZ_SCORE_UCT_REF (the rule that never reads a prior) and sims_in_flight == 1");
+        return rz_fail(RZ_ERR_ARG, "deferred priors need RZ_SCORE_UCT_REF (the rule that never reads a prior) and sims_in_flight == 1");
     if (slots <= e->dev.pend_cap) return RZ_OK;
     RZ_HIP(hipDeviceSynchronize());
     const long long G = e->cfg.n_games;
     // (the records of a smaller reservation stay allocated until rz_destroy: reservations grow once or twice in a process)
-    if ((rc = dev_alloc(e, &e->dev.pend_pb, (long long)slots * G)) != RZ_OK) return rc;
-    if ((rc = dev_alloc(e, &e->dev.pend_ctr, (long long)slots * G)) != RZ_OK) return rc;
-    if ((rc = dev_alloc(e, &e->dev.pend_lw, (long long)slots * G)) != RZ_OK) return rc;
-    if ((rc = dev_alloc(e, &e->dev.pend_stones, (long long)slots * G * 2 * kWords)) != RZ_OK) return rc;
+    RZ_TRY(e->pool.alloc(&e->dev.pend_pb, (long long)slots * G));
+    RZ_TRY(e->pool.alloc(&e->dev.pend_ctr, (long long)slots * G));
+    RZ_TRY(e->pool.alloc(&e->dev.pend_lw, (long long)slots * G));
+    RZ_TRY(e->pool.alloc(&e->dev.pend_stones, (long long)slots * G * 2 * kWords));
     if (e->dev.pend == nullptr) {
-        if ((rc = dev_alloc(e, &e->dev.pend, G)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&e->dev.pend, G));
     }
     RZ_HIP(hipMemset(e->dev.pend, 0, (size_t)G * sizeof(int32_t)));
     // the kept flush: a mask bit and a place in the row list per record, two counts per game
     Keep &kp = e->keep;
     kp.words = (slots + 63) / 64;
-    if ((rc = dev_alloc(e, &kp.mask, (long long)kp.words * G)) != RZ_OK) return rc;
-    if ((rc = dev_alloc(e, &kp.rows, (long long)slots * G)) != RZ_OK) return rc;
+    RZ_TRY(e->pool.alloc(&kp.mask, (long long)kp.words * G));
+    RZ_TRY(e->pool.alloc(&kp.rows, (long long)slots * G));
     if (kp.cnt == nullptr) {
-        if ((rc = dev_alloc(e, &kp.cnt, G)) != RZ_OK || (rc = dev_alloc(e, &kp.pcnt, G)) != RZ_OK) return rc;
-        if ((rc = dev_alloc(e, &kp.count, 1)) != RZ_OK || (rc = dev_alloc(e, &kp.stats, 2)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&kp.cnt, G));
+        RZ_TRY(e->pool.alloc(&kp.pcnt, G));
+        RZ_TRY(e->pool.alloc(&kp.count, 1));
+        RZ_TRY(e->pool.alloc(&kp.stats, 2));
         RZ_HIP(hipMemset(kp.stats, 0, 2 * sizeof(unsigned long long)));
     }
     RZ_HIP(hipMemset(kp.count, 0, sizeof(int32_t)));
@@ -2124,33 +2065,29 @@ int rz_deferred_reserve(rz_engine *e, int32_t slots) {
 }
 
 int rz_trace_attach(rz_engine *e, void *d_trace) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
     e->dev.trace = (unsigned long long *)d_trace;
     return RZ_OK;
 }
 
 int rz_device_view(rz_engine *e, void *out, int64_t out_bytes) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (out == nullptr || out_bytes != (int64_t)sizeof(Dev)) return fail(RZ_ERR_ARG, "rz_device_view: the caller's view is %lld bytes, the engine's %zu", (long long)out_bytes, sizeof(Dev));
+    RZ_ENTER(eng_ready, e);
+    if (out == nullptr || out_bytes != (int64_t)sizeof(Dev)) return rz_fail(RZ_ERR_ARG, "rz_device_view: the caller's view is %lld bytes, the engine's %zu", (long long)out_bytes, sizeof(Dev));
     memcpy(out, &e->dev, sizeof(Dev));
     return RZ_OK;
 }
 
 int rz_deferred_slots(rz_engine *e, const int32_t **d_slot_of_game) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (!d_slot_of_game) return fail(RZ_ERR_ARG, "NULL output pointer");
-    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    RZ_ENTER(eng_ready, e);
+    if (!d_slot_of_game) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
+    if (e->dev.pend_cap <= 0) return rz_fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
     *d_slot_of_game = e->dev.pend;
     return RZ_OK;
 }
 
 int rz_expand_backup_deferred(rz_engine *e, const rz_value_head *head, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if ((rc = deferred_ok(e, head)) != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
+    RZ_TRY(deferred_ok(e, head));
     RZ_NO_PLAYOUTS(e);
     const dim3 block(kWave * kDefWaves);
     switch (head->groups) {   // = 4 waves x 2 halves x PER
@@ -2159,19 +2096,18 @@ int rz_expand_backup_deferred(rz_engine *e, const rz_value_head *head, void *str
         case 64: k_expand_backup_def<8><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head); break;
         default: k_expand_backup_def<16><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head); break;
     }
-    return launched("k_expand_backup_def");
+    return rz_launched("k_expand_backup_def");
 }
 
 int rz_tree_step_deferred(rz_engine *e, const rz_value_head *head, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if ((rc = deferred_ok(e, head)) != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
+    RZ_TRY(deferred_ok(e, head));
     RZ_NO_PLAYOUTS(e);
     e->n_select += 1;
     const dim3 block(kWave * kDefWaves);
     if (e->dev.trace && head->groups == 128) {   // (the traced instantiation exists for the 15 x 15 board's head: rz_trace_attach)
         k_tree_step_def<16, true><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head, nullptr);
-        return launched("k_tree_step_def");
+        return rz_launched("k_tree_step_def");
     }
     switch (head->groups) {   // = 4 waves x 2 halves x PER
         case 16: k_tree_step_def<2, false><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head, nullptr); break;
@@ -2179,34 +2115,32 @@ int rz_tree_step_deferred(rz_engine *e, const rz_value_head *head, void *stream)
         case 64: k_tree_step_def<8, false><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head, nullptr); break;
         default: k_tree_step_def<16, false><<<per_game(e), block, 0, as_stream(stream)>>>(e->dev, *head, nullptr); break;
     }
-    return launched("k_tree_step_def");
+    return rz_launched("k_tree_step_def");
 }
 
 int rz_deferred_flush(rz_engine *e, const rz_deferred_logits *logits, int32_t n_slots, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
     if (e->dev.pend_cap <= 0 || n_slots <= 0) return RZ_OK;
-    if (!logits || !logits->raw) return fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
-    if (n_slots > e->dev.pend_cap) return fail(RZ_ERR_ARG, "more slots than rz_deferred_reserve()d");
-    if (logits->ld < e->dev.A || logits->rows_per_slot < e->cfg.n_games) return fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the batch");
+    if (!logits || !logits->raw) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
+    if (n_slots > e->dev.pend_cap) return rz_fail(RZ_ERR_ARG, "more slots than rz_deferred_reserve()d");
+    if (logits->ld < e->dev.A || logits->rows_per_slot < e->cfg.n_games) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the batch");
     k_deferred_priors<<<dim3((unsigned)e->cfg.n_games, (unsigned)n_slots), dim3(kWave), 0, as_stream(stream)>>>(
         e->dev, logits->raw, logits->ld, (long long)logits->rows_per_slot);
     // (between rz_play_draw and rz_play_apply the counters restart in k_play_apply: one launch less in the chain of a move)
     if (!(e->play_on && e->play_drawn)) k_deferred_reset<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev);
-    return launched("k_deferred_priors");
+    return rz_launched("k_deferred_priors");
 }
 
 static int keep_ok(rz_engine *e) {
-    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
-    if (!(e->play_on && e->play_drawn)) return fail(RZ_ERR_ARG, "the kept flush runs between rz_play_draw and rz_play_apply (the move decides what is kept)");
+    if (e->dev.pend_cap <= 0) return rz_fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    if (!(e->play_on && e->play_drawn)) return rz_fail(RZ_ERR_ARG, "the kept flush runs between rz_play_draw and rz_play_apply (the move decides what is kept)");
     return RZ_OK;
 }
 
 int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (!out) return fail(RZ_ERR_ARG, "NULL output pointer");
-    if ((rc = keep_ok(e)) != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_TRY(keep_ok(e));
     k_keep_mark<<<per_game(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play.keep, e->keep);
     k_keep_rows<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->keep);
     out->rows = e->keep.rows;
@@ -2214,14 +2148,13 @@ int rz_deferred_keep(rz_engine *e, rz_kept_rows *out, void *stream) {
     out->capacity = (int64_t)e->dev.pend_cap * e->cfg.n_games;
     out->n_games = e->cfg.n_games;
     out->reserved = 0;
-    return launched("k_keep_rows");
+    return rz_launched("k_keep_rows");
 }
 
 int rz_deferred_keep_all(rz_engine *e, rz_kept_rows *out, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (!out) return fail(RZ_ERR_ARG, "NULL output pointer");
-    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    RZ_ENTER(eng_ready, e);
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
+    if (e->dev.pend_cap <= 0) return rz_fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
     Keep all = e->keep;
     all.stats = nullptr;
     k_keep_mark<<<per_game(e), dim3(256), 0, as_stream(stream)>>>(e->dev, nullptr, all);
@@ -2231,36 +2164,33 @@ int rz_deferred_keep_all(rz_engine *e, rz_kept_rows *out, void *stream) {
     out->capacity = (int64_t)e->dev.pend_cap * e->cfg.n_games;
     out->n_games = e->cfg.n_games;
     out->reserved = 0;
-    return launched("k_keep_rows");
+    return rz_launched("k_keep_rows");
 }
 
 int rz_deferred_flush_rows(rz_engine *e, const rz_deferred_logits *logits, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (e->dev.pend_cap <= 0) return fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
-    if (!logits || !logits->raw) return fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
-    if (logits->ld < e->dev.A) return fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
+    RZ_ENTER(eng_ready, e);
+    if (e->dev.pend_cap <= 0) return rz_fail(RZ_ERR_ARG, "call rz_deferred_reserve first");
+    if (!logits || !logits->raw) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
+    if (logits->ld < e->dev.A) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
     k_deferred_priors_rows<<<dim3(2048), dim3(kWave), 0, as_stream(stream)>>>(e->dev, logits->raw, logits->ld, e->keep.rows, e->keep.count);
     // (between rz_play_draw and rz_play_apply the counters restart in k_play_apply, as in rz_deferred_flush)
     if (!(e->play_on && e->play_drawn)) k_deferred_reset<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev);
-    return launched("k_deferred_priors_rows");
+    return rz_launched("k_deferred_priors_rows");
 }
 
 int rz_deferred_flush_kept(rz_engine *e, const rz_deferred_logits *logits, void *stream) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if ((rc = keep_ok(e)) != RZ_OK) return rc;
-    if (!logits || !logits->raw) return fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
-    if (logits->ld < e->dev.A) return fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
+    RZ_ENTER(eng_ready, e);
+    RZ_TRY(keep_ok(e));
+    if (!logits || !logits->raw) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: NULL pointer");
+    if (logits->ld < e->dev.A) return rz_fail(RZ_ERR_ARG, "rz_deferred_logits: rows shorter than the policy");
     // (eight waves per CU of a large chip; the counters restart in k_play_apply)
     k_deferred_priors_rows<<<dim3(2048), dim3(kWave), 0, as_stream(stream)>>>(e->dev, logits->raw, logits->ld, e->keep.rows, e->keep.count);
-    return launched("k_deferred_priors_rows");
+    return rz_launched("k_deferred_priors_rows");
 }
 
 int rz_deferred_keep_stats(rz_engine *e, uint64_t *h_out2, int32_t reset) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (!h_out2) return fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_ENTER(eng_ready, e);
+    if (!h_out2) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     h_out2[0] = h_out2[1] = 0;
     if (!e->keep.stats) return RZ_OK;
     RZ_HIP(hipDeviceSynchronize());
@@ -2270,79 +2200,73 @@ int rz_deferred_keep_stats(rz_engine *e, uint64_t *h_out2, int32_t reset) {
 }
 
 int rz_tree_step_raw(rz_engine *e, const rz_raw_heads *heads, float *d_obs, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NO_PLAYOUTS(e);
-    int rc = raw_heads_ok(e, heads);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(raw_heads_ok(e, heads));
     e->n_select += 1;
     const RawHeads rh = *heads;
-    if (e->dev.K > 1) {
-        if (e->ml) k_tree_step_ml<true><<<per_game(e), dim3(kWave * e->dev.K), e->ml_lds, as_stream(stream)>>>(e->dev, nullptr, nullptr, rh, d_obs, e->kb, e->ks);
-        else k_tree_step_vl<true><<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, nullptr, nullptr, rh, d_obs, e->kb, e->ks);
-        return launched("k_tree_step_vl");
-    }
+    if (e->dev.K > 1) return launch_in_flight<true>(e, nullptr, nullptr, rh, d_obs, e->kb, e->ks, stream);
     k_tree_step_raw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, rh, d_obs);
-    return launched("k_tree_step_raw");
+    return rz_launched("k_tree_step_raw");
 }
 
 int rz_root_visits(rz_engine *e, int32_t *d_visits, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_visits);
     k_root_children<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, 0, d_visits);
-    return launched("k_root_children");
+    return rz_launched("k_root_children");
 }
 
 int rz_root_wsum(rz_engine *e, double *d_w, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_w);
     k_root_children<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, 1, d_w);
-    return launched("k_root_children");
+    return rz_launched("k_root_children");
 }
 
 int rz_root_priors(rz_engine *e, float *d_p, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_p);
     k_root_children<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, 2, d_p);
-    return launched("k_root_children");
+    return rz_launched("k_root_children");
 }
 
 int rz_root_stats(rz_engine *e, int32_t *d_n, double *d_w, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_n); RZ_NEED(d_w);
     k_root_stats<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, d_n, d_w);
-    return launched("k_root_stats");
+    return rz_launched("k_root_stats");
 }
 
 int rz_root_values(rz_engine *e, double *d_out, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_out);
     k_root_values<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_out);
-    return launched("k_root_values");
+    return rz_launched("k_root_values");
 }
 
 int rz_advance_roots(rz_engine *e, const int32_t *d_moves, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_moves);
     k_advance<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_moves);
-    return launched("k_advance");
+    return rz_launched("k_advance");
 }
 
 int rz_step_games(rz_engine *e, const int32_t *d_moves, int32_t *d_winner, uint8_t *d_ended, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_moves);
     k_step_games<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, d_moves, d_winner, d_ended);
-    return launched("k_step_games");
+    return rz_launched("k_step_games");
 }
 
 // ------------------------------------------------------------------ the move step on the device
 int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(cfg);
-    if (e->dev.K != 1) return fail(RZ_ERR_ARG, "rz_play_attach: one simulation in flight per tree only");
-    if (!cfg->d_queue_ids || !cfg->d_queue_ctl || !cfg->d_log || cfg->ring_steps < 2) return fail(RZ_ERR_ARG, "rz_play_attach: queue, log and a ring of >= 2 steps are needed");
-    if (!(cfg->temperature > 0.0)) return fail(RZ_ERR_ARG, "rz_play_attach: temperature must be positive");
-    if (cfg->stall_margin < 0.0 || cfg->stall_margin >= 0.5) return fail(RZ_ERR_ARG, "rz_play_attach: stall_margin not in [0, 0.5)");
+    if (e->dev.K != 1) return rz_fail(RZ_ERR_ARG, "rz_play_attach: one simulation in flight per tree only");
+    if (!cfg->d_queue_ids || !cfg->d_queue_ctl || !cfg->d_log || cfg->ring_steps < 2) return rz_fail(RZ_ERR_ARG, "rz_play_attach: queue, log and a ring of >= 2 steps are needed");
+    if (!(cfg->temperature > 0.0)) return rz_fail(RZ_ERR_ARG, "rz_play_attach: temperature must be positive");
+    if (cfg->stall_margin < 0.0 || cfg->stall_margin >= 0.5) return rz_fail(RZ_ERR_ARG, "rz_play_attach: stall_margin not in [0, 0.5)");
     RZ_HIP(hipDeviceSynchronize());
     Play &Y = e->play;
     const long long G = e->cfg.n_games;
@@ -2351,23 +2275,23 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
         e->play_seen = true;
     }
     // Every array once per engine: an attach that ran out of memory is retried array by array -- what an earlier call got stays.
-    if (Y.game_id == nullptr && (rc = dev_alloc(e, &Y.game_id, G)) != RZ_OK) return rc;
-    if (Y.ply == nullptr && (rc = dev_alloc(e, &Y.ply, G)) != RZ_OK) return rc;
-    if (Y.state == nullptr && (rc = dev_alloc(e, &Y.state, G)) != RZ_OK) return rc;
-    if (Y.mailbox == nullptr && (rc = dev_alloc(e, &Y.mailbox, G)) != RZ_OK) return rc;
-    if (Y.keep == nullptr && (rc = dev_alloc(e, &Y.keep, G)) != RZ_OK) return rc;
-    if (Y.stepm == nullptr && (rc = dev_alloc(e, &Y.stepm, G)) != RZ_OK) return rc;
-    if (Y.step_ab == nullptr && (rc = dev_alloc(e, &Y.step_ab, 2)) != RZ_OK) return rc;
-    if (Y.resign == nullptr && (rc = dev_alloc(e, &Y.resign, 2)) != RZ_OK) return rc;
-    if (Y.cap == nullptr && (rc = dev_alloc(e, &Y.cap, 2)) != RZ_OK) return rc;
-    if (Y.sims_of == nullptr && (rc = dev_alloc(e, &Y.sims_of, G)) != RZ_OK) return rc;
-    if (Y.order == nullptr && (rc = dev_alloc(e, &Y.order, G)) != RZ_OK) return rc;
+    if (Y.game_id == nullptr) RZ_TRY(e->pool.alloc(&Y.game_id, G));
+    if (Y.ply == nullptr) RZ_TRY(e->pool.alloc(&Y.ply, G));
+    if (Y.state == nullptr) RZ_TRY(e->pool.alloc(&Y.state, G));
+    if (Y.mailbox == nullptr) RZ_TRY(e->pool.alloc(&Y.mailbox, G));
+    if (Y.keep == nullptr) RZ_TRY(e->pool.alloc(&Y.keep, G));
+    if (Y.stepm == nullptr) RZ_TRY(e->pool.alloc(&Y.stepm, G));
+    if (Y.step_ab == nullptr) RZ_TRY(e->pool.alloc(&Y.step_ab, 2));
+    if (Y.resign == nullptr) RZ_TRY(e->pool.alloc(&Y.resign, 2));
+    if (Y.cap == nullptr) RZ_TRY(e->pool.alloc(&Y.cap, 2));
+    if (Y.sims_of == nullptr) RZ_TRY(e->pool.alloc(&Y.sims_of, G));
+    if (Y.order == nullptr) RZ_TRY(e->pool.alloc(&Y.order, G));
     if (Y.inv_t_of == nullptr) {
         double *tab = nullptr;
-        if ((rc = dev_alloc(e, &tab, 2 * e->dev.S)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&tab, 2 * e->dev.S));
         Y.inv_t_of = tab;
     }
-    if (Y.top_hwm == nullptr && (rc = dev_alloc(e, &Y.top_hwm, G)) != RZ_OK) return rc;
+    if (Y.top_hwm == nullptr) RZ_TRY(e->pool.alloc(&Y.top_hwm, G));
     Y.queue_ids = cfg->d_queue_ids;
     Y.queue_ctl = cfg->d_queue_ctl;
     Y.log = cfg->d_log;
@@ -2380,7 +2304,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
             void *dp = nullptr;
             if (hipHostGetDevicePointer(&dp, cfg->d_log, 0) != hipSuccess || dp == nullptr) {
                 (void)hipGetLastError();
-                return fail(RZ_ERR_ARG, "rz_play_attach: d_log is host memory that device %d cannot address (pass device memory)", e->cfg.device);
+                return rz_fail(RZ_ERR_ARG, "rz_play_attach: d_log is host memory that device %d cannot address (pass device memory)", e->cfg.device);
             }
             Y.log = static_cast<int32_t *>(dp);
         }
@@ -2411,7 +2335,7 @@ int rz_play_draw(rz_engine *e, void *stream) {
     RZ_ENTER_PLAY(e);
     k_play_draw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play);
     e->play_drawn = true;
-    return launched("k_play_draw");
+    return rz_launched("k_play_draw");
 }
 
 int rz_play_apply(rz_engine *e, void *stream) {
@@ -2423,28 +2347,28 @@ int rz_play_apply(rz_engine *e, void *stream) {
     if (Y.cap_on && e->cap_ordered) k_play_order<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(e->dev.active, Y.sims_of, Y.n_full, e->cfg.n_games, Y.order);
     e->play_drawn = false;
     e->play_steps += 1;
-    return launched("k_play_apply");
+    return rz_launched("k_play_apply");
 }
 
 int rz_play_set_resign(rz_engine *e, double threshold, double disabled_frac, void *stream) {
     RZ_ENTER_PLAY(e);
-    if (!(disabled_frac >= 0.0 && disabled_frac <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_resign: disabled_frac %g not in [0, 1]", disabled_frac);
-    if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_resign: a match is on (rz_play_set_match): its games are played to the end");
+    if (!(disabled_frac >= 0.0 && disabled_frac <= 1.0)) return rz_fail(RZ_ERR_ARG, "rz_play_set_resign: disabled_frac %g not in [0, 1]", disabled_frac);
+    if (e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_resign: a match is on (rz_play_set_match): its games are played to the end");
     k_play_set_resign<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play.resign, threshold, disabled_frac);
     e->play.resign_on = 1;
-    return launched("k_play_set_resign");
+    return rz_launched("k_play_set_resign");
 }
 
 int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, void *stream) {
     RZ_ENTER_PLAY(e);
     Play &Y = e->play;
     const int S = e->dev.S;
-    if (n < 0 || n > S) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: %d entries for a board of %d cells (a game has no more plies)", n, S);
-    if (n > 0 && h_temps == nullptr) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: NULL table");
-    if (Y.match_on) return fail(RZ_ERR_ARG, "rz_play_set_temperatures: a match is on (rz_play_set_match): its moves keep the temperature of rz_play_attach");
+    if (n < 0 || n > S) return rz_fail(RZ_ERR_ARG, "rz_play_set_temperatures: %d entries for a board of %d cells (a game has no more plies)", n, S);
+    if (n > 0 && h_temps == nullptr) return rz_fail(RZ_ERR_ARG, "rz_play_set_temperatures: NULL table");
+    if (Y.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_temperatures: a match is on (rz_play_set_match): its moves keep the temperature of rz_play_attach");
     for (int p = 0; p < n; ++p)
         if (!(std::isfinite(h_temps[p]) && h_temps[p] > 0.0))
-            return fail(RZ_ERR_ARG, "rz_play_set_temperatures: entry %d (%g) is not a finite positive temperature", p, h_temps[p]);
+            return rz_fail(RZ_ERR_ARG, "rz_play_set_temperatures: entry %d (%g) is not a finite positive temperature", p, h_temps[p]);
     // 1 / T on the host (the division of rz_play_attach), padded with the last entry; n == 0: the temperature of rz_play_attach.
     // Behind it each ply's stall margin by rz_play_attach's rule (rz_play.h: temp_entry).
     for (int base = 0; base < 2 * S; base += kTempChunk) {
@@ -2453,49 +2377,47 @@ int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, voi
         k_play_set_temps<<<dim3(1), dim3(kTempChunk), 0, as_stream(stream)>>>(const_cast<double *>(Y.inv_t_of), c, base, 2 * S);
     }
     Y.temp_on = 1;
-    return launched("k_play_set_temps");
+    return rz_launched("k_play_set_temps");
 }
 
 static int playouts_route_ok(rz_engine *e, const char *what) {
     if (e->dev.K != 1 || e->dev.score_mode != RZ_SCORE_UCT_REF)
-        return fail(RZ_ERR_ARG, "%s: per-game simulation counts need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)", what);
+        return rz_fail(RZ_ERR_ARG, "%s: per-game simulation counts need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)", what);
     return RZ_OK;
 }
 
 int rz_play_set_cap(rz_engine *e, int32_t n_fast, double p_full, void *stream) {
     RZ_ENTER_PLAY(e);
-    int rc = playouts_route_ok(e, "rz_play_set_cap");
-    if (rc != RZ_OK) return rc;
-    if (e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_set_cap: a match is on (rz_play_set_match): every search of it has n_playout simulations");
+    RZ_TRY(playouts_route_ok(e, "rz_play_set_cap"));
+    if (e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_cap: a match is on (rz_play_set_match): every search of it has n_playout simulations");
     if (!std::isnan(p_full)) {
-        if (!(p_full > 0.0 && p_full <= 1.0)) return fail(RZ_ERR_ARG, "rz_play_set_cap: p_full %g not in (0, 1]", p_full);
-        if (n_fast < 1 || n_fast > e->cfg.n_playout) return fail(RZ_ERR_ARG, "rz_play_set_cap: n_fast %d not in 1 .. n_playout = %d", n_fast, e->cfg.n_playout);
+        if (!(p_full > 0.0 && p_full <= 1.0)) return rz_fail(RZ_ERR_ARG, "rz_play_set_cap: p_full %g not in (0, 1]", p_full);
+        if (n_fast < 1 || n_fast > e->cfg.n_playout) return rz_fail(RZ_ERR_ARG, "rz_play_set_cap: n_fast %d not in 1 .. n_playout = %d", n_fast, e->cfg.n_playout);
     }
     const Play &Y = e->play;
     k_play_cap<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, Y, (double)n_fast, p_full);
     k_play_order<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(e->dev.active, Y.sims_of, Y.n_full, e->cfg.n_games, Y.order);
     e->play.cap_on = 1;
-    return launched("k_play_cap");
+    return rz_launched("k_play_cap");
 }
 
 int rz_play_set_cap_order(rz_engine *e, int32_t longest_first) {
-    if (e == nullptr) return fail(RZ_ERR_ARG, "engine handle is NULL");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "engine handle is NULL");
     e->cap_ordered = longest_first != 0;
     return RZ_OK;
 }
 
 int rz_set_playouts(rz_engine *e, const int32_t *d_counts, const int32_t *d_order, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     if (d_counts == nullptr) {
-        if (d_order != nullptr) return fail(RZ_ERR_ARG, "rz_set_playouts: an order without counts");
+        if (d_order != nullptr) return rz_fail(RZ_ERR_ARG, "rz_set_playouts: an order without counts");
         e->pl_on = e->pl_ordered = false;
         return RZ_OK;
     }
-    int rc = playouts_route_ok(e, "rz_set_playouts");
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(playouts_route_ok(e, "rz_set_playouts"));
     const long long G = e->cfg.n_games;
-    if (e->pl_counts == nullptr && (rc = dev_alloc(e, &e->pl_counts, G)) != RZ_OK) return rc;
-    if (e->pl_order == nullptr && (rc = dev_alloc(e, &e->pl_order, G)) != RZ_OK) return rc;
+    if (e->pl_counts == nullptr) RZ_TRY(e->pool.alloc(&e->pl_counts, G));
+    if (e->pl_order == nullptr) RZ_TRY(e->pool.alloc(&e->pl_order, G));
     RZ_HIP(hipMemcpyAsync(e->pl_counts, d_counts, (size_t)G * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
     if (d_order != nullptr) RZ_HIP(hipMemcpyAsync(e->pl_order, d_order, (size_t)G * 4, hipMemcpyDeviceToDevice, as_stream(stream)));
     e->pl_on = true;
@@ -2504,9 +2426,8 @@ int rz_set_playouts(rz_engine *e, const int32_t *d_counts, const int32_t *d_orde
 }
 
 int rz_playouts_view(rz_engine *e, const int32_t **d_counts, const int32_t **d_order) {
-    int rc = check_engine(e);
-    if (rc != RZ_OK) return rc;
-    if (!d_counts || !d_order) return fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_ENTER(eng_ready, e);
+    if (!d_counts || !d_order) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     *d_counts = *d_order = nullptr;
     if (e->pl_on) {   // the host's counts come before the device's rule
         *d_counts = e->pl_counts;
@@ -2519,11 +2440,10 @@ int rz_playouts_view(rz_engine *e, const int32_t **d_counts, const int32_t **d_o
 }
 
 int rz_playouts_read(rz_engine *e, int32_t *h_counts, int32_t *h_order, int32_t *h_source) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(h_source);
     const int32_t *dc = nullptr, *dor = nullptr;
-    int rc = rz_playouts_view(e, &dc, &dor);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(rz_playouts_view(e, &dc, &dor));
     RZ_HIP(hipDeviceSynchronize());
     const size_t G = (size_t)e->cfg.n_games;
     if (dc != nullptr && h_counts != nullptr) RZ_HIP(hipMemcpy(h_counts, dc, G * 4, hipMemcpyDeviceToHost));
@@ -2539,31 +2459,30 @@ int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t
     if (n_openings == 0) {   // off again: the slots' flags as k_play_apply leaves them
         if (Y.match_on) k_play_side<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, Y, -1);
         Y.match_on = 0;
-        return launched("k_play_side");
+        return rz_launched("k_play_side");
     }
-    if (n_openings < 0 || !d_open_stones || !d_open_to_move || !d_open_last) return fail(RZ_ERR_ARG, "rz_play_set_match: a table of n_openings >= 1 positions is needed");
-    if (e->cfg.add_noise) return fail(RZ_ERR_ARG, "rz_play_set_match: a match is played without Dirichlet noise (add_noise = 0)");
+    if (n_openings < 0 || !d_open_stones || !d_open_to_move || !d_open_last) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: a table of n_openings >= 1 positions is needed");
+    if (e->cfg.add_noise) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: a match is played without Dirichlet noise (add_noise = 0)");
     if (e->dev.K != 1 || e->dev.score_mode != RZ_SCORE_UCT_REF)
-        return fail(RZ_ERR_ARG, "rz_play_set_match: matches need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)");
-    if (Y.resign_on || Y.cap_on) return fail(RZ_ERR_ARG, "rz_play_set_match: resignation or a playout cap is set (attach again: a match has neither)");
-    if (Y.temp_on) return fail(RZ_ERR_ARG, "rz_play_set_match: a temperature schedule is set (attach again: a match keeps the temperature of rz_play_attach)");
+        return rz_fail(RZ_ERR_ARG, "rz_play_set_match: matches need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)");
+    if (Y.resign_on || Y.cap_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: resignation or a playout cap is set (attach again: a match has neither)");
+    if (Y.temp_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: a temperature schedule is set (attach again: a match keeps the temperature of rz_play_attach)");
     if (n_openings > e->open_cap) {   // (hipFree waits for the device: no launch still reads the old table)
         const void *old[3] = {Y.open_stones, Y.open_to_move, Y.open_last};
         for (const void *p : old) {
             if (p == nullptr) continue;
-            e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), const_cast<void *>(p)), e->allocs.end());
+            e->pool.ptrs.erase(std::remove(e->pool.ptrs.begin(), e->pool.ptrs.end(), const_cast<void *>(p)), e->pool.ptrs.end());
             RZ_HIP(hipFree(const_cast<void *>(p)));
         }
         Y.open_stones = nullptr, Y.open_to_move = Y.open_last = nullptr;
         e->open_cap = 0;
         uint64_t *st = nullptr;
         int32_t *tm = nullptr, *la = nullptr;
-        int rc = RZ_OK;
-        if ((rc = dev_alloc(e, &st, (long long)n_openings * 2 * kWords)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&st, (long long)n_openings * 2 * kWords));
         Y.open_stones = st;
-        if ((rc = dev_alloc(e, &tm, n_openings)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&tm, n_openings));
         Y.open_to_move = tm;
-        if ((rc = dev_alloc(e, &la, n_openings)) != RZ_OK) return rc;
+        RZ_TRY(e->pool.alloc(&la, n_openings));
         Y.open_last = la;
         e->open_cap = n_openings;
     }
@@ -2576,15 +2495,15 @@ int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t
 }
 
 int rz_play_side(rz_engine *e, int32_t side, void *stream) {
-    RZ_ENTER(e);
-    if (!e->play_on || !e->play.match_on) return fail(RZ_ERR_ARG, "rz_play_side: call rz_play_set_match first");
-    if (side != 0 && side != 1) return fail(RZ_ERR_ARG, "rz_play_side: side %d is neither 0 (network A) nor 1 (network B)", side);
+    RZ_ENTER(eng_ready, e);
+    if (!e->play_on || !e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_side: call rz_play_set_match first");
+    if (side != 0 && side != 1) return rz_fail(RZ_ERR_ARG, "rz_play_side: side %d is neither 0 (network A) nor 1 (network B)", side);
     k_play_side<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play, side);
-    return launched("k_play_side");
+    return rz_launched("k_play_side");
 }
 
 int rz_active_read(rz_engine *e, uint8_t *h_active) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(h_active);
     RZ_HIP(hipDeviceSynchronize());
     RZ_HIP(hipMemcpy(h_active, e->dev.active, (size_t)e->cfg.n_games, hipMemcpyDeviceToHost));
@@ -2593,15 +2512,15 @@ int rz_active_read(rz_engine *e, uint8_t *h_active) {
 
 int rz_play_resolve(rz_engine *e, int32_t slot, int32_t move, void *stream) {
     RZ_ENTER_PLAY(e);
-    if (slot < 0 || slot >= e->cfg.n_games || move < 0 || move >= e->dev.A) return fail(RZ_ERR_ARG, "rz_play_resolve: slot %d / move %d out of range", slot, move);
+    if (slot < 0 || slot >= e->cfg.n_games || move < 0 || move >= e->dev.A) return rz_fail(RZ_ERR_ARG, "rz_play_resolve: slot %d / move %d out of range", slot, move);
     k_play_resolve<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(e->play, slot, move);
-    return launched("k_play_resolve");
+    return rz_launched("k_play_resolve");
 }
 
 int rz_play_stop(rz_engine *e, void *stream) {
     RZ_ENTER_PLAY(e);
     k_play_stop<<<flat_grid(e), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play);
-    return launched("k_play_stop");
+    return rz_launched("k_play_stop");
 }
 
 int rz_play_state(rz_engine *e, int64_t *h_game_id, int32_t *h_ply, int32_t *h_state, int64_t *h_steps) {
@@ -2620,7 +2539,7 @@ int rz_play_state(rz_engine *e, int64_t *h_game_id, int32_t *h_ply, int32_t *h_s
 }
 
 int rz_get_stats(rz_engine *e, rz_stats *out) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(out);
     RZ_HIP(hipDeviceSynchronize());
     const size_t G = (size_t)e->cfg.n_games;
@@ -2647,14 +2566,14 @@ int rz_get_stats(rz_engine *e, rz_stats *out) {
     }
     out->arena_slots = e->dev.cap;
     out->prior_floats = e->dev.pcap;
-    out->device_bytes = e->bytes;
+    out->device_bytes = e->pool.bytes;
     out->n_select_calls = e->n_select;
     out->reuse_dropped = drops;
     return RZ_OK;
 }
 
 int rz_poll_errors(rz_engine *e, int32_t *h_flags, int32_t *h_reuse_dropped, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(h_flags);
     RZ_HIP(hipStreamSynchronize(as_stream(stream)));
     RZ_HIP(hipMemcpy(h_flags, e->dev.err_any, 4, hipMemcpyDeviceToHost));
@@ -2663,7 +2582,7 @@ int rz_poll_errors(rz_engine *e, int32_t *h_flags, int32_t *h_reuse_dropped, voi
 }
 
 int rz_clear_errors(rz_engine *e) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_HIP(hipDeviceSynchronize());
     RZ_HIP(hipMemset(e->dev.err, 0, (size_t)e->cfg.n_games * 4));
     RZ_HIP(hipMemset(e->dev.err_any, 0, 4));
@@ -2674,9 +2593,9 @@ int rz_clear_errors(rz_engine *e) {
 int rz_copy_arena(rz_engine *e, int32_t game, int64_t max_slots, int32_t *h_n, double *h_w,
                   int32_t *h_first_child, int32_t *h_n_visited, int32_t *h_n_children,
                   int32_t *h_prior_block, float *h_root_prior, int32_t *h_top) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(h_top);
-    if (game < 0 || game >= e->cfg.n_games) return fail(RZ_ERR_ARG, "game %d out of range", game);
+    if (game < 0 || game >= e->cfg.n_games) return rz_fail(RZ_ERR_ARG, "game %d out of range", game);
     RZ_HIP(hipDeviceSynchronize());
     int32_t arena = 0, top = 0;
     RZ_HIP(hipMemcpy(&arena, e->dev.cur_arena + game, 4, hipMemcpyDeviceToHost));
@@ -2701,9 +2620,9 @@ int rz_copy_arena(rz_engine *e, int32_t game, int64_t max_slots, int32_t *h_n, d
 }
 
 int rz_copy_priors(rz_engine *e, int32_t game, int64_t max_floats, float *h_priors, int32_t *h_count) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(h_count);
-    if (game < 0 || game >= e->cfg.n_games) return fail(RZ_ERR_ARG, "game %d out of range", game);
+    if (game < 0 || game >= e->cfg.n_games) return rz_fail(RZ_ERR_ARG, "game %d out of range", game);
     RZ_HIP(hipDeviceSynchronize());
     int32_t arena = 0, ptop = 0;
     RZ_HIP(hipMemcpy(&arena, e->dev.cur_arena + game, 4, hipMemcpyDeviceToHost));
@@ -2718,13 +2637,13 @@ int rz_copy_priors(rz_engine *e, int32_t game, int64_t max_floats, float *h_prio
 
 int rz_uct_scores(rz_engine *e, const double *d_w, const int32_t *d_n, const int32_t *d_np,
                   double c_puct, double *d_out, int64_t count, void *stream) {
-    RZ_ENTER(e);
+    RZ_ENTER(eng_ready, e);
     RZ_NEED(d_w); RZ_NEED(d_n); RZ_NEED(d_np); RZ_NEED(d_out);
     if (count <= 0) return RZ_OK;
     const unsigned blocks = (unsigned)((count + 255) / 256);
     k_uct_scores<<<dim3(blocks), dim3(256), 0, as_stream(stream)>>>(d_w, d_n, d_np, c_puct, e->d_logtab,
                                                                     e->dev.logtab_n, d_out, count);
-    return launched("k_uct_scores");
+    return rz_launched("k_uct_scores");
 }
 
 }  // extern "C"

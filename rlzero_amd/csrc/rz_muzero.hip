@@ -32,10 +32,9 @@
 #include <vector>
 
 #include "rlzero_hip.h"
+#include "rz_host.h"
 
 #pragma clang fp contract(off)
-
-void rz_set_error(const char *msg);  // rz_engine.hip
 
 namespace {
 
@@ -1376,18 +1375,12 @@ __global__ void k_mz_root_stats(MzDev E, int32_t *n, double *value_sum, double *
     if (vmax) vmax[g] = E.vmax[g];
 }
 
-int mz_fail(int code, const char *msg) {
-    rz_set_error(msg);
-    return code;
-}
-
 }  // namespace
 
 struct rz_muzero {
     rz_mz_config cfg;
     MzDev dev;
-    std::vector<void *> allocs;
-    long long bytes = 0;
+    DevPool pool;   // everything the handle owns on the device: the trees, the model, the representation
     MzModel model = {};          // rz_mz_load_model
     float *d_model = nullptr;    // one allocation behind the pointers above
     bool model_loaded = false, representation_loaded = false;
@@ -1399,29 +1392,11 @@ struct rz_muzero {
 
 namespace {
 
-template <typename T>
-int mz_alloc(rz_muzero *e, T **out, long long count) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)count * sizeof(T)) != hipSuccess) return mz_fail(RZ_ERR_OOM, "hipMalloc failed (muzero tree)");
-    e->allocs.push_back(p);
-    e->bytes += count * (long long)sizeof(T);
-    *out = (T *)p;
-    return RZ_OK;
-}
-
 inline dim3 mz_grid(const rz_muzero *e) { return dim3((unsigned)((e->cfg.n_games + 127) / 128)); }
 
 int mz_ready(rz_muzero *e) {
-    if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return mz_fail(RZ_ERR_HIP, "hipGetDevice failed");
-    if (cur != e->cfg.device && hipSetDevice(e->cfg.device) != hipSuccess) return mz_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    return RZ_OK;
-}
-
-int mz_launched(const char *what) {
-    if (hipGetLastError() != hipSuccess) return mz_fail(RZ_ERR_HIP, what);
-    return RZ_OK;
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    return rz_on_device(e->cfg.device);
 }
 
 }  // namespace
@@ -1429,18 +1404,18 @@ int mz_launched(const char *what) {
 extern "C" {
 
 int rz_mz_create(const rz_mz_config *cfg, rz_muzero **out) {
-    if (cfg == nullptr || out == nullptr) return mz_fail(RZ_ERR_ARG, "NULL argument");
+    if (cfg == nullptr || out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (cfg->abi_version != RZ_ABI_VERSION) return mz_fail(RZ_ERR_ARG, "rz_mz_config.abi_version does not match the library");
+    if (cfg->abi_version != RZ_ABI_VERSION) return rz_fail(RZ_ERR_ARG, "rz_mz_config.abi_version does not match the library");
     if (cfg->n_games < 1 || cfg->n_actions < 1 || cfg->n_actions > 64 || cfg->n_sims < 1)
-        return mz_fail(RZ_ERR_ARG, "n_games / n_actions (1..64) / n_sims out of range");
-    if (!(cfg->discount > 0.0) || !(cfg->pb_c_base > 0.0)) return mz_fail(RZ_ERR_ARG, "discount and pb_c_base must be > 0");
+        return rz_fail(RZ_ERR_ARG, "n_games / n_actions (1..64) / n_sims out of range");
+    if (!(cfg->discount > 0.0) || !(cfg->pb_c_base > 0.0)) return rz_fail(RZ_ERR_ARG, "discount and pb_c_base must be > 0");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || cfg->device < 0 || cfg->device >= n_dev)
-        return mz_fail(RZ_ERR_ARG, "bad device ordinal");
-    if (hipSetDevice(cfg->device) != hipSuccess) return mz_fail(RZ_ERR_HIP, "hipSetDevice failed");
+        return rz_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(cfg->device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     rz_muzero *e = new (std::nothrow) rz_muzero();
-    if (!e) return mz_fail(RZ_ERR_OOM, "host allocation failed");
+    if (!e) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     e->cfg = *cfg;
     if (hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || e->n_cus < 1) e->n_cus = 256;
     MzDev &D = e->dev;
@@ -1454,7 +1429,7 @@ int rz_mz_create(const rz_mz_config *cfg, rz_muzero **out) {
     const long long G = cfg->n_games, slots = G * D.cap;
     int rc = RZ_OK;
     double *d_log = nullptr;
-#define MZ_ALLOC(field, count) if (rc == RZ_OK) rc = mz_alloc(e, &D.field, (count))
+#define MZ_ALLOC(field, count) if (rc == RZ_OK) rc = e->pool.alloc(&D.field, (count))
     MZ_ALLOC(nodes, slots);
     MZ_ALLOC(top, G);
     MZ_ALLOC(depth, G);
@@ -1463,14 +1438,14 @@ int rz_mz_create(const rz_mz_config *cfg, rz_muzero **out) {
     MZ_ALLOC(vmax, G);
     MZ_ALLOC(err, 1);
 #undef MZ_ALLOC
-    if (rc == RZ_OK) rc = mz_alloc(e, &d_log, cfg->n_sims + 2);
+    if (rc == RZ_OK) rc = e->pool.alloc(&d_log, cfg->n_sims + 2);
     if (rc == RZ_OK) {
         std::vector<double> tab((size_t)cfg->n_sims + 2);
         for (int n = 0; n < cfg->n_sims + 2; ++n) tab[(size_t)n] = std::log(((double)n + cfg->pb_c_base + 1.0) / cfg->pb_c_base);
         if (hipMemcpy(d_log, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(D.err, 0, 4) != hipSuccess || hipMemset(D.nodes, 0xff, (size_t)slots * sizeof(MzNode)) != hipSuccess ||
             hipMemset(D.top, 0, (size_t)G * 4) != hipSuccess || hipMemset(D.depth, 0, (size_t)G * 4) != hipSuccess)
-            rc = mz_fail(RZ_ERR_HIP, "initialisation of the muzero tree failed");
+            rc = rz_fail(RZ_ERR_HIP, "initialisation of the muzero tree failed");
     }
     if (rc != RZ_OK) {
         rz_mz_destroy(e);
@@ -1485,71 +1460,63 @@ int rz_mz_destroy(rz_muzero *e) {
     if (e == nullptr) return RZ_OK;
     (void)hipSetDevice(e->cfg.device);
     (void)hipDeviceSynchronize();
-    for (void *p : e->allocs) (void)hipFree(p);
-    delete e;
+    delete e;   // (the pool frees)
     return RZ_OK;
 }
 
 int rz_mz_upload_log_table(rz_muzero *e, const double *h_table, int64_t count) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (h_table == nullptr || count != e->cfg.n_sims + 2) return mz_fail(RZ_ERR_ARG, "table must hold n_sims + 2 entries");
+    RZ_ENTER(mz_ready, e);
+    if (h_table == nullptr || count != e->cfg.n_sims + 2) return rz_fail(RZ_ERR_ARG, "table must hold n_sims + 2 entries");
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(const_cast<double *>(e->dev.pb_log), h_table, (size_t)count * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return mz_fail(RZ_ERR_HIP, "hipMemcpy(log table) failed");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(log table) failed");
     return RZ_OK;
 }
 
 int rz_mz_init_roots(rz_muzero *e, const float *d_probs, const double *d_noise, double noise_frac, const uint8_t *d_mask,
                      void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (d_probs == nullptr) return mz_fail(RZ_ERR_ARG, "d_probs is NULL");
+    RZ_ENTER(mz_ready, e);
+    if (d_probs == nullptr) return rz_fail(RZ_ERR_ARG, "d_probs is NULL");
     k_mz_init<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, d_probs, d_noise, noise_frac, d_mask);
-    return mz_launched("launch of k_mz_init failed");
+    return rz_launched("k_mz_init");
 }
 
 int rz_mz_select(rz_muzero *e, int32_t *d_parent, int32_t *d_action, int32_t *d_leaf, const uint8_t *d_mask, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (!d_parent || !d_action || !d_leaf) return mz_fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_ENTER(mz_ready, e);
+    if (!d_parent || !d_action || !d_leaf) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     k_mz_select<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, d_parent, d_action, d_leaf, d_mask);
-    return mz_launched("launch of k_mz_select failed");
+    return rz_launched("k_mz_select");
 }
 
 int rz_mz_expand_backup(rz_muzero *e, const float *d_reward, const float *d_probs, const float *d_value,
                         const uint8_t *d_mask, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (!d_reward || !d_probs || !d_value) return mz_fail(RZ_ERR_ARG, "NULL input pointer");
+    RZ_ENTER(mz_ready, e);
+    if (!d_reward || !d_probs || !d_value) return rz_fail(RZ_ERR_ARG, "NULL input pointer");
     k_mz_expand_backup<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, d_reward, d_probs, d_value, d_mask);
-    return mz_launched("launch of k_mz_expand_backup failed");
+    return rz_launched("k_mz_expand_backup");
 }
 
 int rz_mz_root_children(rz_muzero *e, int32_t what, void *d_out, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (d_out == nullptr || what < 0 || what > 3) return mz_fail(RZ_ERR_ARG, "bad argument");
+    RZ_ENTER(mz_ready, e);
+    if (d_out == nullptr || what < 0 || what > 3) return rz_fail(RZ_ERR_ARG, "bad argument");
     k_mz_root_children<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, what, d_out);
-    return mz_launched("launch of k_mz_root_children failed");
+    return rz_launched("k_mz_root_children");
 }
 
 int rz_mz_root_stats(rz_muzero *e, int32_t *d_n, double *d_value_sum, double *d_vmin, double *d_vmax, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(mz_ready, e);
     k_mz_root_stats<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, d_n, d_value_sum, d_vmin, d_vmax);
-    return mz_launched("launch of k_mz_root_stats failed");
+    return rz_launched("k_mz_root_stats");
 }
 
 int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (h_params == nullptr || n_params != 14) return mz_fail(RZ_ERR_ARG, "expected the 14 tensors of the dynamics / reward / prediction layers");
-    if (hidden != kMzH) return mz_fail(RZ_ERR_ARG, "the fused search is built for hidden size 64");
+    RZ_ENTER(mz_ready, e);
+    if (h_params == nullptr || n_params != 14) return rz_fail(RZ_ERR_ARG, "expected the 14 tensors of the dynamics / reward / prediction layers");
+    if (hidden != kMzH) return rz_fail(RZ_ERR_ARG, "the fused search is built for hidden size 64");
     const int A = e->cfg.n_actions;
-    if (A > kMzMaxA) return mz_fail(RZ_ERR_ARG, "the fused search handles up to 8 actions");
+    if (A > kMzMaxA) return rz_fail(RZ_ERR_ARG, "the fused search handles up to 8 actions");
     for (int i = 0; i < 14; ++i)
-        if (!h_params[i]) return mz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
+        if (!h_params[i]) return rz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
     const int KX = kMzH + A;
     // order: dyn1.w [H][H+A], dyn1.b, dyn2.w [H][H], dyn2.b, rew1.w, rew1.b, rew2.w [1][H], rew2.b, pre1.w, pre1.b,
     //        pol.w [A][H], pol.b, val.w [1][H], val.b (torch layout [out][in]); big matrices go k-major [in][out]
@@ -1619,20 +1586,18 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
                 }
         e->f16_ok = finite;
     }
-    if (hipDeviceSynchronize() != hipSuccess) return mz_fail(RZ_ERR_HIP, "hipDeviceSynchronize failed");
+    RZ_HIP(hipDeviceSynchronize());
     if (e->d_model == nullptr) {
-        if (hipMalloc((void **)&e->d_model, total * sizeof(float)) != hipSuccess) return mz_fail(RZ_ERR_OOM, "hipMalloc failed (muzero model)");
-        e->allocs.push_back(e->d_model);
-        e->bytes += (long long)(total * sizeof(float));
+        RZ_TRY(e->pool.alloc(&e->d_model, (long long)total));
         const int most = 160 * 1024;
         if (hipFuncSetAttribute((const void *)k_mz_search<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_mz_search<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_mz_search<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_mz_search<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
-            return mz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+            return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
     }
     if (hipMemcpy(e->d_model, host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return mz_fail(RZ_ERR_HIP, "hipMemcpy(model) failed");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(model) failed");
     const float *b = e->d_model;
     const MzModel seen = e->model;   // (the representation layers are loaded by their own call)
     e->model = MzModel{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], b + off[6], b + off[7],
@@ -1643,12 +1608,11 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
 }
 
 int rz_mz_load_representation(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t obs_dim, int32_t hidden) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (h_params == nullptr || n_params != 4) return mz_fail(RZ_ERR_ARG, "expected rep1.weight, rep1.bias, rep2.weight, rep2.bias");
-    if (hidden != kMzH || obs_dim < 1 || obs_dim > kMzObs) return mz_fail(RZ_ERR_ARG, "the fused moves are built for hidden size 64 and <= 8 observation features");
+    RZ_ENTER(mz_ready, e);
+    if (h_params == nullptr || n_params != 4) return rz_fail(RZ_ERR_ARG, "expected rep1.weight, rep1.bias, rep2.weight, rep2.bias");
+    if (hidden != kMzH || obs_dim < 1 || obs_dim > kMzObs) return rz_fail(RZ_ERR_ARG, "the fused moves are built for hidden size 64 and <= 8 observation features");
     for (int i = 0; i < 4; ++i)
-        if (!h_params[i]) return mz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
+        if (!h_params[i]) return rz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
     // rep1.w [64][obs_dim] -> k-major [8][64] (rows >= obs_dim zero), rep1.b, rep2.w [64][64] -> k-major, rep2.b
     const size_t off[4] = {0, (size_t)kMzObs * kMzH, (size_t)kMzObs * kMzH + kMzH, (size_t)kMzObs * kMzH + kMzH + (size_t)kMzH * kMzH};
     const size_t total = off[3] + kMzH;
@@ -1659,14 +1623,10 @@ int rz_mz_load_representation(rz_muzero *e, const float *const *h_params, int32_
         host[off[1] + o] = h_params[1][o];
         host[off[3] + o] = h_params[3][o];
     }
-    if (hipDeviceSynchronize() != hipSuccess) return mz_fail(RZ_ERR_HIP, "hipDeviceSynchronize failed");
-    if (e->d_rep == nullptr) {
-        if (hipMalloc((void **)&e->d_rep, total * sizeof(float)) != hipSuccess) return mz_fail(RZ_ERR_OOM, "hipMalloc failed (muzero representation)");
-        e->allocs.push_back(e->d_rep);
-        e->bytes += (long long)(total * sizeof(float));
-    }
+    RZ_HIP(hipDeviceSynchronize());
+    if (e->d_rep == nullptr) RZ_TRY(e->pool.alloc(&e->d_rep, (long long)total));
     if (hipMemcpy(e->d_rep, host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return mz_fail(RZ_ERR_HIP, "hipMemcpy(representation) failed");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(representation) failed");
     e->model.rep1_w = e->d_rep + off[0];
     e->model.rep1_b = e->d_rep + off[1];
     e->model.rep2_w = e->d_rep + off[2];
@@ -1700,7 +1660,7 @@ static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const
     const MzPlan plan = mz_search_plan(e, play != nullptr);
     const int gpw = plan.gpw, lds = plan.lds;
     const bool tree_lds = plan.tree_lds;
-    if (lds > 160 * 1024) return mz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    if (lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
     const dim3 grid((unsigned)((e->cfg.n_games + gpw - 1) / gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
     hipStream_t st = (hipStream_t)stream;
@@ -1711,42 +1671,40 @@ static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const
         if (tree_lds) k_mz_search<true, false><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, none);
         else k_mz_search<false, false><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, none);
     }
-    return mz_launched("launch of k_mz_search failed");
+    return rz_launched("k_mz_search");
 }
 
 int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace_parent, int32_t *d_trace_action,
                  int32_t *d_trace_leaf, float *d_trace_reward, float *d_trace_probs, float *d_trace_value, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (!e->model_loaded) return mz_fail(RZ_ERR_ARG, "rz_mz_load_model has not been called");
-    if (d_hidden == nullptr || n_sims < 1 || n_sims > e->cfg.n_sims) return mz_fail(RZ_ERR_ARG, "d_hidden is NULL or n_sims out of range");
+    RZ_ENTER(mz_ready, e);
+    if (!e->model_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model has not been called");
+    if (d_hidden == nullptr || n_sims < 1 || n_sims > e->cfg.n_sims) return rz_fail(RZ_ERR_ARG, "d_hidden is NULL or n_sims out of range");
     const bool any = d_trace_parent || d_trace_action || d_trace_leaf || d_trace_reward || d_trace_probs || d_trace_value;
     const bool all = d_trace_parent && d_trace_action && d_trace_leaf && d_trace_reward && d_trace_probs && d_trace_value;
-    if (any && !all) return mz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
+    if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
     const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
     return mz_launch_search(e, d_hidden, n_sims, T, nullptr, stream);
 }
 
 int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_cartpole_play *play, void *stream) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (!e->model_loaded || !e->representation_loaded) return mz_fail(RZ_ERR_ARG, "rz_mz_load_model and rz_mz_load_representation first");
-    if (e->cfg.n_actions != 2) return mz_fail(RZ_ERR_ARG, "CartPole has 2 actions");
+    RZ_ENTER(mz_ready, e);
+    if (!e->model_loaded || !e->representation_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model and rz_mz_load_representation first");
+    if (e->cfg.n_actions != 2) return rz_fail(RZ_ERR_ARG, "CartPole has 2 actions");
     if (!e->f16_ok)
-        return mz_fail(RZ_ERR_ARG, "the model has non-finite weights: whole moves run their layers on the f16 matrix pipe and need finite "
+        return rz_fail(RZ_ERR_ARG, "the model has non-finite weights: whole moves run their layers on the f16 matrix pipe and need finite "
                                    "bounds (use the move-by-move search, rz_mz_search / fused_moves=False)");
     if (d_hidden == nullptr || play == nullptr || n_sims < 1 || n_sims > e->cfg.n_sims || n_moves < 1)
-        return mz_fail(RZ_ERR_ARG, "NULL pointer or n_sims / n_moves out of range");
+        return rz_fail(RZ_ERR_ARG, "NULL pointer or n_sims / n_moves out of range");
     if (!play->d_state || !play->d_steps || !play->d_episode || !play->d_episode_start || !play->d_ring || !play->d_arena ||
         !play->d_counters || !play->d_entries)
-        return mz_fail(RZ_ERR_ARG, "NULL environment / history pointer");
+        return rz_fail(RZ_ERR_ARG, "NULL environment / history pointer");
     if (play->ring_steps < 500 + n_moves || play->arena_rows < 1 || play->max_entries < (int64_t)e->cfg.n_games * n_moves || play->first_step < 0)
-        return mz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (500 steps) + the launch, max_entries one entry per environment and move");
-    if (!(play->dirichlet_alpha > 0.0) || play->noise_frac < 0.0 || play->noise_frac > 1.0) return mz_fail(RZ_ERR_ARG, "dirichlet_alpha must be > 0, noise_frac in [0, 1]");
+        return rz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (500 steps) + the launch, max_entries one entry per environment and move");
+    if (!(play->dirichlet_alpha > 0.0) || play->noise_frac < 0.0 || play->noise_frac > 1.0) return rz_fail(RZ_ERR_ARG, "dirichlet_alpha must be > 0, noise_frac in [0, 1]");
     // mz_gamma floors a draw at 1e-30: P(Gamma(alpha, 1) < 1e-30) is 1.05e-3 at alpha 0.1 and 0.128 at 0.03, and a move whose draws are
     // ALL floored gets uniform noise where Dirichlet(alpha) is almost one-hot (tests/test_noise_streams_host.py states the figures)
     if (play->dirichlet_alpha < 0.1)
-        return mz_fail(RZ_ERR_ARG, "dirichlet_alpha must be >= 0.1: below it the root noise's float32 draws reach their 1e-30 floor too often");
+        return rz_fail(RZ_ERR_ARG, "dirichlet_alpha must be >= 0.1: below it the root noise's float32 draws reach their 1e-30 floor too often");
     MzPlay p = {};
     p.n_moves = n_moves;
     p.row = 4 + 4 + e->cfg.n_actions;
@@ -1774,16 +1732,16 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
 int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                      float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream) {
     if (!d_state || !d_steps || !d_episode || !d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated || n_envs < 1)
-        return mz_fail(RZ_ERR_ARG, "NULL pointer or n_envs < 1");
+        return rz_fail(RZ_ERR_ARG, "NULL pointer or n_envs < 1");
     k_cartpole_step<<<dim3((unsigned)((n_envs + 127) / 128)), dim3(128), 0, (hipStream_t)stream>>>(
         d_state, reinterpret_cast<long long *>(d_steps), reinterpret_cast<long long *>(d_episode),
         reinterpret_cast<const long long *>(d_actions), n_envs, seed, d_obs, d_reward, d_terminated, d_truncated);
-    return mz_launched("launch of k_cartpole_step failed");
+    return rz_launched("k_cartpole_step");
 }
 
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup) {
-    if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    if (games_per_workgroup < 0 || games_per_workgroup > kMzMaxGpw) return mz_fail(RZ_ERR_ARG, "games_per_workgroup must be 0 (auto) .. 16");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    if (games_per_workgroup < 0 || games_per_workgroup > kMzMaxGpw) return rz_fail(RZ_ERR_ARG, "games_per_workgroup must be 0 (auto) .. 16");
     e->games_per_wg = games_per_workgroup;
     return RZ_OK;
 }
@@ -1795,7 +1753,7 @@ int rz_mz_debug_profile(long long *h_out16) {
 #endif
 
 int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
-    if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
     const MzPlan plan = mz_search_plan(e, whole_moves != 0);
     if (games_per_workgroup) *games_per_workgroup = plan.gpw;
     if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
@@ -1804,31 +1762,29 @@ int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_work
 }
 
 int rz_mz_tree_nodes(rz_muzero *e, void *h_nodes, int32_t *h_top) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (h_nodes == nullptr || h_top == nullptr) return mz_fail(RZ_ERR_ARG, "h_nodes / h_top is NULL");
+    RZ_ENTER(mz_ready, e);
+    if (h_nodes == nullptr || h_top == nullptr) return rz_fail(RZ_ERR_ARG, "h_nodes / h_top is NULL");
     static_assert(sizeof(MzNode) == sizeof(rz_mz_node), "rz_mz_node is the device's node record");
     const size_t G = (size_t)e->cfg.n_games;
     if (hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(h_nodes, e->dev.nodes, G * (size_t)e->dev.cap * sizeof(MzNode), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(h_top, e->dev.top, G * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return mz_fail(RZ_ERR_HIP, "hipMemcpy(tree nodes) failed");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(tree nodes) failed");
     return RZ_OK;
 }
 
 int rz_mz_geometry(rz_muzero *e, int32_t *slots_per_game, int64_t *device_bytes) {
-    if (e == nullptr) return mz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
     if (slots_per_game) *slots_per_game = e->dev.cap;
-    if (device_bytes) *device_bytes = e->bytes;
+    if (device_bytes) *device_bytes = e->pool.bytes;
     return RZ_OK;
 }
 
 int rz_mz_error_flags(rz_muzero *e, int32_t *flags) {
-    int rc = mz_ready(e);
-    if (rc != RZ_OK) return rc;
-    if (flags == nullptr) return mz_fail(RZ_ERR_ARG, "flags is NULL");
+    RZ_ENTER(mz_ready, e);
+    if (flags == nullptr) return rz_fail(RZ_ERR_ARG, "flags is NULL");
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(flags, e->dev.err, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return mz_fail(RZ_ERR_HIP, "hipMemcpy(err) failed");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(err) failed");
     return RZ_OK;
 }
 

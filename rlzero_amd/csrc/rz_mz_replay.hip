@@ -22,9 +22,8 @@
 #include <vector>
 
 #include "rlzero_hip.h"
+#include "rz_host.h"
 #include "rz_mz_target.h"
-
-void rz_set_error(const char *msg);  // rz_engine.hip
 
 namespace {
 
@@ -369,11 +368,6 @@ __global__ __launch_bounds__(kThreads) void k_mzr_draw_prio(MzrDev R, MzrPrio P,
     prob[i] = (double)w / (double)total;
 }
 
-int mr_fail(int code, const char *msg) {
-    rz_set_error(msg);
-    return code;
-}
-
 }  // namespace
 
 struct rz_mz_replay {
@@ -383,13 +377,11 @@ struct rz_mz_replay {
     long long stored = 0;              // episodes ever stored: the ticket of rz_mz_replay_positions / rz_mz_replay_update
     std::vector<int32_t> lengths;      // [E] by slot: the host's copy of dev.length
     double *d_disc = nullptr;
-    // one staging pair (pinned host + device), reused: the host half after `copied`, the device half after `consumed`
-    void *h_stage = nullptr, *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    hipEvent_t copied = nullptr, consumed = nullptr;
-    bool in_flight = false;
+    DevPool pool;    // the store
+    Staging stage;   // what the host hands to a launch
     // prioritized replay (rz_mz_replay_enable_priorities): nothing of it exists until it is enabled
     MzrPrio prio = {};
+    DevPool prio_pool;
     bool prio_on = false;
     bool prio_stale = false;   // a slot was written since the prefixes were formed: the next prioritized draw refreshes first
 };
@@ -397,46 +389,10 @@ struct rz_mz_replay {
 namespace {
 
 int mr_ready(rz_mz_replay *r) {
-    if (r == nullptr) return mr_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipGetDevice failed");
-    if (cur != r->device && hipSetDevice(r->device) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    return RZ_OK;
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
+    return rz_on_device(r->device);
 }
 
-// the staging pair with room for `bytes`, its host half free to be written; `stream` waits for the device half's last reader
-int mr_stage(rz_mz_replay *r, size_t bytes, hipStream_t stream) {
-    if (r->in_flight && hipEventSynchronize(r->copied) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventSynchronize failed (MuZero replay staging)");
-    if (bytes > r->stage_bytes) {
-        if (r->in_flight && hipEventSynchronize(r->consumed) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventSynchronize failed (MuZero replay staging)");
-        r->in_flight = false;
-        if (r->h_stage) (void)hipHostFree(r->h_stage);
-        if (r->d_stage) (void)hipFree(r->d_stage);
-        r->h_stage = r->d_stage = nullptr;
-        r->stage_bytes = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc(&r->h_stage, want, hipHostMallocDefault) != hipSuccess) return mr_fail(RZ_ERR_OOM, "hipHostMalloc failed (MuZero replay staging)");
-        if (hipMalloc(&r->d_stage, want) != hipSuccess) return mr_fail(RZ_ERR_OOM, "hipMalloc failed (MuZero replay staging)");
-        r->stage_bytes = want;
-    }
-    if (r->in_flight && hipStreamWaitEvent(stream, r->consumed, 0) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipStreamWaitEvent failed (MuZero replay staging)");
-    return RZ_OK;
-}
-
-int mr_upload(rz_mz_replay *r, size_t bytes, hipStream_t stream) {
-    if (hipMemcpyAsync(r->d_stage, r->h_stage, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "staging copy failed (MuZero replay)");
-    if (hipEventRecord(r->copied, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventRecord failed (MuZero replay)");
-    return RZ_OK;
-}
-
-int mr_launched(rz_mz_replay *r, hipStream_t stream, const char *what) {
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, what);
-    if (hipEventRecord(r->consumed, stream) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipEventRecord failed (MuZero replay)");
-    r->in_flight = true;
-    return RZ_OK;
-}
-
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline long long mr_oldest(const rz_mz_replay *r) { return ((r->cursor - r->count) % r->dev.E + r->dev.E) % r->dev.E; }
 
 // The entry table of `n` episodes (empty ones skipped; of more than the capacity only the last E get a slot) in `table`; -> the
@@ -447,11 +403,11 @@ int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t
     const long long E = r->dev.E;
     long long kept = 0, next = 0;
     for (int32_t i = 0; i < n; ++i) {
-        if (h_lengths[i] < 0) return mr_fail(RZ_ERR_ARG, "an episode of negative length");
-        if (h_lengths[i] > r->dev.T) return mr_fail(RZ_ERR_ARG, "an episode is longer than max_episode_steps");
+        if (h_lengths[i] < 0) return rz_fail(RZ_ERR_ARG, "an episode of negative length");
+        if (h_lengths[i] > r->dev.T) return rz_fail(RZ_ERR_ARG, "an episode is longer than max_episode_steps");
         const long long first = h_first_rows ? h_first_rows[i] : next;
         if (h_lengths[i] > 0 && (first < 0 || first > 0x7fffffffLL || first + h_lengths[i] > n_rows))
-            return mr_fail(RZ_ERR_ARG, "an episode's rows lie outside the block");
+            return rz_fail(RZ_ERR_ARG, "an episode's rows lie outside the block");
         next = first + h_lengths[i];
         kept += h_lengths[i] > 0;
     }
@@ -482,9 +438,9 @@ void mr_commit(rz_mz_replay *r, const std::vector<int32_t> &table, long long kep
 }
 
 int mr_outputs(rz_mz_replay *r, int64_t n, const MzrOut &O) {
-    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
     if (n > 0 && (O.obs == nullptr || O.actions == nullptr || O.tv == nullptr || O.tr == nullptr || O.tp == nullptr || O.mask == nullptr))
-        return mr_fail(RZ_ERR_ARG, "NULL output buffer");
+        return rz_fail(RZ_ERR_ARG, "NULL output buffer");
     return RZ_OK;
 }
 
@@ -495,7 +451,7 @@ int mr_mark(rz_mz_replay *r, long long first, long long n, hipStream_t s) {
     if (!r->prio_on || n <= 0) return RZ_OK;
     if (n > r->dev.E) n = r->dev.E;
     hipLaunchKernelGGL(k_mzr_mark, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r->prio, r->dev.E, first, n);
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_mark launch failed");
+    RZ_TRY(rz_launched("k_mzr_mark"));
     r->prio_stale = true;
     return RZ_OK;
 }
@@ -511,7 +467,7 @@ int mr_refresh(rz_mz_replay *r, hipStream_t s) {
         const long long oldest = mr_oldest(r);
         hipLaunchKernelGGL(k_mzr_prio, dim3((unsigned)r->count), dim3(kThreads), 0, s, r->dev, r->prio, oldest, r->count);
         hipLaunchKernelGGL(k_mzr_scan, dim3(1), dim3(kScanThreads), 0, s, r->prio, r->dev.E, oldest, r->count);
-        if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_prio / k_mzr_scan launch failed");
+        RZ_TRY(rz_launched("k_mzr_prio / k_mzr_scan"));
     }
     r->prio_stale = false;
     return RZ_OK;
@@ -523,33 +479,34 @@ extern "C" {
 
 int rz_mz_replay_create(int32_t obs_dim, int32_t n_actions, int64_t capacity_episodes, int32_t max_episode_steps, int32_t unroll_steps,
                         int32_t td_steps, const double *h_disc, int32_t device, rz_mz_replay **out) {
-    if (out == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (obs_dim < 1 || obs_dim > RZ_MZR_MAX_OBS) return mr_fail(RZ_ERR_ARG, "obs_dim outside 1 .. 16");
-    if (n_actions < 1 || n_actions > RZ_MZR_MAX_ACTIONS) return mr_fail(RZ_ERR_ARG, "n_actions outside 1 .. 8");
-    if (unroll_steps < 1 || unroll_steps > RZ_MZR_MAX_UNROLL) return mr_fail(RZ_ERR_ARG, "unroll_steps outside 1 .. 16");
-    if (td_steps < 1 || td_steps > RZ_MZR_MAX_TD) return mr_fail(RZ_ERR_ARG, "td_steps outside 1 .. 64");
-    if (max_episode_steps < 1 || max_episode_steps > 65536) return mr_fail(RZ_ERR_ARG, "max_episode_steps outside 1 .. 65536");
+    if (obs_dim < 1 || obs_dim > RZ_MZR_MAX_OBS) return rz_fail(RZ_ERR_ARG, "obs_dim outside 1 .. 16");
+    if (n_actions < 1 || n_actions > RZ_MZR_MAX_ACTIONS) return rz_fail(RZ_ERR_ARG, "n_actions outside 1 .. 8");
+    if (unroll_steps < 1 || unroll_steps > RZ_MZR_MAX_UNROLL) return rz_fail(RZ_ERR_ARG, "unroll_steps outside 1 .. 16");
+    if (td_steps < 1 || td_steps > RZ_MZR_MAX_TD) return rz_fail(RZ_ERR_ARG, "td_steps outside 1 .. 64");
+    if (max_episode_steps < 1 || max_episode_steps > 65536) return rz_fail(RZ_ERR_ARG, "max_episode_steps outside 1 .. 65536");
     if (capacity_episodes < 1 || capacity_episodes > (1LL << 22) || capacity_episodes * max_episode_steps > (1LL << 30))
-        return mr_fail(RZ_ERR_ARG, "capacity_episodes outside 1 .. 2^22, or more than 2^30 steps in all");
-    if (h_disc == nullptr) return mr_fail(RZ_ERR_ARG, "NULL discount table");
+        return rz_fail(RZ_ERR_ARG, "capacity_episodes outside 1 .. 2^22, or more than 2^30 steps in all");
+    if (h_disc == nullptr) return rz_fail(RZ_ERR_ARG, "NULL discount table");
     int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return mr_fail(RZ_ERR_ARG, "bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return mr_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     rz_mz_replay *r = new (std::nothrow) rz_mz_replay();
-    if (!r) return mr_fail(RZ_ERR_OOM, "host allocation failed");
+    if (!r) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     r->device = device;
     MzrDev &R = r->dev;
     R.E = (int)capacity_episodes, R.T = max_episode_steps, R.D = obs_dim, R.A = n_actions, R.K = unroll_steps, R.td = td_steps;
     r->lengths.assign((size_t)R.E, 0);
     const size_t steps = (size_t)R.E * R.T, n_disc = (size_t)td_steps + 1;
-    bool ok = hipMalloc((void **)&R.obs, steps * R.D * sizeof(float)) == hipSuccess && hipMalloc((void **)&R.action, steps * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc((void **)&R.reward, steps * sizeof(double)) == hipSuccess && hipMalloc((void **)&R.root_value, steps * sizeof(double)) == hipSuccess &&
-              hipMalloc((void **)&R.policy, steps * R.A * sizeof(float)) == hipSuccess && hipMalloc((void **)&R.length, (size_t)R.E * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc((void **)&r->d_disc, n_disc * sizeof(double)) == hipSuccess && hipMalloc((void **)&R.err, sizeof(int32_t)) == hipSuccess;
+    const long long n_steps = (long long)steps;
+    DevPool &pool = r->pool;
+    bool ok = pool.alloc(&R.obs, n_steps * R.D) == RZ_OK && pool.alloc(&R.action, n_steps) == RZ_OK && pool.alloc(&R.reward, n_steps) == RZ_OK &&
+              pool.alloc(&R.root_value, n_steps) == RZ_OK && pool.alloc(&R.policy, n_steps * R.A) == RZ_OK && pool.alloc(&R.length, R.E) == RZ_OK &&
+              pool.alloc(&r->d_disc, (long long)n_disc) == RZ_OK && pool.alloc(&R.err, 1) == RZ_OK;
     if (!ok) {
         rz_mz_replay_destroy(r);
-        return mr_fail(RZ_ERR_OOM, "hipMalloc failed (MuZero replay store)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (MuZero replay store)");
     }
     R.disc = r->d_disc;
     ok = hipMemset(R.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(R.obs, 0, steps * R.D * sizeof(float)) == hipSuccess &&
@@ -557,11 +514,10 @@ int rz_mz_replay_create(int32_t obs_dim, int32_t n_actions, int64_t capacity_epi
          hipMemset(R.root_value, 0, steps * sizeof(double)) == hipSuccess && hipMemset(R.policy, 0, steps * R.A * sizeof(float)) == hipSuccess &&
          hipMemset(R.length, 0, (size_t)R.E * sizeof(int32_t)) == hipSuccess &&
          hipMemcpy(r->d_disc, h_disc, n_disc * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipEventCreateWithFlags(&r->copied, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&r->consumed, hipEventDisableTiming) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+         r->stage.create("MuZero replay") == RZ_OK && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         rz_mz_replay_destroy(r);
-        return mr_fail(RZ_ERR_HIP, "initialisation of the MuZero replay store failed");
+        return rz_fail(RZ_ERR_HIP, "initialisation of the MuZero replay store failed");
     }
     *out = r;
     return RZ_OK;
@@ -571,19 +527,13 @@ int rz_mz_replay_destroy(rz_mz_replay *r) {
     if (r == nullptr) return RZ_OK;
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
-    if (r->copied) (void)hipEventDestroy(r->copied);
-    if (r->consumed) (void)hipEventDestroy(r->consumed);
-    if (r->h_stage) (void)hipHostFree(r->h_stage);
-    void *dev[] = {r->d_stage, r->dev.obs, r->dev.action, r->dev.reward, r->dev.root_value, r->dev.policy, r->dev.length, r->d_disc, r->dev.err,
-                   r->prio.cum, r->prio.mass, r->prio.ecum, r->prio.total, r->prio.dirty};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    delete r;
+    r->stage.destroy();
+    delete r;   // (the pools free the store and the priority tables)
     return RZ_OK;
 }
 
 int rz_mz_replay_state(rz_mz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity, int32_t *h_lengths) {
-    if (r == nullptr) return mr_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
     if (count) *count = r->count;
     if (cursor) *cursor = r->cursor;
     if (capacity) *capacity = r->dev.E;
@@ -595,51 +545,46 @@ int rz_mz_replay_state(rz_mz_replay *r, int64_t *count, int64_t *cursor, int64_t
 }
 
 int rz_mz_replay_add(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int32_t *h_flags, const double *h_rows, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (n_episodes < 0) return mr_fail(RZ_ERR_ARG, "n_episodes < 0");
+    RZ_ENTER(mr_ready, r);
+    if (n_episodes < 0) return rz_fail(RZ_ERR_ARG, "n_episodes < 0");
     if (n_episodes == 0) return RZ_OK;
-    if (h_lengths == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_lengths == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     long long total = 0;
     for (int32_t i = 0; i < n_episodes; ++i) total += h_lengths[i] > 0 ? h_lengths[i] : 0;
-    if (total > 0x7fffffffLL) return mr_fail(RZ_ERR_ARG, "more than 2^31 - 1 rows in one call");
+    if (total > 0x7fffffffLL) return rz_fail(RZ_ERR_ARG, "more than 2^31 - 1 rows in one call");
     std::vector<int32_t> table;
     long long kept = 0;
     const int n = mr_table(r, n_episodes, h_lengths, h_flags, nullptr, total, table, &kept);
     if (n < 0) return n;
     if (kept == 0) return RZ_OK;
-    if (h_rows == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_rows == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     const int W = r->dev.D + 4 + r->dev.A;
     for (long long row = 0; row < total; ++row) {
         const double a = h_rows[row * W + r->dev.D];
-        if (!(a >= 0.0 && a < (double)r->dev.A && a == (double)(int)a)) return mr_fail(RZ_ERR_ARG, "an action is outside 0 .. A-1");
+        if (!(a >= 0.0 && a < (double)r->dev.A && a == (double)(int)a)) return rz_fail(RZ_ERR_ARG, "an action is outside 0 .. A-1");
     }
     // staging: entry table | rows
     const size_t o_rows = align16(table.size() * sizeof(int32_t)), bytes = o_rows + (size_t)total * W * sizeof(double);
     hipStream_t s = (hipStream_t)stream;
-    rc = mr_stage(r, bytes, s);
-    if (rc != RZ_OK) return rc;
-    char *h = (char *)r->h_stage, *d = (char *)r->d_stage;
+    RZ_TRY(r->stage.reserve(bytes, s));
+    char *h = (char *)r->stage.h, *d = (char *)r->stage.d;
     memcpy(h, table.data(), table.size() * sizeof(int32_t));
     memcpy(h + o_rows, h_rows, (size_t)total * W * sizeof(double));
-    rc = mr_upload(r, bytes, s);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.upload(bytes, s));
     hipLaunchKernelGGL(k_mzr_add, dim3((unsigned)n), dim3(kThreads), 0, s, r->dev, (const int32_t *)d, (const double *)(d + o_rows), total);
-    rc = mr_launched(r, s, "k_mzr_add launch failed");
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.launched(s, "k_mzr_add"));
     mr_commit(r, table, kept);
     return mr_mark_table(r, table, s);
 }
 
 int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_lengths, const int64_t *h_first_rows, const double *d_arena,
                         int64_t arena_rows, int32_t row_doubles, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (n_episodes < 0) return mr_fail(RZ_ERR_ARG, "n_episodes < 0");
+    RZ_ENTER(mr_ready, r);
+    if (n_episodes < 0) return rz_fail(RZ_ERR_ARG, "n_episodes < 0");
     if (n_episodes == 0) return RZ_OK;
-    if (h_lengths == nullptr || h_first_rows == nullptr || d_arena == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
-    if (row_doubles != r->dev.D + 4 + r->dev.A) return mr_fail(RZ_ERR_ARG, "the arena's rows are not obs_dim + 4 + n_actions doubles");
-    if (arena_rows < 0 || arena_rows > 0x7fffffffLL) return mr_fail(RZ_ERR_ARG, "arena_rows outside 0 .. 2^31 - 1");
+    if (h_lengths == nullptr || h_first_rows == nullptr || d_arena == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (row_doubles != r->dev.D + 4 + r->dev.A) return rz_fail(RZ_ERR_ARG, "the arena's rows are not obs_dim + 4 + n_actions doubles");
+    if (arena_rows < 0 || arena_rows > 0x7fffffffLL) return rz_fail(RZ_ERR_ARG, "arena_rows outside 0 .. 2^31 - 1");
     std::vector<int32_t> table;
     long long kept = 0;
     const int n = mr_table(r, n_episodes, h_lengths, nullptr, h_first_rows, arena_rows, table, &kept);
@@ -647,28 +592,23 @@ int rz_mz_replay_ingest(rz_mz_replay *r, int32_t n_episodes, const int32_t *h_le
     if (kept == 0) return RZ_OK;
     const size_t bytes = table.size() * sizeof(int32_t);
     hipStream_t s = (hipStream_t)stream;
-    rc = mr_stage(r, bytes, s);
-    if (rc != RZ_OK) return rc;
-    memcpy(r->h_stage, table.data(), bytes);
-    rc = mr_upload(r, bytes, s);
-    if (rc != RZ_OK) return rc;
-    hipLaunchKernelGGL(k_mzr_ingest, dim3((unsigned)n), dim3(kThreads), 0, s, r->dev, (const int32_t *)r->d_stage, d_arena, (long long)arena_rows);
-    rc = mr_launched(r, s, "k_mzr_ingest launch failed");
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.reserve(bytes, s));
+    memcpy(r->stage.h, table.data(), bytes);
+    RZ_TRY(r->stage.upload(bytes, s));
+    hipLaunchKernelGGL(k_mzr_ingest, dim3((unsigned)n), dim3(kThreads), 0, s, r->dev, (const int32_t *)r->stage.d, d_arena, (long long)arena_rows);
+    RZ_TRY(r->stage.launched(s, "k_mzr_ingest"));
     mr_commit(r, table, kept);
     return mr_mark_table(r, table, s);
 }
 
 int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv,
                         float *d_tr, float *d_tp, float *d_mask, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(mr_ready, r);
     const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
-    rc = mr_outputs(r, n, O);
-    if (rc != RZ_OK) return rc;
-    if ((h_draws == nullptr) == (d_draws == nullptr)) return mr_fail(RZ_ERR_ARG, "exactly one of h_draws / d_draws");
+    RZ_TRY(mr_outputs(r, n, O));
+    if ((h_draws == nullptr) == (d_draws == nullptr)) return rz_fail(RZ_ERR_ARG, "exactly one of h_draws / d_draws");
     if (n == 0) return RZ_OK;
-    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
     const long long oldest = mr_oldest(r);
     const long long *draws = (const long long *)d_draws;
@@ -676,93 +616,80 @@ int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *
     if (h_draws != nullptr) {
         for (int64_t i = 0; i < n; ++i) {
             const int64_t *dr = h_draws + i * (K + 2);
-            if (dr[0] < 0 || dr[0] >= r->count) return mr_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
-            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return mr_fail(RZ_ERR_ARG, "a position is outside its episode");
+            if (dr[0] < 0 || dr[0] >= r->count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
             for (int j = 0; j < K; ++j)
-                if (dr[2 + j] < 0 || dr[2 + j] >= r->dev.A) return mr_fail(RZ_ERR_ARG, "a filler action is outside 0 .. A-1");
+                if (dr[2 + j] < 0 || dr[2 + j] >= r->dev.A) return rz_fail(RZ_ERR_ARG, "a filler action is outside 0 .. A-1");
         }
         const size_t bytes = (size_t)n * (K + 2) * sizeof(int64_t);
-        rc = mr_stage(r, bytes, s);
-        if (rc != RZ_OK) return rc;
-        memcpy(r->h_stage, h_draws, bytes);
-        rc = mr_upload(r, bytes, s);
-        if (rc != RZ_OK) return rc;
-        draws = (const long long *)r->d_stage;
+        RZ_TRY(r->stage.reserve(bytes, s));
+        memcpy(r->stage.h, h_draws, bytes);
+        RZ_TRY(r->stage.upload(bytes, s));
+        draws = (const long long *)r->stage.d;
     }
     hipLaunchKernelGGL(k_mzr_gather, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
-    if (h_draws != nullptr) return mr_launched(r, s, "k_mzr_gather launch failed");
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_gather launch failed");
-    return RZ_OK;
+    return h_draws != nullptr ? r->stage.launched(s, "k_mzr_gather") : rz_launched("k_mzr_gather");
 }
 
 int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_obs, int64_t *d_actions, float *d_tv, float *d_tr,
                         float *d_tp, float *d_mask, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(mr_ready, r);
     const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
-    rc = mr_outputs(r, n, O);
-    if (rc != RZ_OK) return rc;
-    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    RZ_TRY(mr_outputs(r, n, O));
+    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     if (n == 0) return RZ_OK;
     hipLaunchKernelGGL(k_mzr_sample, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
                        (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_sample launch failed");
-    return RZ_OK;
+    return rz_launched("k_mzr_sample");
 }
 
 int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, uint64_t seed, uint64_t step, int64_t n,
                             int32_t *d_where, float *d_obs, int64_t *ticket, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
-    if (ticket == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
-    if (h_draws != nullptr && d_draws != nullptr) return mr_fail(RZ_ERR_ARG, "at most one of h_draws / d_draws");
+    RZ_ENTER(mr_ready, r);
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (ticket == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_draws != nullptr && d_draws != nullptr) return rz_fail(RZ_ERR_ARG, "at most one of h_draws / d_draws");
     *ticket = r->stored;
     if (n == 0) return RZ_OK;
-    if (d_where == nullptr || d_obs == nullptr) return mr_fail(RZ_ERR_ARG, "NULL output buffer");
-    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (d_where == nullptr || d_obs == nullptr) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
+    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
     const long long oldest = mr_oldest(r);
     const long long *draws = (const long long *)d_draws;
     if (h_draws != nullptr) {
         for (int64_t i = 0; i < n; ++i) {
             const int64_t *dr = h_draws + 2 * i;
-            if (dr[0] < 0 || dr[0] >= r->count) return mr_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
-            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return mr_fail(RZ_ERR_ARG, "a position is outside its episode");
+            if (dr[0] < 0 || dr[0] >= r->count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
         }
         const size_t bytes = (size_t)n * 2 * sizeof(int64_t);
-        rc = mr_stage(r, bytes, s);
-        if (rc != RZ_OK) return rc;
-        memcpy(r->h_stage, h_draws, bytes);
-        rc = mr_upload(r, bytes, s);
-        if (rc != RZ_OK) return rc;
-        draws = (const long long *)r->d_stage;
+        RZ_TRY(r->stage.reserve(bytes, s));
+        memcpy(r->stage.h, h_draws, bytes);
+        RZ_TRY(r->stage.upload(bytes, s));
+        draws = (const long long *)r->stage.d;
     }
     const unsigned blocks = (unsigned)((n * r->dev.D + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(k_mzr_positions, dim3(blocks), dim3(kThreads), 0, s, r->dev, draws, (unsigned long long)seed, (unsigned long long)step, oldest,
                        r->count, (long long)n, d_where, d_obs);
-    if (h_draws != nullptr) return mr_launched(r, s, "k_mzr_positions launch failed");
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_positions launch failed");
-    return RZ_OK;
+    return h_draws != nullptr ? r->stage.launched(s, "k_mzr_positions") : rz_launched("k_mzr_positions");
 }
 
 int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, const int32_t *d_root_n,
                         const double *d_root_sum, int64_t ticket, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    RZ_ENTER(mr_ready, r);
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
     // an add or ingest since rz_mz_replay_positions may have given a slot to another episode: the search's result has no home
-    if (ticket != r->stored) return mr_fail(RZ_ERR_ARG, "stale ticket: episodes were stored since rz_mz_replay_positions");
+    if (ticket != r->stored) return rz_fail(RZ_ERR_ARG, "stale ticket: episodes were stored since rz_mz_replay_positions");
     if (n == 0) return RZ_OK;
-    if (d_where == nullptr || d_visits == nullptr || d_root_n == nullptr || d_root_sum == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    if (d_where == nullptr || d_visits == nullptr || d_root_n == nullptr || d_root_sum == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     const unsigned blocks = (unsigned)((n * (r->dev.A + 1) + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(k_mzr_update, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, r->dev, d_where, (long long)n, d_visits, d_root_n,
                        d_root_sum);
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_update launch failed");
+    RZ_TRY(rz_launched("k_mzr_update"));
     if (r->prio_on) {   // a changed root value moves the priority of its step and of the step td before it: both in this slot
         hipLaunchKernelGGL(k_mzr_mark_where, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, r->prio,
                            d_where, (long long)n);
-        if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_mark_where launch failed");
+        RZ_TRY(rz_launched("k_mzr_mark_where"));
         r->prio_stale = true;
     }
     return RZ_OK;
@@ -770,9 +697,8 @@ int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, cons
 
 int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
                       float *h_policy, int32_t *h_length, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (first < 0 || n < 0 || first + n > r->count) return mr_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    RZ_ENTER(mr_ready, r);
+    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
     hipStream_t s = (hipStream_t)stream;
     const MzrDev &R = r->dev;
     const long long E = R.E, start = (mr_oldest(r) + first) % E;
@@ -790,41 +716,36 @@ int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, i
         if (h_policy) ok = ok && hipMemcpyAsync(h_policy + at * T * A, R.policy + from * T * A, c * T * A * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess;
         if (h_length) ok = ok && hipMemcpyAsync(h_length + at, R.length + from, c * sizeof(int32_t), hipMemcpyDeviceToHost, s) == hipSuccess;
     }
-    if (!ok || hipStreamSynchronize(s) != hipSuccess) return mr_fail(RZ_ERR_HIP, "read-back failed (MuZero replay)");
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rz_fail(RZ_ERR_HIP, "read-back failed (MuZero replay)");
     return RZ_OK;
 }
 
 int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (flags == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    RZ_ENTER(mr_ready, r);
+    if (flags == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemcpyAsync(flags, r->dev.err, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemsetAsync(r->dev.err, 0, sizeof(int32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return mr_fail(RZ_ERR_HIP, "reading the MuZero replay flags failed");
+        return rz_fail(RZ_ERR_HIP, "reading the MuZero replay flags failed");
     return RZ_OK;
 }
 
 int rz_mz_replay_enable_priorities(rz_mz_replay *r, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(mr_ready, r);
     if (r->prio_on) return RZ_OK;
     const MzrDev &R = r->dev;
-    if ((long long)R.E * R.T > (1LL << 30)) return mr_fail(RZ_ERR_ARG, "priorities need at most 2^30 steps in all (the total stays below 2^62)");
+    if ((long long)R.E * R.T > (1LL << 30)) return rz_fail(RZ_ERR_ARG, "priorities need at most 2^30 steps in all (the total stays below 2^62)");
     MzrPrio P = {};
+    DevPool pool;   // the handle's once every table is there and zeroed; until then a failure frees what there is
     const size_t E = (size_t)R.E;
-    const bool ok = hipMalloc((void **)&P.cum, E * R.T * sizeof(uint64_t)) == hipSuccess && hipMalloc((void **)&P.mass, E * sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc((void **)&P.ecum, E * sizeof(uint64_t)) == hipSuccess && hipMalloc((void **)&P.total, sizeof(uint64_t)) == hipSuccess &&
-                    hipMalloc((void **)&P.dirty, E * sizeof(int32_t)) == hipSuccess;
+    const bool ok = pool.alloc(&P.cum, (long long)R.E * R.T) == RZ_OK && pool.alloc(&P.mass, R.E) == RZ_OK && pool.alloc(&P.ecum, R.E) == RZ_OK &&
+                    pool.alloc(&P.total, 1) == RZ_OK && pool.alloc(&P.dirty, R.E) == RZ_OK;
     hipStream_t s = (hipStream_t)stream;
     if (!ok || hipMemsetAsync(P.cum, 0, E * R.T * sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(P.mass, 0, E * sizeof(uint64_t), s) != hipSuccess ||
         hipMemsetAsync(P.ecum, 0, E * sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(P.total, 0, sizeof(uint64_t), s) != hipSuccess ||
-        hipMemsetAsync(P.dirty, 0, E * sizeof(int32_t), s) != hipSuccess) {
-        void *dev[] = {P.cum, P.mass, P.ecum, P.total, P.dirty};
-        for (void *p : dev)
-            if (p) (void)hipFree(p);
-        return mr_fail(ok ? RZ_ERR_HIP : RZ_ERR_OOM, "allocating the priority tables failed (MuZero replay)");
-    }
+        hipMemsetAsync(P.dirty, 0, E * sizeof(int32_t), s) != hipSuccess)
+        return rz_fail(ok ? RZ_ERR_HIP : RZ_ERR_OOM, "allocating the priority tables failed (MuZero replay)");
+    r->prio_pool.ptrs.swap(pool.ptrs);
     r->prio = P;
     r->prio_on = true;
     r->prio_stale = true;
@@ -832,21 +753,18 @@ int rz_mz_replay_enable_priorities(rz_mz_replay *r, void *stream) {
 }
 
 int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    RZ_ENTER(mr_ready, r);
+    if (!r->prio_on) return rz_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
     return mr_refresh(r, (hipStream_t)stream);
 }
 
 int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int64_t *h_w, int64_t *h_total, void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
-    if (first < 0 || n < 0 || first + n > r->count) return mr_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
-    if (n > 0 && h_w == nullptr) return mr_fail(RZ_ERR_ARG, "NULL argument");
+    RZ_ENTER(mr_ready, r);
+    if (!r->prio_on) return rz_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    if (n > 0 && h_w == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
-    rc = mr_refresh(r, s);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(mr_refresh(r, s));
     const MzrDev &R = r->dev;
     const long long E = R.E, start = (mr_oldest(r) + first) % E;
     const long long n1 = n < E - start ? n : E - start;   // up to the ring's end, then from its start
@@ -860,7 +778,7 @@ int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int6
         ok = ok && hipMemcpyAsync(cum.data() + at * T, r->prio.cum + from * T, (size_t)cnt * T * sizeof(uint64_t), hipMemcpyDeviceToHost, s) == hipSuccess;
     }
     ok = ok && hipMemcpyAsync(&total, r->prio.total, sizeof(uint64_t), hipMemcpyDeviceToHost, s) == hipSuccess;
-    if (!ok || hipStreamSynchronize(s) != hipSuccess) return mr_fail(RZ_ERR_HIP, "read-back failed (MuZero replay priorities)");
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rz_fail(RZ_ERR_HIP, "read-back failed (MuZero replay priorities)");
     for (int64_t j = 0; j < n; ++j) {
         const int len = r->lengths[(size_t)((start + j) % E)];
         for (int t = 0; t < R.T; ++t)
@@ -872,22 +790,19 @@ int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int6
 
 int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, const int64_t *d_targets, int64_t *d_draws, double *d_prob,
                                   void *stream) {
-    int rc = mr_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (!r->prio_on) return mr_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
-    if (n < 0 || n > (1LL << 24)) return mr_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
-    if (r->count == 0) return mr_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    RZ_ENTER(mr_ready, r);
+    if (!r->prio_on) return rz_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     if (n == 0) return RZ_OK;
-    if (d_draws == nullptr || d_prob == nullptr) return mr_fail(RZ_ERR_ARG, "NULL output buffer");
+    if (d_draws == nullptr || d_prob == nullptr) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
     hipStream_t s = (hipStream_t)stream;
     if (r->prio_stale) {
-        rc = mr_refresh(r, s);
-        if (rc != RZ_OK) return rc;
+        RZ_TRY(mr_refresh(r, s));
     }
     hipLaunchKernelGGL(k_mzr_draw_prio, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r->dev, r->prio, (unsigned long long)seed,
                        (unsigned long long)step, (const long long *)d_targets, mr_oldest(r), r->count, (long long)n, (long long *)d_draws, d_prob);
-    if (hipGetLastError() != hipSuccess) return mr_fail(RZ_ERR_HIP, "k_mzr_draw_prio launch failed");
-    return RZ_OK;
+    return rz_launched("k_mzr_draw_prio");
 }
 
 }  // extern "C"

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "rlzero_hip.h"
+#include "rz_host.h"
 #include "rz_pack.h"
 #include "rz_trace.h"
 #include "rz_tree.h"
@@ -53,22 +54,6 @@
 #include "rz_delta.h"
 #include "rz_net_f32.h"
 #include "rz_net_heads.h"
-
-void rz_set_error(const char *msg);  // rz_engine.hip
-
-// A device allocation its holder owns: move-only, freed with the holder.  Reads as the pointer it holds.
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
-    ~DevBuf() { release(); }
-    operator T *() const { return p; }
-    void release() { if (p) (void)hipFree(p); p = nullptr, bytes = 0; }
-    bool alloc(size_t n) { release(); return hipMalloc((void **)&p, n) == hipSuccess ? (bytes = n, true) : (p = nullptr, false); }
-    bool fill(int byte) { return hipMemset(p, byte, bytes) == hipSuccess; }
-};
 
 struct rz_net {
     int board_size = 0, device = 0;
@@ -119,54 +104,43 @@ struct rz_net {
 
 namespace {
 
-int net_fail(int code, const char *msg, const char *detail = "") {
-    char buf[480];
-    snprintf(buf, sizeof(buf), "%s%s", msg, detail);
-    rz_set_error(buf);
-    return code;
-}
-
 // Parameter buffers are allocated by the first rz_net_load and REUSED by later ones (same shapes, same
 // order), so device pointers captured in hipGraphs stay valid across weight updates.
 template <typename T>
 int net_upload(rz_net *net, const float *host, size_t count, const T **out) {
     const size_t bytes = count * sizeof(float);
     if (net->upload_cursor < net->allocs.size()) {
-        if (net->allocs[net->upload_cursor].bytes != bytes) return net_fail(RZ_ERR_ARG, "parameter size changed between loads");
+        if (net->allocs[net->upload_cursor].bytes != bytes) return rz_fail(RZ_ERR_ARG, "parameter size changed between loads");
     } else {
         DevBuf<char> fresh;
-        if (!fresh.alloc(bytes)) return net_fail(RZ_ERR_OOM, "hipMalloc failed (net)");
+        if (!fresh.alloc(bytes)) return rz_fail(RZ_ERR_OOM, "hipMalloc failed (net)");
         net->allocs.push_back(std::move(fresh));
     }
     void *p = net->allocs[net->upload_cursor].p;
     net->upload_cursor += 1;
-    if (hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipMemcpy failed (net)");
+    if (hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (net)");
     *out = (const T *)p;
     return RZ_OK;
 }
 
 int net_ready(rz_net *net, int32_t n) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
-    if (!net->loaded) return net_fail(RZ_ERR_ARG, "rz_net_load has not been called");
-    if (n < 0) return net_fail(RZ_ERR_ARG, "negative batch");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipGetDevice failed");
-    if (cur != net->device && hipSetDevice(net->device) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    return RZ_OK;
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net->loaded) return rz_fail(RZ_ERR_ARG, "rz_net_load has not been called");
+    if (n < 0) return rz_fail(RZ_ERR_ARG, "negative batch");
+    return rz_on_device(net->device);
 }
 
 // ---- the records the entry points hand to the kernels and to the engine, each built in one place
 
 // the engine's device view, and the net ready for a batch of its games
 int engine_view(rz_net *net, rz_engine *engine, rzt::Dev *dev) {
-    int rc = rz_device_view(engine, dev, (int64_t)sizeof(*dev));
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(rz_device_view(engine, dev, (int64_t)sizeof(*dev)));
     return net_ready(net, dev->n_games);
 }
 
 int same_board(const rz_net *net, const rzt::Dev &dev, bool actions_too) {
     if (dev.BH != net->dev.BH || dev.BW != net->dev.BW || (actions_too && dev.A != net->dev.A))
-        return net_fail(RZ_ERR_ARG, "engine and network disagree on the board");
+        return rz_fail(RZ_ERR_ARG, "engine and network disagree on the board");
     return RZ_OK;
 }
 
@@ -198,7 +172,7 @@ int policy_store_dev(const rz_net *net, NetDev *nd, int *n_groups) {
     *nd = net->dev;
     nd->groups_val = 0;
     *n_groups = (nd->Npad / 32 + 3) / 4;
-    if (*n_groups > 2) return net_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
+    if (*n_groups > 2) return rz_fail(RZ_ERR_INTERNAL, "more than 256 policy outputs");
     return RZ_OK;
 }
 
@@ -271,17 +245,17 @@ static void launch_trunk_split(int ms, bool compact, dim3 grid, hipStream_t st, 
 extern "C" {
 
 int rz_net_create(int32_t height, int32_t width, int32_t n_actions, int32_t device, rz_net **out) {
-    if (out == nullptr) return net_fail(RZ_ERR_ARG, "out is NULL");
+    if (out == nullptr) return rz_fail(RZ_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (height < 1 || height > RZ_MAX_BOARD_SIZE || width < 1 || width > RZ_MAX_BOARD_SIZE)
-        return net_fail(RZ_ERR_ARG, "board dimensions out of range");
+        return rz_fail(RZ_ERR_ARG, "board dimensions out of range");
     if (n_actions < 1 || n_actions > RZ_MAX_BOARD_SIZE * RZ_MAX_BOARD_SIZE)
-        return net_fail(RZ_ERR_ARG, "n_actions out of range");
+        return rz_fail(RZ_ERR_ARG, "n_actions out of range");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-        return net_fail(RZ_ERR_ARG, "bad device ordinal");
+        return rz_fail(RZ_ERR_ARG, "bad device ordinal");
     rz_net *net = new (std::nothrow) rz_net();
-    if (!net) return net_fail(RZ_ERR_OOM, "host allocation failed");
+    if (!net) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     net->board_size = height;
     net->device = device;
     if (const char *v = getenv("RZ_NET_COMPACT")) {
@@ -295,7 +269,7 @@ int rz_net_create(int32_t height, int32_t width, int32_t n_actions, int32_t devi
     }
     if (hipSetDevice(device) != hipSuccess || !net->d_flags.alloc(sizeof(unsigned)) || !net->d_flags.fill(0)) {
         delete net;
-        return net_fail(RZ_ERR_OOM, "hipMalloc failed (net flags)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (net flags)");
     }
     memset(&net->dev, 0, sizeof(net->dev));
     net->dev.BH = height;
@@ -331,23 +305,23 @@ int rz_net_destroy(rz_net *net) {
 }
 
 int rz_net_error_flags(rz_net *net, uint32_t *h_flags) {
-    if (!net || !h_flags) return net_fail(RZ_ERR_ARG, "NULL argument");
-    if (hipSetDevice(net->device) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    if (!net || !h_flags) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (hipSetDevice(net->device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     unsigned v = 0;
     if (hipMemcpy(&v, net->d_flags, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemcpy failed (net flags)");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (net flags)");
     if (v != 0 && hipMemset(net->d_flags, 0, sizeof(unsigned)) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemset failed (net flags)");
+        return rz_fail(RZ_ERR_HIP, "hipMemset failed (net flags)");
     *h_flags = v;
     return RZ_OK;
 }
 
 int rz_net_load(rz_net *net, const float *const *h_params, int32_t n_params) {
-    if (!net || !h_params) return net_fail(RZ_ERR_ARG, "NULL argument");
-    if (n_params != 16) return net_fail(RZ_ERR_ARG, "expected the 16 tensors of PolicyValueNet.state_dict()");
+    if (!net || !h_params) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (n_params != 16) return rz_fail(RZ_ERR_ARG, "expected the 16 tensors of PolicyValueNet.state_dict()");
     for (int i = 0; i < 16; ++i)
-        if (!h_params[i]) return net_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
-    if (hipSetDevice(net->device) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipSetDevice failed");
+        if (!h_params[i]) return rz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
+    if (hipSetDevice(net->device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
     net->upload_cursor = 0;
     const int S = net->dev.S;
@@ -393,14 +367,13 @@ int rz_net_load(rz_net *net, const float *const *h_params, int32_t n_params) {
     // the receptive-field bases hold activations of the weights they were built with: none survives an upload (a leaf of a game
     // without a valid base takes the route without one until rz_net_delta_bases runs again)
     if (rc == RZ_OK && net->base_games > 0 && !net->d_base_hdr.fill(0))
-        rc = net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
+        rc = rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->loaded = rc == RZ_OK;
     return rc;
 }
 
 int rz_net_reserve(rz_net *net, int32_t max_boards) {
-    int rc = net_ready(net, max_boards);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, max_boards);
     if (max_boards <= net->feat_boards) return RZ_OK;
     (void)hipDeviceSynchronize();
     net->d_feat.release();
@@ -415,13 +388,13 @@ int rz_net_reserve(rz_net *net, int32_t max_boards) {
     if (!net->d_feat.alloc(net->feat_floats * sizeof(float)) ||
         !net->d_raw.alloc(4 * (((size_t)max_boards + 63) / 64 * 64) * net->dev.Npad * sizeof(float)) ||
         !net->d_hid.alloc(4 * (((size_t)max_boards + 63) / 64 * 64) * 64 * sizeof(float)))
-        return net_fail(RZ_ERR_OOM, "hipMalloc failed (feature buffers)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (feature buffers)");
     // padded boards and the K tail must read as finite values (they meet zero weights)
-    if (!net->d_feat.fill(0)) return net_fail(RZ_ERR_HIP, "hipMemset failed (feature buffer)");
+    if (!net->d_feat.fill(0)) return rz_fail(RZ_ERR_HIP, "hipMemset failed (feature buffer)");
     {   // f16 pieces: [boards padded to 64][K-steps][hi | lo][16 x f16]; the K tail and padded boards stay zero
         const size_t bytes = (((size_t)max_boards + 63) / 64 * 64) * (size_t)(net->dev.groups_act + net->dev.groups_val) * 64;
-        if (!net->d_feat16.alloc(bytes)) return net_fail(RZ_ERR_OOM, "hipMalloc failed (f16 feature buffer)");
-        if (!net->d_feat16.fill(0)) return net_fail(RZ_ERR_HIP, "hipMemset failed (f16 feature buffer)");
+        if (!net->d_feat16.alloc(bytes)) return rz_fail(RZ_ERR_OOM, "hipMalloc failed (f16 feature buffer)");
+        if (!net->d_feat16.fill(0)) return rz_fail(RZ_ERR_HIP, "hipMemset failed (f16 feature buffer)");
     }
     net->raw_part_floats = (((size_t)max_boards + 63) / 64 * 64) * net->dev.Npad;  // room for four K-quarter parts
     net->hid_part_floats = (((size_t)max_boards + 63) / 64 * 64) * 64;
@@ -556,45 +529,39 @@ static int launch_heads(rz_net *net, const float *d_feat, int32_t n_boards, floa
     k_heads_finish<<<dim3((unsigned)n_boards), dim3(64), 0, (hipStream_t)stream>>>(
         net->dev, net->d_raw, net->d_hid, d_logp, d_value, n_boards, net->raw_parts, (long long)net->raw_part_floats,
         (long long)net->hid_part_floats);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_* failed");
-    return RZ_OK;
+    return rz_launched("k_heads_*");
 }
 
 int rz_net_trunk(rz_net *net, const float *d_obs, int32_t n_boards, float *d_feat, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_boards);
     if (n_boards == 0) return RZ_OK;  // an empty batch is a no-op (its tensors have no storage)
-    if (!d_obs) return net_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (!d_obs) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
     if (net->fp8_cross)
-        return net_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 evaluates positions (rz_net_trunk_leaves*, rz_net_search_resident): float planes are refused, "
+        return rz_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 evaluates positions (rz_net_trunk_leaves*, rz_net_search_resident): float planes are refused, "
                                     "not computed in another arithmetic");
     if (!d_feat) {  // internal feature buffer (the input of rz_net_heads)
-        if (n_boards > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
+        if (n_boards > net->feat_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
         d_feat = net->d_feat;
     }
     launch_trunk(net, d_obs, d_feat, n_boards, stream);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk failed");
-    return RZ_OK;
+    return rz_launched("k_trunk");
 }
 
 int rz_net_trunk_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_to_move, const int32_t *d_last_cell,
                         int32_t n_boards, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_boards);
     if (n_boards == 0) return RZ_OK;
-    if (!d_stones || !d_to_move || !d_last_cell) return net_fail(RZ_ERR_ARG, "NULL device pointer");
-    if (n_boards > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
+    if (!d_stones || !d_to_move || !d_last_cell) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (n_boards > net->feat_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
     if (!split_trunk_ok(net))
-        return net_fail(RZ_ERR_ARG, "rz_net_trunk_leaves needs the RZ_NET_SPLIT_F16 trunk (the others read float planes: rz_net_trunk)");
+        return rz_fail(RZ_ERR_ARG, "rz_net_trunk_leaves needs the RZ_NET_SPLIT_F16 trunk (the others read float planes: rz_net_trunk)");
     launch_trunk(net, nullptr, net->d_feat, n_boards, stream, LeafBits{d_stones, d_to_move, d_last_cell});
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_split failed");
-    return RZ_OK;
+    return rz_launched("k_trunk_split");
 }
 
 int rz_net_deferred_reserve(rz_net *net, int32_t max_boards, int32_t slots) {
-    int rc = net_ready(net, max_boards);
-    if (rc != RZ_OK) return rc;
-    if (slots < 1 || max_boards < 1) return net_fail(RZ_ERR_ARG, "rz_net_deferred_reserve: slots and max_boards must be positive");
+    RZ_ENTER(net_ready, net, max_boards);
+    if (slots < 1 || max_boards < 1) return rz_fail(RZ_ERR_ARG, "rz_net_deferred_reserve: slots and max_boards must be positive");
     if (max_boards <= net->store_boards && slots <= net->store_slots) return RZ_OK;
     // grow to the larger of what is held and what is asked in BOTH directions: an engine that reserved more boards (or slots)
     // earlier keeps fitting when another one asks for more of the other
@@ -611,11 +578,11 @@ int rz_net_deferred_reserve(rz_net *net, int32_t max_boards, int32_t slots) {
     const size_t raw_bytes = (size_t)slots * tiles * 32 * net->dev.Npad * sizeof(float);
     const size_t val_bytes = (size_t)tiles * 32 * net->vf_groups * 4 * sizeof(float);
     if (!net->d_store16.alloc(store_bytes) || !net->d_store_raw.alloc(raw_bytes) || !net->d_valfeat.alloc(val_bytes))
-        return net_fail(RZ_ERR_OOM, "hipMalloc failed (deferred-priors store)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (deferred-priors store)");
     // the K tail of a tile's last K-step, the rows of boards that do not exist and the padding of the value rows are never
     // written: they must read as finite values (they meet zero weights, or rows nobody reads)
     if (!net->d_store16.fill(0) || !net->d_valfeat.fill(0))
-        return net_fail(RZ_ERR_HIP, "hipMemset failed (deferred-priors store)");
+        return rz_fail(RZ_ERR_HIP, "hipMemset failed (deferred-priors store)");
     net->store_tiles = tiles;
     net->store_slots = slots;
     net->store_boards = max_boards;
@@ -624,16 +591,15 @@ int rz_net_deferred_reserve(rz_net *net, int32_t max_boards, int32_t slots) {
 
 int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const int32_t *d_to_move, const int32_t *d_last_cell,
                                  int32_t n_boards, const int32_t *d_slot_of_board, rz_value_head *out, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
-    if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_ENTER(net_ready, net, n_boards);
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     if (!split_trunk_ok(net))
-        return net_fail(RZ_ERR_ARG, "the deferred-priors route needs the RZ_NET_SPLIT_F16 trunk (a net with finite activation bounds)");
-    if (n_boards > net->store_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
+        return rz_fail(RZ_ERR_ARG, "the deferred-priors route needs the RZ_NET_SPLIT_F16 trunk (a net with finite activation bounds)");
+    if (n_boards > net->store_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
     if (n_boards > 0) {
-        if (!d_stones || !d_to_move || !d_last_cell || !d_slot_of_board) return net_fail(RZ_ERR_ARG, "NULL device pointer");
+        if (!d_stones || !d_to_move || !d_last_cell || !d_slot_of_board) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
         launch_trunk(net, nullptr, net->d_feat, n_boards, stream, LeafBits{d_stones, d_to_move, d_last_cell}, store_out(net, d_slot_of_board, true));
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the split-f16 trunk failed");
+        RZ_TRY(rz_launched("the split-f16 trunk"));
     }
     *out = value_head_of(net);
     return RZ_OK;
@@ -642,24 +608,22 @@ int rz_net_trunk_leaves_deferred(rz_net *net, const uint64_t *d_stones, const in
 // policy == false: rz_net_search_resident_values (policy on demand: k_delta_res<false> or a refusal)
 static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream, bool policy) {
     rzt::Dev dev;
-    int rc = engine_view(net, engine, &dev);
-    if (rc != RZ_OK) return rc;
-    if (n_sims < 1) return net_fail(RZ_ERR_ARG, "rz_net_search_resident: n_sims must be positive");
+    RZ_TRY(engine_view(net, engine, &dev));
+    if (n_sims < 1) return rz_fail(RZ_ERR_ARG, "rz_net_search_resident: n_sims must be positive");
     // a game's leaves go to store slots pend[g] .. pend[g] + n_sims - 1: more simulations than either side has slots can never fit
     // (and a leaf whose slot lies beyond the store is not written: the tree code flags its game RZ_FLAG_INTERNAL)
     if (n_sims > net->store_slots || n_sims > dev.pend_cap) {
-        char detail[160];
-        snprintf(detail, sizeof(detail), ": %d simulations, %d / %d slots (rz_net_deferred_reserve / rz_deferred_reserve)", n_sims, net->store_slots, dev.pend_cap);
-        return net_fail(RZ_ERR_ARG, "rz_net_search_resident: more simulations than the store has slots", detail);
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident: more simulations than the store has slots: %d simulations, %d / %d slots "
+                                   "(rz_net_deferred_reserve / rz_deferred_reserve)", n_sims, net->store_slots, dev.pend_cap);
     }
     const bool rows = net->algo == RZ_NET_SPLIT_F16 && rows_kernel_covers(net->dev.BH, net->dev.BW);
     const TrunkClass tc = trunk_class(net);
     if (!split_trunk_ok(net) || (!rows && (tc.ms == 0 || net->dev.BH > 10 || net->dev.BW > 10)))
-        return net_fail(RZ_ERR_ARG, "the resident search needs the RZ_NET_SPLIT_F16 trunk on a board of 11 .. 16 rows and columns (the row-tile "
+        return rz_fail(RZ_ERR_ARG, "the resident search needs the RZ_NET_SPLIT_F16 trunk on a board of 11 .. 16 rows and columns (the row-tile "
                                     "kernel) or of up to 10 x 10 (k_trunk_split with one N-tile per wave)");
     if (dev.K != 1 || dev.score_mode != RZ_SCORE_UCT_REF || dev.pend_cap <= 0)
-        return net_fail(RZ_ERR_ARG, "the resident search is the deferred-priors route: RZ_SCORE_UCT_REF, one simulation in flight, rz_deferred_reserve first");
-    if ((rc = same_board(net, dev, true)) != RZ_OK) return rc;
+        return rz_fail(RZ_ERR_ARG, "the resident search is the deferred-priors route: RZ_SCORE_UCT_REF, one simulation in flight, rz_deferred_reserve first");
+    RZ_TRY(same_board(net, dev, true));
     // receptive-field evaluation (rz_net_delta_reserve for this many games, the default trunk on a board of 11 .. 16 rows and columns):
     // k_delta_res, TWO workgroups per CU; rz_net_delta_resident(net, 0) keeps k_trunk_rows_res
     const bool delta_res = net->delta_resident && delta_covers(net) && net->base_games >= dev.n_games;
@@ -670,9 +634,9 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     // is 1-2 % ahead even with ONE game on the chip, TicTacToe 93.3 -> 94.6 k)
     const bool compact_res = !rows && tc.compact;
     if (dev.n_games > net->store_boards || (!delta_res && !compact_res && dev.n_games > net->n_cus))
-        return net_fail(RZ_ERR_ARG, "the resident search runs one workgroup per game, at most one per CU (any number with rz_net_delta_reserve, or on a board of "
+        return rz_fail(RZ_ERR_ARG, "the resident search runs one workgroup per game, at most one per CU (any number with rz_net_delta_reserve, or on a board of "
                                     "the compact grid) and rz_net_deferred_reserve()d");
-    if (rows ? (net->vf_groups != 64 && net->vf_groups != 128) : net->vf_groups > 64) return net_fail(RZ_ERR_INTERNAL, "value head groups");
+    if (rows ? (net->vf_groups != 64 && net->vf_groups != 128) : net->vf_groups > 64) return rz_fail(RZ_ERR_INTERNAL, "value head groups");
     ResArgs<true> res;
     res.E = dev;
     res.vh = value_head_of(net, false);
@@ -682,24 +646,23 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     // (zeros, or finite features of an earlier search).  They are NOT skipped: rz_net_deferred_gemm runs over them -- rows do not mix,
     // the GEMM raises no range flag (only the trunk's stores do) -- and what it computes there is IGNORED: k_deferred_priors reads the
     // slots below pend[g] only, and pend[g] counts the leaves the game stored.
-    if ((rc = rz_playouts_view(engine, &res.sims_of, &res.order)) != RZ_OK) return rc;
+    RZ_TRY(rz_playouts_view(engine, &res.sims_of, &res.order));
     const DeferredOut later = store_out(net, dev.pend, false);
     const LeafBits leaves{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last};
     const dim3 grid((unsigned)dev.n_games);
     const hipStream_t st = (hipStream_t)stream;
     net->feat16_valid = net->feat32_valid = false;
     if (!policy && !delta_res)
-        return net_fail(RZ_ERR_ARG, "rz_net_search_resident_values: the search without policy features is k_delta_res's (the default trunk on a board of "
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_values: the search without policy features is k_delta_res's (the default trunk on a board of "
                                     "11 .. 16 rows and columns, rz_net_delta_reserve for the engine's games, rz_net_delta_resident on)");
     if (delta_res) {
         if (select_first) {   // a search begins: the bases of its roots (a continued search finds them, or takes the route without)
-            if ((rc = rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream)) != RZ_OK) return rc;
+            RZ_TRY(rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream));
         }
         const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, true, 0, net->d_win);
         if (policy) dl::k_delta_res<true><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
         else dl::k_delta_res<false><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search (k_delta_res) failed");
-        return RZ_OK;
+        return rz_launched("the resident search (k_delta_res)");
     }
     if (rows)
         with_board_rows(net->dev.BH, [&](auto nt) {
@@ -708,8 +671,7 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
     else   // (the launches of launch_trunk for these boards, RES instantiations)
         launch_trunk_split<true>(tc.ms, compact_res, grid, st, net->dev, nullptr, leaves, nullptr, net->d_store16, dev.n_games, net->d_flags,
                                  nullptr, nullptr, later, res);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of the resident search failed");
-    return RZ_OK;
+    return rz_launched("the resident search");
 }
 
 int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
@@ -721,41 +683,38 @@ int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims
 }
 
 int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream) {
-    if (!kept) return net_fail(RZ_ERR_ARG, "NULL argument");
+    if (!kept) return rz_fail(RZ_ERR_ARG, "NULL argument");
     rzt::Dev dev;
-    int rc = engine_view(net, engine, &dev);
-    if (rc != RZ_OK) return rc;
-    if (!kept->rows || !kept->count) return net_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
+    RZ_TRY(engine_view(net, engine, &dev));
+    if (!kept->rows || !kept->count) return rz_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
     if (!delta_covers(net) || net->base_games < dev.n_games || !split_trunk_ok(net))
-        return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the receptive-field trunk (the default trunk on a board of 11 .. 16 rows and columns) and "
+        return rz_fail(RZ_ERR_ARG, "rz_net_policy_rows: the receptive-field trunk (the default trunk on a board of 11 .. 16 rows and columns) and "
                                     "rz_net_delta_reserve for the engine's games");
-    if ((rc = same_board(net, dev, true)) != RZ_OK) return rc;
-    if (dev.pend_cap <= 0 || dev.pend_stones == nullptr || dev.pend_lw == nullptr) return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: rz_deferred_reserve first");
+    RZ_TRY(same_board(net, dev, true));
+    if (dev.pend_cap <= 0 || dev.pend_stones == nullptr || dev.pend_lw == nullptr) return rz_fail(RZ_ERR_ARG, "rz_net_policy_rows: rz_deferred_reserve first");
     // a listed row addresses slot rows[i] / n_games of the store (the kernel skips a slot beyond it) and the game's tile
     if (kept->n_games != dev.n_games || dev.n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)dev.pend_cap * dev.n_games)
-        return net_fail(RZ_ERR_ARG, "rz_net_policy_rows: the rows are not this engine's, or more boards than rz_net_deferred_reserve()d");
+        return rz_fail(RZ_ERR_ARG, "rz_net_policy_rows: the rows are not this engine's, or more boards than rz_net_deferred_reserve()d");
     const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, false, 0);
     const dl::PolicyRows pr{kept->rows, kept->count, dev.pend_stones, dev.pend_lw, dev.n_games, net->store_slots, store_stride(net)};
     const dim3 grid((unsigned)(2 * (net->n_cus > 0 ? net->n_cus : 1)));   // fixed: two workgroups per CU, striding over the device's count
     dl::k_trunk_policy_rows<<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, net->d_store16, da, pr);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_policy_rows failed");
-    return RZ_OK;
+    return rz_launched("k_trunk_policy_rows");
 }
 
 int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
-    int rc = net_ready(net, n_games);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_games);
     if (!delta_covers(net))
-        return net_fail(RZ_ERR_ARG, "receptive-field evaluation exists for the RZ_NET_SPLIT_F16 trunk on boards of 11 .. 16 rows and columns");
-    if (n_games < 1) return net_fail(RZ_ERR_ARG, "rz_net_delta_reserve: n_games must be positive");
+        return rz_fail(RZ_ERR_ARG, "receptive-field evaluation exists for the RZ_NET_SPLIT_F16 trunk on boards of 11 .. 16 rows and columns");
+    if (n_games < 1) return rz_fail(RZ_ERR_ARG, "rz_net_delta_reserve: n_games must be positive");
     if (n_games <= net->base_games) return RZ_OK;
     (void)hipDeviceSynchronize();
     if (!net->d_win) {   // the window table of the net's board (k_delta_res's leaf_windows)
         std::vector<uint64_t> win(rzw::kEntries);
         rzw::window_table(win.data(), net->dev.BH, net->dev.BW);
-        if (!net->d_win.alloc(win.size() * sizeof(uint64_t))) return net_fail(RZ_ERR_OOM, "hipMalloc failed (window table)");
+        if (!net->d_win.alloc(win.size() * sizeof(uint64_t))) return rz_fail(RZ_ERR_OOM, "hipMalloc failed (window table)");
         if (hipMemcpy(net->d_win, win.data(), win.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
-            return net_fail(RZ_ERR_HIP, "hipMemcpy failed (window table)");
+            return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (window table)");
     }
     net->d_base_hdr.release();
     net->d_base_recs.release();
@@ -763,57 +722,54 @@ int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
     net->base_games = 0;
     const size_t hdr_bytes = (size_t)n_games * sizeof(dl::BaseHdr), rec_bytes = (size_t)n_games * 2 * dl::kBaseBytes;
     if (!net->d_base_hdr.alloc(hdr_bytes) || !net->d_base_recs.alloc(rec_bytes) || !net->d_base_ones.alloc((size_t)n_games))
-        return net_fail(RZ_ERR_OOM, "hipMalloc failed (base cache)");
-    if (!net->d_base_ones.fill(1)) return net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (base cache)");
+    if (!net->d_base_ones.fill(1)) return rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     if (!net->d_delta_stats && !net->d_delta_stats.alloc(8 * sizeof(unsigned)))
-        return net_fail(RZ_ERR_OOM, "hipMalloc failed (delta counters)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (delta counters)");
     // valid = 0: a leaf of a game without bases takes the four passes without a base
     if (!net->d_base_hdr.fill(0) || !net->d_delta_stats.fill(0))
-        return net_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
+        return rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->base_games = n_games;
     return RZ_OK;
 }
 
 int rz_net_delta_resident(rz_net *net, int32_t on) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
     net->delta_resident = on != 0;
     return RZ_OK;
 }
 
 int rz_net_delta_invalidate(rz_net *net, void *stream) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
     if (net->base_games > 0 &&
         hipMemsetAsync(net->d_base_hdr, 0, (size_t)net->base_games * sizeof(dl::BaseHdr), (hipStream_t)stream) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemsetAsync failed (base cache)");
+        return rz_fail(RZ_ERR_HIP, "hipMemsetAsync failed (base cache)");
     return RZ_OK;
 }
 
 int rz_net_delta_bases(rz_net *net, const uint64_t *d_root_stones, const int32_t *d_root_to_move, int32_t n_games, void *stream) {
-    int rc = net_ready(net, n_games);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_games);
     if (n_games == 0) return RZ_OK;
-    if (!delta_covers(net)) return net_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
-    if (n_games > net->base_games) return net_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
-    if (!d_root_stones || !d_root_to_move) return net_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (!delta_covers(net)) return rz_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
+    if (n_games > net->base_games) return rz_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
+    if (!d_root_stones || !d_root_to_move) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
     const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, false, 1);
     dl::k_trunk_delta<false><<<dim3((unsigned)(2 * n_games)), dim3(256), 0, (hipStream_t)stream>>>(
         net->dev, LeafBits{d_root_stones, d_root_to_move, nullptr}, nullptr, 2 * n_games, no_store(), da);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta (bases) failed");
-    return RZ_OK;
+    return rz_launched("k_trunk_delta (bases)");
 }
 
 int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_to_move, const int32_t *d_last_cell, int32_t n_boards,
                         const int32_t *d_slot_of_board, const uint8_t *d_active, float *d_feat32, int32_t without_base, rz_value_head *out,
                         void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
-    if (!delta_covers(net)) return net_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
-    if (without_base && n_boards > net->base_games && (rc = rz_net_delta_reserve(net, n_boards)) != RZ_OK) return rc;   // (the kernel reads a header per board in every mode)
-    if (n_boards > net->base_games) return net_fail(RZ_ERR_ARG, "more boards than rz_net_delta_reserve()d games");
-    if (d_slot_of_board && n_boards > net->store_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
+    RZ_ENTER(net_ready, net, n_boards);
+    if (!delta_covers(net)) return rz_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
+    if (without_base && n_boards > net->base_games) RZ_TRY(rz_net_delta_reserve(net, n_boards));   // (the kernel reads a header per board in every mode)
+    if (n_boards > net->base_games) return rz_fail(RZ_ERR_ARG, "more boards than rz_net_delta_reserve()d games");
+    if (d_slot_of_board && n_boards > net->store_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_deferred_reserve()d");
     if (n_boards > 0) {
-        if (!d_stones || !d_to_move || !d_last_cell) return net_fail(RZ_ERR_ARG, "NULL device pointer");
-        if (!d_slot_of_board && !d_feat32) return net_fail(RZ_ERR_ARG, "rz_net_delta_leaves: neither a store slot nor an f32 buffer to write to");
+        if (!d_stones || !d_to_move || !d_last_cell) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
+        if (!d_slot_of_board && !d_feat32) return rz_fail(RZ_ERR_ARG, "rz_net_delta_leaves: neither a store slot nor an f32 buffer to write to");
         const DeferredOut later = store_out(net, d_slot_of_board, true);
         const dl::DeltaArgs da = delta_args(net, d_active, d_feat32, true, without_base ? 2 : 0);
         const dim3 grid((unsigned)n_boards);
@@ -823,7 +779,7 @@ int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
             dl::k_trunk_delta<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, LeafBits{d_stones, d_to_move, d_last_cell}, store, n_boards, later, da);
         else
             dl::k_trunk_delta<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(net->dev, LeafBits{d_stones, d_to_move, d_last_cell}, store, n_boards, later, da);
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta failed");
+        RZ_TRY(rz_launched("k_trunk_delta"));
     }
     if (out) *out = value_head_of(net);
     return RZ_OK;
@@ -833,20 +789,18 @@ int rz_net_delta_leaves(rz_net *net, const uint64_t *d_stones, const int32_t *d_
 // slot pend[g], games whose active flag is 0 skipped)
 int rz_net_delta_bases_engine(rz_net *net, rz_engine *engine, void *stream) {
     rzt::Dev dev;
-    int rc = engine_view(net, engine, &dev);
-    if (rc != RZ_OK) return rc;
-    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
+    RZ_TRY(engine_view(net, engine, &dev));
+    RZ_TRY(same_board(net, dev, false));
     return rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream);
 }
 
 int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *stream) {
     rzt::Dev dev;
-    int rc = engine_view(net, engine, &dev);
-    if (rc != RZ_OK) return rc;
-    if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_TRY(engine_view(net, engine, &dev));
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     if (dev.K != 1 || dev.pend_cap <= 0 || dev.pend == nullptr)
-        return net_fail(RZ_ERR_ARG, "rz_net_delta_step is the deferred-priors route: one simulation in flight, rz_deferred_reserve first");
-    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
+        return rz_fail(RZ_ERR_ARG, "rz_net_delta_step is the deferred-priors route: one simulation in flight, rz_deferred_reserve first");
+    RZ_TRY(same_board(net, dev, false));
     return rz_net_delta_leaves(net, dev.leaf_stones, dev.leaf_to_move, dev.leaf_last, dev.n_games, dev.pend, dev.active, nullptr, 0, out, stream);
 }
 
@@ -854,14 +808,13 @@ int rz_net_delta_step(rz_net *net, rz_engine *engine, rz_value_head *out, void *
 // (policy and value K-steps of the FC GEMM: rz_net_heads_gemm next) -- the three-launch step (PUCT) on boards of 11 .. 16 rows.
 int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream) {
     rzt::Dev dev;
-    int rc = engine_view(net, engine, &dev);
-    if (rc != RZ_OK) return rc;
-    if (!delta_covers(net)) return net_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
-    if (dev.K != 1) return net_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine: one simulation in flight per tree (a base per game)");
-    if ((rc = same_board(net, dev, false)) != RZ_OK) return rc;
-    if (dev.n_games > net->base_games) return net_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
-    if (dev.n_games > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
-    if (net->heads_algo == RZ_NET_HEADS_F32) return net_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine writes the f16 tiles only (RZ_NET_HEADS_F32 reads f32 features: rz_net_trunk_leaves)");
+    RZ_TRY(engine_view(net, engine, &dev));
+    if (!delta_covers(net)) return rz_fail(RZ_ERR_ARG, "receptive-field evaluation: RZ_NET_SPLIT_F16 on boards of 11 .. 16 rows and columns");
+    if (dev.K != 1) return rz_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine: one simulation in flight per tree (a base per game)");
+    RZ_TRY(same_board(net, dev, false));
+    if (dev.n_games > net->base_games) return rz_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
+    if (dev.n_games > net->feat_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
+    if (net->heads_algo == RZ_NET_HEADS_F32) return rz_fail(RZ_ERR_ARG, "rz_net_delta_trunk_engine writes the f16 tiles only (RZ_NET_HEADS_F32 reads f32 features: rz_net_trunk_leaves)");
     net->feat16_valid = true;
     net->feat32_valid = false;
     net->raw_from_trunk = false;
@@ -869,43 +822,41 @@ int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream) {
     const dl::DeltaArgs da = delta_args(net, dev.active, nullptr, true, 0);
     dl::k_trunk_delta<false><<<dim3((unsigned)dev.n_games), dim3(256), 0, (hipStream_t)stream>>>(
         net->dev, LeafBits{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last}, net->d_feat16, dev.n_games, no_store(), da);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk_delta failed");
-    return RZ_OK;
+    return rz_launched("k_trunk_delta");
 }
 
 int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset) {
-    if (!net || !h_out8) return net_fail(RZ_ERR_ARG, "NULL argument");
+    if (!net || !h_out8) return rz_fail(RZ_ERR_ARG, "NULL argument");
     memset(h_out8, 0, 8 * sizeof(uint32_t));
     if (!net->d_delta_stats) return RZ_OK;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out8, net->d_delta_stats, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return net_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
-    if (reset && hipMemset(net->d_delta_stats, 0, 8 * sizeof(uint32_t)) != hipSuccess) return net_fail(RZ_ERR_HIP, "hipMemset failed (delta counters)");
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
+    if (reset && hipMemset(net->d_delta_stats, 0, 8 * sizeof(uint32_t)) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipMemset failed (delta counters)");
     return RZ_OK;
 }
 
 int rz_net_trace_attach(rz_net *net, void *d_trace) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
     net->d_trace = (unsigned long long *)d_trace;
     return RZ_OK;
 }
 
 int rz_net_deferred_gemm(rz_net *net, int32_t n_boards, int32_t n_slots, rz_deferred_logits *out, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
-    if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
+    RZ_ENTER(net_ready, net, n_boards);
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
     if (n_slots < 0 || n_slots > net->store_slots || n_boards > net->store_boards)
-        return net_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
+        return rz_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
     if (n_slots > 0 && n_boards > 0) {
         // the store is a list of n_slots * store_tiles tiles of groups_act K-steps each: k_heads_split's policy groups over all of
         // them (64 boards x 128 outputs per workgroup, the K quarters over its four waves: the bits of every other shape)
         NetDev nd;
         int n_groups = 0;
-        if ((rc = policy_store_dev(net, &nd, &n_groups)) != RZ_OK) return rc;
+        RZ_TRY(policy_store_dev(net, &nd, &n_groups));
         const size_t pairs = (size_t)n_slots * net->store_tiles / 2;   // workgroups per output group: two board tiles each
         const dim3 grid((unsigned)(n_groups == 2 ? 2 * ((pairs + 7) / 8 * 8) : pairs));
         k_heads_split<2, 4, 3, false, true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(
             nd, reinterpret_cast<const f32x4 *>(net->d_store16.p), net->d_store_raw, nullptr, n_slots * net->store_tiles * 32);
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_split failed");
+        RZ_TRY(rz_launched("k_heads_split"));
     }
     out->raw = net->d_store_raw;
     out->ld = net->dev.Npad;
@@ -914,21 +865,20 @@ int rz_net_deferred_gemm(rz_net *net, int32_t n_boards, int32_t n_slots, rz_defe
 }
 
 int rz_net_deferred_gemm_rows(rz_net *net, const rz_kept_rows *kept, rz_deferred_logits *out, void *stream) {
-    if (!kept || !out) return net_fail(RZ_ERR_ARG, "NULL argument");
-    int rc = net_ready(net, kept->n_games);
-    if (rc != RZ_OK) return rc;
-    if (!kept->rows || !kept->count) return net_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
+    if (!kept || !out) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    RZ_ENTER(net_ready, net, kept->n_games);
+    if (!kept->rows || !kept->count) return rz_fail(RZ_ERR_ARG, "rz_kept_rows: NULL pointer");
     // a listed row addresses slot rows[i] / n_games < capacity / n_games of the store, and logits row i < capacity exists
     if (kept->n_games < 1 || kept->n_games > net->store_boards || kept->capacity < 1 || kept->capacity > (int64_t)net->store_slots * kept->n_games)
-        return net_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
+        return rz_fail(RZ_ERR_ARG, "more slots / boards than rz_net_deferred_reserve()d");
     NetDev nd;
     int n_groups = 0;
-    if ((rc = policy_store_dev(net, &nd, &n_groups)) != RZ_OK) return rc;
+    RZ_TRY(policy_store_dev(net, &nd, &n_groups));
     // one workgroup per CU (`part` is 128 KB of its LDS), whole groups of 16 (k_heads_rows: the output groups of a block 8 apart)
     const dim3 grid((unsigned)(((net->n_cus > 16 ? net->n_cus : 16) + 15) / 16 * 16));
     k_heads_rows<2, 4, 3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(nd, reinterpret_cast<const f32x4 *>(net->d_store16.p), net->d_store_raw,
                                                                      kept->rows, kept->count, kept->n_games, net->store_tiles);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_rows failed");
+    RZ_TRY(rz_launched("k_heads_rows"));
     out->raw = net->d_store_raw;
     out->ld = net->dev.Npad;
     out->rows_per_slot = 0;
@@ -936,20 +886,20 @@ int rz_net_deferred_gemm_rows(rz_net *net, const rz_kept_rows *kept, rz_deferred
 }
 
 int rz_net_set_algo(rz_net *net, int32_t algo) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
     if (algo != RZ_NET_DIRECT && algo != RZ_NET_WINOGRAD_F4 && algo != RZ_NET_SPLIT_F16 && algo != RZ_NET_SPLIT_F16_TILES &&
         algo != RZ_NET_SPLIT_F16_FP8)
-        return net_fail(RZ_ERR_ARG, "unknown algorithm");
+        return rz_fail(RZ_ERR_ARG, "unknown algorithm");
     if (algo == RZ_NET_SPLIT_F16_FP8 && !rows_kernel_covers(net->dev.BH, net->dev.BW))
-        return net_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 exists for boards of 11 .. 16 rows and columns (k_trunk_rows)");
+        return rz_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 exists for boards of 11 .. 16 rows and columns (k_trunk_rows)");
     net->fp8_cross = algo == RZ_NET_SPLIT_F16_FP8;
     net->algo = net->fp8_cross ? RZ_NET_SPLIT_F16 : algo;
     return RZ_OK;
 }
 
 int rz_net_range_info(rz_net *net, float *h_info8) {
-    if (!net || !h_info8) return net_fail(RZ_ERR_ARG, "NULL argument");
-    if (!net->loaded) return net_fail(RZ_ERR_ARG, "rz_net_load has not been called");
+    if (!net || !h_info8) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (!net->loaded) return rz_fail(RZ_ERR_ARG, "rz_net_load has not been called");
     memcpy(h_info8, net->range_info, sizeof(net->range_info));
     return RZ_OK;
 }
@@ -961,27 +911,26 @@ int rz_net_debug_profile(long long *h_out16) {
 #endif
 
 int rz_net_set_heads_algo(rz_net *net, int32_t heads_algo) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
-    if (heads_algo < RZ_NET_HEADS_AUTO || heads_algo > RZ_NET_HEADS_IN_TRUNK) return net_fail(RZ_ERR_ARG, "unknown heads algorithm");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (heads_algo < RZ_NET_HEADS_AUTO || heads_algo > RZ_NET_HEADS_IN_TRUNK) return rz_fail(RZ_ERR_ARG, "unknown heads algorithm");
     net->heads_algo = heads_algo;
     return RZ_OK;
 }
 
 int rz_net_set_max_workgroups(rz_net *net, int32_t max_workgroups) {
-    if (!net) return net_fail(RZ_ERR_ARG, "net handle is NULL");
-    if (max_workgroups < 0) return net_fail(RZ_ERR_ARG, "max_workgroups must be >= 0");
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (max_workgroups < 0) return rz_fail(RZ_ERR_ARG, "max_workgroups must be >= 0");
     net->max_wgs = max_workgroups;
     return RZ_OK;
 }
 
 int rz_net_heads_gemm(rz_net *net, int32_t n_boards, rz_raw_heads *out, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
-    if (!out) return net_fail(RZ_ERR_ARG, "NULL output pointer");
-    if (n_boards > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
+    RZ_ENTER(net_ready, net, n_boards);
+    if (!out) return rz_fail(RZ_ERR_ARG, "NULL output pointer");
+    if (n_boards > net->feat_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
     if (n_boards > 0) {
         launch_heads_gemm(net, net->d_feat, n_boards, stream);
-        if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_heads_gemm failed");
+        RZ_TRY(rz_launched("k_heads_gemm"));
     }
     memset(out, 0, sizeof(*out));
     out->raw = net->d_raw;
@@ -1000,26 +949,24 @@ int rz_net_heads_gemm(rz_net *net, int32_t n_boards, rz_raw_heads *out, void *st
 }
 
 int rz_net_heads(rz_net *net, int32_t n_boards, float *d_logp, float *d_value, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_boards);
     if (n_boards == 0) return RZ_OK;
-    if (!d_logp || !d_value) return net_fail(RZ_ERR_ARG, "NULL device pointer");
-    if (n_boards > net->feat_boards) return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
+    if (!d_logp || !d_value) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (n_boards > net->feat_boards) return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d");
     return launch_heads(net, net->d_feat, n_boards, d_logp, d_value, stream);
 }
 
 int rz_net_forward(rz_net *net, const float *d_obs, int32_t n_boards, float *d_logp, float *d_value, void *stream) {
-    int rc = net_ready(net, n_boards);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(net_ready, net, n_boards);
     if (n_boards == 0) return RZ_OK;
-    if (!d_obs || !d_logp || !d_value) return net_fail(RZ_ERR_ARG, "NULL device pointer");
+    if (!d_obs || !d_logp || !d_value) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
     if (net->fp8_cross)
-        return net_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 evaluates positions (rz_net_trunk_leaves*, rz_net_search_resident): float planes are refused, "
+        return rz_fail(RZ_ERR_ARG, "RZ_NET_SPLIT_F16_FP8 evaluates positions (rz_net_trunk_leaves*, rz_net_search_resident): float planes are refused, "
                                     "not computed in another arithmetic");
     if (n_boards > net->feat_boards)
-        return net_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d (no allocation on the launch path)");
+        return rz_fail(RZ_ERR_ARG, "batch larger than rz_net_reserve()d (no allocation on the launch path)");
     launch_trunk(net, d_obs, net->d_feat, n_boards, stream);
-    if (hipGetLastError() != hipSuccess) return net_fail(RZ_ERR_HIP, "launch of k_trunk failed");
+    RZ_TRY(rz_launched("k_trunk"));
     return launch_heads(net, net->d_feat, n_boards, d_logp, d_value, stream);
 }
 

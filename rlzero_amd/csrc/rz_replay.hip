@@ -16,8 +16,7 @@
 #include <vector>
 
 #include "rlzero_hip.h"
-
-void rz_set_error(const char *msg);  // rz_engine.hip
+#include "rz_host.h"
 
 namespace {
 
@@ -158,11 +157,6 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_sample(ReplayDev R, unsign
     replay_emit(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
 }
 
-int rp_fail(int code, const char *msg) {
-    rz_set_error(msg);
-    return code;
-}
-
 }  // namespace
 
 struct rz_replay {
@@ -171,61 +165,21 @@ struct rz_replay {
     long long cursor = 0, count = 0;   // next slot written; positions held
     int16_t *d_tables = nullptr;
     bool tables = false;
-    // one staging pair (pinned host + device), reused: the host half after `copied`, the device half after `consumed`
-    void *h_stage = nullptr, *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    hipEvent_t copied = nullptr, consumed = nullptr;
-    bool in_flight = false;
+    DevPool pool;    // the store
+    Staging stage;   // what the host hands to a launch
 };
 
 namespace {
 
 int rp_ready(rz_replay *r) {
-    if (r == nullptr) return rp_fail(RZ_ERR_ARG, "replay handle is NULL");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipGetDevice failed");
-    if (cur != r->device && hipSetDevice(r->device) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    return RZ_OK;
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "replay handle is NULL");
+    return rz_on_device(r->device);
 }
-
-// the staging pair with room for `bytes`, its host half free to be written; `stream` waits for the device half's last reader
-int rp_stage(rz_replay *r, size_t bytes, hipStream_t stream) {
-    if (r->in_flight && hipEventSynchronize(r->copied) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventSynchronize failed (replay staging)");
-    if (bytes > r->stage_bytes) {
-        if (r->in_flight && hipEventSynchronize(r->consumed) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventSynchronize failed (replay staging)");
-        r->in_flight = false;
-        if (r->h_stage) (void)hipHostFree(r->h_stage);
-        if (r->d_stage) (void)hipFree(r->d_stage);
-        r->h_stage = r->d_stage = nullptr;
-        r->stage_bytes = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc(&r->h_stage, want, hipHostMallocDefault) != hipSuccess) return rp_fail(RZ_ERR_OOM, "hipHostMalloc failed (replay staging)");
-        if (hipMalloc(&r->d_stage, want) != hipSuccess) return rp_fail(RZ_ERR_OOM, "hipMalloc failed (replay staging)");
-        r->stage_bytes = want;
-    }
-    if (r->in_flight && hipStreamWaitEvent(stream, r->consumed, 0) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipStreamWaitEvent failed (replay staging)");
-    return RZ_OK;
-}
-
-int rp_upload(rz_replay *r, size_t bytes, hipStream_t stream) {
-    if (hipMemcpyAsync(r->d_stage, r->h_stage, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "staging copy failed (replay)");
-    if (hipEventRecord(r->copied, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventRecord failed (replay)");
-    return RZ_OK;
-}
-
-int rp_launched(rz_replay *r, hipStream_t stream, const char *what) {
-    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, what);
-    if (hipEventRecord(r->consumed, stream) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipEventRecord failed (replay)");
-    r->in_flight = true;
-    return RZ_OK;
-}
-
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 int rp_outputs(rz_replay *r, int64_t n, const float *d_states, const float *d_pis, const float *d_zs) {
-    if (!r->tables) return rp_fail(RZ_ERR_ARG, "rz_replay_set_tables has not been called");
-    if (n < 0 || n > 0x7fffffffLL) return rp_fail(RZ_ERR_ARG, "n out of range");
-    if (n > 0 && (d_states == nullptr || d_pis == nullptr || d_zs == nullptr)) return rp_fail(RZ_ERR_ARG, "NULL output buffer");
+    if (!r->tables) return rz_fail(RZ_ERR_ARG, "rz_replay_set_tables has not been called");
+    if (n < 0 || n > 0x7fffffffLL) return rz_fail(RZ_ERR_ARG, "n out of range");
+    if (n > 0 && (d_states == nullptr || d_pis == nullptr || d_zs == nullptr)) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
     return RZ_OK;
 }
 
@@ -237,37 +191,35 @@ inline long long rp_oldest(const rz_replay *r) { return ((r->cursor - r->count) 
 extern "C" {
 
 int rz_replay_create(int32_t board_size, int64_t capacity, int32_t device, rz_replay **out) {
-    if (out == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    if (out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (board_size < 3 || board_size > RZ_MAX_BOARD_SIZE) return rp_fail(RZ_ERR_ARG, "board_size outside 3 .. 16");
-    if (capacity < 1 || capacity > (1LL << 24)) return rp_fail(RZ_ERR_ARG, "capacity outside 1 .. 2^24 positions");
+    if (board_size < 3 || board_size > RZ_MAX_BOARD_SIZE) return rz_fail(RZ_ERR_ARG, "board_size outside 3 .. 16");
+    if (capacity < 1 || capacity > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "capacity outside 1 .. 2^24 positions");
     int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rp_fail(RZ_ERR_ARG, "bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return rp_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     rz_replay *r = new (std::nothrow) rz_replay();
-    if (!r) return rp_fail(RZ_ERR_OOM, "host allocation failed");
+    if (!r) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     r->board = board_size;
     r->device = device;
     ReplayDev &D = r->dev;
     D.A = board_size * board_size;
     D.capacity = capacity;
     const size_t cap = (size_t)capacity, A = (size_t)D.A;
-    bool ok = hipMalloc((void **)&D.stones, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void **)&D.meta, cap * sizeof(int32_t)) == hipSuccess && hipMalloc((void **)&D.pi, cap * A * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&r->d_tables, 2 * 8 * A * sizeof(int16_t)) == hipSuccess && hipMalloc((void **)&D.err, sizeof(int32_t)) == hipSuccess;
+    bool ok = r->pool.alloc(&D.stones, capacity * kRecWords) == RZ_OK && r->pool.alloc(&D.meta, capacity) == RZ_OK && r->pool.alloc(&D.pi, capacity * D.A) == RZ_OK &&
+              r->pool.alloc(&r->d_tables, 2 * 8 * D.A) == RZ_OK && r->pool.alloc(&D.err, 1) == RZ_OK;
     if (!ok) {
         rz_replay_destroy(r);
-        return rp_fail(RZ_ERR_OOM, "hipMalloc failed (replay store)");
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (replay store)");
     }
     D.src_state = r->d_tables;
     D.src_pi = r->d_tables + 8 * A;
     ok = hipMemset(D.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(D.stones, 0, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
          hipMemset(D.meta, 0, cap * sizeof(int32_t)) == hipSuccess && hipMemset(D.pi, 0, cap * A * sizeof(float)) == hipSuccess &&
-         hipEventCreateWithFlags(&r->copied, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&r->consumed, hipEventDisableTiming) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+         r->stage.create("replay") == RZ_OK && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         rz_replay_destroy(r);
-        return rp_fail(RZ_ERR_HIP, "initialisation of the replay store failed");
+        return rz_fail(RZ_ERR_HIP, "initialisation of the replay store failed");
     }
     *out = r;
     return RZ_OK;
@@ -277,40 +229,31 @@ int rz_replay_destroy(rz_replay *r) {
     if (r == nullptr) return RZ_OK;
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
-    if (r->copied) (void)hipEventDestroy(r->copied);
-    if (r->consumed) (void)hipEventDestroy(r->consumed);
-    if (r->h_stage) (void)hipHostFree(r->h_stage);
-    void *dev[] = {r->d_stage, r->dev.stones, r->dev.meta, r->dev.pi, r->d_tables, r->dev.err};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    delete r;
+    r->stage.destroy();
+    delete r;   // (the pool frees the store)
     return RZ_OK;
 }
 
 int rz_replay_set_tables(rz_replay *r, const int16_t *h_src_state, const int16_t *h_src_pi, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (h_src_state == nullptr || h_src_pi == nullptr) return rp_fail(RZ_ERR_ARG, "NULL table");
+    RZ_ENTER(rp_ready, r);
+    if (h_src_state == nullptr || h_src_pi == nullptr) return rz_fail(RZ_ERR_ARG, "NULL table");
     const int A = r->dev.A;
     for (int i = 0; i < 8 * A; ++i)
-        if (h_src_state[i] < 0 || h_src_state[i] >= A || h_src_pi[i] < 0 || h_src_pi[i] >= A) return rp_fail(RZ_ERR_ARG, "table entry outside 0 .. A-1");
+        if (h_src_state[i] < 0 || h_src_state[i] >= A || h_src_pi[i] < 0 || h_src_pi[i] >= A) return rz_fail(RZ_ERR_ARG, "table entry outside 0 .. A-1");
     hipStream_t s = (hipStream_t)stream;
     const size_t half = (size_t)8 * A * sizeof(int16_t);
-    rc = rp_stage(r, 2 * half, s);
-    if (rc != RZ_OK) return rc;
-    memcpy(r->h_stage, h_src_state, half);
-    memcpy((char *)r->h_stage + half, h_src_pi, half);
-    rc = rp_upload(r, 2 * half, s);
-    if (rc != RZ_OK) return rc;
-    if (hipMemcpyAsync(r->d_tables, r->d_stage, 2 * half, hipMemcpyDeviceToDevice, s) != hipSuccess) return rp_fail(RZ_ERR_HIP, "table copy failed (replay)");
-    rc = rp_launched(r, s, "table copy failed (replay)");
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.reserve(2 * half, s));
+    memcpy(r->stage.h, h_src_state, half);
+    memcpy((char *)r->stage.h + half, h_src_pi, half);
+    RZ_TRY(r->stage.upload(2 * half, s));
+    RZ_HIP(hipMemcpyAsync(r->d_tables, r->stage.d, 2 * half, hipMemcpyDeviceToDevice, s));
+    RZ_TRY(r->stage.launched(s, "the table copy (replay)"));
     r->tables = true;
     return RZ_OK;
 }
 
 int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity) {
-    if (r == nullptr) return rp_fail(RZ_ERR_ARG, "replay handle is NULL");
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "replay handle is NULL");
     if (count) *count = r->count;
     if (cursor) *cursor = r->cursor;
     if (capacity) *capacity = r->dev.capacity;
@@ -319,52 +262,48 @@ int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capa
 
 int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
                   const int32_t *h_winner, const float *h_pi, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (n_games < 0) return rp_fail(RZ_ERR_ARG, "n_games < 0");
+    RZ_ENTER(rp_ready, r);
+    if (n_games < 0) return rz_fail(RZ_ERR_ARG, "n_games < 0");
     if (n_games == 0) return RZ_OK;
-    if (h_offsets == nullptr || h_winner == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_offsets == nullptr || h_winner == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     const int A = r->dev.A;
-    if (h_offsets[0] != 0) return rp_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
+    if (h_offsets[0] != 0) return rz_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
     std::vector<int32_t> base((size_t)n_games);
     long long kept = 0;
     for (int g = 0; g < n_games; ++g) {
         const long long P = (long long)h_offsets[g + 1] - h_offsets[g];
-        if (P < 0) return rp_fail(RZ_ERR_ARG, "h_offsets must not decrease");
-        if (P > A) return rp_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
-        if (h_winner[g] < -1 || h_winner[g] > 1) return rp_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
-        if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rp_fail(RZ_ERR_ARG, "NULL argument");
+        if (P < 0) return rz_fail(RZ_ERR_ARG, "h_offsets must not decrease");
+        if (P > A) return rz_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
+        if (h_winner[g] < -1 || h_winner[g] > 1) return rz_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
+        if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rz_fail(RZ_ERR_ARG, "NULL argument");
         base[(size_t)g] = (int32_t)kept;
         for (int p = h_offsets[g]; p < h_offsets[g + 1]; ++p) {
-            if (h_moves[p] < 0 || h_moves[p] >= A) return rp_fail(RZ_ERR_ARG, "a move is outside the board");
+            if (h_moves[p] < 0 || h_moves[p] >= A) return rz_fail(RZ_ERR_ARG, "a move is outside the board");
             kept += h_keep[p] != 0;
         }
     }
     const long long total = h_offsets[n_games];
     if (kept == 0) return RZ_OK;
-    if (h_pi == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_pi == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     // staging: offsets | base | winner | moves | keep | pi rows
     const size_t o_off = 0, o_base = o_off + align16(((size_t)n_games + 1) * 4), o_win = o_base + align16((size_t)n_games * 4),
                  o_moves = o_win + align16((size_t)n_games * 4), o_keep = o_moves + align16((size_t)total * 4),
                  o_pi = o_keep + align16((size_t)total), bytes = o_pi + (size_t)kept * A * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    rc = rp_stage(r, bytes, s);
-    if (rc != RZ_OK) return rc;
-    char *h = (char *)r->h_stage, *d = (char *)r->d_stage;
+    RZ_TRY(r->stage.reserve(bytes, s));
+    char *h = (char *)r->stage.h, *d = (char *)r->stage.d;
     memcpy(h + o_off, h_offsets, ((size_t)n_games + 1) * 4);
     memcpy(h + o_base, base.data(), (size_t)n_games * 4);
     memcpy(h + o_win, h_winner, (size_t)n_games * 4);
     memcpy(h + o_moves, h_moves, (size_t)total * 4);
     memcpy(h + o_keep, h_keep, (size_t)total);
     memcpy(h + o_pi, h_pi, (size_t)kept * A * sizeof(float));
-    rc = rp_upload(r, bytes, s);
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.upload(bytes, s));
     const long long cap = r->dev.capacity, skip = kept > cap ? kept - cap : 0;
     hipLaunchKernelGGL(k_replay_add, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
                        (const int32_t *)(d + o_win), (const int32_t *)(d + o_moves), (const uint8_t *)(d + o_keep), (const float *)(d + o_pi),
                        r->cursor, skip);
-    rc = rp_launched(r, s, "k_replay_add launch failed");
-    if (rc != RZ_OK) return rc;
+    RZ_TRY(r->stage.launched(s, "k_replay_add"));
     r->cursor = (r->cursor + kept) % cap;
     r->count = r->count + kept > cap ? cap : r->count + kept;
     return RZ_OK;
@@ -372,50 +311,40 @@ int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const
 
 int rz_replay_gather(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, int64_t n, float *d_states, float *d_pis,
                      float *d_zs, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    rc = rp_outputs(r, n, d_states, d_pis, d_zs);
-    if (rc != RZ_OK) return rc;
-    if ((h_indices == nullptr) == (d_indices == nullptr)) return rp_fail(RZ_ERR_ARG, "exactly one of h_indices / d_indices");
+    RZ_ENTER(rp_ready, r);
+    RZ_TRY(rp_outputs(r, n, d_states, d_pis, d_zs));
+    if ((h_indices == nullptr) == (d_indices == nullptr)) return rz_fail(RZ_ERR_ARG, "exactly one of h_indices / d_indices");
     if (n == 0) return RZ_OK;
     const long long n_entries = 8 * r->count;
-    if (n_entries == 0) return rp_fail(RZ_ERR_ARG, "the replay buffer is empty");
+    if (n_entries == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
     const long long *idx = (const long long *)d_indices;
     if (h_indices != nullptr) {
         for (int64_t i = 0; i < n; ++i)
-            if (h_indices[i] < 0 || h_indices[i] >= n_entries) return rp_fail(RZ_ERR_ARG, "entry index outside 0 .. 8 * count - 1");
-        rc = rp_stage(r, (size_t)n * 8, s);
-        if (rc != RZ_OK) return rc;
-        memcpy(r->h_stage, h_indices, (size_t)n * 8);
-        rc = rp_upload(r, (size_t)n * 8, s);
-        if (rc != RZ_OK) return rc;
-        idx = (const long long *)r->d_stage;
+            if (h_indices[i] < 0 || h_indices[i] >= n_entries) return rz_fail(RZ_ERR_ARG, "entry index outside 0 .. 8 * count - 1");
+        RZ_TRY(r->stage.reserve((size_t)n * 8, s));
+        memcpy(r->stage.h, h_indices, (size_t)n * 8);
+        RZ_TRY(r->stage.upload((size_t)n * 8, s));
+        idx = (const long long *)r->stage.d;
     }
     hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
-    if (h_indices != nullptr) return rp_launched(r, s, "k_replay_gather launch failed");
-    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, "k_replay_gather launch failed");
-    return RZ_OK;
+    return h_indices != nullptr ? r->stage.launched(s, "k_replay_gather") : rz_launched("k_replay_gather");
 }
 
 int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_states, float *d_pis, float *d_zs, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    rc = rp_outputs(r, n, d_states, d_pis, d_zs);
-    if (rc != RZ_OK) return rc;
+    RZ_ENTER(rp_ready, r);
+    RZ_TRY(rp_outputs(r, n, d_states, d_pis, d_zs));
     const long long n_entries = 8 * r->count;
-    if (n_entries == 0) return rp_fail(RZ_ERR_ARG, "the replay buffer is empty");
+    if (n_entries == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
     if (n == 0) return RZ_OK;
     hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
                        (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
-    if (hipGetLastError() != hipSuccess) return rp_fail(RZ_ERR_HIP, "k_replay_sample launch failed");
-    return RZ_OK;
+    return rz_launched("k_replay_sample");
 }
 
 int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (first < 0 || n < 0 || first + n > r->count) return rp_fail(RZ_ERR_ARG, "positions outside 0 .. count - 1");
+    RZ_ENTER(rp_ready, r);
+    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "positions outside 0 .. count - 1");
     hipStream_t s = (hipStream_t)stream;
     const long long cap = r->dev.capacity, start = (rp_oldest(r) + first) % cap;
     const long long n1 = n < cap - start ? n : cap - start;   // up to the ring's end, then from its start
@@ -428,18 +357,17 @@ int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, i
         if (h_meta) ok = ok && hipMemcpyAsync(h_meta + at, r->dev.meta + from, (size_t)cnt * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
         if (h_pi) ok = ok && hipMemcpyAsync(h_pi + at * A, r->dev.pi + from * A, (size_t)cnt * A * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
     }
-    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rp_fail(RZ_ERR_HIP, "read-back failed (replay)");
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rz_fail(RZ_ERR_HIP, "read-back failed (replay)");
     return RZ_OK;
 }
 
 int rz_replay_poll_errors(rz_replay *r, int32_t *flags, void *stream) {
-    int rc = rp_ready(r);
-    if (rc != RZ_OK) return rc;
-    if (flags == nullptr) return rp_fail(RZ_ERR_ARG, "NULL argument");
+    RZ_ENTER(rp_ready, r);
+    if (flags == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemcpyAsync(flags, r->dev.err, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemsetAsync(r->dev.err, 0, sizeof(int32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return rp_fail(RZ_ERR_HIP, "reading the replay flags failed");
+        return rz_fail(RZ_ERR_HIP, "reading the replay flags failed");
     return RZ_OK;
 }
 
