@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 37
+#define RZ_ABI_VERSION 38
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -911,6 +911,37 @@ int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, floa
                      void *stream);
 int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream);
 int rz_replay_poll_errors(rz_replay *r, int32_t *flags, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Reanalyse for the device replay buffer (ABI 38; rz_replay.hip: k_replay_positions, k_replay_update_pi; rz_replay_rules.h;
+ * rlzero_amd/replay.py: ReplayReanalyser): the two device ends of searching stored positions again with the current network.
+ * Between them the caller hands the roots to a search engine (rz_set_roots takes exactly these arrays), searches, and reads the
+ * visit counts (rz_root_visits).  No function or kernel above changes.
+ *
+ * rz_replay_positions: n positions in ONE launch (k_replay_positions: a thread per position and record word).  Position i (0 = the
+ *   oldest held) is resolved to its physical ring slot, written to d_where int32 [n], and its record is written as a root in the
+ *   engine's layout: d_stones uint64 [n][2][RZ_BOARD_WORDS] by PLAYER (the record's mover is player `parity`, its opponent
+ *   1 - parity), d_to_move int32 [n] = the ply's parity, d_last_move int32 [n] = (meta & 511) - 1.  The indices are int64, from
+ *   the host (h_indices: checked here, RZ_ERR_ARG for one outside 0 .. count - 1, and staged), from the device (d_indices: checked
+ *   by the kernel), or, both NULL, the device's own draws of refresh `step`: position i is mulhi64(x, count) of
+ *   x = sm(sm(sm(seed ^ "azreanal") ^ step) ^ i) -- uniform over POSITIONS, not entries: the eight symmetries of a position share
+ *   one pi row (rlzero_amd/replay.py: replay_reanalyse_draws gives the same bits; the salt keeps a refresh and a mini-batch of
+ *   one update number apart).  seed and step are ignored when indices are given.  A device index out of range: where = -1,
+ *   nothing else written for the row, bit 1 of the flags of rz_replay_poll_errors set.  RZ_ERR_ARG on an empty buffer.
+ *   *ticket receives the number of positions EVER stored in this handle (host state, advanced by rz_replay_add), also for n = 0.
+ * rz_replay_update_pi: ONE launch (k_replay_update_pi: a workgroup per row, a thread per action).  For every row with
+ *   0 <= where < capacity it writes pi[where][a] = (float)((double)max(N[a], 0) / (double)sum) from d_visits int32 [n][A], the sum
+ *   taken over max(N, 0) in int64 (an integer reduction: exact in any order) -- the visit distribution, i.e. the reference's pi
+ *   at temperature 1 up to rounding (a documented deviation from its softmax(log(N + 1e-10)) expression).  A sum of 0, or any
+ *   other where -- the -1 of a refused or a padding row -- writes nothing; stones and meta are never written.  `ticket` must be what
+ *   rz_replay_positions returned and still be the handle's counter: an add in between may have given a slot to another position,
+ *   and the result of a search must never land there -- RZ_ERR_ARG, no launch.  Two rows that name one slot BOTH write it: the
+ *   search is deterministic, so they carry the same bits.
+ * rz_replay_ticket: the handle's counter as it is now (rz_replay_state keeps its three values). */
+int rz_replay_ticket(rz_replay *r, int64_t *ticket);
+int rz_replay_positions(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, uint64_t seed, uint64_t step, int64_t n,
+                        int32_t *d_where, uint64_t *d_stones, int32_t *d_to_move, int32_t *d_last_move, int64_t *ticket, void *stream);
+int rz_replay_update_pi(rz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, int64_t ticket, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * MuZero device replay (ABI 35; rz_mz_replay.hip, rz_mz_target.h; an opt-in extension beside the host ReplayBuffer of

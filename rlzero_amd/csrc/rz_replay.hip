@@ -1,4 +1,4 @@
-// rz_replay.hip -- the device replay buffer (include/rlzero_hip.h: rz_replay_*, ABI 31).
+// rz_replay.hip -- the device replay buffer (include/rlzero_hip.h: rz_replay_*, ABI 31; Reanalyse, ABI 38).
 //
 // The learner's samples live in device memory as a ring of self-contained positions (two bitboards, one meta word, a pi row) and
 // a mini-batch is ONE launch: k_replay_gather / k_replay_sample write the observation planes, the symmetry-transformed pi and z
@@ -17,6 +17,7 @@
 
 #include "rlzero_hip.h"
 #include "rz_host.h"
+#include "rz_replay_rules.h"
 
 namespace {
 
@@ -157,12 +158,65 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_sample(ReplayDev R, unsign
     replay_emit(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
 }
 
+// Reanalyse, the way out: position index -> ring slot (`where`, -1 for an index outside 0 .. count - 1) and the stored record as a
+// root of the search engine.  A thread per (row, record word): word j of the record goes to rzrr::root_word of row i; thread 0 of a
+// row also writes the slot, the side to move and the last move.  indices NULL: the draws of refresh `step` made here.  A bad index
+// sets the flag and writes only where[i] = -1: nothing of the store is read for it and its root is left as it was.
+__global__ __launch_bounds__(kMaxCells) void k_replay_positions(ReplayDev R, const long long *__restrict__ indices, unsigned long long seed,
+                                                                 unsigned long long step, long long oldest, long long count, long long n,
+                                                                 int32_t *__restrict__ where, unsigned long long *__restrict__ stones,
+                                                                 int32_t *__restrict__ to_move, int32_t *__restrict__ last_move) {
+    const long long tid = (long long)blockIdx.x * kMaxCells + threadIdx.x;
+    const long long i = tid / kRecWords;
+    const int j = (int)(tid % kRecWords);
+    if (i >= n) return;
+    const long long index = indices != nullptr ? indices[i] : rzrr::reanalyse_position(seed, step, (uint64_t)i, (uint64_t)count);
+    const long long slot = rzrr::slot_of_position(index, oldest, count, R.capacity);
+    if (slot < 0) {
+        if (j == 0) {
+            atomicOr(R.err, kFlagBadIndex);
+            where[i] = -1;
+        }
+        return;
+    }
+    const int32_t meta = R.meta[slot];
+    stones[i * kRecWords + rzrr::root_word(meta, j)] = R.stones[slot * kRecWords + j];
+    if (j == 0) {
+        where[i] = (int32_t)slot;
+        to_move[i] = rzrr::root_to_move(meta);
+        last_move[i] = rzrr::root_last_move(meta);
+    }
+}
+
+// Reanalyse, the way back: pi[where[i]][a] = N[i][a] / sum N[i] (rzrr::pi_of_visits).  A workgroup per row, a thread per action
+// (blockDim.x = A rounded up to whole waves).  The sum is an INTEGER reduction -- across the lanes of a wave, then across the waves
+// through LDS -- so it is exact whatever the order.  where < 0 (a refused or a padding row), a slot outside the capacity or a sum of
+// 0 writes nothing; stones and meta are never written.  Every branch before the barrier is uniform across the workgroup.
+__global__ __launch_bounds__(kMaxCells) void k_replay_update_pi(ReplayDev R, const int32_t *__restrict__ where, const int32_t *__restrict__ visits) {
+    __shared__ long long s_part[kMaxCells / 64];
+    const long long i = blockIdx.x;
+    const int a = threadIdx.x, A = R.A, lane = a & 63, wave = a >> 6;
+    const long long slot = where[i];
+    if (slot < 0 || slot >= R.capacity) return;
+    const int32_t mine = a < A ? visits[i * A + a] : 0;
+    long long part = rzrr::visit_count(mine);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+    if (lane == 0) s_part[wave] = part;
+    __syncthreads();
+    long long sum = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) sum += s_part[w];
+    if (sum == 0 || a >= A) return;
+    R.pi[slot * A + a] = rzrr::pi_of_visits(mine, sum);
+}
+
 }  // namespace
 
 struct rz_replay {
     ReplayDev dev = {};
     int board = 0, device = 0;
     long long cursor = 0, count = 0;   // next slot written; positions held
+    long long stored = 0;              // positions ever stored: the ticket of rz_replay_positions / rz_replay_update_pi
     int16_t *d_tables = nullptr;
     bool tables = false;
     DevPool pool;    // the store
@@ -306,6 +360,7 @@ int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const
     RZ_TRY(r->stage.launched(s, "k_replay_add"));
     r->cursor = (r->cursor + kept) % cap;
     r->count = r->count + kept > cap ? cap : r->count + kept;
+    r->stored += kept;
     return RZ_OK;
 }
 
@@ -340,6 +395,50 @@ int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, floa
     hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
                        (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
     return rz_launched("k_replay_sample");
+}
+
+int rz_replay_ticket(rz_replay *r, int64_t *ticket) {
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "replay handle is NULL");
+    if (ticket == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    *ticket = r->stored;
+    return RZ_OK;
+}
+
+int rz_replay_positions(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, uint64_t seed, uint64_t step, int64_t n,
+                        int32_t *d_where, uint64_t *d_stones, int32_t *d_to_move, int32_t *d_last_move, int64_t *ticket, void *stream) {
+    RZ_ENTER(rp_ready, r);
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (ticket == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    if (h_indices != nullptr && d_indices != nullptr) return rz_fail(RZ_ERR_ARG, "at most one of h_indices / d_indices");
+    *ticket = r->stored;
+    if (n == 0) return RZ_OK;
+    if (d_where == nullptr || d_stones == nullptr || d_to_move == nullptr || d_last_move == nullptr) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
+    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
+    hipStream_t s = (hipStream_t)stream;
+    const long long *idx = (const long long *)d_indices;
+    if (h_indices != nullptr) {
+        for (int64_t i = 0; i < n; ++i)
+            if (h_indices[i] < 0 || h_indices[i] >= r->count) return rz_fail(RZ_ERR_ARG, "position index outside 0 .. count - 1");
+        RZ_TRY(r->stage.reserve((size_t)n * 8, s));
+        memcpy(r->stage.h, h_indices, (size_t)n * 8);
+        RZ_TRY(r->stage.upload((size_t)n * 8, s));
+        idx = (const long long *)r->stage.d;
+    }
+    const unsigned blocks = (unsigned)((n * kRecWords + kMaxCells - 1) / kMaxCells);
+    hipLaunchKernelGGL(k_replay_positions, dim3(blocks), dim3(kMaxCells), 0, s, r->dev, idx, (unsigned long long)seed, (unsigned long long)step,
+                       rp_oldest(r), r->count, (long long)n, d_where, (unsigned long long *)d_stones, d_to_move, d_last_move);
+    return h_indices != nullptr ? r->stage.launched(s, "k_replay_positions") : rz_launched("k_replay_positions");
+}
+
+int rz_replay_update_pi(rz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, int64_t ticket, void *stream) {
+    RZ_ENTER(rp_ready, r);
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    // an add since rz_replay_positions may have given a slot to another position: the search's result has no home
+    if (!rzrr::ticket_current(ticket, r->stored)) return rz_fail(RZ_ERR_ARG, "stale ticket: positions were stored since rz_replay_positions");
+    if (n == 0) return RZ_OK;
+    if (d_where == nullptr || d_visits == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    hipLaunchKernelGGL(k_replay_update_pi, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, d_where, d_visits);
+    return rz_launched("k_replay_update_pi");
 }
 
 int rz_replay_read(rz_replay *r, int64_t first, int64_t n, uint64_t *h_stones, int32_t *h_meta, float *h_pi, void *stream) {

@@ -1,0 +1,89 @@
+// rz_replay_rules.h -- Reanalyse for the AlphaZero device replay (rz_replay.hip: k_replay_positions, k_replay_update_pi;
+// include/rlzero_hip.h: rz_replay_positions, rz_replay_update_pi; rlzero_amd/replay.py: ReplayReanalyser): everything about it that
+// is neither a kernel launch nor a memory access.  Plain C++, no HIP include, so that the CPU can test it against
+// rlzero_amd/replay.py (pack_positions, reanalysed_pi, replay_reanalyse_draws) and the Gomoku environment
+// (tests/test_replay_reanalyse_host.py); the kernels call these functions.  Three rules: a stored record as a root of the search
+// engine, the pi row of fresh visit counts, the draws of a refresh -- and the ticket that ties a result to the store it was drawn from.
+#pragma once
+#include <stdint.h>
+
+#include "rlzero_hip.h"
+
+#if defined(__HIPCC__)
+#define RZR_FN __host__ __device__ __forceinline__
+#else
+#define RZR_FN inline
+#endif
+
+namespace rzrr {
+
+constexpr int kMetaLastMask = 511, kMetaParityBit = 9;   // the meta word: bits 0..8 last move + 1 (0: none), bit 9 ply parity
+
+// ---- record to root.  A record holds stones[2][RZ_BOARD_WORDS] -- [0] the mover's, [1] the opponent's -- and the meta word; the
+// engine (rz_set_roots) takes stones[player][word] with player 0 = the first player, the side to move and the last move (-1: none).
+// The ply's parity IS the mover's player id: the first player moves at the even plies.
+RZR_FN int32_t root_to_move(int32_t meta) { return (meta >> kMetaParityBit) & 1; }
+RZR_FN int32_t root_last_move(int32_t meta) { return (meta & kMetaLastMask) - 1; }
+// the player whose stones the record's `side` (0 the mover's, 1 the opponent's) holds
+RZR_FN int root_player(int32_t meta, int side) { return side == 0 ? root_to_move(meta) : 1 - root_to_move(meta); }
+// word j = side * RZ_BOARD_WORDS + w of a record -> its place among the 2 * RZ_BOARD_WORDS words of the root
+RZR_FN int root_word(int32_t meta, int j) { return root_player(meta, j / RZ_BOARD_WORDS) * RZ_BOARD_WORDS + j % RZ_BOARD_WORDS; }
+// the whole record at once (the CPU's use; the kernel places a word per thread through root_word)
+RZR_FN void root_of_record(const uint64_t *rec, int32_t meta, uint64_t *stones, int32_t *to_move, int32_t *last_move) {
+    for (int j = 0; j < 2 * RZ_BOARD_WORDS; ++j) stones[root_word(meta, j)] = rec[j];
+    *to_move = root_to_move(meta);
+    *last_move = root_last_move(meta);
+}
+
+// ---- pi of visits: the visit distribution N / sum N, i.e. softmax(log(N + 1e-10)) of the reference at T = 1 up to rounding (the
+// numpy expression itself is not reproducible on the device: a documented deviation, bounded in the host test).  Counts below 0
+// count as 0; the sum is an integer, exact in any order; one fp64 division, cast to float32 once.  A sum of 0: no row is written.
+RZR_FN int64_t visit_count(int32_t n) { return n > 0 ? (int64_t)n : 0; }
+RZR_FN int64_t visit_sum(const int32_t *visits, int A) {
+    int64_t sum = 0;
+    for (int a = 0; a < A; ++a) sum += visit_count(visits[a]);
+    return sum;
+}
+// (sum > 0)
+RZR_FN float pi_of_visits(int32_t n, int64_t sum) { return (float)((double)visit_count(n) / (double)sum); }
+
+// ---- the draws of reanalyse_sample (rlzero_amd/replay.py: replay_reanalyse_draws, the same bits): position i of refresh `step` is
+// the high half of x * positions_held for the 64-bit x of a splitmix64 chain over (seed ^ salt, step, i) -- uniform over POSITIONS
+// (the eight symmetries of a position share one pi row), within 2^-64.  The salt keeps a refresh and a mini-batch
+// (rz_replay_sample: "replay") of one update number apart.
+RZR_FN uint64_t mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+RZR_FN uint64_t mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+constexpr uint64_t kReanalyseSalt = 0x617A7265616E616Cull;   // "azreanal"
+
+RZR_FN int64_t reanalyse_position(uint64_t seed, uint64_t step, uint64_t i, uint64_t positions_held) {
+    uint64_t x = mix64(seed ^ kReanalyseSalt);
+    x = mix64(x ^ step);
+    x = mix64(x ^ i);
+    return (int64_t)mulhi64(x, positions_held);
+}
+
+// ---- a position index (0 = the oldest held) to its ring slot, or -1 for an index outside 0 .. count - 1
+RZR_FN int64_t slot_of_position(int64_t index, int64_t oldest, int64_t count, int64_t capacity) {
+    if (index < 0 || index >= count) return -1;
+    return (oldest + index) % capacity;
+}
+
+// ---- the ticket: the number of positions EVER stored in the handle when rz_replay_positions resolved a request.  A count, not the
+// write cursor: the cursor returns to the same slot after `capacity` positions, the count never does.  A result may be written
+// only while nothing was stored in between -- a slot may hold another position by then.
+RZR_FN bool ticket_current(int64_t ticket, int64_t stored) { return ticket == stored; }
+
+}  // namespace rzrr

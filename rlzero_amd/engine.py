@@ -779,6 +779,23 @@ class MCTSEngine(object):
                                     mptr, 1 if reset_trees else 0, self.stream()), 'rz_set_roots')
         self.roots_epoch += 1
 
+    def set_roots_device(self, stones, to_move, last_move, mask=None, reset_trees=False):
+        """``set_roots`` for roots that are already in device memory (rz_replay_positions writes them there): stones int64 (the
+        uint64 bits) [G,2,WORDS], to_move / last_move int32 [G], mask uint8 [G] or None -- contiguous tensors on this engine's
+        device, read by rz_set_roots on the current stream.  No copy and no wait; pending priors are flushed first and the roots'
+        epoch moves, as in ``set_roots``."""
+        t, G = self.torch, self.n_games
+        want = [('stones', stones, t.int64, (G, 2, WORDS)), ('to_move', to_move, t.int32, (G, )), ('last_move', last_move, t.int32, (G, ))]
+        if mask is not None:
+            want.append(('mask', mask, t.uint8, (G, )))
+        for name, x, dtype, shape in want:
+            if not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError('set_roots_device: %s must be a contiguous %s tensor of shape %r on %s' % (name, dtype, shape, self.device))
+        self.flush_deferred()   # (pending priors belong to the trees as they are)
+        check(self.lib.rz_set_roots(self.handle, _ptr(stones), _ptr(to_move), _ptr(last_move), None if mask is None else _ptr(mask),
+                                    1 if reset_trees else 0, self.stream()), 'rz_set_roots')
+        self.roots_epoch += 1
+
     def reset_games(self, mask=None):
         """Empty boards, player 0 to move, fresh trees for the selected games."""
         G = self.n_games
@@ -1234,6 +1251,13 @@ class MCTSEngine(object):
             done.synchronize()
             return self._visits_host.numpy().copy()
         return self.visits.cpu().numpy()
+
+    def root_visits_device(self):
+        """The visit counts of the roots' children, left on the device: int32 [G, A] (``self.visits``, valid on the current stream
+        until the next read-out).  Enqueues rz_root_visits and nothing else -- no host copy, no wait, and pending priors stay
+        pending: the counts do not depend on them."""
+        check(self.lib.rz_root_visits(self.handle, _ptr(self.visits), self.stream()), 'rz_root_visits')
+        return self.visits
 
     def root_wsum(self):
         check(self.lib.rz_root_wsum(self.handle, _ptr(self.wsum), self.stream()), 'rz_root_wsum')

@@ -19,6 +19,18 @@ SURVEY.md D-9): for an odd number of quarter turns the planes turn one way and p
 ``sample`` draws WITH replacement -- entry i of update ``step`` is ``replay_index(seed, step, i, len(buffer))``, a counter-based
 uniform -- where the reference's ``random.sample`` draws without: a documented deviation; ``gather`` takes whatever indices the
 caller drew.
+
+Reanalyse (``ReplayReanalyser``, below): a stored pi row is frozen at the search that played the move -- the network of that time,
+under Dirichlet noise, on a reused subtree -- while a position stays in the ring for many rounds.  ``ReplayReanalyser`` searches
+stored positions again with the CURRENT network, from a fresh root without noise, and rewrites their pi rows in place; the two
+device ends are ``DeviceReplay.position_roots`` (records -> roots of a search engine) and ``DeviceReplay.update_pi`` (visit counts -> pi
+rows).  What is refreshed and what is not:
+
+* the new row is the VISIT DISTRIBUTION ``N / sum(N)`` (``reanalysed_pi``), i.e. the reference's pi at temperature 1 up to rounding
+  -- not its ``softmax(log(N + 1e-10))`` expression, which is not reproducible on the device: a documented deviation (bounded in
+  tests/test_replay_reanalyse_host.py).  A ``pi_temperature`` or temperature schedule of the self-play run is NOT reapplied;
+* z is never refreshed: it is the outcome of the game that was played;
+* the fast plies of a playout cap are not in the buffer, so they are not refreshed either.
 """
 import ctypes
 
@@ -86,6 +98,43 @@ def replay_index(seed, step, i, n_entries):
     x = sm(x ^ (int(step) & _MASK))
     x = sm(x ^ (int(i) & _MASK))
     return (x * n_entries) >> 64
+
+
+_REANALYSE_SALT = 0x617A7265616E616C   # "azreanal" (csrc/rz_replay_rules.h: kReanalyseSalt): a refresh and a mini-batch share no draw
+_MAX_REQUEST = 1 << 20                 # positions resolved by one ``position_roots`` launch
+
+
+def replay_reanalyse_draws(seed, step, n, positions):
+    """The positions ``ReplayReanalyser.reanalyse_sample(n, step)`` refreshes in a buffer holding ``positions`` of them, in Python
+    integers -- the device's bits (k_replay_positions; csrc/rz_replay_rules.h: reanalyse_position): position i of refresh ``step``
+    is the high half of x * positions for the 64-bit x of the splitmix64 chain over (seed ^ "azreanal", step, i).  Uniform over
+    POSITIONS (0 = the oldest held), with replacement: the eight symmetries of a position share one pi row.  -> int64 [n]."""
+    positions = int(positions)
+    if positions <= 0:
+        raise ValueError('draws need at least one position')
+
+    def sm(x):
+        x = (x + 0x9E3779B97F4A7C15) & _MASK
+        z = x
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
+        return z ^ (z >> 31)
+    base = sm(sm((int(seed) & _MASK) ^ _REANALYSE_SALT) ^ (int(step) & _MASK))
+    return np.array([(sm(base ^ (i & _MASK)) * positions) >> 64 for i in range(int(n))], dtype=np.int64).reshape(-1)
+
+
+def reanalysed_pi(visits):
+    """The pi rows ``DeviceReplay.update_pi`` writes for these visit counts (int [n, A]), in numpy -- the device's bits
+    (csrc/rz_replay_rules.h: pi_of_visits): counts below 0 count as 0, the sum is an exact integer, ONE float64 division per entry,
+    cast to float32.  -> (pi float32 [n, A], written bool [n]); a row whose counts sum to 0 is not written (its pi here: zeros)."""
+    n = np.maximum(np.asarray(visits).astype(np.int64), 0)
+    if n.ndim != 2:
+        raise ValueError('visits: [n, A]')
+    total = n.sum(axis=1)
+    written = total > 0
+    pi = np.zeros(n.shape, dtype=np.float32)
+    pi[written] = (n[written].astype(np.float64) / total[written, None].astype(np.float64)).astype(np.float32)
+    return pi, written
 
 
 def pack_positions(trajectories, board_size):
@@ -228,6 +277,69 @@ class DeviceReplay(object):
                                              zs.data_ptr(), self._stream()), 'rz_replay_sample')
         return states, pis, zs
 
+    # ------------------------------------------------------------------ Reanalyse: the two device ends
+    @property
+    def ticket(self):
+        """The number of positions EVER stored in this buffer (advanced by ``add``): what ``position_roots`` hands out and ``update_pi``
+        compares."""
+        out = ctypes.c_int64()
+        _hip.check(self.lib.rz_replay_ticket(self.handle, ctypes.byref(out)), 'rz_replay_ticket')
+        return out.value
+
+    def position_roots(self, indices=None, n=None, seed=None, step=0, pad_to=1):
+        """Positions ``indices`` (0 = the oldest held; a numpy array / sequence, checked before the launch, or a device int64 tensor,
+        checked by the kernel) -- or, ``indices`` None, the ``n`` positions ``replay_reanalyse_draws(seed, step, n, self.positions)``
+        names, drawn on the device -- as roots of a search engine, ONE launch: -> (where int32 [m] the ring slot of each, -1 for a
+        bad device index; stones int64 [m, 2, WORDS] by player; to_move int32 [m]; last_move int32 [m]; ticket).  m = the request
+        rounded up to a multiple of ``pad_to``; the rows past the request are padding -- where -1, an empty board -- that
+        ``update_pi`` ignores.  A bad device index leaves its row as the padding is and sets the flag ``poll_errors`` reads."""
+        t = self.torch
+        h_idx = d_idx = None
+        if indices is None:
+            count = int(n)
+        elif isinstance(indices, t.Tensor):
+            if indices.device != self.device or indices.dtype != t.int64:
+                raise ValueError('device indices: an int64 tensor on %s' % (self.device, ))
+            keep = indices.contiguous().view(-1)
+            count, d_idx = keep.numel(), ctypes.c_void_p(keep.data_ptr())
+        else:
+            keep = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+            count, h_idx = len(keep), _ptr(keep)
+        pad_to = max(1, int(pad_to))
+        m = (count + pad_to - 1) // pad_to * pad_to
+        kw = dict(device=self.device)
+        where = t.full((m, ), -1, dtype=t.int32, **kw)
+        stones = t.zeros((m, 2, _hip.BOARD_WORDS), dtype=t.int64, **kw)
+        to_move = t.zeros((m, ), dtype=t.int32, **kw)
+        last_move = t.full((m, ), -1, dtype=t.int32, **kw)
+        ticket = ctypes.c_int64()
+        seed = self.seed if seed is None else int(seed)
+        _hip.check(self.lib.rz_replay_positions(self.handle, h_idx, d_idx, seed & _MASK, int(step) & _MASK, count, where.data_ptr(),
+                                                stones.data_ptr(), to_move.data_ptr(), last_move.data_ptr(), ctypes.byref(ticket),
+                                                self._stream()), 'rz_replay_positions')
+        return where, stones, to_move, last_move, ticket.value
+
+    def update_pi(self, where, visits, ticket, n=None):
+        """pi row of slot ``where[i]`` := ``reanalysed_pi(visits[i])`` for the first ``n`` rows (default: all of ``where``), one launch:
+        where int32 [>= n] and visits int32 [>= n, A], contiguous device tensors.  A row whose where is negative or whose counts sum
+        to 0 writes nothing; stones, meta and every other row stay as they are.  ``ticket``: of the ``position_roots`` call that gave
+        ``where`` -- HipError, and nothing written, if an ``add`` came in between."""
+        t = self.torch
+        n = int(where.shape[0]) if n is None else int(n)
+        for name, x, cols in (('where', where, None), ('visits', visits, self.n_actions)):
+            if (not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != t.int32 or not x.is_contiguous()
+                    or x.dim() != (1 if cols is None else 2) or (cols is not None and x.shape[1] != cols)):
+                raise ValueError('update_pi: %s must be a contiguous int32 tensor on %s%s' % (name, self.device, '' if cols is None else ', [n, %d]' % cols))
+        if n < 0 or n > int(where.shape[0]) or n > int(visits.shape[0]):
+            raise ValueError('update_pi: %d rows of %d slots and %d rows of counts' % (n, int(where.shape[0]), int(visits.shape[0])))
+        _hip.check(self.lib.rz_replay_update_pi(self.handle, where.data_ptr(), n, visits.data_ptr(), int(ticket), self._stream()), 'rz_replay_update_pi')
+
+    def poll_errors(self):
+        """The device's flag word (waits for the current stream), cleared by the call."""
+        flags = ctypes.c_int32()
+        _hip.check(self.lib.rz_replay_poll_errors(self.handle, ctypes.byref(flags), self._stream()), 'rz_replay_poll_errors')
+        return flags.value
+
     def read(self, first=0, n=None):
         """The raw records of positions ``first`` .. ``first + n - 1`` (oldest = 0), a synchronous copy: (stones uint64 [n][2][4] --
         [0] the mover's, [1] the opponent's --, meta int32 [n], pi float32 [n][A])."""
@@ -248,3 +360,125 @@ class DeviceReplay(object):
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+class ReplayReanalyser(object):
+    """Fresh searches of positions held by ``replay`` (a DeviceReplay) with ``net_module`` (a PolicyValueNet) as it is now; see the
+    module docstring for what a refreshed row holds.
+
+    It owns a private ``MCTSEngine`` of ``slots`` games without noise and a ``HipNetEvaluator`` of ``net_module``, built the way
+    ``BatchedEvaluation.for_network`` builds its pair, apart from any self-play engine.  A request is resolved in ONE ``position_roots``
+    launch and then worked off in chunks of ``slots`` rows, every chunk on the current torch stream:
+
+      ``set_roots_device(reset_trees=True)`` -> ``set_active`` (all ones; in a short last chunk only its rows) -> ``simulate`` (the
+      route the engine picks for the board: k_delta_res at 11 .. 16 rows, the resident k_trunk_split below) -> ``root_visits_device``
+      -> ``update_pi``
+
+    Nothing waits for the GPU, the error poll for indices given as a device tensor apart; ``check()`` reads the engine's and the
+    network's error flags when the caller wants them (it waits).  The trees of a chunk are thrown away by the next chunk's
+    ``reset_trees``, so the prior flush ``set_roots_device`` triggers writes priors nobody reads -- matches have the same waste;
+    profiles/ab_replay_reanalyse.py measures its share.
+
+    ``update_pi`` carries the ticket ``position_roots`` gave out: if an ``add`` comes between them (from a ``timer`` hook, say) a slot may
+    hold another position by then, and the call raises ``HipError`` instead of writing.  Two rows that name one position both write
+    it; the search is deterministic, so they write the same bits.  ``timer``: None, or a callable ``timer(label)`` called on the
+    stream between the stages ('start', 'positions', then per chunk 'roots', 'search', 'update')."""
+
+    def __init__(self, net_module, replay, n_in_row, n_playout, slots=512, c_puct=5.0, seed=0, **engine_kw):
+        from .engine import HipNetEvaluator, MCTSEngine
+        self.torch, self.replay = replay.torch, replay
+        self.device = replay.device
+        self.n_playout, self.slots = int(n_playout), int(slots)
+        if self.n_playout < 1 or self.slots < 1:
+            raise ValueError('n_playout and slots must be positive')
+        self.seed = int(seed)
+        self.step = 0   # the next refresh ``reanalyse_sample`` draws without a ``step``
+        self.engine = MCTSEngine(replay.board_size, n_in_row, n_games=self.slots, n_playout=self.n_playout, c_puct=c_puct,
+                                 device=str(self.device), add_noise=False, **engine_kw)
+        self.evaluator = HipNetEvaluator(net_module, replay.board_size, str(self.device), max_boards=self.slots)
+        self._active_rows = None   # rows the engine's active flags select now (None: whatever the engine was created with)
+        self.positions_done = 0
+        self.sims_done = 0
+        self.timer = None
+
+    def close(self):
+        eng = getattr(self, 'engine', None)
+        if eng is not None:
+            eng.close()
+            self.engine = None
+        hip = getattr(getattr(self, 'evaluator', None), 'hip', None)
+        if hip is not None:
+            hip.close()
+            self.evaluator = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def refresh_weights(self):
+        """Re-upload the network weights if the torch module changed (after a learner step)."""
+        self.evaluator.refresh_if_changed(content=True)
+
+    def check(self):
+        """Raise if a search overflowed its arena or the network left its range (waits for the GPU) -> the engine's statistics."""
+        self.evaluator.hip.check_flags()
+        return self.engine.check()
+
+    def _mark(self, label):
+        if self.timer is not None:
+            self.timer(label)
+
+    def _chunk(self, a, rows, where, stones, to_move, last_move, ticket):
+        """Rows a .. a + slots - 1 of a resolved request, of which the first ``rows`` are real: search them, write their pi back."""
+        eng, G = self.engine, self.slots
+        eng.set_roots_device(stones[a:a + G], to_move[a:a + G], last_move[a:a + G], reset_trees=True)
+        if self._active_rows != rows:
+            eng.set_active((np.arange(G) < rows).astype(np.uint8))
+            self._active_rows = rows
+        self._mark('roots')
+        eng.simulate(self.evaluator, self.n_playout)
+        self._mark('search')
+        self.replay.update_pi(where[a:a + G], eng.root_visits_device(), ticket, n=rows)
+        self._mark('update')
+        self.sims_done += self.n_playout * rows
+
+    def _request(self, n, indices=None, step=0):
+        """``n`` positions (given, or drawn on the device) resolved in one launch, then chunk by chunk."""
+        if n == 0:
+            return 0
+        self._mark('start')
+        where, stones, to_move, last_move, ticket = self.replay.position_roots(indices, n=n, seed=self.seed, step=step, pad_to=self.slots)
+        if isinstance(indices, self.torch.Tensor) and self.replay.poll_errors() & _hip.REPLAY_BAD_INDEX:
+            raise HipError('reanalyse: a position index from the device is outside 0 .. %d; nothing was refreshed' % (self.replay.positions - 1))
+        self._mark('positions')
+        for a in range(0, n, self.slots):
+            self._chunk(a, min(self.slots, n - a), where, stones, to_move, last_move, ticket)
+        self.positions_done += n
+        return n
+
+    def reanalyse(self, indices):
+        """Refresh positions ``indices`` (0 = the oldest held, as in ``read``): a numpy array / sequence (checked before any launch)
+        or a device int64 tensor (checked on the device: HipError, and nothing is refreshed).  -> their number."""
+        if isinstance(indices, self.torch.Tensor):
+            indices = indices.reshape(-1)
+        else:
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+        n = int(indices.shape[0])
+        return sum(self._request(min(_MAX_REQUEST, n - a), indices[a:a + _MAX_REQUEST]) for a in range(0, n, _MAX_REQUEST))
+
+    def reanalyse_sample(self, n, step=None):
+        """Refresh the ``n`` positions ``replay_reanalyse_draws(seed, step, n, replay.positions)`` names, drawn on the device (uniform
+        over the positions held, with replacement).  ``step``: the refresh's number; None = an internal counter, advanced by the
+        call.  -> n."""
+        n = int(n)
+        if not 0 <= n <= (1 << 24):
+            raise ValueError('n outside 0 .. 2^24')
+        if step is None:
+            step, self.step = self.step, self.step + 1
+        return self._request(n, step=step)
+
+    def reanalyse_all(self):
+        """Refresh every position held.  -> their number."""
+        return self.reanalyse(np.arange(self.replay.positions, dtype=np.int64))

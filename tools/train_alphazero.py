@@ -151,7 +151,8 @@ class TrainPipeline:
     def __init__(self, board_size=6, n_in_row=4, n_playout=400, game_batch_num=64, check_freq=50,
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
-                 device_replay=False, temperature_schedule=None, pi_temperature=None):
+                 device_replay=False, temperature_schedule=None, pi_temperature=None, reanalyse=None, reanalyse_slots=512,
+                 reanalyse_playouts=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -175,7 +176,12 @@ class TrainPipeline:
         update)), and the KL / explained variances of ``policy_update`` are computed on the device.
         ``temperature_schedule``: None or what --temperature-schedule parses to, ('step', t_early, n_plies, t_late) or ('decay',
         t_start, t_end, halflife) -- a per-ply move temperature (BatchedSelfPlay.set_temperature_schedule; batched mode only, an
-        opt-in extension); ``pi_temperature``: None (the stored pi at the ply's T, the reference's rule) or the T of the stored pi."""
+        opt-in extension); ``pi_temperature``: None (the stored pi at the ply's T, the reference's rule) or the T of the stored pi.
+        ``reanalyse`` (needs ``device_replay``, an opt-in extension): None / 0 = off -- nothing is allocated or launched --, N or
+        'all': before every round's updates rank 0 searches N drawn positions of the buffer (or all of them) again with the
+        current network and rewrites their pi rows (rlzero_amd.replay.ReplayReanalyser: the visit distribution at T = 1, z and
+        the boards untouched); ``reanalyse_slots`` positions per search batch, ``reanalyse_playouts`` simulations each (None:
+        ``n_playout``)."""
         if (temperature_schedule is not None or pi_temperature is not None) and selfplay_games_in_flight <= 0:
             raise ValueError('the temperature schedule is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.temperature_schedule = None if temperature_schedule is None else temperature_table(temperature_schedule, board_size * board_size)
@@ -185,6 +191,16 @@ class TrainPipeline:
         if int(batch_size) < 1 or int(updates_per_round) < 1:
             raise ValueError('batch_size and updates_per_round must be >= 1')
         self.device_replay, self.updates_per_round, self._updates = bool(device_replay), int(updates_per_round), 0
+        self.reanalyse = reanalyse if reanalyse == 'all' else (int(reanalyse) if reanalyse else None)
+        if self.reanalyse is not None and not device_replay:
+            raise ValueError('reanalyse needs --device-replay: it refreshes the pi rows of the device replay buffer')
+        if self.reanalyse is not None and self.reanalyse != 'all' and self.reanalyse < 0:
+            raise ValueError('reanalyse: a number of positions >= 0 or "all"')
+        self.reanalyse_slots = int(reanalyse_slots)
+        self.reanalyse_playouts = int(n_playout if reanalyse_playouts is None else reanalyse_playouts)
+        if self.reanalyse is not None and (self.reanalyse_slots < 1 or self.reanalyse_playouts < 1):
+            raise ValueError('reanalyse_slots and reanalyse_playouts must be >= 1')
+        self._reanalyser = None
         if gate_against is not None and selfplay_games_in_flight <= 0:
             raise ValueError('the gate match is a batched-mode option: selfplay_games_in_flight must be > 0')
         self.gate_against, self._gate, self._gate_rounds = gate_against, None, 0
@@ -504,6 +520,21 @@ class TrainPipeline:
                                                   explained_var_new))
         return loss, entropy
 
+    def reanalyse_round(self):
+        """Before a round's updates (rank 0, ``reanalyse`` on): stored positions searched again with the network as it is now, their
+        pi rows rewritten in the device replay buffer.  -> positions refreshed."""
+        if self.reanalyse is None or len(self.data_buffer) == 0:
+            return 0
+        if self._reanalyser is None:
+            from rlzero_amd.replay import ReplayReanalyser
+            self._reanalyser = ReplayReanalyser(self.alphazero_agent.policy_value_net, self.data_buffer, self.n_in_row,
+                                                self.reanalyse_playouts, slots=self.reanalyse_slots, c_puct=self.c_puct,
+                                                seed=self.selfplay_seed)
+        self._reanalyser.refresh_weights()
+        done = self._reanalyser.reanalyse_all() if self.reanalyse == 'all' else self._reanalyser.reanalyse_sample(self.reanalyse)
+        self._reanalyser.check()
+        return done
+
     def policy_update(self):
         """update the policy-value net."""
         if self.device_replay:
@@ -606,6 +637,7 @@ class TrainPipeline:
                 if lead:
                     print('batch i:{}, episode_len:{}'.format(i + 1, self.episode_len))
                     if len(self.data_buffer) > self.batch_size:
+                        self.reanalyse_round()
                         for _ in range(self.updates_per_round):
                             loss, entropy = self.policy_update()
                 self._sync_weights()
@@ -685,6 +717,20 @@ def temperature_table(spec, n_cells):
     return decay_schedule(spec[1], spec[2], spec[3], n_cells)
 
 
+def reanalyse_arg(text):
+    """--reanalyse N | all -> N (0 = off) or 'all'."""
+    import argparse
+    if text == 'all':
+        return 'all'
+    try:
+        value = int(text)
+    except ValueError:
+        value = -1
+    if value < 0:
+        raise argparse.ArgumentTypeError('a number of positions >= 0 or "all", not %r' % text)
+    return value
+
+
 def positive_float_arg(text):
     import argparse
     try:
@@ -727,9 +773,20 @@ def parse_args(argv=None):
     ap.add_argument('--device-replay', action='store_true',
                     help='batched mode on a GPU only: the replay buffer lives in device memory and a mini-batch is one kernel launch '
                          '(drawn on the device, with replacement)')
+    ap.add_argument('--reanalyse', type=reanalyse_arg, default=0, metavar='N|all',
+                    help='with --device-replay: before every round\'s updates search N drawn positions of the buffer (or all) again '
+                         'with the current network and refresh their policy targets (visit distribution at T = 1; z is kept)')
+    ap.add_argument('--reanalyse-slots', type=int, default=512, metavar='G', help='positions searched per batch of a refresh')
+    ap.add_argument('--reanalyse-playouts', type=int, default=None, metavar='P', help='simulations of a refreshing search (default: --playouts)')
     args = ap.parse_args(argv)
     if args.batch_size < 1 or args.updates_per_round < 1:
         ap.error('--batch-size and --updates-per-round must be >= 1')
+    if args.reanalyse and not args.device_replay:
+        ap.error('--reanalyse needs --device-replay')
+    if args.reanalyse and args.games_in_flight <= 0:
+        ap.error('--reanalyse needs --games-in-flight > 0 (batched mode)')
+    if args.reanalyse and (args.reanalyse_slots < 1 or (args.reanalyse_playouts is not None and args.reanalyse_playouts < 1)):
+        ap.error('--reanalyse-slots and --reanalyse-playouts must be >= 1')
     if args.device_replay and args.games_in_flight <= 0:
         ap.error('--device-replay needs --games-in-flight > 0 (batched mode)')
     if args.device_replay and not torch.cuda.is_available():
@@ -769,7 +826,8 @@ def main():
                          resign=args.resign_threshold, resign_disabled_frac=args.resign_disabled_frac,
                          resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against,
                          batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay,
-                         temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature)
+                         temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature,
+                         reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
