@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 38
+#define RZ_ABI_VERSION 39
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -865,7 +865,8 @@ int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_work
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * Device replay buffer (ABI 31; rz_replay.hip; an opt-in extension -- the reference's learner keeps its samples in a host
- * deque, tools/train_alphazero.py:32,59-79,88-90).  Gomoku, square boards of 3 .. 16 rows, A = B * B actions.
+ * deque, tools/train_alphazero.py:32,59-79,88-90).  Gomoku, square boards of 3 .. 16 rows, A = B * B actions (Connect4: ABI 39,
+ * the section after Reanalyse).
  *
  * The store is a ring of `capacity` self-contained POSITIONS (eviction is per position, nothing refers to a game):
  *   stones  uint64 [capacity][2][RZ_BOARD_WORDS]   [0] = the stones of the player to move, [1] = the opponent's (bit a = cell a)
@@ -942,6 +943,40 @@ int rz_replay_ticket(rz_replay *r, int64_t *ticket);
 int rz_replay_positions(rz_replay *r, const int64_t *h_indices, const int64_t *d_indices, uint64_t seed, uint64_t step, int64_t n,
                         int32_t *d_where, uint64_t *d_stones, int32_t *d_to_move, int32_t *d_last_move, int64_t *ticket, void *stream);
 int rz_replay_update_pi(rz_replay *r, const int32_t *d_where, int64_t n, const int32_t *d_visits, int64_t ticket, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The device replay buffer for Connect4 (ABI 39; rz_replay.hip: the <true> instantiations of k_replay_add / k_replay_gather /
+ * k_replay_sample; rz_replay_rules.h: cell_of_ply, first_illegal_drop; rlzero_amd/replay.py: DeviceReplay(game='connect4')).
+ * Build-defined, like RZ_GAME_CONNECT4 itself: the reference has no Connect4.  rz_replay_create and rz_replay_set_tables keep
+ * their signatures and behaviour, and a Gomoku handle writes the bits it wrote before.
+ *
+ * A handle has a GAME and four sizes: C cells (rows * cols), A actions = the width of a pi row (Gomoku: C; Connect4: cols),
+ * S symmetries (Gomoku: 8; Connect4: 2) and the column count.  An ENTRY is e = S * j + k: symmetry k of the j-th oldest position,
+ * so 8 * count above reads S * count.  The record of a Connect4 position is the Gomoku record over CELLS (cell = row * cols +
+ * column, row 0 at the bottom): two bitboards, the meta word -- its "last move + 1" field holds the last CELL + 1, which is what
+ * plane 2 marks and what rz_set_roots takes as the last move of a Connect4 root -- and a pi row of `cols` floats.
+ * The two symmetries: k = 0 the position as played, k = 1 its left-right mirror (every plane [:, :, ::-1], pi[::-1]); the
+ * rotations of a square board do not exist under gravity.  As for Gomoku they are tables the host obtains by pushing cell and
+ * column numbers through those numpy expressions (rlzero_amd/replay.py: symmetry_tables(..., game='connect4')).
+ *
+ * rz_replay_create_game: game_kind RZ_GAME_GOMOKU (rows == cols, 3 .. 16: rz_replay_create) or RZ_GAME_CONNECT4 (rows and cols
+ *   1 .. 16 each, rz_create's limit).
+ * rz_replay_set_tables_game: h_src_state int16 [n_symmetries][n_cells], h_src_pi int16 [n_symmetries][n_actions]; the three
+ *   sizes must be the handle's (RZ_ERR_ARG otherwise), entries outside 0 .. n_cells - 1 / 0 .. n_actions - 1 are refused.
+ *   rz_replay_set_tables is this call with (8, A, A) and refuses a Connect4 handle.
+ * rz_replay_geometry: the handle's game and sizes (any pointer may be NULL).
+ * rz_replay_add on a Connect4 handle: h_moves are COLUMNS; a column outside 0 .. cols - 1, or a column played more often than
+ *   the board has rows, is refused before the launch (RZ_ERR_ARG), as a move outside the board is for Gomoku.  The kernel turns
+ *   the columns into cells -- the cell of ply q is (plies q' < q in the same column) * cols + column, a thread per ply over the
+ *   move list in LDS -- and forms the positions from the cells as before.  h_pi is [kept plies][cols].
+ * rz_replay_gather / rz_replay_sample on a Connect4 handle: a thread per CELL; d_states float32 [n][4][rows][cols], d_pis
+ *   float32 [n][cols] (written by the first `cols` threads).  rz_replay_positions is unchanged (d_last_move is the last cell);
+ *   rz_replay_update_pi takes d_visits int32 [n][cols]. */
+int rz_replay_create_game(int32_t game_kind, int32_t rows, int32_t cols, int64_t capacity, int32_t device, rz_replay **out);
+int rz_replay_set_tables_game(rz_replay *r, int32_t n_symmetries, int32_t n_cells, int32_t n_actions, const int16_t *h_src_state,
+                              const int16_t *h_src_pi, void *stream);
+int rz_replay_geometry(rz_replay *r, int32_t *game_kind, int32_t *rows, int32_t *cols, int32_t *n_cells, int32_t *n_actions,
+                       int32_t *n_symmetries);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * MuZero device replay (ABI 35; rz_mz_replay.hip, rz_mz_target.h; an opt-in extension beside the host ReplayBuffer of

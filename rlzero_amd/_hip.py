@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -227,6 +227,9 @@ _SIGNATURES = {
     'rz_replay_ticket': (c_int, [P, POINTER(c_int64)]),
     'rz_replay_positions': (c_int, [P, P, P, c_uint64, c_uint64, c_int64, P, P, P, P, POINTER(c_int64), P]),
     'rz_replay_update_pi': (c_int, [P, P, c_int64, P, c_int64, P]),
+    'rz_replay_create_game': (c_int, [c_int32, c_int32, c_int32, c_int64, c_int32, POINTER(c_void_p)]),
+    'rz_replay_set_tables_game': (c_int, [P, c_int32, c_int32, c_int32, P, P, P]),
+    'rz_replay_geometry': (c_int, [P] + [POINTER(c_int32)] * 6),
     'rz_mz_replay_create': (c_int, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, P, c_int32, POINTER(c_void_p)]),
     'rz_mz_replay_destroy': (c_int, [P]),
     'rz_mz_replay_state': (c_int, [P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), P]),

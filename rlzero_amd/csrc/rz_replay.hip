@@ -1,4 +1,4 @@
-// rz_replay.hip -- the device replay buffer (include/rlzero_hip.h: rz_replay_*, ABI 31; Reanalyse, ABI 38).
+// rz_replay.hip -- the device replay buffer (include/rlzero_hip.h: rz_replay_*, ABI 31; Reanalyse, ABI 38; Connect4, ABI 39).
 //
 // The learner's samples live in device memory as a ring of self-contained positions (two bitboards, one meta word, a pi row) and
 // a mini-batch is ONE launch: k_replay_gather / k_replay_sample write the observation planes, the symmetry-transformed pi and z
@@ -6,8 +6,14 @@
 // from the reference's own numpy expressions (tools/train_alphazero.py:59-79) -- the planes and pi are permuted DIFFERENTLY there,
 // and nothing here re-derives either permutation.  k_replay_add forms the positions of finished games from their move lists.
 //
-// Bounds: every slot is reduced modulo the capacity, every table entry is checked at upload (< A), an entry index from the device
-// is checked by the kernel before anything is read, moves are checked on the host (< A) and index registers, not memory.
+// Two games share the store.  Gomoku: C = A = B * B, S = 8 symmetries.  Connect4: C = rows * cols cells, a pi row of A = cols floats,
+// S = 2 (the position and its left-right mirror); its moves are columns, which k_replay_add<true> turns into cells
+// (rz_replay_rules.h: cell_of_ply) before the Gomoku code runs on them.  k_replay_add, k_replay_gather and k_replay_sample are
+// templates on the game so that the Gomoku instantiations keep the code they had (entry >> 3, entry & 7, one table width).
+//
+// Bounds: every slot is reduced modulo the capacity, every table entry is checked at upload (< C for the planes, < A for pi), an
+// entry index from the device is checked by the kernel before anything is read, moves are checked on the host (Gomoku: < A;
+// Connect4: a column < cols that is not full) and index registers or LDS arrays of kMaxCells entries under a mask, not memory.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -31,11 +37,12 @@ struct ReplayDev {
     unsigned long long *stones;   // [capacity][2][RZ_BOARD_WORDS]
     int32_t *meta;                // [capacity]
     float *pi;                    // [capacity][A]
-    const int16_t *src_state;     // [8][A]
-    const int16_t *src_pi;        // [8][A]
+    const int16_t *src_state;     // [S][C]
+    const int16_t *src_pi;        // [S][A]
     int32_t *err;
     long long capacity;
-    int A;
+    int A;                        // width of a pi row (Gomoku: C; Connect4: cols)
+    int C, S, cols;               // cells; symmetries (8 or 2); columns of the board
 };
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
@@ -59,6 +66,9 @@ __device__ __forceinline__ long long replay_index(unsigned long long seed, unsig
 // One workgroup per game, thread p = ply p (blockDim.x == 256 >= plies).  `base[g]`: kept plies of the games before g; a kept ply of
 // global rank t goes to slot (cursor + t) % capacity unless t < skip (more kept plies than slots: only the last `capacity` are
 // written, so no two threads of the launch share a slot).
+// kC4: the moves are Connect4 columns.  Thread p turns column p into its cell over the move list in LDS, behind the first barrier;
+// one more barrier, and everything below reads cells.
+template <bool kC4>
 __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int32_t *__restrict__ offsets, const int32_t *__restrict__ base,
                                                            const int32_t *__restrict__ winner, const int32_t *__restrict__ moves,
                                                            const uint8_t *__restrict__ keep, const float *__restrict__ pi_rows,
@@ -76,6 +86,13 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
     const unsigned long long ballot = __ballot(kept);
     if (lane == 0) s_kept[wave] = __popcll(ballot);
     __syncthreads();
+    const int32_t *s_cells = s_moves;   // the cell of every ply (Gomoku: the move itself)
+    if (kC4) {
+        __shared__ int32_t s_dropped[kMaxCells];
+        s_dropped[p] = in ? (rzrr::cell_of_ply(s_moves, p, R.cols) & (kMaxCells - 1)) : 0;
+        __syncthreads();
+        s_cells = s_dropped;
+    }
     int rank = __popcll(ballot & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) rank += s_kept[w];
     const long long t = (long long)base[g] + rank;
@@ -84,7 +101,7 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
         slot = (int)((cursor + t) % R.capacity);
         unsigned long long own[RZ_BOARD_WORDS] = {0, 0, 0, 0}, opp[RZ_BOARD_WORDS] = {0, 0, 0, 0};
         for (int q = 0; q < p; ++q) {
-            const int m = s_moves[q];
+            const int m = s_cells[q];
             const unsigned long long bit = 1ull << (m & 63);
             const bool mine = ((q ^ p) & 1) == 0;   // ply q was the mover's when q and p have the same parity
 #pragma unroll
@@ -101,7 +118,7 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
         }
         const int win = winner[g];
         const int z = win < 0 ? 0 : ((p & 1) == win ? 1 : -1);
-        const int last = p > 0 ? s_moves[p - 1] + 1 : 0;
+        const int last = p > 0 ? s_cells[p - 1] + 1 : 0;
         R.meta[slot] = last | ((p & 1) << kMetaParityBit) | ((z + 1) << kMetaZShift);
     }
     s_slot[p] = slot;
@@ -117,28 +134,32 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
     }
 }
 
-// entry e -> output row i: a thread per output cell (blockDim.x >= A)
+// entry e -> output row i: a thread per output cell (blockDim.x >= C >= A).  Gomoku: entry 8 j + k, one width for both tables;
+// Connect4: entry 2 j + k, the planes over the C cells and pi over the A columns, written by the first A threads.
+template <bool kC4>
 __device__ __forceinline__ void replay_emit(const ReplayDev &R, long long e, long long oldest, long long i, float *__restrict__ states,
                                             float *__restrict__ pis, float *__restrict__ zs) {
-    const int o = threadIdx.x, A = R.A, k = (int)(e & 7);
-    const long long slot = (oldest + (e >> 3)) % R.capacity;
+    const int o = threadIdx.x, A = R.A, C = kC4 ? R.C : R.A, k = (int)(e & (kC4 ? 1 : 7));
+    const long long slot = (oldest + (e >> (kC4 ? 1 : 3))) % R.capacity;
     const unsigned long long *rec = R.stones + slot * kRecWords;   // (uniform across the workgroup)
     const unsigned long long a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], b0 = rec[4], b1 = rec[5], b2 = rec[6], b3 = rec[7];
     const int meta = R.meta[slot];
     if (o == 0) zs[i] = (float)(((meta >> kMetaZShift) & 3) - 1);
-    if (o >= A) return;
-    const int s = R.src_state[k * A + o];
+    if (o >= C) return;
+    const int s = R.src_state[k * C + o];
     const int w = s >> 6;
     const unsigned long long own = w == 0 ? a0 : w == 1 ? a1 : w == 2 ? a2 : a3;
     const unsigned long long opp = w == 0 ? b0 : w == 1 ? b1 : w == 2 ? b2 : b3;
-    float *out = states + i * 4 * A;
+    float *out = states + i * 4 * C;
     out[o] = (float)((own >> (s & 63)) & 1ull);
-    out[A + o] = (float)((opp >> (s & 63)) & 1ull);
-    out[2 * A + o] = (s + 1 == (meta & 511)) ? 1.0f : 0.0f;
-    out[3 * A + o] = ((meta >> kMetaParityBit) & 1) ? 0.0f : 1.0f;
+    out[C + o] = (float)((opp >> (s & 63)) & 1ull);
+    out[2 * C + o] = (s + 1 == (meta & 511)) ? 1.0f : 0.0f;
+    out[3 * C + o] = ((meta >> kMetaParityBit) & 1) ? 0.0f : 1.0f;
+    if (kC4 && o >= A) return;
     pis[i * A + o] = R.pi[slot * A + R.src_pi[k * A + o]];
 }
 
+template <bool kC4>
 __global__ __launch_bounds__(kMaxCells) void k_replay_gather(ReplayDev R, const long long *__restrict__ indices, long long oldest,
                                                               long long n_entries, float *__restrict__ states, float *__restrict__ pis,
                                                               float *__restrict__ zs) {
@@ -148,14 +169,15 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_gather(ReplayDev R, const 
         if (threadIdx.x == 0) atomicOr(R.err, kFlagBadIndex);
         return;
     }
-    replay_emit(R, e, oldest, i, states, pis, zs);
+    replay_emit<kC4>(R, e, oldest, i, states, pis, zs);
 }
 
+template <bool kC4>
 __global__ __launch_bounds__(kMaxCells) void k_replay_sample(ReplayDev R, unsigned long long seed, unsigned long long step, long long oldest,
                                                               long long n_entries, float *__restrict__ states, float *__restrict__ pis,
                                                               float *__restrict__ zs) {
     const long long i = blockIdx.x;
-    replay_emit(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
+    replay_emit<kC4>(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
 }
 
 // Reanalyse, the way out: position index -> ring slot (`where`, -1 for an index outside 0 .. count - 1) and the stored record as a
@@ -189,7 +211,7 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_positions(ReplayDev R, con
 }
 
 // Reanalyse, the way back: pi[where[i]][a] = N[i][a] / sum N[i] (rzrr::pi_of_visits).  A workgroup per row, a thread per action
-// (blockDim.x = A rounded up to whole waves).  The sum is an INTEGER reduction -- across the lanes of a wave, then across the waves
+// (blockDim.x = A rounded up to whole waves: one wave for Connect4's A = cols <= 16, up to four for Gomoku).  The sum is an INTEGER reduction -- across the lanes of a wave, then across the waves
 // through LDS -- so it is exact whatever the order.  where < 0 (a refused or a padding row), a slot outside the capacity or a sum of
 // 0 writes nothing; stones and meta are never written.  Every branch before the barrier is uniform across the workgroup.
 __global__ __launch_bounds__(kMaxCells) void k_replay_update_pi(ReplayDev R, const int32_t *__restrict__ where, const int32_t *__restrict__ visits) {
@@ -214,7 +236,7 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_update_pi(ReplayDev R, con
 
 struct rz_replay {
     ReplayDev dev = {};
-    int board = 0, device = 0;
+    int game = RZ_GAME_GOMOKU, rows = 0, device = 0;
     long long cursor = 0, count = 0;   // next slot written; positions held
     long long stored = 0;              // positions ever stored: the ticket of rz_replay_positions / rz_replay_update_pi
     int16_t *d_tables = nullptr;
@@ -237,8 +259,47 @@ int rp_outputs(rz_replay *r, int64_t n, const float *d_states, const float *d_pi
     return RZ_OK;
 }
 
-inline unsigned rp_block(const rz_replay *r) { return (unsigned)((r->dev.A + 63) / 64 * 64); }
+inline unsigned rp_block(const rz_replay *r) { return (unsigned)((r->dev.C + 63) / 64 * 64); }       // a thread per cell
+inline unsigned rp_pi_block(const rz_replay *r) { return (unsigned)((r->dev.A + 63) / 64 * 64); }   // a thread per action
+inline bool rp_connect4(const rz_replay *r) { return r->game == RZ_GAME_CONNECT4; }
 inline long long rp_oldest(const rz_replay *r) { return ((r->cursor - r->count) % r->dev.capacity + r->dev.capacity) % r->dev.capacity; }
+
+// the store of `capacity` positions of a rows x cols board (the caller has checked the board)
+int rp_create(int game, int rows, int cols, int64_t capacity, int32_t device, rz_replay **out) {
+    if (capacity < 1 || capacity > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "capacity outside 1 .. 2^24 positions");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    rz_replay *r = new (std::nothrow) rz_replay();
+    if (!r) return rz_fail(RZ_ERR_OOM, "host allocation failed");
+    r->game = game;
+    r->rows = rows;
+    r->device = device;
+    ReplayDev &D = r->dev;
+    D.C = rows * cols;
+    D.A = game == RZ_GAME_CONNECT4 ? cols : D.C;
+    D.S = game == RZ_GAME_CONNECT4 ? 2 : 8;
+    D.cols = cols;
+    D.capacity = capacity;
+    const size_t cap = (size_t)capacity, A = (size_t)D.A;
+    bool ok = r->pool.alloc(&D.stones, capacity * kRecWords) == RZ_OK && r->pool.alloc(&D.meta, capacity) == RZ_OK && r->pool.alloc(&D.pi, capacity * D.A) == RZ_OK &&
+              r->pool.alloc(&r->d_tables, D.S * (D.C + D.A)) == RZ_OK && r->pool.alloc(&D.err, 1) == RZ_OK;
+    if (!ok) {
+        rz_replay_destroy(r);
+        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (replay store)");
+    }
+    D.src_state = r->d_tables;
+    D.src_pi = r->d_tables + (size_t)D.S * D.C;
+    ok = hipMemset(D.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(D.stones, 0, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
+         hipMemset(D.meta, 0, cap * sizeof(int32_t)) == hipSuccess && hipMemset(D.pi, 0, cap * A * sizeof(float)) == hipSuccess &&
+         r->stage.create("replay") == RZ_OK && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        rz_replay_destroy(r);
+        return rz_fail(RZ_ERR_HIP, "initialisation of the replay store failed");
+    }
+    *out = r;
+    return RZ_OK;
+}
 
 }  // namespace
 
@@ -248,34 +309,30 @@ int rz_replay_create(int32_t board_size, int64_t capacity, int32_t device, rz_re
     if (out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     *out = nullptr;
     if (board_size < 3 || board_size > RZ_MAX_BOARD_SIZE) return rz_fail(RZ_ERR_ARG, "board_size outside 3 .. 16");
-    if (capacity < 1 || capacity > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "capacity outside 1 .. 2^24 positions");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
-    rz_replay *r = new (std::nothrow) rz_replay();
-    if (!r) return rz_fail(RZ_ERR_OOM, "host allocation failed");
-    r->board = board_size;
-    r->device = device;
-    ReplayDev &D = r->dev;
-    D.A = board_size * board_size;
-    D.capacity = capacity;
-    const size_t cap = (size_t)capacity, A = (size_t)D.A;
-    bool ok = r->pool.alloc(&D.stones, capacity * kRecWords) == RZ_OK && r->pool.alloc(&D.meta, capacity) == RZ_OK && r->pool.alloc(&D.pi, capacity * D.A) == RZ_OK &&
-              r->pool.alloc(&r->d_tables, 2 * 8 * D.A) == RZ_OK && r->pool.alloc(&D.err, 1) == RZ_OK;
-    if (!ok) {
-        rz_replay_destroy(r);
-        return rz_fail(RZ_ERR_OOM, "hipMalloc failed (replay store)");
+    return rp_create(RZ_GAME_GOMOKU, board_size, board_size, capacity, device, out);
+}
+
+int rz_replay_create_game(int32_t game_kind, int32_t rows, int32_t cols, int64_t capacity, int32_t device, rz_replay **out) {
+    if (out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (game_kind == RZ_GAME_GOMOKU) {
+        if (rows != cols) return rz_fail(RZ_ERR_ARG, "a Gomoku board is square");
+        return rz_replay_create(rows, capacity, device, out);
     }
-    D.src_state = r->d_tables;
-    D.src_pi = r->d_tables + 8 * A;
-    ok = hipMemset(D.err, 0, sizeof(int32_t)) == hipSuccess && hipMemset(D.stones, 0, cap * kRecWords * sizeof(unsigned long long)) == hipSuccess &&
-         hipMemset(D.meta, 0, cap * sizeof(int32_t)) == hipSuccess && hipMemset(D.pi, 0, cap * A * sizeof(float)) == hipSuccess &&
-         r->stage.create("replay") == RZ_OK && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) {
-        rz_replay_destroy(r);
-        return rz_fail(RZ_ERR_HIP, "initialisation of the replay store failed");
-    }
-    *out = r;
+    if (game_kind != RZ_GAME_CONNECT4) return rz_fail(RZ_ERR_ARG, "unknown game_kind");
+    if (rows < 1 || rows > RZ_MAX_BOARD_SIZE || cols < 1 || cols > RZ_MAX_BOARD_SIZE) return rz_fail(RZ_ERR_ARG, "rows or cols outside 1 .. 16");
+    return rp_create(RZ_GAME_CONNECT4, rows, cols, capacity, device, out);
+}
+
+int rz_replay_geometry(rz_replay *r, int32_t *game_kind, int32_t *rows, int32_t *cols, int32_t *n_cells, int32_t *n_actions,
+                       int32_t *n_symmetries) {
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "replay handle is NULL");
+    if (game_kind) *game_kind = r->game;
+    if (rows) *rows = r->rows;
+    if (cols) *cols = r->dev.cols;
+    if (n_cells) *n_cells = r->dev.C;
+    if (n_actions) *n_actions = r->dev.A;
+    if (n_symmetries) *n_symmetries = r->dev.S;
     return RZ_OK;
 }
 
@@ -288,22 +345,31 @@ int rz_replay_destroy(rz_replay *r) {
     return RZ_OK;
 }
 
-int rz_replay_set_tables(rz_replay *r, const int16_t *h_src_state, const int16_t *h_src_pi, void *stream) {
+int rz_replay_set_tables_game(rz_replay *r, int32_t n_symmetries, int32_t n_cells, int32_t n_actions, const int16_t *h_src_state,
+                              const int16_t *h_src_pi, void *stream) {
     RZ_ENTER(rp_ready, r);
     if (h_src_state == nullptr || h_src_pi == nullptr) return rz_fail(RZ_ERR_ARG, "NULL table");
-    const int A = r->dev.A;
-    for (int i = 0; i < 8 * A; ++i)
-        if (h_src_state[i] < 0 || h_src_state[i] >= A || h_src_pi[i] < 0 || h_src_pi[i] >= A) return rz_fail(RZ_ERR_ARG, "table entry outside 0 .. A-1");
+    const int S = r->dev.S, C = r->dev.C, A = r->dev.A;
+    if (n_symmetries != S || n_cells != C || n_actions != A) return rz_fail(RZ_ERR_ARG, "the tables are not of this buffer's symmetries, cells and actions");
+    for (int i = 0; i < S * C; ++i)
+        if (h_src_state[i] < 0 || h_src_state[i] >= C) return rz_fail(RZ_ERR_ARG, "table entry outside 0 .. C-1");
+    for (int i = 0; i < S * A; ++i)
+        if (h_src_pi[i] < 0 || h_src_pi[i] >= A) return rz_fail(RZ_ERR_ARG, "table entry outside 0 .. A-1");
     hipStream_t s = (hipStream_t)stream;
-    const size_t half = (size_t)8 * A * sizeof(int16_t);
-    RZ_TRY(r->stage.reserve(2 * half, s));
-    memcpy(r->stage.h, h_src_state, half);
-    memcpy((char *)r->stage.h + half, h_src_pi, half);
-    RZ_TRY(r->stage.upload(2 * half, s));
-    RZ_HIP(hipMemcpyAsync(r->d_tables, r->stage.d, 2 * half, hipMemcpyDeviceToDevice, s));
+    const size_t planes = (size_t)S * C * sizeof(int16_t), pis = (size_t)S * A * sizeof(int16_t);   // (d_tables: src_state, then src_pi)
+    RZ_TRY(r->stage.reserve(planes + pis, s));
+    memcpy(r->stage.h, h_src_state, planes);
+    memcpy((char *)r->stage.h + planes, h_src_pi, pis);
+    RZ_TRY(r->stage.upload(planes + pis, s));
+    RZ_HIP(hipMemcpyAsync(r->d_tables, r->stage.d, planes + pis, hipMemcpyDeviceToDevice, s));
     RZ_TRY(r->stage.launched(s, "the table copy (replay)"));
     r->tables = true;
     return RZ_OK;
+}
+
+int rz_replay_set_tables(rz_replay *r, const int16_t *h_src_state, const int16_t *h_src_pi, void *stream) {
+    if (r != nullptr && rp_connect4(r)) return rz_fail(RZ_ERR_ARG, "rz_replay_set_tables takes Gomoku's [8][A] tables: rz_replay_set_tables_game");
+    return rz_replay_set_tables_game(r, 8, r != nullptr ? r->dev.A : 0, r != nullptr ? r->dev.A : 0, h_src_state, h_src_pi, stream);
 }
 
 int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity) {
@@ -320,17 +386,24 @@ int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const
     if (n_games < 0) return rz_fail(RZ_ERR_ARG, "n_games < 0");
     if (n_games == 0) return RZ_OK;
     if (h_offsets == nullptr || h_winner == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
-    const int A = r->dev.A;
+    const int A = r->dev.A, C = r->dev.C;
     if (h_offsets[0] != 0) return rz_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
     std::vector<int32_t> base((size_t)n_games);
     long long kept = 0;
     for (int g = 0; g < n_games; ++g) {
         const long long P = (long long)h_offsets[g + 1] - h_offsets[g];
         if (P < 0) return rz_fail(RZ_ERR_ARG, "h_offsets must not decrease");
-        if (P > A) return rz_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
+        if (P > C) return rz_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
         if (h_winner[g] < -1 || h_winner[g] > 1) return rz_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
         if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rz_fail(RZ_ERR_ARG, "NULL argument");
         base[(size_t)g] = (int32_t)kept;
+        if (rp_connect4(r) && P > 0) {   // columns: each inside the board and not played more often than the board has rows
+            const int bad = rzrr::first_illegal_drop(h_moves + h_offsets[g], (int)P, r->rows, r->dev.cols);
+            if (bad >= 0) {
+                const int32_t column = h_moves[h_offsets[g] + bad];
+                return rz_fail(RZ_ERR_ARG, column < 0 || column >= r->dev.cols ? "a move is outside the board" : "a column is played more often than the board has rows");
+            }
+        }
         for (int p = h_offsets[g]; p < h_offsets[g + 1]; ++p) {
             if (h_moves[p] < 0 || h_moves[p] >= A) return rz_fail(RZ_ERR_ARG, "a move is outside the board");
             kept += h_keep[p] != 0;
@@ -354,7 +427,7 @@ int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const
     memcpy(h + o_pi, h_pi, (size_t)kept * A * sizeof(float));
     RZ_TRY(r->stage.upload(bytes, s));
     const long long cap = r->dev.capacity, skip = kept > cap ? kept - cap : 0;
-    hipLaunchKernelGGL(k_replay_add, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
+    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_add<true> : k_replay_add<false>, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
                        (const int32_t *)(d + o_win), (const int32_t *)(d + o_moves), (const uint8_t *)(d + o_keep), (const float *)(d + o_pi),
                        r->cursor, skip);
     RZ_TRY(r->stage.launched(s, "k_replay_add"));
@@ -370,29 +443,29 @@ int rz_replay_gather(rz_replay *r, const int64_t *h_indices, const int64_t *d_in
     RZ_TRY(rp_outputs(r, n, d_states, d_pis, d_zs));
     if ((h_indices == nullptr) == (d_indices == nullptr)) return rz_fail(RZ_ERR_ARG, "exactly one of h_indices / d_indices");
     if (n == 0) return RZ_OK;
-    const long long n_entries = 8 * r->count;
+    const long long n_entries = r->dev.S * r->count;
     if (n_entries == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
     const long long *idx = (const long long *)d_indices;
     if (h_indices != nullptr) {
         for (int64_t i = 0; i < n; ++i)
-            if (h_indices[i] < 0 || h_indices[i] >= n_entries) return rz_fail(RZ_ERR_ARG, "entry index outside 0 .. 8 * count - 1");
+            if (h_indices[i] < 0 || h_indices[i] >= n_entries) return rz_fail(RZ_ERR_ARG, "entry index outside 0 .. S * count - 1");
         RZ_TRY(r->stage.reserve((size_t)n * 8, s));
         memcpy(r->stage.h, h_indices, (size_t)n * 8);
         RZ_TRY(r->stage.upload((size_t)n * 8, s));
         idx = (const long long *)r->stage.d;
     }
-    hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
+    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_gather<true> : k_replay_gather<false>, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
     return h_indices != nullptr ? r->stage.launched(s, "k_replay_gather") : rz_launched("k_replay_gather");
 }
 
 int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, float *d_states, float *d_pis, float *d_zs, void *stream) {
     RZ_ENTER(rp_ready, r);
     RZ_TRY(rp_outputs(r, n, d_states, d_pis, d_zs));
-    const long long n_entries = 8 * r->count;
+    const long long n_entries = r->dev.S * r->count;
     if (n_entries == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
     if (n == 0) return RZ_OK;
-    hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
+    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_sample<true> : k_replay_sample<false>, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
                        (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
     return rz_launched("k_replay_sample");
 }
@@ -437,7 +510,7 @@ int rz_replay_update_pi(rz_replay *r, const int32_t *d_where, int64_t n, const i
     if (!rzrr::ticket_current(ticket, r->stored)) return rz_fail(RZ_ERR_ARG, "stale ticket: positions were stored since rz_replay_positions");
     if (n == 0) return RZ_OK;
     if (d_where == nullptr || d_visits == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
-    hipLaunchKernelGGL(k_replay_update_pi, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, d_where, d_visits);
+    hipLaunchKernelGGL(k_replay_update_pi, dim3((unsigned)n), dim3(rp_pi_block(r)), 0, (hipStream_t)stream, r->dev, d_where, d_visits);
     return rz_launched("k_replay_update_pi");
 }
 

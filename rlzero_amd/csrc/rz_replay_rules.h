@@ -4,6 +4,7 @@
 // rlzero_amd/replay.py (pack_positions, reanalysed_pi, replay_reanalyse_draws) and the Gomoku environment
 // (tests/test_replay_reanalyse_host.py); the kernels call these functions.  Three rules: a stored record as a root of the search
 // engine, the pi row of fresh visit counts, the draws of a refresh -- and the ticket that ties a result to the store it was drawn from.
+// For Connect4 (at the end; tests/test_replay_connect4_host.py against Connect4Env): the cell a dropped stone comes to rest in.
 #pragma once
 #include <stdint.h>
 
@@ -85,5 +86,27 @@ RZR_FN int64_t slot_of_position(int64_t index, int64_t oldest, int64_t count, in
 // write cursor: the cursor returns to the same slot after `capacity` positions, the count never does.  A result may be written
 // only while nothing was stored in between -- a slot may hold another position by then.
 RZR_FN bool ticket_current(int64_t ticket, int64_t stored) { return ticket == stored; }
+
+// ---- Connect4 (RZ_GAME_CONNECT4; k_replay_add<true>, rz_replay_add): a move is a COLUMN and the stone drops, a record holds CELLS
+// (cell = row * cols + column, row 0 at the bottom: Connect4Env.step).  The cell of ply q of a move list: as many rows up as the
+// earlier plies put stones into its column.  The kernel runs it over the move list in LDS, a thread per ply; everything behind it
+// (the stones of a position, the last move of the meta word, the root of a search) works on cells, as for Gomoku.
+RZR_FN int cell_of_ply(const int32_t *moves, int q, int cols) {
+    const int32_t column = moves[q];
+    int below = 0;
+    for (int j = 0; j < q; ++j) below += moves[j] == column ? 1 : 0;
+    return below * cols + column;
+}
+// the first ply of a move list that is no legal drop on a board of rows x cols (cols <= RZ_MAX_BOARD_SIZE) -- a column outside
+// 0 .. cols - 1, or one that holds `rows` stones already --, or -1: what the host refuses before a launch
+RZR_FN int first_illegal_drop(const int32_t *moves, int n, int rows, int cols) {
+    int height[RZ_MAX_BOARD_SIZE] = {0};
+    for (int p = 0; p < n; ++p) {
+        const int32_t column = moves[p];
+        if (column < 0 || column >= cols || height[column] >= rows) return p;
+        ++height[column];
+    }
+    return -1;
+}
 
 }  // namespace rzrr

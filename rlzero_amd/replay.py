@@ -31,6 +31,22 @@ rows).  What is refreshed and what is not:
   tests/test_replay_reanalyse_host.py).  A ``pi_temperature`` or temperature schedule of the self-play run is NOT reapplied;
 * z is never refreshed: it is the outcome of the game that was played;
 * the fast plies of a playout cap are not in the buffer, so they are not refreshed either.
+
+Connect4 (``DeviceReplay((rows, cols), C, game='connect4')``; build-defined, the reference has no Connect4):
+
+* a stored position is the position before a kept ply, as for Gomoku: two bitboards over CELLS (cell = row * cols + column, row 0
+  at the bottom, as in ``Connect4Env``), the meta word and a pi row of ``n_actions = cols`` floats.  The meta word's "last move + 1"
+  field holds the last CELL, not the column: plane 2 marks that cell, and a Connect4 root of the search engine takes the last
+  stone's cell (``rz_set_roots`` stores it as it comes; the engine's own move step writes the cell there too);
+* a game arrives as its COLUMNS; ``add`` refuses a column outside the board or played more often than the board has rows, and the
+  device lets the stones drop (csrc/rz_replay_rules.h: ``cell_of_ply``; ``pack_positions`` drops them again in plain Python);
+* the augmentation has TWO symmetries: entry ``2 j + k`` is the j-th oldest position held, ``k = 0`` as played and ``k = 1`` its
+  left-right mirror -- every plane ``[:, :, ::-1]`` and ``pi[::-1]``; ``len(buffer) = 2 * positions``.  The rotations of a square
+  board do not exist here: gravity breaks them.  As for Gomoku the tables come from pushing cell and column numbers through these
+  numpy expressions (``symmetry_tables(..., game='connect4')``: ``src_state`` int16 [2][cells], ``src_pi`` int16 [2][cols]);
+* ``sample``, ``reanalyse_sample``, ``reanalysed_pi`` and the ticket are exactly Gomoku's: the draw of ``sample`` runs over the
+  ``len(buffer)`` entries -- ``replay_index(seed, step, i, 2 * positions)`` --, ``reanalyse_sample`` draws over positions;
+* the contract: the entries are those of the trainer's host ``ReplayBuffer(2 * C, (rows, cols), game='connect4')`` for the same games.
 """
 import ctypes
 
@@ -45,11 +61,28 @@ _REPLAY_SALT = np.uint64(0x7265706C61790000)   # ("replay": the sampler's own st
 META_PARITY_BIT, META_Z_SHIFT = 9, 10          # the meta word: bits 0..8 last move + 1 (0: none), bit 9 ply parity, bits 10..11 z + 1
 
 
-def symmetry_tables(board_size):
+def _rows_cols(board_size, game):
+    if game == 'connect4':
+        rows, cols = board_size
+        return int(rows), int(cols)
+    if game != 'gomoku':
+        raise ValueError('game %r: gomoku or connect4' % (game, ))
+    return int(board_size), int(board_size)
+
+
+def symmetry_tables(board_size, game='gomoku'):
     """-> (src_state, src_pi), int16 [8][A]: for output cell ``o`` of symmetry ``k`` the source cell of the planes and of pi, i.e.
     ``entry_state[c].flat == state[c].flat[src_state[k]]`` and ``entry_pi == pi[src_pi[k]]``.  Obtained by pushing the cell numbers
-    through the numpy expressions the trainer's ReplayBuffer forms an entry with (get_equi_data's, train_alphazero.py:59-79)."""
-    size = int(board_size)
+    through the numpy expressions the trainer's ReplayBuffer forms an entry with (get_equi_data's, train_alphazero.py:59-79).
+    ``game='connect4'``, ``board_size`` (rows, cols): int16 [2][rows * cols] and [2][cols] -- the position as played and its
+    left-right mirror, ``planes[:, :, ::-1]`` and ``pi[::-1]``."""
+    if game == 'connect4':
+        rows, cols = _rows_cols(board_size, game)
+        cells, columns = np.arange(rows * cols, dtype=np.int16).reshape(1, rows, cols), np.arange(cols, dtype=np.int16)
+        src_state = [np.ascontiguousarray(cells).reshape(-1), np.ascontiguousarray(cells[:, :, ::-1]).reshape(-1)]
+        src_pi = [np.ascontiguousarray(columns), np.ascontiguousarray(columns[::-1])]
+        return np.stack(src_state).astype(np.int16), np.stack(src_pi).astype(np.int16)
+    size = _rows_cols(board_size, game)[0]
     cells = np.arange(size * size, dtype=np.int16)
     states, grids = cells.reshape(1, 1, size, size), cells.reshape(1, size, size)
     src_state, src_pi = [], []
@@ -108,7 +141,7 @@ def replay_reanalyse_draws(seed, step, n, positions):
     """The positions ``ReplayReanalyser.reanalyse_sample(n, step)`` refreshes in a buffer holding ``positions`` of them, in Python
     integers -- the device's bits (k_replay_positions; csrc/rz_replay_rules.h: reanalyse_position): position i of refresh ``step``
     is the high half of x * positions for the 64-bit x of the splitmix64 chain over (seed ^ "azreanal", step, i).  Uniform over
-    POSITIONS (0 = the oldest held), with replacement: the eight symmetries of a position share one pi row.  -> int64 [n]."""
+    POSITIONS (0 = the oldest held), with replacement: the symmetries of a position share one pi row.  -> int64 [n]."""
     positions = int(positions)
     if positions <= 0:
         raise ValueError('draws need at least one position')
@@ -137,13 +170,23 @@ def reanalysed_pi(visits):
     return pi, written
 
 
-def pack_positions(trajectories, board_size):
+def pack_positions(trajectories, board_size, game='gomoku'):
     """The raw records ``DeviceReplay.add`` stores for these games, formed on the host: (stones uint64 [N][2][4], meta int32 [N],
-    pi float32 [N][A]) of the kept plies in order -- what ``DeviceReplay.read`` returns for them."""
-    A = int(board_size) ** 2
+    pi float32 [N][A]) of the kept plies in order -- what ``DeviceReplay.read`` returns for them.  ``game='connect4'``,
+    ``board_size`` (rows, cols): the moves are columns, and every stone drops onto its column's stack here, in plain Python."""
+    rows, cols = _rows_cols(board_size, game)
+    A = cols if game == 'connect4' else rows * cols
     stones, meta, pis = [], [], []
     for t in trajectories:
         P = len(t.moves)
+        cells = list(t.moves)
+        if game == 'connect4':
+            height = [0] * cols
+            for q, column in enumerate(t.moves):
+                if not (0 <= column < cols and height[column] < rows):
+                    raise ValueError('game %d: ply %d is no legal drop (column %d)' % (t.game_id, q, column))
+                cells[q] = height[column] * cols + column
+                height[column] += 1
         keep = np.ones(P, dtype=bool) if t.full is None else t.full[:P]
         z = t.z()
         for p in range(P):
@@ -151,10 +194,10 @@ def pack_positions(trajectories, board_size):
                 continue
             rec = [[0] * _hip.BOARD_WORDS, [0] * _hip.BOARD_WORDS]
             for q in range(p):
-                m = t.moves[q]
+                m = cells[q]
                 rec[(q ^ p) & 1][m >> 6] |= 1 << (m & 63)
             stones.append(rec)
-            meta.append((t.moves[p - 1] + 1 if p else 0) | ((p & 1) << META_PARITY_BIT) | ((int(z[p]) + 1) << META_Z_SHIFT))
+            meta.append((cells[p - 1] + 1 if p else 0) | ((p & 1) << META_PARITY_BIT) | ((int(z[p]) + 1) << META_Z_SHIFT))
             pis.append(np.asarray(t.pis[p], dtype=np.float32))
     return (np.array(stones, dtype=np.uint64).reshape(-1, 2, _hip.BOARD_WORDS), np.array(meta, dtype=np.int32),
             np.array(pis, dtype=np.float32).reshape(-1, A))
@@ -166,9 +209,11 @@ def _ptr(a):
 
 class DeviceReplay(object):
     """A ring of ``capacity_positions`` positions of Gomoku games on ``device``; ``len()`` is 8 x the positions held (entries, like
-    the host buffer).  No CPU fallback: HipError without a GPU."""
+    the host buffer).  ``game='connect4'``: of Connect4 games, ``board_size`` (rows, cols), ``len()`` 2 x the positions held (the
+    module docstring).  ``n_cells``, ``n_actions`` (the width of a pi row) and ``n_symmetries`` are the buffer's three sizes.
+    No CPU fallback: HipError without a GPU."""
 
-    def __init__(self, board_size, capacity_positions, device='cuda:0', seed=0):
+    def __init__(self, board_size, capacity_positions, device='cuda:0', seed=0, game='gomoku'):
         import torch
         self.torch = torch
         self.lib = _hip.load()
@@ -177,15 +222,27 @@ class DeviceReplay(object):
             raise HipError('the device replay buffer needs an MI355X (device=%r, cuda available=%s); there is no CPU fallback'
                            % (device, torch.cuda.is_available()))
         self.device = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
-        self.board_size, self.capacity = int(board_size), int(capacity_positions)
-        self.n_actions = self.board_size ** 2
+        self.game, self.capacity = game, int(capacity_positions)
+        self.rows, self.cols = _rows_cols(board_size, game)
+        self.board_size = (self.rows, self.cols) if game == 'connect4' else self.rows
+        self.n_cells = self.rows * self.cols
+        self.n_actions = self.cols if game == 'connect4' else self.n_cells
+        self.n_symmetries = 2 if game == 'connect4' else 8
         self.seed = int(seed)
         self.step = 0   # the next update ``sample`` draws without a ``step``
         handle = ctypes.c_void_p()
-        _hip.check(self.lib.rz_replay_create(self.board_size, self.capacity, self.device.index, ctypes.byref(handle)), 'rz_replay_create')
+        if game == 'connect4':
+            _hip.check(self.lib.rz_replay_create_game(_hip.GAME_CONNECT4, self.rows, self.cols, self.capacity, self.device.index, ctypes.byref(handle)),
+                       'rz_replay_create_game')
+        else:
+            _hip.check(self.lib.rz_replay_create(self.board_size, self.capacity, self.device.index, ctypes.byref(handle)), 'rz_replay_create')
         self.handle = handle
-        self.src_state, self.src_pi = symmetry_tables(self.board_size)
-        _hip.check(self.lib.rz_replay_set_tables(self.handle, _ptr(self.src_state), _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables')
+        self.src_state, self.src_pi = symmetry_tables(self.board_size, game)
+        if game == 'connect4':
+            _hip.check(self.lib.rz_replay_set_tables_game(self.handle, self.n_symmetries, self.n_cells, self.n_actions, _ptr(self.src_state),
+                                                          _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables_game')
+        else:
+            _hip.check(self.lib.rz_replay_set_tables(self.handle, _ptr(self.src_state), _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables')
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -200,7 +257,7 @@ class DeviceReplay(object):
         return self._state()[0]
 
     def __len__(self):
-        return 8 * self._state()[0]
+        return self.n_symmetries * self._state()[0]
 
     def add(self, trajectories):
         """The positions of finished games (selfplay.Trajectory; ``pis`` float64 or float32), in order: every ply, or under a
@@ -210,10 +267,10 @@ class DeviceReplay(object):
         A = self.n_actions
         offsets, moves, keeps, winners, rows = [0], [], [], [], []
         for t in trajectories:
-            if getattr(t, 'game', 'gomoku') != 'gomoku':
-                raise ValueError('the device replay buffer holds Gomoku positions, not %r' % (t.game, ))
-            if t.board_size != self.board_size:
-                raise ValueError('a game of board size %r in a buffer of %d' % (t.board_size, self.board_size))
+            if getattr(t, 'game', 'gomoku') != self.game:
+                raise ValueError('the device replay buffer holds %s positions, not %r' % ('Connect4' if self.game == 'connect4' else 'Gomoku', getattr(t, 'game', 'gomoku')))
+            if (tuple(t.board_size) if self.game == 'connect4' else t.board_size) != self.board_size:
+                raise ValueError('a game of board size %r in a buffer of %r' % (t.board_size, self.board_size))
             P = len(t.moves)
             keep = np.ones(P, dtype=np.uint8) if t.full is None else np.asarray(t.full[:P], dtype=np.uint8)
             if len(keep) != P:
@@ -239,8 +296,8 @@ class DeviceReplay(object):
         return int(h_keep.sum())
 
     def _outputs(self, n):
-        t, B = self.torch, self.board_size
-        return (t.empty((n, 4, B, B), dtype=t.float32, device=self.device), t.empty((n, self.n_actions), dtype=t.float32, device=self.device),
+        t = self.torch
+        return (t.empty((n, 4, self.rows, self.cols), dtype=t.float32, device=self.device), t.empty((n, self.n_actions), dtype=t.float32, device=self.device),
                 t.empty((n, ), dtype=t.float32, device=self.device))
 
     def gather(self, indices):
@@ -393,9 +450,11 @@ class ReplayReanalyser(object):
             raise ValueError('n_playout and slots must be positive')
         self.seed = int(seed)
         self.step = 0   # the next refresh ``reanalyse_sample`` draws without a ``step``
+        # (the buffer's game: Connect4's network has rows x cols planes and a policy head of cols columns)
+        net_shape = (replay.rows, replay.cols, replay.n_actions) if replay.game == 'connect4' else replay.board_size
         self.engine = MCTSEngine(replay.board_size, n_in_row, n_games=self.slots, n_playout=self.n_playout, c_puct=c_puct,
-                                 device=str(self.device), add_noise=False, **engine_kw)
-        self.evaluator = HipNetEvaluator(net_module, replay.board_size, str(self.device), max_boards=self.slots)
+                                 device=str(self.device), add_noise=False, game=replay.game, **engine_kw)
+        self.evaluator = HipNetEvaluator(net_module, net_shape, str(self.device), max_boards=self.slots)
         self._active_rows = None   # rows the engine's active flags select now (None: whatever the engine was created with)
         self.positions_done = 0
         self.sims_done = 0

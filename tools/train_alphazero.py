@@ -24,6 +24,11 @@ Reference quirks kept on purpose: ``lr_multiplier`` is ad
 applied and ``learn_rate`` is never passed to the agent (D-7); ``policy_evaluate`` counts
 ``win_cnt[1]`` as wins although player ids are 0/1 (D-6); ``get_equi_data`` rotates the planes
 by +i*90 degrees and pi by -i*90 degrees for odd i (D-9).
+
+``--game connect4`` (build-defined: the reference has no Connect4) trains on a ``--board`` x ``--board-width`` board (6 x 7, four in
+a row) in the batched mode only: self-play, the evaluation games, either replay buffer and Reanalyse take the game; the reference
+flow, ``--gate-against`` and several ranks are refused.  Its augmentation is the left-right mirror alone -- entry 2 j + k of a
+buffer is sample j as played (k = 0) or with every plane ``[:, :, ::-1]`` and ``pi[::-1]`` (k = 1) --: gravity breaks the rotations.
 """
 from __future__ import print_function
 
@@ -65,10 +70,14 @@ class ReplayBuffer(Sequence):
     hold (tests/test_train_script.py) -- but a collection round of 512 games (52 k positions, 420 k entries) costs the host a list
     append per game where forming every symmetry up front cost more than the round's self-play on the GPU, and a mini-batch reads 32.
     Sequence protocol (len, index, iteration: what ``random.sample`` and the tests use), ``maxlen``, ``extend`` (ready-made
-    entries: the reference flow), ``extend_samples`` (a game's un-augmented samples)."""
+    entries: the reference flow), ``extend_samples`` (a game's un-augmented samples).
+    ``game='connect4'`` (``board_size``: (rows, cols)): TWO symmetries, entry 2 j + k -- k = 0 the sample as played, k = 1 its
+    left-right mirror, every plane ``[:, :, ::-1]`` and ``pi[::-1]``."""
 
-    def __init__(self, maxlen, board_size):
-        self.maxlen, self.size = int(maxlen), int(board_size)
+    def __init__(self, maxlen, board_size, game='gomoku'):
+        self.maxlen, self.game = int(maxlen), game
+        self.size = tuple(int(v) for v in board_size) if game == 'connect4' else int(board_size)
+        self.n_symmetries = 2 if game == 'connect4' else 8
         self._blocks = deque()   # ('raw', [entries]) or ('game', states [P,4,B,B], pi grids [P,B,B], z [P])
         self._counts = deque()   # entries each block contributes
         self._skip = 0           # entries of the FIRST block that have fallen out (maxlen)
@@ -101,21 +110,29 @@ class ReplayBuffer(Sequence):
             self._trim()
 
     def extend_samples(self, play_data):
-        """A game's (state, mcts_prob, z) samples, un-augmented: 8 entries each, formed on access."""
+        """A game's (state, mcts_prob, z) samples, un-augmented: 8 entries each (Connect4: 2), formed on access."""
         play_data = list(play_data)
         if not play_data:
             return
         states = np.stack([np.asarray(s_) for s_, _, _ in play_data])
-        grids = np.stack([np.asarray(p_).reshape(self.size, self.size) for _, p_, _ in play_data])
+        if self.game == 'connect4':
+            grids = np.stack([np.asarray(p_).reshape(self.size[1]) for _, p_, _ in play_data])   # (a pi row: one value per column)
+        else:
+            grids = np.stack([np.asarray(p_).reshape(self.size, self.size) for _, p_, _ in play_data])
         self._blocks.append(('game', states, grids, [w for _, _, w in play_data]))
-        self._counts.append(8 * len(play_data))
-        self._len += 8 * len(play_data)
+        self._counts.append(self.n_symmetries * len(play_data))
+        self._len += self.n_symmetries * len(play_data)
         self._trim()
 
     def _entry(self, block, i):
         if block[0] == 'raw':
             return block[1][i]
         _, states, grids, zs = block
+        if self.game == 'connect4':
+            j, k = divmod(i, 2)
+            if k == 1:   # the left-right mirror
+                return np.ascontiguousarray(states[j][:, :, ::-1]), np.ascontiguousarray(grids[j][::-1]), zs[j]
+            return states[j], grids[j], zs[j]
         j, k = divmod(i, 8)
         quarter_turns, mirrored = k // 2 + 1, k % 2 == 1
         turned = np.rot90(states[j:j + 1], quarter_turns, axes=(2, 3))            # get_equi_data's operations on a stack of one
@@ -152,7 +169,7 @@ class TrainPipeline:
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
                  device_replay=False, temperature_schedule=None, pi_temperature=None, reanalyse=None, reanalyse_slots=512,
-                 reanalyse_playouts=None):
+                 reanalyse_playouts=None, game='gomoku', board_width=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -181,10 +198,28 @@ class TrainPipeline:
         'all': before every round's updates rank 0 searches N drawn positions of the buffer (or all of them) again with the
         current network and rewrites their pi rows (rlzero_amd.replay.ReplayReanalyser: the visit distribution at T = 1, z and
         the boards untouched); ``reanalyse_slots`` positions per search batch, ``reanalyse_playouts`` simulations each (None:
-        ``n_playout``)."""
+        ``n_playout``).
+        ``game``: 'gomoku' or 'connect4' -- Connect4 on ``board_size`` rows x ``board_width`` columns (default 7), an action is a
+        column; batched mode on one rank only, without a gate match (the reference flow's GameControl and rlzero_amd.match are
+        Gomoku's); both replay buffers hold its two symmetries (ReplayBuffer)."""
+        if game not in ('gomoku', 'connect4'):
+            raise ValueError('game %r: gomoku or connect4' % (game, ))
+        self.game_kind = game
+        if game == 'connect4':
+            if selfplay_games_in_flight <= 0:
+                raise ValueError('Connect4 is a batched-mode game: selfplay_games_in_flight must be > 0')
+            if gate_against is not None:
+                raise ValueError('the gate match is a Gomoku option: rlzero_amd.match plays no Connect4')
+            self.rows, self.cols = int(board_size), int(7 if board_width is None else board_width)
+            board_size = (self.rows, self.cols)
+        else:
+            if board_width is not None and int(board_width) != int(board_size):
+                raise ValueError('a Gomoku board is square: board_width %r with board_size %r' % (board_width, board_size))
+            self.rows = self.cols = board_size
+        self.n_cells, self.n_symmetries = self.rows * self.cols, 2 if game == 'connect4' else 8
         if (temperature_schedule is not None or pi_temperature is not None) and selfplay_games_in_flight <= 0:
             raise ValueError('the temperature schedule is a batched self-play option: selfplay_games_in_flight must be > 0')
-        self.temperature_schedule = None if temperature_schedule is None else temperature_table(temperature_schedule, board_size * board_size)
+        self.temperature_schedule = None if temperature_schedule is None else temperature_table(temperature_schedule, self.n_cells)
         self.pi_temperature = None if pi_temperature is None else float(pi_temperature)
         if device_replay and selfplay_games_in_flight <= 0:
             raise ValueError('the device replay buffer is a batched-mode option: selfplay_games_in_flight must be > 0')
@@ -210,6 +245,8 @@ class TrainPipeline:
         if resign != 'off' and selfplay_games_in_flight <= 0:
             raise ValueError('resignation is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.rank, self.world = self._init_ranks()
+        if self.world > 1 and game == 'connect4':
+            raise ValueError('Connect4 trains on one rank: several ranks are a Gomoku option')
         if self.world > 1 and selfplay_games_in_flight <= 0:
             raise ValueError('several ranks share a collection round: selfplay_games_in_flight must be > 0 (games per GPU)')
         self.resign_mode = resign if resign in ('off', 'auto') else float(resign)
@@ -219,8 +256,12 @@ class TrainPipeline:
         # board and game
         self.board_size = board_size
         self.n_in_row = n_in_row
-        self.board = GomokuEnv(board_size=self.board_size, n_in_row=self.n_in_row)
-        self.game = GameControl(self.board)
+        if game == 'connect4':   # (no GameControl: the reference flow is Gomoku's)
+            from rlzero_amd.games.connect4.connect4_env import Connect4Env
+            self.board, self.game = Connect4Env(self.rows, self.cols, self.n_in_row), None
+        else:
+            self.board = GomokuEnv(board_size=self.board_size, n_in_row=self.n_in_row)
+            self.game = GameControl(self.board)
         # training hyper-parameters (train_alphazero.py:26-41)
         self.learn_rate = 2e-3
         self.lr_multiplier = 1.0
@@ -229,11 +270,11 @@ class TrainPipeline:
         self.c_puct = 5
         if buffer_size is None:
             buffer_size = 1000 if selfplay_games_in_flight <= 0 else \
-                max(1000, selfplay_games_in_flight * self.world * board_size * board_size * 8)
+                max(1000, selfplay_games_in_flight * self.world * self.n_cells * self.n_symmetries)
         self.buffer_size = int(buffer_size)
         self.batch_size = int(batch_size)
         # (the reference's deque of augmented samples, the symmetries formed on access: ReplayBuffer)
-        self.data_buffer = ReplayBuffer(self.buffer_size, self.board_size)
+        self.data_buffer = ReplayBuffer(self.buffer_size, self.board_size, game=game)
         self.play_batch_size = 1
         self.epochs = 5
         self.kl_targ = 0.02
@@ -246,10 +287,13 @@ class TrainPipeline:
                 raise ValueError('the device replay buffer needs a GPU (this process runs on %s)' % (self.device, ))
             if self.rank == 0:   # (rank 0 holds the buffer, as with the host one; sized like the batched mode's default: one round)
                 from rlzero_amd.replay import DeviceReplay
-                self.data_buffer = DeviceReplay(self.board_size, max(1, self.buffer_size // 8), device=str(self.device))
+                self.data_buffer = DeviceReplay(self.board_size, max(1, self.buffer_size // self.n_symmetries), device=str(self.device), game=game)
         self.pure_mcts_playout_num = 100
         self.selfplay_games_in_flight = selfplay_games_in_flight
-        self.alphazero_agent = AlphaZeroAgent(self.board_size, device=self.device)
+        if game == 'connect4':
+            self.alphazero_agent = AlphaZeroAgent(self.rows, device=self.device, board_width=self.cols, n_actions=self.cols)
+        else:
+            self.alphazero_agent = AlphaZeroAgent(self.board_size, device=self.device)
         self.mcts_player = AlphaZeroPlayer(self.alphazero_agent.policy_value_fn, n_playout=self.n_playout,
                                            c_puct=self.c_puct, is_selfplay=True)
         self._batched = None
@@ -313,6 +357,13 @@ class TrainPipeline:
         play_data = list(play_data)
         if not play_data:
             return []
+        if getattr(self, 'game_kind', 'gomoku') == 'connect4':   # two symmetries: the sample as played, then its left-right mirror
+            extend_data = []
+            for state, mcts_prob, winner in play_data:
+                state, mcts_prob = np.asarray(state), np.asarray(mcts_prob)
+                extend_data.append((state, mcts_prob, winner))
+                extend_data.append((np.ascontiguousarray(state[:, :, ::-1]), np.ascontiguousarray(mcts_prob[::-1]), winner))
+            return extend_data
         size = self.board_size
         states = np.stack([np.asarray(s_) for s_, _, _ in play_data])                                   # [P, 4, B, B]
         grids = np.stack([np.asarray(p_).reshape(size, size) for _, p_, _ in play_data])                # [P, B, B]
@@ -341,7 +392,7 @@ class TrainPipeline:
                 self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
                 device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
-                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature)
+                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature, **self._game_kw())
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
         if self.resign_mode != 'off':
             # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
@@ -359,6 +410,10 @@ class TrainPipeline:
             self._trace_round(trajs)
         return trajs
 
+    def _game_kw(self):
+        """What BatchedSelfPlay.for_network / BatchedEvaluation.for_network take beyond Gomoku's defaults."""
+        return dict(game='connect4', net_shape=(self.rows, self.cols, self.cols)) if self.game_kind == 'connect4' else {}
+
     def _trace_round(self, trajs):
         """RZ_TRAIN_TRACE=<directory>: one JSON line per collection round and rank -- a digest of the torch parameters, a digest
         of what every lane's HIP evaluator answers on a fixed batch of positions (i.e. of the weights it was handed), and the
@@ -370,7 +425,7 @@ class TrainPipeline:
         for p in net.parameters():
             digest.update(p.detach().cpu().numpy().tobytes())
         rng = np.random.RandomState(7)
-        obs = torch.from_numpy((rng.rand(8, 4, self.board_size, self.board_size) < 0.3).astype(np.float32)).to(self.device)
+        obs = torch.from_numpy((rng.rand(8, 4, self.rows, self.cols) < 0.3).astype(np.float32)).to(self.device)
         answers = []
         for lane in self._batched.lanes:
             with torch.cuda.stream(lane.stream):
@@ -575,7 +630,7 @@ class TrainPipeline:
             self._duel = BatchedEvaluation.for_network(
                 self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row, n_games=n_games,
                 n_playout=self.n_playout, rollout_playouts=self.pure_mcts_playout_num, c_puct=self.c_puct, rollout_c_puct=5,
-                device=str(self.device), seed=self.selfplay_seed)
+                device=str(self.device), seed=self.selfplay_seed, **self._game_kw())
             self._duel_key = key
         self._duel.refresh_weights()
         self._duel.seed = (self.selfplay_seed + 0x9E37 * self._evaluations) & 0x7fffffff   # fresh draws every evaluation
@@ -744,9 +799,12 @@ def positive_float_arg(text):
 
 def parse_args(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku on MI355X (no arguments: the reference script\'s run)')
+    ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku (or, --game connect4, Connect4) on MI355X (no arguments: the reference script\'s run)')
     ap.add_argument('--gpus', type=int, default=1, help='processes (one per GPU); > 1 without a launcher starts them itself')
-    ap.add_argument('--board', type=int, default=6)
+    ap.add_argument('--game', choices=('gomoku', 'connect4'), default='gomoku',
+                    help='connect4: batched mode on one GPU only (needs --games-in-flight > 0; no --gate-against)')
+    ap.add_argument('--board', type=int, default=6, help='rows of the board (Gomoku: rows and columns)')
+    ap.add_argument('--board-width', type=int, default=None, metavar='W', help='connect4 only: columns of the board (default 7)')
     ap.add_argument('--n-in-row', type=int, default=4)
     ap.add_argument('--playouts', type=int, default=400)
     ap.add_argument('--batches', type=int, default=64, help='game_batch_num')
@@ -779,6 +837,18 @@ def parse_args(argv=None):
     ap.add_argument('--reanalyse-slots', type=int, default=512, metavar='G', help='positions searched per batch of a refresh')
     ap.add_argument('--reanalyse-playouts', type=int, default=None, metavar='P', help='simulations of a refreshing search (default: --playouts)')
     args = ap.parse_args(argv)
+    if args.game == 'connect4':
+        if args.board_width is None:
+            args.board_width = 7
+        if args.games_in_flight <= 0:
+            ap.error('--game connect4 needs --games-in-flight > 0 (batched mode)')
+        if args.gate_against is not None:
+            ap.error('--gate-against is a Gomoku option: matches play no Connect4')
+        if args.gpus > 1:
+            ap.error('--game connect4 runs on one GPU')
+    elif args.board_width is not None:
+        ap.error('--board-width is a Connect4 option (--game connect4)')
+    n_cells = args.board * (args.board_width if args.game == 'connect4' else args.board)
     if args.batch_size < 1 or args.updates_per_round < 1:
         ap.error('--batch-size and --updates-per-round must be >= 1')
     if args.reanalyse and not args.device_replay:
@@ -801,8 +871,8 @@ def parse_args(argv=None):
         ap.error('--temperature-schedule needs --games-in-flight > 0 (batched self-play)')
     if args.pi_temperature is not None and args.games_in_flight <= 0:
         ap.error('--pi-temperature needs --games-in-flight > 0 (batched self-play)')
-    if args.temperature_schedule is not None and args.temperature_schedule[0] == 'step' and args.temperature_schedule[2] + 1 > args.board * args.board:
-        ap.error('--temperature-schedule: N = %d early plies, the board has %d cells' % (args.temperature_schedule[2], args.board * args.board))
+    if args.temperature_schedule is not None and args.temperature_schedule[0] == 'step' and args.temperature_schedule[2] + 1 > n_cells:
+        ap.error('--temperature-schedule: N = %d early plies, the board has %d cells' % (args.temperature_schedule[2], n_cells))
     if args.resign_threshold != 'off' and args.games_in_flight <= 0:
         ap.error('--resign-threshold needs --games-in-flight > 0 (batched self-play)')
     if args.resign_threshold not in ('off', 'auto'):
@@ -827,7 +897,8 @@ def main():
                          resign_fp_target=args.resign_fp_target, playout_cap=args.playout_cap, gate_against=args.gate_against,
                          batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay,
                          temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature,
-                         reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts)
+                         reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts,
+                         game=args.game, board_width=args.board_width)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
