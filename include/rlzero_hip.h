@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 39
+#define RZ_ABI_VERSION 40
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -1103,6 +1103,43 @@ int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream);
 int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int64_t *h_w, int64_t *h_total, void *stream);
 int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n, const int64_t *d_targets, int64_t *d_draws,
                                   double *d_prob, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The fused MuZero learner (ABI 40; rz_mz_learn.hip: k_mzl_grad, k_mzl_reduce, k_mzl_adam; rz_mz_learn.h; an opt-in route beside
+ * rlzero_amd/muzero/agent.py: MuZeroAgent.learn, whose arithmetic it restates in float32): forward through initial_inference
+ * and K recurrent_inference steps, the three losses, backward through the unroll, clip_grad_norm_ and torch's single-tensor
+ * Adam with weight decay in THREE launches on `stream`, no host synchronisation.  Hidden size 64 only, obs_dim <= 16,
+ * n_actions <= 8, unroll_steps <= 16 (the device replay's limits).  Every reduction (weight gradients across workgroups, the
+ * norm, the loss means) runs in a fixed order without floating-point atomics: the same inputs give the same bits.
+ *
+ * rz_mz_learner_bind: params void* [18] = the DEVICE storage of weight and bias of rep1 rep2 dyn1 dyn2 rew1 rew2 pre1 pol val
+ *   (contiguous float32, row-major [out][in], 16-byte aligned), read and written where they lie; exp_avg / exp_avg_sq float32
+ *   [n_params] flat in that order (rz_mz_learner_n_params), owned by the caller.
+ * The batch: the six tensors of rz_mz_replay_gather -- d_obs float32 [n][D], d_actions int64 [n][K], d_tv / d_tr float32
+ *   [n][K + 1], d_tp float32 [n][K + 1][A], d_mask float32 [n][K + 1] -- and d_weights float32 [n] or NULL (all ones);
+ *   1 <= n <= max_batch.  An action outside 0 .. A-1 is read as 0, indexes nothing, and sets RZ_MZ_LEARNER_BAD_ACTION
+ *   (rz_mz_learner_poll_errors; sticky until polled); while the flag stands rz_mz_learner_step updates nothing, and
+ *   rz_mz_learner_poll_errors reports in *skipped how many updates were dropped (the caller takes them off its step count).
+ * rz_mz_learner_grads: d_flat_grad float32 [n_params] = the raw gradient of the loss (before the clip), d_out4 float32 [4] =
+ *   (loss, value, reward, policy) means; two launches, nothing is updated.
+ * rz_mz_learner_step: the same, then the clip by max_norm and Adam step number `step_count` (1 = the first) on the bound
+ *   parameters and moments; the bias corrections are formed on the host in double from step_count. */
+enum { RZ_MZ_LEARNER_BAD_ACTION = 1 };
+typedef struct rz_mz_learner_config {
+    int32_t abi_version; /* RZ_ABI_VERSION */
+    int32_t obs_dim, n_actions, hidden, unroll_steps, max_batch, device, reserved;
+    double lr, weight_decay, beta1, beta2, eps, max_norm;
+} rz_mz_learner_config;
+typedef struct rz_mz_learner rz_mz_learner;
+int rz_mz_learner_create(const rz_mz_learner_config *cfg, rz_mz_learner **out);
+int rz_mz_learner_destroy(rz_mz_learner *l);
+int rz_mz_learner_n_params(rz_mz_learner *l, int64_t *n_params);
+int rz_mz_learner_bind(rz_mz_learner *l, void *const *d_params, float *d_exp_avg, float *d_exp_avg_sq);
+int rz_mz_learner_grads(rz_mz_learner *l, const float *d_obs, const int64_t *d_actions, const float *d_tv, const float *d_tr, const float *d_tp,
+                        const float *d_mask, const float *d_weights, int64_t n, float *d_flat_grad, float *d_out4, void *stream);
+int rz_mz_learner_step(rz_mz_learner *l, const float *d_obs, const int64_t *d_actions, const float *d_tv, const float *d_tr, const float *d_tp,
+                       const float *d_mask, const float *d_weights, int64_t n, int64_t step_count, float *d_out4, void *stream);
+int rz_mz_learner_poll_errors(rz_mz_learner *l, int32_t *flags, int32_t *skipped, void *stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 LIB = os.path.join(PKG, 'librlzero_hip.so')
 OBJ_DIR = os.path.join(PKG, 'csrc', '_obj')
-SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip', 'rz_replay.hip', 'rz_mz_replay.hip')]
+SOURCES = [os.path.join(PKG, 'csrc', name) for name in ('rz_engine.hip', 'rz_net.hip', 'rz_muzero.hip', 'rz_replay.hip', 'rz_mz_replay.hip',
+                                                             'rz_mz_learn.hip')]
 HEADERS = [os.path.join(REPO, 'include', 'rlzero_hip.h')] + sorted(glob.glob(os.path.join(PKG, 'csrc', '*.h')))  # every header beside the sources
 FLAGS = ['--offload-arch=gfx950', '-O3', '-ffp-contract=off', '-fno-fast-math', '-fno-slp-vectorize', '-std=c++17',
          '-fPIC', '-Wall', '-Wno-unused-function']

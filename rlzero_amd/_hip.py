@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -44,6 +44,13 @@ class RzMzConfig(Structure):
     _fields_ = [('abi_version', c_int32), ('n_games', c_int32), ('n_actions', c_int32), ('n_sims', c_int32),
                 ('discount', c_double), ('pb_c_base', c_double), ('pb_c_init', c_double),
                 ('device', c_int32), ('reserved', c_int32)]
+
+
+class RzMzLearnerConfig(Structure):
+    """rz_mz_learner_config: the geometry and the optimizer's constants of the fused MuZero learner (ABI 40)."""
+    _fields_ = [('abi_version', c_int32), ('obs_dim', c_int32), ('n_actions', c_int32), ('hidden', c_int32), ('unroll_steps', c_int32),
+                ('max_batch', c_int32), ('device', c_int32), ('reserved', c_int32), ('lr', c_double), ('weight_decay', c_double),
+                ('beta1', c_double), ('beta2', c_double), ('eps', c_double), ('max_norm', c_double)]
 
 
 class RzMzCartPolePlay(Structure):
@@ -89,6 +96,7 @@ PLAY_RUNNING, PLAY_STALLED, PLAY_RESOLVED, PLAY_ENDED, PLAY_SEARCHED = 1, 2, 4, 
 PLAY_RESIGNED, PLAY_NO_RESIGN, PLAY_WOULD_RESIGN = 32, 64, 128   # resignation (rz_play_set_resign, ABI 27)
 PLAY_FULL = 256   # playout cap (rz_play_set_cap, ABI 28): the record's search had the full budget
 REPLAY_BAD_INDEX = 1   # rz_replay_poll_errors (ABI 31): an entry index from the device was out of range
+MZ_LEARNER_BAD_ACTION = 1   # rz_mz_learner_poll_errors (ABI 40): an action of a batch was outside 0 .. A-1
 MZ_REPLAY_BAD_INDEX, MZ_REPLAY_BAD_ROWS = 1, 2   # rz_mz_replay_poll_errors (ABI 35): a draw from the device / an entry's rows out of range
 
 
@@ -245,6 +253,13 @@ _SIGNATURES = {
     'rz_mz_replay_refresh_priorities': (c_int, [P, P]),
     'rz_mz_replay_read_priorities': (c_int, [P, c_int64, c_int64, P, POINTER(c_int64), P]),
     'rz_mz_replay_draw_prioritized': (c_int, [P, c_uint64, c_uint64, c_int64, P, P, P, P]),
+    'rz_mz_learner_create': (c_int, [POINTER(RzMzLearnerConfig), POINTER(c_void_p)]),
+    'rz_mz_learner_destroy': (c_int, [P]),
+    'rz_mz_learner_n_params': (c_int, [P, POINTER(c_int64)]),
+    'rz_mz_learner_bind': (c_int, [P, P, P, P]),
+    'rz_mz_learner_grads': (c_int, [P, P, P, P, P, P, P, P, c_int64, P, P, P]),
+    'rz_mz_learner_step': (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, P, P]),
+    'rz_mz_learner_poll_errors': (c_int, [P, POINTER(c_int32), POINTER(c_int32), P]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// rz_host.h -- the host-side runtime the five translation units share (rz_engine, rz_net, rz_muzero, rz_replay, rz_mz_replay): the error
+// rz_host.h -- the host-side runtime the six translation units share (rz_engine, rz_net, rz_muzero, rz_replay, rz_mz_replay, rz_mz_learn): the error
 // message, the checks every entry point opens with, the two ways to own device memory and the staging pair.  Host code only: no kernel,
 // nothing a kernel reads.  One copy of each, so that a new subsystem takes its plumbing from here instead of copying a neighbour's.
 #pragma once

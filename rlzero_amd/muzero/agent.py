@@ -1,7 +1,10 @@
 """MuZero learner: K-step unrolled training of the learned model (arXiv:1911.08265v2, appendix G and the
 pseudocode's ``update_weights``): value and reward by squared error (scalar heads), policy by cross-entropy
 against the search visit distribution, gradient of the unrolled steps scaled by 1/K, the gradient flowing into
-the dynamics function halved at every step."""
+the dynamics function halved at every step.
+
+``fused_learner=True`` (opt-in): the same update as three HIP launches without a host synchronisation (learner.py:
+MuZeroFusedLearner; csrc/rz_mz_learn.hip).  ``learn`` below stays the definition of the arithmetic and the default."""
 import torch
 import torch.nn.functional as F
 
@@ -14,17 +17,47 @@ def scale_gradient(x, scale):
 
 class MuZeroAgent(object):
 
-    def __init__(self, obs_dim=4, n_actions=2, hidden=64, lr=3e-3, weight_decay=1e-4, device='cuda:0'):
+    def __init__(self, obs_dim=4, n_actions=2, hidden=64, lr=3e-3, weight_decay=1e-4, device='cuda:0', fused_learner=False, unroll_steps=5,
+                 max_batch=1024):
+        """``fused_learner``: updates run in the HIP learner (hidden 64, obs_dim <= 16, n_actions <= 8, unroll_steps <= 16: a
+        ValueError names the limit before anything is allocated); ``unroll_steps`` and ``max_batch`` size it (batches of K =
+        unroll_steps and up to max_batch rows) and mean nothing to the PyTorch route.  The route is fixed for the agent's life; a
+        checkpoint moves between the routes."""
+        self.fused_learner = bool(fused_learner)
+        if self.fused_learner:
+            from .learner import check_limits
+            check_limits(obs_dim, n_actions, hidden, unroll_steps)
         self.device = torch.device(device)
         self.n_actions = n_actions
         self.net = MuZeroNet(obs_dim, n_actions, hidden).to(self.device)
-        self.optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=weight_decay)
+        self.optimizer = None
+        self.fused = None
+        if self.fused_learner:
+            from .learner import MuZeroFusedLearner
+            self.net.eval()
+            self.fused = MuZeroFusedLearner(self.net, lr=lr, weight_decay=weight_decay, unroll_steps=unroll_steps, max_batch=max_batch)
+        else:
+            self.optimizer = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=weight_decay)
+
+    def learn_async(self, batch, weights=None):
+        """One fused update enqueued on the current stream -> float32 [4] on the device: (loss, value loss, reward loss, policy
+        loss).  Nothing is synchronised; read the result (or call ``check``) when it is needed."""
+        if self.fused is None:
+            raise RuntimeError('learn_async is the fused learner\'s (MuZeroAgent(fused_learner=True)); this agent learns through PyTorch')
+        return self.fused.step(batch, weights)
+
+    def check(self):
+        """Fused route: raises if an update since the last call met an action outside 0 .. A-1 (it changed no parameter)."""
+        if self.fused is not None:
+            self.fused.check()
 
     def learn(self, batch, weights=None):
         """batch = ReplayBuffer.sample(...) (numpy arrays) or MuZeroDeviceReplay.sample(...) (device tensors, taken as they are)
         -> (loss, value loss, reward loss, policy loss) floats.  ``weights`` [b] (MuZeroDeviceReplay.sample_prioritized): the
         importance weights of prioritized replay, a factor on every entry's loss before the mean (appendix G); the three
         component losses returned stay unweighted."""
+        if self.fused is not None:
+            return tuple(self.learn_async(batch, weights).tolist())
         obs, actions, tv, tr, tp, mask = ((a if isinstance(a, torch.Tensor) else torch.from_numpy(a)).to(self.device) for a in batch)
         K = actions.shape[1]
         net = self.net
@@ -53,9 +86,15 @@ class MuZeroAgent(object):
         return float(loss.item()), float(lv.mean().item()), float(lr_.mean().item()), float(lp.mean().item())
 
     def save_model(self, path):
-        torch.save({'model': self.net.state_dict(), 'optimizer': self.optimizer.state_dict()}, path)
+        """Either route writes torch's Adam ``state_dict`` (the fused one: views of its flat moments, ``step`` as torch stores it)."""
+        opt = self.fused.optimizer_state_dict() if self.fused is not None else self.optimizer.state_dict()
+        torch.save({'model': self.net.state_dict(), 'optimizer': opt}, path)
 
     def load_model(self, path):
+        """Reads either route's file."""
         ck = torch.load(path, map_location=self.device)
         self.net.load_state_dict(ck['model'])
-        self.optimizer.load_state_dict(ck['optimizer'])
+        if self.fused is not None:
+            self.fused.load_optimizer_state_dict(ck['optimizer'])
+        else:
+            self.optimizer.load_state_dict(ck['optimizer'])

@@ -9,6 +9,7 @@ its ``tools/train_alphazero.py`` (a pipeline class with ``collect_selfplay_data`
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay   # episodes and mini-batches stay on the GPU
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --reanalyse all   # and their targets stay fresh
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --prioritized-replay   # steps drawn by |value - return|
+    python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --fused-learner   # and every update is three HIP launches
 """
 import argparse
 import os
@@ -39,7 +40,7 @@ class MuZeroPipeline(object):
 
     def __init__(self, n_envs=256, n_sims=50, unroll_steps=5, td_steps=10, discount=0.997, batch_size=256,
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
-                 reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0):
+                 reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False):
         """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
@@ -47,7 +48,10 @@ class MuZeroPipeline(object):
         (MuZeroReanalyser: a second, small search object; the self-play object and its counters are not touched).  0: off.
         ``prioritized_replay`` (needs ``device_replay``): mini-batches are drawn in proportion to |search value - n-step return|
         of the stored steps (MuZeroDeviceReplay.sample_prioritized) and the loss of an entry is scaled by its importance weight
-        (1 / (N P)) ** ``priority_beta``; a Reanalyse moves the priorities with the root values it rewrites."""
+        (1 / (N P)) ** ``priority_beta``; a Reanalyse moves the priorities with the root values it rewrites.
+        ``fused_learner``: the updates run in the HIP learner (MuZeroAgent(fused_learner=True)): ``policy_update`` enqueues all of
+        them and reads only the last result.  Works with either buffer and with every option above."""
+        self.fused_learner = bool(fused_learner)
         self.prioritized_replay, self.priority_beta = bool(prioritized_replay), float(priority_beta)
         if self.prioritized_replay and not device_replay:
             raise ValueError(PRIORITIES_NEED_DEVICE_REPLAY)
@@ -55,7 +59,8 @@ class MuZeroPipeline(object):
         if self.reanalyse and not device_replay:
             raise ValueError(NEEDS_DEVICE_REPLAY)
         from rlzero_amd.muzero import CartPoleBatch, MuZeroAgent, MuZeroDeviceReplay, MuZeroReanalyser, MuZeroSelfPlay, ReplayBuffer
-        self.agent = MuZeroAgent(device=device)
+        self.agent = (MuZeroAgent(device=device, fused_learner=True, unroll_steps=unroll_steps, max_batch=batch_size) if self.fused_learner
+                      else MuZeroAgent(device=device))
         self.env = CartPoleBatch(n_envs, device, seed=seed)
         self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed)
         self.device_replay = bool(device_replay)
@@ -92,8 +97,25 @@ class MuZeroPipeline(object):
             return 0
         return self.reanalyser.reanalyse_all() if self.reanalyse == 'all' else self.reanalyser.reanalyse_sample(self.reanalyse)
 
+    def _batch(self):
+        """-> (mini-batch, importance weights or None)."""
+        if self.prioritized_replay:
+            return self.buffer.sample_prioritized(self.batch_size, beta=self.priority_beta)
+        if self.device_replay:
+            return self.buffer.sample(self.batch_size), None
+        return self.buffer.sample(self.batch_size, self.env.n_actions), None
+
     def policy_update(self):
         out = (0.0, 0.0, 0.0, 0.0)
+        if self.fused_learner:   # every update enqueued behind the last; one read at the end
+            last = None
+            for _ in range(self.updates_per_iteration):
+                batch, weights = self._batch()
+                last = self.agent.learn_async(batch, weights=weights)
+            if last is not None:
+                out = tuple(last.tolist())
+                self.agent.check()
+            return out
         for _ in range(self.updates_per_iteration):
             if self.prioritized_replay:
                 batch, weights = self.buffer.sample_prioritized(self.batch_size, beta=self.priority_beta)
@@ -117,7 +139,7 @@ class MuZeroPipeline(object):
         return self.episode_len
 
 
-if __name__ == '__main__':
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=256)
     ap.add_argument('--sims', type=int, default=50)
@@ -134,6 +156,13 @@ if __name__ == '__main__':
                     help='draw mini-batches in proportion to |search value - n-step return| of the stored steps and scale the loss by the '
                          'importance weights (needs --device-replay)')
     ap.add_argument('--priority-beta', type=float, default=1.0, metavar='B', help='exponent of the importance weights (1 / (N P)) ** B')
+    ap.add_argument('--fused-learner', action='store_true',
+                    help='run every update in the HIP learner: forward, backward, clip and Adam in three launches, no host synchronisation')
+    return ap
+
+
+if __name__ == '__main__':
+    ap = build_parser()
     args = ap.parse_args()
     if args.reanalyse and not args.device_replay:
         ap.error(NEEDS_DEVICE_REPLAY)
@@ -141,7 +170,7 @@ if __name__ == '__main__':
         ap.error(PRIORITIES_NEED_DEVICE_REPLAY)
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
                           updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
-                          prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta)
+                          prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta, fused_learner=args.fused_learner)
     pipe.run(args.iterations)
     if args.save:
         pipe.agent.save_model(args.save)
