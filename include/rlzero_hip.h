@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 40
+#define RZ_ABI_VERSION 41
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -837,6 +837,46 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
  * finished environment), d_reward float32, d_terminated / d_truncated uint8. */
 int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                      float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
+/* Moves kept on the device for any environment the library knows (ABI 41; rz_muzero.hip: k_mz_env_step, k_mz_env_move,
+ * k_mz_root_noise; the rules: csrc/rz_mz_env.h).  kind: RZ_MZ_ENV_CARTPOLE (4 state doubles, 4 observations, 2 actions) or
+ * RZ_MZ_ENV_ACROBOT (Acrobot-v1: 4 state doubles theta1, theta2, dtheta1, dtheta2; 6 observations cos / sin of the two angles and
+ * the two velocities; 3 actions = torque -1, 0, +1; reward -1 per step, 0 for the step that reaches the goal).
+ * rz_mz_env_step: rz_cartpole_step for either kind -- one step of n_envs environments with auto-reset in ONE launch, d_state
+ * float64 [n_envs][4], the time limit max_episode_steps an argument; d_obs float32 [n_envs][D] after the reset.  d_actions NULL:
+ * no step, only d_obs is written (the observation of the current state; d_reward and the flags may be NULL then).
+ * rz_mz_env_move: the move behind a finished search (rz_mz_search on the same stream), a thread per environment: the action from
+ * the root's visit counts ^ (1 / temperature) (first maximum at temperature <= 0) with the whole moves' draw keyed (noise_seed,
+ * environment, episode, step); the record obs (D) | action | reward | visits (A) | root value | done to d_ring [n_games]
+ * [ring_steps][D + 4 + A] at step % ring_steps; the environment step; for a finished episode its run in d_arena, its entry
+ * (environment, end step, length, first arena row or -1), d_episode_start, the next episode's initial state; the state; the next
+ * observation to d_obs float32 [n_games][D].  Counters, entries, arena and ring are laid out as rz_mz_play_cartpole's (the caller
+ * zeroes d_counters before the first move that uses an arena); ring_steps >= max_episode_steps, max_entries >= n_games.  The
+ * tree's n_actions must be the environment's.
+ * rz_mz_root_noise: d_eta float64 [n_games][n_actions] = the normalised Dirichlet(alpha) noise of the whole moves under their key
+ * (noise_seed, environment, d_episode, d_steps), in the form rz_mz_init_roots takes; dirichlet_alpha >= 0.1 (see above), at most
+ * 8 actions. */
+#define RZ_MZ_ENV_CARTPOLE 0
+#define RZ_MZ_ENV_ACROBOT 1
+typedef struct rz_mz_env_play {
+    double *d_state;
+    int64_t *d_steps, *d_episode, *d_episode_start;
+    uint64_t env_seed, noise_seed;
+    double temperature;
+    int64_t max_episode_steps;
+    double *d_ring;
+    int32_t ring_steps, reserved;
+    int64_t step;
+    double *d_arena;
+    int64_t arena_rows;
+    int64_t *d_counters, *d_entries;
+    int64_t max_entries;
+    float *d_obs;
+} rz_mz_env_play;
+int rz_mz_env_step(int32_t kind, double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
+                   int64_t max_episode_steps, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
+int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream);
+int rz_mz_root_noise(rz_muzero *e, const int64_t *d_episode, const int64_t *d_steps, uint64_t noise_seed, double dirichlet_alpha, double *d_eta,
+                     void *stream);
 int rz_mz_root_children(rz_muzero *e, int32_t what, void *d_out, void *stream);
 int rz_mz_root_stats(rz_muzero *e, int32_t *d_n, double *d_value_sum, double *d_vmin, double *d_vmax, void *stream);
 int rz_mz_geometry(rz_muzero *e, int32_t *slots_per_game, int64_t *device_bytes);

@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 40
+ABI_VERSION = 41
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -60,6 +60,18 @@ class RzMzCartPolePlay(Structure):
                 ('temperature', c_double), ('d_ring', c_void_p), ('ring_steps', c_int32), ('reserved', c_int32),
                 ('first_step', c_int64), ('d_arena', c_void_p), ('arena_rows', c_int64), ('d_counters', c_void_p),
                 ('d_entries', c_void_p), ('max_entries', c_int64)]
+
+
+class RzMzEnvPlay(Structure):
+    """rz_mz_env_play: environments, random streams and the device-side history of rz_mz_env_move (ABI 41)."""
+    _fields_ = [('d_state', c_void_p), ('d_steps', c_void_p), ('d_episode', c_void_p), ('d_episode_start', c_void_p),
+                ('env_seed', c_uint64), ('noise_seed', c_uint64), ('temperature', c_double), ('max_episode_steps', c_int64),
+                ('d_ring', c_void_p), ('ring_steps', c_int32), ('reserved', c_int32), ('step', c_int64), ('d_arena', c_void_p),
+                ('arena_rows', c_int64), ('d_counters', c_void_p), ('d_entries', c_void_p), ('max_entries', c_int64), ('d_obs', c_void_p)]
+
+
+MZ_ENV_CARTPOLE, MZ_ENV_ACROBOT = 0, 1   # rz_mz_env_step / rz_mz_env_move (ABI 41)
+MZ_ENV_KINDS = {'cartpole': MZ_ENV_CARTPOLE, 'acrobot': MZ_ENV_ACROBOT}
 
 
 class RzRawHeads(Structure):
@@ -217,6 +229,9 @@ _SIGNATURES = {
     'rz_mz_load_representation': (c_int, [P, POINTER(c_void_p), c_int32, c_int32, c_int32]),
     'rz_mz_play_cartpole': (c_int, [P, P, c_int32, c_int32, POINTER(RzMzCartPolePlay), P]),
     'rz_cartpole_step': (c_int, [P, P, P, P, c_int32, c_uint64, P, P, P, P, P]),
+    'rz_mz_env_step': (c_int, [c_int32, P, P, P, P, c_int32, c_uint64, c_int64, P, P, P, P, P]),
+    'rz_mz_env_move': (c_int, [P, c_int32, POINTER(RzMzEnvPlay), P]),
+    'rz_mz_root_noise': (c_int, [P, P, P, c_uint64, c_double, P, P]),
     'rz_mz_root_children': (c_int, [P, c_int32, P, P]),
     'rz_mz_root_stats': (c_int, [P, P, P, P, P, P]),
     'rz_mz_geometry': (c_int, [P, POINTER(c_int32), POINTER(c_int64)]),

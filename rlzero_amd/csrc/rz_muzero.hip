@@ -15,6 +15,9 @@
 //   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search);
 //   * rz_mz_play_cartpole: whole MOVES in one launch -- initial inference, root noise, search, action draw, CartPole step,
 //     episode history on the device (k_mz_search with its MOVES stages).
+// Behind rz_mz_search, for any environment whose rules the library holds (rz_mz_env.h; at the end of this file): rz_mz_env_move --
+// action draw, environment step, record, hand-over of finished episodes, a thread per environment -- with rz_mz_root_noise and
+// rz_mz_env_step beside it.
 // A MuZero tree is tiny (n_sims + 1 expanded nodes, A children each) and its walk is a short chain of dependent steps,
 // so the parallelism is across the thousands of games.  Tree layout in HBM (per game g, node slot i, slot index
 // g * cap + i): one 32-byte record per node: N int32, first_child int32 (-1 = not expanded; the A children of a node are
@@ -33,6 +36,7 @@
 
 #include "rlzero_hip.h"
 #include "rz_host.h"
+#include "rz_mz_env.h"
 
 #pragma clang fp contract(off)
 
@@ -1786,6 +1790,270 @@ int rz_mz_error_flags(rz_muzero *e, int32_t *flags) {
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(flags, e->dev.err, 4, hipMemcpyDeviceToHost) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy(err) failed");
     return RZ_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ moves kept on the device, generic over the environment
+// The layer between a finished search and the replay -- action draw, environment step, record, hand-over of finished episodes --
+// as launches of their own behind rz_mz_search (k_mz_search is not involved: its MOVES stages stay CartPole's).  An environment is
+// a trait (rz_mz_env.h); k_mz_env_step and k_mz_env_move are instantiated once per kind.
+namespace {
+
+// CartPole's trait: the functions above, called (the step's own 500-step limit is replaced by the caller's)
+struct EnvCartPole {
+    typedef MzCartPole State;
+    static constexpr int kState = 4, kObs = 4, kActions = 2;
+    __device__ __forceinline__ static void load(State &c, const double *s, long long steps, long long episode) { c = State{s[0], s[1], s[2], s[3], steps, episode}; }
+    __device__ __forceinline__ static void store(const State &c, double *s) {
+        s[0] = c.x;
+        s[1] = c.x_dot;
+        s[2] = c.theta;
+        s[3] = c.theta_dot;
+    }
+    __device__ __forceinline__ static void reset(State &c, uint64_t seed, int env) { cartpole_reset(c, seed, env); }
+    __device__ __forceinline__ static int step(State &c, int action, long long max_episode_steps, double *reward) {
+        const int bits = cartpole_step(c, action);
+        *reward = 1.0;
+        return (bits & 1 ? RZ_MZE_TERMINATED : 0) | (c.steps >= max_episode_steps ? RZ_MZE_TRUNCATED : 0);
+    }
+    __device__ __forceinline__ static void observe(const State &c, float *obs) {
+        obs[0] = (float)c.x;
+        obs[1] = (float)c.x_dot;
+        obs[2] = (float)c.theta;
+        obs[3] = (float)c.theta_dot;
+    }
+};
+
+// one step of every environment with auto-reset (k_cartpole_step for any kind); actions == nullptr: no step, the observation only
+template <typename Env>
+__global__ __launch_bounds__(128) void k_mz_env_step(double *state, long long *steps, long long *episode, const long long *actions, int n_envs,
+                              unsigned long long seed, long long max_episode_steps, float *obs, float *reward, uint8_t *terminated,
+                              uint8_t *truncated) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_envs) return;
+    typename Env::State c;
+    Env::load(c, state + (long long)Env::kState * g, steps[g], episode[g]);
+    if (actions != nullptr) {
+        long long a = actions[g];
+        a = a < 0 ? 0 : (a >= Env::kActions ? Env::kActions - 1 : a);
+        double r = 0.0;
+        const int done = Env::step(c, (int)a, max_episode_steps, &r);
+        if (done) {
+            c.episode += 1;
+            Env::reset(c, seed, g);
+        }
+        Env::store(c, state + (long long)Env::kState * g);
+        steps[g] = c.steps;
+        episode[g] = c.episode;
+        reward[g] = (float)r;
+        terminated[g] = (uint8_t)(done & RZ_MZE_TERMINATED ? 1 : 0);
+        truncated[g] = (uint8_t)(done & RZ_MZE_TRUNCATED ? 1 : 0);
+    }
+    float o[Env::kObs];
+    Env::observe(c, o);
+#pragma unroll
+    for (int i = 0; i < Env::kObs; ++i) obs[(long long)Env::kObs * g + i] = o[i];
+}
+
+struct MzEnvPlay {      // rz_mz_env_move: MzPlay's history (same layout of ring, arena, entries, counters) around ONE move
+    double *state;                          // [G][kState]
+    long long *steps, *episode, *ep_start;  // [G]
+    unsigned long long env_seed, noise_seed;
+    double inv_temperature;                 // <= 0: the first maximum of the visit counts
+    long long max_episode_steps;
+    double *ring;                           // [G][hist][row]
+    int hist;
+    long long t;                            // global step index of this move
+    double *arena;                          // [arena_rows][row]
+    long long arena_rows;
+    long long *counters, *entries;          // [4]; [max_entries][4]
+    long long max_entries;
+    float *obs;                             // [G][kObs]: the observation the next search starts from
+};
+
+// the move behind a finished search: what the MOVES stage of k_mz_search does at "the move", from the tree in HBM; a thread per
+// environment.  Plain stores and the two counters' atomics; a finished episode's earlier records were written by earlier launches.
+template <typename Env>
+__global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
+    constexpr int D = Env::kObs, A = Env::kActions, ROW = D + 4 + A;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.n_games) return;
+    const MzNode *nodes = E.nodes + (long long)g * E.cap;
+    const MzNode root = nodes[0];
+    const bool grown = root.first_child >= 1 && root.first_child + A <= E.cap;
+    int visits[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) visits[a] = grown ? nodes[root.first_child + a].N : 0;
+    typename Env::State env;
+    Env::load(env, P.state + (long long)Env::kState * g, P.steps[g], P.episode[g]);
+    long long ep_start = P.ep_start[g];
+    // 1, 2: the weights and the draw
+    double wgt[A], total;
+    int action = rzmze::move_weights(visits, A, P.inv_temperature, wgt, &total);
+    if (P.inv_temperature > 0.0)
+        action = rzmze::move_draw(wgt, A, total, rzmze::move_key(P.noise_seed, 0xA5A5A5A5ull, g, env.episode, env.steps));
+    // 3, 4: the record (the observation is the one the search started from) and the step
+    double rec[ROW];
+    {
+        float o[D];
+        Env::observe(env, o);
+#pragma unroll
+        for (int i = 0; i < D; ++i) rec[i] = (double)o[i];
+    }
+    double reward = 0.0;
+    const int done = Env::step(env, action, P.max_episode_steps, &reward);
+    rec[D] = (double)action;
+    rec[D + 1] = reward;
+#pragma unroll
+    for (int a = 0; a < A; ++a) rec[D + 2 + a] = (double)visits[a];
+    rec[D + 2 + A] = root.value_sum / (double)(root.N > 1 ? root.N : 1);
+    rec[D + 3 + A] = done ? 1.0 : 0.0;
+    double *ring_g = P.ring + (long long)g * P.hist * ROW;
+    {
+        double *dst = ring_g + (P.t % P.hist) * ROW;
+#pragma unroll
+        for (int c = 0; c < ROW; ++c) dst[c] = rec[c];
+    }
+    if (done) {
+        // 5: the episode's records as one run in the arena, its entry, the next episode
+        long long len = P.t + 1 - ep_start;
+        const long long most = P.t + 1 < P.hist ? P.t + 1 : P.hist;
+        len = len < 1 ? 1 : (len > most ? most : len);   // (an episode longer than the ring cannot be: rz_mz_env_move sizes it)
+        long long off = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters), (unsigned long long)len);
+        if (off < 0 || off + len > P.arena_rows) {
+            off = -1;
+            atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 2), 1ull);
+        }
+        const long long e = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 1), 1ull);
+        if (e >= 0 && e < P.max_entries) {
+            P.entries[4 * e + 0] = g;
+            P.entries[4 * e + 1] = P.t + 1;
+            P.entries[4 * e + 2] = len;
+            P.entries[4 * e + 3] = off;
+        }
+        if (off >= 0) {
+            for (long long j = 0; j < len - 1; ++j) {
+                const double *src = ring_g + ((P.t + 1 - len + j) % P.hist) * ROW;
+                double *dst = P.arena + (off + j) * ROW;
+#pragma unroll
+                for (int c = 0; c < ROW; ++c) dst[c] = src[c];
+            }
+            double *dst = P.arena + (off + len - 1) * ROW;
+#pragma unroll
+            for (int c = 0; c < ROW; ++c) dst[c] = rec[c];
+        }
+        ep_start = P.t + 1;
+        env.episode += 1;
+        Env::reset(env, P.env_seed, g);
+    }
+    // 6, 7: the state and the next observation
+    Env::store(env, P.state + (long long)Env::kState * g);
+    P.steps[g] = env.steps;
+    P.episode[g] = env.episode;
+    P.ep_start[g] = ep_start;
+    float o[D];
+    Env::observe(env, o);
+#pragma unroll
+    for (int i = 0; i < D; ++i) P.obs[(long long)D * g + i] = o[i];
+}
+
+// the normalised root noise of a move, eta [G][A], under the whole moves' key (noise_seed, g, episode, steps): the draws of
+// k_mz_search's MOVES stage (mz_gamma per action, the sum in fp64 in action order), in the form k_mz_init takes
+__global__ void k_mz_root_noise(int n_games, int n_actions, const long long *episode, const long long *steps, unsigned long long noise_seed,
+                                float alpha, double *eta) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_games) return;
+    const unsigned long long key = rzmze::move_key(noise_seed, 0ull, g, episode[g], steps[g]);
+    float gam[kMzMaxA];
+    double gsum = 0.0;
+#pragma unroll
+    for (int a = 0; a < kMzMaxA; ++a) {
+        gam[a] = a < n_actions ? mz_gamma(alpha, (uint32_t)(key >> 32) + 0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key) : 0.0f;
+        gsum += (double)gam[a];
+    }
+#pragma unroll
+    for (int a = 0; a < kMzMaxA; ++a)
+        if (a < n_actions) eta[(long long)g * n_actions + a] = (double)gam[a] / gsum;
+}
+
+template <typename Env>
+int mz_env_step_launch(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
+                       int64_t max_episode_steps, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream) {
+    k_mz_env_step<Env><<<dim3((unsigned)((n_envs + 127) / 128)), dim3(128), 0, (hipStream_t)stream>>>(
+        d_state, reinterpret_cast<long long *>(d_steps), reinterpret_cast<long long *>(d_episode), reinterpret_cast<const long long *>(d_actions),
+        n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated);
+    return rz_launched("k_mz_env_step");
+}
+
+template <typename Env>
+int mz_env_move_launch(rz_muzero *e, const MzEnvPlay &p, void *stream) {
+    static_assert(Env::kState <= RZ_MZE_MAX_STATE && Env::kObs <= RZ_MZE_MAX_OBS && Env::kActions <= RZ_MZE_MAX_ACTIONS, "environment limits");
+    if (e->cfg.n_actions != Env::kActions) return rz_fail(RZ_ERR_ARG, "the tree has %d actions, the environment %d", e->cfg.n_actions, Env::kActions);
+    k_mz_env_move<Env><<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, p);
+    return rz_launched("k_mz_env_move");
+}
+
+}  // namespace
+
+extern "C" {
+
+int rz_mz_env_step(int32_t kind, double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
+                   int64_t max_episode_steps, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream) {
+    if (!d_state || !d_steps || !d_episode || !d_obs || n_envs < 1) return rz_fail(RZ_ERR_ARG, "NULL pointer or n_envs < 1");
+    if (d_actions != nullptr && (!d_reward || !d_terminated || !d_truncated)) return rz_fail(RZ_ERR_ARG, "a step needs d_reward, d_terminated and d_truncated");
+    if (max_episode_steps < 1) return rz_fail(RZ_ERR_ARG, "max_episode_steps must be >= 1");
+    if (kind == RZ_MZ_ENV_CARTPOLE)
+        return mz_env_step_launch<EnvCartPole>(d_state, d_steps, d_episode, d_actions, n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated, stream);
+    if (kind == RZ_MZ_ENV_ACROBOT)
+        return mz_env_step_launch<rzmze::EnvAcrobot>(d_state, d_steps, d_episode, d_actions, n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated, stream);
+    return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
+}
+
+int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream) {
+    RZ_ENTER(mz_ready, e);
+    if (play == nullptr) return rz_fail(RZ_ERR_ARG, "play is NULL");
+    if (!play->d_state || !play->d_steps || !play->d_episode || !play->d_episode_start || !play->d_ring || !play->d_arena || !play->d_counters ||
+        !play->d_entries || !play->d_obs)
+        return rz_fail(RZ_ERR_ARG, "NULL environment / history pointer");
+    if (play->max_episode_steps < 1 || play->ring_steps < play->max_episode_steps || play->arena_rows < 1 || play->max_entries < (int64_t)e->cfg.n_games ||
+        play->step < 0)
+        return rz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (max_episode_steps), max_entries one entry per environment, step >= 0");
+    MzEnvPlay p = {};
+    p.state = play->d_state;
+    p.steps = reinterpret_cast<long long *>(play->d_steps);
+    p.episode = reinterpret_cast<long long *>(play->d_episode);
+    p.ep_start = reinterpret_cast<long long *>(play->d_episode_start);
+    p.env_seed = play->env_seed;
+    p.noise_seed = play->noise_seed;
+    p.inv_temperature = play->temperature > 0.0 ? 1.0 / play->temperature : 0.0;
+    p.max_episode_steps = play->max_episode_steps;
+    p.ring = play->d_ring;
+    p.hist = play->ring_steps;
+    p.t = play->step;
+    p.arena = play->d_arena;
+    p.arena_rows = play->arena_rows;
+    p.counters = reinterpret_cast<long long *>(play->d_counters);
+    p.entries = reinterpret_cast<long long *>(play->d_entries);
+    p.max_entries = play->max_entries;
+    p.obs = play->d_obs;
+    if (kind == RZ_MZ_ENV_CARTPOLE) return mz_env_move_launch<EnvCartPole>(e, p, stream);
+    if (kind == RZ_MZ_ENV_ACROBOT) return mz_env_move_launch<rzmze::EnvAcrobot>(e, p, stream);
+    return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
+}
+
+int rz_mz_root_noise(rz_muzero *e, const int64_t *d_episode, const int64_t *d_steps, uint64_t noise_seed, double dirichlet_alpha, double *d_eta,
+                     void *stream) {
+    RZ_ENTER(mz_ready, e);
+    if (!d_episode || !d_steps || !d_eta) return rz_fail(RZ_ERR_ARG, "NULL pointer");
+    if (e->cfg.n_actions > kMzMaxA) return rz_fail(RZ_ERR_ARG, "the root noise serves at most 8 actions");
+    // (the floor of mz_gamma: see rz_mz_play_cartpole)
+    if (!(dirichlet_alpha >= 0.1))
+        return rz_fail(RZ_ERR_ARG, "dirichlet_alpha must be >= 0.1: below it the root noise's float32 draws reach their 1e-30 floor too often");
+    k_mz_root_noise<<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->cfg.n_games, e->cfg.n_actions, reinterpret_cast<const long long *>(d_episode),
+                                                                        reinterpret_cast<const long long *>(d_steps), noise_seed, (float)dirichlet_alpha,
+                                                                        d_eta);
+    return rz_launched("k_mz_root_noise");
 }
 
 }  // extern "C"

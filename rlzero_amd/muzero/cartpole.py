@@ -46,6 +46,7 @@ class CartPoleBatch(object):
     n_actions = 2
     obs_dim = 4
     max_episode_steps = MAX_EPISODE_STEPS
+    kind = 'cartpole'   # (MuZeroTree.env_move: the environment's rules in the library)
 
     def __init__(self, n_envs, device='cuda:0', seed=0):
         import torch

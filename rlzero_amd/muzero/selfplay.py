@@ -1,4 +1,4 @@
-"""Batched MuZero self-play: many CartPole environments in lock-step on one GPU.
+"""Batched MuZero self-play: many environments (CartPole, Acrobot) in lock-step on one GPU.
 
 Per move (arXiv:1911.08265v2 appendix: ``play_game`` / ``run_mcts`` / ``select_action``):
   observation -> initial inference (representation + prediction) -> roots expanded with Dirichlet noise
@@ -9,7 +9,12 @@ Three routes (``MuZeroSelfPlay(fused=..., fused_moves=...)``): the step-by-step 
 small MLPs on PyTorch-ROCm, one hipGraph per simulation); the search of a move in ONE launch with the model evaluated
 inside the kernel (``rz_mz_search``); and whole MOVES in one launch -- initial inference, noise, search, action draw,
 CartPole step, episode history on the device (``rz_mz_play_cartpole``), the host reading finished episodes a launch
-behind the GPU.  The last is the default for a ``CartPoleBatch`` environment and a hidden size of 64."""
+behind the GPU.  The last is the default for a ``CartPoleBatch`` environment and a hidden size of 64.
+A fourth route, device moves (``device_moves``), lies between the last two and serves every environment the library knows the
+rules of (``env.kind``; today CartPole and Acrobot): per move the torch initial inference, then launches only -- root noise from
+the whole moves' stream, roots, ``rz_mz_search``, and ``rz_mz_env_move``: action draw, environment step, record, hand-over of
+finished episodes -- with no host synchronisation and no copy per move; the host reads finished episodes a chunk behind, through
+the whole moves' machinery.  It is the default for such an environment that is not a ``CartPoleBatch``."""
 import numpy as np
 
 
@@ -99,6 +104,24 @@ class EpisodeSeq(object):
         """Number of steps of every episode, int64 [len(self)]."""
         return np.concatenate([c[2] for c in self._chunks]) if self._chunks else np.zeros(0, dtype=np.int64)
 
+    def returns(self):
+        """Sum of the rewards of every episode, float64 [len(self)]: one pass over each chunk's reward column, in step order (an
+        episode's rows are one run of its chunk), no Episode formed."""
+        out = []
+        for fields, first_rows, lengths in self._chunks:
+            packed = len(fields) == 3 and isinstance(fields[1], int)
+            rewards = fields[0][:, fields[1] + 1] if packed else np.asarray(fields[2], dtype=np.float64)
+            if len(lengths) == 0:
+                continue
+            order = np.argsort(first_rows, kind='stable')
+            bounds = np.empty(2 * len(order), dtype=np.int64)   # start, end of every run in row order: reduceat sums [start, end) at the even places
+            bounds[0::2] = first_rows[order]
+            bounds[1::2] = bounds[0::2] + lengths[order]
+            sums = np.empty(len(order), dtype=np.float64)
+            sums[order] = np.add.reduceat(np.append(rewards, 0.0), bounds)[0::2]
+            out.append(sums)
+        return np.concatenate(out) if out else np.zeros(0, dtype=np.float64)
+
 
 class ReplayBuffer(object):
     """Finished episodes + the target construction of the MuZero learner (``make_target``): K unrolled
@@ -169,7 +192,7 @@ class MuZeroSelfPlay(object):
 
     def __init__(self, net, env, n_sims=50, discount=0.997, temperature=1.0, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, seed=0, pb_c_base=19652.0, pb_c_init=1.25, use_graph=True, fused=None,
-                 fused_moves=None, moves_per_launch=16, arena_rows=None):
+                 fused_moves=None, moves_per_launch=16, arena_rows=None, device_moves=None):
         """``fused``: run the whole search of a move in ONE kernel launch (csrc/rz_muzero.hip k_mz_search: the model is
         evaluated inside the kernel on the matrix pipe, 16 games per workgroup, trees in LDS); None = whenever the model
         fits it (hidden size 64, <= 8 actions).  Otherwise one hipGraph of ~15 launches per simulation (tree kernels +
@@ -180,7 +203,14 @@ class MuZeroSelfPlay(object):
         CartPoleBatch (the environment step is device code).  Its random draws (root noise, actions) come from the
         kernel's counter-based stream keyed (seed, environment, episode, step), not from the torch generator.
         ``arena_rows``: records the per-launch arena of finished episodes holds (None = twice what a launch plays + a few
-        long episodes; episodes that do not fit are read back from the device ring instead)."""
+        long episodes; episodes that do not fit are read back from the device ring instead).
+        ``device_moves``: the moves stay on the device for any environment of a kind the library knows (``env.kind``): per move the
+        torch initial inference, the root noise (k_mz_root_noise), ``init_roots``, the fused search and ``MuZeroTree.env_move``,
+        all enqueued on the current stream, ``moves_per_launch`` moves per set of buffers; finished episodes are read a chunk
+        behind, as with whole moves, and the draws come from the same counter-based stream.  None = whenever ``fused`` holds, the
+        environment states such a kind, whole moves do not apply and the environment is not a CartPoleBatch (whose default stays
+        whole moves; it takes this route with ``fused_moves=False, device_moves=True``).  True where it cannot run raises a
+        ``ValueError`` that names the reason."""
         import torch
         from .tree import MuZeroTree
         self.torch = torch
@@ -224,6 +254,27 @@ class MuZeroSelfPlay(object):
             self.tree.close()
             raise HipError('dirichlet_alpha must be >= 0.1: below it the root noise\'s float32 draws reach their 1e-30 floor too often '
                            '(root_dirichlet_alpha = %r; the move-by-move routes, fused_moves=False, take any alpha > 0)' % self.alpha)
+        from .. import _hip
+        why_not = None   # why device moves cannot run here
+        if not self.fused:
+            why_not = 'the fused search does not serve this model (it needs hidden size 64 and at most 8 actions, or fused=False was given)'
+        elif getattr(env, 'kind', None) not in _hip.MZ_ENV_KINDS:
+            why_not = 'the environment states no kind the library knows the rules of (env.kind = %r; known: %s)' % (
+                getattr(env, 'kind', None), ', '.join(sorted(_hip.MZ_ENV_KINDS)))
+        elif self.fused_moves:
+            why_not = 'whole moves are on (fused_moves): a move is either inside the search launch or behind it'
+        elif not self.alpha >= self.MIN_FUSED_ALPHA:
+            why_not = ('root_dirichlet_alpha = %r is below 0.1: the root noise is the whole moves\' float32 draw, which reaches its 1e-30 floor '
+                       'too often there (the host loop, device_moves=False, takes any alpha > 0)' % self.alpha)
+        elif net.obs_dim != env.obs_dim:
+            why_not = 'the network takes %d observations, the environment gives %d' % (net.obs_dim, env.obs_dim)
+        if device_moves is None:
+            self.device_moves = why_not is None and not isinstance(env, CartPoleBatch)
+        else:
+            self.device_moves = bool(device_moves)
+            if self.device_moves and why_not is not None:
+                self.tree.close()
+                raise ValueError('device_moves cannot run: ' + why_not)
         self.moves_per_launch = max(1, int(moves_per_launch))
         self._arena_rows = arena_rows
         self.noise_seed = int(seed)
@@ -238,6 +289,9 @@ class MuZeroSelfPlay(object):
             self.sim_step_label = ('k_mz_search with its MOVES stages (whole moves in one launch: initial inference, root noise, '
                                    '%d simulations -- select, recurrent inference on the matrix pipe, expand + backup -- action draw, '
                                    'CartPole step)' % self.n_sims)
+        elif self.device_moves:
+            self.sim_step_label = ('device moves: per move the torch initial inference, k_mz_root_noise, k_mz_init, k_mz_search (%d simulations in '
+                                   'one launch) and k_mz_env_move (action draw, environment step, record, hand-over)' % self.n_sims)
         elif self.fused:
             self.sim_step_label = ('k_mz_search (the whole %d-simulation search of a move in one launch: select, recurrent '
                                    'inference on the matrix pipe with register-resident weights, expand + backup)' % self.n_sims)
@@ -343,7 +397,7 @@ class MuZeroSelfPlay(object):
     def play_move(self, replay=None):
         """One move of every environment; returns the episodes that ended with it.  ``replay`` (a MuZeroDeviceReplay): they are
         handed to it as well (``collect``)."""
-        if self.fused_moves:
+        if self.fused_moves or self.device_moves:
             finished = self._collect_fused(1, replay)
             self.obs = self.env.observe()
             return finished
@@ -418,7 +472,7 @@ class MuZeroSelfPlay(object):
 
     # ------------------------------------------------------------------ whole moves on the device
     def _fused_state(self):
-        """Device-side history of the fused moves (MuZeroTree.play_cartpole) and the two sets of per-launch buffers."""
+        """Device-side history of the moves kept on the device (MuZeroTree.play_cartpole / env_move) and the sets of per-launch buffers."""
         if self._records is None:
             t = self.torch
             G, K = self.n_envs, self.moves_per_launch
@@ -436,6 +490,9 @@ class MuZeroSelfPlay(object):
             if self._arena_rows is not None:
                 rows = max(1, int(self._arena_rows))
             self._copy_stream = t.cuda.Stream(device=self.device)
+            if self.device_moves:   # the observation the next search starts from (env_move writes it) and the root noise
+                self._dev_obs = t.zeros((G, self.net.obs_dim), dtype=t.float32, **kw)
+                self._eta = t.zeros((G, self.n_actions), dtype=t.float64, **kw)
             self._records = []
             for _ in range(3):   # two launches in flight + the one the host reads
                 dev = (t.zeros(4, dtype=t.int64, **kw), t.zeros((n_entries, 4), dtype=t.int64, **kw),
@@ -463,7 +520,8 @@ class MuZeroSelfPlay(object):
         return (pieces[:, :, 0] + pieces[:, :, 1]) / 16.0
 
     def _launch_moves(self, n_moves, buf):
-        """Enqueue ``n_moves`` moves of every environment (one launch) and the copy of what ended during them."""
+        """Enqueue ``n_moves`` moves of every environment (whole moves: one launch; device moves: a few launches per move) and the
+        copy of what ended during them."""
         t = self.torch
         (counters, entries, arena), host, event = buf
         with t.no_grad():
@@ -472,8 +530,11 @@ class MuZeroSelfPlay(object):
             if self.search_events is not None:
                 ev = (t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True), n_moves)
                 ev[0].record()
-            self.tree.play_cartpole(self.hidden, self.n_sims, n_moves, self.env, self.noise_seed, self.noise_frac, self.alpha,
-                                    self.temperature, (self._ring, self._ep_start_dev), self._t, arena, counters, entries)
+            if self.fused_moves:
+                self.tree.play_cartpole(self.hidden, self.n_sims, n_moves, self.env, self.noise_seed, self.noise_frac, self.alpha,
+                                        self.temperature, (self._ring, self._ep_start_dev), self._t, arena, counters, entries)
+            else:
+                self._enqueue_device_moves(n_moves, arena, counters, entries)
             if ev is not None:
                 ev[1].record()
                 self.search_events.append(ev)
@@ -488,6 +549,25 @@ class MuZeroSelfPlay(object):
         self._t += n_moves
         self.sims_done += self.n_sims * self.n_envs * n_moves
         self.moves_done += self.n_envs * n_moves
+
+    def _enqueue_device_moves(self, n_moves, arena, counters, entries):
+        """``n_moves`` device moves on the current stream: nothing here waits for the GPU or copies to the host."""
+        t = self.torch
+        tree, net, env = self.tree, self.net, self.env
+        counters.zero_()
+        obs = self._dev_obs
+        obs.copy_(env.observe())   # (the states may have been set from outside since the last chunk)
+        for k in range(n_moves):
+            s0, logits, _ = net.initial_inference(obs)
+            probs = t.softmax(logits, dim=1).contiguous()
+            self.hidden[:, 0] = s0
+            noise = None
+            if self.noise_frac > 0:   # keyed (seed, environment, episode, step): the same draws however the run is batched
+                noise = tree.root_noise(env.episode_dev, env.steps, self.noise_seed, self.alpha, out=self._eta)
+            tree.init_roots(probs, noise, self.noise_frac)
+            tree.search_fused(self.hidden, self.n_sims)
+            tree.env_move(env, self.noise_seed, self.temperature, (self._ring, self._ep_start_dev), self._t + k, arena, counters,
+                          entries, obs)
 
     def _episodes_of_launch(self, buf, replay=None):
         """The finished episodes of a launch from its arena (host copy), ordered by (last move, environment).  ``replay``: the
@@ -548,7 +628,7 @@ class MuZeroSelfPlay(object):
         """``n_moves`` moves of every environment -> the finished episodes (an EpisodeSeq: len / iteration / indexing).
         ``replay`` (a MuZeroDeviceReplay): the finished episodes are also stored there, in the order of the returned sequence --
         whole moves hand them over on the device (``_episodes_of_launch``), the move-by-move routes through ``replay.add``."""
-        if self.fused_moves:
+        if self.fused_moves or self.device_moves:
             out = self._collect_fused(n_moves, replay)
             self.obs = self.env.observe()
         else:

@@ -87,6 +87,39 @@ class MuZeroTree(object):
         check(self.lib.rz_mz_play_cartpole(self.handle, _ptr(hidden), int(n_sims), int(n_moves), ctypes.byref(play), self.stream()),
               'rz_mz_play_cartpole')
 
+    def env_move(self, env, noise_seed, temperature, history, step, arena, counters, entries, obs_out):
+        """The move behind a finished search (``search_fused`` on the current stream) for the environment batch ``env`` of a kind
+        the library knows (``env.kind``: 'cartpole' | 'acrobot'), one launch (k_mz_env_move): the action from the root's visit
+        counts, the record into ``history`` = (ring float64 [G, ring_steps, D + 4 + A], episode_start int64 [G]) at ``step`` %
+        ring_steps, the environment step, the hand-over of a finished episode to ``arena`` / ``entries`` / ``counters`` (laid out
+        as ``play_cartpole``'s; NOT zeroed here: several moves share an arena) and the next observation to ``obs_out`` float32
+        [G, D]."""
+        ring, episode_start = history
+        kind = _hip.MZ_ENV_KINDS[env.kind]
+        t, G, row = self.torch, self.n_games, env.obs_dim + 4 + self.n_actions
+        if env.n_actions != self.n_actions or env.n_envs != G or ring.dim() != 3 or tuple(ring.shape[::2]) != (G, row) \
+                or tuple(obs_out.shape) != (G, env.obs_dim) or tuple(episode_start.shape) != (G, ) or arena.dim() != 2 or arena.shape[1] != row \
+                or entries.dim() != 2 or entries.shape[1] != 4 or counters.numel() < 4:
+            raise ValueError('env_move: the tree, the ring, the arena, the entries or the observations do not have the environment\'s shape')
+        for x, dtype in ((ring, t.float64), (arena, t.float64), (obs_out, t.float32), (episode_start, t.int64), (counters, t.int64), (entries, t.int64)):
+            if x.dtype != dtype or not x.is_contiguous() or x.device.type != 'cuda':
+                raise ValueError('env_move: contiguous float64 / float32 / int64 tensors on the device are expected')
+        play = _hip.RzMzEnvPlay(
+            env.state.data_ptr(), env.steps.data_ptr(), env.episode_dev.data_ptr(), episode_start.data_ptr(),
+            int(env.seed) & (2 ** 64 - 1), int(noise_seed) & (2 ** 64 - 1), float(temperature), int(env.max_episode_steps),
+            ring.data_ptr(), int(ring.shape[1]), 0, int(step), arena.data_ptr(), int(arena.shape[0]), counters.data_ptr(),
+            entries.data_ptr(), int(entries.shape[0]), obs_out.data_ptr())
+        check(self.lib.rz_mz_env_move(self.handle, kind, ctypes.byref(play), self.stream()), 'rz_mz_env_move')
+
+    def root_noise(self, episode, steps, noise_seed, alpha, out=None):
+        """The whole moves' normalised root noise for the moves (environment g, ``episode[g]``, ``steps[g]``) -- int64 [G] on the
+        device -- under ``noise_seed``: float64 [G, A] in the form ``init_roots`` takes (k_mz_root_noise).  alpha >= 0.1."""
+        if out is None:
+            out = self.torch.zeros((self.n_games, self.n_actions), dtype=self.torch.float64, device=self.device)
+        check(self.lib.rz_mz_root_noise(self.handle, _ptr(episode), _ptr(steps), int(noise_seed) & (2 ** 64 - 1), float(alpha), _ptr(out),
+                                        self.stream()), 'rz_mz_root_noise')
+        return out
+
     def set_search_shape(self, games_per_workgroup=0):
         """Games per workgroup of ``search_fused`` (<= 16; 0 = chosen from the number of games and CUs)."""
         check(self.lib.rz_mz_set_search_shape(self.handle, int(games_per_workgroup)), 'rz_mz_set_search_shape')

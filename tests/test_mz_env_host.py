@@ -1,0 +1,346 @@
+"""The environment rules of the MuZero device moves (rlzero_amd/csrc/rz_mz_env.h) on the CPU, against the scalar twin
+(tests/acrobot_twin.py) and the host restatement of the action draw (tests/device_streams.py).
+
+A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_learner_host.py builds its driver),
+-ffp-contract=off, fed binary inputs and compared with the twin:
+
+* ``acrobot_step`` / ``acrobot_observe`` over 4000 random states and actions and over crafted states -- an angle leaving [-pi, pi]
+  on each side, each velocity bound passed on each side, the height crossing 1.0, steps = max - 1 -- equal the twin BIT FOR BIT:
+  the same libm, the same order of operations, no contraction.
+* ``acrobot_reset`` equals ``rlzero_amd.muzero.acrobot_initial_states`` bit for bit and lies in [-0.1, 0.1).
+* The header's action draw (``move_weights`` / ``move_draw`` / ``move_key``) is ``device_streams.muzero_action``.
+* The same driver built with -fsanitize=address,undefined runs every input as a stand-alone program and writes the same bytes.
+* What the GPU test's bound of 1e-9 catches: the twin with k3 dropped, dt / 6 replaced by dt / 4, the -pi / 2 dropped from phi2, or
+  the velocity clamp removed is more than 1e-4 away from the true twin in at least one of the random states, each.
+* The trainer's parser takes ``--env acrobot`` and refuses an unknown environment."""
+import importlib.util
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import acrobot_twin as twin
+import device_streams as ds
+from rlzero_amd.muzero.acrobot import acrobot_initial_states
+from test_delta_gather_host import host_clangxx
+
+CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
+GPU_BOUND = 1e-9       # tests/test_mz_env_gpu.py
+CAUGHT_ABOVE = 1e-4    # five orders above it
+
+DRIVER = r'''
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "rz_mz_env.h"
+
+namespace re = rzmze;
+
+template <typename T>
+static std::vector<T> load(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { perror(path); exit(2); }
+    fseek(f, 0, SEEK_END);
+    const long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    std::vector<T> v((size_t)bytes / sizeof(T));
+    if (bytes && fread(v.data(), 1, (size_t)bytes, f) != (size_t)bytes) exit(2);
+    fclose(f);
+    return v;
+}
+template <typename T>
+static void store(const char *path, const std::vector<T> &v) {
+    FILE *f = fopen(path, "wb");
+    if (!f || fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) { perror(path); exit(2); }
+    fclose(f);
+}
+
+// step max_steps state.f64 [n][4] steps.i64 [n] actions.i64 [n] -> state.f64 [n][4], steps.i64 [n], reward.f64 [n], flags.i32 [n],
+//   obs before.f32 [n][6], obs after.f32 [n][6]      (through the trait, as the kernels go)
+static int step(char **a) {
+    const long long max_steps = atoll(a[0]);
+    const std::vector<double> state = load<double>(a[1]);
+    const std::vector<int64_t> steps = load<int64_t>(a[2]), actions = load<int64_t>(a[3]);
+    const size_t n = steps.size();
+    if (state.size() != 4 * n || actions.size() != n) return 4;
+    std::vector<double> out(4 * n), reward(n);
+    std::vector<int64_t> steps_out(n);
+    std::vector<int32_t> flags(n);
+    std::vector<float> before(6 * n), after(6 * n);
+    for (size_t i = 0; i < n; ++i) {
+        re::EnvAcrobot::State c;
+        re::EnvAcrobot::load(c, &state[4 * i], steps[i], 0);
+        re::EnvAcrobot::observe(c, &before[6 * i]);
+        flags[i] = re::EnvAcrobot::step(c, (int)actions[i], max_steps, &reward[i]);
+        re::EnvAcrobot::store(c, &out[4 * i]);
+        steps_out[i] = c.steps;
+        re::EnvAcrobot::observe(c, &after[6 * i]);
+    }
+    store(a[4], out);
+    store(a[5], steps_out);
+    store(a[6], reward);
+    store(a[7], flags);
+    store(a[8], before);
+    store(a[9], after);
+    return 0;
+}
+
+// reset seed env.i64 [n] episode.i64 [n] -> state.f64 [n][4], steps.i64 [n]
+static int reset(char **a) {
+    const uint64_t seed = strtoull(a[0], nullptr, 10);
+    const std::vector<int64_t> env = load<int64_t>(a[1]), episode = load<int64_t>(a[2]);
+    const size_t n = env.size();
+    if (episode.size() != n) return 4;
+    std::vector<double> out(4 * n);
+    std::vector<int64_t> steps(n);
+    for (size_t i = 0; i < n; ++i) {
+        re::MzAcrobot c = {9.0, 9.0, 9.0, 9.0, 77, episode[i]};
+        re::acrobot_reset(c, seed, (int)env[i]);
+        re::EnvAcrobot::store(c, &out[4 * i]);
+        steps[i] = c.steps;
+    }
+    store(a[3], out);
+    store(a[4], steps);
+    return 0;
+}
+
+// draw A seed inv_T visits.i32 [n][A] env.i64 [n] episode.i64 [n] steps.i64 [n] -> action.i32 [n]
+static int draw(char **a) {
+    const int A = atoi(a[0]);
+    const uint64_t seed = strtoull(a[1], nullptr, 10);
+    const double inv_t = atof(a[2]);
+    const std::vector<int32_t> visits = load<int32_t>(a[3]);
+    const std::vector<int64_t> env = load<int64_t>(a[4]), episode = load<int64_t>(a[5]), steps = load<int64_t>(a[6]);
+    const size_t n = env.size();
+    if (A < 1 || A > RZ_MZE_MAX_ACTIONS || visits.size() != n * (size_t)A || episode.size() != n || steps.size() != n) return 4;
+    std::vector<int32_t> action(n);
+    for (size_t i = 0; i < n; ++i) {
+        const std::vector<int> v(visits.begin() + i * A, visits.begin() + (i + 1) * A);
+        std::vector<double> w((size_t)A);
+        double total = 0.0;
+        int act = re::move_weights(v.data(), A, inv_t, w.data(), &total);
+        if (inv_t > 0.0) act = re::move_draw(w.data(), A, total, re::move_key(seed, 0xA5A5A5A5ull, (int)env[i], episode[i], steps[i]));
+        action[i] = act;
+    }
+    store(a[7], action);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    const std::string what = argc > 1 ? argv[1] : "";
+    if (what == "step" && argc == 12) return step(argv + 2);
+    if (what == "reset" && argc == 7) return reset(argv + 2);
+    if (what == "draw" && argc == 10) return draw(argv + 2);
+    return 4;
+}
+'''
+
+
+class Driver(object):
+    """The plain and the sanitized build of the driver; ``run`` gives the outputs of one call and holds both builds equal."""
+
+    def __init__(self, tmp):
+        cxx = host_clangxx()
+        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
+        self.tmp, self.exes, self.calls = tmp, [], 0
+        src = os.path.join(tmp, 'mz_env.cpp')
+        with open(src, 'w') as f:
+            f.write(DRIVER)
+        for name, extra in (('mz_env', []), ('mz_env_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
+            exe = os.path.join(tmp, name)
+            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra, '-I', CSRC, src,
+                            '-o', exe], check=True)
+            self.exes.append(exe)
+        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
+
+    def run(self, what, args, inputs, outputs):
+        self.calls += 1
+        paths = []
+        for i, arr in enumerate(inputs):
+            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
+            np.ascontiguousarray(arr).tofile(paths[-1])
+        got = []
+        for exe in self.exes:
+            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
+            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
+            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
+        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
+            assert plain.tobytes() == san.tobytes()
+        return got[0]
+
+
+@pytest.fixture(scope='module')
+def drv():
+    with tempfile.TemporaryDirectory() as tmp:
+        yield Driver(tmp)
+
+
+def random_cases(n=4000, seed=5):
+    """States over the whole range a step can leave behind (angles in [-pi, pi], velocities inside their bounds), any action, any
+    step count below the limit."""
+    rng = np.random.RandomState(seed)
+    state = np.stack([rng.uniform(-twin.PI, twin.PI, n), rng.uniform(-twin.PI, twin.PI, n), rng.uniform(-twin.MAX_VEL_1, twin.MAX_VEL_1, n),
+                      rng.uniform(-twin.MAX_VEL_2, twin.MAX_VEL_2, n)], axis=1)
+    return state, rng.randint(0, 499, size=n).astype(np.int64), rng.randint(0, 3, size=n).astype(np.int64)
+
+
+def twin_steps(state, steps, actions, max_steps, variant=None):
+    out, steps_out, reward, flags = np.zeros_like(state), np.zeros_like(steps), np.zeros(len(state)), np.zeros(len(state), dtype=np.int32)
+    for i in range(len(state)):
+        new, steps_out[i], reward[i], term, trunc = twin.step(tuple(state[i]), int(steps[i]), int(actions[i]), max_steps, variant)
+        out[i] = new
+        flags[i] = (1 if term else 0) | (2 if trunc else 0)
+    return out, steps_out, reward, flags
+
+
+def same_bits(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def driver_step(drv, state, steps, actions, max_steps):
+    out, steps_out, reward, flags, before, after = drv.run('step', [max_steps], [state, steps, actions],
+                                                           [np.float64, np.int64, np.float64, np.int32, np.float32, np.float32])
+    return out.reshape(-1, 4), steps_out, reward, flags, before.reshape(-1, 6), after.reshape(-1, 6)
+
+
+def check_against_twin(drv, state, steps, actions, max_steps):
+    out, steps_out, reward, flags, before, after = driver_step(drv, state, steps, actions, max_steps)
+    want, want_steps, want_reward, want_flags = twin_steps(state, steps, actions, max_steps)
+    assert same_bits(out, want), 'largest difference %g' % np.abs(out - want).max()
+    assert np.array_equal(steps_out, want_steps) and same_bits(reward, want_reward) and np.array_equal(flags, want_flags)
+    assert same_bits(before, np.stack([twin.observe(s) for s in state]))
+    assert same_bits(after, np.stack([twin.observe(s) for s in want]))
+    return want, want_flags, want_reward
+
+
+def test_header_is_the_twin_on_random_states(drv):
+    """4000 states x actions, both builds of the driver (the sanitized one ends clean): every bit of state, reward, flags and both
+    observations.  The sample holds terminal steps, wraps on both sides and clamps (asserted: the comparison saw them)."""
+    state, steps, actions = random_cases()
+    want, flags, reward = check_against_twin(drv, state, steps, actions, 500)
+    raw = np.array([twin.integrate(tuple(s), int(a)) for s, a in zip(state, actions)])
+    assert (flags & 1).any() and not (flags & 1).all() and (reward[(flags & 1) == 1] == 0.0).all() and (reward[(flags & 1) == 0] == -1.0).all()
+    assert (raw[:, :2] > twin.PI).any() and (raw[:, :2] < -twin.PI).any()
+    assert (np.abs(raw[:, 2]) > twin.MAX_VEL_1).any() and (np.abs(raw[:, 3]) > twin.MAX_VEL_2).any()
+    assert np.abs(want[:, :2]).max() <= twin.PI and np.abs(want[:, 2]).max() <= twin.MAX_VEL_1 and np.abs(want[:, 3]).max() <= twin.MAX_VEL_2
+
+
+def test_header_is_the_twin_on_crafted_states(drv):
+    """Every decision of a step met on purpose, and that the crafted states do meet them."""
+    cases = twin.crafted_states()
+    state = np.array([c[1] for c in cases], dtype=np.float64)
+    actions = np.array([c[2] for c in cases], dtype=np.int64)
+    steps = np.full(len(cases), 11, dtype=np.int64)   # steps = max - 1: every one of them is truncated at max = 12
+    want, flags, reward = check_against_twin(drv, state, steps, actions, 12)
+    assert (flags & 2).all()
+    _, flags500, _ = check_against_twin(drv, state, steps, actions, 500)
+    assert not (flags500 & 2).any() and np.array_equal(flags500 & 1, flags & 1)
+    raw = {c[0]: twin.integrate(c[1], c[2]) for c in cases}
+    assert raw['theta1 above pi'][0] > twin.PI and raw['theta1 below -pi'][0] < -twin.PI
+    assert raw['theta2 above pi'][1] > twin.PI and raw['theta2 below -pi'][1] < -twin.PI
+    assert raw['dtheta1 above its bound'][2] > twin.MAX_VEL_1 and raw['dtheta1 below minus its bound'][2] < -twin.MAX_VEL_1
+    assert raw['dtheta2 above its bound'][3] > twin.MAX_VEL_2 and raw['dtheta2 below minus its bound'][3] < -twin.MAX_VEL_2
+    names = [c[0] for c in cases]
+    i, j = names.index('height crosses 1'), names.index('height stays below 1')
+    assert twin.height(cases[i][1]) < 1.0 < twin.height(want[i]) and flags[i] & 1 and reward[i] == 0.0
+    assert twin.height(want[j]) < 1.0 and not flags[j] & 1 and reward[j] == -1.0
+    assert min(twin.decision_margin(c[1], c[2]) for c in cases) > 0.01   # (none of them sits on a decision: the GPU test reuses them)
+
+
+def test_a_huge_angle_does_not_spin(drv):
+    """The wrap is bounded (kAcroWraps turns): 1e300 - 2 pi is 1e300, and a state nobody should set still ends the step, with the
+    twin's bits."""
+    state = np.array([[1e300, 0.0, 0.0, 0.0], [0.0, -1e300, 0.0, 0.0]])
+    steps, actions = np.zeros(2, dtype=np.int64), np.ones(2, dtype=np.int64)
+    out, _, _, _, _, _ = driver_step(drv, state, steps, actions, 500)
+    want, _, _, _ = twin_steps(state, steps, actions, 500)
+    assert np.isfinite(want).all() and same_bits(out, want)
+
+
+def test_reset_is_the_restatement(drv):
+    rng = np.random.RandomState(2)
+    env = np.concatenate([np.arange(40), rng.randint(0, 2 ** 20, size=200)]).astype(np.int64)
+    episode = np.concatenate([np.zeros(40), rng.randint(0, 2 ** 40, size=200)]).astype(np.int64)
+    for seed in (0, 7, 2 ** 64 - 1):
+        got, steps = drv.run('reset', [seed], [env, episode], [np.float64, np.int64])
+        want = acrobot_initial_states(seed, env, episode)
+        assert same_bits(got.reshape(-1, 4), want) and not steps.any()
+        assert want.min() >= -0.1 and want.max() < 0.1
+        assert want.std() > 0.05 and abs(want.mean()) < 0.01   # (uniform over the range: 0.2 / sqrt(12) = 0.0577)
+    assert not same_bits(acrobot_initial_states(0, env, episode), acrobot_initial_states(1, env, episode))
+    assert same_bits(acrobot_initial_states(3, 5, 2), acrobot_initial_states(3, [5], [2]))
+
+
+@pytest.mark.parametrize('A,inv_t', [(3, 1.0), (3, 2.0), (3, 0.0), (2, 1.0), (8, 0.5)])
+def test_the_headers_action_draw_is_the_restatement(drv, A, inv_t):
+    """``move_weights`` / ``move_draw`` under ``move_key``: the bits tests/device_streams.py::muzero_action restates (rows whose
+    draw falls within 1e-12 of a boundary of the cumulative sums of a pow() are left out for 1 / T outside {0, 1}: none here)."""
+    rng = np.random.RandomState(A)
+    n = 3000
+    visits = rng.randint(0, 20, size=(n, A)).astype(np.int32)
+    visits[visits.sum(axis=1) == 0, 0] = 1
+    env, episode, steps = (rng.randint(0, hi, size=n).astype(np.int64) for hi in (8192, 1000, 500))
+    got, = drv.run('draw', [A, 11, inv_t], [visits, env, episode, steps], [np.int32])
+    want, gap = ds.muzero_action(11, env, episode, steps, visits, inv_t)
+    keep = gap > 1e-12
+    assert keep.all() and np.array_equal(got[keep], want[keep])
+    if inv_t > 0:
+        assert len(np.unique(got)) == A
+
+
+@pytest.mark.parametrize('variant', twin.VARIANTS)
+def test_the_gpu_bound_catches_rule_errors(variant):
+    """The GPU test allows 1e-9.  A twin with one rule broken is more than 1e-4 away -- five orders above that -- in at least one
+    of the random states (figures printed)."""
+    state, steps, actions = random_cases()
+    true, _, _, _ = twin_steps(state, steps, actions, 500)
+    broken, _, _, _ = twin_steps(state, steps, actions, 500, variant)
+    diff = np.abs(broken - true)
+    diff[:, :2] = np.minimum(diff[:, :2], np.abs(diff[:, :2] - 2.0 * twin.PI))   # (angles are compared on the circle)
+    worst = diff.max(axis=1)
+    print('%s: largest difference %.3g, %d of %d states above %g' % (variant, worst.max(), int((worst > CAUGHT_ABOVE).sum()), len(worst), CAUGHT_ABOVE))
+    assert (worst > CAUGHT_ABOVE).any() and CAUGHT_ABOVE >= 1e5 * GPU_BOUND
+
+
+def load_trainer():
+    spec = importlib.util.spec_from_file_location('train_muzero', os.path.join(REPO, 'tools', 'train_muzero.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_the_trainers_parser_takes_the_environment(capsys):
+    import inspect
+    mod = load_trainer()
+    ap = mod.build_parser()
+    assert ap.parse_args([]).env == 'cartpole'
+    assert ap.parse_args(['--env', 'acrobot']).env == 'acrobot'
+    with pytest.raises(SystemExit):
+        ap.parse_args(['--env', 'pendulum'])
+    assert 'pendulum' in capsys.readouterr().err
+    params = inspect.signature(mod.MuZeroPipeline.__init__).parameters
+    assert params['env'].default == 'cartpole' and params['max_episode_steps'].default is None
+    with pytest.raises(ValueError, match='pendulum'):
+        mod.MuZeroPipeline(env='pendulum')
+
+
+def test_device_moves_are_exported_and_bound():
+    """The module, the symbols and the ABI number of this feature (none of them exists before it)."""
+    from rlzero_amd import _hip, muzero
+    assert muzero.AcrobotBatch.n_actions == 3 and muzero.AcrobotBatch.obs_dim == 6 and muzero.AcrobotBatch.kind == 'acrobot'
+    assert muzero.CartPoleBatch.kind == 'cartpole'
+    assert {'rz_mz_env_step', 'rz_mz_env_move', 'rz_mz_root_noise'} <= set(_hip.exported_symbols())
+    assert _hip.ABI_VERSION >= 41 and _hip.MZ_ENV_KINDS == {'cartpole': 0, 'acrobot': 1}
+    header = open(os.path.join(REPO, 'include', 'rlzero_hip.h')).read()
+    assert '#define RZ_MZ_ENV_CARTPOLE 0' in header and '#define RZ_MZ_ENV_ACROBOT 1' in header
+    # rz_mz_env_play: 4 pointers, 2 uint64, double, int64, pointer, 2 int32, int64, pointer, int64, 2 pointers, int64, pointer
+    import ctypes
+    assert ctypes.sizeof(_hip.RzMzEnvPlay) == 136 and _hip.RzMzEnvPlay.step.offset == 80 and _hip.RzMzEnvPlay.d_obs.offset == 128
+    import inspect
+    from rlzero_amd.muzero.selfplay import MuZeroSelfPlay
+    assert inspect.signature(MuZeroSelfPlay.__init__).parameters['device_moves'].default is None
