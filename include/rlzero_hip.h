@@ -834,14 +834,16 @@ int rz_mz_load_representation(rz_muzero *e, const float *const *h_params, int32_
 int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_cartpole_play *play, void *stream);
 /* One step of n_envs CartPole-v1 environments (gymnasium classic_control/cartpole.py: Euler, tau 0.02, 500-step limit)
  * with auto-reset, in ONE launch: d_obs float32 [n_envs][4] = the observation AFTER the step (after the reset for a
- * finished environment), d_reward float32, d_terminated / d_truncated uint8. */
+ * finished environment), d_reward float32, d_terminated / d_truncated uint8.  It is rz_mz_env_step(RZ_MZ_ENV_CARTPOLE, ..., 500)
+ * with every pointer required (the same kernel, the same bits): an action outside 0..1 is clamped to it, as there (the kernel this
+ * entry point had of its own took every action other than 1 as 0; such input was never specified). */
 int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                      float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
 /* Moves kept on the device for any environment the library knows (ABI 41; rz_muzero.hip: k_mz_env_step, k_mz_env_move,
  * k_mz_root_noise; the rules: csrc/rz_mz_env.h).  kind: RZ_MZ_ENV_CARTPOLE (4 state doubles, 4 observations, 2 actions) or
  * RZ_MZ_ENV_ACROBOT (Acrobot-v1: 4 state doubles theta1, theta2, dtheta1, dtheta2; 6 observations cos / sin of the two angles and
  * the two velocities; 3 actions = torque -1, 0, +1; reward -1 per step, 0 for the step that reaches the goal).
- * rz_mz_env_step: rz_cartpole_step for either kind -- one step of n_envs environments with auto-reset in ONE launch, d_state
+ * rz_mz_env_step: one step of n_envs environments with auto-reset in ONE launch, d_state
  * float64 [n_envs][4], the time limit max_episode_steps an argument; d_obs float32 [n_envs][D] after the reset.  d_actions NULL:
  * no step, only d_obs is written (the observation of the current state; d_reward and the flags may be NULL then).
  * rz_mz_env_move: the move behind a finished search (rz_mz_search on the same stream), a thread per environment: the action from

@@ -15,9 +15,12 @@
 //   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search);
 //   * rz_mz_play_cartpole: whole MOVES in one launch -- initial inference, root noise, search, action draw, CartPole step,
 //     episode history on the device (k_mz_search with its MOVES stages).
-// Behind rz_mz_search, for any environment whose rules the library holds (rz_mz_env.h; at the end of this file): rz_mz_env_move --
-// action draw, environment step, record, hand-over of finished episodes, a thread per environment -- with rz_mz_root_noise and
-// rz_mz_env_step beside it.
+// Behind rz_mz_search, for any environment whose rules the library holds (at the end of this file): rz_mz_env_move -- action draw,
+// environment step, record, hand-over of finished episodes, a thread per environment -- with rz_mz_root_noise and rz_mz_env_step
+// (rz_cartpole_step is its CartPole instantiation) beside it.
+// The RULES of a move -- CartPole and Acrobot, splitmix64 and the keys built from it, the action draw, the layout of a record -- are
+// plain C++ in rz_mz_env.h, tested on the CPU; the whole moves and the moves behind a search call the same functions, and share
+// mz_root_gammas (the root noise's draws) and mz_claim_episode (the hand-over's counters and entry) below.
 // A MuZero tree is tiny (n_sims + 1 expanded nodes, A children each) and its walk is a short chain of dependent steps,
 // so the parallelism is across the thousands of games.  Tree layout in HBM (per game g, node slot i, slot index
 // g * cap + i): one 32-byte record per node: N int32, first_child int32 (-1 = not expanded; the A children of a node are
@@ -201,83 +204,6 @@ __global__ void k_mz_expand_backup(MzDev E, const float *reward, const float *pr
     mz_expand_backup_one(E, g, reward[g], probs + (long long)g * E.n_actions, value[g]);
 }
 
-// ------------------------------------------------------------------ CartPole-v1 on the device
-// Gymnasium's CartPoleEnv (classic_control/cartpole.py v0.29: Euler integrator, tau 0.02 s, force 10 N, episode ends at
-// |x| > 2.4 or |theta| > 12 degrees, reward 1 per step) with CartPole-v1's 500-step limit and auto-reset -- the device
-// twin of rlzero_amd/muzero/cartpole.py: same constants, same order of operations (fp64, one rounding per operation),
-// initial states from the same counter-based stream keyed (seed, environment, episode).
-__device__ __forceinline__ unsigned long long mz_splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-struct MzCartPole {
-    double x, x_dot, theta, theta_dot;
-    long long steps, episode;
-};
-
-__device__ __forceinline__ void cartpole_reset(MzCartPole &c, unsigned long long seed, int env) {
-    const unsigned long long key = mz_splitmix64(mz_splitmix64(seed ^ ((unsigned long long)env << 24)) ^ (unsigned long long)c.episode);
-    double v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double u = (double)(mz_splitmix64(key ^ (unsigned long long)(j + 1)) >> 11) / 9007199254740992.0;
-        v[j] = -0.05 + 0.1 * u;
-    }
-    c.x = v[0];
-    c.x_dot = v[1];
-    c.theta = v[2];
-    c.theta_dot = v[3];
-    c.steps = 0;
-}
-
-// one step; -> bit 0 terminated, bit 1 truncated (the state is the terminal one: the caller resets)
-__device__ __forceinline__ int cartpole_step(MzCartPole &c, int action) {
-    const double gravity = 9.8, masspole = 0.1, total_mass = 0.1 + 1.0, length = 0.5, polemass_length = 0.1 * 0.5, tau = 0.02;
-    const double theta_threshold = 12 * 2 * 3.141592653589793 / 360, x_threshold = 2.4;
-    const double force = action == 1 ? 10.0 : -10.0;
-    const double costheta = cos(c.theta), sintheta = sin(c.theta);
-    const double temp = (force + polemass_length * (c.theta_dot * c.theta_dot) * sintheta) / total_mass;
-    const double thetaacc = (gravity * sintheta - costheta * temp) / (length * (4.0 / 3.0 - masspole * (costheta * costheta) / total_mass));
-    const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
-    c.x = c.x + tau * c.x_dot;
-    c.x_dot = c.x_dot + tau * xacc;
-    c.theta = c.theta + tau * c.theta_dot;
-    c.theta_dot = c.theta_dot + tau * thetaacc;
-    c.steps += 1;
-    const bool terminated = c.x < -x_threshold || c.x > x_threshold || c.theta < -theta_threshold || c.theta > theta_threshold;
-    const bool truncated = c.steps >= 500;
-    return (terminated ? 1 : 0) | (truncated ? 2 : 0);
-}
-
-__global__ void k_cartpole_step(double *state, long long *steps, long long *episode, const long long *actions, int n_envs,
-                                unsigned long long seed, float *obs, float *reward, uint8_t *terminated, uint8_t *truncated) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_envs) return;
-    MzCartPole c = {state[4 * g], state[4 * g + 1], state[4 * g + 2], state[4 * g + 3], steps[g], episode[g]};
-    const int done = cartpole_step(c, (int)actions[g]);
-    if (done) {
-        c.episode += 1;
-        cartpole_reset(c, seed, g);
-    }
-    state[4 * g] = c.x;
-    state[4 * g + 1] = c.x_dot;
-    state[4 * g + 2] = c.theta;
-    state[4 * g + 3] = c.theta_dot;
-    steps[g] = c.steps;
-    episode[g] = c.episode;
-    obs[4 * g] = (float)c.x;
-    obs[4 * g + 1] = (float)c.x_dot;
-    obs[4 * g + 2] = (float)c.theta;
-    obs[4 * g + 3] = (float)c.theta_dot;
-    reward[g] = 1.0f;
-    terminated[g] = (uint8_t)(done & 1);
-    truncated[g] = (uint8_t)((done >> 1) & 1);
-}
-
 // One Gamma(alpha, 1) sample for the root's Dirichlet noise (add_exploration_noise) from a counter-based stream:
 // Marsaglia-Tsang (boosted by U^(1/alpha) below shape 1).  Noise, not parity: hardware transcendentals, 24-bit uniforms
 // (the scheme of gamma03 in rz_engine.hip with the shape as an argument).
@@ -314,6 +240,40 @@ __device__ __forceinline__ float mz_gamma(float alpha, uint32_t key) {
         g = g * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(ub) * (1.0f / alpha));  // ub^(1/alpha)
     }
     return fmaxf(g, 1e-30f);
+}
+
+// the gamma draws of a move's root noise under its key (rzmze::move_key, salt 0; 0 past the last action) -> their sum, in fp64 in
+// action order
+template <int MAXA>
+__device__ __forceinline__ double mz_root_gammas(float alpha, uint64_t key, int A, float (&gam)[MAXA]) {
+    double gsum = 0.0;
+#pragma unroll
+    for (int a = 0; a < MAXA; ++a) {
+        gam[a] = a < A ? mz_gamma(alpha, rzmze::noise_key(key, a)) : 0.0f;
+        gsum += (double)gam[a];
+    }
+    return gsum;
+}
+
+// the hand-over of an episode of `len` records that ended before step `end`: its run of arena rows (-1 and a count in counters[2]
+// where they do not fit), its entry (environment, end step, length, first arena row) -> the first arena row.  GUARDED: counters that
+// are not counts any more claim nothing
+template <bool GUARDED>
+__device__ __forceinline__ long long mz_claim_episode(long long *counters, long long arena_rows, long long *entries, long long max_entries, int g,
+                                                      long long end, long long len) {
+    long long off = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(counters), (unsigned long long)len);
+    if ((GUARDED && off < 0) || off + len > arena_rows) {
+        off = -1;
+        atomicAdd(reinterpret_cast<unsigned long long *>(counters + 2), 1ull);
+    }
+    const long long e = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(counters + 1), 1ull);
+    if ((!GUARDED || e >= 0) && e < max_entries) {
+        entries[4 * e + 0] = g;
+        entries[4 * e + 1] = end;
+        entries[4 * e + 2] = len;
+        entries[4 * e + 3] = off;
+    }
+    return off;
 }
 
 // ------------------------------------------------------------------ the whole search in ONE launch
@@ -830,11 +790,11 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     int top = 0, depth = 0;
     double lo = 0.0, hi = 0.0;
     double *env_g = ENV + 8 * ge;
-    auto env_load = [&](MzCartPole &c, long long &ep0) {
-        c = MzCartPole{env_g[0], env_g[1], env_g[2], env_g[3], __double_as_longlong(env_g[4]), __double_as_longlong(env_g[5])};
+    auto env_load = [&](rzmze::MzCartPole &c, long long &ep0) {
+        c = rzmze::MzCartPole{env_g[0], env_g[1], env_g[2], env_g[3], __double_as_longlong(env_g[4]), __double_as_longlong(env_g[5])};
         ep0 = __double_as_longlong(env_g[6]);
     };
-    auto env_store = [&](const MzCartPole &c, long long ep0) {   // (the four lanes of a quad write the same values)
+    auto env_store = [&](const rzmze::MzCartPole &c, long long ep0) {   // (the four lanes of a quad write the same values)
         env_g[0] = c.x;
         env_g[1] = c.x_dot;
         env_g[2] = c.theta;
@@ -845,7 +805,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     };
     if (mine) {
         if (MOVES) {
-            env_store(MzCartPole{P.state[4 * g], P.state[4 * g + 1], P.state[4 * g + 2], P.state[4 * g + 3], P.steps[g], P.episode[g]},
+            env_store(rzmze::MzCartPole{P.state[4 * g], P.state[4 * g + 1], P.state[4 * g + 2], P.state[4 * g + 3], P.steps[g], P.episode[g]},
                       P.ep_start[g]);
         } else {
             top = E.top[g];
@@ -1022,24 +982,19 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                 finish_prediction(value, probs);
                 if (mine) {
                     // expand_node(root) + add_exploration_noise: prior * (1 - frac) + noise * frac (k_mz_init), fresh MinMaxStats
-                    // (`gs`: the game's share of the keys, opaque per move -- hoisted out of the move loop the three hashes of it lived
+                    // (`ns`: the seed of the keys, opaque per move -- hoisted out of the move loop the three hashes of seed and game lived
                     // in registers for the whole launch, and three of them in scratch memory)
-                    unsigned long long gs = (unsigned long long)g << 24;
-                    asm volatile("" : "+v"(gs));
-                    const unsigned long long key = mz_splitmix64(mz_splitmix64(mz_splitmix64(P.noise_seed ^ gs) ^
-                                                                                (unsigned long long)__double_as_longlong(env_g[5])) ^
-                                                                 (unsigned long long)__double_as_longlong(env_g[4]));
+                    unsigned long long ns = P.noise_seed;
+                    asm volatile("" : "+v"(ns));
+                    const uint64_t key = rzmze::move_key(ns, 0ull, g, __double_as_longlong(env_g[5]), __double_as_longlong(env_g[4]));
                     // Both distributions are normalised in fp64 here, once per move: the float32 softmax and a float32 sum of the
                     // gamma draws each add up to 1 only within a float32 ulp (6e-8), and the pseudocode's root priors are a
                     // distribution (they sum to 1 within 1e-12: tests/test_muzero_moves_tree.py)
                     float gam[MAXA];
-                    double gsum = 0.0, psum = 0.0;
+                    const double gsum = mz_root_gammas(P.alpha, key, A, gam);
+                    double psum = 0.0;
 #pragma unroll
-                    for (int a = 0; a < MAXA; ++a) {
-                        gam[a] = a < A ? mz_gamma(P.alpha, (uint32_t)(key >> 32) + 0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key) : 0.0f;
-                        gsum += (double)gam[a];
-                        psum += (double)probs[a];   // (0 past the last action: finish_prediction)
-                    }
+                    for (int a = 0; a < MAXA; ++a) psum += (double)probs[a];   // (0 past the last action: finish_prediction)
                     if (TREE_LDS) {
                         hot[0] = MzHot{0, 1, 0.0, 0.0, 0.0};
                         rew[0] = 0.0f;
@@ -1207,87 +1162,49 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     }
         if (MOVES && mine) {
             // ---- the move: action ~ visits ^ (1 / T) (select_action), record for the host, environment step
-            MzCartPole env;
+            rzmze::MzCartPole env;
             long long ep_start;
             env_load(env, ep_start);
-            double wgt[MAXA], total = 0.0, best_w = -1.0;
-            int visits[MAXA], arg = 0;
+            double wgt[MAXA], total;
+            int visits[MAXA];
 #pragma unroll
-            for (int a = 0; a < MAXA; ++a) {
-                visits[a] = a < A ? (TREE_LDS ? hot[1 + a].N : nodes[1 + a].N) : 0;
-                wgt[a] = 0.0;
-                if (a < A) {
-                    wgt[a] = P.inv_temperature == 1.0 || P.inv_temperature <= 0.0 ? (double)visits[a] : pow((double)visits[a], P.inv_temperature);
-                    total += wgt[a];
-                    if (wgt[a] > best_w) {
-                        best_w = wgt[a];
-                        arg = a;
-                    }
-                }
-            }
-            int action = arg;
+            for (int a = 0; a < MAXA; ++a) visits[a] = a < A ? (TREE_LDS ? hot[1 + a].N : nodes[1 + a].N) : 0;
+            int action = rzmze::move_weights(visits, A, P.inv_temperature, wgt, &total);
             if (P.inv_temperature > 0.0) {
-                unsigned long long gs = (unsigned long long)g << 24;
-                asm volatile("" : "+v"(gs));
-                const unsigned long long key = mz_splitmix64(mz_splitmix64(mz_splitmix64(P.noise_seed ^ 0xA5A5A5A5ull ^ gs) ^
-                                                                            (unsigned long long)env.episode) ^ (unsigned long long)env.steps);
-                const double target = ((double)(key >> 11) / 9007199254740992.0) * total;
-                double cum = 0.0;
-                bool found = false;
-                action = A - 1;
-#pragma unroll
-                for (int a = 0; a < MAXA; ++a) {
-                    if (a < A) {
-                        cum += wgt[a];
-                        if (!found && cum > target) {
-                            action = a;
-                            found = true;
-                        }
-                    }
-                }
+                unsigned long long ns = P.noise_seed;
+                asm volatile("" : "+v"(ns));   // (as at the root noise)
+                action = rzmze::move_draw(wgt, A, total, rzmze::move_key(ns, 0xA5A5A5A5ull, g, env.episode, env.steps));
             }
             const double root_sum = TREE_LDS ? hot[0].value_sum : nodes[0].value_sum;
             const int root_n = TREE_LDS ? hot[0].N : nodes[0].N;
             const long long t = P.t0 + move;
             double *ring_g = P.ring + (long long)g * P.hist * P.row;
             double *rec = ring_g + (t % P.hist) * P.row;
-            double last[8 + MAXA];
+            const rzmze::RecordLayout R = rzmze::record_layout(rzmze::EnvCartPole::kObs, A);
+            double last[6 + MAXA];
             last[0] = (double)(float)env.x;   // the observation the search started from
             last[1] = (double)(float)env.x_dot;
             last[2] = (double)(float)env.theta;
             last[3] = (double)(float)env.theta_dot;
-            last[4] = (double)action;
-            last[5] = 1.0;
+            last[R.action] = (double)action;
+            last[R.reward] = 1.0;
 #pragma unroll
-            for (int a = 0; a < MAXA; ++a) last[6 + a] = (double)visits[a];
+            for (int a = 0; a < MAXA; ++a) last[R.visits + a] = (double)visits[a];
             const double root_value = root_sum / (double)(root_n > 1 ? root_n : 1);
-            const int done = cartpole_step(env, action);
+            const int done = rzmze::cartpole_step(env, action, 500);
             if (lead) {
 #pragma unroll
                 for (int c = 0; c < 6 + MAXA; ++c)
-                    if (c < 6 + A) rec[c] = last[c];
-                rec[6 + A] = root_value;
-                rec[7 + A] = done ? 1.0 : 0.0;
+                    if (c < R.root_value) rec[c] = last[c];
+                rec[R.root_value] = root_value;
+                rec[R.done] = done ? 1.0 : 0.0;
             }
             if (done) {
                 // the episode's records as one run in the arena: the quad copies the earlier moves from the ring, the
                 // lead adds this move's from its registers
                 const long long len = t + 1 - ep_start;
                 long long off = -1;
-                if (lead) {
-                    off = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters), (unsigned long long)len);
-                    if (off + len > P.arena_rows) {
-                        off = -1;
-                        atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 2), 1ull);
-                    }
-                    const long long e = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 1), 1ull);
-                    if (e < P.max_entries) {
-                        P.entries[4 * e + 0] = g;
-                        P.entries[4 * e + 1] = t + 1;
-                        P.entries[4 * e + 2] = len;
-                        P.entries[4 * e + 3] = off;
-                    }
-                }
+                if (lead) off = mz_claim_episode<false>(P.counters, P.arena_rows, P.entries, P.max_entries, g, t + 1, len);
                 off = __shfl(off, l & ~3);
                 if (off >= 0) {
                     for (long long j = ca; j < len - 1; j += 4) {
@@ -1300,16 +1217,16 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                         double *dst = P.arena + (off + len - 1) * P.row;
 #pragma unroll
                         for (int c = 0; c < 6 + MAXA; ++c)
-                            if (c < 6 + A) dst[c] = last[c];
-                        dst[6 + A] = root_value;
-                        dst[7 + A] = 1.0;
+                            if (c < R.root_value) dst[c] = last[c];
+                        dst[R.root_value] = root_value;
+                        dst[R.done] = 1.0;
                     }
                 }
                 ep_start = t + 1;
                 env.episode += 1;
                 int g_reset = g;
-                asm volatile("" : "+v"(g_reset));   // (as `gs` above: the reset's key is formed when an episode ends)
-                cartpole_reset(env, P.env_seed, g_reset);
+                asm volatile("" : "+v"(g_reset));   // (as `ns` above: the reset's key is formed when an episode ends)
+                rzmze::cartpole_reset(env, P.env_seed, g_reset);
             }
             OBS[0 * kMzTile + ge] = (float)env.x;
             OBS[1 * kMzTile + ge] = (float)env.x_dot;
@@ -1733,16 +1650,6 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
     return mz_launch_search(e, d_hidden, n_sims, T, &p, stream);
 }
 
-int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
-                     float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream) {
-    if (!d_state || !d_steps || !d_episode || !d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated || n_envs < 1)
-        return rz_fail(RZ_ERR_ARG, "NULL pointer or n_envs < 1");
-    k_cartpole_step<<<dim3((unsigned)((n_envs + 127) / 128)), dim3(128), 0, (hipStream_t)stream>>>(
-        d_state, reinterpret_cast<long long *>(d_steps), reinterpret_cast<long long *>(d_episode),
-        reinterpret_cast<const long long *>(d_actions), n_envs, seed, d_obs, d_reward, d_terminated, d_truncated);
-    return rz_launched("k_cartpole_step");
-}
-
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
     if (games_per_workgroup < 0 || games_per_workgroup > kMzMaxGpw) return rz_fail(RZ_ERR_ARG, "games_per_workgroup must be 0 (auto) .. 16");
@@ -1796,36 +1703,11 @@ int rz_mz_error_flags(rz_muzero *e, int32_t *flags) {
 
 // ------------------------------------------------------------------ moves kept on the device, generic over the environment
 // The layer between a finished search and the replay -- action draw, environment step, record, hand-over of finished episodes --
-// as launches of their own behind rz_mz_search (k_mz_search is not involved: its MOVES stages stay CartPole's).  An environment is
-// a trait (rz_mz_env.h); k_mz_env_step and k_mz_env_move are instantiated once per kind.
+// as launches of their own behind rz_mz_search (k_mz_search is not involved: its MOVES stages stay CartPole's, under the same rules).
+// An environment is a trait (rz_mz_env.h); k_mz_env_step and k_mz_env_move are instantiated once per kind.
 namespace {
 
-// CartPole's trait: the functions above, called (the step's own 500-step limit is replaced by the caller's)
-struct EnvCartPole {
-    typedef MzCartPole State;
-    static constexpr int kState = 4, kObs = 4, kActions = 2;
-    __device__ __forceinline__ static void load(State &c, const double *s, long long steps, long long episode) { c = State{s[0], s[1], s[2], s[3], steps, episode}; }
-    __device__ __forceinline__ static void store(const State &c, double *s) {
-        s[0] = c.x;
-        s[1] = c.x_dot;
-        s[2] = c.theta;
-        s[3] = c.theta_dot;
-    }
-    __device__ __forceinline__ static void reset(State &c, uint64_t seed, int env) { cartpole_reset(c, seed, env); }
-    __device__ __forceinline__ static int step(State &c, int action, long long max_episode_steps, double *reward) {
-        const int bits = cartpole_step(c, action);
-        *reward = 1.0;
-        return (bits & 1 ? RZ_MZE_TERMINATED : 0) | (c.steps >= max_episode_steps ? RZ_MZE_TRUNCATED : 0);
-    }
-    __device__ __forceinline__ static void observe(const State &c, float *obs) {
-        obs[0] = (float)c.x;
-        obs[1] = (float)c.x_dot;
-        obs[2] = (float)c.theta;
-        obs[3] = (float)c.theta_dot;
-    }
-};
-
-// one step of every environment with auto-reset (k_cartpole_step for any kind); actions == nullptr: no step, the observation only
+// one step of every environment with auto-reset; actions == nullptr: no step, the observation only
 template <typename Env>
 __global__ __launch_bounds__(128) void k_mz_env_step(double *state, long long *steps, long long *episode, const long long *actions, int n_envs,
                               unsigned long long seed, long long max_episode_steps, float *obs, float *reward, uint8_t *terminated,
@@ -1876,7 +1758,9 @@ struct MzEnvPlay {      // rz_mz_env_move: MzPlay's history (same layout of ring
 // environment.  Plain stores and the two counters' atomics; a finished episode's earlier records were written by earlier launches.
 template <typename Env>
 __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
-    constexpr int D = Env::kObs, A = Env::kActions, ROW = D + 4 + A;
+    constexpr int D = Env::kObs, A = Env::kActions;
+    constexpr rzmze::RecordLayout R = rzmze::record_layout(D, A);
+    constexpr int ROW = R.row;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= E.n_games) return;
     const MzNode *nodes = E.nodes + (long long)g * E.cap;
@@ -1903,12 +1787,12 @@ __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
     }
     double reward = 0.0;
     const int done = Env::step(env, action, P.max_episode_steps, &reward);
-    rec[D] = (double)action;
-    rec[D + 1] = reward;
+    rec[R.action] = (double)action;
+    rec[R.reward] = reward;
 #pragma unroll
-    for (int a = 0; a < A; ++a) rec[D + 2 + a] = (double)visits[a];
-    rec[D + 2 + A] = root.value_sum / (double)(root.N > 1 ? root.N : 1);
-    rec[D + 3 + A] = done ? 1.0 : 0.0;
+    for (int a = 0; a < A; ++a) rec[R.visits + a] = (double)visits[a];
+    rec[R.root_value] = root.value_sum / (double)(root.N > 1 ? root.N : 1);
+    rec[R.done] = done ? 1.0 : 0.0;
     double *ring_g = P.ring + (long long)g * P.hist * ROW;
     {
         double *dst = ring_g + (P.t % P.hist) * ROW;
@@ -1920,18 +1804,7 @@ __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
         long long len = P.t + 1 - ep_start;
         const long long most = P.t + 1 < P.hist ? P.t + 1 : P.hist;
         len = len < 1 ? 1 : (len > most ? most : len);   // (an episode longer than the ring cannot be: rz_mz_env_move sizes it)
-        long long off = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters), (unsigned long long)len);
-        if (off < 0 || off + len > P.arena_rows) {
-            off = -1;
-            atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 2), 1ull);
-        }
-        const long long e = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.counters + 1), 1ull);
-        if (e >= 0 && e < P.max_entries) {
-            P.entries[4 * e + 0] = g;
-            P.entries[4 * e + 1] = P.t + 1;
-            P.entries[4 * e + 2] = len;
-            P.entries[4 * e + 3] = off;
-        }
+        const long long off = mz_claim_episode<true>(P.counters, P.arena_rows, P.entries, P.max_entries, g, P.t + 1, len);
         if (off >= 0) {
             for (long long j = 0; j < len - 1; ++j) {
                 const double *src = ring_g + ((P.t + 1 - len + j) % P.hist) * ROW;
@@ -1958,20 +1831,14 @@ __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
     for (int i = 0; i < D; ++i) P.obs[(long long)D * g + i] = o[i];
 }
 
-// the normalised root noise of a move, eta [G][A], under the whole moves' key (noise_seed, g, episode, steps): the draws of
-// k_mz_search's MOVES stage (mz_gamma per action, the sum in fp64 in action order), in the form k_mz_init takes
+// the normalised root noise of a move, eta [G][A], under the whole moves' key (noise_seed, g, episode, steps): mz_root_gammas as
+// k_mz_search's MOVES stage calls it, in the form k_mz_init takes
 __global__ void k_mz_root_noise(int n_games, int n_actions, const long long *episode, const long long *steps, unsigned long long noise_seed,
                                 float alpha, double *eta) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_games) return;
-    const unsigned long long key = rzmze::move_key(noise_seed, 0ull, g, episode[g], steps[g]);
     float gam[kMzMaxA];
-    double gsum = 0.0;
-#pragma unroll
-    for (int a = 0; a < kMzMaxA; ++a) {
-        gam[a] = a < n_actions ? mz_gamma(alpha, (uint32_t)(key >> 32) + 0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key) : 0.0f;
-        gsum += (double)gam[a];
-    }
+    const double gsum = mz_root_gammas(alpha, rzmze::move_key(noise_seed, 0ull, g, episode[g], steps[g]), n_actions, gam);
 #pragma unroll
     for (int a = 0; a < kMzMaxA; ++a)
         if (a < n_actions) eta[(long long)g * n_actions + a] = (double)gam[a] / gsum;
@@ -2004,10 +1871,17 @@ int rz_mz_env_step(int32_t kind, double *d_state, int64_t *d_steps, int64_t *d_e
     if (d_actions != nullptr && (!d_reward || !d_terminated || !d_truncated)) return rz_fail(RZ_ERR_ARG, "a step needs d_reward, d_terminated and d_truncated");
     if (max_episode_steps < 1) return rz_fail(RZ_ERR_ARG, "max_episode_steps must be >= 1");
     if (kind == RZ_MZ_ENV_CARTPOLE)
-        return mz_env_step_launch<EnvCartPole>(d_state, d_steps, d_episode, d_actions, n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated, stream);
+        return mz_env_step_launch<rzmze::EnvCartPole>(d_state, d_steps, d_episode, d_actions, n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated, stream);
     if (kind == RZ_MZ_ENV_ACROBOT)
         return mz_env_step_launch<rzmze::EnvAcrobot>(d_state, d_steps, d_episode, d_actions, n_envs, seed, max_episode_steps, d_obs, d_reward, d_terminated, d_truncated, stream);
     return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
+}
+
+int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
+                     float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream) {
+    if (!d_state || !d_steps || !d_episode || !d_actions || !d_obs || !d_reward || !d_terminated || !d_truncated || n_envs < 1)
+        return rz_fail(RZ_ERR_ARG, "NULL pointer or n_envs < 1");
+    return mz_env_step_launch<rzmze::EnvCartPole>(d_state, d_steps, d_episode, d_actions, n_envs, seed, 500, d_obs, d_reward, d_terminated, d_truncated, stream);
 }
 
 int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream) {
@@ -2037,7 +1911,7 @@ int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void 
     p.entries = reinterpret_cast<long long *>(play->d_entries);
     p.max_entries = play->max_entries;
     p.obs = play->d_obs;
-    if (kind == RZ_MZ_ENV_CARTPOLE) return mz_env_move_launch<EnvCartPole>(e, p, stream);
+    if (kind == RZ_MZ_ENV_CARTPOLE) return mz_env_move_launch<rzmze::EnvCartPole>(e, p, stream);
     if (kind == RZ_MZ_ENV_ACROBOT) return mz_env_move_launch<rzmze::EnvAcrobot>(e, p, stream);
     return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
 }

@@ -1,13 +1,16 @@
-// rz_mz_env.h -- the rules of the MuZero environments that are not CartPole (rz_muzero.hip: k_mz_env_step, k_mz_env_move;
-// include/rlzero_hip.h: rz_mz_env_step, rz_mz_env_move): everything about them that is neither a kernel launch nor a memory
-// access.  Plain C++, no HIP include, so that the CPU can run it against the scalar restatement tests/acrobot_twin.py
+// rz_mz_env.h -- the rules of the MuZero environments and of the moves kept on the device (rz_muzero.hip: k_mz_search's MOVES stages,
+// k_mz_env_step, k_mz_env_move, k_mz_root_noise; include/rlzero_hip.h: rz_mz_play_cartpole, rz_cartpole_step, rz_mz_env_step,
+// rz_mz_env_move, rz_mz_root_noise): everything about them that is neither a kernel launch nor a memory access.  Plain C++, no HIP
+// include, so that the CPU can run it against the scalar restatements of CartPole, Acrobot, the keys and the draw
 // (tests/test_mz_env_host.py); the kernels call these functions.  fp64, one rounding per operation (-ffp-contract=off), the
-// expressions in the order the twin writes them: on one host, with one libm, the two give the same bits.
+// expressions in the order the restatements write them: on one host, with one libm, the two give the same bits.
 //
 // An environment is a TRAIT: a struct of static functions over its state record -- kState doubles, kObs floats of an observation,
-// kActions actions, load / store, reset, step, observe -- and one kernel template serves every environment.  CartPole's functions
-// stay in rz_muzero.hip (the whole-move search is built on them); its trait sits beside them there and only calls them.
+// kActions actions, load / store, reset, step, observe -- and one kernel template serves every environment.  The whole-move search
+// is built for CartPole and calls its functions directly.
 //
+// CartPole-v1: Gymnasium classic_control/cartpole.py v0.29 (Euler integrator, tau 0.02 s, force 10 N, the episode ends at |x| > 2.4
+// or |theta| > 12 degrees, reward 1 per step), auto-reset -- the device twin of rlzero_amd/muzero/cartpole.py.
 // Acrobot-v1: Gymnasium classic_control/acrobot.py (Sutton's "book" dynamics, no torque noise): two links, torque -1 / 0 / +1 on
 // the joint between them, one classical RK4 step of 0.2 s per move, reward -1 per step until the tip is one link above the base.
 #pragma once
@@ -28,7 +31,7 @@
 
 namespace rzmze {
 
-// splitmix64: the counter-based stream of rlzero_amd/muzero/cartpole.py (rz_muzero.hip: mz_splitmix64)
+// splitmix64: the counter-based stream of rlzero_amd/muzero/cartpole.py
 RZE_FN uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     uint64_t z = x;
@@ -41,6 +44,66 @@ RZE_FN uint64_t reset_key(uint64_t seed, int env, long long episode) {
     return splitmix64(splitmix64(seed ^ ((uint64_t)env << 24)) ^ (uint64_t)episode);
 }
 RZE_FN double reset_uniform(uint64_t key, int j) { return (double)(splitmix64(key ^ (uint64_t)(j + 1)) >> 11) / 9007199254740992.0; }
+
+// ------------------------------------------------------------------ CartPole-v1
+struct MzCartPole {
+    double x, x_dot, theta, theta_dot;
+    long long steps, episode;
+};
+
+RZE_FN void cartpole_reset(MzCartPole &c, uint64_t seed, int env) {
+    const uint64_t key = reset_key(seed, env, c.episode);
+    double v[4];
+    for (int j = 0; j < 4; ++j) v[j] = -0.05 + 0.1 * reset_uniform(key, j);
+    c.x = v[0];
+    c.x_dot = v[1];
+    c.theta = v[2];
+    c.theta_dot = v[3];
+    c.steps = 0;
+}
+
+// one step (an action other than 1 pushes to the left; the reward is 1); -> RZ_MZE_TERMINATED | RZ_MZE_TRUNCATED (the state is the
+// terminal one: the caller resets)
+RZE_FN int cartpole_step(MzCartPole &c, int action, long long max_episode_steps) {
+    const double gravity = 9.8, masspole = 0.1, total_mass = 0.1 + 1.0, length = 0.5, polemass_length = 0.1 * 0.5, tau = 0.02;
+    const double theta_threshold = 12 * 2 * 3.141592653589793 / 360, x_threshold = 2.4;
+    const double force = action == 1 ? 10.0 : -10.0;
+    const double costheta = cos(c.theta), sintheta = sin(c.theta);
+    const double temp = (force + polemass_length * (c.theta_dot * c.theta_dot) * sintheta) / total_mass;
+    const double thetaacc = (gravity * sintheta - costheta * temp) / (length * (4.0 / 3.0 - masspole * (costheta * costheta) / total_mass));
+    const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
+    c.x = c.x + tau * c.x_dot;
+    c.x_dot = c.x_dot + tau * xacc;
+    c.theta = c.theta + tau * c.theta_dot;
+    c.theta_dot = c.theta_dot + tau * thetaacc;
+    c.steps += 1;
+    const bool terminated = c.x < -x_threshold || c.x > x_threshold || c.theta < -theta_threshold || c.theta > theta_threshold;
+    const bool truncated = c.steps >= max_episode_steps;
+    return (terminated ? RZ_MZE_TERMINATED : 0) | (truncated ? RZ_MZE_TRUNCATED : 0);
+}
+
+struct EnvCartPole {
+    typedef MzCartPole State;
+    static constexpr int kState = 4, kObs = 4, kActions = 2;
+    RZE_FN static void load(State &c, const double *s, long long steps, long long episode) { c = State{s[0], s[1], s[2], s[3], steps, episode}; }
+    RZE_FN static void store(const State &c, double *s) {
+        s[0] = c.x;
+        s[1] = c.x_dot;
+        s[2] = c.theta;
+        s[3] = c.theta_dot;
+    }
+    RZE_FN static void reset(State &c, uint64_t seed, int env) { cartpole_reset(c, seed, env); }
+    RZE_FN static int step(State &c, int action, long long max_episode_steps, double *reward) {
+        *reward = 1.0;
+        return cartpole_step(c, action, max_episode_steps);
+    }
+    RZE_FN static void observe(const State &c, float *obs) {
+        obs[0] = (float)c.x;
+        obs[1] = (float)c.x_dot;
+        obs[2] = (float)c.theta;
+        obs[3] = (float)c.theta_dot;
+    }
+};
 
 // ------------------------------------------------------------------ Acrobot-v1
 struct MzAcrobot {
@@ -143,7 +206,7 @@ struct EnvAcrobot {
     RZE_FN static void observe(const State &c, float *obs) { acrobot_observe(c, obs); }
 };
 
-// ------------------------------------------------------------------ the move behind a search (k_mz_env_move)
+// ------------------------------------------------------------------ the move behind a search (k_mz_search's MOVES stages, k_mz_env_move)
 // weights visits ^ (1 / T) (the visits themselves at 1 / T = 1 or <= 0), their sum in action order and the first maximum
 RZE_FN int move_weights(const int *visits, int A, double inv_temperature, double *wgt, double *total) {
     double sum = 0.0, best = -1.0;
@@ -173,5 +236,14 @@ RZE_FN int move_draw(const double *wgt, int A, double total, uint64_t key) {
 RZE_FN uint64_t move_key(uint64_t noise_seed, uint64_t salt, int g, long long episode, long long steps) {
     return splitmix64(splitmix64(splitmix64(noise_seed ^ salt ^ ((uint64_t)g << 24)) ^ (uint64_t)episode) ^ (uint64_t)steps);
 }
+
+// the 32-bit key of action a's Dirichlet draw under the move's key (salt 0)
+RZE_FN uint32_t noise_key(uint64_t key, int a) { return (uint32_t)(key >> 32) + 0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key; }
+
+// a move's record of D + 4 + A doubles: obs (D, from 0) | action | reward | visits (A) | root value | done
+struct RecordLayout {
+    int action, reward, visits, root_value, done, row;
+};
+RZE_FN constexpr RecordLayout record_layout(int D, int A) { return RecordLayout{D, D + 1, D + 2, D + 2 + A, D + 3 + A, D + 4 + A}; }
 
 }  // namespace rzmze

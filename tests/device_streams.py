@@ -44,7 +44,7 @@ def mix64(x):
 
 
 def splitmix64(x):
-    """rz_muzero.hip mz_splitmix64: rlzero_amd/muzero/cartpole.py's, on uint64 arrays."""
+    """rz_mz_env.h splitmix64: rlzero_amd/muzero/cartpole.py's, on uint64 arrays."""
     from rlzero_amd.muzero.cartpole import _splitmix64
     with np.errstate(over='ignore'):
         return _splitmix64(np.asarray(x, dtype=np.uint64))

@@ -7,7 +7,8 @@ G = 40 environments everywhere: not a multiple of a wave, of the search's 16 gam
   test_cartpole_batch_vs_scalar_restatement allows over 120 unsynchronised steps; one step's rounding (another library's sin and
   cos, about 1e-16 each, through a step whose derivatives reach a few hundred) is about 1e-13.  An environment whose twin comes
   within 1e-9 of a decision (pre-wrap angle against +-pi, height against 1, velocity against its bound) is left out and counted:
-  none is, asserted;
+  none is, asserted; CartPole, which rz_cartpole_step and rz_mz_env_step serve with one kernel, follows oracle/muzero_ref.RefCartPole
+  (tests/cartpole_twin.py) under the same bound and the same rule;
 * the move: tests/device_streams.py (action draw, root noise, under the tolerance rules of tests/test_noise_streams_gpu.py);
 * the route: the host-driven loop (``device_moves=False``) searching from the same torch initial inference with the same kernel:
   the same episodes in the same order, bit for bit."""
@@ -20,6 +21,7 @@ import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
 import acrobot_twin as twin
+import cartpole_twin as cart
 import device_streams as ds
 from test_mz_replay_host import every_position, same_bits
 
@@ -104,26 +106,84 @@ def test_acrobot_batch_against_the_twin_one_step_at_a_time():
     assert seen['truncated'] == G - G // 2 and seen['reset'] < G
 
 
-def test_env_step_serves_cartpole_too():
-    """rz_mz_env_step(RZ_MZ_ENV_CARTPOLE) is rz_cartpole_step: the same bits over 30 steps of the same actions, resets included."""
+def check_cartpole_step(before, steps_before, episode_before, actions, got, seed, max_steps):
+    """One device step of every CartPole environment against RefCartPole set to the device's state -> counts of what was seen."""
+    from rlzero_amd.muzero.cartpole import initial_states
+    state, steps, episode, obs, reward, term, trunc = got
+    seen = dict(left_out=0, terminated=0, truncated=0, both=0, reset=0)
+    for i in range(len(before)):
+        s, a = tuple(before[i]), int(actions[i])
+        if cart.decision_margin(s, a) < BOUND:
+            seen['left_out'] += 1
+            continue
+        new, new_steps, r, t1, t2 = cart.step(s, int(steps_before[i]), a, max_steps)
+        assert (bool(term[i]), bool(trunc[i]), float(reward[i])) == (t1, t2, r), (i, s, a)
+        seen['terminated'] += t1
+        seen['truncated'] += t2
+        seen['both'] += t1 and t2
+        if t1 or t2:   # the state is the next episode's first, exactly
+            seen['reset'] += 1
+            want = initial_states(seed, [i], [episode_before[i] + 1])[0]
+            assert same_bits(state[i], want) and steps[i] == 0 and episode[i] == episode_before[i] + 1
+        else:
+            assert np.abs(state[i] - np.array(new)).max() <= BOUND, (i, s, a, state[i], new)
+            assert steps[i] == new_steps and episode[i] == episode_before[i]
+        assert obs.dtype == np.float32 and same_bits(obs[i], state[i].astype(np.float32))
+    return seen
+
+
+def env_step_cartpole(env, actions, max_steps):
+    """rz_mz_env_step(RZ_MZ_ENV_CARTPOLE) on a CartPoleBatch's tensors -> what ``device_step`` returns."""
     import ctypes
     import torch
     from rlzero_amd import _hip
     from rlzero_amd.engine import _ptr, check
+    act = torch.from_numpy(actions).to(DEV)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+    check(env.lib.rz_mz_env_step(_hip.MZ_ENV_CARTPOLE, _ptr(env.state), _ptr(env.steps), _ptr(env.episode_dev), _ptr(act), G, env.seed, max_steps,
+                                 _ptr(env._obs), _ptr(env._reward), _ptr(env._terminated), _ptr(env._truncated), stream), 'rz_mz_env_step')
+    return (env.state.cpu().numpy(), env.steps.cpu().numpy(), env.episode, env._obs.cpu().numpy(), env._reward.cpu().numpy(),
+            env._terminated.cpu().numpy().astype(bool), env._truncated.cpu().numpy().astype(bool))
+
+
+def test_env_step_serves_cartpole_too():
+    """rz_mz_env_step(RZ_MZ_ENV_CARTPOLE, ..., 500) and rz_cartpole_step are one kernel: over 30 steps of 40 environments each follows
+    RefCartPole from the state before within 1e-9 with equal flags and step counts, a reset carries the bits of ``initial_states``, and
+    the two give the same bits.  Then the crafted states of the host test through rz_mz_env_step with a limit of 12, half of the
+    environments at step 11."""
     from rlzero_amd.muzero import CartPoleBatch
-    a, b = CartPoleBatch(G, DEV, seed=2), CartPoleBatch(G, DEV, seed=2)
+    from rlzero_amd.muzero.cartpole import initial_states
+    seed = 2
+    a, b = CartPoleBatch(G, DEV, seed=seed), CartPoleBatch(G, DEV, seed=seed)
+    assert same_bits(b.state.cpu().numpy(), initial_states(seed, np.arange(G), np.zeros(G, dtype=np.int64)))
     rng = np.random.RandomState(3)
-    resets = 0
+    total = dict()
     for _ in range(30):
-        actions = torch.from_numpy(rng.randint(0, 2, size=G).astype(np.int64)).to(DEV)
-        want = a.step(actions)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(b.device).cuda_stream)
-        check(b.lib.rz_mz_env_step(_hip.MZ_ENV_CARTPOLE, _ptr(b.state), _ptr(b.steps), _ptr(b.episode_dev), _ptr(actions), G, b.seed, 500, _ptr(b._obs),
-                                   _ptr(b._reward), _ptr(b._terminated), _ptr(b._truncated), stream), 'rz_mz_env_step')
-        got = (b._obs, b._reward, b._terminated.bool(), b._truncated.bool())
-        assert all(torch.equal(x, y) for x, y in zip(got, want)) and torch.equal(a.state, b.state) and torch.equal(a.steps, b.steps)
-        resets += int(want[2].sum())
-    assert resets > 0 and np.array_equal(a.episode, b.episode)
+        actions = rng.randint(0, 2, size=G).astype(np.int64)
+        before, steps_before, episode_before = b.state.cpu().numpy(), b.steps.cpu().numpy(), b.episode
+        got_a, got_b = device_step(a, actions), env_step_cartpole(b, actions, 500)
+        for got in (got_a, got_b):
+            seen = check_cartpole_step(before, steps_before, episode_before, actions, got, seed, 500)
+        for x, y in zip(got_a, got_b):   # (state, steps, episode, obs, reward and the two flags)
+            assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+        for k, v in seen.items():
+            total[k] = total.get(k, 0) + int(v)
+    print('30 random steps of %d environments: %s' % (G, total))
+    assert total['left_out'] == 0 and total['terminated'] > 0 and total['reset'] == total['terminated']
+
+    cases = cart.crafted_states()
+    states = np.array([cases[i % len(cases)][1] for i in range(G)], dtype=np.float64)
+    actions = np.array([cases[i % len(cases)][2] for i in range(G)], dtype=np.int64)
+    b.set_states(states)
+    b.steps[G // 2:] = 11
+    b.episode_dev[::3] += 5
+    before, steps_before, episode_before = b.state.cpu().numpy(), b.steps.cpu().numpy(), b.episode
+    assert same_bits(before, states)
+    seen = check_cartpole_step(before, steps_before, episode_before, actions, env_step_cartpole(b, actions, 12), seed, 12)
+    print('crafted states: %s' % seen)
+    ends = sum(bool(cases[i % len(cases)][3]) for i in range(G))
+    assert seen['left_out'] == 0 and seen['terminated'] == ends and seen['truncated'] == G - G // 2
+    assert 1 <= seen['both'] < seen['truncated'] and seen['reset'] < G   # (truncated only, terminated only, both and neither are all met)
 
 
 # ------------------------------------------------------------------------------------------------ env_move alone

@@ -1,5 +1,6 @@
-"""The environment rules of the MuZero device moves (rlzero_amd/csrc/rz_mz_env.h) on the CPU, against the scalar twin
-(tests/acrobot_twin.py) and the host restatement of the action draw (tests/device_streams.py).
+"""The rules of MuZero's moves on the device (rlzero_amd/csrc/rz_mz_env.h) on the CPU, against the scalar twins (tests/acrobot_twin.py;
+oracle/muzero_ref.RefCartPole through tests/cartpole_twin.py) and the host restatement of the keys and the action draw
+(tests/device_streams.py).
 
 A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_learner_host.py builds its driver),
 -ffp-contract=off, fed binary inputs and compared with the twin:
@@ -8,10 +9,15 @@ A driver with its own main is compiled against the header with ROCm's clang++ (a
   on each side, each velocity bound passed on each side, the height crossing 1.0, steps = max - 1 -- equal the twin BIT FOR BIT:
   the same libm, the same order of operations, no contraction.
 * ``acrobot_reset`` equals ``rlzero_amd.muzero.acrobot_initial_states`` bit for bit and lies in [-0.1, 0.1).
-* The header's action draw (``move_weights`` / ``move_draw`` / ``move_key``) is ``device_streams.muzero_action``.
+* ``EnvCartPole`` (the benchmark's environment) over 4000 random states and actions and over crafted states -- x across +2.4 and
+  -2.4, theta across each threshold, steps = 499 truncated only, one state terminated and truncated -- equals RefCartPole BIT FOR BIT;
+  its reset equals ``rlzero_amd.muzero.cartpole.initial_states`` bit for bit and lies in [-0.05, 0.05).
+* The header's action draw (``move_weights`` / ``move_draw`` / ``move_key``) is ``device_streams.muzero_action``, its per-action noise
+  key ``device_streams.muzero_action_keys``, its record layout the one include/rlzero_hip.h documents.
 * The same driver built with -fsanitize=address,undefined runs every input as a stand-alone program and writes the same bytes.
 * What the GPU test's bound of 1e-9 catches: the twin with k3 dropped, dt / 6 replaced by dt / 4, the -pi / 2 dropped from phi2, or
-  the velocity clamp removed is more than 1e-4 away from the true twin in at least one of the random states, each.
+  the velocity clamp removed is more than 1e-4 away from the true twin in at least one of the random states, each; so is RefCartPole's
+  step with tau changed, the 4 / 3 dropped or the force's sign swapped.
 * The trainer's parser takes ``--env acrobot`` and refuses an unknown environment."""
 import importlib.util
 import os
@@ -23,6 +29,7 @@ import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
 import acrobot_twin as twin
+import cartpole_twin as cart
 import device_streams as ds
 from rlzero_amd.muzero.acrobot import acrobot_initial_states
 from test_delta_gather_host import host_clangxx
@@ -61,8 +68,10 @@ static void store(const char *path, const std::vector<T> &v) {
 }
 
 // step max_steps state.f64 [n][4] steps.i64 [n] actions.i64 [n] -> state.f64 [n][4], steps.i64 [n], reward.f64 [n], flags.i32 [n],
-//   obs before.f32 [n][6], obs after.f32 [n][6]      (through the trait, as the kernels go)
+//   obs before.f32 [n][kObs], obs after.f32 [n][kObs]      (through the trait, as the kernels go)
+template <typename Env>
 static int step(char **a) {
+    constexpr int D = Env::kObs;
     const long long max_steps = atoll(a[0]);
     const std::vector<double> state = load<double>(a[1]);
     const std::vector<int64_t> steps = load<int64_t>(a[2]), actions = load<int64_t>(a[3]);
@@ -71,15 +80,15 @@ static int step(char **a) {
     std::vector<double> out(4 * n), reward(n);
     std::vector<int64_t> steps_out(n);
     std::vector<int32_t> flags(n);
-    std::vector<float> before(6 * n), after(6 * n);
+    std::vector<float> before(D * n), after(D * n);
     for (size_t i = 0; i < n; ++i) {
-        re::EnvAcrobot::State c;
-        re::EnvAcrobot::load(c, &state[4 * i], steps[i], 0);
-        re::EnvAcrobot::observe(c, &before[6 * i]);
-        flags[i] = re::EnvAcrobot::step(c, (int)actions[i], max_steps, &reward[i]);
-        re::EnvAcrobot::store(c, &out[4 * i]);
+        typename Env::State c;
+        Env::load(c, &state[4 * i], steps[i], 0);
+        Env::observe(c, &before[D * i]);
+        flags[i] = Env::step(c, (int)actions[i], max_steps, &reward[i]);
+        Env::store(c, &out[4 * i]);
         steps_out[i] = c.steps;
-        re::EnvAcrobot::observe(c, &after[6 * i]);
+        Env::observe(c, &after[D * i]);
     }
     store(a[4], out);
     store(a[5], steps_out);
@@ -91,6 +100,7 @@ static int step(char **a) {
 }
 
 // reset seed env.i64 [n] episode.i64 [n] -> state.f64 [n][4], steps.i64 [n]
+template <typename Env>
 static int reset(char **a) {
     const uint64_t seed = strtoull(a[0], nullptr, 10);
     const std::vector<int64_t> env = load<int64_t>(a[1]), episode = load<int64_t>(a[2]);
@@ -99,9 +109,11 @@ static int reset(char **a) {
     std::vector<double> out(4 * n);
     std::vector<int64_t> steps(n);
     for (size_t i = 0; i < n; ++i) {
-        re::MzAcrobot c = {9.0, 9.0, 9.0, 9.0, 77, episode[i]};
-        re::acrobot_reset(c, seed, (int)env[i]);
-        re::EnvAcrobot::store(c, &out[4 * i]);
+        const double nines[4] = {9.0, 9.0, 9.0, 9.0};
+        typename Env::State c;
+        Env::load(c, nines, 77, episode[i]);
+        Env::reset(c, seed, (int)env[i]);
+        Env::store(c, &out[4 * i]);
         steps[i] = c.steps;
     }
     store(a[3], out);
@@ -131,10 +143,35 @@ static int draw(char **a) {
     return 0;
 }
 
+// noise_keys A seed env.i64 [n] episode.i64 [n] steps.i64 [n] -> key.u32 [n][A]: the per-action keys of a move's root noise
+static int noise_keys(char **a) {
+    const int A = atoi(a[0]);
+    const uint64_t seed = strtoull(a[1], nullptr, 10);
+    const std::vector<int64_t> env = load<int64_t>(a[2]), episode = load<int64_t>(a[3]), steps = load<int64_t>(a[4]);
+    const size_t n = env.size();
+    if (A < 1 || A > RZ_MZE_MAX_ACTIONS || episode.size() != n || steps.size() != n) return 4;
+    std::vector<uint32_t> key(n * (size_t)A);
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < A; ++k) key[i * A + k] = re::noise_key(re::move_key(seed, 0ull, (int)env[i], episode[i], steps[i]), k);
+    store(a[5], key);
+    return 0;
+}
+
+// layout D A -> i32 [6]: the offsets of action, reward, visits, root value and done in a record, and its length
+static int layout(char **a) {
+    const re::RecordLayout r = re::record_layout(atoi(a[0]), atoi(a[1]));
+    store(a[2], std::vector<int32_t>{r.action, r.reward, r.visits, r.root_value, r.done, r.row});
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const std::string what = argc > 1 ? argv[1] : "";
-    if (what == "step" && argc == 12) return step(argv + 2);
-    if (what == "reset" && argc == 7) return reset(argv + 2);
+    if (what == "step" && argc == 12) return step<re::EnvAcrobot>(argv + 2);
+    if (what == "reset" && argc == 7) return reset<re::EnvAcrobot>(argv + 2);
+    if (what == "cartpole_step" && argc == 12) return step<re::EnvCartPole>(argv + 2);
+    if (what == "cartpole_reset" && argc == 7) return reset<re::EnvCartPole>(argv + 2);
+    if (what == "noise_keys" && argc == 8) return noise_keys(argv + 2);
+    if (what == "layout" && argc == 5) return layout(argv + 2);
     if (what == "draw" && argc == 10) return draw(argv + 2);
     return 4;
 }
@@ -291,6 +328,119 @@ def test_the_headers_action_draw_is_the_restatement(drv, A, inv_t):
     assert keep.all() and np.array_equal(got[keep], want[keep])
     if inv_t > 0:
         assert len(np.unique(got)) == A
+
+
+# ------------------------------------------------------------------------------------------------ CartPole and the rules of a move
+def cartpole_random_cases(n=4000, seed=6):
+    """States well past every threshold on both sides (2.4; 12 degrees = 0.2094), any action, any step count below the limit."""
+    rng = np.random.RandomState(seed)
+    state = np.stack([rng.uniform(-2.6, 2.6, n), rng.uniform(-3.0, 3.0, n), rng.uniform(-0.23, 0.23, n), rng.uniform(-3.0, 3.0, n)], axis=1)
+    return state, rng.randint(0, 499, size=n).astype(np.int64), rng.randint(0, 2, size=n).astype(np.int64)
+
+
+def cartpole_ref_steps(state, steps, actions, max_steps, variant=None):
+    out, steps_out, reward, flags = np.zeros_like(state), np.zeros_like(steps), np.zeros(len(state)), np.zeros(len(state), dtype=np.int32)
+    for i in range(len(state)):
+        new, steps_out[i], reward[i], term, trunc = cart.step(tuple(state[i]), int(steps[i]), int(actions[i]), max_steps, variant)
+        out[i] = new
+        flags[i] = (1 if term else 0) | (2 if trunc else 0)
+    return out, steps_out, reward, flags
+
+
+def check_against_ref_cartpole(drv, state, steps, actions, max_steps):
+    """``EnvCartPole`` against RefCartPole: every bit of the state, the step count, both flags, the reward of 1 and the two observations."""
+    got = drv.run('cartpole_step', [max_steps], [state, steps, actions], [np.float64, np.int64, np.float64, np.int32, np.float32, np.float32])
+    out, steps_out, reward, flags, before, after = got
+    want, want_steps, want_reward, want_flags = cartpole_ref_steps(state, steps, actions, max_steps)
+    assert same_bits(out.reshape(-1, 4), want), 'largest difference %g' % np.abs(out.reshape(-1, 4) - want).max()
+    assert np.array_equal(steps_out, want_steps) and np.array_equal(flags, want_flags)
+    assert same_bits(reward, want_reward) and (reward == 1.0).all()
+    assert same_bits(before.reshape(-1, 4), state.astype(np.float32)) and same_bits(after.reshape(-1, 4), want.astype(np.float32))
+    return want, want_flags
+
+
+def test_cartpole_is_the_reference_on_random_states(drv):
+    """4000 states x actions through the trait, both builds of the driver: RefCartPole bit for bit.  The sample ends episodes on each
+    of the four sides and leaves others running (asserted)."""
+    state, steps, actions = cartpole_random_cases()
+    want, flags = check_against_ref_cartpole(drv, state, steps, actions, 500)
+    running = (flags & 1) == 0
+    assert running.any() and (want[:, 0] > cart.X_THRESHOLD).any() and (want[:, 0] < -cart.X_THRESHOLD).any()
+    assert (want[:, 2] > cart.THETA_THRESHOLD).any() and (want[:, 2] < -cart.THETA_THRESHOLD).any()
+    assert np.abs(want[running, 0]).max() <= cart.X_THRESHOLD and np.abs(want[running, 2]).max() <= cart.THETA_THRESHOLD
+    assert not (flags & 2).any()
+    # the limit is the caller's: one step below it is truncated
+    _, flags12 = check_against_ref_cartpole(drv, state, np.full_like(steps, 11), actions, 12)
+    assert (flags12 & 2).all() and np.array_equal(flags12 & 1, flags & 1)
+
+
+def test_cartpole_is_the_reference_on_crafted_states(drv):
+    """x across +2.4 and -2.4, theta across each threshold, and the same short of it; steps = 499 comes back truncated -- truncated ONLY
+    where the step does not end the episode, terminated AND truncated where it does.  Every case is compared, every flag is seen."""
+    cases = cart.crafted_states()
+    state = np.array([c[1] for c in cases], dtype=np.float64)
+    actions = np.array([c[2] for c in cases], dtype=np.int64)
+    ends = np.array([c[3] for c in cases])
+    assert ends.any() and not ends.all()
+    want, flags = check_against_ref_cartpole(drv, state, np.full(len(cases), 499, dtype=np.int64), actions, 500)
+    assert np.array_equal(flags, np.where(ends, 3, 2))   # (2: truncated only; 3: both)
+    _, early = check_against_ref_cartpole(drv, state, np.full(len(cases), 11, dtype=np.int64), actions, 500)
+    assert np.array_equal(early, np.where(ends, 1, 0))   # (1: terminated only; 0: the episode goes on)
+    new = {c[0]: w for c, w in zip(cases, want)}
+    assert state[0][0] < cart.X_THRESHOLD < new['x above 2.4'][0] and state[1][0] > -cart.X_THRESHOLD > new['x below -2.4'][0]
+    assert state[2][2] < cart.THETA_THRESHOLD < new['theta above its threshold'][2]
+    assert state[3][2] > -cart.THETA_THRESHOLD > new['theta below minus its threshold'][2]
+    assert abs(new['x stays inside'][0]) < cart.X_THRESHOLD and abs(new['theta stays inside'][2]) < cart.THETA_THRESHOLD
+    assert min(cart.decision_margin(c[1], c[2]) for c in cases) > 1e-3   # (none of them sits on a decision: the GPU test reuses them)
+
+
+def test_cartpole_reset_is_the_restatement(drv):
+    from rlzero_amd.muzero.cartpole import initial_states
+    rng = np.random.RandomState(2)
+    env = np.concatenate([np.arange(40), rng.randint(0, 2 ** 20, size=200)]).astype(np.int64)
+    episode = np.concatenate([np.zeros(40), rng.randint(0, 2 ** 40, size=200)]).astype(np.int64)
+    for seed in (0, 7, 2 ** 64 - 1):
+        got, steps = drv.run('cartpole_reset', [seed], [env, episode], [np.float64, np.int64])
+        want = initial_states(seed, env, episode)
+        assert same_bits(got.reshape(-1, 4), want) and not steps.any()
+        assert want.min() >= -0.05 and want.max() < 0.05
+        assert want.std() > 0.025 and abs(want.mean()) < 0.005   # (uniform over the range: 0.1 / sqrt(12) = 0.0289)
+
+
+@pytest.mark.parametrize('A', [2, 3, 8])
+def test_the_headers_noise_key_is_the_restatement(drv, A):
+    """``noise_key`` under ``move_key`` with salt 0: the 32-bit key of every action's gamma draw, as device_streams.muzero_action_keys."""
+    rng = np.random.RandomState(A)
+    env, episode, steps = (rng.randint(0, hi, size=3000).astype(np.int64) for hi in (8192, 1000, 500))
+    for seed in (11, 2 ** 64 - 1):
+        got, = drv.run('noise_keys', [A, seed], [env, episode, steps], [np.uint32])
+        want = ds.muzero_action_keys(seed, env, episode, steps, A)
+        assert np.array_equal(got.reshape(-1, A).astype(np.uint64), want)
+    assert len(np.unique(got)) > 0.99 * got.size
+
+
+@pytest.mark.parametrize('D,A', [(4, 2), (6, 3)])
+def test_the_record_layout_is_the_documented_one(drv, D, A):
+    """obs (D) | action | reward | visits (A) | root value | done: D + 4 + A doubles, 8 + A for CartPole (include/rlzero_hip.h)."""
+    got, = drv.run('layout', [D, A], [], [np.int32])
+    assert got.tolist() == [D, D + 1, D + 2, D + 2 + A, D + 3 + A, D + 4 + A]
+    if D == 4:
+        assert got[5] == 8 + A
+    header = open(os.path.join(REPO, 'include', 'rlzero_hip.h')).read()
+    assert 'a record is 8 + A float64 -- observation before the move (4) | action | reward | visit' in header
+    assert 'obs (D) | action | reward | visits (A) | root value | done' in header and '[ring_steps][D + 4 + A]' in header
+
+
+@pytest.mark.parametrize('variant', cart.VARIANTS)
+def test_the_gpu_bound_catches_cartpole_rule_errors(variant):
+    """As for Acrobot below: RefCartPole's step with tau changed, the 4 / 3 dropped or the force's sign swapped is more than 1e-4 away
+    from the true one in at least one of the random states (figures printed); the GPU tests allow 1e-9."""
+    state, steps, actions = cartpole_random_cases()
+    true, _, _, _ = cartpole_ref_steps(state, steps, actions, 500)
+    broken, _, _, _ = cartpole_ref_steps(state, steps, actions, 500, variant)
+    worst = np.abs(broken - true).max(axis=1)
+    print('%s: largest difference %.3g, %d of %d states above %g' % (variant, worst.max(), int((worst > CAUGHT_ABOVE).sum()), len(worst), CAUGHT_ABOVE))
+    assert (worst > CAUGHT_ABOVE).any() and CAUGHT_ABOVE >= 1e5 * GPU_BOUND
 
 
 @pytest.mark.parametrize('variant', twin.VARIANTS)
