@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 41
+#define RZ_ABI_VERSION 42
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -877,6 +877,29 @@ typedef struct rz_mz_env_play {
 int rz_mz_env_step(int32_t kind, double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                    int64_t max_episode_steps, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
 int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream);
+/* Whole MOVES of any environment the library knows, in one launch (ABI 42; k_mz_search<TREE_LDS, MOVES = true, Env>): what
+ * rz_mz_play_cartpole does, with the environment's step, observation, reset, reward and action count taken from its trait in
+ * csrc/rz_mz_env.h and the time limit from the play record.  kind: RZ_MZ_ENV_CARTPOLE or RZ_MZ_ENV_ACROBOT.  The play record is
+ * rz_mz_cartpole_play's, field for field, followed by max_episode_steps; d_state is float64 [n_games][4] for both kinds, a record
+ * is D + 4 + A float64 (CartPole 10, Acrobot 13), ring_steps >= max_episode_steps + n_moves.  RZ_ERR_ARG, with a message that names
+ * the reason, for an unknown kind, a tree whose n_actions or a loaded representation whose obs_dim is not the environment's,
+ * dirichlet_alpha < 0.1, a ring too small, or no representation loaded.  rz_mz_play_cartpole is this call with RZ_MZ_ENV_CARTPOLE
+ * and max_episode_steps 500. */
+typedef struct rz_mz_whole_play {
+    double *d_state;
+    int64_t *d_steps, *d_episode, *d_episode_start;
+    uint64_t env_seed, noise_seed;
+    double noise_frac, dirichlet_alpha, temperature;
+    double *d_ring;
+    int32_t ring_steps, reserved;
+    int64_t first_step;
+    double *d_arena;
+    int64_t arena_rows;
+    int64_t *d_counters, *d_entries;
+    int64_t max_entries;
+    int64_t max_episode_steps;
+} rz_mz_whole_play;
+int rz_mz_play_env(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_whole_play *play, void *stream);
 int rz_mz_root_noise(rz_muzero *e, const int64_t *d_episode, const int64_t *d_steps, uint64_t noise_seed, double dirichlet_alpha, double *d_eta,
                      void *stream);
 int rz_mz_root_children(rz_muzero *e, int32_t what, void *d_out, void *stream);
@@ -892,7 +915,7 @@ int rz_mz_error_flags(rz_muzero *e, int32_t *flags);
  * network's probabilities, reward is stored in the node, and a leaf's value follows from the backup identity
  * value_sum[s] = v[s] + sum over children (N_c * reward_c + discount * value_sum_c) (no v term for the root).
  * rz_mz_search_plan: what a launch of the fused search (whole_moves 0: rz_mz_search) or of whole moves (whole_moves 1:
- * rz_mz_play_cartpole) would be for the current shape (rz_mz_set_search_shape), from the function the launch itself uses: games
+ * rz_mz_play_env / rz_mz_play_cartpole, for the tree's action count) would be for the current shape (rz_mz_set_search_shape), from the function the launch itself uses: games
  * per workgroup, whether the trees live in LDS (1) or stay in HBM (0), dynamic LDS bytes.  Any output pointer may be NULL. */
 typedef struct rz_mz_node {
     int32_t n;           /* visit count */

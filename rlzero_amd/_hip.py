@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -60,6 +60,11 @@ class RzMzCartPolePlay(Structure):
                 ('temperature', c_double), ('d_ring', c_void_p), ('ring_steps', c_int32), ('reserved', c_int32),
                 ('first_step', c_int64), ('d_arena', c_void_p), ('arena_rows', c_int64), ('d_counters', c_void_p),
                 ('d_entries', c_void_p), ('max_entries', c_int64)]
+
+
+class RzMzWholePlay(Structure):
+    """rz_mz_whole_play: rz_mz_cartpole_play's fields followed by the time limit, for rz_mz_play_env (ABI 42)."""
+    _fields_ = RzMzCartPolePlay._fields_ + [('max_episode_steps', c_int64)]
 
 
 class RzMzEnvPlay(Structure):
@@ -231,6 +236,7 @@ _SIGNATURES = {
     'rz_cartpole_step': (c_int, [P, P, P, P, c_int32, c_uint64, P, P, P, P, P]),
     'rz_mz_env_step': (c_int, [c_int32, P, P, P, P, c_int32, c_uint64, c_int64, P, P, P, P, P]),
     'rz_mz_env_move': (c_int, [P, c_int32, POINTER(RzMzEnvPlay), P]),
+    'rz_mz_play_env': (c_int, [P, c_int32, P, c_int32, c_int32, POINTER(RzMzWholePlay), P]),
     'rz_mz_root_noise': (c_int, [P, P, P, c_uint64, c_double, P, P]),
     'rz_mz_root_children': (c_int, [P, c_int32, P, P]),
     'rz_mz_root_stats': (c_int, [P, P, P, P, P, P]),

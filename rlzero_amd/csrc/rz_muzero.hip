@@ -13,8 +13,9 @@
 //     caller gathers the parents' hidden states, runs dynamics + prediction on the batch, stores the new hidden states
 //     at the leaf slots and hands reward / policy / value back;
 //   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search);
-//   * rz_mz_play_cartpole: whole MOVES in one launch -- initial inference, root noise, search, action draw, CartPole step,
-//     episode history on the device (k_mz_search with its MOVES stages).
+//   * rz_mz_play_env (rz_mz_play_cartpole is its CartPole form): whole MOVES in one launch -- initial inference, root noise, search,
+//     action draw, environment step, episode history on the device (k_mz_search with its MOVES stages, instantiated per environment
+//     trait of rz_mz_env.h: CartPole, Acrobot).
 // Behind rz_mz_search, for any environment whose rules the library holds (at the end of this file): rz_mz_env_move -- action draw,
 // environment step, record, hand-over of finished episodes, a thread per environment -- with rz_mz_root_noise and rz_mz_env_step
 // (rz_cartpole_step is its CartPole instantiation) beside it.
@@ -296,10 +297,17 @@ __device__ __forceinline__ long long mz_claim_episode(long long *counters, long 
 //     bit for bit, given the same network outputs (the outputs differ from rocBLAS' in the last bits: another
 //     summation order).  TREE_LDS: the trees (32 B x slots per game), the paths and the log table live in LDS for the
 //     search (a level of the walk costs an LDS round trip instead of an L2 one) and are written back at the end;
-//   * MOVES (rz_mz_play_cartpole): whole MOVES of CartPole environments in the launch -- per move the initial inference
+//   * MOVES (rz_mz_play_env): whole MOVES of the environments in the launch -- per move the initial inference
 //     (representation + prediction on the same tiles), root expansion with Dirichlet noise, the n_sims simulations,
 //     the action drawn from the visit counts, one packed record for the host and the environment step: the host's
-//     part of self-play shrinks to reading the records.
+//     part of self-play shrinks to reading the records.  The stages are generic over the environment trait `Env` of rz_mz_env.h
+//     (EnvCartPole: 2 actions, 4 observations; EnvAcrobot: 3 actions, 6 observations): the action count of the unrolled loops, of the
+//     walk and of dyn1's one-hot columns is Env::kActions, the LDS record of an environment is Env::kState doubles + steps, episode,
+//     episode start (<= 8), Env::observe fills Env::kObs rows of OBS (the rest stay zero, as rep1_w's rows past obs_dim), the record is
+//     record_layout(Env::kObs, Env::kActions) with the reward Env::step returns, the time limit comes from MzPlay.  Every rule is
+//     called from the header, none restated.  Acrobot's step and observation (RK4 and double sin / cos: 230 registers) are CALLS
+//     (mz_env_step_far): inlined they spilled inside the simulation loop; as calls the simulation loop touches no scratch and the
+//     save / reload of the f16 fragments sits once per move (profiles/mz_whole_env/kernel_resources.txt).
 //   * TREE_LDS trees use their own record: MzHot (N, first_child, value_sum, prior and q = reward + discount * value(),
 //     refreshed by the backup that changes it, so the walk does not divide value_sum / N again at every visit) plus one
 //     float of reward per node; sqrt(N) of the walk comes from a table filled with the same IEEE sqrt.  Same operations on
@@ -559,14 +567,14 @@ struct MzTrace {        // optional per-simulation outputs for the parity tests:
     float *reward, *probs, *value;
 };
 
-struct MzPlay {         // rz_mz_play_cartpole
-    int n_moves, row;                       // row = doubles per packed record = 4 + 4 + A
-    double *state;                          // [G][4]
+struct MzPlay {         // rz_mz_play_env (rz_mz_play_cartpole)
+    int n_moves, row;                       // row = doubles per packed record = D + 4 + A
+    double *state;                          // [G][Env::kState]
     long long *steps, *episode;             // [G]
     unsigned long long env_seed, noise_seed;
     double noise_frac, inv_temperature;     // inv_temperature <= 0: arg-max of the visit counts
     float alpha;
-    // history on the device: every move's record -- obs (4) | action | reward | visits (A) | root value | done -- goes
+    // history on the device: every move's record -- obs (D) | action | reward | visits (A) | root value | done -- goes
     // to ring[environment][step % hist]; when an episode ends, its records are copied into `arena` as one contiguous
     // run and (environment, end step, length, first arena row) is appended to `entries`: the host reads finished
     // episodes, not moves
@@ -579,17 +587,20 @@ struct MzPlay {         // rz_mz_play_cartpole
     long long *counters;                    // [0] arena rows claimed, [1] entries, [2] episodes that did not fit (row -1)
     long long *entries;                     // [max_entries][4]
     long long max_entries;
+    long long max_episode_steps;            // the time limit of an episode (CartPole-v1: 500)
 };
 
 // LDS of k_mz_search in bytes: activations, reductions, head weights, per-game scalars, paths, log table (+ the trees)
-__host__ __device__ inline int mz_search_fixed_floats() {
+// `w1_cols`: dyn1's action columns kept in LDS -- 2, or the action count of a whole-move environment with more (mz_w1_cols)
+__host__ __device__ inline int mz_search_fixed_floats(int w1_cols) {
     return kMzKX * kMzTile + (kMzH * kMzTile + 128) + kMzRedRows * kMzWaves * kMzTile + 16 + kMzHeadRows * kMzH + kMzObs * kMzTile + 16 +
-           kMzTile * 16 +                  // (+ the environments of whole MOVES: 7 doubles per game, 8 reserved)
-           2 * kMzH + kMzTile;             // (+ dyn1's action columns [2 actions][unit] and the games' actions: the f16 layers of whole
+           kMzTile * 16 +                  // (+ the environments of whole MOVES: kState + 3 doubles per game, 8 reserved)
+           w1_cols * kMzH + kMzTile;       // (+ dyn1's action columns [action][unit] and the games' actions: the f16 layers of whole
                                            // MOVES; every byte counts -- two workgroups of 16 games share a CU's 160 KB with 1.5 KB to spare)
 }
-__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds) {
-    int bytes = mz_search_fixed_floats() * 4 + gpw * path_stride * 4;
+__host__ __device__ constexpr int mz_w1_cols(bool whole_moves, int n_actions) { return whole_moves && n_actions > 2 ? n_actions : 2; }
+__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols) {
+    int bytes = mz_search_fixed_floats(w1_cols) * 4 + gpw * path_stride * 4;
     bytes = (bytes + 15) / 16 * 16;
     bytes += 2 * (((n_sims_cfg + 2) * 8 + 15) / 16 * 16);   // log and sqrt tables
     if (tree_lds) bytes += gpw * (cap + 1) * (int)sizeof(MzHot) + (gpw * (cap + 1) * 4 + 15) / 16 * 16;   // records (+ a spare per game) + rewards
@@ -640,13 +651,38 @@ __device__ __forceinline__ float mz_head_partial(const mz_f32x4 &p, const float 
     return mz_rowsum(s, l);
 }
 
-// MAXA: the action count the per-action loops are unrolled for (register arrays of that size): 8 in general, 2 for whole MOVES --
-// CartPole has two actions, and with 8-entry arrays the MOVES variants do not fit the 256 registers of two workgroups per CU
-// (200 bytes of scratch per lane, ~20 scratch loads inside every simulation's serial chain)
-template <bool TREE_LDS, bool MOVES, int MAXA = (MOVES ? 2 : kMzMaxA)>
+// the environment step and observation of a whole move OUT of line, for the environments MzFarStep names: Acrobot's RK4 over double
+// sin / cos takes 230 registers of its own, and inlined into k_mz_search they come out of the simulation loop's budget (the f16 weight
+// fragments are live across the move: scratch loads inside the loop).  A call keeps the two apart: what is live across it is saved
+// and reloaded in the move stage, once per move.
+template <typename Env>
+struct MzFarStep {
+    static constexpr bool value = false;
+};
+template <>
+struct MzFarStep<rzmze::EnvAcrobot> {
+    static constexpr bool value = true;
+};
+template <typename Env>
+__device__ __noinline__ int mz_env_step_far(typename Env::State &c, int action, long long max_episode_steps, double *reward) {
+    return Env::step(c, action, max_episode_steps, reward);
+}
+template <typename Env>
+__device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, float *obs) {
+    Env::observe(c, obs);
+}
+
+// Env: the environment of whole MOVES (a trait of rz_mz_env.h; unused without MOVES).
+// MAXA: the action count the per-action loops are unrolled for (register arrays of that size): 8 in general, Env::kActions for whole
+// MOVES -- 2 for CartPole, 3 for Acrobot: with 8-entry arrays the MOVES variants do not fit the 256 registers of two workgroups per
+// CU (200 bytes of scratch per lane, ~20 scratch loads inside every simulation's serial chain)
+template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA)>
 __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
-    constexpr int AFIX = MOVES ? 2 : 0;   // whole MOVES are CartPole's: two actions (rz_mz_play_cartpole checks)
+    constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
+    constexpr int W1C = mz_w1_cols(MOVES, Env::kActions);
+    constexpr bool FAR_STEP = MzFarStep<Env>::value;   // the step and the observation as calls (mz_env_step_far)
+    static_assert(Env::kState + 3 <= 8 && Env::kObs <= kMzObs && Env::kActions <= kMzMaxA, "the LDS record, OBS and the action arrays");
     const int A = AFIX > 0 ? AFIX : E.n_actions, KX = kMzH + A;
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, n = l & 15, q = l >> 4;
     const int g0 = blockIdx.x * gpw;
@@ -657,13 +693,13 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     float *HW = HB + 16;                             // [10][64]: rew2 / val / pol weights
     float *OBS = HW + kMzHeadRows * kMzH;            // [8][16]: observations, [k][game] (MOVES)
     int *Gleaf = reinterpret_cast<int *>(OBS + kMzObs * kMzTile);   // [16]
-    // MOVES: the environments (x, x_dot, theta, theta_dot, steps, episode, episode start) wait in LDS between a move's first and
+    // MOVES: the environments (Env::kState doubles of state, steps, episode, episode start) wait in LDS between a move's first and
     // last stage -- 14 registers that the simulations in between would otherwise carry
     double *ENV = reinterpret_cast<double *>(Gleaf + 16);           // [16][8]
-    float *W1A = reinterpret_cast<float *>(ENV + kMzTile * 8);       // [2][64]: dyn1's weights of the one-hot action rows (F16: two actions)
-    int *Gact = reinterpret_cast<int *>(W1A + 2 * kMzH);             // [16]: the action of the edge into each game's leaf (F16)
+    float *W1A = reinterpret_cast<float *>(ENV + kMzTile * 8);       // [W1C][64]: dyn1's weights of the one-hot action rows (F16)
+    int *Gact = reinterpret_cast<int *>(W1A + W1C * kMzH);           // [16]: the action of the edge into each game's leaf (F16)
     int32_t *PATH = Gact + kMzTile;                                  // [gpw][path_stride]
-    unsigned char *pp = mz_lds + (mz_search_fixed_floats() * 4 + gpw * E.path_stride * 4 + 15) / 16 * 16;
+    unsigned char *pp = mz_lds + (mz_search_fixed_floats(W1C) * 4 + gpw * E.path_stride * 4 + 15) / 16 * 16;
     double *PBL = reinterpret_cast<double *>(pp);    // [n_sims + 2]: the host's log table
     pp += ((E.n_sims + 2) * 8 + 15) / 16 * 16;
     double *SQT = reinterpret_cast<double *>(pp);    // [n_sims + 2]: sqrt(n)
@@ -710,8 +746,8 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         frag(M.dyn2_w, sw2, f2);
         frag(M.rew1_w, swr, fr);
         frag(M.pre1_w, swp, fp);
-        static_assert(!F16 || AFIX == 2, "the f16 layers are built for CartPole's two actions");
-        for (int i = tid; i < 2 * kMzH; i += 64 * kMzWaves) W1A[i] = M.dyn1_w[kMzH * kMzH + i];   // rows 64, 65 of [k][unit]
+        static_assert(!F16 || AFIX == W1C || AFIX < 2, "one column of dyn1 per action of the environment");
+        for (int i = tid; i < AFIX * kMzH; i += 64 * kMzWaves) W1A[i] = M.dyn1_w[kMzH * kMzH + i];   // rows 64 .. 64 + A - 1 of [k][unit]
     } else {
 #pragma unroll
         for (int s = 0; s < kMzKX / 4; ++s) {
@@ -790,23 +826,31 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     int top = 0, depth = 0;
     double lo = 0.0, hi = 0.0;
     double *env_g = ENV + 8 * ge;
-    auto env_load = [&](rzmze::MzCartPole &c, long long &ep0) {
-        c = rzmze::MzCartPole{env_g[0], env_g[1], env_g[2], env_g[3], __double_as_longlong(env_g[4]), __double_as_longlong(env_g[5])};
-        ep0 = __double_as_longlong(env_g[6]);
+    constexpr int KS = Env::kState;   // the LDS record: state | steps | episode | episode start
+    typedef typename Env::State EnvState;
+    auto env_load = [&](EnvState &c, long long &ep0) {
+        Env::load(c, env_g, __double_as_longlong(env_g[KS]), __double_as_longlong(env_g[KS + 1]));
+        ep0 = __double_as_longlong(env_g[KS + 2]);
     };
-    auto env_store = [&](const rzmze::MzCartPole &c, long long ep0) {   // (the four lanes of a quad write the same values)
-        env_g[0] = c.x;
-        env_g[1] = c.x_dot;
-        env_g[2] = c.theta;
-        env_g[3] = c.theta_dot;
-        env_g[4] = __longlong_as_double(c.steps);
-        env_g[5] = __longlong_as_double(c.episode);
-        env_g[6] = __longlong_as_double(ep0);
+    auto env_store = [&](const EnvState &c, long long ep0) {   // (the four lanes of a quad write the same values)
+        Env::store(c, env_g);
+        env_g[KS] = __longlong_as_double(c.steps);
+        env_g[KS + 1] = __longlong_as_double(c.episode);
+        env_g[KS + 2] = __longlong_as_double(ep0);
+    };
+    // the observation of `c` into column `ge` of OBS (rows past Env::kObs stay zero, as rep1_w's rows past obs_dim)
+    auto env_observe = [&](const EnvState &c) {
+        float o[Env::kObs];
+        if constexpr (FAR_STEP) mz_env_observe_far<Env>(c, o);
+        else Env::observe(c, o);
+#pragma unroll
+        for (int i = 0; i < Env::kObs; ++i) OBS[i * kMzTile + ge] = o[i];
     };
     if (mine) {
         if (MOVES) {
-            env_store(rzmze::MzCartPole{P.state[4 * g], P.state[4 * g + 1], P.state[4 * g + 2], P.state[4 * g + 3], P.steps[g], P.episode[g]},
-                      P.ep_start[g]);
+            EnvState c0;
+            Env::load(c0, P.state + (long long)KS * g, P.steps[g], P.episode[g]);
+            env_store(c0, P.ep_start[g]);
         } else {
             top = E.top[g];
             lo = E.vmin[g];
@@ -831,10 +875,10 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     int32_t *path = PATH + (ge < gpw ? ge : 0) * E.path_stride;
     __syncthreads();
     if (MOVES && mine) {   // (after the zero fill of OBS)
-        OBS[0 * kMzTile + ge] = (float)env_g[0];
-        OBS[1 * kMzTile + ge] = (float)env_g[1];
-        OBS[2 * kMzTile + ge] = (float)env_g[2];
-        OBS[3 * kMzTile + ge] = (float)env_g[3];
+        EnvState c0;
+        long long ep0;
+        env_load(c0, ep0);
+        env_observe(c0);
     }
 
     // ---- the pieces the initial inference and a simulation share
@@ -1162,7 +1206,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     }
         if (MOVES && mine) {
             // ---- the move: action ~ visits ^ (1 / T) (select_action), record for the host, environment step
-            rzmze::MzCartPole env;
+            EnvState env;
             long long ep_start;
             env_load(env, ep_start);
             double wgt[MAXA], total;
@@ -1180,21 +1224,22 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             const long long t = P.t0 + move;
             double *ring_g = P.ring + (long long)g * P.hist * P.row;
             double *rec = ring_g + (t % P.hist) * P.row;
-            const rzmze::RecordLayout R = rzmze::record_layout(rzmze::EnvCartPole::kObs, A);
-            double last[6 + MAXA];
-            last[0] = (double)(float)env.x;   // the observation the search started from
-            last[1] = (double)(float)env.x_dot;
-            last[2] = (double)(float)env.theta;
-            last[3] = (double)(float)env.theta_dot;
+            constexpr rzmze::RecordLayout R = rzmze::record_layout(Env::kObs, MAXA);   // (MOVES: MAXA is the environment's action count)
+            constexpr int NLAST = R.root_value;   // obs | action | reward | visits
+            double last[NLAST];
+#pragma unroll
+            for (int i = 0; i < Env::kObs; ++i) last[i] = (double)OBS[i * kMzTile + ge];   // the observation the search started from
             last[R.action] = (double)action;
-            last[R.reward] = 1.0;
 #pragma unroll
             for (int a = 0; a < MAXA; ++a) last[R.visits + a] = (double)visits[a];
             const double root_value = root_sum / (double)(root_n > 1 ? root_n : 1);
-            const int done = rzmze::cartpole_step(env, action, 500);
+            double step_reward = 0.0;
+            const int done = FAR_STEP ? mz_env_step_far<Env>(env, action, P.max_episode_steps, &step_reward)
+                                      : Env::step(env, action, P.max_episode_steps, &step_reward);
+            last[R.reward] = step_reward;
             if (lead) {
 #pragma unroll
-                for (int c = 0; c < 6 + MAXA; ++c)
+                for (int c = 0; c < NLAST; ++c)
                     if (c < R.root_value) rec[c] = last[c];
                 rec[R.root_value] = root_value;
                 rec[R.done] = done ? 1.0 : 0.0;
@@ -1216,7 +1261,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                     if (lead) {
                         double *dst = P.arena + (off + len - 1) * P.row;
 #pragma unroll
-                        for (int c = 0; c < 6 + MAXA; ++c)
+                        for (int c = 0; c < NLAST; ++c)
                             if (c < R.root_value) dst[c] = last[c];
                         dst[R.root_value] = root_value;
                         dst[R.done] = 1.0;
@@ -1226,12 +1271,9 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                 env.episode += 1;
                 int g_reset = g;
                 asm volatile("" : "+v"(g_reset));   // (as `ns` above: the reset's key is formed when an episode ends)
-                rzmze::cartpole_reset(env, P.env_seed, g_reset);
+                Env::reset(env, P.env_seed, g_reset);
             }
-            OBS[0 * kMzTile + ge] = (float)env.x;
-            OBS[1 * kMzTile + ge] = (float)env.x_dot;
-            OBS[2 * kMzTile + ge] = (float)env.theta;
-            OBS[3 * kMzTile + ge] = (float)env.theta_dot;
+            env_observe(env);
             env_store(env, ep_start);
         }
         MZ_TICK(14);
@@ -1246,13 +1288,11 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         E.vmax[g] = hi;
         E.depth[g] = depth;
         if (MOVES) {
-            P.state[4 * g] = env_g[0];
-            P.state[4 * g + 1] = env_g[1];
-            P.state[4 * g + 2] = env_g[2];
-            P.state[4 * g + 3] = env_g[3];
-            P.steps[g] = __double_as_longlong(env_g[4]);
-            P.episode[g] = __double_as_longlong(env_g[5]);
-            P.ep_start[g] = __double_as_longlong(env_g[6]);
+#pragma unroll
+            for (int i = 0; i < KS; ++i) P.state[KS * g + i] = env_g[i];
+            P.steps[g] = __double_as_longlong(env_g[KS]);
+            P.episode[g] = __double_as_longlong(env_g[KS + 1]);
+            P.ep_start[g] = __double_as_longlong(env_g[KS + 2]);
         }
     }
     if (TREE_LDS) {
@@ -1305,6 +1345,7 @@ struct rz_muzero {
     MzModel model = {};          // rz_mz_load_model
     float *d_model = nullptr;    // one allocation behind the pointers above
     bool model_loaded = false, representation_loaded = false;
+    int rep_obs_dim = 0;         // rz_mz_load_representation: the observation features of the loaded rep1
     bool f16_ok = false;   // rz_mz_load_model: finite weights and a finite bound on relu(dyn1): whole MOVES may run their layers on the f16 pipe
     float *d_rep = nullptr;      // rz_mz_load_representation
     int n_cus = 256;             // of cfg.device
@@ -1553,31 +1594,34 @@ int rz_mz_load_representation(rz_muzero *e, const float *const *h_params, int32_
     e->model.rep2_w = e->d_rep + off[2];
     e->model.rep2_b = e->d_rep + off[3];
     e->representation_loaded = true;
+    e->rep_obs_dim = obs_dim;
     return RZ_OK;
 }
 
 // What a launch of k_mz_search looks like for the engine's current shape: mz_launch_search launches exactly this, and
 // rz_mz_search_plan reports it (the tests prove through it which instantiation they ran).  `whole_moves`: the MOVES
-// instantiations (rz_mz_play_cartpole); they share the LDS layout of the move-by-move search, so the plan is the same today.
+// instantiations (rz_mz_play_env); they share the LDS layout of the move-by-move search up to dyn1's action columns -- one per action
+// past the second (mz_w1_cols) -- so the plan is the same at two actions and is the engine's action count's beyond.
 struct MzPlan {
     int gpw;        // games per workgroup
     bool tree_lds;  // trees in LDS (k_mz_search<true, ...>) or in HBM (<false, ...>)
     int lds;        // dynamic LDS bytes of the launch
 };
 static MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves) {
-    (void)whole_moves;
     MzPlan p;
+    const int w1c = mz_w1_cols(whole_moves, e->cfg.n_actions <= kMzMaxA ? e->cfg.n_actions : kMzMaxA);
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
     // other, so the 16 columns of a tile are filled first (profiles/r02/muzero_search_shape.txt)
     p.gpw = e->games_per_wg > 0 ? e->games_per_wg : kMzMaxGpw;
     // the trees go to LDS when two workgroups still fit on a CU
     const MzDev &D = e->dev;
-    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true) <= 80 * 1024;
-    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds);
+    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true, w1c) <= 80 * 1024;
+    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds, w1c);
     return p;
 }
 
-static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, void *stream) {
+// play != nullptr: whole moves of the environment `kind` (checked by rz_mz_play_env)
+static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, int kind, void *stream) {
     const MzPlan plan = mz_search_plan(e, play != nullptr);
     const int gpw = plan.gpw, lds = plan.lds;
     const bool tree_lds = plan.tree_lds;
@@ -1585,7 +1629,10 @@ static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const
     const dim3 grid((unsigned)((e->cfg.n_games + gpw - 1) / gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
     hipStream_t st = (hipStream_t)stream;
-    if (play != nullptr) {
+    if (play != nullptr && kind == RZ_MZ_ENV_ACROBOT) {
+        if (tree_lds) k_mz_search<true, true, rzmze::EnvAcrobot><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+        else k_mz_search<false, true, rzmze::EnvAcrobot><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+    } else if (play != nullptr) {
         if (tree_lds) k_mz_search<true, true><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
         else k_mz_search<false, true><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
     } else {
@@ -1604,13 +1651,29 @@ int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace
     const bool all = d_trace_parent && d_trace_action && d_trace_leaf && d_trace_reward && d_trace_probs && d_trace_value;
     if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
     const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
-    return mz_launch_search(e, d_hidden, n_sims, T, nullptr, stream);
+    return mz_launch_search(e, d_hidden, n_sims, T, nullptr, 0, stream);
 }
 
-int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_cartpole_play *play, void *stream) {
+// whole moves of the environment `kind`: the checks and the launch behind rz_mz_play_env and rz_mz_play_cartpole
+static int mz_play_launch(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_whole_play *play, void *stream) {
     RZ_ENTER(mz_ready, e);
+    int env_actions = 0, env_obs = 0;
+    if (kind == RZ_MZ_ENV_CARTPOLE) {
+        env_actions = rzmze::EnvCartPole::kActions;
+        env_obs = rzmze::EnvCartPole::kObs;
+    } else if (kind == RZ_MZ_ENV_ACROBOT) {
+        env_actions = rzmze::EnvAcrobot::kActions;
+        env_obs = rzmze::EnvAcrobot::kObs;
+    } else {
+        return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
+    }
     if (!e->model_loaded || !e->representation_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model and rz_mz_load_representation first");
-    if (e->cfg.n_actions != 2) return rz_fail(RZ_ERR_ARG, "CartPole has 2 actions");
+    if (e->cfg.n_actions != env_actions) {
+        if (kind == RZ_MZ_ENV_CARTPOLE) return rz_fail(RZ_ERR_ARG, "CartPole has 2 actions");
+        return rz_fail(RZ_ERR_ARG, "the tree has %d actions, the environment %d", e->cfg.n_actions, env_actions);
+    }
+    if (e->rep_obs_dim != env_obs)
+        return rz_fail(RZ_ERR_ARG, "the loaded representation takes obs_dim %d observations, the environment gives %d", e->rep_obs_dim, env_obs);
     if (!e->f16_ok)
         return rz_fail(RZ_ERR_ARG, "the model has non-finite weights: whole moves run their layers on the f16 matrix pipe and need finite "
                                    "bounds (use the move-by-move search, rz_mz_search / fused_moves=False)");
@@ -1619,8 +1682,10 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
     if (!play->d_state || !play->d_steps || !play->d_episode || !play->d_episode_start || !play->d_ring || !play->d_arena ||
         !play->d_counters || !play->d_entries)
         return rz_fail(RZ_ERR_ARG, "NULL environment / history pointer");
-    if (play->ring_steps < 500 + n_moves || play->arena_rows < 1 || play->max_entries < (int64_t)e->cfg.n_games * n_moves || play->first_step < 0)
-        return rz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (500 steps) + the launch, max_entries one entry per environment and move");
+    if (play->max_episode_steps < 1) return rz_fail(RZ_ERR_ARG, "max_episode_steps must be >= 1");
+    if (play->ring_steps < play->max_episode_steps + n_moves || play->arena_rows < 1 || play->max_entries < (int64_t)e->cfg.n_games * n_moves || play->first_step < 0)
+        return rz_fail(RZ_ERR_ARG, "ring_steps must cover an episode (%lld steps) + the launch, max_entries one entry per environment and move",
+                       (long long)play->max_episode_steps);
     if (!(play->dirichlet_alpha > 0.0) || play->noise_frac < 0.0 || play->noise_frac > 1.0) return rz_fail(RZ_ERR_ARG, "dirichlet_alpha must be > 0, noise_frac in [0, 1]");
     // mz_gamma floors a draw at 1e-30: P(Gamma(alpha, 1) < 1e-30) is 1.05e-3 at alpha 0.1 and 0.128 at 0.03, and a move whose draws are
     // ALL floored gets uniform noise where Dirichlet(alpha) is almost one-hot (tests/test_noise_streams_host.py states the figures)
@@ -1628,7 +1693,7 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
         return rz_fail(RZ_ERR_ARG, "dirichlet_alpha must be >= 0.1: below it the root noise's float32 draws reach their 1e-30 floor too often");
     MzPlay p = {};
     p.n_moves = n_moves;
-    p.row = 4 + 4 + e->cfg.n_actions;
+    p.row = rzmze::record_layout(env_obs, env_actions).row;
     p.state = play->d_state;
     p.steps = reinterpret_cast<long long *>(play->d_steps);
     p.episode = reinterpret_cast<long long *>(play->d_episode);
@@ -1646,8 +1711,38 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
     p.counters = reinterpret_cast<long long *>(play->d_counters);
     p.entries = reinterpret_cast<long long *>(play->d_entries);
     p.max_entries = play->max_entries;
+    p.max_episode_steps = play->max_episode_steps;
     const MzTrace T = {};
-    return mz_launch_search(e, d_hidden, n_sims, T, &p, stream);
+    return mz_launch_search(e, d_hidden, n_sims, T, &p, kind, stream);
+}
+
+int rz_mz_play_env(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_whole_play *play, void *stream) {
+    return mz_play_launch(e, kind, d_hidden, n_sims, n_moves, play, stream);
+}
+
+// CartPole-v1 through the same launcher: its play record + the limit of 500 steps
+int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_cartpole_play *play, void *stream) {
+    if (play == nullptr) return mz_play_launch(e, RZ_MZ_ENV_CARTPOLE, d_hidden, n_sims, n_moves, nullptr, stream);
+    rz_mz_whole_play p = {};
+    p.d_state = play->d_state;
+    p.d_steps = play->d_steps;
+    p.d_episode = play->d_episode;
+    p.d_episode_start = play->d_episode_start;
+    p.env_seed = play->env_seed;
+    p.noise_seed = play->noise_seed;
+    p.noise_frac = play->noise_frac;
+    p.dirichlet_alpha = play->dirichlet_alpha;
+    p.temperature = play->temperature;
+    p.d_ring = play->d_ring;
+    p.ring_steps = play->ring_steps;
+    p.first_step = play->first_step;
+    p.d_arena = play->d_arena;
+    p.arena_rows = play->arena_rows;
+    p.d_counters = play->d_counters;
+    p.d_entries = play->d_entries;
+    p.max_entries = play->max_entries;
+    p.max_episode_steps = 500;
+    return mz_play_launch(e, RZ_MZ_ENV_CARTPOLE, d_hidden, n_sims, n_moves, &p, stream);
 }
 
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup) {
@@ -1703,7 +1798,7 @@ int rz_mz_error_flags(rz_muzero *e, int32_t *flags) {
 
 // ------------------------------------------------------------------ moves kept on the device, generic over the environment
 // The layer between a finished search and the replay -- action draw, environment step, record, hand-over of finished episodes --
-// as launches of their own behind rz_mz_search (k_mz_search is not involved: its MOVES stages stay CartPole's, under the same rules).
+// as launches of their own behind rz_mz_search (k_mz_search is not involved: its MOVES stages are the other route, under the same rules).
 // An environment is a trait (rz_mz_env.h); k_mz_env_step and k_mz_env_move are instantiated once per kind.
 namespace {
 

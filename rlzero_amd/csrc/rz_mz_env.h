@@ -6,8 +6,8 @@
 // expressions in the order the restatements write them: on one host, with one libm, the two give the same bits.
 //
 // An environment is a TRAIT: a struct of static functions over its state record -- kState doubles, kObs floats of an observation,
-// kActions actions, load / store, reset, step, observe -- and one kernel template serves every environment.  The whole-move search
-// is built for CartPole and calls its functions directly.
+// kActions actions, load / store, reset, step, observe -- and one kernel template serves every environment: k_mz_env_step, k_mz_env_move
+// and the MOVES stages of the whole-move search, k_mz_search<TREE_LDS, MOVES, Env>.
 //
 // CartPole-v1: Gymnasium classic_control/cartpole.py v0.29 (Euler integrator, tau 0.02 s, force 10 N, the episode ends at |x| > 2.4
 // or |theta| > 12 degrees, reward 1 per step), auto-reset -- the device twin of rlzero_amd/muzero/cartpole.py.

@@ -8,8 +8,9 @@ Per move (arXiv:1911.08265v2 appendix: ``play_game`` / ``run_mcts`` / ``select_a
 Three routes (``MuZeroSelfPlay(fused=..., fused_moves=...)``): the step-by-step one above (tree kernels + the model's
 small MLPs on PyTorch-ROCm, one hipGraph per simulation); the search of a move in ONE launch with the model evaluated
 inside the kernel (``rz_mz_search``); and whole MOVES in one launch -- initial inference, noise, search, action draw,
-CartPole step, episode history on the device (``rz_mz_play_cartpole``), the host reading finished episodes a launch
-behind the GPU.  The last is the default for a ``CartPoleBatch`` environment and a hidden size of 64.
+environment step, episode history on the device (``rz_mz_play_cartpole``; ``rz_mz_play_env`` for every kind the library knows),
+the host reading finished episodes a launch behind the GPU.  The last is the default for a ``CartPoleBatch`` environment and a
+hidden size of 64, and runs for an ``AcrobotBatch`` with ``fused_moves=True``.
 A fourth route, device moves (``device_moves``), lies between the last two and serves every environment the library knows the
 rules of (``env.kind``; today CartPole and Acrobot): per move the torch initial inference, then launches only -- root noise from
 the whole moves' stream, roots, ``rz_mz_search``, and ``rz_mz_env_move``: action draw, environment step, record, hand-over of
@@ -200,7 +201,9 @@ class MuZeroSelfPlay(object):
         ``fused_moves``: whole MOVES in one launch (the MOVES stages of k_mz_search: initial inference, root noise, search,
         action draw, environment step; ``moves_per_launch`` of them per launch) -- the host only reads one packed record
         per environment and move, a chunk behind the GPU.  None = whenever ``fused`` holds and the environment is a
-        CartPoleBatch (the environment step is device code).  Its random draws (root noise, actions) come from the
+        CartPoleBatch.  True: for any environment of a kind the library knows (``env.kind`` in ``_hip.MZ_ENV_KINDS``: CartPole,
+        Acrobot -- k_mz_search<TREE_LDS, MOVES, Env>) when the fused search serves the model and the network's obs_dim and action
+        count are the environment's; otherwise a ``ValueError`` names what is missing.  Its random draws (root noise, actions) come from the
         kernel's counter-based stream keyed (seed, environment, episode, step), not from the torch generator.
         ``arena_rows``: records the per-launch arena of finished episodes holds (None = twice what a launch plays + a few
         long episodes; episodes that do not fit are read back from the device ring instead).
@@ -245,16 +248,31 @@ class MuZeroSelfPlay(object):
         self.fused = (net.hidden == 64 and self.n_actions <= 8) if fused is None else bool(fused)
         self._model_seen = None
         from .cartpole import CartPoleBatch
+        from .. import _hip
+        # whole moves: the default for a CartPoleBatch (unchanged); on request for every environment of a kind the library knows
         can_fuse_moves = self.fused and isinstance(env, CartPoleBatch) and net.obs_dim == 4 and self.n_actions == 2
         self.fused_moves = can_fuse_moves if fused_moves is None else bool(fused_moves)
         if self.fused_moves and not can_fuse_moves:
-            raise ValueError('fused_moves needs the fused search and a CartPoleBatch environment')
+            missing = None   # what whole moves miss here
+            if getattr(env, 'kind', None) not in _hip.MZ_ENV_KINDS:
+                missing = 'an environment of a kind the library knows the rules of (env.kind = %r; known: %s)' % (
+                    getattr(env, 'kind', None), ', '.join(sorted(_hip.MZ_ENV_KINDS)))
+            elif not self.fused:
+                missing = 'the fused search (it needs hidden size 64 and at most 8 actions, or fused=False was given)'
+            elif net.obs_dim != env.obs_dim:
+                missing = 'a network for the environment\'s observations (the network takes obs_dim %d, the environment gives %d)' % (
+                    net.obs_dim, env.obs_dim)
+            elif getattr(net, 'n_actions', self.n_actions) != env.n_actions:
+                missing = 'a network for the environment\'s actions (the network has %d actions, the environment %d)' % (
+                    net.n_actions, env.n_actions)
+            if missing is not None:
+                self.tree.close()
+                raise ValueError('fused_moves needs ' + missing)
         if self.fused_moves and not self.alpha >= self.MIN_FUSED_ALPHA:
             from .._hip import HipError
             self.tree.close()
             raise HipError('dirichlet_alpha must be >= 0.1: below it the root noise\'s float32 draws reach their 1e-30 floor too often '
                            '(root_dirichlet_alpha = %r; the move-by-move routes, fused_moves=False, take any alpha > 0)' % self.alpha)
-        from .. import _hip
         why_not = None   # why device moves cannot run here
         if not self.fused:
             why_not = 'the fused search does not serve this model (it needs hidden size 64 and at most 8 actions, or fused=False was given)'
@@ -288,7 +306,7 @@ class MuZeroSelfPlay(object):
         if self.fused_moves:
             self.sim_step_label = ('k_mz_search with its MOVES stages (whole moves in one launch: initial inference, root noise, '
                                    '%d simulations -- select, recurrent inference on the matrix pipe, expand + backup -- action draw, '
-                                   'CartPole step)' % self.n_sims)
+                                   '%s step)' % (self.n_sims, {'cartpole': 'CartPole', 'acrobot': 'Acrobot'}.get(env.kind, env.kind)))
         elif self.device_moves:
             self.sim_step_label = ('device moves: per move the torch initial inference, k_mz_root_noise, k_mz_init, k_mz_search (%d simulations in '
                                    'one launch) and k_mz_env_move (action draw, environment step, record, hand-over)' % self.n_sims)
@@ -530,9 +548,12 @@ class MuZeroSelfPlay(object):
             if self.search_events is not None:
                 ev = (t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True), n_moves)
                 ev[0].record()
-            if self.fused_moves:
+            if self.fused_moves and self.env.kind == 'cartpole':
                 self.tree.play_cartpole(self.hidden, self.n_sims, n_moves, self.env, self.noise_seed, self.noise_frac, self.alpha,
                                         self.temperature, (self._ring, self._ep_start_dev), self._t, arena, counters, entries)
+            elif self.fused_moves:
+                self.tree.play_env(self.hidden, self.n_sims, n_moves, self.env, self.noise_seed, self.noise_frac, self.alpha,
+                                   self.temperature, (self._ring, self._ep_start_dev), self._t, arena, counters, entries)
             else:
                 self._enqueue_device_moves(n_moves, arena, counters, entries)
             if ev is not None:

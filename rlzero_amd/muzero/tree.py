@@ -9,7 +9,7 @@ from ..engine import _ptr, check
 
 class MuZeroTree(object):
     """Search trees of ``n_games`` environments on one GPU.  Step by step (``select`` / ``expand_backup``) the learned
-    model is the caller's: see ``MuZeroSelfPlay.search`` for the simulation loop; ``search_fused`` and ``play_cartpole``
+    model is the caller's: see ``MuZeroSelfPlay.search`` for the simulation loop; ``search_fused``, ``play_cartpole`` and ``play_env``
     evaluate it inside the kernel (``load_model`` / ``load_representation`` first)."""
 
     def __init__(self, n_games, n_actions, n_sims, discount=0.997, pb_c_base=19652.0, pb_c_init=1.25,
@@ -60,7 +60,7 @@ class MuZeroTree(object):
     REPRESENTATION_PARAMS = ('rep1.weight', 'rep1.bias', 'rep2.weight', 'rep2.bias')
 
     def load_representation(self, net):
-        """Upload the representation layers h(o) of a MuZeroNet (for ``play_cartpole``); call again after every
+        """Upload the representation layers h(o) of a MuZeroNet (for ``play_cartpole`` / ``play_env``); call again after every
         optimiser step, like ``load_model``."""
         sd = net.state_dict()
         arrays = [sd[name].detach().to('cpu', self.torch.float32).contiguous().numpy() for name in self.REPRESENTATION_PARAMS]
@@ -86,6 +86,35 @@ class MuZeroTree(object):
             counters.data_ptr(), entries.data_ptr(), int(entries.shape[0]))
         check(self.lib.rz_mz_play_cartpole(self.handle, _ptr(hidden), int(n_sims), int(n_moves), ctypes.byref(play), self.stream()),
               'rz_mz_play_cartpole')
+
+    def play_env(self, hidden, n_sims, n_moves, env, noise_seed, noise_frac, alpha, temperature, history, first_step,
+                 arena, counters, entries, kind=None, max_episode_steps=None):
+        """``play_cartpole`` for the environment batch ``env`` of any kind the library knows (``env.kind``: 'cartpole' | 'acrobot';
+        rz_mz_play_env, k_mz_search<TREE_LDS, MOVES, Env>): ``n_moves`` whole moves in ONE launch.  A record is obs (D) | action |
+        reward | visits (A) | root value | done, D + 4 + A float64; ``history`` = (ring [G, ring_steps, D + 4 + A], episode_start
+        int64 [G]) with ring_steps >= max_episode_steps + n_moves; ``arena`` float64 [rows, D + 4 + A]; ``entries`` and ``counters``
+        (zeroed here) as ``play_cartpole``'s.  ``kind`` / ``max_episode_steps``: None = the environment's (``_hip.MZ_ENV_KINDS``).
+        The library refuses -- HipError, nothing launched -- an unknown kind, a tree or a loaded representation of another shape
+        than the environment's, alpha < 0.1 and a ring too small."""
+        ring, episode_start = history
+        kind = _hip.MZ_ENV_KINDS[env.kind] if kind is None else int(kind)
+        limit = int(env.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        t, G, row = self.torch, self.n_games, env.obs_dim + 4 + env.n_actions
+        if env.n_envs != G or ring.dim() != 3 or tuple(ring.shape[::2]) != (G, row) or tuple(episode_start.shape) != (G, ) \
+                or arena.dim() != 2 or arena.shape[1] != row or entries.dim() != 2 or entries.shape[1] != 4 or counters.numel() < 4 \
+                or tuple(env.state.shape) != (G, 4) or hidden.numel() < G * self.slots_per_game * 64:
+            raise ValueError('play_env: the ring, the arena, the entries, the states or the hidden states do not have the environment\'s shape')
+        for x, dtype in ((ring, t.float64), (arena, t.float64), (episode_start, t.int64), (counters, t.int64), (entries, t.int64)):
+            if x.dtype != dtype or not x.is_contiguous() or x.device.type != 'cuda':
+                raise ValueError('play_env: contiguous float64 / int64 tensors on the device are expected')
+        counters.zero_()
+        play = _hip.RzMzWholePlay(
+            env.state.data_ptr(), env.steps.data_ptr(), env.episode_dev.data_ptr(), episode_start.data_ptr(),
+            int(env.seed) & (2 ** 64 - 1), int(noise_seed) & (2 ** 64 - 1), float(noise_frac), float(alpha), float(temperature),
+            ring.data_ptr(), int(ring.shape[1]), 0, int(first_step), arena.data_ptr(), int(arena.shape[0]),
+            counters.data_ptr(), entries.data_ptr(), int(entries.shape[0]), limit)
+        check(self.lib.rz_mz_play_env(self.handle, kind, _ptr(hidden), int(n_sims), int(n_moves), ctypes.byref(play), self.stream()),
+              'rz_mz_play_env')
 
     def env_move(self, env, noise_seed, temperature, history, step, arena, counters, entries, obs_out):
         """The move behind a finished search (``search_fused`` on the current stream) for the environment batch ``env`` of a kind
@@ -207,7 +236,8 @@ class MuZeroTree(object):
         return nodes, top
 
     def search_plan(self, whole_moves):
-        """What a launch of ``search_fused`` (``whole_moves`` false) or ``play_cartpole`` (true) would be for the current shape
+        """What a launch of ``search_fused`` (``whole_moves`` false) or ``play_env`` / ``play_cartpole`` (true; for this tree's action
+        count) would be for the current shape
         (``set_search_shape``), from the host function the launch itself uses -> dict games_per_workgroup, tree_in_lds (bool),
         lds_bytes."""
         gpw, in_lds, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)

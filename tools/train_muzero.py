@@ -11,6 +11,7 @@ its ``tools/train_alphazero.py`` (a pipeline class with ``collect_selfplay_data`
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --prioritized-replay   # steps drawn by |value - return|
     python tools/train_muzero.py --envs 256 --iterations 60 --device-replay --fused-learner   # and every update is three HIP launches
     python tools/train_muzero.py --env acrobot --envs 256 --iterations 60 --device-replay --fused-learner   # Acrobot-v1, moves kept on the device
+    python tools/train_muzero.py --env acrobot --whole-moves --envs 256 --iterations 60 --device-replay --fused-learner   # ... whole moves in one launch
 """
 import argparse
 import os
@@ -43,7 +44,7 @@ class MuZeroPipeline(object):
     def __init__(self, n_envs=256, n_sims=50, unroll_steps=5, td_steps=10, discount=0.997, batch_size=256,
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
                  reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False, env='cartpole',
-                 max_episode_steps=None):
+                 max_episode_steps=None, whole_moves=None):
         """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
@@ -56,7 +57,10 @@ class MuZeroPipeline(object):
         them and reads only the last result.  Works with either buffer and with every option above.
         ``env``: 'cartpole' (CartPoleBatch: whole moves in one launch) or 'acrobot' (AcrobotBatch: 3 actions, 6 observations, reward -1
         per step; moves kept on the device, MuZeroSelfPlay(device_moves=...)).  The agent, the buffers, Reanalyse and the learner are
-        built for the environment's shape.  ``max_episode_steps`` (Acrobot only): its time limit, None = the environment's 500."""
+        built for the environment's shape.  ``max_episode_steps`` (Acrobot only): its time limit, None = the environment's 500.
+        ``whole_moves``: True asks for whole moves in one launch (MuZeroSelfPlay(fused_moves=True)) whatever the environment, and is
+        refused with a ValueError where they cannot run; None = the environment's default route (CartPole: whole moves, Acrobot:
+        device moves)."""
         if env not in ENVIRONMENTS:
             raise ValueError('unknown environment %r (known: %s)' % (env, ', '.join(ENVIRONMENTS)))
         if max_episode_steps is not None and env == 'cartpole':
@@ -79,7 +83,8 @@ class MuZeroPipeline(object):
             self.env = CartPoleBatch(n_envs, device, seed=seed)
         else:
             self.env = AcrobotBatch(n_envs, device, seed=seed, **({} if max_episode_steps is None else dict(max_episode_steps=max_episode_steps)))
-        self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed)
+        route = {} if whole_moves is None else dict(fused_moves=bool(whole_moves))
+        self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed, **route)
         self.device_replay = bool(device_replay)
         if self.device_replay:
             self.buffer = MuZeroDeviceReplay(self.agent.net.obs_dim, self.env.n_actions, 2000, int(self.env.max_episode_steps),
@@ -181,6 +186,8 @@ def build_parser():
     ap.add_argument('--env', choices=ENVIRONMENTS, default='cartpole',
                     help='the environment: CartPole-v1 (whole moves in one launch) or Acrobot-v1 (moves kept on the device)')
     ap.add_argument('--max-episode-steps', type=int, default=None, metavar='N', help='time limit of an Acrobot episode (default: 500)')
+    ap.add_argument('--whole-moves', action='store_true',
+                    help='whole moves in one launch for the chosen environment (CartPole\'s default; Acrobot: instead of device moves)')
     ap.add_argument('--envs', type=int, default=256)
     ap.add_argument('--sims', type=int, default=50)
     ap.add_argument('--iterations', type=int, default=60)
@@ -201,9 +208,9 @@ def build_parser():
     return ap
 
 
-if __name__ == '__main__':
+def main(argv=None):
     ap = build_parser()
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.reanalyse and not args.device_replay:
         ap.error(NEEDS_DEVICE_REPLAY)
     if args.prioritized_replay and not args.device_replay:
@@ -211,7 +218,12 @@ if __name__ == '__main__':
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
                           updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
                           prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta, fused_learner=args.fused_learner,
-                          env=args.env, max_episode_steps=args.max_episode_steps)
+                          env=args.env, max_episode_steps=args.max_episode_steps, whole_moves=True if args.whole_moves else None)
     pipe.run(args.iterations)
     if args.save:
         pipe.agent.save_model(args.save)
+    return pipe
+
+
+if __name__ == '__main__':
+    main()
