@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 42
+#define RZ_ABI_VERSION 43
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -795,6 +795,16 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
 int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace_parent, int32_t *d_trace_action,
                  int32_t *d_trace_leaf, float *d_trace_reward, float *d_trace_probs, float *d_trace_value, void *stream);
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup);
+/* The value transform (ABI 43; csrc/rz_mz_value.h): MuZero's invertible h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, eps = 0.001
+ * (arXiv:1911.08265v2 appendix F), for a model whose scalar reward and value heads are trained on h of their targets (the paper's
+ * categorical support is not built).  rz_mz_set_value_transform(e, 1): every launcher of k_mz_search -- rz_mz_search, rz_mz_play_env,
+ * rz_mz_play_cartpole -- takes the kernel's VT instantiation, in which wave 0 replaces the network's reward and value of a simulation by
+ * float32(h^-1(float64(.))) right after the heads are finished: before the trace arrays are written (they hold what entered the
+ * backup) and before expand + backup.  The tree, its MinMax bounds, the root value of a record, what Reanalyse writes back and the
+ * priorities therefore stay in raw units; the root's own predicted value is not used by the search and is not touched.  0 (the default):
+ * the instantiations without it, the code of ABI 42.  The step-by-step route (rz_mz_expand_backup) takes what the caller hands it: the
+ * caller applies the inverse.  No launch; takes effect with the next one. */
+int rz_mz_set_value_transform(rz_muzero *e, int32_t on);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action
@@ -1105,6 +1115,13 @@ int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n
 int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
                       float *h_policy, int32_t *h_length, void *stream);
 int rz_mz_replay_poll_errors(rz_mz_replay *r, int32_t *flags, void *stream);
+/* The value transform of the targets (ABI 43; csrc/rz_mz_value.h, csrc/rz_mz_target.h: unroll_row<VT>).  rz_mz_replay_set_value_transform(r, 1):
+ * the launch that forms a mini-batch -- rz_mz_replay_gather, rz_mz_replay_sample, and the gather behind a prioritized draw -- writes
+ * d_tv = float32(h(z)) and d_tr = float32(h(u)), z the fp64 n-step return exactly as formed without it and u the stored fp64
+ * reward; rows past the episode's end stay 0, and nothing else of a batch changes (k_mzr_gather<true> / k_mzr_sample<true>; 0, the
+ * default: the kernels of ABI 42).  The store keeps raw rewards and root values, and the priorities (k_mzr_prio) stay
+ * |root value - n-step return| in raw units.  No launch; takes effect with the next one. */
+int rz_mz_replay_set_value_transform(rz_mz_replay *r, int32_t on);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * MuZero Reanalyse (ABI 36; rz_mz_replay.hip: k_mzr_positions, k_mzr_update; rz_mz_target.h; rlzero_amd/muzero/reanalyse.py):

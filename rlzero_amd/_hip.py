@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -231,6 +231,7 @@ _SIGNATURES = {
     'rz_mz_load_model': (c_int, [P, POINTER(c_void_p), c_int32, c_int32]),
     'rz_mz_search': (c_int, [P, P, c_int32, P, P, P, P, P, P, P]),
     'rz_mz_set_search_shape': (c_int, [P, c_int32]),
+    'rz_mz_set_value_transform': (c_int, [P, c_int32]),
     'rz_mz_load_representation': (c_int, [P, POINTER(c_void_p), c_int32, c_int32, c_int32]),
     'rz_mz_play_cartpole': (c_int, [P, P, c_int32, c_int32, POINTER(RzMzCartPolePlay), P]),
     'rz_cartpole_step': (c_int, [P, P, P, P, c_int32, c_uint64, P, P, P, P, P]),
@@ -270,6 +271,7 @@ _SIGNATURES = {
     'rz_mz_replay_update': (c_int, [P, P, c_int64, P, P, P, c_int64, P]),
     'rz_mz_replay_read': (c_int, [P, c_int64, c_int64, P, P, P, P, P, P, P]),
     'rz_mz_replay_poll_errors': (c_int, [P, POINTER(c_int32), P]),
+    'rz_mz_replay_set_value_transform': (c_int, [P, c_int32]),
     'rz_mz_replay_enable_priorities': (c_int, [P, P]),
     'rz_mz_replay_refresh_priorities': (c_int, [P, P]),
     'rz_mz_replay_read_priorities': (c_int, [P, c_int64, c_int64, P, POINTER(c_int64), P]),

@@ -41,6 +41,7 @@
 #include "rlzero_hip.h"
 #include "rz_host.h"
 #include "rz_mz_env.h"
+#include "rz_mz_value.h"
 
 #pragma clang fp contract(off)
 
@@ -676,7 +677,9 @@ __device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, fl
 // MAXA: the action count the per-action loops are unrolled for (register arrays of that size): 8 in general, Env::kActions for whole
 // MOVES -- 2 for CartPole, 3 for Acrobot: with 8-entry arrays the MOVES variants do not fit the 256 registers of two workgroups per
 // CU (200 bytes of scratch per lane, ~20 scratch loads inside every simulation's serial chain)
-template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA)>
+// VT: the network's reward and value are in the transformed space of rz_mz_value.h (rz_mz_set_value_transform): wave 0 takes them
+// through value_h_inv before the trace and the backup, so the tree, its MinMax bounds and the root value stay in raw units.
+template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false>
 __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
     constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
@@ -1183,6 +1186,10 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             for (int u = 0; u < kMzWaves; ++u) reward += RED[(2 * kMzWaves + u) * kMzTile + ge];
             float value, probs[MAXA];
             finish_prediction(value, probs);
+            if constexpr (VT) {   // widened, inverted in fp64, rounded once
+                reward = (float)rzmzv::value_h_inv((double)reward);
+                value = (float)rzmzv::value_h_inv((double)value);
+            }
             MZ_TICK(11);
             if (mine) {
                 if (!MOVES && lead && T.reward != nullptr) {
@@ -1350,11 +1357,34 @@ struct rz_muzero {
     float *d_rep = nullptr;      // rz_mz_load_representation
     int n_cus = 256;             // of cfg.device
     int games_per_wg = 0;        // rz_mz_set_search_shape: 0 = chosen from n_games and n_cus
+    bool value_transform = false;   // rz_mz_set_value_transform: the launchers take the VT instantiations of k_mz_search
 };
 
 namespace {
 
 inline dim3 mz_grid(const rz_muzero *e) { return dim3((unsigned)((e->cfg.n_games + 127) / 128)); }
+
+// the instantiation of k_mz_search for a tree placement, a route, an environment and the value transform (MAXA: the kernel's default)
+template <bool TREE_LDS, bool MOVES, typename Env, bool VT>
+constexpr auto mz_search_kernel = k_mz_search<TREE_LDS, MOVES, Env, (MOVES ? Env::kActions : kMzMaxA), VT>;
+
+// the six launches of mz_launch_search, with (VT) or without the value transform
+template <bool VT>
+void mz_launch_kernels(rz_muzero *e, dim3 grid, dim3 block, int lds, hipStream_t st, bool tree_lds, float *d_hidden, int32_t n_sims, int gpw,
+                              const MzTrace &T, const MzPlay *play, bool moves, int kind) {
+    using rzmze::EnvAcrobot;
+    using rzmze::EnvCartPole;
+    if (moves && kind == RZ_MZ_ENV_ACROBOT) {
+        if (tree_lds) mz_search_kernel<true, true, EnvAcrobot, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+        else mz_search_kernel<false, true, EnvAcrobot, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+    } else if (moves) {
+        if (tree_lds) mz_search_kernel<true, true, EnvCartPole, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+        else mz_search_kernel<false, true, EnvCartPole, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+    } else {
+        if (tree_lds) mz_search_kernel<true, false, EnvCartPole, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+        else mz_search_kernel<false, false, EnvCartPole, VT><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
+    }
+}
 
 int mz_ready(rz_muzero *e) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
@@ -1555,7 +1585,13 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
         if (hipFuncSetAttribute((const void *)k_mz_search<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_mz_search<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
             hipFuncSetAttribute((const void *)k_mz_search<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
-            hipFuncSetAttribute((const void *)k_mz_search<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+            hipFuncSetAttribute((const void *)k_mz_search<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<true, false, rzmze::EnvCartPole, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<false, false, rzmze::EnvCartPole, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<true, true, rzmze::EnvCartPole, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<false, true, rzmze::EnvCartPole, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<true, true, rzmze::EnvAcrobot, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+            hipFuncSetAttribute((const void *)mz_search_kernel<false, true, rzmze::EnvAcrobot, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
             return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
     }
     if (hipMemcpy(e->d_model, host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -1629,16 +1665,8 @@ static int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const
     const dim3 grid((unsigned)((e->cfg.n_games + gpw - 1) / gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
     hipStream_t st = (hipStream_t)stream;
-    if (play != nullptr && kind == RZ_MZ_ENV_ACROBOT) {
-        if (tree_lds) k_mz_search<true, true, rzmze::EnvAcrobot><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
-        else k_mz_search<false, true, rzmze::EnvAcrobot><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
-    } else if (play != nullptr) {
-        if (tree_lds) k_mz_search<true, true><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
-        else k_mz_search<false, true><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, *play);
-    } else {
-        if (tree_lds) k_mz_search<true, false><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, none);
-        else k_mz_search<false, false><<<grid, block, lds, st>>>(e->dev, e->model, d_hidden, n_sims, gpw, T, none);
-    }
+    if (e->value_transform) mz_launch_kernels<true>(e, grid, block, lds, st, tree_lds, d_hidden, n_sims, gpw, T, play != nullptr ? play : &none, play != nullptr, kind);
+    else mz_launch_kernels<false>(e, grid, block, lds, st, tree_lds, d_hidden, n_sims, gpw, T, play != nullptr ? play : &none, play != nullptr, kind);
     return rz_launched("k_mz_search");
 }
 
@@ -1743,6 +1771,13 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
     p.max_entries = play->max_entries;
     p.max_episode_steps = 500;
     return mz_play_launch(e, RZ_MZ_ENV_CARTPOLE, d_hidden, n_sims, n_moves, &p, stream);
+}
+
+int rz_mz_set_value_transform(rz_muzero *e, int32_t on) {
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    if (on != 0 && on != 1) return rz_fail(RZ_ERR_ARG, "value transform: 0 (off) or 1 (on)");
+    e->value_transform = on != 0;
+    return RZ_OK;
 }
 
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup) {

@@ -96,10 +96,12 @@ __global__ __launch_bounds__(kThreads) void k_mzr_ingest(MzrDev R, const int32_t
 }
 
 // row k of output entry b from position `pos` of the episode in `slot` (length `len`, 0 <= pos < len)
+// VT (here and in the two kernels below; rz_mz_replay_set_value_transform): tv and tr through value_h (rz_mz_target.h: unroll_row<VT>)
+template <bool VT>
 __device__ __forceinline__ void mzr_emit(const MzrDev &R, const MzrOut &O, long long b, int k, int slot, int len, int pos, long long filler) {
     const long long base = (long long)slot * R.T;
     const int K = R.K, A = R.A, D = R.D;
-    const rzmzt::Row r = rzmzt::unroll_row(R.reward + base, R.root_value + base, R.action + base, len, pos, k, R.td, R.disc, filler);
+    const rzmzt::Row r = rzmzt::unroll_row<VT>(R.reward + base, R.root_value + base, R.action + base, len, pos, k, R.td, R.disc, filler);
     const long long o = b * (K + 1) + k;
     O.tv[o] = r.value;
     O.tr[o] = r.reward;
@@ -114,6 +116,7 @@ __device__ __forceinline__ void mzr_emit(const MzrDev &R, const MzrOut &O, long 
 }
 
 // A thread per (entry, unroll step).  draws int64 [n][K + 2]: episode (0 = the oldest held), position, the K filler actions.
+template <bool VT = false>
 __global__ __launch_bounds__(kThreads) void k_mzr_gather(MzrDev R, MzrOut O, const long long *__restrict__ draws, long long oldest, long long count,
                                                           long long n) {
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -135,11 +138,12 @@ __global__ __launch_bounds__(kThreads) void k_mzr_gather(MzrDev R, MzrOut O, con
         if (k == 0) atomicOr(R.err, kFlagBadIndex);
         return;
     }
-    mzr_emit(R, O, b, k, slot, len, (int)pos, k > 0 ? dr[2 + k - 1] : 0);
+    mzr_emit<VT>(R, O, b, k, slot, len, (int)pos, k > 0 ? dr[2 + k - 1] : 0);
 }
 
 // The same rows with the draws made here: counter c = b (K + 2) + j of update `step` (rz_mz_target.h: draw) -- j = 0 the episode,
 // uniform over the episodes held; j = 1 the position, uniform over that episode's length; j = 2 + k the filler action of step k.
+template <bool VT = false>
 __global__ __launch_bounds__(kThreads) void k_mzr_sample(MzrDev R, MzrOut O, unsigned long long seed, unsigned long long step, long long oldest,
                                                           long long count, long long n) {
     const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_mzr_sample(MzrDev R, MzrOut O, uns
     }
     const int pos = (int)rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 1), (uint64_t)len);
     const long long filler = k > 0 ? rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 2 + k - 1), (uint64_t)R.A) : 0;
-    mzr_emit(R, O, b, k, slot, len, pos, filler);
+    mzr_emit<VT>(R, O, b, k, slot, len, pos, filler);
 }
 
 // Reanalyse, the way out: entry i resolved to a physical (slot, position) in `where` int32 [n][2] and its stored observation in
@@ -384,6 +388,7 @@ struct rz_mz_replay {
     DevPool prio_pool;
     bool prio_on = false;
     bool prio_stale = false;   // a slot was written since the prefixes were formed: the next prioritized draw refreshes first
+    bool value_transform = false;   // rz_mz_replay_set_value_transform: mini-batches come from k_mzr_gather<true> / k_mzr_sample<true>
 };
 
 namespace {
@@ -627,7 +632,8 @@ int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *
         RZ_TRY(r->stage.upload(bytes, s));
         draws = (const long long *)r->stage.d;
     }
-    hipLaunchKernelGGL(k_mzr_gather, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
+    if (r->value_transform) hipLaunchKernelGGL(k_mzr_gather<true>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
+    else hipLaunchKernelGGL(k_mzr_gather<false>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
     return h_draws != nullptr ? r->stage.launched(s, "k_mzr_gather") : rz_launched("k_mzr_gather");
 }
 
@@ -638,9 +644,20 @@ int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n
     RZ_TRY(mr_outputs(r, n, O));
     if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     if (n == 0) return RZ_OK;
-    hipLaunchKernelGGL(k_mzr_sample, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
-                       (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
+    if (r->value_transform)
+        hipLaunchKernelGGL(k_mzr_sample<true>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
+                           (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
+    else
+        hipLaunchKernelGGL(k_mzr_sample<false>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
+                           (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
     return rz_launched("k_mzr_sample");
+}
+
+int rz_mz_replay_set_value_transform(rz_mz_replay *r, int32_t on) {
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
+    if (on != 0 && on != 1) return rz_fail(RZ_ERR_ARG, "value transform: 0 (off) or 1 (on)");
+    r->value_transform = on != 0;
+    return RZ_OK;
 }
 
 int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_t *d_draws, uint64_t seed, uint64_t step, int64_t n,

@@ -9,6 +9,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rz_mz_value.h"
+
 #if defined(__HIPCC__)
 #define RZT_FN __host__ __device__ __forceinline__
 #else
@@ -70,12 +72,20 @@ struct Row {
     int64_t action;     // actions[b, k - 1] (k > 0)
 };
 // `filler`: the action drawn for actions[b, k - 1] when step pos + k - 1 lies past the end
+// VT (rz_mz_replay_set_value_transform): the value and the reward of a row inside the episode go through rz_mz_value.h's value_h in
+// fp64 -- the n-step return exactly as formed without it, the stored reward -- before their one cast to float32; rows past the end
+// stay 0.  Nothing else of a row changes.
+template <bool VT>
+RZT_FN float target_f32(double x) {
+    return VT ? (float)rzmzv::value_h(x) : (float)x;
+}
+template <bool VT = false>
 RZT_FN Row unroll_row(const double *reward, const double *root_value, const int32_t *action, int len, int pos, int k, int td,
                       const double *disc, int64_t filler) {
     Row r;
     const int i = pos + k;
     const bool in = i < len;
-    r.value = in ? (float)value_target(reward, root_value, len, i, td, disc) : 0.0f;
+    r.value = in ? target_f32<VT>(value_target(reward, root_value, len, i, td, disc)) : 0.0f;
     r.mask = in ? 1.0f : 0.0f;
     r.policy_step = in ? i : -1;
     r.reward = 0.0f;
@@ -83,7 +93,7 @@ RZT_FN Row unroll_row(const double *reward, const double *root_value, const int3
     if (k > 0) {   // the action taken at step i - 1 and its reward: still real at i == len
         const bool prev = i - 1 < len;
         r.action = prev ? (int64_t)action[i - 1] : filler;
-        r.reward = prev ? (float)reward[i - 1] : 0.0f;
+        r.reward = prev ? target_f32<VT>(reward[i - 1]) : 0.0f;
     }
     return r;
 }

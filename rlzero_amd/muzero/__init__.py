@@ -7,11 +7,12 @@ from .acrobot import AcrobotBatch, acrobot_initial_states
 from .agent import MuZeroAgent
 from .cartpole import CartPoleBatch
 from .learner import MuZeroFusedLearner
-from .network import MuZeroNet
+from .network import MuZeroNet, inverse_value_transform, value_transform
 from .reanalyse import MuZeroReanalyser, mz_reanalyse_draws
 from .replay import MuZeroDeviceReplay, mz_prioritized_draws, mz_priority_weights, mz_replay_draws
 from .selfplay import MuZeroSelfPlay, ReplayBuffer
 from .tree import MuZeroTree
 
 __all__ = ['MuZeroAgent', 'CartPoleBatch', 'MuZeroNet', 'MuZeroSelfPlay', 'ReplayBuffer', 'MuZeroTree', 'MuZeroDeviceReplay', 'mz_replay_draws',
-           'MuZeroReanalyser', 'mz_reanalyse_draws', 'mz_priority_weights', 'mz_prioritized_draws', 'MuZeroFusedLearner', 'AcrobotBatch', 'acrobot_initial_states']
+           'MuZeroReanalyser', 'mz_reanalyse_draws', 'mz_priority_weights', 'mz_prioritized_draws', 'MuZeroFusedLearner', 'AcrobotBatch', 'acrobot_initial_states',
+           'value_transform', 'inverse_value_transform']

@@ -65,6 +65,8 @@ class MuZeroReanalyser(object):
         self.n_actions, self.obs_dim = replay.n_actions, replay.obs_dim
         if (net.obs_dim, net.n_actions) != (self.obs_dim, self.n_actions):
             raise ValueError('a net of obs_dim %d, %d actions on a buffer of %d, %d' % (net.obs_dim, net.n_actions, self.obs_dim, self.n_actions))
+        from .agent import check_value_transform
+        check_value_transform(net, replay)
         self.n_sims, self.batch = int(n_sims), int(batch)
         if self.batch < 1 or self.n_sims < 1:
             raise ValueError('batch and n_sims must be positive')
@@ -72,6 +74,10 @@ class MuZeroReanalyser(object):
         self.step = 0   # the next refresh ``reanalyse_sample`` draws without a ``step``
         self.fused = (net.hidden == 64 and self.n_actions <= 8) if fused is None else bool(fused)
         self.tree = MuZeroTree(self.batch, self.n_actions, self.n_sims, discount, pb_c_base, pb_c_init, device=str(self.device))
+        # the net's flag (MuZeroNet(value_transform=True)): the search inverts the heads, so what is written back is a RAW root value
+        self.value_transform = bool(getattr(net, 'value_transform', False))
+        if self.value_transform:
+            self.tree.set_value_transform(True)
         kw = dict(device=self.device)
         self.hidden = torch.zeros((self.batch, self.tree.slots_per_game, net.hidden), dtype=torch.float32, **kw)
         self.rows = torch.arange(self.batch, **kw)
@@ -108,6 +114,9 @@ class MuZeroReanalyser(object):
             state = self.hidden[self.rows, parent.long()]
             nxt, reward, logits, value = net.recurrent_inference(state, action.long())
             self.hidden[self.rows, leaf.long()] = nxt
+            if self.value_transform:
+                from .network import inverse_value_transform
+                reward, value = inverse_value_transform(reward), inverse_value_transform(value)
             tree.expand_backup(reward.contiguous(), t.softmax(logits, dim=1).contiguous(), value.contiguous())
 
     def _chunk(self, where, obs, ticket):

@@ -24,6 +24,12 @@ with probability w / sum(w), w the fixed-point integer of |root value - n-step r
 rewrites root values moves the priorities with no read-back; ``sample_prioritized`` returns the mini-batch and the
 importance weights (1 / (N P)) ** beta.  Integer sums are exact in any order: ``mz_prioritized_draws`` restates the device's
 draws bit for bit.
+
+``value_transform=True`` (rz_mz_replay_set_value_transform; for a ``MuZeroNet(value_transform=True)``): the launch that forms a
+mini-batch -- ``gather``, ``sample`` and the gather of ``sample_prioritized`` -- writes ``tv = float32(h(z))`` and ``tr =
+float32(h(u))``, z the fp64 n-step return as formed without it and u the stored reward (csrc/rz_mz_value.h), bit for bit what
+``ReplayBuffer(value_transform=True).sample`` forms; rows past the episode's end stay 0.  The store stays raw, and the priorities
+stay |root value - n-step return| in RAW units: ``priorities()`` is the same with and without the flag.
 """
 import bisect
 import ctypes
@@ -152,7 +158,7 @@ class MuZeroDeviceReplay(object):
     episodes held, like the host buffer.  No CPU fallback: HipError without a GPU."""
 
     def __init__(self, obs_dim, n_actions, capacity_episodes, max_episode_steps, unroll_steps=5, td_steps=10, discount=0.997,
-                 device='cuda:0', seed=0, prioritized=False):
+                 device='cuda:0', seed=0, prioritized=False, value_transform=False):
         import torch
         self.torch = torch
         self.lib = _hip.load()
@@ -173,6 +179,9 @@ class MuZeroDeviceReplay(object):
         _hip.check(self.lib.rz_mz_replay_create(self.obs_dim, self.n_actions, self.capacity, self.max_episode_steps, self.K, self.td_steps,
                                                 _ptr(self.disc), self.device.index, ctypes.byref(handle)), 'rz_mz_replay_create')
         self.handle = handle
+        self.value_transform = bool(value_transform)
+        if self.value_transform:
+            _hip.check(self.lib.rz_mz_replay_set_value_transform(self.handle, 1), 'rz_mz_replay_set_value_transform')
         self.prioritized = False
         if prioritized:
             self.enable_priorities()
@@ -372,7 +381,8 @@ class MuZeroDeviceReplay(object):
 
     def priorities(self):
         """The integer priority of every step held: a list of int64 arrays, oldest episode first (``mz_priority_weights`` of
-        each episode, bit for bit).  A synchronous copy (tests, debugging)."""
+        each episode, bit for bit).  With ``value_transform`` they are still |root value - n-step return| in raw units: the
+        same numbers as without it.  A synchronous copy (tests, debugging)."""
         self._need_priorities('priorities')
         n, T = len(self), self.max_episode_steps
         w = np.zeros((max(n, 1), T), dtype=np.int64)

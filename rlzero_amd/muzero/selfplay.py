@@ -126,10 +126,14 @@ class EpisodeSeq(object):
 
 class ReplayBuffer(object):
     """Finished episodes + the target construction of the MuZero learner (``make_target``): K unrolled
-    steps, n-step value targets bootstrapped from the stored root values."""
+    steps, n-step value targets bootstrapped from the stored root values.
+    ``value_transform``: the value and reward targets of steps inside the episode are h of the fp64 targets formed without it
+    (network.py: value_transform; numpy float64, the same expression in the same order) before their cast to float32; targets past
+    the end stay 0, and the episodes are stored raw."""
 
-    def __init__(self, capacity=2000, unroll_steps=5, td_steps=10, discount=0.997, seed=0):
+    def __init__(self, capacity=2000, unroll_steps=5, td_steps=10, discount=0.997, seed=0, value_transform=False):
         self.capacity, self.K, self.td_steps, self.discount = capacity, unroll_steps, td_steps, discount
+        self.value_transform = bool(value_transform)
         self.episodes = []
         self.rng = np.random.RandomState(seed)
 
@@ -153,6 +157,12 @@ class ReplayBuffer(object):
             value += r * self.discount ** i
         return value
 
+    @staticmethod
+    def _h(x):
+        """h(x) of one float64 (csrc/rz_mz_value.h: value_h, the same operations in the same order)."""
+        x = np.float64(x)
+        return np.copysign(np.sqrt(np.abs(x) + np.float64(1.0)) - np.float64(1.0), x) + np.float64(0.001) * x
+
     def sample(self, batch_size, n_actions):
         """-> obs [b, obs_dim], actions [b, K], target value [b, K+1], target reward [b, K+1], target policy
         [b, K+1, A], mask [b, K+1] (0 past the end of the episode: no policy loss there)."""
@@ -169,13 +179,13 @@ class ReplayBuffer(object):
             for k in range(K + 1):
                 i = t + k
                 if i < len(ep):
-                    tv[b, k] = self._value_target(ep, i)
+                    tv[b, k] = self._h(self._value_target(ep, i)) if self.value_transform else self._value_target(ep, i)
                     tp[b, k] = ep.policies[i]
                     mask[b, k] = 1.0
                 if k > 0:
                     if i - 1 < len(ep):
                         actions[b, k - 1] = ep.actions[i - 1]
-                        tr[b, k] = ep.rewards[i - 1]
+                        tr[b, k] = self._h(ep.rewards[i - 1]) if self.value_transform else ep.rewards[i - 1]
                     else:
                         actions[b, k - 1] = self.rng.randint(n_actions)  # past the end: random action, zero targets
         return obs, actions, tv, tr, tp, mask
@@ -224,6 +234,12 @@ class MuZeroSelfPlay(object):
         self.alpha, self.noise_frac = float(root_dirichlet_alpha), float(root_exploration_fraction)
         self.tree = MuZeroTree(self.n_envs, self.n_actions, self.n_sims, discount, pb_c_base, pb_c_init,
                                device=str(self.device))
+        # the net owns the flag (MuZeroNet(value_transform=True)): its reward and value heads live in h's space, and every route
+        # takes them through h^-1 before the backup -- inside k_mz_search (its VT instantiations) or in _sim_step
+        self.value_transform = bool(getattr(net, 'value_transform', False))
+        if self.value_transform:
+            self.tree.set_value_transform(True)
+        self.entry_log = None   # a list: receives (environment int64 [n], end step int64 [n]) of the finished episodes, in their order
         self.hidden = torch.zeros((self.n_envs, self.tree.slots_per_game, net.hidden), dtype=torch.float32,
                                   device=self.device)
         self.rows = torch.arange(self.n_envs, device=self.device)
@@ -344,12 +360,26 @@ class MuZeroSelfPlay(object):
         nxt, reward, logits, value = self.net.recurrent_inference(state, action.long())
         self.hidden[self.rows, leaf.long()] = nxt
         probs = t.softmax(logits, dim=1).contiguous()
+        if self.value_transform:   # the tree is in raw units
+            from .network import inverse_value_transform
+            reward, value = inverse_value_transform(reward), inverse_value_transform(value)
         reward, value = reward.contiguous(), value.contiguous()
         self.tree.expand_backup(reward, probs, value)
         return parent, action, leaf, reward, probs, value
 
     def close(self):
         self.tree.close()
+
+    def restart_episodes(self):
+        """Every environment begins episode 0 again, from that episode's initial state (the environment's counter-based stream:
+        the same states at every call), and the running episodes of the history are dropped: the next move is the first of a new
+        episode everywhere (an evaluation's start; nothing is launched into before the last ``collect`` has been read)."""
+        self.env.episode_dev.zero_()
+        self.env.reset_all()
+        self._ep_start[:] = self._t
+        if self._records is not None:
+            self._ep_start_dev.fill_(self._t)
+        self.obs = self.env.observe()
 
     # ------------------------------------------------------------------ search
     def search(self, obs, add_noise=True, record=None):
@@ -464,6 +494,8 @@ class MuZeroSelfPlay(object):
         kk, ee = np.nonzero(rec[:, :, D + 3 + A] != 0.0)   # (move, environment) of every episode end, by move then environment
         if len(kk):
             end = t0 + kk + 1                                # global step index behind the episode's last move
+            if getattr(self, 'entry_log', None) is not None:
+                self.entry_log.append((ee.astype(np.int64), end.astype(np.int64)))
             # an environment may finish more than once in the stretch: its later episodes start where the previous ended
             order = np.lexsort((kk, ee))
             ee_s, end_s = ee[order], end[order]
@@ -610,6 +642,8 @@ class MuZeroSelfPlay(object):
             used = min(n_rows, arena.shape[0])
             # (a copy: the pinned buffer is the next-but-one launch's; the episodes' fields are formed when they are asked for)
             finished._add_packed(arena.numpy()[:used].copy(), D, A, ent[fits, 2], ent[fits, 3])
+            if self.entry_log is not None:
+                self.entry_log.append((ent[fits, 0].copy(), ent[fits, 1].copy()))
             if replay is not None:
                 replay.ingest(arena_dev, ent[fits, 2], ent[fits, 3])
         if missed:  # the arena was too small for these: their records are still in the ring
@@ -620,6 +654,8 @@ class MuZeroSelfPlay(object):
             step_idx = (np.repeat(end - length, length) + within) % self._ring.shape[1]
             block = self._ring[t.from_numpy(env_idx).to(self.device), t.from_numpy(step_idx).to(self.device)].cpu().numpy()
             finished._add_packed(block, D, A, length)
+            if self.entry_log is not None:
+                self.entry_log.append((env.copy(), end.copy()))
             if replay is not None:
                 replay.add_packed(block, length)
         return finished

@@ -22,6 +22,7 @@ class MuZeroTree(object):
             raise _hip.HipError('MuZeroTree needs an MI355X (device=%r): there is no CPU path' % (device, ))
         self.n_games, self.n_actions, self.n_sims = int(n_games), int(n_actions), int(n_sims)
         self.discount = float(discount)
+        self.value_transform = False   # set_value_transform
         cfg = _hip.RzMzConfig(_hip.ABI_VERSION, self.n_games, self.n_actions, self.n_sims, self.discount,
                               float(pb_c_base), float(pb_c_init), self.device.index or 0, 0)
         self.handle = ctypes.c_void_p()
@@ -152,6 +153,15 @@ class MuZeroTree(object):
     def set_search_shape(self, games_per_workgroup=0):
         """Games per workgroup of ``search_fused`` (<= 16; 0 = chosen from the number of games and CUs)."""
         check(self.lib.rz_mz_set_search_shape(self.handle, int(games_per_workgroup)), 'rz_mz_set_search_shape')
+        return self
+
+    def set_value_transform(self, on=True):
+        """The value transform of the searches inside the kernel (rz_mz_set_value_transform; ``search_fused``, ``play_cartpole``,
+        ``play_env``): on, the network's reward and value of every simulation go through ``h^-1`` (csrc/rz_mz_value.h, fp64, one
+        rounding to float32) before the trace and the backup, so the tree and the root values are in raw units; off (the default),
+        they are used as they come.  ``expand_backup`` takes what it is given either way."""
+        check(self.lib.rz_mz_set_value_transform(self.handle, 1 if on else 0), 'rz_mz_set_value_transform')
+        self.value_transform = bool(on)
         return self
 
     def search_fused(self, hidden, n_sims, trace=False):
