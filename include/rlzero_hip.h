@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 43
+#define RZ_ABI_VERSION 44
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -508,6 +508,17 @@ int rz_play_set_temperatures(rz_engine *e, const double *h_temps, int32_t n, voi
 /* Whether the cap's searches take their workgroups in the partition's order (default) or in slot order (0: no order kernel in the
  * move step; a measurement's switch).  A host-side setting read when launches are enqueued: set it before a move graph is captured. */
 int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
+/* The root values of the move step (ABI 44; an opt-in extension: the value target of the learner, rz_replay_add_values).  d_ring:
+ * float32 [ring_steps][n_games] of the caller, ring_steps as in rz_play_attach -- device memory, or pinned host memory the device can
+ * address (as d_log) --; NULL: off again.  With a ring, lane 0 of a slot's wave in k_play_draw writes float32(v_root), v_root =
+ * N(root) > 0 ? -(W(root) / N(root)) : NaN (rz_play.h: root_value; rz_root_values' [0], the same fp64 bits), into row
+ * step % ring_steps for every slot that holds a game -- a stalled slot's root does not change, so its rows repeat the value of its
+ * searched record -- and NaN for an idle slot.  The record's words and the visit counts are untouched (word [7] stays the
+ * resignation statistic).  The ring is a kernel ARGUMENT of the draw: the call is valid after rz_play_attach and before the first
+ * move step is enqueued or captured (a whole-move graph is then captured with the ring in it and stays one replay), RZ_ERR_ARG
+ * afterwards and while a match is on; rz_play_set_match is refused while a ring is set.  rz_play_attach turns it off.  `stream` is
+ * unused: nothing is enqueued. */
+int rz_play_set_root_values(rz_engine *e, float *d_ring, void *stream);
 /* Match mode (above).  The table -- d_open_stones uint64 [n_openings][2][RZ_BOARD_WORDS], d_open_to_move / d_open_last int32
  * [n_openings], device memory -- is copied on `stream` into the engine's own; launches enqueued after the call read it.
  * n_openings == 0 (pointers ignored): off again.  Valid after rz_play_attach, before the games are queued, on an engine without
@@ -1052,6 +1063,33 @@ int rz_replay_set_tables_game(rz_replay *r, int32_t n_symmetries, int32_t n_cell
                               const int16_t *h_src_pi, void *stream);
 int rz_replay_geometry(rz_replay *r, int32_t *game_kind, int32_t *rows, int32_t *cols, int32_t *n_cells, int32_t *n_actions,
                        int32_t *n_symmetries);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Value targets from the search (ABI 44; rz_replay.hip: k_replay_add<.., true>, k_replay_gather<.., true>, k_replay_sample<.., true>,
+ * k_replay_update_q; rz_replay_rules.h: value_target; rlzero_amd/replay.py: mixed_value_targets).  Opt-in, both games; without
+ * rz_replay_enable_values nothing is allocated and every call above launches the kernels of ABI 43.
+ *
+ * rz_replay_enable_values: a float32 array q [capacity] beside the meta words, every slot NaN.  Only while nothing has been stored
+ *   in the handle (RZ_ERR_ARG afterwards); a second call is a no-op.
+ * rz_replay_add_values: rz_replay_add with h_q float32 [kept plies] -- the root value the mover's search saw at every kept ply
+ *   (rz_play_set_root_values), in the order of h_pi's rows -- stored in q beside the position.  h_q NULL, or rz_replay_add on a
+ *   handle with values: NaN.  RZ_ERR_ARG for h_q on a handle without values.
+ * rz_replay_set_value_mix: lam in [0, 1] (default 0) of the value target rz_replay_gather / rz_replay_sample write,
+ *   zs[i] = isnan(q) ? z : float32((1 - lam) * double(z) + lam * double(q)) -- fp64, each product rounded before the sum (no fused
+ *   multiply-add).  lam travels to the kernels by value.  At lam = 0 the kernels without q run and zs is z, the bits of ABI 43.
+ *   RZ_ERR_ARG for lam outside [0, 1] (NaN included) and for lam > 0 on a handle without values.  Host state: no launch.
+ * rz_replay_update_values: Reanalyse's way back for q, ONE launch (k_replay_update_q: a thread per row).  d_where int32 [n] as
+ *   rz_replay_positions wrote it, d_root_values float64 [n][2] as rz_root_values writes it ([0]: the root value for the player to
+ *   move): q[d_where[i]] = float32(d_root_values[i][0]).  A row with d_where < 0 or outside the capacity, or a NaN value, writes
+ *   nothing; stones, meta, pi and every other slot stay as they are.  `ticket` as in rz_replay_update_pi: RZ_ERR_ARG, and nothing
+ *   launched, if positions were stored since rz_replay_positions.  RZ_ERR_ARG on a handle without values.
+ * rz_replay_read_values: a SYNCHRONOUS copy of q of n positions from position `first` (oldest = 0), like rz_replay_read. */
+int rz_replay_enable_values(rz_replay *r, void *stream);
+int rz_replay_add_values(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
+                         const int32_t *h_winner, const float *h_pi, const float *h_q, void *stream);
+int rz_replay_set_value_mix(rz_replay *r, double lam);
+int rz_replay_update_values(rz_replay *r, const int32_t *d_where, int64_t n, const double *d_root_values, int64_t ticket, void *stream);
+int rz_replay_read_values(rz_replay *r, int64_t first, int64_t n, float *h_q, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * MuZero device replay (ABI 35; rz_mz_replay.hip, rz_mz_target.h; an opt-in extension beside the host ReplayBuffer of

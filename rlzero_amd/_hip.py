@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -179,6 +179,7 @@ _SIGNATURES = {
     'rz_set_playouts': (c_int, [P, P, P, P]),
     'rz_playouts_view': (c_int, [P, POINTER(c_void_p), POINTER(c_void_p)]),
     'rz_play_set_cap_order': (c_int, [P, c_int32]),
+    'rz_play_set_root_values': (c_int, [P, P, P]),
     'rz_playouts_read': (c_int, [P, P, P, POINTER(c_int32)]),
     'rz_play_set_match': (c_int, [P, P, P, P, c_int32, P]),
     'rz_play_side': (c_int, [P, c_int32, P]),
@@ -260,6 +261,11 @@ _SIGNATURES = {
     'rz_replay_create_game': (c_int, [c_int32, c_int32, c_int32, c_int64, c_int32, POINTER(c_void_p)]),
     'rz_replay_set_tables_game': (c_int, [P, c_int32, c_int32, c_int32, P, P, P]),
     'rz_replay_geometry': (c_int, [P] + [POINTER(c_int32)] * 6),
+    'rz_replay_enable_values': (c_int, [P, P]),
+    'rz_replay_add_values': (c_int, [P, c_int32, P, P, P, P, P, P, P]),
+    'rz_replay_set_value_mix': (c_int, [P, c_double]),
+    'rz_replay_update_values': (c_int, [P, P, c_int64, P, c_int64, P]),
+    'rz_replay_read_values': (c_int, [P, c_int64, c_int64, P, P]),
     'rz_mz_replay_create': (c_int, [c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, P, c_int32, POINTER(c_void_p)]),
     'rz_mz_replay_destroy': (c_int, [P]),
     'rz_mz_replay_state': (c_int, [P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), P]),

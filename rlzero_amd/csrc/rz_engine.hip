@@ -1295,7 +1295,10 @@ __device__ __forceinline__ void cap_write(const Play &Y, int g, int64_t gid, int
 // keep = -1, so k_play_apply starts the next search of the game from a fresh root; stepm stays the move.
 // The kernel gathers the counts and computes log, the wave maximum and exp; the draw, the resignation rule and what the step
 // changes are rz_play.h's (ry::draw, ry::resign_rule, ry::decide), and lane 0 writes all of it at the end.
-__global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
+// `vring` (rz_play_set_root_values; nullptr: off, nothing more is read or written): float32 [Y.ring][n_games], the root value the
+// mover's search saw (ry::root_value: rz_root_values' [0]) into the row of this step for every slot that holds a game -- a stalled
+// slot's root does not change, so its rows repeat the searched one's value --, NaN for an idle slot.
+__global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y, float *__restrict__ vring) {
     __shared__ double sh_e[kWave * kWords];
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
@@ -1304,6 +1307,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
     ry::SlotIn in = {};
     in.state = Y.state[g];
+    double v_root = NAN;
     if (in.state != ry::kIdle) {
         // the root's children by action (k_root_children)
         const int arena = E.cur_arena[g];
@@ -1314,6 +1318,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
         for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
         const Legal L = legal_of(E, occ, lane);
         const int4 lo = R[0];
+        if (vring != nullptr) v_root = ry::root_value(lo.x, rec_w(R[1]));
         const bool expanded = rec_k(lo) > 0;
         const int fc = lo.y;
         const int nv = expanded ? lo.z : 0;
@@ -1376,6 +1381,7 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y) {
     if (lane != 0) return;
     const ry::SlotOut o = ry::decide(in);
     ry::write_record(rec, in, o);
+    if (vring != nullptr) vring[(long long)(step % Y.ring) * E.n_games + g] = (float)v_root;
     Y.keep[g] = o.keep;
     Y.stepm[g] = o.stepm;
     if (o.clear_mail) Y.mailbox[g] = -1;
@@ -1577,6 +1583,7 @@ struct rz_engine {
     bool play_seen = false;   // rz_play_attach has been called: `play` holds the arrays it got (all of them once play_on)
     bool play_on = false, play_drawn = false;
     long long play_steps = 0;   // move steps enqueued (rz_play_apply calls) since rz_play_attach
+    float *play_vring = nullptr;   // rz_play_set_root_values: the caller's ring of root values (nullptr: off), an argument of k_play_draw
     // rz_set_playouts: the host's per-game simulation counts (and workgroup order) of the resident search, copies of the caller's
     int32_t *pl_counts = nullptr, *pl_order = nullptr;
     bool pl_on = false, pl_ordered = false;
@@ -2328,12 +2335,37 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     e->play_on = true;
     e->play_drawn = false;
     e->play_steps = 0;
+    e->play_vring = nullptr;   // (and the ring of root values: rz_play_set_root_values)
+    return RZ_OK;
+}
+
+int rz_play_set_root_values(rz_engine *e, float *d_ring, void *stream) {
+    RZ_ENTER_PLAY(e);
+    (void)stream;   // (nothing is enqueued: the ring is an argument of the draws to come)
+    // a move step enqueued -- or captured into a whole-move graph -- holds the ring it was launched with
+    if (e->play_steps > 0 || e->play_drawn) return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: a move step has been enqueued since rz_play_attach (attach again)");
+    if (d_ring != nullptr && e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: a match is on (rz_play_set_match): its games are not training data");
+    if (d_ring != nullptr) {   // host memory (pinned, written directly like the log) must be addressable from this device
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        if (hipPointerGetAttributes(&attr, d_ring) != hipSuccess) {
+            (void)hipGetLastError();
+        } else if (attr.type == hipMemoryTypeHost) {
+            void *dp = nullptr;
+            if (hipHostGetDevicePointer(&dp, d_ring, 0) != hipSuccess || dp == nullptr) {
+                (void)hipGetLastError();
+                return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: d_ring is host memory that device %d cannot address (pass device memory)", e->cfg.device);
+            }
+            d_ring = static_cast<float *>(dp);
+        }
+    }
+    e->play_vring = d_ring;
     return RZ_OK;
 }
 
 int rz_play_draw(rz_engine *e, void *stream) {
     RZ_ENTER_PLAY(e);
-    k_play_draw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play);
+    k_play_draw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play, e->play_vring);
     e->play_drawn = true;
     return rz_launched("k_play_draw");
 }
@@ -2467,6 +2499,7 @@ int rz_play_set_match(rz_engine *e, const uint64_t *d_open_stones, const int32_t
         return rz_fail(RZ_ERR_ARG, "rz_play_set_match: matches need the resident search (RZ_SCORE_UCT_REF, one simulation in flight per tree)");
     if (Y.resign_on || Y.cap_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: resignation or a playout cap is set (attach again: a match has neither)");
     if (Y.temp_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: a temperature schedule is set (attach again: a match keeps the temperature of rz_play_attach)");
+    if (e->play_vring != nullptr) return rz_fail(RZ_ERR_ARG, "rz_play_set_match: a ring of root values is set (rz_play_set_root_values; attach again: a match logs none)");
     if (n_openings > e->open_cap) {   // (hipFree waits for the device: no launch still reads the old table)
         const void *old[3] = {Y.open_stones, Y.open_to_move, Y.open_last};
         for (const void *p : old) {

@@ -74,8 +74,10 @@ struct Resign {
     double s;
     bool fire;
 };
+// the value the mover sees at the root (rz_root_values' [0]; float32 of it is what rz_play_set_root_values logs): NaN at an unvisited root
+RZY_FN double root_value(int n_root, double w_root) { return n_root > 0 ? -(w_root / (double)n_root) : NAN; }
 RZY_FN Resign resign_rule(int n_root, double w_root, double q_children, double threshold) {
-    const double v_root = n_root > 0 ? -(w_root / (double)n_root) : NAN;
+    const double v_root = root_value(n_root, w_root);
     const double q_best = q_children > -INFINITY ? q_children : NAN;
     Resign r;
     r.s = (isnan(v_root) || isnan(q_best)) ? NAN : fmax(v_root, q_best);

@@ -11,6 +11,11 @@
 // (rz_replay_rules.h: cell_of_ply) before the Gomoku code runs on them.  k_replay_add, k_replay_gather and k_replay_sample are
 // templates on the game so that the Gomoku instantiations keep the code they had (entry >> 3, entry & 7, one table width).
 //
+// Value targets from the search (ABI 44, opt-in: rz_replay_enable_values): a float32 array q [capacity] beside the meta words holds the
+// root value the mover's search saw (NaN: none), written by k_replay_add<.., true> and refreshed by k_replay_update_q; with
+// rz_replay_set_value_mix(lam > 0) k_replay_gather<.., true> / k_replay_sample<.., true> write zs = (1 - lam) z + lam q
+// (rz_replay_rules.h: value_target).  Without the option no array exists and the <.., false> instantiations -- the code of ABI 43 -- run.
+//
 // Bounds: every slot is reduced modulo the capacity, every table entry is checked at upload (< C for the planes, < A for pi), an
 // entry index from the device is checked by the kernel before anything is read, moves are checked on the host (Gomoku: < A;
 // Connect4: a column < cols that is not full) and index registers or LDS arrays of kMaxCells entries under a mask, not memory.
@@ -68,11 +73,14 @@ __device__ __forceinline__ long long replay_index(unsigned long long seed, unsig
 // written, so no two threads of the launch share a slot).
 // kC4: the moves are Connect4 columns.  Thread p turns column p into its cell over the move list in LDS, behind the first barrier;
 // one more barrier, and everything below reads cells.
-template <bool kC4>
+// kQ (rz_replay_enable_values): the search's root value of every kept ply, q_rows[t], goes to q_of[slot] beside the meta word; the
+// instantiations without it never read either pointer and are the code they were.
+template <bool kC4, bool kQ>
 __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int32_t *__restrict__ offsets, const int32_t *__restrict__ base,
                                                            const int32_t *__restrict__ winner, const int32_t *__restrict__ moves,
                                                            const uint8_t *__restrict__ keep, const float *__restrict__ pi_rows,
-                                                           long long cursor, long long skip) {
+                                                           long long cursor, long long skip, const float *__restrict__ q_rows,
+                                                           float *__restrict__ q_of) {
     __shared__ int32_t s_moves[kMaxCells];
     __shared__ int32_t s_slot[kMaxCells];
     __shared__ int32_t s_row[kMaxCells];
@@ -120,6 +128,7 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
         const int z = win < 0 ? 0 : ((p & 1) == win ? 1 : -1);
         const int last = p > 0 ? s_cells[p - 1] + 1 : 0;
         R.meta[slot] = last | ((p & 1) << kMetaParityBit) | ((z + 1) << kMetaZShift);
+        if (kQ) q_of[slot] = q_rows[t];
     }
     s_slot[p] = slot;
     s_row[p] = (int32_t)t;
@@ -136,15 +145,20 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_add(ReplayDev R, const int
 
 // entry e -> output row i: a thread per output cell (blockDim.x >= C >= A).  Gomoku: entry 8 j + k, one width for both tables;
 // Connect4: entry 2 j + k, the planes over the C cells and pi over the A columns, written by the first A threads.
-template <bool kC4>
+// kMix (rz_replay_set_value_mix, lam > 0): zs[i] = rzrr::value_target(z, q[slot], lam) -- the eight symmetries of a position share its
+// q --; without it neither q nor lam is read and zs[i] is z, the code it was.
+template <bool kC4, bool kMix>
 __device__ __forceinline__ void replay_emit(const ReplayDev &R, long long e, long long oldest, long long i, float *__restrict__ states,
-                                            float *__restrict__ pis, float *__restrict__ zs) {
+                                            float *__restrict__ pis, float *__restrict__ zs, const float *__restrict__ q, double lam) {
     const int o = threadIdx.x, A = R.A, C = kC4 ? R.C : R.A, k = (int)(e & (kC4 ? 1 : 7));
     const long long slot = (oldest + (e >> (kC4 ? 1 : 3))) % R.capacity;
     const unsigned long long *rec = R.stones + slot * kRecWords;   // (uniform across the workgroup)
     const unsigned long long a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], b0 = rec[4], b1 = rec[5], b2 = rec[6], b3 = rec[7];
     const int meta = R.meta[slot];
-    if (o == 0) zs[i] = (float)(((meta >> kMetaZShift) & 3) - 1);
+    if (o == 0) {
+        const float z = (float)(((meta >> kMetaZShift) & 3) - 1);
+        zs[i] = kMix ? rzrr::value_target(z, q[slot], lam) : z;
+    }
     if (o >= C) return;
     const int s = R.src_state[k * C + o];
     const int w = s >> 6;
@@ -159,25 +173,25 @@ __device__ __forceinline__ void replay_emit(const ReplayDev &R, long long e, lon
     pis[i * A + o] = R.pi[slot * A + R.src_pi[k * A + o]];
 }
 
-template <bool kC4>
+template <bool kC4, bool kMix>
 __global__ __launch_bounds__(kMaxCells) void k_replay_gather(ReplayDev R, const long long *__restrict__ indices, long long oldest,
                                                               long long n_entries, float *__restrict__ states, float *__restrict__ pis,
-                                                              float *__restrict__ zs) {
+                                                              float *__restrict__ zs, const float *__restrict__ q, double lam) {
     const long long i = blockIdx.x;
     const long long e = indices[i];
     if (e < 0 || e >= n_entries) {   // an index from the device: nothing is read or written for it
         if (threadIdx.x == 0) atomicOr(R.err, kFlagBadIndex);
         return;
     }
-    replay_emit<kC4>(R, e, oldest, i, states, pis, zs);
+    replay_emit<kC4, kMix>(R, e, oldest, i, states, pis, zs, q, lam);
 }
 
-template <bool kC4>
+template <bool kC4, bool kMix>
 __global__ __launch_bounds__(kMaxCells) void k_replay_sample(ReplayDev R, unsigned long long seed, unsigned long long step, long long oldest,
                                                               long long n_entries, float *__restrict__ states, float *__restrict__ pis,
-                                                              float *__restrict__ zs) {
+                                                              float *__restrict__ zs, const float *__restrict__ q, double lam) {
     const long long i = blockIdx.x;
-    replay_emit<kC4>(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs);
+    replay_emit<kC4, kMix>(R, replay_index(seed, step, (unsigned long long)i, (unsigned long long)n_entries), oldest, i, states, pis, zs, q, lam);
 }
 
 // Reanalyse, the way out: position index -> ring slot (`where`, -1 for an index outside 0 .. count - 1) and the stored record as a
@@ -232,6 +246,19 @@ __global__ __launch_bounds__(kMaxCells) void k_replay_update_pi(ReplayDev R, con
     R.pi[slot * A + a] = rzrr::pi_of_visits(mine, sum);
 }
 
+// Reanalyse, the way back for the value target: q[where[i]] = float32(values[i][0]) -- values: the engine's rz_root_values,
+// float64 [n][2], of which [0] is the root value for the player to move.  A thread per row.  where < 0 (a refused or a padding row), a
+// slot outside the capacity or a NaN value (an unvisited root) writes nothing (rzrr::value_written); stones, meta and pi are never
+// written.  Two rows that name one slot write the same bits: the search is deterministic.
+__global__ __launch_bounds__(kMaxCells) void k_replay_update_q(float *__restrict__ q, long long capacity, const int32_t *__restrict__ where,
+                                                                const double *__restrict__ values, long long n) {
+    const long long i = (long long)blockIdx.x * kMaxCells + threadIdx.x;
+    if (i >= n) return;
+    const long long slot = where[i];
+    const double v = values[2 * i];
+    if (rzrr::value_written(slot, capacity, v)) q[slot] = (float)v;
+}
+
 }  // namespace
 
 struct rz_replay {
@@ -241,6 +268,8 @@ struct rz_replay {
     long long stored = 0;              // positions ever stored: the ticket of rz_replay_positions / rz_replay_update_pi
     int16_t *d_tables = nullptr;
     bool tables = false;
+    float *q = nullptr;   // [capacity] the search's root value of every position (rz_replay_enable_values; NaN: none), else no array
+    double mix = 0.0;     // rz_replay_set_value_mix: lam of the value target; 0: zs is z, the kernels without q
     DevPool pool;    // the store
     Staging stage;   // what the host hands to a launch
 };
@@ -300,6 +329,75 @@ int rp_create(int game, int rows, int cols, int64_t capacity, int32_t device, rz
     *out = r;
     return RZ_OK;
 }
+
+// rz_replay_add / rz_replay_add_values: h_q float [kept] the root value of every kept ply, or NULL (a buffer with values stores NaN)
+int rp_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep, const int32_t *h_winner,
+           const float *h_pi, const float *h_q, void *stream) {
+    RZ_ENTER(rp_ready, r);
+    if (h_q != nullptr && r->q == nullptr) return rz_fail(RZ_ERR_ARG, "values for a buffer without them: rz_replay_enable_values");
+    if (n_games < 0) return rz_fail(RZ_ERR_ARG, "n_games < 0");
+    if (n_games == 0) return RZ_OK;
+    if (h_offsets == nullptr || h_winner == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    const int A = r->dev.A, C = r->dev.C;
+    if (h_offsets[0] != 0) return rz_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
+    std::vector<int32_t> base((size_t)n_games);
+    long long kept = 0;
+    for (int g = 0; g < n_games; ++g) {
+        const long long P = (long long)h_offsets[g + 1] - h_offsets[g];
+        if (P < 0) return rz_fail(RZ_ERR_ARG, "h_offsets must not decrease");
+        if (P > C) return rz_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
+        if (h_winner[g] < -1 || h_winner[g] > 1) return rz_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
+        if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rz_fail(RZ_ERR_ARG, "NULL argument");
+        base[(size_t)g] = (int32_t)kept;
+        if (rp_connect4(r) && P > 0) {   // columns: each inside the board and not played more often than the board has rows
+            const int bad = rzrr::first_illegal_drop(h_moves + h_offsets[g], (int)P, r->rows, r->dev.cols);
+            if (bad >= 0) {
+                const int32_t column = h_moves[h_offsets[g] + bad];
+                return rz_fail(RZ_ERR_ARG, column < 0 || column >= r->dev.cols ? "a move is outside the board" : "a column is played more often than the board has rows");
+            }
+        }
+        for (int p = h_offsets[g]; p < h_offsets[g + 1]; ++p) {
+            if (h_moves[p] < 0 || h_moves[p] >= A) return rz_fail(RZ_ERR_ARG, "a move is outside the board");
+            kept += h_keep[p] != 0;
+        }
+    }
+    const long long total = h_offsets[n_games];
+    if (kept == 0) return RZ_OK;
+    if (h_pi == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    const bool with_q = r->q != nullptr;
+    // staging: offsets | base | winner | moves | keep | pi rows | (a buffer with values) q rows
+    const size_t o_off = 0, o_base = o_off + align16(((size_t)n_games + 1) * 4), o_win = o_base + align16((size_t)n_games * 4),
+                 o_moves = o_win + align16((size_t)n_games * 4), o_keep = o_moves + align16((size_t)total * 4),
+                 o_pi = o_keep + align16((size_t)total), o_q = o_pi + align16((size_t)kept * A * sizeof(float)),
+                 bytes = with_q ? o_q + (size_t)kept * sizeof(float) : o_pi + (size_t)kept * A * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    RZ_TRY(r->stage.reserve(bytes, s));
+    char *h = (char *)r->stage.h, *d = (char *)r->stage.d;
+    memcpy(h + o_off, h_offsets, ((size_t)n_games + 1) * 4);
+    memcpy(h + o_base, base.data(), (size_t)n_games * 4);
+    memcpy(h + o_win, h_winner, (size_t)n_games * 4);
+    memcpy(h + o_moves, h_moves, (size_t)total * 4);
+    memcpy(h + o_keep, h_keep, (size_t)total);
+    memcpy(h + o_pi, h_pi, (size_t)kept * A * sizeof(float));
+    if (with_q) {
+        float *hq = (float *)(h + o_q);
+        for (long long t = 0; t < kept; ++t) hq[t] = h_q != nullptr ? h_q[t] : NAN;
+    }
+    RZ_TRY(r->stage.upload(bytes, s));
+    const long long cap = r->dev.capacity, skip = kept > cap ? kept - cap : 0;
+    auto kernel = with_q ? (rp_connect4(r) ? k_replay_add<true, true> : k_replay_add<false, true>)
+                         : (rp_connect4(r) ? k_replay_add<true, false> : k_replay_add<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
+                       (const int32_t *)(d + o_win), (const int32_t *)(d + o_moves), (const uint8_t *)(d + o_keep), (const float *)(d + o_pi),
+                       r->cursor, skip, with_q ? (const float *)(d + o_q) : (const float *)nullptr, r->q);
+    RZ_TRY(r->stage.launched(s, "k_replay_add"));
+    r->cursor = (r->cursor + kept) % cap;
+    r->count = r->count + kept > cap ? cap : r->count + kept;
+    r->stored += kept;
+    return RZ_OK;
+}
+
+inline bool rp_mixing(const rz_replay *r) { return r->q != nullptr && r->mix > 0.0; }
 
 }  // namespace
 
@@ -382,58 +480,59 @@ int rz_replay_state(rz_replay *r, int64_t *count, int64_t *cursor, int64_t *capa
 
 int rz_replay_add(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
                   const int32_t *h_winner, const float *h_pi, void *stream) {
+    return rp_add(r, n_games, h_offsets, h_moves, h_keep, h_winner, h_pi, nullptr, stream);
+}
+
+int rz_replay_add_values(rz_replay *r, int32_t n_games, const int32_t *h_offsets, const int32_t *h_moves, const uint8_t *h_keep,
+                         const int32_t *h_winner, const float *h_pi, const float *h_q, void *stream) {
+    return rp_add(r, n_games, h_offsets, h_moves, h_keep, h_winner, h_pi, h_q, stream);
+}
+
+int rz_replay_enable_values(rz_replay *r, void *stream) {
     RZ_ENTER(rp_ready, r);
-    if (n_games < 0) return rz_fail(RZ_ERR_ARG, "n_games < 0");
-    if (n_games == 0) return RZ_OK;
-    if (h_offsets == nullptr || h_winner == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
-    const int A = r->dev.A, C = r->dev.C;
-    if (h_offsets[0] != 0) return rz_fail(RZ_ERR_ARG, "h_offsets[0] must be 0");
-    std::vector<int32_t> base((size_t)n_games);
-    long long kept = 0;
-    for (int g = 0; g < n_games; ++g) {
-        const long long P = (long long)h_offsets[g + 1] - h_offsets[g];
-        if (P < 0) return rz_fail(RZ_ERR_ARG, "h_offsets must not decrease");
-        if (P > C) return rz_fail(RZ_ERR_ARG, "a game is longer than the board has cells");
-        if (h_winner[g] < -1 || h_winner[g] > 1) return rz_fail(RZ_ERR_ARG, "winner must be 0, 1 or -1");
-        if (P > 0 && (h_moves == nullptr || h_keep == nullptr)) return rz_fail(RZ_ERR_ARG, "NULL argument");
-        base[(size_t)g] = (int32_t)kept;
-        if (rp_connect4(r) && P > 0) {   // columns: each inside the board and not played more often than the board has rows
-            const int bad = rzrr::first_illegal_drop(h_moves + h_offsets[g], (int)P, r->rows, r->dev.cols);
-            if (bad >= 0) {
-                const int32_t column = h_moves[h_offsets[g] + bad];
-                return rz_fail(RZ_ERR_ARG, column < 0 || column >= r->dev.cols ? "a move is outside the board" : "a column is played more often than the board has rows");
-            }
-        }
-        for (int p = h_offsets[g]; p < h_offsets[g + 1]; ++p) {
-            if (h_moves[p] < 0 || h_moves[p] >= A) return rz_fail(RZ_ERR_ARG, "a move is outside the board");
-            kept += h_keep[p] != 0;
-        }
-    }
-    const long long total = h_offsets[n_games];
-    if (kept == 0) return RZ_OK;
-    if (h_pi == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
-    // staging: offsets | base | winner | moves | keep | pi rows
-    const size_t o_off = 0, o_base = o_off + align16(((size_t)n_games + 1) * 4), o_win = o_base + align16((size_t)n_games * 4),
-                 o_moves = o_win + align16((size_t)n_games * 4), o_keep = o_moves + align16((size_t)total * 4),
-                 o_pi = o_keep + align16((size_t)total), bytes = o_pi + (size_t)kept * A * sizeof(float);
+    if (r->q != nullptr) return RZ_OK;
+    if (r->stored != 0) return rz_fail(RZ_ERR_ARG, "rz_replay_enable_values: the buffer holds positions stored without a value");
+    float *q = nullptr;
+    if (r->pool.alloc(&q, r->dev.capacity) != RZ_OK) return rz_fail(RZ_ERR_OOM, "hipMalloc failed (replay values)");
+    // every slot NaN (0x7FC00000): a position that never got a value keeps z as its target
+    if (hipMemsetD32Async((hipDeviceptr_t)q, 0x7FC00000, (size_t)r->dev.capacity, (hipStream_t)stream) != hipSuccess)
+        return rz_fail(RZ_ERR_HIP, "initialisation of the replay values failed");
+    r->q = q;
+    return RZ_OK;
+}
+
+int rz_replay_set_value_mix(rz_replay *r, double lam) {
+    if (r == nullptr) return rz_fail(RZ_ERR_ARG, "replay handle is NULL");
+    if (!(lam >= 0.0 && lam <= 1.0)) return rz_fail(RZ_ERR_ARG, "rz_replay_set_value_mix: lam %g not in [0, 1]", lam);
+    if (lam > 0.0 && r->q == nullptr) return rz_fail(RZ_ERR_ARG, "rz_replay_set_value_mix: lam > 0 needs the search values (rz_replay_enable_values)");
+    r->mix = lam;
+    return RZ_OK;
+}
+
+int rz_replay_update_values(rz_replay *r, const int32_t *d_where, int64_t n, const double *d_root_values, int64_t ticket, void *stream) {
+    RZ_ENTER(rp_ready, r);
+    if (r->q == nullptr) return rz_fail(RZ_ERR_ARG, "rz_replay_update_values: the buffer keeps no search values (rz_replay_enable_values)");
+    if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
+    if (!rzrr::ticket_current(ticket, r->stored)) return rz_fail(RZ_ERR_ARG, "stale ticket: positions were stored since rz_replay_positions");
+    if (n == 0) return RZ_OK;
+    if (d_where == nullptr || d_root_values == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    const unsigned blocks = (unsigned)((n + kMaxCells - 1) / kMaxCells);
+    hipLaunchKernelGGL(k_replay_update_q, dim3(blocks), dim3(kMaxCells), 0, (hipStream_t)stream, r->q, r->dev.capacity, d_where, d_root_values, (long long)n);
+    return rz_launched("k_replay_update_q");
+}
+
+int rz_replay_read_values(rz_replay *r, int64_t first, int64_t n, float *h_q, void *stream) {
+    RZ_ENTER(rp_ready, r);
+    if (r->q == nullptr) return rz_fail(RZ_ERR_ARG, "rz_replay_read_values: the buffer keeps no search values (rz_replay_enable_values)");
+    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "positions outside 0 .. count - 1");
+    if (n == 0) return RZ_OK;
+    if (h_q == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
-    RZ_TRY(r->stage.reserve(bytes, s));
-    char *h = (char *)r->stage.h, *d = (char *)r->stage.d;
-    memcpy(h + o_off, h_offsets, ((size_t)n_games + 1) * 4);
-    memcpy(h + o_base, base.data(), (size_t)n_games * 4);
-    memcpy(h + o_win, h_winner, (size_t)n_games * 4);
-    memcpy(h + o_moves, h_moves, (size_t)total * 4);
-    memcpy(h + o_keep, h_keep, (size_t)total);
-    memcpy(h + o_pi, h_pi, (size_t)kept * A * sizeof(float));
-    RZ_TRY(r->stage.upload(bytes, s));
-    const long long cap = r->dev.capacity, skip = kept > cap ? kept - cap : 0;
-    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_add<true> : k_replay_add<false>, dim3((unsigned)n_games), dim3(kMaxCells), 0, s, r->dev, (const int32_t *)(d + o_off), (const int32_t *)(d + o_base),
-                       (const int32_t *)(d + o_win), (const int32_t *)(d + o_moves), (const uint8_t *)(d + o_keep), (const float *)(d + o_pi),
-                       r->cursor, skip);
-    RZ_TRY(r->stage.launched(s, "k_replay_add"));
-    r->cursor = (r->cursor + kept) % cap;
-    r->count = r->count + kept > cap ? cap : r->count + kept;
-    r->stored += kept;
+    const long long cap = r->dev.capacity, start = (rp_oldest(r) + first) % cap;
+    const long long n1 = n < cap - start ? n : cap - start;   // up to the ring's end, then from its start
+    bool ok = hipMemcpyAsync(h_q, r->q + start, (size_t)n1 * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (n > n1) ok = ok && hipMemcpyAsync(h_q + n1, r->q, (size_t)(n - n1) * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return rz_fail(RZ_ERR_HIP, "read-back failed (replay values)");
     return RZ_OK;
 }
 
@@ -455,7 +554,11 @@ int rz_replay_gather(rz_replay *r, const int64_t *h_indices, const int64_t *d_in
         RZ_TRY(r->stage.upload((size_t)n * 8, s));
         idx = (const long long *)r->stage.d;
     }
-    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_gather<true> : k_replay_gather<false>, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
+    // (rz_replay_set_value_mix: at lam = 0 the kernels without q, whose zs is z)
+    auto kernel = rp_mixing(r) ? (rp_connect4(r) ? k_replay_gather<true, true> : k_replay_gather<false, true>)
+                               : (rp_connect4(r) ? k_replay_gather<true, false> : k_replay_gather<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(rp_block(r)), 0, s, r->dev, idx, rp_oldest(r), n_entries, d_states, d_pis, d_zs,
+                       rp_mixing(r) ? (const float *)r->q : (const float *)nullptr, r->mix);
     return h_indices != nullptr ? r->stage.launched(s, "k_replay_gather") : rz_launched("k_replay_gather");
 }
 
@@ -465,8 +568,11 @@ int rz_replay_sample(rz_replay *r, uint64_t seed, uint64_t step, int64_t n, floa
     const long long n_entries = r->dev.S * r->count;
     if (n_entries == 0) return rz_fail(RZ_ERR_ARG, "the replay buffer is empty");
     if (n == 0) return RZ_OK;
-    hipLaunchKernelGGL(rp_connect4(r) ? k_replay_sample<true> : k_replay_sample<false>, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
-                       (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs);
+    auto kernel = rp_mixing(r) ? (rp_connect4(r) ? k_replay_sample<true, true> : k_replay_sample<false, true>)
+                               : (rp_connect4(r) ? k_replay_sample<true, false> : k_replay_sample<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(rp_block(r)), 0, (hipStream_t)stream, r->dev, (unsigned long long)seed,
+                       (unsigned long long)step, rp_oldest(r), n_entries, d_states, d_pis, d_zs,
+                       rp_mixing(r) ? (const float *)r->q : (const float *)nullptr, r->mix);
     return rz_launched("k_replay_sample");
 }
 

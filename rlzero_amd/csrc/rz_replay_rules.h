@@ -87,6 +87,18 @@ RZR_FN int64_t slot_of_position(int64_t index, int64_t oldest, int64_t count, in
 // only while nothing was stored in between -- a slot may hold another position by then.
 RZR_FN bool ticket_current(int64_t ticket, int64_t stored) { return ticket == stored; }
 
+// ---- the value target (rz_replay_set_value_mix; rlzero_amd/replay.py: mixed_value_targets, the same bits): z of the game mixed
+// with the search's root value q of the position, (1 - lam) z + lam q.  In fp64, each product ROUNDED before the sum -- this file is
+// compiled with -ffp-contract=off on both sides; a fused multiply-add gives other bits (tests/test_value_targets_host.py shows
+// that it would be caught) -- and cast to float32 once.  A NaN q (a position stored without a value) leaves z as it is.
+RZR_FN float value_target(float z, float q, double lam) {
+    if (q != q) return z;
+    const double keep = (1.0 - lam) * (double)z, take = lam * (double)q;
+    return (float)(keep + take);
+}
+// ---- a refreshed q (k_replay_update_q): float32 of the fresh search's fp64 root value; a NaN (an unvisited root) writes nothing
+RZR_FN bool value_written(int64_t slot, int64_t capacity, double v) { return slot >= 0 && slot < capacity && v == v; }
+
 // ---- Connect4 (RZ_GAME_CONNECT4; k_replay_add<true>, rz_replay_add): a move is a COLUMN and the stone drops, a record holds CELLS
 // (cell = row * cols + column, row 0 at the bottom: Connect4Env.step).  The cell of ply q of a move list: as many rows up as the
 // earlier plies put stones into its column.  The kernel runs it over the move list in LDS, a thread per ply; everything behind it

@@ -1281,6 +1281,14 @@ class MCTSEngine(object):
         check(self.lib.rz_root_values(self.handle, _ptr(self._root_values), self.stream()), 'rz_root_values')
         return self._root_values.cpu().numpy()
 
+    def root_values_device(self):
+        """``root_values`` left on the device: the float64 [G, 2] tensor rz_root_values writes (valid on the current stream until the
+        next read-out).  Enqueues that one launch -- no host copy, no wait (Reanalyse's value refresh: DeviceReplay.update_values)."""
+        if getattr(self, '_root_values', None) is None:
+            self._root_values = self.torch.empty((self.n_games, 2), dtype=self.torch.float64, device=self.device)
+        check(self.lib.rz_root_values(self.handle, _ptr(self._root_values), self.stream()), 'rz_root_values')
+        return self._root_values
+
     def advance(self, moves):
         """update_with_move for every game: move >= 0 keep that subtree, -1 reset, -2 skip."""
         self.flush_deferred()   # (the kept subtree's prior blocks are copied: they must be written)
@@ -1363,6 +1371,7 @@ class MCTSEngine(object):
         self.play_cap_on = False      # (and the playout cap)
         self.play_match_on = False    # (and match mode)
         self.play_temp_on = False     # (and the temperature schedule)
+        self.play_values_on, self.play_values = False, None   # (and the ring of root values: play_set_root_values)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log
@@ -1471,6 +1480,24 @@ class MCTSEngine(object):
         check(self.lib.rz_play_set_temperatures(self.handle, ctypes.c_void_p(tab.ctypes.data) if tab.size else None, int(tab.size),
                                                 self.stream()), 'rz_play_set_temperatures')
         self.play_temp_on = True
+
+    def play_set_root_values(self, on=True):
+        """The root values of the move step (rz_play_set_root_values): allocates -- and owns -- the side ring float32 [ring_steps,
+        n_games] beside the log (pinned host memory where the log is, else device memory) and hands it to the draw; row r holds, for
+        every slot with a game, float32 of ``root_values()[:, 0]`` as the draw of log row r saw it, NaN for idle slots.  ``on``
+        False: off again.  After play_attach and BEFORE the first move step is enqueued or a whole-move graph captured (HipError
+        afterwards: the draw holds the ring as an argument), never while a match is on.  -> the tensor (``play_values``), or None."""
+        t = self.torch
+        if not on:
+            check(self.lib.rz_play_set_root_values(self.handle, None, self.stream()), 'rz_play_set_root_values')
+            self.play_values_on, self.play_values = False, None
+            return None
+        shape = (int(self.play_log.shape[0]), self.n_games)
+        ring = t.full(shape, float('nan'), dtype=t.float32)
+        ring = ring.pin_memory() if self.play_log_on_host else ring.to(self.device)
+        check(self.lib.rz_play_set_root_values(self.handle, ring.data_ptr(), self.stream()), 'rz_play_set_root_values')
+        self.play_values_on, self.play_values = True, ring
+        return ring
 
     def play_set_cap_order(self, longest_first):
         """Whether play_set_cap's searches follow the device's longest-first partition (default) or the slot order; before the move

@@ -33,6 +33,16 @@ def running(rows):
     return g_i, decode(rows[row_i, g_i]), int(on[-1].sum())
 
 
+def running_values(rows, side):
+    """The optional column of the log: the side ring of root values (rz_play_set_root_values), float32 [R, G] -- the same rows as
+    ``rows`` -> its entries of the RUNNING records, in running()'s order (a stalled slot's rows repeat its searched record's value)."""
+    side = np.asarray(side, dtype=np.float32)
+    if side.shape != rows.shape[:2]:
+        raise ValueError('the side ring\'s rows %r do not match the log\'s %r' % (side.shape, rows.shape[:2]))
+    row_i, g_i = np.nonzero((rows[..., 4] & PLAY_RUNNING) != 0)
+    return side[row_i, g_i]
+
+
 def check_moves(d, chosen):
     """Every move the device drew is the arbiter's (a stalled, resolved or resigning record holds no draw)."""
     wrong = ((d.flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED)) == 0) & (chosen != d.move)

@@ -29,7 +29,8 @@ rows).  What is refreshed and what is not:
 * the new row is the VISIT DISTRIBUTION ``N / sum(N)`` (``reanalysed_pi``), i.e. the reference's pi at temperature 1 up to rounding
   -- not its ``softmax(log(N + 1e-10))`` expression, which is not reproducible on the device: a documented deviation (bounded in
   tests/test_replay_reanalyse_host.py).  A ``pi_temperature`` or temperature schedule of the self-play run is NOT reapplied;
-* z is never refreshed: it is the outcome of the game that was played;
+* z is never refreshed: it is the outcome of the game that was played -- what ``targets='value'`` / ``'both'`` refresh is q, the
+  search's root value stored beside it ("Value targets from the search", below);
 * the fast plies of a playout cap are not in the buffer, so they are not refreshed either.
 
 Connect4 (``DeviceReplay((rows, cols), C, game='connect4')``; build-defined, the reference has no Connect4):
@@ -47,6 +48,16 @@ Connect4 (``DeviceReplay((rows, cols), C, game='connect4')``; build-defined, the
 * ``sample``, ``reanalyse_sample``, ``reanalysed_pi`` and the ticket are exactly Gomoku's: the draw of ``sample`` runs over the
   ``len(buffer)`` entries -- ``replay_index(seed, step, i, 2 * positions)`` --, ``reanalyse_sample`` draws over positions;
 * the contract: the entries are those of the trainer's host ``ReplayBuffer(2 * C, (rows, cols), game='connect4')`` for the same games.
+
+Value targets from the search (opt-in, both games: ``DeviceReplay(..., search_values=True)`` or ``enable_search_values()``).  Under the
+default selection rule the network steers the search through its value head alone, and z -- the outcome of ONE game played at
+T = 1 -- is a noisy target for it; the root's -W / N is an average over the search's evaluations.  With the option a float32 ``q``
+[capacity] sits beside the meta words: ``add`` stores ``Trajectory.root_values`` of the kept plies (NaN for a game without them),
+and ``set_value_mix(lam)`` makes ``gather`` / ``sample`` write ``zs = mixed_value_targets(z, q, lam)`` = (1 - lam) z + lam q (z where q
+is NaN).  ``ReplayReanalyser(..., targets='value' | 'both')`` rewrites q with the current network's search (``update_values``).
+The two q are not the same quantity: the self-play q comes from a REUSED subtree searched under Dirichlet noise, the refreshed q from
+a FRESH tree without noise at the reanalyser's ``n_playout`` simulations.  z itself is never rewritten.  With the option off nothing
+is allocated and every kernel launched is the one it was; at lam = 0 the kernels without q run, so zs is z bit for bit.
 """
 import ctypes
 
@@ -170,6 +181,36 @@ def reanalysed_pi(visits):
     return pi, written
 
 
+def mixed_value_targets(z, q, lam):
+    """The value target (1 - lam) z + lam q in numpy -- the arbiter of the device's bits (csrc/rz_replay_rules.h: value_target;
+    k_replay_gather / k_replay_sample with ``set_value_mix``) and the host route's own (Trajectory.training_samples(value_mix=)):
+    float64, each product rounded before the sum (numpy never fuses them), cast to float32 once; z where q is NaN.  z in {-1, 0, 1}
+    (any array), q float32 of the same shape, lam in [0, 1].  -> float32, the shape of z."""
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError('lam %r not in [0, 1]' % lam)
+    z32, q32 = np.asarray(z, dtype=np.float32), np.asarray(q, dtype=np.float32)
+    if z32.shape != q32.shape:
+        raise ValueError('z of shape %r, q of shape %r' % (z32.shape, q32.shape))
+    keep = np.float64(1.0 - lam) * z32.astype(np.float64)
+    take = np.float64(lam) * q32.astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        mixed = (keep + take).astype(np.float32)
+    return np.where(np.isnan(q32), z32, mixed)
+
+
+def kept_root_values(trajectories):
+    """float32 [kept plies]: ``Trajectory.root_values`` of the plies ``DeviceReplay.add`` keeps (every ply, or the full-budget plies
+    under a cap), in ``pack_positions``' order; NaN for the plies of a game without root values -- what ``read(values=True)`` returns."""
+    out = []
+    for t in trajectories:
+        P = len(t.moves)
+        keep = np.ones(P, dtype=bool) if t.full is None else np.asarray(t.full[:P], dtype=bool)
+        q = np.full(P, np.nan, dtype=np.float32) if getattr(t, 'root_values', None) is None else np.asarray(t.root_values, dtype=np.float32)
+        out.append(q[keep])
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.float32)
+
+
 def pack_positions(trajectories, board_size, game='gomoku'):
     """The raw records ``DeviceReplay.add`` stores for these games, formed on the host: (stones uint64 [N][2][4], meta int32 [N],
     pi float32 [N][A]) of the kept plies in order -- what ``DeviceReplay.read`` returns for them.  ``game='connect4'``,
@@ -213,7 +254,7 @@ class DeviceReplay(object):
     module docstring).  ``n_cells``, ``n_actions`` (the width of a pi row) and ``n_symmetries`` are the buffer's three sizes.
     No CPU fallback: HipError without a GPU."""
 
-    def __init__(self, board_size, capacity_positions, device='cuda:0', seed=0, game='gomoku'):
+    def __init__(self, board_size, capacity_positions, device='cuda:0', seed=0, game='gomoku', search_values=False):
         import torch
         self.torch = torch
         self.lib = _hip.load()
@@ -243,6 +284,32 @@ class DeviceReplay(object):
                                                           _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables_game')
         else:
             _hip.check(self.lib.rz_replay_set_tables(self.handle, _ptr(self.src_state), _ptr(self.src_pi), self._stream()), 'rz_replay_set_tables')
+        self.search_values, self.value_mix = False, 0.0
+        if search_values:
+            self.enable_search_values()
+
+    def enable_search_values(self):
+        """Keep the search's root value q of every position beside its meta word (rz_replay_enable_values: a float32 [capacity]
+        array, allocated here, every slot NaN) -- what ``set_value_mix`` mixes into zs and ``update_values`` refreshes.  Only while
+        the buffer is empty: ValueError once positions were stored without one."""
+        if self.search_values:
+            return
+        if self.ticket != 0:
+            raise ValueError('enable_search_values: the buffer holds positions stored without a value (enable it on an empty buffer)')
+        _hip.check(self.lib.rz_replay_enable_values(self.handle, self._stream()), 'rz_replay_enable_values')
+        self.search_values = True
+
+    def set_value_mix(self, lam):
+        """lam in [0, 1] of the value target ``gather`` / ``sample`` write: zs = mixed_value_targets(z, q, lam).  0 (the default):
+        zs is z, written by the kernels that never read q.  ValueError for lam outside [0, 1], and for lam > 0 on a buffer without
+        search values."""
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError('value mix %r not in [0, 1]' % lam)
+        if lam > 0.0 and not self.search_values:
+            raise ValueError('value mix %r > 0 on a buffer without search values: DeviceReplay(..., search_values=True)' % lam)
+        _hip.check(self.lib.rz_replay_set_value_mix(self.handle, lam), 'rz_replay_set_value_mix')
+        self.value_mix = lam
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -262,7 +329,9 @@ class DeviceReplay(object):
     def add(self, trajectories):
         """The positions of finished games (selfplay.Trajectory; ``pis`` float64 or float32), in order: every ply, or under a
         playout cap the plies searched with the full budget (``full``, as ``training_samples()`` keeps them -- the other plies
-        still place their stones).  One staging copy and one launch for all of them.  -> positions added."""
+        still place their stones).  One staging copy and one launch for all of them.  A buffer with search values takes
+        ``Trajectory.root_values`` of the kept plies along, like the pi rows; a game without them stores NaN, so its target stays z.
+        -> positions added."""
         trajectories = list(trajectories)
         A = self.n_actions
         offsets, moves, keeps, winners, rows = [0], [], [], [], []
@@ -291,6 +360,14 @@ class DeviceReplay(object):
         h_keep = np.ascontiguousarray(np.concatenate(keeps)) if keeps else np.zeros(0, dtype=np.uint8)
         h_win = np.asarray(winners, dtype=np.int32)
         h_pi = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, A), dtype=np.float32)
+        if self.search_values:
+            for t in trajectories:
+                if getattr(t, 'root_values', None) is not None and len(t.root_values) != len(t.moves):
+                    raise ValueError('game %d: %d root values for %d plies' % (t.game_id, len(t.root_values), len(t.moves)))
+            h_q = np.ascontiguousarray(kept_root_values(trajectories), dtype=np.float32)
+            _hip.check(self.lib.rz_replay_add_values(self.handle, len(trajectories), _ptr(h_off), _ptr(h_moves), _ptr(h_keep), _ptr(h_win),
+                                                     _ptr(h_pi), _ptr(h_q), self._stream()), 'rz_replay_add_values')
+            return int(h_keep.sum())
         _hip.check(self.lib.rz_replay_add(self.handle, len(trajectories), _ptr(h_off), _ptr(h_moves), _ptr(h_keep), _ptr(h_win), _ptr(h_pi),
                                           self._stream()), 'rz_replay_add')
         return int(h_keep.sum())
@@ -391,20 +468,44 @@ class DeviceReplay(object):
             raise ValueError('update_pi: %d rows of %d slots and %d rows of counts' % (n, int(where.shape[0]), int(visits.shape[0])))
         _hip.check(self.lib.rz_replay_update_pi(self.handle, where.data_ptr(), n, visits.data_ptr(), int(ticket), self._stream()), 'rz_replay_update_pi')
 
+    def update_values(self, where, root_values, ticket, n=None):
+        """q of slot ``where[i]`` := float32(``root_values[i][0]``) for the first ``n`` rows (default: all of ``where``), one launch:
+        where int32 [>= n] and root_values float64 [>= n, 2] (MCTSEngine.root_values_device), contiguous device tensors.  A row whose
+        where is negative or whose value is NaN writes nothing; stones, meta, pi and every other row stay as they are.  ``ticket``:
+        of the ``position_roots`` call that gave ``where`` -- HipError, and nothing written, if an ``add`` came in between."""
+        t = self.torch
+        if not self.search_values:
+            raise ValueError('update_values: the buffer keeps no search values: DeviceReplay(..., search_values=True)')
+        n = int(where.shape[0]) if n is None else int(n)
+        for name, x, dtype, cols in (('where', where, t.int32, None), ('root_values', root_values, t.float64, 2)):
+            if (not isinstance(x, t.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous()
+                    or x.dim() != (1 if cols is None else 2) or (cols is not None and x.shape[1] != cols)):
+                raise ValueError('update_values: %s must be a contiguous %s tensor on %s%s' % (name, str(dtype).split('.')[-1], self.device, '' if cols is None else ', [n, %d]' % cols))
+        if n < 0 or n > int(where.shape[0]) or n > int(root_values.shape[0]):
+            raise ValueError('update_values: %d rows of %d slots and %d rows of values' % (n, int(where.shape[0]), int(root_values.shape[0])))
+        _hip.check(self.lib.rz_replay_update_values(self.handle, where.data_ptr(), n, root_values.data_ptr(), int(ticket), self._stream()), 'rz_replay_update_values')
+
     def poll_errors(self):
         """The device's flag word (waits for the current stream), cleared by the call."""
         flags = ctypes.c_int32()
         _hip.check(self.lib.rz_replay_poll_errors(self.handle, ctypes.byref(flags), self._stream()), 'rz_replay_poll_errors')
         return flags.value
 
-    def read(self, first=0, n=None):
+    def read(self, first=0, n=None, values=False):
         """The raw records of positions ``first`` .. ``first + n - 1`` (oldest = 0), a synchronous copy: (stones uint64 [n][2][4] --
-        [0] the mover's, [1] the opponent's --, meta int32 [n], pi float32 [n][A])."""
+        [0] the mover's, [1] the opponent's --, meta int32 [n], pi float32 [n][A]).  ``values=True`` (a buffer with search values):
+        a 4-tuple, with q float32 [n] (NaN: none stored) behind them."""
         n = self.positions - first if n is None else int(n)
         stones = np.zeros((n, 2, _hip.BOARD_WORDS), dtype=np.uint64)
         meta = np.zeros(n, dtype=np.int32)
         pi = np.zeros((n, self.n_actions), dtype=np.float32)
         _hip.check(self.lib.rz_replay_read(self.handle, int(first), n, _ptr(stones), _ptr(meta), _ptr(pi), self._stream()), 'rz_replay_read')
+        if values:
+            if not self.search_values:
+                raise ValueError('read(values=True): the buffer keeps no search values: DeviceReplay(..., search_values=True)')
+            q = np.full(n, np.nan, dtype=np.float32)
+            _hip.check(self.lib.rz_replay_read_values(self.handle, int(first), n, _ptr(q), self._stream()), 'rz_replay_read_values')
+            return stones, meta, pi, q
         return stones, meta, pi
 
     def close(self):
@@ -429,7 +530,7 @@ class ReplayReanalyser(object):
 
       ``set_roots_device(reset_trees=True)`` -> ``set_active`` (all ones; in a short last chunk only its rows) -> ``simulate`` (the
       route the engine picks for the board: k_delta_res at 11 .. 16 rows, the resident k_trunk_split below) -> ``root_visits_device``
-      -> ``update_pi``
+      -> ``update_pi`` (and / or ``root_values_device`` -> ``update_values``: ``targets``)
 
     Nothing waits for the GPU, the error poll for indices given as a device tensor apart; ``check()`` reads the engine's and the
     network's error flags when the caller wants them (it waits).  The trees of a chunk are thrown away by the next chunk's
@@ -439,10 +540,20 @@ class ReplayReanalyser(object):
     ``update_pi`` carries the ticket ``position_roots`` gave out: if an ``add`` comes between them (from a ``timer`` hook, say) a slot may
     hold another position by then, and the call raises ``HipError`` instead of writing.  Two rows that name one position both write
     it; the search is deterministic, so they write the same bits.  ``timer``: None, or a callable ``timer(label)`` called on the
-    stream between the stages ('start', 'positions', then per chunk 'roots', 'search', 'update')."""
+    stream between the stages ('start', 'positions', then per chunk 'roots', 'search', 'update').
 
-    def __init__(self, net_module, replay, n_in_row, n_playout, slots=512, c_puct=5.0, seed=0, **engine_kw):
+    ``targets``: 'pi' (the default) refreshes the pi rows only; 'value' the stored root values q only (``update_values``, pi and meta
+    untouched); 'both' the two from the same search.  'value' / 'both' need a buffer with search values (ValueError here).  A
+    refreshed q is the root's -W / N of a FRESH tree without noise at ``n_playout`` simulations; the q self-play stored came from
+    a reused subtree under noise.  z is never rewritten."""
+
+    def __init__(self, net_module, replay, n_in_row, n_playout, slots=512, c_puct=5.0, seed=0, targets='pi', **engine_kw):
         from .engine import HipNetEvaluator, MCTSEngine
+        if targets not in ('pi', 'value', 'both'):
+            raise ValueError('targets %r: pi, value or both' % (targets, ))
+        if targets != 'pi' and not replay.search_values:
+            raise ValueError('targets=%r needs a buffer with search values: DeviceReplay(..., search_values=True)' % (targets, ))
+        self.targets = targets
         self.torch, self.replay = replay.torch, replay
         self.device = replay.device
         self.n_playout, self.slots = int(n_playout), int(slots)
@@ -499,7 +610,10 @@ class ReplayReanalyser(object):
         self._mark('roots')
         eng.simulate(self.evaluator, self.n_playout)
         self._mark('search')
-        self.replay.update_pi(where[a:a + G], eng.root_visits_device(), ticket, n=rows)
+        if self.targets != 'value':
+            self.replay.update_pi(where[a:a + G], eng.root_visits_device(), ticket, n=rows)
+        if self.targets != 'pi':   # (the same stream, no host wait: q := float32 of the fresh root's -W / N)
+            self.replay.update_values(where[a:a + G], eng.root_values_device(), ticket, n=rows)
         self._mark('update')
         self.sims_done += self.n_playout * rows
 

@@ -175,13 +175,17 @@ class Trajectory(object):
     """One finished game: what start_self_play returns, in compact form."""
 
     def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku', resigned=False, no_resign=False,
-                 resign_stats=None, fp_margin=np.nan, full=None):
+                 resign_stats=None, fp_margin=np.nan, full=None, root_values=None):
         """Resignation (BatchedSelfPlay.set_resign): ``resigned`` -- the game ended with the loser's resignation; ``moves`` / ``pis``
         are the plies actually played (the resigning search's pi is not recorded).  ``no_resign``: a calibration game (played
         out).  ``resign_stats``: float32 max(v_root, q_best) of every search of the game -- one more than the moves of a resigned
         game --, None with resignation off.  ``fp_margin``: a calibration game's selfplay.fp_margin, else NaN.
         Playout cap (BatchedSelfPlay.set_playout_cap): ``full`` -- a bool per search of the game, True where it had the full budget
-        (one entry more than the moves of a resigned game, like ``resign_stats``); None with the cap off."""
+        (one entry more than the moves of a resigned game, like ``resign_stats``); None with the cap off.
+        Root values (BatchedSelfPlay.set_root_values): ``root_values`` -- float32 [plies], aligned with ``moves`` / ``pis``: -W / N of
+        the root of the search that played the ply, the value the mover saw (MCTSEngine.root_values()[:, 0]); like ``pis`` the
+        resigning search of a resigned game is not recorded.  None with the option off."""
+        self.root_values = None if root_values is None else np.asarray(root_values, dtype=np.float32).reshape(-1)
         self.full = None if full is None else np.asarray(full, dtype=bool).reshape(-1)
         self.resigned, self.no_resign = bool(resigned), bool(no_resign)
         self.resign_stats = None if resign_stats is None else np.asarray(resign_stats, dtype=np.float32)
@@ -195,6 +199,8 @@ class Trajectory(object):
             pis = pis.astype(np.float64, copy=False)
         self.pis = pis.reshape(len(self.moves), -1) if len(self.moves) else pis.reshape(0, 0)
         self.winner = int(winner)
+        if self.root_values is not None and len(self.root_values) != len(self.moves):
+            raise ValueError('game %d: %d root values for %d plies' % (self.game_id, len(self.root_values), len(self.moves)))
 
     def _env(self):
         if self.game == 'connect4':
@@ -245,10 +251,19 @@ class Trajectory(object):
         """(winner, [(state, mcts_prob, z), ...]) -- start_self_play's return value."""
         return self.winner, list(zip(self.states(), list(self.pis), self.z()))
 
-    def training_samples(self):
+    def training_samples(self, value_mix=0.0):
         """[(state, mcts_prob, z), ...] of the plies a learner takes its policy target from: under a playout cap the plies whose
-        search had the full budget (``full``), each with its own state and z; every ply without a cap."""
-        samples = list(zip(self.states(), list(self.pis), self.z()))
+        search had the full budget (``full``), each with its own state and z; every ply without a cap.  ``value_mix`` = lam > 0 on a
+        game with ``root_values``: the third element is replay.mixed_value_targets(z, root_values, lam) -- (1 - lam) z + lam q, float32,
+        what the device buffer's kernels write (DeviceReplay.set_value_mix) -- instead of z; without root values, or at 0, z as it is."""
+        value_mix = float(value_mix)
+        if not 0.0 <= value_mix <= 1.0:
+            raise ValueError('value_mix %r not in [0, 1]' % value_mix)
+        targets = self.z()
+        if value_mix > 0.0 and self.root_values is not None:
+            from .replay import mixed_value_targets
+            targets = mixed_value_targets(targets, self.root_values, value_mix)
+        samples = list(zip(self.states(), list(self.pis), targets))
         if self.full is None:
             return samples
         return [sm for sm, f in zip(samples, self.full[:len(self.moves)]) if f]
@@ -430,7 +445,9 @@ class SelfPlayReader(object):
         self.book = SlotBook(n_slots, max_plies, resolve, dict(
             pi=(np.float64, (n_actions, ), 'move'),
             stat=(np.float32, (), 'search'),    # resignation statistic of every search (set_resign)
-            full=(bool, (), 'search')))         # full budget of every search (set_playout_cap)
+            full=(bool, (), 'search'),          # full budget of every search (set_playout_cap)
+            q=(np.float32, (), 'search')))      # root value of every search (set_root_values; NaN with it off)
+        self.root_values_on = False   # set_root_values: the side ring of the log is read and Trajectory.root_values formed
         self.slot_game, self.slot_ply = self.book.slot_game, self.book.slot_ply
         self.sims_done = 0
         self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
@@ -476,10 +493,13 @@ class SelfPlayReader(object):
         return dict(resigned=resigned, no_resign=no_resign, resign_stats=stats,
                     fp_margin=fp_margin(stats, winner) if no_resign else np.nan)
 
-    def read_rows(self, rows, lo=0):
+    def read_rows(self, rows, lo=0, values=None):
         """Log rows int32 [R, G, words] of the slots ``lo`` .. ``lo + G - 1``, oldest first -> (the trajectories of the games that
         ended in them, the RUNNING records of the last row).  pi is formed here, from the logged visit counts with the reference's
-        expression, and every move and flag of the device is verified against this side's draw on the same key."""
+        expression, and every move and flag of the device is verified against this side's draw on the same key.  ``values``: the
+        same rows of the side ring of root values, float32 [R, G] (set_root_values; required while it is on)."""
+        if self.root_values_on and values is None:
+            raise ValueError('root values are on (set_root_values): read_rows needs the side ring\'s rows')
         g_i, d, last_running = playlog.running(rows)
         if g_i.size == 0:
             return [], last_running
@@ -492,12 +512,15 @@ class SelfPlayReader(object):
         self.full_plies += full
         if self.resign_on:
             self.resign_would += playlog.check_resignation(d, self.resign_threshold, self._calibration(d.game))
-        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=(d.flags & PLAY_FULL) != 0))
+        q = playlog.running_values(rows, values) if self.root_values_on else np.full(g_i.shape, np.nan, dtype=np.float32)
+        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=(d.flags & PLAY_FULL) != 0, q=q))
         done = []
         for f in finished:
             extra = self._resign_record(f.columns['stat'], f.winner, not f.resigned and bool(self._calibration(f.game)), f.resigned)
             if cap is not None:
                 extra['full'] = f.columns['full']
+            if self.root_values_on:   # (a resigned game has one search more than moves: the resigning one is not recorded)
+                extra['root_values'] = f.columns['q'][:len(f.moves)]
             done.append(Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
                                    game=self.geometry[2], **extra))
         return done, last_running
@@ -565,6 +588,21 @@ class BatchedSelfPlay(SelfPlayReader):
         self.slot_stats = [[] for _ in range(G)]   # resignation statistic of every search of the slot's game (set_resign)
         self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
         self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
+        self.slot_values = [[] for _ in range(G)]   # root value of every search that played a ply of the slot's game (set_root_values)
+
+    def set_root_values(self, on=True):
+        """Keep the root value of every search that plays a ply (an opt-in extension: the learner's value target can mix it with z,
+        DeviceReplay.set_value_mix / Trajectory.training_samples(value_mix=)), for every lane and BOTH loops (run, run_device):
+        Trajectory.root_values, float32 [plies] -- float32 of MCTSEngine.root_values()[:, 0], -W / N of the root, as the draw saw it.
+        run reads it after its search; the device move step writes it into a side ring of its log (rz_play_set_root_values), which
+        is an argument of the draw: an attached object attaches again (same settings) when the option changes.  Games, moves, pis
+        and the log's records do not depend on it.  ValueError while a lane's engine is in match mode."""
+        on = bool(on)
+        if on and any(getattr(lane.eng, 'play_match_on', False) for lane in self.lanes):
+            raise ValueError('a lane\'s engine is in match mode (play_set_match): a match logs no root values')
+        changed, self.root_values_on = on != self.root_values_on, on
+        if self._dev_on and changed:
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)
 
     def set_playout_cap(self, n_fast, p_full=None):
         """Playout cap randomization (KataGo, Wu 2019, section 3.1; an opt-in extension) for every lane and BOTH loops (run,
@@ -664,7 +702,7 @@ class BatchedSelfPlay(SelfPlayReader):
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
                     deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None,
-                    temperature_schedule=None, pi_temperature=None, **engine_kw):
+                    temperature_schedule=None, pi_temperature=None, root_values=False, **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -683,7 +721,7 @@ class BatchedSelfPlay(SelfPlayReader):
         checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU).
         ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign.  ``playout_cap``: None (off) or (n_fast, p_full):
         set_playout_cap.  ``temperature_schedule``: None (off) or a table of per-ply temperatures, with ``pi_temperature``:
-        set_temperature_schedule."""
+        set_temperature_schedule.  ``root_values``: set_root_values."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -752,6 +790,8 @@ class BatchedSelfPlay(SelfPlayReader):
             sp.set_playout_cap(*playout_cap)
         if temperature_schedule is not None or pi_temperature is not None:
             sp.set_temperature_schedule(temperature_schedule, pi_temperature=pi_temperature)
+        if root_values:
+            sp.set_root_values(True)
         if before_warm is not None:
             before_warm(sp)
         sp.warm_graphs()
@@ -794,6 +834,7 @@ class BatchedSelfPlay(SelfPlayReader):
             self.slot_pis[s] = []
             self.slot_stats[s] = []
             self.slot_full[s] = []
+            self.slot_values[s] = []
         # a game's Dirichlet noise (read by the PUCT rule only), like its move draws, is keyed by (seed, game id): the trajectory
         # does not depend on the slot, lane or GPU the game is played on
         with np.errstate(over='ignore'):
@@ -903,10 +944,12 @@ class BatchedSelfPlay(SelfPlayReader):
             self.full_plies += len(running)
         moves = np.full(eng.n_games, -2, dtype=np.int32)
         resigned = running[:0]
-        if self.resign_on and len(running):
-            # the rule of k_play_draw on the same fp64 values: the mover resigns when v_root and q_best are both below the threshold
+        vals = None
+        if (self.resign_on or self.root_values_on) and len(running):
             with self._on(lane):
                 vals = lane.eng.root_values()[running - lo]
+        if self.resign_on and len(running):
+            # the rule of k_play_draw on the same fp64 values: the mover resigns when v_root and q_best are both below the threshold
             stat = np.maximum(vals[:, 0], vals[:, 1]).astype(np.float32)   # (NaN when either is)
             fire = (vals[:, 0] < self.resign_threshold) & (vals[:, 1] < self.resign_threshold)
             calib = self._calibration(self.slot_game[running])
@@ -915,7 +958,10 @@ class BatchedSelfPlay(SelfPlayReader):
                 self.slot_stats[s_].append(stat[i])
             resigned = running[fire & ~calib]
             moves[resigned - lo] = -1    # (no move; the tree is dropped, like reset_player at the end of a game)
-            running = running[~(fire & ~calib)]
+            running, vals = running[~(fire & ~calib)], vals[~(fire & ~calib)]
+        if self.root_values_on and len(running):   # (k_play_draw's float32 of the same fp64 value; a resigning search is not recorded)
+            for s_, v in zip(running, vals[:, 0].astype(np.float32)):
+                self.slot_values[s_].append(v)
         if len(running):
             us = move_uniform(self.seed, self.slot_game[running], self.slot_ply[running])
             taken = self.cell_taken[running]
@@ -944,6 +990,8 @@ class BatchedSelfPlay(SelfPlayReader):
                 extra = self._resign_record(self.slot_stats[s], win, bool(self._calibration(self.slot_game[s])), quit_)
                 if self.playout_cap is not None:
                     extra['full'] = self.slot_full[s]
+                if self.root_values_on:
+                    extra['root_values'] = self.slot_values[s]
                 done.append(Trajectory(self.slot_game[s], eng.board_size, eng.n_in_row,
                                        self.slot_moves[s], self.slot_pis[s], win, game=eng.game, **extra))
                 self.slot_game[s] = -1
@@ -1106,11 +1154,18 @@ class BatchedSelfPlay(SelfPlayReader):
                 lane.eng.play_set_cap_order(self.cap_longest_first)
                 self._apply_option(self._cap_option(), attaching=lane)
                 self._apply_option(self._temperature_option(), attaching=lane)
+                if self.root_values_on:   # (an argument of the draw: before the first move step is enqueued or captured)
+                    lane.eng.play_set_root_values(True)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
             lane.host_log = lane.eng.play_log if lane.eng.play_log_on_host else t.empty((int(ring_steps), lane.eng.n_games, words), dtype=t.int32, pin_memory=True)
             lane.host_np = lane.host_log.numpy()
+            lane.values_np = None   # (set_root_values: the side ring's rows, where the log's are)
+            if self.root_values_on:
+                ring = lane.eng.play_values
+                lane.host_values = ring if lane.eng.play_log_on_host else t.empty(tuple(ring.shape), dtype=t.float32, pin_memory=True)
+                lane.values_np = lane.host_values.numpy()
             lane.uncopied = []          # rows written by enqueued moves, their read-back not enqueued yet
             lane.inflight = []          # [(rows, event)] read-backs enqueued, oldest first
             lane.last_running = -1      # RUNNING records in the last row read (-1: none read yet)
@@ -1155,6 +1210,8 @@ class BatchedSelfPlay(SelfPlayReader):
                     end += 1
                 if not lane.eng.play_log_on_host:
                     lane.host_log[rows[at]:rows[end - 1] + 1].copy_(lane.eng.play_log[rows[at]:rows[end - 1] + 1], non_blocking=True)
+                    if lane.values_np is not None:
+                        lane.host_values[rows[at]:rows[end - 1] + 1].copy_(lane.eng.play_values[rows[at]:rows[end - 1] + 1], non_blocking=True)
                 at = end
             ev = self.torch.cuda.Event()
             ev.record(lane.stream)
@@ -1199,7 +1256,8 @@ class BatchedSelfPlay(SelfPlayReader):
         if not rows:
             return []
         # (host_np[rows] is a copy: the pinned rows may be overwritten from now on)
-        done, lane.last_running = self.read_rows(lane.host_np[rows], lane.slots.start)
+        done, lane.last_running = self.read_rows(lane.host_np[rows], lane.slots.start,
+                                                 values=None if lane.values_np is None else lane.values_np[rows])
         return done
 
     def _resolve(self, slot, move):

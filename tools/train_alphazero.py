@@ -169,7 +169,7 @@ class TrainPipeline:
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
                  device_replay=False, temperature_schedule=None, pi_temperature=None, reanalyse=None, reanalyse_slots=512,
-                 reanalyse_playouts=None, game='gomoku', board_width=None):
+                 reanalyse_playouts=None, game='gomoku', board_width=None, value_mix=0.0, reanalyse_targets='pi'):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -201,7 +201,13 @@ class TrainPipeline:
         ``n_playout``).
         ``game``: 'gomoku' or 'connect4' -- Connect4 on ``board_size`` rows x ``board_width`` columns (default 7), an action is a
         column; batched mode on one rank only, without a gate match (the reference flow's GameControl and rlzero_amd.match are
-        Gomoku's); both replay buffers hold its two symmetries (ReplayBuffer)."""
+        Gomoku's); both replay buffers hold its two symmetries (ReplayBuffer).
+        ``value_mix`` = lam in [0, 1] (batched mode on one rank, either buffer, both games; an opt-in extension): 0 = off -- nothing
+        is allocated, launched or stored differently --; lam > 0: self-play keeps the root value q of every search
+        (BatchedSelfPlay.set_root_values) and the learner's value target is (1 - lam) z + lam q (rlzero_amd.replay.mixed_value_targets:
+        DeviceReplay.set_value_mix, or Trajectory.training_samples(value_mix=) into the host buffer).  ValueError with several
+        ranks: the ranks' payload carries no root values.  ``reanalyse_targets``: 'pi' (default), 'value' or 'both' -- what a refresh
+        rewrites (ReplayReanalyser(targets=)); 'value' / 'both' need ``value_mix`` > 0, whose buffer keeps q."""
         if game not in ('gomoku', 'connect4'):
             raise ValueError('game %r: gomoku or connect4' % (game, ))
         self.game_kind = game
@@ -236,6 +242,16 @@ class TrainPipeline:
         if self.reanalyse is not None and (self.reanalyse_slots < 1 or self.reanalyse_playouts < 1):
             raise ValueError('reanalyse_slots and reanalyse_playouts must be >= 1')
         self._reanalyser = None
+        self.value_mix = float(value_mix)
+        if not 0.0 <= self.value_mix <= 1.0:
+            raise ValueError('value_mix %r not in [0, 1]' % (value_mix, ))
+        if self.value_mix > 0.0 and selfplay_games_in_flight <= 0:
+            raise ValueError('the value mix is a batched self-play option: selfplay_games_in_flight must be > 0')
+        if reanalyse_targets not in ('pi', 'value', 'both'):
+            raise ValueError('reanalyse_targets %r: pi, value or both' % (reanalyse_targets, ))
+        if reanalyse_targets != 'pi' and not self.value_mix > 0.0:
+            raise ValueError('reanalyse_targets %r refreshes the stored root values: it needs value_mix > 0' % (reanalyse_targets, ))
+        self.reanalyse_targets = reanalyse_targets
         if gate_against is not None and selfplay_games_in_flight <= 0:
             raise ValueError('the gate match is a batched-mode option: selfplay_games_in_flight must be > 0')
         self.gate_against, self._gate, self._gate_rounds = gate_against, None, 0
@@ -245,6 +261,8 @@ class TrainPipeline:
         if resign != 'off' and selfplay_games_in_flight <= 0:
             raise ValueError('resignation is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.rank, self.world = self._init_ranks()
+        if self.world > 1 and self.value_mix > 0.0:
+            raise ValueError('the value mix runs on one rank: the payload the ranks gather carries no root values (%d ranks)' % self.world)
         if self.world > 1 and game == 'connect4':
             raise ValueError('Connect4 trains on one rank: several ranks are a Gomoku option')
         if self.world > 1 and selfplay_games_in_flight <= 0:
@@ -287,7 +305,9 @@ class TrainPipeline:
                 raise ValueError('the device replay buffer needs a GPU (this process runs on %s)' % (self.device, ))
             if self.rank == 0:   # (rank 0 holds the buffer, as with the host one; sized like the batched mode's default: one round)
                 from rlzero_amd.replay import DeviceReplay
-                self.data_buffer = DeviceReplay(self.board_size, max(1, self.buffer_size // self.n_symmetries), device=str(self.device), game=game)
+                self.data_buffer = DeviceReplay(self.board_size, max(1, self.buffer_size // self.n_symmetries), device=str(self.device), game=game,
+                                                search_values=self.value_mix > 0.0)
+                self.data_buffer.set_value_mix(self.value_mix)
         self.pure_mcts_playout_num = 100
         self.selfplay_games_in_flight = selfplay_games_in_flight
         if game == 'connect4':
@@ -392,7 +412,8 @@ class TrainPipeline:
                 self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
                 device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
-                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature, **self._game_kw())
+                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature,
+                root_values=self.value_mix > 0.0, **self._game_kw())
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
         if self.resign_mode != 'off':
             # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
@@ -446,6 +467,8 @@ class TrainPipeline:
         buffer the trajectory itself: its positions are formed on the device from the move list (DeviceReplay.add)."""
         if self.device_replay:
             return t
+        if self.value_mix > 0.0:   # (the mixed value target in z's place; under a cap the full-budget plies, as below)
+            return t.winner, t.training_samples(value_mix=self.value_mix)
         return t.as_reference_tuple() if self.playout_cap is None else (t.winner, t.training_samples())
 
     def _cap_round(self, trajs):
@@ -584,7 +607,7 @@ class TrainPipeline:
             from rlzero_amd.replay import ReplayReanalyser
             self._reanalyser = ReplayReanalyser(self.alphazero_agent.policy_value_net, self.data_buffer, self.n_in_row,
                                                 self.reanalyse_playouts, slots=self.reanalyse_slots, c_puct=self.c_puct,
-                                                seed=self.selfplay_seed)
+                                                seed=self.selfplay_seed, targets=self.reanalyse_targets)
         self._reanalyser.refresh_weights()
         done = self._reanalyser.reanalyse_all() if self.reanalyse == 'all' else self._reanalyser.reanalyse_sample(self.reanalyse)
         self._reanalyser.check()
@@ -797,6 +820,16 @@ def positive_float_arg(text):
     return value
 
 
+def value_mix_of(args):
+    """--value-mix of parsed arguments (0.0 when it was not given)."""
+    return float(getattr(args, 'value_mix', 0.0))
+
+
+def reanalyse_targets_of(args):
+    """--reanalyse-targets of parsed arguments ('pi' when it was not given)."""
+    return getattr(args, 'reanalyse_targets', 'pi')
+
+
 def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku (or, --game connect4, Connect4) on MI355X (no arguments: the reference script\'s run)')
@@ -836,7 +869,22 @@ def parse_args(argv=None):
                          'with the current network and refresh their policy targets (visit distribution at T = 1; z is kept)')
     ap.add_argument('--reanalyse-slots', type=int, default=512, metavar='G', help='positions searched per batch of a refresh')
     ap.add_argument('--reanalyse-playouts', type=int, default=None, metavar='P', help='simulations of a refreshing search (default: --playouts)')
+    # (the two options below stay out of the namespace unless given -- argparse.SUPPRESS: value_mix_of / reanalyse_targets_of read them)
+    ap.add_argument('--value-mix', type=float, default=argparse.SUPPRESS, metavar='L',
+                    help='batched mode on one GPU: the value target (1 - L) z + L q, q the root value of the search that played the ply '
+                         '(kept by self-play); 0 = z alone, the default')
+    ap.add_argument('--reanalyse-targets', choices=('pi', 'value', 'both'), default=argparse.SUPPRESS,
+                    help='with --reanalyse: refresh the policy targets, the stored root values q (needs --value-mix > 0) or both')
     args = ap.parse_args(argv)
+    value_mix, targets = value_mix_of(args), reanalyse_targets_of(args)
+    if not 0.0 <= value_mix <= 1.0:
+        ap.error('--value-mix: L in [0, 1]')
+    if value_mix > 0.0 and args.games_in_flight <= 0:
+        ap.error('--value-mix needs --games-in-flight > 0 (batched self-play)')
+    if targets != 'pi' and not args.reanalyse:
+        ap.error('--reanalyse-targets needs --reanalyse')
+    if targets != 'pi' and not value_mix > 0.0:
+        ap.error('--reanalyse-targets %s refreshes the stored root values: it needs --value-mix > 0' % targets)
     if args.game == 'connect4':
         if args.board_width is None:
             args.board_width = 7
@@ -883,8 +931,11 @@ def parse_args(argv=None):
     return args
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
+    if value_mix_of(args) > 0.0 and (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+        raise ValueError('--value-mix runs on one rank: the payload the ranks gather carries no root values (--gpus %d, WORLD_SIZE %s)'
+                         % (args.gpus, os.environ.get('WORLD_SIZE', '1')))
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.seed is not None:   # a reproducible run: initial weights, random.sample of the replay buffer, numpy draws
@@ -898,7 +949,7 @@ def main():
                          batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay,
                          temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature,
                          reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts,
-                         game=args.game, board_width=args.board_width)
+                         game=args.game, board_width=args.board_width, value_mix=value_mix_of(args), reanalyse_targets=reanalyse_targets_of(args))
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
