@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 44
+#define RZ_ABI_VERSION 45
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -73,11 +73,13 @@ enum {
     RZ_FLAG_ILLEGAL_MOVE = 4,
     RZ_FLAG_LOGTAB = 8,
     RZ_FLAG_INTERNAL = 16,
-    RZ_FLAG_REUSE_DROPPED = 32 /* NOT an error: rz_advance_roots found the kept subtree larger than the carry limit (see
+    RZ_FLAG_REUSE_DROPPED = 32,/* NOT an error: rz_advance_roots found the kept subtree larger than the carry limit (see
                                   rz_config.pool_factor: more than int(pool_factor * n_playout) + 7 expanded nodes for a
                                   pool_factor * n_playout without a fraction, or too many prior floats / record slots) and
                                   restarted that game's search from a fresh root (the reference's tree is unbounded,
                                   alphazero_mcts.py:96-103); counted in rz_stats.reuse_dropped, part of rz_stats.error_flags */
+    RZ_FLAG_QUEUE_FULL = 64    /* rz_play_queue_push (ABI 45) would have overwritten a game id that no slot had claimed: nothing was
+                                  written (an error of the engine, booked on game 0) */
 };
 
 typedef struct rz_engine rz_engine;
@@ -478,6 +480,19 @@ typedef struct rz_play_config {
 } rz_play_config;
 /* Attach (allocates the per-slot state on first use; every slot idle, inactive, with a fresh tree; move step counter 0). */
 int rz_play_attach(rz_engine *e, const rz_play_config *cfg);
+/* The queue of game ids as a RING (ABI 45; for a collection that never stops the device: ids are appended while games run).
+ * rz_play_queue_ring(e, capacity): from now on d_queue_ids holds `capacity` entries (the caller's to provide) and k_play_apply reads
+ * the entry of head at head mod capacity (rz_play.h: queue_slot); head and the valid count stay ever-growing int32 counts.
+ * Capacity 0 -- the default after every rz_play_attach -- is the linear queue.  Every engine (lane) that shares the queue takes the
+ * same capacity.  The capacity is a kernel ARGUMENT of the move step: valid after rz_play_attach and before the first move step is
+ * enqueued or captured, RZ_ERR_ARG afterwards.
+ * rz_play_queue_push(e, first_id, count, stream): ONE small launch on `stream`, no host wait -- ids first_id .. first_id + count - 1
+ * go behind the valid count, then the count is raised (vector stores, a fence, the count last: a k_play_apply that sees the new
+ * count reads the ids).  The caller orders the push before the move steps that are to see it on other streams.  A push that would
+ * overwrite an entry no slot has claimed, or take the valid count past the int32 range (rz_play.h: queue_room), writes nothing and
+ * sets RZ_FLAG_QUEUE_FULL.  RZ_ERR_ARG for count > capacity, a negative count or id, and on a linear queue; count 0 launches nothing. */
+int rz_play_queue_ring(rz_engine *e, int32_t capacity);
+int rz_play_queue_push(rz_engine *e, int64_t first_id, int32_t count, void *stream);
 /* After the search of a move, BEFORE rz_deferred_flush: read the root visits into the log, draw (or stall, or take a resolved
  * move).  One launch. */
 int rz_play_draw(rz_engine *e, void *stream);

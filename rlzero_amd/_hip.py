@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -21,7 +21,7 @@ NET_FLAG_F16_RANGE = 1
 NET_HEADS_AUTO, NET_HEADS_F32, NET_HEADS_SPLIT_32, NET_HEADS_SPLIT_64, NET_HEADS_SPLIT_PARTS, NET_HEADS_IN_TRUNK = 0, 1, 2, 3, 4, 5
 EVAL_V0, EVAL_VLIN = 0, 1
 FLAG_NAMES = {1: 'arena full', 2: 'block queue full', 4: 'illegal move', 8: 'ln table too short',
-              16: 'internal'}
+              16: 'internal', 64: 'queue of game ids full'}
 FLAG_REUSE_DROPPED = 32  # not an error: a kept subtree exceeded the arena's carry limit and was dropped (counted)
 
 
@@ -171,6 +171,8 @@ _SIGNATURES = {
     'rz_advance_roots': (c_int, [P, P, P]),
     'rz_step_games': (c_int, [P, P, P, P, P]),
     'rz_play_attach': (c_int, [P, POINTER(RzPlayConfig)]),
+    'rz_play_queue_ring': (c_int, [P, c_int32]),
+    'rz_play_queue_push': (c_int, [P, c_int64, c_int32, P]),
     'rz_play_draw': (c_int, [P, P]),
     'rz_play_apply': (c_int, [P, P]),
     'rz_play_set_resign': (c_int, [P, c_double, c_double, P]),

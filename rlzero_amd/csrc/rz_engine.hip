@@ -1281,6 +1281,7 @@ struct Play {
     const int32_t *open_to_move, *open_last;   // [n_open]
     int n_open;
     int match_on;              // rz_play_set_match in force: the kernels read the table and the pair's uniform (else never)
+    int queue_cap;             // rz_play_queue_ring: queue_ids is a ring of this many entries (0: the linear queue)
 };
 namespace ry = rzplay;   // rz_play.h: the move step's rules, the record and a slot's decision (tested on the CPU)
 
@@ -1434,7 +1435,7 @@ __global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) 
     while (head < Y.queue_ctl[1]) {
         const int seen = atomicCAS(&Y.queue_ctl[0], head, head + 1);
         if (seen == head) {
-            gid = Y.queue_ids[head];
+            gid = Y.queue_ids[ry::queue_slot(head, Y.queue_cap)];
             break;
         }
         head = seen;
@@ -1548,6 +1549,25 @@ __global__ void k_play_set_resign(double *resign, double threshold, double disab
         resign[1] = disabled_frac;
     }
 }
+// rz_play_queue_push: ids first .. first + count - 1 behind the valid count of the ring, then the count raised -- one workgroup; the ids
+// are written, fenced, and only then counted, so a k_play_apply that sees the new count reads them.  A push that would overwrite an
+// id no slot has claimed (ry::queue_room) writes nothing and raises RZ_FLAG_QUEUE_FULL.
+__global__ __launch_bounds__(256) void k_play_push(Dev E, Play Y, int64_t first, int count) {
+    int64_t *ids = const_cast<int64_t *>(Y.queue_ids);
+    const int head = Y.queue_ctl[0], valid = Y.queue_ctl[1];
+    if (count > ry::queue_room(head, valid, Y.queue_cap)) {
+        if (threadIdx.x == 0) {
+            atomicOr(&E.err[0], RZ_FLAG_QUEUE_FULL);
+            atomicOr(E.err_any, RZ_FLAG_QUEUE_FULL);
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < count; i += blockDim.x) ids[ry::queue_slot(valid + i, Y.queue_cap)] = first + i;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) Y.queue_ctl[1] = valid + count;
+}
+
 __global__ void k_play_no_draw(Play Y) { Y.step_ab[1] = Y.step_ab[0]; }   // rz_play_apply without a draw: the step k_play_apply reads
 
 __global__ void k_play_stop(Dev E, Play Y) {
@@ -2324,6 +2344,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.resign_on = 0;   // (resignation is off after every attach: rz_play_set_resign)
     Y.cap_on = 0;      // (and so is the playout cap: rz_play_set_cap)
     Y.match_on = 0;    // (and match mode: rz_play_set_match)
+    Y.queue_cap = 0;   // (and the queue of game ids is the linear one: rz_play_queue_ring)
     e->play_margin_cfg = cfg->stall_margin;
     Y.temp_on = 0;     // (and the temperature schedule: rz_play_set_temperatures)
     Y.n_full = e->cfg.n_playout;
@@ -2361,6 +2382,26 @@ int rz_play_set_root_values(rz_engine *e, float *d_ring, void *stream) {
     }
     e->play_vring = d_ring;
     return RZ_OK;
+}
+
+int rz_play_queue_ring(rz_engine *e, int32_t capacity) {
+    RZ_ENTER_PLAY(e);
+    if (capacity < 0) return rz_fail(RZ_ERR_ARG, "rz_play_queue_ring: capacity %d is negative", capacity);
+    // the capacity is a kernel argument of the move step: one enqueued -- or captured into a whole-move graph -- keeps the one it had
+    if (e->play_steps > 0 || e->play_drawn) return rz_fail(RZ_ERR_ARG, "rz_play_queue_ring: a move step has been enqueued since rz_play_attach (attach again)");
+    e->play.queue_cap = capacity;
+    return RZ_OK;
+}
+
+int rz_play_queue_push(rz_engine *e, int64_t first_id, int32_t count, void *stream) {
+    RZ_ENTER_PLAY(e);
+    const int cap = e->play.queue_cap;
+    if (cap <= 0) return rz_fail(RZ_ERR_ARG, "rz_play_queue_push: the queue is linear (call rz_play_queue_ring first)");
+    if (first_id < 0) return rz_fail(RZ_ERR_ARG, "rz_play_queue_push: first id %lld is negative", (long long)first_id);
+    if (count < 0 || count > cap) return rz_fail(RZ_ERR_ARG, "rz_play_queue_push: %d ids for a ring of %d", count, cap);
+    if (count == 0) return RZ_OK;
+    k_play_push<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(e->dev, e->play, first_id, count);
+    return rz_launched("k_play_push");
 }
 
 int rz_play_draw(rz_engine *e, void *stream) {

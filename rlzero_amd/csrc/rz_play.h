@@ -116,6 +116,19 @@ RZY_FN Draw draw(const double *e, int A, double u, double margin) {
     return d;
 }
 
+// ---- the queue of game ids (rz_play_queue_ring): head and valid count are ever-growing int32 counts, 0 <= head <= valid; with a
+// capacity the entry of count c is c mod capacity, without one (0: the linear queue) it is c itself
+RZY_FN int queue_slot(int count, int capacity) { return capacity > 0 ? count % capacity : count; }
+// how many ids rz_play_queue_push may write behind `valid`: the ring's entries that hold no unclaimed id, and never more than the
+// counts have left below the int32 limit (a push beyond either writes nothing); 0 for counts that are no queue's
+RZY_FN int queue_room(int head, int valid, int capacity) {
+    if (capacity <= 0 || head < 0 || valid < head) return 0;
+    const int64_t free_entries = (int64_t)capacity - ((int64_t)valid - (int64_t)head);
+    const int64_t counts_left = (int64_t)INT32_MAX - (int64_t)valid;
+    const int64_t room = free_entries < counts_left ? free_entries : counts_left;
+    return room > 0 ? (int)room : 0;
+}
+
 // ---- a slot's move step
 enum { kIdle = 0, kRunning = 1, kStalled = 2 };   // Play::state
 constexpr int kKeepAll = -2;      // Play::keep: no move -- the whole tree stays

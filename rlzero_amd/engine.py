@@ -11,8 +11,10 @@ One simulation step of all games = what the reference does once per game in
     evaluator           policy_value_fn on the batch of leaves
     rz_expand_backup    expand / terminal value + update_recursive
 """
+import contextlib
 import ctypes
 import functools
+import gc
 import os
 
 import numpy as np
@@ -602,6 +604,22 @@ class HostEvaluator(object):
         eng.value64.copy_(torch.from_numpy(values))
         eng.logp.copy_(torch.from_numpy(probs))
         return eng.logp, eng.value64
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """Around a stream capture: what Python's cycle collector finds is collected BEFORE it, and the collector rests for its length.
+    An object that owns device memory or a graph (an evaluator, an engine, a CUDAGraph of a BatchedSelfPlay nobody holds any more --
+    it sits in a reference cycle with its reader's book) is destroyed when the collector happens to run, and a free or a graph
+    destruction inside a capture is an error of the runtime (torch.cuda.graph collects nothing by itself)."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def bits_to_int(words):
@@ -1217,7 +1235,7 @@ class MCTSEngine(object):
         graph = t.cuda.CUDAGraph()
         self._capturing = True
         try:
-            with t.cuda.graph(graph):
+            with _no_gc(), t.cuda.graph(graph):
                 self.sim_chunk(evaluator, per)
         finally:
             self._capturing = False
@@ -1370,6 +1388,7 @@ class MCTSEngine(object):
         self.play_resign_on = False   # (rz_play_attach turns resignation off)
         self.play_cap_on = False      # (and the playout cap)
         self.play_match_on = False    # (and match mode)
+        self.play_queue_cap = 0       # (and the queue is the linear one: play_queue_ring)
         self.play_temp_on = False     # (and the temperature schedule)
         self.play_values_on, self.play_values = False, None   # (and the ring of root values: play_set_root_values)
         self._play_on, self._play_active = True, None
@@ -1413,7 +1432,7 @@ class MCTSEngine(object):
         graph = t.cuda.CUDAGraph()
         self._capturing = True
         try:
-            with t.cuda.graph(graph):
+            with _no_gc(), t.cuda.graph(graph):
                 st = self.stream()
                 values = self._search_mode(evaluator)   # (nothing is pending: flushed above)
                 evaluator.search_resident(self, n, True)
@@ -1446,6 +1465,21 @@ class MCTSEngine(object):
         check(self.lib.rz_play_apply(self.handle, self.stream()), 'rz_play_apply')
         self.roots_epoch += 1
         self.play_steps += 1
+
+    def play_queue_ring(self, capacity):
+        """The queue of game ids as a ring of ``capacity`` entries (rz_play_queue_ring; 0: the linear queue, what play_attach leaves):
+        after play_attach and BEFORE the first move step is enqueued or a whole-move graph captured (HipError afterwards: the move
+        step holds the capacity as an argument).  Every lane that shares the queue takes the same capacity."""
+        capacity = int(capacity)
+        if capacity > self._play_queue[0].numel():
+            raise ValueError('a ring of %d entries in a queue tensor of %d' % (capacity, self._play_queue[0].numel()))
+        check(self.lib.rz_play_queue_ring(self.handle, capacity), 'rz_play_queue_ring')
+        self.play_queue_cap = capacity
+
+    def play_queue_push(self, first_id, count):
+        """Append the ids ``first_id`` .. ``first_id + count - 1`` to the ring (rz_play_queue_push): one small launch on the current
+        stream, no host wait.  A push over an unclaimed id writes nothing and raises the engine's error state (check())."""
+        check(self.lib.rz_play_queue_push(self.handle, int(first_id), int(count), self.stream()), 'rz_play_queue_push')
 
     def play_set_resign(self, threshold, disabled_frac):
         """The resignation rule of the move step on the device (rz_play_set_resign), enqueued on the current stream: the mover resigns

@@ -17,6 +17,9 @@ Multi-GPU: game ``g`` belongs to rank ``g % world_size``; there is no collective
 the search.  ``gather_trajectories`` is the single exchange: fixed-stride records to
 rank 0 (RCCL when the process group backend is nccl, gloo in the CPU tests).
 """
+import collections
+import contextlib
+
 import numpy as np
 
 from . import playlog
@@ -175,7 +178,7 @@ class Trajectory(object):
     """One finished game: what start_self_play returns, in compact form."""
 
     def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku', resigned=False, no_resign=False,
-                 resign_stats=None, fp_margin=np.nan, full=None, root_values=None):
+                 resign_stats=None, fp_margin=np.nan, full=None, root_values=None, epochs=None):
         """Resignation (BatchedSelfPlay.set_resign): ``resigned`` -- the game ended with the loser's resignation; ``moves`` / ``pis``
         are the plies actually played (the resigning search's pi is not recorded).  ``no_resign``: a calibration game (played
         out).  ``resign_stats``: float32 max(v_root, q_best) of every search of the game -- one more than the moves of a resigned
@@ -184,7 +187,12 @@ class Trajectory(object):
         (one entry more than the moves of a resigned game, like ``resign_stats``); None with the cap off.
         Root values (BatchedSelfPlay.set_root_values): ``root_values`` -- float32 [plies], aligned with ``moves`` / ``pis``: -W / N of
         the root of the search that played the ply, the value the mover saw (MCTSEngine.root_values()[:, 0]); like ``pis`` the
-        resigning search of a resigned game is not recorded.  None with the option off."""
+        resigning search of a resigned game is not recorded.  None with the option off.
+        Streams (BatchedSelfPlay.stream_collect): ``epochs`` -- int32 [plies], non-decreasing: the epoch of the search that played
+        each ply (a stalled ply: of its searched record); None outside a stream.  Not part of the ranks' payload."""
+        self.epochs = None if epochs is None else np.asarray(epochs, dtype=np.int32).reshape(-1)
+        if self.epochs is not None and len(self.epochs) != len(moves):
+            raise ValueError('game %d: %d epochs for %d plies' % (int(game_id), len(self.epochs), len(moves)))
         self.root_values = None if root_values is None else np.asarray(root_values, dtype=np.float32).reshape(-1)
         self.full = None if full is None else np.asarray(full, dtype=bool).reshape(-1)
         self.resigned, self.no_resign = bool(resigned), bool(no_resign)
@@ -433,6 +441,24 @@ def plan_route(rows, cols, game, net_algo, score_mode, in_flight, deferred_prior
                 resident_per_cu=r.resident_per_cu if r.resident else 1)
 
 
+def stream_lookahead(copy_every, depth):
+    """Moves of a lane enqueued and unread whenever a stream's calls return (BatchedSelfPlay.stream_start / stream_collect): a constant
+    of the stream, ``depth`` read-backs of ``copy_every`` rows."""
+    return int(copy_every) * int(depth)
+
+
+def stream_topup(n_slots, copy_every, depth):
+    """Ids a stream keeps pushed beyond the host's count of started games -- and the smallest ring its queue needs.  The count lags:
+    when a push is enqueued, stream_lookahead rows are unread, ``copy_every`` more moves run before the next push, a slot claims at
+    most one id per move step, and a claim shows one row later (the game's first record) -- with one more per slot for a claim before
+    the rows read whose record waits (a stall at ply 0): no slot idles for want of an id."""
+    return int(n_slots) * ((int(depth) + 1) * int(copy_every) + 1)
+
+
+# what a log row is verified under: the settings in force when its move was enqueued (a stream's epochs; SelfPlayReader.read_rows)
+Epoch = collections.namedtuple('Epoch', 'first_row temperature_schedule pi_temperature playout_cap resign_threshold resign_disabled_frac')
+
+
 class SelfPlayReader(object):
     """What turns the device move step's log into Trajectories (include/rlzero_hip.h: rz_play_*): the settings a game depends on, the
     counters, and the book of the slots (playlog.SlotBook).  numpy only -- BatchedSelfPlay adds the engines; a test builds one alone.
@@ -446,7 +472,9 @@ class SelfPlayReader(object):
             pi=(np.float64, (n_actions, ), 'move'),
             stat=(np.float32, (), 'search'),    # resignation statistic of every search (set_resign)
             full=(bool, (), 'search'),          # full budget of every search (set_playout_cap)
-            q=(np.float32, (), 'search')))      # root value of every search (set_root_values; NaN with it off)
+            q=(np.float32, (), 'search'),       # root value of every search (set_root_values; NaN with it off)
+            ep=(np.int32, (), 'search')))       # epoch of every search (a stream; 0 outside one)
+        self.epochs = None   # a stream's epochs, oldest first: [Epoch] (BatchedSelfPlay.stream_start); None outside a stream
         self.root_values_on = False   # set_root_values: the side ring of the log is read and Trajectory.root_values formed
         self.slot_game, self.slot_ply = self.book.slot_game, self.book.slot_ply
         self.sims_done = 0
@@ -493,34 +521,82 @@ class SelfPlayReader(object):
         return dict(resigned=resigned, no_resign=no_resign, resign_stats=stats,
                     fp_margin=fp_margin(stats, winner) if no_resign else np.nan)
 
-    def read_rows(self, rows, lo=0, values=None):
+    def settings(self, first_row=0):
+        """-> Epoch: the settings a row is verified under, as they are now."""
+        tab = self.temperature_schedule
+        return Epoch(int(first_row), None if tab is None else tab.copy(), self.pi_temperature, self.playout_cap,
+                     self.resign_threshold, self.resign_disabled_frac)
+
+    @contextlib.contextmanager
+    def _under(self, epoch):
+        """The reader's settings as they were in ``epoch`` (an Epoch; None: as they are) for the block's length."""
+        if epoch is None:
+            yield
+            return
+        now = self.settings()
+        try:
+            (_, self.temperature_schedule, self.pi_temperature, self.playout_cap, self.resign_threshold, self.resign_disabled_frac) = epoch
+            yield
+        finally:
+            (_, self.temperature_schedule, self.pi_temperature, self.playout_cap, self.resign_threshold, self.resign_disabled_frac) = now
+
+    def read_rows(self, rows, lo=0, values=None, row_epochs=None, no_idle=False):
         """Log rows int32 [R, G, words] of the slots ``lo`` .. ``lo + G - 1``, oldest first -> (the trajectories of the games that
         ended in them, the RUNNING records of the last row).  pi is formed here, from the logged visit counts with the reference's
         expression, and every move and flag of the device is verified against this side's draw on the same key.  ``values``: the
-        same rows of the side ring of root values, float32 [R, G] (set_root_values; required while it is on)."""
+        same rows of the side ring of root values, float32 [R, G] (set_root_values; required while it is on).
+        ``row_epochs`` (a stream): int [R], the index into ``self.epochs`` of each row -- its moves, budgets and resignation flags are
+        verified, and its pis formed, under THAT epoch's settings, not the current ones; the trajectories carry ``epochs``, and a
+        game is a calibration game only if it was one in every epoch it spans.  ``no_idle``: HipError for a record without a game
+        (a stream's slots never wait for an id)."""
         if self.root_values_on and values is None:
             raise ValueError('root values are on (set_root_values): read_rows needs the side ring\'s rows')
+        if no_idle and ((rows[..., 4] & playlog.PLAY_RUNNING) == 0).any():
+            r, g = [int(x[0]) for x in np.nonzero((rows[..., 4] & playlog.PLAY_RUNNING) == 0)]
+            raise HipError('slot %d holds no game in row %d of this read: a slot of a stream waited for a game id' % (lo + g, r))
         g_i, d, last_running = playlog.running(rows)
         if g_i.size == 0:
             return [], last_running
-        # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
-        pis, chosen = self._pis_moves(d.counts, d.legal, d.ply, move_uniform(self.seed, d.game, d.ply))
+        if row_epochs is None:
+            rec_ep, groups = np.zeros(g_i.shape, dtype=np.int32), [(None, slice(None))]
+        else:
+            rec_ep = np.asarray(row_epochs, dtype=np.int32)[np.nonzero((rows[..., 4] & playlog.PLAY_RUNNING) != 0)[0]]
+            groups = [(self.epochs[e], rec_ep == e) for e in np.unique(rec_ep)]
+        pis = np.zeros(d.counts.shape, dtype=np.float64)
+        chosen = np.zeros(g_i.shape, dtype=np.int64)
+        fulls = np.zeros(g_i.shape, dtype=bool)
+        for epoch, sel in groups:
+            part = d if epoch is None else playlog.Records(*[f[sel] for f in d])
+            with self._under(epoch):
+                # the reference's expression on the logged counts; the draw with the game's uniform (numpy's inverse-CDF rule): the arbiter
+                pis[sel], chosen[sel] = self._pis_moves(part.counts, part.legal, part.ply, move_uniform(self.seed, part.game, part.ply))
+                cap = self.playout_cap
+                sims, full = playlog.check_budgets(part, self.n_playout, cap, None if cap is None else cap_uniform(self.seed, part.game, part.ply))
+                self.sims_done += sims
+                self.full_plies += full
+                fulls[sel] = ((part.flags & PLAY_FULL) != 0) | (cap is None and row_epochs is not None)   # (a stream: without a cap every search is full)
+                if self.resign_on:
+                    self.resign_would += playlog.check_resignation(part, self.resign_threshold, self._calibration(part.game))
         playlog.check_moves(d, chosen)
-        cap = self.playout_cap
-        sims, full = playlog.check_budgets(d, self.n_playout, cap, None if cap is None else cap_uniform(self.seed, d.game, d.ply))
-        self.sims_done += sims
-        self.full_plies += full
-        if self.resign_on:
-            self.resign_would += playlog.check_resignation(d, self.resign_threshold, self._calibration(d.game))
         q = playlog.running_values(rows, values) if self.root_values_on else np.full(g_i.shape, np.nan, dtype=np.float32)
-        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=(d.flags & PLAY_FULL) != 0, q=q))
+        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=fulls, q=q, ep=rec_ep))
         done = []
         for f in finished:
-            extra = self._resign_record(f.columns['stat'], f.winner, not f.resigned and bool(self._calibration(f.game)), f.resigned)
-            if cap is not None:
+            eps = f.columns['ep']
+            span = [None] if row_epochs is None else self.epochs[int(eps[0]):int(eps[-1]) + 1]
+            calib = not f.resigned
+            for epoch in span:   # (a calibration game: one in every epoch it spans)
+                with self._under(epoch):
+                    calib = calib and self.resign_on and bool(self._calibration(f.game))
+            with self._under(span[-1]):
+                extra = self._resign_record(f.columns['stat'], f.winner, calib, f.resigned)
+            caps = [self.playout_cap if epoch is None else epoch.playout_cap for epoch in span]
+            if any(c is not None for c in caps):
                 extra['full'] = f.columns['full']
             if self.root_values_on:   # (a resigned game has one search more than moves: the resigning one is not recorded)
                 extra['root_values'] = f.columns['q'][:len(f.moves)]
+            if row_epochs is not None:
+                extra['epochs'] = eps[:len(f.moves)]
             done.append(Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
                                    game=self.geometry[2], **extra))
         return done, last_running
@@ -547,6 +623,7 @@ class BatchedSelfPlay(SelfPlayReader):
     games are independent and their uniforms are keyed by game id."""
 
     _dev_on = False      # device_attach: the move step is on the device
+    _streaming = False   # stream_start: a collection that does not stop the device is open
     _chunks_done = -1    # graph chunks of the host loop so far (eager_every)
 
     def __init__(self, engine, evaluator, temperature=1.0, seed=0, use_graph=False, sims_per_graph=8,
@@ -600,6 +677,8 @@ class BatchedSelfPlay(SelfPlayReader):
         on = bool(on)
         if on and any(getattr(lane.eng, 'play_match_on', False) for lane in self.lanes):
             raise ValueError('a lane\'s engine is in match mode (play_set_match): a match logs no root values')
+        if self._streaming and on != self.root_values_on:
+            raise ValueError('a stream is open (stream_start): the root values are an argument of its move step -- set them before stream_start')
         changed, self.root_values_on = on != self.root_values_on, on
         if self._dev_on and changed:
             self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)
@@ -613,6 +692,7 @@ class BatchedSelfPlay(SelfPlayReader):
         as they are.  Dirichlet noise and temperature are untouched: KataGo also drops the noise on fast moves, which is
         deliberately out of scope here.  ValueError for values out of range and for lanes without a resident search (two-launch
         lanes, PUCT, sims_in_flight > 1, host evaluators)."""
+        self._stream_guard('play_cap_on', n_fast is not None)
         if n_fast is None:
             self.playout_cap = None
             for lane in self.lanes:
@@ -630,6 +710,7 @@ class BatchedSelfPlay(SelfPlayReader):
                                      'PUCT, sims_in_flight > 1 and host evaluators search every game alike)')
             self.playout_cap = (n_fast, p_full)
         self._apply_option(self._cap_option())
+        self._open_epoch()
 
     def set_temperature_schedule(self, temps, pi_temperature=None):
         """A per-ply move temperature (an opt-in extension: the reference's self-play has one T) for every lane and BOTH loops (run,
@@ -651,8 +732,10 @@ class BatchedSelfPlay(SelfPlayReader):
         tab = None if temps is None else _check_temperatures(temps, self.eng.n_cells)
         if tab is not None and any(getattr(lane.eng, 'play_match_on', False) for lane in self.lanes):
             raise ValueError('a lane\'s engine is in match mode (play_set_match): a match keeps its own temperature')
+        self._stream_guard('play_temp_on', tab is not None)
         self.temperature_schedule, self.pi_temperature = tab, pi_temperature
         self._apply_option(self._temperature_option())
+        self._open_epoch()
 
     def set_resign(self, threshold, disabled_frac=0.1):
         """AlphaGo Zero's resignation for every lane (an opt-in extension: the reference plays every game to its end): the player to
@@ -665,8 +748,10 @@ class BatchedSelfPlay(SelfPlayReader):
         disabled_frac = float(disabled_frac)
         if not 0.0 <= disabled_frac <= 1.0:
             raise ValueError('disabled_frac %r not in [0, 1]' % disabled_frac)
+        self._stream_guard('play_resign_on', not np.isnan(threshold))
         self.resign_threshold, self.resign_disabled_frac = threshold, disabled_frac
         self._apply_option(self._resign_option())
+        self._open_epoch()
 
     # An option of the device move step: (on here, the engine's attribute that says it is on there, how to hand it to an engine)
     def _resign_option(self):
@@ -818,6 +903,7 @@ class BatchedSelfPlay(SelfPlayReader):
             refresh = getattr(lane.evaluator, 'refresh_if_changed', None)
             if refresh is not None:
                 refresh(content=True)
+        self._open_epoch()   # (a stream: the moves enqueued from here on search with these weights)
 
     def _on(self, lane):
         return self.torch.cuda.stream(lane.stream)
@@ -1068,6 +1154,7 @@ class BatchedSelfPlay(SelfPlayReader):
     def run(self, game_ids, max_moves=None, pipelined=False):
         """Play all ``game_ids`` to the end; returns trajectories sorted by game id.  ``pipelined``: the host side of a
         lane's move under the other lanes' simulations (play_move_pipelined); same trajectories."""
+        self._no_stream('run')
         self.abandon_running()
         if pipelined:
             return self._run_pipelined(game_ids, max_moves)
@@ -1124,7 +1211,8 @@ class BatchedSelfPlay(SelfPlayReader):
     # counts with the reference's numpy expression (alphazero_mcts.py:10-14,91-92), and every move the device drew is checked
     # against numpy's inverse-CDF draw on the same uniform (a mismatch raises; a draw too close to an interval edge was never
     # made by the device: the slot stalls until the move computed here is handed back).  Same trajectories as play_move().
-    def device_attach(self, queue_capacity=1 << 16, ring_steps=64, depth=None, copy_every=None, stall_margin=0.0, move_graphs=True):
+    def device_attach(self, queue_capacity=1 << 16, ring_steps=64, depth=None, copy_every=None, stall_margin=0.0, move_graphs=True,
+                      _ring=False):
         """Switch this object to device-driven moves.  ``copy_every``: moves of a lane per read-back of its log rows (None: 1, or
         8 when a move is a fraction of a millisecond -- boards of a few cells with few simulations); ``depth``: read-backs a lane
         may be ahead of the rows processed here (None: 1 when a move is long, else 2).  ``move_graphs``: a lane whose search is the
@@ -1133,6 +1221,8 @@ class BatchedSelfPlay(SelfPlayReader):
         t = self.torch
         from ._hip import PLAY_RECORD_WORDS
         dev = self.eng.device
+        if self._streaming and not _ring:
+            raise ValueError('a stream is open (stream_start): stream_stop ends it before the move step is attached again')
         if self._dev_on:
             self.device_stop()
         self._attach_kw = dict(ring_steps=ring_steps, depth=depth, copy_every=copy_every, stall_margin=stall_margin, move_graphs=move_graphs)
@@ -1141,6 +1231,12 @@ class BatchedSelfPlay(SelfPlayReader):
         self._copy_every = int(copy_every) if copy_every else (1 if work >= 4000 else 8)
         self._depth = int(depth) if depth else (1 if work >= 100000 else 2)
         ring_steps = max(int(ring_steps), self._copy_every * (self._depth + 2) + 2)
+        if _ring:   # (a stream: the queue is a ring of at least what the top-up keeps pushed)
+            least = stream_topup(self.n_slots, self._copy_every, self._depth)
+            if queue_capacity is not None and int(queue_capacity) < least:
+                raise ValueError('a ring of %d game ids: the top-up of %d slots, copy_every %d, depth %d needs %d (stream_topup)' % (
+                    queue_capacity, self.n_slots, self._copy_every, self._depth, least))
+            queue_capacity = least if queue_capacity is None else int(queue_capacity)
         self._queue_ids = t.zeros(int(queue_capacity), dtype=t.int64, device=dev)
         self._queue_ctl = t.zeros(2, dtype=t.int32, device=dev)
         self._queue_len, self._started = 0, 0
@@ -1149,6 +1245,8 @@ class BatchedSelfPlay(SelfPlayReader):
             with self._on(lane):
                 lane.eng.play_attach(self.seed, self.temperature, self._queue_ids, self._queue_ctl, ring_steps=ring_steps,
                                      stall_margin=stall_margin)
+                if _ring:   # (an argument of the move step: before it is enqueued or captured)
+                    lane.eng.play_queue_ring(queue_capacity)
                 self._apply_option(self._resign_option(), attaching=lane)
                 lane.eng.set_playouts(None)   # (the device's budgets, not a host-driven run's last counts)
                 lane.eng.play_set_cap_order(self.cap_longest_first)
@@ -1178,6 +1276,7 @@ class BatchedSelfPlay(SelfPlayReader):
     def device_queue(self, game_ids):
         """Replace the queue of waiting game ids (synchronises: not for the middle of a run) and let idle slots take from it."""
         t = self.torch
+        self._no_stream('device_queue')
         ids = np.ascontiguousarray(list(game_ids), dtype=np.int64)
         if ids.size > self._queue_ids.numel():
             raise ValueError('%d game ids for a queue of %d: device_attach(queue_capacity=...)' % (ids.size, self._queue_ids.numel()))
@@ -1280,6 +1379,7 @@ class BatchedSelfPlay(SelfPlayReader):
         """run() with the move step on the device: same trajectories, sorted by game id.  ``on_finished(trajectories)``: called with the
         games found finished after every enqueued move, while the GPU searches on (a consumer's per-game work -- the trainer's
         observation planes and replay-buffer entries -- then costs the round nothing)."""
+        self._no_stream('run_device')
         game_ids = list(game_ids)
         if not self._dev_on:
             self.device_attach(queue_capacity=max(len(game_ids), 1))
@@ -1310,6 +1410,216 @@ class BatchedSelfPlay(SelfPlayReader):
         if len(out) < len(game_ids):
             self.device_stop()
         return sorted(out, key=lambda t: t.game_id)
+
+    # -- a streaming collection: games keep running across the caller's rounds ---------------------------------------------------
+    # run_device returns when the last of its games has ended, the slots of the finished ones idle under its stragglers.  A stream
+    # never stops the device: slots refill from a RING of game ids that the host tops up (rz_play_queue_push), stream_collect(n)
+    # returns once n more games have been read finished, and the others stay in flight for the next call -- on weights and settings
+    # that may change under them (epochs).  What makes that reproducible: rows are read strictly in enqueue order behind
+    # synchronize() -- never "when ready" --, so every host decision that reaches the device (a push, a stalled slot's move, a new
+    # epoch) is enqueued at a position of the stream that depends on the log's CONTENT only; the moves enqueued and unread when a
+    # call returns are a constant, stream_lookahead(copy_every, depth); and the move steps of several lanes, which share the queue,
+    # are chained by events into one order (lane 0, 1, .., lane 0, ..), so which game a slot takes does not depend on timing.
+    def _no_stream(self, what):
+        if self._streaming:
+            raise ValueError('%s: a stream is open (stream_start); stream_stop ends it' % what)
+
+    def _stream_guard(self, flag, on):
+        """A setter called while a stream is open: an option that is turned on over a whole-move graph captured without it would need
+        a new attach, which would drop the games in flight."""
+        if self._streaming and on and any(lane.move_graph is not None and not getattr(lane.eng, flag) for lane in self.lanes):
+            raise ValueError('a stream is open (stream_start) and its whole-move graphs were captured without this option: '
+                             'turn it on before stream_start (a stream takes new VALUES of an option as they are)')
+
+    def _open_epoch(self):
+        """Behind a change of weights or settings while a stream is open: the moves enqueued from here on are searched, drawn and
+        verified under it -- the host notes the first log row of the epoch."""
+        if self._streaming:
+            self.epochs.append(self.settings(first_row=self._stream_rounds))
+
+    @property
+    def stream_epoch(self):
+        """The epoch the next enqueued move belongs to (None outside a stream)."""
+        return len(self.epochs) - 1 if self._streaming else None
+
+    def _chain(self, lane):
+        """Several lanes: order what this lane enqueues next behind the last link of the chain (another lane's move step or push)."""
+        if len(self.lanes) > 1 and self._chain_ev is not None:
+            lane.stream.wait_event(self._chain_ev)
+
+    def _chain_link(self, lane):
+        if len(self.lanes) > 1:
+            self._chain_ev = self.torch.cuda.Event()
+            self._chain_ev.record(lane.stream)
+
+    def stream_start(self, first_game_id=0, queue_capacity=None, **attach_kw):
+        """Open a stream: the device move step is attached as device_attach does -- ``attach_kw``: its arguments, by default those of
+        the last attach; options, whole-move graphs and the root-value ring carry over --, with the queue of game ids as a ring of
+        ``queue_capacity`` entries (None: the smallest the top-up allows, stream_topup).  Games get consecutive ids from
+        ``first_game_id``.  Every slot starts a game and stream_lookahead moves are enqueued: from here on that many moves are
+        enqueued and unread whenever a call returns.  While the stream is open refresh_weights, set_resign, set_playout_cap and
+        set_temperature_schedule each open a new EPOCH: the change is enqueued in stream order behind the moves already enqueued,
+        and every log row is verified under the settings of its own epoch (Trajectory.epochs).  run, run_device, device_queue and
+        device_attach raise ValueError until stream_stop; so do a lane in match mode and a route without the device move step."""
+        self._no_stream('stream_start')
+        first_game_id = int(first_game_id)
+        if first_game_id < 0:
+            raise ValueError('first_game_id %d is negative' % first_game_id)
+        for lane in self.lanes:
+            if getattr(lane.eng, 'play_match_on', False):
+                raise ValueError('a lane\'s engine is in match mode (play_set_match): a match is no stream of self-play games')
+            if getattr(lane.eng, 'sims_in_flight', 1) != 1:
+                raise ValueError('this route has no device move step (sims_in_flight %d: one simulation in flight per tree only)' % lane.eng.sims_in_flight)
+        kw = dict(self._attach_kw) if self._dev_on else {}
+        kw.update(attach_kw)
+        self._stream_before = (self._queue_ids.numel(), dict(self._attach_kw)) if self._dev_on else None
+        self.device_attach(queue_capacity=queue_capacity, _ring=True, **kw)
+        self._streaming = True
+        self._stream_first, self._stream_pushed = first_game_id, 0
+        self._stream_low, self._stream_done_ids = first_game_id, set()   # every id below _stream_low has been returned, and these above it
+        self._stream_rounds = self._stream_batches = self._stream_returned = 0
+        self._stream_topup = stream_topup(self.n_slots, self._copy_every, self._depth)
+        self._chain_ev = None
+        self.epochs = [self.settings(first_row=0)]
+        for lane in self.lanes:   # (a host-driven run's last counts: the device's budgets rule here)
+            with self._on(lane):
+                lane.eng.set_playouts(None)
+        self._stream_push()
+        for lane in self.lanes:
+            with self._on(lane):
+                self._chain(lane)
+                lane.eng.play_refill()
+                self._chain_link(lane)
+            lane.last_running = -1
+        for _ in range(stream_lookahead(self._copy_every, self._depth)):
+            self._stream_round()
+
+    def _stream_push(self):
+        """Top the ring up to stream_topup ids beyond the host's (lagged) count of started games: one launch on lane 0's stream, a
+        link of the lanes' chain."""
+        n = self._started + self._stream_topup - self._stream_pushed
+        if n <= 0:
+            return
+        lane = self.lanes[0]
+        with self._on(lane):
+            self._chain(lane)
+            lane.eng.play_queue_push(self._stream_first + self._stream_pushed, n)
+            self._chain_link(lane)
+        self._stream_pushed += n
+
+    def _stream_round(self):
+        """One more move of every lane, in the lanes' order; every copy_every rounds the read-back of their rows."""
+        for lane in self.lanes:
+            if getattr(lane.eng, 'play_match_on', False):
+                raise ValueError('a lane\'s engine went into match mode (play_set_match) while a stream is open')
+            if lane.move_graph is not None:
+                with self._on(lane):
+                    self._chain(lane)
+                    lane.uncopied.append(lane.eng.play_move_replay(lane.move_graph))
+                    self._chain_link(lane)
+            else:   # (the search runs beside the other lanes' moves; only the move step joins the chain)
+                self._simulate_lane(lane, host_counts=False)
+                with self._on(lane):
+                    self._chain(lane)
+                    lane.uncopied.append(lane.eng.play_move())
+                    self._chain_link(lane)
+        self._stream_rounds += 1
+        if self._stream_rounds % self._copy_every == 0:
+            for lane in self.lanes:
+                self._read_back(lane)
+
+    def _stream_read(self, no_idle=True):
+        """The oldest read-back of every lane, waited for -> the games that ended in its rows, by row, then game id."""
+        ce = self._copy_every
+        rounds = np.arange(self._stream_batches * ce, (self._stream_batches + 1) * ce)
+        row_ep = np.searchsorted([e.first_row for e in self.epochs], rounds, side='right') - 1
+        self._stream_batches += 1
+        batches = []
+        for lane in self.lanes:
+            rows, ev = lane.inflight.pop(0)
+            ev.synchronize()
+            batches.append(rows)
+        done = []
+        # (host_np[rows] is a copy: the pinned rows may be overwritten from now on.)  Row by row, the games of a row by game id:
+        # WHICH slot of a move step takes which id is a race among the step's waves (k_play_apply's CAS loop) -- the ids a step
+        # takes, and so every game's content, are not
+        for i in range(ce):
+            ended = []
+            for lane, rows in zip(self.lanes, batches):
+                got, lane.last_running = self.read_rows(lane.host_np[rows[i:i + 1]], lane.slots.start,
+                                                        values=None if lane.values_np is None else lane.values_np[rows[i:i + 1]],
+                                                        row_epochs=row_ep[i:i + 1], no_idle=no_idle)
+                ended.extend(got)
+            done.extend(sorted(ended, key=lambda t: t.game_id))
+        self._stream_returned += len(done)
+        self._stream_done_ids.update(t.game_id for t in done)
+        while self._stream_low in self._stream_done_ids:
+            self._stream_done_ids.remove(self._stream_low)
+            self._stream_low += 1
+        return done
+
+    def stream_collect(self, n_games, on_finished=None):
+        """Enqueue moves until at least ``n_games`` more games have been read finished -> their Trajectories in finishing order (log
+        row, then game id -- the slot a game sits in is not reproducible, see _stream_read), ``epochs`` filled in.  The other games stay in flight and are continued by the next call.
+        ``on_finished(trajectories)``: as in run_device."""
+        if not self._streaming:
+            raise ValueError('stream_collect: no stream is open (stream_start)')
+        out = []
+        while len(out) < int(n_games):
+            for _ in range(self._copy_every):
+                self._stream_round()
+            done = self._stream_read()
+            self._stream_push()
+            out.extend(done)
+            if on_finished is not None and done:
+                on_finished(done)
+        return out
+
+    def stream_running_ids(self):
+        """The ids of the games the device has started and this stream has not returned yet, ascending (synchronises; what
+        stream_stop(finish=True) would play to the end, or stream_stop() drop)."""
+        if not self._streaming:
+            raise ValueError('stream_running_ids: no stream is open (stream_start)')
+        self.torch.cuda.synchronize(self.eng.device)
+        head = int(self._queue_ctl.cpu()[0])
+        return [g for g in range(self._stream_low, self._stream_first + head) if g not in self._stream_done_ids]
+
+    def stream_stop(self, finish=False):
+        """End the stream.  ``finish``: start no further game, play the running ones to their end -> their Trajectories, in finishing
+        order.  Otherwise drop the running games -> how many were dropped.  Afterwards run / run_device work as before (an object
+        that was attached before stream_start is attached again as it was)."""
+        if not self._streaming:
+            raise ValueError('stream_stop: no stream is open (stream_start)')
+        t, dev = self.torch, self.eng.device
+        out, head = [], self._stream_returned
+        try:
+            t.cuda.synchronize(dev)
+            head = int(self._queue_ctl.cpu()[0])
+            if finish:
+                # the ids no slot has claimed are taken back (the device is idle: a plain copy), then rounds as before until a
+                # read-back shows every slot idle and nothing is enqueued behind it
+                self._queue_ctl.copy_(t.tensor([head, head], dtype=t.int32))
+                t.cuda.synchronize(dev)
+                while True:
+                    while any(lane.inflight for lane in self.lanes):
+                        out.extend(self._stream_read(no_idle=False))
+                    if all(lane.last_running == 0 for lane in self.lanes):
+                        break
+                    for _ in range(self._copy_every):
+                        self._stream_round()
+                self.check()
+                if self._stream_returned != head:
+                    raise HipError('the stream started %d games and returned %d' % (head, self._stream_returned))
+            else:
+                self.check()
+        finally:
+            dropped = 0 if finish else head - self._stream_returned
+            self._streaming, self.epochs = False, None
+            self.device_stop()
+            before, self._stream_before, self._dev_on = self._stream_before, None, False
+            if before is not None:
+                self.device_attach(queue_capacity=before[0], **before[1])
+        return out if finish else dropped
 
 
 # ------------------------------------------------------------------------- multi-GPU gather

@@ -169,7 +169,8 @@ class TrainPipeline:
                  selfplay_games_in_flight=0, buffer_size=None, seed=None, resign='off', resign_disabled_frac=0.1,
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
                  device_replay=False, temperature_schedule=None, pi_temperature=None, reanalyse=None, reanalyse_slots=512,
-                 reanalyse_playouts=None, game='gomoku', board_width=None, value_mix=0.0, reanalyse_targets='pi'):
+                 reanalyse_playouts=None, game='gomoku', board_width=None, value_mix=0.0, reanalyse_targets='pi',
+                 continuous_selfplay=False):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -207,7 +208,13 @@ class TrainPipeline:
         (BatchedSelfPlay.set_root_values) and the learner's value target is (1 - lam) z + lam q (rlzero_amd.replay.mixed_value_targets:
         DeviceReplay.set_value_mix, or Trajectory.training_samples(value_mix=) into the host buffer).  ValueError with several
         ranks: the ranks' payload carries no root values.  ``reanalyse_targets``: 'pi' (default), 'value' or 'both' -- what a refresh
-        rewrites (ReplayReanalyser(targets=)); 'value' / 'both' need ``value_mix`` > 0, whose buffer keeps q."""
+        rewrites (ReplayReanalyser(targets=)); 'value' / 'both' need ``value_mix`` > 0, whose buffer keeps q.
+        ``continuous_selfplay`` (batched mode on one rank with the move step on the device; an opt-in extension -- NOT the reference's
+        loop, which collects and then updates): self-play is ONE stream (BatchedSelfPlay.stream_start) that the rounds do not stop.  A
+        round is ``stream_collect(n)`` behind ``refresh_weights()``: it ends when n more games have finished, and the games still
+        running go on under the next round's weights (Trajectory.epochs tells which plies) instead of idling their slots' neighbours.
+        The replay buffer receives the games in FINISHING order, not in game-id order.  The last round of ``run`` stops the stream and
+        prints the games it drops.  ValueError with several ranks, with RZ_TRAIN_HOST_MOVES=1 and in the reference flow."""
         if game not in ('gomoku', 'connect4'):
             raise ValueError('game %r: gomoku or connect4' % (game, ))
         self.game_kind = game
@@ -261,6 +268,15 @@ class TrainPipeline:
         if resign != 'off' and selfplay_games_in_flight <= 0:
             raise ValueError('resignation is a batched self-play option: selfplay_games_in_flight must be > 0')
         self.rank, self.world = self._init_ranks()
+        self.continuous_selfplay = bool(continuous_selfplay)
+        if self.continuous_selfplay:
+            if selfplay_games_in_flight <= 0:
+                raise ValueError('continuous self-play is a batched-mode option: selfplay_games_in_flight must be > 0')
+            if self.world > 1:
+                raise ValueError('continuous self-play runs on one rank: a stream of games is not sharded (%d ranks)' % self.world)
+            if os.environ.get('RZ_TRAIN_HOST_MOVES') == '1':
+                raise ValueError('continuous self-play needs the move step on the device (RZ_TRAIN_HOST_MOVES=1 is the host-driven loop)')
+        self._final_round = False
         if self.world > 1 and self.value_mix > 0.0:
             raise ValueError('the value mix runs on one rank: the payload the ranks gather carries no root values (%d ranks)' % self.world)
         if self.world > 1 and game == 'connect4':
@@ -405,20 +421,9 @@ class TrainPipeline:
     def _play_games(self, game_ids, on_finished=None):
         """The trajectories of ``game_ids`` (this rank's share of a round), games in lock-step on this rank's GPU.  ``on_finished``: see
         BatchedSelfPlay.run_device (one rank, the move step on the device: the round's samples are formed while the GPU plays on)."""
-        from rlzero.algorithms import BatchedSelfPlay
-        if self._batched is None:
-            # one to four lanes of games, whichever fills the GPU better (selfplay.plan_lanes)
-            self._batched = BatchedSelfPlay.for_network(
-                self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
-                n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
-                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
-                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature,
-                root_values=self.value_mix > 0.0, **self._game_kw())
+        self._selfplay()
         self._batched.refresh_weights()   # (every lane's evaluator: the learner has stepped / new weights have arrived)
-        if self.resign_mode != 'off':
-            # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
-            first = self.resign_mode == 'auto' and not self._resign_history and self.resign_threshold == float('-inf')
-            self._batched.set_resign(self.resign_threshold, 1.0 if first else self.resign_disabled_frac)
+        self._set_resign()
         # the move step on the device (rz_play_*: the host reads the games from a log behind the GPU); RZ_TRAIN_HOST_MOVES=1: the
         # host-driven loop -- the same trajectories either way (tests/test_device_moves.py)
         if os.environ.get('RZ_TRAIN_HOST_MOVES') == '1':
@@ -430,6 +435,50 @@ class TrainPipeline:
         if os.environ.get('RZ_TRAIN_TRACE'):
             self._trace_round(trajs)
         return trajs
+
+    def _selfplay(self):
+        """The rank's BatchedSelfPlay, built on first use."""
+        from rlzero.algorithms import BatchedSelfPlay
+        if self._batched is None:
+            # one to four lanes of games, whichever fills the GPU better (selfplay.plan_lanes)
+            self._batched = BatchedSelfPlay.for_network(
+                self.alphazero_agent.policy_value_net, self.board_size, self.n_in_row,
+                n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
+                device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
+                temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature,
+                root_values=self.value_mix > 0.0, **self._game_kw())
+        return self._batched
+
+    def _set_resign(self):
+        if self.resign_mode != 'off':
+            # 'auto' before its first calibration: threshold -inf and every game a calibration game (statistics only)
+            first = self.resign_mode == 'auto' and not self._resign_history and self.resign_threshold == float('-inf')
+            self._batched.set_resign(self.resign_threshold, 1.0 if first else self.resign_disabled_frac)
+
+    def _collect_continuous(self, n_games, consume):
+        """One round of continuous self-play: the stream's next ``n_games`` finished games (at least), under the weights and the
+        resignation threshold handed over at its start -- a new epoch of the stream; games that started in an earlier round finish
+        here, games this round starts may finish in a later one.  ``consume`` takes every game's tuple in FINISHING order while the
+        GPU plays on.  The last round of run() stops the stream.  -> [] (every game was consumed)."""
+        sp = self._selfplay()
+        sp.refresh_weights()
+        self._set_resign()
+        if not sp._streaming:   # (the first round: the options above are in force when the move step is attached)
+            sp.stream_start(first_game_id=self._next_game_id)
+        epoch = sp.stream_epoch
+        trajs = sp.stream_collect(n_games, on_finished=lambda done: [consume(self._tuple(t)) for t in done])
+        self._next_game_id = max([self._next_game_id] + [t.game_id + 1 for t in trajs])
+        self._resign_round(trajs)
+        self._cap_round(trajs)
+        plies = sum(len(t.moves) for t in trajs)
+        stale = sum(int((t.epochs < epoch).sum()) for t in trajs)
+        print('continuous self-play: {} games finished, {} of {} plies searched in an earlier epoch ({:.3f})'.format(
+            len(trajs), stale, plies, stale / max(plies, 1)), flush=True)
+        if os.environ.get('RZ_TRAIN_TRACE'):
+            self._trace_round(trajs)
+        if self._final_round:
+            print('continuous self-play: stream stopped, {} running games dropped'.format(sp.stream_stop()), flush=True)
+        return []
 
     def _game_kw(self):
         """What BatchedSelfPlay.for_network / BatchedEvaluation.for_network take beyond Gomoku's defaults."""
@@ -553,7 +602,9 @@ class TrainPipeline:
                 self.data_buffer.extend(self.get_equi_data(play_data))
             else:
                 self.data_buffer.extend_samples(play_data)
-        if self.selfplay_games_in_flight > 0:
+        if self.continuous_selfplay:
+            games = self._collect_continuous(max(n_games, self.selfplay_games_in_flight), consume)
+        elif self.selfplay_games_in_flight > 0:
             games = self._collect_batched(max(n_games, self.selfplay_games_in_flight * self.world), consume=consume)
         else:
             games = [self.game.start_self_play(self.mcts_player, temperature=self.temperature)
@@ -711,6 +762,7 @@ class TrainPipeline:
         lead = self.rank == 0   # rank 0 holds the buffer, learns, evaluates, saves and prints; the others play their share
         try:
             for i in range(self.game_batch_num):
+                self._final_round = i + 1 == self.game_batch_num   # (continuous self-play: this round stops the stream)
                 self.collect_selfplay_data(self.play_batch_size)
                 if lead:
                     print('batch i:{}, episode_len:{}'.format(i + 1, self.episode_len))
@@ -875,6 +927,9 @@ def parse_args(argv=None):
                          '(kept by self-play); 0 = z alone, the default')
     ap.add_argument('--reanalyse-targets', choices=('pi', 'value', 'both'), default=argparse.SUPPRESS,
                     help='with --reanalyse: refresh the policy targets, the stored root values q (needs --value-mix > 0) or both')
+    ap.add_argument('--continuous-selfplay', action='store_true', default=argparse.SUPPRESS,   # (absent without the flag, like --value-mix)
+                    help='batched mode on one GPU (an opt-in extension, not the reference loop): self-play is one stream that the rounds do '
+                         'not stop -- a round ends when --games-in-flight more games have finished, the others run on under the next weights')
     args = ap.parse_args(argv)
     value_mix, targets = value_mix_of(args), reanalyse_targets_of(args)
     if not 0.0 <= value_mix <= 1.0:
@@ -936,6 +991,14 @@ def main(argv=None):
     if value_mix_of(args) > 0.0 and (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
         raise ValueError('--value-mix runs on one rank: the payload the ranks gather carries no root values (--gpus %d, WORLD_SIZE %s)'
                          % (args.gpus, os.environ.get('WORLD_SIZE', '1')))
+    if getattr(args, 'continuous_selfplay', False):
+        if args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise ValueError('--continuous-selfplay runs on one rank: a stream of games is not sharded (--gpus %d, WORLD_SIZE %s)'
+                             % (args.gpus, os.environ.get('WORLD_SIZE', '1')))
+        if args.games_in_flight <= 0:
+            raise ValueError('--continuous-selfplay needs --games-in-flight > 0 (batched self-play)')
+        if os.environ.get('RZ_TRAIN_HOST_MOVES') == '1':
+            raise ValueError('--continuous-selfplay needs the move step on the device (RZ_TRAIN_HOST_MOVES=1 is the host-driven loop)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.seed is not None:   # a reproducible run: initial weights, random.sample of the replay buffer, numpy draws
@@ -949,7 +1012,8 @@ def main(argv=None):
                          batch_size=args.batch_size, updates_per_round=args.updates_per_round, device_replay=args.device_replay,
                          temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature,
                          reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts,
-                         game=args.game, board_width=args.board_width, value_mix=value_mix_of(args), reanalyse_targets=reanalyse_targets_of(args))
+                         game=args.game, board_width=args.board_width, value_mix=value_mix_of(args), reanalyse_targets=reanalyse_targets_of(args),
+                         continuous_selfplay=getattr(args, 'continuous_selfplay', False))
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
