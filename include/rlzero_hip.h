@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 45
+#define RZ_ABI_VERSION 46
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -759,6 +759,21 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
  * of the two kinds of search must not share a flush: flush between them. */
 int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream);
 int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream);
+/* RESIDENT SEARCH UNDER PUCT (ABI 46; opt-in: HipNetEvaluator.resident_puct).  rz_net_search_resident above is the deferred-priors
+ * route's and refuses RZ_SCORE_PUCT, whose selection reads the priors of the node it stands on.  rz_net_search_resident_puct runs n_sims
+ * simulations of every active game of a RZ_SCORE_PUCT engine in ONE launch, one workgroup per game, one game per CU: the trunk
+ * (k_trunk_split, one N-tile per wave), the first FC layers of both heads on the game's own leaf inside the same workgroup (the arithmetic
+ * of k_heads_split; final logits and the value head's hidden row in row g of the net's internal buffers), then the body of
+ * rz_tree_step_raw -- log_softmax, tanh, priors with their Dirichlet noise, the dense child records, backup, next selection -- and the
+ * next leaf handed to the trunk through LDS.  The trees, priors, values and noise counters of rz_net_trunk_leaves + rz_net_heads_gemm +
+ * rz_tree_step_raw, bit for bit (policy_value_net.py:34-52, node.py:44-88, alphazero_mcts.py:49-85).  select_first as in
+ * rz_net_search_resident; games whose active flag is 0 are skipped.  Nothing is stored for a flush: no rz_deferred_reserve, no
+ * rz_net_deferred_reserve, no pending records.
+ * RZ_ERR_ARG: an engine that is not RZ_SCORE_PUCT with one simulation in flight; a board of more than 10 rows or columns; a net
+ * without the split-f16 trunk (RZ_NET_SPLIT_F16 with finite activation bounds); RZ_NET_HEADS_F32 (the three-launch step would then use
+ * another arithmetic); an engine whose board is not the net's; more games than CUs; more games than rz_net_reserve()d.  Per-game
+ * simulation counts (rz_set_playouts, the playout cap) and matches keep refusing RZ_SCORE_PUCT. */
+int rz_net_search_resident_puct(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream);
 int rz_net_heads(rz_net *net, int32_t n_boards, float *d_logp, float *d_value, void *stream);
 /* only the FC GEMM of the heads on the internal features; returns the device pointers that
  * rz_tree_step_raw / rz_expand_backup_raw consume (valid until the next rz_net_reserve / load) */

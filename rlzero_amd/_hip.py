@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -213,6 +213,7 @@ _SIGNATURES = {
     'rz_net_search_resident_values': (c_int, [P, P, c_int32, c_int32, P]),
     'rz_net_policy_rows': (c_int, [P, P, POINTER(RzKeptRows), P]),
     'rz_net_search_resident': (c_int, [P, P, c_int32, c_int32, P]),
+    'rz_net_search_resident_puct': (c_int, [P, P, c_int32, c_int32, P]),
     'rz_net_delta_reserve': (c_int, [P, c_int32]),
     'rz_net_delta_invalidate': (c_int, [P, P]),
     'rz_net_delta_resident': (c_int, [P, c_int32]),

@@ -17,7 +17,8 @@
 //   rz_delta.h       k_trunk_delta, k_delta_res, k_trunk_policy_rows: k_trunk_rows' arithmetic on the cells a leaf changes (namespace dl)
 //   rz_net_split.h   k_trunk_split<TN, MS> (smaller boards; the checker of k_trunk_rows): the same arithmetic on v_mfma_f32_32x32x16_f16
 //                    tiles of whole rows, the waves split the rows; optionally the FC layers of its own board behind it
-//                    (RZ_NET_HEADS_IN_TRUNK) and the resident search; namespace sp, whose types and conversions every f16 kernel uses
+//                    (RZ_NET_HEADS_IN_TRUNK) and the resident search (under PUCT both at once: rz_net_search_resident_puct); namespace sp,
+//                    whose types and conversions every f16 kernel uses
 //   rz_net_heads.h   k_heads_split, k_heads_rows, k_heads_part: the first FC layers of both heads on the f16 pipe (hi + lo pairs), fed
 //                    by the f16 feature pieces the trunks above write in MFMA fragment order; k_heads_finish: log_softmax and tanh
 //   rz_net_f32.h     the f32-input MFMA: k_trunk (direct implicit GEMM, bit-for-bit a k-ordered fmaf chain), k_trunk_wino_f4<4>
@@ -240,6 +241,18 @@ static void launch_trunk_split(int ms, bool compact, dim3 grid, hipStream_t st, 
     else if (ms == 3) k_trunk_split<1, 3, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
     else if (RES || ms == 1) k_trunk_split<1, 1, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, raw, hid, later, res);
     else if constexpr (!RES) k_trunk_split<2, 1, RES><<<grid, wg, 0, st>>>(nd, obs, leaves, f32, f16, n_boards, flags, nullptr, nullptr, later, res);
+}
+
+// ... and of its PUCT instantiations (rz_net_search_resident_puct: RES + FC_HERE on the 18 x 18 grid, one per way of covering a board of
+// up to 10 rows; ms = 0 has none).  raw / hid: one row per game.
+static void launch_search_split_puct(int ms, dim3 grid, hipStream_t st, const NetDev &nd, LeafBits leaves, int n_games, unsigned *flags, float *raw,
+                                     float *hid, const ResArgs<true> &res) {
+    const dim3 wg(256);
+    const DeferredOut none = no_store();
+    if (ms == 4) k_trunk_split<1, 4, true, kRowW, 18, true><<<grid, wg, 0, st>>>(nd, nullptr, leaves, nullptr, nullptr, n_games, flags, raw, hid, none, res);
+    else if (ms == 2) k_trunk_split<1, 2, true, kRowW, 18, true><<<grid, wg, 0, st>>>(nd, nullptr, leaves, nullptr, nullptr, n_games, flags, raw, hid, none, res);
+    else if (ms == 3) k_trunk_split<1, 3, true, kRowW, 18, true><<<grid, wg, 0, st>>>(nd, nullptr, leaves, nullptr, nullptr, n_games, flags, raw, hid, none, res);
+    else k_trunk_split<1, 1, true, kRowW, 18, true><<<grid, wg, 0, st>>>(nd, nullptr, leaves, nullptr, nullptr, n_games, flags, raw, hid, none, res);
 }
 
 extern "C" {
@@ -680,6 +693,43 @@ int rz_net_search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
 
 int rz_net_search_resident_values(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
     return search_resident(net, engine, n_sims, select_first, stream, false);
+}
+
+// The resident search under RZ_SCORE_PUCT (k_trunk_split<1, MS, RES, 18 x 18, PUCT>).  The route, as route.decide(resident_puct=True) states
+// it on the other side of the ABI: the split-f16 trunk, positions, one simulation in flight, RZ_SCORE_PUCT, a board of up to 10 x 10 that is the
+// net's, any FC arithmetic but RZ_NET_HEADS_F32, at most one game per CU -- and, here only, rows of d_raw / d_hid for every game.
+int rz_net_search_resident_puct(rz_net *net, rz_engine *engine, int32_t n_sims, int32_t select_first, void *stream) {
+    rzt::Dev dev;
+    RZ_TRY(engine_view(net, engine, &dev));
+    if (n_sims < 1) return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct: n_sims must be positive");
+    if (dev.K != 1 || dev.score_mode != RZ_SCORE_PUCT)
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct: RZ_SCORE_PUCT and one simulation in flight per tree (RZ_SCORE_UCT_REF: rz_net_search_resident)");
+    const TrunkClass tc = trunk_class(net);
+    if (tc.ms == 0 || net->dev.BH > 10 || net->dev.BW > 10)
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct: a board of up to 10 x 10 (k_trunk_split with one N-tile per wave and the FC layers in the trunk)");
+    if (!split_trunk_ok(net))
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct needs the RZ_NET_SPLIT_F16 trunk (a net with finite activation bounds)");
+    if (net->heads_algo == RZ_NET_HEADS_F32)
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct runs the FC layers on the f16 pipe: RZ_NET_HEADS_F32 is the three-launch step's (another arithmetic)");
+    RZ_TRY(same_board(net, dev, true));
+    if (dev.n_games > net->n_cus)
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct: one workgroup per game, one per CU: %d games, %d CUs", dev.n_games, net->n_cus);
+    if (dev.n_games > net->feat_boards)
+        return rz_fail(RZ_ERR_ARG, "rz_net_search_resident_puct: more games than rz_net_reserve()d (a row of logits per game)");
+    ResArgs<true> res;
+    res.E = dev;
+    res.vh = rz_value_head{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};   // (the value head is finished from d_hid: rz_raw_heads)
+    res.n_sims = n_sims;
+    res.select_first = select_first ? 1 : 0;
+    RZ_TRY(rz_playouts_view(engine, &res.sims_of, &res.order));   // (NULL under PUCT: rz_set_playouts and the cap refuse the rule)
+    // what the launch leaves in the internal buffers: final logits and hidden rows of the LAST leaves (rz_net_heads_gemm then has nothing
+    // to run and nothing stale to read), no feature pieces
+    net->feat16_valid = net->feat32_valid = false;
+    net->raw_from_trunk = true;
+    net->raw_parts = 1;
+    launch_search_split_puct(tc.ms, dim3((unsigned)dev.n_games), (hipStream_t)stream, net->dev, LeafBits{dev.leaf_stones, dev.leaf_to_move, dev.leaf_last},
+                             dev.n_games, net->d_flags, net->d_raw, net->d_hid, res);
+    return rz_launched("the resident search (PUCT)");
 }
 
 int rz_net_policy_rows(rz_net *net, rz_engine *engine, const rz_kept_rows *kept, void *stream) {

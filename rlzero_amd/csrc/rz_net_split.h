@@ -221,7 +221,13 @@ __device__ __forceinline__ float other_half(float x, int h) {
 // latency chain of small MFMA loops, and two such chains interleave on a CU where one leaves the pipes idle most of the time.
 // Tile rows beyond the board still read positions past its ring (MFMA columns that are stored nowhere): inside the grid or
 // in the bytes behind it, always inside the workgroup's LDS.  (FC_HERE needs the big grid's spare rows: 18 x 18 only.)
-template <int TN, int MS = 1, bool RES = false, int RW = kRowW, int RH = 18>
+// PUCT (with RES, TN = 1, the 18 x 18 grid; rz_net_search_resident_puct): the resident search under RZ_SCORE_PUCT, whose selection
+// reads the priors of the node it stands on -- nothing of a simulation can wait for a flush.  The workgroup runs FC_HERE on its
+// game's leaf (row blockIdx.x of `raw` / `hid`: final logits and the value head's hidden row, the arithmetic of k_heads_split) and
+// wave 0 finishes the heads inside the tree code (expand_backup_body<RAW>: k_tree_step_raw's body, which holds NO barrier -- the other
+// waves go straight to the barrier behind it): the trees, priors and values of trunk -> FC GEMM -> k_tree_step_raw, in one launch.
+// Nothing goes to the deferred store, no value row or K-quarter sums in LDS, `pend` is not read.  One game per CU.
+template <int TN, int MS = 1, bool RES = false, int RW = kRowW, int RH = 18, bool PUCT = false>
 __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetDev nd, const float *__restrict__ obs, LeafBits leaves,
                                                      float *__restrict__ feat, _Float16 *__restrict__ feat16,
                                                      int n_boards, unsigned *__restrict__ flags,
@@ -233,21 +239,24 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
     long long prof_acc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, prof_t = prof_k0;
 #endif
     constexpr int kThreads = 256;
+    static_assert(!PUCT || (RES && TN == 1 && RW == kRowW && RH == 18), "the resident PUCT search: RES, one N-tile per wave, the 18 x 18 grid (FC_HERE)");
     // the resident search's tree code (rz_tree.h: W): a board of one N-tile (MS = 4) or two (MS = 2) has at most 64 cells = one word
     // of a bitboard, every board of this kernel (four tiles of 32 positions) at most 128 = two
     constexpr int kResWords = (MS == 4 || MS == 2) ? 1 : 2;
     // RES (the resident search, see ResArgs): the value head's input row (boards of up to 10 rows and columns: 2 S <= 256 with
     // the padding), the K-quarter sums of its first layer, the next leaf
-    __shared__ float res_vrow[RES ? 256 : 1];
-    __shared__ float res_part[RES ? rzt::kDefWaves : 1][RES ? rzt::kWave : 1];
+    __shared__ float res_vrow[RES && !PUCT ? 256 : 1];
+    __shared__ float res_part[RES && !PUCT ? rzt::kDefWaves : 1][RES && !PUCT ? rzt::kWave : 1];
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[RES ? 2 * RZ_BOARD_WORDS + 1 : 1];
     int res_slot0 = 0;
     int res_n = 0;   // (RES: the simulations of this workgroup's game)
     if constexpr (RES) {
         if ((int)blockIdx.x >= n_boards || res.E.active[blockIdx.x] == 0) return;   // (uniform: before any barrier)
-        res_slot0 = res.E.pend[blockIdx.x];
         res_n = res_sims(res, blockIdx.x);
-        res_vrow[threadIdx.x] = 0.0f;
+        if constexpr (!PUCT) {
+            res_slot0 = res.E.pend[blockIdx.x];
+            res_vrow[threadIdx.x] = 0.0f;
+        }
     }
     constexpr int POS = RW * RH, IC = RW + 2;   // positions of the halo grid; columns of the observation planes' grid
     constexpr int kInPiece = RH * IC * 8, kInB = 2 * kInPiece, kC1B = 2 * sp::Geo<32, POS>::piece_bytes, kC2B = 2 * sp::Geo<64, POS>::piece_bytes;
@@ -672,9 +681,11 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
         // sector (written whole by neighbouring lanes of this wave), a wave of the GEMM reads the 1 KB of a piece
         _Float16 *dst16 = feat16 ? feat16 + ((size_t)(board >> 5) * (nd.groups_act + nd.groups_val) * 1024 + (board & 31) * 16)
                                  : nullptr;
-        const bool deferred = RES || later.slot_of != nullptr;   // (DeferredOut: the policy pieces wait in the store, the value inputs go on as f32)
+        const bool deferred = (RES && !PUCT) || later.slot_of != nullptr;   // (DeferredOut: the policy pieces wait in the store, the value inputs go on as f32)
         float *vdst = nullptr;
-        if constexpr (RES) {   // the game's slot advances by one per simulation; the value inputs stay in LDS
+        if constexpr (PUCT) {   // no store: every piece stays in LDS for the FC layers behind this stage (fc_here)
+            dst16 = nullptr;
+        } else if constexpr (RES) {   // the game's slot advances by one per simulation; the value inputs stay in LDS
             dst16 = res_slot0 + sim < later.n_slots ? feat16 + (size_t)(res_slot0 + sim) * later.slot_halfs + (size_t)(board >> 5) * nd.groups_act * 1024 + (board & 31) * 16 : nullptr;
             vdst = res_vrow;
         } else if (deferred) {
@@ -811,7 +822,32 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
             __syncthreads();   // (a further board of this workgroup reuses the pieces and the partial sums)
         }
     }
-    if constexpr (RES) {
+    if constexpr (PUCT) {
+        // ---- the rest of the simulation under RZ_SCORE_PUCT: the body of k_tree_step_raw on this game's rows of raw / hid, which the
+        // FC layers above have just written (their last barrier stands between those stores and wave 0's loads)
+        const int game = blockIdx.x;
+        rz_raw_heads rh = rz_raw_heads();
+        rh.raw = raw;
+        rh.hid = hid;
+        rh.w2 = nd.fc_val2_w;
+        rh.b2 = nd.fc_val2_b;
+        rh.ld = nd.Npad;
+        rh.n_parts = 1;
+        // (expand_backup_body<RAW> holds no barrier: waves 1 .. 3 wait at the one below)
+        if (wave == 0) rzt::expand_backup_body<float, false, true, false, false, kResWords>(res.E, nullptr, nullptr, game, lane, rh);
+        __syncthreads();        // the tree's updates before the selection's loads
+        NET_TICK(17);
+        const bool more = sim + 1 < res_n;
+        if (wave == 0 && more) rzt::select_body<false, kResWords>(res.E, nullptr, game, lane, 0, res_leaf);
+        __syncthreads();
+        NET_TICK(18);
+        if (more) {   // the planes of the next leaf, from LDS
+            planes_from_lds(tid);
+            store_obs(tid);
+            __syncthreads();
+        }
+        NET_TICK(19);
+    } else if constexpr (RES) {
         // ---- the rest of the simulation, by the same workgroup (see k_trunk_rows: the body of k_tree_step_def, rz_tree.h)
         __syncthreads();   // the value head's inputs are in LDS
         const int game = blockIdx.x;

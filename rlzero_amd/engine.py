@@ -274,6 +274,14 @@ class HipNet(object):
             return
         check(self.lib.rz_net_search_resident(self.handle, eng.handle, int(n_sims), 1 if select_first else 0, self._stream()), 'rz_net_search_resident')
 
+    def search_resident_puct(self, eng, n_sims, select_first=False):
+        """``n_sims`` simulations of every active game of a PUCT engine in one launch (rz_net_search_resident_puct: trunk, FC layers
+        and k_tree_step_raw's body in one workgroup per game, one game per CU; no store, nothing pending)."""
+        if eng.n_games > self.max_boards:
+            self.reserve(eng.n_games)   # (a row of logits per game)
+        check(self.lib.rz_net_search_resident_puct(self.handle, eng.handle, int(n_sims), 1 if select_first else 0, self._stream()),
+              'rz_net_search_resident_puct')
+
     def deferred_gemm(self, n_boards, n_slots):
         """act_fc1 over the stored leaves of slots [0, n_slots) as one GEMM -> RzDeferredLogits."""
         out = _hip.RzDeferredLogits()
@@ -434,12 +442,18 @@ class HipNetEvaluator(object):
     # With the receptive-field trunk (k_delta_res) or the compact-grid kernel a CU holds TWO games and a launch takes any number of
     # them: beyond two per CU it runs in rounds; plan_lanes says when that pays.  RZ_NET_DELTA_RESIDENT=0: never k_delta_res.
     resident_search = True
+    # The resident search under PUCT (OPT-IN; route.decide(resident_puct=True), rz_net_search_resident_puct): the same one launch per
+    # search for score_mode 'puct' on boards of up to 10 rows and columns, one game per CU -- the FC layers run inside the trunk's
+    # workgroup and the tree code finishes the heads, so the priors exist when the next selection reads them.  The trees of the
+    # three-launch step, bit for bit.  Off: every PUCT search takes the three-launch step.
+    resident_puct = False
 
     def route(self, eng):
         """How ``eng``'s leaves are evaluated with this evaluator -> route.Route (route.decide: the one place that knows the rule)."""
         hip = self.hip   # (positional: this runs once or twice per search, next to a dozen host calls of a third of a millisecond's move)
         return _route.decide(hip.rows, hip.cols, hip.algo, hip._split_ok, hip.heads_algo, self.use_positions, self.deferred_priors, self.delta_trunk,
-                             self.resident_search, eng.score_mode, eng.sims_in_flight, eng.n_games, hip.n_cus, eng.rows == hip.rows and eng.cols == hip.cols)
+                             self.resident_search, eng.score_mode, eng.sims_in_flight, eng.n_games, hip.n_cus, eng.rows == hip.rows and eng.cols == hip.cols,
+                             None, self.resident_puct)
 
     # -- views of the route (route.Route says what each means) ---------------------------------------------------------------------
     @property
@@ -461,6 +475,12 @@ class HipNetEvaluator(object):
 
     def resident_per_cu(self, eng):
         return self.route(eng).resident_per_cu
+
+    def resident_puct_refusal(self, eng):
+        """Why ``eng`` cannot search with the resident search under PUCT (``resident_puct``) -> a sentence, or None when it can."""
+        hip = self.hip
+        return _route.resident_puct_refusal(hip.rows, hip.cols, hip.algo, hip._split_ok, hip.heads_algo, self.use_positions, self.resident_search,
+                                            eng.score_mode, eng.sims_in_flight, eng.n_games, hip.n_cus, eng.rows == hip.rows and eng.cols == hip.cols)
 
     def delta_three_launch_ok(self, eng):
         return self.route(eng).delta_three_launch
@@ -495,7 +515,11 @@ class HipNetEvaluator(object):
         return self.hip.trunk_leaves_deferred(eng)
 
     def search_resident(self, eng, n_sims, select_first=False):
-        want = self.route(eng).resident_delta
+        r = self.route(eng)
+        if r.resident and not r.deferred:   # the resident search under PUCT (resident_puct): no store, no bases
+            self.hip.search_resident_puct(eng, n_sims, select_first)
+            return
+        want = r.resident_delta
         if self._delta_res_set != want:
             check(self.hip.lib.rz_net_delta_resident(self.hip.handle, 1 if want else 0), 'rz_net_delta_resident')
             self._delta_res_set = want
@@ -932,6 +956,11 @@ class MCTSEngine(object):
             begin()
         if r.deferred:
             return self._sim_chunk_deferred(evaluator, n, r.resident)
+        if r.resident:   # the resident search under PUCT: ONE launch, the first selection included; nothing is stored for a flush
+            if self._playouts is not None or getattr(self, 'play_cap_on', False):
+                raise ValueError('per-game simulation counts (set_playouts, play_set_cap) are the deferred route\'s: the resident PUCT search has none')
+            evaluator.search_resident(self, n, True)
+            return
         obs = _ptr(self.obs) if r.needs_planes else None
         steps = -(-n // K)
         counts = [min(K, n - i * K) for i in range(steps)] + [0]  # slots in flight in step i
@@ -1423,7 +1452,12 @@ class MCTSEngine(object):
         if self._playouts is not None:
             raise HipError('warm_move_graph: clear set_playouts first (the graph would hold the host\'s counts, not play_set_cap\'s)')
         self.flush_deferred()
-        if self._deferred_begin(evaluator, n) < n or self._def_slots < n:   # (reserves the store; a search must fit between two flushes)
+        if not r.deferred:
+            # the resident search under PUCT: no store to reserve, nothing to flush in the move -- but the evaluator's buffers must
+            # not move inside the capture (a row of logits per game)
+            if self.n_games > evaluator.hip.max_boards:
+                evaluator.hip.reserve(self.n_games)
+        elif self._deferred_begin(evaluator, n) < n or self._def_slots < n:   # (reserves the store; a search must fit between two flushes)
             return None
         if r.resident_delta:
             owner.reserve_bases(self)   # (before the capture: the base cache of the receptive-field trunk; chunk graphs of the old one go)
@@ -1434,10 +1468,11 @@ class MCTSEngine(object):
         try:
             with _no_gc(), t.cuda.graph(graph):
                 st = self.stream()
-                values = self._search_mode(evaluator)   # (nothing is pending: flushed above)
+                values = self._search_mode(evaluator) if r.deferred else False   # (nothing is pending: flushed above)
                 evaluator.search_resident(self, n, True)
                 check(lib.rz_play_draw(h, st), 'rz_play_draw')
-                self._enqueue_move_flush(hip, n, values)
+                if r.deferred:
+                    self._enqueue_move_flush(hip, n, values)
                 check(lib.rz_play_apply(h, st), 'rz_play_apply')
         finally:
             self._capturing = False

@@ -70,8 +70,12 @@ class AlphaZeroMCTS(object):
     """Monte Carlo tree search guided by a policy-value function."""
 
     def __init__(self, policy_value_fn, n_playout: int = 1000, c_puct: float = 5,
-                 add_noise: bool = False, device=None, score_mode: str = 'uct_ref', sims_in_flight: int = 1) -> None:
+                 add_noise: bool = False, device=None, score_mode: str = 'uct_ref', sims_in_flight: int = 1,
+                 resident_puct: bool = False) -> None:
         self.score_mode = score_mode  # 'uct_ref' = the reference's rule (parity); 'puct' = opt-in
+        # opt-in, with score_mode 'puct': a whole search is one launch (HipNetEvaluator.resident_puct; boards of up to 10 rows);
+        # ValueError at the first search where the route cannot be served -- never the three-launch step in its place
+        self.resident_puct = bool(resident_puct)
         # opt-in, NOT the reference's algorithm: K > 1 simulations of the tree share one evaluator batch (virtual loss)
         self.sims_in_flight = max(1, int(sims_in_flight))
         self.policy_value_fn = policy_value_fn
@@ -122,6 +126,16 @@ class AlphaZeroMCTS(object):
             else:
                 make = lambda s0, s1, to_move, last: GomokuEnv.from_bitboards(size, n_row, s0, s1, to_move, last)  # noqa: E731
             self._evaluator = HostEvaluator(lambda env: self.policy_value_fn(env), make)
+        if self.resident_puct:
+            if not isinstance(self._evaluator, HipNetEvaluator):
+                eng.close()
+                raise ValueError('resident_puct=True cannot be served: the resident search is the hand-written evaluator\'s (this '
+                                 'policy_value_fn runs on the host or through PyTorch)')
+            why = self._evaluator.resident_puct_refusal(eng)
+            if why is not None:
+                eng.close()
+                raise ValueError('resident_puct=True cannot be served: ' + why)
+            self._evaluator.resident_puct = True
         self._engine = eng
         self._bound_k = self.sims_in_flight
         # device evaluators: the simulation loop is replayed from a hipGraph of 8 simulations (three launches each) --
@@ -207,13 +221,13 @@ class AlphaZeroPlayer(Player):
 
     def __init__(self, policy_value_fn, n_playout: int = 1000, c_puct: float = 5,
                  is_selfplay: bool = False, player_id: int = 0, player_name: str = '',
-                 device=None, score_mode: str = 'uct_ref', sims_in_flight: int = 1) -> None:
+                 device=None, score_mode: str = 'uct_ref', sims_in_flight: int = 1, resident_puct: bool = False) -> None:
         super().__init__(player_id, player_name)
         self.is_selfplay = is_selfplay
         self.add_noise = is_selfplay
         self.mcts = AlphaZeroMCTS(policy_value_fn, n_playout=n_playout, c_puct=c_puct,
                                   add_noise=self.add_noise, device=device, score_mode=score_mode,
-                                  sims_in_flight=sims_in_flight)
+                                  sims_in_flight=sims_in_flight, resident_puct=resident_puct)
 
     def reset_player(self):
         self.mcts.update_with_move(-1)

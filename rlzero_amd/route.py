@@ -3,12 +3,13 @@ HipNet, HipNetEvaluator, MCTSEngine and BatchedSelfPlay.for_network ask ``decide
 
 The library decides the same once more for the net it holds: ``rows_kernel_covers`` / ``split_trunk_ok`` / ``delta_covers`` /
 ``compact_grid_covers`` / ``trunk_class`` in csrc/rz_net.hip.  THAT is the one other place that must agree with this module; its
-RZ_ERR_ARG returns (rz_net_trunk_leaves*, rz_net_search_resident, rz_net_delta_*, rz_net_set_algo) are the backstop when they do not.
+RZ_ERR_ARG returns (rz_net_trunk_leaves*, rz_net_search_resident, rz_net_search_resident_puct, rz_net_delta_*, rz_net_set_algo) are the
+backstop when they do not.
 """
 import os
 from collections import namedtuple
 
-from ._hip import SCORE_UCT_REF   # (constants only: importing _hip loads nothing)
+from ._hip import SCORE_PUCT, SCORE_UCT_REF   # (constants only: importing _hip loads nothing)
 
 # the algorithm classes (HipNet.set_algo names)
 SPLIT_TRUNKS = ('split_f16', 'split_f16_tiles', 'split_f16_fp8')   # the split-f16 trunks: fed positions, deferred priors
@@ -84,11 +85,16 @@ resident_per_cu     resident workgroups a CU holds (2: a launch takes any number
 
 
 def decide(rows, cols, algo='split_f16', split_ok=True, heads_algo='auto', use_positions=True, deferred_priors=True, delta_trunk=True,
-           resident_search=True, score_mode=SCORE_UCT_REF, in_flight=1, n_games=0, n_cus=0, same_board=True, environ=None):
+           resident_search=True, score_mode=SCORE_UCT_REF, in_flight=1, n_games=0, n_cus=0, same_board=True, environ=None, resident_puct=False):
     """-> Route.  ``rows`` / ``cols`` / ``algo`` / ``split_ok`` (rz_net_load found finite activation bounds) / ``heads_algo``: the net;
     ``use_positions`` and the three switches: the evaluator; ``score_mode`` / ``in_flight`` / ``n_games`` / ``same_board`` (its board is
     the net's): the engine; ``n_cus``: the chip.  ``environ``: RZ_NET_DELTA, RZ_NET_DELTA_RESIDENT, RZ_NET_COMPACT ('0' = off) are read
-    from it at every call -- None: os.environ; {}: what the kernels can do, whatever the environment says."""
+    from it at every call -- None: os.environ; {}: what the kernels can do, whatever the environment says.
+    ``resident_puct`` (the evaluator's opt-in switch, HipNetEvaluator.resident_puct; off: every Route is what it was without it): the
+    resident search under PUCT (rz_net_search_resident_puct, whose refusals in csrc/rz_net.hip state this rule once more) --
+    ``resident`` is then also true when resident_puct_refusal() finds nothing: the split-f16 trunk fed positions, one simulation in
+    flight, PUCT, a board of up to 10 x 10 that is the net's, any FC arithmetic but 'f32', the resident switch on, at most one game
+    per CU.  ``resident_per_cu`` is 1 there and ``deferred`` stays false: nothing of such a search waits for a flush."""
     split = split_ok and algo in SPLIT_TRUNKS
     one_sim = in_flight == 1
     deferred = bool(split and deferred_priors and use_positions and one_sim and score_mode in (SCORE_UCT_REF, 'uct_ref'))
@@ -98,5 +104,33 @@ def decide(rows, cols, algo='split_f16', split_ok=True, heads_algo='auto', use_p
     net_resident = split and algo in RESIDENT_TRUNKS and (rows_board or tile_resident_board(rows, cols))
     compact = net_resident and not rows_board and compact_grid_board(rows, cols, environ)
     per_cu = 2 if (resident_delta or (compact and same_board)) else 1
+    if resident_puct and resident_puct_refusal(rows, cols, algo, split_ok, heads_algo, use_positions, resident_search, score_mode, in_flight,
+                                               n_games, n_cus, same_board) is None:
+        return Route(False, False, False, False, True, False, False, 1)   # (no receptive-field trunk up to 10 rows; the 18 x 18 grid)
     return Route(not (use_positions and split), deferred, delta, bool(delta and use_positions and one_sim and not deferred and heads_algo != 'f32'),
                  bool(resident_search and deferred and net_resident and (per_cu >= 2 or n_games <= n_cus)), resident_delta, compact, per_cu)
+
+
+def resident_puct_refusal(rows, cols, algo='split_f16', split_ok=True, heads_algo='auto', use_positions=True, resident_search=True,
+                          score_mode=SCORE_PUCT, in_flight=1, n_games=0, n_cus=0, same_board=True):
+    """Why the resident search under PUCT (rz_net_search_resident_puct) cannot serve these numbers -> a sentence, or None when it can.
+    THE rule of that route on this side of the ABI (decide(resident_puct=True) asks here); rz_net.hip's refusals are the other copy."""
+    if score_mode not in (SCORE_PUCT, 'puct'):
+        return 'score_mode %r: the resident PUCT search is for score_mode \'puct\' (uct_ref has the resident search of the deferred route)' % (score_mode, )
+    if in_flight != 1:
+        return 'sims_in_flight %d: the resident search runs one simulation in flight per tree' % in_flight
+    if not (split_ok and algo in SPLIT_TRUNKS):
+        return 'net_algo %r: the resident search needs the split-f16 trunk (a net with finite activation bounds)' % (algo, )
+    if not use_positions:
+        return 'the resident search is fed positions (use_positions)'
+    if not tile_resident_board(rows, cols):
+        return 'a board of %d x %d: the resident PUCT search exists for boards of up to 10 rows and columns' % (rows, cols)
+    if not same_board:
+        return 'engine and network disagree on the board'
+    if heads_algo == 'f32':
+        return 'heads_algo \'f32\': the resident PUCT search runs the FC layers on the f16 pipe'
+    if not resident_search:
+        return 'the resident search is switched off (resident_search)'
+    if n_games > n_cus:
+        return '%d games on %d CUs: the resident PUCT search holds one game per CU' % (n_games, n_cus)
+    return None

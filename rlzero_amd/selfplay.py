@@ -430,11 +430,25 @@ def choose_lanes_by_measurement(key, table_pick, hw_queues, n_games, build, time
 
 
 def plan_route(rows, cols, game, net_algo, score_mode, in_flight, deferred_priors=None, delta_trunk=None, resident_search=None,
-               n_games=0, n_cus=0):
+               n_games=0, n_cus=0, resident_puct=False, lanes=None, host_evaluator=False):
     """What plan_lanes() is told of the route (its ``deferred`` / ``cells`` / ``in_flight`` / ``resident_per_cu``) for the evaluators
-    for_network() will build from these arguments: route.decide() on numbers alone -- no net, no engine, no GPU."""
+    for_network() will build from these arguments: route.decide() on numbers alone -- no net, no engine, no GPU.
+    ``resident_puct`` (for_network's switch: the resident search under PUCT, one game per CU): asked for where it cannot be served it
+    raises ValueError with the reason (route.resident_puct_refusal: the selection rule, sims_in_flight, the trunk, the board; a host
+    evaluator; more games per lane than CUs, with ``lanes`` as given or as plan_lanes() splits the batch) -- never another route."""
+    if resident_puct:
+        why = 'a host evaluator has no resident search' if host_evaluator else _route.resident_puct_refusal(
+            rows, cols, net_algo or 'split_f16', resident_search=resident_search is not False, score_mode=score_mode, in_flight=in_flight)
+        if why is None:
+            n_lanes = lanes if isinstance(lanes, int) else plan_lanes(n_games, n_cus or TABLE_CUS, in_flight=in_flight)[0]
+            per_lane = -(-n_games // max(1, min(int(n_lanes), max(1, n_games))))
+            if n_cus and per_lane > n_cus:
+                why = '%d games per lane on %d CUs: the resident PUCT search holds one game per CU' % (per_lane, n_cus)
+        if why is not None:
+            raise ValueError('resident_puct=True cannot be served: ' + why)
     r = _route.decide(rows, cols, net_algo or 'split_f16', deferred_priors=deferred_priors is not False, delta_trunk=delta_trunk is not False,
-                      resident_search=resident_search is not False, score_mode=score_mode, in_flight=in_flight, n_games=n_games, n_cus=n_cus)
+                      resident_search=resident_search is not False, score_mode=score_mode, in_flight=in_flight, n_games=n_games, n_cus=n_cus,
+                      resident_puct=bool(resident_puct))
     algo_of_small_boards = (net_algo or 'split_f16') in _route.EVERY_BOARD_SPLIT_TRUNKS
     return dict(deferred=r.deferred and game == 'gomoku' and _route.rows_kernel_board(rows, cols),   # (the table's deferred rows: 15x15 Gomoku and its kin)
                 cells=rows * cols if ((r.deferred and algo_of_small_boards) or in_flight > 1) else None, in_flight=in_flight,
@@ -648,8 +662,9 @@ class BatchedSelfPlay(SelfPlayReader):
         if len(engines) > 1 and sum(e.n_games for e in engines) > n_cus * min(r.resident_per_cu for r, _, _ in asked):
             # lanes that share CUs: the resident search (a workgroup keeps its CU for a whole search) is for games that have a CU
             # each -- these lanes run the two-launch step, whose trunk workgroups make way for the other lanes every step
+            # (asked for explicitly -- resident_puct -- it stays: such lanes' launches take turns on the CUs)
             for _, owner, _ in asked:
-                if owner is not None:
+                if owner is not None and not getattr(owner, 'resident_puct', False):
                     owner.resident_search = False
         self.eng = engines[0]  # geometry (board size, n_playout) is common to all lanes
         self.evaluator = evaluators[0]
@@ -705,7 +720,8 @@ class BatchedSelfPlay(SelfPlayReader):
             if not 0.0 < p_full <= 1.0:
                 raise ValueError('p_full %r not in (0, 1]' % p_full)
             for lane in self.lanes:
-                if not lane.eng._ask(lane.evaluator)[0].resident:
+                r_lane = lane.eng._ask(lane.evaluator)[0]
+                if not (r_lane.resident and r_lane.deferred):   # (the resident search under PUCT has no per-game budgets)
                     raise ValueError('the playout cap needs the resident search on every lane (this route has none: two-launch lanes, '
                                      'PUCT, sims_in_flight > 1 and host evaluators search every game alike)')
             self.playout_cap = (n_fast, p_full)
@@ -787,7 +803,7 @@ class BatchedSelfPlay(SelfPlayReader):
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
                     deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None,
-                    temperature_schedule=None, pi_temperature=None, root_values=False, **engine_kw):
+                    temperature_schedule=None, pi_temperature=None, root_values=False, resident_puct=False, **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -806,7 +822,11 @@ class BatchedSelfPlay(SelfPlayReader):
         checker of the receptive-field evaluation, HipNetEvaluator.delta_trunk; with it goes the resident search's second game per CU).
         ``resign``: None (off) or a threshold or (threshold, disabled_frac): set_resign.  ``playout_cap``: None (off) or (n_fast, p_full):
         set_playout_cap.  ``temperature_schedule``: None (off) or a table of per-ply temperatures, with ``pi_temperature``:
-        set_temperature_schedule.  ``root_values``: set_root_values."""
+        set_temperature_schedule.  ``root_values``: set_root_values.
+        ``resident_puct`` (opt-in, with ``score_mode='puct'``): every lane searches with the one-launch resident search under PUCT
+        (HipNetEvaluator.resident_puct: boards of up to 10 rows and columns, one simulation in flight, at most one game per CU and
+        lane) -- run, run_device and the whole-move hipGraphs then play the games of the three-launch step, bit for bit.  ValueError
+        where it cannot be served (plan_route names the reason); nothing falls back to another route."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -815,7 +835,8 @@ class BatchedSelfPlay(SelfPlayReader):
         shape0 = net_shape if net_shape is not None else board
         rows0, cols0 = (shape0[0], shape0[1]) if isinstance(shape0, (tuple, list)) else (shape0, shape0)
         planned = plan_route(rows0, cols0, game, net_algo, engine_kw.get('score_mode', 'uct_ref'), K, deferred_priors=deferred_priors,
-                             delta_trunk=delta_trunk, resident_search=resident_search, n_games=n_games, n_cus=n_cus)
+                             delta_trunk=delta_trunk, resident_search=resident_search, n_games=n_games, n_cus=n_cus,
+                             resident_puct=resident_puct, lanes=lanes if isinstance(lanes, int) else None)
         deferred = planned['deferred']
         auto_lanes, auto_wgs, heads_algo = plan_lanes(n_games * K, n_cus, **planned)
         measured = None
@@ -834,7 +855,7 @@ class BatchedSelfPlay(SelfPlayReader):
                                        net_shape=net_shape, lanes=n_lanes, trunk_workgroups=trunk_workgroups, temperature=temperature,
                                        seed=seed, use_graph=use_graph, sims_per_graph=sims_per_graph, add_noise=add_noise,
                                        sims_in_flight=sims_in_flight, deferred_priors=deferred_priors, resident_search=resident_search,
-                                       net_algo=net_algo, delta_trunk=delta_trunk, **engine_kw)
+                                       net_algo=net_algo, delta_trunk=delta_trunk, resident_puct=resident_puct, **engine_kw)
             lanes, measured = choose_lanes_by_measurement(key, auto_lanes, HW_QUEUES, n_games, build)
         if lanes is None:
             lanes, wgs = auto_lanes, auto_wgs
@@ -863,10 +884,18 @@ class BatchedSelfPlay(SelfPlayReader):
                 ev.resident_search = bool(resident_search)
             if delta_trunk is not None:
                 ev.delta_trunk = bool(delta_trunk)
+            ev.resident_puct = bool(resident_puct)
             evaluators.append(ev)
         sp = cls(engines if lanes > 1 else engines[0], evaluators if lanes > 1 else evaluators[0],
                  temperature=temperature, seed=seed, use_graph=use_graph, sims_per_graph=sims_per_graph,
                  eager_every=eager_every)
+        if resident_puct:
+            for lane in sp.lanes:   # (what plan_route could not see: the net's weights, the lanes as built)
+                if not lane.eng._ask(lane.evaluator)[0].resident:
+                    for other in sp.lanes:
+                        other.eng.close()
+                    raise ValueError('resident_puct=True cannot be served: a lane of %d games does not take the resident route '
+                                     '(weights without finite activation bounds, or more games than CUs)' % lane.eng.n_games)
         sp.trunk_workgroups = int(wgs)
         sp.lanes_measured = measured   # {lanes: simulations / s} when the layout was chosen by measurement, else None
         if resign is not None:
