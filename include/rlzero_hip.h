@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 46
+#define RZ_ABI_VERSION 47
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -534,6 +534,30 @@ int rz_play_set_cap_order(rz_engine *e, int32_t longest_first);
  * afterwards and while a match is on; rz_play_set_match is refused while a ring is set.  rz_play_attach turns it off.  `stream` is
  * unused: nothing is enqueued. */
 int rz_play_set_root_values(rz_engine *e, float *d_ring, void *stream);
+/* FORCED PLAYOUTS AND POLICY TARGET PRUNING (ABI 47; an opt-in extension of RZ_SCORE_PUCT self-play after Wu 2019, section 3.2; the
+ * two rules are rlzero_amd/csrc/rz_forced.h, in fp64, tested on the CPU).  With N the visit count of the ROOT RECORD (the N whose
+ * square root the PUCT term uses; under tree reuse whatever the record holds) and n, p a root child's visit count and stored prior
+ * (the noised one where noise is on):
+ *   forced playouts   in the ROOT's child scan a child with n > 0 and n n < (k p) N scores +infinity; several such children resolve
+ *                     by the first-maximum rule.  Deeper levels, and a root that is still a leaf, are untouched.
+ *   pruning           the best child (the first with the largest n) keeps n; every other child loses playouts one at a time, at
+ *                     most f of them (f the largest integer with f f <= (k p) N), while its PUCT at one playout fewer (its q = w / n
+ *                     held constant) stays below the best child's PUCT; a child left with a single playout goes to 0.
+ * rz_set_forced_playouts: k > 0 turns the rule on for every search of the engine that follows -- the three-launch step (rz_select_step,
+ * rz_tree_step, rz_tree_step_raw) on any board and rz_net_search_resident_puct -- and 0 turns it off (the default: nothing changes).
+ * RZ_ERR_ARG: an engine whose rule is not RZ_SCORE_PUCT, sims_in_flight > 1, a match that is on, k negative or not finite, and --
+ * k travels in the kernel arguments -- once a move step has been enqueued or captured, or a ring of pruned counts set, since
+ * rz_play_attach ("attach again").  (rz_play_set_match refuses every RZ_SCORE_PUCT engine, so no match can begin while k > 0.)
+ * rz_root_pruned_visits: d_out int32 [n_games][A] <- the pruned count of every legal action of the roots, -1 for an illegal one
+ * (k_root_pruned: one wave per game, the children in action order as rz_root_visits gives them); k == 0: the raw counts.
+ * rz_play_set_pruned_visits: the same launch inside the device move step, in front of the draw (so a whole-move graph holds it and
+ * stays one replay): d_ring int32 [ring_steps][n_games][A] of the caller -- device memory, or pinned host memory the device can
+ * address --, row step % ring_steps aligned with the log's rows; a stalled slot repeats its searched row, an idle slot holds -1.
+ * The log's records and its raw counts do not change: the move is still drawn from them.  NULL: off again.  Valid after
+ * rz_play_attach with k > 0 and before the first move step is enqueued or captured; rz_play_attach turns it off.  `stream` unused. */
+int rz_set_forced_playouts(rz_engine *e, double k);
+int rz_root_pruned_visits(rz_engine *e, int32_t *d_out, void *stream);
+int rz_play_set_pruned_visits(rz_engine *e, int32_t *d_ring, void *stream);
 /* Match mode (above).  The table -- d_open_stones uint64 [n_openings][2][RZ_BOARD_WORDS], d_open_to_move / d_open_last int32
  * [n_openings], device memory -- is copied on `stream` into the engine's own; launches enqueued after the call read it.
  * n_openings == 0 (pointers ignored): off again.  Valid after rz_play_attach, before the games are queued, on an engine without

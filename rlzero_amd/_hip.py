@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 46
+ABI_VERSION = 47
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -182,6 +182,9 @@ _SIGNATURES = {
     'rz_playouts_view': (c_int, [P, POINTER(c_void_p), POINTER(c_void_p)]),
     'rz_play_set_cap_order': (c_int, [P, c_int32]),
     'rz_play_set_root_values': (c_int, [P, P, P]),
+    'rz_set_forced_playouts': (c_int, [P, c_double]),
+    'rz_root_pruned_visits': (c_int, [P, P, P]),
+    'rz_play_set_pruned_visits': (c_int, [P, P, P]),
     'rz_playouts_read': (c_int, [P, P, P, POINTER(c_int32)]),
     'rz_play_set_match': (c_int, [P, P, P, P, c_int32, P]),
     'rz_play_side': (c_int, [P, c_int32, P]),

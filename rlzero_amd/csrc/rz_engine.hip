@@ -61,7 +61,7 @@ namespace {
 
 __global__ __launch_bounds__(kWave) void k_select(Dev E, float *obs) {
     __builtin_amdgcn_s_setprio(3);  // latency-bound: issue ahead of a co-resident MFMA kernel
-    select_body<false>(E, obs, blockIdx.x, threadIdx.x);
+    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
 }
 
 template <typename VT, bool PROBS = false>
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kWave) void k_tree_step_raw(Dev E, RawHeads rh, flo
     __builtin_amdgcn_s_setprio(3);
     expand_backup_body<float, false, true>(E, nullptr, nullptr, blockIdx.x, threadIdx.x, rh);
     __syncthreads();
-    select_body<false>(E, obs, blockIdx.x, threadIdx.x);
+    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
 }
 
 // ------------------------------------------------------------------ deferred priors (value_quarter_def: rz_tree.h)
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(kWave) void k_tree_step(Dev E, const float *logp, c
     __builtin_amdgcn_s_setprio(3);
     expand_backup_body<VT>(E, logp, value, blockIdx.x, threadIdx.x);
     __syncthreads();
-    select_body<false>(E, obs, blockIdx.x, threadIdx.x);
+    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
 }
 
 // K simulations in flight (opt-in): the game's wave backs up the kb pending slots of the previous step one after
@@ -1391,6 +1391,85 @@ __global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y, float *__res
     if (o.active >= 0) E.active[g] = (uint8_t)o.active;
 }
 
+// Policy target pruning (rz_forced.h; rz_root_pruned_visits, rz_play_set_pruned_visits), one wave per game: the root's children by
+// action exactly as k_play_draw gathers them, their priors from P[pb + r]; the best child -- the first with the largest count, found
+// with the selection's first-maximum vote over (count, action) -- keeps its count, every other visited child gets rzf::pruned_child
+// against the best child's PUCT.  int32 [A] per game: the pruned count of a legal action, -1 of an illegal one.  forced_k == 0: the
+// raw counts.  `ring` != 0 (the launch in front of k_play_draw): the row of this move step in the side ring [Y.ring][G][A], -1 all
+// over for an idle slot; a stalled slot's root has not changed, so its rows repeat the searched one.  ring == 0: row g of [G][A].
+__global__ __launch_bounds__(kWave) void k_root_pruned(Dev E, Play Y, int32_t *__restrict__ out, int ring) {
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    int32_t *row = out + (long long)g * E.A;
+    bool idle = false;
+    if (ring) {
+        row += (long long)(Y.step_ab[0] % Y.ring) * E.n_games * E.A;
+        idle = Y.state[g] == ry::kIdle;
+    }
+    if (idle) {
+        for (int a = lane; a < E.A; a += kWave) row[a] = -1;
+        return;
+    }
+    const int arena = E.cur_arena[g];
+    const int4 *R = arena_records(E, g, arena);
+    const float *P = arena_priors(E, g, arena);
+    uint64_t st[2][kWords], occ[kWords];
+    load_board(E.root_stones, g, st);
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
+    const Legal L = legal_of(E, occ, lane);
+    const int4 lo = R[0], hi = R[1];
+    const bool expanded = rec_k(lo) > 0;
+    const int fc = lo.y, pb = hi.z;
+    const int nv = expanded ? lo.z : 0;
+    const double k = E.forced_k;
+    const bool prune = k > 0.0 && pb >= 0;
+    int before = 0;
+    int cnt[kWords];
+    bool legal[kWords];
+    double w[kWords];
+    float p[kWords];
+    // the lane's own best child: the first of its (up to four) actions with the largest count
+    double best = -INFINITY, bw = 0.0;
+    int besti = 0x7fffffff, bn = 0;
+    float bp = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) {
+        const int r = lane_action_rank(E, occ, L, j, lane, before);
+        const int a = 64 * j + lane;
+        legal[j] = a < E.A && r >= 0;
+        const bool seen = legal[j] && r < nv;
+        cnt[j] = seen ? R[2 * (fc + r)].x : 0;
+        w[j] = seen ? rec_w(R[2 * (fc + r) + 1]) : 0.0;
+        p[j] = seen && prune ? P[pb + r] : 0.0f;
+        if (legal[j] && (double)cnt[j] > best) {
+            best = (double)cnt[j];
+            besti = a;
+            bw = w[j];
+            bn = cnt[j];
+            bp = p[j];
+        }
+    }
+    const int bi = __builtin_amdgcn_readfirstlane(wave_first_max(best, besti));
+    double s_best = 0.0;
+    if (bi != 0x7fffffff) {   // (a root without a legal action has no best child: its row is -1 all over)
+        const int l = bi & 63;
+        const long long wb = __double_as_longlong(bw);
+        const double w_best = __hiloint2double(__builtin_amdgcn_readlane((int)(wb >> 32), l), __builtin_amdgcn_readlane((int)wb, l));
+        const int n_best = __builtin_amdgcn_readlane(bn, l);
+        const float p_best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bp), l));
+        s_best = rzf::puct(w_best, n_best, p_best, sqrt((double)lo.x), E.c_puct);
+    }
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) {
+        const int a = 64 * j + lane;
+        if (a >= E.A) continue;
+        int m = -1;
+        if (legal[j]) m = (!prune || a == bi) ? cnt[j] : rzf::pruned_child(cnt[j], w[j], p[j], lo.x, sqrt((double)lo.x), k, E.c_puct, s_best);
+        row[a] = m;
+    }
+}
+
 // The rest of a move in ONE launch, one wave per slot: update_with_move with the move just drawn (advance_body: before the board
 // changes), env.step + game_end_winner (step_body), then the end of a finished game (reset_player, game.py:128) and the refill of an
 // idle slot from the queue of game ids (GomokuEnv.reset, gomoku_env.py:33-47: empty board, player 0; a fresh tree; the game's
@@ -1604,6 +1683,7 @@ struct rz_engine {
     bool play_on = false, play_drawn = false;
     long long play_steps = 0;   // move steps enqueued (rz_play_apply calls) since rz_play_attach
     float *play_vring = nullptr;   // rz_play_set_root_values: the caller's ring of root values (nullptr: off), an argument of k_play_draw
+    int32_t *play_pring = nullptr;   // rz_play_set_pruned_visits: the caller's ring of pruned counts (nullptr: off), written by k_root_pruned in front of the draw
     // rz_set_playouts: the host's per-game simulation counts (and workgroup order) of the resident search, copies of the caller's
     int32_t *pl_counts = nullptr, *pl_order = nullptr;
     bool pl_on = false, pl_ordered = false;
@@ -2272,6 +2352,52 @@ int rz_root_values(rz_engine *e, double *d_out, void *stream) {
     return rz_launched("k_root_values");
 }
 
+int rz_set_forced_playouts(rz_engine *e, double k) {
+    RZ_ENTER(eng_ready, e);
+    if (!(std::isfinite(k) && k >= 0.0)) return rz_fail(RZ_ERR_ARG, "rz_set_forced_playouts: k = %g is not a finite number >= 0", k);
+    // (a match first: today it runs under RZ_SCORE_UCT_REF only, and the sentence a caller reads should name what it turned on)
+    if (e->play_on && e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_set_forced_playouts: a match is on (rz_play_set_match): its games are not training data");
+    if (e->dev.score_mode != RZ_SCORE_PUCT) return rz_fail(RZ_ERR_ARG, "rz_set_forced_playouts: forced playouts are a rule of RZ_SCORE_PUCT (this engine selects by RZ_SCORE_UCT_REF)");
+    if (e->dev.K != 1) return rz_fail(RZ_ERR_ARG, "rz_set_forced_playouts: one simulation in flight per tree only (sims_in_flight = %d)", e->dev.K);
+    // k travels in the kernel arguments: a move step enqueued -- or captured into a whole-move graph -- keeps the one it had, and the
+    // ring of pruned counts was handed over for the k it was set under
+    if (e->play_on && (e->play_steps > 0 || e->play_drawn || e->play_pring != nullptr))
+        return rz_fail(RZ_ERR_ARG, "rz_set_forced_playouts: the move step holds k since rz_play_attach (attach again)");
+    e->dev.forced_k = k;
+    return RZ_OK;
+}
+
+int rz_root_pruned_visits(rz_engine *e, int32_t *d_out, void *stream) {
+    RZ_ENTER(eng_ready, e);
+    RZ_NEED(d_out);
+    k_root_pruned<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play, d_out, 0);
+    return rz_launched("k_root_pruned");
+}
+
+int rz_play_set_pruned_visits(rz_engine *e, int32_t *d_ring, void *stream) {
+    RZ_ENTER_PLAY(e);
+    (void)stream;   // (nothing is enqueued: the ring is an argument of the launches to come)
+    if (e->play_steps > 0 || e->play_drawn) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: a move step has been enqueued since rz_play_attach (attach again)");
+    if (d_ring != nullptr && !(e->dev.forced_k > 0.0)) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: forced playouts are off (rz_set_forced_playouts first)");
+    if (d_ring != nullptr && e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: a match is on (rz_play_set_match): its games are not training data");
+    if (d_ring != nullptr) {   // host memory (pinned, written directly like the log) must be addressable from this device
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        if (hipPointerGetAttributes(&attr, d_ring) != hipSuccess) {
+            (void)hipGetLastError();
+        } else if (attr.type == hipMemoryTypeHost) {
+            void *dp = nullptr;
+            if (hipHostGetDevicePointer(&dp, d_ring, 0) != hipSuccess || dp == nullptr) {
+                (void)hipGetLastError();
+                return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: d_ring is host memory that device %d cannot address (pass device memory)", e->cfg.device);
+            }
+            d_ring = static_cast<int32_t *>(dp);
+        }
+    }
+    e->play_pring = d_ring;
+    return RZ_OK;
+}
+
 int rz_advance_roots(rz_engine *e, const int32_t *d_moves, void *stream) {
     RZ_ENTER(eng_ready, e);
     RZ_NEED(d_moves);
@@ -2357,6 +2483,7 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     e->play_drawn = false;
     e->play_steps = 0;
     e->play_vring = nullptr;   // (and the ring of root values: rz_play_set_root_values)
+    e->play_pring = nullptr;   // (and the ring of pruned counts: rz_play_set_pruned_visits)
     return RZ_OK;
 }
 
@@ -2406,6 +2533,8 @@ int rz_play_queue_push(rz_engine *e, int64_t first_id, int32_t count, void *stre
 
 int rz_play_draw(rz_engine *e, void *stream) {
     RZ_ENTER_PLAY(e);
+    // (rz_play_set_pruned_visits: the pruned counts of the roots the draw is about to read, into the row of the same step)
+    if (e->play_pring != nullptr) k_root_pruned<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play, e->play_pring, 1);
     k_play_draw<<<per_game(e), dim3(kWave), 0, as_stream(stream)>>>(e->dev, e->play, e->play_vring);
     e->play_drawn = true;
     return rz_launched("k_play_draw");

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
     bool hw_pending = true;
     if constexpr (RES) {
         if (sel_first) {   // AlphaZeroMCTS._playout's select loop for the first simulation of the search (rz_select_step's work)
-            if ((tid0 >> 6) == 0) rzt::select_body<false, kResWords>(res.E, nullptr, blockIdx.x, tid0 & 63, 0, res_leaf);
+            if ((tid0 >> 6) == 0) rzt::select_body<false, kResWords, rzt::NoHook, PUCT>(res.E, nullptr, blockIdx.x, tid0 & 63, 0, res_leaf);
             __syncthreads();
             planes_from_lds(tid0);
         }
@@ -838,7 +838,7 @@ __global__ __launch_bounds__(256, (RW == kRowW ? 1 : 2)) void k_trunk_split(NetD
         __syncthreads();        // the tree's updates before the selection's loads
         NET_TICK(17);
         const bool more = sim + 1 < res_n;
-        if (wave == 0 && more) rzt::select_body<false, kResWords>(res.E, nullptr, game, lane, 0, res_leaf);
+        if (wave == 0 && more) rzt::select_body<false, kResWords, rzt::NoHook, true>(res.E, nullptr, game, lane, 0, res_leaf);   // (forced playouts: Dev::forced_k)
         __syncthreads();
         NET_TICK(18);
         if (more) {   // the planes of the next leaf, from LDS

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "rlzero_hip.h"
+#include "rz_forced.h"
 #include "rz_play.h"
 #include "rz_trace.h"
 
@@ -63,6 +64,9 @@ struct Dev {
     // tree step scalar registers it does not have (68 B of scratch)
     const uint64_t *line_tab;
     int line_masks;   // four-word boards: != 0 when the first n - 1 cells of every window fit the 64 bits of its mask (else cell by cell)
+    // forced playouts at the root (rz_set_forced_playouts, rz_forced.h): k, 0 = off.  Read only by the kernels that can run PUCT
+    // (select_body<.., FORCED>); the last member, so every other one keeps its offset in the kernel arguments
+    double forced_k;
 };
 
 // a pending record's word: the leaf's last move + 1 (0: none) in the low half, its side to move above
@@ -351,11 +355,9 @@ __device__ __forceinline__ double uct_ref(double w, int n, double ln_parent, dou
 
 // Opt-in PUCT (node.py:105-117 with Q = 0 at N = 0 instead of the reference's division by zero):
 // exploration_score + c_puct * (prior * sqrt(parent N) / (N + 1)), evaluated in this order in fp64.
+// (rz_forced.h holds the one copy: the pruning of the policy target evaluates the same function on the CPU and in k_root_pruned)
 __device__ __forceinline__ double puct(double w, int n, float prior, double sqrt_parent, double c) {
-    const double q = n > 0 ? w / (double)n : 0.0;
-    const double u = ((double)prior * sqrt_parent) / (double)(n + 1);
-    const double cu = c * u;
-    return q + cu;
+    return rzf::puct(w, n, prior, sqrt_parent, c);
 }
 
 using rzplay::mix64;   // (rz_play.h: one definition for host and device)
@@ -507,11 +509,14 @@ __device__ __forceinline__ int4 load_half(const int4 *R, int idx) {
         return R[idx];
     }
 }
-template <bool PUCT, int W = kWords, bool PRE = false>
+// FORCED (PUCT only; the root's scan of the kernels that can run PUCT): a child that rzf::forced holds below its floor of visits
+// scores +infinity -- forced_k > 0 is the engine's k (rz_set_forced_playouts), a value <= 0 leaves every score as it is.
+template <bool PUCT, int W = kWords, bool PRE = false, bool FORCED = false>
 __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const float *P, const int4 &lo,
                                              const int4 &hi, double parent_term, int lane, int4 &clo, int4 &chi,
-                                             int skip = -1, double *best_out = nullptr) {
+                                             int skip = -1, double *best_out = nullptr, double forced_k = 0.0) {
     static_assert(!(PRE && PUCT), "the pre-scan is the reference rule's");
+    static_assert(!FORCED || PUCT, "forced playouts are PUCT's");
     const int k = rec_k(lo), fc = lo.y, pb = hi.z;
     // the lane's (up to) four children r0 = lane + 64 j: all loads first, then the scores; the lane keeps the RECORD
     // of its best child in registers (no array survives the loop: an array of records selected by a run-time index
@@ -534,8 +539,11 @@ __device__ __forceinline__ int scan_children(const Dev &E, const int4 *R, const 
         bool in = r0 < k;
         if constexpr (PRE) in = in && r0 != skip;
         if (in) {
-            const double sc = PUCT ? puct(rec_w(ch), cl.x, prior, parent_term, E.c_puct)
-                                   : uct_ref(rec_w(ch), cl.x, parent_term, E.c_puct);
+            double sc = PUCT ? puct(rec_w(ch), cl.x, prior, parent_term, E.c_puct)
+                             : uct_ref(rec_w(ch), cl.x, parent_term, E.c_puct);
+            if constexpr (FORCED) {
+                if (forced_k > 0.0 && rzf::forced(cl.x, prior, lo.x, forced_k)) sc = INFINITY;
+            }
             if (sc > best) {
                 best = sc;
                 besti = r0;
@@ -634,10 +642,13 @@ __device__ __forceinline__ void root_prescan(const Dev &E, int g, int lane, Root
 // inactive one before its first barrier) -- the early return on `!act` below lies in front of the hook, and nothing inside a launch
 // clears the flag (flag() sets error bits only);
 // hook->tick(i, v) is a phase tick of the profile build behind the arrival of v.  NoHook: none of it.
-template <bool VL, int W = kWords, class Hook = NoHook>
+// FORCED (k_select, k_tree_step, k_tree_step_raw, k_trunk_split<.., PUCT>: the kernels that can run PUCT with one simulation in
+// flight): the root's PUCT scan applies the forced-playout rule when E.forced_k > 0; every other instantiation compiles as before.
+template <bool VL, int W = kWords, class Hook = NoHook, bool FORCED = false>
 __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr,
                                             Hook *hook = nullptr) {
     static_assert(!(Hook::kOn && VL), "the root pre-scan is the sequential search's");
+    static_assert(!(FORCED && (VL || Hook::kOn)), "forced playouts: one simulation in flight, no root pre-scan");
     const int gk = VL ? g * E.K + j : g;
     // every load that does not depend on another one is issued before `active` is tested: a kernel of dependent
     // round trips (an inactive game's slots exist, reading them is harmless)
@@ -692,7 +703,14 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         int4 clo = make_int4(0, -1, 0, 0), chi = make_int4(0, 0, -1, 0);
         if (use_puct) {
             // every child was initialised at expansion (N = 0, W = 0): scan all k
-            r = scan_children<true, W>(E, R, P, lo, hi, sqrt((double)lo.x), lane, clo, chi);
+            // (FORCED: k is wave-uniform, so this is a scalar branch -- with the rule off, and below the root, the scan is the one it
+            // always was, instruction for instruction)
+            bool force = false;
+            if constexpr (FORCED) force = it == 0 && E.forced_k > 0.0;
+            if (force)
+                r = scan_children<true, W, false, FORCED>(E, R, P, lo, hi, sqrt((double)lo.x), lane, clo, chi, -1, nullptr, E.forced_k);
+            else
+                r = scan_children<true, W>(E, R, P, lo, hi, sqrt((double)lo.x), lane, clo, chi);
         } else if (lo.z < k) {
             // some child still has N == 0 -> score +inf, first such child wins; its record is
             // written by the backup of this simulation, here only the slot is reserved

@@ -694,6 +694,7 @@ class MCTSEngine(object):
             if isinstance(score_mode, str) else int(score_mode)
         self.add_noise = bool(add_noise)
         self.sims_in_flight = max(1, int(sims_in_flight))
+        self.forced_k = 0.0   # set_forced_playouts
         self.n_leaves = self.n_games * self.sims_in_flight  # rows of obs / logp / value
         cfg = _hip.RzConfig(abi_version=_hip.ABI_VERSION,
                             game_kind=_hip.GAME_CONNECT4 if game == 'connect4' else _hip.GAME_GOMOKU,
@@ -1336,6 +1337,48 @@ class MCTSEngine(object):
         check(self.lib.rz_root_values(self.handle, _ptr(self._root_values), self.stream()), 'rz_root_values')
         return self._root_values
 
+    def set_forced_playouts(self, k):
+        """Forced playouts at the root of every search that follows (rz_set_forced_playouts; rz_forced.h states the rule): ``k`` > 0
+        turns them on -- a root child with n > 0 and n n < (k p) N is selected whatever its score -- and 0 turns them off (the
+        default).  ValueError, never a fallback, on an engine whose rule is not 'puct', with sims_in_flight > 1, or for a k that is
+        negative or not finite; HipError (the library's argument error) once the device move step holds k (attach again)."""
+        k = float(k)
+        if not (np.isfinite(k) and k >= 0.0):
+            raise ValueError('forced playouts: k = %r is not a finite number >= 0' % (k,))
+        if self.score_mode != _hip.SCORE_PUCT:
+            raise ValueError("forced playouts are a rule of score_mode 'puct' (this engine selects by 'uct_ref')")
+        if self.sims_in_flight != 1:
+            raise ValueError('forced playouts need one simulation in flight per tree (sims_in_flight = %d)' % self.sims_in_flight)
+        check(self.lib.rz_set_forced_playouts(self.handle, k), 'rz_set_forced_playouts')
+        if k != self.forced_k:   # (k travels in the kernel arguments: a captured launch would keep the old one)
+            self._drop_graphs('forced playouts changed (set_forced_playouts): call warm_graph again')
+        self.forced_k = k
+
+    def root_pruned_visits(self):
+        """-> int32 [G, A]: the roots' visit counts after policy target pruning (rz_root_pruned_visits; rz_forced.h) -- -1 for an
+        illegal action; with forced playouts off, the raw counts."""
+        if getattr(self, '_pruned', None) is None:
+            self._pruned = self.torch.empty((self.n_games, self.n_actions), dtype=self.torch.int32, device=self.device)
+        self.flush_deferred()
+        check(self.lib.rz_root_pruned_visits(self.handle, _ptr(self._pruned), self.stream()), 'rz_root_pruned_visits')
+        return self._pruned.cpu().numpy()
+
+    def play_set_pruned_visits(self, on=True):
+        """The pruned counts of the move step (rz_play_set_pruned_visits): allocates -- and owns -- the side ring int32 [ring_steps,
+        n_games, A] beside the log (pinned host memory where the log is, else device memory); row r holds what ``root_pruned_visits``
+        gives for the roots the draw of log row r read, -1 for idle slots.  After play_attach, with forced playouts on, and BEFORE the
+        first move step is enqueued or a whole-move graph captured.  -> the tensor (``play_pruned``), or None."""
+        t = self.torch
+        if not on:
+            check(self.lib.rz_play_set_pruned_visits(self.handle, None, self.stream()), 'rz_play_set_pruned_visits')
+            self.play_pruned = None
+            return None
+        ring = t.full((int(self.play_log.shape[0]), self.n_games, self.n_actions), -1, dtype=t.int32)
+        ring = ring.pin_memory() if self.play_log_on_host else ring.to(self.device)
+        check(self.lib.rz_play_set_pruned_visits(self.handle, ring.data_ptr(), self.stream()), 'rz_play_set_pruned_visits')
+        self.play_pruned = ring
+        return ring
+
     def advance(self, moves):
         """update_with_move for every game: move >= 0 keep that subtree, -1 reset, -2 skip."""
         self.flush_deferred()   # (the kept subtree's prior blocks are copied: they must be written)
@@ -1420,6 +1463,7 @@ class MCTSEngine(object):
         self.play_queue_cap = 0       # (and the queue is the linear one: play_queue_ring)
         self.play_temp_on = False     # (and the temperature schedule)
         self.play_values_on, self.play_values = False, None   # (and the ring of root values: play_set_root_values)
+        self.play_pruned = None       # (and the ring of pruned counts: play_set_pruned_visits)
         self._play_on, self._play_active = True, None
         self.active_host[:] = 0
         return self.play_log

@@ -118,6 +118,20 @@ class SlotBook(object):
         self.stalls = {}    # slot -> (game id, ply, move, the 'move' columns of its record): decided here, waiting for the device to take it
         self.started = self.stalls_resolved = self.moves_done = 0
 
+    def set_column(self, name, spec=None):
+        """Add a column ((dtype, shape of one entry, 'move' | 'search')) or, ``spec`` None, drop it -- between runs, with every slot
+        idle: an optional column costs its pages only while its option is on."""
+        if (self.slot_game >= 0).any() or self.stalls:
+            raise HipError('the columns of a book change only while every slot is idle')
+        for cols in (self.move_cols, self.search_cols):
+            if name in cols:
+                cols.remove(name)
+        self.buf.pop(name, None)
+        if spec is not None:
+            dtype, shape, per = spec
+            (self.move_cols if per == 'move' else self.search_cols).append(name)
+            self.buf[name] = np.zeros(self.moves.shape + tuple(shape), dtype=dtype)
+
     def clear(self):
         """Every slot idle, no stall waiting."""
         self.slot_game[:] = -1

@@ -178,7 +178,7 @@ class Trajectory(object):
     """One finished game: what start_self_play returns, in compact form."""
 
     def __init__(self, game_id, board_size, n_in_row, moves, pis, winner, game='gomoku', resigned=False, no_resign=False,
-                 resign_stats=None, fp_margin=np.nan, full=None, root_values=None, epochs=None):
+                 resign_stats=None, fp_margin=np.nan, full=None, root_values=None, epochs=None, raw_visits=None):
         """Resignation (BatchedSelfPlay.set_resign): ``resigned`` -- the game ended with the loser's resignation; ``moves`` / ``pis``
         are the plies actually played (the resigning search's pi is not recorded).  ``no_resign``: a calibration game (played
         out).  ``resign_stats``: float32 max(v_root, q_best) of every search of the game -- one more than the moves of a resigned
@@ -194,6 +194,9 @@ class Trajectory(object):
         if self.epochs is not None and len(self.epochs) != len(moves):
             raise ValueError('game %d: %d epochs for %d plies' % (int(game_id), len(self.epochs), len(moves)))
         self.root_values = None if root_values is None else np.asarray(root_values, dtype=np.float32).reshape(-1)
+        # forced playouts (BatchedSelfPlay.set_forced_playouts): int32 [plies, A], the RAW visit counts of every ply's search -- what
+        # the move was drawn from; ``pis`` is then formed from the pruned counts.  None with the option off.
+        self.raw_visits = None if raw_visits is None else np.asarray(raw_visits, dtype=np.int32).reshape(len(moves), -1)
         self.full = None if full is None else np.asarray(full, dtype=bool).reshape(-1)
         self.resigned, self.no_resign = bool(resigned), bool(no_resign)
         self.resign_stats = None if resign_stats is None else np.asarray(resign_stats, dtype=np.float32)
@@ -478,6 +481,8 @@ class SelfPlayReader(object):
     counters, and the book of the slots (playlog.SlotBook).  numpy only -- BatchedSelfPlay adds the engines; a test builds one alone.
     ``resolve(slot, move)`` hands a stalled slot's move back to the device."""
 
+    forced_k, forced_prune = 0.0, True   # set_forced_playouts (off: what every object starts with)
+
     def __init__(self, n_slots, n_actions, max_plies, n_playout, geometry, resolve, temperature=1.0, seed=0):
         self.n_slots, self.n_playout, self.geometry = n_slots, n_playout, geometry   # geometry: (board_size, n_in_row, game)
         self.temperature = float(temperature)
@@ -490,6 +495,7 @@ class SelfPlayReader(object):
             ep=(np.int32, (), 'search')))       # epoch of every search (a stream; 0 outside one)
         self.epochs = None   # a stream's epochs, oldest first: [Epoch] (BatchedSelfPlay.stream_start); None outside a stream
         self.root_values_on = False   # set_root_values: the side ring of the log is read and Trajectory.root_values formed
+        self.forced_k, self.forced_prune = 0.0, True   # set_forced_playouts: k (0: off), and whether pis come from the pruned counts
         self.slot_game, self.slot_ply = self.book.slot_game, self.book.slot_ply
         self.sims_done = 0
         self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
@@ -554,7 +560,7 @@ class SelfPlayReader(object):
         finally:
             (_, self.temperature_schedule, self.pi_temperature, self.playout_cap, self.resign_threshold, self.resign_disabled_frac) = now
 
-    def read_rows(self, rows, lo=0, values=None, row_epochs=None, no_idle=False):
+    def read_rows(self, rows, lo=0, values=None, row_epochs=None, no_idle=False, pruned=None):
         """Log rows int32 [R, G, words] of the slots ``lo`` .. ``lo + G - 1``, oldest first -> (the trajectories of the games that
         ended in them, the RUNNING records of the last row).  pi is formed here, from the logged visit counts with the reference's
         expression, and every move and flag of the device is verified against this side's draw on the same key.  ``values``: the
@@ -562,7 +568,14 @@ class SelfPlayReader(object):
         ``row_epochs`` (a stream): int [R], the index into ``self.epochs`` of each row -- its moves, budgets and resignation flags are
         verified, and its pis formed, under THAT epoch's settings, not the current ones; the trajectories carry ``epochs``, and a
         game is a calibration game only if it was one in every epoch it spans.  ``no_idle``: HipError for a record without a game
-        (a stream's slots never wait for an id)."""
+        (a stream's slots never wait for an id).  ``pruned``: the same rows of the side ring of pruned counts, int32 [R, G, A]
+        (set_forced_playouts with pruning; required while it is on): the moves are still verified from the log's raw counts, the pis
+        are the same expression on the pruned ones, and the trajectories carry ``raw_visits``."""
+        forced, pruning = self.forced_k > 0.0, self.forced_k > 0.0 and self.forced_prune
+        if pruning and pruned is None:
+            raise ValueError('policy target pruning is on (set_forced_playouts): read_rows needs the rows of the pruned counts\' ring')
+        if forced and row_epochs is not None:
+            raise ValueError('forced playouts are on (set_forced_playouts): a stream does not serve them')
         if self.root_values_on and values is None:
             raise ValueError('root values are on (set_root_values): read_rows needs the side ring\'s rows')
         if no_idle and ((rows[..., 4] & playlog.PLAY_RUNNING) == 0).any():
@@ -593,7 +606,18 @@ class SelfPlayReader(object):
                     self.resign_would += playlog.check_resignation(part, self.resign_threshold, self._calibration(part.game))
         playlog.check_moves(d, chosen)
         q = playlog.running_values(rows, values) if self.root_values_on else np.full(g_i.shape, np.nan, dtype=np.float32)
-        finished = self.book.feed(lo + g_i, d, chosen, dict(pi=pis, stat=d.stat, full=fulls, q=q, ep=rec_ep))
+        columns = dict(pi=pis, stat=d.stat, full=fulls, q=q, ep=rec_ep)
+        if pruning:   # the host stays the arbiter: the same numpy expression, on the ring's pruned rows
+            pruned = np.asarray(pruned)
+            if pruned.shape != rows.shape[:2] + (d.counts.shape[-1], ):
+                raise ValueError('the pruned counts\' rows %r do not match the log\'s %r' % (pruned.shape, rows.shape[:2]))
+            pr = pruned[np.nonzero((rows[..., 4] & playlog.PLAY_RUNNING) != 0)]
+            if ((pr >= 0) != d.legal).any() or (pr > d.visits).any() or (np.where(d.legal, pr, 0).sum(axis=-1) <= 0)[d.counts.sum(axis=-1) > 0].any():
+                raise HipError('the ring of pruned counts disagrees with the log: another legal set, a count above the raw one or an empty row')
+            columns['pi'] = self._pis_moves(np.where(d.legal, pr, 0), d.legal, d.ply, move_uniform(self.seed, d.game, d.ply))[0]
+        if forced:
+            columns['raw'] = d.counts.astype(np.int32)
+        finished = self.book.feed(lo + g_i, d, chosen, columns)
         done = []
         for f in finished:
             eps = f.columns['ep']
@@ -611,6 +635,8 @@ class SelfPlayReader(object):
                 extra['root_values'] = f.columns['q'][:len(f.moves)]
             if row_epochs is not None:
                 extra['epochs'] = eps[:len(f.moves)]
+            if forced:
+                extra['raw_visits'] = f.columns['raw']
             done.append(Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
                                    game=self.geometry[2], **extra))
         return done, last_running
@@ -681,6 +707,56 @@ class BatchedSelfPlay(SelfPlayReader):
         self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
         self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
         self.slot_values = [[] for _ in range(G)]   # root value of every search that played a ply of the slot's game (set_root_values)
+        self.slot_raw = [[] for _ in range(G)]   # raw visit counts of every ply of the slot's game (set_forced_playouts)
+
+    def set_forced_playouts(self, k=2.0, prune=True):
+        """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2; an opt-in extension of score_mode 'puct') for every
+        lane and BOTH loops (run, run_device).  ``k`` > 0: in every search a root child the search has touched is selected whatever
+        its score while n n < (k p) N (MCTSEngine.set_forced_playouts; rz_forced.h).  The move is still drawn, and verified, from the
+        RAW counts; ``prune`` True: Trajectory.pis is the same numpy expression on the PRUNED counts (MCTSEngine.root_pruned_visits;
+        in run_device a side ring of the log, rz_play_set_pruned_visits, written in front of the draw and part of the whole-move
+        graph), False: on the raw counts.  Trajectory.raw_visits keeps the raw counts either way.  ``k`` 0 / None: off.  Between
+        runs; an attached object attaches again, and the simulation graphs are captured again: k travels in the kernel arguments.
+        ValueError, never a fallback: a lane that selects by 'uct_ref' or has sims_in_flight > 1, a playout cap, an evaluator that
+        puts no priors into the tree (RolloutEvaluator), an open stream, a lane in match mode."""
+        k = 0.0 if k is None else float(k)
+        if not (np.isfinite(k) and k >= 0.0):
+            raise ValueError('forced playouts: k = %r is not a finite number >= 0' % (k, ))
+        self._no_stream('set_forced_playouts')   # (continuous self-play under PUCT is not served)
+        if k > 0.0:
+            from . import _hip
+            from .engine import RolloutEvaluator
+            if self.playout_cap is not None:
+                raise ValueError('forced playouts: a playout cap is set (set_playout_cap): the cap is a rule of the uct_ref search')
+            for lane in self.lanes:
+                if lane.eng.score_mode != _hip.SCORE_PUCT:
+                    raise ValueError("forced playouts are a rule of score_mode 'puct' (a lane's engine selects by 'uct_ref')")
+                if lane.eng.sims_in_flight != 1:
+                    raise ValueError('forced playouts need one simulation in flight per tree (sims_in_flight = %d)' % lane.eng.sims_in_flight)
+                if isinstance(lane.evaluator, RolloutEvaluator):
+                    raise ValueError('forced playouts read the priors in the tree: this evaluator hands over none (uniform priors)')
+                if getattr(lane.eng, 'play_match_on', False):
+                    raise ValueError('a lane\'s engine is in match mode (play_set_match): its games are not training data')
+        if (k, bool(prune)) == (self.forced_k, self.forced_prune):
+            return
+        was_dev = self._dev_on
+        if was_dev:
+            self.device_stop()
+        self.abandon_running()
+        rewarm = any(lane.eng._graphs for lane in self.lanes)
+        for lane in self.lanes:
+            if lane.eng.forced_k != k:
+                with self._on(lane):
+                    if getattr(lane.eng, '_play_on', False):   # (the move step holds the old k: a fresh attach lets go of it)
+                        lane.eng.play_attach(self.seed, self.temperature, self._queue_ids, self._queue_ctl, ring_steps=2)
+                    lane.eng.set_forced_playouts(k)
+                lane.move_graph = None
+        self.forced_k, self.forced_prune = k, bool(prune)
+        self.book.set_column('raw', (np.int32, (self.eng.n_actions, ), 'move') if k > 0.0 else None)
+        if rewarm:
+            self.warm_graphs()
+        if was_dev:
+            self.device_attach(queue_capacity=self._queue_ids.numel(), **self._attach_kw)
 
     def set_root_values(self, on=True):
         """Keep the root value of every search that plays a ply (an opt-in extension: the learner's value target can mix it with z,
@@ -715,6 +791,8 @@ class BatchedSelfPlay(SelfPlayReader):
                     lane.eng.set_playouts(None)
         else:
             n_fast, p_full = int(n_fast), float(p_full if p_full is not None else 'nan')
+            if self.forced_k > 0.0:
+                raise ValueError('forced playouts are on (set_forced_playouts): the playout cap is a rule of the uct_ref search')
             if not 1 <= n_fast <= self.eng.n_playout:
                 raise ValueError('n_fast %d not in 1 .. n_playout = %d' % (n_fast, self.eng.n_playout))
             if not 0.0 < p_full <= 1.0:
@@ -803,7 +881,8 @@ class BatchedSelfPlay(SelfPlayReader):
                     game='gomoku', net_shape=None, lanes=None, trunk_workgroups=None, temperature=1.0, seed=0,
                     use_graph=True, sims_per_graph=16, eager_every=0, add_noise=True, sims_in_flight=1, before_warm=None,
                     deferred_priors=None, resident_search=None, net_algo=None, delta_trunk=None, resign=None, playout_cap=None,
-                    temperature_schedule=None, pi_temperature=None, root_values=False, resident_puct=False, **engine_kw):
+                    temperature_schedule=None, pi_temperature=None, root_values=False, resident_puct=False, forced_playouts=None,
+                    **engine_kw):
         """Self-play of ``n_games`` games in flight with the hand-written evaluator of ``net_module`` (a
         PolicyValueNet): builds the lanes (engine + HipNetEvaluator each) as plan_lanes() recommends, unless
         ``lanes`` / ``trunk_workgroups`` are given (more than four lanes take turns on the GPU's four compute pipes, and four need
@@ -826,7 +905,8 @@ class BatchedSelfPlay(SelfPlayReader):
         ``resident_puct`` (opt-in, with ``score_mode='puct'``): every lane searches with the one-launch resident search under PUCT
         (HipNetEvaluator.resident_puct: boards of up to 10 rows and columns, one simulation in flight, at most one game per CU and
         lane) -- run, run_device and the whole-move hipGraphs then play the games of the three-launch step, bit for bit.  ValueError
-        where it cannot be served (plan_route names the reason); nothing falls back to another route."""
+        where it cannot be served (plan_route names the reason); nothing falls back to another route.
+        ``forced_playouts``: None (off) or k, or (k, prune): set_forced_playouts."""
         import torch
         from .engine import HipNetEvaluator, MCTSEngine
         dev = torch.device(device)
@@ -906,6 +986,13 @@ class BatchedSelfPlay(SelfPlayReader):
             sp.set_temperature_schedule(temperature_schedule, pi_temperature=pi_temperature)
         if root_values:
             sp.set_root_values(True)
+        if forced_playouts is not None:
+            try:
+                sp.set_forced_playouts(*(forced_playouts if isinstance(forced_playouts, (tuple, list)) else (forced_playouts, )))
+            except ValueError:
+                for lane in sp.lanes:
+                    lane.eng.close()
+                raise
         if before_warm is not None:
             before_warm(sp)
         sp.warm_graphs()
@@ -950,6 +1037,7 @@ class BatchedSelfPlay(SelfPlayReader):
             self.slot_stats[s] = []
             self.slot_full[s] = []
             self.slot_values[s] = []
+            self.slot_raw[s] = []
         # a game's Dirichlet noise (read by the PUCT rule only), like its move draws, is keyed by (seed, game id): the trajectory
         # does not depend on the slot, lane or GPU the game is played on
         with np.errstate(over='ignore'):
@@ -1086,7 +1174,14 @@ class BatchedSelfPlay(SelfPlayReader):
             else:
                 legal = ~taken
             pis, chosen = self._pis_moves(visits[running - lo], legal, self.slot_ply[running], us)
-            cells = heights[np.arange(len(running)), chosen] * eng.cols + chosen if eng.game == 'connect4' else chosen
+            if self.forced_k > 0.0:   # the move from the raw counts, as ever; the stored pi from the pruned ones
+                for i, s_ in enumerate(running):
+                    self.slot_raw[s_].append(visits[s_ - lo].astype(np.int32))
+                if self.forced_prune:
+                    with self._on(lane):
+                        pr = lane.eng.root_pruned_visits()[running - lo]
+                    pis = self._pis_moves(np.where(legal, pr, 0), legal, self.slot_ply[running], us)[0]
+            cells =heights[np.arange(len(running)), chosen] * eng.cols + chosen if eng.game == 'connect4' else chosen
             moves[running - lo] = chosen
             self.cell_taken[running, cells] = True
             self.slot_ply[running] += 1
@@ -1107,6 +1202,8 @@ class BatchedSelfPlay(SelfPlayReader):
                     extra['full'] = self.slot_full[s]
                 if self.root_values_on:
                     extra['root_values'] = self.slot_values[s]
+                if self.forced_k > 0.0:
+                    extra['raw_visits'] = np.asarray(self.slot_raw[s], dtype=np.int32).reshape(len(self.slot_moves[s]), -1)
                 done.append(Trajectory(self.slot_game[s], eng.board_size, eng.n_in_row,
                                        self.slot_moves[s], self.slot_pis[s], win, game=eng.game, **extra))
                 self.slot_game[s] = -1
@@ -1283,6 +1380,8 @@ class BatchedSelfPlay(SelfPlayReader):
                 self._apply_option(self._temperature_option(), attaching=lane)
                 if self.root_values_on:   # (an argument of the draw: before the first move step is enqueued or captured)
                     lane.eng.play_set_root_values(True)
+                if self.forced_k > 0.0 and self.forced_prune:   # (a launch in front of the draw: likewise)
+                    lane.eng.play_set_pruned_visits(True)
                 lane.move_graph = lane.eng.warm_move_graph(lane.evaluator) if move_graphs else None
             # (the engine's log ring is pinned host memory that its kernels write directly: nothing to copy -- or, RZ_PLAY_DEVICE_LOG=1,
             # a device ring whose rows _read_back copies)
@@ -1293,6 +1392,11 @@ class BatchedSelfPlay(SelfPlayReader):
                 ring = lane.eng.play_values
                 lane.host_values = ring if lane.eng.play_log_on_host else t.empty(tuple(ring.shape), dtype=t.float32, pin_memory=True)
                 lane.values_np = lane.host_values.numpy()
+            lane.pruned_np = None   # (set_forced_playouts: the rows of the pruned counts' ring, where the log's are)
+            if self.forced_k > 0.0 and self.forced_prune:
+                ring = lane.eng.play_pruned
+                lane.host_pruned = ring if lane.eng.play_log_on_host else t.empty(tuple(ring.shape), dtype=t.int32, pin_memory=True)
+                lane.pruned_np = lane.host_pruned.numpy()
             lane.uncopied = []          # rows written by enqueued moves, their read-back not enqueued yet
             lane.inflight = []          # [(rows, event)] read-backs enqueued, oldest first
             lane.last_running = -1      # RUNNING records in the last row read (-1: none read yet)
@@ -1340,6 +1444,8 @@ class BatchedSelfPlay(SelfPlayReader):
                     lane.host_log[rows[at]:rows[end - 1] + 1].copy_(lane.eng.play_log[rows[at]:rows[end - 1] + 1], non_blocking=True)
                     if lane.values_np is not None:
                         lane.host_values[rows[at]:rows[end - 1] + 1].copy_(lane.eng.play_values[rows[at]:rows[end - 1] + 1], non_blocking=True)
+                    if lane.pruned_np is not None:
+                        lane.host_pruned[rows[at]:rows[end - 1] + 1].copy_(lane.eng.play_pruned[rows[at]:rows[end - 1] + 1], non_blocking=True)
                 at = end
             ev = self.torch.cuda.Event()
             ev.record(lane.stream)
@@ -1385,7 +1491,8 @@ class BatchedSelfPlay(SelfPlayReader):
             return []
         # (host_np[rows] is a copy: the pinned rows may be overwritten from now on)
         done, lane.last_running = self.read_rows(lane.host_np[rows], lane.slots.start,
-                                                 values=None if lane.values_np is None else lane.values_np[rows])
+                                                 values=None if lane.values_np is None else lane.values_np[rows],
+                                                 **({} if lane.pruned_np is None else dict(pruned=lane.pruned_np[rows])))
         return done
 
     def _resolve(self, slot, move):
@@ -1494,6 +1601,8 @@ class BatchedSelfPlay(SelfPlayReader):
         first_game_id = int(first_game_id)
         if first_game_id < 0:
             raise ValueError('first_game_id %d is negative' % first_game_id)
+        if self.forced_k > 0.0:
+            raise ValueError('forced playouts are on (set_forced_playouts): continuous self-play under PUCT is not served')
         for lane in self.lanes:
             if getattr(lane.eng, 'play_match_on', False):
                 raise ValueError('a lane\'s engine is in match mode (play_set_match): a match is no stream of self-play games')

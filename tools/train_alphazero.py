@@ -170,7 +170,7 @@ class TrainPipeline:
                  resign_fp_target=0.05, playout_cap=None, gate_against=None, batch_size=32, updates_per_round=1,
                  device_replay=False, temperature_schedule=None, pi_temperature=None, reanalyse=None, reanalyse_slots=512,
                  reanalyse_playouts=None, game='gomoku', board_width=None, value_mix=0.0, reanalyse_targets='pi',
-                 continuous_selfplay=False):
+                 continuous_selfplay=False, score_mode='uct_ref', resident_puct=False, forced_playouts=None):
         """``buffer_size``: length of the replay deque.  None = the reference's 1000 (train_alphazero.py:32) in the
         reference flow; in the batched mode (``selfplay_games_in_flight > 0``) None sizes it to hold ONE collection
         round (games in flight x board cells x 8 symmetries) -- a documented deviation: with the reference's 1000 a
@@ -214,7 +214,16 @@ class TrainPipeline:
         round is ``stream_collect(n)`` behind ``refresh_weights()``: it ends when n more games have finished, and the games still
         running go on under the next round's weights (Trajectory.epochs tells which plies) instead of idling their slots' neighbours.
         The replay buffer receives the games in FINISHING order, not in game-id order.  The last round of ``run`` stops the stream and
-        prints the games it drops.  ValueError with several ranks, with RZ_TRAIN_HOST_MOVES=1 and in the reference flow."""
+        prints the games it drops.  ValueError with several ranks, with RZ_TRAIN_HOST_MOVES=1 and in the reference flow.
+        ``score_mode`` (batched mode; governs SELF-PLAY only -- evaluation games and the gate match keep their engines): 'uct_ref'
+        (default, the reference's rule) or 'puct', the rule that reads the policy head; ``resident_puct``: its one-launch resident
+        search (BatchedSelfPlay.for_network(resident_puct=True): boards of up to 10 rows); ``forced_playouts``: None or k > 0 --
+        forced playouts and policy target pruning (BatchedSelfPlay.set_forced_playouts: the stored pis come from the pruned counts).
+        ValueError: 'puct' with a playout cap, Reanalyse or continuous self-play (all three are uct_ref's today), resident_puct or
+        forced_playouts without 'puct'.  Several ranks are served: the payload they gather carries the pis as they are."""
+        check_puct_options(score_mode, resident_puct, forced_playouts, selfplay_games_in_flight, playout_cap, reanalyse, continuous_selfplay)
+        self.score_mode, self.resident_puct = score_mode, bool(resident_puct)
+        self.forced_playouts = None if forced_playouts is None else float(forced_playouts)
         if game not in ('gomoku', 'connect4'):
             raise ValueError('game %r: gomoku or connect4' % (game, ))
         self.game_kind = game
@@ -446,7 +455,7 @@ class TrainPipeline:
                 n_games=self.selfplay_games_in_flight, n_playout=self.n_playout, c_puct=self.c_puct,
                 device=str(self.device), temperature=self.temperature, seed=self.selfplay_seed, playout_cap=self.playout_cap,
                 temperature_schedule=self.temperature_schedule, pi_temperature=self.pi_temperature,
-                root_values=self.value_mix > 0.0, **self._game_kw())
+                root_values=self.value_mix > 0.0, **self._puct_kw(), **self._game_kw())
         return self._batched
 
     def _set_resign(self):
@@ -479,6 +488,12 @@ class TrainPipeline:
         if self._final_round:
             print('continuous self-play: stream stopped, {} running games dropped'.format(sp.stream_stop()), flush=True)
         return []
+
+    def _puct_kw(self):
+        """The selection rule of self-play (for_network's keywords; nothing under the default rule)."""
+        if self.score_mode != 'puct':
+            return {}
+        return dict(score_mode='puct', resident_puct=self.resident_puct, forced_playouts=self.forced_playouts)
 
     def _game_kw(self):
         """What BatchedSelfPlay.for_network / BatchedEvaluation.for_network take beyond Gomoku's defaults."""
@@ -556,8 +571,19 @@ class TrainPipeline:
         local = self._play_games(list(ids), on_finished=take)
         self._resign_round(local)
         self._cap_round(local)
+        self._forced_round(local)
         rest = [t for t in sorted(local, key=lambda t: t.game_id) if t.game_id >= cursor[0] or consume is None]
         return [ready[t.game_id] if t.game_id in ready else self._tuple(t) for t in rest]
+
+    def _forced_round(self, trajs):
+        """After a collection round under forced playouts (one rank: the gathered payload carries no raw counts): what policy target
+        pruning took out of the round's targets."""
+        if self.forced_playouts is None or not trajs or any(t.raw_visits is None for t in trajs):
+            return
+        raw = np.concatenate([t.raw_visits for t in trajs], axis=0)
+        pis = np.concatenate([np.asarray(t.pis) for t in trajs], axis=0)
+        print('forced playouts: k {:g}, {} plies, {} of {} visited root children without weight in the pruned target'.format(
+            self.forced_playouts, len(raw), int(((raw > 0) & (pis < 1e-9)).sum()), int((raw > 0).sum())), flush=True)
 
     RESIGN_ROUNDS = 4   # 'auto': rounds of calibration games the threshold is set from
 
@@ -802,6 +828,28 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+def check_puct_options(score_mode, resident_puct, forced_playouts, games_in_flight, playout_cap, reanalyse, continuous_selfplay):
+    """ValueError for a combination of the self-play rule's options that no route serves (TrainPipeline, main)."""
+    if score_mode not in ('uct_ref', 'puct'):
+        raise ValueError('score_mode %r: uct_ref or puct' % (score_mode, ))
+    if score_mode != 'puct':
+        if resident_puct:
+            raise ValueError('--resident-puct is a route of --score-mode puct')
+        if forced_playouts is not None:
+            raise ValueError('--forced-playouts is a rule of --score-mode puct')
+        return
+    if games_in_flight <= 0:
+        raise ValueError('--score-mode puct is a batched self-play option: --games-in-flight must be > 0')
+    if playout_cap is not None:
+        raise ValueError('--score-mode puct with --playout-cap: the playout cap is served by the uct_ref search only')
+    if reanalyse:
+        raise ValueError('--score-mode puct with --reanalyse: Reanalyse searches by uct_ref only')
+    if continuous_selfplay:
+        raise ValueError('--score-mode puct with --continuous-selfplay: continuous self-play is served by the uct_ref search only')
+    if forced_playouts is not None and not (np.isfinite(forced_playouts) and forced_playouts > 0.0):
+        raise ValueError('--forced-playouts K: a finite K > 0, not %r' % (forced_playouts, ))
+
+
 def playout_cap_arg(text):
     """--playout-cap N_FAST:P_FULL -> (n_fast, p_full)."""
     import argparse
@@ -882,6 +930,11 @@ def reanalyse_targets_of(args):
     return getattr(args, 'reanalyse_targets', 'pi')
 
 
+def puct_options_of(args):
+    """-> (--score-mode, --resident-puct, --forced-playouts) of parsed arguments ('uct_ref', False, None where they were not given)."""
+    return getattr(args, 'score_mode', 'uct_ref'), getattr(args, 'resident_puct', False), getattr(args, 'forced_playouts', None)
+
+
 def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description='AlphaZero training for Gomoku (or, --game connect4, Connect4) on MI355X (no arguments: the reference script\'s run)')
@@ -930,6 +983,13 @@ def parse_args(argv=None):
     ap.add_argument('--continuous-selfplay', action='store_true', default=argparse.SUPPRESS,   # (absent without the flag, like --value-mix)
                     help='batched mode on one GPU (an opt-in extension, not the reference loop): self-play is one stream that the rounds do '
                          'not stop -- a round ends when --games-in-flight more games have finished, the others run on under the next weights')
+    # (the three options below stay out of the namespace unless given, like --value-mix: puct_options_of reads them)
+    ap.add_argument('--score-mode', choices=('uct_ref', 'puct'), default=argparse.SUPPRESS,
+                    help="batched mode: the selection rule of SELF-PLAY (evaluation games and --gate-against keep theirs); 'puct' reads the "
+                         'policy head (with --playout-cap, --reanalyse or --continuous-selfplay: an error); default uct_ref')
+    ap.add_argument('--resident-puct', action='store_true', default=argparse.SUPPRESS, help='with --score-mode puct: the one-launch resident search (boards of up to 10 rows)')
+    ap.add_argument('--forced-playouts', type=float, default=argparse.SUPPRESS, metavar='K',
+                    help='with --score-mode puct: forced playouts at the root (KataGo: K = 2) and policy target pruning of the stored pis')
     args = ap.parse_args(argv)
     value_mix, targets = value_mix_of(args), reanalyse_targets_of(args)
     if not 0.0 <= value_mix <= 1.0:
@@ -988,6 +1048,9 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
+    score_mode, resident_puct, forced_playouts = puct_options_of(args)
+    check_puct_options(score_mode, resident_puct, forced_playouts, args.games_in_flight, args.playout_cap, args.reanalyse,
+                       getattr(args, 'continuous_selfplay', False))
     if value_mix_of(args) > 0.0 and (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
         raise ValueError('--value-mix runs on one rank: the payload the ranks gather carries no root values (--gpus %d, WORLD_SIZE %s)'
                          % (args.gpus, os.environ.get('WORLD_SIZE', '1')))
@@ -1013,7 +1076,8 @@ def main(argv=None):
                          temperature_schedule=args.temperature_schedule, pi_temperature=args.pi_temperature,
                          reanalyse=args.reanalyse or None, reanalyse_slots=args.reanalyse_slots, reanalyse_playouts=args.reanalyse_playouts,
                          game=args.game, board_width=args.board_width, value_mix=value_mix_of(args), reanalyse_targets=reanalyse_targets_of(args),
-                         continuous_selfplay=getattr(args, 'continuous_selfplay', False))
+                         continuous_selfplay=getattr(args, 'continuous_selfplay', False), score_mode=score_mode,
+                         resident_puct=resident_puct, forced_playouts=forced_playouts)
     pipe.run()
     if pipe.world > 1:
         import torch.distributed as dist
