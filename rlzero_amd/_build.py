@@ -7,7 +7,9 @@ twice like CPython does.
 The library carries the hash of what it was built from (sources, headers, flags): ``rz_source_hash()`` and the marker string
 ``RZ_SOURCE_HASH=<hex>`` in its bytes.  ``needs_build()`` compares that hash with the tree's -- not file times -- so a stale
 binary is rebuilt wherever it came from, and ``_hip.load()`` refuses a library whose hash differs from the sources beside it.
-Every source is compiled to an object of its own (in parallel; an object is reused while its own hash holds), then linked.
+Every source is compiled to an object of its own (in parallel), then linked.  An object is reused while its own hash holds: that of
+its source, of the headers the source includes (``headers_of``: directly or through another header) and of the flags -- an edit to a
+kernel header of one translation unit recompiles that unit alone.
 """
 import glob
 import hashlib
@@ -35,6 +37,23 @@ def _digest(paths, extra=''):
         with open(p, 'rb') as f:
             h.update(f.read())
     return h.hexdigest()[:32]
+
+
+def headers_of(src):
+    """The project's headers `src` includes, directly or through another header: every ``#include "..."`` line, found in include/ or
+    beside the sources and followed in turn.  The text alone is scanned -- an include under an #if counts whether or not it is
+    taken --, so the set can be too large, never too small."""
+    found, todo = [], [src]
+    while todo:
+        with open(todo.pop()) as f:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read(), re.M)
+        for name in names:
+            for where in (os.path.join(REPO, 'include'), os.path.join(PKG, 'csrc')):
+                path = os.path.normpath(os.path.join(where, name))
+                if os.path.isfile(path) and path not in found:
+                    found.append(path)
+                    todo.append(path)
+    return sorted(found)
 
 
 def source_hash():
@@ -76,7 +95,7 @@ def _build_locked(force, verbose):
     jobs, objs = [], []
     for src in SOURCES:
         # (rz_engine.hip holds rz_source_hash(): its object depends on the hash of the whole tree)
-        own = _digest([src] + HEADERS, ' '.join(FLAGS) + (want if src.endswith('rz_engine.hip') else ''))
+        own = _digest([src] + headers_of(src), ' '.join(FLAGS) + (want if src.endswith('rz_engine.hip') else ''))
         obj = os.path.join(OBJ_DIR, os.path.basename(src) + '.' + own + '.o')
         objs.append(obj)
         if force or not os.path.exists(obj):

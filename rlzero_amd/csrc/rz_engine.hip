@@ -37,6 +37,19 @@
 // -ffp-contract=off (q + c*u is two roundings in CPython), IEEE division and sqrt, and
 // ln(parent N) comes from a table filled by the HOST libm -- the function CPython's
 // math.log calls -- never from a device logarithm.
+//
+// This file is the host side of ONE translation unit: the kernels lie in headers beside it, one per family, each of which compiles
+// alone (tests/test_csrc_headers.py) and describes its kernels where they are defined; the device code they all call is rz_tree.h.
+//   rz_engine_step.h      the step-by-step tree kernels: k_select, k_expand_backup, k_expand_backup_raw, k_tree_step_raw, k_tree_step,
+//                         and k_tree_step_vl, the sequential restatement of the in-flight kernel
+//   rz_engine_deferred.h  deferred priors: k_expand_backup_def, k_tree_step_def, the flush (deferred_priors_body, k_deferred_priors)
+//                         and the kept flush (Keep, k_keep_mark, k_keep_rows, k_deferred_priors_rows), k_deferred_reset
+//   rz_engine_ml.h        k_tree_step_ml: K simulations in flight, level-synchronous (MlSlot, ml_lds_bytes)
+//   rz_engine_eval.h      the synthetic and rollout evaluators: k_eval_synth, k_eval_rollout
+//   rz_engine_roots.h     the root readers (k_root_children, k_root_stats, k_root_values), tree reuse (advance_body, k_advance), the
+//                         game step (step_body, k_step_games) and the setters and getters of per-game state
+//   rz_engine_play.h      the whole device move step: Play, k_play_draw, k_root_pruned, k_play_apply and the kernels of its options
+// Below: g_err and rz_set_error, struct rz_engine, the launch helpers and every extern "C" entry point of the engine.
 
 #include <hip/hip_runtime.h>
 
@@ -55,1611 +68,17 @@
 
 #include "rz_tree.h"
 
+// (this order is the order of the kernels in the code object; the template instantiations follow in the order the code below names them)
+#include "rz_engine_step.h"
+#include "rz_engine_deferred.h"
+#include "rz_engine_ml.h"
+#include "rz_engine_eval.h"
+#include "rz_engine_roots.h"
+#include "rz_engine_play.h"
+
 using namespace rzt;
 
 namespace {
-
-__global__ __launch_bounds__(kWave) void k_select(Dev E, float *obs) {
-    __builtin_amdgcn_s_setprio(3);  // latency-bound: issue ahead of a co-resident MFMA kernel
-    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
-}
-
-template <typename VT, bool PROBS = false>
-__global__ __launch_bounds__(kWave) void k_expand_backup(Dev E, const float *logp, const VT *value) {
-    __builtin_amdgcn_s_setprio(3);
-    expand_backup_body<VT, PROBS>(E, logp, value, blockIdx.x, threadIdx.x);
-}
-
-__global__ __launch_bounds__(kWave) void k_expand_backup_raw(Dev E, RawHeads rh) {
-    __builtin_amdgcn_s_setprio(3);
-    expand_backup_body<float, false, true>(E, nullptr, nullptr, blockIdx.x, threadIdx.x, rh);
-}
-
-__global__ __launch_bounds__(kWave) void k_tree_step_raw(Dev E, RawHeads rh, float *obs) {
-    __builtin_amdgcn_s_setprio(3);
-    expand_backup_body<float, false, true>(E, nullptr, nullptr, blockIdx.x, threadIdx.x, rh);
-    __syncthreads();
-    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
-}
-
-// ------------------------------------------------------------------ deferred priors (value_quarter_def: rz_tree.h)
-// A value head of 4 * 8 * PER inputs covers a board of at most 16 * PER cells (deferred_ok): PER says how many words of the
-// bitboards the tree code has to look at (rz_tree.h: W)
-template <int PER> constexpr int words_of_per() { return PER <= 4 ? 1 : (PER == 8 ? 2 : kWords); }
-template <int PER>
-__global__ __launch_bounds__(kWave * kDefWaves) void k_expand_backup_def(Dev E, ValueHead vh) {
-    __shared__ float part[kDefWaves][kWave];
-    __builtin_amdgcn_s_setprio(3);
-    const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    value_quarter_def<PER>(vh, blockIdx.x, lane, wave, part);
-    if (wave != 0) {
-        __syncthreads();
-        return;
-    }
-    expand_backup_body<float, false, false, false, true, words_of_per<PER>()>(E, nullptr, nullptr, blockIdx.x, lane, RawHeads(), 0, vh, part);
-}
-
-// (`obs` is always NULL on this route -- the trunk reads positions -- but stays a run-time argument: with the constant hipcc
-// schedules the selection into 115 registers instead of 107, and 112 is what a SIMD has left beside a wave of the trunk)
-// TRACE: the instantiation launched while a trace buffer is attached (rz_trace_attach) leaves a record per game; the production
-// one carries nothing of it (the trace's live values cost the latency chain 132 bytes of scratch).
-template <int PER, bool TRACE>
-__global__ __launch_bounds__(kWave * kDefWaves) void k_tree_step_def(Dev E, ValueHead vh, float *obs) {
-    __shared__ float part[kDefWaves][kWave];
-    __builtin_amdgcn_s_setprio(3);
-    const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    __shared__ unsigned long long trace_t0;
-    if (TRACE && threadIdx.x == 0) trace_t0 = rz_trace_now();
-    value_quarter_def<PER>(vh, blockIdx.x, lane, wave, part);
-    if (wave != 0) {
-        __syncthreads();
-        return;
-    }
-    expand_backup_body<float, false, false, false, true, words_of_per<PER>()>(E, nullptr, nullptr, blockIdx.x, lane, RawHeads(), 0, vh, part);
-    __syncthreads();   // (wave 0's alone: the other waves have ended)
-    select_body<false, words_of_per<PER>()>(E, obs, blockIdx.x, lane);
-    if (TRACE && lane == 0) rz_trace_write(E.trace, RZ_TRACE_TREE, E.pend[blockIdx.x] - 1, blockIdx.x, trace_t0);
-}
-
-// The flush: the priors of the node expanded in step `slot` of game g -- exp(log_softmax) of the leaf's logits over its legal
-// moves, mixed with the Dirichlet noise of counter pend_ctr: expand_backup_body<RAW>'s operations on the same numbers (the
-// logits are final: k_heads_split's epilogue), into the block that step reserved.  grid = (games, slots).
-// record `rec` = slot * n_games + g, its logits at `r`: the body of both grids below
-__device__ __forceinline__ void deferred_priors_body(const Dev &E, int g, long long rec, const float *__restrict__ r, int lane) {
-    const int pb = E.pend_pb[rec];
-    if (pb < 0) return;
-    const int ctr = E.pend_ctr[rec];
-    uint64_t st[2][kWords];
-    load_board(E.pend_stones, (int)rec, st);
-    float x[kWords];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < kWords; ++i) {
-        const int j = lane + 64 * i;
-        x[i] = j < E.A ? r[j] : -INFINITY;
-        mx = fmaxf(mx, x[i]);
-    }
-    mx = wave_max(mx, lane);
-    float sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < kWords; ++i) sum += (lane + 64 * i < E.A) ? expf(x[i] - mx) : 0.0f;
-    sum = wave_sum(sum, lane);
-    const float lse = mx + logf(sum);
-    float *P = arena_priors(E, g, E.cur_arena[g]);
-    uint64_t occ[kWords];
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    int ranks[kWords];
-    int before = 0;
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) ranks[j] = lane_action_rank(E, occ, L, j, lane, before);
-    float noise[kWords] = {0.f, 0.f, 0.f, 0.f};
-    float noise_sum = 1.0f;
-    if (E.add_noise) {
-        const uint64_t key = mix64(mix64(E.noise_key[g]) ^ (uint64_t)ctr);
-        float local = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kWords; ++j)
-            if (ranks[j] >= 0) {
-                noise[j] = gamma03(hash32((uint32_t)key ^ (uint32_t)(key >> 32)) + 0x9E3779B9u * (uint32_t)(64 * j + lane + 1));
-                local += noise[j];
-            }
-        local = wave_sum(local, lane);
-        noise_sum = local > 0.0f ? local : 1.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int rk = ranks[j];
-        if (rk < 0) continue;
-        float prior = expf(x[j] - lse);
-        if (E.add_noise) prior = 0.75f * prior + 0.25f * (noise[j] / noise_sum);
-        P[pb + rk] = prior;
-    }
-}
-
-__global__ __launch_bounds__(kWave) void k_deferred_priors(Dev E, const float *__restrict__ raw, int ld, long long rows_per_slot) {
-    const int g = blockIdx.x, slot = blockIdx.y, lane = threadIdx.x;
-    if (slot >= E.pend[g]) return;
-    deferred_priors_body(E, g, (long long)slot * E.n_games + g, raw + ((size_t)slot * rows_per_slot + g) * ld, lane);
-}
-
-// ------------------------------------------------------------------ the kept flush (between k_play_draw and k_play_apply)
-// The move is known (Play::keep), and a prior block matters only if it survives update_with_move: advance_body copies the blocks
-// of the kept child's subtree and reads one float of the root's own block.  The priors of every other expansion of the search lie
-// in the arena the move abandons: they are never formed.  A record is NEEDED when
-//   * its leaf board is the root board (the root's own block, expanded in this search: the chosen child's prior is read from it), or
-//   * the leaf board has the mover's stone on the cell the move occupies: every leaf below the kept child has, and so has a leaf
-//     that reaches the same stones in another order -- a row too many, never one too few --, or
-//   * no move was drawn (keep == -2: a stalled slot keeps its whole tree and its counter restarts in k_play_apply; a resignation),
-//     or the move is not legal (advance_body flags it).
-// k_keep_mark: one workgroup per game, a wave per 64 slots: the needed records as bit masks, their number and the number of
-// records with a block (what the full flush writes).
-struct Keep {
-    unsigned long long *mask;   // [G][words]: bit s % 64 of word s / 64 = record (s, g) is needed
-    int32_t *cnt, *pcnt;        // [G] needed records / records with a block
-    int32_t *rows;              // [slots * G] the needed records, game-major, slots ascending
-    int32_t *count;             // [1] their number
-    unsigned long long *stats;  // [2] needed / with a block, summed since the last reset (rz_deferred_keep_stats)
-    int words;
-};
-
-// (keep_of == NULL: every record with a block of every game -- the full flush of policy on demand, rz_deferred_keep_all)
-__global__ __launch_bounds__(256) void k_keep_mark(Dev E, const int32_t *__restrict__ keep_of, Keep Kp) {
-    __shared__ int sh[4][2];
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = E.pend[g] < E.pend_cap ? E.pend[g] : E.pend_cap;
-    const int keep = keep_of != nullptr ? keep_of[g] : -2;
-    uint64_t root[2][kWords], occ[kWords];
-    load_board(E.root_stones, g, root);
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = root[0][j] | root[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    int rank = 0, cell = 0;
-    const bool all = keep < 0 || !locate_action(E, occ, L, keep, rank, cell);
-    const bool second = E.root_to_move[g] != 0;   // the mover's colour
-    int kept = 0, with_block = 0;
-    for (int s0 = 64 * wave; s0 < n; s0 += 256) {
-        const int s = s0 + lane;
-        const long long rec = (long long)s * E.n_games + g;
-        const bool has = s < n && E.pend_pb[rec] >= 0;
-        bool need = has && all;
-        if (has && !all) {
-            uint64_t st[2][kWords];
-            load_board(E.pend_stones, (int)rec, st);
-            bool same = true;
-            uint64_t mine[kWords];
-#pragma unroll
-            for (int j = 0; j < kWords; ++j) {
-                same = same && st[0][j] == root[0][j] && st[1][j] == root[1][j];
-                mine[j] = second ? st[1][j] : st[0][j];
-            }
-            need = same || test_bit(mine, cell);
-        }
-        const unsigned long long m = __ballot(need);
-        if (lane == 0) Kp.mask[(long long)g * Kp.words + (s0 >> 6)] = m;
-        kept += __popcll(m);
-        with_block += __popcll(__ballot(has));
-    }
-    if (lane == 0) sh[wave][0] = kept, sh[wave][1] = with_block;
-    __syncthreads();
-    if (tid == 0) {
-        Kp.cnt[g] = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
-        Kp.pcnt[g] = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
-    }
-}
-
-// k_keep_rows: one wave per game: where the game's rows begin (the prefix of cnt over the games before it), then its needed
-// records in slot order (ballot masks of k_keep_mark + mbcnt: k_play_order's compaction).  The last game's wave leaves the total.
-__global__ __launch_bounds__(kWave) void k_keep_rows(Dev E, Keep Kp) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const bool last = g == E.n_games - 1;
-    int base = 0, pending = 0;
-    for (int h = lane; h < g; h += kWave) base += Kp.cnt[h];
-    if (last)
-        for (int h = lane; h < E.n_games; h += kWave) pending += Kp.pcnt[h];
-    for (int off = 32; off >= 1; off >>= 1) {
-        base += __shfl_xor(base, off);
-        pending += __shfl_xor(pending, off);
-    }
-    const int n = E.pend[g] < E.pend_cap ? E.pend[g] : E.pend_cap;
-    int at = base;
-    for (int s0 = 0; s0 < n; s0 += kWave) {
-        const unsigned long long m = Kp.mask[(long long)g * Kp.words + (s0 >> 6)];
-        const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if ((m >> lane) & 1ull) Kp.rows[at + pre] = (s0 + lane) * E.n_games + g;
-        at += __popcll(m);
-    }
-    if (last && lane == 0) {
-        Kp.count[0] = at;
-        if (Kp.stats != nullptr) {   // (NULL: a full flush by rows -- the counters are the kept flushes')
-            Kp.stats[0] += (unsigned long long)at;
-            Kp.stats[1] += (unsigned long long)pending;
-        }
-    }
-}
-
-// k_deferred_priors over the listed records: a fixed grid of waves (the count is the device's), logits of row i in row i
-__global__ __launch_bounds__(kWave) void k_deferred_priors_rows(Dev E, const float *__restrict__ raw, int ld, const int32_t *__restrict__ rows,
-                                                                const int32_t *__restrict__ count) {
-    const int lane = threadIdx.x, n = count[0];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int rec = rows[i];
-        deferred_priors_body(E, rec % E.n_games, rec, raw + (size_t)i * ld, lane);
-    }
-}
-
-__global__ void k_deferred_reset(Dev E) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < E.n_games) E.pend[g] = 0;
-}
-
-// EXPAND + BACKUP of simulation s and SELECT + STEP of simulation s+1 in one launch (same
-// wave, same game): saves a kernel boundary per simulation.  The barrier makes the tree
-// updates of the first half visible to the loads of the second.
-template <typename VT>
-__global__ __launch_bounds__(kWave) void k_tree_step(Dev E, const float *logp, const VT *value, float *obs) {
-    __builtin_amdgcn_s_setprio(3);
-    expand_backup_body<VT>(E, logp, value, blockIdx.x, threadIdx.x);
-    __syncthreads();
-    select_body<false, kWords, NoHook, true>(E, obs, blockIdx.x, threadIdx.x);
-}
-
-// K simulations in flight (opt-in): the game's wave backs up the kb pending slots of the previous step one after
-// the other, then selects ks new ones; the barrier between two slots orders the tree updates of one before the loads
-// of the next (same wave: s_waitcnt + s_barrier).  kb = 0 / ks = 0 give the select-only / backup-only launches.
-template <bool RAW>
-__global__ __launch_bounds__(kWave) void k_tree_step_vl(Dev E, const float *logp, const float *value, RawHeads rh,
-                                                        float *obs, int kb, int ks) {
-    __builtin_amdgcn_s_setprio(3);
-#pragma unroll 1
-    for (int j = 0; j < kb; ++j) {
-        expand_backup_body<float, false, RAW, true>(E, logp, value, blockIdx.x, threadIdx.x, rh, j);
-        __syncthreads();
-    }
-#pragma unroll 1
-    for (int j = 0; j < ks; ++j) {
-        select_body<true>(E, obs, blockIdx.x, threadIdx.x, j);
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------ K simulations in flight, level-synchronous
-// The production kernel of the opt-in virtual-loss mode (k_tree_step_vl above is its sequential restatement: one
-// wave, one slot after the other, kept selectable for the tests that compare the two tree for tree).  A game is a
-// workgroup of K waves.  Every step of the sequential rule "slot j sees the virtual losses of slots 0 .. j-1" that does
-// not depend on an earlier slot is done for all slots at once:
-//   * BACKUP of the kb pending leaves: wave j finishes the heads of leaf j (log_softmax, tanh), draws its noise and
-//     writes its prior block at an offset taken from a prefix sum over the slots (bump allocator in slot order); then
-//     wave 0 trades every virtual loss for the value: W(node) += x + 1 for all (slot, level) pairs with fire-and-forget
-//     f64 atomics issued in slot order (same wave, same address: applied in program order), N untouched.
-//   * SELECT of ks new leaves, level by level: at level L the slots sit in at most K distinct nodes; wave j stages the
-//     child records of slot j's node in LDS (all nodes of a level in ONE memory round trip instead of one per slot and
-//     level), then the slots of a node are walked IN SLOT ORDER by one wave (the groups of different nodes side by side): scores from LDS, first maximum, virtual loss into the staged
-//     record at once (the next slot at the same node sees it), the slot's own view of the chosen child -- N, W as they
-//     were BEFORE its own virtual loss, i.e. with those of the earlier slots only -- goes along to the next level.
-//     This is the sequential rule exactly: what slot j sees at a node are the losses of the slots before it, and
-//     those were all placed at the same level earlier in the same pass.  A moved child block is written back from the
-//     staged copy, so nothing has to be patched.
-//   * the tails (terminal test, duplicate-leaf test, leaf arrays, observation planes) again one wave per slot.
-struct MlSlot {
-    uint64_t st[2][kWords];  // board of the slot's path so far
-    int4 lo, hi;             // the slot's VIEW of its current node: record with the virtual losses of earlier slots only
-    int4 xlo;                // owner slot only: the node's structure fields (y FC, z NV, w K | cap) as they evolve in a pass
-    int node, rank, owner, depth, fresh, active, to_move, last, nst, moved, pad0, pad1;
-};
-
-__host__ __device__ inline int ml_prior_bytes(int K, int A, bool puct) { return puct ? ((K * A * 4 + 15) / 16) * 16 : 0; }
-__host__ __device__ inline int ml_lds_bytes(int K, int A, bool puct) {
-    return K * (int)sizeof(MlSlot) + K * A * 32 + ml_prior_bytes(K, A, puct) + 64 + K * 16;
-}
-
-template <bool RAW>
-__global__ void k_tree_step_ml(Dev E, const float *logp, const float *value, RawHeads rh, float *obs, int kb, int ks) {
-    extern __shared__ __attribute__((aligned(16))) char ml_lds[];
-    const int g = blockIdx.x, K = E.K, A = E.A, S = E.S;
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool puct_mode = E.score_mode == RZ_SCORE_PUCT;
-    MlSlot *SL = reinterpret_cast<MlSlot *>(ml_lds);
-    int4 *stage = reinterpret_cast<int4 *>(ml_lds + K * sizeof(MlSlot));          // [K][A][2]
-    float *stage_p = reinterpret_cast<float *>(stage + (size_t)K * A * 2);          // [K][A] (PUCT)
-    int *misc = reinterpret_cast<int *>(reinterpret_cast<char *>(stage_p) + ml_prior_bytes(K, A, puct_mode));  // [0] any slot active
-    double *bval = reinterpret_cast<double *>(misc + 16);                            // [K] leaf values
-    int *bdepth = reinterpret_cast<int *>(bval + K);                                 // [K]
-    int *bexp = bdepth + K;                                                          // [K] children of an expanded leaf, else 0
-    if (!E.active[g]) return;  // the whole workgroup: before any barrier
-    const int arena = E.cur_arena[g];
-    int4 *R = arena_records(E, g, arena);
-    float *P = arena_priors(E, g, arena);
-
-    // ------------------------------------------------------------- BACKUP of the pending leaves
-    if (kb > 0) {
-        const int j = w, gk = g * K + j;
-        const bool mine = j < kb;
-        const int ptop0 = E.ptop[g], nblk0 = E.nblk[g], ctr0 = E.noise_ctr[g], top0 = E.top[g];  // before anyone moves them
-        int depth = 0, fresh = 0, term = 0, leaf = 0, k = 0;
-        double v = 0.0;
-        float lse = 0.0f;
-        float x[kWords] = {0.f, 0.f, 0.f, 0.f};
-        uint64_t st[2][kWords] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, occ[kWords] = {0, 0, 0, 0};
-        Legal L;
-        L.k = 0; L.cols = 0ull; L.height = 0;
-        bool expand = false;
-        if (mine) {
-            depth = E.leaf_depth[gk];
-            fresh = E.leaf_fresh[gk];
-            term = E.leaf_term[gk];
-            leaf = E.leaf_node[gk];
-            const double tval = E.leaf_tval[gk];
-            load_board(E.leaf_stones, gk, st);
-            float val = 0.0f;
-            if (RAW) {  // the heads of leaf j, as in expand_backup_body
-                const float *r = rh.raw + (size_t)gk * rh.ld;
-                const float *hp = rh.hid + (size_t)gk * 64 + lane;
-                const float w2 = rh.w2[lane], b2 = rh.b2[0];
-                float hid = hp[0], mx = -INFINITY;
-                if (rh.n_parts == 4) {
-                    const long long rs = rh.raw_part_stride, hs = rh.hid_part_stride;
-                    const float act_scale = rh.act_scale[0], val_scale = rh.val_scale[0];
-#pragma unroll
-                    for (int i = 0; i < kWords; ++i) {
-                        const int a = lane + 64 * i;
-                        const bool in = a < A;
-                        const float q0 = in ? r[a] : 0.f, q1 = in ? r[a + rs] : 0.f, q2 = in ? r[a + 2 * rs] : 0.f,
-                                    q3 = in ? r[a + 3 * rs] : 0.f, bias = in ? rh.act_bias[a] : 0.f;
-                        x[i] = in ? fmaf(((q0 + q1) + q2) + q3, act_scale, bias) : -INFINITY;
-                        mx = fmaxf(mx, x[i]);
-                    }
-                    hid = fmaxf(fmaf(((hid + hp[hs]) + hp[2 * hs]) + hp[3 * hs], val_scale, rh.val_bias[lane]), 0.0f);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < kWords; ++i) {
-                        const int a = lane + 64 * i;
-                        x[i] = a < A ? r[a] : -INFINITY;
-                        mx = fmaxf(mx, x[i]);
-                    }
-                }
-                mx = wave_max(mx, lane);
-                float sum = 0.0f;
-#pragma unroll
-                for (int i = 0; i < kWords; ++i) sum += (lane + 64 * i < A) ? expf(x[i] - mx) : 0.0f;
-                sum = wave_sum(sum, lane);
-                lse = mx + logf(sum);
-                float h = hid * w2;
-                h = wave_sum(h, lane);
-                val = tanhf(h + b2);
-            } else {
-                val = value[gk];
-            }
-            v = term ? tval : (double)val;
-            expand = !term && fresh != 2 && fresh != 3;
-#pragma unroll
-            for (int i = 0; i < kWords; ++i) occ[i] = st[0][i] | st[1][i];
-            L = legal_of(E, occ, lane);
-            k = L.k;
-        }
-        if (lane == 0 && j < K) {
-            bexp[j] = (mine && expand) ? k : 0;
-            bval[j] = v;
-            bdepth[j] = mine ? depth : -1;
-        }
-        __syncthreads();
-        // bump allocation in slot order: offsets = prefix sums over the slots before j
-        int before_k = 0, before_n = 0, total_k = 0, total_n = 0;
-        for (int i = 0; i < kb; ++i) {
-            const int ki = bexp[i];
-            if (i < j) { before_k += ki; before_n += ki > 0 ? 1 : 0; }
-            total_k += ki;
-            total_n += ki > 0 ? 1 : 0;
-        }
-        if (w == 0 && lane == 0) {
-            if ((long long)ptop0 + total_k > E.pcap || nblk0 + total_n > E.qcap) {
-                atomicOr(&E.err[g], RZ_FLAG_BLOCKS_FULL);
-                atomicOr(E.err_any, RZ_FLAG_BLOCKS_FULL);
-            } else if (puct_mode && (long long)top0 + total_k > E.cap) {
-                atomicOr(&E.err[g], RZ_FLAG_ARENA_FULL);
-                atomicOr(E.err_any, RZ_FLAG_ARENA_FULL);
-            } else {
-                E.ptop[g] = ptop0 + total_k;
-                E.nblk[g] = nblk0 + total_n;
-                if (E.add_noise) E.noise_ctr[g] = ctr0 + total_n;
-                if (puct_mode) E.top[g] = top0 + total_k;
-            }
-        }
-        const bool fits = (long long)ptop0 + total_k <= E.pcap && nblk0 + total_n <= E.qcap &&
-                          (!puct_mode || (long long)top0 + total_k <= E.cap);
-        if (mine && expand && fits) {
-            const int pb = ptop0 + before_k, ctop = top0 + before_k;
-            const float uniform = 1.0f / (float)k;
-            int ranks[kWords];
-            int before = 0;
-#pragma unroll
-            for (int i = 0; i < kWords; ++i) ranks[i] = lane_action_rank(E, occ, L, i, lane, before);
-            float noise[kWords] = {0.f, 0.f, 0.f, 0.f};
-            float noise_sum = 1.0f;
-            if (E.add_noise) {
-                const uint64_t key = mix64(mix64(E.noise_key[g]) ^ (uint64_t)(ctr0 + before_n));
-                float local = 0.0f;
-#pragma unroll
-                for (int i = 0; i < kWords; ++i)
-                    if (ranks[i] >= 0) {
-                        noise[i] = gamma03(hash32((uint32_t)key ^ (uint32_t)(key >> 32)) + 0x9E3779B9u * (uint32_t)(64 * i + lane + 1));
-                        local += noise[i];
-                    }
-                local = wave_sum(local, lane);
-                noise_sum = local > 0.0f ? local : 1.0f;
-            }
-#pragma unroll
-            for (int i = 0; i < kWords; ++i) {
-                const int r = ranks[i];
-                if (r < 0) continue;
-                const int a = 64 * i + lane;
-                float prior = uniform;
-                if (RAW) prior = expf(x[i] - lse);
-                else if (logp) prior = expf(logp[(long long)gk * A + a]);
-                if (E.add_noise) prior = 0.75f * prior + 0.25f * (noise[i] / noise_sum);
-                P[pb + r] = prior;
-                if (puct_mode) {
-                    R[2 * (ctop + r)] = make_int4(0, -1, 0, 0);
-                    R[2 * (ctop + r) + 1] = make_hi(0.0, -1, prior);
-                }
-            }
-            if (lane == 0) {  // the leaf's record: its blocks (N and W stay: counted at selection / traded below)
-                int32_t *f = reinterpret_cast<int32_t *>(R + 2 * leaf);
-                f[1] = puct_mode ? ctop : -1;
-                f[2] = puct_mode ? k : 0;
-                f[3] = pack_kc(k, puct_mode ? k : 0);
-                *rec_pb(R, leaf) = pb;
-            }
-        }
-        __syncthreads();
-        if (w == 0) {
-            // W(node) += x + 1 for every (slot, level) pair, slot after slot: fire-and-forget atomics of ONE wave.  The
-            // path entries of all slots are fetched first (one round trip), then the atomics go out in slot order.
-            int pnode[RZ_MAX_IN_FLIGHT];
-#pragma unroll
-            for (int i = 0; i < RZ_MAX_IN_FLIGHT; ++i) {
-                pnode[i] = 0;
-                if (i < kb) {
-                    const int di = bdepth[i];
-                    if (lane <= di) pnode[i] = E.path[(long long)(g * K + i) * E.path_stride + lane];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < RZ_MAX_IN_FLIGHT; ++i) {
-                if (i < kb) {
-                    const int di = bdepth[i];
-                    const double vi = bval[i];
-                    if (lane <= di) unsafeAtomicAdd(rec_wsum(R, pnode[i]), (((di - lane) & 1) ? vi : -vi) + 1.0);
-                    if (di >= kWave) {  // (paths longer than a wave: the rest, level by level)
-                        const int32_t *path = E.path + (long long)(g * K + i) * E.path_stride;
-                        for (int d = lane + kWave; d <= di; d += kWave)
-                            unsafeAtomicAdd(rec_wsum(R, path[d]), (((di - d) & 1) ? vi : -vi) + 1.0);
-                    }
-                }
-            }
-        }
-        // the selection below must read what the stores and atomics above wrote
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    if (ks <= 0) return;
-
-    // ------------------------------------------------------------- SELECT, level by level
-    int top = E.top[g];
-    const int top_at_start = top;
-    {
-        const int4 lo0 = R[0], hi0 = R[1];
-        uint64_t st0[2][kWords];
-        load_board(E.root_stones, g, st0);
-        const int to_move0 = E.root_to_move[g], last0 = E.root_last[g];
-        const int j = w;
-        if (j < ks) {
-            double wv = rec_w(hi0);
-            for (int i = 0; i < j; ++i) wv = wv - 1.0;  // the root as slot j sees it: the slots before it have passed
-            if (lane < 2 * kWords) SL[j].st[lane / kWords][lane % kWords] = word_of(st0[lane / kWords], lane % kWords);
-            if (lane == 0) {
-                SL[j].lo = make_int4(lo0.x + j, lo0.y, lo0.z, lo0.w);
-                SL[j].hi = make_hi(wv, hi0.z, __int_as_float(hi0.w));
-                SL[j].xlo = lo0;
-                SL[j].node = 0;
-                SL[j].rank = -1;
-                SL[j].owner = 0;
-                SL[j].depth = 0;
-                SL[j].fresh = 0;
-                SL[j].active = 1;
-                SL[j].to_move = to_move0;
-                SL[j].last = last0;
-                SL[j].nst = count_bits(st0[0]) + count_bits(st0[1]);
-                SL[j].moved = 0;
-                SL[j].pad0 = -1;
-                E.path[(long long)(g * K + j) * E.path_stride] = 0;
-            }
-        }
-        if (w == 0 && lane == 0) {
-            misc[0] = 1;
-            double wv = rec_w(hi0);
-            for (int i = 0; i < ks; ++i) wv = wv - 1.0;
-            *rec_n(R, 0) = lo0.x + ks;  // the root carries the virtual loss of every slot
-            *rec_wsum(R, 0) = wv;
-        }
-    }
-    for (int pass = 0; pass <= S + 1; ++pass) {
-        __syncthreads();
-        if (misc[0] == 0) break;
-        // phase A: wave j stages the child records of its slot's node (once per distinct node: the owner does it)
-        if (w < ks) {
-            const int j = w;
-            if (SL[j].active && SL[j].owner == j) {
-                const int4 xlo = SL[j].xlo;
-                const int k = rec_k(xlo), fc = xlo.y, n_load = puct_mode ? k : xlo.z, pb = SL[j].hi.z;
-                int4 *dst = stage + (size_t)j * A * 2;
-                for (int i = lane; i < n_load; i += kWave) {
-                    dst[2 * i] = R[2 * (fc + i)];
-                    dst[2 * i + 1] = R[2 * (fc + i) + 1];
-                    if (puct_mode) stage_p[(size_t)j * A + i] = P[pb + i];
-                }
-            }
-        }
-        __syncthreads();
-        // phase B: the owner's wave walks the slots of ITS node in slot order (slots at different nodes do not see each
-        // other within a level: the groups run side by side; at the root all slots are one group)
-        int cap0 = -1;   // the capacity of the node's child block before this pass grew it (phase C needs it when the arena is full)
-        if (w < ks && SL[w].active && SL[w].owner == w)
-        for (int j = w; j < ks; ++j) {
-            if (!SL[j].active || SL[j].owner != w) continue;
-            const int o = w;
-            const int4 xlo = SL[o].xlo;
-            const int4 vlo = SL[j].lo;
-            const int k = rec_k(xlo);
-            if (k == 0) {  // the path ends in an existing leaf (its virtual loss came with the choice of it)
-                if (lane == 0) SL[j].active = 0;
-                continue;
-            }
-            int fc = xlo.y, cap = rec_cap(xlo);
-            const int nv = xlo.z;
-            int4 *stg = stage + (size_t)o * A * 2;
-            int r;
-            int4 clo, chi;
-            bool fresh = false;
-            if (!puct_mode && nv < k) {
-                if (nv == cap) {  // the child vector grows: its new block is allocated in phase C (in owner order, whatever the
-                                  // groups' timing) and written from the staged copy
-                    if (cap0 < 0) cap0 = cap;
-                    cap = cap == 0 ? (k < kFirstCap ? k : kFirstCap) : (2 * cap < k ? 2 * cap : k);
-                    if (lane == 0) {
-                        SL[o].moved = 1;
-                        SL[o].pad1 = cap0;
-                    }
-                }
-                r = nv;
-                fresh = true;
-                clo = make_int4(1, -1, 0, 0);          // the pending child: visited once, lost
-                chi = make_hi(-1.0, -1, 0.0f);
-                if (lane == 0) {
-                    stg[2 * r] = clo;
-                    stg[2 * r + 1] = chi;
-                    SL[o].xlo = make_int4(xlo.x, fc, nv + 1, pack_kc(k, cap));
-                }
-            } else {
-                const int pn = vlo.x;
-                if (!puct_mode && (pn < 1 || pn >= E.logtab_n)) {
-                    flag(E, g, RZ_FLAG_LOGTAB, lane);
-                    if (lane == 0) { SL[j].fresh = 2; SL[j].active = 0; }
-                    continue;
-                }
-                const double parent_term = puct_mode ? sqrt((double)pn) : E.logtab[pn];
-                double best = -INFINITY;
-                int besti = 0x7fffffff;
-#pragma unroll
-                for (int i = 0; i < kWords; ++i) {
-                    const int r0 = lane + 64 * i;
-                    if (r0 < k) {
-                        const int4 cl = stg[2 * r0], ch = stg[2 * r0 + 1];
-                        const double sc = puct_mode ? puct(rec_w(ch), cl.x, stage_p[(size_t)o * A + r0], parent_term, E.c_puct)
-                                                    : uct_ref(rec_w(ch), cl.x, parent_term, E.c_puct);
-                        if (sc > best) {
-                            best = sc;
-                            besti = r0;
-                        }
-                    }
-                }
-                r = __builtin_amdgcn_readfirstlane(wave_first_max(best, besti));
-                if (r >= k) {
-                    flag(E, g, RZ_FLAG_INTERNAL, lane);
-                    if (lane == 0) { SL[j].fresh = 2; SL[j].active = 0; }
-                    continue;
-                }
-                clo = stg[2 * r];   // the child as THIS slot sees it: before its own virtual loss
-                chi = stg[2 * r + 1];
-                if (lane == 0) {
-                    stg[2 * r] = make_int4(clo.x + 1, clo.y, clo.z, clo.w);
-                    stg[2 * r + 1] = make_hi(rec_w(chi) - 1.0, chi.z, __int_as_float(chi.w));
-                }
-            }
-            // (the move on the slot's board -- which cell child r is -- depends on no other slot: phase B2 below, every
-            // slot's own wave, instead of inside this slot-after-slot loop)
-            if (lane == 0) {
-                SL[j].depth += 1;
-                SL[j].rank = r;
-                SL[j].pad0 = r;   // for phase B2
-                SL[j].lo = clo;
-                SL[j].hi = chi;
-                if (fresh) {
-                    SL[j].fresh = 1;
-                    SL[j].active = 0;
-                }
-            }
-        }
-        __syncthreads();
-        // phase B2: wave j plays the chosen child on slot j's board (all slots side by side; wave 0 goes on to phase C,
-        // which reads none of what is written here)
-        if (w < ks && SL[w].pad0 >= 0) {
-            const int j = w, r = SL[j].pad0;
-            uint64_t st[2][kWords], occ[kWords];
-#pragma unroll
-            for (int i = 0; i < kWords; ++i) {
-                st[0][i] = SL[j].st[0][i];
-                st[1][i] = SL[j].st[1][i];
-                occ[i] = st[0][i] | st[1][i];
-            }
-            const Legal L = legal_of(E, occ, lane);
-            int action, cell;
-            const bool ok = nth_legal(E, occ, L, r, lane, action, cell);
-            if (!ok) flag(E, g, RZ_FLAG_INTERNAL, lane);
-            if (lane == 0) {
-                SL[j].pad0 = -1;
-                if (ok) {
-                    const int tm = SL[j].to_move;
-                    SL[j].st[tm][cell >> 6] |= 1ull << (cell & 63);
-                    SL[j].to_move = tm ^ 1;
-                    SL[j].last = cell;
-                    SL[j].nst += 1;
-                }
-            }
-        }
-        if (w != 0) continue;
-        // phase C (wave 0): new blocks for the child vectors that grew, write back what the pass changed, resolve the slots'
-        // new nodes, owners of the next pass
-        for (int o = 0; o < ks; ++o) {
-            if (SL[o].owner != o || !SL[o].moved) continue;
-            const int4 xlo = SL[o].xlo;
-            const int need = rec_cap(xlo);
-            if ((long long)top + need > E.cap) {
-                // no room for the grown block: the node keeps its old one (full: cap0 visited children, the staged records of the
-                // slots that chose a child inside it are written one by one below), and the slots that chose a child past it end
-                // at the node itself with fresh = 2, as select_body does -- nothing is written at an offset the old block does not
-                // own (with no block yet its first-child offset is -1)
-                flag(E, g, RZ_FLAG_ARENA_FULL, lane);
-                const int cap0 = SL[o].pad1;
-                if (lane == 0) {
-                    for (int j = o; j < ks; ++j)
-                        if (SL[j].owner == o && SL[j].rank >= cap0) {
-                            SL[j].rank = -1;
-                            SL[j].fresh = 2;
-                            SL[j].depth -= 1;
-                        }
-                    SL[o].xlo = make_int4(xlo.x, xlo.y, cap0, pack_kc(rec_k(xlo), cap0));
-                    SL[o].moved = 0;
-                }
-                continue;
-            }
-            if (lane == 0) SL[o].xlo = make_int4(xlo.x, top, xlo.z, xlo.w);
-            top += need;
-        }
-        for (int o = 0; o < ks; ++o) {
-            if (SL[o].owner != o || SL[o].rank < -1) continue;
-            const int4 xlo = SL[o].xlo;
-            const int X = SL[o].node;
-            bool touched = false;
-            for (int j = o; j < ks; ++j) touched = touched || (SL[j].owner == o && SL[j].rank >= 0);
-            if (!touched) continue;
-            if (lane == 0) {  // the structure fields of the node (its N / W were written when it was chosen)
-                int32_t *f = reinterpret_cast<int32_t *>(R + 2 * X);
-                f[1] = xlo.y;
-                f[2] = xlo.z;
-                f[3] = xlo.w;
-            }
-            const int4 *stg = stage + (size_t)o * A * 2;
-            if (SL[o].moved) {
-                for (int i = lane; i < xlo.z; i += kWave) {
-                    R[2 * (xlo.y + i)] = stg[2 * i];
-                    R[2 * (xlo.y + i) + 1] = stg[2 * i + 1];
-                }
-            }
-        }
-        int any = 0;
-        if (lane < ks) {
-            const int j = lane;
-            const int rk = SL[j].rank;
-            if (rk >= 0) {
-                const int o = SL[j].owner;
-                const int4 xlo = SL[o].xlo;
-                const int node = xlo.y + rk;
-                if (!SL[o].moved) {  // (a moved block was written whole, above)
-                    const int4 *stg = stage + (size_t)o * A * 2;
-                    R[2 * node] = stg[2 * rk];
-                    R[2 * node + 1] = stg[2 * rk + 1];
-                }
-                E.path[(long long)(g * K + j) * E.path_stride + SL[j].depth] = node;
-                SL[j].node = node;
-            }
-        }
-        // (every lane < ks has read its owner's record before any of them is overwritten)
-        __builtin_amdgcn_wave_barrier();
-        int node_l = 0, act_l = 0;
-        if (lane < ks) {
-            const int j = lane;
-            if (SL[j].rank >= 0) {
-                SL[j].xlo = SL[j].lo;
-                SL[j].rank = -1;
-            }
-            SL[j].moved = 0;
-            node_l = SL[j].node;
-            act_l = SL[j].active;
-        }
-        int owner_l = lane;
-        for (int i = ks - 1; i >= 0; --i) {
-            const int ni = __shfl(node_l, i), ai = __shfl(act_l, i);
-            if (ai && ni == node_l && i <= lane) owner_l = i;
-        }
-        if (lane < ks) SL[lane].owner = owner_l;
-        any = __ballot(lane < ks && act_l) != 0ull ? 1 : 0;
-        if (lane == 0) misc[0] = any;
-    }
-    __syncthreads();
-    if (w == 0 && lane == 0 && top != top_at_start) E.top[g] = top;
-
-    // ------------------------------------------------------------- tails: one wave per slot
-    if (w < ks) {
-        const int j = w, gk = g * K + j;
-        uint64_t st[2][kWords];
-#pragma unroll
-        for (int i = 0; i < kWords; ++i) {
-            st[0][i] = SL[j].st[0][i];
-            st[1][i] = SL[j].st[1][i];
-        }
-        const int to_move = SL[j].to_move, last = SL[j].last, nst = SL[j].nst, depth = SL[j].depth, node = SL[j].node;
-        int fresh = SL[j].fresh;
-        int term = 0;
-        double tval = 0.0;
-        int winner = -1;
-        if (depth == 0) {
-            if (line_anywhere(st[0], S, E.BH, E.BW, E.n_row, lane, E.bw_rcp)) winner = 0;
-            else if (line_anywhere(st[1], S, E.BH, E.BW, E.n_row, lane, E.bw_rcp)) winner = 1;
-        } else {
-            const int mover = to_move ^ 1;
-            if (line_through(mover == 0 ? st[0] : st[1], last, E.BH, E.BW, E.n_row, lane, E.bw_rcp, E.n_rcp)) winner = mover;
-        }
-        if (winner >= 0) {
-            term = 2;
-            tval = (winner == to_move) ? 1.0 : -1.0;
-        } else if (nst == S) {
-            term = 1;
-        }
-        if (fresh == 0 && term == 0)  // an unexpanded leaf an earlier slot of this step ends in too: that one expands it
-            for (int i = 0; i < j; ++i)
-                if (SL[i].node == node) fresh = 3;
-        if (lane == 0) {
-            E.leaf_node[gk] = node;
-            E.leaf_depth[gk] = depth;
-            E.leaf_fresh[gk] = fresh;
-            E.leaf_term[gk] = term;
-            E.leaf_tval[gk] = tval;
-            E.leaf_to_move[gk] = to_move;
-            E.leaf_last[gk] = last;
-        }
-        store_board(E.leaf_stones, gk, st, lane);
-        if (obs != nullptr)
-            write_obs(obs + (long long)gk * 4 * S, to_move == 0 ? st[0] : st[1], to_move == 0 ? st[1] : st[0], last, nst, S,
-                      lane);
-    }
-}
-
-// ------------------------------------------------------------------ synthetic evaluators
-__global__ __launch_bounds__(kWave) void k_eval_synth(Dev E, int kind, float *logp, float *value) {
-    const int g = blockIdx.x;  // leaf index: game * K + slot (K = 1: the game)
-    const int lane = threadIdx.x;
-    if (!E.active[g / E.K]) return;
-    const int S = E.S;
-    uint64_t st[2][kWords];
-    load_board(E.leaf_stones, g, st);
-    int acc = 0;
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int c = 64 * j + lane;
-        if (c < S) {
-            const int a = (int)((st[0][j] >> lane) & 1ull), b = (int)((st[1][j] >> lane) & 1ull);
-            acc += (c + 1) * (a + 3 * b);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) {
-        float v = 0.0f;
-        if (kind == RZ_EVAL_VLIN) {
-            const int s = acc + 5 * E.leaf_to_move[g];
-            v = (float)((s % 17) - 8) / 8.0f;
-        }
-        value[g] = v;
-    }
-    if (logp != nullptr) {
-        uint64_t occ[kWords];
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-        const Legal L = legal_of(E, occ, lane);
-        const float lp = L.k > 0 ? logf(1.0f / (float)L.k) : 0.0f;
-        int before = 0;
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) {
-            const int r = lane_action_rank(E, occ, L, j, lane, before);
-            const int a = 64 * j + lane;
-            if (a < E.A) logp[(long long)g * E.A + a] = r >= 0 ? lp : -INFINITY;
-        }
-    }
-}
-
-// ------------------------------------------------------------------ random rollouts
-// RolloutMCTS._evaluate (rlzero/mcts/rollout_mcts.py:49-74): from the leaf play uniformly random
-// legal moves (the reference takes the arg-max of k fresh uniforms, :99-100 = a uniform choice)
-// until the game ends or n_limit plies, then value = 0 on a tie / limit, else +1 if the winner
-// is the player to move AFTER the rollout else -1 (the reference's perspective quirk, :68-72:
-// the winner has just moved, so a decisive rollout always yields -1).  The move index of ply p
-// is floor(u * k) with u = the high 32 bits of splitmix64(seed, game, sim, ply) -- reproducible
-// on the host (rlzero_amd.mcts.rollout_mcts.rollout_pick) so parity tests can drive the checker
-// with the very same choices.
-__global__ __launch_bounds__(kWave) void k_eval_rollout(Dev E, uint64_t seed, uint32_t sim, int n_limit,
-                                                        float *value) {
-    const int g = blockIdx.x;  // leaf index: game * K + slot (K = 1: the game)
-    const int lane = threadIdx.x;
-    if (!E.active[g / E.K]) return;
-    const int S = E.S;
-    uint64_t st[2][kWords];
-    load_board(E.leaf_stones, g, st);
-    int to_move = E.leaf_to_move[g];
-    int nst = count_bits(st[0]) + count_bits(st[1]);
-    int term = E.leaf_term[g];  // 0 running, 1 tie, 2 won by the player who just moved
-    int winner = term == 2 ? (to_move ^ 1) : -1;
-    const uint64_t key = mix64(mix64(seed ^ (uint64_t)g) ^ (uint64_t)sim);
-    for (int ply = 0; ply < n_limit && term == 0; ++ply) {
-        uint64_t occ[kWords];
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-        const Legal L = legal_of(E, occ, lane);
-        const uint32_t u = (uint32_t)(mix64(key ^ (uint64_t)ply) >> 32);
-        const int r = (int)(((uint64_t)u * (uint64_t)L.k) >> 32);
-        int action, cell;
-        if (!nth_legal(E, occ, L, r, lane, action, cell)) {
-            flag(E, g, RZ_FLAG_INTERNAL, lane);
-            break;
-        }
-        if (to_move == 0) set_bit(st[0], cell); else set_bit(st[1], cell);
-        nst += 1;
-        if (line_through(to_move == 0 ? st[0] : st[1], cell, E.BH, E.BW, E.n_row, lane, E.bw_rcp, E.n_rcp)) {
-            term = 2;
-            winner = to_move;
-        } else if (nst == S) {
-            term = 1;
-        }
-        to_move ^= 1;
-    }
-    if (lane == 0) value[g] = (winner < 0) ? 0.0f : (winner == to_move ? 1.0f : -1.0f);
-}
-
-// ------------------------------------------------------------------ root read-out
-// what: 0 = visits (int32), 1 = W (double), 2 = prior (float); output [n_games][A] by action
-__global__ __launch_bounds__(kWave) void k_root_children(Dev E, int what, void *out) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int arena = E.cur_arena[g];
-    const int4 *R = arena_records(E, g, arena);
-    const float *P = arena_priors(E, g, arena);
-    uint64_t st[2][kWords], occ[kWords];
-    load_board(E.root_stones, g, st);
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    const int4 lo = R[0], hi = R[1];
-    const bool expanded = rec_k(lo) > 0;
-    const int fc = lo.y;
-    const int nv = expanded ? lo.z : 0;
-    int before = 0;
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int r = lane_action_rank(E, occ, L, j, lane, before);
-        const int a = 64 * j + lane;
-        if (a >= E.A) continue;
-        const bool seen = r >= 0 && r < nv;
-        const long long o = (long long)g * E.A + a;
-        if (what == 0) ((int32_t *)out)[o] = seen ? R[2 * (fc + r)].x : 0;
-        else if (what == 1) ((double *)out)[o] = seen ? rec_w(R[2 * (fc + r) + 1]) : 0.0;
-        else ((float *)out)[o] = (r >= 0 && expanded) ? P[hi.z + r] : 0.0f;
-    }
-}
-
-__global__ void k_root_stats(Dev E, int32_t *n, double *w) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    const int4 *R = arena_records(E, g, E.cur_arena[g]);
-    n[g] = R[0].x;
-    w[g] = rec_w(R[1]);
-}
-
-// {v_root, q_best} per game (rz_root_values): -W / N of the root, max W / N over the root's children with N > 0; NaN where undefined
-__global__ __launch_bounds__(kWave) void k_root_values(Dev E, double *out) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int4 *R = arena_records(E, g, E.cur_arena[g]);
-    const int4 lo = R[0];
-    const int fc = lo.y;
-    const int nv = rec_k(lo) > 0 ? lo.z : 0;
-    double qb = -INFINITY;
-    for (int r = lane; r < nv; r += kWave) {   // (visited child records: fc .. fc + nv, in rank order; the maximum needs no order)
-        const int n = R[2 * (fc + r)].x;
-        if (n > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)n);
-    }
-    for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
-    if (lane == 0) {
-        out[2 * (long long)g] = lo.x > 0 ? -(rec_w(R[1]) / (double)lo.x) : NAN;
-        out[2 * (long long)g + 1] = qb > -INFINITY ? qb : NAN;
-    }
-}
-
-// ------------------------------------------------------------------ tree reuse
-__device__ __forceinline__ void fresh_root(const Dev &E, int g, int arena, int lane) {
-    if (lane == 0) {
-        int4 *R = arena_records(E, g, arena);
-        R[0] = make_int4(0, -1, 0, 0);
-        R[1] = make_hi(0.0, -1, 1.0f);  // TreeNode(None, 1.0), alphazero_mcts.py:35,103
-        E.cur_arena[g] = arena;
-        E.top[g] = 1;
-        E.ptop[g] = 0;
-        E.nblk[g] = 0;
-    }
-}
-
-// AlphaZeroMCTS.update_with_move (alphazero_mcts.py:96-103).  The kept subtree is copied
-// breadth-first into the game's other arena (per expanded node: its prior block, and the visited
-// prefix of its child records into a block of the same capacity), which also recycles the slots
-// of the discarded siblings and of every outgrown child block.  A copied record keeps its SOURCE
-// first-child / prior-block offsets until the node itself is taken from the queue, so the queue
-// holds destination slots only.
-__device__ __forceinline__ void advance_body(const Dev &E, int g, int lane, int mv) {
-    if (mv == -2) return;
-    const int src_arena = E.cur_arena[g], dst_arena = src_arena ^ 1;
-    const int4 *Rs = arena_records(E, g, src_arena);
-    int4 *Rd = arena_records(E, g, dst_arena);
-    const float *Ps = arena_priors(E, g, src_arena);
-    float *Pd = arena_priors(E, g, dst_arena);
-    if (mv < 0) {
-        if (mv != -1) flag(E, g, RZ_FLAG_ILLEGAL_MOVE, lane);
-        fresh_root(E, g, dst_arena, lane);
-        return;
-    }
-    uint64_t st[2][kWords], occ[kWords];
-    load_board(E.root_stones, g, st);
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    int rank = 0, cell = 0;
-    if (!locate_action(E, occ, L, mv, rank, cell)) {
-        flag(E, g, RZ_FLAG_ILLEGAL_MOVE, lane);
-        fresh_root(E, g, dst_arena, lane);
-        return;
-    }
-    const int4 rlo = Rs[0], rhi = Rs[1];
-    if (rec_k(rlo) == 0 || rank >= rlo.z) {
-        // the chosen child was never visited: it is a TreeNode with N = 0 and no children
-        fresh_root(E, g, dst_arena, lane);
-        return;
-    }
-    const int src = rlo.y + rank;
-    const int4 slo = Rs[2 * src], shi = Rs[2 * src + 1];
-    const float prior = Ps[rhi.z + rank];
-    int32_t *queue = E.queue + (long long)g * E.qcap;
-    if (lane == 0) {
-        Rd[0] = slo;
-        Rd[1] = make_int4(shi.x, shi.y, shi.z, __float_as_int(prior));
-        queue[0] = 0;
-    }
-    int q_tail = rec_k(slo) > 0 ? 1 : 0;
-    __syncthreads();
-    int dtop = 1, dptop = 0, nblk = 0;
-    bool full = false;
-    for (int q_head = 0; q_head < q_tail; ++q_head) {
-        const int dst = queue[q_head];
-        const int4 lo = Rd[2 * dst], hi = Rd[2 * dst + 1];
-        const int k = rec_k(lo), cap = rec_cap(lo), nv = lo.z, sfc = lo.y, spb = hi.z;
-        // the carried subtree must leave room for the n_playout expansions of the coming search
-        if ((long long)dptop + k > E.pcap - (long long)(E.n_playout + 1) * E.A ||
-            (long long)dtop + cap > E.cap - (long long)(E.n_playout + 1) * 8 - 2 * E.A || nblk >= E.qcap - E.n_playout - 1) {
-            full = true;
-            break;
-        }
-        for (int r = lane; r < k; r += kWave) Pd[dptop + r] = Ps[spb + r];
-        for (int r0 = 0; r0 < nv; r0 += kWave) {
-            const int r = r0 + lane;
-            bool expanded = false;
-            if (r < nv) {
-                const int4 a = Rs[2 * (sfc + r)], b = Rs[2 * (sfc + r) + 1];
-                Rd[2 * (dtop + r)] = a;
-                Rd[2 * (dtop + r) + 1] = b;
-                expanded = rec_k(a) > 0;
-            }
-            const unsigned long long has = __ballot(expanded);
-            if (expanded) {
-                const int pos = q_tail + __popcll(has & ((1ull << lane) - 1ull));
-                if (pos < E.qcap) queue[pos] = dtop + r;
-            }
-            q_tail += __popcll(has);
-        }
-        if (q_tail > E.qcap) {
-            full = true;
-            break;
-        }
-        if (lane == 0) {
-            Rd[2 * dst] = make_int4(lo.x, cap > 0 ? dtop : -1, nv, lo.w);
-            *rec_pb(Rd, dst) = dptop;
-        }
-        dtop += cap;
-        dptop += k;
-        nblk += 1;
-        __syncthreads();  // records and queue entries written by other lanes are read next iteration
-    }
-    if (full) {
-        // The reference's tree is unbounded; here the kept subtree is limited to qcap - n_playout - 1 expanded nodes
-        // (and the prior floats / record slots tested above).  A larger one is DROPPED (the search restarts from a fresh root, like update_with_move(-1)):
-        // a deviation from the reference that is counted (rz_stats.reuse_dropped) and flagged per game with the
-        // non-fatal RZ_FLAG_REUSE_DROPPED, never silent and never fatal for the rest of the batch.
-        if (lane == 0) {
-            atomicOr(&E.err[g], RZ_FLAG_REUSE_DROPPED);
-            atomicOr(E.err_any, RZ_FLAG_REUSE_DROPPED);   // (rz_stats.error_flags is the OR over the games: this bit too)
-            atomicAdd(E.reuse_drops, 1);
-        }
-        fresh_root(E, g, dst_arena, lane);
-        return;
-    }
-    if (lane == 0) {
-        E.cur_arena[g] = dst_arena;
-        E.top[g] = dtop;
-        E.ptop[g] = dptop;
-        E.nblk[g] = nblk;
-    }
-}
-
-__global__ __launch_bounds__(kWave) void k_advance(Dev E, const int32_t *moves) {
-    advance_body(E, blockIdx.x, threadIdx.x, moves[blockIdx.x]);
-}
-
-// ------------------------------------------------------------------ game step
-// -> the winner (player id or -1) and whether the game is over, wave-uniform
-__device__ __forceinline__ void step_body(const Dev &E, int g, int lane, int mv, int &who, bool &over) {
-    const int S = E.S;
-    uint64_t st[2][kWords];
-    load_board(E.root_stones, g, st);
-    int to_move = E.root_to_move[g];
-    if (mv >= 0) {
-        uint64_t occ[kWords];
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-        const Legal L = legal_of(E, occ, lane);
-        int rank = 0, cell = 0;
-        if (!locate_action(E, occ, L, mv, rank, cell)) {
-            flag(E, g, RZ_FLAG_ILLEGAL_MOVE, lane);
-        } else {
-            if (to_move == 0) set_bit(st[0], cell); else set_bit(st[1], cell);
-            to_move ^= 1;
-            if (lane == 0) {
-                E.root_to_move[g] = to_move;
-                E.root_last[g] = cell;
-            }
-            store_board(E.root_stones, g, st, lane);
-        }
-    }
-    who = -1;
-    if (line_anywhere(st[0], S, E.BH, E.BW, E.n_row, lane, E.bw_rcp)) who = 0;
-    else if (line_anywhere(st[1], S, E.BH, E.BW, E.n_row, lane, E.bw_rcp)) who = 1;
-    over = who >= 0 || count_bits(st[0]) + count_bits(st[1]) == S;
-}
-
-__global__ __launch_bounds__(kWave) void k_step_games(Dev E, const int32_t *moves, int32_t *winner,
-                                                      uint8_t *ended) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    int who = -1;
-    bool over = false;
-    step_body(E, g, lane, moves[g], who, over);
-    if (lane == 0) {
-        if (winner) winner[g] = who;
-        if (ended) ended[g] = over ? 1 : 0;
-    }
-}
-
-__global__ void k_set_roots(Dev E, const uint64_t *stones, const int32_t *to_move,
-                            const int32_t *last_move, const uint8_t *mask, int reset_trees) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    if (mask != nullptr && !mask[g]) return;
-    for (int j = 0; j < 2 * kWords; ++j) {
-        const uint64_t v = stones[(long long)g * 2 * kWords + j];
-        E.root_stones[(long long)g * 2 * kWords + j] = v & E.valid[j % kWords];
-    }
-    E.root_to_move[g] = to_move[g] & 1;
-    E.root_last[g] = last_move[g];
-    if (reset_trees) fresh_root(E, g, E.cur_arena[g], 0);
-}
-
-__global__ void k_get_roots(Dev E, uint64_t *stones, int32_t *to_move, int32_t *last_move) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    for (int j = 0; j < 2 * kWords; ++j)
-        stones[(long long)g * 2 * kWords + j] = E.root_stones[(long long)g * 2 * kWords + j];
-    to_move[g] = E.root_to_move[g];
-    last_move[g] = E.root_last[g];
-}
-
-__global__ void k_get_leaves(Dev E, uint64_t *stones, int32_t *to_move, int32_t *last_move,
-                             int32_t *terminal) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    for (int j = 0; j < 2 * kWords; ++j)
-        stones[(long long)g * 2 * kWords + j] = E.leaf_stones[(long long)g * 2 * kWords + j];
-    to_move[g] = E.leaf_to_move[g];
-    last_move[g] = E.leaf_last[g];
-    terminal[g] = E.leaf_term[g];
-}
-
-// keys == nullptr: the default keys (noise_seed ^ game << 20) for the selected games
-__global__ void k_set_noise_keys(Dev E, const uint64_t *keys, const uint8_t *mask) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games || (mask != nullptr && !mask[g])) return;
-    E.noise_key[g] = keys != nullptr ? keys[g] : (E.noise_seed ^ ((uint64_t)g << 20));
-    E.noise_ctr[g] = 0;
-}
-
-__global__ void k_set_active(Dev E, const uint8_t *active) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < E.n_games) E.active[g] = active ? (active[g] ? 1 : 0) : 1;
-}
-
-// which: 0 = leaf boards, 1 = root boards
-__global__ __launch_bounds__(kWave) void k_encode(Dev E, int which, float *obs) {
-    const int g = blockIdx.x;  // which == 0: leaf index (game * K + slot); which == 1: game
-    const int lane = threadIdx.x;
-    uint64_t st[2][kWords];
-    load_board(which == 0 ? E.leaf_stones : E.root_stones, g, st);
-    const int to_move = which == 0 ? E.leaf_to_move[g] : E.root_to_move[g];
-    const int last = which == 0 ? E.leaf_last[g] : E.root_last[g];
-    const int nst = count_bits(st[0]) + count_bits(st[1]);
-    write_obs(obs + (long long)g * 4 * E.S, to_move == 0 ? st[0] : st[1],
-              to_move == 0 ? st[1] : st[0], last, nst, E.S, lane);
-}
-
-__global__ void k_uct_scores(const double *w, const int32_t *n, const int32_t *np, double c,
-                             const double *logtab, long long logtab_n, double *out, long long count) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const int pn = np[i];
-    if (pn == 0 || n[i] == 0 || pn >= logtab_n) {
-        out[i] = INFINITY;
-        return;
-    }
-    out[i] = uct_ref(w[i], n[i], logtab[pn], c);
-}
-
-// ------------------------------------------------------------------ the move step on the device (include/rlzero_hip.h: rz_play_*)
-struct Play {
-    int64_t *game_id;          // [G] -1: idle
-    int32_t *ply, *state;      // state: ry::kIdle, kRunning, kStalled
-    int32_t *mailbox;          // [G] the host's move for a stalled slot, -1: none
-    int32_t *keep, *stepm;     // [G] the moves of this step (update_with_move / env.step), written by k_play_draw
-    int32_t *top_hwm;          // [G] the fullest a game's arena has been at the end of a search (read before update_with_move compacts it)
-    int32_t *step_ab;          // [2]: k_play_draw reads [0] and writes [1], k_play_apply reads [1] and writes [0] = [1] + 1
-    const int64_t *queue_ids;
-    int32_t *queue_ctl;        // [0] head, [1] entries valid
-    int32_t *log;
-    // per-ply temperature (rz_play_set_temperatures): 1 / T before ply p, padded with its last entry to the board's cell count S,
-    // then the stall margin of each ply (rz_play.h: temp_entry)
-    const double *inv_t_of;    // [2][S]
-    int ring, words;
-    uint64_t seed;
-    double inv_t, margin;
-    double *resign;            // [2] {threshold, disabled_frac} (rz_play_set_resign; NaN threshold: off)
-    int resign_on;             // rz_play_set_resign called since rz_play_attach: k_play_draw reads `resign` (else never)
-    int temp_on;               // rz_play_set_temperatures called since rz_play_attach: k_play_draw reads `inv_t_of` (else never)
-    // playout cap randomization (rz_play_set_cap): a search has n_full simulations when cap_uniform(seed, game id, ply) < p_full,
-    // else n_fast
-    double *cap;               // [2] {n_fast, p_full} (NaN p_full: off -- every search has n_full)
-    int32_t *sims_of;          // [G] simulations of the slot's COMING search (k_play_apply, k_play_cap); read by the resident search
-    int32_t *order;            // [G] k_play_order's: the slots with a full search, those with a fast one, the inactive ones
-    int n_full;                // the engine's n_playout
-    int cap_on;                // rz_play_set_cap called since rz_play_attach: the kernels read `cap` (else never)
-    // network-vs-network matches (rz_play_set_match): games 2k and 2k + 1 start from opening k % n_open, share their draw uniforms and
-    // are searched from a fresh root by the network whose turn it is (k_play_side); the engine's own copies of the caller's table
-    const uint64_t *open_stones;   // [n_open][2][kWords]
-    const int32_t *open_to_move, *open_last;   // [n_open]
-    int n_open;
-    int match_on;              // rz_play_set_match in force: the kernels read the table and the pair's uniform (else never)
-    int queue_cap;             // rz_play_queue_ring: queue_ids is a ring of this many entries (0: the linear queue)
-};
-namespace ry = rzplay;   // rz_play.h: the move step's rules, the record and a slot's decision (tested on the CPU)
-
-// the budget of the slot's coming search (rz_play_set_cap), read by the resident search
-__device__ __forceinline__ void cap_write(const Play &Y, int g, int64_t gid, int ply) {
-    Y.sims_of[g] = ry::budget(Y.n_full, (int)Y.cap[0], Y.cap[1], Y.seed, (uint64_t)gid, (uint64_t)ply);
-}
-
-// One wave per slot: the root's visit counts into the log, then the draw of alphazero_mcts.py:88-92,147-148 in fp64 -- taken only
-// when the uniform lies farther than `margin` from both edges of its interval (the host's numpy evaluation is the arbiter).
-// In a match (rz_play_set_match) the uniform is the pair's -- (seed, game id >> 1, 2 ply + 1) -- and the move keeps no subtree:
-// keep = -1, so k_play_apply starts the next search of the game from a fresh root; stepm stays the move.
-// The kernel gathers the counts and computes log, the wave maximum and exp; the draw, the resignation rule and what the step
-// changes are rz_play.h's (ry::draw, ry::resign_rule, ry::decide), and lane 0 writes all of it at the end.
-// `vring` (rz_play_set_root_values; nullptr: off, nothing more is read or written): float32 [Y.ring][n_games], the root value the
-// mover's search saw (ry::root_value: rz_root_values' [0]) into the row of this step for every slot that holds a game -- a stalled
-// slot's root does not change, so its rows repeat the searched one's value --, NaN for an idle slot.
-__global__ __launch_bounds__(kWave) void k_play_draw(Dev E, Play Y, float *__restrict__ vring) {
-    __shared__ double sh_e[kWave * kWords];
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int step = Y.step_ab[0];
-    if (g == 0 && lane == 0) Y.step_ab[1] = step;
-    int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
-    ry::SlotIn in = {};
-    in.state = Y.state[g];
-    double v_root = NAN;
-    if (in.state != ry::kIdle) {
-        // the root's children by action (k_root_children)
-        const int arena = E.cur_arena[g];
-        const int4 *R = arena_records(E, g, arena);
-        uint64_t st[2][kWords], occ[kWords];
-        load_board(E.root_stones, g, st);
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-        const Legal L = legal_of(E, occ, lane);
-        const int4 lo = R[0];
-        if (vring != nullptr) v_root = ry::root_value(lo.x, rec_w(R[1]));
-        const bool expanded = rec_k(lo) > 0;
-        const int fc = lo.y;
-        const int nv = expanded ? lo.z : 0;
-        int before = 0;
-        int cnt[kWords];
-        bool legal[kWords];
-        double x[kWords];
-        double mx = -INFINITY;
-        // the ply's temperature (rz_play_set_temperatures): the table is read only once it has been set; a stalled slot keeps its ply,
-        // so its move is judged at the same T
-        const int ply = Y.ply[g];
-        const int tp = ply < 0 ? 0 : (ply < E.S ? ply : E.S - 1);   // (ply < S always holds)
-        const double inv_t = Y.temp_on ? Y.inv_t_of[tp] : Y.inv_t;
-        const double margin = Y.temp_on ? Y.inv_t_of[E.S + tp] : Y.margin;
-        // resignation (rz_play_set_resign): read only once it has been configured -- the rule-free path has no extra memory traffic
-        const double thr = Y.resign_on ? Y.resign[0] : NAN;
-        const bool rs = !isnan(thr) && in.state == ry::kRunning;
-        double qb = -INFINITY;   // max W / N over the visited children (rz_root_values)
-#pragma unroll
-        for (int j = 0; j < kWords; ++j) {
-            const int r = lane_action_rank(E, occ, L, j, lane, before);
-            const int a = 64 * j + lane;
-            legal[j] = a < E.A && r >= 0;
-            cnt[j] = (legal[j] && r < nv) ? R[2 * (fc + r)].x : 0;
-            if (a < E.A) rec[RZ_PLAY_RECORD_WORDS + a] = legal[j] ? cnt[j] : -1;
-            x[j] = legal[j] ? inv_t * log((double)cnt[j] + 1e-10) : -INFINITY;   // alphazero_mcts.py:91
-            mx = fmax(mx, x[j]);
-            if (rs && cnt[j] > 0) qb = fmax(qb, rec_w(R[2 * (fc + r) + 1]) / (double)cnt[j]);
-        }
-        const uint64_t gid = (uint64_t)Y.game_id[g];
-        in.game = (int64_t)gid;
-        in.ply = ply;
-        in.root_n = lo.x;
-        in.match = Y.match_on != 0;
-        if (in.state == ry::kStalled) {
-            in.mail = Y.mailbox[g];
-        } else {
-            // wave maximum of x (doubles: two 32-bit halves through the shuffle)
-            for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-#pragma unroll
-            for (int j = 0; j < kWords; ++j) sh_e[64 * j + lane] = legal[j] ? exp(x[j] - mx) : 0.0;   // :12
-            if (rs)
-                for (int off = 32; off >= 1; off >>= 1) qb = fmax(qb, __shfl_xor(qb, off));
-            __syncthreads();
-            if (lane == 0) {
-                // (rz_play_set_cap: the budget of the search behind this record -- what k_play_apply / k_play_cap wrote into sims_of)
-                in.full = Y.cap_on ? ry::full_flag(Y.cap[1], Y.seed, gid, (uint64_t)ply) : 0;
-                in.resign_on = rs;
-                if (rs) {
-                    in.resign = ry::resign_rule(lo.x, rec_w(R[1]), qb, thr);
-                    in.calibration = ry::resign_uniform(Y.seed, gid) < Y.resign[1];
-                }
-                if (ry::needs_draw(in)) {
-                    const double u = in.match ? ry::match_uniform(Y.seed, gid, (uint64_t)ply) : ry::move_uniform(Y.seed, gid, (uint64_t)ply);
-                    in.draw = ry::draw(sh_e, E.A, u, margin);
-                }
-            }
-        }
-    }
-    if (lane != 0) return;
-    const ry::SlotOut o = ry::decide(in);
-    ry::write_record(rec, in, o);
-    if (vring != nullptr) vring[(long long)(step % Y.ring) * E.n_games + g] = (float)v_root;
-    Y.keep[g] = o.keep;
-    Y.stepm[g] = o.stepm;
-    if (o.clear_mail) Y.mailbox[g] = -1;
-    if (o.state != in.state) Y.state[g] = o.state;
-    if (o.ply != in.ply) Y.ply[g] = o.ply;
-    if (o.active >= 0) E.active[g] = (uint8_t)o.active;
-}
-
-// Policy target pruning (rz_forced.h; rz_root_pruned_visits, rz_play_set_pruned_visits), one wave per game: the root's children by
-// action exactly as k_play_draw gathers them, their priors from P[pb + r]; the best child -- the first with the largest count, found
-// with the selection's first-maximum vote over (count, action) -- keeps its count, every other visited child gets rzf::pruned_child
-// against the best child's PUCT.  int32 [A] per game: the pruned count of a legal action, -1 of an illegal one.  forced_k == 0: the
-// raw counts.  `ring` != 0 (the launch in front of k_play_draw): the row of this move step in the side ring [Y.ring][G][A], -1 all
-// over for an idle slot; a stalled slot's root has not changed, so its rows repeat the searched one.  ring == 0: row g of [G][A].
-__global__ __launch_bounds__(kWave) void k_root_pruned(Dev E, Play Y, int32_t *__restrict__ out, int ring) {
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x;
-    int32_t *row = out + (long long)g * E.A;
-    bool idle = false;
-    if (ring) {
-        row += (long long)(Y.step_ab[0] % Y.ring) * E.n_games * E.A;
-        idle = Y.state[g] == ry::kIdle;
-    }
-    if (idle) {
-        for (int a = lane; a < E.A; a += kWave) row[a] = -1;
-        return;
-    }
-    const int arena = E.cur_arena[g];
-    const int4 *R = arena_records(E, g, arena);
-    const float *P = arena_priors(E, g, arena);
-    uint64_t st[2][kWords], occ[kWords];
-    load_board(E.root_stones, g, st);
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) occ[j] = st[0][j] | st[1][j];
-    const Legal L = legal_of(E, occ, lane);
-    const int4 lo = R[0], hi = R[1];
-    const bool expanded = rec_k(lo) > 0;
-    const int fc = lo.y, pb = hi.z;
-    const int nv = expanded ? lo.z : 0;
-    const double k = E.forced_k;
-    const bool prune = k > 0.0 && pb >= 0;
-    int before = 0;
-    int cnt[kWords];
-    bool legal[kWords];
-    double w[kWords];
-    float p[kWords];
-    // the lane's own best child: the first of its (up to four) actions with the largest count
-    double best = -INFINITY, bw = 0.0;
-    int besti = 0x7fffffff, bn = 0;
-    float bp = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int r = lane_action_rank(E, occ, L, j, lane, before);
-        const int a = 64 * j + lane;
-        legal[j] = a < E.A && r >= 0;
-        const bool seen = legal[j] && r < nv;
-        cnt[j] = seen ? R[2 * (fc + r)].x : 0;
-        w[j] = seen ? rec_w(R[2 * (fc + r) + 1]) : 0.0;
-        p[j] = seen && prune ? P[pb + r] : 0.0f;
-        if (legal[j] && (double)cnt[j] > best) {
-            best = (double)cnt[j];
-            besti = a;
-            bw = w[j];
-            bn = cnt[j];
-            bp = p[j];
-        }
-    }
-    const int bi = __builtin_amdgcn_readfirstlane(wave_first_max(best, besti));
-    double s_best = 0.0;
-    if (bi != 0x7fffffff) {   // (a root without a legal action has no best child: its row is -1 all over)
-        const int l = bi & 63;
-        const long long wb = __double_as_longlong(bw);
-        const double w_best = __hiloint2double(__builtin_amdgcn_readlane((int)(wb >> 32), l), __builtin_amdgcn_readlane((int)wb, l));
-        const int n_best = __builtin_amdgcn_readlane(bn, l);
-        const float p_best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bp), l));
-        s_best = rzf::puct(w_best, n_best, p_best, sqrt((double)lo.x), E.c_puct);
-    }
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-        const int a = 64 * j + lane;
-        if (a >= E.A) continue;
-        int m = -1;
-        if (legal[j]) m = (!prune || a == bi) ? cnt[j] : rzf::pruned_child(cnt[j], w[j], p[j], lo.x, sqrt((double)lo.x), k, E.c_puct, s_best);
-        row[a] = m;
-    }
-}
-
-// The rest of a move in ONE launch, one wave per slot: update_with_move with the move just drawn (advance_body: before the board
-// changes), env.step + game_end_winner (step_body), then the end of a finished game (reset_player, game.py:128) and the refill of an
-// idle slot from the queue of game ids (GomokuEnv.reset, gomoku_env.py:33-47: empty board, player 0; a fresh tree; the game's
-// noise key; in a match -- rz_play_set_match -- the opening of the game's pair instead of the empty board).  drawn == 0 (no
-// k_play_draw before it): only the refill.  The pending-priors counter of the game restarts here
-// (the flush of the move's search ran just before: rz_deferred_flush leaves its own reset launch out between draw and apply).
-__global__ __launch_bounds__(kWave) void k_play_apply(Dev E, Play Y, int drawn) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const int step = Y.step_ab[1];
-    if (g == 0 && lane == 0) Y.step_ab[0] = step + 1;
-    const int keep = drawn ? Y.keep[g] : -2, mv = drawn ? Y.stepm[g] : -1;
-    int state = Y.state[g];
-    if (lane == 0 && drawn) {   // (rz_get_stats: after the move the arena holds the kept subtree only)
-        const int top = E.top[g];
-        if (top > Y.top_hwm[g]) Y.top_hwm[g] = top;
-    }
-    advance_body(E, g, lane, keep);
-    __syncthreads();
-    int who = -1;
-    bool over = false;
-    if (mv >= 0) step_body(E, g, lane, mv, who, over);   // (idle and stalled slots make no move)
-    if (lane != 0) return;
-    if (drawn && E.pend != nullptr) E.pend[g] = 0;
-    if (state == ry::kRunning && ((mv >= 0 && over) || mv == ry::kStepResign)) {
-        int32_t *rec = Y.log + ((long long)(step % Y.ring) * E.n_games + g) * Y.words;
-        if (mv >= 0) rec[ry::kRecFlags] |= ry::ended_flags(who);   // (a resignation's record is complete: k_play_draw)
-        state = ry::kIdle;
-        Y.state[g] = state;
-        Y.game_id[g] = -1;
-        E.active[g] = 0;
-        fresh_root(E, g, E.cur_arena[g], 0);
-    }
-    Y.stepm[g] = -1;
-    Y.keep[g] = -2;
-    if (state != ry::kIdle) {
-        // the budget of the slot's coming search (a stalled slot is not searched; k_play_draw has counted the ply already)
-        if (Y.cap_on && state == ry::kRunning) cap_write(Y, g, Y.game_id[g], Y.ply[g]);
-        return;
-    }
-    int head = Y.queue_ctl[0];
-    int64_t gid = -1;
-    while (head < Y.queue_ctl[1]) {
-        const int seen = atomicCAS(&Y.queue_ctl[0], head, head + 1);
-        if (seen == head) {
-            gid = Y.queue_ids[ry::queue_slot(head, Y.queue_cap)];
-            break;
-        }
-        head = seen;
-    }
-    if (gid < 0) return;
-    Y.game_id[g] = gid;
-    Y.ply[g] = 0;
-    Y.state[g] = ry::kRunning;
-    Y.mailbox[g] = -1;
-    if (Y.match_on) {   // the pair's opening; plies count from it
-        const long long o = (long long)((gid >> 1) % Y.n_open);
-        for (int j = 0; j < 2 * kWords; ++j) E.root_stones[(long long)g * 2 * kWords + j] = Y.open_stones[o * 2 * kWords + j] & E.valid[j % kWords];
-        E.root_to_move[g] = Y.open_to_move[o] & 1;
-        E.root_last[g] = Y.open_last[o];
-    } else {
-        for (int j = 0; j < 2 * kWords; ++j) E.root_stones[(long long)g * 2 * kWords + j] = 0ull;
-        E.root_to_move[g] = 0;
-        E.root_last[g] = -1;
-    }
-    fresh_root(E, g, E.cur_arena[g], 0);
-    E.noise_key[g] = ry::noise_key(Y.seed, (uint64_t)gid);
-    E.noise_ctr[g] = 0;
-    E.active[g] = 1;
-    if (Y.cap_on) cap_write(Y, g, gid, 0);
-}
-
-// rz_play_set_cap: the rule into its device array, then the budgets of the searches that are coming under it
-__global__ void k_play_cap(Dev E, Play Y, double n_fast, double p_full) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    const int64_t gid = Y.game_id[g];
-    const int ply = Y.ply[g];
-    Y.sims_of[g] = gid < 0 ? Y.n_full : ry::budget(Y.n_full, (int)n_fast, p_full, Y.seed, (uint64_t)gid, (uint64_t)ply);   // (an idle slot: no draw)
-    if (g == 0) {
-        Y.cap[0] = n_fast;
-        Y.cap[1] = p_full;
-    }
-}
-
-// rz_play_set_temperatures: up to kTempChunk entries of the engine's table (1 / T per ply, then the margins), handed over by value -- a
-// write in stream order, so a move graph captured earlier reads the new table from its next replay on
-constexpr int kTempChunk = 64;
-struct TempChunk {
-    double v[kTempChunk];
-};
-__global__ __launch_bounds__(kTempChunk) void k_play_set_temps(double *inv_t_of, TempChunk c, int base, int count) {
-    const int i = threadIdx.x;
-    if (i < kTempChunk && base + i < count) inv_t_of[base + i] = c.v[i];
-}
-
-// The order of k_delta_res's workgroups under per-game budgets: a STABLE partition of the slots -- full budget (>= n_full), fewer
-// simulations, inactive -- so that no full search starts in the last round of a grid of more than two games per CU.  ONE workgroup,
-// any number of games in chunks of 256: ballot + mbcnt prefix per wave, the waves' totals through LDS.
-__global__ __launch_bounds__(256) void k_play_order(const uint8_t *__restrict__ active, const int32_t *__restrict__ sims_of, int n_full,
-                                                    int n_games, int32_t *__restrict__ order) {
-    __shared__ int cnt[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int run[3] = {0, 0, 0};   // the next free place of each class (uniform)
-    // pass 1: the classes' totals -> where each begins
-    int t0 = 0, t1 = 0;
-    for (int c0 = 0; c0 < n_games; c0 += 256) {
-        const int g = c0 + tid;
-        const bool act = g < n_games && active[g] != 0;
-        const bool full = act && sims_of[g] >= n_full;
-        t0 += __popcll(__ballot(full));
-        t1 += __popcll(__ballot(act && !full));
-    }
-    if (lane == 0) cnt[wave][0] = t0, cnt[wave][1] = t1;
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) run[1] += cnt[w][0], run[2] += cnt[w][0] + cnt[w][1];
-    __syncthreads();
-    // pass 2: every slot to its place
-    for (int c0 = 0; c0 < n_games; c0 += 256) {
-        const int g = c0 + tid;
-        const bool act = g < n_games && active[g] != 0;
-        const int cls = g >= n_games ? -1 : !act ? 2 : sims_of[g] >= n_full ? 0 : 1;
-        int before = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const unsigned long long m = __ballot(cls == c);
-            const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-            if (cls == c) before = pre;
-            if (lane == 0) cnt[wave][c] = __popcll(m);
-        }
-        __syncthreads();
-        if (cls >= 0) {
-            int at = run[cls] + before;
-            for (int w = 0; w < wave; ++w) at += cnt[w][cls];
-            order[at] = g;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            for (int w = 0; w < 4; ++w) run[c] += cnt[w][c];
-        __syncthreads();
-    }
-}
-
-// rz_play_side: the slots the coming search takes -- the running games whose mover is network `side` (0 = A: player 0 of the even
-// game of a pair, player 1 of the odd one).  side < 0: every running game (what k_play_apply leaves; match mode turned off).
-__global__ void k_play_side(Dev E, Play Y, int side) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    const bool a_moves = (E.root_to_move[g] == 0) == ((Y.game_id[g] & 1) == 0);
-    E.active[g] = (Y.state[g] == ry::kRunning && (side < 0 || side == (a_moves ? 0 : 1))) ? 1 : 0;
-}
-
-__global__ void k_play_resolve(Play Y, int slot, int move) { Y.mailbox[slot] = move; }
-__global__ void k_play_set_resign(double *resign, double threshold, double disabled_frac) {
-    if (threadIdx.x == 0) {
-        resign[0] = threshold;
-        resign[1] = disabled_frac;
-    }
-}
-// rz_play_queue_push: ids first .. first + count - 1 behind the valid count of the ring, then the count raised -- one workgroup; the ids
-// are written, fenced, and only then counted, so a k_play_apply that sees the new count reads them.  A push that would overwrite an
-// id no slot has claimed (ry::queue_room) writes nothing and raises RZ_FLAG_QUEUE_FULL.
-__global__ __launch_bounds__(256) void k_play_push(Dev E, Play Y, int64_t first, int count) {
-    int64_t *ids = const_cast<int64_t *>(Y.queue_ids);
-    const int head = Y.queue_ctl[0], valid = Y.queue_ctl[1];
-    if (count > ry::queue_room(head, valid, Y.queue_cap)) {
-        if (threadIdx.x == 0) {
-            atomicOr(&E.err[0], RZ_FLAG_QUEUE_FULL);
-            atomicOr(E.err_any, RZ_FLAG_QUEUE_FULL);
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < count; i += blockDim.x) ids[ry::queue_slot(valid + i, Y.queue_cap)] = first + i;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) Y.queue_ctl[1] = valid + count;
-}
-
-__global__ void k_play_no_draw(Play Y) { Y.step_ab[1] = Y.step_ab[0]; }   // rz_play_apply without a draw: the step k_play_apply reads
-
-__global__ void k_play_stop(Dev E, Play Y) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.n_games) return;
-    Y.state[g] = ry::kIdle;
-    Y.game_id[g] = -1;
-    Y.mailbox[g] = -1;
-    Y.keep[g] = -2;
-    Y.stepm[g] = -1;
-    E.active[g] = 0;
-    fresh_root(E, g, E.cur_arena[g], 0);
-}
 
 thread_local char g_err[kRzErrBytes] = "";
 
@@ -2380,20 +799,8 @@ int rz_play_set_pruned_visits(rz_engine *e, int32_t *d_ring, void *stream) {
     if (e->play_steps > 0 || e->play_drawn) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: a move step has been enqueued since rz_play_attach (attach again)");
     if (d_ring != nullptr && !(e->dev.forced_k > 0.0)) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: forced playouts are off (rz_set_forced_playouts first)");
     if (d_ring != nullptr && e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: a match is on (rz_play_set_match): its games are not training data");
-    if (d_ring != nullptr) {   // host memory (pinned, written directly like the log) must be addressable from this device
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof(attr));
-        if (hipPointerGetAttributes(&attr, d_ring) != hipSuccess) {
-            (void)hipGetLastError();
-        } else if (attr.type == hipMemoryTypeHost) {
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, d_ring, 0) != hipSuccess || dp == nullptr) {
-                (void)hipGetLastError();
-                return rz_fail(RZ_ERR_ARG, "rz_play_set_pruned_visits: d_ring is host memory that device %d cannot address (pass device memory)", e->cfg.device);
-            }
-            d_ring = static_cast<int32_t *>(dp);
-        }
-    }
+    // host memory (pinned, written directly like the log) must be addressable from this device
+    if (d_ring != nullptr) RZ_TRY(rz_device_address(d_ring, e->cfg.device, "rz_play_set_pruned_visits", "d_ring"));
     e->play_pring = d_ring;
     return RZ_OK;
 }
@@ -2448,20 +855,8 @@ int rz_play_attach(rz_engine *e, const rz_play_config *cfg) {
     Y.queue_ids = cfg->d_queue_ids;
     Y.queue_ctl = cfg->d_queue_ctl;
     Y.log = cfg->d_log;
-    {   // a log in HOST memory (pinned: the kernels write it directly) must be addressable from THIS device: asked, not assumed
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof(attr));
-        if (hipPointerGetAttributes(&attr, cfg->d_log) != hipSuccess) {
-            (void)hipGetLastError();   // (an address the runtime does not know: treated as device memory, as before)
-        } else if (attr.type == hipMemoryTypeHost) {
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, cfg->d_log, 0) != hipSuccess || dp == nullptr) {
-                (void)hipGetLastError();
-                return rz_fail(RZ_ERR_ARG, "rz_play_attach: d_log is host memory that device %d cannot address (pass device memory)", e->cfg.device);
-            }
-            Y.log = static_cast<int32_t *>(dp);
-        }
-    }
+    // a log in HOST memory (pinned: the kernels write it directly) must be addressable from THIS device
+    RZ_TRY(rz_device_address(Y.log, e->cfg.device, "rz_play_attach", "d_log"));
     Y.ring = cfg->ring_steps;
     Y.words = RZ_PLAY_RECORD_WORDS + e->dev.A;
     Y.seed = cfg->seed;
@@ -2493,20 +888,8 @@ int rz_play_set_root_values(rz_engine *e, float *d_ring, void *stream) {
     // a move step enqueued -- or captured into a whole-move graph -- holds the ring it was launched with
     if (e->play_steps > 0 || e->play_drawn) return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: a move step has been enqueued since rz_play_attach (attach again)");
     if (d_ring != nullptr && e->play.match_on) return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: a match is on (rz_play_set_match): its games are not training data");
-    if (d_ring != nullptr) {   // host memory (pinned, written directly like the log) must be addressable from this device
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof(attr));
-        if (hipPointerGetAttributes(&attr, d_ring) != hipSuccess) {
-            (void)hipGetLastError();
-        } else if (attr.type == hipMemoryTypeHost) {
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, d_ring, 0) != hipSuccess || dp == nullptr) {
-                (void)hipGetLastError();
-                return rz_fail(RZ_ERR_ARG, "rz_play_set_root_values: d_ring is host memory that device %d cannot address (pass device memory)", e->cfg.device);
-            }
-            d_ring = static_cast<float *>(dp);
-        }
-    }
+    // host memory (pinned, written directly like the log) must be addressable from this device
+    if (d_ring != nullptr) RZ_TRY(rz_device_address(d_ring, e->cfg.device, "rz_play_set_root_values", "d_ring"));
     e->play_vring = d_ring;
     return RZ_OK;
 }

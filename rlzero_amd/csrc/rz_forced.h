@@ -1,7 +1,7 @@
 // rz_forced.h -- forced playouts and policy target pruning (Wu 2019, "Accelerating Self-Play Learning in Go", section 3.2) for the
 // root of a PUCT search: everything about them that is neither a kernel launch nor a memory access.  Plain C++, no HIP include, so
 // that the CPU can test it against tests/forced_twin.py (tests/test_forced_host.py); the kernels call these functions
-// (rz_tree.h: scan_children at the root; rz_engine.hip: k_root_pruned).  All fp64, each operation rounded once: the including
+// (rz_tree.h: scan_children at the root; rz_engine_play.h: k_root_pruned).  All fp64, each operation rounded once: the including
 // translation units are compiled with -ffp-contract=off, and the pragma below says so again.
 //
 // Notation: N the visit count of the root RECORD (the N whose square root the PUCT term uses -- under tree reuse whatever the record

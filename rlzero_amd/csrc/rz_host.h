@@ -1,5 +1,6 @@
 // rz_host.h -- the host-side runtime the six translation units share (rz_engine, rz_net, rz_muzero, rz_replay, rz_mz_replay, rz_mz_learn): the error
-// message, the checks every entry point opens with, the two ways to own device memory and the staging pair.  Host code only: no kernel,
+// message, the checks every entry point opens with, the check of a caller's buffer that kernels write, the two ways to own device memory
+// and the staging pair.  Host code only (rz_engine.hip and rz_net.hip keep their kernels in headers of their own): no kernel,
 // nothing a kernel reads.  One copy of each, so that a new subsystem takes its plumbing from here instead of copying a neighbour's.
 #pragma once
 
@@ -12,9 +13,9 @@
 
 #include "rlzero_hip.h"
 
-void rz_set_error(const char *msg);  // rz_engine.hip: sets the thread-local message rz_last_error() returns
+void rz_set_error(const char *msg);  // rz_engine.hip (its host side, like g_err): sets the thread-local message rz_last_error() returns
 
-constexpr size_t kRzErrBytes = 512;  // the size of that message (g_err in rz_engine.hip)
+constexpr size_t kRzErrBytes = 512;  // the size of that message (g_err)
 
 // ---------------------------------------------------------------- errors and the checks of an entry point
 
@@ -63,6 +64,27 @@ inline int rz_on_device(int device) {
 inline int rz_launched(const char *what) {
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return rz_fail(RZ_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(err));
+    return RZ_OK;
+}
+
+// ---------------------------------------------------------------- a caller's buffer that kernels write directly
+
+// A buffer in HOST memory (pinned) must be addressable from `device`: asked, not assumed.  `p` becomes the address the device uses; an
+// address the runtime does not know is treated as device memory and stays as it is.  `entry` and `arg` name the entry point and its
+// argument in the message.
+template <typename T>
+int rz_device_address(T *&p, int device, const char *entry, const char *arg) {
+    hipPointerAttribute_t attr = {};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+    } else if (attr.type == hipMemoryTypeHost) {
+        void *dp = nullptr;
+        if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess || dp == nullptr) {
+            (void)hipGetLastError();
+            return rz_fail(RZ_ERR_ARG, "%s: %s is host memory that device %d cannot address (pass device memory)", entry, arg, device);
+        }
+        p = static_cast<T *>(dp);
+    }
     return RZ_OK;
 }
 

@@ -208,7 +208,7 @@ __global__ void k_mz_expand_backup(MzDev E, const float *reward, const float *pr
 
 // One Gamma(alpha, 1) sample for the root's Dirichlet noise (add_exploration_noise) from a counter-based stream:
 // Marsaglia-Tsang (boosted by U^(1/alpha) below shape 1).  Noise, not parity: hardware transcendentals, 24-bit uniforms
-// (the scheme of gamma03 in rz_engine.hip with the shape as an argument).
+// (the scheme of gamma03 in rz_tree.h with the shape as an argument).
 __device__ __forceinline__ uint32_t mz_hash32(uint32_t x) {
     x ^= x >> 16;
     x *= 0x7feb352du;

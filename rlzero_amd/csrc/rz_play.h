@@ -1,4 +1,4 @@
-// rz_play.h -- the move step on the device (rz_engine.hip: k_play_draw, k_play_apply, k_play_cap; include/rlzero_hip.h: rz_play_*):
+// rz_play.h -- the move step on the device (rz_engine_play.h: k_play_draw, k_play_apply, k_play_cap; include/rlzero_hip.h: rz_play_*):
 // everything about it that is neither a kernel launch nor a memory access.  Plain C++, no HIP include, so that the CPU can test it
 // against the host's side of the same rules (tests/test_play_host.py: rlzero_amd/selfplay.py and rlzero_amd/playlog.py); the kernels
 // and the host entry points call these functions.  Apart from the kernel's own log and exp everything here is integer arithmetic or

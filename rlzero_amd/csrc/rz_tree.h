@@ -1,7 +1,7 @@
-// Device-side tree code shared by the engine's kernels (rz_engine.hip) and the resident search kernels of the evaluator
-// (rz_net.hip): the engine's device view (Dev), bitboard rules, the selection and expand / backup bodies, the value head of the
-// deferred-priors route.  Everything lives in namespace rzt with internal linkage; both translation units are compiled with
-// -ffp-contract=off (see rz_engine.hip: the tree arithmetic must round like CPython does).
+// Device-side tree code shared by the engine's kernels (rz_engine.hip's headers, rz_engine_*.h) and the resident search kernels of the
+// evaluator (rz_net.hip's, rz_net_*.h and rz_delta.h): the engine's device view (Dev), bitboard rules, the selection and expand /
+// backup bodies, the value head of the deferred-priors route.  Everything lives in namespace rzt with internal linkage; both translation
+// units are compiled with -ffp-contract=off (see rz_engine.hip's file comment: the tree arithmetic must round like CPython does).
 #pragma once
 #include <hip/hip_runtime.h>
 

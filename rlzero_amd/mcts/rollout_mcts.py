@@ -4,7 +4,7 @@ play-out, most visited move, tree reset after every move.  Used by the reference
 the evaluation opponent (tools/train_alphazero.py:139-163).
 
 The tree lives in the HIP engine; the play-outs run on the device on bitboards
-(csrc/rz_engine.hip, k_eval_rollout).  The reference draws its play-out moves from numpy's
+(csrc/rz_engine_eval.h, k_eval_rollout).  The reference draws its play-out moves from numpy's
 global stream (``np.random.rand(k)`` per ply, :99); here every ``get_action`` draws ONE integer
 from that stream as the seed of a counter-based generator, so ``np.random.seed`` still makes a
 game reproducible, though not move-for-move equal to the reference's stream.

@@ -2,7 +2,7 @@
 
 * the AlphaZero expansion noise -- ``gamma03`` in csrc/rz_tree.h, keyed by ``mix64(mix64(noise_key[g]) ^ ctr)`` with the child's
   sub-key ``hash32(lo ^ hi) + 0x9E3779B9 * (action + 1)``; drawn, summed over the wave and mixed ``0.75 p + 0.25 eta`` in
-  rz_tree.h (the in-step expansion) and twice in rz_engine.hip (deferred_priors_body, the level-synchronous multi-simulation step);
+  rz_tree.h (the in-step expansion) and twice in rz_engine.hip's headers (rz_engine_deferred.h: deferred_priors_body; rz_engine_ml.h: the level-synchronous step);
 * the MuZero whole-move root noise -- ``mz_gamma`` in csrc/rz_muzero.hip, the same scheme with the shape as an argument and a
   floor of 1e-30, keyed by three splitmix64 rounds over (noise_seed ^ g << 24, episode, steps);
 * the MuZero action draw of the whole moves -- cumulative visits ^ (1 / T) against a 53-bit uniform keyed the same way behind

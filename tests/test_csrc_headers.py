@@ -1,10 +1,17 @@
-"""Every kernel header of rz_net.hip compiles alone (rlzero_amd/csrc/rz_net_*.h, rz_delta.h), and so does the profile build.
+"""Every kernel header of rz_net.hip and of rz_engine.hip compiles alone (rlzero_amd/csrc/rz_net_*.h, rz_delta.h, rz_engine_*.h), and
+so does the profile build.
 
-rz_net.hip is one translation unit cut into one header per kernel family.  Each header includes what it uses and opens its own
+Each of the two is one translation unit cut into one header per kernel family.  Each header includes what it uses and opens its own
 anonymous namespace, so it can be read -- and parsed -- without the others before it: a syntax-only pass of hipcc over the header as
-the main file, with the include paths of rlzero_amd/_build.py, must succeed.  A header that leans on what rz_net.hip happens to
+the main file, with the include paths of rlzero_amd/_build.py, must succeed.  A header that leans on what its source happens to
 include before it fails here in under a second.  -DRZ_NET_PROFILE changes kernel text in every family and is built by nothing else,
-so one more case parses all of rz_net.hip with it.  Nothing is compiled to code."""
+so one more case parses all of rz_net.hip with it.  Nothing is compiled to code.
+
+rz_play.h and rz_forced.h are left out: they use __forceinline__ without the runtime header, because the CPU tests also compile them
+as plain C++, so they do not parse alone as HIP.
+
+The last tests hold rlzero_amd/_build.py to what the compiler reads: an object is keyed on the headers headers_of() finds for its
+source, and every project header the preprocessor opens for that source (hipcc -MM) must be among them."""
 import glob
 import os
 import shutil
@@ -12,9 +19,13 @@ import subprocess
 
 import pytest
 
+from rlzero_amd import _build
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_net_*.h'))) + ['rz_delta.h']
+NET_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_net_*.h'))) + ['rz_delta.h']
+ENGINE_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_engine_*.h')))
+HEADERS = NET_HEADERS + ENGINE_HEADERS
 
 
 def find_hipcc():
@@ -36,15 +47,25 @@ def syntax_only(source, *defines):
 
 
 def test_the_family_headers_are_the_ones_the_index_names():
-    assert HEADERS == ['rz_net_dev.h', 'rz_net_f32.h', 'rz_net_heads.h', 'rz_net_rows.h', 'rz_net_split.h', 'rz_delta.h']
-    with open(os.path.join(CSRC, 'rz_net.hip')) as f:
+    assert NET_HEADERS == ['rz_net_dev.h', 'rz_net_f32.h', 'rz_net_heads.h', 'rz_net_rows.h', 'rz_net_split.h', 'rz_delta.h']
+    assert ENGINE_HEADERS == ['rz_engine_deferred.h', 'rz_engine_eval.h', 'rz_engine_ml.h', 'rz_engine_play.h', 'rz_engine_roots.h',
+                              'rz_engine_step.h']
+    for source, names in (('rz_net.hip', NET_HEADERS), ('rz_engine.hip', ENGINE_HEADERS)):
+        with open(os.path.join(CSRC, source)) as f:
+            text = f.read()
+        for name in names:
+            assert '#include "%s"' % name in text, name
+
+
+def test_the_engine_source_is_host_code_only():
+    with open(os.path.join(CSRC, 'rz_engine.hip')) as f:
         text = f.read()
-    for name in HEADERS:
-        assert '#include "%s"' % name in text, name
+    assert '__global__' not in text and '__device__' not in text
 
 
-# (rz_host.h: the host-side runtime all five sources include -- no kernel family, but a header that must stand alone like the others)
-@pytest.mark.parametrize('header', HEADERS + ['rz_host.h'])
+# (rz_host.h: the host-side runtime all six sources include -- no kernel family, but a header that must stand alone like the others;
+# rz_tree.h and rz_trace.h: the device code both translation units' kernels call)
+@pytest.mark.parametrize('header', HEADERS + ['rz_host.h', 'rz_tree.h', 'rz_trace.h'])
 def test_a_kernel_header_compiles_alone(header):
     done = syntax_only(header)
     assert done.returncode == 0, done.stdout.decode(errors='replace')[-4000:]
@@ -53,3 +74,31 @@ def test_a_kernel_header_compiles_alone(header):
 def test_the_profile_build_compiles():
     done = syntax_only('rz_net.hip', '-DRZ_NET_PROFILE')
     assert done.returncode == 0, done.stdout.decode(errors='replace')[-4000:]
+
+
+# ---------------------------------------------------------------- _build.headers_of against the preprocessor
+
+def project_headers_read(src):
+    """The files under include/ and rlzero_amd/csrc/ that the preprocessor opens for `src` (hipcc -MM: nothing is compiled)."""
+    cmd = [HIPCC] + _build.FLAGS + ['-I' + os.path.join(REPO, 'include'), '-MM', src]
+    done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert done.returncode == 0, done.stderr.decode(errors='replace')[-4000:]
+    words = done.stdout.decode().replace('\\\n', ' ').split()
+    paths = {os.path.realpath(w) for w in words if not w.endswith(':')}
+    roots = (os.path.realpath(os.path.join(REPO, 'include')) + os.sep, os.path.realpath(CSRC) + os.sep)
+    return {p for p in paths if p.startswith(roots)} - {os.path.realpath(src)}
+
+
+@pytest.mark.parametrize('src', _build.SOURCES, ids=os.path.basename)
+def test_an_object_depends_on_every_header_its_source_reads(src):
+    read = project_headers_read(src)
+    assert read, 'hipcc -MM lists no project header for %s' % src
+    known = {os.path.realpath(p) for p in _build.headers_of(src)}
+    assert read <= known, sorted(read - known)
+
+
+def test_a_family_header_belongs_to_its_translation_unit_alone():
+    sets = {os.path.basename(src): {os.path.basename(p) for p in _build.headers_of(src)} for src in _build.SOURCES}
+    assert [name for name, hs in sets.items() if 'rz_engine_play.h' in hs] == ['rz_engine.hip']
+    assert 'rz_tree.h' in sets['rz_engine.hip'] and 'rz_tree.h' in sets['rz_net.hip']
+    assert 'rz_mz_learn.h' not in sets['rz_net.hip']

@@ -19,6 +19,7 @@ N_PAIRS = 1 << 18
 def test_hashes_are_the_sources():
     """mix64 against rz_play.h (the constants are read out of the header, the function evaluated with Python integers), hash32 against
     rz_tree.h, splitmix64 = mix64 (one definition, two names on the device)."""
+    import glob
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'rlzero_amd', 'csrc')
@@ -53,10 +54,16 @@ def test_hashes_are_the_sources():
     assert [int(v) for v in ds.splitmix64(np.array(xs, dtype=np.uint64))] == [mix_py(x) for x in xs]
     assert [int(v) for v in ds.hash32(np.array([x & 0xFFFFFFFF for x in xs], dtype=np.uint64))] == [hash_py(x & 0xFFFFFFFF) for x in xs]
     # ... and the noise constants of the three copies of the mix and of the MuZero key are the ones restated here
-    engine = open(os.path.join(csrc, 'rz_engine.hip')).read()
     muzero = open(os.path.join(csrc, 'rz_muzero.hip')).read()
     assert tree.count('0x9E3779B9u * (uint32_t)(64 * j + lane + 1)') == 1
-    assert engine.count('0x9E3779B9u * (uint32_t)(64 * j + lane + 1)') + engine.count('0x9E3779B9u * (uint32_t)(64 * i + lane + 1)') == 2
+
+    def copies(name):
+        text = open(os.path.join(csrc, name)).read()
+        return text.count('0x9E3779B9u * (uint32_t)(64 * j + lane + 1)') + text.count('0x9E3779B9u * (uint32_t)(64 * i + lane + 1)')
+
+    # (one in deferred_priors_body, one in the level-synchronous step -- and none anywhere else in the engine's translation unit)
+    assert copies('rz_engine_deferred.h') == 1 and copies('rz_engine_ml.h') == 1
+    assert copies('rz_engine.hip') + sum(copies(p) for p in glob.glob(os.path.join(csrc, 'rz_engine_*.h'))) == 2
     rules = open(os.path.join(csrc, 'rz_mz_env.h')).read()   # (the MuZero key has one home, which both of its kernels call)
     assert rules.count('0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key') == 1 and '0x9E3779B9u' not in muzero and '0xA5A5A5A5ull' in muzero
     assert tree.count('key + 0x5bd1e995u') == 1 and muzero.count('key + 0x5bd1e995u') == 1

@@ -153,7 +153,7 @@ def test_the_library_is_built_without_contraction():
     with open(os.path.join(CSRC, 'rz_replay.hip')) as f:
         text = f.read()
     assert '#include "rz_replay_rules.h"' in text and 'rzrr::value_target' in text
-    with open(os.path.join(CSRC, 'rz_engine.hip')) as f:
+    with open(os.path.join(CSRC, 'rz_engine_play.h')) as f:
         assert 'ry::root_value' in f.read()
 
 
