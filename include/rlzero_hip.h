@@ -914,7 +914,7 @@ int rz_mz_play_cartpole(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t n
  * entry point had of its own took every action other than 1 as 0; such input was never specified). */
 int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                      float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
-/* Moves kept on the device for any environment the library knows (ABI 41; rz_muzero.hip: k_mz_env_step, k_mz_env_move,
+/* Moves kept on the device for any environment the library knows (ABI 41; csrc/rz_muzero_moves.h: k_mz_env_step, k_mz_env_move,
  * k_mz_root_noise; the rules: csrc/rz_mz_env.h).  kind: RZ_MZ_ENV_CARTPOLE (4 state doubles, 4 observations, 2 actions) or
  * RZ_MZ_ENV_ACROBOT (Acrobot-v1: 4 state doubles theta1, theta2, dtheta1, dtheta2; 6 observations cos / sin of the two angles and
  * the two velocities; 3 actions = torque -1, 0, +1; reward -1 per step, 0 for the step that reaches the goal).

@@ -1,4 +1,4 @@
-// rz_mz_env.h -- the rules of the MuZero environments and of the moves kept on the device (rz_muzero.hip: k_mz_search's MOVES stages,
+// rz_mz_env.h -- the rules of the MuZero environments and of the moves kept on the device (rz_muzero_search.h: k_mz_search's MOVES stages; rz_muzero_moves.h:
 // k_mz_env_step, k_mz_env_move, k_mz_root_noise; include/rlzero_hip.h: rz_mz_play_cartpole, rz_cartpole_step, rz_mz_env_step,
 // rz_mz_env_move, rz_mz_root_noise): everything about them that is neither a kernel launch nor a memory access.  Plain C++, no HIP
 // include, so that the CPU can run it against the scalar restatements of CartPole, Acrobot, the keys and the draw

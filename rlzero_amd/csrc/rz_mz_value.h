@@ -1,5 +1,5 @@
 // rz_mz_value.h -- MuZero's invertible value transform (arXiv:1911.08265v2 appendix F; R2D2's h): ONE copy of the rule for the search
-// (rz_muzero.hip: k_mz_search<..., VT> applies value_h_inv to the network's reward and value before the backup) and for the learner's
+// (rz_muzero_search.h: k_mz_search<..., VT> applies value_h_inv to the network's reward and value before the backup) and for the learner's
 // targets (rz_mz_target.h: unroll_row<VT> applies value_h to the n-step return and the stored reward).  Plain C++, no HIP include,
 // so that the CPU can test it against the Python twin tests/mz_value_twin.py bit for bit (tests/test_mz_value_transform_host.py).
 //   h(x)    = sign(x) (sqrt(|x| + 1) - 1) + eps x

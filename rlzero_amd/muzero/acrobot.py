@@ -34,7 +34,7 @@ def acrobot_initial_states(seed, env_ids, episodes):
 class AcrobotBatch(object):
     """The environments live on the device, as ``CartPoleBatch``'s do: ``state`` float64 [n, 4] (theta1, theta2, dtheta1,
     dtheta2), ``steps`` / ``episode_dev`` int64 [n]; a step of all of them (RK4, termination, auto-reset) is ONE kernel launch
-    (csrc/rz_muzero.hip k_mz_env_step) and never synchronises with the host.  MuZero's device moves (MuZeroTree.env_move) step the
+    (csrc/rz_muzero_moves.h k_mz_env_step) and never synchronises with the host.  MuZero's device moves (MuZeroTree.env_move) step the
     same tensors in place."""
     n_actions = 3
     obs_dim = 6

@@ -41,7 +41,7 @@ def initial_states(seed, env_ids, episodes):
 
 class CartPoleBatch(object):
     """The environments live on the device: ``state`` float64 [n, 4], ``steps`` / ``episode_dev`` int64 [n]; a step of
-    all of them (physics, termination, auto-reset) is ONE kernel launch (rz_cartpole_step: csrc/rz_muzero.hip
+    all of them (physics, termination, auto-reset) is ONE kernel launch (rz_cartpole_step: csrc/rz_muzero_moves.h
     k_mz_env_step over the rules of csrc/rz_mz_env.h) and never synchronises with the host.  The fused MuZero moves
     (MuZeroTree.play_cartpole) step the same tensors in place."""
     n_actions = 2

@@ -204,7 +204,7 @@ class MuZeroSelfPlay(object):
     def __init__(self, net, env, n_sims=50, discount=0.997, temperature=1.0, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, seed=0, pb_c_base=19652.0, pb_c_init=1.25, use_graph=True, fused=None,
                  fused_moves=None, moves_per_launch=16, arena_rows=None, device_moves=None):
-        """``fused``: run the whole search of a move in ONE kernel launch (csrc/rz_muzero.hip k_mz_search: the model is
+        """``fused``: run the whole search of a move in ONE kernel launch (csrc/rz_muzero_search.h k_mz_search: the model is
         evaluated inside the kernel on the matrix pipe, 16 games per workgroup, trees in LDS); None = whenever the model
         fits it (hidden size 64, <= 8 actions).  Otherwise one hipGraph of ~15 launches per simulation (tree kernels +
         PyTorch-ROCm layers).

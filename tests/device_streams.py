@@ -3,7 +3,7 @@
 * the AlphaZero expansion noise -- ``gamma03`` in csrc/rz_tree.h, keyed by ``mix64(mix64(noise_key[g]) ^ ctr)`` with the child's
   sub-key ``hash32(lo ^ hi) + 0x9E3779B9 * (action + 1)``; drawn, summed over the wave and mixed ``0.75 p + 0.25 eta`` in
   rz_tree.h (the in-step expansion) and twice in rz_engine.hip's headers (rz_engine_deferred.h: deferred_priors_body; rz_engine_ml.h: the level-synchronous step);
-* the MuZero whole-move root noise -- ``mz_gamma`` in csrc/rz_muzero.hip, the same scheme with the shape as an argument and a
+* the MuZero whole-move root noise -- ``mz_gamma`` in csrc/rz_muzero_noise.h, the same scheme with the shape as an argument and a
   floor of 1e-30, keyed by three splitmix64 rounds over (noise_seed ^ g << 24, episode, steps);
 * the MuZero action draw of the whole moves -- cumulative visits ^ (1 / T) against a 53-bit uniform keyed the same way behind
   the salt 0xA5A5A5A5.
@@ -23,7 +23,7 @@ ACTION_SALT = 0xA5A5A5A5
 
 # ---------------------------------------------------------------------------------------------------------------------- hashes
 def hash32(x):
-    """rz_tree.h hash32 / rz_muzero.hip mz_hash32 on uint32 arrays (kept in uint64 lanes, masked after every multiply)."""
+    """rz_tree.h hash32 / rz_muzero_noise.h mz_hash32 on uint32 arrays (kept in uint64 lanes, masked after every multiply)."""
     x = np.asarray(x, dtype=np.uint64) & M32
     x = x ^ (x >> np.uint64(16))
     x = (x * np.uint64(0x7feb352d)) & M32
@@ -181,7 +181,7 @@ def muzero_eta(noise_seed, g, episode, steps, A, alpha, dtype=np.float64):
 
 
 def muzero_action(noise_seed, g, episode, steps, visits, inv_T):
-    """The action of one move of the whole moves (rz_muzero.hip, "the move"): ``visits`` int [..., A] -> (action, gap), gap =
+    """The action of one move of the whole moves (rz_muzero_search.h, "the move"): ``visits`` int [..., A] -> (action, gap), gap =
     min_a |cum_a - target| / total (how close the draw came to a boundary; inf for an arg-max).  inv_T <= 0: the first maximum."""
     visits = np.asarray(visits, dtype=np.float64)
     A = visits.shape[-1]

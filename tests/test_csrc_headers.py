@@ -1,14 +1,18 @@
-"""Every kernel header of rz_net.hip and of rz_engine.hip compiles alone (rlzero_amd/csrc/rz_net_*.h, rz_delta.h, rz_engine_*.h), and
-so does the profile build.
+"""Every kernel header of rz_net.hip, of rz_engine.hip and of rz_muzero.hip compiles alone (rlzero_amd/csrc/rz_net_*.h, rz_delta.h,
+rz_engine_*.h, rz_muzero_*.h), and so do the profile builds.
 
-Each of the two is one translation unit cut into one header per kernel family.  Each header includes what it uses and opens its own
+Each of the three is one translation unit cut into one header per kernel family.  Each header includes what it uses and opens its own
 anonymous namespace, so it can be read -- and parsed -- without the others before it: a syntax-only pass of hipcc over the header as
 the main file, with the include paths of rlzero_amd/_build.py, must succeed.  A header that leans on what its source happens to
 include before it fails here in under a second.  -DRZ_NET_PROFILE changes kernel text in every family and is built by nothing else,
-so one more case parses all of rz_net.hip with it.  Nothing is compiled to code.
+so one more case parses all of rz_net.hip with it; -DRZ_MZ_PROFILE changes k_mz_search's text and gets a case of its own.  Nothing is
+compiled to code.
 
 rz_play.h and rz_forced.h are left out: they use __forceinline__ without the runtime header, because the CPU tests also compile them
-as plain C++, so they do not parse alone as HIP.
+as plain C++, so they do not parse alone as HIP.  rz_mz_env.h and rz_mz_value.h are left out for the same reason: under hipcc their
+functions are __host__ __device__ __forceinline__ (RZE_FN, RZV_FN), and they include no runtime header because the CPU tests compile
+them as plain C++ (tests/test_mz_env_host.py, tests/test_mz_value_transform_host.py): "unknown type name '__forceinline__'".
+rz_mz_pack.h -- plain C++ with no attribute at all -- does parse alone as HIP and is held to it.
 
 The last tests hold rlzero_amd/_build.py to what the compiler reads: an object is keyed on the headers headers_of() finds for its
 source, and every project header the preprocessor opens for that source (hipcc -MM) must be among them."""
@@ -25,7 +29,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
 NET_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_net_*.h'))) + ['rz_delta.h']
 ENGINE_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_engine_*.h')))
-HEADERS = NET_HEADERS + ENGINE_HEADERS
+MUZERO_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 'rz_muzero_*.h')))
+HEADERS = NET_HEADERS + ENGINE_HEADERS + MUZERO_HEADERS
 
 
 def find_hipcc():
@@ -50,7 +55,9 @@ def test_the_family_headers_are_the_ones_the_index_names():
     assert NET_HEADERS == ['rz_net_dev.h', 'rz_net_f32.h', 'rz_net_heads.h', 'rz_net_rows.h', 'rz_net_split.h', 'rz_delta.h']
     assert ENGINE_HEADERS == ['rz_engine_deferred.h', 'rz_engine_eval.h', 'rz_engine_ml.h', 'rz_engine_play.h', 'rz_engine_roots.h',
                               'rz_engine_step.h']
-    for source, names in (('rz_net.hip', NET_HEADERS), ('rz_engine.hip', ENGINE_HEADERS)):
+    assert MUZERO_HEADERS == ['rz_muzero_hot.h', 'rz_muzero_moves.h', 'rz_muzero_noise.h', 'rz_muzero_roots.h', 'rz_muzero_search.h',
+                              'rz_muzero_step.h', 'rz_muzero_tree.h']
+    for source, names in (('rz_net.hip', NET_HEADERS), ('rz_engine.hip', ENGINE_HEADERS), ('rz_muzero.hip', MUZERO_HEADERS)):
         with open(os.path.join(CSRC, source)) as f:
             text = f.read()
         for name in names:
@@ -63,9 +70,16 @@ def test_the_engine_source_is_host_code_only():
     assert '__global__' not in text and '__device__' not in text
 
 
+def test_the_muzero_source_is_host_code_only():
+    with open(os.path.join(CSRC, 'rz_muzero.hip')) as f:
+        text = f.read()
+    assert '__global__' not in text and '__device__' not in text
+
+
 # (rz_host.h: the host-side runtime all six sources include -- no kernel family, but a header that must stand alone like the others;
-# rz_tree.h and rz_trace.h: the device code both translation units' kernels call)
-@pytest.mark.parametrize('header', HEADERS + ['rz_host.h', 'rz_tree.h', 'rz_trace.h'])
+# rz_tree.h and rz_trace.h: the device code both translation units' kernels call; rz_mz_pack.h: the host arithmetic whose sizes
+# rz_muzero.hip's headers take)
+@pytest.mark.parametrize('header', HEADERS + ['rz_host.h', 'rz_tree.h', 'rz_trace.h', 'rz_mz_pack.h'])
 def test_a_kernel_header_compiles_alone(header):
     done = syntax_only(header)
     assert done.returncode == 0, done.stdout.decode(errors='replace')[-4000:]
@@ -73,6 +87,11 @@ def test_a_kernel_header_compiles_alone(header):
 
 def test_the_profile_build_compiles():
     done = syntax_only('rz_net.hip', '-DRZ_NET_PROFILE')
+    assert done.returncode == 0, done.stdout.decode(errors='replace')[-4000:]
+
+
+def test_the_muzero_profile_build_compiles():
+    done = syntax_only('rz_muzero.hip', '-DRZ_MZ_PROFILE')
     assert done.returncode == 0, done.stdout.decode(errors='replace')[-4000:]
 
 
@@ -100,5 +119,6 @@ def test_an_object_depends_on_every_header_its_source_reads(src):
 def test_a_family_header_belongs_to_its_translation_unit_alone():
     sets = {os.path.basename(src): {os.path.basename(p) for p in _build.headers_of(src)} for src in _build.SOURCES}
     assert [name for name, hs in sets.items() if 'rz_engine_play.h' in hs] == ['rz_engine.hip']
+    assert [name for name, hs in sets.items() if 'rz_muzero_search.h' in hs] == ['rz_muzero.hip']
     assert 'rz_tree.h' in sets['rz_engine.hip'] and 'rz_tree.h' in sets['rz_net.hip']
     assert 'rz_mz_learn.h' not in sets['rz_net.hip']

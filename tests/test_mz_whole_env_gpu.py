@@ -2,7 +2,7 @@
 six observations, reward -1 per step, the time limit an argument.  tests/test_muzero_moves_tree.py at A = 3 and D = 6, and
 tests/test_mz_env_gpu.py's checks of a move on the records of whole moves.
 
-G = 40 environments everywhere: two workgroups of 16 and half of a third.  Placements, by the plan's own formula for three actions
+G = 40 environments everywhere (but the one case of 16 that asks for more than 64 KB of LDS): two workgroups of 16 and half of a third.  Placements, by the plan's own formula for three actions
 (asserted through ``search_plan(whole_moves=True)``): 30 simulations -> 16 games per workgroup, trees in LDS; 50 simulations -> 16,
 trees in HBM; 50 simulations with 8 asked for -> 8, trees in LDS.  The yardsticks: oracle/muzero_ref.py fed the unfolded expansions
 (tests/mz_unfold.py), ``net.double()`` on the CPU, tests/acrobot_twin.py set to the device's own state, tests/device_streams.py."""
@@ -117,6 +117,40 @@ def test_three_action_placements(case):
     instantiation a whole move then runs (``_one_whole_move`` asserts the same plan before its launch)."""
     run = _one_whole_move(case, noise=True)
     assert (run['top'] == 1 + A * (run['n_sims'] + 1)).all() and (run['root_n'] == run['n_sims']).all()
+
+
+def test_trees_in_lds_past_64_kb_without_the_value_transform():
+    """Acrobot whole moves WITHOUT the value transform where the launch asks for more than 64 KB of dynamic LDS with the trees in it:
+    the two instantiations the dynamic-LDS attribute was not set for until rz_mz_load_model began to walk the table the launcher
+    reads.  16 environments (one full workgroup), 2 moves in one launch, the fewest simulations for which the plan says so -- found by
+    asking the plan, not by the formula.  Then what the placements above assert: full trees, every root visited n_sims times, and every
+    tree of the last move the pseudocode's bit for bit with its record."""
+    from rlzero_amd.muzero import AcrobotBatch, MuZeroTree
+    n_envs, n_sims = 16, None
+    for n in range(1, 65):
+        probe = MuZeroTree(n_envs, A, n, device=DEV)
+        plan = probe.search_plan(whole_moves=True)
+        probe.close()
+        if plan['tree_in_lds'] and plan['lds_bytes'] > 65536:
+            n_sims = n
+            break
+    assert n_sims is not None, 'no simulation count keeps 16 three-action trees in LDS past 64 KB'
+    sp = whole_moves(AcrobotBatch(n_envs, DEV, seed=3), n_sims=n_sims, seed=9, temperature=1.0, moves_per_launch=2)
+    plan = sp.tree.search_plan(whole_moves=True)
+    print('trees in LDS past 64 KB: %d simulations, plan %r' % (n_sims, plan))
+    assert plan['games_per_workgroup'] == 16 and plan['tree_in_lds'] and plan['lds_bytes'] > 65536
+    assert not sp.tree.value_transform and not getattr(sp.net, 'value_transform', False)
+    sp.collect(2)
+    nodes, top = sp.tree.nodes()
+    ring, _ = sp.device_history()
+    n, vsum, vmin, vmax = (x.cpu().numpy().copy() for x in sp.tree.root_stats())
+    run = dict(n_sims=n_sims, discount=sp.discount, nodes=nodes, top=top, record=ring[:, 1].copy(), root_n=n, root_sum=vsum, vmin=vmin, vmax=vmax)
+    sp.tree.check()
+    sp.close()
+    assert (top == 1 + A * (n_sims + 1)).all() and (n == n_sims).all()
+    assert (ring[:, :2, D + 2:D + 2 + A].sum(axis=2) == n_sims).all()   # both moves' visit counts
+    for g in range(n_envs):
+        _replay(run, g)
 
 
 # ------------------------------------------------------------------ 2. the tree is the pseudocode's

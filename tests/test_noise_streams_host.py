@@ -54,7 +54,11 @@ def test_hashes_are_the_sources():
     assert [int(v) for v in ds.splitmix64(np.array(xs, dtype=np.uint64))] == [mix_py(x) for x in xs]
     assert [int(v) for v in ds.hash32(np.array([x & 0xFFFFFFFF for x in xs], dtype=np.uint64))] == [hash_py(x & 0xFFFFFFFF) for x in xs]
     # ... and the noise constants of the three copies of the mix and of the MuZero key are the ones restated here
-    muzero = open(os.path.join(csrc, 'rz_muzero.hip')).read()
+    # (the MuZero translation unit: the source and its family headers -- mz_gamma lies in rz_muzero_noise.h, the action draw's salt
+    # in the two kernels that draw a move; every count below is over the whole unit)
+    noise = open(os.path.join(csrc, 'rz_muzero_noise.h')).read()
+    muzero = ''.join(open(p).read() for p in [os.path.join(csrc, 'rz_muzero.hip')] + sorted(glob.glob(os.path.join(csrc, 'rz_muzero_*.h'))))
+    assert noise in muzero and 'float mz_gamma(float alpha, uint32_t key)' in noise
     assert tree.count('0x9E3779B9u * (uint32_t)(64 * j + lane + 1)') == 1
 
     def copies(name):
@@ -66,12 +70,13 @@ def test_hashes_are_the_sources():
     assert copies('rz_engine.hip') + sum(copies(p) for p in glob.glob(os.path.join(csrc, 'rz_engine_*.h'))) == 2
     rules = open(os.path.join(csrc, 'rz_mz_env.h')).read()   # (the MuZero key has one home, which both of its kernels call)
     assert rules.count('0x9E3779B9u * (uint32_t)(a + 1) + (uint32_t)key') == 1 and '0x9E3779B9u' not in muzero and '0xA5A5A5A5ull' in muzero
-    assert tree.count('key + 0x5bd1e995u') == 1 and muzero.count('key + 0x5bd1e995u') == 1
+    assert tree.count('key + 0x5bd1e995u') == 1 and muzero.count('key + 0x5bd1e995u') == 1 and noise.count('key + 0x5bd1e995u') == 1
+    assert '0xA5A5A5A5ull' in open(os.path.join(csrc, 'rz_muzero_search.h')).read() and '0xA5A5A5A5ull' in open(os.path.join(csrc, 'rz_muzero_moves.h')).read()
     # gamma03's constants are literals; its c lies 2.2e-6 below 1 / sqrt(9 d), and the restatement takes the literal
     assert 'const float d = 1.3f - 1.0f / 3.0f, c = %sf;' % ds.GAMMA03_C in tree
     exact = 1.0 / math.sqrt(9.0 * (1.3 - 1.0 / 3.0))
     assert 2.0e-6 < (exact - ds.GAMMA03_C) / exact < 2.4e-6
-    assert 'c = 1.0f / sqrtf(9.0f * d)' in muzero   # (mz_gamma computes its own)
+    assert 'c = 1.0f / sqrtf(9.0f * d)' in muzero and 'c = 1.0f / sqrtf(9.0f * d)' in noise   # (mz_gamma computes its own)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- schedules
