@@ -1,6 +1,6 @@
 // rz_host.h -- the host-side runtime the six translation units share (rz_engine, rz_net, rz_muzero, rz_replay, rz_mz_replay, rz_mz_learn): the error
 // message, the checks every entry point opens with, the check of a caller's buffer that kernels write, the two ways to own device memory
-// and the staging pair.  Host code only (rz_engine.hip and rz_net.hip keep their kernels in headers of their own): no kernel,
+// and the staging pair.  Host code only (every source keeps its kernels in headers of their own): no kernel,
 // nothing a kernel reads.  One copy of each, so that a new subsystem takes its plumbing from here instead of copying a neighbour's.
 #pragma once
 
@@ -53,11 +53,32 @@ __attribute__((format(printf, 2, 3))) inline int rz_fail(int code, const char *f
         if ((p) == nullptr) return rz_fail(RZ_ERR_ARG, "%s is NULL", #p);   \
     } while (0)
 
+// the host copy and the device copy of one argument (indices, draws): exactly one of the two is given
+#define RZ_ONE_OF(h, d)                                                                                   \
+    do {                                                                                                  \
+        if (((h) == nullptr) == ((d) == nullptr)) return rz_fail(RZ_ERR_ARG, "exactly one of %s / %s", #h, #d); \
+    } while (0)
+
+// the buffers a launch writes: none of them is NULL
+template <typename... T>
+int rz_outputs(const T *...p) {
+    if (((p == nullptr) || ...)) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
+    return RZ_OK;
+}
+
 // the calling thread works on `device` from here on
 inline int rz_on_device(int device) {
     int cur = -1;
     RZ_HIP(hipGetDevice(&cur));
     if (cur != device) RZ_HIP(hipSetDevice(device));
+    return RZ_OK;
+}
+
+// the creation of a handle on `device`: the ordinal names a device, and the calling thread works on it from here on
+inline int rz_claim_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
+    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
     return RZ_OK;
 }
 

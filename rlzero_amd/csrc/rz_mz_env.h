@@ -17,6 +17,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "rz_rng.h"
+
 #if defined(__HIPCC__)
 #define RZE_FN __host__ __device__ __forceinline__
 #else
@@ -31,19 +33,13 @@
 
 namespace rzmze {
 
-// splitmix64: the counter-based stream of rlzero_amd/muzero/cartpole.py
-RZE_FN uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// splitmix64: the counter-based stream of rlzero_amd/muzero/cartpole.py (rz_rng.h: mix64)
+RZE_FN uint64_t splitmix64(uint64_t x) { return rzrng::mix64(x); }
 // the key of an episode's initial state, (seed, environment, episode), and the uniform of its sub-key j + 1 in [0, 1)
 RZE_FN uint64_t reset_key(uint64_t seed, int env, long long episode) {
     return splitmix64(splitmix64(seed ^ ((uint64_t)env << 24)) ^ (uint64_t)episode);
 }
-RZE_FN double reset_uniform(uint64_t key, int j) { return (double)(splitmix64(key ^ (uint64_t)(j + 1)) >> 11) / 9007199254740992.0; }
+RZE_FN double reset_uniform(uint64_t key, int j) { return rzrng::unit(splitmix64(key ^ (uint64_t)(j + 1))); }
 
 // ------------------------------------------------------------------ CartPole-v1
 struct MzCartPole {
@@ -224,7 +220,7 @@ RZE_FN int move_weights(const int *visits, int A, double inv_temperature, double
 }
 // the cumulative search against the uniform of `key` (53 bits): the first action whose cumulative weight exceeds u * total
 RZE_FN int move_draw(const double *wgt, int A, double total, uint64_t key) {
-    const double target = ((double)(key >> 11) / 9007199254740992.0) * total;
+    const double target = rzrng::unit(key) * total;
     double cum = 0.0;
     for (int a = 0; a < A; ++a) {
         cum += wgt[a];

@@ -14,6 +14,16 @@
 // Bounds: every slot is reduced modulo the capacity, every length is clamped to 0 .. T where it is read, every step index is compared
 // with that length before a read, rows of a block are checked against its row count (on the host and again in the kernel), and an
 // index from the device is checked by the kernel before anything is read -- such an entry is not written and a flag is set.
+//
+// This file is the host side of ONE translation unit: the kernels lie in headers beside it, one per family, each of which compiles
+// alone (tests/test_csrc_headers.py) and describes its kernels where they are defined.
+//   rz_mz_replay_dev.h      no kernel: MzrDev, MzrOut, the launch shape and the flags, mzr_slot, mzr_length
+//   rz_mz_replay_store.h    the way in: k_mzr_add, k_mzr_ingest (mzr_store)
+//   rz_mz_replay_batch.h    the mini-batch: k_mzr_gather, k_mzr_sample (mzr_emit)
+//   rz_mz_replay_refresh.h  Reanalyse: k_mzr_positions, k_mzr_update
+//   rz_mz_replay_prio.h     prioritized replay: MzrPrio, k_mzr_mark, k_mzr_mark_where, k_mzr_prio, k_mzr_scan, k_mzr_draw_prio
+// The rules the kernels and the host share are plain C++ in rz_mz_target.h, the ring of episodes is rz_ring.h's; both are tested on
+// the CPU.  Below: struct rz_mz_replay, the entry table of an add, the argument checks and every extern "C" entry point.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -24,361 +34,19 @@
 #include "rlzero_hip.h"
 #include "rz_host.h"
 #include "rz_mz_target.h"
+#include "rz_ring.h"
 
-namespace {
-
-constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr int kFlagBadIndex = RZ_MZ_REPLAY_BAD_INDEX, kFlagBadRows = RZ_MZ_REPLAY_BAD_ROWS;
-constexpr int kEntryWords = 4;   // an entry of the table of k_mzr_add / k_mzr_ingest: length, first row, slot, flags (bit 0: final policy)
-
-struct MzrDev {
-    float *obs;           // [E][T][D]
-    int32_t *action;      // [E][T]
-    double *reward;       // [E][T]
-    double *root_value;   // [E][T]
-    float *policy;        // [E][T][A]
-    int32_t *length;      // [E]
-    const double *disc;   // [td + 1]: discount ** i, formed on the host
-    int32_t *err;
-    int E, T, D, A, K, td;
-};
-
-struct MzrOut {
-    float *obs;           // [n][D]
-    long long *actions;   // [n][K]
-    float *tv, *tr;       // [n][K + 1]
-    float *tp;            // [n][K + 1][A]
-    float *mask;          // [n][K + 1]
-};
-
-__device__ __forceinline__ int mzr_slot(const MzrDev &R, long long s) { return (int)(((s % R.E) + R.E) % R.E); }
-__device__ __forceinline__ int mzr_length(const MzrDev &R, int slot) { return min(max(R.length[slot], 0), R.T); }
-
-// Entry e of the table: its rows of `rows` [n_rows][D + 4 + A] into its slot.  A workgroup per entry, a wave per step row with the
-// lanes across the row (D + 4 + A <= 28 doubles: one coalesced read), each lane casting and storing its own column.
-__device__ __forceinline__ void mzr_store(const MzrDev &R, const int32_t *__restrict__ table, const double *__restrict__ rows, long long n_rows) {
-    const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int len = min(max(table[kEntryWords * e], 0), R.T);
-    const long long first = table[kEntryWords * e + 1];
-    const int slot = mzr_slot(R, table[kEntryWords * e + 2]);
-    const bool final_policy = (table[kEntryWords * e + 3] & 1) != 0;
-    if (first < 0 || first + len > n_rows) {   // (checked on the host too: nothing outside the block is read)
-        if (threadIdx.x == 0) atomicOr(R.err, kFlagBadRows);
-        return;
-    }
-    const int D = R.D, A = R.A, W = D + 4 + A;
-    for (int t = wave; t < len; t += kWaves) {
-        const double *row = rows + (first + t) * W;
-        const long long at = (long long)slot * R.T + t;
-        if (lane < D) {
-            R.obs[at * D + lane] = (float)row[lane];
-        } else if (lane == D) {
-            R.action[at] = (int32_t)row[lane];
-        } else if (lane == D + 1) {
-            R.reward[at] = row[lane];
-        } else if (lane < D + 2 + A) {
-            R.policy[at * A + (lane - D - 2)] = rzmzt::policy_of_row(row, D, A, lane - D - 2, final_policy);
-        } else if (lane == D + 2 + A) {
-            R.root_value[at] = row[lane];
-        }
-    }
-    if (threadIdx.x == 0) R.length[slot] = len;
-}
-
-__global__ __launch_bounds__(kThreads) void k_mzr_add(MzrDev R, const int32_t *__restrict__ table, const double *__restrict__ rows, long long n_rows) {
-    mzr_store(R, table, rows, n_rows);
-}
-
-// the same body, the rows read from the arena of a launch of rz_mz_play_cartpole (device memory: the records never leave the GPU)
-__global__ __launch_bounds__(kThreads) void k_mzr_ingest(MzrDev R, const int32_t *__restrict__ table, const double *__restrict__ arena,
-                                                          long long arena_rows) {
-    mzr_store(R, table, arena, arena_rows);
-}
-
-// row k of output entry b from position `pos` of the episode in `slot` (length `len`, 0 <= pos < len)
-// VT (here and in the two kernels below; rz_mz_replay_set_value_transform): tv and tr through value_h (rz_mz_target.h: unroll_row<VT>)
-template <bool VT>
-__device__ __forceinline__ void mzr_emit(const MzrDev &R, const MzrOut &O, long long b, int k, int slot, int len, int pos, long long filler) {
-    const long long base = (long long)slot * R.T;
-    const int K = R.K, A = R.A, D = R.D;
-    const rzmzt::Row r = rzmzt::unroll_row<VT>(R.reward + base, R.root_value + base, R.action + base, len, pos, k, R.td, R.disc, filler);
-    const long long o = b * (K + 1) + k;
-    O.tv[o] = r.value;
-    O.tr[o] = r.reward;
-    O.mask[o] = r.mask;
-    const float uniform = rzmzt::uniform_policy(A);
-    for (int a = 0; a < A; ++a) O.tp[o * A + a] = r.policy_step >= 0 ? R.policy[(base + r.policy_step) * A + a] : uniform;
-    if (k > 0) {
-        O.actions[b * K + (k - 1)] = r.action;
-    } else {
-        for (int d = 0; d < D; ++d) O.obs[b * D + d] = R.obs[(base + pos) * D + d];
-    }
-}
-
-// A thread per (entry, unroll step).  draws int64 [n][K + 2]: episode (0 = the oldest held), position, the K filler actions.
-template <bool VT = false>
-__global__ __launch_bounds__(kThreads) void k_mzr_gather(MzrDev R, MzrOut O, const long long *__restrict__ draws, long long oldest, long long count,
-                                                          long long n) {
-    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
-    const int K = R.K;
-    const long long b = tid / (K + 1);
-    const int k = (int)(tid % (K + 1));
-    if (b >= n) return;
-    const long long *dr = draws + b * (K + 2);
-    const long long ep = dr[0], pos = dr[1];
-    bool bad = ep < 0 || ep >= count;
-    int slot = 0, len = 0;
-    if (!bad) {
-        slot = mzr_slot(R, oldest + ep);
-        len = mzr_length(R, slot);
-        bad = pos < 0 || pos >= len;
-    }
-    for (int j = 0; j < K; ++j) bad = bad || dr[2 + j] < 0 || dr[2 + j] >= R.A;   // every thread of the entry comes to the same verdict
-    if (bad) {   // an index from the device: nothing of this entry is read or written
-        if (k == 0) atomicOr(R.err, kFlagBadIndex);
-        return;
-    }
-    mzr_emit<VT>(R, O, b, k, slot, len, (int)pos, k > 0 ? dr[2 + k - 1] : 0);
-}
-
-// The same rows with the draws made here: counter c = b (K + 2) + j of update `step` (rz_mz_target.h: draw) -- j = 0 the episode,
-// uniform over the episodes held; j = 1 the position, uniform over that episode's length; j = 2 + k the filler action of step k.
-template <bool VT = false>
-__global__ __launch_bounds__(kThreads) void k_mzr_sample(MzrDev R, MzrOut O, unsigned long long seed, unsigned long long step, long long oldest,
-                                                          long long count, long long n) {
-    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
-    const int K = R.K;
-    const long long b = tid / (K + 1);
-    const int k = (int)(tid % (K + 1));
-    if (b >= n) return;
-    const long long ep = rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 0), (uint64_t)count);
-    const int slot = mzr_slot(R, oldest + ep);
-    const int len = mzr_length(R, slot);
-    if (len == 0) {   // (an episode held is never empty)
-        if (k == 0) atomicOr(R.err, kFlagBadIndex);
-        return;
-    }
-    const int pos = (int)rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 1), (uint64_t)len);
-    const long long filler = k > 0 ? rzmzt::draw(seed, step, rzmzt::draw_counter((uint64_t)b, K, 2 + k - 1), (uint64_t)R.A) : 0;
-    mzr_emit<VT>(R, O, b, k, slot, len, pos, filler);
-}
-
-// Reanalyse, the way out: entry i resolved to a physical (slot, position) in `where` int32 [n][2] and its stored observation in
-// obs float32 [n][D].  A thread per (entry, observation element).  draws int64 [n][2] (episode, 0 = the oldest held; position), or
-// NULL: the draws of refresh `step` made here (rz_mz_target.h: reanalyse_draw).  An entry out of range: where = (-1, -1), a zeroed
-// row, the flag, and nothing of the store is read for it.
-__global__ __launch_bounds__(kThreads) void k_mzr_positions(MzrDev R, const long long *__restrict__ draws, unsigned long long seed,
-                                                             unsigned long long step, long long oldest, long long count, long long n,
-                                                             int32_t *__restrict__ where, float *__restrict__ obs) {
-    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
-    const int D = R.D;
-    const long long i = tid / D;
-    const int d = (int)(tid % D);
-    if (i >= n) return;
-    long long ep, pos = -1;
-    if (draws != nullptr) {
-        ep = draws[2 * i], pos = draws[2 * i + 1];
-    } else {
-        ep = rzmzt::reanalyse_draw(seed, step, (uint64_t)i, 0, (uint64_t)count);
-    }
-    bool bad = ep < 0 || ep >= count;
-    int slot = 0;
-    if (!bad) {
-        slot = mzr_slot(R, oldest + ep);
-        const int len = mzr_length(R, slot);
-        if (draws == nullptr && len > 0) pos = rzmzt::reanalyse_draw(seed, step, (uint64_t)i, 1, (uint64_t)len);
-        bad = pos < 0 || pos >= len;   // (len == 0 with draws made here: an episode held is never empty)
-    }
-    if (bad) {
-        if (d == 0) {
-            atomicOr(R.err, kFlagBadIndex);
-            where[2 * i] = -1, where[2 * i + 1] = -1;
-        }
-        obs[i * D + d] = 0.0f;
-        return;
-    }
-    if (d == 0) where[2 * i] = slot, where[2 * i + 1] = (int32_t)pos;
-    obs[i * D + d] = R.obs[((long long)slot * R.T + pos) * D + d];
-}
-
-// Reanalyse, the way back: the policy and the root value of step where[i] from the visit counts and the root's (N, value sum) of a
-// fresh search (rz_mz_target.h: policy_of_visits, root_value_of).  A thread per (entry, action) plus one for the value; nothing
-// else of the step is written.  `where` is checked again here -- slot against E, position against T and the slot's length -- and
-// an entry that fails (the (-1, -1) of a refused or padded row among them) writes nothing.
-__global__ __launch_bounds__(kThreads) void k_mzr_update(MzrDev R, const int32_t *__restrict__ where, long long n, const int32_t *__restrict__ visits,
-                                                          const int32_t *__restrict__ root_n, const double *__restrict__ root_sum) {
-    const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
-    const int A = R.A;
-    const long long i = tid / (A + 1);
-    const int a = (int)(tid % (A + 1));
-    if (i >= n) return;
-    const int slot = where[2 * i], pos = where[2 * i + 1];
-    if (slot < 0 || slot >= R.E || pos < 0 || pos >= R.T) return;
-    if (pos >= mzr_length(R, slot)) return;
-    const long long at = (long long)slot * R.T + pos;
-    if (a < A) {
-        R.policy[at * A + a] = rzmzt::policy_of_visits(visits + i * A, A, a);
-    } else {
-        R.root_value[at] = rzmzt::root_value_of(root_n[i], root_sum[i]);
-    }
-}
-
-// ---- Prioritized replay (ABI 37; the arithmetic and the draws: rz_mz_target.h).  Step t of a held episode weighs
-// w = priority_weight(|root value - n-step return|), an integer; cum[slot][t] is the inclusive prefix of w inside the episode,
-// mass[slot] its last entry, ecum[j] the inclusive prefix of the masses over the episodes held, oldest first, and *total the sum
-// of everything.  Integer sums: the scans below give the bits of a loop in any order.  dirty[slot] != 0: the slot was written
-// (k_mzr_add / k_mzr_ingest / k_mzr_update) since its prefix was formed.
-constexpr int kScanThreads = 1024, kScanWaves = kScanThreads / 64;
-
-struct MzrPrio {
-    uint64_t *cum;     // [E][T]
-    uint64_t *mass;    // [E] by slot
-    uint64_t *ecum;    // [E] by age: 0 = the oldest held
-    uint64_t *total;   // [1]
-    int32_t *dirty;    // [E] by slot
-};
-
-// the inclusive scan of v over the 64 lanes of a wave
-__device__ __forceinline__ uint64_t mzr_wave_scan(uint64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t below = (uint64_t)__shfl_up((unsigned long long)v, (unsigned)d, 64);
-        if (lane >= d) v += below;
-    }
-    return v;
-}
-
-// the slots first .. first + n - 1 (modulo E) were written
-__global__ __launch_bounds__(kThreads) void k_mzr_mark(MzrPrio P, int E, long long first, long long n) {
-    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n || i >= E) return;
-    P.dirty[(int)((first + i) % E)] = 1;
-}
-
-// the slots k_mzr_update wrote to: its own checks of `where`, entry by entry, and nothing but the mark of slot where[i].slot
-__global__ __launch_bounds__(kThreads) void k_mzr_mark_where(MzrDev R, MzrPrio P, const int32_t *__restrict__ where, long long n) {
-    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const int slot = where[2 * i], pos = where[2 * i + 1];
-    if (slot < 0 || slot >= R.E || pos < 0 || pos >= R.T) return;
-    if (pos >= mzr_length(R, slot)) return;
-    P.dirty[slot] = 1;
-}
-
-// A workgroup per held episode; one whose slot is clean returns at once.  Chunks of kThreads steps: each thread forms its step's
-// weight, a wave scan, the waves' sums through LDS, and the chunk's sum carried into the next chunk (any T).
-__global__ __launch_bounds__(kThreads) void k_mzr_prio(MzrDev R, MzrPrio P, long long oldest, long long count) {
-    __shared__ uint64_t wave_sum[kWaves];
-    if ((long long)blockIdx.x >= count) return;
-    const int slot = mzr_slot(R, oldest + blockIdx.x);
-    const int mark = P.dirty[slot];
-    __syncthreads();   // (every thread has read the mark before thread 0 clears it)
-    if (mark == 0) return;
-    const int len = mzr_length(R, slot), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)slot * R.T;
-    uint64_t carry = 0;
-    for (int first = 0; first < len; first += kThreads) {
-        const int t = first + (int)threadIdx.x;
-        const uint64_t w = t < len ? rzmzt::priority_weight(rzmzt::priority_of(R.reward + base, R.root_value + base, len, t, R.td, R.disc)) : 0;
-        uint64_t s = mzr_wave_scan(w, lane);
-        if (lane == 63) wave_sum[wave] = s;
-        __syncthreads();
-        uint64_t chunk = 0;
-#pragma unroll
-        for (int v = 0; v < kWaves; ++v) {
-            if (v < wave) s += wave_sum[v];
-            chunk += wave_sum[v];
-        }
-        if (t < len) P.cum[base + t] = carry + s;
-        carry += chunk;
-        __syncthreads();   // (wave_sum is read before the next chunk writes it)
-    }
-    if (threadIdx.x == 0) {
-        P.mass[slot] = carry;
-        P.dirty[slot] = 0;
-    }
-}
-
-// ONE workgroup: thread i sums the masses of the episodes i * per .. (i + 1) * per - 1 (by age), a scan of the partial sums over
-// the workgroup, and the run walked again to write its prefixes.
-__global__ __launch_bounds__(kScanThreads) void k_mzr_scan(MzrPrio P, int E, long long oldest, long long count) {
-    __shared__ uint64_t wave_sum[kScanWaves];
-    if (count > E) count = E;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long per = (count + kScanThreads - 1) / kScanThreads;
-    const long long from = min((long long)threadIdx.x * per, count), to = min(from + per, count);
-    uint64_t run = 0;
-    for (long long j = from; j < to; ++j) run += P.mass[(int)((oldest + j) % E)];
-    uint64_t s = mzr_wave_scan(run, lane);
-    if (lane == 63) wave_sum[wave] = s;
-    __syncthreads();
-    uint64_t all = 0;
-#pragma unroll
-    for (int v = 0; v < kScanWaves; ++v) {
-        if (v < wave) s += wave_sum[v];
-        all += wave_sum[v];
-    }
-    uint64_t at = s - run;   // the sum of everything before this thread's run
-    for (long long j = from; j < to; ++j) {
-        at += P.mass[(int)((oldest + j) % E)];
-        P.ecum[j] = at;
-    }
-    if (threadIdx.x == 0) *P.total = all;
-}
-
-// A thread per entry: ONE target g in 0 .. total - 1 -- from the entry's stream or from `targets` -- resolved by two searches,
-// the episode in ecum, the position in the episode's cum; the draw row (episode by age, position, K fillers) in the layout of
-// k_mzr_gather and the step's probability w / total.  A target out of range (or a table that does not hold it): the flag, a row
-// of -1 that k_mzr_gather refuses as well, and probability 0.
-__global__ __launch_bounds__(kThreads) void k_mzr_draw_prio(MzrDev R, MzrPrio P, unsigned long long seed, unsigned long long step,
-                                                             const long long *__restrict__ targets, long long oldest, long long count, long long n,
-                                                             long long *__restrict__ draws, double *__restrict__ prob) {
-    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const int K = R.K;
-    long long *dr = draws + i * (K + 2);
-    const uint64_t total = *P.total;
-    if (count > R.E) count = R.E;
-    bool bad = total == 0 || count <= 0;
-    uint64_t g = 0;
-    if (targets != nullptr) {
-        bad = bad || targets[i] < 0 || (uint64_t)targets[i] >= total;
-        g = (uint64_t)targets[i];
-    } else if (!bad) {
-        g = rzmzt::prio_target(seed, step, (uint64_t)i, K, total);
-    }
-    long long ep = 0, pos = 0;
-    uint64_t w = 0;
-    if (!bad) {
-        ep = rzmzt::upper_bound_u64(P.ecum, count, g);
-        bad = ep >= count;
-    }
-    if (!bad) {
-        const int slot = mzr_slot(R, oldest + ep);
-        const int len = mzr_length(R, slot);
-        const uint64_t *cum = P.cum + (long long)slot * R.T;
-        pos = rzmzt::upper_bound_u64(cum, len, g - (ep > 0 ? P.ecum[ep - 1] : 0));
-        bad = pos >= len;
-        if (!bad) w = cum[pos] - (pos > 0 ? cum[pos - 1] : 0);
-    }
-    if (bad) {
-        atomicOr(R.err, kFlagBadIndex);
-        for (int j = 0; j < K + 2; ++j) dr[j] = -1;
-        prob[i] = 0.0;
-        return;
-    }
-    dr[0] = ep, dr[1] = pos;
-    for (int k = 0; k < K; ++k) dr[2 + k] = rzmzt::prio_filler(seed, step, (uint64_t)i, K, k, (uint64_t)R.A);
-    prob[i] = (double)w / (double)total;
-}
-
-}  // namespace
+// (this order is the order of the kernels in the code object; the template instantiations follow in the order the code below names them)
+#include "rz_mz_replay_dev.h"
+#include "rz_mz_replay_store.h"
+#include "rz_mz_replay_batch.h"
+#include "rz_mz_replay_refresh.h"
+#include "rz_mz_replay_prio.h"
 
 struct rz_mz_replay {
     MzrDev dev = {};
     int device = 0;
-    long long cursor = 0, count = 0;   // next slot written; episodes held
-    long long stored = 0;              // episodes ever stored: the ticket of rz_mz_replay_positions / rz_mz_replay_update
+    rz_ring ring;   // of episodes; ring.stored is the ticket of rz_mz_replay_positions / rz_mz_replay_update
     std::vector<int32_t> lengths;      // [E] by slot: the host's copy of dev.length
     double *d_disc = nullptr;
     DevPool pool;    // the store
@@ -398,14 +66,11 @@ int mr_ready(rz_mz_replay *r) {
     return rz_on_device(r->device);
 }
 
-inline long long mr_oldest(const rz_mz_replay *r) { return ((r->cursor - r->count) % r->dev.E + r->dev.E) % r->dev.E; }
-
 // The entry table of `n` episodes (empty ones skipped; of more than the capacity only the last E get a slot) in `table`; -> the
 // number of entries, or a negative code.  first_rows NULL: the episodes lie one behind the other.  Every run of rows is checked
 // against n_rows here.
 int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t *h_flags, const int64_t *h_first_rows, int64_t n_rows,
              std::vector<int32_t> &table, long long *held) {
-    const long long E = r->dev.E;
     long long kept = 0, next = 0;
     for (int32_t i = 0; i < n; ++i) {
         if (h_lengths[i] < 0) return rz_fail(RZ_ERR_ARG, "an episode of negative length");
@@ -416,7 +81,7 @@ int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t
         next = first + h_lengths[i];
         kept += h_lengths[i] > 0;
     }
-    const long long skip = kept > E ? kept - E : 0;
+    const long long skip = r->ring.skip(kept);
     table.clear();
     long long t = 0;
     next = 0;
@@ -425,7 +90,7 @@ int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t
         next = first + h_lengths[i];
         if (h_lengths[i] == 0) continue;
         if (t >= skip) {
-            const int32_t entry[kEntryWords] = {h_lengths[i], (int32_t)first, (int32_t)((r->cursor + t) % E), h_flags ? h_flags[i] : 0};
+            const int32_t entry[kEntryWords] = {h_lengths[i], (int32_t)first, (int32_t)r->ring.slot(t), h_flags ? h_flags[i] : 0};
             table.insert(table.end(), entry, entry + kEntryWords);
         }
         ++t;
@@ -435,18 +100,13 @@ int mr_table(rz_mz_replay *r, int32_t n, const int32_t *h_lengths, const int32_t
 }
 
 void mr_commit(rz_mz_replay *r, const std::vector<int32_t> &table, long long kept) {
-    const long long E = r->dev.E;
     for (size_t e = 0; e < table.size() / kEntryWords; ++e) r->lengths[(size_t)table[kEntryWords * e + 2]] = table[kEntryWords * e];
-    r->cursor = (r->cursor + kept) % E;
-    r->count = r->count + kept > E ? E : r->count + kept;
-    r->stored += kept;
+    r->ring.commit(kept);
 }
 
 int mr_outputs(rz_mz_replay *r, int64_t n, const MzrOut &O) {
     if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
-    if (n > 0 && (O.obs == nullptr || O.actions == nullptr || O.tv == nullptr || O.tr == nullptr || O.tp == nullptr || O.mask == nullptr))
-        return rz_fail(RZ_ERR_ARG, "NULL output buffer");
-    return RZ_OK;
+    return n > 0 ? rz_outputs(O.obs, O.actions, O.tv, O.tr, O.tp, O.mask) : RZ_OK;
 }
 
 inline unsigned mr_blocks(const rz_mz_replay *r, int64_t n) { return (unsigned)((n * (r->dev.K + 1) + kThreads - 1) / kThreads); }
@@ -468,10 +128,10 @@ int mr_mark_table(rz_mz_replay *r, const std::vector<int32_t> &table, hipStream_
 
 // the prefixes of every slot written since they were last formed, then the prefix over the episodes: two launches on `s`
 int mr_refresh(rz_mz_replay *r, hipStream_t s) {
-    if (r->count > 0) {
-        const long long oldest = mr_oldest(r);
-        hipLaunchKernelGGL(k_mzr_prio, dim3((unsigned)r->count), dim3(kThreads), 0, s, r->dev, r->prio, oldest, r->count);
-        hipLaunchKernelGGL(k_mzr_scan, dim3(1), dim3(kScanThreads), 0, s, r->prio, r->dev.E, oldest, r->count);
+    if (r->ring.count > 0) {
+        const long long oldest = r->ring.oldest();
+        hipLaunchKernelGGL(k_mzr_prio, dim3((unsigned)r->ring.count), dim3(kThreads), 0, s, r->dev, r->prio, oldest, r->ring.count);
+        hipLaunchKernelGGL(k_mzr_scan, dim3(1), dim3(kScanThreads), 0, s, r->prio, r->dev.E, oldest, r->ring.count);
         RZ_TRY(rz_launched("k_mzr_prio / k_mzr_scan"));
     }
     r->prio_stale = false;
@@ -494,14 +154,13 @@ int rz_mz_replay_create(int32_t obs_dim, int32_t n_actions, int64_t capacity_epi
     if (capacity_episodes < 1 || capacity_episodes > (1LL << 22) || capacity_episodes * max_episode_steps > (1LL << 30))
         return rz_fail(RZ_ERR_ARG, "capacity_episodes outside 1 .. 2^22, or more than 2^30 steps in all");
     if (h_disc == nullptr) return rz_fail(RZ_ERR_ARG, "NULL discount table");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return rz_fail(RZ_ERR_ARG, "bad device ordinal");
-    if (hipSetDevice(device) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipSetDevice failed");
+    RZ_TRY(rz_claim_device(device));
     rz_mz_replay *r = new (std::nothrow) rz_mz_replay();
     if (!r) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     r->device = device;
     MzrDev &R = r->dev;
     R.E = (int)capacity_episodes, R.T = max_episode_steps, R.D = obs_dim, R.A = n_actions, R.K = unroll_steps, R.td = td_steps;
+    r->ring.capacity = R.E;
     r->lengths.assign((size_t)R.E, 0);
     const size_t steps = (size_t)R.E * R.T, n_disc = (size_t)td_steps + 1;
     const long long n_steps = (long long)steps;
@@ -539,12 +198,11 @@ int rz_mz_replay_destroy(rz_mz_replay *r) {
 
 int rz_mz_replay_state(rz_mz_replay *r, int64_t *count, int64_t *cursor, int64_t *capacity, int32_t *h_lengths) {
     if (r == nullptr) return rz_fail(RZ_ERR_ARG, "MuZero replay handle is NULL");
-    if (count) *count = r->count;
-    if (cursor) *cursor = r->cursor;
-    if (capacity) *capacity = r->dev.E;
+    if (count) *count = r->ring.count;
+    if (cursor) *cursor = r->ring.cursor;
+    if (capacity) *capacity = r->ring.capacity;
     if (h_lengths) {
-        const long long oldest = mr_oldest(r);
-        for (long long j = 0; j < r->count; ++j) h_lengths[j] = r->lengths[(size_t)((oldest + j) % r->dev.E)];
+        for (long long j = 0; j < r->ring.count; ++j) h_lengths[j] = r->lengths[(size_t)r->ring.window_start(j)];
     }
     return RZ_OK;
 }
@@ -611,18 +269,18 @@ int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *
     RZ_ENTER(mr_ready, r);
     const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
     RZ_TRY(mr_outputs(r, n, O));
-    if ((h_draws == nullptr) == (d_draws == nullptr)) return rz_fail(RZ_ERR_ARG, "exactly one of h_draws / d_draws");
+    RZ_ONE_OF(h_draws, d_draws);
     if (n == 0) return RZ_OK;
-    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (r->ring.count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
-    const long long oldest = mr_oldest(r);
+    const long long oldest = r->ring.oldest();
     const long long *draws = (const long long *)d_draws;
     const int K = r->dev.K;
     if (h_draws != nullptr) {
         for (int64_t i = 0; i < n; ++i) {
             const int64_t *dr = h_draws + i * (K + 2);
-            if (dr[0] < 0 || dr[0] >= r->count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
-            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
+            if (dr[0] < 0 || dr[0] >= r->ring.count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)r->ring.window_start(dr[0])]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
             for (int j = 0; j < K; ++j)
                 if (dr[2 + j] < 0 || dr[2 + j] >= r->dev.A) return rz_fail(RZ_ERR_ARG, "a filler action is outside 0 .. A-1");
         }
@@ -632,8 +290,8 @@ int rz_mz_replay_gather(rz_mz_replay *r, const int64_t *h_draws, const int64_t *
         RZ_TRY(r->stage.upload(bytes, s));
         draws = (const long long *)r->stage.d;
     }
-    if (r->value_transform) hipLaunchKernelGGL(k_mzr_gather<true>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
-    else hipLaunchKernelGGL(k_mzr_gather<false>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->count, (long long)n);
+    if (r->value_transform) hipLaunchKernelGGL(k_mzr_gather<true>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->ring.count, (long long)n);
+    else hipLaunchKernelGGL(k_mzr_gather<false>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, s, r->dev, O, draws, oldest, r->ring.count, (long long)n);
     return h_draws != nullptr ? r->stage.launched(s, "k_mzr_gather") : rz_launched("k_mzr_gather");
 }
 
@@ -642,14 +300,14 @@ int rz_mz_replay_sample(rz_mz_replay *r, uint64_t seed, uint64_t step, int64_t n
     RZ_ENTER(mr_ready, r);
     const MzrOut O = {d_obs, (long long *)d_actions, d_tv, d_tr, d_tp, d_mask};
     RZ_TRY(mr_outputs(r, n, O));
-    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (r->ring.count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     if (n == 0) return RZ_OK;
     if (r->value_transform)
         hipLaunchKernelGGL(k_mzr_sample<true>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
-                           (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
+                           (unsigned long long)step, r->ring.oldest(), r->ring.count, (long long)n);
     else
         hipLaunchKernelGGL(k_mzr_sample<false>, dim3(mr_blocks(r, n)), dim3(kThreads), 0, (hipStream_t)stream, r->dev, O, (unsigned long long)seed,
-                           (unsigned long long)step, mr_oldest(r), r->count, (long long)n);
+                           (unsigned long long)step, r->ring.oldest(), r->ring.count, (long long)n);
     return rz_launched("k_mzr_sample");
 }
 
@@ -666,18 +324,18 @@ int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_
     if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
     if (ticket == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     if (h_draws != nullptr && d_draws != nullptr) return rz_fail(RZ_ERR_ARG, "at most one of h_draws / d_draws");
-    *ticket = r->stored;
+    *ticket = r->ring.ticket();
     if (n == 0) return RZ_OK;
-    if (d_where == nullptr || d_obs == nullptr) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
-    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    RZ_TRY(rz_outputs(d_where, d_obs));
+    if (r->ring.count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     hipStream_t s = (hipStream_t)stream;
-    const long long oldest = mr_oldest(r);
+    const long long oldest = r->ring.oldest();
     const long long *draws = (const long long *)d_draws;
     if (h_draws != nullptr) {
         for (int64_t i = 0; i < n; ++i) {
             const int64_t *dr = h_draws + 2 * i;
-            if (dr[0] < 0 || dr[0] >= r->count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
-            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)((oldest + dr[0]) % r->dev.E)]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
+            if (dr[0] < 0 || dr[0] >= r->ring.count) return rz_fail(RZ_ERR_ARG, "an episode index is outside 0 .. count - 1");
+            if (dr[1] < 0 || dr[1] >= r->lengths[(size_t)r->ring.window_start(dr[0])]) return rz_fail(RZ_ERR_ARG, "a position is outside its episode");
         }
         const size_t bytes = (size_t)n * 2 * sizeof(int64_t);
         RZ_TRY(r->stage.reserve(bytes, s));
@@ -687,7 +345,7 @@ int rz_mz_replay_positions(rz_mz_replay *r, const int64_t *h_draws, const int64_
     }
     const unsigned blocks = (unsigned)((n * r->dev.D + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(k_mzr_positions, dim3(blocks), dim3(kThreads), 0, s, r->dev, draws, (unsigned long long)seed, (unsigned long long)step, oldest,
-                       r->count, (long long)n, d_where, d_obs);
+                       r->ring.count, (long long)n, d_where, d_obs);
     return h_draws != nullptr ? r->stage.launched(s, "k_mzr_positions") : rz_launched("k_mzr_positions");
 }
 
@@ -696,7 +354,7 @@ int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, cons
     RZ_ENTER(mr_ready, r);
     if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
     // an add or ingest since rz_mz_replay_positions may have given a slot to another episode: the search's result has no home
-    if (ticket != r->stored) return rz_fail(RZ_ERR_ARG, "stale ticket: episodes were stored since rz_mz_replay_positions");
+    if (!r->ring.ticket_current(ticket)) return rz_fail(RZ_ERR_ARG, "stale ticket: episodes were stored since rz_mz_replay_positions");
     if (n == 0) return RZ_OK;
     if (d_where == nullptr || d_visits == nullptr || d_root_n == nullptr || d_root_sum == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     const unsigned blocks = (unsigned)((n * (r->dev.A + 1) + kThreads - 1) / kThreads);
@@ -715,10 +373,10 @@ int rz_mz_replay_update(rz_mz_replay *r, const int32_t *d_where, int64_t n, cons
 int rz_mz_replay_read(rz_mz_replay *r, int64_t first, int64_t n, float *h_obs, int32_t *h_action, double *h_reward, double *h_root_value,
                       float *h_policy, int32_t *h_length, void *stream) {
     RZ_ENTER(mr_ready, r);
-    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    if (first < 0 || n < 0 || first + n > r->ring.count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
     hipStream_t s = (hipStream_t)stream;
     const MzrDev &R = r->dev;
-    const long long E = R.E, start = (mr_oldest(r) + first) % E;
+    const long long E = R.E, start = r->ring.window_start(first);
     const long long n1 = n < E - start ? n : E - start;   // up to the ring's end, then from its start
     const size_t T = (size_t)R.T, D = (size_t)R.D, A = (size_t)R.A;
     bool ok = true;
@@ -766,7 +424,7 @@ int rz_mz_replay_enable_priorities(rz_mz_replay *r, void *stream) {
     r->prio = P;
     r->prio_on = true;
     r->prio_stale = true;
-    return mr_mark(r, mr_oldest(r), r->count, s);   // every episode held
+    return mr_mark(r, r->ring.oldest(), r->ring.count, s);   // every episode held
 }
 
 int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream) {
@@ -778,12 +436,12 @@ int rz_mz_replay_refresh_priorities(rz_mz_replay *r, void *stream) {
 int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int64_t *h_w, int64_t *h_total, void *stream) {
     RZ_ENTER(mr_ready, r);
     if (!r->prio_on) return rz_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
-    if (first < 0 || n < 0 || first + n > r->count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
+    if (first < 0 || n < 0 || first + n > r->ring.count) return rz_fail(RZ_ERR_ARG, "episodes outside 0 .. count - 1");
     if (n > 0 && h_w == nullptr) return rz_fail(RZ_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
     RZ_TRY(mr_refresh(r, s));
     const MzrDev &R = r->dev;
-    const long long E = R.E, start = (mr_oldest(r) + first) % E;
+    const long long E = R.E, start = r->ring.window_start(first);
     const long long n1 = n < E - start ? n : E - start;   // up to the ring's end, then from its start
     const size_t T = (size_t)R.T;
     std::vector<uint64_t> cum((size_t)n * T);
@@ -797,7 +455,7 @@ int rz_mz_replay_read_priorities(rz_mz_replay *r, int64_t first, int64_t n, int6
     ok = ok && hipMemcpyAsync(&total, r->prio.total, sizeof(uint64_t), hipMemcpyDeviceToHost, s) == hipSuccess;
     if (!ok || hipStreamSynchronize(s) != hipSuccess) return rz_fail(RZ_ERR_HIP, "read-back failed (MuZero replay priorities)");
     for (int64_t j = 0; j < n; ++j) {
-        const int len = r->lengths[(size_t)((start + j) % E)];
+        const int len = r->lengths[(size_t)r->ring.window_start(first + j)];
         for (int t = 0; t < R.T; ++t)
             h_w[(size_t)j * T + t] = t < len ? (int64_t)(cum[(size_t)j * T + t] - (t > 0 ? cum[(size_t)j * T + t - 1] : 0)) : 0;
     }
@@ -810,15 +468,15 @@ int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step,
     RZ_ENTER(mr_ready, r);
     if (!r->prio_on) return rz_fail(RZ_ERR_ARG, "priorities are off (rz_mz_replay_enable_priorities)");
     if (n < 0 || n > (1LL << 24)) return rz_fail(RZ_ERR_ARG, "n outside 0 .. 2^24");
-    if (r->count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
+    if (r->ring.count == 0) return rz_fail(RZ_ERR_ARG, "the MuZero replay buffer is empty");
     if (n == 0) return RZ_OK;
-    if (d_draws == nullptr || d_prob == nullptr) return rz_fail(RZ_ERR_ARG, "NULL output buffer");
+    RZ_TRY(rz_outputs(d_draws, d_prob));
     hipStream_t s = (hipStream_t)stream;
     if (r->prio_stale) {
         RZ_TRY(mr_refresh(r, s));
     }
     hipLaunchKernelGGL(k_mzr_draw_prio, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, r->dev, r->prio, (unsigned long long)seed,
-                       (unsigned long long)step, (const long long *)d_targets, mr_oldest(r), r->count, (long long)n, (long long *)d_draws, d_prob);
+                       (unsigned long long)step, (const long long *)d_targets, r->ring.oldest(), r->ring.count, (long long)n, (long long *)d_draws, d_prob);
     return rz_launched("k_mzr_draw_prio");
 }
 

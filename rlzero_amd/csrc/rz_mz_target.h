@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "rz_mz_value.h"
+#include "rz_rng.h"
 
 #if defined(__HIPCC__)
 #define RZT_FN __host__ __device__ __forceinline__
@@ -25,20 +26,8 @@
 namespace rzmzt {
 
 // ---- the draws of k_mzr_sample (rlzero_amd/muzero/replay.py: mz_replay_draws, the same bits)
-RZT_FN uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-RZT_FN uint64_t mulhi64(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __umul64hi(a, b);
-#else
-    return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
+using rzrng::mix64;     // (rz_rng.h)
+using rzrng::mulhi64;
 
 constexpr uint64_t kSampleSalt = 0x6D7A7265706C6179ull;   // "mzreplay": the sampler's own stream, apart from rz_replay's
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "rlzero_hip.h"
+#include "rz_rng.h"
 
 #if defined(__HIPCC__)
 #define RZY_FN __host__ __device__ __forceinline__
@@ -17,15 +18,9 @@
 
 namespace rzplay {
 
-// ---- keyed values: 53 high bits of a splitmix64 chain (rlzero_amd/selfplay.py: the same bits)
-RZY_FN uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-RZY_FN double unit(uint64_t x) { return (double)(x >> 11) * (1.0 / 9007199254740992.0); }
+// ---- keyed values: 53 high bits of a splitmix64 chain (rz_rng.h; rlzero_amd/selfplay.py: the same bits)
+using rzrng::mix64;
+using rzrng::unit;
 
 constexpr uint64_t kResignSalt = 0x72657369676E0000ull;   // "resign": the calibration draw, apart from the move and noise streams
 constexpr uint64_t kCapSalt = 0x706C61796F757400ull;      // "playout": the budget draw's own stream

@@ -4,11 +4,14 @@
 // rlzero_amd/replay.py (pack_positions, reanalysed_pi, replay_reanalyse_draws) and the Gomoku environment
 // (tests/test_replay_reanalyse_host.py); the kernels call these functions.  Three rules: a stored record as a root of the search
 // engine, the pi row of fresh visit counts, the draws of a refresh -- and the ticket that ties a result to the store it was drawn from.
+// Beside the refresh's draws stand the mini-batch's own (replay_index: k_replay_sample; tests/test_rng_host.py).
 // For Connect4 (at the end; tests/test_replay_connect4_host.py against Connect4Env): the cell a dropped stone comes to rest in.
 #pragma once
 #include <stdint.h>
 
 #include "rlzero_hip.h"
+#include "rz_ring.h"
+#include "rz_rng.h"
 
 #if defined(__HIPCC__)
 #define RZR_FN __host__ __device__ __forceinline__
@@ -52,20 +55,8 @@ RZR_FN float pi_of_visits(int32_t n, int64_t sum) { return (float)((double)visit
 // the high half of x * positions_held for the 64-bit x of a splitmix64 chain over (seed ^ salt, step, i) -- uniform over POSITIONS
 // (the eight symmetries of a position share one pi row), within 2^-64.  The salt keeps a refresh and a mini-batch
 // (rz_replay_sample: "replay") of one update number apart.
-RZR_FN uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-RZR_FN uint64_t mulhi64(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __umul64hi(a, b);
-#else
-    return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
+using rzrng::mix64;     // (rz_rng.h)
+using rzrng::mulhi64;
 
 constexpr uint64_t kReanalyseSalt = 0x617A7265616E616Cull;   // "azreanal"
 
@@ -76,6 +67,18 @@ RZR_FN int64_t reanalyse_position(uint64_t seed, uint64_t step, uint64_t i, uint
     return (int64_t)mulhi64(x, positions_held);
 }
 
+// ---- the draws of a mini-batch (k_replay_sample; rlzero_amd/replay.py: replay_index, replay_indices, the same bits): entry i of
+// update `step` is the high half of x * n_entries (integer only; a value's probability is floor or ceil of 2^64 / n over 2^64, i.e.
+// within 2^-64 of 1 / n) -- uniform over ENTRIES, a position under one of its symmetries.
+constexpr uint64_t kReplaySalt = 0x7265706C61790000ull;   // "replay": the sampler's own stream
+
+RZR_FN int64_t replay_index(uint64_t seed, uint64_t step, uint64_t i, uint64_t n_entries) {
+    uint64_t x = mix64(seed ^ kReplaySalt);
+    x = mix64(x ^ step);
+    x = mix64(x ^ i);
+    return (int64_t)mulhi64(x, n_entries);
+}
+
 // ---- a position index (0 = the oldest held) to its ring slot, or -1 for an index outside 0 .. count - 1
 RZR_FN int64_t slot_of_position(int64_t index, int64_t oldest, int64_t count, int64_t capacity) {
     if (index < 0 || index >= count) return -1;
@@ -84,8 +87,13 @@ RZR_FN int64_t slot_of_position(int64_t index, int64_t oldest, int64_t count, in
 
 // ---- the ticket: the number of positions EVER stored in the handle when rz_replay_positions resolved a request.  A count, not the
 // write cursor: the cursor returns to the same slot after `capacity` positions, the count never does.  A result may be written
-// only while nothing was stored in between -- a slot may hold another position by then.
-RZR_FN bool ticket_current(int64_t ticket, int64_t stored) { return ticket == stored; }
+// only while nothing was stored in between -- a slot may hold another position by then.  (The store's own check is its ring's,
+// rz_ring.h; this forwarder is the host test's way in.)
+inline bool ticket_current(int64_t ticket, int64_t stored) {
+    rz_ring ring;
+    ring.stored = stored;
+    return ring.ticket_current(ticket);
+}
 
 // ---- the value target (rz_replay_set_value_mix; rlzero_amd/replay.py: mixed_value_targets, the same bits): z of the game mixed
 // with the search's root value q of the position, (1 - lam) z + lam q.  In fp64, each product ROUNDED before the sum -- this file is

@@ -13,19 +13,10 @@ import os
 
 import numpy as np
 
+from .._rng import MASK as _M64, mix64 as _mix64
 from ..engine import MCTSEngine, RolloutEvaluator, int_to_bits
 from .alphazero_mcts import TreeNodeView, _bitboards_of
 from .player import Player
-
-_M64 = (1 << 64) - 1
-
-
-def _mix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    z = x
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
 
 
 def rollout_pick(seed, game, sim, ply, k):

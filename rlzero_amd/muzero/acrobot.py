@@ -13,7 +13,7 @@ import ctypes
 
 import numpy as np
 
-from .cartpole import _splitmix64
+from .._rng import mix64_u64 as _splitmix64
 
 MAX_EPISODE_STEPS = 500
 

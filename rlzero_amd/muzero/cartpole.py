@@ -10,20 +10,14 @@ import math
 
 import numpy as np
 
+from .._rng import mix64_u64 as _splitmix64
+
 GRAVITY, MASSCART, MASSPOLE, LENGTH, FORCE_MAG, TAU = 9.8, 1.0, 0.1, 0.5, 10.0, 0.02
 TOTAL_MASS = MASSPOLE + MASSCART
 POLEMASS_LENGTH = MASSPOLE * LENGTH
 THETA_THRESHOLD = 12 * 2 * math.pi / 360
 X_THRESHOLD = 2.4
 MAX_EPISODE_STEPS = 500
-
-
-def _splitmix64(x):
-    x = (x + np.uint64(0x9E3779B97F4A7C15)) & np.uint64(0xFFFFFFFFFFFFFFFF)
-    z = x
-    z = ((z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)) & np.uint64(0xFFFFFFFFFFFFFFFF)
-    z = ((z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)) & np.uint64(0xFFFFFFFFFFFFFFFF)
-    return z ^ (z >> np.uint64(31))
 
 
 def initial_states(seed, env_ids, episodes):

@@ -24,7 +24,7 @@ comes between them a slot may hold another episode by then, and the call raises 
 import numpy as np
 
 from .._hip import MZ_REPLAY_BAD_INDEX, HipError
-from .replay import _MASK, _sm
+from .._rng import MASK as _MASK, mix64 as _sm
 
 _REANALYSE_SALT = 0x6D7A7265616E616C   # "mzreanal" (csrc/rz_mz_target.h: kReanalyseSalt)
 _MAX_REQUEST = 1 << 20                 # entries resolved by one ``positions`` launch (its staging copy: 16 bytes each)

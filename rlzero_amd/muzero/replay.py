@@ -38,20 +38,12 @@ import numpy as np
 
 from .. import _hip
 from .._hip import HipError
+from .._rng import MASK as _MASK, mix64 as _sm
 
-_MASK = (1 << 64) - 1
 _SAMPLE_SALT = 0x6D7A7265706C6179   # "mzreplay" (csrc/rz_mz_target.h: kSampleSalt)
 _PRIO_SALT = 0x6D7A7072696F7269     # "mzpriori" (csrc/rz_mz_target.h: kPrioSalt)
 MAX_OBS, MAX_ACTIONS, MAX_UNROLL, MAX_TD = 16, 8, 16, 64
 FINAL_POLICY = 1                    # rz_mz_replay_add's flag: the visit columns of the episode's rows hold the float32 policy
-
-
-def _sm(x):
-    x = (x + 0x9E3779B97F4A7C15) & _MASK
-    z = x
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
-    return z ^ (z >> 31)
 
 
 def mz_replay_draws(seed, step, n, lengths, K, A):

@@ -65,9 +65,8 @@ import numpy as np
 
 from . import _hip
 from ._hip import HipError
-from .selfplay import _splitmix64
+from ._rng import MASK as _MASK, mix64 as _mix64, mix64_u64 as _splitmix64
 
-_MASK = (1 << 64) - 1
 _REPLAY_SALT = np.uint64(0x7265706C61790000)   # ("replay": the sampler's own stream, apart from the move / noise / cap draws)
 META_PARITY_BIT, META_Z_SHIFT = 9, 10          # the meta word: bits 0..8 last move + 1 (0: none), bit 9 ply parity, bits 10..11 z + 1
 
@@ -129,18 +128,12 @@ def replay_indices(seed, step, n, n_entries):
 
 def replay_index(seed, step, i, n_entries):
     """Entry ``i`` of update ``step`` (replay_indices, one value, in Python integers)."""
-    def sm(x):
-        x = (x + 0x9E3779B97F4A7C15) & _MASK
-        z = x
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
-        return z ^ (z >> 31)
     n_entries = int(n_entries)
     if n_entries <= 0:
         raise ValueError('n_entries %d must be positive' % n_entries)
-    x = sm((int(seed) & _MASK) ^ int(_REPLAY_SALT))
-    x = sm(x ^ (int(step) & _MASK))
-    x = sm(x ^ (int(i) & _MASK))
+    x = _mix64((int(seed) & _MASK) ^ int(_REPLAY_SALT))
+    x = _mix64(x ^ (int(step) & _MASK))
+    x = _mix64(x ^ (int(i) & _MASK))
     return (x * n_entries) >> 64
 
 
@@ -156,15 +149,8 @@ def replay_reanalyse_draws(seed, step, n, positions):
     positions = int(positions)
     if positions <= 0:
         raise ValueError('draws need at least one position')
-
-    def sm(x):
-        x = (x + 0x9E3779B97F4A7C15) & _MASK
-        z = x
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
-        return z ^ (z >> 31)
-    base = sm(sm((int(seed) & _MASK) ^ _REANALYSE_SALT) ^ (int(step) & _MASK))
-    return np.array([(sm(base ^ (i & _MASK)) * positions) >> 64 for i in range(int(n))], dtype=np.int64).reshape(-1)
+    base = _mix64(_mix64((int(seed) & _MASK) ^ _REANALYSE_SALT) ^ (int(step) & _MASK))
+    return np.array([(_mix64(base ^ (i & _MASK)) * positions) >> 64 for i in range(int(n))], dtype=np.int64).reshape(-1)
 
 
 def reanalysed_pi(visits):

@@ -25,18 +25,9 @@ import numpy as np
 from . import playlog
 from . import route as _route
 from ._hip import PLAY_FULL, HipError
+from ._rng import mix64_u64 as _splitmix64
 from .playlog import SlotBook
 from .route import fc_in_trunk_pays   # noqa: F401  (a board rule: route.py; importable from here as before)
-
-_MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-def _splitmix64(x):
-    x = (x + np.uint64(0x9E3779B97F4A7C15)) & _MASK
-    z = x
-    z = ((z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)) & _MASK
-    z = ((z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)) & _MASK
-    return z ^ (z >> np.uint64(31))
 
 
 def move_uniform(seed, game_id, ply):

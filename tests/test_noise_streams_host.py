@@ -17,13 +17,14 @@ N_PAIRS = 1 << 18
 
 # ---------------------------------------------------------------------------------------------------------------------- hashes
 def test_hashes_are_the_sources():
-    """mix64 against rz_play.h (the constants are read out of the header, the function evaluated with Python integers), hash32 against
-    rz_tree.h, splitmix64 = mix64 (one definition, two names on the device)."""
+    """mix64 against rz_rng.h, which rz_play.h names as rzplay::mix64 (the constants are read out of the header, the function evaluated
+    with Python integers), hash32 against rz_tree.h, splitmix64 = mix64 (one definition, two names on the device)."""
     import glob
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'rlzero_amd', 'csrc')
-    play = open(os.path.join(csrc, 'rz_play.h')).read()
+    assert 'using rzrng::mix64;' in open(os.path.join(csrc, 'rz_play.h')).read()
+    play = open(os.path.join(csrc, 'rz_rng.h')).read()
     body = play[play.index('uint64_t mix64(uint64_t x)'):]
     body = body[:body.index('}')]
     inc, m1, m2 = (int(c, 16) for c in re.findall(r'0x([0-9A-Fa-f]{16})ull', body))

@@ -152,6 +152,9 @@ def test_the_library_is_built_without_contraction():
     assert '-ffp-contract=off' in _build.FLAGS
     with open(os.path.join(CSRC, 'rz_replay.hip')) as f:
         text = f.read()
+    assert '#include "rz_replay_rules.h"' in text and '#include "rz_replay_dev.h"' in text
+    with open(os.path.join(CSRC, 'rz_replay_dev.h')) as f:   # (replay_emit, which both mini-batch kernels of rz_replay.hip write through)
+        text = f.read()
     assert '#include "rz_replay_rules.h"' in text and 'rzrr::value_target' in text
     with open(os.path.join(CSRC, 'rz_engine_play.h')) as f:
         assert 'ry::root_value' in f.read()
