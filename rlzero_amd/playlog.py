@@ -99,12 +99,34 @@ def counter(name):
     return property(lambda self: getattr(self.book, name), lambda self, value: setattr(self.book, name, value))
 
 
+class Plies(object):
+    """A read-only view ``v`` of a book's column (None: the moves): ``v[slot]`` is the entries of the plies of the slot's game -- of its
+    last one until the slot starts another --, a list (``as_list``) or an array, sliced when asked for; two views are equal when
+    every slot's entries are -- exactly: meant for the moves -- and, mutable, a view has no hash."""
+
+    def __init__(self, book, column, as_list=False):
+        self.book, self.column, self.as_list = book, column, as_list
+
+    def __len__(self):
+        return len(self.book.slot_ply)
+
+    def __getitem__(self, slot):
+        rows = (self.book.moves if self.column is None else self.book.buf[self.column])[slot, :self.book.slot_ply[slot]]
+        return rows.tolist() if self.as_list else rows
+
+    def __eq__(self, other):
+        if not hasattr(other, '__len__'):
+            return NotImplemented
+        return len(self) == len(other) and all(np.array_equal(self[s], other[s]) for s in range(len(self)))
+
+
 class SlotBook(object):
     """Which game and ply every slot is at, what its plies logged, and the stalls the host has decided.
 
     ``columns``: {name: (dtype, shape of one entry, 'move' | 'search')} -- what to keep per ply beside the move: a 'move' column of every
     move played, a 'search' column of every SEARCHED record (the stalled one and the resigning one included: a resigned game has ``ply``
-    moves and ``ply + 1`` searches).  ``resolve(slot, move)`` hands a stalled slot's move back to the device."""
+    moves and ``ply + 1`` searches).  ``resolve(slot, move)`` hands a stalled slot's move back to the device.
+    Two ways in: ``feed`` for the records of a log, ``start`` / ``put_search`` / ``put_moves`` / ``close`` for an owner that has the moves."""
 
     def __init__(self, n_slots, max_plies, resolve, columns):
         self.resolve = resolve
@@ -142,7 +164,45 @@ class SlotBook(object):
             raise HipError('slot %d: the log says game %d ply %d, the host expected game %d ply %d' % (
                 slot, game, ply, self.slot_game[slot], self.slot_ply[slot]))
 
-    def _close(self, slot, game, plies, searched, winner, resigned):
+    # The direct writer.  ``slots`` / ``plies``: one slot or an array of distinct ones, and the ply the CALLER counts each to be at: a
+    # caller out of step with the book -- an idle slot, a ply written twice, a count kept elsewhere -- is refused before anything is
+    # written (SelfPlayReader reads its plies from the book: there the idle half is the one at work).
+    def _here(self, slots, plies):
+        bad = np.atleast_1d((self.slot_game[slots] < 0) | (self.slot_ply[slots] != plies))
+        if bad.any():
+            i = np.nonzero(bad)[0][0]
+            s, p = int(np.atleast_1d(slots)[i]), int(np.atleast_1d(plies)[i])
+            raise HipError('slot %d: a write at ply %d, the book has game %d at ply %d' % (s, p, self.slot_game[s], self.slot_ply[s]))
+
+    def start(self, slot, game):
+        """``slot`` begins ``game`` at ply 0 (``started`` counts the ids taken from the device's queue: feed's alone)."""
+        self.slot_game[slot], self.slot_ply[slot] = game, 0
+
+    def put_search(self, slots, plies, values, check=True):
+        """The 'search' columns ({name: one entry per slot, or one for all}) of the searches before the slots' plies (``check``
+        False: feed's records, held against the log by feed itself)."""
+        if check:
+            self._here(slots, plies)
+        for name in self.search_cols:
+            self.buf[name][slots, plies] = values[name]
+
+    def put_moves(self, slots, plies, moves, values, check=True):
+        """One move per slot with its 'move' columns ({name: one entry per slot}); the slots are a ply further."""
+        if check:
+            self._here(slots, plies)
+        self.moves[slots, plies] = moves
+        for name in self.move_cols:
+            self.buf[name][slots, plies] = values[name]
+        self.slot_ply[slots] += 1
+        self.moves_done += int(np.size(slots))
+
+    def close(self, slot, winner, resigned):
+        """The slot's game has ended, ``resigned``: by the resignation of the player to move, after one search more than moves ->
+        Finished, each column copied up to its own length; the slot is idle."""
+        game, plies = int(self.slot_game[slot]), int(self.slot_ply[slot])
+        if game < 0:
+            raise HipError('slot %d holds no game to close' % slot)
+        searched = plies + (1 if resigned else 0)
         self.slot_game[slot] = -1
         cols = dict((name, self.buf[name][slot, :plies].copy()) for name in self.move_cols)
         cols.update((name, self.buf[name][slot, :searched].copy()) for name in self.search_cols)
@@ -155,6 +215,9 @@ class SlotBook(object):
         flags, gids, plies = d.flags, d.game, d.ply
         special = ((flags & (PLAY_STALLED | PLAY_RESOLVED | PLAY_RESIGNED | PLAY_ENDED)) != 0) | (plies == 0)
         done = []
+
+        def pick(cols, at):
+            return dict((name, values[name][at]) for name in cols)
         first = [0] + (np.nonzero(slots[1:] <= slots[:-1])[0] + 1).tolist() + [len(slots)]
         for a, b in zip(first[:-1], first[1:]):
             easy = np.nonzero(~special[a:b])[0] + a
@@ -164,16 +227,12 @@ class SlotBook(object):
                 if bad.any():
                     i = easy[np.nonzero(bad)[0][0]]
                     self._expect(slots[i], gids[i], plies[i])
-                self.moves[s, p] = d.move[easy]
-                for name, buf in self.buf.items():
-                    buf[s, p] = values[name][easy]
-                self.slot_ply[s] += 1
-                self.moves_done += int(easy.size)
+                self.put_search(s, p, pick(self.search_cols, easy), check=False)
+                self.put_moves(s, p, d.move[easy], pick(self.move_cols, easy), check=False)
             for i in np.nonzero(special[a:b])[0] + a:
                 s, f, gid, ply, mv = int(slots[i]), int(flags[i]), int(gids[i]), int(plies[i]), int(d.move[i])
                 if f & PLAY_SEARCHED:   # (a stall's searched record comes before the resolved one of its ply)
-                    for name in self.search_cols:
-                        self.buf[name][s, ply] = values[name][i]
+                    self.put_search(s, ply, pick(self.search_cols, i), check=False)
                 if f & PLAY_STALLED:
                     known = self.stalls.get(s)
                     if known is None or known[:2] != (gid, ply):   # first sight of this stall: decide, hand the move back
@@ -189,17 +248,13 @@ class SlotBook(object):
                     played = known[3]
                     self.stalls_resolved += 1
                 if ply == 0:   # the slot has started this game
-                    self.slot_game[s], self.slot_ply[s] = gid, 0
+                    self.start(s, gid)
                     self.started += 1
                 self._expect(s, gid, ply)
                 if f & PLAY_RESIGNED:   # the game ends without a move: the plies before it
-                    done.append(self._close(s, gid, ply, ply + 1, int(d.winner[i]), True))
+                    done.append(self.close(s, int(d.winner[i]), True))
                     continue
-                self.moves[s, ply] = mv
-                for name in self.move_cols:
-                    self.buf[name][s, ply] = values[name][i] if played is None else played[name]
-                self.slot_ply[s] += 1
-                self.moves_done += 1
+                self.put_moves(s, ply, mv, pick(self.move_cols, i) if played is None else played, check=False)
                 if f & PLAY_ENDED:
-                    done.append(self._close(s, gid, ply + 1, ply + 1, int(d.winner[i]), False))
+                    done.append(self.close(s, int(d.winner[i]), False))
         return done

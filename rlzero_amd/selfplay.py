@@ -488,6 +488,9 @@ class SelfPlayReader(object):
         self.root_values_on = False   # set_root_values: the side ring of the log is read and Trajectory.root_values formed
         self.forced_k, self.forced_prune = 0.0, True   # set_forced_playouts: k (0: off), and whether pis come from the pruned counts
         self.slot_game, self.slot_ply = self.book.slot_game, self.book.slot_ply
+        # the plies of a slot's game (of its last one until it starts another), read-only: moves (a list), pis, root values
+        self.slot_moves, self.slot_pis, self.slot_values = (
+            playlog.Plies(self.book, None, as_list=True), playlog.Plies(self.book, 'pi'), playlog.Plies(self.book, 'q'))
         self.sims_done = 0
         self.resign_threshold, self.resign_disabled_frac = float('nan'), 0.0
         self.resign_would = 0   # plies of calibration games where the rule fired (RZ_PLAY_WOULD_RESIGN on the device)
@@ -608,29 +611,72 @@ class SelfPlayReader(object):
             columns['pi'] = self._pis_moves(np.where(d.legal, pr, 0), d.legal, d.ply, move_uniform(self.seed, d.game, d.ply))[0]
         if forced:
             columns['raw'] = d.counts.astype(np.int32)
-        finished = self.book.feed(lo + g_i, d, chosen, columns)
         done = []
-        for f in finished:
+        for f in self.book.feed(lo + g_i, d, chosen, columns):
             eps = f.columns['ep']
-            span = [None] if row_epochs is None else self.epochs[int(eps[0]):int(eps[-1]) + 1]
-            calib = not f.resigned
-            for epoch in span:   # (a calibration game: one in every epoch it spans)
-                with self._under(epoch):
-                    calib = calib and self.resign_on and bool(self._calibration(f.game))
-            with self._under(span[-1]):
-                extra = self._resign_record(f.columns['stat'], f.winner, calib, f.resigned)
-            caps = [self.playout_cap if epoch is None else epoch.playout_cap for epoch in span]
-            if any(c is not None for c in caps):
-                extra['full'] = f.columns['full']
-            if self.root_values_on:   # (a resigned game has one search more than moves: the resigning one is not recorded)
-                extra['root_values'] = f.columns['q'][:len(f.moves)]
-            if row_epochs is not None:
-                extra['epochs'] = eps[:len(f.moves)]
-            if forced:
-                extra['raw_visits'] = f.columns['raw']
-            done.append(Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
-                                   game=self.geometry[2], **extra))
+            done.append(self.trajectory(f, [None] if row_epochs is None else self.epochs[int(eps[0]):int(eps[-1]) + 1]))
         return done, last_running
+
+    def trajectory(self, f, span=(None, )):
+        """A game the book has closed (playlog.Finished) -> its Trajectory.  ``span``: the epochs of its searches, oldest first (a
+        stream); (None, ) outside one: the settings as they are."""
+        calib = not f.resigned
+        for epoch in span:   # (a calibration game: one in every epoch it spans)
+            with self._under(epoch):
+                calib = calib and self.resign_on and bool(self._calibration(f.game))
+        with self._under(span[-1]):
+            extra = self._resign_record(f.columns['stat'], f.winner, calib, f.resigned)
+        caps = [self.playout_cap if epoch is None else epoch.playout_cap for epoch in span]
+        if any(c is not None for c in caps):
+            extra['full'] = f.columns['full']
+        if self.root_values_on:   # (a resigned game has one search more than moves: the resigning one is not recorded)
+            extra['root_values'] = f.columns['q'][:len(f.moves)]
+        if span[0] is not None:
+            extra['epochs'] = f.columns['ep'][:len(f.moves)]
+        if self.forced_k > 0.0:
+            extra['raw_visits'] = f.columns['raw']
+        return Trajectory(f.game, self.geometry[0], self.geometry[1], f.moves.tolist(), f.columns['pi'], f.winner,
+                          game=self.geometry[2], **extra)
+
+    def decide_and_record(self, slots, visits, legal, values=None, pruned=None):
+        """The move step of the host-driven loop, for running ``slots`` (distinct) after their searches: ``visits`` int [n, A] the
+        roots' counts, ``legal`` bool [n, A], ``values`` fp64 [n, 2] = (v_root, q_best) of MCTSEngine.root_values (required under
+        resignation or root values), ``pruned`` int [n, A] the pruned counts (required under policy target pruning) -> (the move of
+        every slot, -1 where its mover resigns; bool per slot: resigned).  The rules of k_play_draw on the same numbers; the book and
+        the counters take the searches and the moves, the caller ends the games (``book.close`` -> ``trajectory``)."""
+        slots = np.asarray(slots, dtype=np.int64)
+        n = len(slots)
+        if n == 0:   # (a lane whose slots are all idle: nothing was fetched for it, nothing is decided)
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+        if (self.resign_on or self.root_values_on) and values is None:
+            raise ValueError('resignation or root values are on: decide_and_record needs the roots\' values')
+        if self.forced_k > 0.0 and self.forced_prune and pruned is None:
+            raise ValueError('policy target pruning is on (set_forced_playouts): decide_and_record needs the pruned counts')
+        gids, plies = self.slot_game[slots], self.slot_ply[slots]
+        full = np.ones(n, dtype=bool) if self.playout_cap is None else self._full(gids, plies)
+        self.sims_done += self.n_playout * n if self.playout_cap is None else int(np.where(full, self.n_playout, self.playout_cap[0]).sum())
+        self.full_plies += int(full.sum())
+        stat, quit_ = np.float32(np.nan), np.zeros(n, dtype=bool)
+        if self.resign_on:   # the mover resigns when v_root and q_best are both below the threshold, except in a calibration game
+            stat = np.maximum(values[:, 0], values[:, 1]).astype(np.float32)   # (NaN when either is)
+            fire = (values[:, 0] < self.resign_threshold) & (values[:, 1] < self.resign_threshold)
+            calib = self._calibration(gids)
+            self.resign_would += int((fire & calib).sum())
+            quit_ = fire & ~calib
+        q = values[:, 0].astype(np.float32) if self.root_values_on else np.float32(np.nan)   # (k_play_draw's float32 of the same fp64 value)
+        self.book.put_search(slots, plies, dict(stat=stat, full=full, q=q, ep=0))
+        moves = np.full(n, -1, dtype=np.int64)
+        on = ~quit_
+        if on.any():
+            us = move_uniform(self.seed, gids[on], plies[on])
+            pis, moves[on] = self._pis_moves(visits[on], legal[on], plies[on], us)
+            cols = dict(pi=pis)
+            if self.forced_k > 0.0:   # the move from the raw counts, as ever; the stored pi from the pruned ones
+                cols['raw'] = visits[on].astype(np.int32)
+                if self.forced_prune:
+                    cols['pi'] = self._pis_moves(np.where(legal[on], pruned[on], 0), legal[on], plies[on], us)[0]
+            self.book.put_moves(slots[on], plies[on], moves[on], cols)
+        return moves, quit_
 
 
 class _Lane(object):
@@ -692,13 +738,7 @@ class BatchedSelfPlay(SelfPlayReader):
         self.eager_every = int(eager_every)  # with graphs: every k-th chunk runs eagerly (timing samples)
         G = self.n_slots
         self.cell_taken = np.zeros((G, self.eng.n_cells), dtype=bool)  # host mirror of the root boards
-        self.slot_moves = [[] for _ in range(G)]
-        self.slot_pis = [[] for _ in range(G)]
-        self.slot_stats = [[] for _ in range(G)]   # resignation statistic of every search of the slot's game (set_resign)
         self.cap_longest_first = True   # workgroups of k_delta_res take the full-budget games first (both loops; read at device_attach)
-        self.slot_full = [[] for _ in range(G)]   # budget flag of every search of the slot's game (set_playout_cap)
-        self.slot_values = [[] for _ in range(G)]   # root value of every search that played a ply of the slot's game (set_root_values)
-        self.slot_raw = [[] for _ in range(G)]   # raw visit counts of every ply of the slot's game (set_forced_playouts)
 
     def set_forced_playouts(self, k=2.0, prune=True):
         """Forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2; an opt-in extension of score_mode 'puct') for every
@@ -1020,15 +1060,8 @@ class BatchedSelfPlay(SelfPlayReader):
         mask = np.zeros(self.n_slots, dtype=np.uint8)
         for s, g in zip(slots, game_ids):
             mask[s] = 1
-            self.slot_game[s] = g
-            self.slot_ply[s] = 0
+            self.book.start(s, g)
             self.cell_taken[s] = False
-            self.slot_moves[s] = []
-            self.slot_pis[s] = []
-            self.slot_stats[s] = []
-            self.slot_full[s] = []
-            self.slot_values[s] = []
-            self.slot_raw[s] = []
         # a game's Dirichlet noise (read by the PUCT rule only), like its move draws, is keyed by (seed, game id): the trajectory
         # does not depend on the slot, lane or GPU the game is played on
         with np.errstate(over='ignore'):
@@ -1115,90 +1148,51 @@ class BatchedSelfPlay(SelfPlayReader):
                 lane.eng.sim_chunk(lane.evaluator, n)
 
     # -- one move for every running game ----------------------------------------------
-    def _finish_lane(self, lane):
-        """The move of one lane after its simulations: root visits -> pi -> move drawn (alphazero_mcts.py:88-92,148),
-        tree reuse, game step.  Synchronises that lane's stream only.  Returns the trajectories that ended."""
-        eng = lane.eng
-        lo = lane.slots.start
-        running = lo + np.nonzero(self.slot_game[lane.slots] >= 0)[0]
+    def _fetch_lane(self, lane, running):
+        """What the lane's search left for its ``running`` slots, read on the lane's stream (synchronises that stream only) ->
+        (visits, root values or None, pruned counts or None), a row per slot."""
+        at = running - lane.slots.start
+        vals = pruned = None
         with self._on(lane):
             visits = lane.eng.root_visits()
             # the split-f16 trunk reports an input outside its range: float planes only (positions are 0 / 1 planes by construction,
             # and the query waits for the device)
             if hasattr(getattr(lane.evaluator, 'hip', None), 'check_flags') and getattr(lane.evaluator, 'needs_obs', True):
                 lane.evaluator.hip.check_flags()
-        if self.playout_cap is not None and len(running):
-            full = self._full(self.slot_game[running], self.slot_ply[running])
-            for i, s_ in enumerate(running):
-                self.slot_full[s_].append(bool(full[i]))
-            self.sims_done += int(np.where(full, eng.n_playout, self.playout_cap[0]).sum())
-            self.full_plies += int(full.sum())
-        else:
-            self.sims_done += eng.n_playout * len(running)
-            self.full_plies += len(running)
+            if (self.resign_on or self.root_values_on) and len(running):
+                vals = lane.eng.root_values()[at]
+            if self.forced_k > 0.0 and self.forced_prune and len(running):
+                pruned = lane.eng.root_pruned_visits()[at]
+        return visits[at], vals, pruned
+
+    def _apply_lane(self, lane, running, chosen, quit_):
+        """The moves of ``decide_and_record`` on the lane's boards and trees: the host's mirror, tree reuse and the game step, then
+        the ended and the resigned games out of the book -> their trajectories."""
+        eng, lo = lane.eng, lane.slots.start
         moves = np.full(eng.n_games, -2, dtype=np.int32)
-        resigned = running[:0]
-        vals = None
-        if (self.resign_on or self.root_values_on) and len(running):
-            with self._on(lane):
-                vals = lane.eng.root_values()[running - lo]
-        if self.resign_on and len(running):
-            # the rule of k_play_draw on the same fp64 values: the mover resigns when v_root and q_best are both below the threshold
-            stat = np.maximum(vals[:, 0], vals[:, 1]).astype(np.float32)   # (NaN when either is)
-            fire = (vals[:, 0] < self.resign_threshold) & (vals[:, 1] < self.resign_threshold)
-            calib = self._calibration(self.slot_game[running])
-            self.resign_would += int((fire & calib).sum())
-            for i, s_ in enumerate(running):
-                self.slot_stats[s_].append(stat[i])
-            resigned = running[fire & ~calib]
-            moves[resigned - lo] = -1    # (no move; the tree is dropped, like reset_player at the end of a game)
-            running, vals = running[~(fire & ~calib)], vals[~(fire & ~calib)]
-        if self.root_values_on and len(running):   # (k_play_draw's float32 of the same fp64 value; a resigning search is not recorded)
-            for s_, v in zip(running, vals[:, 0].astype(np.float32)):
-                self.slot_values[s_].append(v)
-        if len(running):
-            us = move_uniform(self.seed, self.slot_game[running], self.slot_ply[running])
-            taken = self.cell_taken[running]
-            if eng.game == 'connect4':  # action = column, legal while its top cell is empty; the stone drops
-                legal = ~taken[:, (eng.rows - 1) * eng.cols:]
-                heights = taken.reshape(len(running), eng.rows, eng.cols).sum(axis=1)
-            else:
-                legal = ~taken
-            pis, chosen = self._pis_moves(visits[running - lo], legal, self.slot_ply[running], us)
-            if self.forced_k > 0.0:   # the move from the raw counts, as ever; the stored pi from the pruned ones
-                for i, s_ in enumerate(running):
-                    self.slot_raw[s_].append(visits[s_ - lo].astype(np.int32))
-                if self.forced_prune:
-                    with self._on(lane):
-                        pr = lane.eng.root_pruned_visits()[running - lo]
-                    pis = self._pis_moves(np.where(legal, pr, 0), legal, self.slot_ply[running], us)[0]
-            cells =heights[np.arange(len(running)), chosen] * eng.cols + chosen if eng.game == 'connect4' else chosen
-            moves[running - lo] = chosen
-            self.cell_taken[running, cells] = True
-            self.slot_ply[running] += 1
-            for i, s_ in enumerate(running):
-                self.slot_pis[s_].append(pis[i])
-                self.slot_moves[s_].append(int(chosen[i]))
-        step_moves = np.where(moves >= 0, moves, -1).astype(np.int32)
+        moves[running - lo] = chosen   # (-1 where the mover resigns: no move, the tree is dropped like reset_player at a game's end)
+        played, cells = running[~quit_], chosen[~quit_]
+        if eng.game == 'connect4':   # action = column: the stone drops
+            heights = self.cell_taken[played].reshape(len(played), eng.rows, eng.cols).sum(axis=1)
+            cells = heights[np.arange(len(played)), cells] * eng.cols + cells
+        self.cell_taken[played, cells] = True
         with self._on(lane):
-            winner, ended = lane.eng.advance_and_step(moves, step_moves)  # tree reuse before the boards change
-        self.moves_done += len(running)
+            winner, ended = eng.advance_and_step(moves, np.where(moves >= 0, moves, -1).astype(np.int32))  # tree reuse before the boards change
         done = []
-        for s in sorted(list(running) + list(resigned)):
-            quit_ = s in resigned
-            if quit_ or ended[s - lo]:
-                win = 1 - len(self.slot_moves[s]) % 2 if quit_ else int(winner[s - lo])   # (player 0 moves the even plies)
-                extra = self._resign_record(self.slot_stats[s], win, bool(self._calibration(self.slot_game[s])), quit_)
-                if self.playout_cap is not None:
-                    extra['full'] = self.slot_full[s]
-                if self.root_values_on:
-                    extra['root_values'] = self.slot_values[s]
-                if self.forced_k > 0.0:
-                    extra['raw_visits'] = np.asarray(self.slot_raw[s], dtype=np.int32).reshape(len(self.slot_moves[s]), -1)
-                done.append(Trajectory(self.slot_game[s], eng.board_size, eng.n_in_row,
-                                       self.slot_moves[s], self.slot_pis[s], win, game=eng.game, **extra))
-                self.slot_game[s] = -1
+        for s, gone in zip(running, quit_):
+            if gone or ended[s - lo]:   # (player 0 moves the even plies: the mover who resigns loses)
+                done.append(self.trajectory(self.book.close(s, 1 - int(self.slot_ply[s]) % 2 if gone else int(winner[s - lo]), bool(gone))))
         return done
+
+    def _finish_lane(self, lane):
+        """The move of one lane after its simulations: root visits -> pi -> move drawn (alphazero_mcts.py:88-92,148),
+        tree reuse, game step.  Synchronises that lane's stream only.  Returns the trajectories that ended."""
+        running = lane.slots.start + np.nonzero(self.slot_game[lane.slots] >= 0)[0]
+        visits, vals, pruned = self._fetch_lane(lane, running)
+        legal = ~self.cell_taken[running]
+        if lane.eng.game == 'connect4':   # action = column, legal while its top cell is empty
+            legal = legal[:, (lane.eng.rows - 1) * lane.eng.cols:]
+        return self._apply_lane(lane, running, *self.decide_and_record(running, visits, legal, vals, pruned))
 
     def play_move(self):
         """n_playout simulations, then pick / apply one move per game.  Returns the list of
