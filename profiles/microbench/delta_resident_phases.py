@@ -1,10 +1,12 @@
 """Cycles per phase of ONE simulation of the resident search with the receptive-field trunk (k_delta_res; wave 0 of the workgroup of
 game 0), from a library built with -DRZ_NET_PROFILE (profiles/microbench/build_netprof.sh):
 
-    python profiles/microbench/delta_resident_phases.py [--values] [games ...]     (default: 1, 256, 512 games; a whole 800-simulation search each)
+    python profiles/microbench/delta_resident_phases.py [--values] [--backup-rows] [games ...]     (default: 1, 256, 512 games; a whole 800-simulation search each)
 
 --values: the search of policy on demand (k_delta_res<false>: no policy features; the engine here has no move step, so the decision
 is forced).
+--backup-rows: the library was built with -DRZ_BKP_TICKS=1 (rz_delta.h): the slots of the selection's ticks 1 .. 3 hold the rows of expand +
+backup, slot 22 wave 1's conv2.
 """
 import ctypes, os, sys
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '.'))
@@ -26,11 +28,15 @@ NAMES = [(0, 'verdict'), (1, 'requests, ranks'), (3, 'maps; wave 0: planes, conv
          (2, 'sel: root record'), (8, 'sel: root scan / answer'), (13, 'sel: level-0 cell'), (14, 'sel: deeper levels'), (15, 'sel: tail behind the release'),
          (18, 'selection (up to the release)'), (19, 'wave 1: pre-scan'), (20, 'wave 1: wait behind it'),
          (21, 'wave 1: release -> its arrival at the barrier before conv2')]
+FLAGS = ('--values', '--backup-rows')
+if '--backup-rows' in sys.argv[1:]:
+    BACKUP = {8: 'backup: fetches issued', 13: 'backup: join -> value', 14: 'backup: bookkeeping', 17: 'backup: stores + barrier'}
+    NAMES = [(k, BACKUP.get(k, nm)) for k, nm in NAMES] + [(22, 'wave 1: conv2')]
 VALUES = '--values' in sys.argv[1:]
 if VALUES:
     import rlzero_amd.route as _R
     _R.policy_on_demand = lambda *a, **k: True
-sizes = [int(a) for a in sys.argv[1:] if a != '--values'] or [1, 256, 512]
+sizes = [int(a) for a in sys.argv[1:] if a not in FLAGS] or [1, 256, 512]
 for games in sizes:
     torch.manual_seed(0)
     net = PolicyValueNet(15).to('cuda:0')

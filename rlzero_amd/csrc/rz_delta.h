@@ -58,6 +58,13 @@
 #ifndef RZ_DELTA_PRESCAN
 #define RZ_DELTA_PRESCAN 1
 #endif
+// (k_delta_res: wave 0 asks for the tree phase's loads one phase early -- rz_tree.h's fetch steps.  Bit 0: the backup's leaf state in
+// front of the value layer, its path's records behind wave 0's own quarter of it; bit 1: the selection's root state behind the backup,
+// in front of the barrier that orders the backup's stores.  3 is what ships and what the tests run; 0 and 1 exist for the A / B builds
+// of profiles/r14/ab_early_loads.txt alone: every load where its body has it, the backup's fetch steps without the selection's)
+#ifndef RZ_DELTA_EARLY
+#define RZ_DELTA_EARLY 3
+#endif
 
 namespace {
 
@@ -1093,6 +1100,31 @@ __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uin
 #if defined(RZ_NET_PROFILE) && !defined(RZ_SEL_TICKS)
 #define RZ_SEL_TICKS 0
 #endif
+// expand_backup_from's ticks in k_delta_res (the profile build with -DRZ_BKP_TICKS=1; RZ_SEL_TICKS 0 or 1 beside it: the rows take the
+// slots of the selection's ticks 1 .. 3): net_prof[8] the backup's fetches issued (behind the value layer's quarter), [13] join ->
+// leaf value, [14] the expansion's bookkeeping; [17] is then the backup's stores and the barrier behind them; [22] wave 1's conv2
+#if defined(RZ_NET_PROFILE) && !defined(RZ_BKP_TICKS)
+#define RZ_BKP_TICKS 0
+#endif
+#ifdef RZ_NET_PROFILE
+static_assert(!(RZ_BKP_TICKS && (RZ_SEL_TICKS & 14)), "the backup's rows stand in the slots of the selection's ticks 1 .. 3");
+struct ResTick {
+    static constexpr bool kOn = true;
+    Prof *prof;
+    __device__ __forceinline__ void tick(int i, int arrived) {
+        if (RZ_BKP_TICKS) {
+            asm volatile("" ::"v"(arrived));
+            __builtin_amdgcn_sched_barrier(0);
+            const long long now = __builtin_readcyclecounter();
+            prof->acc[13 + i] += now - prof->t;
+            prof->t = now;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+};
+#else
+typedef rzt::NoTick ResTick;
+#endif
 struct ResHook {
     static constexpr bool kOn = true;
     rzt::RootPre *pre;
@@ -1296,13 +1328,74 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         // ---- the rest of the simulation, by the same workgroup (k_tree_step_def's body: rz_tree.h), as in trunk_rows_body
         const int lane = tid_s & 63;
         if (RZ_DELTA_TREE_PRIO) __builtin_amdgcn_s_setprio(RZ_DELTA_TREE_PRIO);   // (the serial part of a simulation: ahead of the other game's trunk waves at issue)
-        if (res.vh.groups == 128) rzt::value_quarter_lds<16>(res.vh, res_vrow, lane, wave, res_part);
-        else rzt::value_quarter_lds<8>(res.vh, res_vrow, lane, wave, res_part);
-        NET_TICK(16);
         const bool more = sim + 1 < n_sims;
+        const auto value_quarter = [&]() {
+            if (res.vh.groups == 128) rzt::value_quarter_lds<16>(res.vh, res_vrow, lane, wave, res_part);
+            else rzt::value_quarter_lds<8>(res.vh, res_vrow, lane, wave, res_part);
+        };
+        constexpr bool kBackupDeferred = true;   // expand_backup's DEF in BOTH calls below (what the early root fetch relies on)
         if (wave == 0) {
-            rzt::expand_backup_body<float, false, false, false, true>(res.E, nullptr, nullptr, game, lane, rz_raw_heads(), 0, res.vh, res_part);
+            // Wave 0, the game's: its quarter of the value layer, expand + backup, the next selection -- ONE region, so that what is asked
+            // for a phase early and its uses stand together.  RZ_DELTA_EARLY: the backup's leaf state (written by this wave's selection a
+            // trunk ago) is requested in front of the quarter and arrives under the quarter's weight loads; the records of the path's
+            // nodes are requested behind the quarter and travel under the join, the hidden sum, tanh and the expansion's bookkeeping.
+            if (RZ_DELTA_EARLY & 1) {
+                const rzt::BackupLeaf bl = rzt::backup_leaf_fetch<false, true>(res.E, game, lane);
+                value_quarter();
+                NET_TICK(16);
+                const rzt::PathRecs recs = rzt::backup_path_fetch(res.E, game, lane, bl);
+#ifdef RZ_NET_PROFILE
+                if (RZ_BKP_TICKS) NET_TICK(8);   // the path's records requested (not their arrival)
+                ResTick btick;
+                btick.prof = &prof;
+                ResTick *tk = &btick;
+#else
+                ResTick *tk = nullptr;
+#endif
+                rzt::expand_backup_from<float, false, false, false, kBackupDeferred, rzt::kWords, rzt::PathRecs, ResTick>(res.E, nullptr, nullptr, game, lane, bl, recs,
+                                                                                                               rz_raw_heads(), 0, res.vh, res_part, tk);
+            } else {
+                value_quarter();
+                NET_TICK(16);
+                rzt::expand_backup_body<float, false, false, false, kBackupDeferred>(res.E, nullptr, nullptr, game, lane, rz_raw_heads(), 0, res.vh, res_part);
+            }
+            // The next selection.  Its hook meets the RELEASE barrier the moment the leaf's cell is chosen, the leaf and its window sets in LDS
+            // (ResHook::leaf); waves 1 .. 3 wait for nothing else and go on to the next leaf's prologue, wave 0 finishes the selection
+            // beside them.  (res_leaf / res_win: written before the release, rewritten by the next selection, at least three barriers on;
+            // res_pre: the tail's stash is read by wave 1 behind the barrier inside expand_backup_body; the gather tables: rows 1 .. 3 of
+            // res_part, which the tail does not touch.)  The last simulation: no selection, no barrier, for anyone.
+            if (more) {
+                hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
+                hook.release = true;
+                // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
+                // and kept -- spilled -- across the trunk)
+                int lane_t = lane;
+                asm volatile("" : "+v"(lane_t));
+                if (RZ_DELTA_EARLY & 2) {
+                    // (top[g] in particular: the backup in front of this fetch is the one with deferred priors, whose expansion is never
+                    // dense -- `dense = !DEF && ...` in expand_backup_from --, so only this wave's own selection tail stores to it)
+                    static_assert(kBackupDeferred, "the root fetch in front of the barrier: no dense expansion may move top[g] behind it");
+                    // the selection's root state -- arena, top, root position, window: words neither the backup with deferred priors nor
+                    // the pre-scan stores to (top[g]: only this wave's own selection tail) -- requested in front of the barrier: it
+                    // travels with the backup's store acknowledgements.  Behind the barrier stay what the backup and wave 1 write: the
+                    // stash (LDS), the root's record and child r's.
+                    const rzt::SelectRoot root = rzt::select_root_fetch<rzt::kWords>(res.E, game, lane_t);
+                    __syncthreads();   // the tree's updates before the selection's record loads; the pre-scan's answer
+                    NET_TICK(17);
+                    rzt::select_body_from<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, root, 0, res_leaf, &hook);
+                } else {
+                    __syncthreads();   // the tree's updates before the selection's loads; the pre-scan's answer
+                    NET_TICK(17);
+                    rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, 0, res_leaf, &hook);
+                }
+                NET_TICK(15);   // wave 0: the selection's tail, behind the release
+            } else {
+                __syncthreads();
+                NET_TICK(17);
+            }
         } else {
+            value_quarter();
+            NET_TICK(16);
             __syncthreads();   // (the barrier inside the body, where the quarters meet)
             // wave 1, idle until the next barrier: the root's siblings for the next selection (it reads the tree, it writes LDS)
             if (RZ_DELTA_PRESCAN && wave == 1 && more) {
@@ -1317,28 +1410,12 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                 pre_wait -= t1;
 #endif
             }
-        }
-        __syncthreads();        // the tree's updates before the selection's loads; the pre-scan's answer
+            __syncthreads();        // (wave 0: behind the backup) the pre-scan's answer
 #ifdef RZ_NET_PROFILE
-        if (RZ_DELTA_PRESCAN && wave == 1 && more) pre_wait += __builtin_readcyclecounter();
+            if (RZ_DELTA_PRESCAN && wave == 1 && more) pre_wait += __builtin_readcyclecounter();
 #endif
-        NET_TICK(17);
-        // The next selection.  Its hook meets the RELEASE barrier the moment the leaf's cell is chosen, the leaf and its window sets in LDS
-        // (ResHook::leaf); waves 1 .. 3 wait for nothing else and go on to the next leaf's prologue, wave 0 finishes the selection
-        // beside them.  (res_leaf / res_win: written before the release, rewritten by the next selection, at least three barriers on;
-        // res_pre: the tail's stash is read by wave 1 behind the barrier inside expand_backup_body; the gather tables: rows 1 .. 3 of
-        // res_part, which the tail does not touch.)  The last simulation: no selection, no barrier, for anyone.
-        if (more) {
-            if (wave == 0) {
-                hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
-                hook.release = true;
-                // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
-                // and kept -- spilled -- across the trunk)
-                int lane_t = lane;
-                asm volatile("" : "+v"(lane_t));
-                rzt::select_body<false, rzt::kWords, ResHook>(res.E, nullptr, game, lane_t, 0, res_leaf, &hook);
-                NET_TICK(15);   // wave 0: the selection's tail, behind the release
-            } else {
+            NET_TICK(17);
+            if (more) {
                 __syncthreads();   // the release
                 NET_TICK(18);
             }
@@ -1360,11 +1437,12 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
 #ifdef RZ_NET_PROFILE
     if (blockIdx.x == 0 && tid0 == 0) {
         for (int i = 0; i < 24; ++i)
-            if (i != 19 && i != 20 && i != 21) net_prof[i] = prof_acc[i];
+            if (i != 19 && i != 20 && i != 21 && !(RZ_BKP_TICKS && i == 22)) net_prof[i] = prof_acc[i];
         net_prof[23] = __builtin_readcyclecounter() - prof_k0;
-        net_prof[22] = tiles_total;
+        if (!RZ_BKP_TICKS) net_prof[22] = tiles_total;
     }
     if (blockIdx.x == 0 && tid0 == 64) {   // wave 1's first lane: the pre-scan and the wait behind it
+        if (RZ_BKP_TICKS) net_prof[22] = prof_acc[7];   // (its conv2, in the place of the tile count)
         net_prof[19] = pre_cycles;
         net_prof[20] = pre_wait;
         net_prof[21] = prof_acc[0] + prof_acc[1] + prof_acc[3];   // ... from the release to the barrier before conv2 (its arrival there)

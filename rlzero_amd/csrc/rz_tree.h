@@ -644,26 +644,51 @@ __device__ __forceinline__ void root_prescan(const Dev &E, int g, int lane, Root
 // hook->tick(i, v) is a phase tick of the profile build behind the arrival of v.  NoHook: none of it.
 // FORCED (k_select, k_tree_step, k_tree_step_raw, k_trunk_split<.., PUCT>: the kernels that can run PUCT with one simulation in
 // flight): the root's PUCT scan applies the forced-playout rule when E.forced_k > 0; every other instantiation compiles as before.
+// The selection's FIRST LOADS, none of which depends on another load or on a record of the tree: the game's arena and the top of its
+// records, the root position, the `active` flag, the lane's window of line_through.  select_root_fetch asks for them and returns the
+// VALUES (a plain struct of registers: behind a pointer it would go through scratch); select_body asks directly in front of its
+// body.  A caller that knows that nothing between an earlier point and the selection stores to any of these words may ask there
+// and call select_body_from itself (k_delta_res: behind the backup, in front of the barrier that orders the backup's stores --
+// the backup with deferred priors writes records, prior blocks and pending slots, never one of these).
+struct SelectRoot {
+    int arena, top0, to_move, last;
+    bool act;
+    uint64_t st[2][kWords];
+    uint64_t window, window_hi;
+};
+template <int W = kWords>
+__device__ __forceinline__ SelectRoot select_root_fetch(const Dev &E, int g, int lane) {
+    SelectRoot f;
+    // every load that does not depend on another one is issued before `active` is tested: a kernel of dependent
+    // round trips (an inactive game's slots exist, reading them is harmless)
+    f.arena = E.cur_arena[g];
+    f.top0 = E.top[g];
+    f.to_move = E.root_to_move[g];
+    f.last = E.root_last[g];
+    f.act = E.active[g] != 0;
+    load_board<W>(E.root_stones, g, f.st);
+    f.window = E.line_tab[lane];   // (line_through<1>: asked for with the first loads, used at the end)
+    f.window_hi = 0;
+    if constexpr (W == 2) f.window_hi = E.line_tab[kWave + lane];
+    return f;
+}
+
 template <bool VL, int W = kWords, class Hook = NoHook, bool FORCED = false>
-__device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr,
-                                            Hook *hook = nullptr) {
+__device__ __forceinline__ void select_body_from(const Dev &E, float *obs, int g, int lane, const SelectRoot f, int j = 0,
+                                                 uint64_t *lds_leaf = nullptr, Hook *hook = nullptr) {
     static_assert(!(Hook::kOn && VL), "the root pre-scan is the sequential search's");
     static_assert(!(FORCED && (VL || Hook::kOn)), "forced playouts: one simulation in flight, no root pre-scan");
     const int gk = VL ? g * E.K + j : g;
-    // every load that does not depend on another one is issued before `active` is tested: a kernel of dependent
-    // round trips (an inactive game's slots exist, reading them is harmless)
-    const int arena = E.cur_arena[g];
-    const int top0 = E.top[g];
-    int to_move = E.root_to_move[g];
-    int last = E.root_last[g];
-    const bool act = E.active[g] != 0;
+    const int arena = f.arena;
+    const int top0 = f.top0;
+    int to_move = f.to_move;
+    int last = f.last;
+    const bool act = f.act;
     const int S = E.S;
     uint64_t st[2][kWords];
-    load_board<W>(E.root_stones, g, st);
-    uint64_t window = 0;   // (line_through<1>: asked for with the first loads, used at the end)
-    window = E.line_tab[lane];
-    uint64_t window_hi = 0;
-    if constexpr (W == 2) window_hi = E.line_tab[kWave + lane];
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) st[0][i] = f.st[0][i], st[1][i] = f.st[1][i];
+    const uint64_t window = f.window, window_hi = f.window_hi;
     // the helper's answer and the stash it was made from (LDS: asked for with the first loads); the stash this selection leaves
     RootPre was = {};
     bool pre_ok = false;
@@ -896,6 +921,11 @@ __device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int
         write_obs(obs + (long long)gk * 4 * S, to_move == 0 ? st[0] : st[1],
                   to_move == 0 ? st[1] : st[0], last, nst, S, lane);
 }
+template <bool VL, int W = kWords, class Hook = NoHook, bool FORCED = false>
+__device__ __forceinline__ void select_body(const Dev &E, float *obs, int g, int lane, int j = 0, uint64_t *lds_leaf = nullptr,
+                                            Hook *hook = nullptr) {
+    select_body_from<VL, W, Hook, FORCED>(E, obs, g, lane, select_root_fetch<W>(E, g, lane), j, lds_leaf, hook);
+}
 
 // Un-normalised outputs of the evaluator's last GEMM (rz_raw_heads, include/rlzero_hip.h), finished inside the tree
 // kernel (same wave per game): with n_parts == 4 the sum of the four K-quarter partial sums of the FC GEMM + scale +
@@ -918,28 +948,90 @@ constexpr int kDefWaves = 4;   // waves of a game's workgroup: all sum a quarter
 // game's workgroup has just finished (value_head_def below); an expansion reserves its prior block and leaves a record
 // (block, noise counter, board) in slot pend[g] -- the priors themselves are written by k_deferred_priors at the next flush
 // -- and every active game moves on to the next slot.
-template <typename VT, bool PROBS = false, bool RAW = false, bool VL = false, bool DEF = false, int W = kWords>
-__device__ __forceinline__ void expand_backup_body(const Dev &E, const float *logp, const VT *value, int g,
-                                                   int lane, RawHeads rh = RawHeads(), int j = 0, ValueHead vh = ValueHead(),
-                                                   float (*part)[kWave] = nullptr) {
-    const int gk = VL ? g * E.K + j : g;
-    const int slot = DEF ? E.pend[g] : 0;
-    // loads first, the test of `active` after them (see select_body)
-    const bool act = E.active[g] != 0;
-    const int arena = E.cur_arena[g];
-    const int depth = E.leaf_depth[gk];
-    const int fresh = E.leaf_fresh[gk];
-    const int term = E.leaf_term[gk];
-    const double leaf_tval = E.leaf_tval[gk];
-    const int ptop = E.ptop[g];
-    const int nblk = E.nblk[g];
-    const int top_now = E.top[g];
-    const int noise_ctr = E.noise_ctr[g];
-    const int leaf_tm = DEF ? E.leaf_to_move[gk] : 0, leaf_lc = DEF ? E.leaf_last[gk] : 0;   // (the pending record's word)
-    const int32_t *path = E.path + (long long)gk * E.path_stride;
-    const int path_lane = path[lane < E.path_stride ? lane : 0];  // the node of path level `lane` (if that level exists)
+//
+// The body's loads come in two FETCH STEPS that return values (plain structs of registers: behind a pointer they would go through
+// scratch), so that a caller can ask for them a phase early.  backup_leaf_fetch: what the selection that chose the leaf left in the
+// engine's arrays -- the leaf, its path's node of level `lane`, the game's counters; none of these addresses depends on a load.
+// backup_path_fetch: both halves of the record of that node, for the lanes of the loop's first turn (level <= depth; the others
+// read the root's record and drop it) -- their addresses depend on the first step's arena, depth and path, on nothing else.
+// expand_backup_body asks for the first step directly in front of its body and leaves the records to the loop (NoRecs: the loads
+// it always had).  A caller may ask earlier when no store to these words lies in between: k_delta_res asks for the first step in
+// front of the value layer and for the second behind its own quarter of it -- the words were written by the same wave's selection
+// a whole trunk (and several barriers) earlier, and with deferred priors the expansion in front of the loop stores to no record.
+struct BackupLeaf {
+    int slot;
+    bool act;
+    int arena, depth, fresh, term;
+    double tval;
+    int ptop, nblk, top_now, noise_ctr, leaf_tm, leaf_lc;
+    int path_lane;   // the node of path level `lane` (if that level exists)
     uint64_t st[2][kWords];
-    load_board<W>(E.leaf_stones, gk, st);
+};
+struct NoRecs { static constexpr bool kOn = false; };   // the loop loads what it adds to
+struct PathRecs {
+    static constexpr bool kOn = true;
+    int4 lo, hi;   // lane <= depth: the record of path_lane
+};
+template <bool VL = false, bool DEF = false, int W = kWords>
+__device__ __forceinline__ BackupLeaf backup_leaf_fetch(const Dev &E, int g, int lane, int j = 0) {
+    BackupLeaf f;
+    const int gk = VL ? g * E.K + j : g;
+    f.slot = DEF ? E.pend[g] : 0;
+    // loads first, the test of `active` after them (see select_body)
+    f.act = E.active[g] != 0;
+    f.arena = E.cur_arena[g];
+    f.depth = E.leaf_depth[gk];
+    f.fresh = E.leaf_fresh[gk];
+    f.term = E.leaf_term[gk];
+    f.tval = E.leaf_tval[gk];
+    f.ptop = E.ptop[g];
+    f.nblk = E.nblk[g];
+    f.top_now = E.top[g];
+    f.noise_ctr = E.noise_ctr[g];
+    f.leaf_tm = DEF ? E.leaf_to_move[gk] : 0, f.leaf_lc = DEF ? E.leaf_last[gk] : 0;   // (the pending record's word)
+    const int32_t *path = E.path + (long long)gk * E.path_stride;
+    f.path_lane = path[lane < E.path_stride ? lane : 0];
+    load_board<W>(E.leaf_stones, gk, f.st);
+    return f;
+}
+__device__ __forceinline__ PathRecs backup_path_fetch(const Dev &E, int g, int lane, const BackupLeaf f) {
+    // (no branch of its own: a load under one makes hipcc wait for every load in flight before each use)
+    const int4 *R = arena_records(E, g, f.arena);
+    const int node = lane <= f.depth ? f.path_lane : 0;
+    PathRecs p;
+    p.lo = R[2 * node];
+    p.hi = R[2 * node + 1];
+    return p;
+}
+
+// `tk` (Tk::kOn; the profile build of k_delta_res): tk->tick(0, v) behind the leaf value's arrival (the join, the hidden sum, tanh),
+// tk->tick(1, v) in front of the backup's stores (the expansion's bookkeeping lies between the two).  NoTick: none of it.
+struct NoTick { static constexpr bool kOn = false; };
+template <typename VT, bool PROBS = false, bool RAW = false, bool VL = false, bool DEF = false, int W = kWords, class Recs = NoRecs, class Tk = NoTick>
+__device__ __forceinline__ void expand_backup_from(const Dev &E, const float *logp, const VT *value, int g, int lane, const BackupLeaf f,
+                                                   const Recs recs, RawHeads rh = RawHeads(), int j = 0, ValueHead vh = ValueHead(),
+                                                   float (*part)[kWave] = nullptr, Tk *tk = nullptr) {
+    // (records fetched early: only where nothing in front of the loop stores to a record or moves the arena's top -- no dense
+    // expansion, no virtual loss)
+    static_assert(!Recs::kOn || (DEF && !VL && !RAW), "records fetched ahead of the body: deferred priors, one simulation in flight");
+    const int gk = VL ? g * E.K + j : g;
+    const int slot = f.slot;
+    const bool act = f.act;
+    const int arena = f.arena;
+    const int depth = f.depth;
+    const int fresh = f.fresh;
+    const int term = f.term;
+    const double leaf_tval = f.tval;
+    const int ptop = f.ptop;
+    const int nblk = f.nblk;
+    const int top_now = f.top_now;
+    const int noise_ctr = f.noise_ctr;
+    const int leaf_tm = f.leaf_tm, leaf_lc = f.leaf_lc;
+    const int32_t *path = E.path + (long long)gk * E.path_stride;
+    const int path_lane = f.path_lane;
+    uint64_t st[2][kWords];
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) st[0][i] = f.st[0][i], st[1][i] = f.st[1][i];
     float lse = 0.0f, raw_value = 0.0f;
     float x[kWords] = {0.f, 0.f, 0.f, 0.f};  // RAW: the lane's policy logits, kept for the priors below
     if (RAW) {
@@ -998,6 +1090,7 @@ __device__ __forceinline__ void expand_backup_body(const Dev &E, const float *lo
         hid = fmaxf(hid + b1, 0.0f);
         def_value = tanhf(wave_sum(hid * w2, lane) + b2);
     }
+    if constexpr (Tk::kOn) tk->tick(0, __float_as_int(def_value));
     if (!act) return;
     int4 *R = arena_records(E, g, arena);
     float *P = arena_priors(E, g, arena);
@@ -1100,8 +1193,30 @@ __device__ __forceinline__ void expand_backup_body(const Dev &E, const float *lo
         E.pend[g] = slot + 1;
     }
 
+    if constexpr (Tk::kOn) tk->tick(1, new_pb);
     // TreeNode.update_recursive(-leaf_value): leaf gets -v, its parent +v, ... (node.py:135-144)
-    for (int d = lane; d <= depth; d += kWave) {
+    if constexpr (Recs::kOn) {
+        // the first turn (level `lane`) from the record fetched ahead: the stores of the loop below -- the same words, the same
+        // values --, none of its loads; a path longer than a wave goes on in the loop
+        if (lane <= depth) {
+            const int node = path_lane;
+            const double x = ((depth - lane) & 1) ? v : -v;
+            const int4 m = recs.lo;
+            if (lane != depth) {
+                *rec_n(R, node) = m.x + 1;
+                *rec_wsum(R, node) = rec_w(recs.hi) + x;
+            } else if (fresh == 1) {
+                R[2 * node] = make_int4(1, new_fc, new_nv, pack_kc(new_k, new_cap));
+                R[2 * node + 1] = make_hi(0.0 + x, new_pb, 0.0f);
+            } else {
+                R[2 * node] = (new_k > 0) ? make_int4(m.x + 1, new_fc, new_nv, pack_kc(new_k, new_cap))
+                                          : make_int4(m.x + 1, m.y, m.z, m.w);
+                *rec_wsum(R, node) = rec_w(recs.hi) + x;
+                if (new_k > 0) *rec_pb(R, node) = new_pb;
+            }
+        }
+    }
+    for (int d = Recs::kOn ? lane + kWave : lane; d <= depth; d += kWave) {
         const int node = d == lane ? path_lane : path[d];
         const double x = ((depth - d) & 1) ? v : -v;
         if (VL) {
@@ -1130,6 +1245,12 @@ __device__ __forceinline__ void expand_backup_body(const Dev &E, const float *lo
             *rec_wsum(R, node) += x;
         }
     }
+}
+template <typename VT, bool PROBS = false, bool RAW = false, bool VL = false, bool DEF = false, int W = kWords>
+__device__ __forceinline__ void expand_backup_body(const Dev &E, const float *logp, const VT *value, int g,
+                                                   int lane, RawHeads rh = RawHeads(), int j = 0, ValueHead vh = ValueHead(),
+                                                   float (*part)[kWave] = nullptr) {
+    expand_backup_from<VT, PROBS, RAW, VL, DEF, W>(E, logp, value, g, lane, backup_leaf_fetch<VL, DEF, W>(E, g, lane, j), NoRecs(), rh, j, vh, part);
 }
 
 // ------------------------------------------------------------------ deferred priors
