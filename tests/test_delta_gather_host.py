@@ -1,6 +1,6 @@
 """Which lane moves which 16 bytes of a leaf's base records (rlzero_amd/csrc/rz_gather.h), on the CPU.
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_net_pack.py does).  It plays the four
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py).  It plays the four
 waves of a workgroup lane by lane with the header's functions, the way delta_passes<SETS> uses them: every wave writes the table
 entries of the held cells whose records fall to it, reads the entries of its rounds back, and reports per (set, round, wave, lane)
 the offset requested from the base and the byte of the layer's LDS records it is stored to (-1: nothing stored).  The same is
@@ -9,15 +9,12 @@ restated in numpy from the header's opening comment and compared element by elem
 The window sets of a leaf are restated here as well: cells within Chebyshev distance r = 1 .. 4 of a changed cell, on the board.
 The same driver is also built with -fsanitize=address,undefined and run over all inputs (the tables are heap arrays of exactly
 rzg::kTabEntries entries)."""
-import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
+import host_driver
 
 BOARDS = [11, 13, 15, 16]
 C1_MAX, C2_MAX = 128, 164          # records a pass may hold (rz_delta.h: kC1Slots, kC2Slots)
@@ -113,20 +110,6 @@ int main(int argc, char **argv) {   // gather pitch1 pitch2 base_c2 sets.bin out
 '''
 
 
-def host_clangxx():
-    """ROCm's clang++: beside HIPCC, or under ROCM_PATH / /opt/rocm."""
-    roots = []
-    if os.environ.get('HIPCC'):
-        roots.append(os.path.dirname(os.path.dirname(os.path.realpath(os.environ['HIPCC']))))
-    roots += [os.environ.get('ROCM_PATH') or '/opt/rocm', '/opt/rocm']
-    for root in roots:
-        for sub in ('llvm/bin', 'lib/llvm/bin', 'bin'):
-            path = os.path.join(root, sub, 'clang++')
-            if os.path.exists(path):
-                return path
-    return None
-
-
 # ---- the leaves
 
 def window_sets(n, changed):
@@ -195,25 +178,14 @@ def expected(sets, geo, outer, inner):
 @pytest.fixture(scope='module')
 def gathered():
     """(cases, sets of each, the plain driver's output, the sanitized driver's output)"""
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the gather driver (HIPCC, ROCM_PATH or /opt/rocm)"
     cases = leaves()
     sets = [window_sets(n, ch) for n, ch in cases]
+    per_case = 2 + (C1['rounds'] + C2['rounds']) * 4 * 64 * 2
     with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, 'gather.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        inp = os.path.join(tmp, 'sets.bin')
-        np.stack([words(s) for s in sets]).astype('<u8').tofile(inp)
-        outs = []
-        for name, extra in (('gather', []), ('gather_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe, out = os.path.join(tmp, name), os.path.join(tmp, name + '.bin')
-            subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', *extra, '-I', CSRC, src, '-o', exe], check=True)
-            env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program: its runtime is linked in)
-            subprocess.run([exe, str(P1), str(P2), str(BASE_C2), inp, out], check=True, env=env)
-            per_case = 2 + (C1['rounds'] + C2['rounds']) * 4 * 64 * 2
-            outs.append(np.fromfile(out, dtype='<i4').reshape(len(cases), per_case))
-    return cases, sets, outs[0], outs[1]
+        drv = host_driver.Driver(tmp, 'gather', DRIVER)
+        outs = drv.both([P1, P2, BASE_C2, *drv.write([np.stack([words(s) for s in sets]).astype('<u8')])], drv.fresh(1))
+        plain, san = (np.fromfile(out, dtype='<i4').reshape(len(cases), per_case) for (out, ) in outs)
+    return cases, sets, plain, san
 
 
 def split(row):

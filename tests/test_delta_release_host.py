@@ -7,15 +7,12 @@ no place of its own (gathering wave -1) and no record anywhere.  It reports per 
 the base and the byte of the layer's LDS records it is stored to (-1: nothing stored).  The same is restated in numpy and compared
 element by element; the driver is also built with -fsanitize=address,undefined and run (the tables are heap arrays of exactly
 Split<3>::kTabEntries entries, read with bounds checks)."""
-import os
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
+import host_driver
 
 C1_MAX, C2_MAX = 128, 164          # records a pass may hold (rz_delta.h: kC1Slots, kC2Slots)
 P1, P2 = 160, 288                  # bytes from one LDS record to the next (rz_delta.h: P1, P2)
@@ -125,20 +122,6 @@ int main(int argc, char **argv) {   // gather3 pitch1 pitch2 base_c2 sets.bin ou
 '''
 
 
-def host_clangxx():
-    """ROCm's clang++: beside HIPCC, or under ROCM_PATH / /opt/rocm."""
-    roots = []
-    if os.environ.get('HIPCC'):
-        roots.append(os.path.dirname(os.path.dirname(os.path.realpath(os.environ['HIPCC']))))
-    roots += [os.environ.get('ROCM_PATH') or '/opt/rocm', '/opt/rocm']
-    for root in roots:
-        for sub in ('llvm/bin', 'lib/llvm/bin', 'bin'):
-            path = os.path.join(root, sub, 'clang++')
-            if os.path.exists(path):
-                return path
-    return None
-
-
 # ---- the sets
 
 def window_sets(n, changed):
@@ -224,24 +207,13 @@ def expected(sets, geo, outer, inner):
 @pytest.fixture(scope='module')
 def gathered():
     """(sets of each case, the plain driver's output, the sanitized driver's output)"""
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the gather driver (HIPCC, ROCM_PATH or /opt/rocm)"
     sets = cases()
+    per_case = 2 + (C1['rounds'] + C2['rounds']) * 4 * 64 * 2
     with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, 'gather3.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        inp = os.path.join(tmp, 'sets.bin')
-        np.stack([words(s) for s in sets]).astype('<u8').tofile(inp)
-        outs = []
-        for name, extra in (('gather3', []), ('gather3_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe, out = os.path.join(tmp, name), os.path.join(tmp, name + '.bin')
-            subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', *extra, '-I', CSRC, src, '-o', exe], check=True)
-            env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program: its runtime is linked in)
-            subprocess.run([exe, str(P1), str(P2), str(BASE_C2), inp, out], check=True, env=env)
-            per_case = 2 + (C1['rounds'] + C2['rounds']) * 4 * 64 * 2
-            outs.append(np.fromfile(out, dtype='<i4').reshape(len(sets), per_case))
-    return sets, outs[0], outs[1]
+        drv = host_driver.Driver(tmp, 'gather3', DRIVER)
+        outs = drv.both([P1, P2, BASE_C2, *drv.write([np.stack([words(s) for s in sets]).astype('<u8')])], drv.fresh(1))
+        plain, san = (np.fromfile(out, dtype='<i4').reshape(len(sets), per_case) for (out, ) in outs)
+    return sets, plain, san
 
 
 def split(row):

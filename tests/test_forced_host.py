@@ -7,7 +7,6 @@ once more with -fsanitize=address,undefined (a stand-alone program); every call 
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,12 +14,12 @@ import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
 import forced_twin as ft
+import host_driver
+from host_driver import CSRC
 from oracle.gomoku_ref import RefGomoku
 from oracle.mcts_ref import RefSearch, tree_dump
 from rlzero_amd import _hip
-from test_delta_gather_host import host_clangxx
 from test_gpu_parity import _skewed
-from test_mz_replay_host import CSRC, INCLUDE
 
 DRIVER = r'''
 #include <cmath>
@@ -91,55 +90,22 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'forced.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('forced', []), ('forced_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-    def forced(self, n, p, N, k):
-        return self.run('forced', [np.asarray(n, np.int32), np.asarray(p, np.float32), np.asarray(N, np.int32), np.asarray(k, np.float64)],
-                        [np.int32])[0]
-
-    def pruned(self, roots):
-        """roots: [(n list, w list, p list, N, k, c)] -> ([counts per root], [best child per root])."""
-        first = np.cumsum([0] + [len(r[0]) for r in roots]).astype(np.int32)
-        cat = lambda i, dt: np.concatenate([np.asarray(r[i], dtype=dt) for r in roots])   # noqa: E731
-        out, best = self.run('pruned', [first, cat(0, np.int32), cat(1, np.float64), cat(2, np.float32), np.asarray([r[3] for r in roots], np.int32),
-                                        np.asarray([r[4] for r in roots], np.float64), np.asarray([r[5] for r in roots], np.float64)],
-                             [np.int32, np.int32])
-        return [out[a:b].tolist() for a, b in zip(first[:-1], first[1:])], best.tolist()
+driver = host_driver.fixture('forced', DRIVER)
 
 
-@pytest.fixture(scope='module')
-def driver(tmp_path_factory):
-    return Driver(str(tmp_path_factory.mktemp('forced')))
+def forced(driver, n, p, N, k):
+    return driver.run('forced', [], [np.asarray(n, np.int32), np.asarray(p, np.float32), np.asarray(N, np.int32), np.asarray(k, np.float64)],
+                      [np.int32])[0]
+
+
+def pruned(driver, roots):
+    """roots: [(n list, w list, p list, N, k, c)] -> ([counts per root], [best child per root])."""
+    first = np.cumsum([0] + [len(r[0]) for r in roots]).astype(np.int32)
+    cat = lambda i, dt: np.concatenate([np.asarray(r[i], dtype=dt) for r in roots])   # noqa: E731
+    out, best = driver.run('pruned', [], [first, cat(0, np.int32), cat(1, np.float64), cat(2, np.float32), np.asarray([r[3] for r in roots], np.int32),
+                                          np.asarray([r[4] for r in roots], np.float64), np.asarray([r[5] for r in roots], np.float64)],
+                           [np.int32, np.int32])
+    return [out[a:b].tolist() for a, b in zip(first[:-1], first[1:])], best.tolist()
 
 
 def twin_pruned(root):
@@ -173,7 +139,7 @@ def random_roots(rs, count):
 def test_header_equals_twin_on_random_roots(driver):
     rs = np.random.RandomState(5)
     roots = random_roots(rs, 3000)
-    got, best = driver.pruned(roots)
+    got, best = pruned(driver, roots)
     lowered = zeroed = 0
     for root, g, b in zip(roots, got, best):
         assert g == twin_pruned(root)
@@ -186,7 +152,7 @@ def test_header_equals_twin_on_random_roots(driver):
     p = np.concatenate([r[2] for r in roots])
     N = np.concatenate([np.full(len(r[0]), r[3]) for r in roots])
     k = np.concatenate([np.full(len(r[0]), r[4]) for r in roots])
-    got_f = driver.forced(n, p, N, k)
+    got_f = forced(driver, n, p, N, k)
     want_f = [1 if ft.forced(int(a), b, int(c), float(d)) else 0 for a, b, c, d in zip(n, p, N, k)]
     assert got_f.tolist() == want_f and 0 < sum(want_f) < len(want_f)
 
@@ -200,7 +166,7 @@ def test_forced_at_the_threshold(driver):
             (0, 0.5, 16, 2.0, 0), (0, 1.0, 1000, 8.0, 0), (1, 0.125, 4, 2.0, 0), (1, 0.125, 5, 2.0, 1), (2, 0.125, 16, 2.0, 0),
             (46340, 1.0, 2147483647, 1.0, 1), (46341, 1.0, 2147483647, 1.0, 0)]   # (46341^2 = 2147488281 > 2^31 - 1: squared as doubles)
     assert (2.0 * 0.5) * 16.0 == 16.0 and (up * 0.5) * 16.0 == math.nextafter(16.0, 17.0) and (down * 0.5) * 16.0 == math.nextafter(16.0, 0.0)
-    got = driver.forced(*[[r[i] for r in rows] for i in range(4)])
+    got = forced(driver, *[[r[i] for r in rows] for i in range(4)])
     assert got.tolist() == [r[4] for r in rows]
     assert [1 if ft.forced(r[0], np.float32(r[1]), r[2], r[3]) else 0 for r in rows] == [r[4] for r in rows]
     # what a rule with <= would answer at the equalities
@@ -232,7 +198,7 @@ def test_pruning_crafted_roots(driver):
         # a huge k: f is capped by n, the loop by m > 0 -- the child loses everything it may lose
         (([9, 4], [0.0, -4.0], [0.9, 0.1], 16, 1e300, 1.0), [9, 0]),
     ]
-    got, best = driver.pruned([c[0] for c in cases])
+    got, best = pruned(driver, [c[0] for c in cases])
     for (root, want), g, b in zip(cases, got, best):
         assert twin_pruned(root) == want, root
         assert g == want, root

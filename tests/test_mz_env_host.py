@@ -2,7 +2,7 @@
 oracle/muzero_ref.RefCartPole through tests/cartpole_twin.py) and the host restatement of the keys and the action draw
 (tests/device_streams.py).
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_learner_host.py builds its driver),
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py),
 -ffp-contract=off, fed binary inputs and compared with the twin:
 
 * ``acrobot_step`` / ``acrobot_observe`` over 4000 random states and actions and over crafted states -- an angle leaving [-pi, pi]
@@ -21,8 +21,6 @@ A driver with its own main is compiled against the header with ROCm's clang++ (a
 * The trainer's parser takes ``--env acrobot`` and refuses an unknown environment."""
 import importlib.util
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -31,10 +29,9 @@ from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
 import acrobot_twin as twin
 import cartpole_twin as cart
 import device_streams as ds
+import host_driver
 from rlzero_amd.muzero.acrobot import acrobot_initial_states
-from test_delta_gather_host import host_clangxx
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
 GPU_BOUND = 1e-9       # tests/test_mz_env_gpu.py
 CAUGHT_ABOVE = 1e-4    # five orders above it
 
@@ -178,43 +175,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives the outputs of one call and holds both builds equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_env.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_env', []), ('mz_env_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra, '-I', CSRC, src,
-                            '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_env', DRIVER)
 
 
 def random_cases(n=4000, seed=5):

@@ -1,6 +1,6 @@
 """The arithmetic of the fused MuZero learner (rlzero_amd/csrc/rz_mz_learn.h) on the CPU, against torch autograd.
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_replay_host.py builds its driver),
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py),
 -ffp-contract=off, fed binary inputs and compared with the TWIN: the expressions of ``MuZeroAgent.learn`` run by torch autograd on
 float64 copies of the same parameters and batch (``twin_losses`` below restates them so that they can also be perturbed).
 
@@ -17,8 +17,6 @@ float64 copies of the same parameters and batch (``twin_losses`` below restates 
 * The refusals of the limits, and the trainer's parser."""
 import importlib.util
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -26,13 +24,11 @@ import torch
 import torch.nn.functional as F
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd.muzero import network
 from rlzero_amd.muzero.agent import MuZeroAgent, scale_gradient
 from rlzero_amd.muzero.network import MuZeroNet
-from test_delta_gather_host import host_clangxx
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 YARDSTICK = 4.0
 
 DRIVER = r'''
@@ -141,43 +137,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives the outputs of one call and holds both builds equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_learn.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_learn', []), ('mz_learn_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_learn', DRIVER)
 
 
 # ----------------------------------------------------------------------------------------------- nets, batches, the twin

@@ -13,16 +13,13 @@ What the edge inputs show (the header's comments say the same; nothing here chan
   * a nan never reaches the bound or a scale (fmax drops it) and a -inf weight does not either: only the scan of the 14 tensors makes
     f16_ok false for them.  Finite float32 weights cannot make the bound infinite (64 x 3.4e38 is finite in fp64): +inf does."""
 import math
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from test_net_pack import driver_command, same_bits
+import host_driver
+from test_net_pack import run_both, same_bits
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, f64 = np.float32, np.float64
 H = 64
 NAMES = ('dyn1.w', 'dyn1.b', 'dyn2.w', 'dyn2.b', 'rew1.w', 'rew1.b', 'rew2.w', 'rew2.b', 'pre1.w', 'pre1.b', 'pol.w', 'pol.b', 'val.w', 'val.b')
@@ -97,27 +94,16 @@ int main(int argc, char **argv) {
 '''
 
 
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'mz_pack.cpp'), os.path.join(tmp, 'mz_pack')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        subprocess.run(driver_command(src, exe), check=True)
-        count = [0]
+driver = host_driver.fixture('mz_pack', DRIVER)
 
-        def run(cmd, *args, data, out_dtype=None):
-            """Runs `cmd args <file of data> <out>` -> the output file as `out_dtype`, or (host float32, meta float64) of an output directory."""
-            count[0] += 1
-            path, out = os.path.join(tmp, 'in%d.bin' % count[0]), os.path.join(tmp, 'out%d' % count[0])
-            np.ascontiguousarray(data).tofile(path)
-            if out_dtype is None:
-                os.mkdir(out)
-            subprocess.run([exe, cmd, *[str(a) for a in args], path, out], check=True)
-            if out_dtype is not None:
-                return np.fromfile(out, dtype=out_dtype)
-            return np.fromfile(os.path.join(out, 'host.bin'), dtype=f32), np.fromfile(os.path.join(out, 'meta.bin'), dtype=f64)
-        yield run
+
+@pytest.fixture(scope='module')
+def drv(driver):
+    def run(cmd, *args, data, out_dtype=None):
+        """Runs `cmd args <file of data> <out>` -> the output file as `out_dtype`, or (host float32, meta float64) of an output directory."""
+        got = run_both(driver, [cmd, *args, *driver.write([data])], out_dtype, {'host': f32, 'meta': f64})
+        return got if out_dtype is not None else (got['host'], got['meta'])
+    return run
 
 
 def model_weights(A, seed):

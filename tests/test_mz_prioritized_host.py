@@ -2,23 +2,23 @@
 and k_mzr_draw_prio call (priority_of, priority_weight, prio_target, prio_filler, upper_bound_u64), BIT FOR BIT against their
 Python statements in rlzero_amd/muzero/replay.py (mz_priority_weights, mz_prioritized_draws), with ReplayBuffer._value_target as
 the source of the n-step return.  A driver with its own main is compiled against the header with ROCm's clang++ and
--ffp-contract=off, as tests/test_mz_reanalyse_host.py compiles its driver, and once more with -fsanitize=address,undefined (a
+-ffp-contract=off, by
+tests/host_driver.py, and once more with -fsanitize=address,undefined (a
 stand-alone program); every call runs both and holds their outputs equal.  The search is checked EXACTLY, not statistically: every
 target 0 .. total - 1 of a small table goes through the driver, and each step is hit as often as it weighs.  Then the learner's
 importance weights and the trainer's refusal of --prioritized-replay without --device-replay."""
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd.muzero.replay import mz_prioritized_draws, mz_priority_weights, mz_replay_draws
 from rlzero_amd.muzero.selfplay import ReplayBuffer
-from test_delta_gather_host import host_clangxx
-from test_mz_replay_host import CONFIGS, CSRC, DISCOUNTS, INCLUDE, episode_lengths, episodes_of, packed_block, same_bits
+from test_mz_replay_host import CONFIGS, DISCOUNTS, episode_lengths, episodes_of, packed_block, same_bits
 
 DRIVER = r'''
 #include <cstdio>
@@ -156,43 +156,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_prioritized.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_prioritized', []), ('mz_prioritized_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_prioritized', DRIVER)
 
 
 def flat(weights):

@@ -1,25 +1,24 @@
 """MuZero Reanalyse on the CPU: the arithmetic and the draws of rlzero_amd/csrc/rz_mz_target.h that k_mzr_positions and
 k_mzr_update call (policy_of_visits, root_value_of, reanalyse_draw), BIT FOR BIT against their numpy / Python statements --
 EpisodeSeq.fields_of_packed's policy expression, MuZeroSelfPlay.search's root value, rlzero_amd/muzero/reanalyse.py:
-mz_reanalyse_draws.  A driver with its own main is compiled against the header with ROCm's clang++ and -ffp-contract=off, as
-tests/test_mz_replay_host.py compiles its driver, and once more with -fsanitize=address,undefined (a stand-alone program); every
+mz_reanalyse_draws.  A driver with its own main is compiled against the header with ROCm's clang++ and -ffp-contract=off, by
+tests/host_driver.py, and once more with -fsanitize=address,undefined (a stand-alone program); every
 call runs both and holds their outputs equal.  ``patched`` -- the host ReplayBuffer with some steps' targets replaced by those
 numpy expressions -- is what the GPU tests (tests/test_mz_reanalyse_gpu.py) compare the device store with."""
 import copy
 import os
 import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd.muzero.reanalyse import mz_reanalyse_draws
 from rlzero_amd.muzero.replay import mz_replay_draws
 from rlzero_amd.muzero.selfplay import Episode, ReplayBuffer
-from test_delta_gather_host import host_clangxx
-from test_mz_replay_host import CSRC, INCLUDE, same_bits
+from test_mz_replay_host import same_bits
 
 DRIVER = r'''
 #include <cstdio>
@@ -99,43 +98,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_reanalyse.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_reanalyse', []), ('mz_reanalyse_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_reanalyse', DRIVER)
 
 
 # ----------------------------------------------------------------------------------------------- the numpy statements

@@ -1,26 +1,20 @@
 """The MuZero learner's unrolled targets (rlzero_amd/csrc/rz_mz_target.h) on the CPU, against the host buffer they restate.
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_play_host.py does) with
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py) with
 -ffp-contract=off, fed binary inputs and compared in numpy with rlzero_amd/muzero/selfplay.py: ReplayBuffer.sample BIT FOR BIT --
 value targets, rewards, masks, actions and policy rows of hand-made episodes -- and with EpisodeSeq.fields_of_packed (the policy of
 a packed record) and rlzero_amd/muzero/replay.py: mz_replay_draws (the sampler's draws).  The draws fed to the driver are the host
 buffer's own: its RandomState is seeded and its draw sequence replayed (randint for the episodes, then for the positions, then the
 filler actions in (b, k) order); a second pass scripts the generator so that EVERY (episode, position) is an entry.  The same driver
 is also built with -fsanitize=address,undefined and run over all inputs (a stand-alone program)."""
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd.muzero.replay import mz_replay_draws
 from rlzero_amd.muzero.selfplay import EpisodeSeq, ReplayBuffer
-from test_delta_gather_host import host_clangxx
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 MAX_STEPS = 12
 CONFIGS = [(2, 3), (5, 10)]       # (K, td_steps)
 DISCOUNTS = [0.5, 0.997]
@@ -132,44 +126,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_target.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_target', []), ('mz_target_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        """``inputs``: arrays written to files; ``outputs``: dtypes of the files read back.  The files' names follow ``args``."""
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_target', DRIVER)
 
 
 # ----------------------------------------------------------------------------------------------- hand-made episodes

@@ -1,6 +1,6 @@
 """MuZero's invertible value transform (rlzero_amd/csrc/rz_mz_value.h) on the CPU, against its Python twin (tests/mz_value_twin.py).
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_replay_host.py does) with
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py) with
 -ffp-contract=off, plain and with -fsanitize=address,undefined (a stand-alone program: no Python process is involved), fed binary
 inputs and compared BIT FOR BIT: ``value_h`` / ``value_h_inv`` with the twin, ``unroll_row<true>`` (rz_mz_target.h: the targets of
 k_mzr_gather<true>) with ``ReplayBuffer(value_transform=True).sample``.  The torch functions of rlzero_amd/muzero/network.py and the
@@ -17,24 +17,20 @@ errors of the torch float32 route): the last test forms that tolerance on the CP
 many tolerances away three wrong inverses land."""
 import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 import mz_net_twin
 import mz_value_twin as vt
 from rlzero_amd.muzero.network import MuZeroNet, inverse_value_transform, value_transform
 from rlzero_amd.muzero.selfplay import Episode, ReplayBuffer
-from test_delta_gather_host import host_clangxx
 from test_mz_learner_host import YARDSTICK, copy_net
 from test_mz_search_net_host import host_case, rolled_net
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 EPS = 0.001
 U = 2.0 ** -23
 REACH = (0.9, 20.0)   # what rew2 / val are scaled to reach on either side of 0: |y| within about 1, and up to about 20 (h(500) = 21.9)
@@ -132,43 +128,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'mz_value.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('mz_value', []), ('mz_value_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('mz_value', DRIVER)
 
 
 # ----------------------------------------------------------------------------------------------- the values

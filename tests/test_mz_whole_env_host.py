@@ -8,10 +8,9 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 from conftest import REPO
-from test_delta_gather_host import host_clangxx
+import host_driver
 
 HEADER = os.path.join(REPO, 'include', 'rlzero_hip.h')
 
@@ -46,8 +45,6 @@ def test_play_record_is_the_headers(tmp_path):
     """sizeof and offsetof of every field of rz_mz_whole_play (and of rz_mz_cartpole_play, whose fields it begins with) from the
     compiled header against the ctypes structures."""
     from rlzero_amd import _hip
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the probe (HIPCC, ROCM_PATH or /opt/rocm)"
     records = {'rz_mz_whole_play': _hip.RzMzWholePlay, 'rz_mz_cartpole_play': _hip.RzMzCartPolePlay}
     lines = ['#include <cstddef>', '#include <cstdio>', '#include "rlzero_hip.h"', 'int main() {']
     for name, cls in sorted(records.items()):
@@ -55,11 +52,7 @@ def test_play_record_is_the_headers(tmp_path):
         for field, _ in cls._fields_:
             lines.append('    std::printf("%s %s %%zu\\n", offsetof(%s, %s));' % (name, field, name, field))
     lines += ['    return 0;', '}']
-    src, exe = str(tmp_path / 'probe.cpp'), str(tmp_path / 'probe')
-    with open(src, 'w') as f:
-        f.write('\n'.join(lines) + '\n')
-    subprocess.run([cxx, '-std=c++17', '-Wall', '-Werror', '-I', os.path.join(REPO, 'include'), src, '-o', exe], check=True)
-    out = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().split('\n')
+    out = host_driver.probe(tmp_path, '\n'.join(lines) + '\n').decode().split('\n')
     got = {tuple(ln.split()[:2]): int(ln.split()[2]) for ln in out if ln}
     want = {}
     for name, cls in records.items():

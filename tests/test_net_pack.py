@@ -6,16 +6,15 @@ PolicyValueNet and writes every prepared buffer; each layout is then restated in
 reshape / transpose of the weight tensor that puts "lane h*32 + r of tile t, step s" where the comment says -- and compared bit
 for bit, padding included.  The scalar pieces (weight scale, hi + lo split, e4m3, activation bounds and scales) are run on edge
 inputs of their own through the same driver."""
+import filecmp
 import math
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
+import host_driver
+
 f32, f64, f16, u8, u16, u32 = np.float32, np.float64, np.float16, np.uint8, np.uint16, np.uint32
 
 # (rows, cols, policy outputs): the smallest; n_actions != cells; 9 x 9; not square; padding in A; none
@@ -105,53 +104,31 @@ int main(int argc, char **argv) {
 '''
 
 
-def host_clangxx():
-    """ROCm's clang++ (a host g++ may not know _Float16): beside HIPCC, or under ROCM_PATH / /opt/rocm."""
-    roots = []
-    if os.environ.get('HIPCC'):
-        roots.append(os.path.dirname(os.path.dirname(os.path.realpath(os.environ['HIPCC']))))
-    roots += [os.environ.get('ROCM_PATH') or '/opt/rocm', '/opt/rocm']
-    for root in roots:
-        for sub in ('llvm/bin', 'lib/llvm/bin', 'bin'):
-            path = os.path.join(root, sub, 'clang++')
-            if os.path.exists(path):
-                return path
-    return None
+def run_both(driver, argv, out_dtype, files):
+    """`argv <out>` through both builds of `driver` -> the plain build's output file as `out_dtype`, or (None) {name: array} of the
+    `files` = {name: dtype} in its output directory.  Every file is held equal between the builds, byte for byte."""
+    outs = driver.fresh(1)
+    if out_dtype is None:
+        for (path, ) in outs:
+            os.mkdir(path)
+    (plain, ), (san, ) = driver.both(argv, outs)
+    if out_dtype is not None:
+        assert filecmp.cmp(plain, san, shallow=False)
+        return np.fromfile(plain, dtype=out_dtype)
+    assert filecmp.cmpfiles(plain, san, [name + '.bin' for name in files], shallow=False)[1:] == ([], [])   # (none differs, none is missing)
+    return {name: np.fromfile(os.path.join(plain, name + '.bin'), dtype=dt) for name, dt in files.items()}
 
 
-def driver_command(src, exe):
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the packing driver (HIPCC, ROCM_PATH or /opt/rocm)"
-    return [cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-I', CSRC, src, '-o', exe]
+driver = host_driver.fixture('pack', DRIVER)
 
 
 @pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'pack.cpp'), os.path.join(tmp, 'pack')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        subprocess.run(driver_command(src, exe), check=True)
-        count = [0]
-
-        def run(cmd, *args, inputs=(), out_dtype=None):
-            """Runs `cmd`; each of `inputs` (arrays; None: '-') becomes a file argument behind `args`, the output file comes last."""
-            count[0] += 1
-            paths = []
-            for i, a in enumerate(inputs):
-                if a is None:
-                    paths.append('-')
-                else:
-                    paths.append(os.path.join(tmp, 'in%d_%d.bin' % (count[0], i)))
-                    np.ascontiguousarray(a).tofile(paths[-1])
-            out = os.path.join(tmp, 'out%d' % count[0])
-            if out_dtype is None:
-                os.mkdir(out)
-            subprocess.run([exe, cmd, *[str(a) for a in args], *paths, out], check=True)
-            if out_dtype is not None:
-                return np.fromfile(out, dtype=out_dtype)
-            return {name: np.fromfile(os.path.join(out, name + '.bin'), dtype=f32) for name in BUFFERS + ('meta', )}
-        yield run
+def drv(driver):
+    def run(cmd, *args, inputs=(), out_dtype=None):
+        """Runs `cmd`; each of `inputs` (arrays; None: '-') becomes a file argument behind `args`, the output file comes last."""
+        argv = [cmd, *args, *['-' if a is None else driver.write([a])[0] for a in inputs]]
+        return run_both(driver, argv, out_dtype, {name: f32 for name in BUFFERS + ('meta', )})
+    return run
 
 
 def shape_of(board):

@@ -1,26 +1,20 @@
 """The move step's rules (rlzero_amd/csrc/rz_play.h) on the CPU, against the host's side of them.
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_delta_gather_host.py does) with
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py) with
 -ffp-contract=off, fed binary inputs and compared in numpy: the keyed uniforms and the noise key with rlzero_amd/selfplay.py bit for
 bit, the budget rule, the temperature table, the draw with selfplay.batch_pi_and_moves (the arbiter), the resignation rule with the
 host's, and -- scripted slots played through rzplay::decide and rzplay::write_record into a log -- the device's writer with the
 host's reader, rlzero_amd/playlog.py.  The same driver is also built with -fsanitize=address,undefined and run over all inputs."""
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd import playlog
 from rlzero_amd._hip import (PLAY_ENDED, PLAY_FULL, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RESIGNED, PLAY_RESOLVED, PLAY_RUNNING,
                              PLAY_SEARCHED, PLAY_STALLED, PLAY_WOULD_RESIGN)
 from rlzero_amd.selfplay import _splitmix64, batch_pi_and_moves, cap_uniform, move_uniform, resign_uniform
-from test_delta_gather_host import host_clangxx
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 W0 = PLAY_RECORD_WORDS
 IDLE, RUNNING, STALLED = 0, 1, 2
 
@@ -193,44 +187,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'play.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('play', []), ('play_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        """``inputs``: arrays written to files; ``outputs``: dtypes of the files read back.  The files' names follow ``args``."""
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('play', DRIVER)
 
 
 def f64(bits):

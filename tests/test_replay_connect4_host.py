@@ -3,26 +3,24 @@
 rz_replay_add refuses before a launch) -- against ``Connect4Env.step``; the stored record as a root of the search engine against
 ``Connect4Env.from_bitboards`` for every ply (the last CELL lands in plane 2); ``symmetry_tables(..., game='connect4')`` against the
 numpy expressions it stands for; the trainer's host ``ReplayBuffer`` and ``get_equi_data`` entry for entry; the trainer's options.
-A driver with its own main is compiled against the header with ROCm's clang++, as tests/test_replay_reanalyse_host.py compiles its
-driver, and once more with -fsanitize=address,undefined (a stand-alone program); every call runs both and holds their outputs
+A driver with its own main is compiled against the header with ROCm's clang++, by
+tests/host_driver.py, and once more with -fsanitize=address,undefined (a stand-alone program); every call runs both and holds their outputs
 equal.  Nothing here touches a GPU."""
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 import replay_cases as rc
 import replay_connect4_cases as c4
 from rlzero_amd import _hip
 from rlzero_amd.games.connect4.connect4_env import Connect4Env
 from rlzero_amd.replay import pack_positions, symmetry_tables
 from rlzero_amd.selfplay import Trajectory
-from test_delta_gather_host import host_clangxx
-from test_mz_replay_host import CSRC, INCLUDE
 
 WORDS = _hip.BOARD_WORDS
 
@@ -107,43 +105,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'replay_connect4.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('replay_connect4', []), ('replay_connect4_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('replay_connect4', DRIVER)
 
 
 def _games(rows, cols, n_in_row):

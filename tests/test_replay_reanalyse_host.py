@@ -3,24 +3,25 @@ k_replay_update_pi call -- a stored record as a root of the search engine, the p
 the slot of a position and the ticket -- against their Python statements: ``pack_positions`` plus ``GomokuEnv`` stepped through the
 same moves, ``reanalysed_pi`` (bit for bit), ``replay_reanalyse_draws`` (Python integers), and, for the documented deviation, the
 reference's pi expression at T = 1 (``batch_pi_and_moves``) within a bound derived below.  A driver with its own main is compiled
-against the header with ROCm's clang++, as tests/test_mz_reanalyse_host.py compiles its driver, and once more with
+against the header with ROCm's clang++, by
+tests/host_driver.py, and once more with
 -fsanitize=address,undefined (a stand-alone program); every call runs both and holds their outputs equal.  The trainer's options
 are refused by the parser where they make no sense; nothing here touches a GPU."""
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
+from host_driver import CSRC
 from rlzero_amd import _hip
 from rlzero_amd.games.gomoku.gomoku_env import GomokuEnv
 from rlzero_amd.replay import pack_positions, reanalysed_pi, replay_index, replay_reanalyse_draws
 from rlzero_amd.selfplay import Trajectory, batch_pi_and_moves
-from test_delta_gather_host import host_clangxx
-from test_mz_replay_host import CSRC, INCLUDE, same_bits
+from test_mz_replay_host import same_bits
 
 WORDS = _hip.BOARD_WORDS
 
@@ -144,52 +145,16 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'replay_reanalyse.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        # (the header as the main file of a plain C++ compiler: it parses alone, without a HIP include)
-        subprocess.run([cxx, '-std=c++17', '-fsyntax-only', '-Wall', '-Werror', '-Wno-pragma-once-outside-header', '-x', 'c++', '-I', CSRC, '-I', INCLUDE,
-                        os.path.join(CSRC, 'rz_replay_rules.h')], check=True)
-        for name, extra in (('replay_reanalyse', []), ('replay_reanalyse_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('replay_reanalyse', DRIVER)
 
 
 def test_the_header_has_no_hip_include():
     with open(os.path.join(CSRC, 'rz_replay_rules.h')) as f:
         text = f.read()
     assert 'hip/' not in text and '#include "rz_host.h"' not in text
+    # (the header as the main file of a plain C++ compiler: it parses alone)
+    subprocess.run(host_driver.compile_command('-fsyntax-only', '-Wno-pragma-once-outside-header', '-x', 'c++', os.path.join(CSRC, 'rz_replay_rules.h')),
+                   check=True)
     with open(os.path.join(CSRC, 'rz_replay.hip')) as f:
         assert '#include "rz_replay_rules.h"' in f.read()
 

@@ -3,25 +3,21 @@ CPU, against a model that knows no modular arithmetic about items: an array of `
 are written ONE BEHIND THE OTHER, each over whatever lies in its cell, read back as the list of (slot, item) pairs it holds -- the
 newest `capacity` items.
 
-A driver with its own main is compiled against the header with ROCm's clang++ (as tests/test_mz_replay_host.py builds its driver),
+A driver with its own main is compiled against the header with ROCm's clang++ (by tests/host_driver.py),
 once plain and once with -fsanitize=address,undefined -fno-sanitize-recover=all, and run as a stand-alone program over a sequence of
 add sizes.  After EVERY add it reports the ticket before and after, skip(kept), oldest(), cursor, count, stored, slot(t) of every
 item of the add that gets a slot and window_start(first) of every item held; all of it is compared with the model, and no two items
 of one add may share a slot.  The sequences hold adds of 0, 1, exactly the capacity, the capacity + 1 and several times the
 capacity, which take the cursor round the ring five times, for capacities 1, 2, 7 and 2^24 (the largest a store takes); the three
 small capacities go on with runs of small adds that take it round dozens of times more."""
-import filecmp
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
-from test_delta_gather_host import host_clangxx
+import host_driver
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
 STATE_WORDS = 9
 
 DRIVER = r'''
@@ -102,36 +98,15 @@ class Model(object):
         return slots, items
 
 
-@pytest.fixture(scope='module')
-def drivers():
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, 'ring.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        exes = []
-        for name, extra in (('ring', []), ('ring_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exes.append(os.path.join(tmp, name))
-            subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', *extra, '-I', CSRC, src, '-o', exes[-1]], check=True)
-        yield tmp, exes
+drv = host_driver.fixture('ring', DRIVER)
 
 
-def run_ring(drivers, capacity, adds):
+def run_ring(drv, capacity, adds):
     """-> (state int64 [adds][9], slots int32) of the plain build; the sanitized build ran without a report and wrote the same bytes."""
-    tmp, exes = drivers
-    script = os.path.join(tmp, 'script.bin')
-    np.array([capacity] + list(adds), dtype=np.int64).tofile(script)
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-    outs = [[os.path.join(tmp, os.path.basename(exe) + ext) for ext in ('.state', '.slots')] for exe in exes]
-    for exe, files in zip(exes, outs):
-        subprocess.run([exe, script] + files, check=True, env=env)
-    assert filecmp.cmp(outs[0][0], outs[1][0], shallow=False) and filecmp.cmp(outs[0][1], outs[1][1], shallow=False)
-    os.remove(outs[1][1])
-    state = np.fromfile(outs[0][0], dtype=np.int64).reshape(len(adds), STATE_WORDS)
+    state, slots = drv.same(drv.write([np.array([capacity] + list(adds), dtype=np.int64)]), 2)
+    state = np.fromfile(state, dtype=np.int64).reshape(len(adds), STATE_WORDS)
     # (at 2^24 slots an add's report is 128 MB: mapped, not read into memory at once)
-    slots = np.memmap(outs[0][1], dtype=np.int32, mode='r') if os.path.getsize(outs[0][1]) else np.zeros(0, dtype=np.int32)
-    return state, slots
+    return state, np.memmap(slots, dtype=np.int32, mode='r') if os.path.getsize(slots) else np.zeros(0, dtype=np.int32)
 
 
 def sequences(capacity):
@@ -146,10 +121,10 @@ def sequences(capacity):
 
 
 @pytest.mark.parametrize('capacity', [1, 2, 7, 1 << 24])
-def test_the_ring_holds_the_newest_items_where_the_model_holds_them(drivers, capacity):
+def test_the_ring_holds_the_newest_items_where_the_model_holds_them(drv, capacity):
     adds = sequences(capacity)
     assert {0, 1, capacity, capacity + 1, 3 * capacity + 5} <= set(adds)
-    state, slots = run_ring(drivers, capacity, adds)
+    state, slots = run_ring(drv, capacity, adds)
     model, at, wraps, cursor_before = Model(capacity), 0, 0, 0
     for kept, row in zip(adds, state):
         before, current_before, skip, oldest, cursor, count, stored, after, current_after = (int(v) for v in row)

@@ -1,27 +1,20 @@
 """The one 64-bit mix (rlzero_amd/csrc/rz_rng.h: mix64, mulhi64, unit; rlzero_amd/_rng.py: the host's two forms of it) and the
 mini-batch draw built on it (rlzero_amd/csrc/rz_replay_rules.h: replay_index -- what k_replay_sample calls) on the CPU.
 
-A driver with its own main is compiled against the headers with ROCm's clang++ (as tests/test_mz_replay_host.py builds its driver),
+A driver with its own main is compiled against the headers with ROCm's clang++ (by tests/host_driver.py),
 once plain and once with -fsanitize=address,undefined -fno-sanitize-recover=all, and run as a stand-alone program.  mix64 and
 mulhi64 are held to Python integers (the arithmetic written out below, no import of the package's) at 0, 1, 2^32 - 1, 2^32, 2^63,
 2^64 - 1 and a few hundred random 64-bit words; unit at the two ends of its range; replay_index to rlzero_amd.replay.replay_index
 and replay_indices for n_entries from 1 to 2^31 - 1 over a few steps and seeds, one of them above 2^63.  The last test holds the two
 forms of rlzero_amd/_rng.py to each other and to tests/device_streams.py (an independent copy on purpose) on the same words."""
-import os
-import subprocess
-import tempfile
-
 import numpy as np
-import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
 import device_streams
+import host_driver
 from rlzero_amd import _rng
 from rlzero_amd.replay import replay_index, replay_indices
-from test_delta_gather_host import host_clangxx
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 M64 = (1 << 64) - 1
 EDGES = [0, 1, (1 << 32) - 1, 1 << 32, 1 << 63, M64]
 
@@ -100,59 +93,33 @@ def words():
     return EDGES + random
 
 
-@pytest.fixture(scope='module')
-def run():
-    cxx = host_clangxx()
-    assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, 'rng.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        exes = []
-        for name, extra in (('rng', []), ('rng_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exes.append(os.path.join(tmp, name))
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra, '-I', CSRC, '-I', INCLUDE,
-                            src, '-o', exes[-1]], check=True)
-        env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-        def call(what, array, dtypes):
-            path = os.path.join(tmp, 'in.bin')
-            np.ascontiguousarray(array, dtype=np.uint64).tofile(path)
-            got = []
-            for exe in exes:
-                outs = [os.path.join(tmp, 'out%d.bin' % i) for i in range(len(dtypes))]
-                subprocess.run([exe, what, path] + outs, check=True, env=env)
-                got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, dtypes)])
-            for plain, san in zip(*got):   # the sanitized build ran without a report and wrote the same bytes
-                assert plain.tobytes() == san.tobytes()
-            return got[0]
-        yield call
+drv = host_driver.fixture('rng', DRIVER)
 
 
-def test_mix64_and_unit_are_the_integers_arithmetic(run):
+def test_mix64_and_unit_are_the_integers_arithmetic(drv):
     xs = words()
-    mixed, units = run('mix', np.array(xs, dtype=np.uint64), [np.uint64, np.float64])
+    mixed, units = drv.run('mix', [], [np.array(xs, dtype=np.uint64)], [np.uint64, np.float64])
     assert [int(v) for v in mixed] == [mix64_int(x) for x in xs]
     # the unit step: the 53 high bits over 2^53, exact in a double -- 0 at one end, 1 - 2^-53 at the other
     assert units.tolist() == [(x >> 11) / float(1 << 53) for x in xs]
     assert units[xs.index(0)] == 0.0 and units[xs.index(M64)] == 1.0 - 2.0 ** -53 and float(units.max()) < 1.0
     more = [(1 << 11) - 1, 1 << 11]
-    _, edge = run('mix', np.array(more, dtype=np.uint64), [np.uint64, np.float64])
+    _, edge = drv.run('mix', [], [np.array(more, dtype=np.uint64)], [np.uint64, np.float64])
     assert edge.tolist() == [0.0, 2.0 ** -53]
 
 
-def test_mulhi64_is_the_high_half_of_the_product(run):
+def test_mulhi64_is_the_high_half_of_the_product(drv):
     xs = words()
     pairs = [(a, b) for a in EDGES for b in EDGES] + list(zip(xs[6:], reversed(xs[6:]))) + [(x, e) for x in xs[6:40] for e in EDGES]
-    (hi, ) = run('mulhi', np.array(pairs, dtype=np.uint64), [np.uint64])
+    (hi, ) = drv.run('mulhi', [], [np.array(pairs, dtype=np.uint64)], [np.uint64])
     assert [int(v) for v in hi] == [(a * b) >> 64 for a, b in pairs]
 
 
-def test_replay_index_is_the_packages_draw(run):
+def test_replay_index_is_the_packages_draw(drv):
     sizes = [1, 2, 3, 7, 8, 1000, 65536, 722 * 8, (1 << 24) * 8, (1 << 31) - 2, (1 << 31) - 1]
     seeds, steps, n = [0, 7, (1 << 63) + 12345, M64], [0, 1, 2, 1 << 40], 24
     rows = [(seed, step, i, size) for size in sizes for seed in seeds for step in steps for i in range(n)]
-    (index, ) = run('index', np.array(rows, dtype=np.uint64), [np.int64])
+    (index, ) = drv.run('index', [], [np.array(rows, dtype=np.uint64)], [np.int64])
     assert index.tolist() == [replay_index(*row) for row in rows]
     at = 0
     for size in sizes:
@@ -165,7 +132,7 @@ def test_replay_index_is_the_packages_draw(run):
     assert at == len(index)
     # counters beyond a mini-batch's: the chain takes any 64-bit i
     far = [(3, 5, i, 1 << 20) for i in ((1 << 32) - 1, 1 << 32, 1 << 63, M64)]
-    (index, ) = run('index', np.array(far, dtype=np.uint64), [np.int64])
+    (index, ) = drv.run('index', [], [np.array(far, dtype=np.uint64)], [np.int64])
     assert index.tolist() == [replay_index(*row) for row in far]
 
 

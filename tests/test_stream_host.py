@@ -6,24 +6,20 @@ return, no slot waits for an id); the trainer's refusals; and the ranks' payload
 import contextlib
 import importlib.util
 import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+import host_driver
 from oracle.mcts_ref import inverse_cdf_choice, softmax
 from rlzero_amd import playlog
 from rlzero_amd._hip import PLAY_ENDED, PLAY_NO_RESIGN, PLAY_RECORD_WORDS, PLAY_RUNNING, PLAY_SEARCHED, HipError
 from rlzero_amd.selfplay import (BatchedSelfPlay, Epoch, SelfPlayReader, Trajectory, cap_uniform, move_uniform, pack_trajectories, payload_of,
                                  resign_uniform, stream_lookahead, stream_topup)
-from test_delta_gather_host import host_clangxx
 from test_playlog_host import CALIB, FRAC, N_PLAYOUT, PLAIN, PLAYED, SEED, Cfg, Game, Writer, _bits
 
-CSRC = os.path.join(REPO, 'rlzero_amd', 'csrc')
-INCLUDE = os.path.join(REPO, 'include')
 W0 = PLAY_RECORD_WORDS
 INT32_MAX = 2 ** 31 - 1
 
@@ -102,40 +98,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives the output of both, held equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'queue.cpp')
-        with open(src, 'w') as f:
-            f.write('#include <string>\n' + DRIVER)
-        for name, extra in (('queue', []), ('queue_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, array, dtype):
-        self.calls += 1
-        src = os.path.join(self.tmp, 'in%d.bin' % self.calls)
-        np.ascontiguousarray(array).tofile(src)
-        got = []
-        for exe in self.exes:
-            dst = os.path.join(self.tmp, 'out%d.bin' % self.calls)
-            subprocess.run([exe, what] + [str(a) for a in args] + [src, dst], check=True, env=self.env)
-            got.append(np.fromfile(dst, dtype=dtype))
-        assert got[0].tobytes() == got[1].tobytes()   # (the sanitized build ran without a report and wrote the same bytes)
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('queue', '#include <string>\n' + DRIVER)
 
 
 def room(head, valid, cap):
@@ -156,7 +119,7 @@ def test_queue_rules(drv):
         cap = int(rng.randint(1, 40))
         head = int(rng.randint(0, INT32_MAX - 50))
         rows.append((head, head + int(rng.randint(0, cap + 1)), cap))
-    got = drv.run('rules', [], np.array(rows, dtype=np.int32), np.int32).reshape(-1, 3)
+    got = drv.run('rules', [], [np.array(rows, dtype=np.int32)], [np.int32])[0].reshape(-1, 3)
     for (head, valid, cap), (s_head, s_valid, r) in zip(rows, got.tolist()):
         if head >= 0:   # (a negative count is no queue's: only queue_room answers for it)
             assert s_head == (head % cap if cap > 0 else head) and s_valid == (valid % cap if cap > 0 else valid), (head, valid, cap)
@@ -172,7 +135,7 @@ def test_a_ring_played_through(drv, cap, start):
     beyond the room is refused whole, and at the int32 limit the ring refuses instead of wrapping its counts."""
     rng = np.random.RandomState(cap)
     ops = np.stack([rng.randint(0, 2, size=400), rng.randint(0, cap + 2, size=400)], axis=1).astype(np.int32)
-    got = drv.run('ring', [cap, start], ops, np.int64).tolist()
+    got = drv.run('ring', [cap, start], [ops], [np.int64])[0].tolist()
     head = valid = start
     queue, nxt, want = [], 1000, []
     for op, n in ops.tolist():

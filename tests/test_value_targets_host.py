@@ -13,20 +13,19 @@ z at random, a float32 tie M between them at random, lam = fp64((z - M) / (z - q
 of M.  Among those a few per cent come out differently under a fused evaluation (computed here in exact rationals), and the test
 requires that at least one does: the bit comparison with numpy would catch a contracted build."""
 import os
-import subprocess
 import sys
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from conftest import REPO  # noqa: F401  (puts the repository on sys.path)
+import host_driver
 from rlzero_amd._hip import PLAY_RESOLVED, PLAY_RUNNING, PLAY_SEARCHED, PLAY_STALLED
 from rlzero_amd.replay import kept_root_values, mixed_value_targets
 from rlzero_amd.selfplay import Trajectory
-from test_delta_gather_host import host_clangxx
-from test_mz_replay_host import CSRC, INCLUDE, same_bits
+from host_driver import CSRC
+from test_mz_replay_host import same_bits
 from test_playlog_host import Cfg, Game, Writer
 
 DRIVER = r'''
@@ -107,43 +106,7 @@ int main(int argc, char **argv) {
 '''
 
 
-class Driver(object):
-    """The plain and the sanitized build of the driver; ``run`` gives both outputs of one call and holds them equal."""
-
-    def __init__(self, tmp):
-        cxx = host_clangxx()
-        assert cxx is not None, "ROCm's clang++ builds the driver (HIPCC, ROCM_PATH or /opt/rocm)"
-        self.tmp, self.exes, self.calls = tmp, [], 0
-        src = os.path.join(tmp, 'value_targets.cpp')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        for name, extra in (('value_targets', []), ('value_targets_san', ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'])):
-            exe = os.path.join(tmp, name)
-            subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-fno-fast-math', '-Wall', '-Werror', *extra,
-                            '-I', CSRC, '-I', INCLUDE, src, '-o', exe], check=True)
-            self.exes.append(exe)
-        self.env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1')   # (a stand-alone program)
-
-    def run(self, what, args, inputs, outputs):
-        self.calls += 1
-        paths = []
-        for i, arr in enumerate(inputs):
-            paths.append(os.path.join(self.tmp, 'in%d_%d.bin' % (self.calls, i)))
-            np.ascontiguousarray(arr).tofile(paths[-1])
-        got = []
-        for exe in self.exes:
-            outs = [os.path.join(self.tmp, 'out%d_%d.bin' % (self.calls, i)) for i in range(len(outputs))]
-            subprocess.run([exe, what] + [str(a) for a in args] + paths + outs, check=True, env=self.env)
-            got.append([np.fromfile(p, dtype=dt) for p, dt in zip(outs, outputs)])
-        for plain, san in zip(*got):   # the sanitized build ran without a report (it would have exited non-zero) and wrote the same bytes
-            assert plain.tobytes() == san.tobytes()
-        return got[0]
-
-
-@pytest.fixture(scope='module')
-def drv():
-    with tempfile.TemporaryDirectory() as tmp:
-        yield Driver(tmp)
+drv = host_driver.fixture('value_targets', DRIVER)
 
 
 def test_the_library_is_built_without_contraction():

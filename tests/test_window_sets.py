@@ -5,14 +5,13 @@ changed cells -- as unions of the window table's rows, handed over by the select
 The table must be exactly what cell_dist gives (CPU), and the resident search must select, evaluate and count exactly what the
 two-launch step (k_trunk_delta, which keeps the distances and ballots) does on the same leaves (GPU): the same trees bit for bit
 (priors and values come out of the features) and the same delta counters."""
-import os
-import shutil
-import subprocess
+import tempfile
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_driver
+
 RADII, WORDS = 4, 4
 DRIVER = r'''
 #include <cstdio>
@@ -48,15 +47,8 @@ def _words(members):
 
 @pytest.fixture(scope='module')
 def tables():
-    cxx = next((c for c in ('c++', 'g++', 'clang++') if shutil.which(c)), None)
-    assert cxx is not None, 'a host C++ compiler builds the table driver'
-    import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'win.cpp'), os.path.join(tmp, 'win')
-        with open(src, 'w') as f:
-            f.write(DRIVER)
-        subprocess.run([cxx, '-std=c++17', '-O1', '-I', os.path.join(REPO, 'rlzero_amd', 'csrc'), src, '-o', exe], check=True)
-        raw = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout
+        raw = host_driver.probe(tmp, DRIVER)
     t = np.frombuffer(raw, dtype=np.uint64).reshape(6, 6, 256, RADII, WORDS)
     return {(11 + i, 11 + j): t[i, j] for i in range(6) for j in range(6)}
 
