@@ -150,6 +150,30 @@ def test_policy_of_visits(drv, A):
         assert got.reshape(-1, A)[5].tolist() == [np.float32(17 / 50), np.float32(16 / 50), np.float32(17 / 50)]
 
 
+@pytest.mark.parametrize('A', [1, 8])
+def test_policy_and_root_value_at_the_action_limits(drv, A):
+    """One action and eight, the limits of the device buffer: an unvisited root, a single visit, counts whose sum needs 33 bits
+    at A = 8, random rows; and the root value at N = 0, 1 and 40."""
+    rng = np.random.RandomState(40 + A)
+    rows = [[0] * A, [1] + [0] * (A - 1), [0] * (A - 1) + [1], [40] * A, [2 ** 30] * A]
+    vis = np.concatenate((np.array(rows, dtype=np.int32), rng.randint(0, 51, size=(64, A)).astype(np.int32)))
+    got, = drv.run('visits', [A], [vis], [np.float32])
+    got = got.reshape(-1, A)
+    assert same_bits(got, policy_of_visits(vis))
+    assert same_bits(got[0], np.full(A, 1.0 / A, dtype=np.float32))
+    with np.errstate(invalid='ignore'):
+        want = (vis.astype(np.float64) / vis.astype(np.float64).sum(axis=1, keepdims=True)).astype(np.float32)
+    some = vis.sum(axis=1) > 0
+    assert same_bits(got[some], want[some]) and some.sum() >= len(vis) - 2
+    if A == 1:
+        assert (got == 1.0).all()   # one action: the policy is 1 whatever the count, zero included
+    n = np.array([0, 1, 40] * 8, dtype=np.int32)
+    vsum = rng.standard_normal(len(n)) * 9.3
+    value, = drv.run('values', [], [n, vsum], [np.float64])
+    assert same_bits(value, root_value_of(n, vsum))
+    assert same_bits(value, np.array([s / max(int(k), 1) for k, s in zip(n, vsum)], dtype=np.float64))
+
+
 def test_root_value_of(drv):
     rng = np.random.RandomState(5)
     ns, sums = [], []

@@ -130,9 +130,10 @@ drv = host_driver.fixture('mz_target', DRIVER)
 
 
 # ----------------------------------------------------------------------------------------------- hand-made episodes
-def episode_lengths(K, td):
-    """1, 2, K, td_steps, td_steps + 1 and the longest a slot holds (in this order; equal ones stay: a buffer may hold them)."""
-    return [1, 2, K, td, td + 1, MAX_STEPS]
+def episode_lengths(K, td, T=MAX_STEPS):
+    """1, 2, K, td_steps, td_steps + 1 and the longest a slot of T steps holds (in this order; equal ones stay: a buffer may hold
+    them)."""
+    return [1, 2, K, td, td + 1, T]
 
 
 def packed_block(rng, lengths, D, A):
@@ -223,10 +224,10 @@ def same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-def driver_sample(drv, episodes, K, td, discount, draws, A):
+def driver_sample(drv, episodes, K, td, discount, draws, A, T=MAX_STEPS):
     """The six arrays from the header's functions: rows through the driver, the policy rows and the observation looked up here."""
     ep_idx, pos, filler = draws
-    E, T, n = len(episodes), MAX_STEPS, len(ep_idx)
+    E, n = len(episodes), len(ep_idx)
     lengths = np.array([len(ep) for ep in episodes], dtype=np.int32)
     reward, value = np.zeros((E, T)), np.zeros((E, T))
     action = np.zeros((E, T), dtype=np.int32)
@@ -256,6 +257,130 @@ def assert_same_batch(got, want):
         assert same_bits(g, w), name
 
 
+def boundary_kinds(buf, draws, got, A):
+    """How many rows of the batch ``got`` (raw targets: no value transform) of ``draws`` from the host buffer ``buf`` are of each
+    of the four boundary kinds, every such row held to what the rules say about it."""
+    ep_idx, pos, filler = draws
+    K, td, discount = buf.K, buf.td_steps, buf.discount
+    obs, actions, tv, tr, tp, mask = got
+    seen = {'boot == len': 0, 'boot == len - 1': 0, 'pos + k == len': 0, 'past the end': 0}
+    for b in range(len(pos)):
+        ep = buf.episodes[ep_idx[b]]
+        m = len(ep)
+        for k in range(K + 1):
+            i = pos[b] + k
+            if i < m and i + td == m:      # no bootstrap: the discounted rewards to the end alone
+                seen['boot == len'] += 1
+                assert tv[b, k] == np.float32(sum(ep.rewards[i + j] * discount ** j for j in range(td)))
+            if i < m and i + td == m - 1:  # bootstrapped from the last step's root value
+                seen['boot == len - 1'] += 1
+                assert tv[b, k] == np.float32(buf._value_target(ep, i)) and ep.root_values[m - 1] != 0.0
+            if k > 0 and i == m:           # the last step's action and reward are real, policy and mask are off
+                seen['pos + k == len'] += 1
+                assert actions[b, k - 1] == ep.actions[m - 1] and tr[b, k] == np.float32(ep.rewards[m - 1])
+                assert mask[b, k] == 0.0 and tv[b, k] == 0.0 and (tp[b, k] == np.float32(1.0 / A)).all()
+            if k > 0 and i > m:
+                seen['past the end'] += 1
+                assert actions[b, k - 1] == filler[b, k - 1] and tr[b, k] == 0.0 and mask[b, k] == 0.0
+    return seen
+
+
+def kinds_that_exist(K, td, T):
+    """Which boundary kinds a buffer of slots of T steps can show at all.  A return that ends exactly at the episode's end needs
+    an episode of td steps, one bootstrapped from the last step an episode of td + 1; row k = 1 of the last position always has
+    pos + k == len; a row PAST the end needs K >= 2, since pos <= len - 1 puts row 1 at len at the most."""
+    return {'boot == len': T >= td, 'boot == len - 1': T >= td + 1, 'pos + k == len': True, 'past the end': K >= 2}
+
+
+# ----------------------------------------------------------------------------------------------- the corners
+# The limits rz_mz_replay_create accepts (obs_dim 1 .. 16, n_actions 1 .. 8, unroll_steps 1 .. 16, td_steps 1 .. 64), each at its
+# largest and its smallest value, and the trainer's own shape: slots of 500 steps in a ring of hundreds of episodes that wraps.
+# T = 80 is the smallest slot above td + K = 64 + 16.  The CPU tests hold the header to the host buffer at these shapes, the GPU
+# tests (tests/test_mz_replay_limits_gpu.py) the kernels; both take the episodes, the arbiter and the entries from ``corner``.
+CORNERS = {
+    'MAX': dict(D=16, A=8, K=16, td=64, T=80, capacity=5, discount=0.997),
+    'MIN': dict(D=1, A=1, K=1, td=1, T=1, capacity=1, discount=0.5),
+    'TALL': dict(D=16, A=1, K=16, td=1, T=80, capacity=5, discount=0.5),
+    'WIDE': dict(D=1, A=8, K=1, td=64, T=80, capacity=5, discount=0.997),
+    'REAL': dict(D=4, A=2, K=5, td=10, T=500, capacity=300, discount=0.997),
+}
+REAL_CALLS = (350, 250, 100)   # 700 episodes: the first call alone overfills the ring of 300, and the ring wraps twice
+
+
+class Corner(object):
+    """One corner's episodes in the three calls that store them, and the host ``ReplayBuffer`` fed the same episodes: made once
+    (``corner``), shared by the tests and written by none of them.
+    The small corners: the distinct values of 1, 2, K, K + 1, td, td + 1 and T, clipped to T, then two more episodes (2 and 1
+    steps, so that short episodes are among those held at the end); more episodes than the ring has slots, cut into three calls.
+    REAL: 700 lengths drawn from 1 .. 500 with 1, 499 and 500 forced in among the 300 held at the end, in calls of REAL_CALLS."""
+
+    def __init__(self, name):
+        self.name = name
+        self.__dict__.update(CORNERS[name])
+        D, A, K, td, T = self.D, self.A, self.K, self.td, self.T
+        rng = np.random.RandomState(sum(ord(ch) for ch in name))
+        if name == 'REAL':
+            lengths = rng.randint(1, T + 1, size=sum(REAL_CALLS))
+            lengths[[450, 500, 650]] = 1, T - 1, T
+            sizes = REAL_CALLS
+        else:
+            lengths = sorted({min(v, T) for v in (1, 2, K, K + 1, td, td + 1, T)}) + [min(2, T), 1]
+            sizes = (len(lengths) // 3, len(lengths) // 3, len(lengths) - 2 * (len(lengths) // 3))
+        self.lengths = [int(v) for v in lengths]
+        assert len(self.lengths) > self.capacity and min(sizes) >= 1
+        host = self.arbiter(held=[])
+        self.calls, self.held, at = [], [], 0   # (lengths, packed block, Episodes) per call; the arbiter's episodes after it
+        for size in sizes:
+            lens = self.lengths[at:at + size]
+            block = packed_block(rng, lens, D, A)
+            eps = episodes_of(block, lens, D, A)
+            for ep in eps:
+                host.add(ep)
+            self.calls.append((lens, block, eps))
+            self.held.append(list(host.episodes))
+            at += size
+        # the episode held in slot 0 of a ring of `capacity` slots after this many adds: the one past the ring's seam
+        self.seam = self.capacity - len(self.lengths) % self.capacity
+
+    def arbiter(self, call=-1, value_transform=False, held=None):
+        """The host buffer as it stood after ``call``; its episodes are the shared ones (``sample`` only reads them)."""
+        buf = ReplayBuffer(capacity=self.capacity, unroll_steps=self.K, td_steps=self.td, discount=self.discount, seed=11,
+                           value_transform=value_transform)
+        buf.episodes = list(self.held[call]) if held is None else held
+        return buf
+
+    def named(self):
+        """REAL's subset of the episodes held: the oldest, the newest, the shortest, the longest and the two on either side of
+        the ring's seam (the last slot and slot 0)."""
+        lens = [len(ep) for ep in self.held[-1]]
+        return sorted({0, len(lens) - 1, int(np.argmin(lens)), int(np.argmax(lens)), self.seam - 1, self.seam % len(lens)})
+
+    def positions(self):
+        """(ep_idx, pos) of every step held; on REAL of every step of the ``named`` episodes (the CPython arbiter stays in seconds)."""
+        lens = [len(ep) for ep in self.held[-1]]
+        which = self.named() if self.name == 'REAL' else range(len(lens))
+        ep_idx = np.repeat(np.array(list(which), dtype=np.int64), [lens[j] for j in which])
+        return ep_idx, np.concatenate([np.arange(lens[j]) for j in which]).astype(np.int64)
+
+    def entries(self, rng):
+        """The draws ``gather`` is held to: ``positions`` with random fillers; on REAL 512 draws of the sampler's stream as well."""
+        ep_idx, pos = self.positions()
+        filler = rng.randint(self.A, size=(len(ep_idx), self.K)).astype(np.int64)
+        if self.name != 'REAL':
+            return ep_idx, pos, filler
+        more = mz_replay_draws(5, 0, 512, [len(ep) for ep in self.held[-1]], self.K, self.A)
+        return tuple(np.concatenate(pair) for pair in zip((ep_idx, pos, filler), more))
+
+
+_corners = {}
+
+
+def corner(name):
+    if name not in _corners:
+        _corners[name] = Corner(name)
+    return _corners[name]
+
+
 # ----------------------------------------------------------------------------------------------- the tests
 @pytest.mark.parametrize('discount', DISCOUNTS)
 @pytest.mark.parametrize('K,td', CONFIGS)
@@ -279,31 +404,26 @@ def test_rows_equal_the_host_buffers_sample(drv, K, td, discount, A):
     got = driver_sample(drv, episodes, K, td, discount, draws, A)
     assert_same_batch(got, want)
     # the boundary cases are among them, and they look as the rules say
-    ep_idx, pos, filler = draws
-    lens = np.asarray(lengths)[ep_idx]
-    obs, actions, tv, tr, tp, mask = got
-    seen = {'boot == len': 0, 'boot == len - 1': 0, 'pos + k == len': 0, 'past the end': 0}
-    for b in range(len(pos)):
-        ep = episodes[ep_idx[b]]
-        for k in range(K + 1):
-            i, m = pos[b] + k, lens[b]
-            if i < m and i + td == m:      # no bootstrap: the discounted rewards to the end alone
-                seen['boot == len'] += 1
-                assert tv[b, k] == np.float32(sum(ep.rewards[i + j] * discount ** j for j in range(td)))
-            if i < m and i + td == m - 1:  # bootstrapped from the last step's root value
-                seen['boot == len - 1'] += 1
-                assert tv[b, k] == np.float32(buf._value_target(ep, i)) and ep.root_values[m - 1] != 0.0
-            if k > 0 and i == m:           # the last step's action and reward are real, policy and mask are off
-                seen['pos + k == len'] += 1
-                assert actions[b, k - 1] == ep.actions[m - 1] and tr[b, k] == np.float32(ep.rewards[m - 1])
-                assert mask[b, k] == 0.0 and tv[b, k] == 0.0 and (tp[b, k] == np.float32(1.0 / A)).all()
-            if k > 0 and i > m:
-                seen['past the end'] += 1
-                assert actions[b, k - 1] == filler[b, k - 1] and tr[b, k] == 0.0 and mask[b, k] == 0.0
+    seen = boundary_kinds(buf, draws, got, A)
     assert all(seen.values()), seen
 
 
-@pytest.mark.parametrize('A', [2, 3, 8])
+@pytest.mark.parametrize('name', sorted(CORNERS))
+def test_rows_equal_the_host_buffers_sample_at_the_corners(drv, name):
+    """The same at the limits rz_mz_replay_create accepts and at the trainer's shape: the corner's entries (every (episode,
+    position) held; a subset on REAL) bit for bit, and every boundary kind that exists at the shape is among them."""
+    c = corner(name)
+    buf = c.arbiter()
+    draws = c.entries(np.random.RandomState(7))
+    want = host_sample(buf, draws, c.A)
+    got = driver_sample(drv, buf.episodes, c.K, c.td, c.discount, draws, c.A, T=c.T)
+    assert_same_batch(got, want)
+    seen = boundary_kinds(buf, draws, got, c.A)
+    print('%s: %d entries, %d rows, boundary kinds %r' % (name, len(draws[0]), len(draws[0]) * (c.K + 1), seen))
+    assert {kind: n > 0 for kind, n in seen.items()} == kinds_that_exist(c.K, c.td, c.T), seen
+
+
+@pytest.mark.parametrize('A', [1, 2, 3, 8])
 def test_policy_of_a_packed_record(drv, A):
     """visits / sum(visits) in fp64, cast to float32: EpisodeSeq.fields_of_packed's bits; a final policy is only cast."""
     D = 4
@@ -319,7 +439,7 @@ def test_policy_of_a_packed_record(drv, A):
     assert same_bits(again, got)
 
 
-@pytest.mark.parametrize('K,A', [(2, 2), (5, 3), (16, 8)])
+@pytest.mark.parametrize('K,A', [(1, 1), (2, 2), (5, 3), (16, 8)])
 def test_draws_equal_the_restatement(drv, K, A):
     lengths = np.array([1, 2, 5, 500, 7, 12, 1], dtype=np.int32)
     for seed, step in ((0, 0), (13, 1), (2 ** 64 - 1, 2 ** 40 + 3)):
