@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 47
+#define RZ_ABI_VERSION 48
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -756,6 +756,18 @@ int rz_net_delta_trunk_engine(rz_net *net, rz_engine *engine, void *stream);
  * cells, conv2 tiles of 16 cells, root scans of the resident search answered from the pre-scan, and -- of workgroup 0 of the LAST resident launch -- its shader-clock cycles >> 8 and its ticks
  * of the constant 100 MHz clock: the clock the search ran at = 256 [6] / (10 ns [7])} */
 int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
+/* THE FEATURE MEMO of the resident search without policy features (ABI 48; rz_net_search_resident_values on k_delta_res).  Most leaves
+ * of a move are root + a + b; with the two stones 7 or more cells apart (Chebyshev) no head feature sees both, so the 7 x 7 windows
+ * of the two value features around a (the mover's stone) and around b (the other side's stone, the last move) are kept per game the
+ * first time a leaf computes them, and a later leaf whose two windows are there lays them over the root base's planes instead of
+ * running the trunk: the same bits.  2 x cells entries of 512 bytes per rz_net_delta_reserve()d game; whatever builds or drops a
+ * game's bases clears its entries.  on = 0: every leaf runs its passes, as before ABI 48, and the entries' memory is released (a change
+ * of the switch synchronises and drops the bases; call it before rz_net_delta_reserve to never reserve it).  Where the memory cannot be
+ * had the search runs without the memo; the base cache does not fail for it.  Default: on.  A leaf served from the memo counts, in
+ * rz_net_delta_stats, among the leaves against a base with the tiles its passes WOULD have run (the counters of the routes stay equal).
+ * rz_net_delta_memo_stats (synchronises): {leaves served from the memo, entries filled} since the last rz_net_delta_stats(reset). */
+int rz_net_delta_memo(rz_net *net, int32_t on);
+int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out2);
 /* RESIDENT SEARCH -- n_sims consecutive simulations of every active game of `engine` (AlphaZeroMCTS.simulate's loop,
  * alphazero_mcts.py:82-85) in ONE launch, one workgroup per game: trunk -> value head -> expand / backup -> next selection without
  * a kernel boundary, the leaf handed from the tree code to the trunk through LDS.  Kernels that hold a whole CU (151 KB of LDS: boards

@@ -5,6 +5,9 @@ game 0), from a library built with -DRZ_NET_PROFILE (profiles/microbench/build_n
 
 --values: the search of policy on demand (k_delta_res<false>: no policy features; the engine here has no move step, so the decision
 is forced).
+The memo (rz_memo.h; --values only): the share of the timed search's leaves served from it and the entries filled (delta_stats), and
+the patch copy's cycles PER HIT -- slot 5 is ticked by a served leaf from the verdict to its two stores (and by conv1 of a pass without
+a base: the row is printed only when no leaf went without one).  RZ_DELTA_MEMO=0 in the environment: the kernel without the memo.
 --backup-rows: the library was built with -DRZ_BKP_TICKS=1 (rz_delta.h): the slots of the selection's ticks 1 .. 3 hold the rows of expand +
 backup, slot 22 wave 1's conv2.
 """
@@ -66,4 +69,9 @@ for games in sizes:
         games, sims, us, total, total / us / 1e3, st['tiles3'] / max(1, st['delta'] + st['no_base']), st['tiles2'] / max(1, st['delta'] + st['no_base']),
         st['cells'] / max(1, st['delta'] + st['no_base']), st['no_base']))
     print('   ' + '  '.join('%s=%d' % (nm, out[k] / sims) for k, nm in NAMES) + '  prescans=%d' % st['prescans'], flush=True)
+    leaves = max(1, st['delta'] + st['no_base'])
+    hits, fills = st.get('memo_hits', 0), st.get('memo_fills', 0)   # (a library from before the memo has neither)
+    print('   memo: %d of %d leaves served (%.1f %%), %d entries filled (%.1f a game)' % (hits, leaves, 100.0 * hits / leaves, fills, fills / games)
+          + ('; game 0, wave 0: patch copy %d cycles per hit (slot 5 / the launch\'s mean hits per game)' % (out[5] / (hits / games))
+             if hits and st['no_base'] == 0 else ''), flush=True)
     eng.close(); ev.hip.close()

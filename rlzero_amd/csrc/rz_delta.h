@@ -38,6 +38,7 @@
 
 #include "rlzero_hip.h"
 #include "rz_gather.h"
+#include "rz_memo.h"
 #include "rz_net_dev.h"
 #include "rz_net_rows.h"
 #include "rz_net_split.h"
@@ -92,8 +93,10 @@ static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's 
 // the resident search's hand-over from the selection to the next leaf's prologue (leaf_windows): the four window sets of pass -1
 // (radius 1 .. 4) as 4 x 4 words, their words' popcounts, the verdict (use_delta | parity << 1 | nD << 8)
 constexpr int kWinSets = rzw::kRadii * rzw::kWords, kWinLds = kWinSets * 8 + kWinSets * 4 + 16;
-static_assert(2 * (kLdsBytes + 512 * 4 + 4 * 64 * 4 + 80 + kWinLds + (int)sizeof(rzt::RootPre) + 512) <= 160 * 1024,
-              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan)");
+// (k_delta_res' own arrays, exactly: 81 376 bytes with the 96-byte RootPre -- 544 below half a CU)
+constexpr int kResLds = kLdsBytes + 512 * 4 + 4 * 64 * 4 + (2 * RZ_BOARD_WORDS + 2) * 8 + kWinLds + (int)sizeof(rzt::RootPre) + rzm::kBitmapWords * 8;
+static_assert(2 * kResLds <= 160 * 1024,
+              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan, the memo's valid bits)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
 
 // The base cache: per game a header (the stones the two bases were computed from) and per (game, parity) the records.
@@ -102,6 +105,7 @@ struct BaseHdr {
     uint64_t stones[2 * RZ_BOARD_WORDS];
     int32_t to_move, valid, pad[2];
 };
+constexpr int kStats = 16;   // DeltaArgs::stats
 constexpr size_t kBaseC2 = (size_t)kCells * 128, kBaseV = kBaseC2 + (size_t)kCells * 256, kBaseBytes = kBaseV + (size_t)6 * kCells * 4;
 
 struct DeltaArgs {
@@ -110,13 +114,18 @@ struct DeltaArgs {
                              // head features [6][kCells] f32 (behind their ReLU)
     const uint8_t *active;   // mode 0: games whose flag is 0 are skipped (NULL: none is)
     float *feat32;           // the features as f32 [board][6 S] (tests; NULL otherwise)
-    unsigned *stats;         // [8] counters (NULL: none): delta leaves, leaves without a base, conv3 tiles, changed cells, conv2 tiles, root scans
+    unsigned *stats;         // [kStats] counters (NULL: none): delta leaves, leaves without a base, conv3 tiles, changed cells, conv2 tiles, root scans
                              // answered from the pre-scan (k_delta_res), and of workgroup 0 of the LAST resident launch: shader-clock
-                             // cycles >> 8, ticks of the constant 100 MHz clock
+                             // cycles >> 8, ticks of the constant 100 MHz clock; [8], [9]: leaves served from the memo, entries filled
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
     const uint64_t *win;     // k_delta_res: the window table of the net's board (rz_window.h; NULL elsewhere)
+};
+// k_delta_res<false>'s feature memo (rz_memo.h)
+struct MemoArgs {
+    char *memo;              // [games][2 S entries] (NULL: off, every leaf runs its passes)
+    uint64_t *bits;          // [games][rzm::kBitmapWords] the valid bits (k_memo_clear in front of every mode-1 launch)
 };
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -1044,12 +1053,20 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (TRACE && tid0 == 0) rz_trace_write(later.trace, RZ_TRACE_TRUNK, deferred ? slot_ : 0, board, trace_t0);
 }
 
+// The memo's valid bits of the first n_games games -> 0, in front of every launch of mode 1: the memo patches the bases that were there
+// before, none of it is valid any more.  (a kernel of its own: k_trunk_delta keeps its registers, and a captured search needs no memset node)
+__global__ void k_memo_clear(uint64_t *bits, int n_words) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) bits[i] = 0ull;
+}
+
 // The hand-over of k_delta_res: wave 0, behind a selection (the leaf in LDS: select_body's lds_leaf), sets the next leaf against the root
 // -- changed_cells' verdict -- and, for pass -1, the cells within Chebyshev distance 1 .. 4 of its changed cells: per radius the union
 // of the window table's rows of the (at most kMaxD) changed cells.  Lane 16 i + 4 (r - 1) + w reads word w of the radius-r row of
 // changed cell i, two lane swaps OR the four cells' rows.  -> ws: [kWinSets] words, [kWinSets] their popcounts, the verdict.
 // (the lane's word of its changed cell's rows, zero without one -> the sets, the popcounts, the verdict)
-__device__ __forceinline__ void windows_store(uint64_t row, bool use_delta, int parity, int nD, int lane, uint64_t *ws) {
+// memo: the memo's word of this leaf (ResHook::leaf; 0: the memo neither serves nor learns it), behind the verdict
+__device__ __forceinline__ void windows_store(uint64_t row, bool use_delta, int parity, int nD, int lane, uint64_t *ws, int memo = 0) {
     unsigned lo = (unsigned)row, hi = (unsigned)(row >> 32);
     {   // (a swap leaves the lane's own value and its partner's: the OR does not care which is which)
         const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
@@ -1067,8 +1084,15 @@ __device__ __forceinline__ void windows_store(uint64_t row, bool use_delta, int 
         ws[lane] = v;
         cnt[lane] = __popcll(v);
     }
-    if (lane == 0) cnt[kWinSets] = (use_delta ? 1 : 0) | (parity << 1) | (nD << 8);
+    if (lane == 0) {
+        cnt[kWinSets] = (use_delta ? 1 : 0) | (parity << 1) | (nD << 8);
+        cnt[kWinSets + 1] = memo;
+    }
 }
+static_assert(kWinLds >= kWinSets * 12 + 8, "the verdict and the memo's word");
+// the memo's word of a leaf: a far pair (rzm::far_pair) | served from the memo << 1 | entry (a, OWN) to be filled << 2 | entry
+// (b, OPP_LAST) to be filled << 3 | a << 8 | b << 16
+constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8;
 __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
                                              int lane, uint64_t *ws) {
     uint64_t ls[8];
@@ -1091,6 +1115,9 @@ __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uin
     }
     const bool any = dy >= 0;   // (no such cell: -100)
     const uint64_t row = da.win[(any ? dy * BW + dx : 0) * kWinSets + (lane & (kWinSets - 1))];
+    // (the memo's word stays 0: the first leaf of a CONTINUED search -- selected by another launch, its path's cells are not known
+    // here -- runs its passes and fills nothing even where it is a far pair with valid entries.  One leaf per launch, the same bits;
+    // rzm::hit and memo_probe.py's classify state the rule for leaves selected inside the launch)
     windows_store(any ? row : 0ull, use_delta, parity, nD, lane, ws);
 }
 
@@ -1140,9 +1167,27 @@ struct ResHook {
         any0 = stones > 0 && last >= 0 && last < kCells;
         row = win[(any0 ? last : 0) * kWinSets + (lane & (kWinSets - 1))];
     }
+    // The memo (rz_memo.h): the word of the valid bits that holds the level's cell -- kind OWN at level 0, OPP_LAST at level 1 -- is
+    // asked for with the cell's rows (LDS: mbits, all zero without a memo), every level its read, none under a branch; leaf() tests
+    // the two bits.
+    const uint64_t *mbits;
+    bool memo_on;
+    int bw_rcp, BW, c0, c1;
+    uint64_t mw0, mw1;
     __device__ __forceinline__ void cell(int level, int c, int lane) {
         const uint64_t v = win[c * kWinSets + (lane & (kWinSets - 1))];
         row = (lane >> 4) == level ? v : row;
+        const uint64_t w = mbits[rzm::bit_word(level & 1, c)];
+        c0 = level == 0 ? c : c0, mw0 = level == 0 ? w : mw0;
+        c1 = level == 1 ? c : c1, mw1 = level == 1 ? w : mw1;
+    }
+    // the memo's word of a leaf at depth d (windows_store): the rule is rzm::far_pair's, the bits those asked for above
+    __device__ __forceinline__ int memo_word(int d) const {
+        const int a = __builtin_amdgcn_readfirstlane(c0), b = __builtin_amdgcn_readfirstlane(c1);
+        const int ay = (a * bw_rcp) >> 16, ax = a - ay * BW, by = (b * bw_rcp) >> 16, bx = b - by * BW;
+        const bool far = memo_on && rzm::far_pair_yx(d, base_ok, ay, ax, by, bx);
+        const bool va = (uni64(mw0) >> (a & 63)) & 1ull, vb = (uni64(mw1) >> (b & 63)) & 1ull;
+        return far ? kMemoFar | (va && vb ? kMemoHit : 0) | (va ? 0 : kMemoFillA) | (vb ? 0 : kMemoFillB) | (a << 8) | (b << 16) : 0;
     }
     // Behind the descent (select_body calls it once, whichever way the descent ended): the leaf to LDS, the hand-over of its windows --
     // the rows were requested during the descent, and the verdict is changed_cells' without the leaf: against a base that is the root
@@ -1163,7 +1208,7 @@ struct ResHook {
         }
         const bool mine = d == 0 ? (lane < 16 && any0) : (lane >> 4) < d;
         const int nD = d == 0 ? (any0 ? 1 : 0) : d;
-        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws);
+        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, memo_word(d));
         if (release) __syncthreads();
 #ifdef RZ_NET_PROFILE
         {   // -> net_prof[18]: the selection up to the release
@@ -1205,7 +1250,8 @@ struct ResHook {
 // k_trunk_policy_rows forms them at the flush, for the records the flush lists.
 constexpr int kResVrow = 512;
 template <bool POL>
-__global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__restrict__ store16, DeferredOut later, DeltaArgs da, ResArgs<true> res) {
+__global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__restrict__ store16, DeferredOut later, DeltaArgs da, ResArgs<true> res,
+                                                      MemoArgs mm) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     __shared__ float res_vrow[kResVrow];
     __shared__ float res_part[rzt::kDefWaves][rzt::kWave];
@@ -1214,6 +1260,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) uint64_t res_leaf[2 * RZ_BOARD_WORDS + 2];
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
+    __shared__ __attribute__((aligned(16))) uint64_t res_mbits[rzm::kBitmapWords];   // the game's memo: its valid bits (zero without one)
     // (rz_set_playouts' order: the games with the most simulations in the first round of a grid of more than two games per CU)
     const int game = res.order != nullptr ? res.order[blockIdx.x] : (int)blockIdx.x;
     if ((unsigned)game >= (unsigned)res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier; an order's entry out of range: no game)
@@ -1258,6 +1305,14 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         init_maps(lds, tid0);
         for (int i = tid0; i < kResVrow; i += 256) res_vrow[i] = 0.0f;
     }
+    // The memo (rz_memo.h; the search without policy features alone: a leaf it serves has no policy planes to store).  The valid bits
+    // live in LDS for the launch and are written through to memory as entries fill, so that a continued search finds them.
+    const bool memo_on = !POL && mm.memo != nullptr;
+    char *const memo_g = memo_on ? mm.memo + (size_t)game * (size_t)rzm::game_bytes(nd.S) : nullptr;   // (neither is formed, let alone read, without a memo)
+    uint64_t *const memo_bits_g = memo_on ? mm.bits + (size_t)game * rzm::kBitmapWords : nullptr;
+    if (tid0 < rzm::kBitmapWords) res_mbits[tid0] = memo_on ? memo_bits_g[tid0] : 0ull;
+    int memo_hits = 0, memo_fills = 0;
+    bool head_stored = false;   // (the head weights go to LDS in the first leaf that runs its passes)
     if (tid0 == 0) res_pre.scan = res_pre.valid = res_pre.answered = 0;   // (no stash yet: a select_first == 0 launch's first selection was not made here)
     ResHook hook;
     hook.pre = &res_pre;
@@ -1269,6 +1324,11 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     hook.ws = res_win;
     hook.base_ok = base_ok;
     hook.release = false;   // (the first selection: every wave meets the barrier behind it)
+    hook.mbits = res_mbits;
+    hook.memo_on = memo_on;
+    hook.bw_rcp = da.bw_rcp, hook.BW = BW;
+    hook.c0 = hook.c1 = 0;
+    hook.mw0 = hook.mw1 = 0ull;
 #ifdef RZ_NET_PROFILE
     hook.prof = &prof;
     long long pre_cycles = 0, pre_wait = 0;   // wave 1: the pre-scan, the barrier behind it (= its slack under expand + backup)
@@ -1316,9 +1376,72 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         leaf.vdst = res_vrow;
         leaf.dst32 = nullptr;
         leaf.deferred = true;
-        leaf.store_head = sim == 0;
+        leaf.store_head = !head_stored;
         NET_TICK(0);
-        const int n_tiles = delta_passes<true, POL ? 0 : 4, 6>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
+        // ---- the memo (rz_memo.h): a leaf root + a + b with the two stones 7 or more apart, both of whose windows an earlier leaf of
+        // this move has left in the game's memo, needs no trunk -- ONE workgroup-uniform branch around pass -1 and its feature stage.
+        // Thread = cell asks for its two value features at a SELECTED address -- the window of a, the window of b or the base's planes:
+        // two unconditional loads -- and stores them where the feature stage would have.  The counters see the tiles pass -1 would
+        // have run (the window sets' popcounts were handed over as for any leaf).
+        const int memo_w = POL ? 0 : __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_win + kWinSets)[kWinSets + 1]);
+        int n_tiles;
+        if (!POL && (memo_w & kMemoHit)) {
+            const int a = (memo_w >> 8) & 255, b = (memo_w >> 16) & 255, S = nd.S;
+            const int ay = (a * da.bw_rcp) >> 16, ax = a - ay * BW, by = (b * da.bw_rcp) >> 16, bx = b - by * BW;
+            const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
+            int slot;
+            const int src = rzm::source_of_yx(cy, cx, ay, ax, by, bx, &slot);
+            const int e = rzm::entry_index(src == rzm::kFromA ? rzm::kOwn : rzm::kOppLast, src == rzm::kFromA ? a : b, S);
+            const float *pm = reinterpret_cast<const float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot < 0 ? 0 : slot, 0));
+            const float *pb = reinterpret_cast<const float *>(leaf.base + kBaseV) + 4 * kCells + tid_s;
+            const float *p = src == rzm::kFromBase ? pb : pm;
+            const float v4 = p[0], v5 = p[src == rzm::kFromBase ? kCells : 1];
+            if (tid_s < S) {
+                res_vrow[tid_s] = v4;
+                res_vrow[S + tid_s] = v5;
+            }
+            const int *cnt = reinterpret_cast<const int *>(res_win + kWinSets);
+            int t2 = 0, t3 = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                t2 += __builtin_amdgcn_readfirstlane(cnt[4 * 1 + w]);
+                t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]);
+            }
+            n_tiles = ((t3 + 15) >> 4) | (((t2 + 15) >> 4) << 16);
+            memo_hits += 1;
+            NET_TICK(5);   // the memo's patch copy (a search whose leaves all have a base: conv1 of the passes without one never ticks here)
+        } else {
+            n_tiles = delta_passes<true, POL ? 0 : 4, 6>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
+            head_stored = true;
+            // a far pair that ran its passes leaves the windows the memo does not hold yet: the threads within 3 of a / of b store the
+            // two values they have just put into the value row, the valid bits follow behind the stores (LDS: this wave 0 tests them;
+            // memory: a later launch's copy).  Only this workgroup ever reads its game's memo, the next reader is barriers away.
+            if (!POL && (memo_w & (kMemoFillA | kMemoFillB)) && use_delta) {
+                const int a = (memo_w >> 8) & 255, b = (memo_w >> 16) & 255, S = nd.S;
+                const int ay = (a * da.bw_rcp) >> 16, ax = a - ay * BW, by = (b * da.bw_rcp) >> 16, bx = b - by * BW;
+                const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
+                int slot;
+                const int src = rzm::source_of_yx(cy, cx, ay, ax, by, bx, &slot);
+                const bool fill = tid_s < S && ((src == rzm::kFromA && (memo_w & kMemoFillA)) || (src == rzm::kFromB && (memo_w & kMemoFillB)));
+                if (fill) {
+                    const int e = rzm::entry_index(src == rzm::kFromA ? rzm::kOwn : rzm::kOppLast, src == rzm::kFromA ? a : b, S);
+                    float *pm = reinterpret_cast<float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot, 0));
+                    pm[0] = res_vrow[tid_s];
+                    pm[1] = res_vrow[S + tid_s];
+                }
+                if (tid_s == 0) {
+                    if (memo_w & kMemoFillA) {
+                        const int w = rzm::bit_word(rzm::kOwn, a);
+                        memo_bits_g[w] = res_mbits[w] = res_mbits[w] | (1ull << (a & 63));
+                    }
+                    if (memo_w & kMemoFillB) {
+                        const int w = rzm::bit_word(rzm::kOppLast, b);
+                        memo_bits_g[w] = res_mbits[w] = res_mbits[w] | (1ull << (b & 63));
+                    }
+                }
+                memo_fills += ((memo_w & kMemoFillA) ? 1 : 0) + ((memo_w & kMemoFillB) ? 1 : 0);
+            }
+        }
         tiles_total += n_tiles & 0xffff;
         tiles2_total += n_tiles >> 16;
         deltas += use_delta ? 1 : 0;
@@ -1366,6 +1489,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
             // res_part, which the tail does not touch.)  The last simulation: no selection, no barrier, for anyone.
             if (more) {
                 hook.depth = 0, hook.any0 = false, hook.row = 0ull;   // (nothing of the last selection's is kept)
+                hook.c0 = hook.c1 = 0, hook.mw0 = hook.mw1 = 0ull;
                 hook.release = true;
                 // (the lane number opaque once more: what the selection derives from it is not worked out at the top of the simulation
                 // and kept -- spilled -- across the trunk)
@@ -1429,6 +1553,10 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         atomicAdd(da.stats + 3, (unsigned)cells_total);
         atomicAdd(da.stats + 4, (unsigned)tiles2_total);
         atomicAdd(da.stats + 5, (unsigned)res_pre.answered);
+        if (memo_on) {
+            atomicAdd(da.stats + 8, (unsigned)memo_hits);
+            atomicAdd(da.stats + 9, (unsigned)memo_fills);
+        }
         if (game == 0) {   // the clock this search ran at: cycles / (ticks x 10 ns)
             da.stats[6] = (unsigned)((__builtin_readcyclecounter() - clk0) >> 8);
             da.stats[7] = (unsigned)(__builtin_amdgcn_s_memrealtime() - rt0);

@@ -284,9 +284,12 @@ int rz_create(const rz_config *cfg, rz_engine **out) {
     }
     D.logtab = e->d_logtab;
     D.line_tab = e->d_line_tab;
-    // zero the small state; arenas need no initialisation beyond the root slot
+    // zero the small state.  The search itself needs nothing of the arenas beyond the root slot, but a node reserves child slots it
+    // has not visited yet (the doubling child vectors) and rz_copy_arena hands them to the host with the rest: they read zero, not
+    // what an engine freed earlier left in the memory (tests/test_noise_streams_gpu.py compares two engines' snapshots slot by slot)
     hipError_t herr = hipSuccess;
     auto zero = [&](void *p, size_t bytes) { if (herr == hipSuccess) herr = hipMemset(p, 0, bytes); };
+    zero(D.R, (size_t)slots * 2 * sizeof(*D.R)); zero(D.P, (size_t)G * 2 * D.pcap * sizeof(*D.P));
     zero(D.cur_arena, G * 4); zero(D.top, G * 4); zero(D.ptop, G * 4); zero(D.nblk, G * 4);
     zero(D.root_stones, G * 2 * kWords * 8); zero(D.root_to_move, G * 4);
     zero(D.leaf_node, GL * 4); zero(D.leaf_depth, GL * 4); zero(D.leaf_fresh, GL * 4);

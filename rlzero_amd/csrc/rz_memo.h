@@ -1,0 +1,87 @@
+// rz_memo.h -- the per-move feature memo of k_delta_res<false> (rz_delta.h): plain C++, no HIP include, so that the CPU can test the
+// rule and the layout (tests/test_delta_memo_host.py); the kernel and rz_net.hip call these functions.
+//
+// What is remembered.  Under the reference's selection rule most leaves of a move are root + a + b: a the root mover's stone, b the
+// other side's stone and the last move.  A value feature at cell c depends on the input cells within Chebyshev distance 3 of c (three
+// 3 x 3 convolutions, 1 x 1 heads).  With distance(a, b) >= 7 no cell has both stones in its field, so every cell of the leaf has
+//   - within 3 of a: the feature it has in "root + a as the mover's stone, not the last move"         (kind OWN),
+//   - within 3 of b: the feature it has in "root + b as the other side's stone and the last move"    (kind OPP_LAST),
+//   - elsewhere:     the parity-0 base's value,
+// and the first two do not depend on the other stone: an entry (cell, kind) holds the 7 x 7 window of the two value features around the
+// cell, filled by the first far-apart leaf that computes it and laid over the base's planes by every later one (a HIT: no trunk).
+// rz_delta.h's invariant -- a cell's accumulator sees its products in a fixed order, whatever tile it sits in -- makes the window's
+// values the bits the leaf's own passes would compute.
+//
+// Layout.  Per game 2 x S entries (S = cells of the net's board), entry kind * S + cell, kEntryBytes = 512 apart: 49 slots
+// (dy + 3) * 7 + (dx + 3) of two f32 (392 bytes used; off-board slots are never written or read).  The pitch is a multiple of the
+// 128-byte line, so no line holds parts of two entries: an entry's lines are written once per base (its valid bit is clear until then)
+// and read only behind that, by the one workgroup that owns the game -- a line can never sit in the CU's L1 from before its entry was
+// written, which a denser pitch (392 or 448 bytes) would allow through the neighbouring entry's reads.  Plain loads therefore; the
+// price is 23 % of unused memory.  Per game a valid bitmap of 2 kinds x 256 bits (kBitmapWords 64-bit words, kind-major), cleared
+// wherever the game's bases are built or invalidated: a memo never outlives the base it patches.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define RZM_FN __host__ __device__ inline
+#else
+#define RZM_FN inline
+#endif
+
+namespace rzm {
+
+constexpr int kOwn = 0, kOppLast = 1;             // the kinds
+constexpr int kRadius = 3, kSide = 2 * kRadius + 1, kSlots = kSide * kSide;   // the window of a head feature: 7 x 7
+constexpr int kFeatures = 2;                      // the value planes (head outputs 4 and 5)
+constexpr int kEntryBytes = 512, kLineBytes = 128;
+constexpr int kMinDist = 2 * kRadius + 1;         // 7: no cell within kRadius of both
+constexpr int kBitmapWords = 2 * 4;               // uint64 words of a game's valid bits: [kind][256 cells]
+static_assert(kSlots * kFeatures * 4 <= kEntryBytes && kEntryBytes % kLineBytes == 0, "an entry owns its lines");
+
+// sources of a cell's value features on a hit
+constexpr int kFromBase = 0, kFromA = 1, kFromB = 2;
+
+RZM_FN int entries_per_game(int S) { return 2 * S; }
+RZM_FN long long game_bytes(int S) { return (long long)entries_per_game(S) * kEntryBytes; }
+RZM_FN int entry_index(int kind, int cell, int S) { return kind * S + cell; }
+// byte offset of feature f of window slot `slot` inside an entry
+RZM_FN int slot_offset(int slot, int f) { return (slot * kFeatures + f) * 4; }
+RZM_FN int bit_word(int kind, int cell) { return kind * 4 + (cell >> 6); }
+
+RZM_FN int abs_i(int v) { return v < 0 ? -v : v; }
+RZM_FN int cheb(int y0, int x0, int y1, int x1) {
+    const int dy = abs_i(y0 - y1), dx = abs_i(x0 - x1);
+    return dy > dx ? dy : dx;
+}
+// the window slot of cell (cy, cx) around the centre (y, x), -1 outside the window
+RZM_FN int slot_of(int cy, int cx, int y, int x) {
+    const int dy = cy - y, dx = cx - x;
+    return abs_i(dy) <= kRadius && abs_i(dx) <= kRadius ? (dy + kRadius) * kSide + dx + kRadius : -1;
+}
+
+// A leaf whose path from the root is `depth` cells, a then b (board cells y * BW + x), evaluated against a base that is the parity-0
+// base of the root (base_is_root: the header equals the root): can the memo serve or learn it at all?
+// (the _yx forms take board coordinates: the kernel divides by the width with its own reciprocal)
+RZM_FN bool far_pair_yx(int depth, bool base_is_root, int ay, int ax, int by, int bx) {
+    return depth == 2 && base_is_root && cheb(ay, ax, by, bx) >= kMinDist;
+}
+RZM_FN bool far_pair(int depth, bool base_is_root, int a, int b, int BW) {
+    return far_pair_yx(depth, base_is_root, a / BW, a % BW, b / BW, b % BW);
+}
+RZM_FN bool valid_bit(const uint64_t *bits, int kind, int cell) { return (bits[bit_word(kind, cell)] >> (cell & 63)) & 1ull; }
+// the hit rule: a far pair with both entries valid
+RZM_FN bool hit(int depth, bool base_is_root, int a, int b, int BW, const uint64_t *bits) {
+    return far_pair(depth, base_is_root, a, b, BW) && valid_bit(bits, kOwn, a) && valid_bit(bits, kOppLast, b);
+}
+
+// where cell (cy, cx) of a hit's leaf takes its value features from, and the window slot there (far pair: at most one window holds it)
+RZM_FN int source_of_yx(int cy, int cx, int ay, int ax, int by, int bx, int *slot) {
+    const int sa = slot_of(cy, cx, ay, ax), sb = slot_of(cy, cx, by, bx);
+    *slot = sa >= 0 ? sa : sb;
+    return sa >= 0 ? kFromA : sb >= 0 ? kFromB : kFromBase;
+}
+RZM_FN int source_of(int cy, int cx, int a, int b, int BW, int *slot) {
+    return source_of_yx(cy, cx, a / BW, a % BW, b / BW, b % BW, slot);
+}
+
+}  // namespace rzm

@@ -99,8 +99,11 @@ struct rz_net {
     DevBuf<unsigned> d_delta_stats;
     DevBuf<uint8_t> d_base_ones;      // [base_games] of 1: the `active` flags of a caller that has none
     DevBuf<uint64_t> d_win;           // the window table of the net's board (rz_window.h; the board is fixed per net): k_delta_res
+    DevBuf<char> d_memo;              // the feature memo of k_delta_res<false> (rz_memo.h): [base_games][2 S entries].  Its valid bits lie
+                                      // BEHIND the headers in d_base_hdr (memo_bits), so that whatever clears the headers clears them
     int base_games = 0;
     bool delta_resident = true;       // rz_net_delta_resident: rz_net_search_resident runs k_delta_res where the cache allows
+    bool delta_memo = true;           // rz_net_delta_memo: k_delta_res<false> serves far-apart two-stone leaves from the memo
 };
 
 namespace {
@@ -166,6 +169,21 @@ DeferredOut no_store() { return DeferredOut{nullptr, 0, nullptr, 0, nullptr, 0};
 dl::DeltaArgs delta_args(const rz_net *net, const uint8_t *active, float *feat32, bool count, int mode, const uint64_t *win = nullptr) {
     return dl::DeltaArgs{net->d_base_hdr, net->d_base_recs, active ? active : net->d_base_ones.p, feat32, count ? net->d_delta_stats.p : nullptr,
                          mode, (65536 + net->dev.BW - 1) / net->dev.BW, win};
+}
+// the headers of the base cache and, behind them, the valid bits of the feature memo (rz_memo.h): one block, cleared together
+size_t base_hdr_bytes(int n_games) { return (size_t)n_games * (sizeof(dl::BaseHdr) + rzm::kBitmapWords * sizeof(uint64_t)); }
+uint64_t *memo_bits(const rz_net *net) { return reinterpret_cast<uint64_t *>(net->d_base_hdr.p + net->base_games); }
+// on: k_delta_res<false> may serve leaves from the memo and fill it (no memo memory: every leaf runs its passes)
+dl::MemoArgs memo_args(const rz_net *net, bool on) { return dl::MemoArgs{on ? net->d_memo.p : nullptr, memo_bits(net)}; }
+// The memo's entries for the reserved games (15 x 15: 230 KB a game, 118 MB at 512 games), only while the memo is switched on.  The
+// memo is an optimisation: where the memory is not to be had the search runs without it, the base cache stands.
+void memo_reserve(rz_net *net) {
+    const size_t bytes = (size_t)net->base_games * (size_t)rzm::game_bytes(net->dev.S);
+    if (!net->delta_memo || net->base_games == 0) {
+        net->d_memo.release();
+    } else if (net->d_memo.bytes != bytes && !net->d_memo.alloc(bytes)) {
+        (void)hipGetLastError();   // (the failed hipMalloc's error is not the next launch's)
+    }
 }
 
 // the NetDev of a GEMM over the store's tiles, which hold the policy K-steps only; n_groups: groups of 128 policy outputs
@@ -672,9 +690,11 @@ static int search_resident(rz_net *net, rz_engine *engine, int32_t n_sims, int32
         if (select_first) {   // a search begins: the bases of its roots (a continued search finds them, or takes the route without)
             RZ_TRY(rz_net_delta_bases(net, dev.root_stones, dev.root_to_move, dev.n_games, stream));
         }
+        // (the memo: the search without policy features alone -- a leaf it serves has no policy planes to store)
         const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, true, 0, net->d_win);
-        if (policy) dl::k_delta_res<true><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
-        else dl::k_delta_res<false><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res);
+        const dl::MemoArgs mm = memo_args(net, !policy && net->delta_memo);
+        if (policy) dl::k_delta_res<true><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res, mm);
+        else dl::k_delta_res<false><<<grid, dim3(256), 0, st>>>(net->dev, net->d_store16, later, da, res, mm);
         return rz_launched("the resident search (k_delta_res)");
     }
     if (rows)
@@ -769,17 +789,20 @@ int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
     net->d_base_hdr.release();
     net->d_base_recs.release();
     net->d_base_ones.release();
+    net->d_memo.release();
     net->base_games = 0;
-    const size_t hdr_bytes = (size_t)n_games * sizeof(dl::BaseHdr), rec_bytes = (size_t)n_games * 2 * dl::kBaseBytes;
+    // (the headers, and behind them the memo's valid bits: base_hdr_bytes)
+    const size_t hdr_bytes = base_hdr_bytes(n_games), rec_bytes = (size_t)n_games * 2 * dl::kBaseBytes;
     if (!net->d_base_hdr.alloc(hdr_bytes) || !net->d_base_recs.alloc(rec_bytes) || !net->d_base_ones.alloc((size_t)n_games))
         return rz_fail(RZ_ERR_OOM, "hipMalloc failed (base cache)");
     if (!net->d_base_ones.fill(1)) return rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
-    if (!net->d_delta_stats && !net->d_delta_stats.alloc(8 * sizeof(unsigned)))
+    if (!net->d_delta_stats && !net->d_delta_stats.alloc(dl::kStats * sizeof(unsigned)))
         return rz_fail(RZ_ERR_OOM, "hipMalloc failed (delta counters)");
     // valid = 0: a leaf of a game without bases takes the four passes without a base
     if (!net->d_base_hdr.fill(0) || !net->d_delta_stats.fill(0))
         return rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");
     net->base_games = n_games;
+    memo_reserve(net);
     return RZ_OK;
 }
 
@@ -792,7 +815,7 @@ int rz_net_delta_resident(rz_net *net, int32_t on) {
 int rz_net_delta_invalidate(rz_net *net, void *stream) {
     if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
     if (net->base_games > 0 &&
-        hipMemsetAsync(net->d_base_hdr, 0, (size_t)net->base_games * sizeof(dl::BaseHdr), (hipStream_t)stream) != hipSuccess)
+        hipMemsetAsync(net->d_base_hdr, 0, base_hdr_bytes(net->base_games), (hipStream_t)stream) != hipSuccess)   // (and the memo's valid bits)
         return rz_fail(RZ_ERR_HIP, "hipMemsetAsync failed (base cache)");
     return RZ_OK;
 }
@@ -804,6 +827,10 @@ int rz_net_delta_bases(rz_net *net, const uint64_t *d_root_stones, const int32_t
     if (n_games > net->base_games) return rz_fail(RZ_ERR_ARG, "more games than rz_net_delta_reserve()d");
     if (!d_root_stones || !d_root_to_move) return rz_fail(RZ_ERR_ARG, "NULL device pointer");
     const dl::DeltaArgs da = delta_args(net, nullptr, nullptr, false, 1);
+    {   // the feature memo patches the bases that are replaced now: its valid bits go first
+        const int n_words = n_games * rzm::kBitmapWords;
+        dl::k_memo_clear<<<dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(memo_bits(net), n_words);
+    }
     dl::k_trunk_delta<false><<<dim3((unsigned)(2 * n_games)), dim3(256), 0, (hipStream_t)stream>>>(
         net->dev, LeafBits{d_root_stones, d_root_to_move, nullptr}, nullptr, 2 * n_games, no_store(), da);
     return rz_launched("k_trunk_delta (bases)");
@@ -881,7 +908,29 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset) {
     if (!net->d_delta_stats) return RZ_OK;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out8, net->d_delta_stats, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
-    if (reset && hipMemset(net->d_delta_stats, 0, 8 * sizeof(uint32_t)) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipMemset failed (delta counters)");
+    if (reset && hipMemset(net->d_delta_stats, 0, dl::kStats * sizeof(uint32_t)) != hipSuccess) return rz_fail(RZ_ERR_HIP, "hipMemset failed (delta counters)");
+    return RZ_OK;
+}
+
+int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out2) {
+    if (!net || !h_out2) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    h_out2[0] = h_out2[1] = 0;
+    if (!net->d_delta_stats) return RZ_OK;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out2, net->d_delta_stats.p + 8, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
+    return RZ_OK;
+}
+
+int rz_net_delta_memo(rz_net *net, int32_t on) {
+    if (!net) return rz_fail(RZ_ERR_ARG, "net handle is NULL");
+    if (net->delta_memo == (on != 0)) return RZ_OK;
+    net->delta_memo = on != 0;
+    if (net->base_games > 0) {   // (searches in flight may read the entries that go, or the bits of entries that come)
+        RZ_TRY(rz_on_device(net->device));
+        (void)hipDeviceSynchronize();
+        memo_reserve(net);
+        if (!net->d_base_hdr.fill(0)) return rz_fail(RZ_ERR_HIP, "hipMemset failed (base cache)");   // no entry is valid, and no base: they are rebuilt
+    }
     return RZ_OK;
 }
 
