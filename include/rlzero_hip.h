@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 48
+#define RZ_ABI_VERSION 49
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -882,6 +882,27 @@ int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup);
  * the instantiations without it, the code of ABI 42.  The step-by-step route (rz_mz_expand_backup) takes what the caller hands it: the
  * caller applies the inverse.  No launch; takes effect with the next one. */
 int rz_mz_set_value_transform(rz_muzero *e, int32_t on);
+/* Gumbel MuZero's search rule in the one-launch search (ABI 49; csrc/rz_mz_gumbel.h holds the rules, k_mz_search's GUMBEL
+ * instantiations run them): a Gumbel top-m draw at the root with Sequential Halving of the budget, the deterministic rule
+ * arg-max pi'(a) - N(a) / (1 + sum N) below it, and the policy target pi' = softmax(log prior + sigma(completed Q)),
+ * sigma(x) = (c_visit + max N) * c_scale * x, completed Q through the tree's own MinMax normalisation.
+ * rz_mz_set_gumbel: max_considered = 0 switches it off (the default; nothing else is read).  Otherwise h_cv is the HOST table of
+ * considered visits of m = min(max_considered, n_actions) actions and n_sims simulations (rzmzg::considered_visits;
+ * rlzero_amd.muzero.gumbel.considered_visits), count = the tree's n_sims.  RZ_ERR_ARG with the reason for a table of another
+ * length, entries outside 0 .. s, non-finite or negative constants, more than 8 actions.  While it is on, whole moves
+ * (rz_mz_play_env, rz_mz_play_cartpole) are refused with RZ_ERR_ARG: those instantiations keep the pUCT rule.  rz_mz_search is
+ * untouched; rz_mz_search_plan (whole_moves 0) reports the Gumbel launch, whose LDS holds 12 bytes more per node.
+ * rz_mz_search_gumbel: rz_mz_search with that rule, n_sims = the tree's n_sims (the table is the schedule of the whole budget).
+ * d_gumbel float32 [n_games][n_actions]: the move's Gumbel(0, 1) draws g (zeros: the greedy move).  The roots come from
+ * rz_mz_init_roots WITHOUT noise, fresh for every call (a tree that is not root + A children sets RZ_FLAG_INTERNAL in
+ * rz_mz_error_flags; rz_mz_env_move_gumbel sets RZ_FLAG_ILLEGAL_MOVE for an action outside 0 .. A - 1); the launch first evaluates the prediction on the roots' states (slot 0 of d_hidden) for their raw
+ * values, and ends by writing d_action_out int32 [n_games] -- among the most visited actions the arg-max of g + logit +
+ * sigma(completed Q) -- and d_pi_out float32 [n_games][n_actions] = pi' of the root.  Every node's raw network value is kept in the
+ * pad word of its rz_mz_node (float32 bits) by these launches only.  The trace arrays are rz_mz_search's. */
+int rz_mz_set_gumbel(rz_muzero *e, int32_t max_considered, double c_visit, double c_scale, const int32_t *h_cv, int64_t count);
+int rz_mz_search_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const float *d_gumbel, int32_t *d_action_out, float *d_pi_out,
+                        int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward,
+                        float *d_trace_probs, float *d_trace_value, void *stream);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action
@@ -964,6 +985,12 @@ typedef struct rz_mz_env_play {
 int rz_mz_env_step(int32_t kind, double *d_state, int64_t *d_steps, int64_t *d_episode, const int64_t *d_actions, int32_t n_envs, uint64_t seed,
                    int64_t max_episode_steps, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, void *stream);
 int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream);
+/* (ABI 49) The move behind rz_mz_search_gumbel (k_mz_env_move<Env, GUMBEL>): rz_mz_env_move with the search's outputs, d_action
+ * int32 [n_games] and d_pi float32 [n_games][A].  The action is the search's own (no draw: temperature and noise_seed are not used),
+ * and the record's A "visits" words hold pi' widened to float64 -- both replay buffers form visits / sum, and a row that sums to 1
+ * within float32 rounding stays the same distribution within one float32 rounding.  The play record stays rz_mz_env_play, field for
+ * field; everything else (ring, arena, entries, counters, root value = value_sum / N) is rz_mz_env_move's. */
+int rz_mz_env_move_gumbel(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, const int32_t *d_action, const float *d_pi, void *stream);
 /* Whole MOVES of any environment the library knows, in one launch (ABI 42; k_mz_search<TREE_LDS, MOVES = true, Env>): what
  * rz_mz_play_cartpole does, with the environment's step, observation, reset, reward and action count taken from its trait in
  * csrc/rz_mz_env.h and the time limit from the play record.  kind: RZ_MZ_ENV_CARTPOLE or RZ_MZ_ENV_ACROBOT.  The play record is

@@ -79,6 +79,11 @@ struct rz_muzero {
     int n_cus = 256;             // of cfg.device
     int games_per_wg = 0;        // rz_mz_set_search_shape: 0 = chosen from n_games and n_cus
     bool value_transform = false;   // rz_mz_set_value_transform: the launchers take the VT instantiations of k_mz_search
+    // rz_mz_set_gumbel: max_considered > 0 = on (rz_mz_search_gumbel launches the GUMBEL instantiations, whole moves are refused)
+    int gumbel_considered = 0;
+    double gumbel_c_visit = 50.0, gumbel_c_scale = 1.0;
+    int32_t *d_gumbel_cv = nullptr;    // [n_sims]: the considered-visits table
+    double *d_gumbel_logit = nullptr;  // [n_games][cap]: log(prior) of HBM trees
 };
 
 namespace {
@@ -93,7 +98,7 @@ constexpr auto mz_search_kernel = k_mz_search<TREE_LDS, MOVES, Env, (MOVES ? Env
 // the same rows for the dynamic-LDS attribute, so what can be launched is what was prepared.  A row is a route -- the search alone
 // (kMzNoEnv) or whole moves of an environment kind -- with or without the value transform, and holds its kernel for either placement of
 // the trees.  A new environment is one line: its two rows.  (The rows stand in the order of the instantiations in the code object.)
-typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay);
+typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel);
 constexpr int kMzNoEnv = -1;
 struct MzSearchRow {
     int kind;   // RZ_MZ_ENV_* of whole moves, kMzNoEnv for rz_mz_search
@@ -104,11 +109,22 @@ template <bool MOVES, typename Env, bool VT>
 constexpr MzSearchRow mz_search_row(int kind) {
     return {kind, VT, mz_search_kernel<true, MOVES, Env, VT>, mz_search_kernel<false, MOVES, Env, VT>};
 }
+// the GUMBEL instantiations (rz_mz_search_gumbel): the search alone, trees in LDS and in HBM, with and without the value transform
+typedef void (*MzGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel);
+struct MzGumbelRow {
+    bool vt;
+    MzGumbelFn tree_lds, tree_hbm;
+};
+template <bool VT>
+constexpr MzGumbelRow mz_gumbel_row() {
+    return {VT, k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, VT, true>, k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, VT, true>};
+}
 constexpr MzSearchRow kMzSearchRows[] = {
     mz_search_row<false, rzmze::EnvCartPole, false>(kMzNoEnv), mz_search_row<true, rzmze::EnvCartPole, false>(RZ_MZ_ENV_CARTPOLE),
     mz_search_row<false, rzmze::EnvCartPole, true>(kMzNoEnv), mz_search_row<true, rzmze::EnvCartPole, true>(RZ_MZ_ENV_CARTPOLE),
     mz_search_row<true, rzmze::EnvAcrobot, true>(RZ_MZ_ENV_ACROBOT), mz_search_row<true, rzmze::EnvAcrobot, false>(RZ_MZ_ENV_ACROBOT),
 };
+constexpr MzGumbelRow kMzGumbelRows[] = {mz_gumbel_row<false>(), mz_gumbel_row<true>()};
 
 int mz_ready(rz_muzero *e) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
@@ -124,7 +140,8 @@ struct MzPlan {
     bool tree_lds;  // trees in LDS (k_mz_search<true, ...>) or in HBM (<false, ...>)
     int lds;        // dynamic LDS bytes of the launch
 };
-MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves) {
+// `gumbel`: a launch of the GUMBEL instantiations (their LDS holds more per node and per launch: mz_search_lds_bytes)
+MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false) {
     MzPlan p;
     const int w1c = mz_w1_cols(whole_moves, e->cfg.n_actions <= kMzMaxA ? e->cfg.n_actions : kMzMaxA);
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
@@ -132,8 +149,8 @@ MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves) {
     p.gpw = e->games_per_wg > 0 ? e->games_per_wg : kMzMaxGpw;
     // the trees go to LDS when two workgroups still fit on a CU
     const MzDev &D = e->dev;
-    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true, w1c) <= 80 * 1024;
-    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds, w1c);
+    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true, w1c, gumbel) <= 80 * 1024;
+    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds, w1c, gumbel);
     return p;
 }
 
@@ -148,8 +165,19 @@ int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrac
     if (fn == nullptr) return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
     const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
-    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, play != nullptr ? *play : none);
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, play != nullptr ? *play : none, MzNoGumbel{});
     return rz_launched("k_mz_search");
+}
+
+int mz_launch_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzGumbel &Z, void *stream) {
+    const MzPlan plan = mz_search_plan(e, false, true);
+    if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    MzGumbelFn fn = nullptr;
+    for (const MzGumbelRow &row : kMzGumbelRows)
+        if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
+    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z);
+    return rz_launched("k_mz_search (gumbel)");
 }
 
 template <typename Env>
@@ -165,7 +193,8 @@ template <typename Env>
 int mz_env_move_launch(rz_muzero *e, const MzEnvPlay &p, void *stream) {
     static_assert(Env::kState <= RZ_MZE_MAX_STATE && Env::kObs <= RZ_MZE_MAX_OBS && Env::kActions <= RZ_MZE_MAX_ACTIONS, "environment limits");
     if (e->cfg.n_actions != Env::kActions) return rz_fail(RZ_ERR_ARG, "the tree has %d actions, the environment %d", e->cfg.n_actions, Env::kActions);
-    k_mz_env_move<Env><<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, p);
+    if (p.g_action != nullptr) k_mz_env_move<Env, true><<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, p);
+    else k_mz_env_move<Env><<<mz_grid(e), dim3(128), 0, (hipStream_t)stream>>>(e->dev, p);
     return rz_launched("k_mz_env_move");
 }
 
@@ -298,6 +327,10 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
             for (MzSearchFn fn : {row.tree_lds, row.tree_hbm})
                 if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
                     return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        for (const MzGumbelRow &row : kMzGumbelRows)
+            for (MzGumbelFn fn : {row.tree_lds, row.tree_hbm})
+                if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+                    return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
     }
     if (hipMemcpy(e->d_model, packed.host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy(model) failed");
@@ -344,9 +377,56 @@ int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace
     return mz_launch_search(e, d_hidden, n_sims, T, nullptr, 0, stream);
 }
 
+int rz_mz_set_gumbel(rz_muzero *e, int32_t max_considered, double c_visit, double c_scale, const int32_t *h_cv, int64_t count) {
+    RZ_ENTER(mz_ready, e);
+    if (max_considered < 0) return rz_fail(RZ_ERR_ARG, "max_considered must be >= 0 (0 = off)");
+    if (max_considered == 0) {
+        e->gumbel_considered = 0;
+        return RZ_OK;
+    }
+    if (!std::isfinite(c_visit) || !std::isfinite(c_scale) || c_visit < 0.0 || c_scale < 0.0)
+        return rz_fail(RZ_ERR_ARG, "c_visit and c_scale must be finite and >= 0");
+    if (e->cfg.n_actions > kMzMaxA) return rz_fail(RZ_ERR_ARG, "the fused search handles up to 8 actions");
+    if (h_cv == nullptr || count != e->cfg.n_sims)
+        return rz_fail(RZ_ERR_ARG, "the considered-visits table must hold n_sims = %d entries, not %lld", e->cfg.n_sims, (long long)count);
+    for (int64_t s = 0; s < count; ++s)
+        if (h_cv[s] < 0 || h_cv[s] > s) return rz_fail(RZ_ERR_ARG, "considered visits out of range at simulation %lld", (long long)s);
+    RZ_HIP(hipDeviceSynchronize());
+    if (e->d_gumbel_cv == nullptr) {
+        RZ_TRY(e->pool.alloc(&e->d_gumbel_cv, (long long)e->cfg.n_sims));
+    }
+    if (hipMemcpy(e->d_gumbel_cv, h_cv, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(considered visits) failed");
+    e->gumbel_considered = max_considered;
+    e->gumbel_c_visit = c_visit;
+    e->gumbel_c_scale = c_scale;
+    return RZ_OK;
+}
+
+int rz_mz_search_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const float *d_gumbel, int32_t *d_action_out, float *d_pi_out,
+                        int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward, float *d_trace_probs,
+                        float *d_trace_value, void *stream) {
+    RZ_ENTER(mz_ready, e);
+    if (!e->model_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model has not been called");
+    if (e->gumbel_considered < 1) return rz_fail(RZ_ERR_ARG, "rz_mz_set_gumbel has not switched the Gumbel search on");
+    if (d_hidden == nullptr || d_gumbel == nullptr || d_action_out == nullptr || d_pi_out == nullptr) return rz_fail(RZ_ERR_ARG, "NULL pointer");
+    if (n_sims != e->cfg.n_sims)
+        return rz_fail(RZ_ERR_ARG, "the considered-visits table is the schedule of n_sims = %d simulations, not of %d", e->cfg.n_sims, n_sims);
+    const bool any = d_trace_parent || d_trace_action || d_trace_leaf || d_trace_reward || d_trace_probs || d_trace_value;
+    const bool all = d_trace_parent && d_trace_action && d_trace_leaf && d_trace_reward && d_trace_probs && d_trace_value;
+    if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
+    const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
+    if (e->d_gumbel_logit == nullptr && !mz_search_plan(e, false, true).tree_lds)   // (only HBM trees keep log(prior) there)
+        RZ_TRY(e->pool.alloc(&e->d_gumbel_logit, (long long)e->cfg.n_games * e->dev.cap));
+    const MzGumbel Z = {e->d_gumbel_cv, d_gumbel, e->d_gumbel_logit, d_action_out, d_pi_out, e->gumbel_c_visit, e->gumbel_c_scale};
+    return mz_launch_gumbel(e, d_hidden, n_sims, T, Z, stream);
+}
+
 // whole moves of the environment `kind`: the checks and the launch behind rz_mz_play_env and rz_mz_play_cartpole
 static int mz_play_launch(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_whole_play *play, void *stream) {
     RZ_ENTER(mz_ready, e);
+    if (e->gumbel_considered > 0)
+        return rz_fail(RZ_ERR_ARG, "the Gumbel search is on (rz_mz_set_gumbel): whole moves keep the pUCT rule and are not served");
     int env_actions = 0, env_obs = 0;
     if (kind == RZ_MZ_ENV_CARTPOLE) {
         env_actions = rzmze::EnvCartPole::kActions;
@@ -457,7 +537,7 @@ int rz_mz_debug_profile(long long *h_out16) {
 
 int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    const MzPlan plan = mz_search_plan(e, whole_moves != 0);
+    const MzPlan plan = mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);
     if (games_per_workgroup) *games_per_workgroup = plan.gpw;
     if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
     if (lds_bytes) *lds_bytes = plan.lds;
@@ -512,7 +592,8 @@ int rz_cartpole_step(double *d_state, int64_t *d_steps, int64_t *d_episode, cons
     return mz_env_step_launch<rzmze::EnvCartPole>(d_state, d_steps, d_episode, d_actions, n_envs, seed, 500, d_obs, d_reward, d_terminated, d_truncated, stream);
 }
 
-int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream) {
+// the checks and the launch behind rz_mz_env_move and rz_mz_env_move_gumbel (d_action / d_pi: null without the Gumbel search)
+static int mz_env_move_checked(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, const int32_t *d_action, const float *d_pi, void *stream) {
     RZ_ENTER(mz_ready, e);
     if (play == nullptr) return rz_fail(RZ_ERR_ARG, "play is NULL");
     if (!play->d_state || !play->d_steps || !play->d_episode || !play->d_episode_start || !play->d_ring || !play->d_arena || !play->d_counters ||
@@ -539,9 +620,20 @@ int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void 
     p.entries = reinterpret_cast<long long *>(play->d_entries);
     p.max_entries = play->max_entries;
     p.obs = play->d_obs;
+    p.g_action = d_action;
+    p.g_pi = d_pi;
     if (kind == RZ_MZ_ENV_CARTPOLE) return mz_env_move_launch<rzmze::EnvCartPole>(e, p, stream);
     if (kind == RZ_MZ_ENV_ACROBOT) return mz_env_move_launch<rzmze::EnvAcrobot>(e, p, stream);
     return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
+}
+
+int rz_mz_env_move(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, void *stream) {
+    return mz_env_move_checked(e, kind, play, nullptr, nullptr, stream);
+}
+
+int rz_mz_env_move_gumbel(rz_muzero *e, int32_t kind, const rz_mz_env_play *play, const int32_t *d_action, const float *d_pi, void *stream) {
+    if (d_action == nullptr || d_pi == nullptr) return rz_fail(RZ_ERR_ARG, "d_action / d_pi is NULL");
+    return mz_env_move_checked(e, kind, play, d_action, d_pi, stream);
 }
 
 int rz_mz_root_noise(rz_muzero *e, const int64_t *d_episode, const int64_t *d_steps, uint64_t noise_seed, double dirichlet_alpha, double *d_eta,

@@ -64,11 +64,16 @@ struct MzEnvPlay {      // rz_mz_env_move: MzPlay's history (same layout of ring
     long long *counters, *entries;          // [4]; [max_entries][4]
     long long max_entries;
     float *obs;                             // [G][kObs]: the observation the next search starts from
+    const int32_t *g_action;                // (GUMBEL) [G]: the move rz_mz_search_gumbel chose; null otherwise
+    const float *g_pi;                      // (GUMBEL) [G][A]: its policy target pi'
 };
 
 // the move behind a finished search: what the MOVES stage of k_mz_search does at "the move", from the tree in HBM; a thread per
 // environment.  Plain stores and the two counters' atomics; a finished episode's earlier records were written by earlier launches.
-template <typename Env>
+// GUMBEL: the move behind rz_mz_search_gumbel -- the action is the search's own (no draw), and the record's A "visits" words hold pi'
+// widened to doubles: both replay buffers form visits / sum, and a row that sums to 1 within float32 rounding stays the same
+// distribution within one float32 rounding.  Everything else is the same code.
+template <typename Env, bool GUMBEL = false>
 __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
     constexpr int D = Env::kObs, A = Env::kActions;
     constexpr rzmze::RecordLayout R = rzmze::record_layout(D, A);
@@ -85,10 +90,17 @@ __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
     Env::load(env, P.state + (long long)Env::kState * g, P.steps[g], P.episode[g]);
     long long ep_start = P.ep_start[g];
     // 1, 2: the weights and the draw
-    double wgt[A], total;
-    int action = rzmze::move_weights(visits, A, P.inv_temperature, wgt, &total);
-    if (P.inv_temperature > 0.0)
-        action = rzmze::move_draw(wgt, A, total, rzmze::move_key(P.noise_seed, 0xA5A5A5A5ull, g, env.episode, env.steps));
+    int action;
+    if constexpr (GUMBEL) {   // (an action outside 0 .. A - 1 cannot come from the search: flagged, and played as the nearest)
+        const int a = P.g_action[g];
+        if (a < 0 || a >= A) atomicOr(E.err, RZ_FLAG_ILLEGAL_MOVE);
+        action = a < 0 ? 0 : (a >= A ? A - 1 : a);
+    } else {
+        double wgt[A], total;
+        action = rzmze::move_weights(visits, A, P.inv_temperature, wgt, &total);
+        if (P.inv_temperature > 0.0)
+            action = rzmze::move_draw(wgt, A, total, rzmze::move_key(P.noise_seed, 0xA5A5A5A5ull, g, env.episode, env.steps));
+    }
     // 3, 4: the record (the observation is the one the search started from) and the step
     double rec[ROW];
     {
@@ -102,7 +114,7 @@ __global__ __launch_bounds__(128) void k_mz_env_move(MzDev E, MzEnvPlay P) {
     rec[R.action] = (double)action;
     rec[R.reward] = reward;
 #pragma unroll
-    for (int a = 0; a < A; ++a) rec[R.visits + a] = (double)visits[a];
+    for (int a = 0; a < A; ++a) rec[R.visits + a] = GUMBEL ? (double)P.g_pi[(long long)g * A + a] : (double)visits[a];
     rec[R.root_value] = root.value_sum / (double)(root.N > 1 ? root.N : 1);
     rec[R.done] = done ? 1.0 : 0.0;
     double *ring_g = P.ring + (long long)g * P.hist * ROW;

@@ -42,12 +42,14 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "rlzero_hip.h"
 #include "rz_muzero_hot.h"
 #include "rz_muzero_noise.h"
 #include "rz_muzero_tree.h"
 #include "rz_mz_env.h"
+#include "rz_mz_gumbel.h"
 #include "rz_mz_pack.h"
 #include "rz_mz_value.h"
 
@@ -109,11 +111,17 @@ __host__ __device__ inline int mz_search_fixed_floats(int w1_cols) {
                                            // MOVES; every byte counts -- two workgroups of 16 games share a CU's 160 KB with 1.5 KB to spare)
 }
 __host__ __device__ constexpr int mz_w1_cols(bool whole_moves, int n_actions) { return whole_moves && n_actions > 2 ? n_actions : 2; }
-__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols) {
+// `gumbel`: the GUMBEL instantiations add, per node of an LDS tree, log(prior) (a double) and the raw value v_hat (a float), and for
+// every launch the considered-visits table (int32 [n_sims]) and the games' Gumbel rows (float [gpw][8])
+__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols, bool gumbel = false) {
     int bytes = mz_search_fixed_floats(w1_cols) * 4 + gpw * path_stride * 4;
     bytes = (bytes + 15) / 16 * 16;
     bytes += 2 * (((n_sims_cfg + 2) * 8 + 15) / 16 * 16);   // log and sqrt tables
     if (tree_lds) bytes += gpw * (cap + 1) * (int)sizeof(MzHot) + (gpw * (cap + 1) * 4 + 15) / 16 * 16;   // records (+ a spare per game) + rewards
+    if (gumbel) {
+        if (tree_lds) bytes += gpw * (cap + 1) * 8 + (gpw * (cap + 1) * 4 + 15) / 16 * 16;
+        bytes += (n_sims_cfg * 4 + 15) / 16 * 16 + gpw * rzmzg::kMaxA * 4;
+    }
     return bytes;
 }
 
@@ -161,6 +169,267 @@ __device__ __forceinline__ float mz_head_partial(const mz_f32x4 &p, const float 
     return mz_rowsum(s, l);
 }
 
+// ---- Gumbel MuZero on wave 0 (the GUMBEL instantiations; the rules and their one summation order: rz_mz_gumbel.h)
+// A pUCT level costs two divisions; a Gumbel level costs, per child, a completed value (a division), an fp64 exp and two more divisions,
+// and sums over the children that every child's score needs.  So the walk is laid out ACROSS the children: all 64 lanes of wave 0 walk,
+// lane 16 q + n on game n and the actions 2 q, 2 q + 1 -- the (n, q) layout of the heads.  A lane forms its two children's terms; the
+// visited-prior sums of v_mix, the visit total and maximum, the maximum and the sum of the exponentials and the (score, action) arg-max
+// are combined over q with v_permlane16_swap / v_permlane32_swap in mz_rowsum's order: no LDS round trip, no barrier, and the four
+// lanes of a game hold the same bits and step down together.  No log in the walk: log(prior) is formed when a node is expanded and
+// kept beside the record (LDS trees: a double array beside REW; HBM trees: MzGumbel::logit); the node's raw value v_hat lives in a
+// float array beside REW, in HBM in MzNode's pad word.  Expansion and backup are mz_grow_backup's arithmetic, run by the four lanes
+// of a game on the same words with the same values (an HBM lane reads only what it wrote itself).
+struct MzGumbel {
+    const int32_t *cv;     // [n_sims]: the considered-visits table
+    const float *g;        // [G][A]: the Gumbel draws of this move
+    double *logit;         // [G][cap]: log(prior) of the HBM trees
+    int32_t *action_out;   // [G]
+    float *pi_out;         // [G][A]
+    double c_visit, c_scale;
+};
+struct MzNoGumbel {};
+
+template <int W>
+__device__ __forceinline__ unsigned mz_xor_word(unsigned x, int l) {   // the word of lane l ^ W, W = 16 | 32
+    const auto r = W == 16 ? __builtin_amdgcn_permlane16_swap(x, x, false, false) : __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return (l & W) ? r[0] : r[1];
+}
+template <int W>
+__device__ __forceinline__ double mz_xor_f64(double x, int l) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const unsigned lo = mz_xor_word<W>((unsigned)b, l), hi = mz_xor_word<W>((unsigned)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double mzg_sum(double x, int l) {   // over q: rzmzg::sum4's order in every lane
+    x += mz_xor_f64<16>(x, l);
+    x += mz_xor_f64<32>(x, l);
+    return x;
+}
+
+struct MzgChild {
+    int N, fc;
+    double prior, logit, q;
+};
+// the two placements of a Gumbel tree behind one set of accessors (slots relative to the game's tree)
+struct MzgLds {
+    MzHot *hot;
+    float *rew, *vh;
+    double *lgt;
+    double discount;
+    __device__ __forceinline__ int first_child(int s) const { return hot[s].first_child; }
+    __device__ __forceinline__ MzgChild child(int s) const {
+        const MzHot h = hot[s];
+        return MzgChild{h.N, h.first_child, h.prior, lgt[s], h.q};
+    }
+    __device__ __forceinline__ double v_hat(int s) const { return (double)vh[s]; }
+    __device__ __forceinline__ void set_v_hat(int s, float v) const { vh[s] = v; }
+    // expand_node: the leaf's reward, children and raw value; lane q writes its own two children
+    template <int MAXA>
+    __device__ __forceinline__ void expand(int leaf, int top, int A, int q, float reward, const float (&probs)[MAXA], float value) const {
+        rew[leaf] = reward;
+        hot[leaf].first_child = top;
+        vh[leaf] = value;
+        float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a) {
+            p0 = a == 2 * q ? probs[a] : p0;
+            p1 = a == 2 * q + 1 ? probs[a] : p1;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int a = 2 * q + i;
+            const float p = i == 0 ? p0 : p1;
+            if (a < A) {
+                hot[top + a] = MzHot{0, -1, 0.0, (double)p, 0.0};
+                rew[top + a] = 0.0f;
+                vh[top + a] = 0.0f;
+                lgt[top + a] = log((double)p);
+            }
+        }
+    }
+    // a level of backpropagate: -> the node's new value(), r = its reward
+    __device__ __forceinline__ double visit(int s, double v, double &r) const {
+        const double sum = hot[s].value_sum + v;
+        const int n = hot[s].N + 1;
+        r = (double)rew[s];
+        const double nv = sum / (double)n;
+        hot[s].value_sum = sum;
+        hot[s].N = n;
+        hot[s].q = r + discount * nv;
+        return nv;
+    }
+};
+struct MzgHbm {
+    MzNode *nodes;
+    double *lgt;
+    double discount;
+    __device__ __forceinline__ int first_child(int s) const { return nodes[s].first_child; }
+    __device__ __forceinline__ MzgChild child(int s) const {
+        const MzNode nd = nodes[s];
+        return MzgChild{nd.N, nd.first_child, nd.prior, lgt[s], nd.N > 0 ? (double)nd.reward + discount * node_value(nd) : 0.0};
+    }
+    __device__ __forceinline__ double v_hat(int s) const { return (double)__int_as_float(nodes[s].pad); }
+    __device__ __forceinline__ void set_v_hat(int s, float v) const { nodes[s].pad = __float_as_int(v); }
+    // (every lane of the game writes every child: a lane then reads nothing but its own stores)
+    template <int MAXA>
+    __device__ __forceinline__ void expand(int leaf, int top, int A, int, float reward, const float (&probs)[MAXA], float value) const {
+        nodes[leaf].reward = reward;
+        nodes[leaf].first_child = top;
+        nodes[leaf].pad = __float_as_int(value);
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a) {
+            if (a < A) {
+                nodes[top + a] = MzNode{0, -1, 0.0, (double)probs[a], 0.0f, 0};
+                lgt[top + a] = log((double)probs[a]);
+            }
+        }
+    }
+    __device__ __forceinline__ double visit(int s, double v, double &r) const {
+        const double sum = nodes[s].value_sum + v;
+        const int n = nodes[s].N + 1;
+        nodes[s].value_sum = sum;
+        nodes[s].N = n;
+        r = (double)nodes[s].reward;
+        return sum / (double)n;
+    }
+};
+
+struct MzgLane {   // a lane's two children of a node: visits, first children, s(a) = logit + sigma(completed q); the node's totals
+    int n0, n1, fc0, fc1, sum_n, max_n;
+    double s0, s1;
+};
+template <typename Tree>
+__device__ __forceinline__ MzgLane mzg_scores(const MzGumbel &Z, const Tree &tree, int node, int fc, int A, int q, int l, double lo, double hi) {
+    const bool h0 = 2 * q < A, h1 = 2 * q + 1 < A;
+    const MzgChild none = {0, -1, 0.0, -INFINITY, 0.0};
+    const MzgChild r0 = tree.child(fc + (h0 ? 2 * q : 0)), r1 = tree.child(fc + (h1 ? 2 * q + 1 : 0));
+    const MzgChild c0 = h0 ? r0 : none, c1 = h1 ? r1 : none;
+    const double sp = mzg_sum(rzmzg::sum2(c0.N > 0 ? c0.prior : 0.0, c1.N > 0 ? c1.prior : 0.0), l);
+    const double spq = mzg_sum(rzmzg::sum2(c0.N > 0 ? c0.prior * c0.q : 0.0, c1.N > 0 ? c1.prior * c1.q : 0.0), l);
+    int sn = c0.N + c1.N, mn = c0.N > c1.N ? c0.N : c1.N;
+    sn += (int)mz_xor_word<16>((unsigned)sn, l);
+    sn += (int)mz_xor_word<32>((unsigned)sn, l);
+    mn = max(mn, (int)mz_xor_word<16>((unsigned)mn, l));
+    mn = max(mn, (int)mz_xor_word<32>((unsigned)mn, l));
+    const double vm = rzmzg::v_mix(tree.v_hat(node), sn, sp, spq);
+    const double scale = rzmzg::sigma_scale(Z.c_visit, Z.c_scale, mn);
+    MzgLane L;
+    L.n0 = c0.N;
+    L.n1 = c1.N;
+    L.fc0 = c0.fc;
+    L.fc1 = c1.fc;
+    L.sum_n = sn;
+    L.max_n = mn;
+    L.s0 = h0 ? rzmzg::logit_score(c0.logit, scale, rzmzg::completed(c0.N, c0.q, vm, lo, hi)) : -INFINITY;
+    L.s1 = h1 ? rzmzg::logit_score(c1.logit, scale, rzmzg::completed(c1.N, c1.q, vm, lo, hi)) : -INFINITY;
+    return L;
+}
+// pi' of the lane's two children
+__device__ __forceinline__ void mzg_policy(const MzgLane &L, int l, double &pi0, double &pi1) {
+    double mx = L.s0 > L.s1 ? L.s0 : L.s1, o = mz_xor_f64<16>(mx, l);
+    mx = o > mx ? o : mx;
+    o = mz_xor_f64<32>(mx, l);
+    mx = o > mx ? o : mx;
+    const double e0 = exp(L.s0 - mx), e1 = exp(L.s1 - mx);
+    const double den = mzg_sum(rzmzg::sum2(e0, e1), l);
+    pi0 = e0 / den;
+    pi1 = e1 / den;
+}
+// the best (score, action) of a game's children, with the winner's first child, in all four lanes
+__device__ __forceinline__ void mzg_argmax(double sc0, int a0, int fc0, double sc1, int a1, int fc1, int l, int &act, int &fc) {
+    bool take = rzmzg::better(sc1, a1, sc0, a0);
+    double best = take ? sc1 : sc0;
+    act = take ? a1 : a0;
+    fc = take ? fc1 : fc0;
+    double ob = mz_xor_f64<16>(best, l);
+    int oa = (int)mz_xor_word<16>((unsigned)act, l), ofc = (int)mz_xor_word<16>((unsigned)fc, l);
+    take = rzmzg::better(ob, oa, best, act);
+    best = take ? ob : best;
+    act = take ? oa : act;
+    fc = take ? ofc : fc;
+    ob = mz_xor_f64<32>(best, l);
+    oa = (int)mz_xor_word<32>((unsigned)act, l);
+    ofc = (int)mz_xor_word<32>((unsigned)fc, l);
+    take = rzmzg::better(ob, oa, best, act);
+    act = take ? oa : act;
+    fc = take ? ofc : fc;
+}
+
+// the walk of one simulation: the root rule at depth 0 (eligible: N(a) == cv_s; score g + s), the deterministic rule below
+template <typename Tree, typename PathP>
+__device__ __forceinline__ int mzg_descend(const MzDev &E, const MzGumbel &Z, const Tree &tree, PathP path, int A, int q, int l, double lo, double hi,
+                                           float g0, float g1, int cv_s, int &par_out, int &act_out, int &leaf_out) {
+    const int a0 = 2 * q < A ? 2 * q : -1, a1 = 2 * q + 1 < A ? 2 * q + 1 : -1;   // (an action past A loses every comparison)
+    int node = 0, depth = 0, par = 0, last = 0;
+    path[0] = 0;
+    int fc = tree.first_child(0);
+    while (fc >= 0 && depth + 1 < E.path_stride) {
+        const MzgLane L = mzg_scores(Z, tree, node, fc, A, q, l, lo, hi);
+        double sc0, sc1;
+        if (depth == 0) {
+            sc0 = a0 >= 0 && L.n0 == cv_s ? rzmzg::root_score(g0, L.s0) : -INFINITY;
+            sc1 = a1 >= 0 && L.n1 == cv_s ? rzmzg::root_score(g1, L.s1) : -INFINITY;
+        } else {
+            double pi0, pi1;
+            mzg_policy(L, l, pi0, pi1);
+            sc0 = a0 >= 0 ? rzmzg::below_score(pi0, L.n0, L.sum_n) : -INFINITY;
+            sc1 = a1 >= 0 ? rzmzg::below_score(pi1, L.n1, L.sum_n) : -INFINITY;
+        }
+        int act, cfc;
+        mzg_argmax(sc0, a0, L.fc0, sc1, a1, L.fc1, l, act, cfc);
+        par = node;
+        last = act;
+        node = fc + act;
+        fc = cfc;
+        depth += 1;
+        path[depth] = node;
+    }
+    par_out = par;
+    act_out = last;
+    leaf_out = node;
+    return depth;
+}
+
+// the result of a search: the move (among the most visited, the best g + s) and the lane's two entries of pi'
+template <typename Tree>
+__device__ __forceinline__ int mzg_result(const MzGumbel &Z, const Tree &tree, int A, int q, int l, double lo, double hi, float g0, float g1,
+                                          double &pi0, double &pi1) {
+    const int a0 = 2 * q < A ? 2 * q : -1, a1 = 2 * q + 1 < A ? 2 * q + 1 : -1;
+    const int fc = tree.first_child(0);
+    if (fc < 0) {   // (a root rz_mz_init_roots never expanded: nothing to report)
+        pi0 = pi1 = 0.0;
+        return 0;
+    }
+    const MzgLane L = mzg_scores(Z, tree, 0, fc, A, q, l, lo, hi);
+    mzg_policy(L, l, pi0, pi1);
+    const double sc0 = a0 >= 0 && L.n0 == L.max_n ? rzmzg::root_score(g0, L.s0) : -INFINITY;
+    const double sc1 = a1 >= 0 && L.n1 == L.max_n ? rzmzg::root_score(g1, L.s1) : -INFINITY;
+    int act, cfc;
+    mzg_argmax(sc0, a0, L.fc0, sc1, a1, L.fc1, l, act, cfc);
+    return act;
+}
+
+// expand_node + backpropagate with mz_grow_backup's arithmetic (same operations on the same operands: same bits)
+template <int MAXA, typename Tree, typename PathP>
+__device__ __forceinline__ void mzg_grow_backup(const MzDev &E, const Tree &tree, PathP path, int A, int q, int depth, int &top, double &lo,
+                                                double &hi, float reward_g, const float (&probs)[MAXA], float value_g) {
+    const int leaf = path[depth];
+    if (top + A > E.cap) {
+        atomicOr(E.err, RZ_FLAG_ARENA_FULL);
+    } else {
+        tree.template expand<MAXA>(leaf, top, A, q, reward_g, probs, value_g);
+        top += A;
+    }
+    double v = (double)value_g;
+    for (int d = depth; d >= 0; --d) {
+        double r;
+        const double nv = tree.visit(path[d], v, r);
+        hi = nv > hi ? nv : hi;   // MinMaxStats.update
+        lo = nv < lo ? nv : lo;
+        v = r + E.discount * v;
+    }
+}
+
 // the environment step and observation of a whole move OUT of line, for the environments MzFarStep names: Acrobot's RK4 over double
 // sin / cos takes 230 registers of its own, and inlined into k_mz_search they come out of the simulation loop's budget (the f16 weight
 // fragments are live across the move: scratch loads inside the loop).  A call keeps the two apart: what is live across it is saved
@@ -188,8 +457,14 @@ __device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, fl
 // CU (200 bytes of scratch per lane, ~20 scratch loads inside every simulation's serial chain)
 // VT: the network's reward and value are in the transformed space of rz_mz_value.h (rz_mz_set_value_transform): wave 0 takes them
 // through value_h_inv before the trace and the backup, so the tree, its MinMax bounds and the root value stay in raw units.
-template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false>
-__global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P) {
+// GUMBEL (MOVES = false only): the search rule is Gumbel MuZero's (above; rz_mz_set_gumbel) instead of pUCT -- wave 0's tree phase
+// is the (n, q) walk, the launch starts with the prediction of the roots' own states (their raw values) and ends with the move and
+// pi' of every game in Z.action_out / Z.pi_out.  The matrix-pipe stages are the same code.  Z: MzGumbel, an empty record otherwise.
+template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false,
+          bool GUMBEL = false>
+__global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P,
+                                                                 typename std::conditional<GUMBEL, MzGumbel, MzNoGumbel>::type Z) {
+    static_assert(!(GUMBEL && MOVES), "whole moves keep the pUCT rule");
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
     constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
     constexpr int W1C = mz_w1_cols(MOVES, Env::kActions);
@@ -219,6 +494,13 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     const int tcap = E.cap + 1;                      // slots per game in LDS: the tree + one spare record (mz_grow_backup_hot)
     MzHot *TREE = reinterpret_cast<MzHot *>(pp);     // [gpw][tcap] (TREE_LDS)
     float *REW = reinterpret_cast<float *>(pp + gpw * tcap * (int)sizeof(MzHot));   // [gpw][tcap] rewards (TREE_LDS)
+    // GUMBEL, in the order of mz_search_lds_bytes: log(prior) and v_hat per node (TREE_LDS), the considered visits, the Gumbel rows
+    if (TREE_LDS) pp += gpw * tcap * (int)sizeof(MzHot) + (gpw * tcap * 4 + 15) / 16 * 16;
+    double *LGT = reinterpret_cast<double *>(pp);    // [gpw][tcap]
+    float *VH = reinterpret_cast<float *>(pp + gpw * tcap * 8);   // [gpw][tcap]
+    if (TREE_LDS) pp += gpw * tcap * 8 + (gpw * tcap * 4 + 15) / 16 * 16;
+    int32_t *CV = reinterpret_cast<int32_t *>(pp);   // [n_sims]
+    float *GB = reinterpret_cast<float *>(pp + (E.n_sims * 4 + 15) / 16 * 16);   // [gpw][8]
 
     // ---- once: weight fragments into registers (A operand of 16x16x4: lane holds W[unit 16w + n][k = 4s + q])
     // (the representation network's fragments -- 18 + 8 registers, used once per MOVE -- are fetched at the start of every
@@ -327,13 +609,22 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         PBL[i] = E.pb_log[i];
         SQT[i] = sqrt((double)i);
     }
+    if constexpr (GUMBEL) {
+        for (int i = tid; i < n_sims; i += 64 * kMzWaves) CV[i] = Z.cv[i];
+        for (int i = tid; i < gpw * rzmzg::kMaxA; i += 64 * kMzWaves) {
+            const int ee = i >> 3, a = i & 7;
+            GB[i] = g0 + ee < E.n_games && a < A ? Z.g[(long long)(g0 + ee) * A + a] : 0.0f;
+        }
+    }
     // the trees of this workgroup's games
     // wave 0 walks the trees: the four lanes of quad `ge` own game g0 + ge together -- they score different children in
     // the walk and otherwise run the same tree code on the same values (same LDS words, same bits); `lead` writes to HBM
+    // (GUMBEL: lane 16 q + n works on game g0 + n -- `te` is the column of the game a lane's tree code serves)
     const int ge = l >> 2, ca = l & 3;
-    const bool mine = w == 0 && ge < gpw && g0 + ge < E.n_games;
-    const bool lead = mine && ca == 0;
-    const int g = g0 + (ge < gpw ? ge : 0);
+    const int te = GUMBEL ? n : ge;
+    const bool mine = w == 0 && te < gpw && g0 + te < E.n_games;
+    const bool lead = mine && (GUMBEL ? q == 0 : ca == 0);
+    const int g = g0 + (te < gpw ? te : 0);
     const bool live_n = n < gpw && g0 + n < E.n_games;           // column n of the tiles is a game
     int top = 0, depth = 0;
     double lo = 0.0, hi = 0.0;
@@ -367,6 +658,8 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             top = E.top[g];
             lo = E.vmin[g];
             hi = E.vmax[g];
+            // (GUMBEL) the schedule counts from roots rz_mz_init_roots has just made: anything else is flagged, not searched on quietly
+            if (GUMBEL && lead && top != 1 + A) atomicOr(E.err, RZ_FLAG_INTERNAL);
         }
     }
     if (TREE_LDS && !MOVES) {
@@ -382,9 +675,30 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         }
     }
     MzNode *nodes = E.nodes + (long long)g * E.cap;                 // (!TREE_LDS)
-    MzHot *hot = TREE + (ge < gpw ? ge : 0) * tcap;                 // (TREE_LDS)
-    float *rew = REW + (ge < gpw ? ge : 0) * tcap;
-    int32_t *path = PATH + (ge < gpw ? ge : 0) * E.path_stride;
+    MzHot *hot = TREE + (te < gpw ? te : 0) * tcap;                 // (TREE_LDS)
+    float *rew = REW + (te < gpw ? te : 0) * tcap;
+    int32_t *path = PATH + (te < gpw ? te : 0) * E.path_stride;
+    // (GUMBEL) the game's tree behind its accessors, log(prior) and v_hat of the nodes that are there already
+    const auto gtree = [&]() {
+        if constexpr (!GUMBEL) return 0;
+        else if constexpr (TREE_LDS) return MzgLds{hot, rew, VH + (te < gpw ? te : 0) * tcap, LGT + (te < gpw ? te : 0) * tcap, E.discount};
+        else return MzgHbm{nodes, Z.logit + (long long)g * E.cap, E.discount};
+    }();
+    (void)gtree;
+    if constexpr (GUMBEL) {
+        for (int ee = 0; ee < gpw && g0 + ee < E.n_games; ++ee) {
+            const MzNode *src = E.nodes + (long long)(g0 + ee) * E.cap;
+            const int used = E.top[g0 + ee] < E.cap ? E.top[g0 + ee] : E.cap;
+            for (int i = tid; i < used; i += 64 * kMzWaves) {
+                if (TREE_LDS) {
+                    LGT[ee * tcap + i] = log(src[i].prior);
+                    VH[ee * tcap + i] = __int_as_float(src[i].pad);
+                } else {
+                    Z.logit[(long long)(g0 + ee) * E.cap + i] = log(src[i].prior);
+                }
+            }
+        }
+    }
     __syncthreads();
     if (MOVES && mine) {   // (after the zero fill of OBS)
         EnvState c0;
@@ -471,7 +785,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     auto finish_prediction = [&](float &value, float (&probs)[MAXA]) {
         value = HB[1];
 #pragma unroll
-        for (int u = 0; u < kMzWaves; ++u) value += RED[(3 * kMzWaves + u) * kMzTile + ge];
+        for (int u = 0; u < kMzWaves; ++u) value += RED[(3 * kMzWaves + u) * kMzTile + te];
         float logit[MAXA], mxl = -INFINITY;
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
@@ -479,7 +793,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             if (a < A) {
                 float x = HB[2 + a];
 #pragma unroll
-                for (int u = 0; u < kMzWaves; ++u) x += RED[((4 + a) * kMzWaves + u) * kMzTile + ge];
+                for (int u = 0; u < kMzWaves; ++u) x += RED[((4 + a) * kMzWaves + u) * kMzTile + te];
                 logit[a] = x;
                 mxl = fmaxf(mxl, x);
             }
@@ -582,14 +896,47 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             }
             MZ_TICK(13);
         }
+        // (GUMBEL) the quad of a game is live: the gathers below run in the quad layout whichever lanes walk
+        const bool live_quad = GUMBEL ? ge < gpw && g0 + ge < E.n_games : mine;
+        float gum0 = 0.0f, gum1 = 0.0f;   // (GUMBEL) the Gumbel draws of the lane's two actions
+        if constexpr (GUMBEL) {
+            // ---- the roots' raw values: the prediction on the states the search starts from (v_mix of the root needs v_hat)
+            if (w == 0) {
+                const float4 *src = reinterpret_cast<const float4 *>(hidden + (long long)(g0 + (live_quad ? ge : 0)) * E.cap * kMzH);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = ca + 4 * j;
+                    const float4 v = live_quad ? src[c] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+                    XS[(4 * c + 0) * kMzTile + ge] = v.x;
+                    XS[(4 * c + 1) * kMzTile + ge] = v.y;
+                    XS[(4 * c + 2) * kMzTile + ge] = v.z;
+                    XS[(4 * c + 3) * kMzTile + ge] = v.w;
+                }
+            }
+            __syncthreads();
+            predict_partials();
+            __syncthreads();
+            if (w == 0) {
+                float value, probs[MAXA];
+                finish_prediction(value, probs);
+                if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);
+                if (mine) gtree.set_v_hat(0, value);
+                gum0 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q];
+                gum1 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q + 1];
+            }
+        }
     for (int sim = 0; sim < n_sims; ++sim) {
         // S0 (wave 0): select, one lane per game; then the gather of the parents' hidden states into XS[k][game]
         // (lane -> game l / 4, four 16-byte pieces of its 256-byte row) and the one-hot action rows
         int par = 0, act = 0, lf = 0;
         if (w == 0) {
-            if (mine)
-                depth = TREE_LDS ? mz_descend_hot<AFIX>(E, hot, path, PBL, SQT, lo, hi, ca, hidden + (long long)g * E.cap * kMzH, touch_sink, par, act, lf)
-                                 : mz_descend(E, nodes, path, PBL, lo, hi, par, act, lf);
+            if constexpr (GUMBEL) {
+                if (mine) depth = mzg_descend(E, Z, gtree, path, A, q, l, lo, hi, gum0, gum1, CV[sim], par, act, lf);
+            } else {
+                if (mine)
+                    depth = TREE_LDS ? mz_descend_hot<AFIX>(E, hot, path, PBL, SQT, lo, hi, ca, hidden + (long long)g * E.cap * kMzH, touch_sink, par, act, lf)
+                                     : mz_descend(E, nodes, path, PBL, lo, hi, par, act, lf);
+            }
             MZ_TICK(0);
 #ifdef RZ_MZ_PROFILE
             {   // the wave walks as long as its deepest game
@@ -598,9 +945,10 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                 prof_acc[15] += md;
             }
 #endif
-            if (ca == 0) Gleaf[ge] = lf;
-            const int ee = ge, pe = par;   // (the quad of a game also gathers its parent's state: 4 x 64 bytes per lane)
-            const bool live_e = mine;
+            if (GUMBEL ? q == 0 : ca == 0) Gleaf[te] = lf;
+            // (the quad of a game also gathers its parent's state: 4 x 64 bytes per lane; GUMBEL: lane `ge` walked that game)
+            const int ee = ge, pe = GUMBEL ? __shfl(par, ge) : par;
+            const bool live_e = live_quad;
             const float4 *src = reinterpret_cast<const float4 *>(hidden + ((long long)(g0 + (live_e ? ee : 0)) * E.cap + pe) * kMzH);
             if constexpr (F16) {   // the slot holds the record's 256 bytes as they are: a copy (16 games x 4 lanes x 4 pieces)
 #pragma unroll
@@ -620,7 +968,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                     XS[(4 * c + 2) * kMzTile + ee] = v.z;
                     XS[(4 * c + 3) * kMzTile + ee] = v.w;
                 }
-                const int an = __shfl(act, 4 * n);
+                const int an = GUMBEL ? act : __shfl(act, 4 * n);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int a = q + 4 * j;
@@ -692,7 +1040,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         if (w == 0) {
             float reward = HB[0];
 #pragma unroll
-            for (int u = 0; u < kMzWaves; ++u) reward += RED[(2 * kMzWaves + u) * kMzTile + ge];
+            for (int u = 0; u < kMzWaves; ++u) reward += RED[(2 * kMzWaves + u) * kMzTile + te];
             float value, probs[MAXA];
             finish_prediction(value, probs);
             if constexpr (VT) {   // widened, inverted in fp64, rounded once
@@ -712,7 +1060,8 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                     for (int a = 0; a < MAXA; ++a)
                         if (a < A) T.probs[o * A + a] = probs[a];
                 }
-                if (TREE_LDS) mz_grow_backup_hot<MAXA, AFIX>(E, hot, rew, path, E.cap, ca, depth, top, lo, hi, reward, probs, value);
+                if constexpr (GUMBEL) mzg_grow_backup<MAXA>(E, gtree, path, A, q, depth, top, lo, hi, reward, probs, value);
+                else if (TREE_LDS) mz_grow_backup_hot<MAXA, AFIX>(E, hot, rew, path, E.cap, ca, depth, top, lo, hi, reward, probs, value);
                 else mz_grow_backup<MAXA>(E, nodes, path, depth, top, lo, hi, reward, probs, value);
             }
             MZ_TICK(12);
@@ -720,6 +1069,16 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         // (no barrier: the next select and gather are wave 0's too; XS -- which the gather rewrites -- was last read
         // before the barrier behind S4, and RED, which wave 0 reads above, is rewritten only after the next S0 barrier)
     }
+        if constexpr (GUMBEL) {
+            // ---- the result: the move and pi' of every game, a lane its two entries (no launch behind this one)
+            if (mine) {
+                double pi0, pi1;
+                const int move_g = mzg_result(Z, gtree, A, q, l, lo, hi, gum0, gum1, pi0, pi1);
+                if (q == 0) Z.action_out[g] = move_g;
+                if (2 * q < A) Z.pi_out[(long long)g * A + 2 * q] = (float)pi0;
+                if (2 * q + 1 < A) Z.pi_out[(long long)g * A + 2 * q + 1] = (float)pi1;
+            }
+        }
         if (MOVES && mine) {
             // ---- the move: action ~ visits ^ (1 / T) (select_action), record for the host, environment step
             EnvState env;
@@ -813,14 +1172,14 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     }
     if (TREE_LDS) {
         __syncthreads();
-        if (w == 0 && ca == 0) Gleaf[ge] = top;   // (every wave needs the final tops)
+        if (w == 0 && (GUMBEL ? q == 0 : ca == 0)) Gleaf[te] = top;   // (every wave needs the final tops)
         __syncthreads();
         for (int ee = 0; ee < gpw && g0 + ee < E.n_games; ++ee) {
             MzNode *dst = E.nodes + (long long)(g0 + ee) * E.cap;
             const int used = Gleaf[ee];
             for (int i = tid; i < used; i += 64 * kMzWaves) {
                 const MzHot h = TREE[ee * tcap + i];
-                dst[i] = MzNode{h.N, h.first_child, h.value_sum, h.prior, REW[ee * tcap + i], 0};
+                dst[i] = MzNode{h.N, h.first_child, h.value_sum, h.prior, REW[ee * tcap + i], GUMBEL ? __float_as_int(VH[ee * tcap + i]) : 0};
             }
         }
     }

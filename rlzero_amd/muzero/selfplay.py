@@ -203,7 +203,8 @@ class MuZeroSelfPlay(object):
 
     def __init__(self, net, env, n_sims=50, discount=0.997, temperature=1.0, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, seed=0, pb_c_base=19652.0, pb_c_init=1.25, use_graph=True, fused=None,
-                 fused_moves=None, moves_per_launch=16, arena_rows=None, device_moves=None):
+                 fused_moves=None, moves_per_launch=16, arena_rows=None, device_moves=None, search='puct', gumbel_considered=4,
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, gumbel_greedy=False):
         """``fused``: run the whole search of a move in ONE kernel launch (csrc/rz_muzero_search.h k_mz_search: the model is
         evaluated inside the kernel on the matrix pipe, 16 games per workgroup, trees in LDS); None = whenever the model
         fits it (hidden size 64, <= 8 actions).  Otherwise one hipGraph of ~15 launches per simulation (tree kernels +
@@ -223,7 +224,17 @@ class MuZeroSelfPlay(object):
         behind, as with whole moves, and the draws come from the same counter-based stream.  None = whenever ``fused`` holds, the
         environment states such a kind, whole moves do not apply and the environment is not a CartPoleBatch (whose default stays
         whole moves; it takes this route with ``fused_moves=False, device_moves=True``).  True where it cannot run raises a
-        ``ValueError`` that names the reason."""
+        ``ValueError`` that names the reason.
+        ``search``: 'puct' (the default: nothing changes) or 'gumbel' -- Gumbel MuZero's rule (``MuZeroTree.set_gumbel`` /
+        ``search_gumbel``; csrc/rz_mz_gumbel.h): a Gumbel top-m draw at the root, m = min(``gumbel_considered``, A), Sequential
+        Halving of the ``n_sims`` simulations, the deterministic rule below the root, sigma(x) = (``gumbel_c_visit`` + max N)
+        ``gumbel_c_scale`` x.  It needs the fused search and raises a ``ValueError`` naming the reason for ``fused=False``, a model the
+        fused search does not serve, or ``fused_moves=True`` (whole moves keep pUCT; left to None they are off here, and device moves
+        are the default for every environment kind the library knows, CartPole included).  No Dirichlet noise is added; g = -log(-log U)
+        is drawn with torch on the device from this object's generator, one [n, A] draw per move, with no host synchronisation
+        (``gumbel_greedy``: g = 0, the evaluation's move).  The move is the search's own, so ``temperature`` is IGNORED; a record's A
+        visits words hold pi' (both buffers form visits / sum of them: the same distribution within a float32 rounding) and the root
+        value stays value_sum / N.  It serves the host loop (``play_move``) and device moves."""
         import torch
         from .tree import MuZeroTree
         self.torch = torch
@@ -262,6 +273,23 @@ class MuZeroSelfPlay(object):
         # times per move.  Captured before any search (the capture runs the step on the still empty trees;
         # every search starts by re-initialising its roots).  Weight updates are in place: the graph stays valid.
         self.fused = (net.hidden == 64 and self.n_actions <= 8) if fused is None else bool(fused)
+        if search not in ('puct', 'gumbel'):
+            self.tree.close()
+            raise ValueError('search must be \'puct\' or \'gumbel\', not %r' % (search, ))
+        self.gumbel, self.gumbel_greedy = search == 'gumbel', bool(gumbel_greedy)
+        if self.gumbel:
+            why = None
+            if fused is not None and not fused:
+                why = 'fused=False was given: the rule lives in the one-launch search only'
+            elif not (net.hidden == 64 and self.n_actions <= 8):
+                why = 'the fused search does not serve this model (it needs hidden size 64 and at most 8 actions)'
+            elif fused_moves:
+                why = 'fused_moves=True was given: whole moves keep the pUCT rule'
+            if why is not None:
+                self.tree.close()
+                raise ValueError('search=\'gumbel\' cannot run: ' + why)
+            fused_moves = False
+            self.tree.set_gumbel(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
         self._model_seen = None
         from .cartpole import CartPoleBatch
         from .. import _hip
@@ -297,13 +325,13 @@ class MuZeroSelfPlay(object):
                 getattr(env, 'kind', None), ', '.join(sorted(_hip.MZ_ENV_KINDS)))
         elif self.fused_moves:
             why_not = 'whole moves are on (fused_moves): a move is either inside the search launch or behind it'
-        elif not self.alpha >= self.MIN_FUSED_ALPHA:
+        elif not self.gumbel and not self.alpha >= self.MIN_FUSED_ALPHA:
             why_not = ('root_dirichlet_alpha = %r is below 0.1: the root noise is the whole moves\' float32 draw, which reaches its 1e-30 floor '
                        'too often there (the host loop, device_moves=False, takes any alpha > 0)' % self.alpha)
         elif net.obs_dim != env.obs_dim:
             why_not = 'the network takes %d observations, the environment gives %d' % (net.obs_dim, env.obs_dim)
         if device_moves is None:
-            self.device_moves = why_not is None and not isinstance(env, CartPoleBatch)
+            self.device_moves = why_not is None and (self.gumbel or not isinstance(env, CartPoleBatch))
         else:
             self.device_moves = bool(device_moves)
             if self.device_moves and why_not is not None:
@@ -370,6 +398,14 @@ class MuZeroSelfPlay(object):
     def close(self):
         self.tree.close()
 
+    def _gumbel_draws(self):
+        """g = -log(-log U) float32 [n, A] on the device from the object's generator (zeros with ``gumbel_greedy``); no synchronisation."""
+        t = self.torch
+        if self.gumbel_greedy:
+            return t.zeros((self.n_envs, self.n_actions), dtype=t.float32, device=self.device)
+        u = t.rand((self.n_envs, self.n_actions), generator=self.gen, dtype=t.float32, device=self.device).clamp_(1e-7, 1.0 - 1e-7)
+        return (-t.log(-t.log(u))).contiguous()
+
     def restart_episodes(self):
         """Every environment begins episode 0 again, from that episode's initial state (the environment's counter-based stream:
         the same states at every call), and the running episodes of the history are dropped: the next move is the first of a new
@@ -384,7 +420,8 @@ class MuZeroSelfPlay(object):
     # ------------------------------------------------------------------ search
     def search(self, obs, add_noise=True, record=None):
         """One MuZero search per environment from the observations ``obs`` [n, obs_dim].
-        -> (visit counts int32 [n, A], root value float64 [n]).  ``record`` (list): receives per simulation
+        -> (visit counts int32 [n, A], root value float64 [n]); with ``search='gumbel'`` the first is pi' float32 [n, A] in the visits'
+        position (no noise is added; the move is kept for ``select_actions``).  ``record`` (list): receives per simulation
         (parent, action, leaf, reward, probs, value) tensors -- parity tests replay them through their CPython restatement."""
         t = self.torch
         tree, net = self.tree, self.net
@@ -393,6 +430,16 @@ class MuZeroSelfPlay(object):
             probs = t.softmax(logits, dim=1).contiguous()
             self.hidden[:, 0] = s0
             noise = None
+            if self.gumbel:
+                if record is not None:
+                    raise ValueError('search: record is the pUCT routes\' (MuZeroTree.search_gumbel(trace=True) traces a Gumbel search)')
+                tree.init_roots(probs)
+                self._refresh_model()
+                actions, pi = tree.search_gumbel(self.hidden, self.n_sims, self._gumbel_draws())
+                self._gumbel_actions = actions.long().clone()
+                n, vsum, _, _ = tree.root_stats()
+                self.sims_done += self.n_sims * self.n_envs
+                return pi.clone(), vsum / n.clamp_min(1).to(t.float64)
             if add_noise and self.noise_frac > 0:
                 conc = t.full((self.n_envs, self.n_actions), self.alpha, dtype=t.float64, device=self.device)
                 g = t._standard_gamma(conc, generator=self.gen)
@@ -436,6 +483,8 @@ class MuZeroSelfPlay(object):
     def select_actions(self, visits):
         """pseudocode ``select_action``: sample from visit counts ^ (1 / temperature) (arg-max at T = 0)."""
         t = self.torch
+        if self.gumbel:   # the move of the last ``search``
+            return self._gumbel_actions
         if self.temperature <= 0:
             return visits.argmax(dim=1)
         w = visits.to(t.float64) ** (1.0 / self.temperature)
@@ -614,6 +663,12 @@ class MuZeroSelfPlay(object):
             s0, logits, _ = net.initial_inference(obs)
             probs = t.softmax(logits, dim=1).contiguous()
             self.hidden[:, 0] = s0
+            if self.gumbel:
+                tree.init_roots(probs)
+                tree.search_gumbel(self.hidden, self.n_sims, self._gumbel_draws())
+                tree.env_move(env, self.noise_seed, self.temperature, (self._ring, self._ep_start_dev), self._t + k, arena, counters,
+                              entries, obs, gumbel=True)
+                continue
             noise = None
             if self.noise_frac > 0:   # keyed (seed, environment, episode, step): the same draws however the run is batched
                 noise = tree.root_noise(env.episode_dev, env.steps, self.noise_seed, self.alpha, out=self._eta)

@@ -117,13 +117,14 @@ class MuZeroTree(object):
         check(self.lib.rz_mz_play_env(self.handle, kind, _ptr(hidden), int(n_sims), int(n_moves), ctypes.byref(play), self.stream()),
               'rz_mz_play_env')
 
-    def env_move(self, env, noise_seed, temperature, history, step, arena, counters, entries, obs_out):
+    def env_move(self, env, noise_seed, temperature, history, step, arena, counters, entries, obs_out, gumbel=False):
         """The move behind a finished search (``search_fused`` on the current stream) for the environment batch ``env`` of a kind
         the library knows (``env.kind``: 'cartpole' | 'acrobot'), one launch (k_mz_env_move): the action from the root's visit
         counts, the record into ``history`` = (ring float64 [G, ring_steps, D + 4 + A], episode_start int64 [G]) at ``step`` %
         ring_steps, the environment step, the hand-over of a finished episode to ``arena`` / ``entries`` / ``counters`` (laid out
         as ``play_cartpole``'s; NOT zeroed here: several moves share an arena) and the next observation to ``obs_out`` float32
-        [G, D]."""
+        [G, D].  ``gumbel``: the move behind ``search_gumbel`` (k_mz_env_move<Env, GUMBEL>) -- the action is the search's own, and the
+        record's A visits words hold pi' as float64 (``temperature`` is not used)."""
         ring, episode_start = history
         kind = _hip.MZ_ENV_KINDS[env.kind]
         t, G, row = self.torch, self.n_games, env.obs_dim + 4 + self.n_actions
@@ -139,6 +140,10 @@ class MuZeroTree(object):
             int(env.seed) & (2 ** 64 - 1), int(noise_seed) & (2 ** 64 - 1), float(temperature), int(env.max_episode_steps),
             ring.data_ptr(), int(ring.shape[1]), 0, int(step), arena.data_ptr(), int(arena.shape[0]), counters.data_ptr(),
             entries.data_ptr(), int(entries.shape[0]), obs_out.data_ptr())
+        if gumbel:
+            check(self.lib.rz_mz_env_move_gumbel(self.handle, kind, ctypes.byref(play), _ptr(self.gumbel_action), _ptr(self.gumbel_pi),
+                                                 self.stream()), 'rz_mz_env_move_gumbel')
+            return
         check(self.lib.rz_mz_env_move(self.handle, kind, ctypes.byref(play), self.stream()), 'rz_mz_env_move')
 
     def root_noise(self, episode, steps, noise_seed, alpha, out=None):
@@ -164,22 +169,59 @@ class MuZeroTree(object):
         self.value_transform = bool(on)
         return self
 
+    def _trace(self, n_sims, trace):
+        """-> (the trace tensors of a fused search or None, the six pointers the library takes)"""
+        if not trace:
+            return None, [None] * 6
+        t, kw = self.torch, dict(device=self.device)
+        G, A = self.n_games, self.n_actions
+        out = {'parent': t.zeros((n_sims, G), dtype=t.int32, **kw), 'action': t.zeros((n_sims, G), dtype=t.int32, **kw),
+               'leaf': t.zeros((n_sims, G), dtype=t.int32, **kw), 'reward': t.zeros((n_sims, G), dtype=t.float32, **kw),
+               'probs': t.zeros((n_sims, G, A), dtype=t.float32, **kw), 'value': t.zeros((n_sims, G), dtype=t.float32, **kw)}
+        return out, [_ptr(out[k]) for k in ('parent', 'action', 'leaf', 'reward', 'probs', 'value')]
+
     def search_fused(self, hidden, n_sims, trace=False):
         """All ``n_sims`` simulations of every game in ONE launch (k_mz_search; init_roots and the root's hidden state
         in ``hidden[:, 0]`` first).  ``trace``: returns per simulation what the kernel selected and its network outputs:
         dict of tensors parent / action / leaf int32 [n_sims, G], reward / value float32 [n_sims, G], probs [n_sims, G, A]."""
-        t = self.torch
-        out = None
-        args = [None] * 6
-        if trace:
-            kw = dict(device=self.device)
-            G, A = self.n_games, self.n_actions
-            out = {'parent': t.zeros((n_sims, G), dtype=t.int32, **kw), 'action': t.zeros((n_sims, G), dtype=t.int32, **kw),
-                   'leaf': t.zeros((n_sims, G), dtype=t.int32, **kw), 'reward': t.zeros((n_sims, G), dtype=t.float32, **kw),
-                   'probs': t.zeros((n_sims, G, A), dtype=t.float32, **kw), 'value': t.zeros((n_sims, G), dtype=t.float32, **kw)}
-            args = [_ptr(out[k]) for k in ('parent', 'action', 'leaf', 'reward', 'probs', 'value')]
+        out, args = self._trace(n_sims, trace)
         check(self.lib.rz_mz_search(self.handle, _ptr(hidden), int(n_sims), *args, self.stream()), 'rz_mz_search')
         return out
+
+    def set_gumbel(self, max_considered=4, c_visit=50.0, c_scale=1.0):
+        """Gumbel MuZero's rule for ``search_gumbel`` (rz_mz_set_gumbel; csrc/rz_mz_gumbel.h): a Gumbel top-m draw at the root, m =
+        min(max_considered, A), Sequential Halving of the tree's ``n_sims`` simulations over it (``gumbel.considered_visits``, uploaded
+        here), the deterministic rule below the root, sigma(x) = (c_visit + max N) c_scale x.  ``max_considered`` 0 switches it off.
+        While it is on the library refuses whole moves (``play_env`` / ``play_cartpole``); ``search_fused`` is untouched, and
+        ``search_plan(False)`` describes the Gumbel launch."""
+        from .gumbel import considered_visits
+        m = int(max_considered)
+        cv = considered_visits(min(m, self.n_actions), self.n_sims) if m > 0 else np.zeros(0, dtype=np.int32)
+        check(self.lib.rz_mz_set_gumbel(self.handle, m, float(c_visit), float(c_scale), ctypes.c_void_p(cv.ctypes.data) if m > 0 else None,
+                                        cv.size), 'rz_mz_set_gumbel')
+        self.gumbel_considered = m
+        if m > 0 and getattr(self, 'gumbel_action', None) is None:
+            t = self.torch
+            self.gumbel_action = t.zeros(self.n_games, dtype=t.int32, device=self.device)
+            self.gumbel_pi = t.zeros((self.n_games, self.n_actions), dtype=t.float32, device=self.device)
+        return self
+
+    def search_gumbel(self, hidden, n_sims, gumbel, trace=False):
+        """``search_fused`` under Gumbel MuZero's rule, ONE launch (k_mz_search's GUMBEL instantiations; ``set_gumbel`` first,
+        ``init_roots`` without noise, ``n_sims`` = the tree's).  ``gumbel`` float32 [G, A] on the device: the move's Gumbel(0, 1) draws
+        (zeros: the greedy move).  -> (actions int32 [G], pi float32 [G, A]) -- the move, among the most visited actions the arg-max of
+        g + logit + sigma(completed Q), and the policy target pi' = softmax(logits + sigma(completed Q)) of the root; the tensors are
+        the tree's own and are rewritten by the next call.  ``trace``: -> (actions, pi, trace) with ``search_fused``'s trace."""
+        t = self.torch
+        if gumbel.dtype != t.float32 or tuple(gumbel.shape) != (self.n_games, self.n_actions) or not gumbel.is_contiguous() \
+                or gumbel.device.type != 'cuda':
+            raise ValueError('search_gumbel: gumbel must be a contiguous float32 [n_games, n_actions] tensor on the device')
+        if getattr(self, 'gumbel_action', None) is None:
+            raise _hip.HipError('search_gumbel: set_gumbel first')
+        out, args = self._trace(n_sims, trace)
+        check(self.lib.rz_mz_search_gumbel(self.handle, _ptr(hidden), int(n_sims), _ptr(gumbel), _ptr(self.gumbel_action), _ptr(self.gumbel_pi),
+                                           *args, self.stream()), 'rz_mz_search_gumbel')
+        return (self.gumbel_action, self.gumbel_pi, out) if trace else (self.gumbel_action, self.gumbel_pi)
 
     def stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -259,4 +301,5 @@ class MuZeroTree(object):
         flags = ctypes.c_int32(0)
         check(self.lib.rz_mz_error_flags(self.handle, ctypes.byref(flags)), 'rz_mz_error_flags')
         if flags.value:
-            raise _hip.HipError('MuZero tree error flags 0x%x (tree arena full)' % flags.value)
+            raise _hip.HipError('MuZero tree error flags 0x%x (1: tree arena full; 4: a Gumbel move outside the actions; 16: a Gumbel search '
+                                'on roots init_roots had not just made)' % flags.value)

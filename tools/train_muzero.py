@@ -46,7 +46,8 @@ class MuZeroPipeline(object):
     def __init__(self, n_envs=256, n_sims=50, unroll_steps=5, td_steps=10, discount=0.997, batch_size=256,
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
                  reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False, env='cartpole',
-                 max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None):
+                 max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None, search='puct', gumbel_considered=4,
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0):
         """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
@@ -66,7 +67,9 @@ class MuZeroPipeline(object):
         ``value_transform``: MuZero's invertible value rescaling h (arXiv:1911.08265v2 appendix F) on the scalar heads: the net is
         built with it (``MuZeroNet(value_transform=True)``), so every search inverts the heads' reward and value (inside the search
         kernel) and the buffer -- either one -- hands out h of the value and reward targets; Reanalyse reads the flag from the net.
-        Off (the default), nothing changes.  ``eval_envs``: environments of ``evaluate`` (None: as many as train)."""
+        Off (the default), nothing changes.  ``eval_envs``: environments of ``evaluate`` (None: as many as train).
+        ``search``: 'gumbel' plays with Gumbel MuZero's rule (MuZeroSelfPlay(search='gumbel', gumbel_considered, gumbel_c_visit,
+        gumbel_c_scale): device moves, the policy targets are pi'); the evaluation player then plays greedily, g = 0.  'puct': as before."""
         if env not in ENVIRONMENTS:
             raise ValueError('unknown environment %r (known: %s)' % (env, ', '.join(ENVIRONMENTS)))
         if max_episode_steps is not None and env == 'cartpole':
@@ -91,6 +94,8 @@ class MuZeroPipeline(object):
         else:
             self.env = AcrobotBatch(n_envs, device, seed=seed, **({} if max_episode_steps is None else dict(max_episode_steps=max_episode_steps)))
         route = {} if whole_moves is None else dict(fused_moves=bool(whole_moves))
+        if search != 'puct':
+            route.update(search=search, gumbel_considered=gumbel_considered, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
         self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed, **route)
         self._env_class, self._route, self._n_sims, self._discount, self._device = env_class, route, n_sims, discount, device
         self._max_episode_steps = max_episode_steps
@@ -171,7 +176,8 @@ class MuZeroPipeline(object):
             kw = {} if self._max_episode_steps is None else dict(max_episode_steps=self._max_episode_steps)
             env = self._env_class(n_envs, self._device, seed=int(seed), **kw)
             sp = MuZeroSelfPlay(self.agent.net, env, n_sims=self._n_sims, discount=self._discount, temperature=0.0,
-                                root_exploration_fraction=0.0, seed=int(seed), **self._route)
+                                root_exploration_fraction=0.0, seed=int(seed), **self._route,
+                                **(dict(gumbel_greedy=True) if 'search' in self._route else {}))
             self._evaluator = (sp, n_envs, int(seed))
         sp = self._evaluator[0]
         sp.restart_episodes()
@@ -285,6 +291,12 @@ def build_parser():
     ap.add_argument('--eval-every', type=int, default=0, metavar='N',
                     help='after every N-th iteration, a greedy evaluation (temperature 0, no root noise) on environments of its own '
                          'from fixed initial states, reported on a line of its own (0 = never)')
+    ap.add_argument('--search', choices=('puct', 'gumbel'), default='puct',
+                    help='the search rule: pUCT with Dirichlet noise, or Gumbel MuZero (top-m Gumbel draw, Sequential Halving, policy targets '
+                         'from completed Q-values; device moves)')
+    ap.add_argument('--gumbel-considered', type=int, default=4, metavar='M', help='actions the Gumbel root considers (clamped to the action count)')
+    ap.add_argument('--gumbel-c-visit', type=float, default=50.0)
+    ap.add_argument('--gumbel-c-scale', type=float, default=1.0)
     ap.add_argument('--eval-envs', type=int, default=None, metavar='M', help='environments of an evaluation (default: --envs)')
     return ap
 
@@ -300,7 +312,8 @@ def main(argv=None):
                           updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
                           prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta, fused_learner=args.fused_learner,
                           env=args.env, max_episode_steps=args.max_episode_steps, whole_moves=True if args.whole_moves else None,
-                          value_transform=args.value_transform, eval_envs=args.eval_envs)
+                          value_transform=args.value_transform, eval_envs=args.eval_envs, search=args.search,
+                          gumbel_considered=args.gumbel_considered, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
     pipe.run(args.iterations, eval_every=args.eval_every)
     if args.save:
         pipe.agent.save_model(args.save)
