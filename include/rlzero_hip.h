@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 49
+#define RZ_ABI_VERSION 50
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -874,7 +874,7 @@ int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace
 int rz_mz_set_search_shape(rz_muzero *e, int32_t games_per_workgroup);
 /* The value transform (ABI 43; csrc/rz_mz_value.h): MuZero's invertible h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, eps = 0.001
  * (arXiv:1911.08265v2 appendix F), for a model whose scalar reward and value heads are trained on h of their targets (the paper's
- * categorical support is not built).  rz_mz_set_value_transform(e, 1): every launcher of k_mz_search -- rz_mz_search, rz_mz_play_env,
+ * categorical support: rz_mz_set_support below).  rz_mz_set_value_transform(e, 1): every launcher of k_mz_search -- rz_mz_search, rz_mz_play_env,
  * rz_mz_play_cartpole -- takes the kernel's VT instantiation, in which wave 0 replaces the network's reward and value of a simulation by
  * float32(h^-1(float64(.))) right after the heads are finished: before the trace arrays are written (they hold what entered the
  * backup) and before expand + backup.  The tree, its MinMax bounds, the root value of a record, what Reanalyse writes back and the
@@ -903,6 +903,17 @@ int rz_mz_set_gumbel(rz_muzero *e, int32_t max_considered, double c_visit, doubl
 int rz_mz_search_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const float *d_gumbel, int32_t *d_action_out, float *d_pi_out,
                         int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward,
                         float *d_trace_probs, float *d_trace_value, void *stream);
+/* Categorical reward and value heads in the one-launch search (ABI 50; csrc/rz_mz_support.h holds the rule, k_mz_search's CAT
+ * instantiations run it): each head is a softmax over the 2 S + 1 integer bins -S .. S of h's space, 1 <= S <= 31, and the scalar the
+ * trace, the backup and MinMax see is float32(h^-1(expectation)); everything behind it stays in raw units, as with the value transform.
+ * rz_mz_load_model_support: rz_mz_load_model for such a model -- the same 14 tensors, rew2.weight and val.weight [2 S + 1][64],
+ * rew2.bias and val.bias [2 S + 1].  rz_mz_set_support(e, S): rz_mz_search and rz_mz_search_gumbel launch the CAT instantiations
+ * (0, the default: scalar heads, the code of ABI 49); rz_mz_search_plan (whole_moves 0) then reports that launch, whose LDS holds
+ * 45696 bytes more (relu(rew1) of the tile, the two heads' logits, weights and biases), so trees leave LDS at smaller shapes.  RZ_ERR_ARG with the
+ * reason, nothing launched: S outside 1 .. 31; a hidden size other than 64; a search whose support is not the loaded model's; a support
+ * without the value transform; whole moves (rz_mz_play_env, rz_mz_play_cartpole) while either is set -- they keep scalar heads. */
+int rz_mz_load_model_support(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden, int32_t support);
+int rz_mz_set_support(rz_muzero *e, int32_t support);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action

@@ -74,6 +74,7 @@ struct rz_muzero {
     float *d_model = nullptr;    // one allocation behind the pointers above
     bool model_loaded = false, representation_loaded = false;
     int rep_obs_dim = 0;         // rz_mz_load_representation: the observation features of the loaded rep1
+    bool attributes_set = false;   // the dynamic-LDS attribute of every instantiation (the first load)
     bool f16_ok = false;   // rz_mz_load_model: finite weights and a finite bound on relu(dyn1): whole MOVES may run their layers on the f16 pipe
     float *d_rep = nullptr;      // rz_mz_load_representation
     int n_cus = 256;             // of cfg.device
@@ -84,6 +85,11 @@ struct rz_muzero {
     double gumbel_c_visit = 50.0, gumbel_c_scale = 1.0;
     int32_t *d_gumbel_cv = nullptr;    // [n_sims]: the considered-visits table
     double *d_gumbel_logit = nullptr;  // [n_games][cap]: log(prior) of HBM trees
+    // rz_mz_set_support: S > 0 = categorical heads (rz_mz_search / rz_mz_search_gumbel launch the CAT instantiations, whole moves are
+    // refused); model_support: the support of the heads the last loader uploaded (0: scalar heads) -- a launch needs the two equal
+    int support = 0, model_support = 0;
+    MzSupport cat = {};                // rz_mz_load_model_support: the packed heads inside d_model_cat
+    float *d_model_cat = nullptr;
 };
 
 namespace {
@@ -98,7 +104,7 @@ constexpr auto mz_search_kernel = k_mz_search<TREE_LDS, MOVES, Env, (MOVES ? Env
 // the same rows for the dynamic-LDS attribute, so what can be launched is what was prepared.  A row is a route -- the search alone
 // (kMzNoEnv) or whole moves of an environment kind -- with or without the value transform, and holds its kernel for either placement of
 // the trees.  A new environment is one line: its two rows.  (The rows stand in the order of the instantiations in the code object.)
-typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel);
+typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzNoSupport);
 constexpr int kMzNoEnv = -1;
 struct MzSearchRow {
     int kind;   // RZ_MZ_ENV_* of whole moves, kMzNoEnv for rz_mz_search
@@ -110,7 +116,7 @@ constexpr MzSearchRow mz_search_row(int kind) {
     return {kind, VT, mz_search_kernel<true, MOVES, Env, VT>, mz_search_kernel<false, MOVES, Env, VT>};
 }
 // the GUMBEL instantiations (rz_mz_search_gumbel): the search alone, trees in LDS and in HBM, with and without the value transform
-typedef void (*MzGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel);
+typedef void (*MzGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzNoSupport);
 struct MzGumbelRow {
     bool vt;
     MzGumbelFn tree_lds, tree_hbm;
@@ -125,6 +131,23 @@ constexpr MzSearchRow kMzSearchRows[] = {
     mz_search_row<true, rzmze::EnvAcrobot, true>(RZ_MZ_ENV_ACROBOT), mz_search_row<true, rzmze::EnvAcrobot, false>(RZ_MZ_ENV_ACROBOT),
 };
 constexpr MzGumbelRow kMzGumbelRows[] = {mz_gumbel_row<false>(), mz_gumbel_row<true>()};
+// the CAT instantiations (rz_mz_set_support): the search alone with the value transform, pUCT and Gumbel, trees in LDS and in HBM
+typedef void (*MzCatFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzSupport);
+typedef void (*MzCatGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzSupport);
+constexpr MzCatFn kMzCatLds = k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, true, false, true>;
+constexpr MzCatFn kMzCatHbm = k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, true, false, true>;
+constexpr MzCatGumbelFn kMzCatGumbelLds = k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, true, true, true>;
+constexpr MzCatGumbelFn kMzCatGumbelHbm = k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, true, true, true>;
+
+// what a launch with categorical heads needs (rz_mz_set_support), and what one without them must not meet
+int mz_support_ready(const rz_muzero *e) {
+    if (e->support != e->model_support)
+        return rz_fail(RZ_ERR_ARG, "the search is set to support %d (rz_mz_set_support; 0 = scalar heads) but the loaded model has support %d",
+                       e->support, e->model_support);
+    if (e->support > 0 && !e->value_transform)
+        return rz_fail(RZ_ERR_ARG, "a support needs the value transform (rz_mz_set_value_transform): its bins lie in h's space");
+    return RZ_OK;
+}
 
 int mz_ready(rz_muzero *e) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
@@ -141,42 +164,57 @@ struct MzPlan {
     int lds;        // dynamic LDS bytes of the launch
 };
 // `gumbel`: a launch of the GUMBEL instantiations (their LDS holds more per node and per launch: mz_search_lds_bytes)
+// (a support net's launch -- never whole moves -- carries the CAT instantiations' extra LDS)
 MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false) {
     MzPlan p;
+    const bool cat = e->support > 0 && !whole_moves;
     const int w1c = mz_w1_cols(whole_moves, e->cfg.n_actions <= kMzMaxA ? e->cfg.n_actions : kMzMaxA);
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
     // other, so the 16 columns of a tile are filled first (profiles/r02/muzero_search_shape.txt)
     p.gpw = e->games_per_wg > 0 ? e->games_per_wg : kMzMaxGpw;
     // the trees go to LDS when two workgroups still fit on a CU
     const MzDev &D = e->dev;
-    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true, w1c, gumbel) <= 80 * 1024;
-    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds, w1c, gumbel);
+    p.tree_lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, true, w1c, gumbel, cat) <= 80 * 1024;
+    p.lds = mz_search_lds_bytes(p.gpw, D.cap, D.path_stride, D.n_sims, p.tree_lds, w1c, gumbel, cat);
     return p;
 }
 
 // play != nullptr: whole moves of the environment `kind` (checked by rz_mz_play_env)
 int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, int kind, void *stream) {
+    RZ_TRY(mz_support_ready(e));
     const MzPlan plan = mz_search_plan(e, play != nullptr);
     if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
+    if (e->support > 0) {   // (never whole moves: mz_play_launch has refused them)
+        (plan.tree_lds ? kMzCatLds : kMzCatHbm)<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{},
+                                                                                                MzNoGumbel{}, e->cat);
+        return rz_launched("k_mz_search (support)");
+    }
     const int route = play != nullptr ? kind : kMzNoEnv;
     MzSearchFn fn = nullptr;
     for (const MzSearchRow &row : kMzSearchRows)
         if (row.kind == route && row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
     if (fn == nullptr) return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
-    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
     const MzPlay none = {};
-    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, play != nullptr ? *play : none, MzNoGumbel{});
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, play != nullptr ? *play : none, MzNoGumbel{},
+                                                       MzNoSupport{});
     return rz_launched("k_mz_search");
 }
 
 int mz_launch_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzGumbel &Z, void *stream) {
+    RZ_TRY(mz_support_ready(e));
     const MzPlan plan = mz_search_plan(e, false, true);
     if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
+    if (e->support > 0) {
+        (plan.tree_lds ? kMzCatGumbelLds : kMzCatGumbelHbm)<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T,
+                                                                                                            MzPlay{}, Z, e->cat);
+        return rz_launched("k_mz_search (gumbel, support)");
+    }
     MzGumbelFn fn = nullptr;
     for (const MzGumbelRow &row : kMzGumbelRows)
         if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
-    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
-    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z);
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z, MzNoSupport{});
     return rz_launched("k_mz_search (gumbel)");
 }
 
@@ -308,7 +346,8 @@ int rz_mz_root_stats(rz_muzero *e, int32_t *d_n, double *d_value_sum, double *d_
     return rz_launched("k_mz_root_stats");
 }
 
-int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden) {
+// the loaders' common part; S > 0: the heads are the support's (rz_mz_load_model_support), uploaded to an allocation of their own size
+static int mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden, int S) {
     RZ_ENTER(mz_ready, e);
     if (h_params == nullptr || n_params != 14) return rz_fail(RZ_ERR_ARG, "expected the 14 tensors of the dynamics / reward / prediction layers");
     if (hidden != kMzH) return rz_fail(RZ_ERR_ARG, "the fused search is built for hidden size 64");
@@ -316,12 +355,13 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
     if (A > kMzMaxA) return rz_fail(RZ_ERR_ARG, "the fused search handles up to 8 actions");
     for (int i = 0; i < 14; ++i)
         if (!h_params[i]) return rz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
-    const rzmp::Model packed = rzmp::pack_model(h_params, A);   // layouts, scales and the f16 verdict: rz_mz_pack.h
+    const rzmp::Model packed = rzmp::pack_model(h_params, A, S);   // layouts, scales and the f16 verdict: rz_mz_pack.h
     const size_t *off = packed.off, off_scales = packed.off_scales, total = packed.host.size();
     e->f16_ok = packed.f16_ok;
     RZ_HIP(hipDeviceSynchronize());
-    if (e->d_model == nullptr) {
-        RZ_TRY(e->pool.alloc(&e->d_model, (long long)total));
+    float *&d_model = S > 0 ? e->d_model_cat : e->d_model;
+    if (d_model == nullptr) RZ_TRY(e->pool.alloc(&d_model, (long long)total));
+    if (!e->attributes_set) {
         const int most = 160 * 1024;
         for (const MzSearchRow &row : kMzSearchRows)
             for (MzSearchFn fn : {row.tree_lds, row.tree_hbm})
@@ -331,15 +371,38 @@ int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_param
             for (MzGumbelFn fn : {row.tree_lds, row.tree_hbm})
                 if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
                     return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        for (const void *fn : {(const void *)kMzCatLds, (const void *)kMzCatHbm, (const void *)kMzCatGumbelLds, (const void *)kMzCatGumbelHbm})
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+                return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        e->attributes_set = true;
     }
-    if (hipMemcpy(e->d_model, packed.host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(d_model, packed.host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy(model) failed");
-    const float *b = e->d_model;
+    const float *b = d_model;
     const MzModel seen = e->model;   // (the representation layers are loaded by their own call)
+    // (S > 0: rew2 / val of e->model point at the PACKED 64 x 64 heads in d_model_cat, which only e->cat reads -- every launch is behind mz_support_ready)
     e->model = MzModel{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], b + off[6], b + off[7],
                        b + off[8], b + off[9], b + off[10], b + off[11], b + off[12], b + off[13],
                        seen.rep1_w, seen.rep1_b, seen.rep2_w, seen.rep2_b, b + off_scales};
+    e->cat = S > 0 ? MzSupport{b + off[6], b + off[7], b + off[12], b + off[13], S} : MzSupport{};
+    e->model_support = S;
     e->model_loaded = true;
+    return RZ_OK;
+}
+
+int rz_mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden) {
+    return mz_load_model(e, h_params, n_params, hidden, 0);
+}
+
+int rz_mz_load_model_support(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden, int32_t support) {
+    if (!rzmzs::support_ok(support)) return rz_fail(RZ_ERR_ARG, "support must be 1 .. 31 (2 S + 1 <= 63 bins), not %d", support);
+    return mz_load_model(e, h_params, n_params, hidden, support);
+}
+
+int rz_mz_set_support(rz_muzero *e, int32_t support) {
+    if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
+    if (support != 0 && !rzmzs::support_ok(support)) return rz_fail(RZ_ERR_ARG, "support must be 0 (scalar heads) or 1 .. 31 (2 S + 1 <= 63 bins), not %d", support);
+    e->support = support;
     return RZ_OK;
 }
 
@@ -427,6 +490,8 @@ static int mz_play_launch(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n
     RZ_ENTER(mz_ready, e);
     if (e->gumbel_considered > 0)
         return rz_fail(RZ_ERR_ARG, "the Gumbel search is on (rz_mz_set_gumbel): whole moves keep the pUCT rule and are not served");
+    if (e->support > 0 || e->model_support > 0)
+        return rz_fail(RZ_ERR_ARG, "categorical heads (rz_mz_set_support / rz_mz_load_model_support): whole moves keep scalar heads and are not served");
     int env_actions = 0, env_obs = 0;
     if (kind == RZ_MZ_ENV_CARTPOLE) {
         env_actions = rzmze::EnvCartPole::kActions;
@@ -537,7 +602,7 @@ int rz_mz_debug_profile(long long *h_out16) {
 
 int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    const MzPlan plan = mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);
+    const MzPlan plan = mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);   // (a support: read from the handle)
     if (games_per_workgroup) *games_per_workgroup = plan.gpw;
     if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
     if (lds_bytes) *lds_bytes = plan.lds;

@@ -51,6 +51,7 @@
 #include "rz_mz_env.h"
 #include "rz_mz_gumbel.h"
 #include "rz_mz_pack.h"
+#include "rz_mz_support.h"
 #include "rz_mz_value.h"
 
 #pragma clang fp contract(off)
@@ -61,6 +62,7 @@ using rzmp::kMzH, rzmp::kMzMaxA, rzmp::kMzObs;   // the model's sizes: defined o
 constexpr int kMzWaves = 4, kMzTile = 16, kMzKX = kMzH + kMzMaxA, kMzMaxGpw = 16;
 constexpr int kMzRedRows = 4 + kMzMaxA;   // min, max, reward, value, logits
 constexpr int kMzHeadRows = 2 + kMzMaxA;  // rew2, val, pol rows
+constexpr int kMzLgStride = rzmzs::kLanes + 1;   // (CAT) floats between two games' logits in LDS: lane (game, chunk) reads bank game + 16 chunk + j
 typedef float mz_f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 mz_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 mz_f16x4 __attribute__((ext_vector_type(4)));
@@ -113,7 +115,10 @@ __host__ __device__ inline int mz_search_fixed_floats(int w1_cols) {
 __host__ __device__ constexpr int mz_w1_cols(bool whole_moves, int n_actions) { return whole_moves && n_actions > 2 ? n_actions : 2; }
 // `gumbel`: the GUMBEL instantiations add, per node of an LDS tree, log(prior) (a double) and the raw value v_hat (a float), and for
 // every launch the considered-visits table (int32 [n_sims]) and the games' Gumbel rows (float [gpw][8])
-__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols, bool gumbel = false) {
+// `cat`: the CAT instantiations add, behind everything else, relu(rew1)'s activations [64][16], the two heads' logits [2][16][65], their
+// weights [2][64][64] and their biases [2][64]
+__host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols, bool gumbel = false,
+                                                   bool cat = false) {
     int bytes = mz_search_fixed_floats(w1_cols) * 4 + gpw * path_stride * 4;
     bytes = (bytes + 15) / 16 * 16;
     bytes += 2 * (((n_sims_cfg + 2) * 8 + 15) / 16 * 16);   // log and sqrt tables
@@ -122,6 +127,7 @@ __host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_st
         if (tree_lds) bytes += gpw * (cap + 1) * 8 + (gpw * (cap + 1) * 4 + 15) / 16 * 16;
         bytes += (n_sims_cfg * 4 + 15) / 16 * 16 + gpw * rzmzg::kMaxA * 4;
     }
+    if (cat) bytes = (bytes + 15) / 16 * 16 + (kMzH * kMzTile + 2 * kMzTile * kMzLgStride + 2 * kMzH * rzmzs::kLanes + 2 * rzmzs::kLanes) * 4;
     return bytes;
 }
 
@@ -188,6 +194,29 @@ struct MzGumbel {
     double c_visit, c_scale;
 };
 struct MzNoGumbel {};
+
+// ---- categorical reward and value heads (the CAT instantiations; the rule and its one summation order: rz_mz_support.h)
+// Each head is a 64 x 64 layer -- the support's B = 2 S + 1 <= 63 bins, padded with rows of zero weights and a bias of -inf -- run on the
+// whole 16-game tile by all four waves with the trunk's arithmetic (v_mfma_f32_16x16x4_f32; wave w owns bins 16 w .. 16 w + 15): the
+// reward head beside S3, where relu(rew1) waits in LDS (RA), the value head behind S4 on relu(pre1), which takes relu(dyn1)'s place in
+// HP.  The trunk's fragments fill the registers (32 more spill inside the simulation loop), so the heads' weights wait in LDS, 32 KB:
+// [head][k][64] with row k rotated by 16 k bins, so that the A operand of a step -- lane (q, n): W[bin 16 w + n][k = 4 s + q] -- is one
+// conflict-free ds_read_b32 at a column the lane keeps for the launch, (16 (w + q) + n) mod 64.  The logits go to LDS as [head][game][bin]; at S5 the four lanes wave 0
+// has per game each take a chunk of 16 bins -- maximum, denominator and numerator in fp64 with the header's functions -- and combine them
+// with two lane exchanges in the header's order; h^-1 of the quotient is the scalar the trace, the backup and MinMax see.
+struct MzSupport {
+    const float *rew2_w, *rew2_b, *val_w, *val_b;   // k-major [64][64 bins] and [64] (rz_mz_pack.h: pack_model with a support)
+    int S;
+};
+struct MzNoSupport {};
+// the double of lane l ^ 1 / l ^ 2 within a quad (DPP quad_perm [1, 0, 3, 2] = 0xB1, [2, 3, 0, 1] = 0x4E)
+template <int CTRL>
+__device__ __forceinline__ double mz_quad_f64(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xF, 0xF, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 template <int W>
 __device__ __forceinline__ unsigned mz_xor_word(unsigned x, int l) {   // the word of lane l ^ W, W = 16 | 32
@@ -460,11 +489,15 @@ __device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, fl
 // GUMBEL (MOVES = false only): the search rule is Gumbel MuZero's (above; rz_mz_set_gumbel) instead of pUCT -- wave 0's tree phase
 // is the (n, q) walk, the launch starts with the prediction of the roots' own states (their raw values) and ends with the move and
 // pi' of every game in Z.action_out / Z.pi_out.  The matrix-pipe stages are the same code.  Z: MzGumbel, an empty record otherwise.
+// CAT (MOVES = false, VT = true only): the reward and value heads are softmaxes over a support (above; rz_mz_set_support), read as
+// h^-1 of their expectation.  C: MzSupport, an empty record otherwise.
 template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false,
-          bool GUMBEL = false>
+          bool GUMBEL = false, bool CAT = false>
 __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P,
-                                                                 typename std::conditional<GUMBEL, MzGumbel, MzNoGumbel>::type Z) {
+                                                                 typename std::conditional<GUMBEL, MzGumbel, MzNoGumbel>::type Z,
+                                                                 typename std::conditional<CAT, MzSupport, MzNoSupport>::type C) {
     static_assert(!(GUMBEL && MOVES), "whole moves keep the pUCT rule");
+    static_assert(!CAT || (VT && !MOVES), "the support lies in h's space; whole moves keep scalar heads");
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
     constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
     constexpr int W1C = mz_w1_cols(MOVES, Env::kActions);
@@ -501,6 +534,11 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     if (TREE_LDS) pp += gpw * tcap * 8 + (gpw * tcap * 4 + 15) / 16 * 16;
     int32_t *CV = reinterpret_cast<int32_t *>(pp);   // [n_sims]
     float *GB = reinterpret_cast<float *>(pp + (E.n_sims * 4 + 15) / 16 * 16);   // [gpw][8]
+    // CAT, behind everything else (mz_search_lds_bytes): relu(rew1) [k][game] and the heads' logits [reward | value][game][kMzLgStride]
+    float *RA = reinterpret_cast<float *>(mz_lds + (mz_search_lds_bytes(gpw, E.cap, E.path_stride, E.n_sims, TREE_LDS, W1C, GUMBEL, false) + 15) / 16 * 16);
+    float *LG = RA + kMzH * kMzTile;
+    float *WH = LG + 2 * kMzTile * kMzLgStride;      // [reward | value][k][64]: row k rotated by 16 k bins
+    float *HBC = WH + 2 * kMzH * rzmzs::kLanes;      // [reward | value][64]: the heads' biases
 
     // ---- once: weight fragments into registers (A operand of 16x16x4: lane holds W[unit 16w + n][k = 4s + q])
     // (the representation network's fragments -- 18 + 8 registers, used once per MOVE -- are fetched at the start of every
@@ -594,14 +632,26 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         br[i] = M.rew1_b[row];
         bp[i] = M.pre1_b[row];
     }
+    if constexpr (CAT) {
+        for (int i = tid; i < kMzH * rzmzs::kLanes; i += 64 * kMzWaves) {
+            const int k = i >> 6, col = ((i & 63) + 16 * k) & 63;
+            WH[k * rzmzs::kLanes + col] = C.rew2_w[i];
+            WH[(kMzH + k) * rzmzs::kLanes + col] = C.val_w[i];
+        }
+        if (tid < rzmzs::kLanes) {
+            HBC[tid] = C.rew2_b[tid];
+            HBC[rzmzs::kLanes + tid] = C.val_b[tid];
+        }
+    }
     if (tid == 0) {
-        HB[0] = M.rew2_b[0];
-        HB[1] = M.val_b[0];
+        HB[0] = CAT ? 0.0f : M.rew2_b[0];
+        HB[1] = CAT ? 0.0f : M.val_b[0];
     }
     if (tid < A) HB[2 + tid] = M.pol_b[tid];
     for (int i = tid; i < kMzHeadRows * kMzH; i += 64 * kMzWaves) {
         const int row = i >> 6, k = i & 63;
-        HW[i] = row == 0 ? M.rew2_w[k] : row == 1 ? M.val_w[k] : row - 2 < A ? M.pol_w[(row - 2) * kMzH + k] : 0.0f;
+        if constexpr (CAT) HW[i] = row >= 2 && row - 2 < A ? M.pol_w[(row - 2) * kMzH + k] : 0.0f;   // (rows 0, 1: the scalar heads, unused)
+        else HW[i] = row == 0 ? M.rew2_w[k] : row == 1 ? M.val_w[k] : row - 2 < A ? M.pol_w[(row - 2) * kMzH + k] : 0.0f;
     }
     for (int i = tid; i < kMzKX * kMzTile; i += 64 * kMzWaves) XS[i] = 0.0f;   // (the padding rows 64 + A .. 71 stay zero)
     for (int i = tid; i < kMzObs * kMzTile; i += 64 * kMzWaves) OBS[i] = 0.0f;
@@ -771,8 +821,13 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
 #pragma unroll
             for (int i = 0; i < 4; ++i) p[i] = fmaxf(p[i], 0.0f);
         }
-        const float pv = mz_head_partial(p, HW + 1 * kMzH, w, q, l);
-        if (q == 0) RED[(3 * kMzWaves + w) * kMzTile + n] = pv;
+        if constexpr (CAT) {   // the value head is a layer of its own (value_logits): relu(pre1) takes relu(dyn1)'s place
+#pragma unroll
+            for (int i = 0; i < 4; ++i) HP[(16 * w + 4 * q + i) * kMzTile + n] = p[i];
+        } else {
+            const float pv = mz_head_partial(p, HW + 1 * kMzH, w, q, l);
+            if (q == 0) RED[(3 * kMzWaves + w) * kMzTile + n] = pv;
+        }
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
             if (a < A) {
@@ -781,11 +836,47 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             }
         }
     };
-    // (lane that owns a game) value and softmax(policy logits) from the partial sums, waves in order
+    // (CAT) a head's logits for the tile from the activations `act` [k][game]: this wave's 16 bins of every game -> LG[head]
+    auto head_logits = [&](const float *act, int head) {
+        if constexpr (CAT) {
+            const float4 bias = *reinterpret_cast<const float4 *>(HBC + head * rzmzs::kLanes + 16 * w + 4 * q);
+            mz_f32x4 lg = {bias.x, bias.y, bias.z, bias.w};
+            const float *wk = WH + (head * kMzH + q) * rzmzs::kLanes + ((16 * (w + q) + n) & 63);
+#pragma unroll
+            for (int s = 0; s < kMzH / 4; ++s)
+                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(wk[4 * s * rzmzs::kLanes], act[(4 * s + q) * kMzTile + n], lg, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) LG[(head * kMzTile + n) * kMzLgStride + 16 * w + 4 * q + i] = lg[i];
+        }
+    };
+    // (CAT, every lane of wave 0) h^-1 of the expectation of game `te`'s head: the lane's chunk of 16 bins, then the game's four lanes
+    // combined in rzmzs::combine4's order -- two exchanges, c ^ 1 then c ^ 2 (GUMBEL: lanes 16 q + n; else the quad 4 ge + ca)
+    auto cat_scalar = [&](int head) -> float {
+        if constexpr (CAT) {
+            const int c = GUMBEL ? q : (l & 3);
+            const float *x = LG + (head * kMzTile + te) * kMzLgStride + rzmzs::kChunk * c;
+            auto x1 = [&](double v) { return GUMBEL ? mz_xor_f64<16>(v, l) : mz_quad_f64<0xB1>(v); };
+            auto x2 = [&](double v) { return GUMBEL ? mz_xor_f64<32>(v, l) : mz_quad_f64<0x4E>(v); };
+            double m = rzmzs::chunk_max(x, c, C.S), o = x1(m);
+            m = o > m ? o : m;
+            o = x2(m);
+            m = o > m ? o : m;
+            double den, num;
+            rzmzs::chunk_sums(x, c, C.S, m, &den, &num);
+            den = den + x1(den);
+            num = num + x1(num);
+            den = den + x2(den);
+            num = num + x2(num);
+            return (float)rzmzv::value_h_inv(num / den);
+        } else {
+            return 0.0f;
+        }
+    };
+    // (lane that owns a game) value and softmax(policy logits) from the partial sums, waves in order (CAT: the value is cat_scalar's)
     auto finish_prediction = [&](float &value, float (&probs)[MAXA]) {
         value = HB[1];
 #pragma unroll
-        for (int u = 0; u < kMzWaves; ++u) value += RED[(3 * kMzWaves + u) * kMzTile + te];
+        for (int u = 0; u < (CAT ? 0 : kMzWaves); ++u) value += RED[(3 * kMzWaves + u) * kMzTile + te];
         float logit[MAXA], mxl = -INFINITY;
 #pragma unroll
         for (int a = 0; a < MAXA; ++a) {
@@ -916,10 +1007,15 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             __syncthreads();
             predict_partials();
             __syncthreads();
+            if constexpr (CAT) {
+                head_logits(HP, 1);
+                __syncthreads();
+            }
             if (w == 0) {
                 float value, probs[MAXA];
                 finish_prediction(value, probs);
-                if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);
+                if constexpr (CAT) value = cat_scalar(1);
+                else if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);
                 if (mine) gtree.set_v_hat(0, value);
                 gum0 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q];
                 gum1 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q + 1];
@@ -1020,14 +1116,20 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             wave_extremes(t);
 #pragma unroll
             for (int i = 0; i < 4; ++i) r[i] = fmaxf(r[i], 0.0f);
-            const float pr = mz_head_partial(r, HW, w, q, l);
-            if (q == 0) RED[(2 * kMzWaves + w) * kMzTile + n] = pr;
+            if constexpr (CAT) {   // the reward head runs beside S3, on these activations
+#pragma unroll
+                for (int i = 0; i < 4; ++i) RA[(16 * w + 4 * q + i) * kMzTile + n] = r[i];
+            } else {
+                const float pr = mz_head_partial(r, HW, w, q, l);
+                if (q == 0) RED[(2 * kMzWaves + w) * kMzTile + n] = pr;
+            }
         }
         MZ_TICK(5);
         __syncthreads();
         MZ_TICK(6);
         // S3: per-sample min-max scaling of the new state, stored for the leaf
         scale_and_store(t);
+        head_logits(RA, 0);
         MZ_TICK(7);
         __syncthreads();
         MZ_TICK(8);
@@ -1035,15 +1137,22 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         predict_partials();
         MZ_TICK(9);
         __syncthreads();
+        if constexpr (CAT) {   // S4b: the value head on relu(pre1)
+            head_logits(HP, 1);
+            __syncthreads();
+        }
         MZ_TICK(10);
         // S5 (wave 0): finish the heads, expand + backup
         if (w == 0) {
             float reward = HB[0];
 #pragma unroll
-            for (int u = 0; u < kMzWaves; ++u) reward += RED[(2 * kMzWaves + u) * kMzTile + te];
+            for (int u = 0; u < (CAT ? 0 : kMzWaves); ++u) reward += RED[(2 * kMzWaves + u) * kMzTile + te];
             float value, probs[MAXA];
             finish_prediction(value, probs);
-            if constexpr (VT) {   // widened, inverted in fp64, rounded once
+            if constexpr (CAT) {
+                reward = cat_scalar(0);
+                value = cat_scalar(1);
+            } else if constexpr (VT) {   // widened, inverted in fp64, rounded once
                 reward = (float)rzmzv::value_h_inv((double)reward);
                 value = (float)rzmzv::value_h_inv((double)value);
             }

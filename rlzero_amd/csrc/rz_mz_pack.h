@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <vector>
 
+#include "rz_mz_support.h"
+
 namespace rzmp {
 
 // the sizes the fused search is built for: floats of a hidden state, the most actions, the most observation features (rep1's rows)
@@ -68,6 +70,9 @@ inline float s1_for(double bound) {
 // go k-major, w[k][unit] = torch w[unit][k] (dyn1.w: [H+A][H], its action rows last); every other tensor is copied as it is (pol.w
 // stays [A][H]).  Behind them, at off_scales, 8 floats: [0..3] pow2_for(wmax_of) of dyn1, dyn2, rew1, pre1 (MzModel::f16_scales),
 // [4] s1_for(relu_dyn1_bound), [5..7] zero.
+// With a support S > 0 (rz_mz_load_model_support; rz_mz_support.h) rew2.w and val.w are [B][H] and rew2.b, val.b [B], B = 2 S + 1: each
+// head is packed as a 64 x 64 layer like the trunk's -- k-major w[k][bin], 64 bins -- and its bias as 64 floats; the padding bins B .. 63
+// have zero weights and the bias rzmzs::pad_bias() (-inf), so a padding bin's logit is -inf and its softmax term exactly 0.
 struct Model {
     std::vector<float> host;
     size_t off[14], off_scales;
@@ -78,10 +83,13 @@ struct Model {
     bool f16_ok;   // every value of the 14 tensors and the bound are finite
 };
 
-inline Model pack_model(const float *const *p, int A) {
-    const int KX = kMzH + A;
-    const size_t sizes[14] = {(size_t)KX * kMzH, kMzH, (size_t)kMzH * kMzH, kMzH, (size_t)kMzH * kMzH, kMzH, kMzH, 1,
-                              (size_t)kMzH * kMzH, kMzH, (size_t)A * kMzH, (size_t)A, kMzH, 1};
+inline Model pack_model(const float *const *p, int A, int S = 0) {
+    const int KX = kMzH + A, B = S > 0 ? rzmzs::bins(S) : 1;
+    const size_t head_w = S > 0 ? (size_t)kMzH * rzmzs::kLanes : kMzH, head_b = S > 0 ? rzmzs::kLanes : 1;   // floats of a packed head
+    const size_t sizes[14] = {(size_t)KX * kMzH, kMzH, (size_t)kMzH * kMzH, kMzH, (size_t)kMzH * kMzH, kMzH, head_w, head_b,
+                              (size_t)kMzH * kMzH, kMzH, (size_t)A * kMzH, (size_t)A, head_w, head_b};
+    const size_t given[14] = {sizes[0], sizes[1], sizes[2], sizes[3], sizes[4], sizes[5], (size_t)B * kMzH, (size_t)B,
+                              sizes[8], sizes[9], sizes[10], sizes[11], (size_t)B * kMzH, (size_t)B};   // floats of the tensors as they come
     Model m;
     size_t total = 0;
     for (int i = 0; i < 14; ++i) {
@@ -99,8 +107,17 @@ inline Model pack_model(const float *const *p, int A) {
     transpose(2, kMzH, kMzH);
     transpose(4, kMzH, kMzH);
     transpose(8, kMzH, kMzH);
-    for (int i : {1, 3, 5, 6, 7, 9, 10, 11, 12, 13})
+    for (int i : {1, 3, 5, 6, 7, 9, 10, 11, 12, 13}) {
+        if (S > 0 && (i == 6 || i == 7 || i == 12 || i == 13)) continue;
         for (size_t q = 0; q < sizes[i]; ++q) m.host[m.off[i] + q] = p[i][q];
+    }
+    if (S > 0) {
+        for (int i : {6, 12}) {
+            for (int b = 0; b < B; ++b)
+                for (int k = 0; k < kMzH; ++k) m.host[m.off[i] + (size_t)k * rzmzs::kLanes + b] = p[i][(size_t)b * kMzH + k];
+            for (int b = 0; b < rzmzs::kLanes; ++b) m.host[m.off[i + 1] + b] = b < B ? p[i + 1][b] : rzmzs::pad_bias();
+        }
+    }
     // the f16 layers of whole MOVES (MzModel::f16_scales)
     m.host[m.off_scales + 0] = pow2_for(wmax_of(p[0], KX));
     m.host[m.off_scales + 1] = pow2_for(wmax_of(p[2], kMzH));
@@ -110,7 +127,7 @@ inline Model pack_model(const float *const *p, int A) {
     m.host[m.off_scales + 4] = s1_for(bound);
     bool finite = std::isfinite(bound);
     for (int i = 0; i < 14 && finite; ++i)
-        for (size_t q = 0; q < sizes[i]; ++q)
+        for (size_t q = 0; q < given[i]; ++q)
             if (!std::isfinite(p[i][q])) {
                 finite = false;
                 break;

@@ -27,20 +27,27 @@ def scale_gradient(x, scale):
 class MuZeroAgent(object):
 
     def __init__(self, obs_dim=4, n_actions=2, hidden=64, lr=3e-3, weight_decay=1e-4, device='cuda:0', fused_learner=False, unroll_steps=5,
-                 max_batch=1024, value_transform=False):
-        """``value_transform``: passed on to the net (``MuZeroNet(value_transform=...)``, the flag's owner): the mini-batches must
+                 max_batch=1024, value_transform=False, support=None):
+        """``support``: passed on to the net (``MuZeroNet(support=S)``: categorical reward and value heads over 2 S + 1 bins; it needs
+        ``value_transform``): ``learn`` then takes the cross-entropy of the two heads' logits against ``two_hot`` of the batch's
+        targets (which both buffers hand out as float32(h(z)) already), and a checkpoint carries S.  The fused learner does not serve
+        such a net: ``fused_learner=True`` with ``support`` raises a ValueError before anything is allocated.
+        ``value_transform``: passed on to the net (``MuZeroNet(value_transform=...)``, the flag's owner): the mini-batches must
         then come from a buffer built with it (``learn(batch, buffer=...)`` checks), and a checkpoint carries the setting.
         ``fused_learner``: updates run in the HIP learner (hidden 64, obs_dim <= 16, n_actions <= 8, unroll_steps <= 16: a
         ValueError names the limit before anything is allocated); ``unroll_steps`` and ``max_batch`` size it (batches of K =
         unroll_steps and up to max_batch rows) and mean nothing to the PyTorch route.  The route is fixed for the agent's life; a
         checkpoint moves between the routes."""
         self.fused_learner = bool(fused_learner)
+        if self.fused_learner and support is not None:
+            raise ValueError('fused_learner=True does not serve a net with categorical heads (support=%r): the HIP learner\'s value and '
+                             'reward losses are squared errors of scalar heads; use the PyTorch route (fused_learner=False)' % (support, ))
         if self.fused_learner:
             from .learner import check_limits
             check_limits(obs_dim, n_actions, hidden, unroll_steps)
         self.device = torch.device(device)
         self.n_actions = n_actions
-        self.net = MuZeroNet(obs_dim, n_actions, hidden, value_transform=value_transform).to(self.device)
+        self.net = MuZeroNet(obs_dim, n_actions, hidden, value_transform=value_transform, support=support).to(self.device)
         self.optimizer = None
         self.fused = None
         if self.fused_learner:
@@ -78,6 +85,8 @@ class MuZeroAgent(object):
         K = actions.shape[1]
         net = self.net
         net.train()
+        if net.support is not None:
+            return self._learn_support(obs, actions, tv, tr, tp, mask, weights)
         state, logits, value = net.initial_inference(obs)
         lv = F.mse_loss(value, tv[:, 0], reduction='none')
         lr_ = torch.zeros_like(lv)
@@ -94,6 +103,10 @@ class MuZeroAgent(object):
         else:
             weights = (weights if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)).to(self.device, torch.float32)
             loss = ((0.25 * lv + lr_ + lp) * weights).mean()
+        return self._step(loss, lv, lr_, lp)
+
+    def _step(self, loss, lv, lr_, lp):
+        net = self.net
         self.optimizer.zero_grad()
         loss.backward()
         torch.nn.utils.clip_grad_norm_(net.parameters(), 5.0)
@@ -101,12 +114,43 @@ class MuZeroAgent(object):
         net.eval()
         return float(loss.item()), float(lv.mean().item()), float(lr_.mean().item()), float(lp.mean().item())
 
+    def _learn_support(self, obs, actions, tv, tr, tp, mask, weights):
+        """``learn`` for a net with categorical heads: the value and reward losses are cross-entropies of the heads' logits against
+        ``two_hot`` of the (already transformed) targets; the policy loss, the 1 / K scaling, the halved gradient into the dynamics,
+        the 0.25 on the value loss and the priority weights are ``learn``'s."""
+        from .support import two_hot_torch
+        net, S, K = self.net, self.net.support, actions.shape[1]
+
+        def cross_entropy(head, target):
+            return -(two_hot_torch(target, S) * F.log_softmax(head, dim=1)).sum(dim=1)
+        state = net.representation(obs)
+        logits, vhead = net.prediction_logits(state)
+        lv = cross_entropy(vhead, tv[:, 0])
+        lr_ = torch.zeros_like(lv)
+        lp = -(tp[:, 0] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, 0]
+        for k in range(1, K + 1):
+            state, rhead = net.dynamics_logits(state, actions[:, k - 1])
+            logits, vhead = net.prediction_logits(state)
+            g = 1.0 / K
+            lv = lv + scale_gradient(cross_entropy(vhead, tv[:, k]), g)
+            lr_ = lr_ + scale_gradient(cross_entropy(rhead, tr[:, k]), g)
+            lp = lp + scale_gradient(-(tp[:, k] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, k], g)
+            state = scale_gradient(state, 0.5)
+        if weights is None:
+            loss = (0.25 * lv + lr_ + lp).mean()
+        else:
+            weights = (weights if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)).to(self.device, torch.float32)
+            loss = ((0.25 * lv + lr_ + lp) * weights).mean()
+        return self._step(loss, lv, lr_, lp)
+
     def save_model(self, path):
         """Either route writes torch's Adam ``state_dict`` (the fused one: views of its flat moments, ``step`` as torch stores it)."""
         opt = self.fused.optimizer_state_dict() if self.fused is not None else self.optimizer.state_dict()
         ck = {'model': self.net.state_dict(), 'optimizer': opt}
         if self.net.value_transform:   # (written only when on: a checkpoint without the option is what it always was)
             ck['value_transform'] = True
+        if self.net.support is not None:
+            ck['support'] = self.net.support
         torch.save(ck, path)
 
     def load_model(self, path):
@@ -116,6 +160,9 @@ class MuZeroAgent(object):
         if saved != self.net.value_transform:
             raise ValueError('the checkpoint %s was saved with value_transform=%s, this agent\'s net has value_transform=%s: the reward '
                              'and value heads would be read in the wrong space' % (path, saved, self.net.value_transform))
+        if ck.get('support') != self.net.support:
+            raise ValueError('the checkpoint %s was saved with support=%s, this agent\'s net has support=%s: the reward and value heads '
+                             'would not have the same bins' % (path, ck.get('support'), self.net.support))
         self.net.load_state_dict(ck['model'])
         if self.fused is not None:
             self.fused.load_optimizer_state_dict(ck['optimizer'])

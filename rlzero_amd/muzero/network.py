@@ -5,7 +5,10 @@ scaled to [0, 1] per sample (appendix G, "Training"), reward and value are scala
 ``value_transform`` / ``inverse_value_transform``: the invertible rescaling of appendix F, h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x
 with eps = 0.001, and its inverse -- the torch form of csrc/rz_mz_value.h (fp64, the same expressions in the same order: the same
 bits).  A ``MuZeroNet(value_transform=True)`` states that its scalar heads are trained on h of their targets and that a search has
-to take their outputs through h^-1 (R2D2's use of h; the paper's categorical support is not built)."""
+to take their outputs through h^-1 (R2D2's use of h).  ``MuZeroNet(value_transform=True, support=S)`` is the paper's form: both heads
+are softmaxes over the 2 S + 1 integer bins -S .. S of h's space (support.py; csrc/rz_mz_support.h), trained by cross-entropy against
+the two-hot encoding of h(target) and read as the expectation -- every method below that returns a reward or a value still returns
+that SCALAR (in h's space), so no caller changes shape; ``dynamics_logits`` / ``prediction_logits`` hand the learner the raw logits."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -49,37 +52,63 @@ def scale_hidden(s):
 
 class MuZeroNet(nn.Module):
 
-    def __init__(self, obs_dim=4, n_actions=2, hidden=64, value_transform=False):
+    def __init__(self, obs_dim=4, n_actions=2, hidden=64, value_transform=False, support=None):
         """``value_transform``: the flag's owner -- the reward and value heads live in h's space (the learner's targets are
-        transformed by the buffers, every search inverts the heads' outputs); the layers and their outputs are the same either way."""
+        transformed by the buffers, every search inverts the heads' outputs); the layers and their outputs are the same either way.
+        ``support``: None (the default: scalar heads, the module and its state_dict as they always were) or the half-width S, 1 .. 31,
+        of the categorical support: ``rew2`` and ``val`` become Linear(hidden, 2 S + 1).  It needs ``value_transform`` (the bins lie
+        in h's space) and raises a ValueError without it."""
         super().__init__()
         self.obs_dim, self.n_actions, self.hidden = obs_dim, n_actions, hidden
         self.value_transform = bool(value_transform)
+        self.support = None
+        if support is not None:
+            from .support import check_support
+            self.support = check_support(support)
+            if not self.value_transform:
+                raise ValueError('support=%d needs value_transform=True: the bins of the categorical heads lie in h\'s space' % self.support)
+        heads = 1 if self.support is None else 2 * self.support + 1
         self.rep1 = nn.Linear(obs_dim, hidden)
         self.rep2 = nn.Linear(hidden, hidden)
         self.dyn1 = nn.Linear(hidden + n_actions, hidden)
         self.dyn2 = nn.Linear(hidden, hidden)
         self.rew1 = nn.Linear(hidden, hidden)
-        self.rew2 = nn.Linear(hidden, 1)
+        self.rew2 = nn.Linear(hidden, heads)
         self.pre1 = nn.Linear(hidden, hidden)
         self.pol = nn.Linear(hidden, n_actions)
-        self.val = nn.Linear(hidden, 1)
+        self.val = nn.Linear(hidden, heads)
 
     def representation(self, obs):
         return scale_hidden(self.rep2(F.relu(self.rep1(obs))))
 
-    def dynamics(self, state, action):
-        """state [b, hidden], action int64 [b] -> (next state, reward [b])."""
+    def _scalar(self, head):
+        """a head's output [b, 1 | B] -> the scalar [b] in h's space: itself, or the expectation over the support"""
+        if self.support is None:
+            return head.squeeze(1)
+        from .support import expectation_torch
+        return expectation_torch(head, self.support)
+
+    def dynamics_logits(self, state, action):
+        """state [b, hidden], action int64 [b] -> (next state, the reward head's raw output [b, 1] or [b, 2 S + 1])."""
         x = torch.cat((state, F.one_hot(action, self.n_actions).to(state.dtype)), dim=1)
         h = F.relu(self.dyn1(x))
         nxt = scale_hidden(self.dyn2(h))
-        reward = self.rew2(F.relu(self.rew1(h))).squeeze(1)
-        return nxt, reward
+        return nxt, self.rew2(F.relu(self.rew1(h)))
+
+    def prediction_logits(self, state):
+        """-> (policy logits [b, A], the value head's raw output [b, 1] or [b, 2 S + 1])."""
+        h = F.relu(self.pre1(state))
+        return self.pol(h), self.val(h)
+
+    def dynamics(self, state, action):
+        """state [b, hidden], action int64 [b] -> (next state, reward [b])."""
+        nxt, reward = self.dynamics_logits(state, action)
+        return nxt, self._scalar(reward)
 
     def prediction(self, state):
         """-> (policy logits [b, A], value [b])."""
-        h = F.relu(self.pre1(state))
-        return self.pol(h), self.val(h).squeeze(1)
+        logits, value = self.prediction_logits(state)
+        return logits, self._scalar(value)
 
     def initial_inference(self, obs):
         s = self.representation(obs)

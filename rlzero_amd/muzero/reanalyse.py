@@ -78,6 +78,13 @@ class MuZeroReanalyser(object):
         self.value_transform = bool(getattr(net, 'value_transform', False))
         if self.value_transform:
             self.tree.set_value_transform(True)
+        self.support = getattr(net, 'support', None)   # categorical heads: the search reads their expectation (MuZeroTree.set_support)
+        if self.support is not None:
+            if net.hidden != 64:
+                self.tree.close()
+                raise ValueError('a net with support=%d cannot be reanalysed here: the search serves categorical heads at hidden size 64 '
+                                 'only (the net has %d)' % (self.support, net.hidden))
+            self.tree.set_support(self.support)
         kw = dict(device=self.device)
         self.hidden = torch.zeros((self.batch, self.tree.slots_per_game, net.hidden), dtype=torch.float32, **kw)
         self.rows = torch.arange(self.batch, **kw)

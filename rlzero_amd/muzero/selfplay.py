@@ -250,6 +250,20 @@ class MuZeroSelfPlay(object):
         self.value_transform = bool(getattr(net, 'value_transform', False))
         if self.value_transform:
             self.tree.set_value_transform(True)
+        # ... and the support of categorical heads (MuZeroNet(support=S)): k_mz_search's CAT instantiations read the expectation; the
+        # step-by-step route gets the same scalar from the net's own methods
+        self.support = getattr(net, 'support', None)
+        if self.support is not None:
+            why = None
+            if net.hidden != 64:
+                why = 'the search serves categorical heads at hidden size 64 only (the net has %d)' % net.hidden
+            elif fused_moves:
+                why = 'fused_moves=True was given: whole moves keep scalar heads'
+            if why is not None:
+                self.tree.close()
+                raise ValueError('a net with support=%d cannot be played here: %s' % (self.support, why))
+            fused_moves = False
+            self.tree.set_support(self.support)
         self.entry_log = None   # a list: receives (environment int64 [n], end step int64 [n]) of the finished episodes, in their order
         self.hidden = torch.zeros((self.n_envs, self.tree.slots_per_game, net.hidden), dtype=torch.float32,
                                   device=self.device)

@@ -23,6 +23,7 @@ class MuZeroTree(object):
         self.n_games, self.n_actions, self.n_sims = int(n_games), int(n_actions), int(n_sims)
         self.discount = float(discount)
         self.value_transform = False   # set_value_transform
+        self.support = None            # set_support
         cfg = _hip.RzMzConfig(_hip.ABI_VERSION, self.n_games, self.n_actions, self.n_sims, self.discount,
                               float(pb_c_base), float(pb_c_init), self.device.index or 0, 0)
         self.handle = ctypes.c_void_p()
@@ -56,6 +57,13 @@ class MuZeroTree(object):
         sd = net.state_dict()
         arrays = [sd[name].detach().to('cpu', self.torch.float32).contiguous().numpy() for name in self.MODEL_PARAMS]
         ptrs = (ctypes.c_void_p * 14)(*[a.ctypes.data for a in arrays])
+        S = getattr(net, 'support', None)
+        if S is not None:   # categorical heads: rew2 / val are [2 S + 1, 64] (the library refuses a hidden size other than 64)
+            B = 2 * int(S) + 1
+            if tuple(arrays[6].shape) != (B, int(net.hidden)) or tuple(arrays[12].shape) != (B, int(net.hidden)):
+                raise ValueError('load_model: a net with support=%d has heads of %d bins, not %s / %s' % (S, B, arrays[6].shape, arrays[12].shape))
+            check(self.lib.rz_mz_load_model_support(self.handle, ptrs, 14, int(net.hidden), int(S)), 'rz_mz_load_model_support')
+            return
         check(self.lib.rz_mz_load_model(self.handle, ptrs, 14, int(net.hidden)), 'rz_mz_load_model')
 
     REPRESENTATION_PARAMS = ('rep1.weight', 'rep1.bias', 'rep2.weight', 'rep2.bias')
@@ -167,6 +175,21 @@ class MuZeroTree(object):
         they are used as they come.  ``expand_backup`` takes what it is given either way."""
         check(self.lib.rz_mz_set_value_transform(self.handle, 1 if on else 0), 'rz_mz_set_value_transform')
         self.value_transform = bool(on)
+        return self
+
+    def set_support(self, support):
+        """Categorical reward and value heads for ``search_fused`` / ``search_gumbel`` (rz_mz_set_support; csrc/rz_mz_support.h):
+        ``support`` = S, 1 .. 31 -- the heads of the loaded model are softmaxes over the 2 S + 1 bins -S .. S of h's space, and the
+        kernel (its CAT instantiations) uses float32(h^-1(expectation)) where it used the scalar heads; None or 0 = scalar heads (the
+        default).  It needs ``set_value_transform(True)`` and a model loaded from a ``MuZeroNet(support=S)``; the library refuses --
+        HipError, nothing launched -- a search whose support is not the loaded model's, and whole moves (``play_env`` /
+        ``play_cartpole``).  ``search_plan(False)`` describes the launch: its LDS holds 45696 bytes more (the heads' weights: 32 KB), so trees leave LDS at smaller shapes."""
+        S = 0 if support is None else int(support)
+        if S != 0:
+            from .support import check_support
+            check_support(S)
+        check(self.lib.rz_mz_set_support(self.handle, S), 'rz_mz_set_support')
+        self.support = S or None
         return self
 
     def _trace(self, n_sims, trace):

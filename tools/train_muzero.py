@@ -27,6 +27,7 @@ if REPO not in sys.path:
 NEEDS_DEVICE_REPLAY = '--reanalyse needs --device-replay: the steps are searched again and refreshed where they are stored, on the GPU'
 ENVIRONMENTS = ('cartpole', 'acrobot')
 EVAL_SEED = 20191119   # the evaluation environments' seed: every evaluation of every run starts from the same states
+SUPPORT_NEEDS_VALUE_TRANSFORM = '--support needs --value-transform: the bins of the categorical heads lie in the transformed space'
 PRIORITIES_NEED_DEVICE_REPLAY = ('--prioritized-replay needs --device-replay: the priorities are kept beside the stored steps, '
                                  'on the GPU')
 
@@ -47,8 +48,11 @@ class MuZeroPipeline(object):
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
                  reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False, env='cartpole',
                  max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None, search='puct', gumbel_considered=4,
-                 gumbel_c_visit=50.0, gumbel_c_scale=1.0):
-        """``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None):
+        """``support`` (needs ``value_transform``): the half-width S of the categorical support of the reward and value heads
+        (``MuZeroNet(support=S)``: 2 S + 1 bins, cross-entropy against two-hot targets in the PyTorch learner, the expectation read
+        inside the search kernel).  Refused with a ValueError together with ``fused_learner`` or ``whole_moves``.  None: scalar heads.
+        ``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
         (or, 'all', every step held), are searched again with the current network and their policy and root value refreshed
@@ -86,7 +90,13 @@ class MuZeroPipeline(object):
                                        ReplayBuffer)
         env_class = {'cartpole': CartPoleBatch, 'acrobot': AcrobotBatch}[env]
         self.value_transform = bool(value_transform)
+        if support is not None and not self.value_transform:
+            raise ValueError(SUPPORT_NEEDS_VALUE_TRANSFORM)
+        if support is not None and whole_moves:
+            raise ValueError('support=%r with whole moves: whole moves keep scalar heads' % (support, ))
         shape = dict(obs_dim=env_class.obs_dim, n_actions=env_class.n_actions, value_transform=self.value_transform)
+        if support is not None:
+            shape['support'] = int(support)
         self.agent = (MuZeroAgent(device=device, fused_learner=True, unroll_steps=unroll_steps, max_batch=batch_size, **shape)
                       if self.fused_learner else MuZeroAgent(device=device, **shape))
         if env == 'cartpole':
@@ -288,6 +298,9 @@ def build_parser():
     ap.add_argument('--value-transform', action='store_true',
                     help='train the scalar value and reward heads on h(x) = sign(x)(sqrt(|x| + 1) - 1) + 0.001 x of their targets and '
                          'invert them inside every search (arXiv:1911.08265v2 appendix F, without the categorical support)')
+    ap.add_argument('--support', type=int, default=None, metavar='S',
+                    help='categorical value and reward heads over the 2 S + 1 bins -S .. S of the transformed space, 1 <= S <= 31 '
+                         '(arXiv:1911.08265v2 appendix F; needs --value-transform; not with --fused-learner or --whole-moves)')
     ap.add_argument('--eval-every', type=int, default=0, metavar='N',
                     help='after every N-th iteration, a greedy evaluation (temperature 0, no root noise) on environments of its own '
                          'from fixed initial states, reported on a line of its own (0 = never)')
@@ -308,12 +321,15 @@ def main(argv=None):
         ap.error(NEEDS_DEVICE_REPLAY)
     if args.prioritized_replay and not args.device_replay:
         ap.error(PRIORITIES_NEED_DEVICE_REPLAY)
+    if args.support is not None and not args.value_transform:
+        ap.error(SUPPORT_NEEDS_VALUE_TRANSFORM)
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
                           updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
                           prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta, fused_learner=args.fused_learner,
                           env=args.env, max_episode_steps=args.max_episode_steps, whole_moves=True if args.whole_moves else None,
                           value_transform=args.value_transform, eval_envs=args.eval_envs, search=args.search,
-                          gumbel_considered=args.gumbel_considered, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
+                          gumbel_considered=args.gumbel_considered, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
+                          support=args.support)
     pipe.run(args.iterations, eval_every=args.eval_every)
     if args.save:
         pipe.agent.save_model(args.save)
