@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 50
+#define RZ_ABI_VERSION 51
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -1347,11 +1347,15 @@ int rz_mz_replay_draw_prioritized(rz_mz_replay *r, uint64_t seed, uint64_t step,
  * rz_mz_learner_grads: d_flat_grad float32 [n_params] = the raw gradient of the loss (before the clip), d_out4 float32 [4] =
  *   (loss, value, reward, policy) means; two launches, nothing is updated.
  * rz_mz_learner_step: the same, then the clip by max_norm and Adam step number `step_count` (1 = the first) on the bound
- *   parameters and moments; the bias corrections are formed on the host in double from step_count. */
+ *   parameters and moments; the bias corrections are formed on the host in double from step_count.
+ * Categorical heads (ABI 51): cfg.support = S in 1 .. 31 serves MuZeroNet(support=S) -- rew2 and val are Linear(64, 2 S + 1), so
+ *   the flat vector is longer (rz_mz_learner_n_params) -- and the value and reward losses are the cross-entropies of the heads'
+ *   logits against the two-hot spread of d_tv / d_tr (taken as they come: h(z) already; clamped to [-S, S]).  0: scalar heads and
+ *   squared errors, as before.  Anything else: RZ_ERR_ARG. */
 enum { RZ_MZ_LEARNER_BAD_ACTION = 1 };
 typedef struct rz_mz_learner_config {
     int32_t abi_version; /* RZ_ABI_VERSION */
-    int32_t obs_dim, n_actions, hidden, unroll_steps, max_batch, device, reserved;
+    int32_t obs_dim, n_actions, hidden, unroll_steps, max_batch, device, support;
     double lr, weight_decay, beta1, beta2, eps, max_norm;
 } rz_mz_learner_config;
 typedef struct rz_mz_learner rz_mz_learner;

@@ -8,7 +8,7 @@ import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64,
                     c_void_p)
 
-ABI_VERSION = 50
+ABI_VERSION = 51
 BOARD_WORDS = 4
 MAX_BOARD_SIZE = 16
 MAX_IN_FLIGHT = 16
@@ -47,9 +47,10 @@ class RzMzConfig(Structure):
 
 
 class RzMzLearnerConfig(Structure):
-    """rz_mz_learner_config: the geometry and the optimizer's constants of the fused MuZero learner (ABI 40)."""
+    """rz_mz_learner_config: the geometry and the optimizer's constants of the fused MuZero learner (ABI 40); ``support``: the
+    half-width S of categorical reward and value heads, 0 = scalar heads (ABI 51)."""
     _fields_ = [('abi_version', c_int32), ('obs_dim', c_int32), ('n_actions', c_int32), ('hidden', c_int32), ('unroll_steps', c_int32),
-                ('max_batch', c_int32), ('device', c_int32), ('reserved', c_int32), ('lr', c_double), ('weight_decay', c_double),
+                ('max_batch', c_int32), ('device', c_int32), ('support', c_int32), ('lr', c_double), ('weight_decay', c_double),
                 ('beta1', c_double), ('beta2', c_double), ('eps', c_double), ('max_norm', c_double)]
 
 

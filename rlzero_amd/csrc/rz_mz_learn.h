@@ -8,6 +8,8 @@
 //   loss_row = 0.25 * sum_k (v_k - tv_k)^2 + sum_{k>=1} (r_k - tr_k)^2 - sum_k mask_k * sum_a tp_ka log_softmax(logits_k)_a
 //   loss = mean(loss_row * weight_row); the GRADIENT of the terms of steps 1 .. K is scaled by 1 / K, the gradient into the state is
 //   halved after every recurrent step (scale_gradient), the values are not.
+// With a support S > 0 (MuZeroNet(support=S): rew2 and val are Linear(64, B), B = 2 S + 1 bins) the two squared errors give way to
+//   -sum_b two_hot(tv_k)_b log_softmax(val logits_k)_b and the same of the reward (MuZeroAgent._learn_support); all else stays.
 #pragma once
 
 #include <math.h>
@@ -24,28 +26,31 @@
 #define RZ_MZL_MAX_ACTIONS 8    /* A */
 #define RZ_MZL_MAX_UNROLL 16    /* K */
 #define RZ_MZL_TENSORS 18
+#define RZ_MZL_MAX_SUPPORT 31   /* S: B = 2 S + 1 <= 63 bins, one per lane of a wave */
 
 namespace rzmzl {
 
 constexpr int kH = RZ_MZL_HIDDEN;
 enum Tensor { REP1_W, REP1_B, REP2_W, REP2_B, DYN1_W, DYN1_B, DYN2_W, DYN2_B, REW1_W, REW1_B, REW2_W, REW2_B, PRE1_W, PRE1_B, POL_W, POL_B, VAL_W, VAL_B };
 
-RZL_FN int tensor_size(int t, int D, int A) {
+// S = 0: scalar reward and value heads; S > 0: B = 2 S + 1 bins each
+RZL_FN int tensor_size(int t, int D, int A, int S = 0) {
+    const int B = S > 0 ? 2 * S + 1 : 1;
     switch (t) {
         case REP1_W: return kH * D;
         case DYN1_W: return kH * (kH + A);
         case REP2_W: case DYN2_W: case REW1_W: case PRE1_W: return kH * kH;
-        case REW2_W: case VAL_W: return kH;
+        case REW2_W: case VAL_W: return B * kH;
         case POL_W: return A * kH;
         case POL_B: return A;
-        case REW2_B: case VAL_B: return 1;
+        case REW2_B: case VAL_B: return B;
         default: return kH;   // the biases of the 64-wide layers
     }
 }
 // off[t] = where tensor t starts in the flat vector, off[18] = the number of parameters
-RZL_FN void tensor_offsets(int D, int A, int *off) {
+RZL_FN void tensor_offsets(int D, int A, int *off, int S = 0) {
     int at = 0;
-    for (int t = 0; t < RZ_MZL_TENSORS; ++t) off[t] = at, at += tensor_size(t, D, A);
+    for (int t = 0; t < RZ_MZL_TENSORS; ++t) off[t] = at, at += tensor_size(t, D, A, S);
     off[RZ_MZL_TENSORS] = at;
 }
 
@@ -57,6 +62,8 @@ RZL_FN float mzl_sqrt(float x) { return sqrtf(x); }
 RZL_FN double mzl_sqrt(double x) { return sqrt(x); }
 RZL_FN float mzl_fma(float a, float b, float c) { return fmaf(a, b, c); }
 RZL_FN double mzl_fma(double a, double b, double c) { return fma(a, b, c); }
+RZL_FN float mzl_floor(float x) { return floorf(x); }
+RZL_FN double mzl_floor(double x) { return floor(x); }
 
 // ---- scale_hidden: y_i = (s_i - lo) / den, den = max(hi - lo, 1e-5); lo = s[imin], hi = s[imax], ties to the lowest index.
 // `free`: the clamp is inactive and den carries a gradient to both ends.
@@ -115,6 +122,46 @@ RZL_FN T policy_loss_grad(const T *logits, const T *tp, int A, T mask, T scale, 
     return -dot * mask;
 }
 
+// ---- the categorical heads (support S, B = 2 S + 1 bins): the target spread over two bins as support.py's two_hot_torch spreads it,
+// in T.  y is clamped to [-S, S] (a NaN becomes -S: it never indexes outside the row), lo = floor(y); w_hi = y - lo belongs to bin
+// *lo_bin + 1 -- only where it is positive, so never past the last bin --, w_lo = 1 - w_hi to bin *lo_bin = lo + S.
+template <typename T>
+RZL_FN void two_hot_split(T y, int S, int *lo_bin, T *w_lo, T *w_hi) {
+    const T s = (T)S;
+    y = y > -s ? y : -s;
+    y = y < s ? y : s;
+    const T lo = mzl_floor(y);
+    *w_hi = y - lo;
+    *w_lo = (T)1 - *w_hi;
+    *lo_bin = (int)lo + S;
+}
+template <typename T>
+RZL_FN T two_hot_bin(int b, int lo_bin, T w_lo, T w_hi) {
+    return b == lo_bin ? w_lo : (b == lo_bin + 1 && w_hi > (T)0) ? w_hi : (T)0;
+}
+// one bin of the cross-entropy's gradient, ls = log_softmax(x)_b, tsum = w_lo + w_hi: policy_loss_grad's form
+template <typename T>
+RZL_FN T ce_bin_grad(T ls, T tsum, T t, T scale) { return (mzl_exp(ls) * tsum - t) * scale; }
+// -(two_hot(target) . log_softmax(logits)) -> the loss; dlogits_b = (softmax_b (w_lo + w_hi) - t_b) * scale
+template <typename T>
+RZL_FN T ce_two_hot_loss_grad(const T *logits, int B, int S, T target, T scale, T *dlogits) {
+    int lo_bin;
+    T w_lo, w_hi;
+    two_hot_split(target, S, &lo_bin, &w_lo, &w_hi);
+    T m = logits[0];
+    for (int b = 1; b < B; ++b) m = logits[b] > m ? logits[b] : m;
+    T z = (T)0;
+    for (int b = 0; b < B; ++b) z += mzl_exp(logits[b] - m);
+    const T lse = mzl_log(z);
+    T dot = (T)0;
+    for (int b = 0; b < B; ++b) {
+        const T ls = logits[b] - m - lse, t = two_hot_bin(b, lo_bin, w_lo, w_hi);
+        dot += t * ls;
+        dlogits[b] = ce_bin_grad(ls, w_lo + w_hi, t, scale);
+    }
+    return -dot;
+}
+
 // ---- a compensated sum (Kahan): the loss means are compared at the last bit, so their sums carry their rounding error along
 template <typename T>
 RZL_FN void kahan_add(T *sum, T *comp, T x) {
@@ -151,7 +198,7 @@ RZL_FN void adam_elem(T g, const AdamStep<T> &h, T *p, T *m, T *v) {
 // ---- the whole-row reference (host): one batch row through the K + 1 steps and back.
 // params[18]: the tensors; actions int64 [K]; tv, tr, mask [K + 1]; tp [K + 1][A]; `weight` the row's importance weight, n the batch size.
 // grad (flat, off[18] long) and losses[4] = sums of (weight * row loss, value, reward, policy) are ACCUMULATED.  An action outside
-// 0 .. A-1 sets *bad and is read as 0.
+// 0 .. A-1 sets *bad and is read as 0.  S > 0: params[REW2_*] / params[VAL_*] are the B-wide heads, tv / tr are spread by two_hot_split.
 template <typename T>
 inline void mzl_linear(const T *W, const T *b, int n_out, int n_in, int ld, const T *x, T *y) {
     for (int j = 0; j < n_out; ++j) {
@@ -199,14 +246,16 @@ inline void mzl_scale_row_bwd(const RowScale<T> &r, const T *y, const T *dy, T *
 
 template <typename T>
 inline void mzl_row_grad(int D, int A, int K, const T *const *params, const T *obs, const long long *actions, const T *tv, const T *tr,
-                         const T *tp, const T *mask, T weight, long long n, T *grad, T *losses, int *bad) {
-    constexpr int S = RZ_MZL_MAX_UNROLL + 1;
+                         const T *tp, const T *mask, T weight, long long n, T *grad, T *losses, int *bad, int S = 0) {
+    constexpr int NS = RZ_MZL_MAX_UNROLL + 1, NB = 2 * RZ_MZL_MAX_SUPPORT + 1;
+    const int B = S > 0 ? 2 * S + 1 : 1;   // outputs of the value and of the reward head
     int off[RZ_MZL_TENSORS + 1];
-    tensor_offsets(D, A, off);
+    tensor_offsets(D, A, off, S);
     const int ld1 = kH + A;
-    static thread_local T h1[kH], sraw[kH], s[S][kH], p1[S][kH], d1[S][kH], r1[S][kH], x[S][kH + RZ_MZL_MAX_ACTIONS];
-    RowScale<T> sc[S];
-    T dlogits[S][RZ_MZL_MAX_ACTIONS], dvalue[S], dreward[S];
+    static thread_local T h1[kH], sraw[kH], s[NS][kH], p1[NS][kH], d1[NS][kH], r1[NS][kH], x[NS][kH + RZ_MZL_MAX_ACTIONS];
+    static thread_local T dvalue[NS][NB], dreward[NS][NB];
+    RowScale<T> sc[NS];
+    T dlogits[NS][RZ_MZL_MAX_ACTIONS];
     const T rs = weight / (T)n;
     T lv = (T)0, lr = (T)0, lp = (T)0;
     // ---- forward
@@ -215,7 +264,7 @@ inline void mzl_row_grad(int D, int A, int K, const T *const *params, const T *o
             mzl_linear(params[REP1_W], params[REP1_B], kH, D, D, obs, h1);
             for (int i = 0; i < kH; ++i) h1[i] = h1[i] > (T)0 ? h1[i] : (T)0;
             mzl_linear(params[REP2_W], params[REP2_B], kH, kH, kH, h1, sraw);
-            dreward[0] = (T)0;
+            for (int b = 0; b < B; ++b) dreward[0][b] = (T)0;
         } else {
             long long a = actions[k - 1];
             if (a < 0 || a >= A) *bad = 1, a = 0;
@@ -226,18 +275,20 @@ inline void mzl_row_grad(int D, int A, int K, const T *const *params, const T *o
             mzl_linear(params[DYN2_W], params[DYN2_B], kH, kH, kH, d1[k], sraw);
             mzl_linear(params[REW1_W], params[REW1_B], kH, kH, kH, d1[k], r1[k]);
             for (int i = 0; i < kH; ++i) r1[k][i] = r1[k][i] > (T)0 ? r1[k][i] : (T)0;
-            T reward;
-            mzl_linear(params[REW2_W], params[REW2_B], 1, kH, kH, r1[k], &reward);
-            lr += sq_loss_grad(reward, tr[k], step_grad_scale<T>(k, K) * rs, &dreward[k]);
+            T reward[NB];
+            mzl_linear(params[REW2_W], params[REW2_B], B, kH, kH, r1[k], reward);
+            if (S > 0) lr += ce_two_hot_loss_grad(reward, B, S, tr[k], step_grad_scale<T>(k, K) * rs, dreward[k]);
+            else lr += sq_loss_grad(reward[0], tr[k], step_grad_scale<T>(k, K) * rs, &dreward[k][0]);
         }
         sc[k] = mzl_scale_row(sraw, s[k]);
         mzl_linear(params[PRE1_W], params[PRE1_B], kH, kH, kH, s[k], p1[k]);
         for (int i = 0; i < kH; ++i) p1[k][i] = p1[k][i] > (T)0 ? p1[k][i] : (T)0;
-        T logits[RZ_MZL_MAX_ACTIONS], value;
+        T logits[RZ_MZL_MAX_ACTIONS], value[NB];
         mzl_linear(params[POL_W], params[POL_B], A, kH, kH, p1[k], logits);
-        mzl_linear(params[VAL_W], params[VAL_B], 1, kH, kH, p1[k], &value);
+        mzl_linear(params[VAL_W], params[VAL_B], B, kH, kH, p1[k], value);
         const T g = step_grad_scale<T>(k, K) * rs;
-        lv += sq_loss_grad(value, tv[k], (T)0.25 * g, &dvalue[k]);
+        if (S > 0) lv += ce_two_hot_loss_grad(value, B, S, tv[k], (T)0.25 * g, dvalue[k]);
+        else lv += sq_loss_grad(value[0], tv[k], (T)0.25 * g, &dvalue[k][0]);
         lp += policy_loss_grad(logits, tp + k * A, A, mask[k], g, dlogits[k]);
     }
     losses[0] += ((T)0.25 * lv + lr + lp) * weight;
@@ -248,7 +299,7 @@ inline void mzl_row_grad(int D, int A, int K, const T *const *params, const T *o
     for (int k = K; k >= 0; --k) {
         for (int i = 0; i < kH; ++i) dp1[i] = (T)0;
         mzl_linear_bwd(params[POL_W], A, kH, kH, p1[k], dlogits[k], grad + off[POL_W], grad + off[POL_B], dp1);
-        mzl_linear_bwd(params[VAL_W], 1, kH, kH, p1[k], &dvalue[k], grad + off[VAL_W], grad + off[VAL_B], dp1);
+        mzl_linear_bwd(params[VAL_W], B, kH, kH, p1[k], dvalue[k], grad + off[VAL_W], grad + off[VAL_B], dp1);
         for (int i = 0; i < kH; ++i) dp1[i] = p1[k][i] > (T)0 ? dp1[i] : (T)0;
         for (int i = 0; i < kH; ++i) dy[i] = ds[i];
         mzl_linear_bwd(params[PRE1_W], kH, kH, kH, s[k], dp1, grad + off[PRE1_W], grad + off[PRE1_B], dy);
@@ -261,7 +312,7 @@ inline void mzl_row_grad(int D, int A, int K, const T *const *params, const T *o
             break;
         }
         for (int i = 0; i < kH; ++i) dr1[i] = (T)0, dd1[i] = (T)0;
-        mzl_linear_bwd(params[REW2_W], 1, kH, kH, r1[k], &dreward[k], grad + off[REW2_W], grad + off[REW2_B], dr1);
+        mzl_linear_bwd(params[REW2_W], B, kH, kH, r1[k], dreward[k], grad + off[REW2_W], grad + off[REW2_B], dr1);
         for (int i = 0; i < kH; ++i) dr1[i] = r1[k][i] > (T)0 ? dr1[i] : (T)0;
         mzl_linear_bwd(params[REW1_W], kH, kH, kH, d1[k], dr1, grad + off[REW1_W], grad + off[REW1_B], dd1);
         mzl_linear_bwd(params[DYN2_W], kH, kH, kH, d1[k], dsraw, grad + off[DYN2_W], grad + off[DYN2_B], dd1);

@@ -1,4 +1,5 @@
-// rz_mz_learn.hip -- the fused MuZero learner (include/rlzero_hip.h: rz_mz_learner_*, ABI 40; the arithmetic: rz_mz_learn.h).
+// rz_mz_learn.hip -- the fused MuZero learner (include/rlzero_hip.h: rz_mz_learner_*, ABI 40; categorical heads: ABI 51; the arithmetic:
+// rz_mz_learn.h).
 //
 // One update is three launches on the caller's stream:
 //   k_mzl_grad    a workgroup takes a tile of R batch rows through the K + 1 unroll steps and back.  The tile's activations of every
@@ -9,8 +10,12 @@
 //                 Plain fmaf on the vector unit: the products are R x 64 x 64 with R <= 4 -- a quarter of an MFMA tile's rows --
 //                 and the unroll is a chain of ~90 dependent phases, so the time is barriers and latency, not the multiply rate.
 //                 It writes the workgroup's partial gradient and partial loss sums.
+//                 k_mzl_grad<R, true> (cfg.support = S > 0: reward and value heads of B = 2 S + 1 bins): lane j owns bin j of both
+//                 heads, the wave that holds a row forms its log-softmax and two-hot cross-entropy with lane exchanges, the B
+//                 gradients of each head wait in LDS ([R][K + 1][2][64]) for the transposed products of the backward pass and, after
+//                 it, for the two B x 64 weight gradients -- formed when the five 64 x 64 accumulators have left the registers.
 //   k_mzl_reduce  element p of the flat gradient = the partials summed workgroup 0, 1, 2, ..; every block leaves the sum of its
-//                 squares (a fixed tree); block 0 forms the four loss means.
+//                 squares (a fixed tree); block 0 forms the four loss means (categorical heads: from float pairs, in double).
 //   k_mzl_adam    every thread sums the blocks' squares in order (the norm, the clip coefficient), then updates its element of
 //                 the parameters -- in torch's own storage, through the table of 18 pointers -- and of both moments.
 // No atomics on floats, no grid-wide barrier: the same inputs give the same bits.
@@ -71,16 +76,28 @@ int ml_grads(rz_mz_learner *l, const float *d_obs, const int64_t *d_actions, con
     const int R = l->rows, n_wg = (int)((n + R - 1) / R);
     const int D = l->cfg.obs_dim, A = l->cfg.n_actions, K = l->cfg.unroll_steps;
     if (n_wg > l->max_wg) return rz_fail(RZ_ERR_INTERNAL, "more tiles than the partials hold");
+    const int S = l->cfg.support;
     const dim3 grid((unsigned)n_wg), block(kThreads);
-    if (R == 4)
-        hipLaunchKernelGGL(k_mzl_grad<4>, grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err);
+    // (the scalar instantiations are named first: they stay first in the code object)
+    if (S == 0 && R == 4)
+        hipLaunchKernelGGL((k_mzl_grad<4, false>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, 0, nullptr);
+    else if (S == 0 && R == 2)
+        hipLaunchKernelGGL((k_mzl_grad<2, false>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, 0, nullptr);
+    else if (S == 0)
+        hipLaunchKernelGGL((k_mzl_grad<1, false>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, 0, nullptr);
+    else if (R == 4)
+        hipLaunchKernelGGL((k_mzl_grad<4, true>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, S, l->loss_partial + 4LL * l->max_wg);
     else if (R == 2)
-        hipLaunchKernelGGL(k_mzl_grad<2>, grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err);
+        hipLaunchKernelGGL((k_mzl_grad<2, true>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, S, l->loss_partial + 4LL * l->max_wg);
     else
-        hipLaunchKernelGGL(k_mzl_grad<1>, grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err);
+        hipLaunchKernelGGL((k_mzl_grad<1, true>), grid, block, l->lds_bytes, s, W, B, D, A, K, l->n_params, l->partial, l->loss_partial, l->err, S, l->loss_partial + 4LL * l->max_wg);
     RZ_TRY(rz_launched("k_mzl_grad"));
-    hipLaunchKernelGGL(k_mzl_reduce, dim3((unsigned)l->n_blocks), block, 0, s, l->partial, l->loss_partial, n_wg, l->n_params, (long long)n, d_flat_grad,
-                       l->sq, d_out4);
+    if (S == 0)
+        hipLaunchKernelGGL(k_mzl_reduce<false>, dim3((unsigned)l->n_blocks), block, 0, s, l->partial, l->loss_partial, n_wg, l->n_params, (long long)n,
+                           d_flat_grad, l->sq, d_out4, nullptr);
+    else
+        hipLaunchKernelGGL(k_mzl_reduce<true>, dim3((unsigned)l->n_blocks), block, 0, s, l->partial, l->loss_partial, n_wg, l->n_params, (long long)n,
+                           d_flat_grad, l->sq, d_out4, l->loss_partial + 4LL * l->max_wg);
     return rz_launched("k_mzl_reduce");
 }
 
@@ -97,6 +114,8 @@ int rz_mz_learner_create(const rz_mz_learner_config *cfg, rz_mz_learner **out) {
     if (cfg->n_actions < 1 || cfg->n_actions > RZ_MZL_MAX_ACTIONS) return rz_fail(RZ_ERR_ARG, "n_actions outside 1 .. 8");
     if (cfg->unroll_steps < 1 || cfg->unroll_steps > RZ_MZL_MAX_UNROLL) return rz_fail(RZ_ERR_ARG, "unroll_steps outside 1 .. 16");
     if (cfg->max_batch < 1 || cfg->max_batch > (1 << 16)) return rz_fail(RZ_ERR_ARG, "max_batch outside 1 .. 65536");
+    if (cfg->support < 0 || cfg->support > RZ_MZL_MAX_SUPPORT)
+        return rz_fail(RZ_ERR_ARG, "support %d outside 0 (scalar heads) .. %d (2 S + 1 <= 63 bins: one per lane of a wave)", cfg->support, RZ_MZL_MAX_SUPPORT);
     if (!(cfg->lr > 0.0) || !(cfg->weight_decay >= 0.0) || !(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0) || !(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0) ||
         !(cfg->eps > 0.0) || !(cfg->max_norm > 0.0))
         return rz_fail(RZ_ERR_ARG, "lr, eps, max_norm > 0, weight_decay >= 0 and betas in [0, 1) are required");
@@ -105,19 +124,19 @@ int rz_mz_learner_create(const rz_mz_learner_config *cfg, rz_mz_learner **out) {
     if (!l) return rz_fail(RZ_ERR_OOM, "host allocation failed");
     l->cfg = *cfg;
     l->device = cfg->device;
-    tensor_offsets(cfg->obs_dim, cfg->n_actions, l->table.off);
+    tensor_offsets(cfg->obs_dim, cfg->n_actions, l->table.off, cfg->support);
     l->n_params = l->table.off[RZ_MZL_TENSORS];
     l->n_blocks = (l->n_params + kThreads - 1) / kThreads;
     l->rows = kMaxRows;
-    while (l->rows > 1 && (size_t)mzl_lds_floats(l->rows, cfg->unroll_steps) * sizeof(float) > (size_t)kLdsBytes) l->rows /= 2;
-    l->lds_bytes = (size_t)mzl_lds_floats(l->rows, cfg->unroll_steps) * sizeof(float);
+    while (l->rows > 1 && (size_t)mzl_lds_floats(l->rows, cfg->unroll_steps, cfg->support) * sizeof(float) > (size_t)kLdsBytes) l->rows /= 2;
+    l->lds_bytes = (size_t)mzl_lds_floats(l->rows, cfg->unroll_steps, cfg->support) * sizeof(float);
     l->max_wg = (cfg->max_batch + l->rows - 1) / l->rows;
     if (l->lds_bytes > (size_t)kLdsBytes) {
         delete l;
         return rz_fail(RZ_ERR_INTERNAL, "one row's activations exceed the LDS budget");
     }
     DevPool &pool = l->pool;
-    const bool ok = pool.alloc(&l->partial, (long long)l->max_wg * l->n_params) == RZ_OK && pool.alloc(&l->loss_partial, 4LL * l->max_wg) == RZ_OK &&
+    const bool ok = pool.alloc(&l->partial, (long long)l->max_wg * l->n_params) == RZ_OK && pool.alloc(&l->loss_partial, 8LL * l->max_wg) == RZ_OK &&
                     pool.alloc(&l->grad, l->n_params) == RZ_OK && pool.alloc(&l->sq, l->n_blocks) == RZ_OK && pool.alloc(&l->err, 2) == RZ_OK;
     if (!ok) {
         delete l;

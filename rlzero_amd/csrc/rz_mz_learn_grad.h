@@ -1,6 +1,10 @@
 // rz_mz_learn_grad.h -- the gradient kernel of rz_mz_learn.hip: the records every kernel of the learner takes (MzlWeights, MzlTable,
 // MzlBatch), the LDS a tile needs (mzl_act_stride, mzl_lds_floats: the host sizes the launch with them), the matrix-vector pieces
 // (gemv_fwd, gemv_bwd, outer_acc, col_sum, store16) and k_mzl_grad, a tile of R batch rows through the K + 1 unroll steps and back.
+// k_mzl_grad<R, true> serves a net with categorical reward and value heads (support S, B = 2 S + 1 <= 63 bins): lane j owns bin j of
+// both heads, a wave forms the log-softmax and the two-hot cross-entropy of its rows with lane exchanges (ce_wave), the B gradients of
+// each head wait in LDS for the backward pass (gemv_bwd_n: the transposed product over B rows only) and for the heads' weight
+// gradients, which are formed from LDS once the five 64 x 64 accumulators have left the registers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,10 +42,10 @@ struct MzlBatch {
     long long n;
 };
 
-// floats of LDS a tile of R rows takes
+// floats of LDS a tile of R rows takes; with a support S > 0 the heads' gradients [R][K + 1][2][64] lie behind the rest
 __host__ __device__ inline int mzl_act_stride(int K) { return (3 + 4 * K) * kH; }
-__host__ __device__ inline int mzl_lds_floats(int R, int K) {
-    return R * (mzl_act_stride(K) + (K + 1) * kScal + 4 * kH + RZ_MZL_MAX_OBS + RZ_MZL_MAX_UNROLL) + 4 * kMaxRows;
+__host__ __device__ inline int mzl_lds_floats(int R, int K, int S = 0) {
+    return R * (mzl_act_stride(K) + (K + 1) * kScal + 4 * kH + RZ_MZL_MAX_OBS + RZ_MZL_MAX_UNROLL) + 4 * kMaxRows + (S > 0 ? R * (K + 1) * 2 * kH : 0);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -98,6 +102,42 @@ __device__ __forceinline__ void gemv_bwd(const float *__restrict__ W, int ld, in
     }
 }
 
+// gemv_bwd over the first n rows of W only (a head of n = B < 64 outputs ends there); dy: LDS, row stride dys, zero from n on
+template <int R>
+__device__ __forceinline__ void gemv_bwd_n(const float *__restrict__ W, int ld, int i, const float *dy, int dys, int n, int q, float *y) {
+    constexpr int RPW = (R + kWaves - 1) / kWaves;
+    for (int j = 0; j < n; j += 4) {
+        const float w0 = W[j * ld + i], w1 = j + 1 < n ? W[(j + 1) * ld + i] : 0.0f, w2 = j + 2 < n ? W[(j + 2) * ld + i] : 0.0f,
+                    w3 = j + 3 < n ? W[(j + 3) * ld + i] : 0.0f;
+#pragma unroll
+        for (int m = 0; m < RPW; ++m) {
+            const int r = q + kWaves * m;
+            if (r < R) {
+                const float4 v = *(const float4 *)(dy + r * dys + j);
+                y[m] = fmaf(w0, v.x, y[m]), y[m] = fmaf(w1, v.y, y[m]), y[m] = fmaf(w2, v.z, y[m]), y[m] = fmaf(w3, v.w, y[m]);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+// ce_two_hot_loss_grad across a wave: lane j holds logit x of bin j (-inf from bin Bn on) -> the row's loss in every lane, *dx = bin j's gradient
+__device__ __forceinline__ float ce_wave(float x, int j, int Bn, int S, float target, float scale, float *dx) {
+    const float m = wave_max(x);
+    const float lse = mzl_log(wave_sum(j < Bn ? mzl_exp(x - m) : 0.0f));
+    const float ls = x - m - lse;
+    int lo_bin;
+    float w_lo, w_hi;
+    two_hot_split(target, S, &lo_bin, &w_lo, &w_hi);
+    const float t = two_hot_bin(j, lo_bin, w_lo, w_hi);
+    *dx = j < Bn ? ce_bin_grad(ls, w_lo + w_hi, t, scale) : 0.0f;
+    return -wave_sum(j < Bn ? t * ls : 0.0f);
+}
+
 // acc[c] += sum_r dy[r][j] x[r][16 q + c]: the thread's 16 elements of a 64 x 64 weight gradient, every row of the tile in order
 template <int R>
 __device__ __forceinline__ void outer_acc(float *acc, const float *dy, const float *x, int xs, int j, int q) {
@@ -123,9 +163,12 @@ __device__ __forceinline__ void store16(float *dst, const float *acc) {
     for (int c = 0; c < 16; ++c) dst[c] = acc[c];
 }
 
-template <int R>
+// CAT: categorical reward and value heads over Bn = 2 S + 1 bins; otherwise S and loss_lo are not read.  The cross-entropies are tens
+// where the squared errors of scaled targets are fractions, and a float32 partial sum of them is rounded by more than the loss mean's
+// last bit: with CAT the loss sums are kept in double, and a workgroup's four leave as float pairs (loss_partial + loss_lo).
+template <int R, bool CAT>
 __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B, int D, int A, int K, int n_params, float *__restrict__ partial,
-                                                       float *__restrict__ loss_partial, int32_t *__restrict__ err) {
+                                                       float *__restrict__ loss_partial, int32_t *__restrict__ err, int S, float *__restrict__ loss_lo) {
     constexpr int RPW = (R + kWaves - 1) / kWaves;
     extern __shared__ float lds[];
     const int AS = mzl_act_stride(K);
@@ -136,12 +179,14 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
     float *obsL = DS + R * kH;                      // [R][16]
     int *actL = (int *)(obsL + R * RZ_MZL_MAX_OBS); // [R][16]
     float *lossL = (float *)(actL + R * RZ_MZL_MAX_UNROLL);   // [4][kMaxRows]
+    float *HG = lossL + 4 * kMaxRows;               // CAT: [R][K + 1][2][64] d value logits | d reward logits, zero from bin Bn on
+    const int HS = (K + 1) * 2 * kH, Bn = 2 * S + 1;
 
     const int t = threadIdx.x, j = t & 63, q = t >> 6;
     const long long row0 = (long long)blockIdx.x * R;
     const int ld1 = kH + A;
     int off[RZ_MZL_TENSORS + 1];
-    tensor_offsets(D, A, off);
+    tensor_offsets(D, A, off, CAT ? S : 0);
 
     // ---- the tile's observations and actions; rows past n: zeros
     for (int e = t; e < R * RZ_MZL_MAX_OBS; e += kThreads) {
@@ -165,6 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
     const bool my_row = t < R && row0 + t < B.n;
     const float rs = my_row ? (B.weights ? B.weights[row0 + t] : 1.0f) / (float)B.n : 0.0f;
     float lv = 0.0f, lr = 0.0f, lp = 0.0f, c_lv = 0.0f, c_lr = 0.0f, c_lp = 0.0f;   // (compensated: kahan_add)
+    double w_lv = 0.0, w_lr = 0.0, w_lp = 0.0;                                       // CAT: the same three sums
     __syncthreads();
 
     // ================================================================ forward
@@ -236,8 +282,48 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
         for (int m = 0; m < RPW; ++m)
             if (q + kWaves * m < R) p1[(q + kWaves * m) * AS + j] = fmaxf(y[m], 0.0f);
         __syncthreads();
-        // the heads: lane a < A a logit, lane A the value, lane A + 1 the reward
-        if (j < A + 2 && (j < A + 1 || k > 0)) {
+        if constexpr (CAT) {
+            // the heads: lane a < A a policy logit; lane b < Bn bin b of the value and (from step 1 on) of the reward head, whose
+            // rows the wave takes through the log-softmax and the two-hot cross-entropy at once
+            if (j < A) {
+                const float *w = Wt.p[POL_W] + j * kH;
+#pragma unroll
+                for (int m = 0; m < RPW; ++m) {
+                    const int r = q + kWaves * m;
+                    if (r < R) {
+                        float acc = Wt.p[POL_B][j];
+                        for (int i = 0; i < kH; ++i) acc = fmaf(w[i], p1[r * AS + i], acc);
+                        scal[(r * (K + 1) + k) * kScal + S_LOGITS + j] = acc;
+                    }
+                }
+            }
+            float hv[RPW], hr[RPW];
+#pragma unroll
+            for (int m = 0; m < RPW; ++m) hv[m] = hr[m] = -INFINITY;
+            if (j < Bn) {   // (val.weight and rew2.weight end after row Bn - 1)
+#pragma unroll
+                for (int m = 0; m < RPW; ++m) hv[m] = Wt.p[VAL_B][j], hr[m] = Wt.p[REW2_B][j];
+                gemv_fwd<R, true>(Wt.p[VAL_W], kH, kH, p1, AS, q, j, hv);
+                if (k > 0) gemv_fwd<R, true>(Wt.p[REW2_W], kH, kH, base + 2 * kH, AS, q, j, hr);
+            }
+#pragma unroll
+            for (int m = 0; m < RPW; ++m) {
+                const int r = q + kWaves * m;
+                if (r < R) {
+                    const bool live = row0 + r < B.n;
+                    const long long at = (row0 + r) * (K + 1) + k;
+                    const float g = step_grad_scale<float>(k, K) * (live ? (B.weights ? B.weights[row0 + r] : 1.0f) / (float)B.n : 0.0f);
+                    float *hg = HG + r * HS + k * 2 * kH, dv, dr = 0.0f, e_r = 0.0f;
+                    const float e_v = ce_wave(hv[m], j, Bn, S, live ? B.tv[at] : 0.0f, 0.25f * g, &dv);
+                    if (k > 0) e_r = ce_wave(hr[m], j, Bn, S, live ? B.tr[at] : 0.0f, g, &dr);
+                    hg[j] = dv, hg[kH + j] = dr;
+                    if (j == 0) {   // the row's two losses, for the thread that keeps its sums
+                        float *rec = scal + (r * (K + 1) + k) * kScal;
+                        rec[S_VALUE] = e_v, rec[S_REWARD] = e_r;
+                    }
+                }
+            }
+        } else if (j < A + 2 && (j < A + 1 || k > 0)) {   // the heads: lane a < A a logit, lane A the value, lane A + 1 the reward
             const float *w = j < A ? Wt.p[POL_W] + j * kH : j == A ? Wt.p[VAL_W] : Wt.p[REW2_W];
             const float b = j < A ? Wt.p[POL_B][j] : j == A ? Wt.p[VAL_B][0] : Wt.p[REW2_B][0];
             const float *x = j <= A ? p1 : base + 2 * kH;
@@ -263,13 +349,18 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
                 lg[a] = a < A ? rec[S_LOGITS + a] : 0.0f;
                 tpr[a] = (my_row && a < A) ? B.tp[at * A + a] : 0.0f;
             }
-            float dv, dr = 0.0f;
-            const float e_v = sq_loss_grad(rec[S_VALUE], my_row ? B.tv[at] : 0.0f, 0.25f * g, &dv);
+            float dv, dr = 0.0f, e_v, e_r = 0.0f;
+            if constexpr (CAT) e_v = rec[S_VALUE], e_r = rec[S_REWARD];   // (the row's wave formed them)
+            else e_v = sq_loss_grad(rec[S_VALUE], my_row ? B.tv[at] : 0.0f, 0.25f * g, &dv);
             const float e_p = policy_loss_grad(lg, tpr, A, my_row ? B.mask[at] : 0.0f, g, dl);
-            float e_r = 0.0f;
-            if (k > 0) e_r = sq_loss_grad(rec[S_REWARD], my_row ? B.tr[at] : 0.0f, g, &dr);
-            if (my_row) kahan_add(&lv, &c_lv, e_v), kahan_add(&lr, &c_lr, e_r), kahan_add(&lp, &c_lp, e_p);
-            rec[S_VALUE] = dv, rec[S_REWARD] = dr;
+            if constexpr (!CAT)
+                if (k > 0) e_r = sq_loss_grad(rec[S_REWARD], my_row ? B.tr[at] : 0.0f, g, &dr);
+            if constexpr (CAT) {
+                if (my_row) w_lv += (double)e_v, w_lr += (double)e_r, w_lp += (double)e_p;
+            } else {
+                if (my_row) kahan_add(&lv, &c_lv, e_v), kahan_add(&lr, &c_lr, e_r), kahan_add(&lp, &c_lp, e_p);
+                rec[S_VALUE] = dv, rec[S_REWARD] = dr;
+            }
 #pragma unroll
             for (int a = 0; a < RZ_MZL_MAX_ACTIONS; ++a)
                 if (a < A) rec[S_LOGITS + a] = dl[a];
@@ -296,9 +387,25 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
                 const float *rec = rec0 + r * RS;
                 float dp = 0.0f;
                 for (int a = 0; a < A; ++a) dp = fmaf(Wt.p[POL_W][a * kH + j], rec[S_LOGITS + a], dp);
-                dp = fmaf(Wt.p[VAL_W][j], rec[S_VALUE], dp);
-                T1[r * kH + j] = p1[r * AS + j] > 0.0f ? dp : 0.0f;
-                if (k > 0) T2[r * kH + j] = r1[r * AS + j] > 0.0f ? Wt.p[REW2_W][j] * rec[S_REWARD] : 0.0f;
+                if constexpr (CAT) {
+                    y[m] = dp, keep[m] = 0.0f;
+                } else {
+                    dp = fmaf(Wt.p[VAL_W][j], rec[S_VALUE], dp);
+                    T1[r * kH + j] = p1[r * AS + j] > 0.0f ? dp : 0.0f;
+                    if (k > 0) T2[r * kH + j] = r1[r * AS + j] > 0.0f ? Wt.p[REW2_W][j] * rec[S_REWARD] : 0.0f;
+                }
+            }
+        }
+        if constexpr (CAT) {   // + val.w^T d value logits; rew2.w^T d reward logits: over the Bn rows the heads have
+            gemv_bwd_n<R>(Wt.p[VAL_W], kH, j, HG + k * 2 * kH, HS, Bn, q, y);
+            if (k > 0) gemv_bwd_n<R>(Wt.p[REW2_W], kH, j, HG + k * 2 * kH + kH, HS, Bn, q, keep);
+#pragma unroll
+            for (int m = 0; m < RPW; ++m) {
+                const int r = q + kWaves * m;
+                if (r < R) {
+                    T1[r * kH + j] = p1[r * AS + j] > 0.0f ? y[m] : 0.0f;
+                    if (k > 0) T2[r * kH + j] = r1[r * AS + j] > 0.0f ? keep[m] : 0.0f;
+                }
             }
         }
 #pragma unroll
@@ -308,12 +415,16 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
 #pragma unroll
             for (int c = 0; c < 2; ++c)
                 if (2 * q + c < A) a_polw[c] = fmaf(rec[S_LOGITS + 2 * q + c], pv, a_polw[c]);
-            if (q == 0) a_valw = fmaf(rec[S_VALUE], pv, a_valw);
-            if (q == 1 && k > 0) a_rew2w = fmaf(rec[S_REWARD], r1[r * AS + j], a_rew2w);
-            if (q == 2) {
-                if (j < A) a_hb += rec[S_LOGITS + j];
-                if (j == 8) a_hb += rec[S_VALUE];
-                if (j == 9 && k > 0) a_hb += rec[S_REWARD];
+            if constexpr (CAT) {
+                if (q == 2 && j < A) a_hb += rec[S_LOGITS + j];
+            } else {
+                if (q == 0) a_valw = fmaf(rec[S_VALUE], pv, a_valw);
+                if (q == 1 && k > 0) a_rew2w = fmaf(rec[S_REWARD], r1[r * AS + j], a_rew2w);
+                if (q == 2) {
+                    if (j < A) a_hb += rec[S_LOGITS + j];
+                    if (j == 8) a_hb += rec[S_VALUE];
+                    if (j == 9 && k > 0) a_hb += rec[S_REWARD];
+                }
             }
         }
         __syncthreads();
@@ -412,15 +523,70 @@ __global__ __launch_bounds__(kThreads) void k_mzl_grad(MzlWeights Wt, MzlBatch B
 #pragma unroll
     for (int c = 0; c < 4; ++c)
         if (4 * q + c < D) out[off[REP1_W] + j * D + 4 * q + c] = a_rep1[c];
-    if (q == 0) out[off[VAL_W] + j] = a_valw, out[off[DYN2_B] + j] = a_bias_dyn2, out[off[REP2_B] + j] = a_bias_rep2;
-    if (q == 1) out[off[REW2_W] + j] = a_rew2w, out[off[REW1_B] + j] = a_bias_rew1, out[off[REP1_B] + j] = a_bias_rep1;
+    if (q == 0) {
+        if constexpr (!CAT) out[off[VAL_W] + j] = a_valw;
+        out[off[DYN2_B] + j] = a_bias_dyn2, out[off[REP2_B] + j] = a_bias_rep2;
+    }
+    if (q == 1) {
+        if constexpr (!CAT) out[off[REW2_W] + j] = a_rew2w;
+        out[off[REW1_B] + j] = a_bias_rew1, out[off[REP1_B] + j] = a_bias_rep1;
+    }
     if (q == 2) {
         out[off[DYN1_B] + j] = a_bias_dyn1;
         if (j < A) out[off[POL_B] + j] = a_hb;
-        if (j == 8) out[off[VAL_B]] = a_hb;
-        if (j == 9) out[off[REW2_B]] = a_hb;
+        if constexpr (!CAT) {
+            if (j == 8) out[off[VAL_B]] = a_hb;
+            if (j == 9) out[off[REW2_B]] = a_hb;
+        }
     }
     if (q == 3) out[off[PRE1_B] + j] = a_bias_pre1;
+    if constexpr (CAT) {
+        // the heads' own gradients, from what the steps left in LDS (the accumulators above are stored: their registers are free).
+        // Thread (j < Bn, q): the 16 elements [j][16 q ..] of val.w and of rew2.w; wave 0 / wave 1: the two biases' column sums.
+        float a_val[16] = {}, a_rew2[16] = {}, a_vb = 0.0f, a_rb = 0.0f;
+        for (int k = K; k >= 0; --k) {
+            const float *p1 = act + (k == 0 ? 2 * kH : 3 * kH + (k - 1) * 4 * kH + 3 * kH), *hg = HG + k * 2 * kH;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float dv = hg[r * HS + j], dr = hg[r * HS + kH + j];
+                a_vb += dv, a_rb += dr;   // (step 0's d reward logits are zeros)
+#pragma unroll
+                for (int c = 0; c < 16; c += 4) {
+                    const float4 v = *(const float4 *)(p1 + r * AS + 16 * q + c);
+                    a_val[c] = fmaf(dv, v.x, a_val[c]), a_val[c + 1] = fmaf(dv, v.y, a_val[c + 1]), a_val[c + 2] = fmaf(dv, v.z, a_val[c + 2]), a_val[c + 3] = fmaf(dv, v.w, a_val[c + 3]);
+                }
+                if (k > 0) {
+#pragma unroll
+                    for (int c = 0; c < 16; c += 4) {
+                        const float4 v = *(const float4 *)(p1 - kH + r * AS + 16 * q + c);   // relu(rew1) lies before relu(pre1)
+                        a_rew2[c] = fmaf(dr, v.x, a_rew2[c]), a_rew2[c + 1] = fmaf(dr, v.y, a_rew2[c + 1]), a_rew2[c + 2] = fmaf(dr, v.z, a_rew2[c + 2]), a_rew2[c + 3] = fmaf(dr, v.w, a_rew2[c + 3]);
+                    }
+                }
+            }
+        }
+        if (j < Bn) {
+            store16(out + off[VAL_W] + j * kH + 16 * q, a_val);
+            store16(out + off[REW2_W] + j * kH + 16 * q, a_rew2);
+            if (q == 0) out[off[VAL_B] + j] = a_vb;
+            if (q == 1) out[off[REW2_B] + j] = a_rb;
+        }
+    }
+    if constexpr (CAT) {
+        __syncthreads();   // (every wave is through with T1)
+        double *lossD = (double *)T1;   // [4][kMaxRows]
+        if (t < R) {
+            const double w = B.weights && my_row ? (double)B.weights[row0 + t] : 1.0;
+            lossD[t] = (0.25 * w_lv + w_lr + w_lp) * w, lossD[kMaxRows + t] = w_lv, lossD[2 * kMaxRows + t] = w_lr, lossD[3 * kMaxRows + t] = w_lp;
+        }
+        __syncthreads();
+        if (t < 4) {
+            double s = 0.0;
+            for (int r = 0; r < R; ++r) s += lossD[t * kMaxRows + r];   // (rows past n hold zeros)
+            const float hi = (float)s;
+            loss_partial[4 * blockIdx.x + t] = hi, loss_lo[4 * blockIdx.x + t] = (float)(s - (double)hi);
+        }
+        return;
+    }
     if (t < R) {
         const float w = B.weights && my_row ? B.weights[row0 + t] : 1.0f;
         lossL[t] = (0.25f * lv + lr + lp) * w, lossL[kMaxRows + t] = lv, lossL[2 * kMaxRows + t] = lr, lossL[3 * kMaxRows + t] = lp;

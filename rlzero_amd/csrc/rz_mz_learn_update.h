@@ -12,9 +12,12 @@
 
 namespace {
 
-// element p = the partials in workgroup order; sq[block] = the sum of the block's squares; block 0: the four loss means
+// element p = the partials in workgroup order; sq[block] = the sum of the block's squares; block 0: the four loss means.
+// WIDE (categorical heads): a workgroup's loss sums are the float pairs loss_partial + loss_lo, summed in double and rounded once.
+template <bool WIDE>
 __global__ __launch_bounds__(kThreads) void k_mzl_reduce(const float *__restrict__ partial, const float *__restrict__ loss_partial, int n_wg, int n_params,
-                                                         long long n, float *__restrict__ grad, float *__restrict__ sq, float *__restrict__ out4) {
+                                                         long long n, float *__restrict__ grad, float *__restrict__ sq, float *__restrict__ out4,
+                                                         const float *__restrict__ loss_lo) {
     __shared__ float tree[kThreads];
     const int p = blockIdx.x * kThreads + threadIdx.x;
     float g = 0.0f;
@@ -30,9 +33,15 @@ __global__ __launch_bounds__(kThreads) void k_mzl_reduce(const float *__restrict
     }
     if (threadIdx.x == 0) sq[blockIdx.x] = tree[0];
     if (blockIdx.x == 0 && threadIdx.x < 4) {
-        float s = 0.0f, c = 0.0f;
-        for (int w = 0; w < n_wg; ++w) kahan_add(&s, &c, loss_partial[4 * w + threadIdx.x]);
-        out4[threadIdx.x] = s / (float)n;
+        if constexpr (WIDE) {
+            double s = 0.0;
+            for (int w = 0; w < n_wg; ++w) s += (double)loss_partial[4 * w + threadIdx.x] + (double)loss_lo[4 * w + threadIdx.x];
+            out4[threadIdx.x] = (float)(s / (double)n);
+        } else {
+            float s = 0.0f, c = 0.0f;
+            for (int w = 0; w < n_wg; ++w) kahan_add(&s, &c, loss_partial[4 * w + threadIdx.x]);
+            out4[threadIdx.x] = s / (float)n;
+        }
     }
 }
 

@@ -4,7 +4,8 @@ against the search visit distribution, gradient of the unrolled steps scaled by 
 the dynamics function halved at every step.
 
 ``fused_learner=True`` (opt-in): the same update as three HIP launches without a host synchronisation (learner.py:
-MuZeroFusedLearner; csrc/rz_mz_learn.hip).  ``learn`` below stays the definition of the arithmetic and the default."""
+MuZeroFusedLearner; csrc/rz_mz_learn.hip), for scalar and for categorical heads.  ``learn`` below (``support_losses`` for a net with
+a support) stays the definition of the arithmetic and the default."""
 import torch
 import torch.nn.functional as F
 
@@ -24,14 +25,44 @@ def scale_gradient(x, scale):
     return x * scale + x.detach() * (1.0 - scale)
 
 
+def support_losses(net, obs, actions, tv, tr, tp, mask, weights=None):
+    """The losses of a net with categorical heads (any float dtype) -> (loss, lv, lr, lp), the last three per row: the value and
+    reward losses are cross-entropies of the heads' logits against ``two_hot`` of the (already transformed) targets; the policy loss,
+    the 1 / K scaling, the halved gradient into the dynamics, the 0.25 on the value loss and the priority weights are ``learn``'s."""
+    from .support import two_hot_torch
+    S, K = net.support, actions.shape[1]
+
+    def cross_entropy(head, target):
+        return -(two_hot_torch(target, S) * F.log_softmax(head, dim=1)).sum(dim=1)
+    state = net.representation(obs)
+    logits, vhead = net.prediction_logits(state)
+    lv = cross_entropy(vhead, tv[:, 0])
+    lr_ = torch.zeros_like(lv)
+    lp = -(tp[:, 0] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, 0]
+    for k in range(1, K + 1):
+        state, rhead = net.dynamics_logits(state, actions[:, k - 1])
+        logits, vhead = net.prediction_logits(state)
+        g = 1.0 / K
+        lv = lv + scale_gradient(cross_entropy(vhead, tv[:, k]), g)
+        lr_ = lr_ + scale_gradient(cross_entropy(rhead, tr[:, k]), g)
+        lp = lp + scale_gradient(-(tp[:, k] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, k], g)
+        state = scale_gradient(state, 0.5)
+    if weights is None:
+        loss = (0.25 * lv + lr_ + lp).mean()
+    else:
+        loss = ((0.25 * lv + lr_ + lp) * weights).mean()
+    return loss, lv, lr_, lp
+
+
 class MuZeroAgent(object):
 
     def __init__(self, obs_dim=4, n_actions=2, hidden=64, lr=3e-3, weight_decay=1e-4, device='cuda:0', fused_learner=False, unroll_steps=5,
                  max_batch=1024, value_transform=False, support=None):
         """``support``: passed on to the net (``MuZeroNet(support=S)``: categorical reward and value heads over 2 S + 1 bins; it needs
         ``value_transform``): ``learn`` then takes the cross-entropy of the two heads' logits against ``two_hot`` of the batch's
-        targets (which both buffers hand out as float32(h(z)) already), and a checkpoint carries S.  The fused learner does not serve
-        such a net: ``fused_learner=True`` with ``support`` raises a ValueError before anything is allocated.
+        targets (which both buffers hand out as float32(h(z)) already), and a checkpoint carries S.  The fused learner serves such a
+        net on a GPU (S in 1 .. 31); ``fused_learner=True`` with ``support`` and a ``device`` that is no GPU raises a ValueError before
+        anything is allocated.
         ``value_transform``: passed on to the net (``MuZeroNet(value_transform=...)``, the flag's owner): the mini-batches must
         then come from a buffer built with it (``learn(batch, buffer=...)`` checks), and a checkpoint carries the setting.
         ``fused_learner``: updates run in the HIP learner (hidden 64, obs_dim <= 16, n_actions <= 8, unroll_steps <= 16: a
@@ -39,12 +70,12 @@ class MuZeroAgent(object):
         unroll_steps and up to max_batch rows) and mean nothing to the PyTorch route.  The route is fixed for the agent's life; a
         checkpoint moves between the routes."""
         self.fused_learner = bool(fused_learner)
-        if self.fused_learner and support is not None:
-            raise ValueError('fused_learner=True does not serve a net with categorical heads (support=%r): the HIP learner\'s value and '
-                             'reward losses are squared errors of scalar heads; use the PyTorch route (fused_learner=False)' % (support, ))
+        if self.fused_learner and support is not None and torch.device(device).type != 'cuda':
+            raise ValueError('fused_learner=True with categorical heads (support=%r) needs a GPU, not device=%r: the HIP learner has no CPU '
+                             'route; use the PyTorch route (fused_learner=False)' % (support, str(device)))
         if self.fused_learner:
             from .learner import check_limits
-            check_limits(obs_dim, n_actions, hidden, unroll_steps)
+            check_limits(obs_dim, n_actions, hidden, unroll_steps, support)
         self.device = torch.device(device)
         self.n_actions = n_actions
         self.net = MuZeroNet(obs_dim, n_actions, hidden, value_transform=value_transform, support=support).to(self.device)
@@ -115,32 +146,10 @@ class MuZeroAgent(object):
         return float(loss.item()), float(lv.mean().item()), float(lr_.mean().item()), float(lp.mean().item())
 
     def _learn_support(self, obs, actions, tv, tr, tp, mask, weights):
-        """``learn`` for a net with categorical heads: the value and reward losses are cross-entropies of the heads' logits against
-        ``two_hot`` of the (already transformed) targets; the policy loss, the 1 / K scaling, the halved gradient into the dynamics,
-        the 0.25 on the value loss and the priority weights are ``learn``'s."""
-        from .support import two_hot_torch
-        net, S, K = self.net, self.net.support, actions.shape[1]
-
-        def cross_entropy(head, target):
-            return -(two_hot_torch(target, S) * F.log_softmax(head, dim=1)).sum(dim=1)
-        state = net.representation(obs)
-        logits, vhead = net.prediction_logits(state)
-        lv = cross_entropy(vhead, tv[:, 0])
-        lr_ = torch.zeros_like(lv)
-        lp = -(tp[:, 0] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, 0]
-        for k in range(1, K + 1):
-            state, rhead = net.dynamics_logits(state, actions[:, k - 1])
-            logits, vhead = net.prediction_logits(state)
-            g = 1.0 / K
-            lv = lv + scale_gradient(cross_entropy(vhead, tv[:, k]), g)
-            lr_ = lr_ + scale_gradient(cross_entropy(rhead, tr[:, k]), g)
-            lp = lp + scale_gradient(-(tp[:, k] * F.log_softmax(logits, dim=1)).sum(dim=1) * mask[:, k], g)
-            state = scale_gradient(state, 0.5)
-        if weights is None:
-            loss = (0.25 * lv + lr_ + lp).mean()
-        else:
+        """``learn`` for a net with categorical heads: ``support_losses`` above, then the step."""
+        if weights is not None:
             weights = (weights if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)).to(self.device, torch.float32)
-            loss = ((0.25 * lv + lr_ + lp) * weights).mean()
+        loss, lv, lr_, lp = support_losses(self.net, obs, actions, tv, tr, tp, mask, weights)
         return self._step(loss, lv, lr_, lp)
 
     def save_model(self, path):

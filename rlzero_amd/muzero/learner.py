@@ -8,18 +8,23 @@ single-tensor Adam -- on the current stream, with no host synchronisation and no
 written in torch's own storage (a table of 18 pointers: no second copy of the model), the two moments live in two flat tensors
 owned here.  After every step the parameters' version counters are raised, so ``MuZeroSelfPlay`` / ``MuZeroReanalyser`` upload the
 new weights before their next search.  No CPU fallback: HipError without a GPU.
+
+A net with categorical heads (``MuZeroNet(value_transform=True, support=S)``: ``rew2`` and ``val`` are ``Linear(64, 2 S + 1)``) is served
+by the kernel's second form: the value and reward losses are the two-hot cross-entropies of ``MuZeroAgent._learn_support``.
 """
 import ctypes
 
 from .. import _hip
 from .._hip import HipError
 
-HIDDEN, MAX_OBS, MAX_ACTIONS, MAX_UNROLL = 64, 16, 8, 16
+HIDDEN, MAX_OBS, MAX_ACTIONS, MAX_UNROLL, MAX_SUPPORT = 64, 16, 8, 16, 31
 LAYERS = ('rep1', 'rep2', 'dyn1', 'dyn2', 'rew1', 'rew2', 'pre1', 'pol', 'val')   # weight and bias of each: the 18 tensors, net.parameters()'s order
 
 
-def check_limits(obs_dim, n_actions, hidden, unroll_steps):
+def check_limits(obs_dim, n_actions, hidden, unroll_steps, support=None):
     """The fused learner's limits (the device replay's); ValueError naming the one that is exceeded.  Touches no device."""
+    if support is not None and (isinstance(support, bool) or int(support) != support or not 1 <= int(support) <= MAX_SUPPORT):
+        raise ValueError('the fused learner takes support (S) in 1 .. %d, or None for scalar heads (got %r)' % (MAX_SUPPORT, support))
     if int(hidden) != HIDDEN:
         raise ValueError('the fused learner is built for hidden = %d only (got hidden = %d)' % (HIDDEN, hidden))
     if not 1 <= int(obs_dim) <= MAX_OBS:
@@ -30,10 +35,10 @@ def check_limits(obs_dim, n_actions, hidden, unroll_steps):
         raise ValueError('the fused learner takes unroll_steps (K) in 1 .. %d (got %d)' % (MAX_UNROLL, unroll_steps))
 
 
-def n_params(obs_dim, n_actions):
-    """Elements of the flat gradient / moment vectors."""
-    H = HIDDEN
-    return H * obs_dim + H + 5 * (H * H + H) + H * n_actions + (n_actions + 2) * (H + 1)   # rep1; rep2 dyn1 dyn2 rew1 pre1; dyn1's action columns; heads
+def n_params(obs_dim, n_actions, support=None):
+    """Elements of the flat gradient / moment vectors (``support``: the reward and value heads have 2 S + 1 outputs each, not 1)."""
+    H, B = HIDDEN, 1 if support is None else 2 * int(support) + 1
+    return H * obs_dim + H + 5 * (H * H + H) + H * n_actions + (n_actions + 2 * B) * (H + 1)   # rep1; rep2 dyn1 dyn2 rew1 pre1; dyn1's action columns; heads
 
 
 class MuZeroFusedLearner(object):
@@ -44,7 +49,8 @@ class MuZeroFusedLearner(object):
     def __init__(self, net, lr=3e-3, weight_decay=1e-4, unroll_steps=5, max_batch=1024, betas=(0.9, 0.999), eps=1e-8, max_norm=5.0):
         import torch
         self.torch = torch
-        check_limits(net.obs_dim, net.n_actions, net.hidden, unroll_steps)
+        self.support = getattr(net, 'support', None)
+        check_limits(net.obs_dim, net.n_actions, net.hidden, unroll_steps, self.support)
         self.net = net
         self.params = [p for name in LAYERS for p in (getattr(net, name).weight, getattr(net, name).bias)]
         if [id(p) for p in self.params] != [id(p) for p in net.parameters()]:
@@ -57,7 +63,7 @@ class MuZeroFusedLearner(object):
         self.lib = _hip.load()
         self.D, self.A, self.K, self.max_batch = int(net.obs_dim), int(net.n_actions), int(unroll_steps), int(max_batch)
         self.lr, self.weight_decay, self.betas, self.eps, self.max_norm = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps), float(max_norm)
-        cfg = _hip.RzMzLearnerConfig(_hip.ABI_VERSION, self.D, self.A, int(net.hidden), self.K, self.max_batch, dev.index, 0, self.lr, self.weight_decay,
+        cfg = _hip.RzMzLearnerConfig(_hip.ABI_VERSION, self.D, self.A, int(net.hidden), self.K, self.max_batch, dev.index, self.support or 0, self.lr, self.weight_decay,
                                      self.betas[0], self.betas[1], self.eps, self.max_norm)
         handle = ctypes.c_void_p()
         _hip.check(self.lib.rz_mz_learner_create(ctypes.byref(cfg), ctypes.byref(handle)), 'rz_mz_learner_create')
@@ -65,7 +71,7 @@ class MuZeroFusedLearner(object):
         got = ctypes.c_int64()
         _hip.check(self.lib.rz_mz_learner_n_params(self.handle, ctypes.byref(got)), 'rz_mz_learner_n_params')
         self.n_params = got.value
-        if self.n_params != sum(p.numel() for p in self.params) or self.n_params != n_params(self.D, self.A):
+        if self.n_params != sum(p.numel() for p in self.params) or self.n_params != n_params(self.D, self.A, self.support):
             raise HipError('the library counts %d parameters, the network has %d' % (self.n_params, sum(p.numel() for p in self.params)))
         self.exp_avg = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(self.n_params, dtype=torch.float32, device=dev)

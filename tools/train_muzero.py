@@ -50,8 +50,8 @@ class MuZeroPipeline(object):
                  max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None, search='puct', gumbel_considered=4,
                  gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None):
         """``support`` (needs ``value_transform``): the half-width S of the categorical support of the reward and value heads
-        (``MuZeroNet(support=S)``: 2 S + 1 bins, cross-entropy against two-hot targets in the PyTorch learner, the expectation read
-        inside the search kernel).  Refused with a ValueError together with ``fused_learner`` or ``whole_moves``.  None: scalar heads.
+        (``MuZeroNet(support=S)``: 2 S + 1 bins, cross-entropy against two-hot targets in either learner, the expectation read
+        inside the search kernel).  Refused with a ValueError together with ``whole_moves``.  None: scalar heads.
         ``device_replay``: finished episodes go to a MuZeroDeviceReplay (whole moves hand them over on the device) and every
         mini-batch is one launch there; otherwise the host ReplayBuffer, as before.
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
@@ -300,7 +300,7 @@ def build_parser():
                          'invert them inside every search (arXiv:1911.08265v2 appendix F, without the categorical support)')
     ap.add_argument('--support', type=int, default=None, metavar='S',
                     help='categorical value and reward heads over the 2 S + 1 bins -S .. S of the transformed space, 1 <= S <= 31 '
-                         '(arXiv:1911.08265v2 appendix F; needs --value-transform; not with --fused-learner or --whole-moves)')
+                         '(arXiv:1911.08265v2 appendix F; needs --value-transform; not with --whole-moves)')
     ap.add_argument('--eval-every', type=int, default=0, metavar='N',
                     help='after every N-th iteration, a greedy evaluation (temperature 0, no root noise) on environments of its own '
                          'from fixed initial states, reported on a line of its own (0 = never)')
