@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 51
+#define RZ_ABI_VERSION 52
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -914,6 +914,28 @@ int rz_mz_search_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const flo
  * without the value transform; whole moves (rz_mz_play_env, rz_mz_play_cartpole) while either is set -- they keep scalar heads. */
 int rz_mz_load_model_support(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t hidden, int32_t support);
 int rz_mz_set_support(rz_muzero *e, int32_t support);
+/* The search from raw observations in ONE launch (ABI 52; k_mz_search's ROOTS instantiations, csrc/rz_muzero_search.h): what a caller ran
+ * in front of rz_mz_search -- the initial inference, the softmax, the copy of the root states into slot 0, rz_mz_init_roots -- is a
+ * stage at the head of the launch.  rz_mz_load_root_model: HOST pointers to rep1.weight [64][obs_dim], rep1.bias, rep2.weight [64][64],
+ * rep2.bias (torch layout), 1 <= obs_dim <= 16, hidden 64; packed by rzmp::pack_root_model (csrc/rz_mz_pack.h) into storage of its own,
+ * apart from rz_mz_load_representation's; call again after every optimiser step, beside rz_mz_load_model.  RZ_ERR_ARG with the reason
+ * for anything else.
+ * rz_mz_search_obs: d_obs float32 [n_games][obs_dim] of the loaded root model.  Per game: s0 = scale(rep2 relu(rep1 obs)) (the per-sample
+ * min-max scaling of MuZeroNet.initial_inference) is stored at slot 0 of d_hidden, the prediction f(s0) gives the value and the policy
+ * logits, their float32 softmax row goes to d_root_probs [n_games][n_actions] (when not NULL), the root and its children are written
+ * exactly as rz_mz_init_roots writes them for that row with d_noise float64 [n_games][n_actions] (or NULL) and noise_frac -- the same
+ * function, the same bits -- and the n_sims simulations of rz_mz_search follow.  Whatever trees the handle held are not read.  One launch on
+ * `stream`, no host synchronisation, no allocation.  The six trace arrays (all or none) have ONE ROW MORE than rz_mz_search's:
+ * [n_sims + 1][n_games] (probs: x n_actions); row 0 is the root's -- parent -1, action -1, leaf 0, reward 0, the root's softmax row and
+ * its predicted value (raw, through h^-1, under the value transform) -- and row 1 + s is simulation s as rz_mz_search traces it.
+ * The pUCT rule with scalar heads is served, with or without the value transform.  RZ_ERR_ARG with the reason, nothing launched: the
+ * Gumbel search on; a support set or loaded; no model or no root model loaded; more than 8 actions; n_sims outside 1 .. the tree's.
+ * rz_mz_search_plan with whole_moves 2 reports this launch: the plan of rz_mz_search with pUCT and scalar heads -- the stage's observation
+ * tile and staged first layer lie in LDS the simulations use later, so no tree leaves LDS that rz_mz_search keeps there. */
+int rz_mz_load_root_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t obs_dim, int32_t hidden);
+int rz_mz_search_obs(rz_muzero *e, const float *d_obs, float *d_hidden, int32_t n_sims, const double *d_noise, double noise_frac,
+                     float *d_root_probs, int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward,
+                     float *d_trace_probs, float *d_trace_value, void *stream);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action

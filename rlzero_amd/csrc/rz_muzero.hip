@@ -12,7 +12,8 @@
 //   * step by step (rz_mz_select / rz_mz_expand_backup, one THREAD per game): the learned model stays outside -- the
 //     caller gathers the parents' hidden states, runs dynamics + prediction on the batch, stores the new hidden states
 //     at the leaf slots and hands reward / policy / value back;
-//   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search);
+//   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search); rz_mz_search_obs: the
+//     same from raw observations -- initial inference and roots made in the launch too (its ROOTS instantiations);
 //   * rz_mz_play_env (rz_mz_play_cartpole is its CartPole form): whole MOVES in one launch -- initial inference, root noise, search,
 //     action draw, environment step, episode history on the device (k_mz_search with its MOVES stages, instantiated per environment
 //     trait of rz_mz_env.h: CartPole, Acrobot).
@@ -40,7 +41,8 @@
 //   rz_muzero_search.h  k_mz_search with MzModel, MzTrace, MzPlay and its LDS budget (mz_search_lds_bytes)
 //   rz_muzero_roots.h   the root readers: k_mz_root_children, k_mz_root_stats
 //   rz_muzero_moves.h   the moves behind a search: k_mz_env_step, k_mz_env_move (MzEnvPlay), k_mz_root_noise
-// What the two loaders compute before they upload is plain C++ in rz_mz_pack.h, tested on the CPU (tests/test_mz_pack.py).
+// What the loaders compute before they upload is plain C++ in rz_mz_pack.h, tested on the CPU (tests/test_mz_pack.py,
+// tests/test_mz_search_obs_host.py); how a root is made -- by k_mz_init and inside k_mz_search -- is rz_mz_roots.h (no kernel).
 // Below: struct rz_muzero, the table of k_mz_search's instantiations, the launch helpers and every extern "C" entry point.
 
 #include <hip/hip_runtime.h>
@@ -90,6 +92,10 @@ struct rz_muzero {
     int support = 0, model_support = 0;
     MzSupport cat = {};                // rz_mz_load_model_support: the packed heads inside d_model_cat
     float *d_model_cat = nullptr;
+    // rz_mz_load_root_model: the representation network of the search from observations (rz_mz_search_obs), in storage of its own
+    float *d_root = nullptr;
+    int root_obs_dim = 0;              // 0: none loaded
+    const float *root_w[4] = {};       // rep1.w, rep1.b, rep2.w, rep2.b inside d_root (rzmp::pack_root_model)
 };
 
 namespace {
@@ -104,7 +110,7 @@ constexpr auto mz_search_kernel = k_mz_search<TREE_LDS, MOVES, Env, (MOVES ? Env
 // the same rows for the dynamic-LDS attribute, so what can be launched is what was prepared.  A row is a route -- the search alone
 // (kMzNoEnv) or whole moves of an environment kind -- with or without the value transform, and holds its kernel for either placement of
 // the trees.  A new environment is one line: its two rows.  (The rows stand in the order of the instantiations in the code object.)
-typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzNoSupport);
+typedef void (*MzSearchFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzNoSupport, MzNoRoots);
 constexpr int kMzNoEnv = -1;
 struct MzSearchRow {
     int kind;   // RZ_MZ_ENV_* of whole moves, kMzNoEnv for rz_mz_search
@@ -116,7 +122,7 @@ constexpr MzSearchRow mz_search_row(int kind) {
     return {kind, VT, mz_search_kernel<true, MOVES, Env, VT>, mz_search_kernel<false, MOVES, Env, VT>};
 }
 // the GUMBEL instantiations (rz_mz_search_gumbel): the search alone, trees in LDS and in HBM, with and without the value transform
-typedef void (*MzGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzNoSupport);
+typedef void (*MzGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzNoSupport, MzNoRoots);
 struct MzGumbelRow {
     bool vt;
     MzGumbelFn tree_lds, tree_hbm;
@@ -132,12 +138,25 @@ constexpr MzSearchRow kMzSearchRows[] = {
 };
 constexpr MzGumbelRow kMzGumbelRows[] = {mz_gumbel_row<false>(), mz_gumbel_row<true>()};
 // the CAT instantiations (rz_mz_set_support): the search alone with the value transform, pUCT and Gumbel, trees in LDS and in HBM
-typedef void (*MzCatFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzSupport);
-typedef void (*MzCatGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzSupport);
+typedef void (*MzCatFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzSupport, MzNoRoots);
+typedef void (*MzCatGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzSupport, MzNoRoots);
 constexpr MzCatFn kMzCatLds = k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, true, false, true>;
 constexpr MzCatFn kMzCatHbm = k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, true, false, true>;
 constexpr MzCatGumbelFn kMzCatGumbelLds = k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, true, true, true>;
 constexpr MzCatGumbelFn kMzCatGumbelHbm = k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, true, true, true>;
+// the ROOTS instantiations (rz_mz_search_obs): the search alone from raw observations -- pUCT, scalar heads --, trees in LDS and in HBM,
+// with and without the value transform
+typedef void (*MzRootsFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzNoGumbel, MzNoSupport, MzRoots);
+struct MzRootsRow {
+    bool vt;
+    MzRootsFn tree_lds, tree_hbm;
+};
+template <bool VT>
+constexpr MzRootsRow mz_roots_row() {
+    return {VT, k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, VT, false, false, true>,
+            k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, VT, false, false, true>};
+}
+constexpr MzRootsRow kMzRootsRows[] = {mz_roots_row<false>(), mz_roots_row<true>()};
 
 // what a launch with categorical heads needs (rz_mz_set_support), and what one without them must not meet
 int mz_support_ready(const rz_muzero *e) {
@@ -165,9 +184,12 @@ struct MzPlan {
 };
 // `gumbel`: a launch of the GUMBEL instantiations (their LDS holds more per node and per launch: mz_search_lds_bytes)
 // (a support net's launch -- never whole moves -- carries the CAT instantiations' extra LDS)
-MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false) {
+// `roots`: a launch of the ROOTS instantiations (rz_mz_search_obs: pUCT and scalar heads, whatever the handle is set to); their stage
+// takes no LDS of its own, so the plan is rz_mz_search's for such a handle
+MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false, bool roots = false) {
     MzPlan p;
-    const bool cat = e->support > 0 && !whole_moves;
+    const bool cat = e->support > 0 && !whole_moves && !roots;
+    if (roots) gumbel = false;
     const int w1c = mz_w1_cols(whole_moves, e->cfg.n_actions <= kMzMaxA ? e->cfg.n_actions : kMzMaxA);
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
     // other, so the 16 columns of a tile are filled first (profiles/r02/muzero_search_shape.txt)
@@ -179,6 +201,17 @@ MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false)
     return p;
 }
 
+int mz_launch_roots(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzRoots &R, void *stream) {
+    const MzPlan plan = mz_search_plan(e, false, false, true);
+    if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
+    MzRootsFn fn = nullptr;
+    for (const MzRootsRow &row : kMzRootsRows)
+        if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, MzNoGumbel{}, MzNoSupport{}, R);
+    return rz_launched("k_mz_search (observations)");
+}
+
 // play != nullptr: whole moves of the environment `kind` (checked by rz_mz_play_env)
 int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzPlay *play, int kind, void *stream) {
     RZ_TRY(mz_support_ready(e));
@@ -187,7 +220,7 @@ int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrac
     const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
     if (e->support > 0) {   // (never whole moves: mz_play_launch has refused them)
         (plan.tree_lds ? kMzCatLds : kMzCatHbm)<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{},
-                                                                                                MzNoGumbel{}, e->cat);
+                                                                                                MzNoGumbel{}, e->cat, MzNoRoots{});
         return rz_launched("k_mz_search (support)");
     }
     const int route = play != nullptr ? kind : kMzNoEnv;
@@ -197,7 +230,7 @@ int mz_launch_search(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrac
     if (fn == nullptr) return rz_fail(RZ_ERR_ARG, "unknown environment kind %d", kind);
     const MzPlay none = {};
     fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, play != nullptr ? *play : none, MzNoGumbel{},
-                                                       MzNoSupport{});
+                                                       MzNoSupport{}, MzNoRoots{});
     return rz_launched("k_mz_search");
 }
 
@@ -208,13 +241,13 @@ int mz_launch_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrac
     const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
     if (e->support > 0) {
         (plan.tree_lds ? kMzCatGumbelLds : kMzCatGumbelHbm)<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T,
-                                                                                                            MzPlay{}, Z, e->cat);
+                                                                                                            MzPlay{}, Z, e->cat, MzNoRoots{});
         return rz_launched("k_mz_search (gumbel, support)");
     }
     MzGumbelFn fn = nullptr;
     for (const MzGumbelRow &row : kMzGumbelRows)
         if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
-    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z, MzNoSupport{});
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z, MzNoSupport{}, MzNoRoots{});
     return rz_launched("k_mz_search (gumbel)");
 }
 
@@ -374,6 +407,10 @@ static int mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_p
         for (const void *fn : {(const void *)kMzCatLds, (const void *)kMzCatHbm, (const void *)kMzCatGumbelLds, (const void *)kMzCatGumbelHbm})
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
                 return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        for (const MzRootsRow &row : kMzRootsRows)
+            for (MzRootsFn fn : {row.tree_lds, row.tree_hbm})
+                if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+                    return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
         e->attributes_set = true;
     }
     if (hipMemcpy(d_model, packed.host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -438,6 +475,46 @@ int rz_mz_search(rz_muzero *e, float *d_hidden, int32_t n_sims, int32_t *d_trace
     if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
     const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
     return mz_launch_search(e, d_hidden, n_sims, T, nullptr, 0, stream);
+}
+
+int rz_mz_load_root_model(rz_muzero *e, const float *const *h_params, int32_t n_params, int32_t obs_dim, int32_t hidden) {
+    RZ_ENTER(mz_ready, e);
+    if (h_params == nullptr || n_params != 4) return rz_fail(RZ_ERR_ARG, "expected rep1.weight, rep1.bias, rep2.weight, rep2.bias");
+    if (hidden != kMzH) return rz_fail(RZ_ERR_ARG, "the search from observations is built for hidden size 64, not %d", hidden);
+    if (obs_dim < 1 || obs_dim > rzmp::kMzRootObs)
+        return rz_fail(RZ_ERR_ARG, "the search from observations takes 1 .. %d observation features, not %d", rzmp::kMzRootObs, obs_dim);
+    for (int i = 0; i < 4; ++i)
+        if (!h_params[i]) return rz_fail(RZ_ERR_ARG, "a parameter pointer is NULL");
+    const rzmp::Representation packed = rzmp::pack_root_model(h_params, obs_dim);   // rep1 k-major, padded to 16 rows: rz_mz_pack.h
+    RZ_HIP(hipDeviceSynchronize());
+    if (e->d_root == nullptr) RZ_TRY(e->pool.alloc(&e->d_root, (long long)packed.host.size()));
+    if (hipMemcpy(e->d_root, packed.host.data(), packed.host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return rz_fail(RZ_ERR_HIP, "hipMemcpy(root model) failed");
+    for (int i = 0; i < 4; ++i) e->root_w[i] = e->d_root + packed.off[i];
+    e->root_obs_dim = obs_dim;
+    return RZ_OK;
+}
+
+int rz_mz_search_obs(rz_muzero *e, const float *d_obs, float *d_hidden, int32_t n_sims, const double *d_noise, double noise_frac,
+                     float *d_root_probs, int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward,
+                     float *d_trace_probs, float *d_trace_value, void *stream) {
+    RZ_ENTER(mz_ready, e);
+    if (e->gumbel_considered > 0)
+        return rz_fail(RZ_ERR_ARG, "the Gumbel search is on (rz_mz_set_gumbel): the search from observations keeps the pUCT rule and is not served");
+    if (e->support > 0 || e->model_support > 0)
+        return rz_fail(RZ_ERR_ARG, "categorical heads (rz_mz_set_support / rz_mz_load_model_support): the search from observations keeps "
+                                   "scalar heads and is not served");
+    if (!e->model_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model has not been called");
+    if (e->root_obs_dim < 1) return rz_fail(RZ_ERR_ARG, "rz_mz_load_root_model has not been called");
+    if (e->cfg.n_actions > kMzMaxA) return rz_fail(RZ_ERR_ARG, "the fused search handles up to 8 actions, the tree has %d", e->cfg.n_actions);
+    if (d_obs == nullptr || d_hidden == nullptr) return rz_fail(RZ_ERR_ARG, "d_obs or d_hidden is NULL");
+    if (n_sims < 1 || n_sims > e->cfg.n_sims) return rz_fail(RZ_ERR_ARG, "n_sims %d is outside 1 .. %d, the tree's", n_sims, e->cfg.n_sims);
+    const bool any = d_trace_parent || d_trace_action || d_trace_leaf || d_trace_reward || d_trace_probs || d_trace_value;
+    const bool all = d_trace_parent && d_trace_action && d_trace_leaf && d_trace_reward && d_trace_probs && d_trace_value;
+    if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
+    const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
+    const MzRoots R = {d_obs, e->root_obs_dim, e->root_w[0], e->root_w[1], e->root_w[2], e->root_w[3], d_noise, noise_frac, d_root_probs};
+    return mz_launch_roots(e, d_hidden, n_sims, T, R, stream);
 }
 
 int rz_mz_set_gumbel(rz_muzero *e, int32_t max_considered, double c_visit, double c_scale, const int32_t *h_cv, int64_t count) {
@@ -602,7 +679,8 @@ int rz_mz_debug_profile(long long *h_out16) {
 
 int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    const MzPlan plan = mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);   // (a support: read from the handle)
+    const MzPlan plan = whole_moves == 2 ? mz_search_plan(e, false, false, true)
+                                         : mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);   // (a support: read from the handle)
     if (games_per_workgroup) *games_per_workgroup = plan.gpw;
     if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
     if (lds_bytes) *lds_bytes = plan.lds;

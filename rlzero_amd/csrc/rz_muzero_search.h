@@ -32,6 +32,9 @@
 //     called from the header, none restated.  Acrobot's step and observation (RK4 and double sin / cos: 230 registers) are CALLS
 //     (mz_env_step_far): inlined they spilled inside the simulation loop; as calls the simulation loop touches no scratch and the
 //     save / reload of the f16 fragments sits once per move (profiles/mz_whole_env/kernel_resources.txt).
+//   * ROOTS (rz_mz_search_obs): the search alone from raw observations -- representation, root prediction, softmax and the roots
+//     (k_mz_init's rule, rz_mz_roots.h) as a stage in front of simulation 0, on an observation tile and a staged first layer of its own
+//     in LDS (MzRoots, below): a Reanalyse chunk is one launch between `positions` and the read-out.
 //   * TREE_LDS trees use their own record: MzHot (N, first_child, value_sum, prior and q = reward + discount * value(),
 //     refreshed by the backup that changes it, so the walk does not divide value_sum / N again at every visit) plus one
 //     float of reward per node; sqrt(N) of the walk comes from a table filled with the same IEEE sqrt.  Same operations on
@@ -51,6 +54,7 @@
 #include "rz_mz_env.h"
 #include "rz_mz_gumbel.h"
 #include "rz_mz_pack.h"
+#include "rz_mz_roots.h"
 #include "rz_mz_support.h"
 #include "rz_mz_value.h"
 
@@ -58,7 +62,7 @@
 
 namespace {
 
-using rzmp::kMzH, rzmp::kMzMaxA, rzmp::kMzObs;   // the model's sizes: defined once, beside the packing of its weights
+using rzmp::kMzH, rzmp::kMzMaxA, rzmp::kMzObs, rzmp::kMzRootObs;   // the model's sizes: defined once, beside the packing of its weights
 constexpr int kMzWaves = 4, kMzTile = 16, kMzKX = kMzH + kMzMaxA, kMzMaxGpw = 16;
 constexpr int kMzRedRows = 4 + kMzMaxA;   // min, max, reward, value, logits
 constexpr int kMzHeadRows = 2 + kMzMaxA;  // rew2, val, pol rows
@@ -117,6 +121,7 @@ __host__ __device__ constexpr int mz_w1_cols(bool whole_moves, int n_actions) { 
 // every launch the considered-visits table (int32 [n_sims]) and the games' Gumbel rows (float [gpw][8])
 // `cat`: the CAT instantiations add, behind everything else, relu(rew1)'s activations [64][16], the two heads' logits [2][16][65], their
 // weights [2][64][64] and their biases [2][64]
+// (the ROOTS instantiations add nothing: their observation tile and staged first layer lie in RED and XS, which are idle until the stage's end)
 __host__ __device__ inline int mz_search_lds_bytes(int gpw, int cap, int path_stride, int n_sims_cfg, bool tree_lds, int w1_cols, bool gumbel = false,
                                                    bool cat = false) {
     int bytes = mz_search_fixed_floats(w1_cols) * 4 + gpw * path_stride * 4;
@@ -209,6 +214,35 @@ struct MzSupport {
     int S;
 };
 struct MzNoSupport {};
+
+// ---- the search from raw observations (the ROOTS instantiations; rz_mz_search_obs)
+// Everything in front of a search that PyTorch ran before it -- representation, root prediction, softmax, the strided copy of the root
+// states, k_mz_init -- is one stage at the head of the launch, on the tiles the simulations use:
+//   * the workgroup's games load their observation rows into an LDS tile [16 features][16 games] (a thread per element; rows past
+//     n_games and features past obs_dim are written as zero and nothing outside the array is read), and rep1's weights, k-major
+//     [16][64] with the rows past obs_dim zero (rzmp::pack_root_model), are staged with one 16-byte load per thread -- they are used
+//     once, so they never become fragments that live across the simulation loop.  Neither costs LDS of its own: the tile lies in RED
+//     (first written by the stage's own min-max step, a barrier after the tile's last read) and the weights in rows 0 .. 63 of XS (first
+//     written by scale_and_store, two barriers after their last read; the one-hot rows behind them keep their zeros) -- 6 KB more
+//     would have put the trees of Reanalyse's standing shape (2 actions, 50 simulations, 16 games: 81152 of 81920 bytes) into HBM;
+//   * rep1 is four K steps of v_mfma_f32_16x16x4_f32 over the padded tile, rep2 sixteen, with the operand layout, the bias as the
+//     accumulator's start and the order of accumulation of the simulations' layers (mz_tile): observations are raw -- no range is known
+//     for them -- so the products are the exact f32 ones of this route's other layers, not the f16 pieces of whole moves, whose scales rest
+//     on states in [0, 1].  rep2's fragments and the two biases come straight from L2 and die with the stage;
+//   * the min-max scaling, the store of the root state to slot 0 of `hidden` and the prediction are the simulations' own pieces
+//     (scale_and_store with Gleaf = 0, predict_partials, finish_prediction); the scaled state stays in XS, where simulation 0 -- whose
+//     parent is the root in every game -- reads it without the gather from HBM;
+//   * wave 0 takes the value (through h^-1 with VT) and the float32 softmax row, hands them out (root_probs; row 0 of the trace) and
+//     makes the root with rz_mz_roots.h's rule, k_mz_init's: with TREE_LDS the record is born in LDS and reaches HBM with the write-out.
+struct MzRoots {
+    const float *obs;                        // [n_games][obs_dim]
+    int obs_dim;
+    const float *rep1_w, *rep1_b, *rep2_w, *rep2_b;   // rzmp::pack_root_model
+    const double *noise;                     // [n_games][A] or null
+    double noise_frac;
+    float *root_probs;                       // [n_games][A] or null: the float32 softmax rows the roots were made from
+};
+struct MzNoRoots {};
 // the double of lane l ^ 1 / l ^ 2 within a quad (DPP quad_perm [1, 0, 3, 2] = 0xB1, [2, 3, 0, 1] = 0x4E)
 template <int CTRL>
 __device__ __forceinline__ double mz_quad_f64(double x) {
@@ -491,13 +525,18 @@ __device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, fl
 // pi' of every game in Z.action_out / Z.pi_out.  The matrix-pipe stages are the same code.  Z: MzGumbel, an empty record otherwise.
 // CAT (MOVES = false, VT = true only): the reward and value heads are softmaxes over a support (above; rz_mz_set_support), read as
 // h^-1 of their expectation.  C: MzSupport, an empty record otherwise.
+// ROOTS (MOVES = GUMBEL = CAT = false only): the launch starts from raw observations (above; rz_mz_search_obs) -- the trees it finds are
+// not read, the roots are made in the launch, and the trace, when given, has a row 0 for the root in front of the simulations'.
+// R: MzRoots, an empty record otherwise.
 template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false,
-          bool GUMBEL = false, bool CAT = false>
+          bool GUMBEL = false, bool CAT = false, bool ROOTS = false>
 __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel M, float *hidden, int n_sims, int gpw, MzTrace T, MzPlay P,
                                                                  typename std::conditional<GUMBEL, MzGumbel, MzNoGumbel>::type Z,
-                                                                 typename std::conditional<CAT, MzSupport, MzNoSupport>::type C) {
+                                                                 typename std::conditional<CAT, MzSupport, MzNoSupport>::type C,
+                                                                 typename std::conditional<ROOTS, MzRoots, MzNoRoots>::type R) {
     static_assert(!(GUMBEL && MOVES), "whole moves keep the pUCT rule");
     static_assert(!CAT || (VT && !MOVES), "the support lies in h's space; whole moves keep scalar heads");
+    static_assert(!ROOTS || (!MOVES && !GUMBEL && !CAT), "the search from observations serves the pUCT rule with scalar heads");
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
     constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
     constexpr int W1C = mz_w1_cols(MOVES, Env::kActions);
@@ -539,6 +578,9 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
     float *LG = RA + kMzH * kMzTile;
     float *WH = LG + 2 * kMzTile * kMzLgStride;      // [reward | value][k][64]: row k rotated by 16 k bins
     float *HBC = WH + 2 * kMzH * rzmzs::kLanes;      // [reward | value][64]: the heads' biases
+    // ROOTS: the observation tile [feature][game] in RED and rep1's weights [k][64] in rows 0 .. 63 of XS, both dead before their hosts' first write
+    static_assert(kMzRootObs * kMzTile <= kMzRedRows * kMzWaves * kMzTile && kMzRootObs <= kMzH, "the ROOTS stage's tiles fit RED and XS");
+    float *OBT = RED, *W0 = XS;
 
     // ---- once: weight fragments into registers (A operand of 16x16x4: lane holds W[unit 16w + n][k = 4s + q])
     // (the representation network's fragments -- 18 + 8 registers, used once per MOVE -- are fetched at the start of every
@@ -704,7 +746,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             EnvState c0;
             Env::load(c0, P.state + (long long)KS * g, P.steps[g], P.episode[g]);
             env_store(c0, P.ep_start[g]);
-        } else {
+        } else if (!ROOTS) {   // (ROOTS: the trees start in the launch)
             top = E.top[g];
             lo = E.vmin[g];
             hi = E.vmax[g];
@@ -712,7 +754,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             if (GUMBEL && lead && top != 1 + A) atomicOr(E.err, RZ_FLAG_INTERNAL);
         }
     }
-    if (TREE_LDS && !MOVES) {
+    if (TREE_LDS && !MOVES && !ROOTS) {
         for (int ee = 0; ee < gpw && g0 + ee < E.n_games; ++ee) {
             const MzNode *src = E.nodes + (long long)(g0 + ee) * E.cap;
             const int used = E.top[g0 + ee] < E.cap ? E.top[g0 + ee] : E.cap;
@@ -987,6 +1029,81 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             }
             MZ_TICK(13);
         }
+        if constexpr (ROOTS) {
+            // ---- the roots from raw observations (MzRoots, above): s0 = scale(rep2 relu(rep1 obs)) -> XS and hidden slot 0; f(s0) -> the roots
+            OBT[(tid >> 4) * kMzTile + n] =   // 256 threads = 16 features x 16 games: feature tid / 16 of game g0 + n
+                (tid >> 4) < R.obs_dim && live_n ? R.obs[(long long)(g0 + n) * R.obs_dim + (tid >> 4)] : 0.0f;
+            reinterpret_cast<float4 *>(W0)[tid] = reinterpret_cast<const float4 *>(R.rep1_w)[tid];   // (after the preamble's barrier: XS is zeroed)
+            if (tid < kMzTile) Gleaf[tid] = 0;
+            float arep2[kMzH / 4];
+            mz_f32x4 brep1, brep2;
+#pragma unroll
+            for (int s = 0; s < kMzH / 4; ++s) arep2[s] = R.rep2_w[(4 * s + q) * kMzH + unit];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                brep1[i] = R.rep1_b[16 * w + 4 * q + i];
+                brep2[i] = R.rep2_b[16 * w + 4 * q + i];
+            }
+            __syncthreads();
+            {
+                float arep1[kMzRootObs / 4];
+#pragma unroll
+                for (int s = 0; s < kMzRootObs / 4; ++s) arep1[s] = W0[(4 * s + q) * kMzH + unit];
+                const mz_f32x4 h = mz_tile(arep1, OBT, q, n, brep1);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) HP[(16 * w + 4 * q + i) * kMzTile + n] = fmaxf(h[i], 0.0f);
+            }
+            __syncthreads();
+            const mz_f32x4 t0 = mz_tile(arep2, HP, q, n, brep2);
+            wave_extremes(t0);
+            __syncthreads();
+            scale_and_store(t0);
+            __syncthreads();
+            predict_partials();
+            __syncthreads();
+            if (w == 0) {
+                float value, probs[MAXA];
+                finish_prediction(value, probs);
+                if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);   // (as any other node's)
+                if (mine) {
+                    if (lead) {
+#pragma unroll
+                        for (int a = 0; a < MAXA; ++a)
+                            if (a < A && R.root_probs != nullptr) R.root_probs[(long long)g * A + a] = probs[a];
+                        if (T.reward != nullptr) {   // row 0 of the trace: the root (no edge leads to it)
+                            T.parent[g] = -1;
+                            T.action[g] = -1;
+                            T.leaf[g] = 0;
+                            T.reward[g] = 0.0f;
+                            T.value[g] = value;
+#pragma unroll
+                            for (int a = 0; a < MAXA; ++a)
+                                if (a < A) T.probs[(long long)g * A + a] = probs[a];
+                        }
+                    }
+                    // expand_node(root) + add_exploration_noise with k_mz_init's rule (rz_mz_roots.h); an LDS tree takes the record as
+                    // the preamble of the other instantiations would have read it from HBM
+                    auto put = [&](int slot, const MzNode &nd) {
+                        if (TREE_LDS) {
+                            hot[slot] = MzHot{nd.N, nd.first_child, nd.value_sum, nd.prior, 0.0};
+                            rew[slot] = nd.reward;
+                        } else {
+                            nodes[slot] = nd;
+                        }
+                    };
+                    const double *noise_row = R.noise != nullptr ? R.noise + (long long)g * A : nullptr;
+                    put(0, mz_root_record());
+#pragma unroll
+                    for (int a = 0; a < MAXA; ++a)
+                        if (a < A) put(1 + a, mz_root_child(mz_root_prior(probs[a], noise_row, a, R.noise_frac)));
+                    const MzRootStart start = mz_root_start(A);
+                    top = start.top;
+                    depth = start.depth;
+                    lo = start.lo;
+                    hi = start.hi;
+                }
+            }
+        }
         // (GUMBEL) the quad of a game is live: the gathers below run in the quad layout whichever lanes walk
         const bool live_quad = GUMBEL ? ge < gpw && g0 + ge < E.n_games : mine;
         float gum0 = 0.0f, gum1 = 0.0f;   // (GUMBEL) the Gumbel draws of the lane's two actions
@@ -1055,14 +1172,17 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                 }
                 if (ca == 0) Gact[ge] = mine ? act : 0;
             } else {
+                // (ROOTS: every game's parent in simulation 0 is its root, whose state the ROOTS stage left in XS)
+                if (!(ROOTS && sim == 0)) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int c = (l & 3) + 4 * j;
-                    const float4 v = live_e ? src[c] : float4{0.0f, 0.0f, 0.0f, 0.0f};
-                    XS[(4 * c + 0) * kMzTile + ee] = v.x;
-                    XS[(4 * c + 1) * kMzTile + ee] = v.y;
-                    XS[(4 * c + 2) * kMzTile + ee] = v.z;
-                    XS[(4 * c + 3) * kMzTile + ee] = v.w;
+                    for (int j = 0; j < 4; ++j) {
+                        const int c = (l & 3) + 4 * j;
+                        const float4 v = live_e ? src[c] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+                        XS[(4 * c + 0) * kMzTile + ee] = v.x;
+                        XS[(4 * c + 1) * kMzTile + ee] = v.y;
+                        XS[(4 * c + 2) * kMzTile + ee] = v.z;
+                        XS[(4 * c + 3) * kMzTile + ee] = v.w;
+                    }
                 }
                 const int an = GUMBEL ? act : __shfl(act, 4 * n);
 #pragma unroll
@@ -1159,7 +1279,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             MZ_TICK(11);
             if (mine) {
                 if (!MOVES && lead && T.reward != nullptr) {
-                    const long long o = (long long)sim * E.n_games + g;
+                    const long long o = (long long)(sim + (ROOTS ? 1 : 0)) * E.n_games + g;   // (ROOTS: row 0 is the root's)
                     T.parent[o] = par;
                     T.action[o] = act;
                     T.leaf[o] = lf;

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "rz_muzero_tree.h"
+#include "rz_mz_roots.h"
 
 #pragma clang fp contract(off)
 
@@ -20,16 +21,15 @@ __global__ void k_mz_init(MzDev E, const float *probs, const double *noise, doub
     if (g >= E.n_games) return;
     if (mask != nullptr && !mask[g]) return;
     const long long base = (long long)g * E.cap;
-    E.nodes[base] = MzNode{0, 1, 0.0, 0.0, 0.0f, 0};
-    for (int a = 0; a < E.n_actions; ++a) {
-        double p = (double)probs[(long long)g * E.n_actions + a];
-        if (noise != nullptr) p = p * (1.0 - frac) + noise[(long long)g * E.n_actions + a] * frac;
-        E.nodes[base + 1 + a] = MzNode{0, -1, 0.0, p, 0.0f, 0};
-    }
-    E.top[g] = 1 + E.n_actions;
-    E.vmin[g] = INFINITY;   // MinMaxStats(): minimum = +MAX, maximum = -MAX
-    E.vmax[g] = -INFINITY;
-    E.depth[g] = 0;
+    const double *noise_row = noise != nullptr ? noise + (long long)g * E.n_actions : nullptr;
+    E.nodes[base] = mz_root_record();   // (the rule: rz_mz_roots.h -- the search that starts from observations calls it too)
+    for (int a = 0; a < E.n_actions; ++a)
+        E.nodes[base + 1 + a] = mz_root_child(mz_root_prior(probs[(long long)g * E.n_actions + a], noise_row, a, frac));
+    const MzRootStart start = mz_root_start(E.n_actions);
+    E.top[g] = start.top;
+    E.vmin[g] = start.lo;
+    E.vmax[g] = start.hi;
+    E.depth[g] = start.depth;
 }
 
 __global__ void k_mz_select(MzDev E, int32_t *parent, int32_t *action, int32_t *leaf, const uint8_t *mask) {

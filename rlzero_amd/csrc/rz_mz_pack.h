@@ -1,4 +1,4 @@
-// rz_mz_pack.h -- what rz_mz_load_model and rz_mz_load_representation compute on the host between their argument checks and their upload:
+// rz_mz_pack.h -- what rz_mz_load_model, rz_mz_load_representation and rz_mz_load_root_model compute on the host between their argument checks and their upload:
 // the weights of the MuZero network (rlzero_amd/muzero/network.py, hidden size 64) in the layouts k_mz_search reads (rz_muzero_search.h),
 // the power-of-two scales of the f16 layers of whole moves, the bound on relu(dyn1) that gives their activation scale, and the verdict
 // whether whole moves may run at all.  Pure CPU arithmetic, no HIP: plain C++17, included by rz_muzero.hip (through the headers that
@@ -147,6 +147,25 @@ struct Representation {
 
 inline Representation pack_representation(const float *const *p, int obs_dim) {
     Representation r = {{}, {0, (size_t)kMzObs * kMzH, (size_t)kMzObs * kMzH + kMzH, (size_t)kMzObs * kMzH + kMzH + (size_t)kMzH * kMzH}};
+    r.host.assign(r.off[3] + kMzH, 0.0f);
+    for (int o = 0; o < kMzH; ++o) {
+        for (int k = 0; k < obs_dim; ++k) r.host[r.off[0] + (size_t)k * kMzH + o] = p[0][(size_t)o * obs_dim + k];
+        for (int k = 0; k < kMzH; ++k) r.host[r.off[2] + (size_t)k * kMzH + o] = p[2][(size_t)o * kMzH + k];
+        r.host[r.off[1] + o] = p[1][o];
+        r.host[r.off[3] + o] = p[3][o];
+    }
+    return r;
+}
+
+// rz_mz_load_root_model's upload: the representation network for the search that starts from raw observations (k_mz_search's ROOTS
+// stage, rz_muzero_search.h), 1 <= obs_dim <= kMzRootObs features.  From the same four tensors as pack_representation:
+// off[0] rep1.w k-major as [kMzRootObs][H], w[k][unit] = torch w[unit][k], rows obs_dim .. kMzRootObs - 1 zero (the stage multiplies a
+// tile padded to 16 features, four K steps of the 16x16x4 MFMA; the padding columns of the observation tile are zero as well);
+// off[1] rep1.b; off[2] rep2.w k-major [H][H]; off[3] rep2.b.  No padding between the pieces: each is a multiple of 4 floats.
+constexpr int kMzRootObs = 16;
+
+inline Representation pack_root_model(const float *const *p, int obs_dim) {
+    Representation r = {{}, {0, (size_t)kMzRootObs * kMzH, (size_t)kMzRootObs * kMzH + kMzH, (size_t)kMzRootObs * kMzH + kMzH + (size_t)kMzH * kMzH}};
     r.host.assign(r.off[3] + kMzH, 0.0f);
     for (int o = 0; o < kMzH; ++o) {
         for (int k = 0; k < obs_dim; ++k) r.host[r.off[0] + (size_t)k * kMzH + o] = p[0][(size_t)o * obs_dim + k];

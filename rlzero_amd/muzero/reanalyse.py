@@ -53,7 +53,11 @@ def mz_reanalyse_draws(seed, step, n, lengths):
 class MuZeroReanalyser(object):
     """Fresh searches of steps held by ``replay`` (a MuZeroDeviceReplay) with ``net`` as it is now.  ``fused``: the search of a
     chunk in one launch (k_mz_search); None = whenever the model fits it (hidden size 64, <= 8 actions), as MuZeroSelfPlay
-    decides -- the weights are uploaded again whenever the torch parameters changed.  ``timer``: None, or a callable
+    decides -- the weights are uploaded again whenever the torch parameters changed; 'observations' = the chunk's whole search from
+    its stored observations in one launch (``MuZeroTree.search_from_obs``: representation, root prediction, softmax, roots and
+    simulations; no ``initial_inference`` in PyTorch), for a net of hidden size 64, <= 8 actions, <= 16 observation features and scalar
+    heads -- a ValueError names what it does not serve.  What is written back is bit for bit what ``search_from_obs`` gives for the
+    stored observation; against the other routes the root state differs in the last bits (another summation order).  ``timer``: None, or a callable
     ``timer(label)`` called on the stream between the stages of every chunk (profiles/ab_mz_reanalyse.py records events there)."""
 
     def __init__(self, net, replay, n_sims=50, batch=256, discount=0.997, pb_c_base=19652.0, pb_c_init=1.25, fused=None, seed=0):
@@ -72,6 +76,17 @@ class MuZeroReanalyser(object):
             raise ValueError('batch and n_sims must be positive')
         self.seed = int(seed)
         self.step = 0   # the next refresh ``reanalyse_sample`` draws without a ``step``
+        # fused='observations': a chunk's whole search -- initial inference, roots, simulations -- in ONE launch (search_from_obs)
+        self.from_obs = isinstance(fused, str)
+        if self.from_obs:
+            if fused != 'observations':
+                raise ValueError("fused: None, True, False or 'observations', not %r" % (fused, ))
+            for bad, why in ((net.hidden != 64, 'hidden size %d (it is built for 64)' % net.hidden),
+                             (self.n_actions > 8, '%d actions (at most 8)' % self.n_actions),
+                             (self.obs_dim > MuZeroTree.MAX_ROOT_OBS, '%d observation features (at most %d)' % (self.obs_dim, MuZeroTree.MAX_ROOT_OBS)),
+                             (getattr(net, 'support', None) is not None, 'categorical heads (support=%s): it keeps scalar heads' % getattr(net, 'support', None))):
+                if bad:
+                    raise ValueError("fused='observations' does not serve %s" % why)
         self.fused = (net.hidden == 64 and self.n_actions <= 8) if fused is None else bool(fused)
         self.tree = MuZeroTree(self.batch, self.n_actions, self.n_sims, discount, pb_c_base, pb_c_init, device=str(self.device))
         # the net's flag (MuZeroNet(value_transform=True)): the search inverts the heads, so what is written back is a RAW root value
@@ -104,6 +119,8 @@ class MuZeroReanalyser(object):
         seen = tuple((p.data_ptr(), p._version) for p in self.net.parameters())
         if seen != self._model_seen:
             self.tree.load_model(self.net)
+            if self.from_obs:
+                self.tree.load_root_model(self.net)
             self._model_seen = seen
 
     def _mark(self, label):
@@ -136,12 +153,16 @@ class MuZeroReanalyser(object):
             self._where[m:] = -1
             where, obs = self._where, self._obs
         with t.no_grad():
-            s0, logits, _ = self.net.initial_inference(obs)
-            probs = t.softmax(logits, dim=1).contiguous()
-            self.hidden[:, 0] = s0
-            self._mark('inference')
-            tree.init_roots(probs, None)
-            self._search()
+            if self.from_obs:   # positions -> one launch -> read-out -> update
+                self._refresh_model()
+                tree.search_from_obs(obs.contiguous(), self.hidden, self.n_sims)   # (a full chunk: rows of the request, contiguous already)
+            else:
+                s0, logits, _ = self.net.initial_inference(obs)
+                probs = t.softmax(logits, dim=1).contiguous()
+                self.hidden[:, 0] = s0
+                self._mark('inference')
+                tree.init_roots(probs, None)
+                self._search()
             self._mark('search')
             visits = tree.root_visits()
             root_n, root_sum, _, _ = tree.root_stats()

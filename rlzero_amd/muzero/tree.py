@@ -211,6 +211,42 @@ class MuZeroTree(object):
         check(self.lib.rz_mz_search(self.handle, _ptr(hidden), int(n_sims), *args, self.stream()), 'rz_mz_search')
         return out
 
+    MAX_ROOT_OBS = 16   # csrc/rz_mz_pack.h: kMzRootObs
+
+    def load_root_model(self, net):
+        """Upload the representation layers h(o) of a MuZeroNet (hidden size 64, obs_dim <= 16) for ``search_from_obs``
+        (rz_mz_load_root_model: storage of its own, apart from ``load_representation``'s); call again after every optimiser step,
+        beside ``load_model``."""
+        sd = net.state_dict()
+        arrays = [sd[name].detach().to('cpu', self.torch.float32).contiguous().numpy() for name in self.REPRESENTATION_PARAMS]
+        ptrs = (ctypes.c_void_p * 4)(*[a.ctypes.data for a in arrays])
+        check(self.lib.rz_mz_load_root_model(self.handle, ptrs, 4, int(net.obs_dim), int(net.hidden)), 'rz_mz_load_root_model')
+        self.root_obs_dim = int(net.obs_dim)
+
+    def search_from_obs(self, obs, hidden, n_sims, noise=None, noise_frac=0.0, root_probs=None, trace=False):
+        """A whole search from raw observations in ONE launch (rz_mz_search_obs; k_mz_search's ROOTS instantiations): the
+        representation and the root prediction of ``net.initial_inference``, the float32 softmax, the root state into ``hidden[:, 0]``,
+        the roots as ``init_roots(probs, noise, noise_frac)`` makes them -- bit for bit -- and ``n_sims`` simulations, in place of
+        ``initial_inference`` + ``init_roots`` + ``search_fused`` (``load_model`` and ``load_root_model`` first).  ``obs`` float32
+        [G, obs_dim] on the device; ``noise`` float64 [G, A] or None; ``root_probs`` float32 [G, A] or None: receives the softmax rows.
+        ``trace``: -> ``search_fused``'s dict with ONE ROW MORE, [n_sims + 1, G]: row 0 is the root's (parent -1, action -1, leaf 0,
+        reward 0, its probabilities and its predicted value, raw under the value transform), row 1 + s simulation s.  pUCT with scalar
+        heads only: the library refuses -- HipError, nothing launched -- a tree with the Gumbel search on or a support set."""
+        t, G, A = self.torch, self.n_games, self.n_actions
+        D = getattr(self, 'root_obs_dim', None)
+        if D is None:
+            raise _hip.HipError('search_from_obs: load_root_model first')
+        for name, x, dtype, shape in (('obs', obs, t.float32, (G, D)), ('noise', noise, t.float64, (G, A)), ('root_probs', root_probs, t.float32, (G, A))):
+            if x is not None and (x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous() or x.device.type != 'cuda'):
+                raise ValueError('search_from_obs: %s must be a contiguous %s %s tensor on the device' % (name, dtype, list(shape)))
+        if hidden.dtype != t.float32 or hidden.numel() < G * self.slots_per_game * 64 or not hidden.is_contiguous():
+            raise ValueError('search_from_obs: hidden must be a contiguous float32 [n_games, slots_per_game, 64] tensor')
+        out, args = self._trace(int(n_sims) + 1, trace)
+        check(self.lib.rz_mz_search_obs(self.handle, _ptr(obs), _ptr(hidden), int(n_sims), _ptr(noise) if noise is not None else None,
+                                        float(noise_frac), _ptr(root_probs) if root_probs is not None else None, *args, self.stream()),
+              'rz_mz_search_obs')
+        return out
+
     def set_gumbel(self, max_considered=4, c_visit=50.0, c_scale=1.0):
         """Gumbel MuZero's rule for ``search_gumbel`` (rz_mz_set_gumbel; csrc/rz_mz_gumbel.h): a Gumbel top-m draw at the root, m =
         min(max_considered, A), Sequential Halving of the tree's ``n_sims`` simulations over it (``gumbel.considered_visits``, uploaded
@@ -314,9 +350,10 @@ class MuZeroTree(object):
         """What a launch of ``search_fused`` (``whole_moves`` false) or ``play_env`` / ``play_cartpole`` (true; for this tree's action
         count) would be for the current shape
         (``set_search_shape``), from the host function the launch itself uses -> dict games_per_workgroup, tree_in_lds (bool),
-        lds_bytes."""
+        lds_bytes.  ``whole_moves='observations'``: the launch of ``search_from_obs`` (the plan of ``search_fused`` with pUCT and scalar heads)."""
         gpw, in_lds, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        check(self.lib.rz_mz_search_plan(self.handle, 1 if whole_moves else 0, ctypes.byref(gpw), ctypes.byref(in_lds),
+        which = 2 if isinstance(whole_moves, str) and whole_moves == 'observations' else 1 if whole_moves else 0
+        check(self.lib.rz_mz_search_plan(self.handle, which, ctypes.byref(gpw), ctypes.byref(in_lds),
                                          ctypes.byref(lds)), 'rz_mz_search_plan')
         return {'games_per_workgroup': gpw.value, 'tree_in_lds': bool(in_lds.value), 'lds_bytes': lds.value}
 

@@ -24,6 +24,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+REANALYSE_ROUTES = ('torch', 'observations')
+ROUTE_NEEDS_REANALYSE = '--reanalyse-route needs --reanalyse: it chooses how the stored steps are searched again'
 NEEDS_DEVICE_REPLAY = '--reanalyse needs --device-replay: the steps are searched again and refreshed where they are stored, on the GPU'
 ENVIRONMENTS = ('cartpole', 'acrobot')
 EVAL_SEED = 20191119   # the evaluation environments' seed: every evaluation of every run starts from the same states
@@ -48,7 +50,7 @@ class MuZeroPipeline(object):
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
                  reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False, env='cartpole',
                  max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None, search='puct', gumbel_considered=4,
-                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None):
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None, reanalyse_route='torch'):
         """``support`` (needs ``value_transform``): the half-width S of the categorical support of the reward and value heads
         (``MuZeroNet(support=S)``: 2 S + 1 bins, cross-entropy against two-hot targets in either learner, the expectation read
         inside the search kernel).  Refused with a ValueError together with ``whole_moves``.  None: scalar heads.
@@ -57,6 +59,8 @@ class MuZeroPipeline(object):
         ``reanalyse`` (needs ``device_replay``): before the updates of an iteration that many stored steps, drawn on the device
         (or, 'all', every step held), are searched again with the current network and their policy and root value refreshed
         (MuZeroReanalyser: a second, small search object; the self-play object and its counters are not touched).  0: off.
+        ``reanalyse_route`` (needs ``reanalyse``): 'torch' (the default: initial inference in PyTorch, then the search) or 'observations'
+        (MuZeroReanalyser(fused='observations'): a chunk's search from its stored observations in one launch).
         ``prioritized_replay`` (needs ``device_replay``): mini-batches are drawn in proportion to |search value - n-step return|
         of the stored steps (MuZeroDeviceReplay.sample_prioritized) and the loss of an entry is scaled by its importance weight
         (1 / (N P)) ** ``priority_beta``; a Reanalyse moves the priorities with the root values it rewrites.
@@ -86,6 +90,10 @@ class MuZeroPipeline(object):
         self.reanalyse = reanalyse if reanalyse == 'all' else int(reanalyse or 0)
         if self.reanalyse and not device_replay:
             raise ValueError(NEEDS_DEVICE_REPLAY)
+        if reanalyse_route not in REANALYSE_ROUTES:
+            raise ValueError('unknown reanalyse route %r (known: %s)' % (reanalyse_route, ', '.join(REANALYSE_ROUTES)))
+        if reanalyse_route != 'torch' and not self.reanalyse:
+            raise ValueError(ROUTE_NEEDS_REANALYSE)
         from rlzero_amd.muzero import (AcrobotBatch, CartPoleBatch, MuZeroAgent, MuZeroDeviceReplay, MuZeroReanalyser, MuZeroSelfPlay,
                                        ReplayBuffer)
         env_class = {'cartpole': CartPoleBatch, 'acrobot': AcrobotBatch}[env]
@@ -123,7 +131,8 @@ class MuZeroPipeline(object):
         check_value_transform(self.agent.net, self.buffer)
         self.reanalyser = None
         if self.reanalyse:
-            self.reanalyser = MuZeroReanalyser(self.agent.net, self.buffer, n_sims=n_sims, batch=reanalyse_batch, discount=discount, seed=seed)
+            self.reanalyser = MuZeroReanalyser(self.agent.net, self.buffer, n_sims=n_sims, batch=reanalyse_batch, discount=discount, seed=seed,
+                                               **(dict(fused='observations') if reanalyse_route == 'observations' else {}))
         self.batch_size = batch_size
         self.moves_per_iteration = moves_per_iteration
         self.updates_per_iteration = updates_per_iteration
@@ -289,6 +298,9 @@ def build_parser():
     ap.add_argument('--reanalyse', type=reanalyse_arg, default=0, metavar='N|all',
                     help='per iteration, search N stored steps (or all of them) again with the current network and refresh their targets '
                          '(needs --device-replay; 0 = off)')
+    ap.add_argument('--reanalyse-route', choices=REANALYSE_ROUTES, default='torch',
+                    help='how --reanalyse starts a search: the initial inference in PyTorch in front of the search launch, or the whole '
+                         'search from the stored observations in one launch (hidden size 64, <= 16 observation features, scalar heads)')
     ap.add_argument('--prioritized-replay', action='store_true',
                     help='draw mini-batches in proportion to |search value - n-step return| of the stored steps and scale the loss by the '
                          'importance weights (needs --device-replay)')
@@ -319,6 +331,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.reanalyse and not args.device_replay:
         ap.error(NEEDS_DEVICE_REPLAY)
+    if args.reanalyse_route != 'torch' and not args.reanalyse:
+        ap.error(ROUTE_NEEDS_REANALYSE)
     if args.prioritized_replay and not args.device_replay:
         ap.error(PRIORITIES_NEED_DEVICE_REPLAY)
     if args.support is not None and not args.value_transform:
@@ -329,7 +343,7 @@ def main(argv=None):
                           env=args.env, max_episode_steps=args.max_episode_steps, whole_moves=True if args.whole_moves else None,
                           value_transform=args.value_transform, eval_envs=args.eval_envs, search=args.search,
                           gumbel_considered=args.gumbel_considered, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
-                          support=args.support)
+                          support=args.support, reanalyse_route=args.reanalyse_route)
     pipe.run(args.iterations, eval_every=args.eval_every)
     if args.save:
         pipe.agent.save_model(args.save)
