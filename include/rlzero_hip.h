@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 52
+#define RZ_ABI_VERSION 53
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -765,9 +765,15 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
  * of the switch synchronises and drops the bases; call it before rz_net_delta_reserve to never reserve it).  Where the memory cannot be
  * had the search runs without the memo; the base cache does not fail for it.  Default: on.  A leaf served from the memo counts, in
  * rz_net_delta_stats, among the leaves against a base with the tiles its passes WOULD have run (the counters of the routes stay equal).
- * rz_net_delta_memo_stats (synchronises): {leaves served from the memo, entries filled} since the last rz_net_delta_stats(reset). */
+ * ONE WINDOW (ABI 53).  A far pair with exactly ONE of its two entries there runs the passes over the missing stone's window alone and
+ * takes the other stone's 7 x 7 from its entry (rz_memo.h: served -- what the one-window pass takes from the base lies 3 or more cells
+ * from the served stone): the same bits again.  Such a leaf is not "served from the memo", fills the missing entry as before and
+ * counts the tiles of the two-window pass.  on = 2 is a DIAGNOSTIC: the memo without the one-window route (ABI 48's behaviour, for an
+ * A / B inside one library); it is read when a launch is enqueued -- set it before a graph is captured -- and drops nothing.
+ * rz_net_delta_memo_stats (synchronises): h_out4 = {leaves served from the memo, entries filled, leaves that ran one window, 0} since
+ * the last rz_net_delta_stats(reset) (four words since ABI 53, two before). */
 int rz_net_delta_memo(rz_net *net, int32_t on);
-int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out2);
+int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out4);
 /* RESIDENT SEARCH -- n_sims consecutive simulations of every active game of `engine` (AlphaZeroMCTS.simulate's loop,
  * alphazero_mcts.py:82-85) in ONE launch, one workgroup per game: trunk -> value head -> expand / backup -> next selection without
  * a kernel boundary, the leaf handed from the tree code to the trunk through LDS.  Kernels that hold a whole CU (151 KB of LDS: boards

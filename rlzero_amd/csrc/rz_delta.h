@@ -116,7 +116,8 @@ struct DeltaArgs {
     float *feat32;           // the features as f32 [board][6 S] (tests; NULL otherwise)
     unsigned *stats;         // [kStats] counters (NULL: none): delta leaves, leaves without a base, conv3 tiles, changed cells, conv2 tiles, root scans
                              // answered from the pre-scan (k_delta_res), and of workgroup 0 of the LAST resident launch: shader-clock
-                             // cycles >> 8, ticks of the constant 100 MHz clock; [8], [9]: leaves served from the memo, entries filled
+                             // cycles >> 8, ticks of the constant 100 MHz clock; [8], [9]: leaves served from the memo, entries filled;
+                             // [10]: leaves that ran ONE window and took the other from the memo
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
@@ -126,6 +127,7 @@ struct DeltaArgs {
 struct MemoArgs {
     char *memo;              // [games][2 S entries] (NULL: off, every leaf runs its passes)
     uint64_t *bits;          // [games][rzm::kBitmapWords] the valid bits (k_memo_clear in front of every mode-1 launch)
+    int half;                // a far pair with exactly one valid entry runs the missing stone's window alone (rz_memo.h: served); 0: both
 };
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -1091,8 +1093,9 @@ __device__ __forceinline__ void windows_store(uint64_t row, bool use_delta, int 
 }
 static_assert(kWinLds >= kWinSets * 12 + 8, "the verdict and the memo's word");
 // the memo's word of a leaf: a far pair (rzm::far_pair) | served from the memo << 1 | entry (a, OWN) to be filled << 2 | entry
-// (b, OPP_LAST) to be filled << 3 | a << 8 | b << 16
-constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8;
+// (b, OPP_LAST) to be filled << 3 | a's window served, b's alone run << 4 | b's served, a's alone run << 5 | a << 8 | b << 16
+// (the two serve bits: rzm::served of a leaf with exactly one valid entry; a hit has neither)
+constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8, kMemoServeA = 16, kMemoServeB = 32;
 __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
                                              int lane, uint64_t *ws) {
     uint64_t ls[8];
@@ -1171,7 +1174,7 @@ struct ResHook {
     // asked for with the cell's rows (LDS: mbits, all zero without a memo), every level its read, none under a branch; leaf() tests
     // the two bits.
     const uint64_t *mbits;
-    bool memo_on;
+    bool memo_on, half_on;
     int bw_rcp, BW, c0, c1;
     uint64_t mw0, mw1;
     __device__ __forceinline__ void cell(int level, int c, int lane) {
@@ -1187,7 +1190,9 @@ struct ResHook {
         const int ay = (a * bw_rcp) >> 16, ax = a - ay * BW, by = (b * bw_rcp) >> 16, bx = b - by * BW;
         const bool far = memo_on && rzm::far_pair_yx(d, base_ok, ay, ax, by, bx);
         const bool va = (uni64(mw0) >> (a & 63)) & 1ull, vb = (uni64(mw1) >> (b & 63)) & 1ull;
-        return far ? kMemoFar | (va && vb ? kMemoHit : 0) | (va ? 0 : kMemoFillA) | (vb ? 0 : kMemoFillB) | (a << 8) | (b << 16) : 0;
+        // (exactly one entry valid: that window is served, the other stone's alone is run -- rzm::served)
+        const int serve = half_on && va != vb ? (va ? kMemoServeA : kMemoServeB) : 0;
+        return far ? kMemoFar | (va && vb ? kMemoHit : 0) | (va ? 0 : kMemoFillA) | (vb ? 0 : kMemoFillB) | serve | (a << 8) | (b << 16) : 0;
     }
     // Behind the descent (select_body calls it once, whichever way the descent ended): the leaf to LDS, the hand-over of its windows --
     // the rows were requested during the descent, and the verdict is changed_cells' without the leaf: against a base that is the root
@@ -1206,9 +1211,12 @@ struct ResHook {
             reinterpret_cast<int *>(leaf_lds + 2 * rzt::kWords)[0] = to_move;
             reinterpret_cast<int *>(leaf_lds + 2 * rzt::kWords)[1] = last;
         }
-        const bool mine = d == 0 ? (lane < 16 && any0) : (lane >> 4) < d;
+        // (a served window's rows are dropped from the sets -- lanes 0 .. 15 hold a's, 16 .. 31 b's --; nD stays the path's length)
+        const int mw = memo_word(d);
+        const int dropped = (mw & kMemoServeA) ? 0 : (mw & kMemoServeB) ? 1 : -1;
+        const bool mine = (d == 0 ? (lane < 16 && any0) : (lane >> 4) < d) && (lane >> 4) != dropped;
         const int nD = d == 0 ? (any0 ? 1 : 0) : d;
-        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, memo_word(d));
+        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, mw);
         if (release) __syncthreads();
 #ifdef RZ_NET_PROFILE
         {   // -> net_prof[18]: the selection up to the release
@@ -1311,7 +1319,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     char *const memo_g = memo_on ? mm.memo + (size_t)game * (size_t)rzm::game_bytes(nd.S) : nullptr;   // (neither is formed, let alone read, without a memo)
     uint64_t *const memo_bits_g = memo_on ? mm.bits + (size_t)game * rzm::kBitmapWords : nullptr;
     if (tid0 < rzm::kBitmapWords) res_mbits[tid0] = memo_on ? memo_bits_g[tid0] : 0ull;
-    int memo_hits = 0, memo_fills = 0;
+    int memo_hits = 0, memo_fills = 0, memo_half = 0;
     bool head_stored = false;   // (the head weights go to LDS in the first leaf that runs its passes)
     if (tid0 == 0) res_pre.scan = res_pre.valid = res_pre.answered = 0;   // (no stash yet: a select_first == 0 launch's first selection was not made here)
     ResHook hook;
@@ -1326,6 +1334,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     hook.release = false;   // (the first selection: every wave meets the barrier behind it)
     hook.mbits = res_mbits;
     hook.memo_on = memo_on;
+    hook.half_on = memo_on && mm.half != 0;
     hook.bw_rcp = da.bw_rcp, hook.BW = BW;
     hook.c0 = hook.c1 = 0;
     hook.mw0 = hook.mw1 = 0ull;
@@ -1416,18 +1425,45 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
             // a far pair that ran its passes leaves the windows the memo does not hold yet: the threads within 3 of a / of b store the
             // two values they have just put into the value row, the valid bits follow behind the stores (LDS: this wave 0 tests them;
             // memory: a later launch's copy).  Only this workgroup ever reads its game's memo, the next reader is barriers away.
+            // ONE WINDOW (a serve bit in the memo's word: the passes above ran the missing stone's window alone, the sets held no row
+            // of the other stone, so the value row has the base's values around it): the threads within 3 of the SERVED stone overwrite
+            // their two entries of the value row from its memo entry -- the hit branch's two unconditional loads at a selected address,
+            // every other thread reads the base's planes and drops what it read.  The counters see the tiles of the two-window pass:
+            // the served stone's radius-2 / radius-3 rows of the window table are counted here, behind the passes (windows of radius
+            // <= 3 of a far pair are disjoint: the counts add).
             if (!POL && (memo_w & (kMemoFillA | kMemoFillB)) && use_delta) {
                 const int a = (memo_w >> 8) & 255, b = (memo_w >> 16) & 255, S = nd.S;
                 const int ay = (a * da.bw_rcp) >> 16, ax = a - ay * BW, by = (b * da.bw_rcp) >> 16, bx = b - by * BW;
                 const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
                 int slot;
                 const int src = rzm::source_of_yx(cy, cx, ay, ax, by, bx, &slot);
-                const bool fill = tid_s < S && ((src == rzm::kFromA && (memo_w & kMemoFillA)) || (src == rzm::kFromB && (memo_w & kMemoFillB)));
+                const bool in_a = src == rzm::kFromA, in_win = tid_s < S && src != rzm::kFromBase;
+                const bool fill = in_win && (memo_w & (in_a ? kMemoFillA : kMemoFillB));
+                const bool take = in_win && (memo_w & (in_a ? kMemoServeA : kMemoServeB));
+                const int e = rzm::entry_index(in_a ? rzm::kOwn : rzm::kOppLast, in_a ? a : b, S);
+                float *pm = reinterpret_cast<float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot < 0 ? 0 : slot, 0));
+                const float *pb = reinterpret_cast<const float *>(leaf.base + kBaseV) + 4 * kCells + tid_s;
+                const float *p = take ? pm : pb;
+                const float m4 = p[0], m5 = p[take ? 1 : kCells];
+                if (take) {
+                    res_vrow[tid_s] = m4;
+                    res_vrow[S + tid_s] = m5;
+                }
                 if (fill) {
-                    const int e = rzm::entry_index(src == rzm::kFromA ? rzm::kOwn : rzm::kOppLast, src == rzm::kFromA ? a : b, S);
-                    float *pm = reinterpret_cast<float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot, 0));
                     pm[0] = res_vrow[tid_s];
                     pm[1] = res_vrow[S + tid_s];
+                }
+                if (memo_w & (kMemoServeA | kMemoServeB)) {   // (uniform)
+                    const uint64_t *wr = da.win + ((memo_w & kMemoServeA) ? a : b) * kWinSets;
+                    const int *cnt = reinterpret_cast<const int *>(res_win + kWinSets);
+                    int t2 = 0, t3 = 0;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        t2 += __builtin_amdgcn_readfirstlane(cnt[4 * 1 + w]) + __popcll(wr[4 * 1 + w]);
+                        t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]) + __popcll(wr[4 * 2 + w]);
+                    }
+                    n_tiles = ((t3 + 15) >> 4) | (((t2 + 15) >> 4) << 16);
+                    memo_half += 1;
                 }
                 if (tid_s == 0) {
                     if (memo_w & kMemoFillA) {
@@ -1556,6 +1592,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         if (memo_on) {
             atomicAdd(da.stats + 8, (unsigned)memo_hits);
             atomicAdd(da.stats + 9, (unsigned)memo_fills);
+            atomicAdd(da.stats + 10, (unsigned)memo_half);
         }
         if (game == 0) {   // the clock this search ran at: cycles / (ticks x 10 ns)
             da.stats[6] = (unsigned)((__builtin_readcyclecounter() - clk0) >> 8);

@@ -74,6 +74,24 @@ RZM_FN bool hit(int depth, bool base_is_root, int a, int b, int BW, const uint64
     return far_pair(depth, base_is_root, a, b, BW) && valid_bit(bits, kOwn, a) && valid_bit(bits, kOppLast, b);
 }
 
+// ONE WINDOW.  A far pair with exactly one entry valid runs the missing stone's window alone and takes the other stone's from the memo.
+// `served`: the windows of a far pair that come from the memo, a set of kServeA (a's, entry (a, OWN)) and kServeB (b's, entry
+// (b, OPP_LAST)): none -- both windows are run (and every leaf that is no far pair) --, one of them, or both, which is `hit`.
+// Exactness of the pass around the missing stone, say a (b alike): with cheb(a, b) >= 7 every record the pass takes from the base
+// instead of computing it -- conv1's records within 3 of a for conv2, conv2's within 4 of a for conv3 -- lies at distance >= 3 from
+// b, and a conv1 / conv2 record depends on the input cells within 1 / 2 of its cell: none of them is b, so the base's record is the
+// leaf's record there.  What the pass computes itself (conv1 within 1, conv2 within 2, conv3 and the heads within 3 of a) reads
+// inputs within 3 of a, b is not among them either.  The radius-4 sets of the two stones may touch at distance 7 or 8: harmless for
+// the same reason, the shared cells' conv2 records are the base's in the leaf too.  b's 7 x 7 of value features is the entry's, by
+// the argument at the top; every other cell takes the base's value.  So each cell of the leaf has exactly one source (cell_source).
+constexpr int kServeNone = 0, kServeA = 1, kServeB = 2, kServeBoth = kServeA | kServeB;
+RZM_FN int served(int depth, bool base_is_root, int a, int b, int BW, const uint64_t *bits) {
+    if (!far_pair(depth, base_is_root, a, b, BW)) return kServeNone;
+    return (valid_bit(bits, kOwn, a) ? kServeA : 0) | (valid_bit(bits, kOppLast, b) ? kServeB : 0);
+}
+// the sources of a cell's value features in a leaf that serves the windows `srv`: the base's planes, a memo entry, the leaf's own pass
+constexpr int kSrcBase = 0, kSrcMemo = 1, kSrcRun = 2;
+
 // where cell (cy, cx) of a hit's leaf takes its value features from, and the window slot there (far pair: at most one window holds it)
 RZM_FN int source_of_yx(int cy, int cx, int ay, int ax, int by, int bx, int *slot) {
     const int sa = slot_of(cy, cx, ay, ax), sb = slot_of(cy, cx, by, bx);
@@ -82,6 +100,15 @@ RZM_FN int source_of_yx(int cy, int cx, int ay, int ax, int by, int bx, int *slo
 }
 RZM_FN int source_of(int cy, int cx, int a, int b, int BW, int *slot) {
     return source_of_yx(cy, cx, a / BW, a % BW, b / BW, b % BW, slot);
+}
+// cell (cy, cx) of a far pair's leaf that serves the windows `srv` (served): base, memo (window `*win` = kFromA / kFromB, slot `*slot`) or run
+RZM_FN int cell_source_yx(int cy, int cx, int ay, int ax, int by, int bx, int srv, int *win, int *slot) {
+    *win = source_of_yx(cy, cx, ay, ax, by, bx, slot);
+    if (*win == kFromBase) return kSrcBase;
+    return (srv & (*win == kFromA ? kServeA : kServeB)) ? kSrcMemo : kSrcRun;
+}
+RZM_FN int cell_source(int cy, int cx, int a, int b, int BW, int srv, int *win, int *slot) {
+    return cell_source_yx(cy, cx, a / BW, a % BW, b / BW, b % BW, srv, win, slot);
 }
 
 }  // namespace rzm
