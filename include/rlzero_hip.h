@@ -770,6 +770,11 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
  * from the served stone): the same bits again.  Such a leaf is not "served from the memo", fills the missing entry as before and
  * counts the tiles of the two-window pass.  on = 2 is a DIAGNOSTIC: the memo without the one-window route (ABI 48's behaviour, for an
  * A / B inside one library); it is read when a launch is enqueued -- set it before a graph is captured -- and drops nothing.
+ * THE TWIN.  on = 3: the pass that runs a's window alone (b's served) also runs the window of a foretold cell t -- the lowest cell empty
+ * at the root without an (t, OWN) entry, 7 or more from a and from b (rz_memo.h: twin_cell) -- and fills (t, OWN) too, so that the later
+ * leaf root + t + b' is served: the same bits, more leaves served.  The twin's entry counts among the entries filled; the pass counts
+ * its own leaf's tiles only.  on = 1 is the one-window route without twins; both are read when a launch is enqueued.  The fourth word
+ * of rz_net_delta_memo_stats, 0 under on = 0, 1 and 2 as it always was, counts the passes that ran a twin under on = 3.
  * rz_net_delta_memo_stats (synchronises): h_out4 = {leaves served from the memo, entries filled, leaves that ran one window, 0} since
  * the last rz_net_delta_stats(reset) (four words since ABI 53, two before). */
 int rz_net_delta_memo(rz_net *net, int32_t on);

@@ -8,7 +8,7 @@ is forced).
 The memo (rz_memo.h; --values only): the share of the timed search's leaves served from it and the entries filled (delta_stats), and
 the patch copy's cycles PER HIT -- slot 5 is ticked by a served leaf from the verdict to its two stores (and by conv1 of a pass without
 a base: the row is printed only when no leaf went without one), and the share that ran ONE window beside a served one.
-RZ_DELTA_MEMO=0 in the environment: the kernel without the memo; =2: the memo without the one-window route.
+RZ_DELTA_MEMO=0 in the environment: the kernel without the memo; =2: the memo without the one-window route; =1: without the twins.
 --backup-rows: the library was built with -DRZ_BKP_TICKS=1 (rz_delta.h): the slots of the selection's ticks 1 .. 3 hold the rows of expand +
 backup, slot 22 wave 1's conv2.
 """
@@ -73,8 +73,9 @@ for games in sizes:
     leaves = max(1, st['delta'] + st['no_base'])
     hits, fills = st.get('memo_hits', 0), st.get('memo_fills', 0)   # (a library from before the memo has neither)
     half = st.get('memo_half', 0)                                   # (one-window leaves: RZ_DELTA_MEMO=2 or a library from before them has none)
-    print('   memo: %d of %d leaves served (%.1f %%), %d ran one window (%.1f %%), %d entries filled (%.1f a game)' % (
-        hits, leaves, 100.0 * hits / leaves, half, 100.0 * half / leaves, fills, fills / games)
+    twins = st.get('memo_twins', 0)                                 # (passes that also ran a twin's window: RZ_DELTA_MEMO=3, the default)
+    print('   memo: %d of %d leaves served (%.1f %%), %d ran one window (%.1f %%), %d of them with a twin (%.1f %% of leaves), %d entries filled (%.1f a game)' % (
+        hits, leaves, 100.0 * hits / leaves, half, 100.0 * half / leaves, twins, 100.0 * twins / leaves, fills, fills / games)
           + ('; game 0, wave 0: patch copy %d cycles per hit (slot 5 / the launch\'s mean hits per game)' % (out[5] / (hits / games))
              if hits and st['no_base'] == 0 else ''), flush=True)
     eng.close(); ev.hip.close()

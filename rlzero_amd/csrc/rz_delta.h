@@ -94,9 +94,9 @@ static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's 
 // (radius 1 .. 4) as 4 x 4 words, their words' popcounts, the verdict (use_delta | parity << 1 | nD << 8)
 constexpr int kWinSets = rzw::kRadii * rzw::kWords, kWinLds = kWinSets * 8 + kWinSets * 4 + 16;
 // (k_delta_res' own arrays, exactly: 81 376 bytes with the 96-byte RootPre -- 544 below half a CU)
-constexpr int kResLds = kLdsBytes + 512 * 4 + 4 * 64 * 4 + (2 * RZ_BOARD_WORDS + 2) * 8 + kWinLds + (int)sizeof(rzt::RootPre) + rzm::kBitmapWords * 8;
+constexpr int kResLds = kLdsBytes + 512 * 4 + 4 * 64 * 4 + (2 * RZ_BOARD_WORDS + 2) * 8 + kWinLds + (int)sizeof(rzt::RootPre) + rzm::kBitmapWords * 8 + RZ_BOARD_WORDS * 8;
 static_assert(2 * kResLds <= 160 * 1024,
-              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan, the memo's valid bits)");
+              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan, the memo's valid bits, the root's empty cells)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
 
 // The base cache: per game a header (the stones the two bases were computed from) and per (game, parity) the records.
@@ -118,6 +118,7 @@ struct DeltaArgs {
                              // answered from the pre-scan (k_delta_res), and of workgroup 0 of the LAST resident launch: shader-clock
                              // cycles >> 8, ticks of the constant 100 MHz clock; [8], [9]: leaves served from the memo, entries filled;
                              // [10]: leaves that ran ONE window and took the other from the memo
+                             // [11]: one-window passes that ran a twin's window beside their own (rz_memo.h: twin_cell)
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
@@ -128,6 +129,7 @@ struct MemoArgs {
     char *memo;              // [games][2 S entries] (NULL: off, every leaf runs its passes)
     uint64_t *bits;          // [games][rzm::kBitmapWords] the valid bits (k_memo_clear in front of every mode-1 launch)
     int half;                // a far pair with exactly one valid entry runs the missing stone's window alone (rz_memo.h: served); 0: both
+    int twin;                // ... and the pass around a alone also runs and fills the window of a foretold cell (rz_memo.h: twin_cell); 0: not
 };
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -376,6 +378,7 @@ struct Leaf {
     float *vdst;              // the value head's input row (global memory, or LDS in the resident search)
     float *dst32;             // f32 features (tests; NULL otherwise)
     const uint64_t *sets;     // delta_passes<true>: pass -1's window sets, handed over in LDS (leaf_windows)
+    int twin;                 // delta_passes<true>, pass -1: the twin's cell, a stone of the side to move in the planes alone (rz_memo.h); -1: none
     uint16_t *gtab;           // delta_passes<true>: THIS wave's table of the base records it copies (rz_gather.h: rzg::Split<3>::kTabEntries entries of LDS)
     bool deferred, store_head;
 };
@@ -754,6 +757,15 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
                 uint64_t ls[8];
                 int tm, lc, nst;
                 leaf_from_lds(leaf.leaf_lds, ls, tm, lc, nst);
+                {   // the twin (rz_memo.h): a stone of the side to move -- a's side in a far pair -- in the planes of this pass, nowhere else
+                    const int tw = leaf.twin;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const uint64_t bit = tw >= 0 && (tw >> 6) == w ? 1ull << (tw & 63) : 0ull;
+                        ls[w] |= tm == 0 ? bit : 0ull;
+                        ls[4 + w] |= tm == 0 ? 0ull : bit;
+                    }
+                }
                 const int *cnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
                 int b0 = 0, b3 = 0;   // W1's / W3's cells in the words before this one
 #pragma unroll
@@ -1014,7 +1026,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
     if (mode != 1 && !deferred && feat16 != nullptr)   // rz_net_delta_trunk_engine: the FC GEMM's own tiles (policy and value K-steps), as trunk_rows_body writes them
         leaf.dst16 = feat16 + ((size_t)(board >> 5) * (nd.groups_act + nd.groups_val) * 1024 + (board & 31) * 16);
     leaf.dst32 = (mode != 1 && da.feat32 != nullptr) ? da.feat32 + (size_t)board * 6 * S : nullptr;
-    leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr;
+    leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr, leaf.twin = -1;
     leaf.deferred = deferred;
     leaf.store_head = true;
 
@@ -1095,7 +1107,8 @@ static_assert(kWinLds >= kWinSets * 12 + 8, "the verdict and the memo's word");
 // the memo's word of a leaf: a far pair (rzm::far_pair) | served from the memo << 1 | entry (a, OWN) to be filled << 2 | entry
 // (b, OPP_LAST) to be filled << 3 | a's window served, b's alone run << 4 | b's served, a's alone run << 5 | a << 8 | b << 16
 // (the two serve bits: rzm::served of a leaf with exactly one valid entry; a hit has neither)
-constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8, kMemoServeA = 16, kMemoServeB = 32;
+// the twin of a pass around a alone (rz_memo.h: twin_cell): its window is run and entry (t, OWN) filled << 6 | t << 24
+constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8, kMemoServeA = 16, kMemoServeB = 32, kMemoTwin = 64;
 __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
                                              int lane, uint64_t *ws) {
     uint64_t ls[8];
@@ -1204,6 +1217,25 @@ struct ResHook {
     // game, and the other waves would wait at the barrier for ever; k_delta_res returns on such a game before its first barrier)
     uint64_t *leaf_lds, *ws;
     bool base_ok, release;
+    // The twin (rz_memo.h: twin_cell) of a pass that runs a's window alone: the lowest cell that is empty at the root (LDS: emp),
+    // has no (t, OWN) bit and lies 7 or more from a and from b -- lane L tests cells L, 64 + L, 128 + L, 192 + L, four ballots; then the
+    // one request for the cell's window rows (lanes 16 .. 31, the served stone's).
+    const uint64_t *emp;
+    bool twin_on;
+    int S;
+    __device__ __forceinline__ int twin_of(int mw, int lane) const {
+        const int a = (mw >> 8) & 255, b = (mw >> 16) & 255;
+        const int ay = (a * bw_rcp) >> 16, ax = a - ay * BW, by = (b * bw_rcp) >> 16, bx = b - by * BW;
+        int t = -1;
+#pragma unroll
+        for (int w = 3; w >= 0; --w) {
+            const int cell = 64 * w + lane, ty = (cell * bw_rcp) >> 16, tx = cell - ty * BW;
+            const bool ok = cell < S && rzm::twin_ok_yx(ty, tx, (emp[w] >> lane) & 1ull, (mbits[rzm::bit_word(rzm::kOwn, cell)] >> lane) & 1ull, ay, ax, by, bx);
+            const uint64_t m = __ballot(ok);
+            t = m != 0ull ? 64 * w + (int)__builtin_ctzll(m) : t;
+        }
+        return t;
+    }
     __device__ __forceinline__ void leaf(const uint64_t (&st)[2][rzt::kWords], int to_move, int last, int d, int lane) {
         depth = d;
         rzt::store_board<rzt::kWords>(leaf_lds, 0, st, lane);
@@ -1212,11 +1244,22 @@ struct ResHook {
             reinterpret_cast<int *>(leaf_lds + 2 * rzt::kWords)[1] = last;
         }
         // (a served window's rows are dropped from the sets -- lanes 0 .. 15 hold a's, 16 .. 31 b's --; nD stays the path's length)
-        const int mw = memo_word(d);
+        int mw = memo_word(d);
         const int dropped = (mw & kMemoServeA) ? 0 : (mw & kMemoServeB) ? 1 : -1;
         const bool mine = (d == 0 ? (lane < 16 && any0) : (lane >> 4) < d) && (lane >> 4) != dropped;
         const int nD = d == 0 ? (any0 ? 1 : 0) : d;
-        windows_store(mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, mw);
+        // (the twin's rows stand where the served stone's were dropped, OR-ed into the sets as a second stone's are)
+        // ONE uniform branch around the test and the request, taken by the passes around a alone (one leaf in eight): the rows the
+        // descent asked for are waited for just below in any case, so the wait a load under a branch brings costs nothing here, while
+        // the test and a dependent load on every leaf's chain cost more than the twins gave (profiles/TRIED.md, round 17)
+        int t = -1;
+        uint64_t trow = 0ull;
+        if (twin_on && (mw & kMemoServeB) && (mw & kMemoFillA)) {
+            t = twin_of(mw, lane);
+            trow = win[(t >= 0 ? t : 0) * kWinSets + (lane & (kWinSets - 1))];
+        }
+        mw |= t >= 0 ? kMemoTwin | (int)((unsigned)t << 24) : 0;
+        windows_store(t >= 0 && (lane >> 4) == 1 ? trow : mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, mw);
         if (release) __syncthreads();
 #ifdef RZ_NET_PROFILE
         {   // -> net_prof[18]: the selection up to the release
@@ -1269,6 +1312,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) uint64_t res_win[kWinLds / 8];   // leaf_windows' hand-over
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
     __shared__ __attribute__((aligned(16))) uint64_t res_mbits[rzm::kBitmapWords];   // the game's memo: its valid bits (zero without one)
+    __shared__ __attribute__((aligned(16))) uint64_t res_emp[RZ_BOARD_WORDS];        // the root's empty cells (the twin's candidates)
     // (rz_set_playouts' order: the games with the most simulations in the first round of a grid of more than two games per CU)
     const int game = res.order != nullptr ? res.order[blockIdx.x] : (int)blockIdx.x;
     if ((unsigned)game >= (unsigned)res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier; an order's entry out of range: no game)
@@ -1319,7 +1363,8 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     char *const memo_g = memo_on ? mm.memo + (size_t)game * (size_t)rzm::game_bytes(nd.S) : nullptr;   // (neither is formed, let alone read, without a memo)
     uint64_t *const memo_bits_g = memo_on ? mm.bits + (size_t)game * rzm::kBitmapWords : nullptr;
     if (tid0 < rzm::kBitmapWords) res_mbits[tid0] = memo_on ? memo_bits_g[tid0] : 0ull;
-    int memo_hits = 0, memo_fills = 0, memo_half = 0;
+    if (tid0 < RZ_BOARD_WORDS) res_emp[tid0] = ~(res.E.root_stones[(size_t)game * 8 + tid0] | res.E.root_stones[(size_t)game * 8 + RZ_BOARD_WORDS + tid0]);
+    int memo_hits = 0, memo_fills = 0, memo_half = 0, memo_twins = 0;
     bool head_stored = false;   // (the head weights go to LDS in the first leaf that runs its passes)
     if (tid0 == 0) res_pre.scan = res_pre.valid = res_pre.answered = 0;   // (no stash yet: a select_first == 0 launch's first selection was not made here)
     ResHook hook;
@@ -1335,6 +1380,9 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     hook.mbits = res_mbits;
     hook.memo_on = memo_on;
     hook.half_on = memo_on && mm.half != 0;
+    hook.twin_on = hook.half_on && mm.twin != 0;
+    hook.emp = res_emp;
+    hook.S = nd.S;
     hook.bw_rcp = da.bw_rcp, hook.BW = BW;
     hook.c0 = hook.c1 = 0;
     hook.mw0 = hook.mw1 = 0ull;
@@ -1393,6 +1441,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         // two unconditional loads -- and stores them where the feature stage would have.  The counters see the tiles pass -1 would
         // have run (the window sets' popcounts were handed over as for any leaf).
         const int memo_w = POL ? 0 : __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_win + kWinSets)[kWinSets + 1]);
+        leaf.twin = !POL && (memo_w & kMemoTwin) ? (memo_w >> 24) & 255 : -1;
         int n_tiles;
         if (!POL && (memo_w & kMemoHit)) {
             const int a = (memo_w >> 8) & 255, b = (memo_w >> 16) & 255, S = nd.S;
@@ -1437,10 +1486,18 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                 const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
                 int slot;
                 const int src = rzm::source_of_yx(cy, cx, ay, ax, by, bx, &slot);
+                // THE TWIN (rz_memo.h): the passes above also ran the window of t on root + a + b + t.  The threads within 3 of t -- in
+                // neither stone's window, so they have just read the base's two values -- store what the pass left in the value row
+                // to entry (t, OWN) and put the base's values back: the leaf has no stone at t.  The counters see the leaf's own tiles.
+                const bool twin = (memo_w & kMemoTwin) != 0;   // (uniform)
+                const int t = twin ? (memo_w >> 24) & 255 : 0, ty = (t * da.bw_rcp) >> 16, tx = t - ty * BW;
+                const int st = rzm::slot_of(cy, cx, ty, tx);
+                const bool in_t = twin && tid_s < S && st >= 0;
+                slot = in_t ? st : slot;
                 const bool in_a = src == rzm::kFromA, in_win = tid_s < S && src != rzm::kFromBase;
-                const bool fill = in_win && (memo_w & (in_a ? kMemoFillA : kMemoFillB));
+                const bool fill = in_t || (in_win && (memo_w & (in_a ? kMemoFillA : kMemoFillB)));
                 const bool take = in_win && (memo_w & (in_a ? kMemoServeA : kMemoServeB));
-                const int e = rzm::entry_index(in_a ? rzm::kOwn : rzm::kOppLast, in_a ? a : b, S);
+                const int e = rzm::entry_index(in_a || in_t ? rzm::kOwn : rzm::kOppLast, in_t ? t : in_a ? a : b, S);
                 float *pm = reinterpret_cast<float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot < 0 ? 0 : slot, 0));
                 const float *pb = reinterpret_cast<const float *>(leaf.base + kBaseV) + 4 * kCells + tid_s;
                 const float *p = take ? pm : pb;
@@ -1453,14 +1510,18 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                     pm[0] = res_vrow[tid_s];
                     pm[1] = res_vrow[S + tid_s];
                 }
+                if (in_t) {
+                    res_vrow[tid_s] = m4;
+                    res_vrow[S + tid_s] = m5;
+                }
                 if (memo_w & (kMemoServeA | kMemoServeB)) {   // (uniform)
-                    const uint64_t *wr = da.win + ((memo_w & kMemoServeA) ? a : b) * kWinSets;
+                    const uint64_t *wr = da.win + ((memo_w & kMemoServeA) ? a : b) * kWinSets, *wt = da.win + t * kWinSets;
                     const int *cnt = reinterpret_cast<const int *>(res_win + kWinSets);
                     int t2 = 0, t3 = 0;
 #pragma unroll
                     for (int w = 0; w < 4; ++w) {
-                        t2 += __builtin_amdgcn_readfirstlane(cnt[4 * 1 + w]) + __popcll(wr[4 * 1 + w]);
-                        t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]) + __popcll(wr[4 * 2 + w]);
+                        t2 += __builtin_amdgcn_readfirstlane(cnt[4 * 1 + w]) + __popcll(wr[4 * 1 + w]) - (twin ? __popcll(wt[4 * 1 + w]) : 0);
+                        t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]) + __popcll(wr[4 * 2 + w]) - (twin ? __popcll(wt[4 * 2 + w]) : 0);
                     }
                     n_tiles = ((t3 + 15) >> 4) | (((t2 + 15) >> 4) << 16);
                     memo_half += 1;
@@ -1474,8 +1535,13 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                         const int w = rzm::bit_word(rzm::kOppLast, b);
                         memo_bits_g[w] = res_mbits[w] = res_mbits[w] | (1ull << (b & 63));
                     }
+                    if (twin) {
+                        const int w = rzm::bit_word(rzm::kOwn, t);
+                        memo_bits_g[w] = res_mbits[w] = res_mbits[w] | (1ull << (t & 63));
+                    }
                 }
-                memo_fills += ((memo_w & kMemoFillA) ? 1 : 0) + ((memo_w & kMemoFillB) ? 1 : 0);
+                memo_fills += ((memo_w & kMemoFillA) ? 1 : 0) + ((memo_w & kMemoFillB) ? 1 : 0) + (twin ? 1 : 0);
+                memo_twins += twin ? 1 : 0;
             }
         }
         tiles_total += n_tiles & 0xffff;
@@ -1593,6 +1659,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
             atomicAdd(da.stats + 8, (unsigned)memo_hits);
             atomicAdd(da.stats + 9, (unsigned)memo_fills);
             atomicAdd(da.stats + 10, (unsigned)memo_half);
+            atomicAdd(da.stats + 11, (unsigned)memo_twins);
         }
         if (game == 0) {   // the clock this search ran at: cycles / (ticks x 10 ns)
             da.stats[6] = (unsigned)((__builtin_readcyclecounter() - clk0) >> 8);
@@ -1689,7 +1756,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_policy_rows(NetDev nd, _Float1
         leaf.dst16 = store16 + (size_t)slot * pr.slot_halfs + (size_t)(game >> 5) * nd.groups_act * 1024 + (game & 31) * 16;
         leaf.vdst = nullptr;
         leaf.dst32 = nullptr;
-        leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr;
+        leaf.sets = nullptr, leaf.gtab = nullptr, leaf.leaf_lds = nullptr, leaf.twin = -1;
         leaf.deferred = false;
         leaf.store_head = first;
         first = false;

@@ -111,4 +111,43 @@ RZM_FN int cell_source(int cy, int cx, int a, int b, int BW, int srv, int *win, 
     return cell_source_yx(cy, cx, a / BW, a % BW, b / BW, b % BW, srv, win, slot);
 }
 
+// THE TWIN.  A far pair root + a + b that runs a's window alone (b's served, entry (a, OWN) missing) has a second window's budget to
+// spare: it also runs the window of t, the LOWEST cell of the board that is empty at the root, has no (t, OWN) entry and lies
+// kMinDist or more from a AND from b, on the pseudo-position root + a + b + t (t the root mover's stone, as a is, and not the last
+// move), and fills (t, OWN) beside (a, OWN): the leaf root + t + b' that comes later finds its window there.  No such cell: no twin.
+// Exactness.  (1) a's window, with t on the board: what the pass computes around a reads inputs within 3 of a, and every record it
+// takes from the base -- conv1's within 3, conv2's within 4 of a -- depends on inputs within 6 of a: t, 7 or more away, is none of
+// them, as b is not (served, above).  Where the radius-4 sets of a and t touch (distance 7 or 8) a record that is only HELD lies
+// more than 2 from both stones: the base's there, in the leaf too.  So a's 7 x 7 is the leaf's, bit for bit.  (2) t's window: the same
+// argument with a and t exchanged gives the 7 x 7 of "root + t as the mover's stone, not the last move" -- neither a nor b is within
+// 6 of a cell the pass computes or holds for it --, which is the meaning of (t, OWN).  (3) The value row: the LEAF has no stone at t,
+// and with a and b 7 or more away its cells within 3 of t have the BASE's features.  The pass has written the pseudo-position's
+// there, so the threads within 3 of t store their two values to the entry and then put the base's values back into the value row;
+// keeping what the pass wrote would evaluate a position the search never reached.
+// The choice of t changes which later leaves are served, never a value: any cell that passes `twin_ok` would do.
+// What the kernel calls: twin_ok_yx (ResHook::twin_of: lane L tests cells L, 64 + L, ..., a ballot per word, the lowest set bit), slot_of,
+// source_of_yx and entry_index (the fill behind delta_passes).  twin_cell and twin_source_yx below are the HOST's statement of the same
+// rule, cell by cell, as cell_source_yx is of the one-window patch: tests/test_delta_twin_host.py holds them to numpy, and
+// tests/test_delta_twin.py holds the kernel's counters and trees to that rule on the GPU.
+RZM_FN bool twin_ok_yx(int ty, int tx, bool empty, bool has_own, int ay, int ax, int by, int bx) {
+    return empty && !has_own && cheb(ty, tx, ay, ax) >= kMinDist && cheb(ty, tx, by, bx) >= kMinDist;
+}
+// root_empty: 4 words, bit = cell empty at the root (bits past the board's S cells are not looked at) -> t, or -1
+RZM_FN int twin_cell(int a, int b, int BW, int S, const uint64_t *root_empty, const uint64_t *bits) {
+    for (int t = 0; t < S; ++t)
+        if (twin_ok_yx(t / BW, t % BW, (root_empty[t >> 6] >> (t & 63)) & 1ull, valid_bit(bits, kOwn, t), a / BW, a % BW, b / BW, b % BW)) return t;
+    return -1;
+}
+// a twin pass's sources: cell (cy, cx) of the leaf root + a + b, b served, a run, twin t.  -> cell_source's answer, and *fills = the
+// entry the cell's two computed values are stored to: kFromA (a's), kFromTwin (t's; the cell then takes the BASE's values) or kFromBase (none)
+constexpr int kFromTwin = 3;
+RZM_FN int twin_source_yx(int cy, int cx, int ay, int ax, int by, int bx, int ty, int tx, int *fills, int *slot) {
+    int win;
+    const int src = cell_source_yx(cy, cx, ay, ax, by, bx, kServeB, &win, slot);
+    const int st = slot_of(cy, cx, ty, tx);
+    *fills = st >= 0 ? kFromTwin : src == kSrcRun ? kFromA : kFromBase;
+    *slot = st >= 0 ? st : *slot;
+    return st >= 0 ? kSrcBase : src;
+}
+
 }  // namespace rzm

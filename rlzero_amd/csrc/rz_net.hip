@@ -105,6 +105,7 @@ struct rz_net {
     bool delta_resident = true;       // rz_net_delta_resident: rz_net_search_resident runs k_delta_res where the cache allows
     bool delta_memo = true;           // rz_net_delta_memo: k_delta_res<false> serves far-apart two-stone leaves from the memo
     bool memo_half = true;            // ... and runs ONE window where the memo holds the other (rz_net_delta_memo(net, 2): not)
+    bool memo_twin = true;            // ... and a foretold cell's window beside it (rz_net_delta_memo(net, 3); 1: one window, no twin)
 };
 
 namespace {
@@ -175,7 +176,7 @@ dl::DeltaArgs delta_args(const rz_net *net, const uint8_t *active, float *feat32
 size_t base_hdr_bytes(int n_games) { return (size_t)n_games * (sizeof(dl::BaseHdr) + rzm::kBitmapWords * sizeof(uint64_t)); }
 uint64_t *memo_bits(const rz_net *net) { return reinterpret_cast<uint64_t *>(net->d_base_hdr.p + net->base_games); }
 // on: k_delta_res<false> may serve leaves from the memo and fill it (no memo memory: every leaf runs its passes)
-dl::MemoArgs memo_args(const rz_net *net, bool on) { return dl::MemoArgs{on ? net->d_memo.p : nullptr, memo_bits(net), net->memo_half ? 1 : 0}; }
+dl::MemoArgs memo_args(const rz_net *net, bool on) { return dl::MemoArgs{on ? net->d_memo.p : nullptr, memo_bits(net), net->memo_half ? 1 : 0, net->memo_twin ? 1 : 0}; }
 // The memo's entries for the reserved games (15 x 15: 230 KB a game, 118 MB at 512 games), only while the memo is switched on.  The
 // memo is an optimisation: where the memory is not to be had the search runs without it, the base cache stands.
 void memo_reserve(rz_net *net) {
@@ -917,8 +918,9 @@ int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out4) {
     if (!net || !h_out4) return rz_fail(RZ_ERR_ARG, "NULL argument");
     memset(h_out4, 0, 4 * sizeof(uint32_t));
     if (!net->d_delta_stats) return RZ_OK;
-    static_assert(dl::kStats >= 8 + 3, "hits, fills, one-window leaves: words 8 .. 10 of the counters");
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out4, net->d_delta_stats.p + 8, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    // (the fourth word, always 0 before the twins: no kernel of modes 0 .. 2 counts into word 11)
+    static_assert(dl::kStats >= 8 + 4, "hits, fills, one-window leaves, twins run: words 8 .. 11 of the counters");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out4, net->d_delta_stats.p + 8, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
     return RZ_OK;
 }
@@ -928,6 +930,7 @@ int rz_net_delta_memo(rz_net *net, int32_t on) {
     // (2, the diagnostic: the memo without the one-window route.  The entries mean the same either way: nothing is dropped for it.
     // A host-side setting read when launches are enqueued)
     net->memo_half = on != 2;
+    net->memo_twin = on == 3;   // (3: the one-window pass around a also runs a twin's window, rz_memo.h; the entries mean the same)
     if (net->delta_memo == (on != 0)) return RZ_OK;
     net->delta_memo = on != 0;
     if (net->base_games > 0) {   // (searches in flight may read the entries that go, or the bits of entries that come)

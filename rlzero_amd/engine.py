@@ -215,8 +215,9 @@ class HipNet(object):
     def delta_reserve(self, n_games):
         # (RZ_DELTA_MEMO=0: the resident search runs every leaf's passes -- the kernel without the feature memo, in the same library --
         # and the memo's memory is not reserved; the switch goes first so that the reserve knows.  RZ_DELTA_MEMO=2, a diagnostic: the
-        # memo without the one-window route, for an A / B inside one library)
-        check(self.lib.rz_net_delta_memo(self.handle, {'0': 0, '2': 2}.get(os.environ.get('RZ_DELTA_MEMO', '1'), 1)), 'rz_net_delta_memo')
+        # memo without the one-window route, for an A / B inside one library; RZ_DELTA_MEMO=1: the one-window route without the twin
+        # windows of rz_memo.h; unset, or 3: with them)
+        check(self.lib.rz_net_delta_memo(self.handle, {'0': 0, '1': 1, '2': 2}.get(os.environ.get('RZ_DELTA_MEMO', '3'), 3)), 'rz_net_delta_memo')
         check(self.lib.rz_net_delta_reserve(self.handle, int(n_games)), 'rz_net_delta_reserve')
         self._delta_games = max(self._delta_games, int(n_games))
 
@@ -254,7 +255,8 @@ class HipNet(object):
         (k_delta_res), 'resident_sclk_ghz': the shader clock the last resident search ran at, 'memo_hits': leaves of the resident search
         served from the feature memo (they count among 'delta', with the tiles their passes would have run), 'memo_fills': entries filled,
         'memo_half': leaves that ran one stone's window and took the other's from the memo (not among 'memo_hits'; they count the tiles of
-        the two-window pass; 0 under RZ_DELTA_MEMO=2 and =0)}"""
+        the two-window pass; 0 under RZ_DELTA_MEMO=2 and =0), 'memo_twins': one-window passes that also ran and filled a twin's window
+        (rz_memo.h: twin_cell; among 'memo_half'; 0 unless RZ_DELTA_MEMO is 3 or unset)}"""
         out = (ctypes.c_uint32 * 8)()
         memo = (ctypes.c_uint32 * 4)()
         check(self.lib.rz_net_delta_memo_stats(self.handle, memo), 'rz_net_delta_memo_stats')
@@ -262,7 +264,7 @@ class HipNet(object):
         ghz = (256.0 * out[6]) / (10.0 * out[7]) if out[7] else None   # (cycles per nanosecond of the last resident launch's workgroup 0)
         return {'delta': int(out[0]), 'no_base': int(out[1]), 'tiles3': int(out[2]), 'cells': int(out[3]), 'tiles2': int(out[4]),
                 'prescans': int(out[5]), 'resident_sclk_ghz': ghz, 'memo_hits': int(memo[0]), 'memo_fills': int(memo[1]),
-                'memo_half': int(memo[2])}
+                'memo_half': int(memo[2]), 'memo_twins': int(memo[3])}
 
     def compact_resident(self):
         """True when the resident search runs on the COMPACT LDS grid (k_trunk_split<.., RES, 9, 15>: 69 KB, TWO games per CU and any
