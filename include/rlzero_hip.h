@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 53
+#define RZ_ABI_VERSION 54
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -775,10 +775,20 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset);
  * leaf root + t + b' is served: the same bits, more leaves served.  The twin's entry counts among the entries filled; the pass counts
  * its own leaf's tiles only.  on = 1 is the one-window route without twins; both are read when a launch is enqueued.  The fourth word
  * of rz_net_delta_memo_stats, 0 under on = 0, 1 and 2 as it always was, counts the passes that ran a twin under on = 3.
- * rz_net_delta_memo_stats (synchronises): h_out4 = {leaves served from the memo, entries filled, leaves that ran one window, 0} since
- * the last rz_net_delta_stats(reset) (four words since ABI 53, two before). */
+ * KIND D1 (ABI 54).  on = 4: on = 3, and the depth-1 leaves root + a -- a quarter of a search's leaves -- are served too.  A depth-1 leaf
+ * that runs its pass also runs the window of a foretold cell t -- the lowest cell above a that is empty at the root, has no (t, D1) entry
+ * and lies 7 or more from a (rz_memo.h: d1_twin_cell) -- on root + a + t, and fills entry (t, D1): the 7 x 7 of "root + t as the stone of
+ * the side that has just moved, and the last move".  The later depth-1 leaf root + t lays it over the parity-1 base's planes: the same
+ * bits.  The entries live in a store of their own, cells x 512 bytes per reserved game, reserved while on = 4; where that memory cannot
+ * be had the search runs as under on = 3.  A change between on = 4 and the other values synchronises and drops the bases, as a change
+ * of on = 0 does, and it releases or reserves the kind's store: a launch holds the store's address by value, so a search CAPTURED in a
+ * graph before such a change (as before a change of on = 0, which releases the far pairs' store) must be captured again, never
+ * replayed.  A served depth-1 leaf is NOT among "leaves served from the memo": words 0 .. 3 below count what they counted.
+ * rz_net_delta_memo_stats (synchronises): h_out8 = {leaves served from the memo, entries filled, leaves that ran one window, passes that
+ * ran a twin, depth-1 leaves served from kind D1, depth-1 passes that ran a twin, D1 entries filled, 0} since the last
+ * rz_net_delta_stats(reset) (eight words since ABI 54, four in ABI 53, two before; words 4 .. 6 are 0 unless on = 4). */
 int rz_net_delta_memo(rz_net *net, int32_t on);
-int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out4);
+int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out8);
 /* RESIDENT SEARCH -- n_sims consecutive simulations of every active game of `engine` (AlphaZeroMCTS.simulate's loop,
  * alphazero_mcts.py:82-85) in ONE launch, one workgroup per game: trunk -> value head -> expand / backup -> next selection without
  * a kernel boundary, the leaf handed from the tree code to the trunk through LDS.  Kernels that hold a whole CU (151 KB of LDS: boards

@@ -78,4 +78,7 @@ for games in sizes:
         hits, leaves, 100.0 * hits / leaves, half, 100.0 * half / leaves, twins, 100.0 * twins / leaves, fills, fills / games)
           + ('; game 0, wave 0: patch copy %d cycles per hit (slot 5 / the launch\'s mean hits per game)' % (out[5] / (hits / games))
              if hits and st['no_base'] == 0 else ''), flush=True)
+    d1_hits, d1_twins, d1_fills = (st.get(k, 0) for k in ('memo_d1_hits', 'memo_d1_twins', 'memo_d1_fills'))   # (kind D1: RZ_DELTA_MEMO=4, the default)
+    print('   memo, kind D1: %d depth-1 leaves served (%.1f %% of leaves), %d depth-1 passes ran a twin (%.1f %%), %d entries filled (%.1f a game)' % (
+        d1_hits, 100.0 * d1_hits / leaves, d1_twins, 100.0 * d1_twins / leaves, d1_fills, d1_fills / games), flush=True)
     eng.close(); ev.hip.close()

@@ -94,9 +94,9 @@ static_assert(kShareFloats * 4 <= kC1Slots * P1, "the shares lie inside conv1's 
 // (radius 1 .. 4) as 4 x 4 words, their words' popcounts, the verdict (use_delta | parity << 1 | nD << 8)
 constexpr int kWinSets = rzw::kRadii * rzw::kWords, kWinLds = kWinSets * 8 + kWinSets * 4 + 16;
 // (k_delta_res' own arrays, exactly: 81 376 bytes with the 96-byte RootPre -- 544 below half a CU)
-constexpr int kResLds = kLdsBytes + 512 * 4 + 4 * 64 * 4 + (2 * RZ_BOARD_WORDS + 2) * 8 + kWinLds + (int)sizeof(rzt::RootPre) + rzm::kBitmapWords * 8 + RZ_BOARD_WORDS * 8;
+constexpr int kResLds = kLdsBytes + 512 * 4 + 4 * 64 * 4 + (2 * RZ_BOARD_WORDS + 2) * 8 + kWinLds + (int)sizeof(rzt::RootPre) + rzm::kBitmapWords * 8 + RZ_BOARD_WORDS * 8 + rzm::kD1BitmapWords * 8;
 static_assert(2 * kResLds <= 160 * 1024,
-              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan, the memo's valid bits, the root's empty cells)");
+              "two workgroups per CU, also of the resident search (value row, K-quarter sums, leaf, window sets, root pre-scan, the memo's valid bits of both stores, the root's empty cells)");
 static_assert(kOffC1 % 16 == 0 && kOffZero % 16 == 0 && kOffHead % 16 == 0 && kOffMap1 % 16 == 0, "alignment");
 
 // The base cache: per game a header (the stones the two bases were computed from) and per (game, parity) the records.
@@ -119,6 +119,7 @@ struct DeltaArgs {
                              // cycles >> 8, ticks of the constant 100 MHz clock; [8], [9]: leaves served from the memo, entries filled;
                              // [10]: leaves that ran ONE window and took the other from the memo
                              // [11]: one-window passes that ran a twin's window beside their own (rz_memo.h: twin_cell)
+                             // [12] .. [14], kind D1: depth-1 leaves served, depth-1 passes that ran a twin (rz_memo.h: d1_twin_cell), entries filled
     int mode;                // 0: the leaves of `leaves` against the cache; 1: build the cache from the ROOT positions in `leaves`
                              // (board = 2 game + parity); 2: the leaves without a base (the four-pass route alone: a checker)
     int bw_rcp;              // ceil(65536 / width): cell / width = (cell * bw_rcp) >> 16 for cell < 4096
@@ -130,6 +131,8 @@ struct MemoArgs {
     uint64_t *bits;          // [games][rzm::kBitmapWords] the valid bits (k_memo_clear in front of every mode-1 launch)
     int half;                // a far pair with exactly one valid entry runs the missing stone's window alone (rz_memo.h: served); 0: both
     int twin;                // ... and the pass around a alone also runs and fills the window of a foretold cell (rz_memo.h: twin_cell); 0: not
+    char *d1;                // kind D1: [games][S entries] (NULL: depth-1 leaves run their passes alone, as without the kind)
+    uint64_t *d1bits;        // [games][rzm::kD1BitmapWords] its valid bits (cleared with `bits`)
 };
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -379,9 +382,11 @@ struct Leaf {
     float *dst32;             // f32 features (tests; NULL otherwise)
     const uint64_t *sets;     // delta_passes<true>: pass -1's window sets, handed over in LDS (leaf_windows)
     int twin;                 // delta_passes<true>, pass -1: the twin's cell, a stone of the side to move in the planes alone (rz_memo.h); -1: none
+                              // (| kTwinD1, a depth-1 pass's twin: a stone of the side that has just moved and a second last cell)
     uint16_t *gtab;           // delta_passes<true>: THIS wave's table of the base records it copies (rz_gather.h: rzg::Split<3>::kTabEntries entries of LDS)
     bool deferred, store_head;
 };
+constexpr int kTwinD1 = 256;
 struct Layers {
     float k1, k2, k3, act1, act2, act3;
     const char *t2p, *t3p;
@@ -437,7 +442,7 @@ static_assert(rzg::kC1Max == kC1Slots && rzg::kC2Max == kC2Slots && rzg::kC1Byte
               "rz_gather.h's records are the base's and the budget is this file's");
 static_assert(rzg::kC1Bytes <= P1 && rzg::kC2Bytes <= P2, "a record fits its LDS slot");
 
-__device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int tm_eff, bool has_last, int lc, int par_count);
+__device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int tm_eff, bool has_last, int lc, int par_count, int lc2 = -1);
 
 // the leaf the selection left in LDS (wave-uniform values)
 __device__ __forceinline__ void leaf_from_lds(const uint64_t *leaf_lds, uint64_t (&ls)[8], int &tm, int &lc, int &nst) {
@@ -757,13 +762,16 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
                 uint64_t ls[8];
                 int tm, lc, nst;
                 leaf_from_lds(leaf.leaf_lds, ls, tm, lc, nst);
-                {   // the twin (rz_memo.h): a stone of the side to move -- a's side in a far pair -- in the planes of this pass, nowhere else
-                    const int tw = leaf.twin;
+                // the twin (rz_memo.h): a stone of the side to move -- a's side in a far pair -- in the planes of this pass, nowhere else;
+                // a depth-1 pass's twin (kTwinD1): a stone of the side that has just moved, as a is, and a second last cell
+                const int tw = leaf.twin < 0 ? -1 : leaf.twin & 255, lc2 = leaf.twin >= kTwinD1 ? tw : -1;
+                {
+                    const bool first = (tm == 0) != (lc2 >= 0);
 #pragma unroll
                     for (int w = 0; w < 4; ++w) {
                         const uint64_t bit = tw >= 0 && (tw >> 6) == w ? 1ull << (tw & 63) : 0ull;
-                        ls[w] |= tm == 0 ? bit : 0ull;
-                        ls[4 + w] |= tm == 0 ? 0ull : bit;
+                        ls[w] |= first ? bit : 0ull;
+                        ls[4 + w] |= first ? 0ull : bit;
                     }
                 }
                 const int *cnt = reinterpret_cast<const int *>(leaf.sets + kWinSets);
@@ -771,7 +779,7 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
                     const int cell = 64 * w + lane, y = (cell * da.bw_rcp) >> 16, x = cell - y * BW;
-                    const f16x4 planes = planes_of(ls, cell, tm, nst > 0, lc, nst);
+                    const f16x4 planes = planes_of(ls, cell, tm, nst > 0, lc, nst, lc2);
                     if (cell < S) *reinterpret_cast<f16x4 *>(in0 + ((y + 1) * sp::kInCols + (x + 1)) * 8) = planes;
                     const uint64_t w1 = uni64(leaf.sets[4 * 0 + w]), w3 = uni64(leaf.sets[4 * 2 + w]);
                     const int pos = (y + 1) * kRowW + x + 1;
@@ -894,7 +902,8 @@ __device__ __forceinline__ int delta_passes(const NetDev &nd, const DeltaArgs &d
 }
 
 // the four planes of thread `tid`'s cell (load_bits of trunk_rows_body; a base: no last move, the parity's stone count)
-__device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int tm_eff, bool has_last, int lc, int par_count) {
+// (lc2: a second last cell, the twin's in a depth-1 pass of k_delta_res -- rz_memo.h, kind D1 --, -1 everywhere else)
+__device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int tm_eff, bool has_last, int lc, int par_count, int lc2) {
     f16x4 cell_planes;
     const int word = (tid >> 6) & 3, bit = tid & 63;
     uint64_t w0 = 0ull, w1 = 0ull;   // (masks, not a select of array elements: rz_tree.h's word_of)
@@ -909,7 +918,7 @@ __device__ __forceinline__ f16x4 planes_of(const uint64_t (&ls)[8], int tid, int
     const _Float16 one = (_Float16)sp::kObsScale, zero = (_Float16)0.0f;
     cell_planes[0] = mine ? one : zero;
     cell_planes[1] = theirs ? one : zero;
-    cell_planes[2] = (has_last && tid == lc) ? one : zero;
+    cell_planes[2] = (has_last && (tid == lc || tid == lc2)) ? one : zero;
     cell_planes[3] = (par_count & 1) ? zero : one;
     return cell_planes;
 }
@@ -1069,6 +1078,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_delta(NetDev nd, LeafBits leav
 
 // The memo's valid bits of the first n_games games -> 0, in front of every launch of mode 1: the memo patches the bases that were there
 // before, none of it is valid any more.  (a kernel of its own: k_trunk_delta keeps its registers, and a captured search needs no memset node)
+// (kind D1's valid bits of the same games, an array of their own: a second launch)
 __global__ void k_memo_clear(uint64_t *bits, int n_words) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_words) bits[i] = 0ull;
@@ -1108,7 +1118,9 @@ static_assert(kWinLds >= kWinSets * 12 + 8, "the verdict and the memo's word");
 // (b, OPP_LAST) to be filled << 3 | a's window served, b's alone run << 4 | b's served, a's alone run << 5 | a << 8 | b << 16
 // (the two serve bits: rzm::served of a leaf with exactly one valid entry; a hit has neither)
 // the twin of a pass around a alone (rz_memo.h: twin_cell): its window is run and entry (t, OWN) filled << 6 | t << 24
-constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8, kMemoServeA = 16, kMemoServeB = 32, kMemoTwin = 64;
+// kind D1 (rz_memo.h), a depth-1 leaf root + a on the root's base: << 7 | a << 8, with kMemoHit: served from entry (a, D1); with
+// kMemoTwin: its pass also runs t's window and fills (t, D1).  Such a word has none of the far pair's other bits.
+constexpr int kMemoFar = 1, kMemoHit = 2, kMemoFillA = 4, kMemoFillB = 8, kMemoServeA = 16, kMemoServeB = 32, kMemoTwin = 64, kMemoD1 = 128;
 __device__ __forceinline__ void leaf_windows(const uint64_t *leaf_lds, const uint64_t (&rs)[8], bool base_ok, int h_tm, const DeltaArgs &da, int BW,
                                              int lane, uint64_t *ws) {
     uint64_t ls[8];
@@ -1236,6 +1248,23 @@ struct ResHook {
         }
         return t;
     }
+    // Kind D1 (rz_memo.h): a depth-1 leaf root + a whose (a, D1) bit is set (LDS: d1bits) is served; one that runs its pass takes a twin,
+    // the lowest cell above a that is empty at the root, has no (t, D1) bit and lies 7 or more from a -- twin_of's four ballots with
+    // one distance test; the rows go where twin_of's go (lanes 16 .. 31: a depth-1 leaf has no second stone)
+    const uint64_t *d1bits;
+    bool d1_on;
+    __device__ __forceinline__ int d1_twin_of(int a, int lane) const {
+        const int ay = (a * bw_rcp) >> 16, ax = a - ay * BW;
+        int t = -1;
+#pragma unroll
+        for (int w = 3; w >= 0; --w) {
+            const int cell = 64 * w + lane, ty = (cell * bw_rcp) >> 16, tx = cell - ty * BW;
+            const bool ok = cell < S && rzm::d1_twin_ok_yx(ty, tx, (emp[w] >> lane) & 1ull, (d1bits[w] >> lane) & 1ull, ay, ax);
+            const uint64_t m = __ballot(ok);
+            t = m != 0ull ? 64 * w + (int)__builtin_ctzll(m) : t;
+        }
+        return t;
+    }
     __device__ __forceinline__ void leaf(const uint64_t (&st)[2][rzt::kWords], int to_move, int last, int d, int lane) {
         depth = d;
         rzt::store_board<rzt::kWords>(leaf_lds, 0, st, lane);
@@ -1257,6 +1286,19 @@ struct ResHook {
         if (twin_on && (mw & kMemoServeB) && (mw & kMemoFillA)) {
             t = twin_of(mw, lane);
             trow = win[(t >= 0 ? t : 0) * kWinSets + (lane & (kWinSets - 1))];
+        }
+        // KIND D1, again ONE uniform branch, taken by the depth-1 leaves alone (memo_word is 0 at depth 1): the bit's test, and for a
+        // leaf that runs its pass the choice of t and the one request for its rows.  A served leaf keeps a's rows: the counters see
+        // the tiles its pass would have run.  nD stays 1 either way.
+        if (d1_on && d == 1 && base_ok) {
+            const int a = __builtin_amdgcn_readfirstlane(c0);
+            mw = kMemoD1 | (a << 8);
+            if ((uni64(d1bits[a >> 6]) >> (a & 63)) & 1ull) {
+                mw |= kMemoHit;
+            } else {
+                t = d1_twin_of(a, lane);
+                trow = win[(t >= 0 ? t : 0) * kWinSets + (lane & (kWinSets - 1))];
+            }
         }
         mw |= t >= 0 ? kMemoTwin | (int)((unsigned)t << 24) : 0;
         windows_store(t >= 0 && (lane >> 4) == 1 ? trow : mine ? row : 0ull, base_ok && nD <= kMaxD, d & 1, nD, lane, ws, mw);
@@ -1313,6 +1355,7 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     __shared__ __attribute__((aligned(16))) rzt::RootPre res_pre;            // the root pre-scan's (select_body -> wave 1 -> select_body)
     __shared__ __attribute__((aligned(16))) uint64_t res_mbits[rzm::kBitmapWords];   // the game's memo: its valid bits (zero without one)
     __shared__ __attribute__((aligned(16))) uint64_t res_emp[RZ_BOARD_WORDS];        // the root's empty cells (the twin's candidates)
+    __shared__ __attribute__((aligned(16))) uint64_t res_d1bits[rzm::kD1BitmapWords];   // the valid bits of the memo's kind D1 (zero without it)
     // (rz_set_playouts' order: the games with the most simulations in the first round of a grid of more than two games per CU)
     const int game = res.order != nullptr ? res.order[blockIdx.x] : (int)blockIdx.x;
     if ((unsigned)game >= (unsigned)res.E.n_games || res.E.active[game] == 0) return;   // (uniform: before any barrier; an order's entry out of range: no game)
@@ -1364,7 +1407,12 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     uint64_t *const memo_bits_g = memo_on ? mm.bits + (size_t)game * rzm::kBitmapWords : nullptr;
     if (tid0 < rzm::kBitmapWords) res_mbits[tid0] = memo_on ? memo_bits_g[tid0] : 0ull;
     if (tid0 < RZ_BOARD_WORDS) res_emp[tid0] = ~(res.E.root_stones[(size_t)game * 8 + tid0] | res.E.root_stones[(size_t)game * 8 + RZ_BOARD_WORDS + tid0]);
-    int memo_hits = 0, memo_fills = 0, memo_half = 0, memo_twins = 0;
+    // kind D1 (rz_memo.h): a store and valid bits of its own; on with the twins, where the store was to be had
+    const bool d1_on = memo_on && mm.half != 0 && mm.twin != 0 && mm.d1 != nullptr;
+    char *const d1_g = d1_on ? mm.d1 + (size_t)game * (size_t)rzm::d1_game_bytes(nd.S) : nullptr;
+    uint64_t *const d1_bits_g = d1_on ? mm.d1bits + (size_t)game * rzm::kD1BitmapWords : nullptr;
+    if (tid0 < rzm::kD1BitmapWords) res_d1bits[tid0] = d1_on ? d1_bits_g[tid0] : 0ull;
+    int memo_hits = 0, memo_fills = 0, memo_half = 0, memo_twins = 0, d1_hits = 0, d1_twins = 0;
     bool head_stored = false;   // (the head weights go to LDS in the first leaf that runs its passes)
     if (tid0 == 0) res_pre.scan = res_pre.valid = res_pre.answered = 0;   // (no stash yet: a select_first == 0 launch's first selection was not made here)
     ResHook hook;
@@ -1382,6 +1430,8 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
     hook.half_on = memo_on && mm.half != 0;
     hook.twin_on = hook.half_on && mm.twin != 0;
     hook.emp = res_emp;
+    hook.d1bits = res_d1bits;
+    hook.d1_on = d1_on;
     hook.S = nd.S;
     hook.bw_rcp = da.bw_rcp, hook.BW = BW;
     hook.c0 = hook.c1 = 0;
@@ -1441,16 +1491,19 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
         // two unconditional loads -- and stores them where the feature stage would have.  The counters see the tiles pass -1 would
         // have run (the window sets' popcounts were handed over as for any leaf).
         const int memo_w = POL ? 0 : __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(res_win + kWinSets)[kWinSets + 1]);
-        leaf.twin = !POL && (memo_w & kMemoTwin) ? (memo_w >> 24) & 255 : -1;
+        leaf.twin = !POL && (memo_w & kMemoTwin) ? ((memo_w >> 24) & 255) | ((memo_w & kMemoD1) ? kTwinD1 : 0) : -1;
         int n_tiles;
         if (!POL && (memo_w & kMemoHit)) {
-            const int a = (memo_w >> 8) & 255, b = (memo_w >> 16) & 255, S = nd.S;
+            // (kind D1, a served depth-1 leaf root + a: the same two loads -- entry (a, D1) of the D1 store within 3 of a, the parity-1
+            // base's planes elsewhere; b = a below, so that no cell is "within 3 of b alone")
+            const bool d1 = (memo_w & kMemoD1) != 0;   // (uniform)
+            const int a = (memo_w >> 8) & 255, b = d1 ? a : (memo_w >> 16) & 255, S = nd.S;
             const int ay = (a * da.bw_rcp) >> 16, ax = a - ay * BW, by = (b * da.bw_rcp) >> 16, bx = b - by * BW;
             const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
             int slot;
             const int src = rzm::source_of_yx(cy, cx, ay, ax, by, bx, &slot);
-            const int e = rzm::entry_index(src == rzm::kFromA ? rzm::kOwn : rzm::kOppLast, src == rzm::kFromA ? a : b, S);
-            const float *pm = reinterpret_cast<const float *>(memo_g + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot < 0 ? 0 : slot, 0));
+            const int e = d1 ? rzm::d1_entry_index(a) : rzm::entry_index(src == rzm::kFromA ? rzm::kOwn : rzm::kOppLast, src == rzm::kFromA ? a : b, S);
+            const float *pm = reinterpret_cast<const float *>((d1 ? d1_g : memo_g) + (size_t)e * rzm::kEntryBytes + rzm::slot_offset(slot < 0 ? 0 : slot, 0));
             const float *pb = reinterpret_cast<const float *>(leaf.base + kBaseV) + 4 * kCells + tid_s;
             const float *p = src == rzm::kFromBase ? pb : pm;
             const float v4 = p[0], v5 = p[src == rzm::kFromBase ? kCells : 1];
@@ -1466,7 +1519,8 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                 t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]);
             }
             n_tiles = ((t3 + 15) >> 4) | (((t2 + 15) >> 4) << 16);
-            memo_hits += 1;
+            memo_hits += d1 ? 0 : 1;
+            d1_hits += d1 ? 1 : 0;
             NET_TICK(5);   // the memo's patch copy (a search whose leaves all have a base: conv1 of the passes without one never ticks here)
         } else {
             n_tiles = delta_passes<true, POL ? 0 : 4, 6>(nd, da, lds, tid_s, wave, leaf, ly, headv, use_delta, prof);
@@ -1542,6 +1596,37 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
                 }
                 memo_fills += ((memo_w & kMemoFillA) ? 1 : 0) + ((memo_w & kMemoFillB) ? 1 : 0) + (twin ? 1 : 0);
                 memo_twins += twin ? 1 : 0;
+            } else if (!POL && (memo_w & kMemoD1) && (memo_w & kMemoTwin) && use_delta) {
+                // KIND D1 (rz_memo.h): the depth-1 pass above also ran the window of t on root + a + t.  The threads within 3 of t store
+                // what the pass left in the value row to entry (t, D1) and put the parity-1 base's values back: the leaf has no stone
+                // at t.  Every thread reads the base's two values, the others drop them.  a's own window is not stored.  The counters
+                // see the leaf's own tiles: the handed-over counts minus t's rows (the two windows are disjoint).
+                const int S = nd.S, t = (memo_w >> 24) & 255, ty = (t * da.bw_rcp) >> 16, tx = t - ty * BW;
+                const int cy = (tid_s * da.bw_rcp) >> 16, cx = tid_s - cy * BW;
+                const int st = rzm::slot_of(cy, cx, ty, tx);
+                const bool in_t = tid_s < S && st >= 0;
+                float *pm = reinterpret_cast<float *>(d1_g + (size_t)rzm::d1_entry_index(t) * rzm::kEntryBytes + rzm::slot_offset(st < 0 ? 0 : st, 0));
+                const float *pb = reinterpret_cast<const float *>(leaf.base + kBaseV) + 4 * kCells + tid_s;
+                const float m4 = pb[0], m5 = pb[kCells];
+                if (in_t) {
+                    pm[0] = res_vrow[tid_s];
+                    pm[1] = res_vrow[S + tid_s];
+                    res_vrow[tid_s] = m4;
+                    res_vrow[S + tid_s] = m5;
+                }
+                {
+                    const uint64_t *wt = da.win + t * kWinSets;
+                    const int *cnt = reinterpret_cast<const int *>(res_win + kWinSets);
+                    int t2 = 0, t3 = 0;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        t2 += __builtin_amdgcn_readfirstlane(cnt[4 * 1 + w]) - __popcll(wt[4 * 1 + w]);
+                        t3 += __builtin_amdgcn_readfirstlane(cnt[4 * 2 + w]) - __popcll(wt[4 * 2 + w]);
+                    }
+                    n_tiles = ((t3 + 15) >> 4) | (((t2 + 15) >> 4) << 16);
+                }
+                if (tid_s == 0) d1_bits_g[t >> 6] = res_d1bits[t >> 6] = res_d1bits[t >> 6] | (1ull << (t & 63));
+                d1_twins += 1;
             }
         }
         tiles_total += n_tiles & 0xffff;
@@ -1660,6 +1745,11 @@ __global__ __launch_bounds__(256, 2) void k_delta_res(NetDev nd, _Float16 *__res
             atomicAdd(da.stats + 9, (unsigned)memo_fills);
             atomicAdd(da.stats + 10, (unsigned)memo_half);
             atomicAdd(da.stats + 11, (unsigned)memo_twins);
+        }
+        if (d1_on) {   // (every twin a depth-1 pass runs fills its entry: [13] and [14] are one count)
+            atomicAdd(da.stats + 12, (unsigned)d1_hits);
+            atomicAdd(da.stats + 13, (unsigned)d1_twins);
+            atomicAdd(da.stats + 14, (unsigned)d1_twins);
         }
         if (game == 0) {   // the clock this search ran at: cycles / (ticks x 10 ns)
             da.stats[6] = (unsigned)((__builtin_readcyclecounter() - clk0) >> 8);

@@ -150,4 +150,55 @@ RZM_FN int twin_source_yx(int cy, int cx, int ay, int ax, int by, int bx, int ty
     return st >= 0 ? kSrcBase : src;
 }
 
+// KIND D1: THE DEPTH-1 LEAF.  About a quarter of a search's leaves are root + a: a the root mover's stone AND the last move, one changed
+// cell against the parity-1 base.  An entry (t, D1) holds the 7 x 7 window of the two value features around t in "root + t as the stone
+// of the side that has just moved, and the last move"; a depth-1 leaf root + t whose entry is there takes its window from it and the
+// parity-1 base's planes elsewhere (d1_hit): no trunk.  A depth-1 leaf is evaluated once a search, so its OWN window is never stored:
+// the entries are filled by TWINS alone.  A depth-1 leaf root + a that runs its pass also runs the window of t = d1_twin_cell: the
+// lowest cell ABOVE a that is empty at the root, has no (t, D1) entry and lies kMinDist or more from a -- on the pseudo-position
+// root + a + t, t a second stone of the side that has just moved and a second last move -- and fills (t, D1).  Above a: the reference
+// visits a node's unvisited children in index order, so the cells below a have been depth-1 leaves already, in this search or, on a kept
+// tree, in an earlier one, and will not come again (profiles/microbench/d1_probe.py: without the restriction 94 % of the twins are wasted
+// on a kept tree, with it none).
+// Layout.  A store of its own beside the far pairs': d1_entries_per_game(S) = S entries a game, entry = cell, the same pitch and slot
+// layout, and kD1BitmapWords valid words a game of their own (bit = cell), cleared wherever the far pairs' bits are.  Nothing above
+// changes its value or meaning.
+// Exactness.  (1) a's window with t on the board: what the pass computes around a reads inputs within 3 of a, and every record it
+// takes from the base -- conv1's within 3 of a, conv2's within 4 -- depends on inputs within 6 of a; t, 7 or more away, is none of
+// them, so a's 7 x 7 is the leaf's, bit for bit.  (2) t's window on root + a + t is that of root + t: the same argument with a and t
+// exchanged -- both are stones of the same side and both are marked as the last move, so the pseudo-position is symmetric in them.
+// (3) The leaf has no stone at t: the threads within 3 of t store their two values to the entry and put the parity-1 base's values
+// back into the value row.  (4) The colour plane (plane 3) is the same at every cell and follows the LEAF's stone count: the twin's
+// stone is not counted, so the plane is that of root + one stone, which is what both root + a and root + t have.
+// What the kernel calls: d1_twin_ok_yx (ResHook::d1_twin_of: lane L tests cells L, 64 + L, ..., a ballot per word, the lowest set bit),
+// d1_entry_index, d1_game_bytes, slot_of (the fill behind delta_passes) and, for a served leaf, source_of_yx with b = a (the far pair's
+// hit branch).  d1_hit, d1_twin_cell and d1_source_yx below are the HOST's statement of the same rule, cell by cell:
+// tests/test_delta_d1_host.py holds them to numpy -- that is the specification, not the device's path --, and tests/test_delta_d1.py holds
+// the kernel's counters and trees to the rule on the GPU.
+constexpr int kD1BitmapWords = 4;                 // uint64 words of a game's D1 valid bits: [256 cells]
+RZM_FN int d1_entries_per_game(int S) { return S; }
+RZM_FN long long d1_game_bytes(int S) { return (long long)d1_entries_per_game(S) * kEntryBytes; }
+RZM_FN int d1_entry_index(int cell) { return cell; }
+RZM_FN bool d1_valid_bit(const uint64_t *d1bits, int cell) { return (d1bits[cell >> 6] >> (cell & 63)) & 1ull; }
+// the hit rule of a depth-1 leaf root + a: the base is the root's and the entry is there
+RZM_FN bool d1_hit(int depth, bool base_is_root, int a, const uint64_t *d1bits) { return depth == 1 && base_is_root && d1_valid_bit(d1bits, a); }
+RZM_FN bool d1_twin_ok_yx(int ty, int tx, bool empty, bool has_d1, int ay, int ax) {
+    return empty && !has_d1 && (ty > ay || (ty == ay && tx > ax)) && cheb(ty, tx, ay, ax) >= kMinDist;
+}
+// root_empty as twin_cell takes it -> t, or -1
+RZM_FN int d1_twin_cell(int a, int BW, int S, const uint64_t *root_empty, const uint64_t *d1bits) {
+    for (int t = 0; t < S; ++t)
+        if (d1_twin_ok_yx(t / BW, t % BW, (root_empty[t >> 6] >> (t & 63)) & 1ull, d1_valid_bit(d1bits, t), a / BW, a % BW)) return t;
+    return -1;
+}
+// the sources of a depth-1 leaf root + a, cell (cy, cx).  served: a D1 hit (no pass).  (ty, tx): the twin of a pass that runs, ty < 0:
+// none.  -> kSrcMemo (entry (a, D1), slot *slot), kSrcRun (the pass computes it) or kSrcBase (the parity-1 base's planes), and *fills =
+// kFromTwin where the cell's two computed values are stored to entry (t, D1), slot *slot, before the base's are put back; else kFromBase
+RZM_FN int d1_source_yx(int cy, int cx, int ay, int ax, bool served, int ty, int tx, int *fills, int *slot) {
+    const int sa = slot_of(cy, cx, ay, ax), st = ty >= 0 && !served ? slot_of(cy, cx, ty, tx) : -1;
+    *fills = st >= 0 ? kFromTwin : kFromBase;
+    *slot = st >= 0 ? st : sa;
+    return sa >= 0 ? (served ? kSrcMemo : kSrcRun) : kSrcBase;
+}
+
 }  // namespace rzm

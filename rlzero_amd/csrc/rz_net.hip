@@ -106,6 +106,8 @@ struct rz_net {
     bool delta_memo = true;           // rz_net_delta_memo: k_delta_res<false> serves far-apart two-stone leaves from the memo
     bool memo_half = true;            // ... and runs ONE window where the memo holds the other (rz_net_delta_memo(net, 2): not)
     bool memo_twin = true;            // ... and a foretold cell's window beside it (rz_net_delta_memo(net, 3); 1: one window, no twin)
+    bool memo_d1 = false;             // ... and serves depth-1 leaves from kind D1, filled by the depth-1 passes' twins (rz_net_delta_memo(net, 4))
+    DevBuf<char> d_memo_d1;           // kind D1's store: [base_games][S entries], reserved with d_memo while memo_d1 (its bits: memo_d1_bits)
 };
 
 namespace {
@@ -173,18 +175,31 @@ dl::DeltaArgs delta_args(const rz_net *net, const uint8_t *active, float *feat32
                          mode, (65536 + net->dev.BW - 1) / net->dev.BW, win};
 }
 // the headers of the base cache and, behind them, the valid bits of the feature memo (rz_memo.h): one block, cleared together
-size_t base_hdr_bytes(int n_games) { return (size_t)n_games * (sizeof(dl::BaseHdr) + rzm::kBitmapWords * sizeof(uint64_t)); }
+// (and behind those the valid bits of the memo's kind D1, [games][rzm::kD1BitmapWords])
+size_t base_hdr_bytes(int n_games) { return (size_t)n_games * (sizeof(dl::BaseHdr) + (rzm::kBitmapWords + rzm::kD1BitmapWords) * sizeof(uint64_t)); }
 uint64_t *memo_bits(const rz_net *net) { return reinterpret_cast<uint64_t *>(net->d_base_hdr.p + net->base_games); }
-// on: k_delta_res<false> may serve leaves from the memo and fill it (no memo memory: every leaf runs its passes)
-dl::MemoArgs memo_args(const rz_net *net, bool on) { return dl::MemoArgs{on ? net->d_memo.p : nullptr, memo_bits(net), net->memo_half ? 1 : 0, net->memo_twin ? 1 : 0}; }
+uint64_t *memo_d1_bits(const rz_net *net) { return memo_bits(net) + (size_t)net->base_games * rzm::kBitmapWords; }
+// on: k_delta_res<false> may serve leaves from the memo and fill it (no memo memory: every leaf runs its passes).  Kind D1 goes to the
+// kernel only where it is switched on AND its store is there: the kernel takes a non-NULL d1 for both.
+dl::MemoArgs memo_args(const rz_net *net, bool on) {
+    return dl::MemoArgs{on ? net->d_memo.p : nullptr, memo_bits(net), net->memo_half ? 1 : 0, net->memo_twin ? 1 : 0,
+                        on && net->d_memo.p && net->memo_d1 ? net->d_memo_d1.p : nullptr, memo_d1_bits(net)};
+}
 // The memo's entries for the reserved games (15 x 15: 230 KB a game, 118 MB at 512 games), only while the memo is switched on.  The
-// memo is an optimisation: where the memory is not to be had the search runs without it, the base cache stands.
+// memo is an optimisation: where the memory is not to be had the search runs without it, the base cache stands.  Kind D1's store
+// (115 KB a game, 59 MB at 512 games) likewise, while that kind is switched on: without it the memo stands.
 void memo_reserve(rz_net *net) {
     const size_t bytes = (size_t)net->base_games * (size_t)rzm::game_bytes(net->dev.S);
     if (!net->delta_memo || net->base_games == 0) {
         net->d_memo.release();
     } else if (net->d_memo.bytes != bytes && !net->d_memo.alloc(bytes)) {
         (void)hipGetLastError();   // (the failed hipMalloc's error is not the next launch's)
+    }
+    const size_t d1_bytes = (size_t)net->base_games * (size_t)rzm::d1_game_bytes(net->dev.S);
+    if (!net->delta_memo || !net->memo_d1 || net->base_games == 0) {
+        net->d_memo_d1.release();
+    } else if (net->d_memo_d1.bytes != d1_bytes && !net->d_memo_d1.alloc(d1_bytes)) {
+        (void)hipGetLastError();
     }
 }
 
@@ -792,6 +807,7 @@ int rz_net_delta_reserve(rz_net *net, int32_t n_games) {
     net->d_base_recs.release();
     net->d_base_ones.release();
     net->d_memo.release();
+    net->d_memo_d1.release();
     net->base_games = 0;
     // (the headers, and behind them the memo's valid bits: base_hdr_bytes)
     const size_t hdr_bytes = base_hdr_bytes(n_games), rec_bytes = (size_t)n_games * 2 * dl::kBaseBytes;
@@ -832,6 +848,8 @@ int rz_net_delta_bases(rz_net *net, const uint64_t *d_root_stones, const int32_t
     {   // the feature memo patches the bases that are replaced now: its valid bits go first
         const int n_words = n_games * rzm::kBitmapWords;
         dl::k_memo_clear<<<dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(memo_bits(net), n_words);
+        const int n_d1 = n_games * rzm::kD1BitmapWords;
+        dl::k_memo_clear<<<dim3((unsigned)((n_d1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(memo_d1_bits(net), n_d1);
     }
     dl::k_trunk_delta<false><<<dim3((unsigned)(2 * n_games)), dim3(256), 0, (hipStream_t)stream>>>(
         net->dev, LeafBits{d_root_stones, d_root_to_move, nullptr}, nullptr, 2 * n_games, no_store(), da);
@@ -914,13 +932,14 @@ int rz_net_delta_stats(rz_net *net, uint32_t *h_out8, int32_t reset) {
     return RZ_OK;
 }
 
-int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out4) {
-    if (!net || !h_out4) return rz_fail(RZ_ERR_ARG, "NULL argument");
-    memset(h_out4, 0, 4 * sizeof(uint32_t));
+int rz_net_delta_memo_stats(rz_net *net, uint32_t *h_out8) {
+    if (!net || !h_out8) return rz_fail(RZ_ERR_ARG, "NULL argument");
+    memset(h_out8, 0, 8 * sizeof(uint32_t));
     if (!net->d_delta_stats) return RZ_OK;
-    // (the fourth word, always 0 before the twins: no kernel of modes 0 .. 2 counts into word 11)
-    static_assert(dl::kStats >= 8 + 4, "hits, fills, one-window leaves, twins run: words 8 .. 11 of the counters");
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out4, net->d_delta_stats.p + 8, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    // (the fourth word, always 0 before the twins: no kernel of modes 0 .. 2 counts into word 11; words 4 .. 6, kind D1: none of
+    // modes 0 .. 3 counts into words 12 .. 14; the eighth word is 0)
+    static_assert(dl::kStats >= 8 + 8, "hits, fills, one-window leaves, twins run, D1 hits, D1 twins, D1 fills: words 8 .. 14 of the counters");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h_out8, net->d_delta_stats.p + 8, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return rz_fail(RZ_ERR_HIP, "hipMemcpy failed (delta counters)");
     return RZ_OK;
 }
@@ -930,9 +949,13 @@ int rz_net_delta_memo(rz_net *net, int32_t on) {
     // (2, the diagnostic: the memo without the one-window route.  The entries mean the same either way: nothing is dropped for it.
     // A host-side setting read when launches are enqueued)
     net->memo_half = on != 2;
-    net->memo_twin = on == 3;   // (3: the one-window pass around a also runs a twin's window, rz_memo.h; the entries mean the same)
-    if (net->delta_memo == (on != 0)) return RZ_OK;
+    net->memo_twin = on >= 3;   // (3: the one-window pass around a also runs a twin's window, rz_memo.h; the entries mean the same)
+    // (4: and kind D1, rz_memo.h.  Its store comes and goes with the switch, so a change of it takes the path below: the launches
+    // enqueued after it find the kind on with a store whose bits are clear, or off -- memo_args hands the kernel no kind without a store)
+    const bool d1 = on >= 4;
+    if (net->delta_memo == (on != 0) && net->memo_d1 == d1) return RZ_OK;
     net->delta_memo = on != 0;
+    net->memo_d1 = d1;
     if (net->base_games > 0) {   // (searches in flight may read the entries that go, or the bits of entries that come)
         RZ_TRY(rz_on_device(net->device));
         (void)hipDeviceSynchronize();

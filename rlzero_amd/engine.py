@@ -216,8 +216,12 @@ class HipNet(object):
         # (RZ_DELTA_MEMO=0: the resident search runs every leaf's passes -- the kernel without the feature memo, in the same library --
         # and the memo's memory is not reserved; the switch goes first so that the reserve knows.  RZ_DELTA_MEMO=2, a diagnostic: the
         # memo without the one-window route, for an A / B inside one library; RZ_DELTA_MEMO=1: the one-window route without the twin
-        # windows of rz_memo.h; unset, or 3: with them)
-        check(self.lib.rz_net_delta_memo(self.handle, {'0': 0, '1': 1, '2': 2}.get(os.environ.get('RZ_DELTA_MEMO', '3'), 3)), 'rz_net_delta_memo')
+        # windows of rz_memo.h; 3: with them; 4: and depth-1 leaves served from the memo's kind D1.  Unset: 4 where every cell is an action
+        # (Gomoku), 3 where not (Connect4: a D1 twin's cell is chosen among the cells EMPTY at the root, and under gravity most of
+        # those are no legal move -- most twins are then wasted, each at the price of a window; profiles/TRIED.md, round 18))
+        unset = 4 if self.n_actions == self.rows * self.cols else 3
+        mode = {'0': 0, '1': 1, '2': 2, '3': 3, '4': 4}.get(os.environ.get('RZ_DELTA_MEMO', ''), unset)
+        check(self.lib.rz_net_delta_memo(self.handle, mode), 'rz_net_delta_memo')
         check(self.lib.rz_net_delta_reserve(self.handle, int(n_games)), 'rz_net_delta_reserve')
         self._delta_games = max(self._delta_games, int(n_games))
 
@@ -256,15 +260,19 @@ class HipNet(object):
         served from the feature memo (they count among 'delta', with the tiles their passes would have run), 'memo_fills': entries filled,
         'memo_half': leaves that ran one stone's window and took the other's from the memo (not among 'memo_hits'; they count the tiles of
         the two-window pass; 0 under RZ_DELTA_MEMO=2 and =0), 'memo_twins': one-window passes that also ran and filled a twin's window
-        (rz_memo.h: twin_cell; among 'memo_half'; 0 unless RZ_DELTA_MEMO is 3 or unset)}"""
+        (rz_memo.h: twin_cell; among 'memo_half'; 0 under RZ_DELTA_MEMO=0 .. 2), 'memo_d1_hits': depth-1 leaves served from the memo's kind D1
+        (not among 'memo_hits'; they count among 'delta' with the tiles their pass would have run), 'memo_d1_twins': depth-1 passes that
+        also ran a twin's window (rz_memo.h: d1_twin_cell), 'memo_d1_fills': D1 entries filled (all three 0 unless RZ_DELTA_MEMO is 4 or
+        unset)}"""
         out = (ctypes.c_uint32 * 8)()
-        memo = (ctypes.c_uint32 * 4)()
+        memo = (ctypes.c_uint32 * 8)()
         check(self.lib.rz_net_delta_memo_stats(self.handle, memo), 'rz_net_delta_memo_stats')
         check(self.lib.rz_net_delta_stats(self.handle, out, 1 if reset else 0), 'rz_net_delta_stats')
         ghz = (256.0 * out[6]) / (10.0 * out[7]) if out[7] else None   # (cycles per nanosecond of the last resident launch's workgroup 0)
         return {'delta': int(out[0]), 'no_base': int(out[1]), 'tiles3': int(out[2]), 'cells': int(out[3]), 'tiles2': int(out[4]),
                 'prescans': int(out[5]), 'resident_sclk_ghz': ghz, 'memo_hits': int(memo[0]), 'memo_fills': int(memo[1]),
-                'memo_half': int(memo[2]), 'memo_twins': int(memo[3])}
+                'memo_half': int(memo[2]), 'memo_twins': int(memo[3]), 'memo_d1_hits': int(memo[4]), 'memo_d1_twins': int(memo[5]),
+                'memo_d1_fills': int(memo[6])}
 
     def compact_resident(self):
         """True when the resident search runs on the COMPACT LDS grid (k_trunk_split<.., RES, 9, 15>: 69 KB, TWO games per CU and any
