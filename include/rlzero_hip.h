@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RZ_ABI_VERSION 54
+#define RZ_ABI_VERSION 55
 #define RZ_MAX_BOARD_SIZE 16
 #define RZ_BOARD_WORDS 4 /* 4 x 64 bits >= 16*16 cells */
 #define RZ_MAX_IN_FLIGHT 16 /* rz_config.sims_in_flight */
@@ -957,6 +957,20 @@ int rz_mz_load_root_model(rz_muzero *e, const float *const *h_params, int32_t n_
 int rz_mz_search_obs(rz_muzero *e, const float *d_obs, float *d_hidden, int32_t n_sims, const double *d_noise, double noise_frac,
                      float *d_root_probs, int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf, float *d_trace_reward,
                      float *d_trace_probs, float *d_trace_value, void *stream);
+/* (ABI 55) The Gumbel search from raw observations in ONE launch (k_mz_search<.., GUMBEL = true, CAT, ROOTS = true>): rz_mz_search_obs's
+ * root stage in front of rz_mz_search_gumbel's search, with scalar heads or with a support (rz_mz_set_support), with or without the
+ * value transform.  The arguments are rz_mz_search_obs's without the noise pair (Gumbel roots take no Dirichlet noise) plus
+ * rz_mz_search_gumbel's d_gumbel float32 [n_games][n_actions], d_action_out int32 [n_games] and d_pi_out float32 [n_games][n_actions].
+ * The root's raw value v_hat is the stage's own prediction (h^-1 of the support's expectation with a support): the second prediction
+ * on slot 0 of d_hidden that rz_mz_search_gumbel starts with does not run.  Roots, d_root_probs, slot 0 of d_hidden and row 0 of the
+ * trace ([n_sims + 1] rows) are rz_mz_search_obs's; everything behind them -- tree, d_action_out, d_pi_out, trace rows 1 .. -- is what
+ * rz_mz_init_roots(d_root_probs, NULL) + rz_mz_search_gumbel give on that slot 0, bit for bit.  RZ_ERR_ARG with the reason, nothing
+ * launched: the Gumbel search not on; the handle's support differing from the loaded model's; no model or no root model loaded;
+ * n_sims other than the tree's; paths that do not fit LDS.  rz_mz_search_plan with whole_moves 3 reports this launch: the plan of
+ * rz_mz_search_gumbel for the handle (the stage takes no LDS of its own). */
+int rz_mz_search_obs_gumbel(rz_muzero *e, const float *d_obs, float *d_hidden, int32_t n_sims, const float *d_gumbel, int32_t *d_action_out,
+                            float *d_pi_out, float *d_root_probs, int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf,
+                            float *d_trace_reward, float *d_trace_probs, float *d_trace_value, void *stream);
 /* Whole MOVES of CartPole-v1 environments in one launch (k_mz_search with its MOVES stages): per move the initial
  * inference h(o) -> s0, f(s0) -> root priors (+ Dirichlet(alpha) noise, weight noise_frac; probabilities and noise are each
  * normalised in fp64, so the stored root priors sum to 1 within 1e-12), n_sims simulations, the action
@@ -1084,7 +1098,7 @@ int rz_mz_error_flags(rz_muzero *e, int32_t *flags);
  * value_sum[s] = v[s] + sum over children (N_c * reward_c + discount * value_sum_c) (no v term for the root).
  * rz_mz_search_plan: what a launch of the fused search (whole_moves 0: rz_mz_search) or of whole moves (whole_moves 1:
  * rz_mz_play_env / rz_mz_play_cartpole, for the tree's action count) would be for the current shape (rz_mz_set_search_shape), from the function the launch itself uses: games
- * per workgroup, whether the trees live in LDS (1) or stay in HBM (0), dynamic LDS bytes.  Any output pointer may be NULL. */
+ * per workgroup, whether the trees live in LDS (1) or stay in HBM (0), dynamic LDS bytes.  Any output pointer may be NULL.  whole_moves 2: rz_mz_search_obs; 3 (ABI 55): rz_mz_search_obs_gumbel. */
 typedef struct rz_mz_node {
     int32_t n;           /* visit count */
     int32_t first_child; /* slot of the first child, -1 = not expanded */

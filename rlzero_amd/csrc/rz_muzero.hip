@@ -13,7 +13,8 @@
 //     caller gathers the parents' hidden states, runs dynamics + prediction on the batch, stores the new hidden states
 //     at the leaf slots and hands reward / policy / value back;
 //   * rz_mz_search: all simulations of a move in ONE launch, the model evaluated inside the kernel (k_mz_search); rz_mz_search_obs: the
-//     same from raw observations -- initial inference and roots made in the launch too (its ROOTS instantiations);
+//     same from raw observations -- initial inference and roots made in the launch too (its ROOTS instantiations) --, and
+//     rz_mz_search_obs_gumbel that of rz_mz_search_gumbel, with scalar heads or a support;
 //   * rz_mz_play_env (rz_mz_play_cartpole is its CartPole form): whole MOVES in one launch -- initial inference, root noise, search,
 //     action draw, environment step, episode history on the device (k_mz_search with its MOVES stages, instantiated per environment
 //     trait of rz_mz_env.h: CartPole, Acrobot).
@@ -157,6 +158,22 @@ constexpr MzRootsRow mz_roots_row() {
             k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, VT, false, false, true>};
 }
 constexpr MzRootsRow kMzRootsRows[] = {mz_roots_row<false>(), mz_roots_row<true>()};
+// the GUMBEL ROOTS instantiations (rz_mz_search_obs_gumbel): the Gumbel search from raw observations, trees in LDS and in HBM -- scalar
+// heads with and without the value transform, and the support's heads (support > 0: the value transform by definition)
+typedef void (*MzRootsGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzNoSupport, MzRoots);
+typedef void (*MzRootsCatGumbelFn)(MzDev, MzModel, float *, int, int, MzTrace, MzPlay, MzGumbel, MzSupport, MzRoots);
+struct MzRootsGumbelRow {
+    bool vt;
+    MzRootsGumbelFn tree_lds, tree_hbm;
+};
+template <bool VT>
+constexpr MzRootsGumbelRow mz_roots_gumbel_row() {
+    return {VT, k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, VT, true, false, true>,
+            k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, VT, true, false, true>};
+}
+constexpr MzRootsGumbelRow kMzRootsGumbelRows[] = {mz_roots_gumbel_row<false>(), mz_roots_gumbel_row<true>()};
+constexpr MzRootsCatGumbelFn kMzRootsCatGumbelLds = k_mz_search<true, false, rzmze::EnvCartPole, kMzMaxA, true, true, true, true>;
+constexpr MzRootsCatGumbelFn kMzRootsCatGumbelHbm = k_mz_search<false, false, rzmze::EnvCartPole, kMzMaxA, true, true, true, true>;
 
 // what a launch with categorical heads needs (rz_mz_set_support), and what one without them must not meet
 int mz_support_ready(const rz_muzero *e) {
@@ -184,12 +201,12 @@ struct MzPlan {
 };
 // `gumbel`: a launch of the GUMBEL instantiations (their LDS holds more per node and per launch: mz_search_lds_bytes)
 // (a support net's launch -- never whole moves -- carries the CAT instantiations' extra LDS)
-// `roots`: a launch of the ROOTS instantiations (rz_mz_search_obs: pUCT and scalar heads, whatever the handle is set to); their stage
-// takes no LDS of its own, so the plan is rz_mz_search's for such a handle
+// `roots`: a launch of the ROOTS instantiations; their stage takes no LDS of its own.  Without `gumbel` (rz_mz_search_obs: pUCT and scalar
+// heads, whatever the handle is set to) the plan is rz_mz_search's for such a handle; with it (rz_mz_search_obs_gumbel) the plan is
+// rz_mz_search_gumbel's, the support following the handle
 MzPlan mz_search_plan(const rz_muzero *e, bool whole_moves, bool gumbel = false, bool roots = false) {
     MzPlan p;
-    const bool cat = e->support > 0 && !whole_moves && !roots;
-    if (roots) gumbel = false;
+    const bool cat = e->support > 0 && !whole_moves && (!roots || gumbel);
     const int w1c = mz_w1_cols(whole_moves, e->cfg.n_actions <= kMzMaxA ? e->cfg.n_actions : kMzMaxA);
     // games per workgroup: a search is a latency chain per game and two workgroups share a CU without slowing each
     // other, so the 16 columns of a tile are filled first (profiles/r02/muzero_search_shape.txt)
@@ -210,6 +227,22 @@ int mz_launch_roots(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace
         if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
     fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, MzNoGumbel{}, MzNoSupport{}, R);
     return rz_launched("k_mz_search (observations)");
+}
+
+int mz_launch_roots_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const MzTrace &T, const MzGumbel &Z, const MzRoots &R, void *stream) {
+    const MzPlan plan = mz_search_plan(e, false, true, true);
+    if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    const dim3 grid((unsigned)((e->cfg.n_games + plan.gpw - 1) / plan.gpw)), block(64 * kMzWaves);
+    if (e->support > 0) {
+        (plan.tree_lds ? kMzRootsCatGumbelLds : kMzRootsCatGumbelHbm)<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims,
+                                                                                                                      plan.gpw, T, MzPlay{}, Z, e->cat, R);
+        return rz_launched("k_mz_search (observations, gumbel, support)");
+    }
+    MzRootsGumbelFn fn = nullptr;
+    for (const MzRootsGumbelRow &row : kMzRootsGumbelRows)
+        if (row.vt == e->value_transform) fn = plan.tree_lds ? row.tree_lds : row.tree_hbm;
+    fn<<<grid, block, plan.lds, (hipStream_t)stream>>>(e->dev, e->model, d_hidden, n_sims, plan.gpw, T, MzPlay{}, Z, MzNoSupport{}, R);
+    return rz_launched("k_mz_search (observations, gumbel)");
 }
 
 // play != nullptr: whole moves of the environment `kind` (checked by rz_mz_play_env)
@@ -411,6 +444,13 @@ static int mz_load_model(rz_muzero *e, const float *const *h_params, int32_t n_p
             for (MzRootsFn fn : {row.tree_lds, row.tree_hbm})
                 if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
                     return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        for (const MzRootsGumbelRow &row : kMzRootsGumbelRows)
+            for (MzRootsGumbelFn fn : {row.tree_lds, row.tree_hbm})
+                if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+                    return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        for (const void *fn : {(const void *)kMzRootsCatGumbelLds, (const void *)kMzRootsCatGumbelHbm})
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+                return rz_fail(RZ_ERR_HIP, "hipFuncSetAttribute(dynamic LDS) failed");
         e->attributes_set = true;
     }
     if (hipMemcpy(d_model, packed.host.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -562,6 +602,32 @@ int rz_mz_search_gumbel(rz_muzero *e, float *d_hidden, int32_t n_sims, const flo
     return mz_launch_gumbel(e, d_hidden, n_sims, T, Z, stream);
 }
 
+int rz_mz_search_obs_gumbel(rz_muzero *e, const float *d_obs, float *d_hidden, int32_t n_sims, const float *d_gumbel, int32_t *d_action_out,
+                            float *d_pi_out, float *d_root_probs, int32_t *d_trace_parent, int32_t *d_trace_action, int32_t *d_trace_leaf,
+                            float *d_trace_reward, float *d_trace_probs, float *d_trace_value, void *stream) {
+    RZ_ENTER(mz_ready, e);
+    if (e->gumbel_considered < 1)
+        return rz_fail(RZ_ERR_ARG, "rz_mz_set_gumbel has not switched the Gumbel search on (the pUCT search from observations is rz_mz_search_obs)");
+    if (!e->model_loaded) return rz_fail(RZ_ERR_ARG, "rz_mz_load_model has not been called");
+    RZ_TRY(mz_support_ready(e));
+    if (e->root_obs_dim < 1) return rz_fail(RZ_ERR_ARG, "rz_mz_load_root_model has not been called");
+    if (d_obs == nullptr || d_hidden == nullptr || d_gumbel == nullptr || d_action_out == nullptr || d_pi_out == nullptr)
+        return rz_fail(RZ_ERR_ARG, "d_obs, d_hidden, d_gumbel, d_action_out or d_pi_out is NULL");
+    if (n_sims != e->cfg.n_sims)
+        return rz_fail(RZ_ERR_ARG, "the considered-visits table is the schedule of n_sims = %d simulations, not of %d", e->cfg.n_sims, n_sims);
+    const bool any = d_trace_parent || d_trace_action || d_trace_leaf || d_trace_reward || d_trace_probs || d_trace_value;
+    const bool all = d_trace_parent && d_trace_action && d_trace_leaf && d_trace_reward && d_trace_probs && d_trace_value;
+    if (any && !all) return rz_fail(RZ_ERR_ARG, "the trace arrays come all together or not at all");
+    const MzPlan plan = mz_search_plan(e, false, true, true);
+    if (plan.lds > 160 * 1024) return rz_fail(RZ_ERR_ARG, "n_sims too large for the fused search (paths do not fit in LDS)");
+    if (e->d_gumbel_logit == nullptr && !plan.tree_lds)   // (only HBM trees keep log(prior) there)
+        RZ_TRY(e->pool.alloc(&e->d_gumbel_logit, (long long)e->cfg.n_games * e->dev.cap));
+    const MzTrace T = {d_trace_parent, d_trace_action, d_trace_leaf, d_trace_reward, d_trace_probs, d_trace_value};
+    const MzGumbel Z = {e->d_gumbel_cv, d_gumbel, e->d_gumbel_logit, d_action_out, d_pi_out, e->gumbel_c_visit, e->gumbel_c_scale};
+    const MzRoots R = {d_obs, e->root_obs_dim, e->root_w[0], e->root_w[1], e->root_w[2], e->root_w[3], nullptr, 0.0, d_root_probs};
+    return mz_launch_roots_gumbel(e, d_hidden, n_sims, T, Z, R, stream);
+}
+
 // whole moves of the environment `kind`: the checks and the launch behind rz_mz_play_env and rz_mz_play_cartpole
 static int mz_play_launch(rz_muzero *e, int32_t kind, float *d_hidden, int32_t n_sims, int32_t n_moves, const rz_mz_whole_play *play, void *stream) {
     RZ_ENTER(mz_ready, e);
@@ -679,8 +745,9 @@ int rz_mz_debug_profile(long long *h_out16) {
 
 int rz_mz_search_plan(rz_muzero *e, int32_t whole_moves, int32_t *games_per_workgroup, int32_t *tree_in_lds, int32_t *lds_bytes) {
     if (e == nullptr) return rz_fail(RZ_ERR_ARG, "muzero handle is NULL");
-    const MzPlan plan = whole_moves == 2 ? mz_search_plan(e, false, false, true)
-                                         : mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);   // (a support: read from the handle)
+    const MzPlan plan = whole_moves == 3   ? mz_search_plan(e, false, true, true)
+                        : whole_moves == 2 ? mz_search_plan(e, false, false, true)
+                                           : mz_search_plan(e, whole_moves != 0, whole_moves == 0 && e->gumbel_considered > 0);   // (a support: read from the handle)
     if (games_per_workgroup) *games_per_workgroup = plan.gpw;
     if (tree_in_lds) *tree_in_lds = plan.tree_lds ? 1 : 0;
     if (lds_bytes) *lds_bytes = plan.lds;

@@ -34,7 +34,9 @@
 //     save / reload of the f16 fragments sits once per move (profiles/mz_whole_env/kernel_resources.txt).
 //   * ROOTS (rz_mz_search_obs): the search alone from raw observations -- representation, root prediction, softmax and the roots
 //     (k_mz_init's rule, rz_mz_roots.h) as a stage in front of simulation 0, on an observation tile and a staged first layer of its own
-//     in LDS (MzRoots, below): a Reanalyse chunk is one launch between `positions` and the read-out.
+//     in LDS (MzRoots, below): a Reanalyse chunk is one launch between `positions` and the read-out.  With GUMBEL
+//     (rz_mz_search_obs_gumbel; scalar heads or CAT) the stage also writes log(prior) and the root's v_hat, and the Gumbel preamble's own
+//     prediction of the roots does not run: a Gumbel device move of self-play is this launch and k_mz_env_move.
 //   * TREE_LDS trees use their own record: MzHot (N, first_child, value_sum, prior and q = reward + discount * value(),
 //     refreshed by the backup that changes it, so the walk does not divide value_sum / N again at every visit) plus one
 //     float of reward per node; sqrt(N) of the walk comes from a table filled with the same IEEE sqrt.  Same operations on
@@ -238,7 +240,7 @@ struct MzRoots {
     const float *obs;                        // [n_games][obs_dim]
     int obs_dim;
     const float *rep1_w, *rep1_b, *rep2_w, *rep2_b;   // rzmp::pack_root_model
-    const double *noise;                     // [n_games][A] or null
+    const double *noise;                     // [n_games][A] or null (GUMBEL: not read -- Gumbel roots take no noise)
     double noise_frac;
     float *root_probs;                       // [n_games][A] or null: the float32 softmax rows the roots were made from
 };
@@ -310,6 +312,33 @@ struct MzgLds {
             }
         }
     }
+    // (ROOTS) the root from the row the launch has just formed: rz_mz_roots.h's records as the preamble would have read them from HBM, with
+    // log(prior) and v_hat beside them; every lane of the game writes slot 0, lane q its own two children (Gumbel roots take no noise)
+    template <int MAXA>
+    __device__ __forceinline__ void make_root(int A, int q, const float (&probs)[MAXA], float value) const {
+        const MzNode r = mz_root_record();
+        hot[0] = MzHot{r.N, r.first_child, r.value_sum, r.prior, 0.0};
+        rew[0] = r.reward;
+        vh[0] = value;
+        lgt[0] = log(r.prior);
+        float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a) {
+            p0 = a == 2 * q ? probs[a] : p0;
+            p1 = a == 2 * q + 1 ? probs[a] : p1;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int a = 2 * q + i;
+            if (a < A) {
+                const MzNode c = mz_root_child(mz_root_prior(i == 0 ? p0 : p1, nullptr, a, 0.0));
+                hot[1 + a] = MzHot{c.N, c.first_child, c.value_sum, c.prior, 0.0};
+                rew[1 + a] = c.reward;
+                vh[1 + a] = __int_as_float(c.pad);
+                lgt[1 + a] = log(c.prior);
+            }
+        }
+    }
     // a level of backpropagate: -> the node's new value(), r = its reward
     __device__ __forceinline__ double visit(int s, double v, double &r) const {
         const double sum = hot[s].value_sum + v;
@@ -344,6 +373,22 @@ struct MzgHbm {
             if (a < A) {
                 nodes[top + a] = MzNode{0, -1, 0.0, (double)probs[a], 0.0f, 0};
                 lgt[top + a] = log((double)probs[a]);
+            }
+        }
+    }
+    // (ROOTS; as expand: every lane of the game writes the root and every child)
+    template <int MAXA>
+    __device__ __forceinline__ void make_root(int A, int, const float (&probs)[MAXA], float value) const {
+        MzNode r = mz_root_record();
+        lgt[0] = log(r.prior);
+        r.pad = __float_as_int(value);
+        nodes[0] = r;
+#pragma unroll
+        for (int a = 0; a < MAXA; ++a) {
+            if (a < A) {
+                const MzNode c = mz_root_child(mz_root_prior(probs[a], nullptr, a, 0.0));
+                nodes[1 + a] = c;
+                lgt[1 + a] = log(c.prior);
             }
         }
     }
@@ -525,8 +570,10 @@ __device__ __noinline__ void mz_env_observe_far(const typename Env::State &c, fl
 // pi' of every game in Z.action_out / Z.pi_out.  The matrix-pipe stages are the same code.  Z: MzGumbel, an empty record otherwise.
 // CAT (MOVES = false, VT = true only): the reward and value heads are softmaxes over a support (above; rz_mz_set_support), read as
 // h^-1 of their expectation.  C: MzSupport, an empty record otherwise.
-// ROOTS (MOVES = GUMBEL = CAT = false only): the launch starts from raw observations (above; rz_mz_search_obs) -- the trees it finds are
-// not read, the roots are made in the launch, and the trace, when given, has a row 0 for the root in front of the simulations'.
+// ROOTS (MOVES = false; CAT only with GUMBEL): the launch starts from raw observations (above; rz_mz_search_obs, rz_mz_search_obs_gumbel) --
+// the trees it finds are not read, the roots are made in the launch, and the trace, when given, has a row 0 for the root in front of the
+// simulations'.  With GUMBEL the stage also leaves what the GUMBEL preamble forms from records it finds -- log(prior) and v_hat of the
+// root's slots -- and that preamble's second prediction on hidden[:, 0] does not run: three barriers and an L2 round trip less.
 // R: MzRoots, an empty record otherwise.
 template <bool TREE_LDS, bool MOVES, typename Env = rzmze::EnvCartPole, int MAXA = (MOVES ? Env::kActions : kMzMaxA), bool VT = false,
           bool GUMBEL = false, bool CAT = false, bool ROOTS = false>
@@ -536,7 +583,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                                                                  typename std::conditional<ROOTS, MzRoots, MzNoRoots>::type R) {
     static_assert(!(GUMBEL && MOVES), "whole moves keep the pUCT rule");
     static_assert(!CAT || (VT && !MOVES), "the support lies in h's space; whole moves keep scalar heads");
-    static_assert(!ROOTS || (!MOVES && !GUMBEL && !CAT), "the search from observations serves the pUCT rule with scalar heads");
+    static_assert(!ROOTS || (!MOVES && (GUMBEL || !CAT)), "the search from observations: pUCT with scalar heads, Gumbel with either kind");
     extern __shared__ __attribute__((aligned(16))) unsigned char mz_lds[];
     constexpr int AFIX = MOVES ? Env::kActions : 0;   // whole MOVES: the environment's action count (rz_mz_play_env checks the tree's)
     constexpr int W1C = mz_w1_cols(MOVES, Env::kActions);
@@ -777,7 +824,7 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         else return MzgHbm{nodes, Z.logit + (long long)g * E.cap, E.discount};
     }();
     (void)gtree;
-    if constexpr (GUMBEL) {
+    if constexpr (GUMBEL && !ROOTS) {   // (ROOTS: the stage that makes the roots writes both beside the records)
         for (int ee = 0; ee < gpw && g0 + ee < E.n_games; ++ee) {
             const MzNode *src = E.nodes + (long long)(g0 + ee) * E.cap;
             const int used = E.top[g0 + ee] < E.cap ? E.top[g0 + ee] : E.cap;
@@ -1061,10 +1108,15 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
             __syncthreads();
             predict_partials();
             __syncthreads();
+            if constexpr (CAT) {   // (as S4b: the value head on relu(pre1) of the root tile; WH and HBC stand since the preamble's barrier)
+                head_logits(HP, 1);
+                __syncthreads();
+            }
             if (w == 0) {
                 float value, probs[MAXA];
                 finish_prediction(value, probs);
-                if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);   // (as any other node's)
+                if constexpr (CAT) value = cat_scalar(1);
+                else if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);   // (as any other node's)
                 if (mine) {
                     if (lead) {
 #pragma unroll
@@ -1091,11 +1143,18 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                             nodes[slot] = nd;
                         }
                     };
-                    const double *noise_row = R.noise != nullptr ? R.noise + (long long)g * A : nullptr;
-                    put(0, mz_root_record());
+                    if constexpr (GUMBEL) {
+                        // the (n, q) layout: the four lanes 16 q + n of game n hold the same row and value (finish_prediction and cat_scalar
+                        // leave the same bits in each) and all take the start below, so they step down together from simulation 0; the root's
+                        // v_hat is this stage's own value -- the preamble's second prediction on hidden[:, 0] does not run
+                        gtree.template make_root<MAXA>(A, q, probs, value);
+                    } else {
+                        const double *noise_row = R.noise != nullptr ? R.noise + (long long)g * A : nullptr;
+                        put(0, mz_root_record());
 #pragma unroll
-                    for (int a = 0; a < MAXA; ++a)
-                        if (a < A) put(1 + a, mz_root_child(mz_root_prior(probs[a], noise_row, a, R.noise_frac)));
+                        for (int a = 0; a < MAXA; ++a)
+                            if (a < A) put(1 + a, mz_root_child(mz_root_prior(probs[a], noise_row, a, R.noise_frac)));
+                    }
                     const MzRootStart start = mz_root_start(A);
                     top = start.top;
                     depth = start.depth;
@@ -1107,8 +1166,9 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
         // (GUMBEL) the quad of a game is live: the gathers below run in the quad layout whichever lanes walk
         const bool live_quad = GUMBEL ? ge < gpw && g0 + ge < E.n_games : mine;
         float gum0 = 0.0f, gum1 = 0.0f;   // (GUMBEL) the Gumbel draws of the lane's two actions
-        if constexpr (GUMBEL) {
+        if constexpr (GUMBEL && !ROOTS) {
             // ---- the roots' raw values: the prediction on the states the search starts from (v_mix of the root needs v_hat)
+            // (ROOTS: the stage above has predicted on these very states, still in XS, and set the root's v_hat from wave 0's registers)
             if (w == 0) {
                 const float4 *src = reinterpret_cast<const float4 *>(hidden + (long long)(g0 + (live_quad ? ge : 0)) * E.cap * kMzH);
 #pragma unroll
@@ -1134,6 +1194,10 @@ __global__ __launch_bounds__(64 * kMzWaves, 2) void k_mz_search(MzDev E, MzModel
                 if constexpr (CAT) value = cat_scalar(1);
                 else if constexpr (VT) value = (float)rzmzv::value_h_inv((double)value);
                 if (mine) gtree.set_v_hat(0, value);
+            }
+        }
+        if constexpr (GUMBEL) {
+            if (w == 0) {
                 gum0 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q];
                 gum1 = GB[(te < gpw ? te : 0) * rzmzg::kMaxA + 2 * q + 1];
             }

@@ -204,7 +204,7 @@ class MuZeroSelfPlay(object):
     def __init__(self, net, env, n_sims=50, discount=0.997, temperature=1.0, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, seed=0, pb_c_base=19652.0, pb_c_init=1.25, use_graph=True, fused=None,
                  fused_moves=None, moves_per_launch=16, arena_rows=None, device_moves=None, search='puct', gumbel_considered=4,
-                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, gumbel_greedy=False):
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, gumbel_greedy=False, fused_roots=False):
         """``fused``: run the whole search of a move in ONE kernel launch (csrc/rz_muzero_search.h k_mz_search: the model is
         evaluated inside the kernel on the matrix pipe, 16 games per workgroup, trees in LDS); None = whenever the model
         fits it (hidden size 64, <= 8 actions).  Otherwise one hipGraph of ~15 launches per simulation (tree kernels +
@@ -234,7 +234,14 @@ class MuZeroSelfPlay(object):
         is drawn with torch on the device from this object's generator, one [n, A] draw per move, with no host synchronisation
         (``gumbel_greedy``: g = 0, the evaluation's move).  The move is the search's own, so ``temperature`` is IGNORED; a record's A
         visits words hold pi' (both buffers form visits / sum of them: the same distribution within a float32 rounding) and the root
-        value stays value_sum / N.  It serves the host loop (``play_move``) and device moves."""
+        value stays value_sum / N.  It serves the host loop (``play_move``) and device moves.
+        ``fused_roots`` (opt-in, off by default; ``search='gumbel'`` only): the Gumbel search starts from the raw observations in its own
+        launch (``MuZeroTree.search_gumbel_from_obs``: k_mz_search's GUMBEL ROOTS instantiations, scalar heads or a support) -- a device
+        move is ``load_root_model`` (once per weight refresh, beside ``load_model``), that launch and ``env_move``, with no torch
+        ``initial_inference`` and no ``init_roots``; ``search`` takes the same launch.  The same moves as with it off up to the last bits
+        of the root state (the launch's summation order is not rocBLAS').  True where the launch cannot run raises a ``ValueError``
+        that names the reason: the Gumbel search off, a hidden size other than 64, more than 16 observation features, more than 8
+        actions."""
         import torch
         from .tree import MuZeroTree
         self.torch = torch
@@ -304,6 +311,20 @@ class MuZeroSelfPlay(object):
                 raise ValueError('search=\'gumbel\' cannot run: ' + why)
             fused_moves = False
             self.tree.set_gumbel(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
+        self.fused_roots = bool(fused_roots)
+        if self.fused_roots:
+            why = None
+            if not self.gumbel:
+                why = 'search=\'gumbel\' is not set: the pUCT moves keep the torch initial inference'
+            elif net.hidden != 64:
+                why = 'the search from observations is built for hidden size 64 (the net has %d)' % net.hidden
+            elif net.obs_dim > MuZeroTree.MAX_ROOT_OBS:
+                why = 'the search from observations takes at most %d observation features (the net has %d)' % (MuZeroTree.MAX_ROOT_OBS, net.obs_dim)
+            elif self.n_actions > 8:
+                why = 'the search from observations handles at most 8 actions (the environment has %d)' % self.n_actions
+            if why is not None:
+                self.tree.close()
+                raise ValueError('fused_roots cannot run: ' + why)
         self._model_seen = None
         from .cartpole import CartPoleBatch
         from .. import _hip
@@ -365,6 +386,9 @@ class MuZeroSelfPlay(object):
             self.sim_step_label = ('k_mz_search with its MOVES stages (whole moves in one launch: initial inference, root noise, '
                                    '%d simulations -- select, recurrent inference on the matrix pipe, expand + backup -- action draw, '
                                    '%s step)' % (self.n_sims, {'cartpole': 'CartPole', 'acrobot': 'Acrobot'}.get(env.kind, env.kind)))
+        elif self.device_moves and self.fused_roots:
+            self.sim_step_label = ('device moves from observations: per move k_mz_search (representation, roots and %d Gumbel simulations in one '
+                                   'launch) and k_mz_env_move (environment step, record, hand-over)' % self.n_sims)
         elif self.device_moves:
             self.sim_step_label = ('device moves: per move the torch initial inference, k_mz_root_noise, k_mz_init, k_mz_search (%d simulations in '
                                    'one launch) and k_mz_env_move (action draw, environment step, record, hand-over)' % self.n_sims)
@@ -393,6 +417,8 @@ class MuZeroSelfPlay(object):
             self.tree.load_model(self.net)
             if self.fused_moves:
                 self.tree.load_representation(self.net)
+            if self.fused_roots:
+                self.tree.load_root_model(self.net)
             self._model_seen = seen
 
     def _sim_step(self):
@@ -440,6 +466,16 @@ class MuZeroSelfPlay(object):
         t = self.torch
         tree, net = self.tree, self.net
         with t.no_grad():
+            if self.fused_roots:   # (Gumbel: checked at construction) representation, root prediction and roots inside the search launch
+                if record is not None:
+                    raise ValueError('search: record is the pUCT routes\' (MuZeroTree.search_gumbel_from_obs(trace=True) traces this search)')
+                self._refresh_model()
+                obs = obs.to(t.float32).contiguous()
+                actions, pi = tree.search_gumbel_from_obs(obs, self.hidden, self.n_sims, self._gumbel_draws())
+                self._gumbel_actions = actions.long().clone()
+                n, vsum, _, _ = tree.root_stats()
+                self.sims_done += self.n_sims * self.n_envs
+                return pi.clone(), vsum / n.clamp_min(1).to(t.float64)
             s0, logits, _ = net.initial_inference(obs)
             probs = t.softmax(logits, dim=1).contiguous()
             self.hidden[:, 0] = s0
@@ -674,6 +710,11 @@ class MuZeroSelfPlay(object):
         obs = self._dev_obs
         obs.copy_(env.observe())   # (the states may have been set from outside since the last chunk)
         for k in range(n_moves):
+            if self.fused_roots:   # the move is two launches: the search from `obs`, and the move behind it, which rewrites `obs`
+                tree.search_gumbel_from_obs(obs, self.hidden, self.n_sims, self._gumbel_draws())
+                tree.env_move(env, self.noise_seed, self.temperature, (self._ring, self._ep_start_dev), self._t + k, arena, counters,
+                              entries, obs, gumbel=True)
+                continue
             s0, logits, _ = net.initial_inference(obs)
             probs = t.softmax(logits, dim=1).contiguous()
             self.hidden[:, 0] = s0

@@ -282,6 +282,33 @@ class MuZeroTree(object):
                                            *args, self.stream()), 'rz_mz_search_gumbel')
         return (self.gumbel_action, self.gumbel_pi, out) if trace else (self.gumbel_action, self.gumbel_pi)
 
+    def search_gumbel_from_obs(self, obs, hidden, n_sims, gumbel, root_probs=None, trace=False):
+        """``search_gumbel`` from raw observations in ONE launch (rz_mz_search_obs_gumbel; k_mz_search's GUMBEL ROOTS instantiations), in
+        place of ``initial_inference`` + ``init_roots(probs, None)`` + ``search_gumbel``: ``search_from_obs``'s root stage (no noise:
+        Gumbel roots take none), whose own prediction is the root's raw value, then the Gumbel search -- the tree, the move and pi' are
+        those of the three-step route on the same root state, bit for bit.  Scalar heads or a support (``set_support``), with or without
+        the value transform; ``set_gumbel``, ``load_model`` and ``load_root_model`` first; ``n_sims`` = the tree's.  ``obs`` float32
+        [G, obs_dim], ``gumbel`` float32 [G, A], ``root_probs`` float32 [G, A] or None (receives the softmax rows), all on the device.
+        -> (actions, pi) as ``search_gumbel``, or (actions, pi, trace) with ``search_from_obs``'s trace ([n_sims + 1, G]: row 0 the root's)."""
+        t, G, A = self.torch, self.n_games, self.n_actions
+        D = getattr(self, 'root_obs_dim', None)
+        if D is None:
+            raise _hip.HipError('search_gumbel_from_obs: load_root_model first')
+        if getattr(self, 'gumbel_action', None) is None:
+            raise _hip.HipError('search_gumbel_from_obs: set_gumbel first')
+        for name, x, shape in (('obs', obs, (G, D)), ('gumbel', gumbel, (G, A)), ('root_probs', root_probs, (G, A))):
+            if x is not None and (x.dtype != t.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device.type != 'cuda'):
+                raise ValueError('search_gumbel_from_obs: %s must be a contiguous float32 %s tensor on the device' % (name, list(shape)))
+        if obs is None or gumbel is None:
+            raise ValueError('search_gumbel_from_obs: obs and gumbel are required')
+        if hidden.dtype != t.float32 or hidden.numel() < G * self.slots_per_game * 64 or not hidden.is_contiguous():
+            raise ValueError('search_gumbel_from_obs: hidden must be a contiguous float32 [n_games, slots_per_game, 64] tensor')
+        out, args = self._trace(int(n_sims) + 1, trace)
+        check(self.lib.rz_mz_search_obs_gumbel(self.handle, _ptr(obs), _ptr(hidden), int(n_sims), _ptr(gumbel), _ptr(self.gumbel_action),
+                                               _ptr(self.gumbel_pi), _ptr(root_probs) if root_probs is not None else None, *args,
+                                               self.stream()), 'rz_mz_search_obs_gumbel')
+        return (self.gumbel_action, self.gumbel_pi, out) if trace else (self.gumbel_action, self.gumbel_pi)
+
     def stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -352,7 +379,8 @@ class MuZeroTree(object):
         (``set_search_shape``), from the host function the launch itself uses -> dict games_per_workgroup, tree_in_lds (bool),
         lds_bytes.  ``whole_moves='observations'``: the launch of ``search_from_obs`` (the plan of ``search_fused`` with pUCT and scalar heads)."""
         gpw, in_lds, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        which = 2 if isinstance(whole_moves, str) and whole_moves == 'observations' else 1 if whole_moves else 0
+        named = {'observations': 2, 'observations_gumbel': 3}   # (the latter: ``search_gumbel_from_obs``, the plan of ``search_gumbel``)
+        which = named[whole_moves] if isinstance(whole_moves, str) and whole_moves in named else 1 if whole_moves else 0
         check(self.lib.rz_mz_search_plan(self.handle, which, ctypes.byref(gpw), ctypes.byref(in_lds),
                                          ctypes.byref(lds)), 'rz_mz_search_plan')
         return {'games_per_workgroup': gpw.value, 'tree_in_lds': bool(in_lds.value), 'lds_bytes': lds.value}

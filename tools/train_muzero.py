@@ -29,6 +29,7 @@ ROUTE_NEEDS_REANALYSE = '--reanalyse-route needs --reanalyse: it chooses how the
 NEEDS_DEVICE_REPLAY = '--reanalyse needs --device-replay: the steps are searched again and refreshed where they are stored, on the GPU'
 ENVIRONMENTS = ('cartpole', 'acrobot')
 EVAL_SEED = 20191119   # the evaluation environments' seed: every evaluation of every run starts from the same states
+ROOTS_NEED_GUMBEL = '--fused-roots needs --search gumbel: the pUCT moves keep the PyTorch initial inference in front of their search'
 SUPPORT_NEEDS_VALUE_TRANSFORM = '--support needs --value-transform: the bins of the categorical heads lie in the transformed space'
 PRIORITIES_NEED_DEVICE_REPLAY = ('--prioritized-replay needs --device-replay: the priorities are kept beside the stored steps, '
                                  'on the GPU')
@@ -50,7 +51,7 @@ class MuZeroPipeline(object):
                  moves_per_iteration=20, updates_per_iteration=40, device='cuda:0', seed=0, device_replay=False, reanalyse=0,
                  reanalyse_batch=2048, prioritized_replay=False, priority_beta=1.0, fused_learner=False, env='cartpole',
                  max_episode_steps=None, whole_moves=None, value_transform=False, eval_envs=None, search='puct', gumbel_considered=4,
-                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None, reanalyse_route='torch'):
+                 gumbel_c_visit=50.0, gumbel_c_scale=1.0, support=None, reanalyse_route='torch', fused_roots=False):
         """``support`` (needs ``value_transform``): the half-width S of the categorical support of the reward and value heads
         (``MuZeroNet(support=S)``: 2 S + 1 bins, cross-entropy against two-hot targets in either learner, the expectation read
         inside the search kernel).  Refused with a ValueError together with ``whole_moves``.  None: scalar heads.
@@ -77,7 +78,11 @@ class MuZeroPipeline(object):
         kernel) and the buffer -- either one -- hands out h of the value and reward targets; Reanalyse reads the flag from the net.
         Off (the default), nothing changes.  ``eval_envs``: environments of ``evaluate`` (None: as many as train).
         ``search``: 'gumbel' plays with Gumbel MuZero's rule (MuZeroSelfPlay(search='gumbel', gumbel_considered, gumbel_c_visit,
-        gumbel_c_scale): device moves, the policy targets are pi'); the evaluation player then plays greedily, g = 0.  'puct': as before."""
+        gumbel_c_scale): device moves, the policy targets are pi'); the evaluation player then plays greedily, g = 0.  'puct': as before.
+        ``fused_roots`` (needs ``search='gumbel'``): the Gumbel search of a move starts from the raw observations in its own launch
+        (MuZeroSelfPlay(fused_roots=True)): no torch initial inference in front of it, in self-play and in the evaluation."""
+        if fused_roots and search != 'gumbel':
+            raise ValueError(ROOTS_NEED_GUMBEL)
         if env not in ENVIRONMENTS:
             raise ValueError('unknown environment %r (known: %s)' % (env, ', '.join(ENVIRONMENTS)))
         if max_episode_steps is not None and env == 'cartpole':
@@ -114,6 +119,8 @@ class MuZeroPipeline(object):
         route = {} if whole_moves is None else dict(fused_moves=bool(whole_moves))
         if search != 'puct':
             route.update(search=search, gumbel_considered=gumbel_considered, gumbel_c_visit=gumbel_c_visit, gumbel_c_scale=gumbel_c_scale)
+        if fused_roots:
+            route.update(fused_roots=True)
         self.selfplay = MuZeroSelfPlay(self.agent.net, self.env, n_sims=n_sims, discount=discount, seed=seed, **route)
         self._env_class, self._route, self._n_sims, self._discount, self._device = env_class, route, n_sims, discount, device
         self._max_episode_steps = max_episode_steps
@@ -322,6 +329,9 @@ def build_parser():
     ap.add_argument('--gumbel-considered', type=int, default=4, metavar='M', help='actions the Gumbel root considers (clamped to the action count)')
     ap.add_argument('--gumbel-c-visit', type=float, default=50.0)
     ap.add_argument('--gumbel-c-scale', type=float, default=1.0)
+    ap.add_argument('--fused-roots', action='store_true',
+                    help='with --search gumbel: a move\'s search starts from the raw observations in its own launch (representation, root '
+                         'prediction and roots inside the search kernel) instead of the PyTorch initial inference')
     ap.add_argument('--eval-envs', type=int, default=None, metavar='M', help='environments of an evaluation (default: --envs)')
     return ap
 
@@ -337,13 +347,15 @@ def main(argv=None):
         ap.error(PRIORITIES_NEED_DEVICE_REPLAY)
     if args.support is not None and not args.value_transform:
         ap.error(SUPPORT_NEEDS_VALUE_TRANSFORM)
+    if args.fused_roots and args.search != 'gumbel':
+        ap.error(ROOTS_NEED_GUMBEL)
     pipe = MuZeroPipeline(n_envs=args.envs, n_sims=args.sims, device=args.device, batch_size=args.batch_size,
                           updates_per_iteration=args.updates_per_iteration, device_replay=args.device_replay, reanalyse=args.reanalyse,
                           prioritized_replay=args.prioritized_replay, priority_beta=args.priority_beta, fused_learner=args.fused_learner,
                           env=args.env, max_episode_steps=args.max_episode_steps, whole_moves=True if args.whole_moves else None,
                           value_transform=args.value_transform, eval_envs=args.eval_envs, search=args.search,
                           gumbel_considered=args.gumbel_considered, gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
-                          support=args.support, reanalyse_route=args.reanalyse_route)
+                          support=args.support, reanalyse_route=args.reanalyse_route, fused_roots=args.fused_roots)
     pipe.run(args.iterations, eval_every=args.eval_every)
     if args.save:
         pipe.agent.save_model(args.save)
